@@ -2,25 +2,28 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json: attention TFLOP/s + ms/fwd at
 B=4 S=4096 H=16 D=128, 1/2/4/8 GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is ONE forward of the MI355X kernel (through the C ABI) over one batch of synthetic
 Q/K/V already resident in HBM: BASELINE config C3 (B=4, S=4096, H=16, D=128, bf16, causal) per
 GPU.  With N GPUs every rank owns its own B=4 shard of a global batch B=4N (batch x head sharding,
-SURVEY.md section 8(e)); the path has no data-path collective, so scaling is "weak".  The north
-star's single gather of the outputs runs ONCE after the timed region and is reported separately
-(``gather``: RCCL's all_gather_into_tensor and the direct W-1-link exchange), together with a
-secondary loop that overlaps one gather per forward on a side stream (``end_to_end``).
+SURVEY.md section 8(e)); the path has no data-path collective, so scaling is "weak".
 
-What is timed, so that a short driver run (``--steps 20 --warmup 5``) still reports steady state:
+A plain run does only what the headline needs, so that a short run (``--steps 20 --warmup 5``) still reports steady state:
   1. ``prewarm``: a fixed, disclosed clock-settle phase (>= 300 untimed launches and >= 0.25 s; a freshly started process
      runs its first ~60 launches 10-25 % slow while the clocks ramp), then the ``--warmup`` launches;
-  2. ``--reps`` (default 7) repetitions of EXACTLY ``--steps`` launches, each bracketed by barrier + synchronize on both
-     sides, max over ranks per repetition; ``value`` is the MEDIAN repetition, all of them are listed (``reps_ms_per_step``);
-  3. in the same run: the tolerance-meeting variant (fp32 store + split P, ``parity_variant``) and the other BASELINE
-     shapes (``other_workloads``), each with its own kernel name.
+  2. EXACTLY ``--steps`` launches, bracketed by barrier + synchronize on both sides, max over ranks: ``ms_per_step`` and
+     ``value``; ``--reps R`` times R such repetitions instead and reports the MEDIAN one, all of them listed (``reps_ms_per_step``);
+  3. with ``--dump-outputs DIR``: the last step's output as float32 ``.npy`` (``dump_outputs``); the inputs are seeded, so two
+     builds can be compared output for output.
+``--full`` adds the rest (and makes ``--reps`` default to 7): the MFMA ceiling probe, the tolerance-meeting variant (fp32 store +
+split P, ``parity_variant``), the other BASELINE shapes (``other_workloads``, each with its own kernel name), the backward, the
+module level, fp32 operands, the ``need_weights`` pass, the parity check against the oracle and the CPU baseline; with N GPUs, the
+north star's single gather of the outputs, run ONCE after the timed region and reported separately (``gather``: RCCL's
+all_gather_into_tensor and the direct W-1-link exchange), together with a secondary loop that overlaps one gather per forward on a
+side stream (``end_to_end``).  The ``--no-*`` options leave single legs out of a ``--full`` run.
 ``python bench.py --gpus N`` without a launcher starts its N ranks itself (fresh child processes, before the parent touches a GPU).
 
 FLOP convention: 4*B*H*Sq*Sk*D, halved for causal.
@@ -156,19 +159,50 @@ def parity_check(q, k, v, causal, heads, variant):
     return e16, e32
 
 
+DUMP_BYTES = 48 << 20      # float32 bytes a dump may take over all ranks (index file aside): under 64 MB in all
+
+
+def dump_outputs(out, ddir, rank, world):
+    """--dump-outputs: the output a caller of the timed step receives ([B,S,H,D]; the last step wrote it) as float32 .npy.
+    Whole (``out.npy``) when it fits this rank's share of DUMP_BYTES, else a fixed seeded sample of whole D-rows:
+    ``out_rows.npy`` [n, D] and ``out_rows_index.npy`` [n, 3] (batch, seq, head of each row, float64).
+    With N GPUs every rank writes its own shard, suffixed ``_rank<r>``."""
+    import numpy as np
+    import torch
+    os.makedirs(ddir, exist_ok=True)
+    tag = "out" if world == 1 else f"out_rank{rank}"
+    budget = DUMP_BYTES // world
+    if out.numel() * 4 <= budget:
+        np.save(os.path.join(ddir, tag + ".npy"), out.float().cpu().numpy())
+        return
+    B, S, H, D = out.shape
+    pick = np.sort(np.random.default_rng(0).choice(B * S * H, budget // (D * 4), replace=False))
+    idx = np.stack(np.unravel_index(pick, (B, S, H)), axis=1)
+    b, s, h = (torch.from_numpy(idx[:, i]).to(out.device) for i in range(3))
+    np.save(os.path.join(ddir, tag + "_rows.npy"), out[b, s, h].float().cpu().numpy())
+    np.save(os.path.join(ddir, tag + "_rows_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=7, help="repetitions of exactly --steps launches; the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of exactly --steps launches; the median is reported (default 1, 7 with --full)")
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--variant", type=int, default=0, help="A/B only: kernel selector 43 / 44 / 45 of pfa_capi.hip (0 = production choice)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip parity_variant / other_workloads / backward / module (profiling runs)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the MFMA ceiling probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output to DIR as float32 .npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (probe, other shapes, backward, module, fp32, need_weights, "
+                         "parity, CPU baseline; the gathers with N GPUs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity check")
+    ap.add_argument("--no-others", action="store_true", help="--full without parity_variant / other_workloads / backward / module (profiling runs)")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the MFMA ceiling probe")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 7 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -255,11 +289,13 @@ def main():
     kern_ms = statistics.median(kerns)
     f_rank = flops(B, H, S, D, causal)
     value = f_rank * world / (ms_per_step * 1e-3) / 1e12
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world)
 
     # ---- the single gather at the end (outside the timed steps) + overlapped end-to-end loop --------------
     gather = end_to_end = None
     watchdog = None
-    if world > 1:
+    if world > 1 and args.full:
         # Secondary measurements must never cost the headline line -- not even by HANGING (a collective or an IPC mapping that never
         # returns on hardware this code has only met in a CPU rehearsal): if the gather legs are not through in 180 s, rank 0 prints the
         # line without them and every rank leaves.
@@ -324,7 +360,7 @@ def main():
     # 2.5 PFLOP/s is not reachable on random data by any kernel; `frac` stays against the nominal peak, `frac_of_probe` says how much
     # of the achievable rate the kernel holds.
     probe = None
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         try:
             import ctypes as C
             lib = _capi.load()
@@ -358,7 +394,7 @@ def main():
 
     # ---- 3. the tolerance-meeting variant and the other BASELINE shapes, same process --------------------------------------------
     parity_variant = others = None
-    if world == 1 and not args.no_others:
+    if world == 1 and args.full and not args.no_others:
         out32 = torch.empty(B, S, H, D, device=dev, dtype=torch.float32).permute(0, 2, 1, 3)
 
         def step32():
@@ -481,7 +517,7 @@ def main():
     # ---- 4. backward (pfa_fa3_bwd: the reference trains through autograd over its eager core, tests/unit/test_flash_attention_3.py:137-160)
     # and the module level (projections + core, core/flash_attention_3.py:49-118), same workload, same process
     backward = module = fp32 = None
-    if world == 1 and not args.no_others:
+    if world == 1 and args.full and not args.no_others:
         try:
             lse = torch.empty(B, H, S, device=dev, dtype=torch.float32)
             o_f, lse = ops.fa3_forward(qv, kv, vv, causal=causal, out=outv, return_lse=True)
@@ -569,7 +605,7 @@ def main():
             fp32 = {"error": f"{type(exc).__name__}: {exc}"[:300]}
 
     weights_leg = None
-    if world == 1 and not args.no_others:
+    if world == 1 and args.full and not args.no_others:
         try:   # need_weights (flash_attention_3.py:171,180,257-258): the softmax matrix [B,H,Sq,Sk] written by a second pass -- HBM-write bound
             import ctypes as C
             weights_leg = {}
@@ -639,14 +675,14 @@ def main():
             line["fp32_operands"] = fp32
         if weights_leg:
             line["need_weights"] = weights_leg
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             e16, e32 = parity_check(q, k, v, causal, [(0, 0), (B - 1, H - 1)], args.variant)
             line["parity"] = {"benched_kernel_bf16_out_max_abs": round(e16, 6),
                               "parity_variant_fp32_out_max_abs": round(e32, 8), "heads_checked": 2,
                               "oracle": "oracle/fa3_oracle.py (pinned by tests/golden)"}
             if parity_variant:
                 parity_variant["max_abs"] = round(e32, 8)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(B, H, S, D, causal)
         print(json.dumps(line), flush=True)
     if world > 1:

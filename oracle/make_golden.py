@@ -157,6 +157,61 @@ def module_case(name, B, S, E, H, seed):
     save(name, meta, out=y.numpy())
 
 
+def seam_case(name, B, S, E, H):
+    """G9: what the reference hands its seam (_flash_attention_forward) on every entry that ends
+    there: the geometry of each q / k / v view (shape, strides, storage offset, which views share a storage), the scaling
+    and the 2-D key mask.  The seam is replaced by a recorder that returns zeros, so that the reference runs on."""
+    if not wanted(name):
+        return
+    from photonic_flash_attention import PhotonicFlashAttention as RefPFA
+    from photonic_flash_attention.core.photonic_attention import PhotonicAttention as RefPA
+    calls, masks = [], {}
+
+    def recorder(self, q, k, v, attention_mask=None, need_weights=False):
+        ptrs = []
+        geo = {}
+        for tag, t in (("q", q), ("k", k), ("v", v)):
+            p = t.untyped_storage().data_ptr()
+            ptrs += [p] if p not in ptrs else []
+            geo[tag] = dict(shape=list(t.shape), stride=list(t.stride()), offset=t.storage_offset(), storage=ptrs.index(p),
+                            dtype=str(t.dtype).replace("torch.", ""))
+        geo.update(entry=ENTRY[0], scaling=float(self.scaling), need_weights=bool(need_weights), mask=None)
+        if attention_mask is not None:
+            geo["mask"] = f"mask{len(calls)}"
+            masks[geo["mask"]] = attention_mask.detach().float().numpy()
+        calls.append(geo)
+        return torch.zeros_like(q), None
+
+    ENTRY = [None]
+    seam, RefFA3._flash_attention_forward = RefFA3._flash_attention_forward, recorder
+    torch.manual_seed(1201)
+    D = E // H
+    x = torch.randn(B, S, E).to(torch.bfloat16)
+    km = torch.ones(B, S)
+    km[:, 100:] = 0
+    xkv = torch.randn(B, 77 * 8, E).to(torch.bfloat16)
+    with torch.no_grad():
+        m = RefFA3(E, H, dtype=torch.bfloat16).eval()
+        ENTRY[0] = "FlashAttention3.forward"
+        m(x)
+        ENTRY[0] = "FlashAttention3.forward, 2-D attention_mask"
+        m(x, attention_mask=km)
+        ENTRY[0] = "FlashAttention3.forward, cross attention"
+        m(x, xkv, xkv)
+        pfa = RefPFA(E, H, dtype=torch.bfloat16).eval()
+        if hasattr(pfa, "photonic_attention"):
+            pfa.photonic_attention = None            # the router's threshold always selects the GPU branch
+        pfa.photonic_available = False
+        ENTRY[0] = "PhotonicFlashAttention.forward"
+        pfa(x)
+        ENTRY[0] = "PhotonicAttention._fallback_forward"
+        RefPA(E, H, dtype=torch.bfloat16).eval()._fallback_forward(x, None, None, None, False)
+    RefFA3._flash_attention_forward = seam
+    meta = dict(kind="seam", B=B, S=S, E=E, H=H, D=D, calls=calls,
+                note="views handed to _flash_attention_forward by each reference entry that ends in the seam")
+    save(name, meta, **masks)
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(max(1, os.cpu_count() or 1))
@@ -197,6 +252,8 @@ def main():
     rows_16k = sorted(set(list(range(0, 8)) + list(range(8190, 8200)) + list(range(16376, 16384))))
     sampled_case("g6_c5", 1, 32, 16384, 128, 2005, True, [(0, 0), (0, 31)], rows_16k,
                  note="C5 B1 S16384 H32 D128 causal")
+    # G9: the views the reference hands its seam (tests/test_reference_binding.py replays them through INTEGRATION.md's stub)
+    seam_case("g9_seam_views", 2, 128, 256, 4)
 
 
 if __name__ == "__main__":

@@ -441,6 +441,34 @@ def test_cli_benchmark_schema(tmp_path):
     assert set(data) == {"benchmark_info", "results"} and {"version", "timestamp", "device_info", "config"} <= set(data["benchmark_info"])
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_output(tmp_path):
+    """bench.py without --full: one JSON line over exactly --steps timed launches and none of the secondary legs; --dump-outputs
+    writes what the last step computed (a fixed sample of C3's output rows), the forward of the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    from conftest import REPO
+    from photonic_flash_attention_amd import ops
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["metric"] == "attention_fwd_tflops" and line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "bf16"
+    assert line["timing"]["reps"] == 1 and len(line["timing"]["reps_ms_per_step"]) == 1
+    assert not {"parity", "cpu_baseline", "other_workloads", "backward", "parity_variant"} & set(line)
+    assert sorted(os.listdir(tmp_path)) == ["out_rows.npy", "out_rows_index.npy"]
+    rows, idx = np.load(tmp_path / "out_rows.npy"), np.load(tmp_path / "out_rows_index.npy").astype(np.int64)
+    assert rows.dtype == np.float32 and rows.shape == (len(idx), 128) and rows.nbytes + idx.nbytes <= 64e6
+    gen = torch.Generator(device=DEV).manual_seed(1234)                   # bench.py's make(4, 16, 4096, 128, 1234)
+    q, k, v = (torch.randn(4, 4096, 16, 128, device=DEV, dtype=torch.float32, generator=gen).to(torch.bfloat16) for _ in range(3))
+    o, _ = ops.fa3_forward_bshd(q, k, v, causal=True)
+    ref = o[tuple(torch.from_numpy(idx[:, i]).to(DEV) for i in range(3))].float().cpu().numpy()
+    assert float(np.abs(rows - ref).max()) <= 1e-2
+
+
 def test_convert_to_photonic_transformer_layer_on_gpu():
     """Converted nn.TransformerEncoderLayer (bf16, our kernel; weight rule of the reference's convert.py:441-452) vs the
     ORIGINAL torch layer in fp32 on the CPU."""

@@ -1,25 +1,21 @@
-"""The reference-side binding of INTEGRATION.md section B, run against the REAL reference (build container only: the reference
-cannot travel to the GPU box, so this test is skipped wherever /root/reference is absent).
+"""The reference-side binding of INTEGRATION.md section B, driven by what the REAL reference hands its seam.
 
-The ctypes stub a maintainer pastes into core/flash_attention_3.py is taken verbatim from INTEGRATION.md, patched into the
-IMPORTED reference class, and driven through every entry of the reference that ends in the seam (flash_attention_3.py:97-102,
-modules.py:154, photonic_attention.py:385-415).  `pfa_fa3_check` stands in for the launch (no GPU here): what is verified is
-that the argument block the stub builds from the views the reference really produces -- strides (S*3E, D, 3E, 1) -- passes
-the library's validation unchanged."""
+The ctypes stub a maintainer pastes into core/flash_attention_3.py is taken verbatim from INTEGRATION.md and fed the views that
+every entry of the reference ending in the seam (flash_attention_3.py:97-102, modules.py:154, photonic_attention.py:385-415)
+really produces: their shapes, strides (S*3E, D, 3E, 1), storage offsets and key mask were recorded from the imported reference
+by oracle/make_golden.py (tests/golden/g9_seam_views.npz) and are rebuilt here over fresh storage.  `pfa_fa3_check` stands in
+for the launch (no GPU here): what is verified is that the argument block the stub builds from those views passes the library's
+validation unchanged."""
 
 from __future__ import annotations
 
 import ctypes as C
 import os
-import sys
 
 import pytest
 import torch
 
-from conftest import REPO
-
-REF_SRC = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference lives in the build container only")
+from conftest import REPO, load_golden
 
 
 @pytest.fixture(scope="module")
@@ -47,65 +43,45 @@ def binding():
     return ns["fa3_forward"], seen
 
 
-@pytest.fixture(scope="module")
-def reference():
-    os.environ.setdefault("PHOTONIC_LOG_LEVEL", "CRITICAL")
-    sys.path.insert(0, REF_SRC)
-    try:
-        import photonic_flash_attention as ref
-        from photonic_flash_attention.core import flash_attention_3 as ref_fa3
-        yield ref, ref_fa3
-    finally:
-        sys.path.remove(REF_SRC)
+def seam_views(call):
+    """The q / k / v views of one recorded seam call, rebuilt over fresh storage (views that shared one keep sharing it)."""
+    size = {}
+    for t in ("q", "k", "v"):
+        g = call[t]
+        end = g["offset"] + sum((n - 1) * st for n, st in zip(g["shape"], g["stride"])) + 1
+        size[g["storage"]] = max(size.get(g["storage"], 0), end)
+    dt = getattr(torch, call["q"]["dtype"])
+    base = {i: torch.randn(n).to(dt) for i, n in size.items()}
+    return [torch.as_strided(base[call[t]["storage"]], call[t]["shape"], call[t]["stride"], call[t]["offset"]) for t in ("q", "k", "v")]
 
 
-def test_stub_in_the_imported_reference(binding, reference, monkeypatch):
+def test_stub_in_the_imported_reference(binding):
     fa3_forward, seen = binding
-    ref, ref_fa3 = reference
-
-    def patched(self, q, k, v, attention_mask=None, need_weights=False):      # INTEGRATION.md, "replacement for lines 134-150"
-        if need_weights or (attention_mask is not None and attention_mask.dim() != 2):
-            raise NotImplementedError("this minimal stub: 2-D key masks only, no attention weights")
-        return fa3_forward(q, k, v, self.scaling, key_mask=attention_mask), None
-
-    monkeypatch.setattr(ref_fa3.FlashAttention3, "_flash_attention_forward", patched)
-    B, S, E, H = 2, 128, 256, 4
-    D = E // H
-    x = torch.randn(B, S, E).to(torch.bfloat16)
-
-    m = ref_fa3.FlashAttention3(E, H, dtype=torch.bfloat16).eval()
-    with torch.no_grad():
-        y, w = m(x)                                                           # flash_attention_3.py:85-118
-    assert y.shape == (B, S, E) and w is None and len(seen) == 1
-    a = seen[-1]
+    meta, arr = load_golden("g9_seam_views")
+    B, S, E, H, D = (meta[n] for n in ("B", "S", "E", "H", "D"))
+    calls = meta["calls"]
+    assert [c["entry"] for c in calls] == ["FlashAttention3.forward", "FlashAttention3.forward, 2-D attention_mask",
+                                          "FlashAttention3.forward, cross attention", "PhotonicFlashAttention.forward",
+                                          "PhotonicAttention._fallback_forward"]
+    for i, call in enumerate(calls):
+        assert not call["need_weights"]                                       # (the stub: 2-D key masks only, no attention weights)
+        q, k, v = seam_views(call)
+        km = None if call["mask"] is None else torch.from_numpy(arr[call["mask"]])
+        assert km is None or km.dim() == 2
+        out = fa3_forward(q, k, v, call["scaling"], key_mask=km)              # INTEGRATION.md, "replacement for lines 134-150"
+        assert out.shape == q.shape and len(seen) == i + 1, call["entry"]
+    a = seen[0]                                                               # flash_attention_3.py:85-118
     assert (a["B"], a["H"], a["Sq"], a["Sk"], a["D"]) == (B, H, S, S, D) and a["dtype_in"] == 0
     # the strided views of the fused projection (:97-99), read in place: (S*3E, D, 3E) in elements
     assert (a["q_stride_b"], a["q_stride_h"], a["q_stride_s"]) == (S * 3 * E, D, 3 * E)
     assert a["k_stride_s"] == 3 * E and a["v_stride_s"] == 3 * E
     assert (a["o_stride_h"], a["o_stride_s"]) == (D, E)                       # [B,S,H,D] output: the transpose at :107 is a view
-
-    km = torch.ones(B, S)
-    km[:, 100:] = 0
-    with torch.no_grad():
-        m(x, attention_mask=km)                                               # the 2-D key mask of :166-167
-        xkv = torch.randn(B, 77 * 8, E).to(torch.bfloat16)
-        m(x, xkv, xkv)                                                        # cross attention: three separate projections (:92-94)
-    assert len(seen) == 3 and seen[-1]["Sk"] == 77 * 8 and seen[-1]["k_stride_s"] == 3 * E
-
-    pfa = ref.PhotonicFlashAttention(E, H, dtype=torch.bfloat16).eval()       # modules.py:77-116 -> gpu_attention
-    if hasattr(pfa, "photonic_attention"):
-        pfa.photonic_attention = None                                         # the router's threshold always selects the GPU branch
-    pfa.photonic_available = False
-    with torch.no_grad():
-        out = pfa(x)
-    assert torch.is_tensor(out) and out.shape == (B, S, E) and len(seen) == 4
-
-    from photonic_flash_attention.core.photonic_attention import PhotonicAttention
-    pa = PhotonicAttention(E, H, dtype=torch.bfloat16).eval()                 # photonic_attention.py:385-415
-    with torch.no_grad():
-        y2, _ = pa._fallback_forward(x, None, None, None, False)
-    assert y2.shape == (B, S, E) and len(seen) == 5
-    assert (seen[-1]["q_stride_b"], seen[-1]["q_stride_h"], seen[-1]["q_stride_s"]) == (S * 3 * E, D, 3 * E)
+    km = arr[calls[1]["mask"]]                                                # the 2-D key mask of :166-167
+    assert km.shape == (B, S) and (km[:, :100] == 1).all() and (km[:, 100:] == 0).all()
+    assert seen[2]["Sk"] == 77 * 8 and seen[2]["k_stride_s"] == 3 * E         # cross attention: three separate projections (:92-94)
+    # modules.py:77-116 -> gpu_attention and photonic_attention.py:385-415 end in the same views
+    for a in seen[3:]:
+        assert (a["q_stride_b"], a["q_stride_h"], a["q_stride_s"]) == (S * 3 * E, D, 3 * E)
 
 
 def test_stub_reports_library_errors(binding):
