@@ -3,7 +3,8 @@
  * replaces the body of the reference's electronic attention core.
  * ABI history: v1 forward; v2 general masks + weights; v3 backward; v4 grouped-query heads (kv_group); v5 fp32 operands (exact
  * fp32 kernels, forward and backward) and dense-branch attention dropout; v6 pfa_fa3_prepare, reserve_cus, pfa_probe_mfma;
- * v7 pfa_fa3_bwd_args.kv_group (grouped-query heads in the backward: dK / dV summed over the group in the kernel).
+ * v7 pfa_fa3_bwd_args.kv_group (grouped-query heads in the backward: dK / dV summed over the group in the kernel); v8 split-KV decode
+ * over a KV cache (pfa_fa3_decode_args, pfa_fa3_decode*: query rows of a K/V head packed together, keys split over workgroups).
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -45,7 +46,7 @@
 extern "C" {
 #endif
 
-#define PFA_ABI_VERSION 7
+#define PFA_ABI_VERSION 8
 
 typedef enum pfa_status {
     PFA_OK = 0,
@@ -102,7 +103,7 @@ typedef struct pfa_fa3_args {
     int32_t B, H, Sq, Sk, D;
     int32_t dtype_in;           /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 | PFA_DTYPE_FP32 (exact fp32 kernel: strides multiples of 4 elements, dtype_out fp32, no flags) */
     int32_t dtype_out;          /* = dtype_in, or PFA_DTYPE_FP32                     */
-    int32_t causal;             /* 1: key j visible to row i iff j <= i (top-left)   */
+    int32_t causal;             /* 1: key j visible to row i iff j <= i (top-left; pfa_fa3_decode_args.causal is bottom-right) */
     float   softmax_scale;      /* usually D^-0.5                                    */
     int32_t device_id;          /* HIP device ordinal the pointers live on           */
 
@@ -243,6 +244,61 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream);
  * would launch for `a` into buf (NUL terminated, truncated to n) and returns the number of workgroups.
  */
 int pfa_fa3_describe(const pfa_fa3_args* a, char* buf, size_t n);
+
+/*
+ * Decode over a KV cache (ABI v8), in the style of flash_attn_with_kvcache: a few new query rows per batch against the keys a cache
+ * holds.  O[b,i,h,:] = softmax_j(scale * <Q[b,i,h,:], K[b,j,h/g,:]> + mask) V[b,j,h/g,:], g = H / Hkv.
+ *
+ *   q, o            [B, Sq, H, D] by element strides (last dim contiguous); 1 <= Sq <= 64; o in dtype_in or fp32
+ *   k_cache/v_cache [B, Smax, Hkv, D] by element strides: HF's [B, Hkv, S, D] cache and a slice of a larger preallocated cache are other
+ *                   strides.  Query head h reads K/V head h / (H / Hkv).
+ *   cache_seqlens   optional int32 [B] on the device: valid keys of each batch (<= Smax; keys at and past it are never read).  NULL = Smax.
+ *   key_mask        optional [B, Smax] bytes, 0 = masked (left padding, holes of a static cache); key_mask_stride_b bytes between batches.
+ *   causal          1: BOTTOM-RIGHT aligned per batch -- row i sees key j iff j <= cache_seqlens[b] - Sq + i (chunked prefill, speculative
+ *                   verification).  pfa_fa3_args.causal is top-left (j <= i).
+ *   lse             optional fp32 [B, H, Sq] natural-log LSE.  A row with no visible key gets O = 0 and LSE = -inf.
+ *
+ * bf16 / fp16 operands, D in {64, 128}; q/k/v strides multiples of 8 elements, o strides of 4; base pointers 16-byte aligned.
+ * Work is split over keys: each split writes fp32 partials (O, m, l) into `workspace` and a second launch combines them (no atomics:
+ * bitwise reproducible).  pfa_fa3_decode_workspace_bytes() depends on the shapes (B, H, Hkv, Sq, Smax, D) only, never on the
+ * device-side lengths, so a captured graph stays valid while cache_seqlens and the cache change between replays.  The workspace is
+ * required when that size is non-zero (missing or too small: PFA_ERR_NULL).
+ */
+typedef struct pfa_fa3_decode_args {
+    uint32_t size;              /* = sizeof(pfa_fa3_decode_args) */
+    uint32_t flags;             /* must be 0 */
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    void*       o;
+    float*      lse;
+    const int32_t* cache_seqlens;
+    const uint8_t* key_mask;
+    int64_t q_stride_b, q_stride_h, q_stride_s;
+    int64_t k_stride_b, k_stride_h, k_stride_s;
+    int64_t v_stride_b, v_stride_h, v_stride_s;
+    int64_t o_stride_b, o_stride_h, o_stride_s;
+    int64_t key_mask_stride_b;
+    int32_t B, H, Hkv, Sq, Smax, D;
+    int32_t dtype_in;           /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 */
+    int32_t dtype_out;          /* = dtype_in, or PFA_DTYPE_FP32 */
+    int32_t causal;             /* bottom-right, see above */
+    float   softmax_scale;
+    int32_t device_id;
+    int32_t reserved0;          /* must be 0 */
+    void*   workspace;          /* pfa_fa3_decode_workspace_bytes() bytes */
+    size_t  workspace_bytes;
+} pfa_fa3_decode_args;
+
+/* Scratch bytes pfa_fa3_decode needs for `a` (0: none); from shapes only.  0 also for arguments pfa_fa3_decode_check refuses. */
+size_t pfa_fa3_decode_workspace_bytes(const pfa_fa3_decode_args* a);
+/* Validate `a` without launching: PFA_OK or the error pfa_fa3_decode would return. */
+int pfa_fa3_decode_check(const pfa_fa3_decode_args* a);
+/* Enqueue the decode (one launch, plus the combine launch when the keys are split) on `stream`. */
+int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream);
+/* Introspection for tests / tools: the kernel name into buf (NUL terminated, truncated to n), the number of key splits into *nsplit
+ * (may be NULL); returns the workgroups of the main launch, or a pfa_status. */
+int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, int32_t* nsplit);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

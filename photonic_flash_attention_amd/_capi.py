@@ -13,7 +13,7 @@ import os
 import threading
 from typing import Optional
 
-PFA_ABI_VERSION = 7
+PFA_ABI_VERSION = 8
 PFA_DTYPE_BF16, PFA_DTYPE_FP16, PFA_DTYPE_FP32 = 0, 1, 2
 PFA_FLAG_SPLIT_P = 0x1
 PFA_FLAG_NO_XCD_MAP = 0x2
@@ -25,6 +25,7 @@ EXPORTS = (
     "pfa_abi_version", "pfa_status_string", "pfa_device_supported", "pfa_last_hip_error",
     "pfa_fa3_workspace_bytes", "pfa_fa3_check", "pfa_fa3_fwd", "pfa_fa3_describe", "pfa_fa3_weights",
     "pfa_fa3_bwd", "pfa_fa3_bwd_workspace_bytes", "pfa_fa3_bwd_mask_workspace_bytes", "pfa_fa3_prepare", "pfa_probe_mfma",
+    "pfa_fa3_decode_workspace_bytes", "pfa_fa3_decode_check", "pfa_fa3_decode", "pfa_fa3_decode_describe",
 )
 
 
@@ -62,6 +63,19 @@ class PfaFa3BwdArgs(C.Structure):
         + [("mask", C.c_void_p)] + [(f"mask_stride_{a}", C.c_int64) for a in "bhqk"]
         + [("drop_mask", C.c_void_p), ("drop_scale", C.c_float), ("kv_group", C.c_int32)]
         + [("mask_workspace", C.c_void_p), ("mask_workspace_bytes", C.c_size_t)]
+    )
+
+
+class PfaFa3DecodeArgs(C.Structure):
+    """Mirror of ``struct pfa_fa3_decode_args`` (include/pfa_hip.h, ABI v8)."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("q", "k_cache", "v_cache", "o", "lse", "cache_seqlens", "key_mask")]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "qkvo" for a in "bhs"]
+        + [("key_mask_stride_b", C.c_int64)]
+        + [(n, C.c_int32) for n in ("B", "H", "Hkv", "Sq", "Smax", "D", "dtype_in", "dtype_out", "causal")]
+        + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
+        + [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
     )
 
 
@@ -118,6 +132,14 @@ def load(path: Optional[str] = None):
         lib.pfa_fa3_prepare.argtypes = [C.c_int]
         lib.pfa_probe_mfma.restype = C.c_int
         lib.pfa_probe_mfma.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        lib.pfa_fa3_decode_workspace_bytes.restype = C.c_size_t
+        lib.pfa_fa3_decode_workspace_bytes.argtypes = [C.POINTER(PfaFa3DecodeArgs)]
+        lib.pfa_fa3_decode_check.restype = C.c_int
+        lib.pfa_fa3_decode_check.argtypes = [C.POINTER(PfaFa3DecodeArgs)]
+        lib.pfa_fa3_decode.restype = C.c_int
+        lib.pfa_fa3_decode.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_void_p]
+        lib.pfa_fa3_decode_describe.restype = C.c_int
+        lib.pfa_fa3_decode_describe.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
@@ -152,3 +174,21 @@ def describe(args: PfaFa3Args):
     if n < 0:
         check_status(n)
     return buf.value.decode(), n
+
+
+def make_decode_args(**kw) -> PfaFa3DecodeArgs:
+    a = PfaFa3DecodeArgs()
+    a.size = C.sizeof(PfaFa3DecodeArgs)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def describe_decode(args: PfaFa3DecodeArgs):
+    """-> (kernel name, workgroups of the main launch, number of key splits) of ``pfa_fa3_decode``."""
+    buf = C.create_string_buffer(128)
+    ns = C.c_int32(0)
+    n = load().pfa_fa3_decode_describe(C.byref(args), buf, 128, C.byref(ns))
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n, ns.value

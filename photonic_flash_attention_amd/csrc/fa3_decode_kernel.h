@@ -1,0 +1,370 @@
+// fa3_decode_kernel.h -- split-KV decode attention over a KV cache for MI355X (gfx950), hand-written HIP.
+//
+// A decode step reads the whole cache once and does little arithmetic per byte, so the kernel is built around the HBM stream:
+//   * One work item = (batch, K/V head, row block, key split).  Its rows are the Sq x (H / Hkv) query rows that share the K/V
+//     head, packed 16 to a row block (row r = i * G + g: query position i, head g of the group), so each K/V byte is fetched
+//     once per group instead of once per query head.
+//   * Split over keys: the host picks nsplit from shapes alone; split s of batch b covers [s c_b, min((s+1) c_b, len_b)) with
+//     c_b = roundup(ceil(len_b / nsplit), 64), so ragged batches spread over all their splits and a split past a batch's
+//     length writes an empty partial without loading anything.
+//   * A workgroup is 4 waves; wave w takes the split's key tiles w, w + 4, ...  K and V go HBM -> registers by buffer_load_dwordx4
+//     (per-tile descriptor whose record count ends at the split's last key: rows past it read as zeros), one tile ahead of the
+//     math (16 KiB per wave in flight).  S^T = K Q^T and O^T += V^T P^T on the 16x16x32 MFMA: the S^T accumulator holds one
+//     query row per lane, so it is, converted to 16 bits, the P^T operand of the PV product as it stands (key order permuted:
+//     element j of lane group h of PV k-step u is key 32u + 16(j>>2) + 4h + (j&3)); V^T is read in that order from a per-wave
+//     row-major LDS image with ds_read_b64_tr_b16 (rows padded by 32 bytes: conflict-free transposed reads).
+//   * Online softmax in fp32 (log2 domain; with an fp32 output P is carried as 16-bit hi + lo), masks (key mask, split end, bottom-right causal cut) only on tiles they touch.
+//   * The 4 waves' (m, l, O) merge through LDS; the workgroup writes O and LSE (nsplit == 1) or fp32 partials (O, m, l) that
+//     fa3_decode_combine_kernel reduces.  No atomics: bitwise reproducible.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace pfa {
+namespace dec {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __amdgpu_buffer_rsrc_t srd_t;
+typedef __attribute__((address_space(3))) char lds_char;
+
+constexpr int NW = 4;            // waves per workgroup
+constexpr int ROWS = 16;         // query rows per row block (the MFMA's 16-wide dimension)
+constexpr int SPLIT_ALIGN = 64;  // split boundaries are multiples of this many keys
+constexpr int THREADS = NW * 64;
+
+struct DecodeParams {
+    const void* q;
+    const void* k;
+    const void* v;
+    void* o;
+    float* lse;                  // optional [B, H, Sq]
+    const int32_t* seqlens;      // optional [B]
+    const uint8_t* key_mask;     // optional [B, Smax] bytes, 0 = masked
+    int64_t q_sb, q_sh, q_ss;    // element strides
+    int64_t k_sb, k_sh, k_ss;
+    int64_t v_sb, v_sh, v_ss;
+    int64_t o_sb, o_sh, o_ss;
+    int64_t km_sb;
+    float* part_o;               // nsplit > 1: [nsplit][B][H][Sq][D] fp32, un-normalised
+    float* part_ml;              // nsplit > 1: [nsplit][B][H][Sq][2] fp32 (running max in log2 units, row sum)
+    int32_t B, H, Hkv, G, Sq, Smax, nrb, nsplit;
+    int32_t causal;              // bottom-right: row i sees key j iff j <= len_b - Sq + i
+    float scale_log2;            // softmax_scale * log2(e)
+};
+
+template <typename T> struct DElem;
+template <> struct DElem<__bf16> {
+    using v8 = bf16x8;
+    using v4 = bf16x4;
+    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ v4 tr_read(const lds_char* p) {
+        return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) v4*)p);
+    }
+};
+template <> struct DElem<_Float16> {
+    using v8 = f16x8;
+    using v4 = f16x4;
+    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ v4 tr_read(const lds_char* p) {
+        typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 h4;
+        return __builtin_bit_cast(v4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)p));
+    }
+};
+
+// Per head dim: keys per wave tile, loads per lane, LDS image geometry.
+template <int D> struct Geo {
+    static constexpr int KT = D == 128 ? 32 : 64;        // keys per wave tile: 16 KiB of K + V either way
+    static constexpr int NKB = KT / 16;                   // 16-key blocks of S^T
+    static constexpr int KS = D / 32;                     // QK^T k-steps (32 head-dim elements each)
+    static constexpr int NDB = D / 16;                    // 16-column blocks of O^T
+    static constexpr int KLD = NKB * KS;                  // 16-byte K loads per lane per tile
+    static constexpr int KPI = 512 / D;                   // keys per 1-KiB V load instruction
+    static constexpr int VLD = KT / KPI;                  // 16-byte V loads per lane per tile
+    static constexpr int VROW = D * 2 + 32;               // LDS bytes per key row of the V image
+    static constexpr int VIMG = KT * VROW;                // per wave
+    static constexpr int MERGE = NW * ROWS * D * 4 + NW * ROWS * 8;
+    static constexpr int LDS = VIMG * NW > MERGE ? VIMG * NW : MERGE;
+};
+
+// raw-buffer descriptor whose inputs are provably wave-uniform
+__device__ __forceinline__ srd_t uniform_srd(const char* base, uint32_t bytes) {
+    const uint64_t a = (uint64_t)(uintptr_t)base;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), 0, (int)__builtin_amdgcn_readfirstlane(bytes),
+                                             0x00020000);
+}
+
+template <typename OT> __device__ __forceinline__ void store4(OT* p, f32x4 x);
+template <> __device__ __forceinline__ void store4<float>(float* p, f32x4 x) { *(f32x4*)p = x; }
+template <> __device__ __forceinline__ void store4<__bf16>(__bf16* p, f32x4 x) { *(bf16x4*)p = bf16x4{(__bf16)x[0], (__bf16)x[1], (__bf16)x[2], (__bf16)x[3]}; }
+template <> __device__ __forceinline__ void store4<_Float16>(_Float16* p, f32x4 x) {
+    *(f16x4*)p = f16x4{(_Float16)x[0], (_Float16)x[1], (_Float16)x[2], (_Float16)x[3]};
+}
+
+// The split of batch b this item covers: [lo, hi) (empty when lo >= hi).  len is the batch's valid key count.
+__device__ __forceinline__ void split_range(const DecodeParams& p, int b, int s, int& len, int& lo, int& hi) {
+    len = p.seqlens ? min(max(p.seqlens[b], 0), p.Smax) : p.Smax;
+    const int per = (len + p.nsplit - 1) / p.nsplit;
+    const int c = (per + SPLIT_ALIGN - 1) / SPLIT_ALIGN * SPLIT_ALIGN;
+    lo = min(s * c, len);
+    hi = min(lo + c, len);
+}
+
+template <typename T, int D, typename OT>
+__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodeParams p) {
+    using E = DElem<T>;
+    using v8 = typename E::v8;
+    using v4 = typename E::v4;
+    using Gm = Geo<D>;
+    constexpr int KT = Gm::KT, NKB = Gm::NKB, KS = Gm::KS, NDB = Gm::NDB, VLD = Gm::VLD, VROW = Gm::VROW;
+    // fp32 output: P carried as a 16-bit hi + lo pair (two PV MFMAs) so that the result is within 1e-3 of the exact one; the
+    // matrix pipe has time to spare here, the kernel waits on HBM
+    constexpr bool SPLIT_P = sizeof(OT) == 4;
+    __shared__ __attribute__((aligned(16))) char smem[Gm::LDS];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int x = blockIdx.x;
+    const int s = x % p.nsplit;
+    x /= p.nsplit;
+    const int rb = x % p.nrb;
+    x /= p.nrb;
+    const int kvh = x % p.Hkv, b = x / p.Hkv;
+    int len, lo, hi;
+    split_range(p, b, s, len, lo, hi);
+    len = __builtin_amdgcn_readfirstlane(len);
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+
+    // this lane's query row (the MFMA column) and lane group
+    const int c = lane & 15, h = lane >> 4;
+    const int r = rb * ROWS + c;
+    const bool row_ok = r < p.Sq * p.G;
+    const int qi = row_ok ? r / p.G : 0, qg = row_ok ? r % p.G : 0;
+    const int head = kvh * p.G + qg;
+    const int row_lim = p.causal ? len - p.Sq + qi + 1 : len;     // exclusive key bound of this row (before the split's)
+    const int min_lim = p.causal ? len - p.Sq + 1 : len;          // every row sees at least the keys below this
+
+    f32x4 oacc[NDB];
+#pragma unroll
+    for (int d = 0; d < NDB; ++d) oacc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -__builtin_inff(), l = 0.f;
+
+    const int ntile = hi > lo ? (hi - lo + KT - 1) / KT : 0;
+    if (wave < ntile) {
+        // Q^T operand: lane holds Q[row c][32 ks + 8 h .. + 8]
+        v8 qf[KS];
+        const T* qrow = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)qi * p.q_ss + (int64_t)head * p.q_sh;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            u32x4 w = row_ok ? *(const u32x4*)(qrow + 32 * ks + 8 * h) : u32x4{0u, 0u, 0u, 0u};
+            qf[ks] = __builtin_bit_cast(v8, w);
+        }
+        const char* kslab = (const char*)p.k + ((int64_t)b * p.k_sb + (int64_t)kvh * p.k_sh) * 2;
+        const char* vslab = (const char*)p.v + ((int64_t)b * p.v_sb + (int64_t)kvh * p.v_sh) * 2;
+        const uint32_t kss2 = (uint32_t)p.k_ss * 2u, vss2 = (uint32_t)p.v_ss * 2u;
+        // per-lane byte offsets inside a tile: K in the A-operand layout (key kb*16 + c, head dims 32 ks + 8 h ..),
+        // V one 1-KiB piece per instruction (key vi*KPI + lane / (D/8), chunk lane % (D/8))
+        const uint32_t koff0 = (uint32_t)c * kss2 + (uint32_t)h * 16u;
+        const uint32_t vkey = (uint32_t)lane / (D / 8), vch = (uint32_t)lane % (D / 8);
+        const uint32_t voff0 = vkey * vss2 + vch * 16u;
+        lds_char* vimg = (lds_char*)(smem + wave * Gm::VIMG);
+        const uint32_t vwr = vkey * VROW + vch * 16u;
+        // transposed read: lane 4q + p of its 16-lane group addresses key row (block base + 4h + q), columns 4p .. 4p + 3
+        const uint32_t vtr = (uint32_t)(4 * h + ((lane & 15) >> 2)) * VROW + (uint32_t)(lane & 3) * 8u;
+
+        u32x4 kr[NKB * KS], vr[VLD];
+        auto issue = [&](int t) {
+            const int t0 = lo + t * KT;
+            const int nk = min(KT, hi - t0);     // rows past the split's end read as zeros
+            const srd_t vs = uniform_srd(vslab + (int64_t)t0 * p.v_ss * 2, (uint32_t)(nk - 1) * vss2 + D * 2);
+            const srd_t ks = uniform_srd(kslab + (int64_t)t0 * p.k_ss * 2, (uint32_t)(nk - 1) * kss2 + D * 2);
+#pragma unroll
+            for (int i = 0; i < VLD; ++i)
+                vr[i] = __builtin_amdgcn_raw_buffer_load_b128(vs, (int)(voff0 + (uint32_t)(i * Gm::KPI) * vss2), 0, 0);
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                for (int q = 0; q < KS; ++q)
+                    kr[kb * KS + q] = __builtin_amdgcn_raw_buffer_load_b128(ks, (int)(koff0 + (uint32_t)(kb * 16) * kss2 + q * 64), 0, 0);
+        };
+        issue(wave);
+        const uint8_t* km = p.key_mask ? p.key_mask + (int64_t)b * p.km_sb : nullptr;
+
+        for (int t = wave; t < ntile; t += NW) {
+            const int t0 = lo + t * KT;
+            // V tile -> this wave's LDS image (row-major, padded rows)
+#pragma unroll
+            for (int i = 0; i < VLD; ++i) *(__attribute__((address_space(3))) u32x4*)(vimg + vwr + i * Gm::KPI * VROW) = vr[i];
+            // S^T = K Q^T
+            f32x4 sacc[NKB];
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) {
+                sacc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int q = 0; q < KS; ++q) sacc[kb] = E::mfma(__builtin_bit_cast(v8, kr[kb * KS + q]), qf[q], sacc[kb]);
+            }
+            if (t + NW < ntile) issue(t + NW);
+
+            // scores in log2 units; masks only where the tile reaches past the split, the causal cut, or a key mask exists
+            const bool edge = km != nullptr || t0 + KT > hi || t0 + KT > min_lim;
+            float mx = -__builtin_inff();
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float sc = sacc[kb][e] * p.scale_log2;
+                    if (edge) {
+                        const int key = t0 + kb * 16 + 4 * h + e;
+                        bool vis = key < hi && key < row_lim;
+                        if (vis && km) vis = km[key] != 0;
+                        sc = vis ? sc : -__builtin_inff();
+                    }
+                    sacc[kb][e] = sc;
+                    mx = fmaxf(mx, sc);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float m_new = fmaxf(m, mx);
+            const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m - m_use);
+            m = m_new;
+            float ps = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float pe = __builtin_amdgcn_exp2f(sacc[kb][e] - m_use);
+                    sacc[kb][e] = pe;
+                    ps += pe;
+                }
+            l = l * alpha + ps;
+#pragma unroll
+            for (int d = 0; d < NDB; ++d) oacc[d] *= alpha;
+
+            asm volatile("" ::: "memory");     // the image writes above stay ahead of the transposed reads below (in-order LDS)
+            // O^T += V^T P^T, one 32-key k-step per pair of S^T blocks
+#pragma unroll
+            for (int u = 0; u < NKB / 2; ++u) {
+                v8 pf, plo;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    pf[e] = (T)sacc[2 * u][e];
+                    pf[4 + e] = (T)sacc[2 * u + 1][e];
+                    if constexpr (SPLIT_P) {
+                        plo[e] = (T)(sacc[2 * u][e] - (float)pf[e]);
+                        plo[4 + e] = (T)(sacc[2 * u + 1][e] - (float)pf[4 + e]);
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < NDB; ++d) {
+                    const v4 a0 = E::tr_read(vimg + vtr + (uint32_t)(32 * u) * VROW + d * 32);
+                    const v4 a1 = E::tr_read(vimg + vtr + (uint32_t)(32 * u + 16) * VROW + d * 32);
+                    const v8 va = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+                    oacc[d] = E::mfma(va, pf, oacc[d]);
+                    if constexpr (SPLIT_P) oacc[d] = E::mfma(va, plo, oacc[d]);
+                }
+            }
+            asm volatile("" ::: "memory");     // ... and the next tile's image writes behind them
+        }
+    }
+    // row sum over the row's four lane groups
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+
+    // merge the waves' partials through LDS (the V images are dead after this barrier)
+    __syncthreads();
+    float* mo = (float*)smem;                                   // [NW][ROWS][D]
+    float* mml = (float*)(smem + NW * ROWS * D * 4);            // [NW][ROWS][2]
+#pragma unroll
+    for (int d = 0; d < NDB; ++d) *(f32x4*)(mo + (wave * ROWS + c) * D + 16 * d + 4 * h) = oacc[d];
+    if (h == 0) {
+        mml[(wave * ROWS + c) * 2] = m;
+        mml[(wave * ROWS + c) * 2 + 1] = l;
+    }
+    __syncthreads();
+    constexpr int TPR = THREADS / ROWS, DPT = D / TPR;          // threads per row, head-dim elements per thread
+    const int orow = tid / TPR, d0 = (tid % TPR) * DPT;
+    const int rr = rb * ROWS + orow;
+    if (rr >= p.Sq * p.G) return;
+    float mw[NW], M = -__builtin_inff();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        mw[w] = mml[(w * ROWS + orow) * 2];
+        M = fmaxf(M, mw[w]);
+    }
+    const float Mu = M == -__builtin_inff() ? 0.f : M;
+    float L = 0.f, sc[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        sc[w] = __builtin_amdgcn_exp2f(mw[w] - Mu);
+        L += sc[w] * mml[(w * ROWS + orow) * 2 + 1];
+    }
+    const int oi = rr / p.G, oh = kvh * p.G + rr % p.G;
+    if (p.nsplit == 1) {
+        const float inv = L > 0.f ? 1.f / L : 0.f;
+        OT* orow_p = (OT*)p.o + (int64_t)b * p.o_sb + (int64_t)oi * p.o_ss + (int64_t)oh * p.o_sh;
+#pragma unroll
+        for (int d = 0; d < DPT; d += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * D + d0 + d);
+            store4<OT>(orow_p + d0 + d, acc * inv);
+        }
+        if (p.lse && d0 == 0)
+            p.lse[((int64_t)b * p.H + oh) * p.Sq + oi] = L > 0.f ? (M + __log2f(L)) * 0.6931471805599453f : -__builtin_inff();
+    } else {
+        const int64_t prow = (((int64_t)s * p.B + b) * p.H + oh) * p.Sq + oi;
+        float* po = p.part_o + prow * D;
+#pragma unroll
+        for (int d = 0; d < DPT; d += 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * D + d0 + d);
+            *(f32x4*)(po + d0 + d) = acc;
+        }
+        if (d0 == 0) {
+            p.part_ml[prow * 2] = M;
+            p.part_ml[prow * 2 + 1] = L;
+        }
+    }
+}
+
+// Reduce the splits of every (b, h, i) row: one thread per 4 head-dim elements of a row.
+template <int D, typename OT>
+__global__ __launch_bounds__(256) void fa3_decode_combine_kernel(const DecodeParams p) {
+    constexpr int TPR = D / 4;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t rows = (int64_t)p.B * p.H * p.Sq;
+    const int64_t row = t / TPR;
+    if (row >= rows) return;
+    const int d0 = (int)(t % TPR) * 4;
+    const int64_t pstride = rows;
+    float M = -__builtin_inff();
+#pragma unroll 8
+    for (int s = 0; s < p.nsplit; ++s) M = fmaxf(M, p.part_ml[(s * pstride + row) * 2]);
+    const float Mu = M == -__builtin_inff() ? 0.f : M;
+    float L = 0.f;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8   // (eight splits' loads in flight: the launch is a few microseconds of latency, not bandwidth)
+    for (int s = 0; s < p.nsplit; ++s) {
+        const int64_t pr = s * pstride + row;
+        const float w = __builtin_amdgcn_exp2f(p.part_ml[pr * 2] - Mu);
+        L += w * p.part_ml[pr * 2 + 1];
+        acc += w * *(const f32x4*)(p.part_o + pr * D + d0);
+    }
+    const int i = (int)(row % p.Sq);
+    const int64_t bh = row / p.Sq;
+    const int hh = (int)(bh % p.H), b = (int)(bh / p.H);
+    const float inv = L > 0.f ? 1.f / L : 0.f;
+    store4<OT>((OT*)p.o + (int64_t)b * p.o_sb + (int64_t)i * p.o_ss + (int64_t)hh * p.o_sh + d0, acc * inv);
+    if (p.lse && d0 == 0) p.lse[row] = L > 0.f ? (M + __log2f(L)) * 0.6931471805599453f : -__builtin_inff();
+}
+
+}  // namespace dec
+}  // namespace pfa

@@ -187,6 +187,8 @@ int check(const pfa_fa3_args* a) {
 
 }  // namespace
 
+namespace pfa { void set_last_hip_error(int e) { g_last_hip_error = e; } }   // for the other translation units' entry points
+
 namespace {
 template <typename T, int D, bool C, bool K>
 const void* weights_fn(bool w32) {

@@ -52,6 +52,20 @@ def pfa_attention_mask(batch_size: int, q_length: int, kv_length: int, q_offset:
     return mu.sdpa_mask(**kw, **kwargs)
 
 
+def _is_decode_step(query, key, value, attention_mask) -> bool:
+    """A cached generation step ``ops.fa3_decode`` takes: one query row against a longer cache, a head dim it has a kernel for, no
+    gradient wanted, and no mask or a ``[B|1, 1, 1, Sk]`` one (a per-head or per-row mask keeps the general path)."""
+    q_len, k_len = query.shape[2], key.shape[2]
+    if not (q_len == 1 < k_len) or query.shape[-1] not in (64, 128):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (query, key, value)):
+        return False
+    if attention_mask is None:
+        return True
+    return (attention_mask.dim() == 4 and attention_mask.shape[0] in (1, query.shape[0]) and attention_mask.shape[1] == 1
+            and attention_mask.shape[2] == 1 and attention_mask.shape[3] == k_len)
+
+
 def pfa_attention_forward(module, query, key, value, attention_mask, dropout: float = 0.0,
                           scaling: Optional[float] = None, is_causal: Optional[bool] = None, **kwargs):
     """``AttentionInterface`` function: ``query/key/value`` are ``[B, H(kv), S, D]``; returns ``([B, Sq, H, D], None)``.
@@ -67,6 +81,13 @@ def pfa_attention_forward(module, query, key, value, attention_mask, dropout: fl
     if query.shape[-1] > 128:
         raise NotImplementedError(f"head_dim {query.shape[-1]} has no kernel (<= 128)")
     q_len, k_len = query.shape[2], key.shape[2]
+    in_dtype = query.dtype
+    cd = in_dtype if in_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+    if _is_decode_step(query, key, value, attention_mask):
+        # one new token against the cache: the split-KV decode kernel (inference only; the mask's single row is the key mask)
+        km = None if attention_mask is None else _keep_mask(attention_mask)[:, 0, 0, :].expand(query.shape[0], k_len)
+        out, _ = ops.fa3_decode(query.to(cd), key.to(cd), value.to(cd), key_mask=km, softmax_scale=scaling, out_dtype=in_dtype)
+        return out.transpose(1, 2), None
     want_causal = is_causal if is_causal is not None else getattr(module, "is_causal", True)
     key_mask = keep = None
     if attention_mask is not None and attention_mask.dim() == 2:
@@ -78,8 +99,6 @@ def pfa_attention_forward(module, query, key, value, attention_mask, dropout: fl
     else:
         causal = bool(q_len > 1 and attention_mask is None and want_causal)
         keep = _keep_mask(attention_mask)
-    in_dtype = query.dtype
-    cd = in_dtype if in_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
     out = ops.fa3_attention(query.to(cd), key.to(cd), value.to(cd), causal=causal, mask=keep, key_mask=key_mask, softmax_scale=scaling,
                             out_dtype=in_dtype)
     return out.transpose(1, 2), None       # [B,H,S,D] view of a [B,S,H,D] buffer -> contiguous [B,S,H,D]

@@ -123,6 +123,9 @@ _ARANGE1 = {}
 
 def _mask_bound(km: torch.Tensor) -> torch.Tensor:
     """int32 [B]: 1 + the index of the last non-zero byte of every row of a [B, Sk] uint8 mask (0 for an empty row)."""
+    if km.is_cuda and torch.cuda.is_current_stream_capturing():     # nothing allocated inside a graph capture is kept across calls
+        idx = torch.arange(1, km.shape[1] + 1, dtype=torch.int32, device=km.device)
+        return (idx * (km != 0)).amax(dim=1).to(torch.int32)
     key = (km.shape[1], str(km.device))
     with _SEQLENS_LOCK:
         idx = _ARANGE1.get(key)
@@ -455,3 +458,83 @@ def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=Non
     """Autograd-aware attention on ``[B,H,S,D]`` bf16/fp16 operands: forward + backward on the HIP kernels.
     ``return_weights=True`` -> ``(out, weights)``; the weights are detached (no gradient flows through them)."""
     return _FA3Function.apply(q, k, v, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype, bool(return_weights), weights_dtype)
+
+
+def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
+               key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
+               out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
+               out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Decode attention over a KV cache (``pfa_fa3_decode``): a few new query rows per batch against the cached keys.  Inference only.
+
+    q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
+    k_cache / v_cache: ``[B,Hkv,Smax,D]``-shaped views, H a multiple of Hkv (a flash-attn ``[B,Smax,Hkv,D]`` buffer is passed as
+    ``.transpose(1, 2)``; a slice of a larger preallocated cache is just a view).  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of
+    valid keys per batch.  key_mask: optional ``[B,Smax]`` (0 / False = masked); given alone, each batch's length is derived from it
+    on the device, so a static cache's unfilled tail is never read.  ``causal`` is bottom-right aligned: row i sees key j iff
+    j <= len_b - Sq + i (for Sq = 1 it changes nothing).  Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.
+    No host synchronisation and no cached allocation: capturable in ``torch.cuda.graph``."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    B, H, Sq, D = q.shape
+    Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+    if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != (B, Hkv, Smax, D) or Hkv < 1 or H % Hkv:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise ValueError("q, k_cache, v_cache must share dtype bf16 or fp16")
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda) or k_cache.device != q.device or v_cache.device != q.device:
+        raise ValueError("pfa_fa3_decode needs device tensors on one device (there is no CPU path)")
+    odt = q.dtype if out_dtype is None else out_dtype
+    if odt not in (q.dtype, torch.float32):
+        raise ValueError("output dtype must be the input dtype or fp32")
+    if out is None:
+        out = torch.empty((B, Sq, H, D), dtype=odt, device=q.device).permute(0, 2, 1, 3)
+    elif out.shape != (B, H, Sq, D) or out.dtype != odt or out.device != q.device:
+        raise ValueError("out must be a [B, H, Sq, D] tensor of the output dtype on the operands' device")
+    qs, ks, vs, os_ = (_bhsd_strides(t) for t in (q, k_cache, v_cache, out))
+    a = _capi.make_decode_args(
+        q=q.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(), o=out.data_ptr(),
+        q_stride_b=qs[0], q_stride_h=qs[1], q_stride_s=qs[2], k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2],
+        v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2], o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2],
+        B=B, H=H, Hkv=Hkv, Sq=Sq, Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt], causal=1 if causal else 0,
+        softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
+        device_id=q.device.index if q.device.index is not None else torch.cuda.current_device())
+    keep = []
+    if key_mask is not None:
+        if key_mask.shape != (B, Smax):
+            raise ValueError("key_mask must be [B, Smax]")
+        if not key_mask.is_cuda or key_mask.device != q.device:
+            raise ValueError("key_mask must live on the operands' device")
+        km = key_mask.view(torch.uint8) if key_mask.dtype in (torch.bool, torch.uint8) else (key_mask != 0).view(torch.uint8)
+        if km.stride(1) != 1:
+            km = km.contiguous()
+        a.key_mask, a.key_mask_stride_b = km.data_ptr(), km.stride(0)
+        keep.append(km)
+        if cache_seqlens is None:
+            cache_seqlens = _mask_bound(km)
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or not cache_seqlens.is_cuda or cache_seqlens.device != q.device:
+            raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
+        if cache_seqlens.shape != (B,):
+            raise ValueError("cache_seqlens must have B entries")
+        sl = cache_seqlens if cache_seqlens.dtype == torch.int32 and cache_seqlens.is_contiguous() else \
+            cache_seqlens.to(torch.int32).contiguous()
+        a.cache_seqlens = sl.data_ptr()
+        keep.append(sl)
+    lse = None
+    if return_lse:
+        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+        a.lse = lse.data_ptr()
+    lib = _capi.load()
+    ws_bytes = int(lib.pfa_fa3_decode_workspace_bytes(C.byref(a)))
+    if ws_bytes:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        keep.append(ws)
+    stream = torch.cuda.current_stream(q.device)
+    st = lib.pfa_fa3_decode(C.byref(a), C.c_void_p(stream.cuda_stream))
+    if st in (-1, -3, -4, -5, -6, -7, -10):
+        raise ValueError(f"pfa_fa3_decode: {_capi.status_string(st)}")
+    _capi.check_status(st)
+    for t in keep:   # tensors made here must outlive the enqueued kernels
+        t.record_stream(stream)
+    return out, lse

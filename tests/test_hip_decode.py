@@ -1,0 +1,292 @@
+"""GPU tests of the split-KV decode path (``ops.fa3_decode`` / ``pfa_fa3_decode``) against an fp64 reference built here, with the
+bottom-right causal cut, ragged cache lengths and key masks spelled out explicitly; and the Hugging Face generation loop through it.
+
+Tolerance: the per-element bound of the fast variant (tests/test_hip_parity.py's docstring) for a 16-bit output,
+|err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6, and 1e-3 max-abs for an fp32 output."""
+
+from __future__ import annotations
+
+import copy
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
+
+
+def _dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+def _reference(q, k, v, seqlens, key_mask, causal, scale):
+    """fp64 on the GPU: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2)."""
+    B, H, Sq, D = q.shape
+    Hkv, Smax = k.shape[1], k.shape[2]
+    g = H // Hkv
+    kd = k.double().repeat_interleave(g, dim=1)
+    vd = v.double().repeat_interleave(g, dim=1)
+    s = (q.double() @ kd.transpose(-1, -2)) * scale                                   # [B,H,Sq,Smax]
+    j = torch.arange(Smax, device=q.device)
+    i = torch.arange(Sq, device=q.device)
+    L = seqlens.to(q.device).long() if seqlens is not None else torch.full((B,), Smax, device=q.device)
+    vis = (j[None, None, :] < L[:, None, None]).expand(B, Sq, Smax)
+    if causal:
+        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])   # bottom-right, per batch
+    if key_mask is not None:
+        vis = vis & key_mask.to(q.device).bool()[:, None, :]
+    s = s.masked_fill(~vis[:, None], float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    safe = torch.where(l > 0, l, torch.ones_like(l))
+    pn = p / safe
+    o = pn @ vd
+    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
+    return o, lse, pn.norm(dim=-1, keepdim=True)
+
+
+def _check(got, ref, pnorm, vmax, dtype):
+    err = (got.double() - ref).abs()
+    if got.dtype == torch.float32:
+        assert float(err.max()) <= 1e-3, float(err.max())
+        return
+    eps = EPS[dtype]
+    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
+    worst = float((err - bound).max())
+    assert worst <= 0, f"max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
+
+
+def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed, layout="bhsd"):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    dev = _dev()
+    q = torch.randn(B, Sq, H, D, generator=g).to(dev, dtype).permute(0, 2, 1, 3)
+    if layout == "bshd":        # flash-attn style [B, Smax, Hkv, D] buffer, passed as a [B, Hkv, Smax, D] view
+        k = torch.randn(B, Smax, Hkv, D, generator=g).to(dev, dtype).transpose(1, 2)
+        v = torch.randn(B, Smax, Hkv, D, generator=g).to(dev, dtype).transpose(1, 2)
+    elif layout == "slice":     # the first Smax positions of a larger preallocated [B, Hkv, Smax + 96, D] cache
+        k = torch.randn(B, Hkv, Smax + 96, D, generator=g).to(dev, dtype)[:, :, :Smax]
+        v = torch.randn(B, Hkv, Smax + 96, D, generator=g).to(dev, dtype)[:, :, :Smax]
+    else:
+        k = torch.randn(B, Hkv, Smax, D, generator=g).to(dev, dtype)
+        v = torch.randn(B, Hkv, Smax, D, generator=g).to(dev, dtype)
+    return q, k, v
+
+
+def _run_and_check(q, k, v, *, seqlens=None, key_mask=None, causal=True, out_dtype=None, check_lse=True):
+    from photonic_flash_attention_amd import ops
+    D = q.shape[-1]
+    scale = D ** -0.5
+    o, lse = ops.fa3_decode(q, k, v, cache_seqlens=seqlens, key_mask=key_mask, causal=causal, out_dtype=out_dtype, return_lse=True)
+    torch.cuda.synchronize()
+    ref, rlse, pn = _reference(q, k, v, seqlens, key_mask, causal, scale)
+    _check(o, ref, pn, float(v.abs().max()), q.dtype)
+    if check_lse:
+        fin = torch.isfinite(rlse)
+        assert torch.equal(torch.isfinite(lse), fin)
+        assert bool((o[~fin[..., None].expand_as(o)] == 0).all())
+        if bool(fin.any()):
+            assert float((lse.double() - rlse)[fin].abs().max()) <= 2e-3
+    return o, lse
+
+
+@pytest.mark.parametrize("H,Hkv", [(32, 8), (8, 8), (28, 4), (64, 1)])
+@pytest.mark.parametrize("D", [64, 128])
+def test_single_token_head_groups(H, Hkv, D):
+    for dtype, Smax in ((torch.bfloat16, 4097), (torch.float16, 65)):
+        q, k, v = _problem(2, H, Hkv, 1, Smax, D, dtype, seed=H * 7 + Hkv + D)
+        sl = torch.tensor([Smax, Smax // 2 + 1], dtype=torch.int32, device=q.device)
+        _run_and_check(q, k, v, seqlens=sl)
+
+
+@pytest.mark.parametrize("Smax", [1, 63, 64, 65, 4097, 32768])
+def test_cache_lengths_and_ragged_batches(Smax):
+    q, k, v = _problem(4, 32, 8, 1, Smax, 128, torch.bfloat16, seed=Smax)
+    _run_and_check(q, k, v)
+    sl = torch.tensor([0, Smax, max(Smax // 3, 1), max(Smax - 1, 0)], dtype=torch.int32, device=q.device)
+    _run_and_check(q, k, v, seqlens=sl)
+    _run_and_check(q, k, v, seqlens=sl, out_dtype=torch.float32)
+    if Smax >= 64:
+        q64, k64, v64 = _problem(3, 16, 16, 1, Smax, 64, torch.float16, seed=Smax + 1)
+        _run_and_check(q64, k64, v64, seqlens=torch.tensor([Smax, 5, Smax // 2], dtype=torch.int32, device=q.device))
+
+
+@pytest.mark.parametrize("Sq", [2, 4, 8])
+@pytest.mark.parametrize("D", [64, 128])
+def test_bottom_right_causal_multi_row(Sq, D):
+    q, k, v = _problem(3, 16, 4, Sq, 3000, D, torch.bfloat16, seed=Sq * 11 + D)
+    sl = torch.tensor([3000, 1234, Sq - 1], dtype=torch.int32, device=q.device)     # the last batch has rows that see nothing
+    _run_and_check(q, k, v, seqlens=sl, causal=True)
+    _run_and_check(q, k, v, seqlens=sl, causal=False)
+    _run_and_check(q, k, v, seqlens=sl, causal=True, out_dtype=torch.float32)
+
+
+def test_left_padding_key_mask_with_lengths():
+    B, Smax = 3, 2100
+    q, k, v = _problem(B, 32, 8, 1, Smax, 128, torch.bfloat16, seed=5)
+    dev = q.device
+    sl = torch.tensor([2100, 1500, 700], dtype=torch.int32, device=dev)
+    km = torch.ones(B, Smax, dtype=torch.bool, device=dev)
+    km[1, :300] = False           # left padding
+    km[2, :650] = False
+    km[0, 1000:1100] = False      # a hole
+    _run_and_check(q, k, v, seqlens=sl, key_mask=km)
+    # a key mask alone: each batch's length comes from its last visible key (the masked tail is never read)
+    km2 = km.clone()
+    km2[0, 1800:] = False
+    _run_and_check(q, k, v, key_mask=km2)
+    # a batch whose mask hides everything
+    km2[2] = False
+    _run_and_check(q, k, v, key_mask=km2)
+
+
+@pytest.mark.parametrize("layout", ["bshd", "slice"])
+def test_cache_layouts(layout):
+    q, k, v = _problem(2, 32, 8, 4, 5000, 128, torch.bfloat16, seed=9, layout=layout)
+    sl = torch.tensor([5000, 2222], dtype=torch.int32, device=q.device)
+    _run_and_check(q, k, v, seqlens=sl)
+
+
+def test_outputs_are_bitwise_reproducible():
+    from photonic_flash_attention_amd import ops
+    q, k, v = _problem(2, 32, 8, 1, 32768, 128, torch.bfloat16, seed=3)
+    sl = torch.tensor([32768, 20000], dtype=torch.int32, device=q.device)
+    o1, l1 = ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
+    o2, l2 = ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
+    torch.cuda.synchronize()
+    assert torch.equal(o1, o2) and torch.equal(l1, l2)
+
+
+def test_agrees_with_the_forward_on_a_single_token():
+    from photonic_flash_attention_amd import ops
+    q, k, v = _problem(2, 32, 8, 1, 3000, 128, torch.bfloat16, seed=4)
+    km = torch.ones(2, 3000, dtype=torch.bool, device=q.device)
+    km[1, :100] = False
+    km[1, 2500:] = False
+    od, _ = ops.fa3_decode(q, k, v, key_mask=km, causal=False)
+    of, _ = ops.fa3_forward(q, k, v, key_mask=km)
+    torch.cuda.synchronize()
+    ref, _, pn = _reference(q, k, v, None, km, False, 128 ** -0.5)
+    eps = EPS[torch.bfloat16]
+    bound = 2 * (eps * ref.abs() + 3 * eps * float(v.abs().max()) * pn + 2e-6)
+    assert float(((od.double() - of.double()).abs() - bound).max()) <= 0
+
+
+def test_graph_capture_replays_with_new_lengths_and_cache():
+    from photonic_flash_attention_amd import ops
+    q, k, v = _problem(2, 32, 8, 1, 4096, 128, torch.bfloat16, seed=6)
+    dev = q.device
+    sl = torch.tensor([4096, 1000], dtype=torch.int32, device=dev)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        o, lse = ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
+    graph.replay()
+    torch.cuda.synchronize()
+    ref, _, pn = _reference(q, k, v, sl, None, True, 128 ** -0.5)
+    _check(o, ref, pn, float(v.abs().max()), q.dtype)
+    # new lengths and new cache contents, written in place
+    sl.copy_(torch.tensor([77, 3333], dtype=torch.int32))
+    g = torch.Generator(device="cpu").manual_seed(60)
+    k.copy_(torch.randn(k.shape, generator=g).to(dev, k.dtype))
+    v.copy_(torch.randn(v.shape, generator=g).to(dev, v.dtype))
+    graph.replay()
+    torch.cuda.synchronize()
+    ref, rlse, pn = _reference(q, k, v, sl, None, True, 128 ** -0.5)
+    _check(o, ref, pn, float(v.abs().max()), q.dtype)
+    assert float((lse.double() - rlse).abs().max()) <= 2e-3
+
+
+# --- Hugging Face generation ---------------------------------------------------------------------------------------------------------
+
+def _llama(transformers):
+    torch.manual_seed(1)
+    cfg = transformers.LlamaConfig(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, num_hidden_layers=2,
+                                   intermediate_size=512, vocab_size=500, max_position_embeddings=1024)
+    ref = transformers.LlamaForCausalLM(cfg).to(_dev()).eval()
+    ref.config._attn_implementation = "sdpa"
+    from photonic_flash_attention_amd.integration.pytorch.hf import convert_hf_model
+    return cfg, ref, convert_hf_model(copy.deepcopy(ref))
+
+
+@pytest.fixture
+def decode_spy(monkeypatch):
+    from photonic_flash_attention_amd import ops
+    calls = []
+    real = ops.fa3_decode
+
+    def spy(*a, **kw):
+        calls.append(a[0].shape)
+        return real(*a, **kw)
+    monkeypatch.setattr(ops, "fa3_decode", spy)
+    return calls
+
+
+def _teacher_forced(transformers, ref, conv, ids, attention_mask, make_cache, prefill, steps):
+    caches = [make_cache(), make_cache()]
+    worst = 0.0
+    with torch.no_grad():
+        am = attention_mask[:, :prefill] if attention_mask is not None else None
+        outs = [m(input_ids=ids[:, :prefill], attention_mask=am, past_key_values=c, use_cache=True) for m, c in zip((ref, conv), caches)]
+        worst = max(worst, float((outs[1].logits - outs[0].logits).abs().max()))
+        for t in range(prefill, prefill + steps):
+            am = attention_mask[:, :t + 1] if attention_mask is not None else None
+            outs = [m(input_ids=ids[:, t:t + 1], attention_mask=am, past_key_values=c, use_cache=True) for m, c in zip((ref, conv), caches)]
+            assert bool(torch.isfinite(outs[1].logits).all())
+            worst = max(worst, float((outs[1].logits - outs[0].logits).abs().max()))
+    return worst
+
+
+def test_hf_cached_decode_steps_reach_the_decode_kernel(decode_spy):
+    transformers = pytest.importorskip("transformers")
+    cfg, ref, conv = _llama(transformers)
+    ids = torch.randint(0, 500, (2, 300), device=_dev())
+    err = _teacher_forced(transformers, ref, conv, ids, None, lambda: transformers.DynamicCache(config=cfg), 284, 16)
+    print(f"DynamicCache, 16 steps: logits max-abs vs sdpa {err:.3e}")
+    assert err <= 5e-2
+    assert len(decode_spy) == 16 * cfg.num_hidden_layers
+
+
+def test_hf_left_padded_batch_decode(decode_spy):
+    transformers = pytest.importorskip("transformers")
+    cfg, ref, conv = _llama(transformers)
+    ids = torch.randint(0, 500, (2, 200), device=_dev())
+    am = torch.ones(2, 200, dtype=torch.long, device=ids.device)
+    am[1, :37] = 0
+    err = _teacher_forced(transformers, ref, conv, ids, am, lambda: transformers.DynamicCache(config=cfg), 184, 16)
+    print(f"left-padded DynamicCache, 16 steps: logits max-abs vs sdpa {err:.3e}")
+    assert err <= 5e-2
+    assert len(decode_spy) == 16 * cfg.num_hidden_layers
+
+
+def test_hf_static_cache_decode(decode_spy):
+    transformers = pytest.importorskip("transformers")
+    if not hasattr(transformers, "StaticCache"):
+        pytest.skip("this transformers has no StaticCache")
+    cfg, ref, conv = _llama(transformers)
+    ids = torch.randint(0, 500, (2, 150), device=_dev())
+    am = torch.ones(2, 150, dtype=torch.long, device=ids.device)
+    am[0, :11] = 0
+    err = _teacher_forced(transformers, ref, conv, ids, am,
+                          lambda: transformers.StaticCache(config=cfg, max_cache_len=256), 134, 16)
+    print(f"StaticCache, 16 steps: logits max-abs vs sdpa {err:.3e}")
+    assert err <= 5e-2
+    assert len(decode_spy) == 16 * cfg.num_hidden_layers
+
+
+def test_hf_greedy_generate(decode_spy):
+    transformers = pytest.importorskip("transformers")
+    cfg, ref, conv = _llama(transformers)
+    ids = torch.randint(0, 500, (2, 40), device=_dev())
+    with torch.no_grad():
+        out = conv.generate(input_ids=ids, attention_mask=torch.ones_like(ids), max_new_tokens=8, do_sample=False)
+    assert out.shape == (2, 48)
+    assert len(decode_spy) > 0

@@ -1,0 +1,181 @@
+"""Decode step (one query row per batch against a KV cache) on the MI355X: ``ops.fa3_decode`` against today's path
+(``ops.fa3_forward`` with Sq = 1 and a key mask) and ``torch.nn.functional.scaled_dot_product_attention``.
+
+Timing cycles through enough distinct caches (>= 768 MiB in all, like a model's layers) that the 256 MiB Infinity Cache cannot
+serve them; the three paths are timed alternately with device events.  ``--warm`` adds the single-cache (cache-resident) figure,
+labelled as such.  Rate = K + V cache bytes / time, and its share of the ~6.3 TB/s achievable HBM read rate.  Also prints the
+host (Python + ctypes) cost of one call and the time of one graph replay.
+
+    python tools/decode_bench.py [--reps 5] [--quick] [--warm] [--json out.jsonl]
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from photonic_flash_attention_amd import _capi, ops  # noqa: E402
+
+HBM_TBS = 6.3
+MIN_POOL = 768 << 20
+MAX_CACHE = 12 << 30
+
+
+def _caches(B, Hkv, S, D, n, dev):
+    return [(torch.randn(B, Hkv, S, D, device=dev, dtype=torch.bfloat16), torch.randn(B, Hkv, S, D, device=dev, dtype=torch.bfloat16))
+            for _ in range(n)]
+
+
+def bench_shape(B, H, Hkv, D, S, reps, warm, dev):
+    cache_bytes = 2 * B * Hkv * S * D * 2
+    if cache_bytes > MAX_CACHE:
+        return None
+    n = max(1, math.ceil(MIN_POOL / cache_bytes))
+    pool = _caches(B, Hkv, S, D, n, dev)
+    q = torch.randn(B, H, 1, D, device=dev, dtype=torch.bfloat16)
+    km = torch.ones(B, S, dtype=torch.bool, device=dev)
+    g = H // Hkv
+
+    def new(k, v):
+        ops.fa3_decode(q, k, v, key_mask=km)
+
+    def old(k, v):
+        ops.fa3_forward(q, k, v, key_mask=km)
+
+    def sdpa(k, v):
+        torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=km[:, None, None, :], enable_gqa=g > 1)
+
+    paths = {"fa3_decode": new, "fa3_forward": old, "sdpa": sdpa}
+    for f in paths.values():          # warm-up: code objects, algorithm choices, allocator
+        for k, v in pool[:2]:
+            f(k, v)
+    torch.cuda.synchronize()
+    times = {name: [] for name in paths}
+    for _ in range(reps):
+        for name, f in paths.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k, v in pool:
+                f(k, v)
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / n)
+    res = dict(B=B, H=H, Hkv=Hkv, D=D, Skv=S, cache_MB=round(cache_bytes / 1e6, 2), n_caches=n)
+    a = _capi.make_decode_args(B=B, H=H, Hkv=Hkv, Sq=1, Smax=S, D=D, q=1 << 12, k_cache=1 << 12, v_cache=1 << 12, o=1 << 12,
+                               q_stride_b=H * D, q_stride_h=D, q_stride_s=H * D, k_stride_b=Hkv * S * D, k_stride_h=S * D, k_stride_s=D,
+                               v_stride_b=Hkv * S * D, v_stride_h=S * D, v_stride_s=D, o_stride_b=H * D, o_stride_h=D, o_stride_s=H * D,
+                               dtype_in=0, dtype_out=0, softmax_scale=D ** -0.5, workspace=1 << 12, workspace_bytes=1 << 40)
+    _, wgs, nsplit = _capi.describe_decode(a)
+    res.update(workgroups=wgs, nsplit=nsplit)
+    for name, ts in times.items():
+        us = sorted(ts)[len(ts) // 2]
+        res[f"{name}_us"] = round(us, 2)
+        res[f"{name}_TBs"] = round(cache_bytes / us / 1e6, 3)
+        res[f"{name}_pct_hbm"] = round(100 * cache_bytes / us / 1e6 / HBM_TBS, 1)
+    if warm:                           # one cache, replayed back to back: cache-resident when it fits the Infinity Cache
+        k, v = pool[0]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        new(k, v)
+        e0.record()
+        for _ in range(20):
+            new(k, v)
+        e1.record()
+        e1.synchronize()
+        res["fa3_decode_warm_single_cache_us"] = round(e0.elapsed_time(e1) * 1e3 / 20, 2)
+    del pool
+    torch.cuda.empty_cache()
+    return res
+
+
+def host_cost(dev):
+    """Python + ctypes cost of one fa3_decode call (enqueue only: the GPU side is tiny), and one graph replay of it."""
+    B, H, Hkv, D, S = 1, 32, 8, 128, 4096
+    q = torch.randn(B, H, 1, D, device=dev, dtype=torch.bfloat16)
+    k = torch.randn(B, Hkv, S, D, device=dev, dtype=torch.bfloat16)
+    v = torch.randn_like(k)
+    sl = torch.full((B,), S, dtype=torch.int32, device=dev)
+    for _ in range(50):
+        ops.fa3_decode(q, k, v, cache_seqlens=sl)
+    torch.cuda.synchronize()
+    out = {}
+    for label, kw in (("host_us_per_call_seqlens", dict(cache_seqlens=sl)), ("host_us_per_call_keymask",
+                                                                              dict(key_mask=torch.ones(B, S, dtype=torch.bool, device=dev)))):
+        t0 = time.perf_counter()
+        for _ in range(500):
+            ops.fa3_decode(q, k, v, **kw)
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        out[label] = round((t1 - t0) / 500 * 1e6, 2)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        ops.fa3_decode(q, k, v, cache_seqlens=sl)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        ops.fa3_decode(q, k, v, cache_seqlens=sl)
+    graph.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(200):
+        graph.replay()
+    e1.record()
+    e1.synchronize()
+    out["graph_replay_us_per_call"] = round(e0.elapsed_time(e1) * 1e3 / 200, 2)
+    t0 = time.perf_counter()
+    for _ in range(200):
+        graph.replay()
+    out["graph_replay_host_us"] = round((time.perf_counter() - t0) / 200 * 1e6, 2)
+    torch.cuda.synchronize()
+    out["shape"] = dict(B=B, H=H, Hkv=Hkv, D=D, Skv=S)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--quick", action="store_true", help="B 1 and 8, Llama-3-8B heads only")
+    ap.add_argument("--warm", action="store_true")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "decode_bench measures on the GPU"
+    dev = torch.device("cuda:0")
+    heads = [(32, 8, 128), (64, 8, 128), (32, 32, 128), (16, 16, 64)]
+    Bs, Ss = [1, 8, 32], [4096, 32768, 131072]
+    if args.quick:
+        heads, Bs, Ss = heads[:1], [1, 8], [32768]
+    rows = []
+    hdr = f"{'B':>3} {'H':>3} {'Hkv':>3} {'D':>4} {'Skv':>7} {'MB':>8} {'split':>5} | {'decode us':>9} {'TB/s':>5} {'%':>5} | " \
+          f"{'fwd us':>9} {'TB/s':>5} | {'sdpa us':>9} {'TB/s':>5}"
+    print(hdr, flush=True)
+    for H, Hkv, D in heads:
+        for B in Bs:
+            for S in Ss:
+                r = bench_shape(B, H, Hkv, D, S, args.reps, args.warm, dev)
+                if r is None:
+                    print(f"{B:>3} {H:>3} {Hkv:>3} {D:>4} {S:>7}  skipped: one cache exceeds {MAX_CACHE >> 30} GiB", flush=True)
+                    continue
+                rows.append(r)
+                print(f"{B:>3} {H:>3} {Hkv:>3} {D:>4} {S:>7} {r['cache_MB']:>8.1f} {r['nsplit']:>5} | {r['fa3_decode_us']:>9.2f} "
+                      f"{r['fa3_decode_TBs']:>5.2f} {r['fa3_decode_pct_hbm']:>5.1f} | {r['fa3_forward_us']:>9.2f} {r['fa3_forward_TBs']:>5.2f} | "
+                      f"{r['sdpa_us']:>9.2f} {r['sdpa_TBs']:>5.2f}"
+                      + (f"   warm single cache {r['fa3_decode_warm_single_cache_us']:.2f} us" if args.warm else ""), flush=True)
+    hc = host_cost(dev)
+    print("host cost:", json.dumps(hc), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+            f.write(json.dumps({"host": hc}) + "\n")
+
+
+if __name__ == "__main__":
+    main()
