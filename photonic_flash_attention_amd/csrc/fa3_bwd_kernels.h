@@ -1,12 +1,11 @@
 // fa3_bwd_kernels.h -- Flash-Attention BACKWARD for MI355X (gfx950): dQ, dK, dV from the forward's LSE.
 //
 // The reference gets its backward from autograd through the eager forward (flash_attention_3.py:152-262;
-// tests/unit/test_flash_attention_3.py:137-160 only require that gradients exist).  Here it is three kernels
+// tests/unit/test_flash_attention_3.py:137-160 only require that gradients exist).  Here it is two kernels
 // that recompute P = exp(scale*S - LSE) tile by tile instead of storing the S x S matrices:
 //
-//   fa3_bwd_delta   delta[b,h,i] = sum_d dO[i,d] * O[i,d]                       (memory bound; since the end of round 1 the
-//                   dQ kernel computes it for its own rows and publishes it for the dK/dV kernel -- this one is not launched)
 //   fa3_bwd_dq      per 256-row Q block (8 waves x 32 rows, same geometry / LDS images / DMA as the forward):
+//                     delta[b,h,i] = sum_d dO[i,d] * O[i,d] for its own rows (published for the dK/dV kernel behind it),
 //                     S^T = K Q^T, dP^T = V dO^T, dS^T = P^T o (dP^T - delta), dQ^T += K^T dS^T
 //   fa3_bwd_dkdv    per 128-key block (4 waves x 32 keys, one wave per SIMD: K^T/V^T operand fragments and the
 //                   dK^T/dV^T accumulators of the block stay in registers), streaming Q and dO tiles:
@@ -63,30 +62,6 @@ struct BwdParams {
     float scale;           // softmax scale
     float scale_log2;      // scale * log2(e)
 };
-
-// ---------------------------------------------------------------------------------------------------------------
-// delta = rowsum(dO o O): one wave per 64 rows? -> one thread per (row, 8-element chunk), reduced in-wave.
-template <typename T, int D>
-__global__ __launch_bounds__(256) void fa3_bwd_delta_kernel(const BwdParams p) {
-    using v8 = typename Elem<T>::v8;
-    constexpr int CPR = D / 8;                       // 16-byte chunks per row
-    constexpr int ROWS_PER_BLOCK = 256 / CPR;
-    const int bh = blockIdx.y;
-    const int b = bh / p.H, hh = bh - b * p.H;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + threadIdx.x / CPR;
-    const int ch = threadIdx.x % CPR;
-    float acc = 0.f;
-    if (row < p.Sq) {
-        const T* op = (const T*)p.o + (int64_t)b * p.o_sb + (int64_t)hh * p.o_sh + (int64_t)row * p.o_ss + ch * 8;
-        const T* gp = (const T*)p.dout + (int64_t)b * p.do_sb + (int64_t)hh * p.do_sh + (int64_t)row * p.do_ss + ch * 8;
-        const v8 a = *(const v8*)op, g = *(const v8*)gp;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc += (float)a[e] * (float)g[e];
-    }
-#pragma unroll
-    for (int off = CPR / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-    if (row < p.Sq && ch == 0) p.delta[((int64_t)b * p.H + hh) * p.Sq + row] = acc;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Shared tile machinery: 64-row x D tile images (two per stage), LDS-DMA by buffer descriptor, swizzled.

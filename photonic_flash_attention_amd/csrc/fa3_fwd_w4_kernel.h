@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256, 1) void fa3_fwd_w4_kernel(const FwdParams p) {
         for (int ks = 0; ks < KS; ++ks) X.qf[ks] = *(const lds_v8*)(uintptr_t)(base + (((2 * ks + h) ^ (r & 15)) << 4));
     };
 
-    // ---- per-lane LDS read addresses (opaque: see VAR_DIET in fa3_fwd_kernel.h) ---------------------------------------------
+    // ---- per-lane LDS read addresses (opaque, as in fa3_fwd_kernel.h: hipcc otherwise re-adds their row and chunk parts every tile)
     uint32_t koff[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {

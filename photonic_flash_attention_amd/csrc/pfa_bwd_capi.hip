@@ -9,6 +9,7 @@
 
 #include "fa3_bwd_kernels.h"
 #include "fa3_bwd_f32_kernel.h"
+#include "pfa_host.h"
 
 namespace {
 
@@ -82,8 +83,7 @@ void pick_ck(bool g32, const void*& dq, const void*& dkdv) {
     dkdv = g32 ? (const void*)&pfa::fa3_bwd_dkdv_kernel<T, D, C, K, float> : (const void*)&pfa::fa3_bwd_dkdv_kernel<T, D, C, K, T>;
 }
 template <typename T, int D>
-void pick_kernels(bool causal, bool kmask, bool g32, const void*& delta, const void*& dq, const void*& dkdv) {
-    delta = (const void*)&pfa::fa3_bwd_delta_kernel<T, D>;
+void pick_kernels(bool causal, bool kmask, bool g32, const void*& dq, const void*& dkdv) {
     if (causal) kmask ? pick_ck<T, D, true, true>(g32, dq, dkdv) : pick_ck<T, D, true, false>(g32, dq, dkdv);
     else kmask ? pick_ck<T, D, false, true>(g32, dq, dkdv) : pick_ck<T, D, false, false>(g32, dq, dkdv);
 }
@@ -144,21 +144,17 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream) {
         const void* f0 = a->D == 128 ? (const void*)&pfa::fa3_bwd_f32_kernel<128, 0> : (const void*)&pfa::fa3_bwd_f32_kernel<64, 0>;
         const void* f1 = a->D == 128 ? (const void*)&pfa::fa3_bwd_f32_kernel<128, 1> : (const void*)&pfa::fa3_bwd_f32_kernel<64, 1>;
         const int lds = a->D == 128 ? pfa::f32_bwd_lds_bytes<128>() : pfa::f32_bwd_lds_bytes<64>();
-        int prev = -1;
-        hipError_t e = hipGetDevice(&prev);
-        if (e == hipSuccess && prev != a->device_id) e = hipSetDevice(a->device_id);
-        if (e != hipSuccess) { (void)hipGetLastError(); return PFA_ERR_DEVICE; }
+        const pfa::DeviceScope dev(a->device_id);
+        if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
         if (lds > 64 * 1024) {
             (void)hipFuncSetAttribute(f0, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             (void)hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         }
         void* kargs[] = {&p};
-        e = hipLaunchKernel(f0, dim3((unsigned)(((a->Sq + pfa::F32B_BM - 1) / pfa::F32B_BM) * a->B * a->H)), dim3(256), kargs, (size_t)lds, (hipStream_t)stream);
+        hipError_t e = hipLaunchKernel(f0, dim3((unsigned)(((a->Sq + pfa::F32B_BM - 1) / pfa::F32B_BM) * a->B * a->H)), dim3(256), kargs, (size_t)lds, (hipStream_t)stream);
         if (e == hipSuccess)
             e = hipLaunchKernel(f1, dim3((unsigned)(((a->Sk + pfa::F32B_BM - 1) / pfa::F32B_BM) * a->B * a->H)), dim3(256), kargs, (size_t)lds, (hipStream_t)stream);
-        if (prev != a->device_id) (void)hipSetDevice(prev);
-        if (e != hipSuccess) { (void)hipGetLastError(); return PFA_ERR_LAUNCH; }
-        return PFA_OK;
+        return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
     }
     pfa::BwdParams p;
     p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.dout = a->dout; p.lse = a->lse; p.delta = a->delta;
@@ -199,43 +195,26 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream) {
         p.crg_sh = mw.Hm > 1 ? mw.nkb : 0; p.crg_sb = mw.Bm > 1 ? (int64_t)mw.Hm * mw.nkb : 0;
     }
 
-    const void *kdelta, *kdq, *kdkdv;
+    const void *kdq, *kdkdv;
     const bool causal = a->causal != 0, g32 = a->dtype_grad == PFA_DTYPE_FP32, kmask = p.mask != nullptr;     // (not for key-only masks)
     if (a->dtype == PFA_DTYPE_BF16) {
-        if (a->D == 128) pick_kernels<__bf16, 128>(causal, kmask, g32, kdelta, kdq, kdkdv);
-        else pick_kernels<__bf16, 64>(causal, kmask, g32, kdelta, kdq, kdkdv);
+        if (a->D == 128) pick_kernels<__bf16, 128>(causal, kmask, g32, kdq, kdkdv);
+        else pick_kernels<__bf16, 64>(causal, kmask, g32, kdq, kdkdv);
     } else {
-        if (a->D == 128) pick_kernels<_Float16, 128>(causal, kmask, g32, kdelta, kdq, kdkdv);
-        else pick_kernels<_Float16, 64>(causal, kmask, g32, kdelta, kdq, kdkdv);
+        if (a->D == 128) pick_kernels<_Float16, 128>(causal, kmask, g32, kdq, kdkdv);
+        else pick_kernels<_Float16, 64>(causal, kmask, g32, kdq, kdkdv);
     }
-    int prev = -1;
-    hipError_t e = hipGetDevice(&prev);
-    if (e == hipSuccess && prev != a->device_id) e = hipSetDevice(a->device_id);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
+    const pfa::DeviceScope dev(a->device_id);
+    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
     const int lds = 2 * 2 * pfa::BLOCK_N * a->D * 2;
     const int BH = a->B * a->H;
     void* args[] = {&p};
-    const int rows_per_block = 256 / (a->D / 8);
-    // (the dQ kernel computes delta = rowsum(dO o O) for its own rows and publishes it for the dK/dV kernel behind it;
-    //  fa3_bwd_delta_kernel is kept for reference / diagnostics but is no longer launched)
-    (void)kdelta;
-    (void)rows_per_block;
+    // (the dQ kernel computes delta = rowsum(dO o O) for its own rows and publishes it for the dK/dV kernel behind it)
     if (use_words) {
         char* ws = (char*)a->mask_workspace;
         const dim3 bh((unsigned)1, (unsigned)1, (unsigned)(mw.Bm * mw.Hm));
-        const bool wide = a->mask_stride_k == 1 && a->Sk % 16 == 0 && a->mask_stride_b % 16 == 0 && a->mask_stride_h % 16 == 0 &&
-                          a->mask_stride_q % 16 == 0 && ((uintptr_t)a->mask & 15) == 0;
-        if (wide)
-            hipLaunchKernelGGL(pfa::fa3_maskbits16_kernel<0>, dim3((unsigned)(((mw.nt + 15) / 16 + 3) / 4), (unsigned)mw.Qm, bh.z), dim3(256), 0,
-                               (hipStream_t)stream, a->mask, a->mask_stride_b, a->mask_stride_h, a->mask_stride_q, mw.Hm, a->Sk, mw.nt,
-                               (unsigned long long*)ws, p.mw_sb, p.mw_sh, p.mw_sq);
-        else
-            hipLaunchKernelGGL(pfa::fa3_maskbits_kernel<0>, dim3((unsigned)((mw.nt + 3) / 4), (unsigned)mw.Qm, bh.z), dim3(256), 0, (hipStream_t)stream,
-                               a->mask, a->mask_stride_b, a->mask_stride_h, a->mask_stride_q, a->mask_stride_k, mw.Hm, a->Sk, mw.nt,
-                               (unsigned long long*)ws, p.mw_sb, p.mw_sh, p.mw_sq);
+        pfa::launch_mask_words(a->mask, a->mask_stride_b, a->mask_stride_h, a->mask_stride_q, a->mask_stride_k, mw.Bm, mw.Hm, mw.Qm, a->Sk, mw.nt,
+                               (unsigned long long*)ws, p.mw_sb, p.mw_sh, p.mw_sq, (hipStream_t)stream);
         hipLaunchKernelGGL(pfa::fa3_maskrange_kernel<256>, dim3((unsigned)(mw.ngq * pfa::RANGE_PARTS), bh.z), dim3(256), 0, (hipStream_t)stream,
                            (const unsigned long long*)ws, p.mw_sb, p.mw_sh, p.mw_sq, mw.Hm, mw.Qm, mw.nt, (int*)(ws + mw.roww), mw.ngq);
         // (the transposed words always have the problem's own row count: a mask without a row dimension is the same word in every row)
@@ -245,25 +224,17 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream) {
         hipLaunchKernelGGL(pfa::fa3_maskrange_kernel<128>, dim3((unsigned)(mw.nkb * pfa::RANGE_PARTS), bh.z), dim3(256), 0, (hipStream_t)stream,
                            (const unsigned long long*)(ws + mw.roww + mw.rowr), (int64_t)mw.Hm * a->Sk * mw.ntq, (int64_t)a->Sk * mw.ntq,
                            (int64_t)mw.ntq, mw.Hm, a->Sk, mw.ntq, (int*)(ws + mw.roww + mw.rowr + mw.colw), mw.nkb);
-        if (hipGetLastError() != hipSuccess) {
-            if (prev != a->device_id) (void)hipSetDevice(prev);
-            return PFA_ERR_LAUNCH;
-        }
+        if (hipGetLastError() != hipSuccess) return PFA_ERR_LAUNCH;
     }
     p.nblk = (a->Sq + 255) / 256;
-    e = hipLaunchKernel(kdq, dim3((unsigned)(p.nblk * BH)), dim3(512), args, (size_t)lds, (hipStream_t)stream);
+    hipError_t e = hipLaunchKernel(kdq, dim3((unsigned)(p.nblk * BH)), dim3(512), args, (size_t)lds, (hipStream_t)stream);
     if (e == hipSuccess) {
         p.nblk = (a->Sk + 127) / 128;
         if (lds + 1024 > 64 * 1024)   // tile stages + the per-row constants exceed the default 64 KiB dynamic-LDS limit
             (void)hipFuncSetAttribute(kdkdv, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 1024);
         e = hipLaunchKernel(kdkdv, dim3((unsigned)(p.nblk * (BH / p.kv_group))), dim3(256), args, (size_t)lds + 1024, (hipStream_t)stream);   // a workgroup per key block and K/V head
     }
-    if (prev != a->device_id) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return PFA_ERR_LAUNCH;
-    }
-    return PFA_OK;
+    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include "fa3_fwd_kernel.h"
 #include "fa3_weights_kernel.h"
 #include "fa3_fwd_f32_kernel.h"
+#include "pfa_host.h"
 #include "pfa_p4.h"
 
 namespace pfa { const void* w4_kernel(int dtype, bool causal, bool out32); }   // pfa_w4.hip
@@ -31,24 +32,25 @@ struct Variant {
     int p4_grid = 0;
 };
 
-template <typename T, int D, bool C, bool S, bool K, int VAR, typename OT>
+// The 8-wave kernel's names end in _v8269: the schedule-flag word of the round-1 build, kept because tools and logs match on the names.
+constexpr int kFwdNameTag = 8269;
+
+template <typename T, int D, bool C, bool S, bool K, typename OT>
 Variant mk(const char* tn, const char* on) {
     Variant v;
-    v.fn = (const void*)&pfa::fa3_fwd_kernel<T, D, C, S, K, VAR, OT>;
+    v.fn = (const void*)&pfa::fa3_fwd_kernel<T, D, C, S, K, OT>;
     snprintf(v.name, sizeof(v.name), "fa3_fwd_%s_d%d_%s%s%s_%s_v%d", tn, D, C ? "causal" : "full", S ? "_splitp" : "",
-             K ? "_kmask" : "", on, VAR);
-    v.lds_bytes = ((VAR & pfa::VAR_STAGE2) ? 4 : 2) * 2 * pfa::BLOCK_N * D * 2;
-    if (VAR & pfa::VAR_RING3) v.lds_bytes = 3 * 2 * pfa::BLOCK_N * D * 2;
-    if (VAR & pfa::VAR_STAGGER) v.lds_bytes = 5 * pfa::BLOCK_N * D * 2;   // K ring 2 + V ring 3
-    v.nthreads = ((VAR & pfa::VAR_NW4) ? 4 : 8) * 64;
-    v.block_m = v.nthreads / 2;
+             K ? "_kmask" : "", on, kFwdNameTag);
+    v.lds_bytes = 2 * 2 * pfa::BLOCK_N * D * 2;      // two buffers of a K and a V tile image
+    v.nthreads = pfa::FWD_THREADS;
+    v.block_m = pfa::FWD_BLOCK_M;
     return v;
 }
 
-// Production variants: every (dtype, D, causal, split, kmask, out) at VAR_DEFAULT.
+// The 8-wave kernel for every (dtype, D, causal, split, kmask, out).
 template <typename T, int D, bool C, bool S, bool K>
 Variant by_out(bool out32, const char* tn) {
-    return out32 ? mk<T, D, C, S, K, pfa::VAR_DEFAULT, float>(tn, "o32") : mk<T, D, C, S, K, pfa::VAR_DEFAULT, T>(tn, "o16");
+    return out32 ? mk<T, D, C, S, K, float>(tn, "o32") : mk<T, D, C, S, K, T>(tn, "o16");
 }
 template <typename T, int D, bool C, bool S>
 Variant by_kmask(bool kmask, bool out32, const char* tn) {
@@ -227,11 +229,7 @@ int pfa_last_hip_error(void) { return g_last_hip_error; }
 int pfa_device_supported(int device_id) {
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device_id);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
+    if (pfa::hip_failed(e)) return PFA_ERR_DEVICE;
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return 0;
     int herr = 0;                   // load the assembly kernels' code object now: no later call (or graph capture) has to
     if (pfa::p4_prepare(device_id, &herr) != PFA_OK) g_last_hip_error = herr;     // (the HIP kernels still serve the device)
@@ -278,15 +276,8 @@ static MaskBits mask_bits(const pfa_fa3_args* a) {
 }
 
 static bool launch_mask_bits(const MaskBits& mb, const pfa_fa3_args* a, void* stream) {
-    const bool wide = mb.sk == 1 && a->Sk % 16 == 0 && mb.sb % 16 == 0 && mb.sh % 16 == 0 && mb.sq % 16 == 0 && ((uintptr_t)mb.src & 15) == 0;
-    if (wide)       // keys contiguous and 16-byte aligned: 16 mask bytes per lane
-        hipLaunchKernelGGL(pfa::fa3_maskbits16_kernel<0>, dim3((unsigned)(((mb.nt + 15) / 16 + 3) / 4), (unsigned)mb.Qm, (unsigned)(mb.Bm * mb.Hm)),
-                           dim3(256), 0, (hipStream_t)stream, mb.src, mb.sb, mb.sh, mb.sq, mb.Hm, a->Sk, mb.nt, (unsigned long long*)a->workspace,
-                           mb.ob, mb.oh, mb.oq);
-    else
-        hipLaunchKernelGGL(pfa::fa3_maskbits_kernel<0>, dim3((unsigned)((mb.nt + 3) / 4), (unsigned)mb.Qm, (unsigned)(mb.Bm * mb.Hm)), dim3(256), 0,
-                           (hipStream_t)stream, mb.src, mb.sb, mb.sh, mb.sq, mb.sk, mb.Hm, a->Sk, mb.nt, (unsigned long long*)a->workspace,
-                           mb.ob, mb.oh, mb.oq);
+    pfa::launch_mask_words(mb.src, mb.sb, mb.sh, mb.sq, mb.sk, mb.Bm, mb.Hm, mb.Qm, a->Sk, mb.nt, (unsigned long long*)a->workspace, mb.ob, mb.oh,
+                           mb.oq, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return false;
     hipLaunchKernelGGL(pfa::fa3_maskrange_kernel<256>, dim3((unsigned)(mb.ngran * pfa::RANGE_PARTS), (unsigned)(mb.Bm * mb.Hm)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned long long*)a->workspace, mb.ob, mb.oh, mb.oq, mb.Hm, mb.Qm, mb.nt,
@@ -319,11 +310,7 @@ static int launch_f32(const pfa_fa3_args* a, void* stream) {
     pfa::F32Params p;
     p.q = (const float*)a->q; p.k = (const float*)a->k; p.v = (const float*)a->v; p.o = (float*)a->o;
     p.lse = a->lse; p.seqlens_k = a->seqlens_k;
-    if (a->mask) {
-        p.mask = a->mask; p.m_sb = a->mask_stride_b; p.m_sh = a->mask_stride_h; p.m_sq = a->mask_stride_q; p.m_sk = a->mask_stride_k;
-    } else {
-        p.mask = a->key_mask; p.m_sb = a->key_mask_stride_b; p.m_sh = 0; p.m_sq = 0; p.m_sk = 1;
-    }
+    pfa::fill_mask(p, a);
     p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
     p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
     p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
@@ -336,24 +323,13 @@ static int launch_f32(const pfa_fa3_args* a, void* stream) {
     p.drop_scale = a->drop_scale;
     const void* fn = a->D == 128 ? (const void*)&pfa::fa3_fwd_f32_kernel<128> : (const void*)&pfa::fa3_fwd_f32_kernel<64>;
     const int lds = a->D == 128 ? pfa::f32_lds_bytes<128>() : pfa::f32_lds_bytes<64>();
-    int prev_dev = -1;
-    hipError_t e = hipGetDevice(&prev_dev);
-    if (e == hipSuccess && prev_dev != a->device_id) e = hipSetDevice(a->device_id);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
+    const pfa::DeviceScope dev(a->device_id);
+    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     void* kargs[] = {&p};
-    e = hipLaunchKernel(fn, dim3((unsigned)(((a->Sq + pfa::F32_BM - 1) / pfa::F32_BM) * a->B * a->H)), dim3(256), kargs, (size_t)lds, (hipStream_t)stream);
-    if (prev_dev != a->device_id) (void)hipSetDevice(prev_dev);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_LAUNCH;
-    }
-    return PFA_OK;
+    const hipError_t e =
+        hipLaunchKernel(fn, dim3((unsigned)(((a->Sq + pfa::F32_BM - 1) / pfa::F32_BM) * a->B * a->H)), dim3(256), kargs, (size_t)lds, (hipStream_t)stream);
+    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
@@ -364,17 +340,13 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
     pfa::FwdParams p;
     p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o;
     p.lse = a->lse; p.seqlens_k = a->seqlens_k;
-    if (a->mask) {
-        p.mask = a->mask; p.m_sb = a->mask_stride_b; p.m_sh = a->mask_stride_h; p.m_sq = a->mask_stride_q; p.m_sk = a->mask_stride_k;
-    } else {
-        p.mask = a->key_mask; p.m_sb = a->key_mask_stride_b; p.m_sh = 0; p.m_sq = 0; p.m_sk = 1;
-    }
+    pfa::fill_mask(p, a);
     p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
     p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
     p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
     p.o_sb = a->o_stride_b; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
     p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
-    p.dbg = (unsigned long long*)a->workspace;   // only the diagnostic VAR_STAMP variant writes it
+    p.dbg = (unsigned long long*)a->workspace;   // written by diagnostic builds of the 4-wave kernel only (PFA_W4_STAMP)
     // mask + enough workspace: one word per row and tile instead of a mask byte per score (without workspace the byte path runs)
     const MaskBits mb = mask_bits(a);
     const bool use_mbits = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
@@ -411,28 +383,13 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
                                : dim3((unsigned)BH, (unsigned)p.nqblk, 1u);
     }
     void* kargs[] = {&p};
-    int prev_dev = -1;
-    hipError_t e = hipGetDevice(&prev_dev);
-    if (e == hipSuccess && prev_dev != a->device_id) e = hipSetDevice(a->device_id);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
-    if (use_mbits && !launch_mask_bits(mb, a, stream)) {
-        if (prev_dev != a->device_id) (void)hipSetDevice(prev_dev);
-        return PFA_ERR_LAUNCH;
-    }
+    const pfa::DeviceScope dev(a->device_id);
+    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
+    if (use_mbits && !launch_mask_bits(mb, a, stream)) return PFA_ERR_LAUNCH;
     if (v.lds_bytes > 64 * 1024)   // opt in to > 64 KiB of dynamic LDS (idempotent, per function)
         (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_bytes);
-    e = hipLaunchKernel(v.fn, grid, dim3(v.nthreads), kargs, (size_t)v.lds_bytes, (hipStream_t)stream);
-    if (prev_dev != a->device_id) (void)hipSetDevice(prev_dev);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_LAUNCH;
-    }
-    return PFA_OK;
+    const hipError_t e = hipLaunchKernel(v.fn, grid, dim3(v.nthreads), kargs, (size_t)v.lds_bytes, (hipStream_t)stream);
+    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_stride_b, int64_t w_stride_h,
@@ -449,11 +406,7 @@ int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_s
 
     pfa::WeightsParams p;
     p.q = a->q; p.k = a->k; p.lse = a->lse; p.w = w; p.seqlens_k = a->seqlens_k;
-    if (a->mask) {
-        p.mask = a->mask; p.m_sb = a->mask_stride_b; p.m_sh = a->mask_stride_h; p.m_sq = a->mask_stride_q; p.m_sk = a->mask_stride_k;
-    } else {
-        p.mask = a->key_mask; p.m_sb = a->key_mask_stride_b; p.m_sh = 0; p.m_sq = 0; p.m_sk = 1;
-    }
+    pfa::fill_mask(p, a);
     p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
     p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
     p.w_sb = w_stride_b; p.w_sh = w_stride_h; p.w_sq = w_stride_q;
@@ -471,27 +424,12 @@ int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_s
         fn = a->D == 128 ? weights_fn_ck<__bf16, 128>(causal, kmask, w32) : weights_fn_ck<__bf16, 64>(causal, kmask, w32);
     else
         fn = a->D == 128 ? weights_fn_ck<_Float16, 128>(causal, kmask, w32) : weights_fn_ck<_Float16, 64>(causal, kmask, w32);
-    int prev_dev = -1;
-    hipError_t e = hipGetDevice(&prev_dev);
-    if (e == hipSuccess && prev_dev != a->device_id) e = hipSetDevice(a->device_id);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
-    if (use_mbits && !launch_mask_bits(mb, a, stream)) {      // (again: the call may come without a forward before it)
-        if (prev_dev != a->device_id) (void)hipSetDevice(prev_dev);
-        return PFA_ERR_LAUNCH;
-    }
+    const pfa::DeviceScope dev(a->device_id);
+    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
+    if (use_mbits && !launch_mask_bits(mb, a, stream)) return PFA_ERR_LAUNCH;      // (again: the call may come without a forward before it)
     void* kargs[] = {&p};
-    e = hipLaunchKernel(fn, dim3((unsigned)(p.nqblk * a->B * a->H)), dim3(256), kargs, 0, (hipStream_t)stream);
-    if (prev_dev != a->device_id) (void)hipSetDevice(prev_dev);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_LAUNCH;
-    }
-    return PFA_OK;
+    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(p.nqblk * a->B * a->H)), dim3(256), kargs, 0, (hipStream_t)stream);
+    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 }  // extern "C"

@@ -8,8 +8,7 @@
 #include <string.h>
 
 #include "fa3_decode_kernel.h"
-
-namespace pfa { void set_last_hip_error(int e); }   // pfa_capi.hip: what pfa_last_hip_error reports
+#include "pfa_host.h"
 
 namespace {
 
@@ -131,27 +130,15 @@ int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream) {
                         : (a->D == 128 ? main_fn<_Float16, 128>(out32) : main_fn<_Float16, 64>(out32));
     const void* cfn = bf ? (a->D == 128 ? combine_fn<__bf16, 128>(out32) : combine_fn<__bf16, 64>(out32))
                          : (a->D == 128 ? combine_fn<_Float16, 128>(out32) : combine_fn<_Float16, 64>(out32));
-    int prev_dev = -1;
-    hipError_t e = hipGetDevice(&prev_dev);
-    if (e == hipSuccess && prev_dev != a->device_id) e = hipSetDevice(a->device_id);
-    if (e != hipSuccess) {
-        pfa::set_last_hip_error((int)e);
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
+    const pfa::DeviceScope dev(a->device_id);
+    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
     void* kargs[] = {&p};
-    e = hipLaunchKernel(fn, dim3((unsigned)pl.items), dim3(pfa::dec::THREADS), kargs, 0, (hipStream_t)stream);
+    hipError_t e = hipLaunchKernel(fn, dim3((unsigned)pl.items), dim3(pfa::dec::THREADS), kargs, 0, (hipStream_t)stream);
     if (e == hipSuccess && pl.nsplit > 1) {
         const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
         e = hipLaunchKernel(cfn, dim3((unsigned)((threads + 255) / 256)), dim3(256), kargs, 0, (hipStream_t)stream);
     }
-    if (prev_dev != a->device_id) (void)hipSetDevice(prev_dev);
-    if (e != hipSuccess) {
-        pfa::set_last_hip_error((int)e);
-        (void)hipGetLastError();
-        return PFA_ERR_LAUNCH;
-    }
-    return PFA_OK;
+    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "pfa_hip.h"
+#include "pfa_host.h"
 #include "pfa_p4.h"
 #include "build/fa3_fwd_p4_offsets.h"          // generated: P4_KA_* byte offsets of the kernarg block, P4_LDS_BYTES
 
@@ -86,16 +87,10 @@ const DevMod* module_for(int dev, int* hip_err = nullptr) {
             if (permanent) m.state = -1;
             return nullptr;
         };
-        int cur = -1;
-        hipError_t e = hipGetDevice(&cur);
-        if (e != hipSuccess) return fail(e, false);
-        struct Restore {       // the module belongs to the device that is current while it is loaded
-            int cur, dev;
-            Restore(int c, int d) : cur(c), dev(d) { if (c != d) (void)hipSetDevice(d); }
-            ~Restore() { if (cur != dev) (void)hipSetDevice(cur); }
-        } restore(cur, dev);
+        const DeviceScope scope(dev);       // the module belongs to the device that is current while it is loaded
+        if (scope.error() != hipSuccess) return fail(scope.error(), false);
         hipDeviceProp_t prop;
-        e = hipGetDeviceProperties(&prop, dev);
+        hipError_t e = hipGetDeviceProperties(&prop, dev);
         if (e != hipSuccess) return fail(e, false);
         if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(hipErrorNoBinaryForGpu, true);
         m.n_cu = prop.multiProcessorCount;
@@ -221,22 +216,10 @@ int p4_launch(const pfa_fa3_args* a, void* stream, int* hip_err) {
     size_t sz = sizeof(p);
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     hipFunction_t fn = m->fn[a->dtype_in == PFA_DTYPE_BF16 ? 0 : 1][a->D == 64 ? 1 : 0][a->causal ? 1 : 0][p4_flavour(a)][parity ? 1 : 0];
-    int prev = -1;
-    hipError_t e = hipGetDevice(&prev);
-    if (e == hipSuccess && prev != a->device_id) e = hipSetDevice(a->device_id);
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_DEVICE;
-    }
-    e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, config);
-    if (prev != a->device_id) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        if (hip_err) *hip_err = (int)e;
-        (void)hipGetLastError();
-        return PFA_ERR_LAUNCH;
-    }
-    return PFA_OK;
+    const DeviceScope dev(a->device_id);
+    if (hip_failed(dev.error(), hip_err)) return PFA_ERR_DEVICE;
+    const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, config);
+    return hip_failed(e, hip_err) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 }  // namespace pfa

@@ -77,8 +77,8 @@ def test_argument_validation_without_a_gpu(lib):
 
 
 def test_production_library_refuses_development_variants(lib):
-    """flags bits 8..15: 0 or one of the three production kernel selectors; the schedule experiments and the timing-only
-    ablations (which compute wrong answers on purpose) exist only in a `make DEV=1` library."""
+    """flags bits 8..15: 0 or one of the three production kernel selectors; every other value is refused.  The round-1 schedule
+    experiments and timing-only ablations that once lived behind these bits are in git history and in the profile logs, not in the tree."""
     for sel in (0, 43, 44, 45):
         assert lib.pfa_fa3_check(C.byref(_args(flags=sel << 8))) == 0, sel
     for var in (1, 9, 0x14, 19, 28, 30, 41, 42, 46, 49, 255):          # 0x14 << 8 = 0x1400

@@ -14,7 +14,7 @@ CONFIGS = {"C3": (4, 16, 4096, 128, True), "C4": (4, 16, 4096, 128, False), "C5"
            "b1h8S8Kc": (1, 8, 8192, 128, True), "b2h8S1Kc": (2, 8, 1024, 128, True), "b1h12S1Kd64": (1, 12, 1024, 64, False), "b1h16S16Kc": (1, 16, 16384, 128, True)}
 ap = argparse.ArgumentParser()
 ap.add_argument("--configs", default="C4,C3")
-ap.add_argument("--variants", default="0,1,2,3,4,5")
+ap.add_argument("--variants", default="44,43,0", help="kernel selectors: 44 = 8-wave, 43 = 4-wave, 45 = persistent assembly, 0 = the library's choice")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--check", action="store_true")
