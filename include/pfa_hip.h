@@ -4,7 +4,8 @@
  * ABI history: v1 forward; v2 general masks + weights; v3 backward; v4 grouped-query heads (kv_group); v5 fp32 operands (exact
  * fp32 kernels, forward and backward) and dense-branch attention dropout; v6 pfa_fa3_prepare, reserve_cus, pfa_probe_mfma;
  * v7 pfa_fa3_bwd_args.kv_group (grouped-query heads in the backward: dK / dV summed over the group in the kernel); v8 split-KV decode
- * over a KV cache (pfa_fa3_decode_args, pfa_fa3_decode*: query rows of a K/V head packed together, keys split over workgroups).
+ * over a KV cache (pfa_fa3_decode_args, pfa_fa3_decode*: query rows of a K/V head packed together, keys split over workgroups);
+ * v9 paged KV cache for the decode (pfa_fa3_decode_args.block_table / page_size / num_pages appended: a pool of pages and a block table).
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -46,7 +47,7 @@
 extern "C" {
 #endif
 
-#define PFA_ABI_VERSION 8
+#define PFA_ABI_VERSION 9
 
 typedef enum pfa_status {
     PFA_OK = 0,
@@ -263,6 +264,17 @@ int pfa_fa3_describe(const pfa_fa3_args* a, char* buf, size_t n);
  * bitwise reproducible).  pfa_fa3_decode_workspace_bytes() depends on the shapes (B, H, Hkv, Sq, Smax, D) only, never on the
  * device-side lengths, so a captured graph stays valid while cache_seqlens and the cache change between replays.  The workspace is
  * required when that size is non-zero (missing or too small: PFA_ERR_NULL).
+ *
+ * Paged cache (ABI v9), block_table != NULL: k_cache / v_cache point at pools [num_pages, page_size, Hkv, D] by element strides, where
+ * k_stride_b / v_stride_b are the PAGE strides, *_stride_s the token stride inside a page and *_stride_h the head stride.  block_table is a
+ * device int32 [B][max_pages] (block_table_stride_b entries between batches, >= max_pages): logical key j of batch b lives in page
+ * block_table[b][j / page_size] at token j % page_size.  Smax is the LOGICAL capacity and must equal max_pages * page_size; cache_seqlens,
+ * key_mask and causal keep their meaning over logical keys.  page_size must be a multiple of 64, so that a key tile never straddles a
+ * page (pages of 16 or 32 keys are not supported).  Page ids are clamped to [0, num_pages - 1] in the kernel -- a bad table gives wrong
+ * numbers, never an out-of-range address -- and entries at and past ceil(cache_seqlens[b] / page_size) are never read.  The workspace size
+ * and the split count equal those of the contiguous call of the same (B, H, Hkv, Sq, Smax, D), and the result is bit for bit that of
+ * the contiguous call on the gathered cache.  block_table == NULL is the contiguous call; page_size, num_pages and
+ * block_table_stride_b must then be 0 (PFA_ERR_FLAGS).
  */
 typedef struct pfa_fa3_decode_args {
     uint32_t size;              /* = sizeof(pfa_fa3_decode_args) */
@@ -288,6 +300,11 @@ typedef struct pfa_fa3_decode_args {
     int32_t reserved0;          /* must be 0 */
     void*   workspace;          /* pfa_fa3_decode_workspace_bytes() bytes */
     size_t  workspace_bytes;
+    /* ABI v9: paged cache, see above.  NULL / 0: the contiguous cache. */
+    const int32_t* block_table;
+    int64_t block_table_stride_b;
+    int32_t page_size;          /* keys per page, a multiple of 64 */
+    int32_t num_pages;          /* pages in the pools */
 } pfa_fa3_decode_args;
 
 /* Scratch bytes pfa_fa3_decode needs for `a` (0: none); from shapes only.  0 also for arguments pfa_fa3_decode_check refuses. */
@@ -296,7 +313,7 @@ size_t pfa_fa3_decode_workspace_bytes(const pfa_fa3_decode_args* a);
 int pfa_fa3_decode_check(const pfa_fa3_decode_args* a);
 /* Enqueue the decode (one launch, plus the combine launch when the keys are split) on `stream`. */
 int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream);
-/* Introspection for tests / tools: the kernel name into buf (NUL terminated, truncated to n), the number of key splits into *nsplit
+/* Introspection for tests / tools: the kernel name ("_paged" appended with a block table) into buf (NUL terminated, truncated to n), the number of key splits into *nsplit
  * (may be NULL); returns the workgroups of the main launch, or a pfa_status. */
 int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, int32_t* nsplit);
 

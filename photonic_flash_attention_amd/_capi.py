@@ -13,7 +13,7 @@ import os
 import threading
 from typing import Optional
 
-PFA_ABI_VERSION = 8
+PFA_ABI_VERSION = 9
 PFA_DTYPE_BF16, PFA_DTYPE_FP16, PFA_DTYPE_FP32 = 0, 1, 2
 PFA_FLAG_SPLIT_P = 0x1
 PFA_FLAG_NO_XCD_MAP = 0x2
@@ -67,7 +67,7 @@ class PfaFa3BwdArgs(C.Structure):
 
 
 class PfaFa3DecodeArgs(C.Structure):
-    """Mirror of ``struct pfa_fa3_decode_args`` (include/pfa_hip.h, ABI v8)."""
+    """Mirror of ``struct pfa_fa3_decode_args`` (include/pfa_hip.h, ABI v9: the paging fields are appended)."""
     _fields_ = (
         [("size", C.c_uint32), ("flags", C.c_uint32)]
         + [(n, C.c_void_p) for n in ("q", "k_cache", "v_cache", "o", "lse", "cache_seqlens", "key_mask")]
@@ -76,6 +76,7 @@ class PfaFa3DecodeArgs(C.Structure):
         + [(n, C.c_int32) for n in ("B", "H", "Hkv", "Sq", "Smax", "D", "dtype_in", "dtype_out", "causal")]
         + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
         + [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+        + [("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64), ("page_size", C.c_int32), ("num_pages", C.c_int32)]
     )
 
 

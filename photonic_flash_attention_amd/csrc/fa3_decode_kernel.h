@@ -16,6 +16,16 @@
 //   * Online softmax in fp32 (log2 domain; with an fp32 output P is carried as 16-bit hi + lo), masks (key mask, split end, bottom-right causal cut) only on tiles they touch.
 //   * The 4 waves' (m, l, O) merge through LDS; the workgroup writes O and LSE (nsplit == 1) or fp32 partials (O, m, l) that
 //     fa3_decode_combine_kernel reduces.  No atomics: bitwise reproducible.
+//   * PAGED = true: the cache is a pool of fixed-size pages [num_pages, page_size, Hkv, D] (page / head / token strides) and a device
+//     block table int32 [B][max_pages]; logical key j of batch b lives in page block_table[b][j / page_size] at token j % page_size.
+//     page_size is a multiple of 64 (= SPLIT_ALIGN and the largest wave tile), so a tile never straddles a page: issue(t) takes one
+//     wave-uniform table entry and builds the same per-tile descriptors from the page's base.  The entry is a scalar load, fetched
+//     one issue ahead (right behind the previous tile's K / V loads) and carried in a scalar register, so that no dependent load
+//     stands in front of a tile's K / V loads (-DPFA_DECODE_PAGE_LOOKAHEAD=0 fetches it in place, for measurement).  The page id is clamped to
+//     [0, num_pages - 1] (a bad table gives wrong numbers, never an out-of-range address), and an entry at or past
+//     ceil(len_b / page_size) is never read, because a tile exists only below the split's hi <= len_b.  Everything else (split rule,
+//     masks by logical key, softmax, merge, combine) is the one code path, so a paged call returns the bits of the contiguous call
+//     on the gathered cache.  Pages of 16 or 32 keys would put several pages under one tile and are out of scope.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +41,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __amdgpu_buffer_rsrc_t srd_t;
 typedef __attribute__((address_space(3))) char lds_char;
+typedef const __attribute__((address_space(4))) int32_t* const_i32_ptr;   // read-only for the kernel's lifetime: scalar loads
+
+#ifndef PFA_DECODE_PAGE_LOOKAHEAD
+#define PFA_DECODE_PAGE_LOOKAHEAD 1
+#endif
 
 constexpr int NW = 4;            // waves per workgroup
 constexpr int ROWS = 16;         // query rows per row block (the MFMA's 16-wide dimension)
@@ -55,6 +70,10 @@ struct DecodeParams {
     int32_t B, H, Hkv, G, Sq, Smax, nrb, nsplit;
     int32_t causal;              // bottom-right: row i sees key j iff j <= len_b - Sq + i
     float scale_log2;            // softmax_scale * log2(e)
+    // PAGED only: k / v are the pools, k_sb / v_sb the page strides, Smax = max_pages * page_size the logical capacity
+    const int32_t* block_table;  // [B][max_pages] page ids
+    int64_t bt_sb;               // entries between batches
+    int32_t page_size, num_pages;
 };
 
 template <typename T> struct DElem;
@@ -115,7 +134,7 @@ __device__ __forceinline__ void split_range(const DecodeParams& p, int b, int s,
     hi = min(lo + c, len);
 }
 
-template <typename T, int D, typename OT>
+template <typename T, int D, typename OT, bool PAGED = false>
 __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodeParams p) {
     using E = DElem<T>;
     using v8 = typename E::v8;
@@ -165,8 +184,9 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
             u32x4 w = row_ok ? *(const u32x4*)(qrow + 32 * ks + 8 * h) : u32x4{0u, 0u, 0u, 0u};
             qf[ks] = __builtin_bit_cast(v8, w);
         }
-        const char* kslab = (const char*)p.k + ((int64_t)b * p.k_sb + (int64_t)kvh * p.k_sh) * 2;
-        const char* vslab = (const char*)p.v + ((int64_t)b * p.v_sb + (int64_t)kvh * p.v_sh) * 2;
+        // contiguous: this batch's and head's slab; paged: the head's offset inside every page (the page base is added per tile)
+        const char* kslab = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * 2;
+        const char* vslab = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * 2;
         const uint32_t kss2 = (uint32_t)p.k_ss * 2u, vss2 = (uint32_t)p.v_ss * 2u;
         // per-lane byte offsets inside a tile: K in the A-operand layout (key kb*16 + c, head dims 32 ks + 8 h ..),
         // V one 1-KiB piece per instruction (key vi*KPI + lane / (D/8), chunk lane % (D/8))
@@ -179,11 +199,29 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
         const uint32_t vtr = (uint32_t)(4 * h + ((lane & 15) >> 2)) * VROW + (uint32_t)(lane & 3) * 8u;
 
         u32x4 kr[NKB * KS], vr[VLD];
+        // paged: the (unclamped) page id of tile t, a wave-uniform scalar load.  Called only for t < ntile, i.e. for keys below
+        // hi <= len_b, so table entries at and past ceil(len_b / page_size) are never read.
+        const const_i32_ptr table = PAGED ? (const_i32_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
+        auto page_of = [&](int t) { return table[(uint32_t)(lo + t * KT) / (uint32_t)p.page_size]; };
+        int pg_next = 0;
+        if constexpr (PAGED && PFA_DECODE_PAGE_LOOKAHEAD) pg_next = page_of(wave);
         auto issue = [&](int t) {
             const int t0 = lo + t * KT;
             const int nk = min(KT, hi - t0);     // rows past the split's end read as zeros
-            const srd_t vs = uniform_srd(vslab + (int64_t)t0 * p.v_ss * 2, (uint32_t)(nk - 1) * vss2 + D * 2);
-            const srd_t ks = uniform_srd(kslab + (int64_t)t0 * p.k_ss * 2, (uint32_t)(nk - 1) * kss2 + D * 2);
+            int64_t koff, voff;                  // element offsets of the tile's first key row from kslab / vslab
+            if constexpr (PAGED) {
+                // the tile lies inside one page (page_size % 64 == 0, t0 % KT == 0, KT <= 64)
+                int pg = PFA_DECODE_PAGE_LOOKAHEAD ? pg_next : page_of(t);
+                pg = min(max(pg, 0), p.num_pages - 1);           // device data: never an address outside the pool
+                const int tok = (int)((uint32_t)t0 % (uint32_t)p.page_size);
+                koff = (int64_t)pg * p.k_sb + (int64_t)tok * p.k_ss;
+                voff = (int64_t)pg * p.v_sb + (int64_t)tok * p.v_ss;
+            } else {
+                koff = (int64_t)t0 * p.k_ss;
+                voff = (int64_t)t0 * p.v_ss;
+            }
+            const srd_t vs = uniform_srd(vslab + voff * 2, (uint32_t)(nk - 1) * vss2 + D * 2);
+            const srd_t ks = uniform_srd(kslab + koff * 2, (uint32_t)(nk - 1) * kss2 + D * 2);
 #pragma unroll
             for (int i = 0; i < VLD; ++i)
                 vr[i] = __builtin_amdgcn_raw_buffer_load_b128(vs, (int)(voff0 + (uint32_t)(i * Gm::KPI) * vss2), 0, 0);
@@ -192,6 +230,8 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
 #pragma unroll
                 for (int q = 0; q < KS; ++q)
                     kr[kb * KS + q] = __builtin_amdgcn_raw_buffer_load_b128(ks, (int)(koff0 + (uint32_t)(kb * 16) * kss2 + q * 64), 0, 0);
+            if constexpr (PAGED && PFA_DECODE_PAGE_LOOKAHEAD)
+                if (t + NW < ntile) pg_next = page_of(t + NW);   // behind this tile's loads, for the next issue()
         };
         issue(wave);
         const uint8_t* km = p.key_mask ? p.key_mask + (int64_t)b * p.km_sb : nullptr;

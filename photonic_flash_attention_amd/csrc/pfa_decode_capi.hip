@@ -1,4 +1,4 @@
-// pfa_decode_capi.hip -- C ABI of the split-KV decode path (include/pfa_hip.h, ABI v8): validation, the split rule, launches.
+// pfa_decode_capi.hip -- C ABI of the split-KV decode path (include/pfa_hip.h, ABI v9): validation, the split rule, launches.
 // No allocation, no synchronisation, no process-wide state.
 #include "pfa_hip.h"
 
@@ -24,7 +24,8 @@ struct Plan {
     size_t ws_bytes = 0;
 };
 
-// Everything here depends on shapes only (never on cache_seqlens / key_mask), so a captured graph stays valid while they change.
+// Everything here depends on shapes only (never on cache_seqlens / key_mask / the block table or the page size), so a captured graph
+// stays valid while they change, and a paged call splits exactly as the contiguous call of the same (B, H, Hkv, Sq, Smax, D).
 Plan plan(const pfa_fa3_decode_args* a) {
     Plan pl;
     pl.G = a->H / a->Hkv;
@@ -65,6 +66,14 @@ int check(const pfa_fa3_decode_args* a) {
     // a tile's K / V rows are addressed by 32-bit offsets from a per-tile buffer descriptor
     if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_s * 2 * 64 + 256 > 0x7fffffffLL || a->v_stride_s * 2 * 64 + 256 > 0x7fffffffLL)
         return PFA_ERR_STRIDE;
+    if (a->block_table) {
+        // Smax is the logical capacity max_pages * page_size; a 64-key tile must lie inside one page
+        if (a->page_size <= 0 || a->page_size % pfa::dec::SPLIT_ALIGN != 0 || a->num_pages <= 0) return PFA_ERR_SHAPE;
+        if (a->Smax % a->page_size != 0 || a->block_table_stride_b < a->Smax / a->page_size) return PFA_ERR_SHAPE;
+        if (reinterpret_cast<uintptr_t>(a->block_table) & 3u) return PFA_ERR_ALIGN;
+    } else if (a->page_size != 0 || a->num_pages != 0 || a->block_table_stride_b != 0) {
+        return PFA_ERR_FLAGS;
+    }
     const Plan pl = plan(a);
     if (pl.items > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (a->D / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
     if (pl.ws_bytes) {
@@ -75,7 +84,9 @@ int check(const pfa_fa3_decode_args* a) {
 }
 
 template <typename T, int D>
-const void* main_fn(bool out32) {
+const void* main_fn(bool out32, bool paged) {
+    if (paged)
+        return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, true> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, true>;
     return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T>;
 }
 template <typename T, int D>
@@ -101,8 +112,8 @@ int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, i
     if (st != PFA_OK) return st;
     const Plan pl = plan(a);
     if (buf && n)
-        snprintf(buf, n, "fa3_decode_%s_d%d_%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
-                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", pl.nsplit > 1 ? "+combine" : "");
+        snprintf(buf, n, "fa3_decode_%s_d%d_%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
+                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", pl.nsplit > 1 ? "+combine" : "", a->block_table ? "_paged" : "");
     if (nsplit) *nsplit = pl.nsplit;
     return (int)pl.items;
 }
@@ -124,10 +135,11 @@ int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream) {
     p.B = a->B; p.H = a->H; p.Hkv = a->Hkv; p.G = pl.G; p.Sq = a->Sq; p.Smax = a->Smax; p.nrb = pl.nrb; p.nsplit = pl.nsplit;
     p.causal = a->causal != 0;
     p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+    p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
 
-    const bool bf = a->dtype_in == PFA_DTYPE_BF16, out32 = a->dtype_out == PFA_DTYPE_FP32;
-    const void* fn = bf ? (a->D == 128 ? main_fn<__bf16, 128>(out32) : main_fn<__bf16, 64>(out32))
-                        : (a->D == 128 ? main_fn<_Float16, 128>(out32) : main_fn<_Float16, 64>(out32));
+    const bool bf = a->dtype_in == PFA_DTYPE_BF16, out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr;
+    const void* fn = bf ? (a->D == 128 ? main_fn<__bf16, 128>(out32, paged) : main_fn<__bf16, 64>(out32, paged))
+                        : (a->D == 128 ? main_fn<_Float16, 128>(out32, paged) : main_fn<_Float16, 64>(out32, paged));
     const void* cfn = bf ? (a->D == 128 ? combine_fn<__bf16, 128>(out32) : combine_fn<__bf16, 64>(out32))
                          : (a->D == 128 ? combine_fn<_Float16, 128>(out32) : combine_fn<_Float16, 64>(out32));
     const pfa::DeviceScope dev(a->device_id);

@@ -1,0 +1,3 @@
+from .paged_cache import PagedCacheFull, PagedKVCache
+
+__all__ = ["PagedKVCache", "PagedCacheFull"]

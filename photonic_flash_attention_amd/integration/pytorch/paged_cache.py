@@ -1,0 +1,217 @@
+"""A paged KV cache for one attention layer, read by ``ops.fa3_decode(..., block_table=...)``.
+
+The cache is a pool of fixed-size pages (``[num_pages, page_size, Hkv, D]`` for K and for V) plus, per sequence slot, a row of a
+device block table and a device length.  Which page a sequence's next tokens go to is decided on the host, from a host mirror of
+the lengths (the caller says how many tokens it appends, so the host always knows them): nothing here synchronises with the
+device.  The device tensors ``block_table`` and ``cache_seqlens`` are allocated once and updated in place, so a captured graph of
+``decode`` keeps seeing them; pages a sequence will grow into during replays are assigned ahead with ``reserve``.
+
+Everything except ``decode`` (the HIP kernel) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
+The token append is a few KiB per step and stays torch ops; the hot path is the decode kernel.
+"""
+
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple, Union
+
+import torch
+
+from ... import ops
+
+Slots = Union[None, int, slice, range, Sequence[int]]
+
+
+class PagedCacheFull(RuntimeError):
+    """The pool has no free page (or the cache no free slot, or a sequence no table entry) left for the request."""
+
+
+class PagedKVCache:
+    """One layer's K and V page pools, the block table and the per-slot lengths.
+
+    A *slot* is a row of ``block_table`` / ``cache_seqlens``: ``allocate`` hands one out, ``free`` takes it back with its pages.
+    A slot that is not allocated has length 0, so a ``decode`` over all slots returns zeros for it and reads none of its entries.
+    """
+
+    def __init__(self, num_pages: int, page_size: int, Hkv: int, D: int, dtype: torch.dtype = torch.bfloat16,
+                 device: Union[str, torch.device] = "cuda", max_batch: int = 1, max_pages_per_seq: Optional[int] = None):
+        if page_size < 64 or page_size % 64:
+            raise ValueError(f"page size {page_size}: must be a multiple of 64 keys (a key tile of the kernel lies inside one page)")
+        if num_pages < 1 or Hkv < 1 or D < 1 or max_batch < 1:
+            raise ValueError("num_pages, Hkv, D and max_batch must be positive")
+        self.num_pages, self.page_size, self.Hkv, self.D = num_pages, page_size, Hkv, D
+        self.max_batch = max_batch
+        self.max_pages_per_seq = num_pages if max_pages_per_seq is None else max_pages_per_seq
+        if self.max_pages_per_seq < 1:
+            raise ValueError("max_pages_per_seq must be positive")
+        self.device = torch.device(device)
+        self._k = torch.zeros(num_pages, page_size, Hkv, D, dtype=dtype, device=self.device)
+        self._v = torch.zeros_like(self._k)
+        self._table = torch.zeros(max_batch, self.max_pages_per_seq, dtype=torch.int32, device=self.device)
+        self._lens = torch.zeros(max_batch, dtype=torch.int32, device=self.device)
+        # host mirror
+        self._host_lens: List[int] = [0] * max_batch
+        self._pages: List[List[int]] = [[] for _ in range(max_batch)]
+        self._live: List[bool] = [False] * max_batch
+        self._free_pages: List[int] = list(range(num_pages - 1, -1, -1))      # popped from the end: lowest id first
+
+    # --- device tensors (the same storage for the cache's lifetime) ---------------------------------------------------------------
+    @property
+    def block_table(self) -> torch.Tensor:
+        """int32 ``[max_batch, max_pages_per_seq]``; row = slot.  Entries past a sequence's assigned pages are stale and unread."""
+        return self._table
+
+    @property
+    def cache_seqlens(self) -> torch.Tensor:
+        """int32 ``[max_batch]``: tokens held per slot."""
+        return self._lens
+
+    @property
+    def k_pool(self) -> torch.Tensor:
+        """``[num_pages, page_size, Hkv, D]``"""
+        return self._k
+
+    @property
+    def v_pool(self) -> torch.Tensor:
+        return self._v
+
+    # --- host bookkeeping ---------------------------------------------------------------------------------------------------------
+    @property
+    def free_pages(self) -> int:
+        return len(self._free_pages)
+
+    def length(self, slot: int) -> int:
+        return self._host_lens[self._check_slot(slot)]
+
+    def pages(self, slot: int) -> Tuple[int, ...]:
+        """The pages assigned to the slot, in logical order (those holding tokens first, then the reserved ones)."""
+        return tuple(self._pages[self._check_slot(slot)])
+
+    def _check_slot(self, slot: int) -> int:
+        if not 0 <= slot < self.max_batch or not self._live[slot]:
+            raise ValueError(f"slot {slot} is not allocated")
+        return slot
+
+    def _pages_missing(self, slot: int, n_tokens: int) -> int:
+        need = -(-n_tokens // self.page_size)
+        if need > self.max_pages_per_seq:
+            raise PagedCacheFull(f"{n_tokens} tokens need {need} pages, a sequence's table row has {self.max_pages_per_seq}")
+        return max(0, need - len(self._pages[slot]))
+
+    def _assign(self, slot: int, count: int) -> None:
+        if count == 0:
+            return
+        first = len(self._pages[slot])
+        new = [self._free_pages.pop() for _ in range(count)]
+        self._pages[slot].extend(new)
+        self._table[slot, first:first + count] = torch.tensor(new, dtype=torch.int32)
+
+    def allocate(self, n_tokens: int = 0) -> int:
+        """Take a free slot and assign it pages for ``n_tokens`` tokens (its length stays 0).  -> slot."""
+        for slot in range(self.max_batch):
+            if not self._live[slot]:
+                break
+        else:
+            raise PagedCacheFull(f"all {self.max_batch} slots are in use")
+        self._live[slot] = True
+        try:
+            self.reserve(slot, n_tokens)
+        except PagedCacheFull:
+            self._live[slot] = False
+            raise
+        return slot
+
+    def reserve(self, slot: int, n_tokens: int) -> None:
+        """Make sure the slot has pages for ``n_tokens`` tokens in all (e.g. before a graph capture whose replays will append)."""
+        self._check_slot(slot)
+        missing = self._pages_missing(slot, n_tokens)
+        if missing > len(self._free_pages):
+            raise PagedCacheFull(f"slot {slot} needs {missing} more pages, the pool has {len(self._free_pages)} free")
+        self._assign(slot, missing)
+
+    def free(self, slot: int) -> None:
+        """Give the slot and its pages back.  The pages' contents and the table row stay as they are; neither is read again."""
+        self._check_slot(slot)
+        self._free_pages.extend(reversed(self._pages[slot]))
+        self._pages[slot] = []
+        self._host_lens[slot] = 0
+        self._live[slot] = False
+        self._lens[slot] = 0
+
+    def append(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor) -> None:
+        """Write ``k_new`` / ``v_new`` ``[n, Hkv, Sq, D]`` at the current end of each of the ``n`` slots and advance their lengths.
+        Pages are assigned as needed; if the pool cannot serve all of them nothing is written and ``PagedCacheFull`` is raised."""
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        n = len(slots)
+        if len(set(slots)) != n:
+            raise ValueError("a slot may appear once per append")
+        if k_new.dim() != 4 or k_new.shape[:2] != (n, self.Hkv) or k_new.shape[3] != self.D or v_new.shape != k_new.shape:
+            raise ValueError(f"k_new / v_new must be [{n}, {self.Hkv}, Sq, {self.D}], got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
+        if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
+            raise ValueError("k_new / v_new must have the cache's dtype")
+        Sq = k_new.shape[2]
+        missing = [self._pages_missing(self._check_slot(s), self._host_lens[s] + Sq) for s in slots]
+        if sum(missing) > len(self._free_pages):
+            raise PagedCacheFull(f"the append needs {sum(missing)} more pages, the pool has {len(self._free_pages)} free")
+        dst = []
+        for s, m in zip(slots, missing):
+            self._assign(s, m)
+            for j in range(self._host_lens[s], self._host_lens[s] + Sq):
+                dst.append(self._pages[s][j // self.page_size] * self.page_size + j % self.page_size)
+            self._host_lens[s] += Sq
+        if Sq:
+            idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
+            rows = self.num_pages * self.page_size
+            self._k.view(rows, self.Hkv, self.D).index_copy_(0, idx, k_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D))
+            self._v.view(rows, self.Hkv, self.D).index_copy_(0, idx, v_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D))
+        self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
+
+    def swap_pages(self, slot: int, i: int, j: int) -> None:
+        """Exchange the physical pages behind logical pages ``i`` and ``j`` of the slot, moving their contents with them (what a
+        compaction does); the sequence reads the same afterwards."""
+        pg = self._pages[self._check_slot(slot)]
+        if not (0 <= i < len(pg) and 0 <= j < len(pg)):
+            raise ValueError(f"slot {slot} has {len(pg)} pages")
+        if i == j:
+            return
+        a, b = pg[i], pg[j]
+        for pool in (self._k, self._v):
+            tmp = pool[a].clone()
+            pool[a].copy_(pool[b])
+            pool[b].copy_(tmp)
+        pg[i], pg[j] = b, a
+        self._table[slot, i] = b
+        self._table[slot, j] = a
+
+    def gather(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The slot's K and V as contiguous ``[Hkv, len, D]`` tensors (tests, debugging)."""
+        n = self._host_lens[self._check_slot(slot)]
+        pg = torch.tensor(self._pages[slot][:-(-n // self.page_size)], dtype=torch.int64).to(self.device)
+        out = []
+        for pool in (self._k, self._v):
+            out.append(pool.index_select(0, pg).reshape(-1, self.Hkv, self.D)[:n].permute(1, 0, 2).contiguous())
+        return out[0], out[1]
+
+    # --- the kernel ---------------------------------------------------------------------------------------------------------------
+    def _rows(self, slots: Slots) -> Tuple[torch.Tensor, torch.Tensor]:
+        if slots is None:
+            return self._table, self._lens
+        if isinstance(slots, int):
+            slots = range(slots, slots + 1)
+        if isinstance(slots, slice):
+            slots = range(*slots.indices(self.max_batch))
+        slots = list(slots)
+        if not slots:
+            raise ValueError("no slots")
+        if slots == list(range(slots[0], slots[0] + len(slots))) and 0 <= slots[0] and slots[-1] < self.max_batch:
+            return self._table[slots[0]:slots[-1] + 1], self._lens[slots[0]:slots[-1] + 1]     # views: capturable
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.device)
+        return self._table.index_select(0, idx), self._lens.index_select(0, idx)
+
+    def decode(self, q: torch.Tensor, slots: Slots = None, **kw):
+        """``ops.fa3_decode`` of ``q [B, H, Sq, D]`` against the sequences in ``slots`` (batch row i reads slot ``slots[i]``; None:
+        all ``max_batch`` slots in order).  None and a run of consecutive slots read the cache's own table and lengths, so the
+        call can be captured in a graph and replayed while the cache changes; any other list takes a copy of its rows first.
+        Keyword arguments (``causal``, ``key_mask`` over ``max_pages_per_seq * page_size`` logical keys, ``out_dtype``, ...) pass
+        through.  -> ``(o, lse)``."""
+        table, lens = self._rows(slots)
+        return ops.fa3_decode(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)

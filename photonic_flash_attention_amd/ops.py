@@ -463,7 +463,8 @@ def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=Non
 def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
-               out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               out: Optional[torch.Tensor] = None,
+               block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -472,13 +473,36 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     valid keys per batch.  key_mask: optional ``[B,Smax]`` (0 / False = masked); given alone, each batch's length is derived from it
     on the device, so a static cache's unfilled tail is never read.  ``causal`` is bottom-right aligned: row i sees key j iff
     j <= len_b - Sq + i (for Sq = 1 it changes nothing).  Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.
-    No host synchronisation and no cached allocation: capturable in ``torch.cuda.graph``."""
+    No host synchronisation and no cached allocation: capturable in ``torch.cuda.graph``.
+
+    Paged cache: with ``block_table`` (int32 ``[B, max_pages]`` DEVICE tensor, last dim contiguous) k_cache / v_cache are pools,
+    ``[num_pages,Hkv,page_size,D]``-shaped views (a flash-attn ``[num_pages,page_size,Hkv,D]`` pool is passed as ``.transpose(1, 2)``),
+    page_size a multiple of 64: logical key j of batch b lives in page ``block_table[b, j // page_size]`` at token ``j % page_size``.
+    Smax is then ``max_pages * page_size``; cache_seqlens, key_mask (``[B, max_pages * page_size]``) and causal are over logical keys.
+    Table entries at and past ``ceil(len_b / page_size)`` are never read; page ids are clamped into the pool by the kernel.  The
+    result is bit for bit that of the contiguous call on the gathered cache."""
     if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
     B, H, Sq, D = q.shape
     Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
-    if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != (B, Hkv, Smax, D) or Hkv < 1 or H % Hkv:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
+    if block_table is None:
+        if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != (B, Hkv, Smax, D) or Hkv < 1 or H % Hkv:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
+    else:
+        num_pages, page_size = k_cache.shape[0], k_cache.shape[2]
+        if k_cache.shape != (num_pages, Hkv, page_size, D) or v_cache.shape != k_cache.shape or num_pages < 1 or Hkv < 1 or H % Hkv:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} k pool {tuple(k_cache.shape)} v pool {tuple(v_cache.shape)}")
+        if page_size < 64 or page_size % 64:
+            raise ValueError(f"page size {page_size}: must be a multiple of 64 keys")
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+            raise ValueError("block_table must be an int32 tensor")
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be [B, max_pages] with B = {B}, got {tuple(block_table.shape)}")
+        if block_table.stride(1) != 1 and block_table.shape[1] != 1:
+            raise ValueError("block_table: the last dim must be contiguous")
+        if not block_table.is_cuda or block_table.device != q.device:
+            raise ValueError("block_table must live on the operands' device (there is no CPU path)")
+        Smax = block_table.shape[1] * page_size
     if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise ValueError("q, k_cache, v_cache must share dtype bf16 or fp16")
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda) or k_cache.device != q.device or v_cache.device != q.device:
@@ -498,6 +522,9 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         B=B, H=H, Hkv=Hkv, Sq=Sq, Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt], causal=1 if causal else 0,
         softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
         device_id=q.device.index if q.device.index is not None else torch.cuda.current_device())
+    if block_table is not None:
+        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
+        a.page_size, a.num_pages = page_size, num_pages
     keep = []
     if key_mask is not None:
         if key_mask.shape != (B, Smax):

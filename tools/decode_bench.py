@@ -7,6 +7,13 @@ labelled as such.  Rate = K + V cache bytes / time, and its share of the ~6.3 TB
 host (Python + ctypes) cost of one call and the time of one graph replay.
 
     python tools/decode_bench.py [--reps 5] [--quick] [--warm] [--json out.jsonl]
+
+``--paged PAGE_SIZE`` measures the paged cache instead: the same caches scattered over page pools in a seeded random page order
+(``ops.fa3_decode(..., block_table=...)``), timed alternately with the contiguous call under the same cache-cycling rule, plus
+(``--gather``) what the paged call replaces: gathering the pages into a contiguous cache with torch ops and decoding that.
+``--shapes B,H,Hkv,D,Skv[;...]`` picks the shapes.
+
+    python tools/decode_bench.py --paged 256 [--gather] [--shapes "8,32,8,128,32768;1,32,8,128,32768"] [--reps 7]
 """
 
 from __future__ import annotations
@@ -94,6 +101,94 @@ def bench_shape(B, H, Hkv, D, S, reps, warm, dev):
     return res
 
 
+def bench_paged(B, H, Hkv, D, S, page, reps, gather, dev, layout="phsd", seed=0):
+    """Contiguous and paged fa3_decode of one shape, timed alternately.  Pool i holds cache i's pages in a random order of its own."""
+    cache_bytes = 2 * B * Hkv * S * D * 2
+    if cache_bytes > MAX_CACHE or S % page:
+        return None
+    n = max(1, math.ceil(MIN_POOL / cache_bytes))
+    pages = S // page
+    q = torch.randn(B, H, 1, D, device=dev, dtype=torch.bfloat16)
+    sl = torch.full((B,), S, dtype=torch.int32, device=dev)
+    contiguous = _caches(B, Hkv, S, D, n, dev)
+    paged = []
+    for i in range(n):                  # one pool per cache: flash-attn style [num_pages, page, Hkv, D] passed transposed ("phsd"),
+        perm = torch.randperm(B * pages, generator=torch.Generator().manual_seed(seed + i)).to(dev)     # or [num_pages, Hkv, page, D] ("hpsd")
+        if layout == "phsd":
+            kp = torch.randn(B * pages, page, Hkv, D, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+            vp = torch.randn(B * pages, page, Hkv, D, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+        else:
+            kp = torch.randn(B * pages, Hkv, page, D, device=dev, dtype=torch.bfloat16)
+            vp = torch.randn(B * pages, Hkv, page, D, device=dev, dtype=torch.bfloat16)
+        paged.append((kp, vp, perm.to(torch.int32).reshape(B, pages).contiguous()))
+
+    def run_contiguous(i):
+        k, v = contiguous[i]
+        ops.fa3_decode(q, k, v, cache_seqlens=sl)
+
+    def run_paged(i):
+        kp, vp, bt = paged[i]
+        ops.fa3_decode(q, kp, vp, cache_seqlens=sl, block_table=bt)
+
+    def run_gather(i):                  # pages -> contiguous [B, Hkv, S, D] copy, then the contiguous call
+        kp, vp, bt = paged[i]
+        idx = bt.flatten().long()
+        k = kp.index_select(0, idx).reshape(B, pages, Hkv, page, D).permute(0, 2, 1, 3, 4).reshape(B, Hkv, S, D)
+        v = vp.index_select(0, idx).reshape(B, pages, Hkv, page, D).permute(0, 2, 1, 3, 4).reshape(B, Hkv, S, D)
+        ops.fa3_decode(q, k, v, cache_seqlens=sl)
+
+    paths = {"contiguous": run_contiguous, "paged": run_paged}
+    if gather:
+        paths["gather_then_decode"] = run_gather
+    for f in paths.values():
+        for i in range(min(2, n)):
+            f(i)
+    torch.cuda.synchronize()
+    times = {name: [] for name in paths}
+    for _ in range(reps):
+        for name, f in paths.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(n):
+                f(i)
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / n)
+    res = dict(B=B, H=H, Hkv=Hkv, D=D, Skv=S, page=page, pool_layout=layout, cache_MB=round(cache_bytes / 1e6, 2), n_caches=n, reps=reps)
+    for name, ts in times.items():
+        us = sorted(ts)[len(ts) // 2]
+        res[f"{name}_us"] = round(us, 2)
+        res[f"{name}_us_min"], res[f"{name}_us_max"] = round(min(ts), 2), round(max(ts), 2)
+        res[f"{name}_TBs"] = round(cache_bytes / us / 1e6, 3)
+    res["paged_over_contiguous"] = round(res["paged_us"] / res["contiguous_us"], 4)
+    del contiguous, paged
+    torch.cuda.empty_cache()
+    return res
+
+
+def main_paged(args, dev):
+    if args.shapes:
+        shapes = [tuple(int(x) for x in s.split(",")) for s in args.shapes.split(";") if s]
+    else:               # the shapes DESIGN 4.6 reports
+        shapes = [(8, 32, 8, 128, 32768), (8, 32, 8, 128, 131072), (1, 32, 8, 128, 32768), (32, 32, 32, 128, 4096)]
+    rows = []
+    print(f"{'B':>3} {'H':>3} {'Hkv':>3} {'D':>4} {'Skv':>7} {'page':>5} {'MB':>8} | {'contig us':>9} {'TB/s':>5} | {'paged us':>9} {'TB/s':>5} "
+          f"{'ratio':>6}" + (f" | {'gather+decode us':>16}" if args.gather else ""), flush=True)
+    for B, H, Hkv, D, S in shapes:
+        r = bench_paged(B, H, Hkv, D, S, args.paged, args.reps, args.gather, dev, layout=args.pool_layout)
+        if r is None:
+            print(f"{B:>3} {H:>3} {Hkv:>3} {D:>4} {S:>7}  skipped (cache above {MAX_CACHE >> 30} GiB, or Skv no multiple of the page)", flush=True)
+            continue
+        rows.append(r)
+        print(f"{B:>3} {H:>3} {Hkv:>3} {D:>4} {S:>7} {args.paged:>5} {r['cache_MB']:>8.1f} | {r['contiguous_us']:>9.2f} {r['contiguous_TBs']:>5.2f} | "
+              f"{r['paged_us']:>9.2f} {r['paged_TBs']:>5.2f} {r['paged_over_contiguous']:>6.3f}"
+              + (f" | {r['gather_then_decode_us']:>16.2f}" if args.gather else ""), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def host_cost(dev):
     """Python + ctypes cost of one fa3_decode call (enqueue only: the GPU side is tiny), and one graph replay of it."""
     B, H, Hkv, D, S = 1, 32, 8, 128, 4096
@@ -145,9 +240,18 @@ def main():
     ap.add_argument("--quick", action="store_true", help="B 1 and 8, Llama-3-8B heads only")
     ap.add_argument("--warm", action="store_true")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE", help="measure the paged cache with pages of this many keys")
+    ap.add_argument("--gather", action="store_true", help="with --paged: also time gathering the pages with torch ops, then decoding")
+    ap.add_argument("--pool-layout", choices=("phsd", "hpsd"), default="phsd",
+                    help="with --paged: pools as [num_pages, page, Hkv, D] (flash-attn style, a token's heads adjacent) or [num_pages, Hkv, page, D] "
+                         "(a head's tokens adjacent, like the contiguous [B, Hkv, S, D] caches this tool times)")
+    ap.add_argument("--shapes", default=None, help='with --paged: "B,H,Hkv,D,Skv;..." instead of the DESIGN 4.6 shapes')
     args = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench measures on the GPU"
     dev = torch.device("cuda:0")
+    if args.paged:
+        main_paged(args, dev)
+        return
     heads = [(32, 8, 128), (64, 8, 128), (32, 32, 128), (16, 16, 64)]
     Bs, Ss = [1, 8, 32], [4096, 32768, 131072]
     if args.quick:
