@@ -5,7 +5,9 @@
  * fp32 kernels, forward and backward) and dense-branch attention dropout; v6 pfa_fa3_prepare, reserve_cus, pfa_probe_mfma;
  * v7 pfa_fa3_bwd_args.kv_group (grouped-query heads in the backward: dK / dV summed over the group in the kernel); v8 split-KV decode
  * over a KV cache (pfa_fa3_decode_args, pfa_fa3_decode*: query rows of a K/V head packed together, keys split over workgroups);
- * v9 paged KV cache for the decode (pfa_fa3_decode_args.block_table / page_size / num_pages appended: a pool of pages and a block table).
+ * v9 paged KV cache for the decode (pfa_fa3_decode_args.block_table / page_size / num_pages appended: a pool of pages and a block table);
+ * v9, additive: pfa_fa3_prefill* -- the compute-bound forward over a KV cache (any number of query rows, contiguous or paged, on the
+ * unchanged pfa_fa3_decode_args).
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -316,6 +318,24 @@ int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream);
 /* Introspection for tests / tools: the kernel name ("_paged" appended with a block table) into buf (NUL terminated, truncated to n), the number of key splits into *nsplit
  * (may be NULL); returns the workgroups of the main launch, or a pfa_status. */
 int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, int32_t* nsplit);
+
+/*
+ * Forward over a KV cache (ABI v9, additive): chunked prefill, the suffix of a prefix-cached prompt, speculative verification -- ANY number
+ * of query rows against the keys a cache holds, on the 8-wave MFMA forward's schedule (256 rows per workgroup) instead of the decode's
+ * bandwidth kernel.  Takes pfa_fa3_decode_args as pfa_fa3_decode does, contiguous or paged, with the same conventions (bottom-right
+ * causal per batch, cache_seqlens on the device, grouped-query heads, page ids clamped, table entries at and past
+ * ceil(cache_seqlens[b] / page_size) never read, a row with no visible key -> O = 0 and LSE = -inf) and the same field rules, except:
+ *   - Sq is any value >= 1 (B * H * ceil(Sq / 256) workgroups, up to the grid limit);
+ *   - key_mask must be NULL (PFA_ERR_FLAGS): key masks over the cache are out of scope here, pfa_fa3_decode takes them;
+ *   - workspace / workspace_bytes are ignored: there is no split over keys, one launch, no atomics (bitwise reproducible).
+ * Keys at and past cache_seqlens[b] are never read (a cache's unfilled tail may hold anything, NaN included).  The grid depends on
+ * shapes only, so a captured graph stays valid while lengths, table and cache change between replays.  A paged call returns the bits of
+ * the contiguous call on the gathered cache.
+ */
+int pfa_fa3_prefill_check(const pfa_fa3_decode_args* a);
+int pfa_fa3_prefill(const pfa_fa3_decode_args* a, void* stream);
+/* Introspection: the kernel name ("_paged" appended with a block table) into buf (NUL terminated, truncated to n); returns the workgroups, or a pfa_status. */
+int pfa_fa3_prefill_describe(const pfa_fa3_decode_args* a, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

@@ -26,6 +26,7 @@ EXPORTS = (
     "pfa_fa3_workspace_bytes", "pfa_fa3_check", "pfa_fa3_fwd", "pfa_fa3_describe", "pfa_fa3_weights",
     "pfa_fa3_bwd", "pfa_fa3_bwd_workspace_bytes", "pfa_fa3_bwd_mask_workspace_bytes", "pfa_fa3_prepare", "pfa_probe_mfma",
     "pfa_fa3_decode_workspace_bytes", "pfa_fa3_decode_check", "pfa_fa3_decode", "pfa_fa3_decode_describe",
+    "pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_describe",
 )
 
 
@@ -141,6 +142,12 @@ def load(path: Optional[str] = None):
         lib.pfa_fa3_decode.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_void_p]
         lib.pfa_fa3_decode_describe.restype = C.c_int
         lib.pfa_fa3_decode_describe.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.pfa_fa3_prefill_check.restype = C.c_int
+        lib.pfa_fa3_prefill_check.argtypes = [C.POINTER(PfaFa3DecodeArgs)]
+        lib.pfa_fa3_prefill.restype = C.c_int
+        lib.pfa_fa3_prefill.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_void_p]
+        lib.pfa_fa3_prefill_describe.restype = C.c_int
+        lib.pfa_fa3_prefill_describe.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_char_p, C.c_size_t]
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
@@ -193,3 +200,12 @@ def describe_decode(args: PfaFa3DecodeArgs):
     if n < 0:
         check_status(n)
     return buf.value.decode(), n, ns.value
+
+
+def describe_prefill(args: PfaFa3DecodeArgs):
+    """-> (kernel name, workgroups) of ``pfa_fa3_prefill`` (the forward over a KV cache takes the decode's argument block)."""
+    buf = C.create_string_buffer(128)
+    n = load().pfa_fa3_prefill_describe(C.byref(args), buf, 128)
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n

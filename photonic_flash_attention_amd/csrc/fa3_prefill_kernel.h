@@ -1,0 +1,380 @@
+// fa3_prefill_kernel.h -- compute-bound forward over a KV cache (contiguous or paged) for MI355X (gfx950), hand-written HIP.
+//
+// Chunked prefill, the suffix of a prefix-cached prompt, speculative verification: Sq new query rows per batch (any number) against
+// the len_b keys a cache holds, bottom-right causal.  The schedule is the 8-wave forward's (fa3_fwd_kernel.h: 256 Q rows per
+// workgroup, one wave per 32 rows, 64-key K/V tiles in two LDS buffers fed by LDS-DMA, swapped products on the 32x32x16 MFMA, V^T by
+// ds_read_b64_tr_b16, deferred-max online softmax, SPLITP for the fp32 output); that header supplies Elem, tile_off, lds_dma16_buf,
+// store_rows_from_lds and the softmax helpers.  The kernel differs from fa3_fwd_kernel in three places:
+//   1. Length and causal offset come from the device: len_b = clamp(cache_seqlens[b], 0, Smax) (Smax without lengths), off_b =
+//      len_b - Sq; row i sees key j iff j < len_b and (causal) j <= i + off_b -- the convention of pfa_fa3_decode_args.causal.  A
+//      block runs tiles up to min(len_b, q0 + 256 + off_b), a wave computes those below min(len_b, wave_q0 + 32 + off_b).  off_b < 0
+//      (len_b < Sq): the first -off_b rows see nothing, O = 0 and LSE = -inf; a block with no visible key runs no tile and writes
+//      its zeros.
+//   2. PAGED: the cache is a pool of pages and a device block table (DecodeParams' convention: k_sb / v_sb are the page strides).
+//      page_size is a multiple of 64, so a tile lies inside one page: dma_tile takes one wave-uniform table entry, fetched by a scalar
+//      load when the PREVIOUS tile's DMA was issued (no dependent load in front of a tile's DMA), clamps it to [0, num_pages - 1] and
+//      builds both descriptors from the page's base.  Tiles are visited in order, so page index and token offset advance by
+//      addition.  Nothing else in the kernel knows about pages: a paged call returns the bits of the contiguous call on the
+//      gathered cache.
+//   3. Each tile's K and V descriptor ends at the tile's last valid key (< len_b), not at Smax: rows at and past len_b land in LDS
+//      as zeros.  The score mask alone is not enough over a cache, whose unfilled tail or half-used last page may hold NaN, and
+//      0 * NaN in the PV MFMA is NaN.  Table entries at and past ceil(len_b / page_size) are never read (a tile exists only below
+//      len_b).
+// Grid = B * H * ceil(Sq / 256) from shapes alone, no workspace, no atomics: capturable, and valid while lengths, table and cache
+// change between replays.  No split over keys: a short chunk with few B * H leaves CUs idle.
+#pragma once
+#include "fa3_fwd_kernel.h"
+
+namespace pfa {
+
+struct PrefillParams {
+    const void* q;
+    const void* k;               // cache [B, Smax, Hkv, D] by strides, or (PAGED) pool [num_pages, page_size, Hkv, D]
+    const void* v;
+    void* o;
+    float* lse;                  // optional [B, H, Sq]
+    const int32_t* seqlens;      // optional [B]
+    int64_t q_sb, q_sh, q_ss;    // element strides
+    int64_t k_sb, k_sh, k_ss;    // PAGED: k_sb / v_sb are the page strides
+    int64_t v_sb, v_sh, v_ss;
+    int64_t o_sb, o_sh, o_ss;
+    int32_t B, H, Sq, Smax;
+    int32_t nqblk;               // ceil(Sq / 256)
+    int32_t kv_group;            // H / Hkv
+    float scale_log2;            // softmax_scale * log2(e)
+    const int32_t* block_table;  // PAGED: [B][max_pages] page ids
+    int64_t bt_sb;
+    int32_t page_size, num_pages;
+};
+
+typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
+
+template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const PrefillParams p) {
+    constexpr int NW = FWD_WAVES, BLOCK_M = FWD_BLOCK_M;
+    using E = Elem<T>;
+    using v8 = typename E::v8;
+    using v4 = typename E::v4;
+    typedef __attribute__((address_space(3))) v8 lds_v8;
+    constexpr int KS = D / 16;                // k-steps of the QK^T product
+    constexpr int DB = D / 32;                // 32-wide d blocks of the PV product
+    constexpr int TILE_BYTES = BLOCK_N * D * 2;
+    constexpr int BUF_BYTES = 2 * TILE_BYTES; // K image + V image
+    constexpr int HALF_TILE = TILE_BYTES / 2; // 32 keys
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    lds_char* const smem_l = (lds_char*)smem;   // [buf][K|V][TILE_BYTES]
+    const uint32_t smem_base = (uint32_t)(uintptr_t)smem_l;   // LDS byte address (wave-uniform)
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31;
+    const int h = lane >> 5;
+
+    // ---- block -> (q block, batch*head): heaviest (longest causal row) blocks first ----------------
+    const int BH = p.B * p.H;
+    const int n = blockIdx.x;
+    const int qrank = n / BH;
+    const int bh = n - qrank * BH;
+    const int qblk = CAUSAL ? (p.nqblk - 1 - qrank) : qrank;
+    const int b = bh / p.H;
+    const int hh = bh - b * p.H;
+
+    const int q0 = qblk * BLOCK_M;
+    const int wave_q0 = q0 + wave * WAVE_M;
+    const int my_q = wave_q0 + r;
+
+    // ---- (1) the batch's length and causal offset, from the device ----------------------------------
+    int kv_len = p.Smax;
+    if (p.seqlens) kv_len = min(kv_len, max(p.seqlens[b], 0));
+    kv_len = __builtin_amdgcn_readfirstlane(kv_len);
+    const int off = kv_len - p.Sq;                       // row i sees key j iff j <= i + off (may be negative)
+    const int kv_end = CAUSAL ? max(0, min(kv_len, q0 + BLOCK_M + off)) : kv_len;       // keys the block needs
+    const int wave_kv_end = CAUSAL ? min(kv_len, wave_q0 + WAVE_M + off) : kv_len;      // keys this wave needs (<= 0: none)
+    const int my_lim = my_q + off;                       // last key this row sees under the causal cut
+    const int nt = (kv_end + BLOCK_N - 1) / BLOCK_N;
+
+    const int kvh = hh / p.kv_group;
+    const T* __restrict__ qp = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)hh * p.q_sh;
+    // contiguous: this batch's and head's slab; paged: the head's offset inside every page (the page base is added per tile)
+    const char* kp = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * 2;
+    const char* vp = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * 2;
+
+    // ---- Q fragments: B operand of S^T = K Q^T, lane (r,h) holds Q[my_q][16 ks + 8 h .. +7] -----------
+    v8 qf[KS];
+    {
+        const int qrow = min(my_q, p.Sq - 1);
+        const T* src = qp + (int64_t)qrow * p.q_ss + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const v8*)(src + 16 * ks);
+    }
+
+    // ---- K/V staging by LDS-DMA, as in fa3_fwd_kernel: wave w issues pieces w, w+8, ...; piece i covers LDS rows 4i..4i+3, the
+    // XOR swizzle is applied to the per-lane SOURCE chunk
+    constexpr int PIECES = TILE_BYTES / 1024;            // 16 (D=128) or 8 (D=64)
+    constexpr int PPW = PIECES / NW;                     // pieces per wave
+    int dma_key[PPW];
+    int dma_col;                                         // element offset of the source chunk in its key row
+    {
+        const int R0 = 4 * wave + (lane >> 4);           // LDS row of piece `wave`
+        const int sw = ((R0 & 3) << 2) | ((R0 >> 2) & 3);   // rows 4*NW apart share the swizzle term
+        const int cc = (lane & 15) ^ sw;                 // logical chunk stored at this lane's position
+        if constexpr (D == 128) {
+            dma_col = cc * 8;
+#pragma unroll
+            for (int t = 0; t < PPW; ++t) dma_key[t] = R0 + 4 * NW * t;
+        } else {
+            dma_col = (cc & 7) * 8;
+#pragma unroll
+            for (int t = 0; t < PPW; ++t) dma_key[t] = 2 * (R0 + 4 * NW * t) + (cc >> 3);
+        }
+    }
+    // per-lane byte offsets are loop invariant; the tile steps the descriptor base (SALU only, no per-tile VALU)
+    uint32_t kvoff[PPW], vvoff[PPW];
+#pragma unroll
+    for (int t = 0; t < PPW; ++t) {
+        kvoff[t] = (uint32_t)(dma_key[t] * (int)p.k_ss + dma_col) * 2u;
+        vvoff[t] = (uint32_t)(dma_key[t] * (int)p.v_ss + dma_col) * 2u;
+    }
+    // (2) paged: page id of the NEXT tile to fetch (a scalar load issued behind the previous tile's DMA), its index in the table
+    // row and the token offset inside the page.  dma_tile is called for j = 0, 1, 2, ... in order, and only for j < nt, i.e. for
+    // keys below kv_end <= len_b: entries at and past ceil(len_b / page_size) are never read.
+    const prefill_table_ptr table = PAGED ? (prefill_table_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
+    int pg_next = 0, pg_idx = 0, pg_tok = 0;
+    if constexpr (PAGED) {
+        if (nt > 0) pg_next = table[0];
+    }
+    auto dma_tile = [&](auto bufc, int j) {
+        constexpr int BUF = decltype(bufc)::value;
+        // (3) the descriptors end at the tile's last valid key: rows at and past len_b read as zeros
+        const int nk = min(BLOCK_N, kv_len - j * BLOCK_N);
+        int64_t koff, voff;                  // element offsets of the tile's first key row from kp / vp
+        if constexpr (PAGED) {
+            const int pg = min(max(pg_next, 0), p.num_pages - 1);     // device data: never an address outside the pool
+            koff = (int64_t)pg * p.k_sb + (int64_t)pg_tok * p.k_ss;
+            voff = (int64_t)pg * p.v_sb + (int64_t)pg_tok * p.v_ss;
+        } else {
+            koff = (int64_t)j * BLOCK_N * p.k_ss;
+            voff = (int64_t)j * BLOCK_N * p.v_ss;
+        }
+        const srd_t ksrd = __builtin_amdgcn_make_buffer_rsrc((void*)(kp + koff * 2), 0, (int)((int64_t)(nk - 1) * p.k_ss * 2 + D * 2), 0x00020000);
+        const srd_t vsrd = __builtin_amdgcn_make_buffer_rsrc((void*)(vp + voff * 2), 0, (int)((int64_t)(nk - 1) * p.v_ss * 2 + D * 2), 0x00020000);
+#pragma unroll
+        for (int t = 0; t < PPW; ++t) {
+            const uint32_t kd = smem_base + BUF * BUF_BYTES + (wave + NW * t) * 1024;
+            lds_dma16_buf(ksrd, kvoff[t], kd);
+            lds_dma16_buf(vsrd, vvoff[t], kd + TILE_BYTES);
+        }
+        if constexpr (PAGED) {
+            pg_tok += BLOCK_N;
+            if (pg_tok == p.page_size) {
+                pg_tok = 0;
+                ++pg_idx;
+                if (j + 1 < nt) pg_next = table[pg_idx];
+            }
+        }
+    };
+
+    // ---- per-lane LDS read offsets, loop invariant (see fa3_fwd_kernel) ----------
+    uint32_t koff[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) koff[ks] = smem_base + tile_off<D>(r, 2 * ks + h);   // absolute LDS address
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(koff[ks]));
+    const int g1 = (lane >> 4) & 1;
+    const int tq = (lane & 15) >> 2;
+    const int tp = lane & 3;
+    constexpr int NS2 = (D == 128) ? 1 : 2;   // D=64: two keys per LDS row, the swizzle term depends on s2
+    uint32_t voff[NS2][DB][2];
+#pragma unroll
+    for (int s2 = 0; s2 < NS2; ++s2)
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int hi = 0; hi < 2; ++hi)
+            {
+                voff[s2][db][hi] = smem_base + tile_off<D>(16 * s2 + 4 * h + tq + 8 * hi, db * 4 + 2 * g1 + (tp >> 1)) + 8 * (tp & 1);
+                asm volatile("" : "+v"(voff[s2][db][hi]));
+            }
+
+    f32x16 o[DB];
+#pragma unroll
+    for (int i = 0; i < DB; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[i][e] = 0.f;
+    float m_run = -1e30f;   // reference max of the exponentials, raw score units
+    float l_run = 0.f;      // this lane's share of the row sum
+    const float c = p.scale_log2;
+    const float thr = 8.0f / c;                 // deferred max: raw-score headroom (2^8 in the exponent) before O is rescaled
+    float m_thr = -1e30f, mc = -1e30f * c;      // m_run + thr and m_run * c, updated with m_run
+
+    // ---- one K/V tile: S^T = K Q^T, online softmax, O^T += V^T P^T -------------------------------------------
+    auto compute_tile = [&](auto bufc, int key_base) {
+        constexpr int BUF = decltype(bufc)::value;
+        const lds_char* kimg = (const lds_char*)(uintptr_t)(BUF * BUF_BYTES);   // koff[]/voff[] carry the LDS base
+        const lds_char* vimg = kimg + TILE_BYTES;
+
+        f32x16 s[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) s[kb][e] = 0.f;
+        constexpr int NQK = 2 * KS, PF = 4;
+        v8 afr[PF];
+#pragma unroll
+        for (int i = 0; i < PF; ++i) afr[i] = *(const lds_v8*)(kimg + koff[i % KS] + (i / KS) * HALF_TILE);
+#pragma unroll
+        for (int i = 0; i < NQK; ++i) {
+            s[i / KS] = E::mfma(afr[i % PF], qf[i % KS], s[i / KS]);
+            if (i + PF < NQK) afr[i % PF] = *(const lds_v8*)(kimg + koff[(i + PF) % KS] + ((i + PF) / KS) * HALF_TILE);
+        }
+        // pin the read / MFMA interleave: PF reads, then one MFMA per read, then the last PF MFMAs
+        __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);
+#pragma unroll
+        for (int i = 0; i < NQK - PF; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, PF, 0);
+
+        // mask: wave-uniform test, only the tiles on the wave's causal diagonal and the batch's last tile pay
+        const bool need_mask = (key_base + BLOCK_N > kv_len) || (CAUSAL && key_base + BLOCK_N - 1 > wave_q0 + off);
+        if (need_mask) {
+            asm volatile("" ::: "memory");   // keep this a real (wave-uniform) branch, not 32 v_cmp + 32 v_cndmask on every tile
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int key = key_base + 32 * kb + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    bool ok = key < kv_len;
+                    if (CAUSAL) ok = ok && (key <= my_lim);
+                    s[kb][e] = ok ? s[kb][e] : -INFINITY;
+                }
+        }
+
+        // online softmax; a row lives in lanes (l, l^32)
+        float mx = max16_first(s[0]);
+        mx = max16_next(mx, s[1]);
+        mx = row_pair_max_asm(mx);
+        if (__builtin_amdgcn_ballot_w64(mx > m_thr) != 0) {
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = fast_exp2((m_run - m_new) * c);
+            m_run = m_new;
+            m_thr = m_new + thr;
+            mc = m_new * c;
+            l_run *= alpha;
+#pragma unroll
+            for (int i = 0; i < DB; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) o[i][e] *= alpha;
+        }
+        float psum0 = 0.f, psum1 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            s[0][e] = fast_exp2(__builtin_fmaf(s[0][e], c, -mc));
+            s[1][e] = fast_exp2(__builtin_fmaf(s[1][e], c, -mc));
+            psum0 += s[0][e];
+            asm volatile("" : "+v"(psum0));   // keeps SLP from pairing the sums into v_pk_add_f32
+            psum1 += s[1][e];
+        }
+        l_run += psum0 + psum1;
+
+        // O^T += V^T P^T
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                v8 ph, pl;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float pv = s[kb][8 * s2 + e];
+                    const T hi = (T)pv;
+                    ph[e] = hi;
+                    if (SPLITP) pl[e] = (T)(pv - (float)hi);
+                }
+                constexpr int S2I = (D == 128) ? 0 : 1;
+                const int koffs = kb * HALF_TILE + ((D == 128) ? s2 * 16 * 256 : 0);
+#pragma unroll
+                for (int db = 0; db < DB; ++db) {
+                    const v4 lo = E::tr_read(vimg + voff[s2 * S2I][db][0] + koffs);
+                    const v4 hi4 = E::tr_read(vimg + voff[s2 * S2I][db][1] + koffs);
+                    v8 a;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        a[e] = lo[e];
+                        a[4 + e] = hi4[e];
+                    }
+                    o[db] = E::mfma(a, ph, o[db]);
+                    if (SPLITP) o[db] = E::mfma(a, pl, o[db]);
+                }
+            }
+    };
+
+    auto step = [&](auto bufc, int j) {
+        constexpr int BUF = decltype(bufc)::value;
+        if (j + 1 < nt) dma_tile(IC<BUF ^ 1>{}, j + 1);   // lands in the other buffer under this tile's math
+        if (j * BLOCK_N < wave_kv_end) compute_tile(bufc, j * BLOCK_N);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed ...
+        __builtin_amdgcn_s_waitcnt(0xC07F);               // (lgkmcnt(0): this wave's LDS reads are done)
+        __builtin_amdgcn_s_barrier();                     // ... and so have everybody else's
+    };
+
+    if (nt > 0) dma_tile(IC<0>{}, 0);
+    // Q must have LANDED before the loop (see fa3_fwd_kernel: else its vmcnt waits drain the K/V prefetch every iteration)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int j = 0; j < nt; j += 2) {
+        step(IC<0>{}, j);
+        if (j + 1 < nt) step(IC<1>{}, j + 1);
+    }
+
+    // ---- epilogue: normalise once; a row with no visible key -> zeros, LSE = -inf ------------
+    const float l_tot = row_pair_sum(l_run);
+    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+    if constexpr (sizeof(OT) == 2) {
+        // 16-bit store through LDS (free after the loop's last barrier) so that one store instruction covers whole rows: see fa3_fwd_kernel
+        typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
+        constexpr int RB = D * 2, CPRW = RB / 16;      // row bytes, 16-byte chunks per row
+        const uint32_t lbase = smem_base + wave * (32 * RB);
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int g = 0; g < 4; g += 2) {
+                v4 wa, wb;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    wa[e] = (T)(o[db][4 * g + e] * inv);
+                    wb[e] = (T)(o[db][4 * g + 4 + e] * inv);
+                }
+                u32x2 a = __builtin_bit_cast(u32x2, wa), bq = __builtin_bit_cast(u32x2, wb);
+                auto r0 = __builtin_amdgcn_permlane32_swap(a[0], bq[0], false, false);
+                auto r1 = __builtin_amdgcn_permlane32_swap(a[1], bq[1], false, false);
+                u32x4 w = {r0[0], r1[0], r0[1], r1[1]};
+                const uint32_t ch = 4 * db + g + h;
+                *(lds_u32x4_t*)(uintptr_t)(lbase + r * RB + ((ch ^ (r & (CPRW - 1))) << 4)) = w;
+            }
+        store_rows_from_lds<RB>(lbase, lane, (char*)((OT*)p.o + (int64_t)b * p.o_sb + (int64_t)hh * p.o_sh + (int64_t)wave_q0 * p.o_ss),
+                                p.o_ss * 2, p.Sq - wave_q0);
+    } else if (my_q < p.Sq) {      // fp32 rows straight from the accumulators
+        OT* orow = (OT*)p.o + (int64_t)b * p.o_sb + (int64_t)hh * p.o_sh + (int64_t)my_q * p.o_ss;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int d = db * 32 + 8 * g + 4 * h;
+                f32x4 w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = o[db][4 * g + e] * inv;
+                *(f32x4*)(orow + d) = w;
+            }
+    }
+    if (my_q < p.Sq && p.lse && h == 0) {
+        const float lse = l_tot > 0.f ? (m_run * c + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : -INFINITY;
+        p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;
+    }
+}
+
+}  // namespace pfa

@@ -16,8 +16,6 @@ constexpr int kTargetWorkgroups = 512;   // two 4-wave workgroups per CU of the 
 constexpr int kMinSplitKeys = 256;       // every split covers at least four 64-key tiles
 constexpr int kMaxSplits = 128;
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 struct Plan {
     int G = 1, nrb = 0, nsplit = 1;
     int64_t items = 0;           // workgroups of the main kernel
@@ -43,42 +41,13 @@ Plan plan(const pfa_fa3_decode_args* a) {
 }
 
 int check(const pfa_fa3_decode_args* a) {
-    if (!a) return PFA_ERR_NULL;
-    if (a->size != sizeof(pfa_fa3_decode_args)) return PFA_ERR_STRUCT_SIZE;
-    if (a->flags != 0 || a->reserved0 != 0) return PFA_ERR_FLAGS;
-    if (!a->q || !a->k_cache || !a->v_cache || !a->o) return PFA_ERR_NULL;
-    if (a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->Smax <= 0 || a->Sq < 1 || a->Sq > 64) return PFA_ERR_SHAPE;
-    if (a->H % a->Hkv != 0) return PFA_ERR_SHAPE;
-    if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
-    if (a->dtype_in != PFA_DTYPE_BF16 && a->dtype_in != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
-    if (a->dtype_out != a->dtype_in && a->dtype_out != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
-    if (!(a->softmax_scale > 0.f) || !isfinite(a->softmax_scale)) return PFA_ERR_SHAPE;
-    const int64_t st8[] = {a->q_stride_b, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s,
-                           a->v_stride_b, a->v_stride_h, a->v_stride_s};
-    for (int64_t s : st8)
-        if (s % 8 != 0) return PFA_ERR_STRIDE;
-    const int64_t st4[] = {a->o_stride_b, a->o_stride_h, a->o_stride_s};
-    for (int64_t s : st4)
-        if (s % 4 != 0) return PFA_ERR_STRIDE;
-    if (!aligned16(a->q) || !aligned16(a->k_cache) || !aligned16(a->v_cache) || !aligned16(a->o)) return PFA_ERR_ALIGN;
-    if (a->lse && (reinterpret_cast<uintptr_t>(a->lse) & 3u)) return PFA_ERR_ALIGN;
-    if (a->cache_seqlens && (reinterpret_cast<uintptr_t>(a->cache_seqlens) & 3u)) return PFA_ERR_ALIGN;
-    // a tile's K / V rows are addressed by 32-bit offsets from a per-tile buffer descriptor
-    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_s * 2 * 64 + 256 > 0x7fffffffLL || a->v_stride_s * 2 * 64 + 256 > 0x7fffffffLL)
-        return PFA_ERR_STRIDE;
-    if (a->block_table) {
-        // Smax is the logical capacity max_pages * page_size; a 64-key tile must lie inside one page
-        if (a->page_size <= 0 || a->page_size % pfa::dec::SPLIT_ALIGN != 0 || a->num_pages <= 0) return PFA_ERR_SHAPE;
-        if (a->Smax % a->page_size != 0 || a->block_table_stride_b < a->Smax / a->page_size) return PFA_ERR_SHAPE;
-        if (reinterpret_cast<uintptr_t>(a->block_table) & 3u) return PFA_ERR_ALIGN;
-    } else if (a->page_size != 0 || a->num_pages != 0 || a->block_table_stride_b != 0) {
-        return PFA_ERR_FLAGS;
-    }
+    const int st = pfa::check_cache_args(a, 64);
+    if (st != PFA_OK) return st;
     const Plan pl = plan(a);
     if (pl.items > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (a->D / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
     if (pl.ws_bytes) {
         if (!a->workspace || a->workspace_bytes < pl.ws_bytes) return PFA_ERR_NULL;
-        if (!aligned16(a->workspace)) return PFA_ERR_ALIGN;
+        if (!pfa::aligned16(a->workspace)) return PFA_ERR_ALIGN;
     }
     return PFA_OK;
 }

@@ -1,6 +1,7 @@
 // pfa_host.h -- host-side glue the entry points of libpfa_hip.so share (internal: nothing here is exported).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "pfa_hip.h"
@@ -49,6 +50,45 @@ inline void fill_mask(Params& p, const pfa_fa3_args* a) {
     } else {
         p.mask = a->key_mask; p.m_sb = a->key_mask_stride_b; p.m_sh = 0; p.m_sq = 0; p.m_sk = 1;
     }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The field rules pfa_fa3_decode and pfa_fa3_prefill share (include/pfa_hip.h, pfa_fa3_decode_args), in the order their errors are
+// reported: everything but the limits that depend on the kernel (key mask, grid, workspace).  max_sq: the most query rows the caller takes.
+inline int check_cache_args(const pfa_fa3_decode_args* a, int max_sq) {
+    if (!a) return PFA_ERR_NULL;
+    if (a->size != sizeof(pfa_fa3_decode_args)) return PFA_ERR_STRUCT_SIZE;
+    if (a->flags != 0 || a->reserved0 != 0) return PFA_ERR_FLAGS;
+    if (!a->q || !a->k_cache || !a->v_cache || !a->o) return PFA_ERR_NULL;
+    if (a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->Smax <= 0 || a->Sq < 1 || a->Sq > max_sq) return PFA_ERR_SHAPE;
+    if (a->H % a->Hkv != 0) return PFA_ERR_SHAPE;
+    if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
+    if (a->dtype_in != PFA_DTYPE_BF16 && a->dtype_in != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
+    if (a->dtype_out != a->dtype_in && a->dtype_out != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
+    if (!(a->softmax_scale > 0.f) || !isfinite(a->softmax_scale)) return PFA_ERR_SHAPE;
+    const int64_t st8[] = {a->q_stride_b, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s,
+                           a->v_stride_b, a->v_stride_h, a->v_stride_s};
+    for (int64_t s : st8)
+        if (s % 8 != 0) return PFA_ERR_STRIDE;
+    const int64_t st4[] = {a->o_stride_b, a->o_stride_h, a->o_stride_s};
+    for (int64_t s : st4)
+        if (s % 4 != 0) return PFA_ERR_STRIDE;
+    if (!aligned16(a->q) || !aligned16(a->k_cache) || !aligned16(a->v_cache) || !aligned16(a->o)) return PFA_ERR_ALIGN;
+    if (a->lse && (reinterpret_cast<uintptr_t>(a->lse) & 3u)) return PFA_ERR_ALIGN;
+    if (a->cache_seqlens && (reinterpret_cast<uintptr_t>(a->cache_seqlens) & 3u)) return PFA_ERR_ALIGN;
+    // a tile's K / V rows are addressed by 32-bit offsets from a per-tile buffer descriptor
+    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_s * 2 * 64 + 256 > 0x7fffffffLL || a->v_stride_s * 2 * 64 + 256 > 0x7fffffffLL)
+        return PFA_ERR_STRIDE;
+    if (a->block_table) {
+        // Smax is the logical capacity max_pages * page_size; a 64-key tile must lie inside one page
+        if (a->page_size <= 0 || a->page_size % 64 != 0 || a->num_pages <= 0) return PFA_ERR_SHAPE;
+        if (a->Smax % a->page_size != 0 || a->block_table_stride_b < a->Smax / a->page_size) return PFA_ERR_SHAPE;
+        if (reinterpret_cast<uintptr_t>(a->block_table) & 3u) return PFA_ERR_ALIGN;
+    } else if (a->page_size != 0 || a->num_pages != 0 || a->block_table_stride_b != 0) {
+        return PFA_ERR_FLAGS;
+    }
+    return PFA_OK;
 }
 
 }  // namespace pfa

@@ -1,4 +1,4 @@
-"""A paged KV cache for one attention layer, read by ``ops.fa3_decode(..., block_table=...)``.
+"""A paged KV cache for one attention layer, read by ``ops.fa3_decode`` and ``ops.fa3_prefill_cache`` ``(..., block_table=...)``.
 
 The cache is a pool of fixed-size pages (``[num_pages, page_size, Hkv, D]`` for K and for V) plus, per sequence slot, a row of a
 device block table and a device length.  Which page a sequence's next tokens go to is decided on the host, from a host mirror of
@@ -6,7 +6,7 @@ the lengths (the caller says how many tokens it appends, so the host always know
 device.  The device tensors ``block_table`` and ``cache_seqlens`` are allocated once and updated in place, so a captured graph of
 ``decode`` keeps seeing them; pages a sequence will grow into during replays are assigned ahead with ``reserve``.
 
-Everything except ``decode`` (the HIP kernel) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
+Everything except ``decode`` and ``prefill`` (the HIP kernels) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
 The token append is a few KiB per step and stays torch ops; the hot path is the decode kernel.
 """
 
@@ -215,3 +215,11 @@ class PagedKVCache:
         through.  -> ``(o, lse)``."""
         table, lens = self._rows(slots)
         return ops.fa3_decode(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
+
+    def prefill(self, q: torch.Tensor, slots: Slots = None, **kw):
+        """``ops.fa3_prefill_cache`` of ``q [B, H, Sq, D]`` (any Sq: a prompt chunk, the suffix behind shared prefix pages, a
+        speculative step) against the sequences in ``slots``, which are chosen and captured as in ``decode``.  ``append`` the rows'
+        own K / V first: the lengths count them, and ``causal`` (the default) is bottom-right aligned.  Keyword arguments
+        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ...) pass through.  -> ``(o, lse)``."""
+        table, lens = self._rows(slots)
+        return ops.fa3_prefill_cache(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)

@@ -460,27 +460,9 @@ def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=Non
     return _FA3Function.apply(q, k, v, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype, bool(return_weights), weights_dtype)
 
 
-def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
-               key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
-               out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
-               out: Optional[torch.Tensor] = None,
-               block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Decode attention over a KV cache (``pfa_fa3_decode``): a few new query rows per batch against the cached keys.  Inference only.
-
-    q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
-    k_cache / v_cache: ``[B,Hkv,Smax,D]``-shaped views, H a multiple of Hkv (a flash-attn ``[B,Smax,Hkv,D]`` buffer is passed as
-    ``.transpose(1, 2)``; a slice of a larger preallocated cache is just a view).  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of
-    valid keys per batch.  key_mask: optional ``[B,Smax]`` (0 / False = masked); given alone, each batch's length is derived from it
-    on the device, so a static cache's unfilled tail is never read.  ``causal`` is bottom-right aligned: row i sees key j iff
-    j <= len_b - Sq + i (for Sq = 1 it changes nothing).  Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.
-    No host synchronisation and no cached allocation: capturable in ``torch.cuda.graph``.
-
-    Paged cache: with ``block_table`` (int32 ``[B, max_pages]`` DEVICE tensor, last dim contiguous) k_cache / v_cache are pools,
-    ``[num_pages,Hkv,page_size,D]``-shaped views (a flash-attn ``[num_pages,page_size,Hkv,D]`` pool is passed as ``.transpose(1, 2)``),
-    page_size a multiple of 64: logical key j of batch b lives in page ``block_table[b, j // page_size]`` at token ``j % page_size``.
-    Smax is then ``max_pages * page_size``; cache_seqlens, key_mask (``[B, max_pages * page_size]``) and causal are over logical keys.
-    Table entries at and past ``ceil(len_b / page_size)`` are never read; page ids are clamped into the pool by the kernel.  The
-    result is bit for bit that of the contiguous call on the gathered cache."""
+def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table):
+    """Validation and marshalling ``fa3_decode`` and ``fa3_prefill_cache`` share (both take ``pfa_fa3_decode_args``): the operands,
+    the output buffer and the block table.  -> ``(args, out, Smax)``; ``entry`` names the C entry point in the messages."""
     if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
     B, H, Sq, D = q.shape
@@ -506,7 +488,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise ValueError("q, k_cache, v_cache must share dtype bf16 or fp16")
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda) or k_cache.device != q.device or v_cache.device != q.device:
-        raise ValueError("pfa_fa3_decode needs device tensors on one device (there is no CPU path)")
+        raise ValueError(f"{entry} needs device tensors on one device (there is no CPU path)")
     odt = q.dtype if out_dtype is None else out_dtype
     if odt not in (q.dtype, torch.float32):
         raise ValueError("output dtype must be the input dtype or fp32")
@@ -525,6 +507,46 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     if block_table is not None:
         a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
         a.page_size, a.num_pages = page_size, num_pages
+    return a, out, Smax
+
+
+def _set_cache_seqlens(a, cache_seqlens, q, keep) -> None:
+    """``cache_seqlens`` (int32 ``[B]`` device tensor, or None) into the argument block; a converted copy is appended to ``keep``."""
+    B = q.shape[0]
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or not cache_seqlens.is_cuda or cache_seqlens.device != q.device:
+            raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
+        if cache_seqlens.shape != (B,):
+            raise ValueError("cache_seqlens must have B entries")
+        sl = cache_seqlens if cache_seqlens.dtype == torch.int32 and cache_seqlens.is_contiguous() else \
+            cache_seqlens.to(torch.int32).contiguous()
+        a.cache_seqlens = sl.data_ptr()
+        keep.append(sl)
+
+
+def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
+               key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
+               out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
+               out: Optional[torch.Tensor] = None,
+               block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Decode attention over a KV cache (``pfa_fa3_decode``): a few new query rows per batch against the cached keys.  Inference only.
+
+    q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
+    k_cache / v_cache: ``[B,Hkv,Smax,D]``-shaped views, H a multiple of Hkv (a flash-attn ``[B,Smax,Hkv,D]`` buffer is passed as
+    ``.transpose(1, 2)``; a slice of a larger preallocated cache is just a view).  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of
+    valid keys per batch.  key_mask: optional ``[B,Smax]`` (0 / False = masked); given alone, each batch's length is derived from it
+    on the device, so a static cache's unfilled tail is never read.  ``causal`` is bottom-right aligned: row i sees key j iff
+    j <= len_b - Sq + i (for Sq = 1 it changes nothing).  Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.
+    No host synchronisation and no cached allocation: capturable in ``torch.cuda.graph``.
+
+    Paged cache: with ``block_table`` (int32 ``[B, max_pages]`` DEVICE tensor, last dim contiguous) k_cache / v_cache are pools,
+    ``[num_pages,Hkv,page_size,D]``-shaped views (a flash-attn ``[num_pages,page_size,Hkv,D]`` pool is passed as ``.transpose(1, 2)``),
+    page_size a multiple of 64: logical key j of batch b lives in page ``block_table[b, j // page_size]`` at token ``j % page_size``.
+    Smax is then ``max_pages * page_size``; cache_seqlens, key_mask (``[B, max_pages * page_size]``) and causal are over logical keys.
+    Table entries at and past ``ceil(len_b / page_size)`` are never read; page ids are clamped into the pool by the kernel.  The
+    result is bit for bit that of the contiguous call on the gathered cache."""
+    a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
+    B, H, Sq, _ = q.shape
     keep = []
     if key_mask is not None:
         if key_mask.shape != (B, Smax):
@@ -538,15 +560,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         keep.append(km)
         if cache_seqlens is None:
             cache_seqlens = _mask_bound(km)
-    if cache_seqlens is not None:
-        if not isinstance(cache_seqlens, torch.Tensor) or not cache_seqlens.is_cuda or cache_seqlens.device != q.device:
-            raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
-        if cache_seqlens.shape != (B,):
-            raise ValueError("cache_seqlens must have B entries")
-        sl = cache_seqlens if cache_seqlens.dtype == torch.int32 and cache_seqlens.is_contiguous() else \
-            cache_seqlens.to(torch.int32).contiguous()
-        a.cache_seqlens = sl.data_ptr()
-        keep.append(sl)
+    _set_cache_seqlens(a, cache_seqlens, q, keep)
     lse = None
     if return_lse:
         lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
@@ -563,5 +577,39 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         raise ValueError(f"pfa_fa3_decode: {_capi.status_string(st)}")
     _capi.check_status(st)
     for t in keep:   # tensors made here must outlive the enqueued kernels
+        t.record_stream(stream)
+    return out, lse
+
+
+def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
+                      causal: bool = True, softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
+                      return_lse: bool = False, out: Optional[torch.Tensor] = None,
+                      block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Forward over a KV cache (``pfa_fa3_prefill``): ANY number of new query rows per batch against the cached keys -- the later
+    chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
+
+    The tensor conventions are those of ``fa3_decode``: q ``[B,H,Sq,D]`` (Sq >= 1, D 64 or 128, bf16 / fp16), k_cache / v_cache
+    ``[B,Hkv,Smax,D]``-shaped views, or with ``block_table`` (int32 ``[B, max_pages]`` device tensor) pools
+    ``[num_pages,Hkv,page_size,D]``-shaped, page_size a multiple of 64.  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of valid
+    keys per batch, the query rows' own keys included (append first, then call); keys at and past it are never read.  ``causal`` is
+    bottom-right aligned: row i sees key j iff j <= len_b - Sq + i; with len_b < Sq the first Sq - len_b rows see nothing (O = 0, LSE =
+    -inf).  There is no key mask (``fa3_decode`` takes one) and no split over keys: the call is one launch of the 8-wave MFMA kernel,
+    256 query rows per workgroup, and wants B * H * ceil(Sq / 256) of the order of the CU count to fill the chip.
+    Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.  No host synchronisation, no workspace and no cached
+    allocation: capturable in ``torch.cuda.graph`` and valid while lengths, table and cache change between replays.  A paged call
+    returns the bits of the contiguous call on the gathered cache."""
+    a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
+    keep = []
+    _set_cache_seqlens(a, cache_seqlens, q, keep)
+    lse = None
+    if return_lse:
+        lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
+        a.lse = lse.data_ptr()
+    stream = torch.cuda.current_stream(q.device)
+    st = _capi.load().pfa_fa3_prefill(C.byref(a), C.c_void_p(stream.cuda_stream))
+    if st in (-1, -3, -4, -5, -6, -7, -10):
+        raise ValueError(f"pfa_fa3_prefill: {_capi.status_string(st)}")
+    _capi.check_status(st)
+    for t in keep:   # tensors made here must outlive the enqueued kernel
         t.record_stream(stream)
     return out, lse

@@ -1,0 +1,428 @@
+"""GPU tests of the forward over a KV cache (``ops.fa3_prefill_cache`` / ``pfa_fa3_prefill``, ``PagedKVCache.prefill``): any number
+of query rows against a contiguous or paged cache, bottom-right causal per batch.
+
+Every cache handed to the kernel holds NaN at and past each batch's length, and every pool page no table entry names is NaN, so a
+read past ``len_b`` (the descriptor bound) or of a page that is not the sequence's shows as a non-finite output: every test asserts
+that the outputs are finite.  The reference is fp64 attention with the bottom-right rule, computed on the device from the clean
+tensors (the one of tests/test_hip_decode.py, restated here with its bound: |err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6
+for a 16-bit output, 1e-3 max-abs for fp32, 2e-3 on the LSE).  Paged against contiguous needs no tolerance: ``torch.equal``.
+
+Only in-range page ids and legal arguments ever reach the device; refusals are tested on the host (tests/test_prefill_host.py)."""
+
+from __future__ import annotations
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
+NAN = float("nan")
+
+
+def _dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+def _gen(seed):
+    return torch.Generator(device=_dev()).manual_seed(seed)
+
+
+def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed):
+    g = _gen(seed)
+    dev = _dev()
+    q = torch.randn(B, Sq, H, D, generator=g, device=dev).to(dtype).permute(0, 2, 1, 3)
+    k = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
+    v = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
+    return q, k, v
+
+
+def _lens(lens, dev=None):
+    return torch.tensor(lens, dtype=torch.int32, device=dev or _dev())
+
+
+def _poison(k, v, lens):
+    """Copies of the caches with NaN at and past each batch's length (what an unfilled tail may hold)."""
+    kn, vn = k.clone(), v.clone()
+    for b, n in enumerate(lens):
+        kn[b, :, n:] = NAN
+        vn[b, :, n:] = NAN
+    return kn, vn
+
+
+def _scatter(k, v, page, seed, layout="phsd", spare=5):
+    """Scatter contiguous [B, Hkv, Smax, D] caches over pools in a random page order.  -> (k_pool, v_pool, table) with the pools as
+    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN (and so does whatever NaN the caches carry)."""
+    B, Hkv, Smax, D = k.shape
+    assert Smax % page == 0
+    pages = Smax // page
+    NP = B * pages + spare
+    dev = k.device
+    perm = torch.randperm(NP, generator=torch.Generator().manual_seed(seed))[:B * pages]
+    table = perm.to(torch.int32).reshape(B, pages).to(dev)
+    pools = []
+    for src in (k, v):
+        if layout == "phsd":        # flash-attn style [num_pages, page, Hkv, D], passed transposed
+            pool = torch.full((NP, page, Hkv, D), NAN, dtype=k.dtype, device=dev).transpose(1, 2)
+        elif layout == "hpsd":
+            pool = torch.full((NP, Hkv, page, D), NAN, dtype=k.dtype, device=dev)
+        else:                       # every second page of a larger pool, whose pages also have room for 64 more keys
+            pool = torch.full((2 * NP, Hkv, page + 64, D), NAN, dtype=k.dtype, device=dev)[::2, :, :page]
+        pool[perm.to(dev)] = src.reshape(B, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(B * pages, Hkv, page, D)
+        pools.append(pool)
+    return pools[0], pools[1], table
+
+
+def _reference(q, k, v, seqlens, causal, scale):
+    """fp64 on the GPU from CLEAN caches: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2)."""
+    B, H, Sq, D = q.shape
+    Hkv, Smax = k.shape[1], k.shape[2]
+    g = H // Hkv
+    kd = k.double().repeat_interleave(g, dim=1)
+    vd = v.double().repeat_interleave(g, dim=1)
+    s = (q.double() @ kd.transpose(-1, -2)) * scale
+    j = torch.arange(Smax, device=q.device)
+    i = torch.arange(Sq, device=q.device)
+    L = seqlens.to(q.device).long() if seqlens is not None else torch.full((B,), Smax, device=q.device)
+    vis = (j[None, None, :] < L[:, None, None]).expand(B, Sq, Smax)
+    if causal:
+        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])   # bottom-right, per batch
+    s = s.masked_fill(~vis[:, None], float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    safe = torch.where(l > 0, l, torch.ones_like(l))
+    pn = p / safe
+    o = pn @ vd
+    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
+    return o, lse, pn.norm(dim=-1, keepdim=True)
+
+
+def _check(got, ref, pnorm, vmax, dtype):
+    assert bool(torch.isfinite(got).all()), "non-finite output: a key at or past len_b, or a page of another sequence, was read"
+    err = (got.double() - ref).abs()
+    print(f"max-abs vs reference {float(err.max()):.3e} ({got.dtype})")
+    if got.dtype == torch.float32:
+        assert float(err.max()) <= 1e-3, float(err.max())
+        return
+    eps = EPS[dtype]
+    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
+    worst = float((err - bound).max())
+    assert worst <= 0, f"max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
+
+
+def _check_lse(o, lse, rlse):
+    fin = torch.isfinite(rlse)
+    assert torch.equal(torch.isfinite(lse), fin)
+    assert not bool(torch.isnan(lse).any())
+    assert bool((lse[~fin] == float("-inf")).all())
+    assert bool((o[~fin[..., None].expand_as(o)] == 0).all())           # a row with no visible key: exactly zero
+    if bool(fin.any()):
+        assert float((lse.double() - rlse)[fin].abs().max()) <= 2e-3
+
+
+def _run_and_check(q, k, v, lens, *, causal=True, out_dtype=None, ref=None, **kw):
+    """The kernel on the NaN-tailed caches against fp64 on the clean ones.  lens: list or None (then nothing is poisoned)."""
+    from photonic_flash_attention_amd import ops
+    sl = _lens(lens, q.device) if lens is not None else None
+    kn, vn = _poison(k, v, lens) if lens is not None else (k, v)
+    o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=sl, causal=causal, out_dtype=out_dtype, return_lse=True, **kw)
+    torch.cuda.synchronize()
+    if ref is None:
+        ref = _reference(q, k, v, sl, causal, q.shape[-1] ** -0.5)
+    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    _check_lse(o, lse, ref[1])
+    return o, lse
+
+
+# --- against fp64 --------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("Sq", [1, 33, 65, 200, 257, 300])
+@pytest.mark.parametrize("D", [64, 128])
+def test_against_fp64(Sq, D):
+    lens = [Sq + 1000, Sq + 17]
+    for dtype in (torch.bfloat16, torch.float16):
+        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=Sq + D)
+        for causal in (True, False):
+            ref = _reference(q, k, v, _lens(lens), causal, D ** -0.5)
+            for out_dtype in (None, torch.float32):
+                _run_and_check(q, k, v, lens, causal=causal, out_dtype=out_dtype, ref=ref)
+
+
+@pytest.mark.parametrize("H,Hkv", [(4, 4), (16, 1)])
+@pytest.mark.parametrize("Sq", [65, 300])
+def test_head_groups_against_fp64(H, Hkv, Sq):
+    lens = [Sq + 1000, Sq + 17]
+    for dtype, D in ((torch.bfloat16, 128), (torch.float16, 64)):
+        q, k, v = _problem(2, H, Hkv, Sq, 2048, D, dtype, seed=H + Sq)
+        _run_and_check(q, k, v, lens)
+        _run_and_check(q, k, v, lens, causal=False, out_dtype=torch.float32)
+
+
+# --- edges ---------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_no_prefix_is_the_top_left_causal_forward(D):
+    from photonic_flash_attention_amd import ops
+    Sq = 300
+    q, k, v = _problem(2, 8, 2, Sq, 2048, D, torch.bfloat16, seed=40 + D)
+    o, lse = _run_and_check(q, k, v, [Sq, Sq])
+    ref = _reference(q, k, v, _lens([Sq, Sq]), True, D ** -0.5)
+    of, lf = ops.fa3_forward(q, k[:, :, :Sq], v[:, :, :Sq], causal=True, return_lse=True)
+    torch.cuda.synchronize()
+    _check(of, ref[0], ref[2], float(v.abs().max()), q.dtype)            # the forward meets the bound itself ...
+    _check(o, of.double(), ref[2], float(v.abs().max()), q.dtype)        # ... and the two agree within it
+    assert float((lse - lf).abs().max()) <= 2e-3
+
+
+def test_length_below_the_row_count_leaves_the_leading_rows_zero():
+    Sq = 300
+    for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
+        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=50 + D)
+        for lens in ([Sq + 500, 100], [37, Sq + 1]):
+            for out_dtype in (None, torch.float32):
+                o, lse = _run_and_check(q, k, v, lens, out_dtype=out_dtype)
+                b, n = (1, 100) if lens[1] == 100 else (0, 37)
+                assert bool((o[b, :, :Sq - n] == 0).all()) and bool((lse[b, :, :Sq - n] == float("-inf")).all())
+                assert bool(torch.isfinite(lse[b, :, Sq - n:]).all()) and bool(torch.isfinite(lse[1 - b]).all())
+            _run_and_check(q, k, v, lens, causal=False)                   # without the causal cut every row sees the len_b keys
+
+
+def test_zero_length():
+    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=60)
+    for causal in (True, False):
+        for out_dtype in (None, torch.float32):
+            o, lse = _run_and_check(q, k, v, [0, 300 + 64], causal=causal, out_dtype=out_dtype)
+            assert bool((o[0] == 0).all()) and bool((lse[0] == float("-inf")).all())
+    o, lse = _run_and_check(q, k, v, [0, 0])
+    assert bool((o == 0).all()) and bool((lse == float("-inf")).all())
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_full_cache_and_no_lengths(D):
+    Smax = 1024
+    q, k, v = _problem(2, 8, 2, 257, Smax, D, torch.bfloat16, seed=70 + D)
+    for causal in (True, False):
+        o1, l1 = _run_and_check(q, k, v, [Smax, Smax], causal=causal)            # len_b = Smax
+        o2, l2 = _run_and_check(q, k, v, None, causal=causal)                     # cache_seqlens = None
+        assert torch.equal(o1, o2) and torch.equal(l1, l2)
+
+
+@pytest.mark.parametrize("page", [64, 256])
+def test_lengths_next_to_tile_and_page_boundaries(page):
+    from photonic_flash_attention_amd import ops
+    Sq = 40
+    q, k, v = _problem(2, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=80 + page)
+    for lens in ([63, 65], [64, 127], [page - 1, page + 1], [4 * page - 1, 4 * page + 1], [4 * page, 2047]):
+        sl = _lens(lens)
+        kn, vn = _poison(k, v, lens)
+        kp, vp, table = _scatter(kn, vn, page, seed=page)
+        for causal in (True, False):
+            o, lse = _run_and_check(q, k, v, lens, causal=causal)
+            op, lp = ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=sl, causal=causal, return_lse=True)
+            torch.cuda.synchronize()
+            assert torch.equal(op, o) and torch.equal(lp, lse), lens
+
+
+# --- paged == contiguous -------------------------------------------------------------------------------------------------------------
+
+def _both(q, kn, vn, kp, vp, table, **kw):
+    """The contiguous and the paged call; asserts bitwise equality and finiteness, returns the paged (o, lse)."""
+    from photonic_flash_attention_amd import ops
+    oc, lc = ops.fa3_prefill_cache(q, kn, vn, return_lse=True, **kw)
+    op, lp = ops.fa3_prefill_cache(q, kp, vp, block_table=table, return_lse=True, **kw)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(op).all()) and bool(torch.isfinite(oc).all())
+    assert torch.equal(op, oc), f"O differs: max-abs {float((op.double() - oc.double()).abs().max()):.3e}"
+    assert torch.equal(lp, lc), "LSE differs"
+    return op, lp
+
+
+@pytest.mark.parametrize("page", [64, 128, 256, 1024])
+@pytest.mark.parametrize("D", [64, 128])
+def test_paged_equals_contiguous(page, D):
+    Smax = max(2048, 3 * page)
+    for dtype in (torch.bfloat16, torch.float16):
+        for Sq in (65, 300):
+            q, k, v = _problem(2, 8, 2, Sq, Smax, D, dtype, seed=page + D + Sq)
+            lens = [Sq + 1000, Sq + 17]
+            kn, vn = _poison(k, v, lens)
+            kp, vp, table = _scatter(kn, vn, page, seed=page + Sq)
+            for causal in (True, False):
+                for out_dtype in (None, torch.float32):
+                    _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens), causal=causal, out_dtype=out_dtype)
+        kp, vp, table = _scatter(k, v, page, seed=page)
+        _both(q, k, v, kp, vp, table)                                  # no lengths: every page is read
+    # the paged call against fp64 as well, so that the suite does not rest on the contiguous path alone
+    o, lse = _both(q, kn, vn, *_scatter(kn, vn, page, seed=1), cache_seqlens=_lens(lens))
+    ref = _reference(q, k, v, _lens(lens), True, D ** -0.5)
+    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    _check_lse(o, lse, ref[1])
+
+
+@pytest.mark.parametrize("layout", ["phsd", "hpsd", "slice"])
+def test_pool_layouts(layout):
+    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=9)
+    lens = [2048, 1111]
+    kn, vn = _poison(k, v, lens)
+    kp, vp, table = _scatter(kn, vn, 256, seed=3, layout=layout)
+    assert kp.is_contiguous() == (layout == "hpsd")
+    _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens))
+
+
+def test_two_sequences_sharing_prefix_pages():
+    page, Sq = 128, 200
+    q, k, v = _problem(3, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=10)
+    k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
+    v[1, :, :5 * page] = v[0, :, :5 * page]
+    lens = [2048, 5 * page + Sq + 7, 900]            # batch 1: its 207-row suffix attends to the shared pages
+    kn, vn = _poison(k, v, lens)
+    kp, vp, table = _scatter(kn, vn, page, seed=4)
+    freed = table[1, :5].clone()
+    table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
+    for pool in (kp, vp):
+        pool[freed.long()] = NAN                     # the duplicate copies are gone
+    o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens))
+    ref = _reference(q, k, v, _lens(lens), True, 128 ** -0.5)
+    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    _check_lse(o, lse, ref[1])
+
+
+# --- views, determinism --------------------------------------------------------------------------------------------------------------
+
+def test_strided_views_of_q_cache_and_out():
+    from photonic_flash_attention_amd import ops
+    dev = _dev()
+    B, H, Hkv, Sq, Smax, D = 2, 8, 2, 200, 1024, 128
+    g = _gen(11)
+    qkv = torch.randn(B, Sq, 3, H, D, generator=g, device=dev).to(torch.bfloat16)       # a fused projection
+    q = qkv[:, :, 0].permute(0, 2, 1, 3)
+    big_k = torch.randn(B, Hkv, Smax + 96, D, generator=g, device=dev).to(torch.bfloat16)
+    big_v = torch.randn(B, Hkv, Smax + 96, D, generator=g, device=dev).to(torch.bfloat16)
+    lens = [Sq + 700, Sq + 1]
+    for b, n in enumerate(lens):                     # the tails stay NaN inside the larger buffer
+        big_k[b, :, n:] = NAN
+        big_v[b, :, n:] = NAN
+    k, v = big_k[:, :, :Smax], big_v[:, :, :Smax]    # the first Smax positions of a larger preallocated cache
+    assert not q.is_contiguous() and not k.is_contiguous()
+    sl = _lens(lens)
+    ref = _reference(q, torch.nan_to_num(k), torch.nan_to_num(v), sl, True, D ** -0.5)
+    vmax = float(torch.nan_to_num(v).abs().max())
+    o, lse = ops.fa3_prefill_cache(q, k, v, cache_seqlens=sl, return_lse=True)
+    torch.cuda.synchronize()
+    _check(o, ref[0], ref[2], vmax, q.dtype)
+    _check_lse(o, lse, ref[1])
+    # out= given, with strides of its own: a slice of a wider [B, Sq, H, 2 D] buffer, untouched outside the slice
+    wide = torch.full((B, Sq, H, 2 * D), 7.0, dtype=torch.bfloat16, device=dev)
+    out = wide[..., D:].permute(0, 2, 1, 3)
+    o2, _ = ops.fa3_prefill_cache(q, k, v, cache_seqlens=sl, out=out)
+    torch.cuda.synchronize()
+    assert o2.data_ptr() == out.data_ptr() and torch.equal(o2, o) and bool((wide[..., :D] == 7.0).all())
+    # flash-attn style [B, Smax, Hkv, D] cache passed transposed
+    kt, vt = k.transpose(1, 2).contiguous().transpose(1, 2), v.transpose(1, 2).contiguous().transpose(1, 2)
+    o3, l3 = ops.fa3_prefill_cache(q, kt, vt, cache_seqlens=sl, return_lse=True)
+    torch.cuda.synchronize()
+    assert torch.equal(o3, o) and torch.equal(l3, lse)
+
+
+def test_outputs_are_bitwise_reproducible():
+    from photonic_flash_attention_amd import ops
+    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
+    lens = [2048, 1500]
+    kn, vn = _poison(k, v, lens)
+    kp, vp, table = _scatter(kn, vn, 64, seed=7)
+    for out_dtype in (None, torch.float32):
+        runs = [ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=_lens(lens), out_dtype=out_dtype, return_lse=True)
+                for _ in range(2)]
+        torch.cuda.synchronize()
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+        assert bool(torch.isfinite(runs[0][0]).all())
+
+
+# --- graph capture over a PagedKVCache -----------------------------------------------------------------------------------------------
+
+def _contiguous_of(cache, Smax):
+    """The cache's sequences gathered into contiguous [max_batch, Hkv, Smax, D] K and V (zeros past each length)."""
+    B = cache.max_batch
+    k = torch.zeros(B, cache.Hkv, Smax, cache.D, dtype=cache.k_pool.dtype, device=cache.device)
+    v = torch.zeros_like(k)
+    for s in range(B):
+        gk, gv = cache.gather(s)
+        k[s, :, :gk.shape[1]] = gk
+        v[s, :, :gv.shape[1]] = gv
+    return k, v
+
+
+def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
+    from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
+    dev = _dev()
+    H, Hkv, D, page, max_pages, Sq = 8, 2, 128, 64, 12, 100
+    cache = PagedKVCache(num_pages=30, page_size=page, Hkv=Hkv, D=D, dtype=torch.bfloat16, device=dev, max_batch=2,
+                         max_pages_per_seq=max_pages)
+    cache.k_pool.fill_(NAN)                  # whatever is not appended stays NaN: unfilled page tails, unused pages
+    cache.v_pool.fill_(NAN)
+    g = _gen(20)
+
+    def tokens(n, rows=1):
+        return (torch.randn(rows, Hkv, n, D, generator=g, device=dev).to(torch.bfloat16),
+                torch.randn(rows, Hkv, n, D, generator=g, device=dev).to(torch.bfloat16))
+
+    a, b = cache.allocate(), cache.allocate()
+    cache.append(b, *tokens(250))            # b first, so the two sequences' pages interleave in the pool
+    cache.append(a, *tokens(60))             # a holds fewer keys than the chunk has rows: its leading rows see nothing
+    cache.append(b, *tokens(40))
+    cache.reserve(a, 500)                    # pages a will grow into during the replays
+    table_ptr, lens_ptr = cache.block_table.data_ptr(), cache.cache_seqlens.data_ptr()
+    q = torch.randn(2, Sq, H, D, generator=g, device=dev).to(torch.bfloat16).permute(0, 2, 1, 3)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        cache.prefill(q, return_lse=True)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        o, lse = cache.prefill(q, return_lse=True)
+
+    def replay_and_compare():
+        graph.replay()
+        torch.cuda.synchronize()
+        kc, vc = _contiguous_of(cache, max_pages * page)
+        ref = _reference(q, kc, vc, cache.cache_seqlens, True, D ** -0.5)
+        _check(o, ref[0], ref[2], float(vc.abs().max()), q.dtype)
+        _check_lse(o, lse, ref[1])
+
+    replay_and_compare()
+    assert bool((o[a, :, :Sq - 60] == 0).all())
+    pages_a = cache.pages(a)
+    cache.append(a, *tokens(Sq))             # 60 -> 160: a new chunk's keys, into pages reserved before the capture
+    assert cache.pages(a) == pages_a and cache.length(a) == 160
+    cache.swap_pages(b, 0, 2)                # b's pages move, data with them
+    q.copy_(torch.randn(2, Sq, H, D, generator=g, device=dev).to(torch.bfloat16).permute(0, 2, 1, 3))
+    replay_and_compare()
+    cache.append([a, b], *tokens(Sq, rows=2))   # 160 -> 260, 290 -> 390 (pages assigned now)
+    cache.swap_pages(b, 1, 4)
+    cache.swap_pages(a, 0, 3)
+    replay_and_compare()
+    assert cache.block_table.data_ptr() == table_ptr and cache.cache_seqlens.data_ptr() == lens_ptr
+
+
+# --- consistency with the decode kernel ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("Sq", [1, 8, 64])
+def test_prefill_and_decode_both_meet_the_fp64_bound(Sq):
+    from photonic_flash_attention_amd import ops
+    for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
+        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=90 + Sq + D)
+        lens = [Sq + 1000, Sq + 17]
+        sl = _lens(lens)
+        kn, vn = _poison(k, v, lens)
+        ref = _reference(q, k, v, sl, True, D ** -0.5)
+        for out_dtype in (None, torch.float32):
+            for fn in (ops.fa3_prefill_cache, ops.fa3_decode):
+                o, lse = fn(q, kn, vn, cache_seqlens=sl, causal=True, out_dtype=out_dtype, return_lse=True)
+                torch.cuda.synchronize()
+                _check(o, ref[0], ref[2], float(v.abs().max()), dtype)
+                _check_lse(o, lse, ref[1])
