@@ -7,7 +7,8 @@
  * over a KV cache (pfa_fa3_decode_args, pfa_fa3_decode*: query rows of a K/V head packed together, keys split over workgroups);
  * v9 paged KV cache for the decode (pfa_fa3_decode_args.block_table / page_size / num_pages appended: a pool of pages and a block table);
  * v9, additive: pfa_fa3_prefill* -- the compute-bound forward over a KV cache (any number of query rows, contiguous or paged, on the
- * unchanged pfa_fa3_decode_args).
+ * unchanged pfa_fa3_decode_args);
+ * v9, additive: pfa_fa3_prefill_varlen* -- the same forward for ragged batches (packed query rows, cu_seqlens_q on the device).
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -336,6 +337,78 @@ int pfa_fa3_prefill_check(const pfa_fa3_decode_args* a);
 int pfa_fa3_prefill(const pfa_fa3_decode_args* a, void* stream);
 /* Introspection: the kernel name ("_paged" appended with a block table) into buf (NUL terminated, truncated to n); returns the workgroups, or a pfa_status. */
 int pfa_fa3_prefill_describe(const pfa_fa3_decode_args* a, char* buf, size_t n);
+
+/*
+ * Ragged forward over a KV cache (ABI v9, additive): pfa_fa3_prefill for batches whose sequences bring DIFFERENT numbers of query rows --
+ * one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative verification and one-token decode
+ * rows) in one launch.  The packed "varlen" form of flash-attn: the query rows of all sequences lie one after the other in one tensor and
+ * cu_seqlens_q says where each sequence starts.  Same kernel schedule, cache conventions and field rules as pfa_fa3_prefill.
+ *
+ *   q, o            [total_q, H, D] by element strides *_stride_s (between packed rows) and *_stride_h (last dim contiguous); there is no
+ *                   batch stride.  o in dtype_in or fp32.
+ *   cu_seqlens_q    required int32 [B + 1] on the device, non-decreasing, cu[0] >= 0, cu[B] <= total_q: sequence b owns the packed rows
+ *                   cu[b] .. cu[b + 1] - 1 (none if the two are equal).  Read by the kernel as s_b = clamp(cu[b], 0, total_q),
+ *                   e_b = clamp(cu[b + 1], s_b, total_q), Sq_b = min(e_b - s_b, max_seqlen_q): bad values give wrong numbers, never an
+ *                   address outside the packed tensors (the rule for page ids).
+ *   max_seqlen_q    host bound on the rows of one sequence, 1 <= max_seqlen_q <= total_q.  It sizes the grid, B * H * ceil(max_seqlen_q /
+ *                   256) workgroups from host shapes only, so a captured graph stays valid while cu_seqlens_q, cache_seqlens, the block
+ *                   table and the cache change between replays.  Of a sequence with more rows only the first max_seqlen_q are computed
+ *                   (as a sequence of max_seqlen_q rows); the others are left unwritten.
+ *   k_cache/v_cache [B, Smax, Hkv, D] by element strides, or with block_table pools [num_pages, page_size, Hkv, D] where *_stride_b are
+ *                   the PAGE strides, exactly as in pfa_fa3_decode_args.  Smax is then max_pages * page_size.
+ *   cache_seqlens   optional int32 [B] on the device: valid keys of each sequence, its Sq_b new rows' own keys INCLUDED (append the
+ *                   step's K / V first, then call).  NULL = Smax.  Keys at and past len_b = clamp(cache_seqlens[b], 0, Smax) and table
+ *                   entries at and past ceil(len_b / page_size) are never read (an unfilled tail may hold anything, NaN included).
+ *   causal          1: bottom-right aligned per sequence -- row i of sequence b sees key j iff j < len_b and j <= len_b - Sq_b + i.
+ *                   0: every row sees the len_b keys.
+ *   lse             optional fp32 [H, total_q] natural-log LSE: entry h * total_q + (cu[b] + i).
+ * A row with no visible key (len_b = 0, or under causal the first Sq_b - len_b rows when len_b < Sq_b) gets O = 0 and LSE = -inf.
+ * Packed rows no sequence covers -- gaps between sequences, the tail behind cu[B], rows of a sequence past max_seqlen_q -- are never
+ * written, in O or in LSE.  A sequence with no rows costs its workgroups an immediate return.
+ *
+ * The result is bit for bit that of pfa_fa3_prefill called per sequence (B = 1, Sq = Sq_b) on that sequence's rows, cache and length; one
+ * launch, no workspace, no atomics (bitwise reproducible).  A paged call returns the bits of the contiguous call on the gathered cache.
+ *
+ * Field rules: those of pfa_fa3_prefill where the fields coincide (D in {64, 128}, bf16 / fp16 operands, q / k / v strides multiples of 8
+ * elements and o strides of 4, base pointers 16-byte aligned, paging fields all set or all zero), and: cu_seqlens_q NULL -> PFA_ERR_NULL,
+ * not 4-byte aligned -> PFA_ERR_ALIGN; total_q < 1, max_seqlen_q < 1, max_seqlen_q > total_q or more workgroups than a grid holds ->
+ * PFA_ERR_SHAPE.  There is no key mask.
+ */
+typedef struct pfa_fa3_prefill_varlen_args {
+    uint32_t size;              /* = sizeof(pfa_fa3_prefill_varlen_args) */
+    uint32_t flags;             /* must be 0 */
+    const void* q;
+    const void* k_cache;
+    const void* v_cache;
+    void*       o;
+    float*      lse;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cache_seqlens;
+    int64_t q_stride_s, q_stride_h;
+    int64_t o_stride_s, o_stride_h;
+    int64_t k_stride_b, k_stride_h, k_stride_s;
+    int64_t v_stride_b, v_stride_h, v_stride_s;
+    int32_t B, H, Hkv, total_q, max_seqlen_q, Smax, D;
+    int32_t dtype_in;           /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 */
+    int32_t dtype_out;          /* = dtype_in, or PFA_DTYPE_FP32 */
+    int32_t causal;             /* bottom-right per sequence, see above */
+    float   softmax_scale;
+    int32_t device_id;
+    int32_t reserved0;          /* must be 0 */
+    /* paged cache, as in pfa_fa3_decode_args.  NULL / 0: the contiguous cache. */
+    const int32_t* block_table;
+    int64_t block_table_stride_b;
+    int32_t page_size;          /* keys per page, a multiple of 64 */
+    int32_t num_pages;          /* pages in the pools */
+} pfa_fa3_prefill_varlen_args;
+
+/* Validate `a` without launching: PFA_OK or the error pfa_fa3_prefill_varlen would return. */
+int pfa_fa3_prefill_varlen_check(const pfa_fa3_prefill_varlen_args* a);
+/* Enqueue the ragged forward (one launch) on `stream`. */
+int pfa_fa3_prefill_varlen(const pfa_fa3_prefill_varlen_args* a, void* stream);
+/* Introspection: the kernel name (pfa_fa3_prefill_describe's with "_varlen" in front of any "_paged") into buf (NUL terminated, truncated
+ * to n); returns the workgroups, or a pfa_status. */
+int pfa_fa3_prefill_varlen_describe(const pfa_fa3_prefill_varlen_args* a, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

@@ -27,6 +27,7 @@ EXPORTS = (
     "pfa_fa3_bwd", "pfa_fa3_bwd_workspace_bytes", "pfa_fa3_bwd_mask_workspace_bytes", "pfa_fa3_prepare", "pfa_probe_mfma",
     "pfa_fa3_decode_workspace_bytes", "pfa_fa3_decode_check", "pfa_fa3_decode", "pfa_fa3_decode_describe",
     "pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_describe",
+    "pfa_fa3_prefill_varlen_check", "pfa_fa3_prefill_varlen", "pfa_fa3_prefill_varlen_describe",
 )
 
 
@@ -77,6 +78,19 @@ class PfaFa3DecodeArgs(C.Structure):
         + [(n, C.c_int32) for n in ("B", "H", "Hkv", "Sq", "Smax", "D", "dtype_in", "dtype_out", "causal")]
         + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
         + [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+        + [("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64), ("page_size", C.c_int32), ("num_pages", C.c_int32)]
+    )
+
+
+class PfaFa3PrefillVarlenArgs(C.Structure):
+    """Mirror of ``struct pfa_fa3_prefill_varlen_args`` (include/pfa_hip.h): packed query rows, no batch stride on q / o."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("q", "k_cache", "v_cache", "o", "lse", "cu_seqlens_q", "cache_seqlens")]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "qo" for a in "sh"]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "kv" for a in "bhs"]
+        + [(n, C.c_int32) for n in ("B", "H", "Hkv", "total_q", "max_seqlen_q", "Smax", "D", "dtype_in", "dtype_out", "causal")]
+        + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
         + [("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64), ("page_size", C.c_int32), ("num_pages", C.c_int32)]
     )
 
@@ -148,6 +162,12 @@ def load(path: Optional[str] = None):
         lib.pfa_fa3_prefill.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_void_p]
         lib.pfa_fa3_prefill_describe.restype = C.c_int
         lib.pfa_fa3_prefill_describe.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_char_p, C.c_size_t]
+        lib.pfa_fa3_prefill_varlen_check.restype = C.c_int
+        lib.pfa_fa3_prefill_varlen_check.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs)]
+        lib.pfa_fa3_prefill_varlen.restype = C.c_int
+        lib.pfa_fa3_prefill_varlen.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), C.c_void_p]
+        lib.pfa_fa3_prefill_varlen_describe.restype = C.c_int
+        lib.pfa_fa3_prefill_varlen_describe.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), C.c_char_p, C.c_size_t]
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
@@ -206,6 +226,23 @@ def describe_prefill(args: PfaFa3DecodeArgs):
     """-> (kernel name, workgroups) of ``pfa_fa3_prefill`` (the forward over a KV cache takes the decode's argument block)."""
     buf = C.create_string_buffer(128)
     n = load().pfa_fa3_prefill_describe(C.byref(args), buf, 128)
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n
+
+
+def make_prefill_varlen_args(**kw) -> PfaFa3PrefillVarlenArgs:
+    a = PfaFa3PrefillVarlenArgs()
+    a.size = C.sizeof(PfaFa3PrefillVarlenArgs)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def describe_prefill_varlen(args: PfaFa3PrefillVarlenArgs):
+    """-> (kernel name, workgroups) of ``pfa_fa3_prefill_varlen``: ``B * H * ceil(max_seqlen_q / 256)``, from host shapes only."""
+    buf = C.create_string_buffer(128)
+    n = load().pfa_fa3_prefill_varlen_describe(C.byref(args), buf, 128)
     if n < 0:
         check_status(n)
     return buf.value.decode(), n

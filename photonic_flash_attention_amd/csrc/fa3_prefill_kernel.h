@@ -22,6 +22,20 @@
 //      len_b).
 // Grid = B * H * ceil(Sq / 256) from shapes alone, no workspace, no atomics: capturable, and valid while lengths, table and cache
 // change between replays.  No split over keys: a short chunk with few B * H leaves CUs idle.
+//
+// VARLEN (pfa_fa3_prefill_varlen): every batch brings its own number of query rows.  Q, O are packed [total_q, H, D] (no batch
+// stride), LSE is [H, total_q], and a device int32 cu_seqlens_q[B + 1] says where each batch's rows start.  The schedule, the tile
+// loop and the grid (B * H * ceil(max_seqlen_q / 256), p.Sq holding max_seqlen_q) are the uniform kernel's; the prologue and the
+// stores differ:
+//   - s_b = clamp(cu[b], 0, total_q), e_b = clamp(cu[b + 1], s_b, total_q), Sq_b = min(e_b - s_b, max_seqlen_q), off_b = len_b - Sq_b,
+//     all wave-uniform.  Bad device data gives wrong numbers, never a row outside the packed tensors.
+//   - a block with q0 >= Sq_b returns before any load or store (every block of an empty batch does);
+//   - row i of batch b is packed row s_b + i, and every store is bounded by Sq_b: the packed row behind a batch's last row is the
+//     next batch's first.  Rows no batch covers (gaps, the tail behind cu[B], rows past max_seqlen_q) are never written;
+//   - a wave with wave_q0 >= Sq_b has no rows: it issues its DMA pieces and meets the barriers but computes no tile (the uniform
+//     kernel runs such a wave on copies of the last row).  Nothing it holds is stored.
+// The Q clamp (row min(my_q, Sq_b - 1)) and therefore the rescale points of the wave-wide deferred max are those of the uniform kernel
+// at Sq = Sq_b, so a ragged call returns the bits of per-batch uniform calls.
 #pragma once
 #include "fa3_fwd_kernel.h"
 
@@ -47,10 +61,18 @@ struct PrefillParams {
     int32_t page_size, num_pages;
 };
 
+// VARLEN: q_sb / o_sb are unused, Sq is max_seqlen_q, lse is [H, total_q]
+struct PrefillVarlenParams : PrefillParams {
+    const int32_t* cu_seqlens_q; // [B + 1] packed row of each batch's first query row
+    int32_t total_q;             // rows of the packed q / o
+};
+template <bool VARLEN> struct PrefillParamsOf { typedef PrefillParams type; };
+template <> struct PrefillParamsOf<true> { typedef PrefillVarlenParams type; };
+
 typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
 
-template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT>
-__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const PrefillParams p) {
+template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN>::type p) {
     constexpr int NW = FWD_WAVES, BLOCK_M = FWD_BLOCK_M;
     using E = Elem<T>;
     using v8 = typename E::v8;
@@ -85,18 +107,30 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const Prefi
     const int wave_q0 = q0 + wave * WAVE_M;
     const int my_q = wave_q0 + r;
 
+    // ---- VARLEN: the batch's rows in the packed tensors, from the device (clamped: never a row outside them) ----
+    int sq = p.Sq;                                       // query rows of this batch
+    int row0 = 0;                                        // packed row of its first
+    if constexpr (VARLEN) {
+        const int s_b = min(max(p.cu_seqlens_q[b], 0), p.total_q);
+        const int e_b = min(max(p.cu_seqlens_q[b + 1], s_b), p.total_q);
+        row0 = __builtin_amdgcn_readfirstlane(s_b);
+        sq = __builtin_amdgcn_readfirstlane(min(e_b - s_b, p.Sq));
+        if (q0 >= sq) return;                            // nothing of this batch in the block: no load, no store
+    }
+    const bool wave_has_rows = !VARLEN || wave_q0 < sq;
+
     // ---- (1) the batch's length and causal offset, from the device ----------------------------------
     int kv_len = p.Smax;
     if (p.seqlens) kv_len = min(kv_len, max(p.seqlens[b], 0));
     kv_len = __builtin_amdgcn_readfirstlane(kv_len);
-    const int off = kv_len - p.Sq;                       // row i sees key j iff j <= i + off (may be negative)
+    const int off = kv_len - sq;                         // row i sees key j iff j <= i + off (may be negative)
     const int kv_end = CAUSAL ? max(0, min(kv_len, q0 + BLOCK_M + off)) : kv_len;       // keys the block needs
-    const int wave_kv_end = CAUSAL ? min(kv_len, wave_q0 + WAVE_M + off) : kv_len;      // keys this wave needs (<= 0: none)
+    const int wave_kv_end = !wave_has_rows ? 0 : CAUSAL ? min(kv_len, wave_q0 + WAVE_M + off) : kv_len;   // keys this wave needs (<= 0: none)
     const int my_lim = my_q + off;                       // last key this row sees under the causal cut
     const int nt = (kv_end + BLOCK_N - 1) / BLOCK_N;
 
     const int kvh = hh / p.kv_group;
-    const T* __restrict__ qp = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)hh * p.q_sh;
+    const T* __restrict__ qp = (const T*)p.q + (VARLEN ? (int64_t)row0 * p.q_ss : (int64_t)b * p.q_sb) + (int64_t)hh * p.q_sh;
     // contiguous: this batch's and head's slab; paged: the head's offset inside every page (the page base is added per tile)
     const char* kp = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * 2;
     const char* vp = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * 2;
@@ -104,7 +138,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const Prefi
     // ---- Q fragments: B operand of S^T = K Q^T, lane (r,h) holds Q[my_q][16 ks + 8 h .. +7] -----------
     v8 qf[KS];
     {
-        const int qrow = min(my_q, p.Sq - 1);
+        const int qrow = min(my_q, sq - 1);
         const T* src = qp + (int64_t)qrow * p.q_ss + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const v8*)(src + 16 * ks);
@@ -334,6 +368,9 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const Prefi
     // ---- epilogue: normalise once; a row with no visible key -> zeros, LSE = -inf ------------
     const float l_tot = row_pair_sum(l_run);
     const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+    // VARLEN: the batch's rows start at packed row row0, and the row bound of every store is the batch's own count -- the next
+    // packed row is another batch's
+    const int64_t o_batch = VARLEN ? (int64_t)row0 * p.o_ss : (int64_t)b * p.o_sb;
     if constexpr (sizeof(OT) == 2) {
         // 16-bit store through LDS (free after the loop's last barrier) so that one store instruction covers whole rows: see fa3_fwd_kernel
         typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
@@ -356,10 +393,10 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const Prefi
                 const uint32_t ch = 4 * db + g + h;
                 *(lds_u32x4_t*)(uintptr_t)(lbase + r * RB + ((ch ^ (r & (CPRW - 1))) << 4)) = w;
             }
-        store_rows_from_lds<RB>(lbase, lane, (char*)((OT*)p.o + (int64_t)b * p.o_sb + (int64_t)hh * p.o_sh + (int64_t)wave_q0 * p.o_ss),
-                                p.o_ss * 2, p.Sq - wave_q0);
-    } else if (my_q < p.Sq) {      // fp32 rows straight from the accumulators
-        OT* orow = (OT*)p.o + (int64_t)b * p.o_sb + (int64_t)hh * p.o_sh + (int64_t)my_q * p.o_ss;
+        store_rows_from_lds<RB>(lbase, lane, (char*)((OT*)p.o + o_batch + (int64_t)hh * p.o_sh + (int64_t)wave_q0 * p.o_ss),
+                                p.o_ss * 2, sq - wave_q0);
+    } else if (my_q < sq) {        // fp32 rows straight from the accumulators
+        OT* orow = (OT*)p.o + o_batch + (int64_t)hh * p.o_sh + (int64_t)my_q * p.o_ss;
 #pragma unroll
         for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -371,9 +408,10 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const Prefi
                 *(f32x4*)(orow + d) = w;
             }
     }
-    if (my_q < p.Sq && p.lse && h == 0) {
+    if (my_q < sq && p.lse && h == 0) {
         const float lse = l_tot > 0.f ? (m_run * c + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : -INFINITY;
-        p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;
+        if constexpr (VARLEN) p.lse[(int64_t)hh * p.total_q + row0 + my_q] = lse;
+        else p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;
     }
 }
 

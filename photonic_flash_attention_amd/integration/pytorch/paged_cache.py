@@ -1,4 +1,5 @@
-"""A paged KV cache for one attention layer, read by ``ops.fa3_decode`` and ``ops.fa3_prefill_cache`` ``(..., block_table=...)``.
+"""A paged KV cache for one attention layer, read by ``ops.fa3_decode``, ``ops.fa3_prefill_cache`` and ``ops.fa3_prefill_varlen``
+``(..., block_table=...)``.
 
 The cache is a pool of fixed-size pages (``[num_pages, page_size, Hkv, D]`` for K and for V) plus, per sequence slot, a row of a
 device block table and a device length.  Which page a sequence's next tokens go to is decided on the host, from a host mirror of
@@ -6,7 +7,7 @@ the lengths (the caller says how many tokens it appends, so the host always know
 device.  The device tensors ``block_table`` and ``cache_seqlens`` are allocated once and updated in place, so a captured graph of
 ``decode`` keeps seeing them; pages a sequence will grow into during replays are assigned ahead with ``reserve``.
 
-Everything except ``decode`` and ``prefill`` (the HIP kernels) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
+Everything except ``decode``, ``prefill`` and ``prefill_varlen`` (the HIP kernels) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
 The token append is a few KiB per step and stays torch ops; the hot path is the decode kernel.
 """
 
@@ -165,6 +166,37 @@ class PagedKVCache:
             self._v.view(rows, self.Hkv, self.D).index_copy_(0, idx, v_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D))
         self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
 
+    def append_varlen(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor, lens: Sequence[int]) -> None:
+        """``append`` for a different number of tokens per slot: ``k_new`` / ``v_new`` are packed ``[total, Hkv, D]``, slot
+        ``slots[i]`` takes the next ``lens[i]`` tokens (a host list, 0 allowed; ``sum(lens) == total``) at its current end.  All or
+        nothing: if the pool cannot serve every slot nothing is written and ``PagedCacheFull`` is raised."""
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        lens = [int(x) for x in lens]
+        n, total = len(slots), sum(lens)
+        if len(set(slots)) != n:
+            raise ValueError("a slot may appear once per append")
+        if len(lens) != n or any(x < 0 for x in lens):
+            raise ValueError(f"lens must hold one non-negative token count per slot, got {lens} for {n} slots")
+        if k_new.dim() != 3 or k_new.shape != (total, self.Hkv, self.D) or v_new.shape != k_new.shape:
+            raise ValueError(f"k_new / v_new must be [{total}, {self.Hkv}, {self.D}], got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
+        if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
+            raise ValueError("k_new / v_new must have the cache's dtype")
+        missing = [self._pages_missing(self._check_slot(s), self._host_lens[s] + x) for s, x in zip(slots, lens)]
+        if sum(missing) > len(self._free_pages):
+            raise PagedCacheFull(f"the append needs {sum(missing)} more pages, the pool has {len(self._free_pages)} free")
+        dst = []
+        for s, m, x in zip(slots, missing, lens):
+            self._assign(s, m)
+            for j in range(self._host_lens[s], self._host_lens[s] + x):
+                dst.append(self._pages[s][j // self.page_size] * self.page_size + j % self.page_size)
+            self._host_lens[s] += x
+        if total:
+            idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
+            rows = self.num_pages * self.page_size
+            self._k.view(rows, self.Hkv, self.D).index_copy_(0, idx, k_new)
+            self._v.view(rows, self.Hkv, self.D).index_copy_(0, idx, v_new)
+        self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
+
     def swap_pages(self, slot: int, i: int, j: int) -> None:
         """Exchange the physical pages behind logical pages ``i`` and ``j`` of the slot, moving their contents with them (what a
         compaction does); the sequence reads the same afterwards."""
@@ -223,3 +255,31 @@ class PagedKVCache:
         (``causal``, ``out_dtype``, ``return_lse``, ``out``, ...) pass through.  -> ``(o, lse)``."""
         table, lens = self._rows(slots)
         return ops.fa3_prefill_cache(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
+
+    def prefill_varlen(self, q: torch.Tensor, q_lens: Optional[Sequence[int]] = None, slots: Slots = None, *,
+                       cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None, **kw):
+        """``ops.fa3_prefill_varlen`` of the packed ``q [total_q, H, D]`` against the sequences in ``slots`` (chosen and captured as
+        in ``decode``): sequence i brings ``q_lens[i]`` rows, one step of continuous batching in one launch.  ``append_varlen`` the
+        rows' own K / V first.  A host list ``q_lens`` becomes a device ``cu_seqlens_q`` by a non-blocking copy, with
+        ``max_seqlen_q = max(q_lens)`` unless given; a caller that captures graphs passes its own device ``cu_seqlens_q`` (int32
+        ``[len(slots) + 1]``, updated in place between replays) and the ``max_seqlen_q`` bound instead.  Keyword arguments
+        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
+        table, lens = self._rows(slots)
+        if (q_lens is None) == (cu_seqlens_q is None):
+            raise ValueError("give either q_lens (a host list) or cu_seqlens_q (a device tensor) with max_seqlen_q")
+        if cu_seqlens_q is None:
+            q_lens = [int(x) for x in q_lens]
+            if len(q_lens) != table.shape[0] or any(x < 0 for x in q_lens):
+                raise ValueError(f"q_lens must hold one non-negative row count per slot, got {q_lens} for {table.shape[0]} slots")
+            cu = [0]
+            for x in q_lens:
+                cu.append(cu[-1] + x)
+            if cu[-1] > q.shape[0] or cu[-1] < 1:
+                raise ValueError(f"q_lens name {cu[-1]} rows, q has {q.shape[0]}")
+            cu_seqlens_q = torch.tensor(cu, dtype=torch.int32).to(self.device, non_blocking=True)
+            if max_seqlen_q is None:
+                max_seqlen_q = max(q_lens)
+        elif max_seqlen_q is None:
+            raise ValueError("cu_seqlens_q needs max_seqlen_q, the host bound on a sequence's rows (it sizes the grid)")
+        return ops.fa3_prefill_varlen(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cu_seqlens_q=cu_seqlens_q,
+                                      max_seqlen_q=max_seqlen_q, cache_seqlens=lens, block_table=table, **kw)

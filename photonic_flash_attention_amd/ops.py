@@ -460,13 +460,11 @@ def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=Non
     return _FA3Function.apply(q, k, v, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype, bool(return_weights), weights_dtype)
 
 
-def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table):
-    """Validation and marshalling ``fa3_decode`` and ``fa3_prefill_cache`` share (both take ``pfa_fa3_decode_args``): the operands,
-    the output buffer and the block table.  -> ``(args, out, Smax)``; ``entry`` names the C entry point in the messages."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
-        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
-    B, H, Sq, D = q.shape
+def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table):
+    """What every call over a KV cache checks about its 4-D caches (or pools and block table) against a query of B sequences, H
+    heads and head dim D.  -> ``(Hkv, Smax, page_size, num_pages, output dtype)``, the paging pair 0 without a table."""
     Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+    page_size = num_pages = 0
     if block_table is None:
         if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != (B, Hkv, Smax, D) or Hkv < 1 or H % Hkv:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
@@ -492,6 +490,16 @@ def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out
     odt = q.dtype if out_dtype is None else out_dtype
     if odt not in (q.dtype, torch.float32):
         raise ValueError("output dtype must be the input dtype or fp32")
+    return Hkv, Smax, page_size, num_pages, odt
+
+
+def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table):
+    """Validation and marshalling ``fa3_decode`` and ``fa3_prefill_cache`` share (both take ``pfa_fa3_decode_args``): the operands,
+    the output buffer and the block table.  -> ``(args, out, Smax)``; ``entry`` names the C entry point in the messages."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    B, H, Sq, D = q.shape
+    Hkv, Smax, page_size, num_pages, odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table)
     if out is None:
         out = torch.empty((B, Sq, H, D), dtype=odt, device=q.device).permute(0, 2, 1, 3)
     elif out.shape != (B, H, Sq, D) or out.dtype != odt or out.device != q.device:
@@ -510,9 +518,9 @@ def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out
     return a, out, Smax
 
 
-def _set_cache_seqlens(a, cache_seqlens, q, keep) -> None:
+def _set_cache_seqlens(a, cache_seqlens, q, keep, B=None) -> None:
     """``cache_seqlens`` (int32 ``[B]`` device tensor, or None) into the argument block; a converted copy is appended to ``keep``."""
-    B = q.shape[0]
+    B = q.shape[0] if B is None else B
     if cache_seqlens is not None:
         if not isinstance(cache_seqlens, torch.Tensor) or not cache_seqlens.is_cuda or cache_seqlens.device != q.device:
             raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
@@ -609,6 +617,71 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     st = _capi.load().pfa_fa3_prefill(C.byref(a), C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
         raise ValueError(f"pfa_fa3_prefill: {_capi.status_string(st)}")
+    _capi.check_status(st)
+    for t in keep:   # tensors made here must outlive the enqueued kernel
+        t.record_stream(stream)
+    return out, lse
+
+
+def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                       cache_seqlens: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
+                       out_dtype: Optional[torch.dtype] = None, return_lse: bool = False, out: Optional[torch.Tensor] = None,
+                       block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
+    of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
+    verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
+
+    q: ``[total_q, H, D]`` (D 64 or 128, bf16 / fp16; any token / head strides, head dim contiguous), the sequences' rows one after
+    the other.  cu_seqlens_q: int32 ``[B + 1]`` DEVICE tensor, non-decreasing, within ``[0, total_q]``: sequence b owns the packed rows
+    ``cu[b] .. cu[b+1] - 1`` (none is fine).  max_seqlen_q: host bound on the rows of one sequence (1 .. total_q); it alone sizes the
+    grid, ``B * H * ceil(max_seqlen_q / 256)`` workgroups, and of a longer sequence only the first max_seqlen_q rows are computed.
+    k_cache / v_cache, ``block_table`` and ``cache_seqlens`` are passed as in ``fa3_prefill_cache`` with ``B = cu_seqlens_q.numel() - 1``:
+    the lengths count each sequence's own new rows (append first, then call), and ``causal`` is bottom-right aligned per sequence
+    (row i of sequence b sees key j iff j <= len_b - Sq_b + i).  A row with no visible key gets O = 0 and LSE = -inf.  Packed rows no
+    sequence covers (gaps, the tail behind ``cu[B]``) are never written; device values out of range are clamped by the kernel.
+    Returns ``(o [total_q, H, D], lse [H, total_q] or None)``.  The result is bit for bit that of ``fa3_prefill_cache`` called per
+    sequence.  No host synchronisation, no workspace and no cached allocation: capturable in ``torch.cuda.graph`` and valid while
+    cu_seqlens_q, lengths, table and cache change between replays."""
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("q must be 3-D ([total_q,H,D]) and k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
+        raise ValueError("cu_seqlens_q must be an int32 tensor")
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
+        raise ValueError(f"cu_seqlens_q must be [B + 1], got {tuple(cu_seqlens_q.shape)}")
+    total_q, H, D = q.shape
+    B = cu_seqlens_q.numel() - 1
+    Hkv, Smax, page_size, num_pages, odt = _cache_operands("pfa_fa3_prefill_varlen", q, B, H, D, k_cache, v_cache, out_dtype, block_table)
+    if not cu_seqlens_q.is_cuda or cu_seqlens_q.device != q.device:
+        raise ValueError("cu_seqlens_q must live on the operands' device (there is no CPU path)")
+    if not cu_seqlens_q.is_contiguous():
+        raise ValueError("cu_seqlens_q must be contiguous")
+    if q.stride(2) != 1 and D != 1:
+        raise ValueError("last (head_dim) stride must be 1")
+    if out is None:
+        out = torch.empty((total_q, H, D), dtype=odt, device=q.device)
+    elif out.shape != (total_q, H, D) or out.dtype != odt or out.device != q.device or (out.stride(2) != 1 and D != 1):
+        raise ValueError("out must be a [total_q, H, D] tensor of the output dtype on the operands' device, head dim contiguous")
+    ks, vs = _bhsd_strides(k_cache), _bhsd_strides(v_cache)
+    a = _capi.make_prefill_varlen_args(
+        q=q.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(), o=out.data_ptr(), cu_seqlens_q=cu_seqlens_q.data_ptr(),
+        q_stride_s=q.stride(0), q_stride_h=q.stride(1), o_stride_s=out.stride(0), o_stride_h=out.stride(1),
+        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
+        B=B, H=H, Hkv=Hkv, total_q=total_q, max_seqlen_q=int(max_seqlen_q), Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt],
+        causal=1 if causal else 0, softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
+        device_id=q.device.index if q.device.index is not None else torch.cuda.current_device())
+    if block_table is not None:
+        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
+        a.page_size, a.num_pages = page_size, num_pages
+    keep = []
+    _set_cache_seqlens(a, cache_seqlens, q, keep, B)
+    lse = None
+    if return_lse:
+        lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
+        a.lse = lse.data_ptr()
+    stream = torch.cuda.current_stream(q.device)
+    st = _capi.load().pfa_fa3_prefill_varlen(C.byref(a), C.c_void_p(stream.cuda_stream))
+    if st in (-1, -3, -4, -5, -6, -7, -10):
+        raise ValueError(f"pfa_fa3_prefill_varlen: {_capi.status_string(st)}")
     _capi.check_status(st)
     for t in keep:   # tensors made here must outlive the enqueued kernel
         t.record_stream(stream)
