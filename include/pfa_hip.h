@@ -8,7 +8,9 @@
  * v9 paged KV cache for the decode (pfa_fa3_decode_args.block_table / page_size / num_pages appended: a pool of pages and a block table);
  * v9, additive: pfa_fa3_prefill* -- the compute-bound forward over a KV cache (any number of query rows, contiguous or paged, on the
  * unchanged pfa_fa3_decode_args);
- * v9, additive: pfa_fa3_prefill_varlen* -- the same forward for ragged batches (packed query rows, cu_seqlens_q on the device).
+ * v9, additive: pfa_fa3_prefill_varlen* -- the same forward for ragged batches (packed query rows, cu_seqlens_q on the device);
+ * v9, additive: pfa_fa3_cache_ext and the *_ex entry points of the three calls over a KV cache -- a sliding window (each row sees its
+ * last `window` keys), with keys and block-table entries behind the window never read.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -409,6 +411,53 @@ int pfa_fa3_prefill_varlen(const pfa_fa3_prefill_varlen_args* a, void* stream);
 /* Introspection: the kernel name (pfa_fa3_prefill_describe's with "_varlen" in front of any "_paged") into buf (NUL terminated, truncated
  * to n); returns the workgroups, or a pfa_status. */
 int pfa_fa3_prefill_varlen_describe(const pfa_fa3_prefill_varlen_args* a, char* buf, size_t n);
+
+/*
+ * Per-call options of the three calls over a KV cache (ABI v9, additive): pfa_fa3_decode, pfa_fa3_prefill and pfa_fa3_prefill_varlen each
+ * have *_ex twins that take their unchanged argument block plus this extension.  ext == NULL, or an extension whose window is 0, is
+ * exactly the call without the extension: the same kernel function, grid and workspace size, the same bits.  The old entry points are
+ * the new ones with ext = NULL.
+ *
+ * Sliding window.  window = W >= 1 (a host integer): a row sees at most W keys, its own diagonal key included -- Hugging Face's
+ * sliding_window, flash-attn's window_size = (W - 1, 0).  With len_b the sequence's valid keys, Sq_b its query rows (Sq; the ragged
+ * call: its own count) and off_b = len_b - Sq_b, row i of sequence b sees key j iff
+ *       j < len_b   and   j <= i + off_b   and   j > i + off_b - W.
+ * The window needs causal = 1 (causal = 0 with window > 0: PFA_ERR_FLAGS).  Rows with no visible key are the rows of len_b < Sq_b that
+ * have none without a window either (O = 0, LSE = -inf); the window adds no others.  pfa_fa3_decode's key_mask combines with the window
+ * by logical AND.  A window >= Smax hides nothing and returns the bits of the call without a window.
+ *
+ * What is never read, next to "keys at and past len_b and table entries at and past ceil(len_b / page_size)": let
+ * lo_b = max(0, off_b - W + 1), the lowest key row 0 of the call can see.  Keys below floor64(lo_b) = lo_b rounded down to a multiple of
+ * 64 are never read, and with a block table the entries below lo_b / page_size are never read (page_size is a multiple of 64: the same
+ * boundary at page granularity) -- a server may hand the pages behind the window to other sequences and leave anything in those table
+ * entries.  Keys in [floor64(lo_b), lo_b), and keys that lie inside a 64-key tile but below an individual row's bound, ARE read and
+ * hidden by the score mask: they are live cache contents and must be finite.
+ *
+ * pfa_fa3_decode_ex splits [floor64(lo_b), len_b) over the key splits instead of [0, len_b), and picks the number of splits and the
+ * workspace from the shapes and the host `window` alone (min(Smax, window + Sq - 1 rounded up to 64) stands where Smax does), so a
+ * captured graph stays valid while lengths, table and cache change: ask pfa_fa3_decode_workspace_bytes_ex with the same ext.
+ *
+ * Field rules, after those of the argument block: size wrong -> PFA_ERR_STRUCT_SIZE; flags or reserved non-zero -> PFA_ERR_FLAGS;
+ * window < 0 -> PFA_ERR_SHAPE; window > 0 with causal == 0 -> PFA_ERR_FLAGS.  *_describe_ex appends "_win" to the kernel's name (in
+ * front of any "+combine", "_varlen" or "_paged") when a window is set.
+ */
+typedef struct pfa_fa3_cache_ext {
+    uint32_t size;              /* = sizeof(pfa_fa3_cache_ext) */
+    uint32_t flags;             /* must be 0 */
+    int32_t  window;            /* 0: none; W >= 1: each row sees its last W keys, see above */
+    int32_t  reserved;          /* must be 0 */
+} pfa_fa3_cache_ext;
+
+size_t pfa_fa3_decode_workspace_bytes_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext);
+int pfa_fa3_decode_check_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext);
+int pfa_fa3_decode_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, void* stream);
+int pfa_fa3_decode_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n, int32_t* nsplit);
+int pfa_fa3_prefill_check_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext);
+int pfa_fa3_prefill_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, void* stream);
+int pfa_fa3_prefill_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n);
+int pfa_fa3_prefill_varlen_check_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext);
+int pfa_fa3_prefill_varlen_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, void* stream);
+int pfa_fa3_prefill_varlen_describe_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

@@ -28,6 +28,9 @@ EXPORTS = (
     "pfa_fa3_decode_workspace_bytes", "pfa_fa3_decode_check", "pfa_fa3_decode", "pfa_fa3_decode_describe",
     "pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_describe",
     "pfa_fa3_prefill_varlen_check", "pfa_fa3_prefill_varlen", "pfa_fa3_prefill_varlen_describe",
+    "pfa_fa3_decode_workspace_bytes_ex", "pfa_fa3_decode_check_ex", "pfa_fa3_decode_ex", "pfa_fa3_decode_describe_ex",
+    "pfa_fa3_prefill_check_ex", "pfa_fa3_prefill_ex", "pfa_fa3_prefill_describe_ex",
+    "pfa_fa3_prefill_varlen_check_ex", "pfa_fa3_prefill_varlen_ex", "pfa_fa3_prefill_varlen_describe_ex",
 )
 
 
@@ -93,6 +96,11 @@ class PfaFa3PrefillVarlenArgs(C.Structure):
         + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
         + [("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64), ("page_size", C.c_int32), ("num_pages", C.c_int32)]
     )
+
+
+class PfaFa3CacheExt(C.Structure):
+    """Mirror of ``struct pfa_fa3_cache_ext`` (include/pfa_hip.h): per-call options of the ``*_ex`` calls over a KV cache."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PfaError(RuntimeError):
@@ -168,6 +176,27 @@ def load(path: Optional[str] = None):
         lib.pfa_fa3_prefill_varlen.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), C.c_void_p]
         lib.pfa_fa3_prefill_varlen_describe.restype = C.c_int
         lib.pfa_fa3_prefill_varlen_describe.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), C.c_char_p, C.c_size_t]
+        ext = C.POINTER(PfaFa3CacheExt)
+        lib.pfa_fa3_decode_workspace_bytes_ex.restype = C.c_size_t
+        lib.pfa_fa3_decode_workspace_bytes_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext]
+        lib.pfa_fa3_decode_check_ex.restype = C.c_int
+        lib.pfa_fa3_decode_check_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext]
+        lib.pfa_fa3_decode_ex.restype = C.c_int
+        lib.pfa_fa3_decode_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_void_p]
+        lib.pfa_fa3_decode_describe_ex.restype = C.c_int
+        lib.pfa_fa3_decode_describe_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.pfa_fa3_prefill_check_ex.restype = C.c_int
+        lib.pfa_fa3_prefill_check_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext]
+        lib.pfa_fa3_prefill_ex.restype = C.c_int
+        lib.pfa_fa3_prefill_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_void_p]
+        lib.pfa_fa3_prefill_describe_ex.restype = C.c_int
+        lib.pfa_fa3_prefill_describe_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_char_p, C.c_size_t]
+        lib.pfa_fa3_prefill_varlen_check_ex.restype = C.c_int
+        lib.pfa_fa3_prefill_varlen_check_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext]
+        lib.pfa_fa3_prefill_varlen_ex.restype = C.c_int
+        lib.pfa_fa3_prefill_varlen_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext, C.c_void_p]
+        lib.pfa_fa3_prefill_varlen_describe_ex.restype = C.c_int
+        lib.pfa_fa3_prefill_varlen_describe_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext, C.c_char_p, C.c_size_t]
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
@@ -243,6 +272,46 @@ def describe_prefill_varlen(args: PfaFa3PrefillVarlenArgs):
     """-> (kernel name, workgroups) of ``pfa_fa3_prefill_varlen``: ``B * H * ceil(max_seqlen_q / 256)``, from host shapes only."""
     buf = C.create_string_buffer(128)
     n = load().pfa_fa3_prefill_varlen_describe(C.byref(args), buf, 128)
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n
+
+
+def make_cache_ext(**kw) -> PfaFa3CacheExt:
+    e = PfaFa3CacheExt()
+    e.size = C.sizeof(PfaFa3CacheExt)
+    for k, v in kw.items():
+        setattr(e, k, v)
+    return e
+
+
+def _ext_ref(ext: Optional[PfaFa3CacheExt]):
+    return None if ext is None else C.byref(ext)
+
+
+def describe_decode_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
+    """``describe_decode`` of ``pfa_fa3_decode_ex`` (``ext`` None: the NULL extension); "_win" marks a windowed kernel."""
+    buf = C.create_string_buffer(128)
+    ns = C.c_int32(0)
+    n = load().pfa_fa3_decode_describe_ex(C.byref(args), _ext_ref(ext), buf, 128, C.byref(ns))
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n, ns.value
+
+
+def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
+    """``describe_prefill`` of ``pfa_fa3_prefill_ex``."""
+    buf = C.create_string_buffer(128)
+    n = load().pfa_fa3_prefill_describe_ex(C.byref(args), _ext_ref(ext), buf, 128)
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n
+
+
+def describe_prefill_varlen_ex(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaFa3CacheExt]):
+    """``describe_prefill_varlen`` of ``pfa_fa3_prefill_varlen_ex``."""
+    buf = C.create_string_buffer(128)
+    n = load().pfa_fa3_prefill_varlen_describe_ex(C.byref(args), _ext_ref(ext), buf, 128)
     if n < 0:
         check_status(n)
     return buf.value.decode(), n

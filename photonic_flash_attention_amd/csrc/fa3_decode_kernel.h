@@ -26,6 +26,14 @@
 //     ceil(len_b / page_size) is never read, because a tile exists only below the split's hi <= len_b.  Everything else (split rule,
 //     masks by logical key, softmax, merge, combine) is the one code path, so a paged call returns the bits of the contiguous call
 //     on the gathered cache.  Pages of 16 or 32 keys would put several pages under one tile and are out of scope.
+//   * WINDOW = true (pfa_fa3_decode_ex with a window W, causal only; DecodeWinParams carries W): row i sees key j iff j < len_b,
+//     j <= i + off_b and j > i + off_b - W, off_b = len_b - Sq.  The splits divide [base_b, len_b) instead of [0, len_b), with
+//     base_b = floor64(lo_b) and lo_b = max(0, off_b - W + 1) the lowest key row 0 sees: c_b = roundup(ceil((len_b - base_b) / nsplit), 64),
+//     split s covers [base_b + s c_b, min(base_b + (s+1) c_b, len_b)).  Boundaries stay multiples of 64, so a tile still lies inside
+//     one page.  No tile exists below base_b: keys below it, and table entries below lo_b / page_size, are never read (a server may
+//     have given those pages away).  Each row's lower bound row_lo = len_b - Sq + i + 1 - W joins the visibility test on the tiles that
+//     reach below the item's largest row_lo; keys in [base_b, row_lo) are read and masked.  The other instantiations are untouched:
+//     WINDOW = false compiles to the code and the kernel arguments it had.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,6 +84,13 @@ struct DecodeParams {
     int32_t page_size, num_pages;
 };
 
+// WINDOW only: the sliding window, 1 <= window <= Smax (the host clamps it)
+struct DecodeWinParams : DecodeParams {
+    int32_t window;
+};
+template <bool WINDOW> struct DecodeParamsOf { typedef DecodeParams type; };
+template <> struct DecodeParamsOf<true> { typedef DecodeWinParams type; };
+
 template <typename T> struct DElem;
 template <> struct DElem<__bf16> {
     using v8 = bf16x8;
@@ -125,17 +140,17 @@ template <> __device__ __forceinline__ void store4<_Float16>(_Float16* p, f32x4 
     *(f16x4*)p = f16x4{(_Float16)x[0], (_Float16)x[1], (_Float16)x[2], (_Float16)x[3]};
 }
 
-// The split of batch b this item covers: [lo, hi) (empty when lo >= hi).  len is the batch's valid key count.
-__device__ __forceinline__ void split_range(const DecodeParams& p, int b, int s, int& len, int& lo, int& hi) {
-    len = p.seqlens ? min(max(p.seqlens[b], 0), p.Smax) : p.Smax;
-    const int per = (len + p.nsplit - 1) / p.nsplit;
+// The split of batch b this item covers: [lo, hi) (empty when lo >= hi).  len is the batch's valid key count.  The splits divide
+// [base, len): base = 0, or under a window the 64-key boundary at or below the lowest key row 0 of the batch sees.
+__device__ __forceinline__ void split_range(const DecodeParams& p, int s, int base, int len, int& lo, int& hi) {
+    const int per = (len - base + p.nsplit - 1) / p.nsplit;
     const int c = (per + SPLIT_ALIGN - 1) / SPLIT_ALIGN * SPLIT_ALIGN;
-    lo = min(s * c, len);
+    lo = min(base + s * c, len);
     hi = min(lo + c, len);
 }
 
-template <typename T, int D, typename OT, bool PAGED = false>
-__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodeParams p) {
+template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false>
+__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW>::type p) {
     using E = DElem<T>;
     using v8 = typename E::v8;
     using v4 = typename E::v4;
@@ -154,8 +169,10 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
     const int rb = x % p.nrb;
     x /= p.nrb;
     const int kvh = x % p.Hkv, b = x / p.Hkv;
-    int len, lo, hi;
-    split_range(p, b, s, len, lo, hi);
+    int len = p.seqlens ? min(max(p.seqlens[b], 0), p.Smax) : p.Smax, lo, hi;
+    int base = 0;
+    if constexpr (WINDOW) base = max(0, len - p.Sq - p.window + 1) & ~(SPLIT_ALIGN - 1);
+    split_range(p, s, base, len, lo, hi);
     len = __builtin_amdgcn_readfirstlane(len);
     lo = __builtin_amdgcn_readfirstlane(lo);
     hi = __builtin_amdgcn_readfirstlane(hi);
@@ -168,6 +185,13 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
     const int head = kvh * p.G + qg;
     const int row_lim = p.causal ? len - p.Sq + qi + 1 : len;     // exclusive key bound of this row (before the split's)
     const int min_lim = p.causal ? len - p.Sq + 1 : len;          // every row sees at least the keys below this
+    // WINDOW (causal): the row's lowest visible key, and the largest of them among the item's rows (its last row's)
+    int row_lo = 0, max_lo = 0;
+    if constexpr (WINDOW) {
+        row_lo = row_lim - p.window;
+        const int last = min(rb * ROWS + ROWS - 1, p.Sq * p.G - 1);
+        max_lo = __builtin_amdgcn_readfirstlane(len - p.Sq + last / p.G + 1 - p.window);
+    }
 
     f32x4 oacc[NDB];
 #pragma unroll
@@ -251,8 +275,8 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
             }
             if (t + NW < ntile) issue(t + NW);
 
-            // scores in log2 units; masks only where the tile reaches past the split, the causal cut, or a key mask exists
-            const bool edge = km != nullptr || t0 + KT > hi || t0 + KT > min_lim;
+            // scores in log2 units; masks only where the tile reaches past the split, the causal cut, below a row's window, or a key mask exists
+            const bool edge = km != nullptr || t0 + KT > hi || t0 + KT > min_lim || (WINDOW && t0 < max_lo);
             float mx = -__builtin_inff();
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
@@ -261,7 +285,9 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const DecodePara
                     float sc = sacc[kb][e] * p.scale_log2;
                     if (edge) {
                         const int key = t0 + kb * 16 + 4 * h + e;
-                        bool vis = key < hi && key < row_lim;
+                        bool vis;
+                        if constexpr (WINDOW) vis = key < hi && (uint32_t)(key - row_lo) < (uint32_t)p.window;   // row_lo <= key < row_lim
+                        else vis = key < hi && key < row_lim;
                         if (vis && km) vis = km[key] != 0;
                         sc = vis ? sc : -__builtin_inff();
                     }

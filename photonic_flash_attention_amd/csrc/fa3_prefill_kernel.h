@@ -36,6 +36,21 @@
 //     kernel runs such a wave on copies of the last row).  Nothing it holds is stored.
 // The Q clamp (row min(my_q, Sq_b - 1)) and therefore the rescale points of the wave-wide deferred max are those of the uniform kernel
 // at Sq = Sq_b, so a ragged call returns the bits of per-batch uniform calls.
+//
+// WINDOW (pfa_fa3_prefill_ex / pfa_fa3_prefill_varlen_ex with a window W; CAUSAL only, Prefill*WinParams carry W, clamped to Smax by the
+// host): row i sees key j iff j < len_b, j <= i + off_b and j > i + off_b - W.  What changes:
+//   - a block's first tile is j_lo = max(0, q0 + off_b - W + 1) / 64 and its loop runs j_lo .. nt - 1.  Tiles below it are never
+//     fetched, so keys below floor64(max(0, off_b - W + 1)) -- block 0's first tile -- are never read by anybody;
+//   - a wave computes no tile that lies wholly below its first row's bound wave_q0 + off_b - W + 1, as it computes none above
+//     wave_kv_end: it issues its DMA pieces and meets the barriers.  Its first computed tile need not be the block's first, and a
+//     row's first visible key may lie in a later tile than the wave's first: such a row carries m_run = -1e30, l = 0, O = 0 through
+//     tiles whose scores are all -inf (exp2(-inf) = 0, and the wave-wide rescale another row asks for multiplies its zeros by
+//     exp2(0) = 1), and its first finite score rescales them by exp2(-huge) = 0.  The same holds for the rows of len_b < Sq_b;
+//   - the lower bound is applied to the scores only on tiles that reach below the wave's LAST row's bound (need_mask grows by one
+//     wave-uniform term); a tile inside every row's window takes the unmasked path;
+//   - PAGED: dma_tile starts at table entry 64 j_lo / page_size, token 64 j_lo % page_size (one division in the prologue) and
+//     advances by addition as before; the first scalar table load is that entry, and entries below it are never read.
+// WINDOW = false compiles to the code and the kernel arguments the instantiation had.
 #pragma once
 #include "fa3_fwd_kernel.h"
 
@@ -66,13 +81,23 @@ struct PrefillVarlenParams : PrefillParams {
     const int32_t* cu_seqlens_q; // [B + 1] packed row of each batch's first query row
     int32_t total_q;             // rows of the packed q / o
 };
-template <bool VARLEN> struct PrefillParamsOf { typedef PrefillParams type; };
-template <> struct PrefillParamsOf<true> { typedef PrefillVarlenParams type; };
+// WINDOW: the sliding window, 1 <= window <= Smax
+struct PrefillWinParams : PrefillParams {
+    int32_t window;
+};
+struct PrefillVarlenWinParams : PrefillVarlenParams {
+    int32_t window;
+};
+template <bool VARLEN, bool WINDOW = false> struct PrefillParamsOf { typedef PrefillParams type; };
+template <> struct PrefillParamsOf<true, false> { typedef PrefillVarlenParams type; };
+template <> struct PrefillParamsOf<false, true> { typedef PrefillWinParams type; };
+template <> struct PrefillParamsOf<true, true> { typedef PrefillVarlenWinParams type; };
 
 typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
 
-template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false>
-__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN>::type p) {
+template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW>::type p) {
+    static_assert(CAUSAL || !WINDOW, "the window is cut from the causal diagonal");
     constexpr int NW = FWD_WAVES, BLOCK_M = FWD_BLOCK_M;
     using E = Elem<T>;
     using v8 = typename E::v8;
@@ -128,6 +153,14 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     const int wave_kv_end = !wave_has_rows ? 0 : CAUSAL ? min(kv_len, wave_q0 + WAVE_M + off) : kv_len;   // keys this wave needs (<= 0: none)
     const int my_lim = my_q + off;                       // last key this row sees under the causal cut
     const int nt = (kv_end + BLOCK_N - 1) / BLOCK_N;
+    // WINDOW: the block's first tile (j_lo < nt whenever nt > 0: q0 < sq puts the block's lowest bound below kv_end), the lowest
+    // key the wave's first row sees, and the lowest its last row sees (both may be negative)
+    int j_lo = 0, wave_lo = 0, wave_lo_last = 0;
+    if constexpr (WINDOW) {
+        j_lo = max(0, q0 + off - p.window + 1) / BLOCK_N;
+        wave_lo = wave_q0 + off - p.window + 1;
+        wave_lo_last = wave_lo + WAVE_M - 1;
+    }
 
     const int kvh = hh / p.kv_group;
     const T* __restrict__ qp = (const T*)p.q + (VARLEN ? (int64_t)row0 * p.q_ss : (int64_t)b * p.q_sb) + (int64_t)hh * p.q_sh;
@@ -172,12 +205,17 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
         vvoff[t] = (uint32_t)(dma_key[t] * (int)p.v_ss + dma_col) * 2u;
     }
     // (2) paged: page id of the NEXT tile to fetch (a scalar load issued behind the previous tile's DMA), its index in the table
-    // row and the token offset inside the page.  dma_tile is called for j = 0, 1, 2, ... in order, and only for j < nt, i.e. for
-    // keys below kv_end <= len_b: entries at and past ceil(len_b / page_size) are never read.
+    // row and the token offset inside the page.  dma_tile is called for j = j_lo, j_lo + 1, ... in order (j_lo = 0 without a window),
+    // and only for j < nt, i.e. for keys below kv_end <= len_b: entries at and past ceil(len_b / page_size), and those below
+    // 64 j_lo / page_size, are never read.
     const prefill_table_ptr table = PAGED ? (prefill_table_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
     int pg_next = 0, pg_idx = 0, pg_tok = 0;
     if constexpr (PAGED) {
-        if (nt > 0) pg_next = table[0];
+        if constexpr (WINDOW) {
+            pg_idx = (int)((uint32_t)(j_lo * BLOCK_N) / (uint32_t)p.page_size);
+            pg_tok = j_lo * BLOCK_N - pg_idx * p.page_size;
+        }
+        if (j_lo < nt) pg_next = table[pg_idx];
     }
     auto dma_tile = [&](auto bufc, int j) {
         constexpr int BUF = decltype(bufc)::value;
@@ -273,7 +311,8 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
         __builtin_amdgcn_sched_group_barrier(0x008, PF, 0);
 
         // mask: wave-uniform test, only the tiles on the wave's causal diagonal and the batch's last tile pay
-        const bool need_mask = (key_base + BLOCK_N > kv_len) || (CAUSAL && key_base + BLOCK_N - 1 > wave_q0 + off);
+        const bool need_mask = (key_base + BLOCK_N > kv_len) || (CAUSAL && key_base + BLOCK_N - 1 > wave_q0 + off) ||
+                               (WINDOW && key_base < wave_lo_last);
         if (need_mask) {
             asm volatile("" ::: "memory");   // keep this a real (wave-uniform) branch, not 32 v_cmp + 32 v_cndmask on every tile
 #pragma unroll
@@ -283,6 +322,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
                     const int key = key_base + 32 * kb + (e & 3) + 8 * (e >> 2) + 4 * h;
                     bool ok = key < kv_len;
                     if (CAUSAL) ok = ok && (key <= my_lim);
+                    if constexpr (WINDOW) ok = ok && (key > my_lim - p.window);
                     s[kb][e] = ok ? s[kb][e] : -INFINITY;
                 }
         }
@@ -348,19 +388,19 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     auto step = [&](auto bufc, int j) {
         constexpr int BUF = decltype(bufc)::value;
         if (j + 1 < nt) dma_tile(IC<BUF ^ 1>{}, j + 1);   // lands in the other buffer under this tile's math
-        if (j * BLOCK_N < wave_kv_end) compute_tile(bufc, j * BLOCK_N);
+        if (j * BLOCK_N < wave_kv_end && (!WINDOW || j * BLOCK_N + BLOCK_N > wave_lo)) compute_tile(bufc, j * BLOCK_N);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed ...
         __builtin_amdgcn_s_waitcnt(0xC07F);               // (lgkmcnt(0): this wave's LDS reads are done)
         __builtin_amdgcn_s_barrier();                     // ... and so have everybody else's
     };
 
-    if (nt > 0) dma_tile(IC<0>{}, 0);
+    if (j_lo < nt) dma_tile(IC<0>{}, j_lo);
     // Q must have LANDED before the loop (see fa3_fwd_kernel: else its vmcnt waits drain the K/V prefetch every iteration)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int j = 0; j < nt; j += 2) {
+    for (int j = j_lo; j < nt; j += 2) {
         step(IC<0>{}, j);
         if (j + 1 < nt) step(IC<1>{}, j + 1);
     }

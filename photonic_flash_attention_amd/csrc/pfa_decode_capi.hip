@@ -22,15 +22,23 @@ struct Plan {
     size_t ws_bytes = 0;
 };
 
-// Everything here depends on shapes only (never on cache_seqlens / key_mask / the block table or the page size), so a captured graph
-// stays valid while they change, and a paged call splits exactly as the contiguous call of the same (B, H, Hkv, Sq, Smax, D).
-Plan plan(const pfa_fa3_decode_args* a) {
+// Everything here depends on shapes and the host window only (never on cache_seqlens / key_mask / the block table or the page size), so a
+// captured graph stays valid while they change, and a paged call splits exactly as the contiguous call of the same (B, H, Hkv, Sq, Smax,
+// D, window).  window (0: none, else 1 .. Smax): the keys a batch's splits divide are at most window + Sq - 1 and the up to 63 below
+// them in the first tile, so that span, rounded to tiles, stands where Smax does -- a 4096-key window over a 128K cache is not cut
+// into 128 splits of a few tiles.
+Plan plan(const pfa_fa3_decode_args* a, int window) {
     Plan pl;
     pl.G = a->H / a->Hkv;
     pl.nrb = (int)(((int64_t)a->Sq * pl.G + pfa::dec::ROWS - 1) / pfa::dec::ROWS);
     const int64_t base = (int64_t)a->B * a->Hkv * pl.nrb;
     int64_t ns = (kTargetWorkgroups + base - 1) / base;
-    const int64_t max_by_len = a->Smax / kMinSplitKeys > 1 ? a->Smax / kMinSplitKeys : 1;
+    int64_t keys = a->Smax;
+    if (window > 0) {
+        const int64_t span = ((int64_t)window + a->Sq - 1 + pfa::dec::SPLIT_ALIGN - 1) / pfa::dec::SPLIT_ALIGN * pfa::dec::SPLIT_ALIGN;
+        if (span < keys) keys = span;
+    }
+    const int64_t max_by_len = keys / kMinSplitKeys > 1 ? keys / kMinSplitKeys : 1;
     if (ns > max_by_len) ns = max_by_len;
     if (ns > kMaxSplits) ns = kMaxSplits;
     if (ns < 1) ns = 1;
@@ -40,10 +48,13 @@ Plan plan(const pfa_fa3_decode_args* a) {
     return pl;
 }
 
-int check(const pfa_fa3_decode_args* a) {
-    const int st = pfa::check_cache_args(a, 64);
+// -> PFA_OK and the kernels' window (0: none) in *window
+int check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, int* window) {
+    int st = pfa::check_cache_args(a, 64);
     if (st != PFA_OK) return st;
-    const Plan pl = plan(a);
+    st = pfa::check_cache_ext(ext, a->causal, a->Smax, window);
+    if (st != PFA_OK) return st;
+    const Plan pl = plan(a, *window);
     if (pl.items > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (a->D / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
     if (pl.ws_bytes) {
         if (!a->workspace || a->workspace_bytes < pl.ws_bytes) return PFA_ERR_NULL;
@@ -52,11 +63,16 @@ int check(const pfa_fa3_decode_args* a) {
     return PFA_OK;
 }
 
-template <typename T, int D>
+template <typename T, int D, bool WINDOW>
 const void* main_fn(bool out32, bool paged) {
     if (paged)
-        return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, true> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, true>;
-    return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T>;
+        return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, true, WINDOW> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, true, WINDOW>;
+    return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, false, WINDOW> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, false, WINDOW>;
+}
+template <bool WINDOW>
+const void* main_fn(bool bf, int D, bool out32, bool paged) {
+    return bf ? (D == 128 ? main_fn<__bf16, 128, WINDOW>(out32, paged) : main_fn<__bf16, 64, WINDOW>(out32, paged))
+              : (D == 128 ? main_fn<_Float16, 128, WINDOW>(out32, paged) : main_fn<_Float16, 64, WINDOW>(out32, paged));
 }
 template <typename T, int D>
 const void* combine_fn(bool out32) {
@@ -67,31 +83,39 @@ const void* combine_fn(bool out32) {
 
 extern "C" {
 
-size_t pfa_fa3_decode_workspace_bytes(const pfa_fa3_decode_args* a) {
+size_t pfa_fa3_decode_workspace_bytes_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext) {
     if (!a || a->size != sizeof(pfa_fa3_decode_args) || a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->H % a->Hkv != 0 || a->Sq < 1 ||
         a->Smax <= 0 || (a->D != 64 && a->D != 128))
         return 0;
-    return plan(a).ws_bytes;
+    int window;
+    if (pfa::check_cache_ext(ext, a->causal, a->Smax, &window) != PFA_OK) return 0;
+    return plan(a, window).ws_bytes;
 }
 
-int pfa_fa3_decode_check(const pfa_fa3_decode_args* a) { return check(a); }
+int pfa_fa3_decode_check_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext) {
+    int window;
+    return check(a, ext, &window);
+}
 
-int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, int32_t* nsplit) {
-    const int st = check(a);
+int pfa_fa3_decode_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n, int32_t* nsplit) {
+    int window;
+    const int st = check(a, ext, &window);
     if (st != PFA_OK) return st;
-    const Plan pl = plan(a);
+    const Plan pl = plan(a, window);
     if (buf && n)
-        snprintf(buf, n, "fa3_decode_%s_d%d_%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
-                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", pl.nsplit > 1 ? "+combine" : "", a->block_table ? "_paged" : "");
+        snprintf(buf, n, "fa3_decode_%s_d%d_%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
+                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", window ? "_win" : "", pl.nsplit > 1 ? "+combine" : "",
+                 a->block_table ? "_paged" : "");
     if (nsplit) *nsplit = pl.nsplit;
     return (int)pl.items;
 }
 
-int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream) {
-    const int st = check(a);
+int pfa_fa3_decode_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, void* stream) {
+    int window;
+    const int st = check(a, ext, &window);
     if (st != PFA_OK) return st;
-    const Plan pl = plan(a);
-    pfa::dec::DecodeParams p;
+    const Plan pl = plan(a, window);
+    pfa::dec::DecodeWinParams p;    // the window-less kernels take its DecodeParams base, unchanged
     p.q = a->q; p.k = a->k_cache; p.v = a->v_cache; p.o = a->o;
     p.lse = a->lse; p.seqlens = a->cache_seqlens; p.key_mask = a->key_mask;
     p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
@@ -105,15 +129,15 @@ int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream) {
     p.causal = a->causal != 0;
     p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
     p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
+    p.window = window;
 
     const bool bf = a->dtype_in == PFA_DTYPE_BF16, out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr;
-    const void* fn = bf ? (a->D == 128 ? main_fn<__bf16, 128>(out32, paged) : main_fn<__bf16, 64>(out32, paged))
-                        : (a->D == 128 ? main_fn<_Float16, 128>(out32, paged) : main_fn<_Float16, 64>(out32, paged));
+    const void* fn = window ? main_fn<true>(bf, a->D, out32, paged) : main_fn<false>(bf, a->D, out32, paged);
     const void* cfn = bf ? (a->D == 128 ? combine_fn<__bf16, 128>(out32) : combine_fn<__bf16, 64>(out32))
                          : (a->D == 128 ? combine_fn<_Float16, 128>(out32) : combine_fn<_Float16, 64>(out32));
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};
+    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: the base, or all of it
     hipError_t e = hipLaunchKernel(fn, dim3((unsigned)pl.items), dim3(pfa::dec::THREADS), kargs, 0, (hipStream_t)stream);
     if (e == hipSuccess && pl.nsplit > 1) {
         const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
@@ -121,5 +145,13 @@ int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream) {
     }
     return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
+
+// the calls without the extension block
+size_t pfa_fa3_decode_workspace_bytes(const pfa_fa3_decode_args* a) { return pfa_fa3_decode_workspace_bytes_ex(a, nullptr); }
+int pfa_fa3_decode_check(const pfa_fa3_decode_args* a) { return pfa_fa3_decode_check_ex(a, nullptr); }
+int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, int32_t* nsplit) {
+    return pfa_fa3_decode_describe_ex(a, nullptr, buf, n, nsplit);
+}
+int pfa_fa3_decode(const pfa_fa3_decode_args* a, void* stream) { return pfa_fa3_decode_ex(a, nullptr, stream); }
 
 }  // extern "C"

@@ -91,4 +91,18 @@ inline int check_cache_args(const pfa_fa3_decode_args* a, int max_sq) {
     return PFA_OK;
 }
 
+// The extension block of the *_ex calls over a KV cache (include/pfa_hip.h, pfa_fa3_cache_ext), checked after the argument block's own
+// rules.  -> PFA_OK and the window the kernels take in *window: 0 for none, else min(W, Smax) -- a window of Smax keys or more hides
+// nothing, and the clamp keeps the kernels' row bounds inside 32 bits.
+inline int check_cache_ext(const pfa_fa3_cache_ext* e, int causal, int Smax, int* window) {
+    *window = 0;
+    if (!e) return PFA_OK;
+    if (e->size != sizeof(pfa_fa3_cache_ext)) return PFA_ERR_STRUCT_SIZE;
+    if (e->flags != 0 || e->reserved != 0) return PFA_ERR_FLAGS;
+    if (e->window < 0) return PFA_ERR_SHAPE;
+    if (e->window > 0 && causal == 0) return PFA_ERR_FLAGS;
+    *window = e->window < Smax ? e->window : Smax;
+    return PFA_OK;
+}
+
 }  // namespace pfa

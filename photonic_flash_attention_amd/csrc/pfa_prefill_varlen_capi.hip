@@ -32,7 +32,9 @@ pfa_fa3_decode_args as_cache_args(const pfa_fa3_prefill_varlen_args* a) {
     return c;
 }
 
-int check(const pfa_fa3_prefill_varlen_args* a) {
+// -> PFA_OK and the kernel's window (0: none) in *window
+int check(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, int* window) {
+    *window = 0;
     if (!a) return PFA_ERR_NULL;
     if (a->size != sizeof(pfa_fa3_prefill_varlen_args)) return PFA_ERR_STRUCT_SIZE;
     const pfa_fa3_decode_args c = as_cache_args(a);
@@ -42,17 +44,19 @@ int check(const pfa_fa3_prefill_varlen_args* a) {
     if (reinterpret_cast<uintptr_t>(a->cu_seqlens_q) & 3u) return PFA_ERR_ALIGN;
     if (a->total_q < 1 || a->max_seqlen_q > a->total_q) return PFA_ERR_SHAPE;
     if (workgroups(a) > 0x7fffffffLL) return PFA_ERR_SHAPE;
-    return PFA_OK;
+    return pfa::check_cache_ext(ext, a->causal, a->Smax, window);
 }
 
 // fp32 output: P carried as a 16-bit hi + lo pair (SPLITP), as pfa_fa3_prefill does
-template <typename T, int D, bool CAUSAL, bool PAGED>
+template <typename T, int D, bool CAUSAL, bool PAGED, bool WINDOW = false>
 const void* fn_out(bool out32) {
-    return out32 ? (const void*)&pfa::fa3_prefill_kernel<T, D, CAUSAL, true, PAGED, float, true>
-                 : (const void*)&pfa::fa3_prefill_kernel<T, D, CAUSAL, false, PAGED, T, true>;
+    return out32 ? (const void*)&pfa::fa3_prefill_kernel<T, D, CAUSAL, true, PAGED, float, true, WINDOW>
+                 : (const void*)&pfa::fa3_prefill_kernel<T, D, CAUSAL, false, PAGED, T, true, WINDOW>;
 }
+// the windowed instantiations exist under the causal flag only
 template <typename T, int D>
-const void* fn_td(bool causal, bool paged, bool out32) {
+const void* fn_td(bool causal, bool paged, bool out32, bool window) {
+    if (window) return paged ? fn_out<T, D, true, true, true>(out32) : fn_out<T, D, true, false, true>(out32);
     if (causal) return paged ? fn_out<T, D, true, true>(out32) : fn_out<T, D, true, false>(out32);
     return paged ? fn_out<T, D, false, true>(out32) : fn_out<T, D, false, false>(out32);
 }
@@ -61,21 +65,26 @@ const void* fn_td(bool causal, bool paged, bool out32) {
 
 extern "C" {
 
-int pfa_fa3_prefill_varlen_check(const pfa_fa3_prefill_varlen_args* a) { return check(a); }
+int pfa_fa3_prefill_varlen_check_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext) {
+    int window;
+    return check(a, ext, &window);
+}
 
-int pfa_fa3_prefill_varlen_describe(const pfa_fa3_prefill_varlen_args* a, char* buf, size_t n) {
-    const int st = check(a);
+int pfa_fa3_prefill_varlen_describe_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n) {
+    int window;
+    const int st = check(a, ext, &window);
     if (st != PFA_OK) return st;
     if (buf && n)
-        snprintf(buf, n, "fa3_prefill_%s_d%d_%s%s_varlen%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
-                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", a->causal ? "_causal" : "", a->block_table ? "_paged" : "");
+        snprintf(buf, n, "fa3_prefill_%s_d%d_%s%s%s_varlen%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
+                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", a->causal ? "_causal" : "", window ? "_win" : "", a->block_table ? "_paged" : "");
     return (int)workgroups(a);
 }
 
-int pfa_fa3_prefill_varlen(const pfa_fa3_prefill_varlen_args* a, void* stream) {
-    const int st = check(a);
+int pfa_fa3_prefill_varlen_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, void* stream) {
+    int window;
+    const int st = check(a, ext, &window);
     if (st != PFA_OK) return st;
-    pfa::PrefillVarlenParams p;
+    pfa::PrefillVarlenWinParams p;   // the window-less kernels take its PrefillVarlenParams base, unchanged
     p.q = a->q; p.k = a->k_cache; p.v = a->v_cache; p.o = a->o;
     p.lse = a->lse; p.seqlens = a->cache_seqlens;
     p.q_sb = 0; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
@@ -88,17 +97,24 @@ int pfa_fa3_prefill_varlen(const pfa_fa3_prefill_varlen_args* a, void* stream) {
     p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
     p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
     p.cu_seqlens_q = a->cu_seqlens_q; p.total_q = a->total_q;
+    p.window = window;
 
     const bool bf = a->dtype_in == PFA_DTYPE_BF16, out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr;
     const bool causal = a->causal != 0;
-    const void* fn = bf ? (a->D == 128 ? fn_td<__bf16, 128>(causal, paged, out32) : fn_td<__bf16, 64>(causal, paged, out32))
-                        : (a->D == 128 ? fn_td<_Float16, 128>(causal, paged, out32) : fn_td<_Float16, 64>(causal, paged, out32));
+    const bool win = window != 0;
+    const void* fn = bf ? (a->D == 128 ? fn_td<__bf16, 128>(causal, paged, out32, win) : fn_td<__bf16, 64>(causal, paged, out32, win))
+                        : (a->D == 128 ? fn_td<_Float16, 128>(causal, paged, out32, win) : fn_td<_Float16, 64>(causal, paged, out32, win));
     const int lds = 2 * 2 * pfa::BLOCK_N * a->D * 2;      // two buffers of a K and a V tile image (<= 64 KiB)
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};
+    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: the base, or all of it
     const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)workgroups(a)), dim3(pfa::FWD_THREADS), kargs, (size_t)lds, (hipStream_t)stream);
     return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
 }
+
+// the calls without the extension block
+int pfa_fa3_prefill_varlen_check(const pfa_fa3_prefill_varlen_args* a) { return pfa_fa3_prefill_varlen_check_ex(a, nullptr); }
+int pfa_fa3_prefill_varlen_describe(const pfa_fa3_prefill_varlen_args* a, char* buf, size_t n) { return pfa_fa3_prefill_varlen_describe_ex(a, nullptr, buf, n); }
+int pfa_fa3_prefill_varlen(const pfa_fa3_prefill_varlen_args* a, void* stream) { return pfa_fa3_prefill_varlen_ex(a, nullptr, stream); }
 
 }  // extern "C"

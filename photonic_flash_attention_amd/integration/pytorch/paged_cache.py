@@ -7,6 +7,10 @@ the lengths (the caller says how many tokens it appends, so the host always know
 device.  The device tensors ``block_table`` and ``cache_seqlens`` are allocated once and updated in place, so a captured graph of
 ``decode`` keeps seeing them; pages a sequence will grow into during replays are assigned ahead with ``reserve``.
 
+A model with sliding-window attention passes ``window=`` to ``decode`` / ``prefill`` / ``prefill_varlen``; the kernels then never read
+a key below the 64-key boundary under the lowest visible key, nor its table entry, and ``release_behind_window`` returns the pages
+wholly behind the window to the pool while the sequence keeps its logical positions.
+
 Everything except ``decode``, ``prefill`` and ``prefill_varlen`` (the HIP kernels) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
 The token append is a few KiB per step and stays torch ops; the hot path is the decode kernel.
 """
@@ -84,7 +88,8 @@ class PagedKVCache:
         return self._host_lens[self._check_slot(slot)]
 
     def pages(self, slot: int) -> Tuple[int, ...]:
-        """The pages assigned to the slot, in logical order (those holding tokens first, then the reserved ones)."""
+        """The pages assigned to the slot, in logical order (those holding tokens first, then the reserved ones); -1 stands for a
+        page ``release_behind_window`` gave back."""
         return tuple(self._pages[self._check_slot(slot)])
 
     def _check_slot(self, slot: int) -> int:
@@ -130,13 +135,39 @@ class PagedKVCache:
         self._assign(slot, missing)
 
     def free(self, slot: int) -> None:
-        """Give the slot and its pages back.  The pages' contents and the table row stay as they are; neither is read again."""
+        """Give the slot and its pages back (those not released already).  The pages' contents and the table row stay as they
+        are; neither is read again."""
         self._check_slot(slot)
-        self._free_pages.extend(reversed(self._pages[slot]))
+        self._free_pages.extend(pg for pg in reversed(self._pages[slot]) if pg >= 0)
         self._pages[slot] = []
         self._host_lens[slot] = 0
         self._live[slot] = False
         self._lens[slot] = 0
+
+    def release_behind_window(self, slot: int, window: int) -> int:
+        """Return to the pool every page of the slot that lies wholly behind a sliding window of ``window`` keys: logical page p
+        with ``(p + 1) * page_size <= max(0, length(slot) - window + 1)``, the lowest key the sequence's newest row sees.  -> the
+        number of pages released by this call.
+
+        The slot keeps its length and logical positions: later appends go where they would have gone and take fresh pages.  The
+        released table entries are overwritten with -1 and ``pages()`` reports -1 for them.  Afterwards the slot may only be read
+        with ``window=`` this value or smaller, by calls whose query rows are the tokens appended since (one decode row, a chunk,
+        a ragged step): such a call's lowest visible key is at or above the bound used here, and the kernels read neither a key
+        below that key's 64-key boundary nor its table entry.  ``gather`` and ``swap_pages`` refuse a released page.  Host-side
+        bookkeeping plus one small table write; works on CPU tensors."""
+        self._check_slot(slot)
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError(f"window must be an integer >= 1, got {window!r}")
+        pg = self._pages[slot]
+        behind = min(max(0, self._host_lens[slot] - window + 1) // self.page_size, len(pg))
+        gone = [p for p in range(behind) if pg[p] >= 0]
+        if not gone:
+            return 0
+        self._free_pages.extend(pg[p] for p in reversed(gone))
+        for p in gone:
+            pg[p] = -1
+        self._table[slot, gone[0]:behind] = -1           # every entry in front of it went in an earlier call
+        return len(gone)
 
     def append(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor) -> None:
         """Write ``k_new`` / ``v_new`` ``[n, Hkv, Sq, D]`` at the current end of each of the ``n`` slots and advance their lengths.
@@ -203,6 +234,8 @@ class PagedKVCache:
         pg = self._pages[self._check_slot(slot)]
         if not (0 <= i < len(pg) and 0 <= j < len(pg)):
             raise ValueError(f"slot {slot} has {len(pg)} pages")
+        if pg[i] < 0 or pg[j] < 0:
+            raise ValueError(f"slot {slot}: page {i if pg[i] < 0 else j} was released behind the window")
         if i == j:
             return
         a, b = pg[i], pg[j]
@@ -217,6 +250,8 @@ class PagedKVCache:
     def gather(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The slot's K and V as contiguous ``[Hkv, len, D]`` tensors (tests, debugging)."""
         n = self._host_lens[self._check_slot(slot)]
+        if any(p < 0 for p in self._pages[slot][:-(-n // self.page_size)]):
+            raise ValueError(f"slot {slot}: its first pages were released behind the window, their keys are gone")
         pg = torch.tensor(self._pages[slot][:-(-n // self.page_size)], dtype=torch.int64).to(self.device)
         out = []
         for pool in (self._k, self._v):
@@ -243,8 +278,9 @@ class PagedKVCache:
         """``ops.fa3_decode`` of ``q [B, H, Sq, D]`` against the sequences in ``slots`` (batch row i reads slot ``slots[i]``; None:
         all ``max_batch`` slots in order).  None and a run of consecutive slots read the cache's own table and lengths, so the
         call can be captured in a graph and replayed while the cache changes; any other list takes a copy of its rows first.
-        Keyword arguments (``causal``, ``key_mask`` over ``max_pages_per_seq * page_size`` logical keys, ``out_dtype``, ...) pass
-        through.  -> ``(o, lse)``."""
+        Keyword arguments (``causal``, ``key_mask`` over ``max_pages_per_seq * page_size`` logical keys, ``out_dtype``,
+        ``window`` -- the sliding window, required once ``release_behind_window`` has given pages back --, ...) pass through.
+        -> ``(o, lse)``."""
         table, lens = self._rows(slots)
         return ops.fa3_decode(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
 
@@ -252,7 +288,7 @@ class PagedKVCache:
         """``ops.fa3_prefill_cache`` of ``q [B, H, Sq, D]`` (any Sq: a prompt chunk, the suffix behind shared prefix pages, a
         speculative step) against the sequences in ``slots``, which are chosen and captured as in ``decode``.  ``append`` the rows'
         own K / V first: the lengths count them, and ``causal`` (the default) is bottom-right aligned.  Keyword arguments
-        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ...) pass through.  -> ``(o, lse)``."""
+        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o, lse)``."""
         table, lens = self._rows(slots)
         return ops.fa3_prefill_cache(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
 
@@ -263,7 +299,7 @@ class PagedKVCache:
         rows' own K / V first.  A host list ``q_lens`` becomes a device ``cu_seqlens_q`` by a non-blocking copy, with
         ``max_seqlen_q = max(q_lens)`` unless given; a caller that captures graphs passes its own device ``cu_seqlens_q`` (int32
         ``[len(slots) + 1]``, updated in place between replays) and the ``max_seqlen_q`` bound instead.  Keyword arguments
-        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
+        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
         table, lens = self._rows(slots)
         if (q_lens is None) == (cu_seqlens_q is None):
             raise ValueError("give either q_lens (a host list) or cu_seqlens_q (a device tensor) with max_seqlen_q")

@@ -14,6 +14,7 @@ No fallback lives here: unsupported arguments raise ``ValueError`` (pre-launch
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import threading
 from typing import Optional, Tuple
 
@@ -532,12 +533,28 @@ def _set_cache_seqlens(a, cache_seqlens, q, keep, B=None) -> None:
         keep.append(sl)
 
 
+def _window_ext(window, causal):
+    """``window`` (None, or an integer >= 1: each row sees its last ``window`` keys) as the ``*_ex`` calls' extension block, or None.
+    Refused before anything is launched: any other value, and a window without ``causal``."""
+    if window is None:
+        return None
+    try:
+        w = None if isinstance(window, bool) else operator.index(window)
+    except TypeError:
+        w = None
+    if w is None or w < 1:
+        raise ValueError(f"window must be None or an integer >= 1, got {window!r}")
+    if not causal:
+        raise ValueError("a sliding window needs causal=True (it is cut from the causal diagonal)")
+    return _capi.make_cache_ext(window=min(w, 0x7fffffff))
+
+
 def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
                out: Optional[torch.Tensor] = None,
-               block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Decode attention over a KV cache (``pfa_fa3_decode``): a few new query rows per batch against the cached keys.  Inference only.
+               block_table: Optional[torch.Tensor] = None, window: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
     k_cache / v_cache: ``[B,Hkv,Smax,D]``-shaped views, H a multiple of Hkv (a flash-attn ``[B,Smax,Hkv,D]`` buffer is passed as
@@ -552,7 +569,15 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     page_size a multiple of 64: logical key j of batch b lives in page ``block_table[b, j // page_size]`` at token ``j % page_size``.
     Smax is then ``max_pages * page_size``; cache_seqlens, key_mask (``[B, max_pages * page_size]``) and causal are over logical keys.
     Table entries at and past ``ceil(len_b / page_size)`` are never read; page ids are clamped into the pool by the kernel.  The
-    result is bit for bit that of the contiguous call on the gathered cache."""
+    result is bit for bit that of the contiguous call on the gathered cache.
+
+    Sliding window: ``window=W`` (an integer >= 1, with ``causal=True``; Hugging Face's ``sliding_window``, flash-attn's
+    ``window_size=(W - 1, 0)``): a row sees at most W keys, its own diagonal key included -- row i sees key j iff j < len_b,
+    j <= len_b - Sq + i and j > len_b - Sq + i - W.  A key_mask combines with it (AND).  Only the windowed span is streamed, and it
+    alone is split over workgroups.  With lo_b = max(0, len_b - Sq - W + 1), keys below lo_b rounded down to a multiple of 64 and
+    table entries below ``lo_b // page_size`` are never read, so the pages behind the window can be given away
+    (``PagedKVCache.release_behind_window``); keys between that boundary and a row's own bound are read and masked.  ``None``: no window."""
+    ext = _window_ext(window, causal)
     a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     B, H, Sq, _ = q.shape
     keep = []
@@ -574,13 +599,14 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
     lib = _capi.load()
-    ws_bytes = int(lib.pfa_fa3_decode_workspace_bytes(C.byref(a)))
+    ext_ref = None if ext is None else C.byref(ext)
+    ws_bytes = int(lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), ext_ref))
     if ws_bytes:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
         keep.append(ws)
     stream = torch.cuda.current_stream(q.device)
-    st = lib.pfa_fa3_decode(C.byref(a), C.c_void_p(stream.cuda_stream))
+    st = lib.pfa_fa3_decode_ex(C.byref(a), ext_ref, C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
         raise ValueError(f"pfa_fa3_decode: {_capi.status_string(st)}")
     _capi.check_status(st)
@@ -592,8 +618,8 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
 def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                       causal: bool = True, softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
                       return_lse: bool = False, out: Optional[torch.Tensor] = None,
-                      block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Forward over a KV cache (``pfa_fa3_prefill``): ANY number of new query rows per batch against the cached keys -- the later
+                      block_table: Optional[torch.Tensor] = None, window: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
     The tensor conventions are those of ``fa3_decode``: q ``[B,H,Sq,D]`` (Sq >= 1, D 64 or 128, bf16 / fp16), k_cache / v_cache
@@ -605,7 +631,13 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     256 query rows per workgroup, and wants B * H * ceil(Sq / 256) of the order of the CU count to fill the chip.
     Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.  No host synchronisation, no workspace and no cached
     allocation: capturable in ``torch.cuda.graph`` and valid while lengths, table and cache change between replays.  A paged call
-    returns the bits of the contiguous call on the gathered cache."""
+    returns the bits of the contiguous call on the gathered cache.
+
+    Sliding window: ``window=W`` (an integer >= 1, with ``causal=True``) as in ``fa3_decode``: row i sees key j iff j < len_b,
+    j <= len_b - Sq + i and j > len_b - Sq + i - W.  A workgroup starts at the first 64-key tile its rows can see.  With
+    lo_b = max(0, len_b - Sq - W + 1), keys below lo_b rounded down to a multiple of 64 and table entries below ``lo_b // page_size``
+    are never read; keys between that boundary and a row's own bound are read and masked.  ``None``: no window."""
+    ext = _window_ext(window, causal)
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
@@ -614,7 +646,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
     stream = torch.cuda.current_stream(q.device)
-    st = _capi.load().pfa_fa3_prefill(C.byref(a), C.c_void_p(stream.cuda_stream))
+    st = _capi.load().pfa_fa3_prefill_ex(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
         raise ValueError(f"pfa_fa3_prefill: {_capi.status_string(st)}")
     _capi.check_status(st)
@@ -626,8 +658,8 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
                        cache_seqlens: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                        out_dtype: Optional[torch.dtype] = None, return_lse: bool = False, out: Optional[torch.Tensor] = None,
-                       block_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
+                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen_ex``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
     verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
 
@@ -641,7 +673,13 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     sequence covers (gaps, the tail behind ``cu[B]``) are never written; device values out of range are clamped by the kernel.
     Returns ``(o [total_q, H, D], lse [H, total_q] or None)``.  The result is bit for bit that of ``fa3_prefill_cache`` called per
     sequence.  No host synchronisation, no workspace and no cached allocation: capturable in ``torch.cuda.graph`` and valid while
-    cu_seqlens_q, lengths, table and cache change between replays."""
+    cu_seqlens_q, lengths, table and cache change between replays.
+
+    Sliding window: ``window=W`` (an integer >= 1, with ``causal=True``), per sequence as in ``fa3_prefill_cache``: row i of sequence b
+    sees key j iff j < len_b, j <= len_b - Sq_b + i and j > len_b - Sq_b + i - W.  With lo_b = max(0, len_b - Sq_b - W + 1), keys below
+    lo_b rounded down to a multiple of 64 and table entries below ``lo_b // page_size`` are never read; keys between that boundary and a
+    row's own bound are read and masked.  The bits are still those of per-sequence ``fa3_prefill_cache(window=W)`` calls.  ``None``: no window."""
+    ext = _window_ext(window, causal)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q must be 3-D ([total_q,H,D]) and k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
     if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
@@ -679,7 +717,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
     stream = torch.cuda.current_stream(q.device)
-    st = _capi.load().pfa_fa3_prefill_varlen(C.byref(a), C.c_void_p(stream.cuda_stream))
+    st = _capi.load().pfa_fa3_prefill_varlen_ex(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
         raise ValueError(f"pfa_fa3_prefill_varlen: {_capi.status_string(st)}")
     _capi.check_status(st)

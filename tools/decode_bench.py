@@ -14,6 +14,14 @@ host (Python + ctypes) cost of one call and the time of one graph replay.
 ``--shapes B,H,Hkv,D,Skv[;...]`` picks the shapes.
 
     python tools/decode_bench.py --paged 256 [--gather] [--shapes "8,32,8,128,32768;1,32,8,128,32768"] [--reps 7]
+
+``--window W[,W...]`` measures the sliding window: per shape the call without a window, the call with each window over the same full
+cache (``ops.fa3_decode(..., window=W)``), and, as the bound a windowed call should approach, the call without a window over a cache
+that holds only ``Skv = W`` keys -- all timed alternately, every path cycling through its own >= 768 MiB of keys and values: the
+windowed calls take their lengths from a list that slides the window to a different, disjoint span of the caches on every call.
+TB/s of a windowed call is taken over the bytes of its span (the W keys and the up to 63 below them in the first tile).
+
+    python tools/decode_bench.py --window 1024,4096 [--shapes "8,32,8,128,32768;8,32,8,128,131072"] [--reps 7]
 """
 
 from __future__ import annotations
@@ -189,6 +197,85 @@ def main_paged(args, dev):
                 f.write(json.dumps(r) + "\n")
 
 
+def bench_window(B, H, Hkv, D, S, windows, reps, dev):
+    """No window, each window over the full cache, and no window over a cache of W keys (the bound), timed alternately."""
+    cache_bytes = 2 * B * Hkv * S * D * 2
+    if cache_bytes > MAX_CACHE:
+        return None
+    q = torch.randn(B, H, 1, D, device=dev, dtype=torch.bfloat16)
+    n = max(1, math.ceil(MIN_POOL / cache_bytes))
+    full = _caches(B, Hkv, S, D, n, dev)
+    sl = torch.full((B,), S, dtype=torch.int32, device=dev)
+    paths, counts = {"none": lambda i: ops.fa3_decode(q, full[i][0], full[i][1], cache_seqlens=sl)}, {"none": n}
+    span_bytes, small = {}, {}
+    for W in windows:
+        # a windowed call touches only its span: call i reads cache i % n at length S - (i // n) * step, so that the spans of one
+        # timed window are disjoint and exceed the pool size together (as far as the caches are long enough)
+        span = S - max(0, S - W) // 64 * 64
+        span_bytes[W] = 2 * B * Hkv * span * D * 2
+        step = (W + 127) // 64 * 64
+        per_cache = max(1, min(math.ceil(MIN_POOL / span_bytes[W] / n), (S - W) // step + 1))
+        lens = [torch.full((B,), S - j * step, dtype=torch.int32, device=dev) for j in range(per_cache)]
+        paths[f"win{W}"] = lambda i, W=W, lens=lens: ops.fa3_decode(q, full[i % n][0], full[i % n][1], cache_seqlens=lens[i // n], window=W)
+        counts[f"win{W}"] = n * per_cache
+        m = max(1, math.ceil(MIN_POOL / (2 * B * Hkv * W * D * 2)))
+        small[W] = _caches(B, Hkv, W, D, m, dev)
+        paths[f"bound{W}"] = lambda i, W=W: ops.fa3_decode(q, small[W][i][0], small[W][i][1])
+        counts[f"bound{W}"] = m
+    for name, f in paths.items():
+        for i in range(min(2, counts[name])):
+            f(i)
+    torch.cuda.synchronize()
+    times = {name: [] for name in paths}
+    for _ in range(reps):
+        for name, f in paths.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(counts[name]):
+                f(i)
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / counts[name])
+    res = dict(B=B, H=H, Hkv=Hkv, D=D, Skv=S, cache_MB=round(cache_bytes / 1e6, 2), n_caches=n, reps=reps)
+    for name, ts in times.items():
+        res[f"{name}_us"] = round(sorted(ts)[len(ts) // 2], 2)
+        res[f"{name}_us_min"], res[f"{name}_us_max"] = round(min(ts), 2), round(max(ts), 2)
+    res["none_TBs"] = round(cache_bytes / res["none_us"] / 1e6, 3)
+    for W in windows:
+        res[f"win{W}_span_TBs"] = round(span_bytes[W] / res[f"win{W}_us"] / 1e6, 3)
+        res[f"win{W}_cycled_span_MB"] = round(counts[f"win{W}"] * span_bytes[W] / 1e6, 1)       # below 256 MB the spans can sit in the Infinity Cache
+        res[f"bound{W}_TBs"] = round(2 * B * Hkv * W * D * 2 / res[f"bound{W}_us"] / 1e6, 3)
+        res[f"win{W}_over_bound"] = round(res[f"win{W}_us"] / res[f"bound{W}_us"], 3)
+    del full, small
+    torch.cuda.empty_cache()
+    return res
+
+
+def main_window(args, dev):
+    windows = [int(x) for x in args.window.split(",") if x]
+    if args.shapes:
+        shapes = [tuple(int(x) for x in s.split(",")) for s in args.shapes.split(";") if s]
+    else:
+        shapes = [(8, 32, 8, 128, 32768), (8, 32, 8, 128, 131072)]
+    rows = []
+    for B, H, Hkv, D, S in shapes:
+        r = bench_window(B, H, Hkv, D, S, windows, args.reps, dev)
+        if r is None:
+            print(f"B {B} H {H} Hkv {Hkv} D {D} Skv {S}: skipped (cache above {MAX_CACHE >> 30} GiB)", flush=True)
+            continue
+        rows.append(r)
+        print(f"B {B} H {H} Hkv {Hkv} D {D} Skv {S}: no window {r['none_us']:.2f} us [{r['none_us_min']:.2f}, {r['none_us_max']:.2f}] "
+              f"{r['none_TBs']:.2f} TB/s", flush=True)
+        for W in windows:
+            print(f"    W {W:>6}: {r[f'win{W}_us']:.2f} us [{r[f'win{W}_us_min']:.2f}, {r[f'win{W}_us_max']:.2f}] {r[f'win{W}_span_TBs']:.2f} TB/s "
+                  f"of the span ({r[f'win{W}_cycled_span_MB']:.0f} MB of spans cycled) | Skv = W without a window {r[f'bound{W}_us']:.2f} us "
+                  f"[{r[f'bound{W}_us_min']:.2f}, {r[f'bound{W}_us_max']:.2f}] | ratio {r[f'win{W}_over_bound']:.3f}", flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def host_cost(dev):
     """Python + ctypes cost of one fa3_decode call (enqueue only: the GPU side is tiny), and one graph replay of it."""
     B, H, Hkv, D, S = 1, 32, 8, 128, 4096
@@ -245,12 +332,16 @@ def main():
     ap.add_argument("--pool-layout", choices=("phsd", "hpsd"), default="phsd",
                     help="with --paged: pools as [num_pages, page, Hkv, D] (flash-attn style, a token's heads adjacent) or [num_pages, Hkv, page, D] "
                          "(a head's tokens adjacent, like the contiguous [B, Hkv, S, D] caches this tool times)")
-    ap.add_argument("--shapes", default=None, help='with --paged: "B,H,Hkv,D,Skv;..." instead of the DESIGN 4.6 shapes')
+    ap.add_argument("--shapes", default=None, help='with --paged / --window: "B,H,Hkv,D,Skv;..." instead of the DESIGN 4.6 shapes')
+    ap.add_argument("--window", default=None, metavar="W[,W...]", help="measure sliding windows of these many keys against no window")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench measures on the GPU"
     dev = torch.device("cuda:0")
     if args.paged:
         main_paged(args, dev)
+        return
+    if args.window:
+        main_window(args, dev)
         return
     heads = [(32, 8, 128), (64, 8, 128), (32, 32, 128), (16, 16, 64)]
     Bs, Ss = [1, 8, 32], [4096, 32768, 131072]

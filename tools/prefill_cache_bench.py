@@ -14,6 +14,11 @@ the minimum and maximum in the JSON.  TFLOP/s = 4 D x visible (row, key) pairs x
 
     python tools/prefill_cache_bench.py [--reps 5] [--quick] [--no-paged] [--no-today] [--json out.jsonl]
     python tools/prefill_cache_bench.py --shapes "B,H,Hkv,D,chunk,prefix;..."
+
+``--window W`` adds the sliding window: ``fa3_prefill_cache(..., window=W)`` timed alternately with the call without a window on the
+same caches (``prefill_win_us``, ``window_over_none``), TFLOP/s over the pairs the window leaves visible.
+
+    python tools/prefill_cache_bench.py --window 4096 --shapes "8,32,8,128,2048,30720" --no-paged --no-today
 """
 
 from __future__ import annotations
@@ -76,7 +81,7 @@ def _pools(B, Hkv, S, D, page, layout, n, dev, seed):
     return out
 
 
-def bench_shape(B, H, Hkv, D, Sq, prefix, reps, dev, paged=True, today=True):
+def bench_shape(B, H, Hkv, D, Sq, prefix, reps, dev, paged=True, today=True, window=None):
     S = prefix + Sq                                     # keys in the cache when the chunk attends (its own included)
     cache_bytes = 2 * B * Hkv * S * D * 2
     if cache_bytes > MAX_CACHE:
@@ -99,6 +104,8 @@ def bench_shape(B, H, Hkv, D, Sq, prefix, reps, dev, paged=True, today=True):
         ops.fa3_prefill_cache(q, caches[i][0], caches[i][1], cache_seqlens=sl)
 
     paths = {"prefill": prefill}
+    if window:
+        paths["prefill_win"] = lambda i: ops.fa3_prefill_cache(q, caches[i][0], caches[i][1], cache_seqlens=sl, window=window)
     if today:        # the element-mask path on the (already gathered) cache
         mask = (torch.arange(S, device=dev)[None, :] <= torch.arange(Sq, device=dev)[:, None] + prefix)[None, None].expand(B, 1, Sq, S)
         paths["mask_attention"] = lambda i: ops.fa3_forward(q, caches[i][0], caches[i][1], mask=mask)
@@ -107,6 +114,12 @@ def bench_shape(B, H, Hkv, D, Sq, prefix, reps, dev, paged=True, today=True):
         paths["fwd_v0"] = lambda i: ops.fa3_forward(q, caches[i][0], caches[i][1], causal=True, _variant=0)
     _stats(res, _timed(paths, n, reps))
     res["prefill_tflops"] = round(flops / res["prefill_us"] / 1e6, 1)
+    if window:
+        wpairs = sum(min(window, prefix + i + 1) for i in range(Sq))
+        res["window"] = window
+        res["prefill_win_tflops"] = round(4.0 * D * wpairs * B * H / res["prefill_win_us"] / 1e6, 1)
+        res["window_over_none"] = round(res["prefill_win_us"] / res["prefill_us"], 4)
+        res["visible_pairs_ratio"] = round(wpairs / pairs, 4)
     if prefix == 0:
         res["prefill_over_v44"] = round(res["prefill_us"] / res["fwd_v44_us"], 4)
         res["prefill_over_v0"] = round(res["prefill_us"] / res["fwd_v0_us"], 4)
@@ -152,6 +165,7 @@ def main():
     ap.add_argument("--no-paged", action="store_true")
     ap.add_argument("--no-today", action="store_true", help="skip the gather + element-mask baseline")
     ap.add_argument("--shapes", default=None, help='"B,H,Hkv,D,chunk,prefix;..." instead of the profiles/prefill_cache.md shapes')
+    ap.add_argument("--window", type=int, default=None, help="also time fa3_prefill_cache(window=W) against the call without a window")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "prefill_cache_bench measures on the GPU"
@@ -167,7 +181,7 @@ def main():
     print(f"{'B':>2} {'H':>3} {'Hkv':>3} {'D':>4} {'chunk':>5} {'prefix':>6} {'WGs':>5} | {'prefill us':>10} {'TF/s':>6} | {'gather us':>9} {'mask-attn us':>12} "
           f"{'today/new':>9} | {'hpsd64':>6} {'hpsd256':>7} {'phsd64':>6} {'phsd256':>7} | {'/v44':>6} {'/v0':>6}", flush=True)
     for B, H, Hkv, D, c, p in shapes:
-        r = bench_shape(B, H, Hkv, D, c, p, args.reps, dev, paged=not args.no_paged, today=not args.no_today)
+        r = bench_shape(B, H, Hkv, D, c, p, args.reps, dev, paged=not args.no_paged, today=not args.no_today, window=args.window)
         if r is None:
             print(f"{B:>2} {H:>3} {Hkv:>3} {D:>4} {c:>5} {p:>6}  skipped: one cache exceeds {MAX_CACHE >> 30} GiB", flush=True)
             continue
@@ -176,7 +190,10 @@ def main():
         print(f"{B:>2} {H:>3} {Hkv:>3} {D:>4} {c:>5} {p:>6} {r['workgroups']:>5} | {r['prefill_us']:>10.1f} {r['prefill_tflops']:>6.1f} | "
               f"{g('gather_us', '.1f'):>9} {g('mask_attention_us', '.1f'):>12} {g('today_over_prefill', '.2f'):>9} | "
               f"{g('paged_hpsd64_ratio', '.3f'):>6} {g('paged_hpsd256_ratio', '.3f'):>7} {g('paged_phsd64_ratio', '.3f'):>6} "
-              f"{g('paged_phsd256_ratio', '.3f'):>7} | {g('prefill_over_v44', '.3f'):>6} {g('prefill_over_v0', '.3f'):>6}", flush=True)
+              f"{g('paged_phsd256_ratio', '.3f'):>7} | {g('prefill_over_v44', '.3f'):>6} {g('prefill_over_v0', '.3f'):>6}"
+              + (f" | W {args.window}: {r['prefill_win_us']:.1f} us [{r['prefill_win_us_min']:.1f}, {r['prefill_win_us_max']:.1f}] "
+                 f"{r['prefill_win_tflops']:.1f} TF/s, x{r['window_over_none']:.3f} of no window [{r['prefill_us_min']:.1f}, {r['prefill_us_max']:.1f}]"
+                 if args.window else ""), flush=True)
     if args.json:
         with open(args.json, "w") as f:
             for r in rows:
