@@ -10,7 +10,8 @@
  * unchanged pfa_fa3_decode_args);
  * v9, additive: pfa_fa3_prefill_varlen* -- the same forward for ragged batches (packed query rows, cu_seqlens_q on the device);
  * v9, additive: pfa_fa3_cache_ext and the *_ex entry points of the three calls over a KV cache -- a sliding window (each row sees its
- * last `window` keys), with keys and block-table entries behind the window never read.
+ * last `window` keys), with keys and block-table entries behind the window never read;
+ * v9, additive: pfa_kv_append* -- the device-side append of a step's new K / V rows into a contiguous or paged cache.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -458,6 +459,84 @@ int pfa_fa3_prefill_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cach
 int pfa_fa3_prefill_varlen_check_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext);
 int pfa_fa3_prefill_varlen_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, void* stream);
 int pfa_fa3_prefill_varlen_describe_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n);
+
+/*
+ * Device-side KV-cache append (ABI v9, additive): the write side of a step over a KV cache.  Places the step's new K / V rows into a
+ * contiguous or paged cache from device data alone, so that append + attention is two launches with no host round trip, capturable as
+ * a whole -- what flash_attn_with_kvcache(k=, v=) does in front of its attention.
+ *
+ * Lengths are those AFTER the step, the convention of the three calls over a KV cache: one device cache_seqlens serves this call and
+ * the attention call behind it.  The kernel never writes lengths, and a replay is idempotent.  For sequence b:
+ *       len_b = clamp(cache_seqlens[b], 0, Smax)
+ *       ragged  (cu_seqlens_q != NULL): s_b = clamp(cu[b], 0, total_new), e_b = clamp(cu[b + 1], s_b, total_new),
+ *               Sq_b = min(e_b - s_b, max_seqlen_q) -- exactly pfa_fa3_prefill_varlen's clamps; row i is packed row s_b + i
+ *       uniform (cu_seqlens_q == NULL): Sq_b = max_seqlen_q; row i is at b * *n_stride_b + i * *n_stride_s
+ *       new row i (0 <= i < Sq_b) goes to logical key pos = len_b - Sq_b + i.
+ *
+ *   k_new, v_new    [total_new, Hkv, D] packed rows by *n_stride_s / *n_stride_h (last dim contiguous), or uniform [B, Sq, Hkv, D] with
+ *                   *n_stride_b as well; total_new is the rows the tensors hold (ragged: >= max_seqlen_q; uniform: >= B * max_seqlen_q).
+ *   k_cache/v_cache [B, Smax, Hkv, D] by element strides: dst = cache + b * stride_b + pos * stride_s + hk * stride_h.  With block_table,
+ *                   pools [num_pages, page_size, Hkv, D] where *_stride_b are the PAGE strides, exactly as in pfa_fa3_decode_args: the row
+ *                   goes to page block_table[b][pos / page_size] at token pos % page_size, and Smax is max_pages * page_size.
+ *   cache_seqlens   REQUIRED int32 [B] on the device: valid keys of each sequence after the step, its new rows included.
+ *   max_seqlen_q    host bound on the rows of one sequence.  It sizes the grid, B * ceil(max_seqlen_q * Hkv * (D / 8) / 256) workgroups
+ *                   from host shapes only, so a captured graph stays valid while cu_seqlens_q, cache_seqlens, the block table and the
+ *                   tensors change between replays.  Of a sequence with more rows only the first max_seqlen_q are written (at
+ *                   len_b - max_seqlen_q + i: where the attention call, which computes only those rows, looks for them).
+ *
+ * Dropped, not written anywhere: rows with pos < 0 (a sequence with len_b < Sq_b: the rows the attention call gives O = 0), and on a
+ * paged cache rows whose page id lies outside [0, num_pages - 1].  A write is NOT clamped into the pool as the reads are: a clamped read
+ * gives wrong numbers, a clamped write would overwrite a live page of another sequence.  Bad device data loses rows; it never yields an
+ * address outside the cache, the pools or the packed tensors.
+ * Never read: packed rows no sequence covers -- gaps between sequences, the tail behind cu[B], rows of a sequence past max_seqlen_q --
+ * and table entries other than those of the destination rows.  Never written: anything but the destination rows, in cache or pool
+ * (lengths and table included).
+ * If two sequences are given the same destination (a shared prefix page handed to two writers) the row ends up as one of the two.
+ * Copy-on-write of shared pages is the caller's business.
+ *
+ * One launch; no workspace, no atomics, no LDS.  bf16 / fp16 (any 2-byte type moves the same way), D a multiple of 8 up to 256, strides
+ * multiples of 8 elements, base pointers 16-byte aligned: K and V move as 16-byte loads and stores.
+ *
+ * Field rules, in the order their errors are reported: size wrong -> PFA_ERR_STRUCT_SIZE; flags / reserved0 / reserved1 non-zero ->
+ * PFA_ERR_FLAGS; k_new, v_new, k_cache, v_cache or cache_seqlens NULL -> PFA_ERR_NULL; B, Hkv, Smax, total_new or max_seqlen_q < 1 ->
+ * PFA_ERR_SHAPE; D not a multiple of 8 in [8, 256] -> PFA_ERR_HEAD_DIM; dtype not bf16 / fp16 -> PFA_ERR_DTYPE; a stride not a multiple
+ * of 8, or a negative cache token stride -> PFA_ERR_STRIDE; a base not 16-byte aligned, cache_seqlens / cu_seqlens_q / block_table not
+ * 4-byte aligned -> PFA_ERR_ALIGN; the paging fields as in pfa_fa3_decode_args (all zero without a table: PFA_ERR_FLAGS; page_size not a
+ * multiple of 64, num_pages < 1, Smax not a multiple of page_size or block_table_stride_b < Smax / page_size: PFA_ERR_SHAPE); ragged
+ * with a non-zero kn_stride_b / vn_stride_b -> PFA_ERR_FLAGS; ragged with max_seqlen_q > total_new, uniform with B * max_seqlen_q >
+ * total_new, more workgroups than a grid holds or max_seqlen_q * Hkv * (D / 8) + 256 past 2^31 - 1 -> PFA_ERR_SHAPE.
+ */
+typedef struct pfa_kv_append_args {
+    uint32_t size;              /* = sizeof(pfa_kv_append_args) */
+    uint32_t flags;             /* must be 0 */
+    const void* k_new;
+    const void* v_new;
+    void*       k_cache;
+    void*       v_cache;
+    const int32_t* cu_seqlens_q;   /* device [B + 1], or NULL = uniform */
+    const int32_t* cache_seqlens;  /* device [B], required: lengths after the step */
+    int64_t kn_stride_b, kn_stride_s, kn_stride_h;   /* *_b: uniform only, else 0 */
+    int64_t vn_stride_b, vn_stride_s, vn_stride_h;
+    int64_t k_stride_b, k_stride_h, k_stride_s;
+    int64_t v_stride_b, v_stride_h, v_stride_s;
+    int32_t B, Hkv, total_new, max_seqlen_q, Smax, D;
+    int32_t dtype;              /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 */
+    int32_t device_id;
+    /* paged cache, as in pfa_fa3_decode_args.  NULL / 0: the contiguous cache. */
+    const int32_t* block_table;
+    int64_t block_table_stride_b;
+    int32_t page_size;          /* keys per page, a multiple of 64 */
+    int32_t num_pages;          /* pages in the pools */
+    int32_t reserved0, reserved1;   /* must be 0 */
+} pfa_kv_append_args;
+
+/* Validate `a` without launching: PFA_OK or the error pfa_kv_append would return. */
+int pfa_kv_append_check(const pfa_kv_append_args* a);
+/* Enqueue the append (one launch) on `stream`. */
+int pfa_kv_append(const pfa_kv_append_args* a, void* stream);
+/* Introspection: the kernel name ("_varlen" appended with cu_seqlens_q, then "_paged" with a block table) into buf (NUL terminated,
+ * truncated to n); returns the workgroups, or a pfa_status. */
+int pfa_kv_append_describe(const pfa_kv_append_args* a, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

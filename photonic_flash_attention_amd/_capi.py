@@ -31,6 +31,7 @@ EXPORTS = (
     "pfa_fa3_decode_workspace_bytes_ex", "pfa_fa3_decode_check_ex", "pfa_fa3_decode_ex", "pfa_fa3_decode_describe_ex",
     "pfa_fa3_prefill_check_ex", "pfa_fa3_prefill_ex", "pfa_fa3_prefill_describe_ex",
     "pfa_fa3_prefill_varlen_check_ex", "pfa_fa3_prefill_varlen_ex", "pfa_fa3_prefill_varlen_describe_ex",
+    "pfa_kv_append_check", "pfa_kv_append", "pfa_kv_append_describe",
 )
 
 
@@ -101,6 +102,19 @@ class PfaFa3PrefillVarlenArgs(C.Structure):
 class PfaFa3CacheExt(C.Structure):
     """Mirror of ``struct pfa_fa3_cache_ext`` (include/pfa_hip.h): per-call options of the ``*_ex`` calls over a KV cache."""
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PfaKvAppendArgs(C.Structure):
+    """Mirror of ``struct pfa_kv_append_args`` (include/pfa_hip.h): the device-side KV-cache append."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("k_new", "v_new", "k_cache", "v_cache", "cu_seqlens_q", "cache_seqlens")]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in ("kn", "vn") for a in "bsh"]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "kv" for a in "bhs"]
+        + [(n, C.c_int32) for n in ("B", "Hkv", "total_new", "max_seqlen_q", "Smax", "D", "dtype", "device_id")]
+        + [("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64), ("page_size", C.c_int32), ("num_pages", C.c_int32)]
+        + [("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+    )
 
 
 class PfaError(RuntimeError):
@@ -197,6 +211,12 @@ def load(path: Optional[str] = None):
         lib.pfa_fa3_prefill_varlen_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext, C.c_void_p]
         lib.pfa_fa3_prefill_varlen_describe_ex.restype = C.c_int
         lib.pfa_fa3_prefill_varlen_describe_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext, C.c_char_p, C.c_size_t]
+        lib.pfa_kv_append_check.restype = C.c_int
+        lib.pfa_kv_append_check.argtypes = [C.POINTER(PfaKvAppendArgs)]
+        lib.pfa_kv_append.restype = C.c_int
+        lib.pfa_kv_append.argtypes = [C.POINTER(PfaKvAppendArgs), C.c_void_p]
+        lib.pfa_kv_append_describe.restype = C.c_int
+        lib.pfa_kv_append_describe.argtypes = [C.POINTER(PfaKvAppendArgs), C.c_char_p, C.c_size_t]
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
@@ -312,6 +332,23 @@ def describe_prefill_varlen_ex(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaF
     """``describe_prefill_varlen`` of ``pfa_fa3_prefill_varlen_ex``."""
     buf = C.create_string_buffer(128)
     n = load().pfa_fa3_prefill_varlen_describe_ex(C.byref(args), _ext_ref(ext), buf, 128)
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n
+
+
+def make_kv_append_args(**kw) -> PfaKvAppendArgs:
+    a = PfaKvAppendArgs()
+    a.size = C.sizeof(PfaKvAppendArgs)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def describe_kv_append(args: PfaKvAppendArgs):
+    """-> (kernel name, workgroups) of ``pfa_kv_append``: ``B * ceil(max_seqlen_q * Hkv * (D / 8) / 256)``, from host shapes only."""
+    buf = C.create_string_buffer(128)
+    n = load().pfa_kv_append_describe(C.byref(args), buf, 128)
     if n < 0:
         check_status(n)
     return buf.value.decode(), n

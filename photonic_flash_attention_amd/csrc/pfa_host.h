@@ -54,6 +54,19 @@ inline void fill_mask(Params& p, const pfa_fa3_args* a) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The paging fields every call over a KV cache carries (include/pfa_hip.h, pfa_fa3_decode_args): all set, or all zero.
+inline int check_paging(const int32_t* block_table, int64_t block_table_stride_b, int32_t page_size, int32_t num_pages, int32_t Smax) {
+    if (block_table) {
+        // Smax is the logical capacity max_pages * page_size; a 64-key tile must lie inside one page
+        if (page_size <= 0 || page_size % 64 != 0 || num_pages <= 0) return PFA_ERR_SHAPE;
+        if (Smax % page_size != 0 || block_table_stride_b < Smax / page_size) return PFA_ERR_SHAPE;
+        if (reinterpret_cast<uintptr_t>(block_table) & 3u) return PFA_ERR_ALIGN;
+    } else if (page_size != 0 || num_pages != 0 || block_table_stride_b != 0) {
+        return PFA_ERR_FLAGS;
+    }
+    return PFA_OK;
+}
+
 // The field rules pfa_fa3_decode and pfa_fa3_prefill share (include/pfa_hip.h, pfa_fa3_decode_args), in the order their errors are
 // reported: everything but the limits that depend on the kernel (key mask, grid, workspace).  max_sq: the most query rows the caller takes.
 inline int check_cache_args(const pfa_fa3_decode_args* a, int max_sq) {
@@ -80,15 +93,7 @@ inline int check_cache_args(const pfa_fa3_decode_args* a, int max_sq) {
     // a tile's K / V rows are addressed by 32-bit offsets from a per-tile buffer descriptor
     if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_s * 2 * 64 + 256 > 0x7fffffffLL || a->v_stride_s * 2 * 64 + 256 > 0x7fffffffLL)
         return PFA_ERR_STRIDE;
-    if (a->block_table) {
-        // Smax is the logical capacity max_pages * page_size; a 64-key tile must lie inside one page
-        if (a->page_size <= 0 || a->page_size % 64 != 0 || a->num_pages <= 0) return PFA_ERR_SHAPE;
-        if (a->Smax % a->page_size != 0 || a->block_table_stride_b < a->Smax / a->page_size) return PFA_ERR_SHAPE;
-        if (reinterpret_cast<uintptr_t>(a->block_table) & 3u) return PFA_ERR_ALIGN;
-    } else if (a->page_size != 0 || a->num_pages != 0 || a->block_table_stride_b != 0) {
-        return PFA_ERR_FLAGS;
-    }
-    return PFA_OK;
+    return check_paging(a->block_table, a->block_table_stride_b, a->page_size, a->num_pages, a->Smax);
 }
 
 // The extension block of the *_ex calls over a KV cache (include/pfa_hip.h, pfa_fa3_cache_ext), checked after the argument block's own

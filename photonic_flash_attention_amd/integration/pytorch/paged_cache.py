@@ -12,7 +12,10 @@ a key below the 64-key boundary under the lowest visible key, nor its table entr
 wholly behind the window to the pool while the sequence keeps its logical positions.
 
 Everything except ``decode``, ``prefill`` and ``prefill_varlen`` (the HIP kernels) also runs on CPU tensors, which is how the bookkeeping is tested without a GPU.
-The token append is a few KiB per step and stays torch ops; the hot path is the decode kernel.
+``append`` / ``append_varlen`` move the tokens with torch ops from a host-built index, which a captured graph cannot replay.  The
+capturable form splits the append in two: ``advance`` (host: pages, lengths, table) and ``write_step`` (device: ``ops.kv_append``, the
+HIP copy kernel that places the rows from the device table and lengths).  ``advance`` then ``write_step`` equals ``append_varlen``; a
+graph holds ``write_step`` + ``prefill_varlen``, and ``advance`` runs between replays.
 """
 
 from __future__ import annotations
@@ -169,6 +172,24 @@ class PagedKVCache:
         self._table[slot, gone[0]:behind] = -1           # every entry in front of it went in an earlier call
         return len(gone)
 
+    def _grow(self, slots: List[int], lens: List[int]) -> List[int]:
+        """The host half of an append, all or nothing: assign the pages ``lens[i]`` more tokens of ``slots[i]`` need and advance the
+        host lengths.  -> each slot's length before."""
+        missing = [self._pages_missing(self._check_slot(s), self._host_lens[s] + x) for s, x in zip(slots, lens)]
+        if sum(missing) > len(self._free_pages):
+            raise PagedCacheFull(f"the append needs {sum(missing)} more pages, the pool has {len(self._free_pages)} free")
+        starts = []
+        for s, m, x in zip(slots, missing, lens):
+            self._assign(s, m)
+            starts.append(self._host_lens[s])
+            self._host_lens[s] += x
+        return starts
+
+    def _dst_rows(self, slots: List[int], starts: List[int], lens: List[int]) -> List[int]:
+        """Row of the ``[num_pages * page_size]`` token view each appended token goes to."""
+        return [self._pages[s][j // self.page_size] * self.page_size + j % self.page_size
+                for s, at, x in zip(slots, starts, lens) for j in range(at, at + x)]
+
     def append(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor) -> None:
         """Write ``k_new`` / ``v_new`` ``[n, Hkv, Sq, D]`` at the current end of each of the ``n`` slots and advance their lengths.
         Pages are assigned as needed; if the pool cannot serve all of them nothing is written and ``PagedCacheFull`` is raised."""
@@ -181,15 +202,7 @@ class PagedKVCache:
         if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
             raise ValueError("k_new / v_new must have the cache's dtype")
         Sq = k_new.shape[2]
-        missing = [self._pages_missing(self._check_slot(s), self._host_lens[s] + Sq) for s in slots]
-        if sum(missing) > len(self._free_pages):
-            raise PagedCacheFull(f"the append needs {sum(missing)} more pages, the pool has {len(self._free_pages)} free")
-        dst = []
-        for s, m in zip(slots, missing):
-            self._assign(s, m)
-            for j in range(self._host_lens[s], self._host_lens[s] + Sq):
-                dst.append(self._pages[s][j // self.page_size] * self.page_size + j % self.page_size)
-            self._host_lens[s] += Sq
+        dst = self._dst_rows(slots, self._grow(slots, [Sq] * n), [Sq] * n)
         if Sq:
             idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
             rows = self.num_pages * self.page_size
@@ -212,20 +225,27 @@ class PagedKVCache:
             raise ValueError(f"k_new / v_new must be [{total}, {self.Hkv}, {self.D}], got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
         if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
             raise ValueError("k_new / v_new must have the cache's dtype")
-        missing = [self._pages_missing(self._check_slot(s), self._host_lens[s] + x) for s, x in zip(slots, lens)]
-        if sum(missing) > len(self._free_pages):
-            raise PagedCacheFull(f"the append needs {sum(missing)} more pages, the pool has {len(self._free_pages)} free")
-        dst = []
-        for s, m, x in zip(slots, missing, lens):
-            self._assign(s, m)
-            for j in range(self._host_lens[s], self._host_lens[s] + x):
-                dst.append(self._pages[s][j // self.page_size] * self.page_size + j % self.page_size)
-            self._host_lens[s] += x
+        dst = self._dst_rows(slots, self._grow(slots, lens), lens)
         if total:
             idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
             rows = self.num_pages * self.page_size
             self._k.view(rows, self.Hkv, self.D).index_copy_(0, idx, k_new)
             self._v.view(rows, self.Hkv, self.D).index_copy_(0, idx, v_new)
+        self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
+
+    def advance(self, slots: Union[int, Sequence[int]], lens: Sequence[int]) -> None:
+        """The host half of ``append_varlen``: slot ``slots[i]`` grows by ``lens[i]`` tokens (a host list, 0 allowed).  Assigns the
+        pages, updates the host mirror and refreshes the device table and lengths in place; moves no K / V.  All or nothing: if the
+        pool cannot serve every slot nothing changes and ``PagedCacheFull`` is raised.  ``write_step`` is the device half:
+        ``advance(slots, lens)`` followed by ``write_step(k_new, v_new, lens, slots)`` equals ``append_varlen(slots, k_new, v_new,
+        lens)``.  A graph user captures ``write_step`` + ``prefill_varlen`` once and calls ``advance`` between replays."""
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        lens = [int(x) for x in lens]
+        if len(set(slots)) != len(slots):
+            raise ValueError("a slot may appear once per append")
+        if len(lens) != len(slots) or any(x < 0 for x in lens):
+            raise ValueError(f"lens must hold one non-negative token count per slot, got {lens} for {len(slots)} slots")
+        self._grow(slots, lens)
         self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
 
     def swap_pages(self, slot: int, i: int, j: int) -> None:
@@ -274,6 +294,43 @@ class PagedKVCache:
         idx = torch.tensor(slots, dtype=torch.int64).to(self.device)
         return self._table.index_select(0, idx), self._lens.index_select(0, idx)
 
+    def _cu(self, q_lens, cu_seqlens_q, max_seqlen_q, n_slots: int, rows: int, what: str):
+        """A ragged step's ``(cu_seqlens_q, max_seqlen_q)``: the caller's device tensor and bound, or the prefix sums of the host
+        list ``q_lens`` (a non-blocking copy) with ``max(q_lens)`` unless a bound is given."""
+        if (q_lens is None) == (cu_seqlens_q is None):
+            raise ValueError("give either q_lens (a host list) or cu_seqlens_q (a device tensor) with max_seqlen_q")
+        if cu_seqlens_q is None:
+            q_lens = [int(x) for x in q_lens]
+            if len(q_lens) != n_slots or any(x < 0 for x in q_lens):
+                raise ValueError(f"q_lens must hold one non-negative row count per slot, got {q_lens} for {n_slots} slots")
+            cu = [0]
+            for x in q_lens:
+                cu.append(cu[-1] + x)
+            if cu[-1] > rows or cu[-1] < 1:
+                raise ValueError(f"q_lens name {cu[-1]} rows, {what} has {rows}")
+            cu_seqlens_q = torch.tensor(cu, dtype=torch.int32).to(self.device, non_blocking=True)
+            if max_seqlen_q is None:
+                max_seqlen_q = max(q_lens)
+        elif max_seqlen_q is None:
+            raise ValueError("cu_seqlens_q needs max_seqlen_q, the host bound on a sequence's rows (it sizes the grid)")
+        return cu_seqlens_q, max_seqlen_q
+
+    def write_step(self, k_new: torch.Tensor, v_new: torch.Tensor, q_lens: Optional[Sequence[int]] = None, slots: Slots = None, *,
+                   cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None) -> None:
+        """The device half of an append (``ops.kv_append``, one launch of the HIP copy kernel): write the packed ``k_new`` / ``v_new``
+        ``[total, Hkv, D]`` of a ragged step to where the cache's own table and lengths say, sequence i bringing ``q_lens[i]`` rows.
+        Call ``advance`` first: the lengths count the step's rows, and row j of sequence i goes to key ``length - q_lens[i] + j``.  Does
+        no bookkeeping, so ``advance(slots, lens)`` + ``write_step(k_new, v_new, lens, slots)`` equals ``append_varlen``.  Slots are
+        chosen and captured as in ``decode``; a host list ``q_lens``, or a device ``cu_seqlens_q`` (int32 ``[len(slots) + 1]``) plus
+        the ``max_seqlen_q`` bound, as in ``prefill_varlen`` -- the form a graph captures, next to ``prefill_varlen``, and replays
+        while ``advance`` and in-place updates of ``cu_seqlens_q`` and the inputs happen in between.  Also runs on CPU tensors."""
+        table, lens = self._rows(slots)
+        if cu_seqlens_q is None and q_lens is not None and len(q_lens) == table.shape[0] and not any(q_lens):
+            return                                       # a step without rows, as append_varlen takes one
+        cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], k_new.shape[0], "k_new")
+        ops.kv_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, cu_seqlens_q=cu_seqlens_q,
+                      max_seqlen_q=max_seqlen_q, block_table=table)
+
     def decode(self, q: torch.Tensor, slots: Slots = None, **kw):
         """``ops.fa3_decode`` of ``q [B, H, Sq, D]`` against the sequences in ``slots`` (batch row i reads slot ``slots[i]``; None:
         all ``max_batch`` slots in order).  None and a run of consecutive slots read the cache's own table and lengths, so the
@@ -301,21 +358,6 @@ class PagedKVCache:
         ``[len(slots) + 1]``, updated in place between replays) and the ``max_seqlen_q`` bound instead.  Keyword arguments
         (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
         table, lens = self._rows(slots)
-        if (q_lens is None) == (cu_seqlens_q is None):
-            raise ValueError("give either q_lens (a host list) or cu_seqlens_q (a device tensor) with max_seqlen_q")
-        if cu_seqlens_q is None:
-            q_lens = [int(x) for x in q_lens]
-            if len(q_lens) != table.shape[0] or any(x < 0 for x in q_lens):
-                raise ValueError(f"q_lens must hold one non-negative row count per slot, got {q_lens} for {table.shape[0]} slots")
-            cu = [0]
-            for x in q_lens:
-                cu.append(cu[-1] + x)
-            if cu[-1] > q.shape[0] or cu[-1] < 1:
-                raise ValueError(f"q_lens name {cu[-1]} rows, q has {q.shape[0]}")
-            cu_seqlens_q = torch.tensor(cu, dtype=torch.int32).to(self.device, non_blocking=True)
-            if max_seqlen_q is None:
-                max_seqlen_q = max(q_lens)
-        elif max_seqlen_q is None:
-            raise ValueError("cu_seqlens_q needs max_seqlen_q, the host bound on a sequence's rows (it sizes the grid)")
+        cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], q.shape[0], "q")
         return ops.fa3_prefill_varlen(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cu_seqlens_q=cu_seqlens_q,
                                       max_seqlen_q=max_seqlen_q, cache_seqlens=lens, block_table=table, **kw)

@@ -549,11 +549,157 @@ def _window_ext(window, causal):
     return _capi.make_cache_ext(window=min(w, 0x7fffffff))
 
 
+def _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, max_seqlen_q, block_table) -> None:
+    """``pfa_kv_append``'s rule in plain torch, every clamp and drop included: the executable specification, and what ``kv_append``
+    runs on CPU tensors.  ``lens`` / ``cu`` are host lists; k_new ``[total, Hkv, D]`` with ``cu``, else ``[B, Hkv, Sq, D]``."""
+    paged = block_table is not None
+    Smax = block_table.shape[1] * k_cache.shape[2] if paged else k_cache.shape[2]
+    page_size, num_pages, total = k_cache.shape[2], k_cache.shape[0], k_new.shape[0]
+    for b, n in enumerate(lens):
+        len_b = min(max(n, 0), Smax)
+        if cu is not None:
+            s_b = min(max(cu[b], 0), total)
+            e_b = min(max(cu[b + 1], s_b), total)
+            sq = min(e_b - s_b, max_seqlen_q)
+            rows = [t[s_b:s_b + sq] for t in (k_new, v_new)]                 # [Sq_b, Hkv, D]
+        else:
+            sq = max_seqlen_q
+            rows = [t[b].transpose(0, 1) for t in (k_new, v_new)]
+        first = max(0, sq - len_b)                                            # rows in front of key 0 are dropped
+        if first >= sq:
+            continue
+        pos = torch.arange(len_b - sq + first, len_b)
+        rows = [r[first:sq] for r in rows]
+        if not paged:
+            for cache, r in zip((k_cache, v_cache), rows):
+                cache[b][:, pos] = r.transpose(0, 1)
+            continue
+        pg = block_table[b, pos // page_size].to(torch.int64)
+        ok = (pg >= 0) & (pg < num_pages)                                     # a page id outside the pool drops the write
+        for pool, r in zip((k_cache, v_cache), rows):
+            pool[pg[ok], :, (pos % page_size)[ok]] = r[ok]
+
+
+def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
+              cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None,
+              block_table: Optional[torch.Tensor] = None) -> None:
+    """Device-side KV-cache append (``pfa_kv_append``): place a step's new K / V rows into the cache the calls over a KV cache read --
+    the write side of ``fa3_decode`` / ``fa3_prefill_cache`` / ``fa3_prefill_varlen``, from device data alone.
+
+    k_cache / v_cache (and ``block_table``) are passed exactly as to ``fa3_prefill_varlen``: ``[B,Hkv,Smax,D]``-shaped views, or with
+    ``block_table`` (int32 ``[B, max_pages]``) pools ``[num_pages,Hkv,page_size,D]``-shaped, page_size a multiple of 64.  k_new / v_new:
+    with ``cu_seqlens_q`` (int32 ``[B + 1]``, as in ``fa3_prefill_varlen``) the packed ``[total, Hkv, D]`` rows and ``max_seqlen_q`` the
+    host bound on one sequence's rows; without it ``[B,Hkv,Sq,D]`` (any strides, head dim contiguous), ``max_seqlen_q`` being Sq.
+    bf16 / fp16, D a multiple of 8 up to 256.  cache_seqlens: int32 ``[B]``, required, the lengths AFTER the step -- the tensor the
+    attention call behind it takes.  With len_b = clamp(cache_seqlens[b], 0, Smax) and Sq_b the sequence's rows (clamped as
+    ``fa3_prefill_varlen`` clamps them), row i goes to logical key ``len_b - Sq_b + i``.  Rows in front of key 0 (len_b < Sq_b) are
+    dropped, and so is a row whose page id lies outside the pool: a write is never clamped into someone else's page.  Packed rows no
+    sequence covers are never read; nothing but the destination rows is written, lengths and table included, so a replay is
+    idempotent.  Two sequences given the same destination leave one of the two rows there (copy-on-write is the caller's business).
+
+    On device tensors: one launch of a HIP copy kernel whose grid depends on host shapes only -- no host synchronisation, no tensor
+    creation, capturable in ``torch.cuda.graph`` and valid while cu_seqlens_q, lengths, table and cache change between replays.  On CPU
+    tensors the same rule runs in plain torch (the executable specification; ``PagedKVCache``'s bookkeeping is tested through it)."""
+    ragged = cu_seqlens_q is not None
+    if k_new.dim() != (3 if ragged else 4) or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("k_new must be 3-D ([total,Hkv,D]) with cu_seqlens_q, else 4-D ([B,Hkv,Sq,D]); k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
+    if v_new.shape != k_new.shape:
+        raise ValueError(f"shape mismatch: k_new {tuple(k_new.shape)} v_new {tuple(v_new.shape)}")
+    if ragged:
+        if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
+            raise ValueError("cu_seqlens_q must be an int32 tensor")
+        if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
+            raise ValueError(f"cu_seqlens_q must be [B + 1], got {tuple(cu_seqlens_q.shape)}")
+        if not cu_seqlens_q.is_contiguous():
+            raise ValueError("cu_seqlens_q must be contiguous")
+        if max_seqlen_q is None:
+            raise ValueError("cu_seqlens_q needs max_seqlen_q, the host bound on a sequence's rows (it sizes the grid)")
+        B, (total, Hkv, D) = cu_seqlens_q.numel() - 1, k_new.shape
+    else:
+        B, Hkv, Sq, D = k_new.shape
+        if max_seqlen_q is not None and int(max_seqlen_q) != Sq:
+            raise ValueError(f"max_seqlen_q {max_seqlen_q}: without cu_seqlens_q every sequence brings k_new's {Sq} rows")
+        max_seqlen_q, total = Sq, B * Sq
+    max_seqlen_q = int(max_seqlen_q)
+    page_size = num_pages = 0
+    if block_table is None:
+        Smax = k_cache.shape[2]
+        if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != k_cache.shape:
+            raise ValueError(f"shape mismatch: k_new {tuple(k_new.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
+    else:
+        num_pages, page_size = k_cache.shape[0], k_cache.shape[2]
+        if k_cache.shape != (num_pages, Hkv, page_size, D) or v_cache.shape != k_cache.shape or num_pages < 1:
+            raise ValueError(f"shape mismatch: k_new {tuple(k_new.shape)} k pool {tuple(k_cache.shape)} v pool {tuple(v_cache.shape)}")
+        if page_size < 64 or page_size % 64:
+            raise ValueError(f"page size {page_size}: must be a multiple of 64 keys")
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+            raise ValueError("block_table must be an int32 tensor")
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be [B, max_pages] with B = {B}, got {tuple(block_table.shape)}")
+        if block_table.stride(1) != 1 and block_table.shape[1] != 1:
+            raise ValueError("block_table: the last dim must be contiguous")
+        Smax = block_table.shape[1] * page_size
+    if k_new.dtype not in (torch.bfloat16, torch.float16) or any(t.dtype != k_new.dtype for t in (v_new, k_cache, v_cache)):
+        raise ValueError("k_new, v_new, k_cache, v_cache must share dtype bf16 or fp16")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.shape != (B,):
+        raise ValueError("cache_seqlens must be a [B] tensor (the lengths after the step)")
+    if total < 1 or not 1 <= max_seqlen_q <= total:
+        raise ValueError(f"max_seqlen_q {max_seqlen_q}: must lie in 1 .. {total}, the rows k_new holds")
+    dev = k_new.device
+    if any(t.device != dev for t in (v_new, k_cache, v_cache, cache_seqlens) + ((cu_seqlens_q,) if ragged else ())
+           + ((block_table,) if block_table is not None else ())):
+        raise ValueError("pfa_kv_append needs all its tensors on one device")
+    if dev.type == "cpu":
+        _kv_append_model(k_new, v_new, k_cache, v_cache, cache_seqlens.tolist(), cu_seqlens_q.tolist() if ragged else None,
+                         max_seqlen_q, block_table)
+        return
+    if not k_new.is_cuda:
+        raise ValueError("pfa_kv_append needs device tensors (or CPU tensors for the torch model)")
+    if any(t.stride(-1) != 1 and D != 1 for t in (k_new, v_new)):
+        raise ValueError("last (head_dim) stride must be 1")
+    ks, vs = _bhsd_strides(k_cache), _bhsd_strides(v_cache)
+    a = _capi.make_kv_append_args(
+        k_new=k_new.data_ptr(), v_new=v_new.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(),
+        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
+        B=B, Hkv=Hkv, total_new=total, max_seqlen_q=max_seqlen_q, Smax=Smax, D=D, dtype=_DT[k_new.dtype],
+        device_id=dev.index if dev.index is not None else torch.cuda.current_device())
+    if ragged:
+        a.cu_seqlens_q = cu_seqlens_q.data_ptr()
+        a.kn_stride_s, a.kn_stride_h, a.vn_stride_s, a.vn_stride_h = k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1)
+    else:
+        (a.kn_stride_b, a.kn_stride_h, a.kn_stride_s), (a.vn_stride_b, a.vn_stride_h, a.vn_stride_s) = k_new.stride()[:3], v_new.stride()[:3]
+    if block_table is not None:
+        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
+        a.page_size, a.num_pages = page_size, num_pages
+    keep = []
+    _set_cache_seqlens(a, cache_seqlens, k_new, keep, B)
+    stream = torch.cuda.current_stream(dev)
+    st = _capi.load().pfa_kv_append(C.byref(a), C.c_void_p(stream.cuda_stream))
+    if st in (-1, -3, -4, -5, -6, -7, -10):
+        raise ValueError(f"pfa_kv_append: {_capi.status_string(st)}")
+    _capi.check_status(st)
+    for t in keep:   # tensors made here must outlive the enqueued kernel
+        t.record_stream(stream)
+
+
+def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, **ragged) -> None:
+    """The ``k_new=, v_new=`` form of the calls over a KV cache: ``kv_append`` enqueued in front of the attention launch, on the
+    same stream, with the same lengths, ``cu_seqlens_q`` and table."""
+    if k_new is None and v_new is None:
+        return
+    if k_new is None or v_new is None:
+        raise ValueError("k_new and v_new go together")
+    if cache_seqlens is None:
+        raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
+    kv_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, **ragged)
+
+
 def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
                out: Optional[torch.Tensor] = None,
-               block_table: Optional[torch.Tensor] = None, window: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
+               k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -576,8 +722,14 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     j <= len_b - Sq + i and j > len_b - Sq + i - W.  A key_mask combines with it (AND).  Only the windowed span is streamed, and it
     alone is split over workgroups.  With lo_b = max(0, len_b - Sq - W + 1), keys below lo_b rounded down to a multiple of 64 and
     table entries below ``lo_b // page_size`` are never read, so the pages behind the window can be given away
-    (``PagedKVCache.release_behind_window``); keys between that boundary and a row's own bound are read and masked.  ``None``: no window."""
+    (``PagedKVCache.release_behind_window``); keys between that boundary and a row's own bound are read and masked.  ``None``: no window.
+
+    ``k_new=, v_new=`` (``[B,Hkv,Sq,D]``; needs ``cache_seqlens``, the lengths after the step): ``kv_append`` of these rows is enqueued on the
+    same stream in front of the attention launch, with the same lengths and table -- flash-attn's ``flash_attn_with_kvcache(k=, v=)``.
+    ``None``: nothing is appended."""
     ext = _window_ext(window, causal)
+    if k_new is not None and cache_seqlens is None:
+        raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     B, H, Sq, _ = q.shape
     keep = []
@@ -605,6 +757,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
         keep.append(ws)
+    _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, max_seqlen_q=Sq)
     stream = torch.cuda.current_stream(q.device)
     st = lib.pfa_fa3_decode_ex(C.byref(a), ext_ref, C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
@@ -618,7 +771,8 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
 def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                       causal: bool = True, softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
                       return_lse: bool = False, out: Optional[torch.Tensor] = None,
-                      block_table: Optional[torch.Tensor] = None, window: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                      k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
@@ -636,7 +790,11 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     Sliding window: ``window=W`` (an integer >= 1, with ``causal=True``) as in ``fa3_decode``: row i sees key j iff j < len_b,
     j <= len_b - Sq + i and j > len_b - Sq + i - W.  A workgroup starts at the first 64-key tile its rows can see.  With
     lo_b = max(0, len_b - Sq - W + 1), keys below lo_b rounded down to a multiple of 64 and table entries below ``lo_b // page_size``
-    are never read; keys between that boundary and a row's own bound are read and masked.  ``None``: no window."""
+    are never read; keys between that boundary and a row's own bound are read and masked.  ``None``: no window.
+
+    ``k_new=, v_new=`` (``[B,Hkv,Sq,D]``; needs ``cache_seqlens``, the lengths after the step): ``kv_append`` of these rows is enqueued on the
+    same stream in front of the attention launch, with the same lengths and table -- flash-attn's ``flash_attn_with_kvcache(k=, v=)``.
+    ``None``: nothing is appended."""
     ext = _window_ext(window, causal)
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     keep = []
@@ -645,6 +803,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     if return_lse:
         lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
+    _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, max_seqlen_q=q.shape[2])
     stream = torch.cuda.current_stream(q.device)
     st = _capi.load().pfa_fa3_prefill_ex(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
@@ -658,7 +817,8 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
                        cache_seqlens: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                        out_dtype: Optional[torch.dtype] = None, return_lse: bool = False, out: Optional[torch.Tensor] = None,
-                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen_ex``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
     verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
@@ -678,7 +838,11 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     Sliding window: ``window=W`` (an integer >= 1, with ``causal=True``), per sequence as in ``fa3_prefill_cache``: row i of sequence b
     sees key j iff j < len_b, j <= len_b - Sq_b + i and j > len_b - Sq_b + i - W.  With lo_b = max(0, len_b - Sq_b - W + 1), keys below
     lo_b rounded down to a multiple of 64 and table entries below ``lo_b // page_size`` are never read; keys between that boundary and a
-    row's own bound are read and masked.  The bits are still those of per-sequence ``fa3_prefill_cache(window=W)`` calls.  ``None``: no window."""
+    row's own bound are read and masked.  The bits are still those of per-sequence ``fa3_prefill_cache(window=W)`` calls.  ``None``: no window.
+
+    ``k_new=, v_new=`` (packed ``[total_q,Hkv,D]``; needs ``cache_seqlens``, the lengths after the step): ``kv_append`` of these rows is enqueued on the
+    same stream in front of the attention launch, with the same lengths, ``cu_seqlens_q``, ``max_seqlen_q`` and table -- flash-attn's ``flash_attn_with_kvcache(k=, v=)``.
+    ``None``: nothing is appended."""
     ext = _window_ext(window, causal)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q must be 3-D ([total_q,H,D]) and k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
@@ -716,6 +880,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     if return_lse:
         lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
+    _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
     stream = torch.cuda.current_stream(q.device)
     st = _capi.load().pfa_fa3_prefill_varlen_ex(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     if st in (-1, -3, -4, -5, -6, -7, -10):
