@@ -21,20 +21,6 @@ PFA_FLAG_NO_XCD_MAP = 0x2
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, "libpfa_hip.so")
 
-EXPORTS = (
-    "pfa_abi_version", "pfa_status_string", "pfa_device_supported", "pfa_last_hip_error",
-    "pfa_fa3_workspace_bytes", "pfa_fa3_check", "pfa_fa3_fwd", "pfa_fa3_describe", "pfa_fa3_weights",
-    "pfa_fa3_bwd", "pfa_fa3_bwd_workspace_bytes", "pfa_fa3_bwd_mask_workspace_bytes", "pfa_fa3_prepare", "pfa_probe_mfma",
-    "pfa_fa3_decode_workspace_bytes", "pfa_fa3_decode_check", "pfa_fa3_decode", "pfa_fa3_decode_describe",
-    "pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_describe",
-    "pfa_fa3_prefill_varlen_check", "pfa_fa3_prefill_varlen", "pfa_fa3_prefill_varlen_describe",
-    "pfa_fa3_decode_workspace_bytes_ex", "pfa_fa3_decode_check_ex", "pfa_fa3_decode_ex", "pfa_fa3_decode_describe_ex",
-    "pfa_fa3_prefill_check_ex", "pfa_fa3_prefill_ex", "pfa_fa3_prefill_describe_ex",
-    "pfa_fa3_prefill_varlen_check_ex", "pfa_fa3_prefill_varlen_ex", "pfa_fa3_prefill_varlen_describe_ex",
-    "pfa_kv_append_check", "pfa_kv_append", "pfa_kv_append_describe",
-)
-
-
 class PfaFa3Args(C.Structure):
     """Mirror of ``struct pfa_fa3_args`` (include/pfa_hip.h)."""
     _fields_ = [
@@ -117,6 +103,57 @@ class PfaKvAppendArgs(C.Structure):
     )
 
 
+def _prototypes():
+    """Export name -> ``(restype, argtypes)``, one row per symbol ``include/pfa_hip.h`` declares (argtypes None: left untyped)."""
+    i, sz, vp, buf = C.c_int, C.c_size_t, C.c_void_p, [C.c_char_p, C.c_size_t]
+    fa3, bwd, dec, var, app, ext = (C.POINTER(t) for t in (PfaFa3Args, PfaFa3BwdArgs, PfaFa3DecodeArgs, PfaFa3PrefillVarlenArgs,
+                                                           PfaKvAppendArgs, PfaFa3CacheExt))
+    ns = [C.POINTER(C.c_int32)]
+    return {
+        "pfa_abi_version": (i, None),
+        "pfa_status_string": (C.c_char_p, [i]),
+        "pfa_device_supported": (i, [i]),
+        "pfa_last_hip_error": (i, None),
+        "pfa_fa3_workspace_bytes": (sz, [fa3]),
+        "pfa_fa3_check": (i, [fa3]),
+        "pfa_fa3_fwd": (i, [fa3, vp]),
+        "pfa_fa3_describe": (i, [fa3] + buf),
+        "pfa_fa3_weights": (i, [fa3, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp]),
+        "pfa_fa3_bwd": (i, [bwd, vp]),
+        "pfa_fa3_bwd_workspace_bytes": (sz, [bwd]),
+        "pfa_fa3_bwd_mask_workspace_bytes": (sz, [bwd]),
+        "pfa_fa3_prepare": (i, [i]),
+        "pfa_probe_mfma": (i, [vp, vp, i, i, vp, C.POINTER(C.c_double)]),
+        "pfa_fa3_decode_workspace_bytes": (sz, [dec]),
+        "pfa_fa3_decode_check": (i, [dec]),
+        "pfa_fa3_decode": (i, [dec, vp]),
+        "pfa_fa3_decode_describe": (i, [dec] + buf + ns),
+        "pfa_fa3_prefill_check": (i, [dec]),
+        "pfa_fa3_prefill": (i, [dec, vp]),
+        "pfa_fa3_prefill_describe": (i, [dec] + buf),
+        "pfa_fa3_prefill_varlen_check": (i, [var]),
+        "pfa_fa3_prefill_varlen": (i, [var, vp]),
+        "pfa_fa3_prefill_varlen_describe": (i, [var] + buf),
+        "pfa_fa3_decode_workspace_bytes_ex": (sz, [dec, ext]),
+        "pfa_fa3_decode_check_ex": (i, [dec, ext]),
+        "pfa_fa3_decode_ex": (i, [dec, ext, vp]),
+        "pfa_fa3_decode_describe_ex": (i, [dec, ext] + buf + ns),
+        "pfa_fa3_prefill_check_ex": (i, [dec, ext]),
+        "pfa_fa3_prefill_ex": (i, [dec, ext, vp]),
+        "pfa_fa3_prefill_describe_ex": (i, [dec, ext] + buf),
+        "pfa_fa3_prefill_varlen_check_ex": (i, [var, ext]),
+        "pfa_fa3_prefill_varlen_ex": (i, [var, ext, vp]),
+        "pfa_fa3_prefill_varlen_describe_ex": (i, [var, ext] + buf),
+        "pfa_kv_append_check": (i, [app]),
+        "pfa_kv_append": (i, [app, vp]),
+        "pfa_kv_append_describe": (i, [app] + buf),
+    }
+
+
+_PROTOTYPES = _prototypes()
+EXPORTS = tuple(_PROTOTYPES)
+
+
 class PfaError(RuntimeError):
     """A non-zero ``pfa_status`` from the native library."""
 
@@ -143,80 +180,9 @@ def load(path: Optional[str] = None):
                 f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C photonic_flash_attention_amd/csrc` (there is no CPU fallback)")
         lib = C.CDLL(p)
-        lib.pfa_abi_version.restype = C.c_int
-        lib.pfa_status_string.restype = C.c_char_p
-        lib.pfa_status_string.argtypes = [C.c_int]
-        lib.pfa_device_supported.restype = C.c_int
-        lib.pfa_device_supported.argtypes = [C.c_int]
-        lib.pfa_last_hip_error.restype = C.c_int
-        lib.pfa_fa3_workspace_bytes.restype = C.c_size_t
-        lib.pfa_fa3_workspace_bytes.argtypes = [C.POINTER(PfaFa3Args)]
-        lib.pfa_fa3_check.restype = C.c_int
-        lib.pfa_fa3_check.argtypes = [C.POINTER(PfaFa3Args)]
-        lib.pfa_fa3_fwd.restype = C.c_int
-        lib.pfa_fa3_fwd.argtypes = [C.POINTER(PfaFa3Args), C.c_void_p]
-        lib.pfa_fa3_weights.restype = C.c_int
-        lib.pfa_fa3_weights.argtypes = [C.POINTER(PfaFa3Args), C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
-                                        C.c_void_p]
-        lib.pfa_fa3_bwd.restype = C.c_int
-        lib.pfa_fa3_bwd.argtypes = [C.POINTER(PfaFa3BwdArgs), C.c_void_p]
-        lib.pfa_fa3_bwd_workspace_bytes.restype = C.c_size_t
-        lib.pfa_fa3_bwd_workspace_bytes.argtypes = [C.POINTER(PfaFa3BwdArgs)]
-        lib.pfa_fa3_bwd_mask_workspace_bytes.restype = C.c_size_t
-        lib.pfa_fa3_bwd_mask_workspace_bytes.argtypes = [C.POINTER(PfaFa3BwdArgs)]
-        lib.pfa_fa3_describe.restype = C.c_int
-        lib.pfa_fa3_describe.argtypes = [C.POINTER(PfaFa3Args), C.c_char_p, C.c_size_t]
-        lib.pfa_fa3_prepare.restype = C.c_int
-        lib.pfa_fa3_prepare.argtypes = [C.c_int]
-        lib.pfa_probe_mfma.restype = C.c_int
-        lib.pfa_probe_mfma.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
-        lib.pfa_fa3_decode_workspace_bytes.restype = C.c_size_t
-        lib.pfa_fa3_decode_workspace_bytes.argtypes = [C.POINTER(PfaFa3DecodeArgs)]
-        lib.pfa_fa3_decode_check.restype = C.c_int
-        lib.pfa_fa3_decode_check.argtypes = [C.POINTER(PfaFa3DecodeArgs)]
-        lib.pfa_fa3_decode.restype = C.c_int
-        lib.pfa_fa3_decode.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_void_p]
-        lib.pfa_fa3_decode_describe.restype = C.c_int
-        lib.pfa_fa3_decode_describe.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
-        lib.pfa_fa3_prefill_check.restype = C.c_int
-        lib.pfa_fa3_prefill_check.argtypes = [C.POINTER(PfaFa3DecodeArgs)]
-        lib.pfa_fa3_prefill.restype = C.c_int
-        lib.pfa_fa3_prefill.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_void_p]
-        lib.pfa_fa3_prefill_describe.restype = C.c_int
-        lib.pfa_fa3_prefill_describe.argtypes = [C.POINTER(PfaFa3DecodeArgs), C.c_char_p, C.c_size_t]
-        lib.pfa_fa3_prefill_varlen_check.restype = C.c_int
-        lib.pfa_fa3_prefill_varlen_check.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs)]
-        lib.pfa_fa3_prefill_varlen.restype = C.c_int
-        lib.pfa_fa3_prefill_varlen.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), C.c_void_p]
-        lib.pfa_fa3_prefill_varlen_describe.restype = C.c_int
-        lib.pfa_fa3_prefill_varlen_describe.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), C.c_char_p, C.c_size_t]
-        ext = C.POINTER(PfaFa3CacheExt)
-        lib.pfa_fa3_decode_workspace_bytes_ex.restype = C.c_size_t
-        lib.pfa_fa3_decode_workspace_bytes_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext]
-        lib.pfa_fa3_decode_check_ex.restype = C.c_int
-        lib.pfa_fa3_decode_check_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext]
-        lib.pfa_fa3_decode_ex.restype = C.c_int
-        lib.pfa_fa3_decode_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_void_p]
-        lib.pfa_fa3_decode_describe_ex.restype = C.c_int
-        lib.pfa_fa3_decode_describe_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
-        lib.pfa_fa3_prefill_check_ex.restype = C.c_int
-        lib.pfa_fa3_prefill_check_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext]
-        lib.pfa_fa3_prefill_ex.restype = C.c_int
-        lib.pfa_fa3_prefill_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_void_p]
-        lib.pfa_fa3_prefill_describe_ex.restype = C.c_int
-        lib.pfa_fa3_prefill_describe_ex.argtypes = [C.POINTER(PfaFa3DecodeArgs), ext, C.c_char_p, C.c_size_t]
-        lib.pfa_fa3_prefill_varlen_check_ex.restype = C.c_int
-        lib.pfa_fa3_prefill_varlen_check_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext]
-        lib.pfa_fa3_prefill_varlen_ex.restype = C.c_int
-        lib.pfa_fa3_prefill_varlen_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext, C.c_void_p]
-        lib.pfa_fa3_prefill_varlen_describe_ex.restype = C.c_int
-        lib.pfa_fa3_prefill_varlen_describe_ex.argtypes = [C.POINTER(PfaFa3PrefillVarlenArgs), ext, C.c_char_p, C.c_size_t]
-        lib.pfa_kv_append_check.restype = C.c_int
-        lib.pfa_kv_append_check.argtypes = [C.POINTER(PfaKvAppendArgs)]
-        lib.pfa_kv_append.restype = C.c_int
-        lib.pfa_kv_append.argtypes = [C.POINTER(PfaKvAppendArgs), C.c_void_p]
-        lib.pfa_kv_append_describe.restype = C.c_int
-        lib.pfa_kv_append_describe.argtypes = [C.POINTER(PfaKvAppendArgs), C.c_char_p, C.c_size_t]
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
@@ -236,119 +202,82 @@ def check_status(status: int) -> None:
         raise PfaError(status, status_string(status) + extra)
 
 
-def make_args(**kw) -> PfaFa3Args:
-    a = PfaFa3Args()
-    a.size = C.sizeof(PfaFa3Args)
+def _make(cls, kw):
+    """A zeroed argument block of type ``cls`` with its ``size`` field set, then the given fields."""
+    a = cls()
+    a.size = C.sizeof(cls)
     for k, v in kw.items():
         setattr(a, k, v)
     return a
+
+
+def _describe(export: str, args, *ext, nsplit: bool = False):
+    """One ``*_describe`` export: -> ``(kernel name, workgroups)``, with ``nsplit`` also the call's int32 out-parameter.
+    ``ext``: nothing, or the ``_ex`` form's extension block (None: the NULL extension)."""
+    buf = C.create_string_buffer(128)
+    ns = C.c_int32(0)
+    refs = [None if e is None else C.byref(e) for e in ext] + [buf, 128] + ([C.byref(ns)] if nsplit else [])
+    n = getattr(load(), export)(C.byref(args), *refs)
+    if n < 0:
+        check_status(n)
+    return (buf.value.decode(), n, ns.value) if nsplit else (buf.value.decode(), n)
+
+
+def make_args(**kw) -> PfaFa3Args:
+    return _make(PfaFa3Args, kw)
 
 
 def describe(args: PfaFa3Args):
     """-> (kernel variant name, number of workgroups) the library would launch."""
-    buf = C.create_string_buffer(128)
-    n = load().pfa_fa3_describe(C.byref(args), buf, 128)
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n
+    return _describe("pfa_fa3_describe", args)
 
 
 def make_decode_args(**kw) -> PfaFa3DecodeArgs:
-    a = PfaFa3DecodeArgs()
-    a.size = C.sizeof(PfaFa3DecodeArgs)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
+    return _make(PfaFa3DecodeArgs, kw)
 
 
 def describe_decode(args: PfaFa3DecodeArgs):
     """-> (kernel name, workgroups of the main launch, number of key splits) of ``pfa_fa3_decode``."""
-    buf = C.create_string_buffer(128)
-    ns = C.c_int32(0)
-    n = load().pfa_fa3_decode_describe(C.byref(args), buf, 128, C.byref(ns))
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n, ns.value
+    return _describe("pfa_fa3_decode_describe", args, nsplit=True)
 
 
 def describe_prefill(args: PfaFa3DecodeArgs):
     """-> (kernel name, workgroups) of ``pfa_fa3_prefill`` (the forward over a KV cache takes the decode's argument block)."""
-    buf = C.create_string_buffer(128)
-    n = load().pfa_fa3_prefill_describe(C.byref(args), buf, 128)
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n
+    return _describe("pfa_fa3_prefill_describe", args)
 
 
 def make_prefill_varlen_args(**kw) -> PfaFa3PrefillVarlenArgs:
-    a = PfaFa3PrefillVarlenArgs()
-    a.size = C.sizeof(PfaFa3PrefillVarlenArgs)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
+    return _make(PfaFa3PrefillVarlenArgs, kw)
 
 
 def describe_prefill_varlen(args: PfaFa3PrefillVarlenArgs):
     """-> (kernel name, workgroups) of ``pfa_fa3_prefill_varlen``: ``B * H * ceil(max_seqlen_q / 256)``, from host shapes only."""
-    buf = C.create_string_buffer(128)
-    n = load().pfa_fa3_prefill_varlen_describe(C.byref(args), buf, 128)
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n
+    return _describe("pfa_fa3_prefill_varlen_describe", args)
 
 
 def make_cache_ext(**kw) -> PfaFa3CacheExt:
-    e = PfaFa3CacheExt()
-    e.size = C.sizeof(PfaFa3CacheExt)
-    for k, v in kw.items():
-        setattr(e, k, v)
-    return e
-
-
-def _ext_ref(ext: Optional[PfaFa3CacheExt]):
-    return None if ext is None else C.byref(ext)
+    return _make(PfaFa3CacheExt, kw)
 
 
 def describe_decode_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
     """``describe_decode`` of ``pfa_fa3_decode_ex`` (``ext`` None: the NULL extension); "_win" marks a windowed kernel."""
-    buf = C.create_string_buffer(128)
-    ns = C.c_int32(0)
-    n = load().pfa_fa3_decode_describe_ex(C.byref(args), _ext_ref(ext), buf, 128, C.byref(ns))
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n, ns.value
+    return _describe("pfa_fa3_decode_describe_ex", args, ext, nsplit=True)
 
 
 def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
     """``describe_prefill`` of ``pfa_fa3_prefill_ex``."""
-    buf = C.create_string_buffer(128)
-    n = load().pfa_fa3_prefill_describe_ex(C.byref(args), _ext_ref(ext), buf, 128)
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n
+    return _describe("pfa_fa3_prefill_describe_ex", args, ext)
 
 
 def describe_prefill_varlen_ex(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaFa3CacheExt]):
     """``describe_prefill_varlen`` of ``pfa_fa3_prefill_varlen_ex``."""
-    buf = C.create_string_buffer(128)
-    n = load().pfa_fa3_prefill_varlen_describe_ex(C.byref(args), _ext_ref(ext), buf, 128)
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n
+    return _describe("pfa_fa3_prefill_varlen_describe_ex", args, ext)
 
 
 def make_kv_append_args(**kw) -> PfaKvAppendArgs:
-    a = PfaKvAppendArgs()
-    a.size = C.sizeof(PfaKvAppendArgs)
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a
+    return _make(PfaKvAppendArgs, kw)
 
 
 def describe_kv_append(args: PfaKvAppendArgs):
     """-> (kernel name, workgroups) of ``pfa_kv_append``: ``B * ceil(max_seqlen_q * Hkv * (D / 8) / 256)``, from host shapes only."""
-    buf = C.create_string_buffer(128)
-    n = load().pfa_kv_append_describe(C.byref(args), buf, 128)
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n
+    return _describe("pfa_kv_append_describe", args)

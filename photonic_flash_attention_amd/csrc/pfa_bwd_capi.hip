@@ -179,7 +179,7 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream) {
     p.mask_dw = (p.mask && a->mask_stride_k == 1 && a->Sk % 4 == 0 && a->mask_stride_b % 4 == 0 && a->mask_stride_h % 4 == 0 &&
                  a->mask_stride_q % 4 == 0 && ((uintptr_t)a->mask & 3) == 0) ? 1 : 0;
     p.scale = a->softmax_scale;
-    p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+    p.scale_log2 = a->softmax_scale * pfa::LOG2E;
     // element mask + scratch: words, transposed words and tile ranges (launched below, in front of the two kernels)
     const BwdMaskWs mw = p.mask ? bwd_mask_ws(a) : BwdMaskWs();
     const bool use_words = mw.bytes() > 0 && a->mask_workspace && a->mask_workspace_bytes >= mw.bytes();

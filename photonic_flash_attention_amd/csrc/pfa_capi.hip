@@ -368,7 +368,7 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
     p.nqblk = (a->Sq + v.block_m - 1) / v.block_m;
     p.kv_group = a->kv_group > 1 ? a->kv_group : 1;
     p.xcd_group = v.xcd_group;
-    p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+    p.scale_log2 = a->softmax_scale * pfa::LOG2E;
     p.magic_h = (uint32_t)((1ull << 32) / (uint64_t)a->H) + 1u;
     p.magic_g = (uint32_t)((1ull << 32) / (uint64_t)p.kv_group) + 1u;
 
@@ -413,7 +413,7 @@ int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_s
     p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
     p.nqblk = (a->Sq + 127) / 128;
     p.kv_group = a->kv_group > 1 ? a->kv_group : 1;
-    p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+    p.scale_log2 = a->softmax_scale * pfa::LOG2E;
     const MaskBits mb = mask_bits(a);          // as in pfa_fa3_fwd: the mask as words when the caller gave workspace
     const bool use_mbits = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
     p.mbits = use_mbits ? (const unsigned long long*)a->workspace : nullptr;

@@ -70,9 +70,8 @@ const void* main_fn(bool out32, bool paged) {
     return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, false, WINDOW> : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, false, WINDOW>;
 }
 template <bool WINDOW>
-const void* main_fn(bool bf, int D, bool out32, bool paged) {
-    return bf ? (D == 128 ? main_fn<__bf16, 128, WINDOW>(out32, paged) : main_fn<__bf16, 64, WINDOW>(out32, paged))
-              : (D == 128 ? main_fn<_Float16, 128, WINDOW>(out32, paged) : main_fn<_Float16, 64, WINDOW>(out32, paged));
+const void* main_fn(int dtype, int D, bool out32, bool paged) {
+    return pfa::dispatch_elem_dim(dtype, D, [&](auto t) { return main_fn<typename decltype(t)::type, decltype(t)::D, WINDOW>(out32, paged); });
 }
 template <typename T, int D>
 const void* combine_fn(bool out32) {
@@ -84,9 +83,7 @@ const void* combine_fn(bool out32) {
 extern "C" {
 
 size_t pfa_fa3_decode_workspace_bytes_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext) {
-    if (!a || a->size != sizeof(pfa_fa3_decode_args) || a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->H % a->Hkv != 0 || a->Sq < 1 ||
-        a->Smax <= 0 || (a->D != 64 && a->D != 128))
-        return 0;
+    if (!a || a->size != sizeof(pfa_fa3_decode_args) || pfa::check_cache_shape(a) != PFA_OK) return 0;
     int window;
     if (pfa::check_cache_ext(ext, a->causal, a->Smax, &window) != PFA_OK) return 0;
     return plan(a, window).ws_bytes;
@@ -116,25 +113,17 @@ int pfa_fa3_decode_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext
     if (st != PFA_OK) return st;
     const Plan pl = plan(a, window);
     pfa::dec::DecodeWinParams p;    // the window-less kernels take its DecodeParams base, unchanged
-    p.q = a->q; p.k = a->k_cache; p.v = a->v_cache; p.o = a->o;
-    p.lse = a->lse; p.seqlens = a->cache_seqlens; p.key_mask = a->key_mask;
-    p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
-    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
-    p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
-    p.o_sb = a->o_stride_b; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
-    p.km_sb = a->key_mask_stride_b;
+    pfa::fill_attention_params(p, a);
+    p.key_mask = a->key_mask; p.km_sb = a->key_mask_stride_b;
     p.part_o = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
     p.part_ml = pl.nsplit > 1 ? (float*)((char*)a->workspace + (size_t)pl.nsplit * a->B * a->H * a->Sq * a->D * sizeof(float)) : nullptr;
-    p.B = a->B; p.H = a->H; p.Hkv = a->Hkv; p.G = pl.G; p.Sq = a->Sq; p.Smax = a->Smax; p.nrb = pl.nrb; p.nsplit = pl.nsplit;
+    p.Hkv = a->Hkv; p.G = pl.G; p.nrb = pl.nrb; p.nsplit = pl.nsplit;
     p.causal = a->causal != 0;
-    p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
-    p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
     p.window = window;
 
-    const bool bf = a->dtype_in == PFA_DTYPE_BF16, out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr;
-    const void* fn = window ? main_fn<true>(bf, a->D, out32, paged) : main_fn<false>(bf, a->D, out32, paged);
-    const void* cfn = bf ? (a->D == 128 ? combine_fn<__bf16, 128>(out32) : combine_fn<__bf16, 64>(out32))
-                         : (a->D == 128 ? combine_fn<_Float16, 128>(out32) : combine_fn<_Float16, 64>(out32));
+    const bool out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr;
+    const void* fn = window ? main_fn<true>(a->dtype_in, a->D, out32, paged) : main_fn<false>(a->dtype_in, a->D, out32, paged);
+    const void* cfn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) { return combine_fn<typename decltype(t)::type, decltype(t)::D>(out32); });
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
     void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: the base, or all of it

@@ -4,6 +4,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "pfa_hip.h"
 
 namespace pfa {
@@ -52,7 +54,32 @@ inline void fill_mask(Params& p, const pfa_fa3_args* a) {
     }
 }
 
+constexpr float LOG2E = 1.4426950408889634f;   // exp(x) = exp2(x * LOG2E): softmax_scale * LOG2E is every kernel's scale_log2
+
+// The pointer and stride rules of the 16-bit tensors: 16-byte data pointers, 4-byte int32 / fp32 arrays (NULL passes both), element
+// strides that keep every row of 8 (fp32 output: of 4) elements aligned.
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool multiples_of(int m, std::initializer_list<int64_t> strides) {
+    for (int64_t s : strides)
+        if (s % m != 0) return false;
+    return true;
+}
+// cache rows run forward: k_stride_s / v_stride_s >= 0, for the calls that read the cache and the one that writes it
+template <typename Args>
+inline bool kv_rows_forward(const Args* a) { return a->k_stride_s >= 0 && a->v_stride_s >= 0; }
+
+// Calls f with a tag of the 16-bit element type and the head dim (validated before: bf16 / fp16, D 64 / 128): the one dtype x D ladder.
+template <typename T, int HEAD_DIM>
+struct ElemDim {
+    using type = T;
+    static constexpr int D = HEAD_DIM;
+};
+template <typename F>
+inline auto dispatch_elem_dim(int dtype, int D, F&& f) {
+    return dtype == PFA_DTYPE_BF16 ? (D == 128 ? f(ElemDim<__bf16, 128>{}) : f(ElemDim<__bf16, 64>{}))
+                                   : (D == 128 ? f(ElemDim<_Float16, 128>{}) : f(ElemDim<_Float16, 64>{}));
+}
 
 // The paging fields every call over a KV cache carries (include/pfa_hip.h, pfa_fa3_decode_args): all set, or all zero.
 inline int check_paging(const int32_t* block_table, int64_t block_table_stride_b, int32_t page_size, int32_t num_pages, int32_t Smax) {
@@ -60,40 +87,78 @@ inline int check_paging(const int32_t* block_table, int64_t block_table_stride_b
         // Smax is the logical capacity max_pages * page_size; a 64-key tile must lie inside one page
         if (page_size <= 0 || page_size % 64 != 0 || num_pages <= 0) return PFA_ERR_SHAPE;
         if (Smax % page_size != 0 || block_table_stride_b < Smax / page_size) return PFA_ERR_SHAPE;
-        if (reinterpret_cast<uintptr_t>(block_table) & 3u) return PFA_ERR_ALIGN;
+        if (!aligned4(block_table)) return PFA_ERR_ALIGN;
     } else if (page_size != 0 || num_pages != 0 || block_table_stride_b != 0) {
         return PFA_ERR_FLAGS;
     }
     return PFA_OK;
 }
 
-// The field rules pfa_fa3_decode and pfa_fa3_prefill share (include/pfa_hip.h, pfa_fa3_decode_args), in the order their errors are
-// reported: everything but the limits that depend on the kernel (key mask, grid, workspace).  max_sq: the most query rows the caller takes.
-inline int check_cache_args(const pfa_fa3_decode_args* a, int max_sq) {
+// What the two argument blocks of the attention calls over a cache name differently: the query rows of one sequence and the q / o
+// batch strides.  The packed tensors of the ragged call have no batch stride (0 passes every stride rule) and max_seqlen_q stands
+// where Sq does.  Every other field the templates below touch has one name in both blocks.
+struct QueryRows {
+    int32_t Sq;
+    int64_t q_sb, o_sb;
+};
+inline QueryRows query_rows(const pfa_fa3_decode_args* a) { return {a->Sq, a->q_stride_b, a->o_stride_b}; }
+inline QueryRows query_rows(const pfa_fa3_prefill_varlen_args* a) { return {a->max_seqlen_q, 0, 0}; }
+
+// The shape rules a plan can be made from (pfa_fa3_decode_workspace_bytes stops here: it takes no pointers and no strides).
+template <typename Args>
+inline int check_cache_shape(const Args* a) {
+    if (a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->Smax <= 0 || query_rows(a).Sq < 1 || a->H % a->Hkv != 0) return PFA_ERR_SHAPE;
+    if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
+    return PFA_OK;
+}
+
+// The field rules pfa_fa3_decode, pfa_fa3_prefill and pfa_fa3_prefill_varlen share (include/pfa_hip.h, pfa_fa3_decode_args), in the
+// order their errors are reported: everything but the limits that depend on the kernel (key mask, cu_seqlens_q, grid, workspace).
+// max_sq: the most query rows the caller takes.
+template <typename Args>
+inline int check_cache_args(const Args* a, int max_sq) {
     if (!a) return PFA_ERR_NULL;
-    if (a->size != sizeof(pfa_fa3_decode_args)) return PFA_ERR_STRUCT_SIZE;
+    if (a->size != sizeof(Args)) return PFA_ERR_STRUCT_SIZE;
     if (a->flags != 0 || a->reserved0 != 0) return PFA_ERR_FLAGS;
     if (!a->q || !a->k_cache || !a->v_cache || !a->o) return PFA_ERR_NULL;
-    if (a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->Smax <= 0 || a->Sq < 1 || a->Sq > max_sq) return PFA_ERR_SHAPE;
-    if (a->H % a->Hkv != 0) return PFA_ERR_SHAPE;
-    if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
+    const QueryRows g = query_rows(a);
+    if (g.Sq > max_sq) return PFA_ERR_SHAPE;
+    const int st = check_cache_shape(a);
+    if (st != PFA_OK) return st;
     if (a->dtype_in != PFA_DTYPE_BF16 && a->dtype_in != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
     if (a->dtype_out != a->dtype_in && a->dtype_out != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
     if (!(a->softmax_scale > 0.f) || !isfinite(a->softmax_scale)) return PFA_ERR_SHAPE;
-    const int64_t st8[] = {a->q_stride_b, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s,
-                           a->v_stride_b, a->v_stride_h, a->v_stride_s};
-    for (int64_t s : st8)
-        if (s % 8 != 0) return PFA_ERR_STRIDE;
-    const int64_t st4[] = {a->o_stride_b, a->o_stride_h, a->o_stride_s};
-    for (int64_t s : st4)
-        if (s % 4 != 0) return PFA_ERR_STRIDE;
+    if (!multiples_of(8, {g.q_sb, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s, a->v_stride_b, a->v_stride_h,
+                          a->v_stride_s}))
+        return PFA_ERR_STRIDE;
+    if (!multiples_of(4, {g.o_sb, a->o_stride_h, a->o_stride_s})) return PFA_ERR_STRIDE;
     if (!aligned16(a->q) || !aligned16(a->k_cache) || !aligned16(a->v_cache) || !aligned16(a->o)) return PFA_ERR_ALIGN;
-    if (a->lse && (reinterpret_cast<uintptr_t>(a->lse) & 3u)) return PFA_ERR_ALIGN;
-    if (a->cache_seqlens && (reinterpret_cast<uintptr_t>(a->cache_seqlens) & 3u)) return PFA_ERR_ALIGN;
+    if (!aligned4(a->lse) || !aligned4(a->cache_seqlens)) return PFA_ERR_ALIGN;
     // a tile's K / V rows are addressed by 32-bit offsets from a per-tile buffer descriptor
-    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_s * 2 * 64 + 256 > 0x7fffffffLL || a->v_stride_s * 2 * 64 + 256 > 0x7fffffffLL)
+    if (!kv_rows_forward(a) || a->k_stride_s * 2 * 64 + 256 > 0x7fffffffLL || a->v_stride_s * 2 * 64 + 256 > 0x7fffffffLL)
         return PFA_ERR_STRIDE;
     return check_paging(a->block_table, a->block_table_stride_b, a->page_size, a->num_pages, a->Smax);
+}
+
+// What every kernel parameter block over a cache carries (DecodeParams, Prefill*Params, KvAppendParams name these members alike):
+// the cache strides, the lengths and the paging fields.
+template <typename Params, typename Args>
+inline void fill_cache_params(Params& p, const Args* a) {
+    p.seqlens = a->cache_seqlens; p.Smax = a->Smax;
+    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
+    p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
+    p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
+}
+// ... and on top of them what the attention kernels' blocks (DecodeParams, Prefill*Params) share: the tensors, q / o strides, scale.
+template <typename Params, typename Args>
+inline void fill_attention_params(Params& p, const Args* a) {
+    fill_cache_params(p, a);
+    const QueryRows g = query_rows(a);
+    p.q = a->q; p.k = a->k_cache; p.v = a->v_cache; p.o = a->o; p.lse = a->lse;
+    p.q_sb = g.q_sb; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
+    p.o_sb = g.o_sb; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
+    p.B = a->B; p.H = a->H; p.Sq = g.Sq;
+    p.scale_log2 = a->softmax_scale * LOG2E;
 }
 
 // The extension block of the *_ex calls over a KV cache (include/pfa_hip.h, pfa_fa3_cache_ext), checked after the argument block's own

@@ -26,17 +26,16 @@ int check(const pfa_kv_append_args* a) {
     if (a->B <= 0 || a->Hkv <= 0 || a->Smax <= 0 || a->total_new < 1 || a->max_seqlen_q < 1) return PFA_ERR_SHAPE;
     if (a->D < 8 || a->D % 8 != 0 || a->D > 256) return PFA_ERR_HEAD_DIM;
     if (a->dtype != PFA_DTYPE_BF16 && a->dtype != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
-    const int64_t st8[] = {a->kn_stride_b, a->kn_stride_s, a->kn_stride_h, a->vn_stride_b, a->vn_stride_s, a->vn_stride_h,
-                           a->k_stride_b,  a->k_stride_h,  a->k_stride_s,  a->v_stride_b,  a->v_stride_h,  a->v_stride_s};
-    for (int64_t s : st8)
-        if (s % 8 != 0) return PFA_ERR_STRIDE;
-    if (a->k_stride_s < 0 || a->v_stride_s < 0) return PFA_ERR_STRIDE;      // as the calls that read the cache
+    if (!pfa::multiples_of(8, {a->kn_stride_b, a->kn_stride_s, a->kn_stride_h, a->vn_stride_b, a->vn_stride_s, a->vn_stride_h,
+                               a->k_stride_b, a->k_stride_h, a->k_stride_s, a->v_stride_b, a->v_stride_h, a->v_stride_s}))
+        return PFA_ERR_STRIDE;
+    if (!pfa::kv_rows_forward(a)) return PFA_ERR_STRIDE;      // as the calls that read the cache
     if (!pfa::aligned16(a->k_new) || !pfa::aligned16(a->v_new) || !pfa::aligned16(a->k_cache) || !pfa::aligned16(a->v_cache)) return PFA_ERR_ALIGN;
-    if (reinterpret_cast<uintptr_t>(a->cache_seqlens) & 3u) return PFA_ERR_ALIGN;
+    if (!pfa::aligned4(a->cache_seqlens)) return PFA_ERR_ALIGN;
     const int st = pfa::check_paging(a->block_table, a->block_table_stride_b, a->page_size, a->num_pages, a->Smax);
     if (st != PFA_OK) return st;
     if (a->cu_seqlens_q) {
-        if (reinterpret_cast<uintptr_t>(a->cu_seqlens_q) & 3u) return PFA_ERR_ALIGN;
+        if (!pfa::aligned4(a->cu_seqlens_q)) return PFA_ERR_ALIGN;
         if (a->kn_stride_b != 0 || a->vn_stride_b != 0) return PFA_ERR_FLAGS;      // packed rows have no batch stride
         if (a->max_seqlen_q > a->total_new) return PFA_ERR_SHAPE;
     } else if ((int64_t)a->B * a->max_seqlen_q > a->total_new) {
@@ -67,16 +66,13 @@ int pfa_kv_append(const pfa_kv_append_args* a, void* stream) {
     if (st != PFA_OK) return st;
     pfa::KvAppendParams p;
     p.k_new = a->k_new; p.v_new = a->v_new; p.k_cache = a->k_cache; p.v_cache = a->v_cache;
-    p.cu_seqlens_q = a->cu_seqlens_q; p.seqlens = a->cache_seqlens; p.block_table = a->block_table;
+    p.cu_seqlens_q = a->cu_seqlens_q;
     p.kn_sb = a->kn_stride_b; p.kn_ss = a->kn_stride_s; p.kn_sh = a->kn_stride_h;
     p.vn_sb = a->vn_stride_b; p.vn_ss = a->vn_stride_s; p.vn_sh = a->vn_stride_h;
-    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
-    p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
-    p.bt_sb = a->block_table_stride_b;
+    pfa::fill_cache_params(p, a);
     p.nchunk = (int32_t)(workgroups(a) / a->B);
-    p.Sq = a->max_seqlen_q; p.Smax = a->Smax; p.total_new = a->total_new;
+    p.Sq = a->max_seqlen_q; p.total_new = a->total_new;
     p.dchunks = a->D / 8; p.units = a->Hkv * (a->D / 8);
-    p.page_size = a->page_size; p.num_pages = a->num_pages;
 
     const bool varlen = a->cu_seqlens_q != nullptr, paged = a->block_table != nullptr;
     const void* fn = varlen ? (paged ? (const void*)&pfa::kv_append_kernel<true, true> : (const void*)&pfa::kv_append_kernel<true, false>)

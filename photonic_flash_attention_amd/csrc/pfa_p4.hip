@@ -199,7 +199,7 @@ int p4_launch(const pfa_fa3_args* a, void* stream, int* hip_err) {
     p.magic_NU = magic(p.NU); p.magic_H = magic(p.H);
     p.kv_group = a->kv_group > 1 ? (uint32_t)a->kv_group : 1u;
     p.magic_G = magic(p.kv_group);
-    p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+    p.scale_log2 = a->softmax_scale * pfa::LOG2E;
     p.thr = 8.0f / p.scale_log2;
     const int BH = a->B * a->H;
     const int grid = grid_for(m, a);

@@ -1,0 +1,78 @@
+// pfa_prefill_host.h -- what pfa_fa3_prefill and pfa_fa3_prefill_varlen share behind their argument blocks (internal): the grid, the
+// kernel table, the parameter fill and the launch of fa3_prefill_kernel.  VARLEN picks the ragged instantiations; each of the two
+// translation units instantiates one side only, so they still compile side by side.
+#pragma once
+#include <limits.h>
+#include <stdio.h>
+
+#include "fa3_prefill_kernel.h"
+#include "pfa_host.h"
+
+namespace pfa {
+namespace prefill {
+
+// workgroups: from host shapes only (Sq or max_seqlen_q, never device data), so a captured graph stays valid while cache_seqlens,
+// cu_seqlens_q, the block table and the cache change
+template <typename Args>
+int64_t workgroups(const Args* a) {
+    return (int64_t)a->B * a->H * (((int64_t)query_rows(a).Sq + FWD_BLOCK_M - 1) / FWD_BLOCK_M);
+}
+
+// The tail of both calls' checks, behind check_cache_args and the call's own rules: the grid, then the extension block.
+// -> PFA_OK and the kernel's window (0: none) in *window
+template <typename Args>
+int check_grid_and_ext(const Args* a, const pfa_fa3_cache_ext* ext, int* window) {
+    if (workgroups(a) > 0x7fffffffLL) return PFA_ERR_SHAPE;
+    return check_cache_ext(ext, a->causal, a->Smax, window);
+}
+
+// fp32 output: P carried as a 16-bit hi + lo pair (SPLITP), as the forward does for its <= 1e-3 mode
+template <typename T, int D, bool VARLEN, bool CAUSAL, bool PAGED, bool WINDOW = false>
+const void* fn_out(bool out32) {
+    return out32 ? (const void*)&fa3_prefill_kernel<T, D, CAUSAL, true, PAGED, float, VARLEN, WINDOW>
+                 : (const void*)&fa3_prefill_kernel<T, D, CAUSAL, false, PAGED, T, VARLEN, WINDOW>;
+}
+// the windowed instantiations exist under the causal flag only
+template <typename T, int D, bool VARLEN>
+const void* fn_td(bool causal, bool paged, bool out32, bool window) {
+    if (window) return paged ? fn_out<T, D, VARLEN, true, true, true>(out32) : fn_out<T, D, VARLEN, true, false, true>(out32);
+    if (causal) return paged ? fn_out<T, D, VARLEN, true, true>(out32) : fn_out<T, D, VARLEN, true, false>(out32);
+    return paged ? fn_out<T, D, VARLEN, false, true>(out32) : fn_out<T, D, VARLEN, false, false>(out32);
+}
+
+// of checked arguments: the kernel's name into buf -> workgroups
+template <bool VARLEN, typename Args>
+int describe(const Args* a, int window, char* buf, size_t n) {
+    if (buf && n)
+        snprintf(buf, n, "fa3_prefill_%s_d%d_%s%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
+                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", a->causal ? "_causal" : "", window ? "_win" : "", VARLEN ? "_varlen" : "",
+                 a->block_table ? "_paged" : "");
+    return (int)workgroups(a);
+}
+
+// of checked arguments: one launch on `stream`
+template <bool VARLEN, typename Args>
+int launch(const Args* a, int window, void* stream) {
+    typename PrefillParamsOf<VARLEN, true>::type p;   // the window-less kernels take its base, unchanged
+    fill_attention_params(p, a);
+    p.nqblk = (p.Sq + FWD_BLOCK_M - 1) / FWD_BLOCK_M;
+    p.kv_group = a->H / a->Hkv;
+    if constexpr (VARLEN) {
+        p.cu_seqlens_q = a->cu_seqlens_q; p.total_q = a->total_q;
+    }
+    p.window = window;
+
+    const bool out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr, causal = a->causal != 0, win = window != 0;
+    const void* fn = dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
+        return fn_td<typename decltype(t)::type, decltype(t)::D, VARLEN>(causal, paged, out32, win);
+    });
+    const int lds = 2 * 2 * BLOCK_N * a->D * 2;      // two buffers of a K and a V tile image (<= 64 KiB)
+    const DeviceScope dev(a->device_id);
+    if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
+    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: the base, or all of it
+    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)workgroups(a)), dim3(FWD_THREADS), kargs, (size_t)lds, (hipStream_t)stream);
+    return hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+}
+
+}  // namespace prefill
+}  // namespace pfa

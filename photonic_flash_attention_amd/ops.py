@@ -166,7 +166,7 @@ def build_args(q, k, v, out, *, causal=False, seqlens_k=None, key_mask=None, sof
         B=B, H=H, Sq=Sq, Sk=Sk, D=D,
         dtype_in=_DT[q.dtype], dtype_out=_DT[out.dtype], causal=1 if causal else 0,
         softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
-        device_id=q.device.index if q.device.index is not None else torch.cuda.current_device(),
+        device_id=_device_index(q.device),
         kv_group=H // Hkv,
     )
     keep = []
@@ -276,9 +276,7 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
                             drop_mask=drop_mask, drop_scale=drop_scale)
     stream = torch.cuda.current_stream(q.device).cuda_stream
     st = _capi.load().pfa_fa3_fwd(C.byref(args), C.c_void_p(stream))
-    if st in (-3, -4, -5, -6, -7, -10):
-        raise ValueError(f"pfa_fa3_fwd: {_capi.status_string(st)}")
-    _capi.check_status(st)
+    _raise_status("pfa_fa3_fwd", st)
     weights = None
     if return_weights:
         Sk = k.shape[2]
@@ -286,9 +284,7 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
         weights = torch.empty((B, H, Sq, Sk), dtype=wdt, device=q.device)     # the kernel writes every element, masked ones as zeros
         stw = _capi.load().pfa_fa3_weights(C.byref(args), C.c_void_p(weights.data_ptr()), _DT[wdt],
                                            weights.stride(0), weights.stride(1), weights.stride(2), C.c_void_p(stream))
-        if stw in (-3, -4, -5, -6, -7, -10):
-            raise ValueError(f"pfa_fa3_weights: {_capi.status_string(stw)}")
-        _capi.check_status(stw)
+        _raise_status("pfa_fa3_weights", stw)
     for t in keep:   # tensors made here must outlive the enqueued kernels
         t.record_stream(torch.cuda.current_stream(q.device))
     if return_weights:
@@ -370,7 +366,7 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
     a.kv_group = H // Hkv
     a.dtype, a.dtype_grad, a.causal = _DT[q.dtype], _DT[gdt], 1 if causal else 0
     a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
-    a.device_id = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    a.device_id = _device_index(q.device)
     stream = torch.cuda.current_stream(q.device)
     if a.mask:   # element masks: scratch for the condensed words / tile ranges (0 bytes for key-only masks; optional for the library)
         mws = int(_capi.load().pfa_fa3_bwd_mask_workspace_bytes(C.byref(a)))
@@ -379,9 +375,7 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
             a.mask_workspace, a.mask_workspace_bytes = ws.data_ptr(), mws
             keep.append(ws)
     st = _capi.load().pfa_fa3_bwd(C.byref(a), C.c_void_p(stream.cuda_stream))
-    if st in (-3, -4, -5, -6, -7, -10):
-        raise ValueError(f"pfa_fa3_bwd: {_capi.status_string(st)}")
-    _capi.check_status(st)
+    _raise_status("pfa_fa3_bwd", st)
     for t in keep:
         t.record_stream(stream)
     return dq, dk, dv
@@ -461,18 +455,32 @@ def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=Non
     return _FA3Function.apply(q, k, v, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype, bool(return_weights), weights_dtype)
 
 
-def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table):
-    """What every call over a KV cache checks about its 4-D caches (or pools and block table) against a query of B sequences, H
-    heads and head dim D.  -> ``(Hkv, Smax, page_size, num_pages, output dtype)``, the paging pair 0 without a table."""
-    Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+def _device_index(device: torch.device) -> int:
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def _raise_status(entry: str, st: int, null_too: bool = False) -> None:
+    """A non-zero status of the C entry point ``entry``: what the caller's arguments caused as ``ValueError`` (``null_too``: the
+    calls over a KV cache count a missing pointer among them), anything else as ``PfaError``."""
+    if st in (-3, -4, -5, -6, -7, -10) or (null_too and st == -1):
+        raise ValueError(f"{entry}: {_capi.status_string(st)}")
+    _capi.check_status(st)
+
+
+def _cache_geometry(name: str, rows, B, Hkv, D, k_cache, v_cache, block_table, H=None):
+    """What every call over a KV cache, reading or writing, checks about its 4-D caches (or pools and block table) against B
+    sequences of Hkv key heads and head dim D.  ``rows`` (printed as ``name``) is the tensor they are matched with: q, or k_new.
+    The readers pass H: Hkv must divide it.  -> ``(Smax, page_size, num_pages)``, the paging pair 0 without a table."""
+    Smax = k_cache.shape[2]
     page_size = num_pages = 0
+    bad_heads = H is not None and (Hkv < 1 or H % Hkv)
     if block_table is None:
-        if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != (B, Hkv, Smax, D) or Hkv < 1 or H % Hkv:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
+        if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != k_cache.shape or bad_heads:
+            raise ValueError(f"shape mismatch: {name} {tuple(rows.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
     else:
         num_pages, page_size = k_cache.shape[0], k_cache.shape[2]
-        if k_cache.shape != (num_pages, Hkv, page_size, D) or v_cache.shape != k_cache.shape or num_pages < 1 or Hkv < 1 or H % Hkv:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} k pool {tuple(k_cache.shape)} v pool {tuple(v_cache.shape)}")
+        if k_cache.shape != (num_pages, Hkv, page_size, D) or v_cache.shape != k_cache.shape or num_pages < 1 or bad_heads:
+            raise ValueError(f"shape mismatch: {name} {tuple(rows.shape)} k pool {tuple(k_cache.shape)} v pool {tuple(v_cache.shape)}")
         if page_size < 64 or page_size % 64:
             raise ValueError(f"page size {page_size}: must be a multiple of 64 keys")
         if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
@@ -481,9 +489,17 @@ def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_t
             raise ValueError(f"block_table must be [B, max_pages] with B = {B}, got {tuple(block_table.shape)}")
         if block_table.stride(1) != 1 and block_table.shape[1] != 1:
             raise ValueError("block_table: the last dim must be contiguous")
-        if not block_table.is_cuda or block_table.device != q.device:
-            raise ValueError("block_table must live on the operands' device (there is no CPU path)")
         Smax = block_table.shape[1] * page_size
+    return Smax, page_size, num_pages
+
+
+def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table):
+    """What the attention calls over a KV cache check about their caches against a query of B sequences, H heads and head dim D:
+    ``_cache_geometry`` and what only the readers ask.  -> ``(Hkv, Smax, page_size, num_pages, output dtype)``."""
+    Hkv = k_cache.shape[1]
+    Smax, page_size, num_pages = _cache_geometry("q", q, B, Hkv, D, k_cache, v_cache, block_table, H)
+    if block_table is not None and (not block_table.is_cuda or block_table.device != q.device):
+        raise ValueError("block_table must live on the operands' device (there is no CPU path)")
     if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise ValueError("q, k_cache, v_cache must share dtype bf16 or fp16")
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda) or k_cache.device != q.device or v_cache.device != q.device:
@@ -512,7 +528,7 @@ def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out
         v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2], o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2],
         B=B, H=H, Hkv=Hkv, Sq=Sq, Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt], causal=1 if causal else 0,
         softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
-        device_id=q.device.index if q.device.index is not None else torch.cuda.current_device())
+        device_id=_device_index(q.device))
     if block_table is not None:
         a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
         a.page_size, a.num_pages = page_size, num_pages
@@ -621,24 +637,7 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
             raise ValueError(f"max_seqlen_q {max_seqlen_q}: without cu_seqlens_q every sequence brings k_new's {Sq} rows")
         max_seqlen_q, total = Sq, B * Sq
     max_seqlen_q = int(max_seqlen_q)
-    page_size = num_pages = 0
-    if block_table is None:
-        Smax = k_cache.shape[2]
-        if k_cache.shape != (B, Hkv, Smax, D) or v_cache.shape != k_cache.shape:
-            raise ValueError(f"shape mismatch: k_new {tuple(k_new.shape)} k_cache {tuple(k_cache.shape)} v_cache {tuple(v_cache.shape)}")
-    else:
-        num_pages, page_size = k_cache.shape[0], k_cache.shape[2]
-        if k_cache.shape != (num_pages, Hkv, page_size, D) or v_cache.shape != k_cache.shape or num_pages < 1:
-            raise ValueError(f"shape mismatch: k_new {tuple(k_new.shape)} k pool {tuple(k_cache.shape)} v pool {tuple(v_cache.shape)}")
-        if page_size < 64 or page_size % 64:
-            raise ValueError(f"page size {page_size}: must be a multiple of 64 keys")
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
-            raise ValueError("block_table must be an int32 tensor")
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
-            raise ValueError(f"block_table must be [B, max_pages] with B = {B}, got {tuple(block_table.shape)}")
-        if block_table.stride(1) != 1 and block_table.shape[1] != 1:
-            raise ValueError("block_table: the last dim must be contiguous")
-        Smax = block_table.shape[1] * page_size
+    Smax, page_size, num_pages = _cache_geometry("k_new", k_new, B, Hkv, D, k_cache, v_cache, block_table)
     if k_new.dtype not in (torch.bfloat16, torch.float16) or any(t.dtype != k_new.dtype for t in (v_new, k_cache, v_cache)):
         raise ValueError("k_new, v_new, k_cache, v_cache must share dtype bf16 or fp16")
     if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.shape != (B,):
@@ -662,7 +661,7 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
         k_new=k_new.data_ptr(), v_new=v_new.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(),
         k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
         B=B, Hkv=Hkv, total_new=total, max_seqlen_q=max_seqlen_q, Smax=Smax, D=D, dtype=_DT[k_new.dtype],
-        device_id=dev.index if dev.index is not None else torch.cuda.current_device())
+        device_id=_device_index(dev))
     if ragged:
         a.cu_seqlens_q = cu_seqlens_q.data_ptr()
         a.kn_stride_s, a.kn_stride_h, a.vn_stride_s, a.vn_stride_h = k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1)
@@ -675,9 +674,7 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
     _set_cache_seqlens(a, cache_seqlens, k_new, keep, B)
     stream = torch.cuda.current_stream(dev)
     st = _capi.load().pfa_kv_append(C.byref(a), C.c_void_p(stream.cuda_stream))
-    if st in (-1, -3, -4, -5, -6, -7, -10):
-        raise ValueError(f"pfa_kv_append: {_capi.status_string(st)}")
-    _capi.check_status(st)
+    _raise_status("pfa_kv_append", st, null_too=True)
     for t in keep:   # tensors made here must outlive the enqueued kernel
         t.record_stream(stream)
 
@@ -692,6 +689,23 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, **
     if cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     kv_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, **ragged)
+
+
+def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, **ragged):
+    """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
+    ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
+    the current stream right behind it, the status, and the kept tensors' hold on the stream.  -> lse or None."""
+    lse = None
+    if lse_shape is not None:
+        lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
+        a.lse = lse.data_ptr()
+    _append_first(*new_rows, **ragged)
+    stream = torch.cuda.current_stream(q.device)
+    st = getattr(_capi.load(), entry + "_ex")(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
+    _raise_status(entry, st, null_too=True)
+    for t in keep:   # tensors made here must outlive the enqueued kernels
+        t.record_stream(stream)
+    return lse
 
 
 def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
@@ -746,25 +760,13 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         if cache_seqlens is None:
             cache_seqlens = _mask_bound(km)
     _set_cache_seqlens(a, cache_seqlens, q, keep)
-    lse = None
-    if return_lse:
-        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-        a.lse = lse.data_ptr()
-    lib = _capi.load()
-    ext_ref = None if ext is None else C.byref(ext)
-    ws_bytes = int(lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), ext_ref))
+    ws_bytes = int(_capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)))
     if ws_bytes:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
         keep.append(ws)
-    _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, max_seqlen_q=Sq)
-    stream = torch.cuda.current_stream(q.device)
-    st = lib.pfa_fa3_decode_ex(C.byref(a), ext_ref, C.c_void_p(stream.cuda_stream))
-    if st in (-1, -3, -4, -5, -6, -7, -10):
-        raise ValueError(f"pfa_fa3_decode: {_capi.status_string(st)}")
-    _capi.check_status(st)
-    for t in keep:   # tensors made here must outlive the enqueued kernels
-        t.record_stream(stream)
+    lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), max_seqlen_q=Sq)
     return out, lse
 
 
@@ -799,18 +801,8 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
-    lse = None
-    if return_lse:
-        lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
-        a.lse = lse.data_ptr()
-    _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, max_seqlen_q=q.shape[2])
-    stream = torch.cuda.current_stream(q.device)
-    st = _capi.load().pfa_fa3_prefill_ex(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
-    if st in (-1, -3, -4, -5, -6, -7, -10):
-        raise ValueError(f"pfa_fa3_prefill: {_capi.status_string(st)}")
-    _capi.check_status(st)
-    for t in keep:   # tensors made here must outlive the enqueued kernel
-        t.record_stream(stream)
+    lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), max_seqlen_q=q.shape[2])
     return out, lse
 
 
@@ -870,22 +862,13 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
         B=B, H=H, Hkv=Hkv, total_q=total_q, max_seqlen_q=int(max_seqlen_q), Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt],
         causal=1 if causal else 0, softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
-        device_id=q.device.index if q.device.index is not None else torch.cuda.current_device())
+        device_id=_device_index(q.device))
     if block_table is not None:
         a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
         a.page_size, a.num_pages = page_size, num_pages
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep, B)
-    lse = None
-    if return_lse:
-        lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
-        a.lse = lse.data_ptr()
-    _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
-    stream = torch.cuda.current_stream(q.device)
-    st = _capi.load().pfa_fa3_prefill_varlen_ex(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
-    if st in (-1, -3, -4, -5, -6, -7, -10):
-        raise ValueError(f"pfa_fa3_prefill_varlen: {_capi.status_string(st)}")
-    _capi.check_status(st)
-    for t in keep:   # tensors made here must outlive the enqueued kernel
-        t.record_stream(stream)
+    lse = _finish_cache_call("pfa_fa3_prefill_varlen", a, ext, q, (H, total_q) if return_lse else None, keep,
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table),
+                             cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
     return out, lse
