@@ -298,6 +298,16 @@ def fa3_forward_bshd(q, k, v, **kw):
     return (res[0].permute(0, 2, 1, 3),) + tuple(res[1:])
 
 
+def _dout_meets_abi(dout: torch.Tensor, D: int) -> bool:
+    """``pfa_fa3_bwd``'s rules for ``dout`` (check_bwd in csrc/pfa_bwd_capi.hip): head dim contiguous, read in 16-byte pieces --
+    base 16-byte aligned, every stride a multiple of 8 elements (fp32: 4) -- and, on the fp32 kernels, rows at least ``D`` apart.
+    Autograd hands over whatever view the loss produced (a slice of a wider tensor, a broadcast): what fails a rule is copied."""
+    unit = 16 // dout.element_size()
+    sb, sh, ss, sd = dout.stride()
+    return (sd == 1 and dout.data_ptr() % 16 == 0 and sb % unit == 0 and sh % unit == 0 and ss % unit == 0
+            and (dout.dtype != torch.float32 or ss >= D))
+
+
 def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=None, key_mask=None, mask=None,
                  softmax_scale: Optional[float] = None, grad_dtype: Optional[torch.dtype] = None,
                  drop_mask: Optional[torch.Tensor] = None, drop_scale: float = 1.0):
@@ -326,7 +336,7 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
                              grad_dtype=grad_dtype, drop_mask=drop_mask, drop_scale=drop_scale)
         return tuple(g[..., :D] for g in grads)
     gdt = q.dtype if grad_dtype is None else grad_dtype
-    if dout.stride(3) != 1:
+    if not _dout_meets_abi(dout, D):
         dout = dout.contiguous()
     dq = torch.empty((B, Sq, H, D), dtype=gdt, device=q.device).permute(0, 2, 1, 3)
     dk = torch.empty((B, Sk, Hkv, D), dtype=gdt, device=q.device).permute(0, 2, 1, 3)      # grouped-query heads: dK / dV summed over
