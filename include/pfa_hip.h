@@ -12,6 +12,7 @@
  * v9, additive: pfa_fa3_cache_ext and the *_ex entry points of the three calls over a KV cache -- a sliding window (each row sees its
  * last `window` keys), with keys and block-table entries behind the window never read;
  * v9, additive: pfa_kv_append* -- the device-side append of a step's new K / V rows into a contiguous or paged cache.
+ * v9, additive: pfa_rope_append* -- rotary embedding fused into that append: Q and the new K rotated by positions derived on the device.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -537,6 +538,103 @@ int pfa_kv_append(const pfa_kv_append_args* a, void* stream);
 /* Introspection: the kernel name ("_varlen" appended with cu_seqlens_q, then "_paged" with a block table) into buf (NUL terminated,
  * truncated to n); returns the workgroups, or a pfa_status. */
 int pfa_kv_append_describe(const pfa_kv_append_args* a, char* buf, size_t n);
+
+/*
+ * Rotary embedding fused into the KV-cache append (ABI v9, additive): pfa_kv_append that also rotates the step's Q and new K rows by
+ * each row's position -- flash-attn's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=, rotary_interleaved=).  The position is
+ * derived on the device from the data the append already reads, so rotary + append + attention is two launches with no host round
+ * trip and replays as one graph.
+ *
+ * Sequences, lengths, clamps, drops and paging are exactly pfa_kv_append's (above): len_b, s_b, e_b, Sq_b, and new row i of sequence b
+ * belongs to logical key pos = len_b - Sq_b + i.
+ *
+ *   position        p = clamp(pos + pos_offsets[b], 0, max_pos - 1), computed in 64 bits.  pos_offsets: optional device int32 [B], NULL =
+ *                   all 0 (a cache whose leading tokens were evicted or left-padded).  An out-of-range position gives wrong numbers,
+ *                   never an address outside the tables: the rule for page ids.
+ *   rot_dim         R, a multiple of 16 with 16 <= R <= D; D a multiple of 16 with 16 <= D <= 256.  half = R / 2.  Elements at and past R
+ *                   of every head are copied unchanged.
+ *   cos, sin        fp32 [max_pos, half] device tables, row stride cs_stride elements (>= half, a multiple of 4), bases 16-byte aligned.
+ *   pairing         default (half-rotated: Hugging Face rotate_half, NeoX, Llama): (x1, x2) = (x[j], x[j + half]), j < half;
+ *                   PFA_ROPE_INTERLEAVED (GPT-J): (x1, x2) = (x[2j], x[2j + 1]).  With c = cos[p][j], s = sin[p][j]:
+ *                       y1 = x1 * c - x2 * s        y2 = x2 * c + x1 * s
+ *   arithmetic      operands widened to fp32; each product and the one add / subtract rounded to fp32 separately (no fused multiply-
+ *                   add); the result converted round-to-nearest-even to the operand dtype.  Reproducible, and a plain-torch model
+ *                   written as separate fp32 ops matches bit for bit.  (A NaN result is a NaN; its payload is not specified.)
+ *   K               row i rotated and written where pfa_kv_append would write it, with the same drops: pos < 0, and on a paged cache a
+ *                   page id outside [0, num_pages - 1].
+ *   V               copied there unrotated.
+ *   q, q_out        optional (both NULL, with H = 0: K / V only).  H heads, laid out as the step's rows: packed [total_new, H, D] by
+ *                   *_stride_s / *_stride_h, or uniform [B, Sq, H, D] with *_stride_b as well.  Every one of the sequence's Sq_b rows is
+ *                   rotated at its clamped p and written to q_out, rows with pos < 0 included (the attention call gives those O = 0
+ *                   whatever Q holds).  q_out may be q itself (same pointer and strides: in place) or disjoint storage; partial overlap
+ *                   is undefined.
+ *   max_seqlen_q    sizes the grid as in pfa_kv_append: B * ceil(max_seqlen_q * (H + 2 * Hkv) * (D / 16) / 256) workgroups from host
+ *                   shapes only, valid while cu_seqlens_q, cache_seqlens, pos_offsets, the block table, the tables' contents and the
+ *                   tensors change between replays.
+ *
+ * Never read: packed rows no sequence covers, and table rows other than the p of a row that is processed.  Never written: anything but
+ * the destination rows of the cache or pool and the covered rows of q_out (lengths, offsets and block table included), so a replay is
+ * idempotent unless it runs in place on Q.
+ *
+ * One launch; no workspace, no atomics, no LDS.  Q, K and V move as 16-byte loads and stores; every source element is read by one
+ * work item and every destination written by one, and an item reads all it needs before it writes.
+ *
+ * Field rules, in the order their errors are reported.  First pfa_kv_append's, in its order, where the fields coincide: size wrong ->
+ * PFA_ERR_STRUCT_SIZE; reserved0 / reserved1 non-zero -> PFA_ERR_FLAGS; k_new, v_new, k_cache, v_cache or cache_seqlens NULL ->
+ * PFA_ERR_NULL; B, Hkv, Smax, total_new or max_seqlen_q < 1 -> PFA_ERR_SHAPE; D not a multiple of 8 in [8, 256] -> PFA_ERR_HEAD_DIM; dtype
+ * not bf16 / fp16 -> PFA_ERR_DTYPE; a kn / vn / k / v stride not a multiple of 8, or a negative cache token stride -> PFA_ERR_STRIDE;
+ * k_new, v_new, k_cache or v_cache not 16-byte aligned, cache_seqlens / cu_seqlens_q / block_table not 4-byte aligned -> PFA_ERR_ALIGN;
+ * the paging fields as in pfa_fa3_decode_args; ragged with a non-zero kn_stride_b / vn_stride_b -> PFA_ERR_FLAGS; ragged with max_seqlen_q
+ * > total_new, uniform with B * max_seqlen_q > total_new -> PFA_ERR_SHAPE.  Then: flag bits other than PFA_ROPE_INTERLEAVED ->
+ * PFA_ERR_FLAGS; cos or sin NULL -> PFA_ERR_NULL; exactly one of q / q_out NULL -> PFA_ERR_NULL; H < 1 with q -> PFA_ERR_SHAPE; H != 0
+ * without q -> PFA_ERR_FLAGS; max_pos < 1 -> PFA_ERR_SHAPE; D not a multiple of 16 in [16, 256] or rot_dim not a multiple of 16 in
+ * [16, D] -> PFA_ERR_HEAD_DIM; a q / qo stride not a multiple of 8, cs_stride not a multiple of 4 or < rot_dim / 2 -> PFA_ERR_STRIDE; q,
+ * q_out, cos or sin not 16-byte aligned, pos_offsets not 4-byte aligned -> PFA_ERR_ALIGN; ragged with a non-zero q_stride_b /
+ * qo_stride_b -> PFA_ERR_FLAGS; more workgroups than a grid holds or max_seqlen_q * (H + 2 * Hkv) * (D / 16) + 256 past 2^31 - 1 ->
+ * PFA_ERR_SHAPE.
+ */
+#define PFA_ROPE_INTERLEAVED 0x1u   /* pfa_rope_append_args.flags: pair (x[2j], x[2j + 1]) instead of (x[j], x[j + rot_dim / 2]) */
+
+typedef struct pfa_rope_append_args {
+    uint32_t size;              /* = sizeof(pfa_rope_append_args) */
+    uint32_t flags;             /* 0 | PFA_ROPE_INTERLEAVED */
+    const void* q;              /* NULL with q_out NULL and H = 0: K / V only */
+    void*       q_out;          /* may be q (in place) */
+    const void* k_new;
+    const void* v_new;
+    void*       k_cache;
+    void*       v_cache;
+    const float* cos;           /* device fp32 [max_pos, rot_dim / 2] by cs_stride */
+    const float* sin;
+    const int32_t* cu_seqlens_q;   /* device [B + 1], or NULL = uniform */
+    const int32_t* cache_seqlens;  /* device [B], required: lengths after the step */
+    const int32_t* pos_offsets;    /* device [B], or NULL = 0 */
+    int64_t q_stride_b, q_stride_s, q_stride_h;      /* *_b: uniform only, else 0 */
+    int64_t qo_stride_b, qo_stride_s, qo_stride_h;   /* of q_out */
+    int64_t kn_stride_b, kn_stride_s, kn_stride_h;
+    int64_t vn_stride_b, vn_stride_s, vn_stride_h;
+    int64_t k_stride_b, k_stride_h, k_stride_s;
+    int64_t v_stride_b, v_stride_h, v_stride_s;
+    int64_t cs_stride;          /* row stride of cos and of sin, in elements */
+    int32_t B, H, Hkv, total_new, max_seqlen_q, Smax, D, rot_dim, max_pos;
+    int32_t dtype;              /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 */
+    int32_t device_id;
+    int32_t reserved0;          /* must be 0 */
+    /* paged cache, as in pfa_fa3_decode_args.  NULL / 0: the contiguous cache. */
+    const int32_t* block_table;
+    int64_t block_table_stride_b;
+    int32_t page_size;          /* keys per page, a multiple of 64 */
+    int32_t num_pages;          /* pages in the pools */
+    int32_t reserved1;          /* must be 0 */
+} pfa_rope_append_args;
+
+/* Validate `a` without launching: PFA_OK or the error pfa_rope_append would return. */
+int pfa_rope_append_check(const pfa_rope_append_args* a);
+/* Enqueue the rotation and the append (one launch) on `stream`. */
+int pfa_rope_append(const pfa_rope_append_args* a, void* stream);
+/* Introspection: the kernel name rope_append_{bf16|fp16}_d{D}_r{rot_dim} ("_il" appended with PFA_ROPE_INTERLEAVED, then "_varlen" with
+ * cu_seqlens_q, then "_paged" with a block table) into buf (NUL terminated, truncated to n); returns the workgroups, or a pfa_status. */
+int pfa_rope_append_describe(const pfa_rope_append_args* a, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

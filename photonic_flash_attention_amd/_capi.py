@@ -17,6 +17,7 @@ PFA_ABI_VERSION = 9
 PFA_DTYPE_BF16, PFA_DTYPE_FP16, PFA_DTYPE_FP32 = 0, 1, 2
 PFA_FLAG_SPLIT_P = 0x1
 PFA_FLAG_NO_XCD_MAP = 0x2
+PFA_ROPE_INTERLEAVED = 0x1
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, "libpfa_hip.so")
@@ -103,11 +104,27 @@ class PfaKvAppendArgs(C.Structure):
     )
 
 
+class PfaRopeAppendArgs(C.Structure):
+    """Mirror of ``struct pfa_rope_append_args`` (include/pfa_hip.h): rotary embedding fused into the KV-cache append."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("q", "q_out", "k_new", "v_new", "k_cache", "v_cache", "cos", "sin", "cu_seqlens_q", "cache_seqlens",
+                                     "pos_offsets")]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in ("q", "qo", "kn", "vn") for a in "bsh"]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "kv" for a in "bhs"]
+        + [("cs_stride", C.c_int64)]
+        + [(n, C.c_int32) for n in ("B", "H", "Hkv", "total_new", "max_seqlen_q", "Smax", "D", "rot_dim", "max_pos", "dtype", "device_id",
+                                    "reserved0")]
+        + [("block_table", C.c_void_p), ("block_table_stride_b", C.c_int64), ("page_size", C.c_int32), ("num_pages", C.c_int32)]
+        + [("reserved1", C.c_int32)]
+    )
+
+
 def _prototypes():
     """Export name -> ``(restype, argtypes)``, one row per symbol ``include/pfa_hip.h`` declares (argtypes None: left untyped)."""
     i, sz, vp, buf = C.c_int, C.c_size_t, C.c_void_p, [C.c_char_p, C.c_size_t]
-    fa3, bwd, dec, var, app, ext = (C.POINTER(t) for t in (PfaFa3Args, PfaFa3BwdArgs, PfaFa3DecodeArgs, PfaFa3PrefillVarlenArgs,
-                                                           PfaKvAppendArgs, PfaFa3CacheExt))
+    fa3, bwd, dec, var, app, ext, rope = (C.POINTER(t) for t in (PfaFa3Args, PfaFa3BwdArgs, PfaFa3DecodeArgs, PfaFa3PrefillVarlenArgs,
+                                                                 PfaKvAppendArgs, PfaFa3CacheExt, PfaRopeAppendArgs))
     ns = [C.POINTER(C.c_int32)]
     return {
         "pfa_abi_version": (i, None),
@@ -147,6 +164,9 @@ def _prototypes():
         "pfa_kv_append_check": (i, [app]),
         "pfa_kv_append": (i, [app, vp]),
         "pfa_kv_append_describe": (i, [app] + buf),
+        "pfa_rope_append_check": (i, [rope]),
+        "pfa_rope_append": (i, [rope, vp]),
+        "pfa_rope_append_describe": (i, [rope] + buf),
     }
 
 
@@ -281,3 +301,13 @@ def make_kv_append_args(**kw) -> PfaKvAppendArgs:
 def describe_kv_append(args: PfaKvAppendArgs):
     """-> (kernel name, workgroups) of ``pfa_kv_append``: ``B * ceil(max_seqlen_q * Hkv * (D / 8) / 256)``, from host shapes only."""
     return _describe("pfa_kv_append_describe", args)
+
+
+def make_rope_append_args(**kw) -> PfaRopeAppendArgs:
+    return _make(PfaRopeAppendArgs, kw)
+
+
+def describe_rope_append(args: PfaRopeAppendArgs):
+    """-> (kernel name, workgroups) of ``pfa_rope_append``: ``B * ceil(max_seqlen_q * (H + 2 * Hkv) * (D / 16) / 256)``, from host
+    shapes only."""
+    return _describe("pfa_rope_append_describe", args)

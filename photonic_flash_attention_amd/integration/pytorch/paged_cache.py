@@ -316,18 +316,33 @@ class PagedKVCache:
         return cu_seqlens_q, max_seqlen_q
 
     def write_step(self, k_new: torch.Tensor, v_new: torch.Tensor, q_lens: Optional[Sequence[int]] = None, slots: Slots = None, *,
-                   cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None) -> None:
+                   cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None, q: Optional[torch.Tensor] = None,
+                   rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+                   pos_offsets: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """The device half of an append (``ops.kv_append``, one launch of the HIP copy kernel): write the packed ``k_new`` / ``v_new``
         ``[total, Hkv, D]`` of a ragged step to where the cache's own table and lengths say, sequence i bringing ``q_lens[i]`` rows.
         Call ``advance`` first: the lengths count the step's rows, and row j of sequence i goes to key ``length - q_lens[i] + j``.  Does
         no bookkeeping, so ``advance(slots, lens)`` + ``write_step(k_new, v_new, lens, slots)`` equals ``append_varlen``.  Slots are
         chosen and captured as in ``decode``; a host list ``q_lens``, or a device ``cu_seqlens_q`` (int32 ``[len(slots) + 1]``) plus
         the ``max_seqlen_q`` bound, as in ``prefill_varlen`` -- the form a graph captures, next to ``prefill_varlen``, and replays
-        while ``advance`` and in-place updates of ``cu_seqlens_q`` and the inputs happen in between.  Also runs on CPU tensors."""
+        while ``advance`` and in-place updates of ``cu_seqlens_q`` and the inputs happen in between.  Also runs on CPU tensors.
+
+        With ``rotary_cos=, rotary_sin=`` (and ``rotary_interleaved``, ``pos_offsets`` -- int32, one per slot of the call) the launch is
+        ``ops.rope_append`` instead: the K rows are rotated at the positions they are written to, and the packed ``q [total, H, D]``, if
+        given, is rotated into a fresh buffer that is returned (else None): the tensor ``prefill_varlen`` then takes."""
+        rotary = rotary_cos is not None or rotary_sin is not None
+        if not rotary and (q is not None or rotary_interleaved or pos_offsets is not None):
+            raise ValueError("q, rotary_interleaved and pos_offsets need rotary_cos and rotary_sin")
+        if rotary and (rotary_cos is None or rotary_sin is None):
+            raise ValueError("rotary_cos and rotary_sin go together")
         table, lens = self._rows(slots)
         if cu_seqlens_q is None and q_lens is not None and len(q_lens) == table.shape[0] and not any(q_lens):
-            return                                       # a step without rows, as append_varlen takes one
+            return None if q is None else torch.empty_like(q)   # a step without rows, as append_varlen takes one
         cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], k_new.shape[0], "k_new")
+        if rotary:
+            return ops.rope_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens,
+                                   rotary_cos=rotary_cos, rotary_sin=rotary_sin, q=q, rotary_interleaved=rotary_interleaved,
+                                   pos_offsets=pos_offsets, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, block_table=table)
         ops.kv_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, cu_seqlens_q=cu_seqlens_q,
                       max_seqlen_q=max_seqlen_q, block_table=table)
 

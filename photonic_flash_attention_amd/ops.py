@@ -606,26 +606,9 @@ def _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, max_seqlen_q, blo
             pool[pg[ok], :, (pos % page_size)[ok]] = r[ok]
 
 
-def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
-              cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None,
-              block_table: Optional[torch.Tensor] = None) -> None:
-    """Device-side KV-cache append (``pfa_kv_append``): place a step's new K / V rows into the cache the calls over a KV cache read --
-    the write side of ``fa3_decode`` / ``fa3_prefill_cache`` / ``fa3_prefill_varlen``, from device data alone.
-
-    k_cache / v_cache (and ``block_table``) are passed exactly as to ``fa3_prefill_varlen``: ``[B,Hkv,Smax,D]``-shaped views, or with
-    ``block_table`` (int32 ``[B, max_pages]``) pools ``[num_pages,Hkv,page_size,D]``-shaped, page_size a multiple of 64.  k_new / v_new:
-    with ``cu_seqlens_q`` (int32 ``[B + 1]``, as in ``fa3_prefill_varlen``) the packed ``[total, Hkv, D]`` rows and ``max_seqlen_q`` the
-    host bound on one sequence's rows; without it ``[B,Hkv,Sq,D]`` (any strides, head dim contiguous), ``max_seqlen_q`` being Sq.
-    bf16 / fp16, D a multiple of 8 up to 256.  cache_seqlens: int32 ``[B]``, required, the lengths AFTER the step -- the tensor the
-    attention call behind it takes.  With len_b = clamp(cache_seqlens[b], 0, Smax) and Sq_b the sequence's rows (clamped as
-    ``fa3_prefill_varlen`` clamps them), row i goes to logical key ``len_b - Sq_b + i``.  Rows in front of key 0 (len_b < Sq_b) are
-    dropped, and so is a row whose page id lies outside the pool: a write is never clamped into someone else's page.  Packed rows no
-    sequence covers are never read; nothing but the destination rows is written, lengths and table included, so a replay is
-    idempotent.  Two sequences given the same destination leave one of the two rows there (copy-on-write is the caller's business).
-
-    On device tensors: one launch of a HIP copy kernel whose grid depends on host shapes only -- no host synchronisation, no tensor
-    creation, capturable in ``torch.cuda.graph`` and valid while cu_seqlens_q, lengths, table and cache change between replays.  On CPU
-    tensors the same rule runs in plain torch (the executable specification; ``PagedKVCache``'s bookkeeping is tested through it)."""
+def _append_operands(entry: str, k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others=()):
+    """What ``kv_append`` and ``rope_append`` check about the step's rows, the caches and the device data they share (``others``: the
+    further tensors that must live on k_new's device).  -> ``(ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages)``."""
     ragged = cu_seqlens_q is not None
     if k_new.dim() != (3 if ragged else 4) or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("k_new must be 3-D ([total,Hkv,D]) with cu_seqlens_q, else 4-D ([B,Hkv,Sq,D]); k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
@@ -656,22 +639,25 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
         raise ValueError(f"max_seqlen_q {max_seqlen_q}: must lie in 1 .. {total}, the rows k_new holds")
     dev = k_new.device
     if any(t.device != dev for t in (v_new, k_cache, v_cache, cache_seqlens) + ((cu_seqlens_q,) if ragged else ())
-           + ((block_table,) if block_table is not None else ())):
-        raise ValueError("pfa_kv_append needs all its tensors on one device")
-    if dev.type == "cpu":
-        _kv_append_model(k_new, v_new, k_cache, v_cache, cache_seqlens.tolist(), cu_seqlens_q.tolist() if ragged else None,
-                         max_seqlen_q, block_table)
-        return
+           + ((block_table,) if block_table is not None else ()) + tuple(others)):
+        raise ValueError(f"{entry} needs all its tensors on one device")
+    return ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages
+
+
+def _append_args(make, entry: str, k_new, v_new, k_cache, v_cache, geometry, cu_seqlens_q, block_table, **more):
+    """The argument block of ``pfa_kv_append`` / ``pfa_rope_append`` (``make``: its ``_capi`` constructor) with the fields the two
+    share filled in from ``_append_operands``' ``geometry``; ``more`` are further fields."""
+    ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages = geometry
     if not k_new.is_cuda:
-        raise ValueError("pfa_kv_append needs device tensors (or CPU tensors for the torch model)")
+        raise ValueError(f"{entry} needs device tensors (or CPU tensors for the torch model)")
     if any(t.stride(-1) != 1 and D != 1 for t in (k_new, v_new)):
         raise ValueError("last (head_dim) stride must be 1")
     ks, vs = _bhsd_strides(k_cache), _bhsd_strides(v_cache)
-    a = _capi.make_kv_append_args(
+    a = make(
         k_new=k_new.data_ptr(), v_new=v_new.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(),
         k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
         B=B, Hkv=Hkv, total_new=total, max_seqlen_q=max_seqlen_q, Smax=Smax, D=D, dtype=_DT[k_new.dtype],
-        device_id=_device_index(dev))
+        device_id=_device_index(k_new.device), **more)
     if ragged:
         a.cu_seqlens_q = cu_seqlens_q.data_ptr()
         a.kn_stride_s, a.kn_stride_h, a.vn_stride_s, a.vn_stride_h = k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1)
@@ -680,36 +666,258 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
     if block_table is not None:
         a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
         a.page_size, a.num_pages = page_size, num_pages
+    return a
+
+
+def _append_launch(entry: str, a, cache_seqlens, k_new, B) -> None:
+    """``cache_seqlens`` into the block, then the one launch of ``entry`` on k_new's current stream."""
     keep = []
     _set_cache_seqlens(a, cache_seqlens, k_new, keep, B)
-    stream = torch.cuda.current_stream(dev)
-    st = _capi.load().pfa_kv_append(C.byref(a), C.c_void_p(stream.cuda_stream))
-    _raise_status("pfa_kv_append", st, null_too=True)
+    stream = torch.cuda.current_stream(k_new.device)
+    st = getattr(_capi.load(), entry)(C.byref(a), C.c_void_p(stream.cuda_stream))
+    _raise_status(entry, st, null_too=True)
     for t in keep:   # tensors made here must outlive the enqueued kernel
         t.record_stream(stream)
 
 
-def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, **ragged) -> None:
-    """The ``k_new=, v_new=`` form of the calls over a KV cache: ``kv_append`` enqueued in front of the attention launch, on the
-    same stream, with the same lengths, ``cu_seqlens_q`` and table."""
-    if k_new is None and v_new is None:
+def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
+              cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None,
+              block_table: Optional[torch.Tensor] = None) -> None:
+    """Device-side KV-cache append (``pfa_kv_append``): place a step's new K / V rows into the cache the calls over a KV cache read --
+    the write side of ``fa3_decode`` / ``fa3_prefill_cache`` / ``fa3_prefill_varlen``, from device data alone.
+
+    k_cache / v_cache (and ``block_table``) are passed exactly as to ``fa3_prefill_varlen``: ``[B,Hkv,Smax,D]``-shaped views, or with
+    ``block_table`` (int32 ``[B, max_pages]``) pools ``[num_pages,Hkv,page_size,D]``-shaped, page_size a multiple of 64.  k_new / v_new:
+    with ``cu_seqlens_q`` (int32 ``[B + 1]``, as in ``fa3_prefill_varlen``) the packed ``[total, Hkv, D]`` rows and ``max_seqlen_q`` the
+    host bound on one sequence's rows; without it ``[B,Hkv,Sq,D]`` (any strides, head dim contiguous), ``max_seqlen_q`` being Sq.
+    bf16 / fp16, D a multiple of 8 up to 256.  cache_seqlens: int32 ``[B]``, required, the lengths AFTER the step -- the tensor the
+    attention call behind it takes.  With len_b = clamp(cache_seqlens[b], 0, Smax) and Sq_b the sequence's rows (clamped as
+    ``fa3_prefill_varlen`` clamps them), row i goes to logical key ``len_b - Sq_b + i``.  Rows in front of key 0 (len_b < Sq_b) are
+    dropped, and so is a row whose page id lies outside the pool: a write is never clamped into someone else's page.  Packed rows no
+    sequence covers are never read; nothing but the destination rows is written, lengths and table included, so a replay is
+    idempotent.  Two sequences given the same destination leave one of the two rows there (copy-on-write is the caller's business).
+
+    On device tensors: one launch of a HIP copy kernel whose grid depends on host shapes only -- no host synchronisation, no tensor
+    creation, capturable in ``torch.cuda.graph`` and valid while cu_seqlens_q, lengths, table and cache change between replays.  On CPU
+    tensors the same rule runs in plain torch (the executable specification; ``PagedKVCache``'s bookkeeping is tested through it)."""
+    geo = _append_operands("pfa_kv_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table)
+    if k_new.device.type == "cpu":
+        _kv_append_model(k_new, v_new, k_cache, v_cache, cache_seqlens.tolist(), cu_seqlens_q.tolist() if geo[0] else None, geo[5], block_table)
         return
+    a = _append_args(_capi.make_kv_append_args, "pfa_kv_append", k_new, v_new, k_cache, v_cache, geo, cu_seqlens_q, block_table)
+    _append_launch("pfa_kv_append", a, cache_seqlens, k_new, geo[1])
+
+
+def rotary_tables(max_pos: int, rot_dim: int, base: float = 10000.0, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The standard rotary tables for ``rope_append``: ``(cos, sin)``, fp32 ``[max_pos, rot_dim // 2]``, of the angles
+    ``pos * inv_freq[j]`` with ``inv_freq = base ** (-arange(0, rot_dim, 2) / rot_dim)``.  Computed in fp64 and rounded once."""
+    max_pos, rot_dim = int(max_pos), int(rot_dim)
+    if max_pos < 1 or rot_dim < 2 or rot_dim % 2:
+        raise ValueError(f"rotary_tables: max_pos {max_pos} must be >= 1 and rot_dim {rot_dim} a positive even number")
+    inv_freq = float(base) ** (-torch.arange(0, rot_dim, 2, dtype=torch.float64) / rot_dim)
+    angle = torch.arange(max_pos, dtype=torch.float64)[:, None] * inv_freq[None, :]
+    cos, sin = angle.cos().to(torch.float32), angle.sin().to(torch.float32)
+    return (cos, sin) if device is None else (cos.to(device), sin.to(device))
+
+
+def _rope_rotate(x: torch.Tensor, c: torch.Tensor, s: torch.Tensor, interleaved: bool) -> torch.Tensor:
+    """Rows ``x [n, heads, D]`` rotated by their table rows ``c`` / ``s`` (fp32 ``[n, half]``), as ``pfa_rope_append`` rounds: operands
+    widened to fp32, the two products and the add / subtract separate fp32 operations, one rounding to the dtype.  Elements at and
+    past ``2 * half`` are copied.  -> a new tensor."""
+    half = c.shape[-1]
+    R = 2 * half
+    c, s = c[:, None, :], s[:, None, :]
+    x1, x2 = (x[..., 0:R:2], x[..., 1:R:2]) if interleaved else (x[..., :half], x[..., half:R])
+    y1 = (x1.float() * c - x2.float() * s).to(x.dtype)
+    y2 = (x2.float() * c + x1.float() * s).to(x.dtype)
+    out = x.clone()
+    if interleaved:
+        out[..., 0:R:2], out[..., 1:R:2] = y1, y2
+    else:
+        out[..., :half], out[..., half:R] = y1, y2
+    return out
+
+
+def _rope_append_model(k_new, v_new, k_cache, v_cache, cos, sin, lens, cu, max_seqlen_q, block_table, offsets, interleaved,
+                       q=None, q_out=None) -> None:
+    """``pfa_rope_append``'s rule in plain torch, every clamp and drop included: the executable specification, and what
+    ``rope_append`` runs on CPU tensors.  The placement is ``_kv_append_model``'s, one sequence at a time, on that sequence's rotated K
+    rows.  ``lens`` / ``cu`` / ``offsets`` are host lists (``offsets`` or None); the tensors as in ``rope_append``."""
+    paged = block_table is not None
+    Smax = block_table.shape[1] * k_cache.shape[2] if paged else k_cache.shape[2]
+    total, max_pos = k_new.shape[0], cos.shape[0]
+    q_src = None if q is None else q.clone()                                   # q_out may be q
+    k_rot = k_new.clone()                                                      # rows no sequence covers stay as they are, unread
+    for b, n in enumerate(lens):
+        len_b = min(max(n, 0), Smax)
+        if cu is not None:
+            s_b = min(max(cu[b], 0), total)
+            e_b = min(max(cu[b + 1], s_b), total)
+            sq = min(e_b - s_b, max_seqlen_q)
+        else:
+            sq = max_seqlen_q
+        if sq < 1:
+            continue
+        pos = torch.arange(len_b - sq, len_b, dtype=torch.int64) + (0 if offsets is None else offsets[b])
+        pos.clamp_(0, max_pos - 1)                                             # rows in front of key 0 too: their Q is still written
+        c, s = cos[pos], sin[pos]
+        if cu is not None:
+            rows = slice(s_b, s_b + sq)
+            k_rot[rows] = _rope_rotate(k_new[rows], c, s, interleaved)
+            if q is not None:
+                q_out[rows] = _rope_rotate(q_src[rows], c, s, interleaved)
+            one = (k_rot, v_new)
+        else:
+            k_rot[b] = _rope_rotate(k_new[b].transpose(0, 1), c, s, interleaved).transpose(0, 1)
+            if q is not None:
+                q_out[b] = _rope_rotate(q_src[b].transpose(0, 1), c, s, interleaved).transpose(0, 1)
+            one = (k_rot[b:b + 1], v_new[b:b + 1])
+        caches = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
+        _kv_append_model(*one, *caches, [n], None if cu is None else [cu[b], cu[b + 1]], max_seqlen_q,
+                         block_table[b:b + 1] if paged else None)
+
+
+def _fp32_tables(rotary_cos, rotary_sin) -> None:
+    for t in (rotary_cos, rotary_sin):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("rotary_cos / rotary_sin must be fp32 tensors (the tables are not converted per call)")
+
+
+def _rotary_operands(rotary_cos, rotary_sin, D: int):
+    """What ``rope_append`` checks about its fp32 tables against head dim D.  -> ``(rot_dim, max_pos)``."""
+    if rotary_cos.dim() != 2 or rotary_sin.shape != rotary_cos.shape or rotary_cos.shape[0] < 1:
+        raise ValueError(f"rotary_cos / rotary_sin must both be [max_pos, rot_dim / 2], got {tuple(rotary_cos.shape)} / {tuple(rotary_sin.shape)}")
+    max_pos, half = rotary_cos.shape
+    if D % 16 or not 16 <= D <= 256:
+        raise ValueError(f"head dim {D}: rope_append takes a multiple of 16 in 16 .. 256")
+    if (2 * half) % 16 or not 16 <= 2 * half <= D:
+        raise ValueError(f"rot_dim {2 * half}: must be a multiple of 16 in 16 .. {D}, the head dim")
+    if rotary_cos.stride(1) != 1 or rotary_sin.stride() != rotary_cos.stride():
+        raise ValueError("rotary_cos / rotary_sin: the last dim must be contiguous and the two row strides equal")
+    return 2 * half, max_pos
+
+
+def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
+                rotary_cos: torch.Tensor, rotary_sin: torch.Tensor, q: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None,
+                rotary_interleaved: bool = False, pos_offsets: Optional[torch.Tensor] = None,
+                cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None,
+                block_table: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Rotary embedding fused into the KV-cache append (``pfa_rope_append``): ``kv_append`` that also rotates the step's Q and new K rows
+    by each row's position -- flash-attn's ``flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=, rotary_interleaved=)``.
+
+    k_new / v_new, the caches, ``block_table``, ``cache_seqlens`` (the lengths AFTER the step), ``cu_seqlens_q`` and ``max_seqlen_q`` are
+    ``kv_append``'s, with D a multiple of 16 in 16 .. 256.  New row i of sequence b belongs to logical key ``pos = len_b - Sq_b + i`` and
+    is rotated at position ``clamp(pos + pos_offsets[b], 0, max_pos - 1)`` (``pos_offsets``: optional int32 ``[B]``, for a cache whose
+    leading tokens were evicted or left-padded; an out-of-range position gives wrong numbers, never an address outside the tables).
+    rotary_cos / rotary_sin: fp32 ``[max_pos, rot_dim / 2]`` (``rotary_tables``), rot_dim a multiple of 16 in 16 .. D; elements at and
+    past rot_dim are copied.  The pair is ``(x[j], x[j + rot_dim / 2])`` -- Hugging Face's ``rotate_half``, NeoX, Llama -- or with
+    ``rotary_interleaved`` ``(x[2j], x[2j + 1])`` (GPT-J), and ``y1 = x1 * cos - x2 * sin``, ``y2 = x2 * cos + x1 * sin`` with each
+    product and the add / subtract rounded to fp32 separately, then once to the dtype.
+
+    The rotated K goes where ``kv_append`` would put the row, with its drops; V is copied there.  q (optional): ``[total, H, D]`` with
+    ``cu_seqlens_q``, else ``[B, H, Sq, D]``; every row a sequence covers is rotated into ``q_out``, which is returned: the given
+    tensor (``q_out is q``: in place), or a fresh one in the layout the attention calls prefer, of which the packed rows no sequence
+    covers are not written.  Without q, None.
+
+    On device tensors one launch of a HIP kernel whose grid depends on host shapes only: no host synchronisation, capturable, and
+    valid while cu_seqlens_q, lengths, offsets, tables and inputs change between replays.  On CPU tensors the same rule runs in plain
+    torch, bit for bit (``_rope_append_model``, the executable specification)."""
+    _fp32_tables(rotary_cos, rotary_sin)
+    others = [rotary_cos, rotary_sin] + [t for t in (q, q_out, pos_offsets) if isinstance(t, torch.Tensor)]
+    geo = _append_operands("pfa_rope_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others)
+    ragged, B, Hkv, D, total, max_seqlen_q = geo[:6]
+    rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, D)
+    if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
+                                    or pos_offsets.shape != (B,) or not pos_offsets.is_contiguous()):
+        raise ValueError("pos_offsets must be a contiguous int32 [B] tensor")
+    H = 0
+    if q is None:
+        if q_out is not None:
+            raise ValueError("q_out without q")
+    else:
+        H = q.shape[1] if q.dim() >= 2 else 0
+        want = (total, H, D) if ragged else (B, H, max_seqlen_q, D)
+        if q.shape != want or H < 1:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_new {tuple(k_new.shape)}: q must be "
+                             + ("[total, H, D]" if ragged else "[B, H, Sq, D]") + " over k_new's rows and head dim")
+        if q.dtype != k_new.dtype:
+            raise ValueError("q must have k_new's dtype")
+        if q_out is None:
+            q_out = torch.empty(want, dtype=q.dtype, device=q.device) if ragged else \
+                torch.empty((B, max_seqlen_q, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        elif q_out.shape != q.shape or q_out.dtype != q.dtype:
+            raise ValueError("q_out must have q's shape and dtype")
+    if k_new.device.type == "cpu":
+        _rope_append_model(k_new, v_new, k_cache, v_cache, rotary_cos, rotary_sin, cache_seqlens.tolist(),
+                           cu_seqlens_q.tolist() if ragged else None, max_seqlen_q, block_table,
+                           None if pos_offsets is None else pos_offsets.tolist(), bool(rotary_interleaved), q, q_out)
+        return q_out
+    a = _append_args(_capi.make_rope_append_args, "pfa_rope_append", k_new, v_new, k_cache, v_cache, geo, cu_seqlens_q, block_table,
+                     flags=_capi.PFA_ROPE_INTERLEAVED if rotary_interleaved else 0, cos=rotary_cos.data_ptr(), sin=rotary_sin.data_ptr(),
+                     cs_stride=rotary_cos.stride(0), rot_dim=rot_dim, max_pos=max_pos, H=H)
+    if pos_offsets is not None:
+        a.pos_offsets = pos_offsets.data_ptr()
+    if q is not None:
+        if any(t.stride(-1) != 1 for t in (q, q_out)):
+            raise ValueError("last (head_dim) stride must be 1")
+        a.q, a.q_out = q.data_ptr(), q_out.data_ptr()
+        if ragged:
+            a.q_stride_s, a.q_stride_h, a.qo_stride_s, a.qo_stride_h = q.stride(0), q.stride(1), q_out.stride(0), q_out.stride(1)
+        else:
+            (a.q_stride_b, a.q_stride_h, a.q_stride_s), (a.qo_stride_b, a.qo_stride_h, a.qo_stride_s) = q.stride()[:3], q_out.stride()[:3]
+    _append_launch("pfa_rope_append", a, cache_seqlens, k_new, B)
+    return q_out
+
+
+def _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens):
+    """The rotary keywords of the attention calls over a KV cache: None without them, else what ``rope_append`` takes.  Refused before
+    anything else is looked at: one table without the other, ``rotary_interleaved`` / ``pos_offsets`` without tables, tables that are
+    not fp32, and rotary without ``k_new`` / ``v_new`` and ``cache_seqlens`` (the positions are those of the appended rows)."""
+    if rotary_cos is None and rotary_sin is None:
+        if rotary_interleaved or pos_offsets is not None:
+            raise ValueError("rotary_interleaved / pos_offsets need rotary_cos and rotary_sin")
+        return None
+    if rotary_cos is None or rotary_sin is None:
+        raise ValueError("rotary_cos and rotary_sin go together")
+    _fp32_tables(rotary_cos, rotary_sin)
+    if k_new is None or v_new is None or cache_seqlens is None:
+        raise ValueError("rotary_cos / rotary_sin need k_new, v_new and cache_seqlens: rows are rotated at the positions they are appended at")
+    return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets)
+
+
+def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=None, rotary=None, **ragged):
+    """The ``k_new=, v_new=`` form of the calls over a KV cache: ``kv_append`` enqueued in front of the attention launch, on the
+    same stream, with the same lengths, ``cu_seqlens_q`` and table.  With ``rotary`` (``_rotary_kw``) it is ``rope_append`` instead, and
+    q rotated into a fresh buffer is returned; otherwise None."""
+    if k_new is None and v_new is None:
+        return None
     if k_new is None or v_new is None:
         raise ValueError("k_new and v_new go together")
     if cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
+    if rotary is not None:
+        return rope_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, q=q, **rotary, **ragged)
     kv_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, **ragged)
+    return None
 
 
-def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, **ragged):
+def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, **ragged):
     """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
     ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
-    the current stream right behind it, the status, and the kept tensors' hold on the stream.  -> lse or None."""
+    the current stream right behind it, the status, and the kept tensors' hold on the stream.  With ``rotary`` the launch reads the
+    rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
-    _append_first(*new_rows, **ragged)
+    q_rot = _append_first(*new_rows, q=q, rotary=rotary, **ragged)
+    if q_rot is not None:
+        a.q = q_rot.data_ptr()
+        if q_rot.dim() == 3:
+            a.q_stride_s, a.q_stride_h = q_rot.stride(0), q_rot.stride(1)
+        else:
+            a.q_stride_b, a.q_stride_h, a.q_stride_s = q_rot.stride()[:3]
+        keep.append(q_rot)
     stream = torch.cuda.current_stream(q.device)
     st = getattr(_capi.load(), entry + "_ex")(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
@@ -723,7 +931,9 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
                out: Optional[torch.Tensor] = None,
                block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
-               k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+               rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+               pos_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -750,8 +960,13 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
 
     ``k_new=, v_new=`` (``[B,Hkv,Sq,D]``; needs ``cache_seqlens``, the lengths after the step): ``kv_append`` of these rows is enqueued on the
     same stream in front of the attention launch, with the same lengths and table -- flash-attn's ``flash_attn_with_kvcache(k=, v=)``.
-    ``None``: nothing is appended."""
+    ``None``: nothing is appended.
+
+    ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
+    need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
+    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified."""
     ext = _window_ext(window, causal)
+    rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     if k_new is not None and cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
@@ -776,7 +991,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
         keep.append(ws)
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), max_seqlen_q=Sq)
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, max_seqlen_q=Sq)
     return out, lse
 
 
@@ -784,7 +999,9 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                       causal: bool = True, softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
                       return_lse: bool = False, out: Optional[torch.Tensor] = None,
                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
-                      k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+                      rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+                      pos_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
@@ -806,13 +1023,18 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 
     ``k_new=, v_new=`` (``[B,Hkv,Sq,D]``; needs ``cache_seqlens``, the lengths after the step): ``kv_append`` of these rows is enqueued on the
     same stream in front of the attention launch, with the same lengths and table -- flash-attn's ``flash_attn_with_kvcache(k=, v=)``.
-    ``None``: nothing is appended."""
+    ``None``: nothing is appended.
+
+    ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
+    need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
+    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified."""
     ext = _window_ext(window, causal)
+    rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
     lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), max_seqlen_q=q.shape[2])
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, max_seqlen_q=q.shape[2])
     return out, lse
 
 
@@ -820,7 +1042,9 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                        cache_seqlens: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                        out_dtype: Optional[torch.dtype] = None, return_lse: bool = False, out: Optional[torch.Tensor] = None,
                        block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
-                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+                       rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+                       pos_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen_ex``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
     verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
@@ -844,8 +1068,13 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
 
     ``k_new=, v_new=`` (packed ``[total_q,Hkv,D]``; needs ``cache_seqlens``, the lengths after the step): ``kv_append`` of these rows is enqueued on the
     same stream in front of the attention launch, with the same lengths, ``cu_seqlens_q``, ``max_seqlen_q`` and table -- flash-attn's ``flash_attn_with_kvcache(k=, v=)``.
-    ``None``: nothing is appended."""
+    ``None``: nothing is appended.
+
+    ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
+    need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
+    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified."""
     ext = _window_ext(window, causal)
+    rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q must be 3-D ([total_q,H,D]) and k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
     if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
@@ -879,6 +1108,6 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep, B)
     lse = _finish_cache_call("pfa_fa3_prefill_varlen", a, ext, q, (H, total_q) if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table),
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary,
                              cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
     return out, lse
