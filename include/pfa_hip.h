@@ -13,6 +13,8 @@
  * last `window` keys), with keys and block-table entries behind the window never read;
  * v9, additive: pfa_kv_append* -- the device-side append of a step's new K / V rows into a contiguous or paged cache.
  * v9, additive: pfa_rope_append* -- rotary embedding fused into that append: Q and the new K rotated by positions derived on the device.
+ * v9, additive: pfa_attn_merge* -- the merge of partial attention results (O, LSE) over disjoint key sets into the result over their
+ * union: what a shared prefix computed once per batch, a split over keys or keys spread over several GPUs need behind them.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -635,6 +637,73 @@ int pfa_rope_append(const pfa_rope_append_args* a, void* stream);
 /* Introspection: the kernel name rope_append_{bf16|fp16}_d{D}_r{rot_dim} ("_il" appended with PFA_ROPE_INTERLEAVED, then "_varlen" with
  * cu_seqlens_q, then "_paged" with a block table) into buf (NUL terminated, truncated to n); returns the workgroups, or a pfa_status. */
 int pfa_rope_append_describe(const pfa_rope_append_args* a, char* buf, size_t n);
+
+/*
+ * Merge of partial attention results (ABI v9, additive).  N attention results over DISJOINT key sets -- each an O and the natural-log LSE
+ * the calls over a KV cache return -- become the result over the union of the keys: FlashInfer's merge_state, vLLM's
+ * merge_attn_states.  For every row (b, i, h), in fp32 and in part order n = 0 .. N - 1:
+ *       m    = max_n lse_n                    over the parts whose lse_n > -inf
+ *       w_n  = exp(lse_n - m),   s = sum_n w_n
+ *       O[d] = (sum_n w_n * O_n[d]) / s,      LSE = m + log(s)
+ *   -inf            a part whose LSE is -inf (a row with no visible key there) is SKIPPED, not multiplied by zero: its O may hold
+ *                   anything, NaN included, and does not reach the result.  If every part is -inf: O = 0 and LSE = -inf, the library's
+ *                   row with no visible key.
+ *   NaN             a NaN LSE gives a NaN row (O and LSE).
+ *   rows            are independent: garbage in one input row stays in that row.
+ *   reproducible    no atomics, fixed order: two runs give the same bits.
+ *   exact           merging one finite part with parts that are all -inf returns that part's LSE bit for bit and its O bit for bit
+ *                   (fp32 output) or rounded once (16-bit output): exp(0) = 1 and log(1) = 0 are exact in the hardware
+ *                   transcendentals the kernel uses, and it divides by s itself (no epsilon, no reciprocal).
+ *
+ *   n_parts         N, 2 <= N <= PFA_MERGE_MAX_PARTS.  Array entries at and past N are ignored.
+ *   o_part[n]       [B, Sq, H, D] by element strides op_stride_b / _h / _s[n] (last dim contiguous), dtype_part (one for all parts:
+ *                   bf16, fp16 or fp32).
+ *   lse_part[n]     fp32, entry (b, h, i) at lp_stride_b[n] * b + lp_stride_h[n] * h + lp_stride_s[n] * i.  Any strides: the parts of
+ *                   one merge come from calls with different layouts -- [B, H, Sq]; one call over all B * Sq rows as one sequence,
+ *                   [1, H, B * Sq] (strides Sq, B * Sq, 1); the ragged call's [H, total_q] (B = 1, Sq = total_q).
+ *   o               [B, Sq, H, D] by element strides, dtype_out: bf16, fp16 or fp32; with 16-bit parts dtype_part or fp32.  16-bit
+ *                   output is converted round-to-nearest-even.  o must not overlap a part (undefined).
+ *   lse_out         optional fp32 by lo_stride_b / _h / _s, as lse_part; NULL: not written.
+ * Nothing but the B * Sq * H rows of o and lse_out is written.
+ *
+ * One launch of a memory-bound kernel: ceil(B * Sq * H * (D / 8) / 256) workgroups from host shapes only, so a captured graph stays
+ * valid while the tensors' contents change.  No workspace, no LDS.
+ *
+ * Field rules, in the order their errors are reported: size wrong -> PFA_ERR_STRUCT_SIZE; flags / reserved0 / reserved1 non-zero ->
+ * PFA_ERR_FLAGS; o, or o_part[n] / lse_part[n] of a part n < min(n_parts, PFA_MERGE_MAX_PARTS), NULL -> PFA_ERR_NULL; n_parts outside
+ * [2, PFA_MERGE_MAX_PARTS], B, H or Sq < 1 -> PFA_ERR_SHAPE; D not a multiple of 8 in [8, 256] -> PFA_ERR_HEAD_DIM; dtype_part or
+ * dtype_out not bf16 / fp16 / fp32, or 16-bit parts with a dtype_out that is neither dtype_part nor fp32 -> PFA_ERR_DTYPE; an op_stride
+ * or o_stride not a multiple of 8 elements (16-bit tensor) or of 4 (fp32 tensor) -> PFA_ERR_STRIDE; o or an o_part not 16-byte aligned,
+ * lse_out or an lse_part not 4-byte aligned -> PFA_ERR_ALIGN; B * Sq * H * (D / 8) + 256 past 2^31 - 1 (the grid and the item index) ->
+ * PFA_ERR_SHAPE.
+ */
+#define PFA_MERGE_MAX_PARTS 8
+
+typedef struct pfa_attn_merge_args {
+    uint32_t size;              /* = sizeof(pfa_attn_merge_args) */
+    uint32_t flags;             /* must be 0 */
+    const void*  o_part[PFA_MERGE_MAX_PARTS];
+    const float* lse_part[PFA_MERGE_MAX_PARTS];
+    void*        o;
+    float*       lse_out;       /* optional */
+    int64_t op_stride_b[PFA_MERGE_MAX_PARTS], op_stride_h[PFA_MERGE_MAX_PARTS], op_stride_s[PFA_MERGE_MAX_PARTS];
+    int64_t lp_stride_b[PFA_MERGE_MAX_PARTS], lp_stride_h[PFA_MERGE_MAX_PARTS], lp_stride_s[PFA_MERGE_MAX_PARTS];
+    int64_t o_stride_b, o_stride_h, o_stride_s;
+    int64_t lo_stride_b, lo_stride_h, lo_stride_s;
+    int32_t n_parts, B, H, Sq, D;
+    int32_t dtype_part;         /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 | PFA_DTYPE_FP32, of every o_part */
+    int32_t dtype_out;          /* any of the three; with 16-bit parts: = dtype_part, or PFA_DTYPE_FP32 */
+    int32_t device_id;
+    int32_t reserved0, reserved1;   /* must be 0 */
+} pfa_attn_merge_args;
+
+/* Validate `a` without launching: PFA_OK or the error pfa_attn_merge would return. */
+int pfa_attn_merge_check(const pfa_attn_merge_args* a);
+/* Enqueue the merge (one launch) on `stream`. */
+int pfa_attn_merge(const pfa_attn_merge_args* a, void* stream);
+/* Introspection: the kernel name attn_merge_{bf16|fp16|fp32}_{bf16|fp16|fp32}_d{D}_n{N} (part dtype, then output dtype) into buf (NUL
+ * terminated, truncated to n); returns the workgroups, or a pfa_status. */
+int pfa_attn_merge_describe(const pfa_attn_merge_args* a, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

@@ -18,6 +18,7 @@ PFA_DTYPE_BF16, PFA_DTYPE_FP16, PFA_DTYPE_FP32 = 0, 1, 2
 PFA_FLAG_SPLIT_P = 0x1
 PFA_FLAG_NO_XCD_MAP = 0x2
 PFA_ROPE_INTERLEAVED = 0x1
+PFA_MERGE_MAX_PARTS = 8
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, "libpfa_hip.so")
@@ -120,11 +121,23 @@ class PfaRopeAppendArgs(C.Structure):
     )
 
 
+class PfaAttnMergeArgs(C.Structure):
+    """Mirror of ``struct pfa_attn_merge_args`` (include/pfa_hip.h): the merge of partial attention results."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [("o_part", C.c_void_p * PFA_MERGE_MAX_PARTS), ("lse_part", C.c_void_p * PFA_MERGE_MAX_PARTS)]
+        + [("o", C.c_void_p), ("lse_out", C.c_void_p)]
+        + [(f"{t}_stride_{a}", C.c_int64 * PFA_MERGE_MAX_PARTS) for t in ("op", "lp") for a in "bhs"]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in ("o", "lo") for a in "bhs"]
+        + [(n, C.c_int32) for n in ("n_parts", "B", "H", "Sq", "D", "dtype_part", "dtype_out", "device_id", "reserved0", "reserved1")]
+    )
+
+
 def _prototypes():
     """Export name -> ``(restype, argtypes)``, one row per symbol ``include/pfa_hip.h`` declares (argtypes None: left untyped)."""
     i, sz, vp, buf = C.c_int, C.c_size_t, C.c_void_p, [C.c_char_p, C.c_size_t]
-    fa3, bwd, dec, var, app, ext, rope = (C.POINTER(t) for t in (PfaFa3Args, PfaFa3BwdArgs, PfaFa3DecodeArgs, PfaFa3PrefillVarlenArgs,
-                                                                 PfaKvAppendArgs, PfaFa3CacheExt, PfaRopeAppendArgs))
+    fa3, bwd, dec, var, app, ext, rope, mrg = (C.POINTER(t) for t in (PfaFa3Args, PfaFa3BwdArgs, PfaFa3DecodeArgs, PfaFa3PrefillVarlenArgs,
+                                                                      PfaKvAppendArgs, PfaFa3CacheExt, PfaRopeAppendArgs, PfaAttnMergeArgs))
     ns = [C.POINTER(C.c_int32)]
     return {
         "pfa_abi_version": (i, None),
@@ -167,6 +180,9 @@ def _prototypes():
         "pfa_rope_append_check": (i, [rope]),
         "pfa_rope_append": (i, [rope, vp]),
         "pfa_rope_append_describe": (i, [rope] + buf),
+        "pfa_attn_merge_check": (i, [mrg]),
+        "pfa_attn_merge": (i, [mrg, vp]),
+        "pfa_attn_merge_describe": (i, [mrg] + buf),
     }
 
 
@@ -311,3 +327,20 @@ def describe_rope_append(args: PfaRopeAppendArgs):
     """-> (kernel name, workgroups) of ``pfa_rope_append``: ``B * ceil(max_seqlen_q * (H + 2 * Hkv) * (D / 16) / 256)``, from host
     shapes only."""
     return _describe("pfa_rope_append_describe", args)
+
+
+def make_attn_merge_args(**kw) -> PfaAttnMergeArgs:
+    """A zeroed ``pfa_attn_merge_args``; the per-part arrays (``o_part``, ``lse_part``, ``op_stride_*``, ``lp_stride_*``) are given as
+    sequences of up to ``PFA_MERGE_MAX_PARTS`` values."""
+    a = _make(PfaAttnMergeArgs, {k: v for k, v in kw.items() if not isinstance(v, (list, tuple))})
+    for k, v in kw.items():
+        if isinstance(v, (list, tuple)):
+            arr = getattr(a, k)
+            for n, x in enumerate(v):
+                arr[n] = x
+    return a
+
+
+def describe_attn_merge(args: PfaAttnMergeArgs):
+    """-> (kernel name, workgroups) of ``pfa_attn_merge``: ``ceil(B * Sq * H * (D / 8) / 256)``, from host shapes only."""
+    return _describe("pfa_attn_merge_describe", args)

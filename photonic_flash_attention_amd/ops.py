@@ -926,6 +926,164 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     return lse
 
 
+def _attn_merge_model(outs, lses, out, lse_out) -> None:
+    """``pfa_attn_merge``'s rule in plain fp32 torch ops, in part order: the executable specification, and what ``attn_merge`` runs on
+    CPU tensors.  A part whose LSE is -inf is selected away, never multiplied in; a NaN LSE makes the row NaN."""
+    neg_inf = float("-inf")
+    L = torch.stack([l.to(torch.float32) for l in lses])                      # [N, B, H, Sq]
+    live = L > neg_inf                                                        # False for -inf and for NaN
+    m = torch.where(live, L, torch.full_like(L, neg_inf)).max(dim=0).values
+    s = torch.zeros_like(m)
+    acc = torch.zeros(outs[0].shape, dtype=torch.float32, device=m.device)
+    for n, o_n in enumerate(outs):
+        w = torch.exp(L[n] - m)
+        s = torch.where(live[n], s + w, s)
+        acc = torch.where(live[n][..., None], acc + w[..., None] * o_n.to(torch.float32), acc)
+    none = ~(m > neg_inf)                                                     # no part with a visible key
+    o = torch.where(none[..., None], torch.zeros_like(acc), acc / s[..., None])
+    lse = torch.where(none, torch.full_like(m, neg_inf), m + torch.log(s))
+    nan = torch.isnan(L).any(dim=0)
+    o = torch.where(nan[..., None], torch.full_like(o, float("nan")), o)
+    lse = torch.where(nan, torch.full_like(lse, float("nan")), lse)
+    out.copy_(o)                                                              # 16-bit: round to nearest even
+    if lse_out is not None:
+        lse_out.copy_(lse)
+
+
+def attn_merge(outs, lses, *, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+               return_lse: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Merge of partial attention results (``pfa_attn_merge``): N results over DISJOINT key sets -- each an O and the natural-log LSE
+    the calls over a KV cache return -- into the result over the union of the keys (FlashInfer's ``merge_state``, vLLM's
+    ``merge_attn_states``).  For every row, in fp32 and in part order::
+
+        m = max_n lse_n  (over the parts with lse_n > -inf)     w_n = exp(lse_n - m)     s = sum_n w_n
+        O = (sum_n w_n * O_n) / s                               LSE = m + log(s)
+
+    outs: 2 .. 8 ``[B,H,Sq,D]``-shaped views of one dtype (bf16, fp16 or fp32; any strides, head dim contiguous, D a multiple of 8 up
+    to 256) -- the layout the cache calls return.  lses: as many ``[B,H,Sq]``-shaped fp32 views, ANY strides: the LSE of one call over
+    all ``B * Sq`` rows as one sequence goes in as ``lse.view(H, B, Sq).transpose(0, 1)`` without a copy.  The result has ``out_dtype``
+    (default: the parts' dtype; 16-bit parts give their own dtype or fp32, fp32 parts any of the three; 16-bit output is rounded to
+    nearest even) or is written into ``out`` (``[B,H,Sq,D]``-shaped, not overlapping a part).  Returns ``(o, lse [B,H,Sq] or None)``.
+
+    A part whose LSE is -inf (a row that saw no key there) is skipped, not multiplied by zero: its O may hold anything, NaN included.
+    If every part is -inf the row is O = 0, LSE = -inf, the calls' own "row with no visible key".  A NaN LSE gives a NaN row.  Rows
+    are independent.  Merging one finite part with parts that are all -inf returns that part's LSE bit for bit and its O bit for bit
+    (fp32 output) or rounded once (16-bit output).  Fixed order, no atomics: two runs give the same bits.
+
+    On device tensors one launch of a memory-bound HIP kernel on the current stream, its grid from host shapes only: no host
+    synchronisation, no workspace, no cached allocation, capturable in ``torch.cuda.graph``.  On CPU tensors the same rule runs in plain
+    fp32 torch ops (``_attn_merge_model``, the executable specification)."""
+    outs, lses = list(outs), list(lses)
+    N = len(outs)
+    if not 2 <= N <= _capi.PFA_MERGE_MAX_PARTS or len(lses) != N:
+        raise ValueError(f"attn_merge takes 2 .. {_capi.PFA_MERGE_MAX_PARTS} parts and as many LSEs, got {N} and {len(lses)}")
+    o0 = outs[0]
+    if any(not isinstance(t, torch.Tensor) for t in outs + lses) or o0.dim() != 4:
+        raise ValueError("outs must be [B,H,Sq,D]-shaped tensors and lses [B,H,Sq]-shaped tensors")
+    B, H, Sq, D = o0.shape
+    if o0.dtype not in _DT or any(t.shape != o0.shape or t.dtype != o0.dtype for t in outs):
+        raise ValueError("outs must share one shape and one dtype, bf16, fp16 or fp32")
+    if any(t.shape != (B, H, Sq) or t.dtype != torch.float32 for t in lses):
+        raise ValueError(f"lses must be fp32 [B,H,Sq] = {(B, H, Sq)}-shaped views")
+    if D % 8 or not 8 <= D <= 256:
+        raise ValueError(f"head dim {D}: attn_merge takes a multiple of 8 in 8 .. 256")
+    if min(B, H, Sq) < 1:
+        raise ValueError(f"attn_merge: empty shape {tuple(o0.shape)}")
+    if out is not None and not isinstance(out, torch.Tensor):
+        raise ValueError("out must be a tensor")
+    odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else o0.dtype)
+    if odt not in _DT or (o0.dtype != torch.float32 and odt not in (o0.dtype, torch.float32)):
+        raise ValueError("output dtype must be bf16, fp16 or fp32, and with 16-bit parts the parts' dtype or fp32")
+    dev = o0.device
+    if any(t.device != dev for t in outs + lses) or (out is not None and out.device != dev):
+        raise ValueError("attn_merge needs all its tensors on one device")
+    if out is None:
+        out = torch.empty((B, Sq, H, D), dtype=odt, device=dev).permute(0, 2, 1, 3)
+    elif out.shape != o0.shape or out.dtype != odt:
+        raise ValueError("out must be a [B, H, Sq, D] tensor of the output dtype")
+    lse_out = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    if dev.type == "cpu":
+        _attn_merge_model(outs, lses, out, lse_out)
+        return out, lse_out
+    if dev.type != "cuda":
+        raise ValueError("attn_merge needs device tensors (or CPU tensors for the torch model)")
+    ostr = [_bhsd_strides(t) for t in outs]
+    os_ = _bhsd_strides(out)
+    a = _capi.make_attn_merge_args(
+        n_parts=N, B=B, H=H, Sq=Sq, D=D, dtype_part=_DT[o0.dtype], dtype_out=_DT[odt], device_id=_device_index(dev),
+        o_part=[t.data_ptr() for t in outs], lse_part=[t.data_ptr() for t in lses], o=out.data_ptr(),
+        op_stride_b=[x[0] for x in ostr], op_stride_h=[x[1] for x in ostr], op_stride_s=[x[2] for x in ostr],
+        lp_stride_b=[t.stride(0) for t in lses], lp_stride_h=[t.stride(1) for t in lses], lp_stride_s=[t.stride(2) for t in lses],
+        o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2])
+    if lse_out is not None:
+        a.lse_out = lse_out.data_ptr()
+        a.lo_stride_b, a.lo_stride_h, a.lo_stride_s = lse_out.stride()
+    st = _capi.load().pfa_attn_merge(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    _raise_status("pfa_attn_merge", st, null_too=True)
+    return out, lse_out
+
+
+def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *, cache_seqlens, key_mask, window, causal, softmax_scale,
+                        out_dtype, return_lse, out, block_table, k_new, v_new, rotary):
+    """``shared_prefix=P`` of ``fa3_decode`` / ``fa3_prefill_cache`` (``call``; ``entry`` names its C entry point in the messages): the
+    attention cut at logical key P.  All ``B * Sq`` rows go as ONE sequence against sequence 0's first P keys (``causal=False``; every
+    row lies behind the prefix), each sequence goes against its own keys from P on (``call`` unchanged on the cache view that starts
+    at P, lengths ``max(len_b - P, 0)``), and ``attn_merge`` joins the two fp32 parts through their LSEs into the caller's ``out`` /
+    ``out_dtype``.  The optional append runs once, first, on the whole cache, and both passes read the rotated q.  Everything is
+    enqueued on the current stream with no host synchronisation; every ``ValueError`` is raised before the first launch."""
+    try:
+        P = None if isinstance(shared_prefix, bool) else operator.index(shared_prefix)
+    except TypeError:
+        P = None
+    if P is None:
+        raise ValueError(f"shared_prefix must be None or a host integer, got {shared_prefix!r}")
+    if key_mask is not None or window is not None:
+        raise ValueError("shared_prefix does not combine with key_mask or window: their indices are over the unshifted keys")
+    if cache_seqlens is None:
+        raise ValueError("shared_prefix needs cache_seqlens: each sequence's own keys are those from the prefix up to its length")
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    B, H, Sq, D = q.shape
+    Hkv = k_cache.shape[1]
+    Smax, page_size, _ = _cache_geometry("q", q, B, Hkv, D, k_cache, v_cache, block_table, H)
+    if P < 64 or P % 64:
+        raise ValueError(f"shared_prefix {P}: must be a positive multiple of 64 keys")
+    if block_table is not None and P % page_size:
+        raise ValueError(f"shared_prefix {P}: with a block table it must be a multiple of the page size {page_size}")
+    if P >= Smax:
+        raise ValueError(f"shared_prefix {P}: must be below the cache capacity {Smax} (the sequences' own keys lie behind it)")
+    if entry == "pfa_fa3_decode" and Sq > 64:
+        raise ValueError(f"{entry}: at most 64 query rows per sequence, got {Sq} (fa3_prefill_cache takes any number)")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.device != q.device or cache_seqlens.shape != (B,):
+        raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
+    odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table)[4]
+    if out is not None and (out.shape != (B, H, Sq, D) or out.dtype != odt or out.device != q.device):
+        raise ValueError("out must be a [B, H, Sq, D] tensor of the output dtype on the operands' device")
+
+    q_rot = _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=q, rotary=rotary, max_seqlen_q=Sq)
+    if q_rot is not None:
+        q = q_rot
+    rows = B * Sq
+    # the prefix pass: B' = 1, Sq' = B * Sq.  A view when q's batch stride is Sq token strides (the layout the calls return), else one copy
+    q_all = q.transpose(1, 2).reshape(1, rows, H, D).transpose(1, 2)
+    if block_table is None:
+        pre = (k_cache[:1, :, :P], v_cache[:1, :, :P], None)
+        own = (k_cache[:, :, P:], v_cache[:, :, P:], None)
+    else:
+        pre = (k_cache, v_cache, block_table[:1, :P // page_size])
+        own = (k_cache, v_cache, block_table[:, P // page_size:])              # the row stride stays
+    # the decode kernel packs a K/V head's rows and splits the keys over workgroups: it fills the chip at few rows; past 64 the MFMA forward.
+    # No length tensor: the prefix views hold exactly P keys, and without cache_seqlens the kernels take the capacity.
+    prefix_call = fa3_decode if rows <= 64 else fa3_prefill_cache
+    o_pre, lse_pre = prefix_call(q_all, pre[0], pre[1], block_table=pre[2], causal=False, softmax_scale=softmax_scale,
+                                 out_dtype=torch.float32, return_lse=True)
+    own_lens = (cache_seqlens.to(torch.int32) - P).clamp_(min=0)
+    o_own, lse_own = call(q, own[0], own[1], block_table=own[2], cache_seqlens=own_lens, causal=causal, softmax_scale=softmax_scale,
+                          out_dtype=torch.float32, return_lse=True)
+    return attn_merge([o_pre.transpose(1, 2).reshape(B, Sq, H, D).transpose(1, 2), o_own],
+                      [lse_pre.view(H, B, Sq).transpose(0, 1), lse_own], out=out, out_dtype=odt, return_lse=return_lse)
+
+
 def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                key_mask: Optional[torch.Tensor] = None, causal: bool = True, softmax_scale: Optional[float] = None,
                out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
@@ -933,7 +1091,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-               pos_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -964,9 +1122,33 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
 
     ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
     need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
-    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified."""
+    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified.
+
+    ``shared_prefix=P`` (a host integer; ``None``: the call above, unchanged): the caller promises that (a) the first P logical keys of
+    every sequence have the same contents -- with a block table normally the same page ids -- and (b) every row of the step lies
+    behind the prefix, ``len_b - Sq >= P``.  The attention is then cut at key P: all ``B * Sq`` rows go as one sequence against sequence
+    0's first P keys (``fa3_decode`` up to 64 rows, else ``fa3_prefill_cache``; the prefix is streamed once instead of B times), each
+    sequence goes against its own keys from P on, and ``attn_merge`` joins the two fp32 parts through their LSEs into ``out`` /
+    ``out_dtype`` (and the merged LSE).  ``k_new`` / ``v_new`` and rotary run once, first, as above.  P must be a multiple of 64, with a
+    block table of the page size, and below Smax; ``cache_seqlens`` is required; ``key_mask`` and ``window`` do not combine with it (their
+    indices are over the unshifted keys).  All of these raise ``ValueError`` before anything is enqueued.  A broken promise gives wrong
+    numbers, never a wrong address: every clamp of the underlying calls stays in force.  No host synchronisation: the whole step
+    (append, prefix pass, own-keys pass, merge) is capturable and replays while lengths, table and cache contents change.
+
+    When it pays (one MI355X, H 32 / Hkv 8, D 128, 256 private keys, ``profiles/shared_prefix.md``): the step is two attention calls
+    and a merge instead of one call, so a captured step costs about 40 us at the least against 25 us.  With the prefix in shared
+    pages -- where the plain call already gets its B re-reads from L2 / the Infinity Cache -- a captured step wins from B 32 at
+    P 8192 (1.5 x) and from B 8 at P 32768 (1.4 x; 2.5 x at B 32), and loses at P 2048 for every B (0.64 - 0.94) and at B 8, P 8192
+    (0.77).  When every sequence holds its own copy of the prefix it wins 1.25 - 5.6 x from B 32 at P 2048 and from B 8 at P 8192.
+    Eager calls add a host floor of about 100 us per step and win only where the plain call is slower than that (B 32 at P 32768):
+    capture the step.  Past ``B * Sq`` = 64 rows the prefix pass is the MFMA forward over ONE sequence, 32 - 64 workgroups with no
+    split over keys, and the gain shrinks to 1.1 - 1.2 x (B 128; Sq 16 at B 32) until that pass gets a split over keys."""
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
+    if shared_prefix is not None:
+        return _shared_prefix_step(fa3_decode, "pfa_fa3_decode", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
+                                   key_mask=key_mask, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
+                                   return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary)
     if k_new is not None and cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
@@ -1001,7 +1183,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                       rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-                      pos_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
@@ -1027,9 +1209,20 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 
     ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
     need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
-    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified."""
+    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified.
+
+    ``shared_prefix=P``: as in ``fa3_decode`` -- the first P keys of every sequence are the same and every row lies behind them
+    (``len_b - Sq >= P``); all ``B * Sq`` rows go once against sequence 0's first P keys, each sequence against its own keys from P on
+    with ``causal`` as given, and ``attn_merge`` joins the two.  Same restrictions (a multiple of 64 and of the page size, below Smax,
+    ``cache_seqlens`` required, no ``window``), raised as ``ValueError`` before anything is enqueued.  Past 64 rows the prefix pass is
+    this call over one sequence of ``B * Sq`` rows, H * ceil(B * Sq / 256) workgroups with no split over keys.  Measured so far
+    (``profiles/shared_prefix.md``): the 512-row speculative step through ``fa3_decode``, 1.09 x shared pages, 2.3 x own copies."""
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
+    if shared_prefix is not None:
+        return _shared_prefix_step(fa3_prefill_cache, "pfa_fa3_prefill", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
+                                   key_mask=None, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
+                                   return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary)
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
