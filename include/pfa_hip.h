@@ -334,7 +334,8 @@ int pfa_fa3_decode_describe(const pfa_fa3_decode_args* a, char* buf, size_t n, i
  * ceil(cache_seqlens[b] / page_size) never read, a row with no visible key -> O = 0 and LSE = -inf) and the same field rules, except:
  *   - Sq is any value >= 1 (B * H * ceil(Sq / 256) workgroups, up to the grid limit);
  *   - key_mask must be NULL (PFA_ERR_FLAGS): key masks over the cache are out of scope here, pfa_fa3_decode takes them;
- *   - workspace / workspace_bytes are ignored: there is no split over keys, one launch, no atomics (bitwise reproducible).
+ *   - workspace / workspace_bytes are ignored: this call does not split the keys (pfa_fa3_prefill_split below does), one launch, no
+ *     atomics (bitwise reproducible).
  * Keys at and past cache_seqlens[b] are never read (a cache's unfilled tail may hold anything, NaN included).  The grid depends on
  * shapes only, so a captured graph stays valid while lengths, table and cache change between replays.  A paged call returns the bits of
  * the contiguous call on the gathered cache.
@@ -462,6 +463,55 @@ int pfa_fa3_prefill_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cach
 int pfa_fa3_prefill_varlen_check_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext);
 int pfa_fa3_prefill_varlen_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, void* stream);
 int pfa_fa3_prefill_varlen_describe_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n);
+
+/*
+ * Forward over a KV cache with the keys split over workgroups (ABI v9, additive).  pfa_fa3_prefill launches B * H * ceil(Sq / 256)
+ * workgroups and each walks every key its rows see: a short chunk of few sequences against a long cache (chunked prefill at B = 1, the
+ * prefix pass of a shared-prefix step) leaves most of the chip idle.  These entry points take the unchanged pfa_fa3_decode_args plus a host
+ * integer (pfa_fa3_cache_ext is full), cut every q block's keys into N ranges, run one workgroup per range and join the N fp32 partial
+ * results with pfa_attn_merge.  Same conventions and field rules as pfa_fa3_prefill; there is no window and no ragged form.
+ *
+ *   key_splits      1 .. PFA_PREFILL_MAX_SPLITS: exactly that many splits.  0: the library's plan.  Anything else: PFA_ERR_SHAPE.
+ *   the plan        pfa_fa3_prefill_split_plan returns the resolved count N in 1 .. 8 (or a negative pfa_status): key_splits itself, or for
+ *                   0 the largest N that keeps B * H * ceil(Sq / 256) * N within 256 workgroups (one round of one D = 128 workgroup per
+ *                   CU), capped by Smax / 1024 (a split holds at least 1024 keys of capacity) and by 8, and at least 1.  It is 1 when
+ *                   B * H * ceil(Sq / 256) > 128 and when Smax is below 2048.  A function of (B, H, Sq, Smax, D) only -- never of
+ *                   pointers, cache_seqlens, the block table or the page size -- so a captured graph stays valid while they change
+ *                   and a paged call plans like the contiguous one.
+ *   N = 1           the call IS pfa_fa3_prefill: the same kernel function, grid, field rules and bits.  No workspace (0 bytes; the
+ *                   workspace fields are ignored).
+ *   N > 1           one launch of B * H * ceil(Sq / 256) * N workgroups into `workspace`, then pfa_attn_merge of the N parts, in split
+ *                   order, into o (dtype_out) and the optional lse.  Two launches, fixed order, no atomics (bitwise reproducible), no
+ *                   host synchronisation, no allocation; both grids come from host shapes, so the pair is capturable.
+ *   the split rule  a q block (256 rows) that would run n 64-key tiles unsplit -- n = ceil(len_b / 64), under causal
+ *                   ceil(min(len_b, q0 + 256 + len_b - Sq) / 64) for the block whose first row is q0 -- gives split s the tiles
+ *                   [s * per, min(n, (s + 1) * per)), per = ceil(n / N).  An empty range fetches nothing and contributes a part whose
+ *                   LSE is -inf, which the merge skips.  The partial result of split s is bit for bit the fp32 result (and LSE) of
+ *                   pfa_fa3_prefill over those keys alone, so the whole call equals pfa_attn_merge of N such calls.
+ *   workspace       N * B * Sq * H * (D + 1) * 4 bytes (pfa_fa3_prefill_split_workspace_bytes; 0 for N = 1 and for refused shapes), 16-byte
+ *                   aligned: partial O fp32 [N][B][Sq][H][D], then partial LSE fp32 [N][B][H][Sq].  Every byte of it is written.
+ *   never read      keys at and past len_b; table entries at and past ceil(len_b / page_size); by a given workgroup, table entries
+ *                   outside its own tiles (a split may begin in the middle of a page; page ids are clamped as always).
+ * A paged call returns the bits of the contiguous call with the same N on the gathered cache.
+ *
+ * Field rules, in the order their errors are reported: those of pfa_fa3_prefill's argument block (pfa_fa3_decode_args above); key_mask set
+ * -> PFA_ERR_FLAGS; key_splits outside 0 .. 8 -> PFA_ERR_SHAPE; B * H * ceil(Sq / 256) * N past 2^31 - 1 -> PFA_ERR_SHAPE; and for N > 1:
+ * a 16-bit o whose strides are not multiples of 8 elements (the merge's rule, on top of the prefill's 4) -> PFA_ERR_STRIDE; workspace NULL or
+ * smaller than the size above -> PFA_ERR_NULL; workspace not 16-byte aligned -> PFA_ERR_ALIGN; then what pfa_attn_merge_check says of the
+ * merge (its grid: B * Sq * H * (D / 8) + 256 past 2^31 - 1 -> PFA_ERR_SHAPE).
+ */
+#define PFA_PREFILL_MAX_SPLITS 8      /* = PFA_MERGE_MAX_PARTS */
+/* The resolved number of key splits, 1 .. 8, from shapes only; or a negative pfa_status (NULL, size, shape, head dim, key_splits). */
+int pfa_fa3_prefill_split_plan(const pfa_fa3_decode_args* a, int32_t key_splits);
+/* Scratch bytes pfa_fa3_prefill_split needs for (`a`, key_splits); from shapes only.  0 for one split and for what _plan refuses. */
+size_t pfa_fa3_prefill_split_workspace_bytes(const pfa_fa3_decode_args* a, int32_t key_splits);
+/* Validate without launching: PFA_OK or the error pfa_fa3_prefill_split would return. */
+int pfa_fa3_prefill_split_check(const pfa_fa3_decode_args* a, int32_t key_splits);
+/* Enqueue the forward (one split: pfa_fa3_prefill; else the split launch and the merge launch) on `stream`. */
+int pfa_fa3_prefill_split(const pfa_fa3_decode_args* a, int32_t key_splits, void* stream);
+/* Introspection: pfa_fa3_prefill_describe's name with "_split{N}+merge" in front of any "_paged" when N > 1, the resolved N into *nsplit
+ * (may be NULL); returns the workgroups of the main launch, B * H * ceil(Sq / 256) * N, or a pfa_status. */
+int pfa_fa3_prefill_split_describe(const pfa_fa3_decode_args* a, int32_t key_splits, char* buf, size_t n, int32_t* nsplit);
 
 /*
  * Device-side KV-cache append (ABI v9, additive): the write side of a step over a KV cache.  Places the step's new K / V rows into a

@@ -19,6 +19,7 @@ PFA_FLAG_SPLIT_P = 0x1
 PFA_FLAG_NO_XCD_MAP = 0x2
 PFA_ROPE_INTERLEAVED = 0x1
 PFA_MERGE_MAX_PARTS = 8
+PFA_PREFILL_MAX_SPLITS = 8
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, "libpfa_hip.so")
@@ -174,6 +175,11 @@ def _prototypes():
         "pfa_fa3_prefill_varlen_check_ex": (i, [var, ext]),
         "pfa_fa3_prefill_varlen_ex": (i, [var, ext, vp]),
         "pfa_fa3_prefill_varlen_describe_ex": (i, [var, ext] + buf),
+        "pfa_fa3_prefill_split_plan": (i, [dec, C.c_int32]),
+        "pfa_fa3_prefill_split_workspace_bytes": (sz, [dec, C.c_int32]),
+        "pfa_fa3_prefill_split_check": (i, [dec, C.c_int32]),
+        "pfa_fa3_prefill_split": (i, [dec, C.c_int32, vp]),
+        "pfa_fa3_prefill_split_describe": (i, [dec, C.c_int32] + buf + ns),
         "pfa_kv_append_check": (i, [app]),
         "pfa_kv_append": (i, [app, vp]),
         "pfa_kv_append_describe": (i, [app] + buf),
@@ -308,6 +314,17 @@ def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
 def describe_prefill_varlen_ex(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaFa3CacheExt]):
     """``describe_prefill_varlen`` of ``pfa_fa3_prefill_varlen_ex``."""
     return _describe("pfa_fa3_prefill_varlen_describe_ex", args, ext)
+
+
+def describe_prefill_split(args: PfaFa3DecodeArgs, key_splits: int):
+    """-> (kernel name, workgroups of the main launch, resolved number of key splits) of ``pfa_fa3_prefill_split`` (``key_splits`` 0:
+    the library's plan); "_split{N}+merge" marks a split call."""
+    buf = C.create_string_buffer(128)
+    ns = C.c_int32(0)
+    n = load().pfa_fa3_prefill_split_describe(C.byref(args), int(key_splits), buf, 128, C.byref(ns))
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n, ns.value
 
 
 def make_kv_append_args(**kw) -> PfaKvAppendArgs:

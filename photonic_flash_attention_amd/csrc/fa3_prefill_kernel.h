@@ -21,7 +21,8 @@
 //      0 * NaN in the PV MFMA is NaN.  Table entries at and past ceil(len_b / page_size) are never read (a tile exists only below
 //      len_b).
 // Grid = B * H * ceil(Sq / 256) from shapes alone, no workspace, no atomics: capturable, and valid while lengths, table and cache
-// change between replays.  No split over keys: a short chunk with few B * H leaves CUs idle.
+// change between replays.  These instantiations do not split the keys: a short chunk with few B * H leaves CUs idle;
+// SPLIT below is the mode that does.
 //
 // VARLEN (pfa_fa3_prefill_varlen): every batch brings its own number of query rows.  Q, O are packed [total_q, H, D] (no batch
 // stride), LSE is [H, total_q], and a device int32 cu_seqlens_q[B + 1] says where each batch's rows start.  The schedule, the tile
@@ -51,6 +52,27 @@
 //   - PAGED: dma_tile starts at table entry 64 j_lo / page_size, token 64 j_lo % page_size (one division in the prologue) and
 //     advances by addition as before; the first scalar table load is that entry, and entries below it are never read.
 // WINDOW = false compiles to the code and the kernel arguments the instantiation had.
+//
+// SPLIT (pfa_fa3_prefill_split with N = nsplit > 1 key splits; uniform only -- no VARLEN, no WINDOW; PrefillSplitParams carry nsplit and the
+// two workspace bases): the keys of a q block are cut over N workgroups, each writes an fp32 partial result, and pfa_attn_merge joins
+// the N parts in split order.  What changes:
+//   - grid B * H * nqblk * N from host shapes; blockIdx = ((qrank * B * H) + bh) * N + s.  The q-block rank stays the slowest index,
+//     so the heaviest causal blocks still start first; the split s is the FASTEST, so the blocks that stream the same K/V tiles -- the
+//     H / Hkv query heads of one K/V head at one split -- are N apart in blockIdx and, blocks being dealt round-robin over the 8 XCDs,
+//     share an XCD's L2 at N = 8 (every second one at N = 4, every fourth at N = 2); the splits of one q block share no key;
+//   - THE SPLIT RULE: with n the 64-key tiles the block would run unsplit (nt, from kv_end: per q block under the causal flag) and
+//     per = ceil(n / N), split s runs tiles [s * per, min(n, (s + 1) * per)).  An empty range runs no tile and fetches nothing.  Inside
+//     its range the block is the unsplit kernel: wave_kv_end skips a wave's tiles above its rows, descriptors end at the last valid key,
+//     need_mask is computed on global key indices -- the partial result of split s is, bit for bit, the fp32 result of the unsplit
+//     kernel on the key slice [64 s per, 64 min(n, (s + 1) per)) with the length clamp(len_b - 64 s per, 0, slice);
+//   - PAGED: dma_tile starts at table entry 64 s per / page_size, token 64 s per % page_size (one division in the prologue, as WINDOW
+//     does for j_lo) and advances by addition: a split may begin in the middle of a page.  Entries outside the split's tiles, and those
+//     at or past ceil(len_b / page_size), are never read;
+//   - the output is always fp32 from the accumulators (SPLITP, OT = float), into the workspace: partial O [N][B][Sq][H][D], partial
+//     LSE [N][B][H][Sq].  p.o, p.lse and the o strides are not used.  Every split writes O and LSE of every row below Sq; a row with
+//     no visible key in the split's range (an empty range, rows above the range under the causal cut, len_b < Sq) gets O = 0 and
+//     LSE = -inf from the epilogue below, and the merge skips such a part.
+// SPLIT = false compiles to the code and the kernel arguments the instantiation had.
 #pragma once
 #include "fa3_fwd_kernel.h"
 
@@ -88,16 +110,25 @@ struct PrefillWinParams : PrefillParams {
 struct PrefillVarlenWinParams : PrefillVarlenParams {
     int32_t window;
 };
-template <bool VARLEN, bool WINDOW = false> struct PrefillParamsOf { typedef PrefillParams type; };
+// SPLIT: the key splits (2 .. 8) and the workspace, partial O [nsplit][B][Sq][H][D] and partial LSE [nsplit][B][H][Sq], both fp32
+struct PrefillSplitParams : PrefillParams {
+    int32_t nsplit;
+    float* part_o;
+    float* part_lse;
+};
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false> struct PrefillParamsOf { typedef PrefillParams type; };
 template <> struct PrefillParamsOf<true, false> { typedef PrefillVarlenParams type; };
 template <> struct PrefillParamsOf<false, true> { typedef PrefillWinParams type; };
 template <> struct PrefillParamsOf<true, true> { typedef PrefillVarlenWinParams type; };
+template <> struct PrefillParamsOf<false, false, true> { typedef PrefillSplitParams type; };
 
 typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
 
-template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false>
-__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW>::type p) {
+template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false, bool SPLIT = false>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW, SPLIT>::type p) {
     static_assert(CAUSAL || !WINDOW, "the window is cut from the causal diagonal");
+    static_assert(!SPLIT || (!VARLEN && !WINDOW), "the split over keys is for the uniform, window-less call");
+    static_assert(!SPLIT || (SPLITP && sizeof(OT) == 4), "the partial results are fp32, P carried as hi + lo");
     constexpr int NW = FWD_WAVES, BLOCK_M = FWD_BLOCK_M;
     using E = Elem<T>;
     using v8 = typename E::v8;
@@ -120,8 +151,15 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     const int h = lane >> 5;
 
     // ---- block -> (q block, batch*head): heaviest (longest causal row) blocks first ----------------
+    // SPLIT: the key split is the fastest index (see the header)
     const int BH = p.B * p.H;
-    const int n = blockIdx.x;
+    int n = blockIdx.x;
+    int split = 0;
+    if constexpr (SPLIT) {
+        const int item = n;
+        n = item / p.nsplit;
+        split = item - n * p.nsplit;
+    }
     const int qrank = n / BH;
     const int bh = n - qrank * BH;
     const int qblk = CAUSAL ? (p.nqblk - 1 - qrank) : qrank;
@@ -152,7 +190,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     const int kv_end = CAUSAL ? max(0, min(kv_len, q0 + BLOCK_M + off)) : kv_len;       // keys the block needs
     const int wave_kv_end = !wave_has_rows ? 0 : CAUSAL ? min(kv_len, wave_q0 + WAVE_M + off) : kv_len;   // keys this wave needs (<= 0: none)
     const int my_lim = my_q + off;                       // last key this row sees under the causal cut
-    const int nt = (kv_end + BLOCK_N - 1) / BLOCK_N;
+    int nt = (kv_end + BLOCK_N - 1) / BLOCK_N;
     // WINDOW: the block's first tile (j_lo < nt whenever nt > 0: q0 < sq puts the block's lowest bound below kv_end), the lowest
     // key the wave's first row sees, and the lowest its last row sees (both may be negative)
     int j_lo = 0, wave_lo = 0, wave_lo_last = 0;
@@ -160,6 +198,12 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
         j_lo = max(0, q0 + off - p.window + 1) / BLOCK_N;
         wave_lo = wave_q0 + off - p.window + 1;
         wave_lo_last = wave_lo + WAVE_M - 1;
+    }
+    // SPLIT: this block's share of the nt tiles, [j_lo, nt) from here on (empty: j_lo >= nt)
+    if constexpr (SPLIT) {
+        const int per = (nt + p.nsplit - 1) / p.nsplit;
+        j_lo = split * per;
+        nt = min(nt, j_lo + per);
     }
 
     const int kvh = hh / p.kv_group;
@@ -207,11 +251,11 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     // (2) paged: page id of the NEXT tile to fetch (a scalar load issued behind the previous tile's DMA), its index in the table
     // row and the token offset inside the page.  dma_tile is called for j = j_lo, j_lo + 1, ... in order (j_lo = 0 without a window),
     // and only for j < nt, i.e. for keys below kv_end <= len_b: entries at and past ceil(len_b / page_size), and those below
-    // 64 j_lo / page_size, are never read.
+    // 64 j_lo / page_size, are never read.  SPLIT: j_lo and nt bound the split's own tiles, so the same holds for the entries outside them.
     const prefill_table_ptr table = PAGED ? (prefill_table_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
     int pg_next = 0, pg_idx = 0, pg_tok = 0;
     if constexpr (PAGED) {
-        if constexpr (WINDOW) {
+        if constexpr (WINDOW || SPLIT) {
             pg_idx = (int)((uint32_t)(j_lo * BLOCK_N) / (uint32_t)p.page_size);
             pg_tok = j_lo * BLOCK_N - pg_idx * p.page_size;
         }
@@ -436,7 +480,9 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
         store_rows_from_lds<RB>(lbase, lane, (char*)((OT*)p.o + o_batch + (int64_t)hh * p.o_sh + (int64_t)wave_q0 * p.o_ss),
                                 p.o_ss * 2, sq - wave_q0);
     } else if (my_q < sq) {        // fp32 rows straight from the accumulators
-        OT* orow = (OT*)p.o + o_batch + (int64_t)hh * p.o_sh + (int64_t)my_q * p.o_ss;
+        OT* orow;
+        if constexpr (SPLIT) orow = p.part_o + ((((int64_t)split * p.B + b) * p.Sq + my_q) * p.H + hh) * D;
+        else orow = (OT*)p.o + o_batch + (int64_t)hh * p.o_sh + (int64_t)my_q * p.o_ss;
 #pragma unroll
         for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -448,9 +494,10 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
                 *(f32x4*)(orow + d) = w;
             }
     }
-    if (my_q < sq && p.lse && h == 0) {
+    if (my_q < sq && (SPLIT || p.lse) && h == 0) {
         const float lse = l_tot > 0.f ? (m_run * c + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : -INFINITY;
-        if constexpr (VARLEN) p.lse[(int64_t)hh * p.total_q + row0 + my_q] = lse;
+        if constexpr (SPLIT) p.part_lse[(((int64_t)split * p.B + b) * p.H + hh) * p.Sq + my_q] = lse;
+        else if constexpr (VARLEN) p.lse[(int64_t)hh * p.total_q + row0 + my_q] = lse;
         else p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;
     }
 }

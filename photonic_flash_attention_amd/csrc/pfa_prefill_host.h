@@ -40,13 +40,13 @@ const void* fn_td(bool causal, bool paged, bool out32, bool window) {
     return paged ? fn_out<T, D, VARLEN, false, true>(out32) : fn_out<T, D, VARLEN, false, false>(out32);
 }
 
-// of checked arguments: the kernel's name into buf -> workgroups
+// of checked arguments: the kernel's name into buf -> workgroups.  `mode` (pfa_fa3_prefill_split: "_split{N}+merge") goes in front of "_paged"
 template <bool VARLEN, typename Args>
-int describe(const Args* a, int window, char* buf, size_t n) {
+int describe(const Args* a, int window, char* buf, size_t n, const char* mode = "") {
     if (buf && n)
-        snprintf(buf, n, "fa3_prefill_%s_d%d_%s%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
+        snprintf(buf, n, "fa3_prefill_%s_d%d_%s%s%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
                  a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", a->causal ? "_causal" : "", window ? "_win" : "", VARLEN ? "_varlen" : "",
-                 a->block_table ? "_paged" : "");
+                 mode, a->block_table ? "_paged" : "");
     return (int)workgroups(a);
 }
 

@@ -575,6 +575,24 @@ def _window_ext(window, causal):
     return _capi.make_cache_ext(window=min(w, 0x7fffffff))
 
 
+def _key_splits_arg(name: str, value):
+    """``key_splits`` / ``prefix_key_splits`` (``name``) as the C value: None stays None, ``"auto"`` is 0 (the library's plan), an integer
+    1 .. 8 is itself.  Any other value or type is refused before anything is launched."""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        if value == "auto":
+            return 0
+    elif not isinstance(value, bool):
+        try:
+            n = operator.index(value)
+        except TypeError:
+            n = 0
+        if 1 <= n <= _capi.PFA_PREFILL_MAX_SPLITS:
+            return n
+    raise ValueError(f'{name} must be None, "auto" or an integer 1 .. {_capi.PFA_PREFILL_MAX_SPLITS}, got {value!r}')
+
+
 def _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, max_seqlen_q, block_table) -> None:
     """``pfa_kv_append``'s rule in plain torch, every clamp and drop included: the executable specification, and what ``kv_append``
     runs on CPU tensors.  ``lens`` / ``cu`` are host lists; k_new ``[total, Hkv, D]`` with ``cu``, else ``[B, Hkv, Sq, D]``."""
@@ -901,11 +919,12 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=
     return None
 
 
-def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, **ragged):
+def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, **ragged):
     """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
     ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
     the current stream right behind it, the status, and the kept tensors' hold on the stream.  With ``rotary`` the launch reads the
-    rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  -> lse or None."""
+    rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  ``key_splits`` (the C value, ``pfa_fa3_prefill`` only)
+    launches ``pfa_fa3_prefill_split`` instead, which takes no extension.  -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
@@ -919,7 +938,10 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
             a.q_stride_b, a.q_stride_h, a.q_stride_s = q_rot.stride()[:3]
         keep.append(q_rot)
     stream = torch.cuda.current_stream(q.device)
-    st = getattr(_capi.load(), entry + "_ex")(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
+    if key_splits is not None:
+        st = _capi.load().pfa_fa3_prefill_split(C.byref(a), key_splits, C.c_void_p(stream.cuda_stream))
+    else:
+        st = getattr(_capi.load(), entry + "_ex")(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
     for t in keep:   # tensors made here must outlive the enqueued kernels
         t.record_stream(stream)
@@ -1024,13 +1046,15 @@ def attn_merge(outs, lses, *, out: Optional[torch.Tensor] = None, out_dtype: Opt
 
 
 def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *, cache_seqlens, key_mask, window, causal, softmax_scale,
-                        out_dtype, return_lse, out, block_table, k_new, v_new, rotary):
+                        out_dtype, return_lse, out, block_table, k_new, v_new, rotary, prefix_key_splits=None):
     """``shared_prefix=P`` of ``fa3_decode`` / ``fa3_prefill_cache`` (``call``; ``entry`` names its C entry point in the messages): the
     attention cut at logical key P.  All ``B * Sq`` rows go as ONE sequence against sequence 0's first P keys (``causal=False``; every
     row lies behind the prefix), each sequence goes against its own keys from P on (``call`` unchanged on the cache view that starts
     at P, lengths ``max(len_b - P, 0)``), and ``attn_merge`` joins the two fp32 parts through their LSEs into the caller's ``out`` /
     ``out_dtype``.  The optional append runs once, first, on the whole cache, and both passes read the rotated q.  Everything is
-    enqueued on the current stream with no host synchronisation; every ``ValueError`` is raised before the first launch."""
+    enqueued on the current stream with no host synchronisation; every ``ValueError`` is raised before the first launch.
+    ``prefix_key_splits`` (as the caller gave it, already validated) is the prefix pass's ``key_splits`` when that pass is
+    ``fa3_prefill_cache``; the decode kernel splits by itself."""
     try:
         P = None if isinstance(shared_prefix, bool) else operator.index(shared_prefix)
     except TypeError:
@@ -1075,8 +1099,9 @@ def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *,
     # the decode kernel packs a K/V head's rows and splits the keys over workgroups: it fills the chip at few rows; past 64 the MFMA forward.
     # No length tensor: the prefix views hold exactly P keys, and without cache_seqlens the kernels take the capacity.
     prefix_call = fa3_decode if rows <= 64 else fa3_prefill_cache
+    split_kw = {} if rows <= 64 or prefix_key_splits is None else dict(key_splits=prefix_key_splits)
     o_pre, lse_pre = prefix_call(q_all, pre[0], pre[1], block_table=pre[2], causal=False, softmax_scale=softmax_scale,
-                                 out_dtype=torch.float32, return_lse=True)
+                                 out_dtype=torch.float32, return_lse=True, **split_kw)
     own_lens = (cache_seqlens.to(torch.int32) - P).clamp_(min=0)
     o_own, lse_own = call(q, own[0], own[1], block_table=own[2], cache_seqlens=own_lens, causal=causal, softmax_scale=softmax_scale,
                           out_dtype=torch.float32, return_lse=True)
@@ -1091,7 +1116,8 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-               pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
+               prefix_key_splits=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -1141,14 +1167,23 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     P 8192 (1.5 x) and from B 8 at P 32768 (1.4 x; 2.5 x at B 32), and loses at P 2048 for every B (0.64 - 0.94) and at B 8, P 8192
     (0.77).  When every sequence holds its own copy of the prefix it wins 1.25 - 5.6 x from B 32 at P 2048 and from B 8 at P 8192.
     Eager calls add a host floor of about 100 us per step and win only where the plain call is slower than that (B 32 at P 32768):
-    capture the step.  Past ``B * Sq`` = 64 rows the prefix pass is the MFMA forward over ONE sequence, 32 - 64 workgroups with no
-    split over keys, and the gain shrinks to 1.1 - 1.2 x (B 128; Sq 16 at B 32) until that pass gets a split over keys."""
+    capture the step.  Past ``B * Sq`` = 64 rows the prefix pass is the MFMA forward over ONE sequence, 32 - 64 workgroups, and
+    without a split over keys the gain shrinks to 1.1 - 1.2 x (B 128; Sq 16 at B 32).
+
+    ``prefix_key_splits`` (``None``, ``"auto"`` or 1 .. 8; only with ``shared_prefix``, else ``ValueError``): the ``key_splits`` of that
+    prefix pass when it is ``fa3_prefill_cache``, i.e. for ``B * Sq`` > 64 -- the P keys are cut over that many workgroups per q block
+    and merged (``profiles/prefill_split.md``).  With 64 rows or fewer the decode kernel splits by itself and the value is only
+    validated.  ``None``: exactly the calls made without the argument."""
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
+    _key_splits_arg("prefix_key_splits", prefix_key_splits)
+    if prefix_key_splits is not None and shared_prefix is None:
+        raise ValueError("prefix_key_splits needs shared_prefix: it splits the keys of the prefix pass")
     if shared_prefix is not None:
         return _shared_prefix_step(fa3_decode, "pfa_fa3_decode", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
                                    key_mask=key_mask, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
-                                   return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary)
+                                   return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary,
+                                   prefix_key_splits=prefix_key_splits)
     if k_new is not None and cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
@@ -1183,7 +1218,8 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                       rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-                      pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
+                      key_splits=None, prefix_key_splits=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
@@ -1192,11 +1228,21 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     ``[num_pages,Hkv,page_size,D]``-shaped, page_size a multiple of 64.  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of valid
     keys per batch, the query rows' own keys included (append first, then call); keys at and past it are never read.  ``causal`` is
     bottom-right aligned: row i sees key j iff j <= len_b - Sq + i; with len_b < Sq the first Sq - len_b rows see nothing (O = 0, LSE =
-    -inf).  There is no key mask (``fa3_decode`` takes one) and no split over keys: the call is one launch of the 8-wave MFMA kernel,
-    256 query rows per workgroup, and wants B * H * ceil(Sq / 256) of the order of the CU count to fill the chip.
+    -inf).  There is no key mask (``fa3_decode`` takes one).  By default the call is one launch of the 8-wave MFMA kernel, 256 query
+    rows per workgroup, each walking every key its rows see: it wants B * H * ceil(Sq / 256) of the order of the CU count to fill the
+    chip (``key_splits`` below is for the calls that have fewer).
     Returns ``(o [B,H,Sq,D] view of a [B,Sq,H,D] buffer, lse [B,H,Sq] or None)``.  No host synchronisation, no workspace and no cached
     allocation: capturable in ``torch.cuda.graph`` and valid while lengths, table and cache change between replays.  A paged call
     returns the bits of the contiguous call on the gathered cache.
+
+    ``key_splits`` (``None``: the call above through ``pfa_fa3_prefill_ex``, untouched; an integer 1 .. 8; or ``"auto"``, the library's
+    plan from (B, H, Sq, Smax) alone) goes through ``pfa_fa3_prefill_split``: every q block's 64-key tiles are cut into N ranges
+    (split s of n tiles runs ``[s * per, min(n, (s + 1) * per))``, ``per = ceil(n / N)``), one workgroup per range writes an fp32 partial
+    result into a fresh workspace of ``N * B * Sq * H * (D + 1) * 4`` bytes, and ``pfa_attn_merge`` joins them in split order: two
+    launches, no atomics, the same bits every run, still capturable.  A count that resolves to 1 is the call above bit for bit.  For a
+    short chunk of few sequences over a long cache (chunked prefill at B = 1; ``profiles/prefill_split.md``).  It does not combine with
+    ``window`` or ``shared_prefix`` (``ValueError`` before anything is enqueued, as for a bad value), and with a 16-bit ``out`` the
+    merge wants strides that are multiples of 8 elements.
 
     Sliding window: ``window=W`` (an integer >= 1, with ``causal=True``) as in ``fa3_decode``: row i sees key j iff j < len_b,
     j <= len_b - Sq + i and j > len_b - Sq + i - W.  A workgroup starts at the first 64-key tile its rows can see.  With
@@ -1215,19 +1261,37 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     (``len_b - Sq >= P``); all ``B * Sq`` rows go once against sequence 0's first P keys, each sequence against its own keys from P on
     with ``causal`` as given, and ``attn_merge`` joins the two.  Same restrictions (a multiple of 64 and of the page size, below Smax,
     ``cache_seqlens`` required, no ``window``), raised as ``ValueError`` before anything is enqueued.  Past 64 rows the prefix pass is
-    this call over one sequence of ``B * Sq`` rows, H * ceil(B * Sq / 256) workgroups with no split over keys.  Measured so far
-    (``profiles/shared_prefix.md``): the 512-row speculative step through ``fa3_decode``, 1.09 x shared pages, 2.3 x own copies."""
+    this call over one sequence of ``B * Sq`` rows, H * ceil(B * Sq / 256) workgroups; ``prefix_key_splits`` (``None``, ``"auto"`` or
+    1 .. 8; only with ``shared_prefix``) is that pass's ``key_splits``, as in ``fa3_decode``.  ``key_splits`` itself is refused with
+    ``shared_prefix``: the own-keys pass is short.  Measured (``profiles/shared_prefix.md``, ``profiles/prefill_split.md``): the 512-row
+    speculative step through ``fa3_decode``, 1.09 x shared pages, 2.3 x own copies, without a split of the prefix pass."""
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
+    splits = _key_splits_arg("key_splits", key_splits)
+    _key_splits_arg("prefix_key_splits", prefix_key_splits)
+    if prefix_key_splits is not None and shared_prefix is None:
+        raise ValueError("prefix_key_splits needs shared_prefix: it splits the keys of the prefix pass")
+    if splits is not None and window is not None:
+        raise ValueError("key_splits does not combine with window: the windowed kernel has no split over keys")
     if shared_prefix is not None:
+        if splits is not None:
+            raise ValueError("key_splits does not combine with shared_prefix (the own-keys pass is short): use prefix_key_splits")
         return _shared_prefix_step(fa3_prefill_cache, "pfa_fa3_prefill", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
                                    key_mask=None, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
-                                   return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary)
+                                   return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary,
+                                   prefix_key_splits=prefix_key_splits)
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
+    if splits is not None:
+        ws_bytes = int(_capi.load().pfa_fa3_prefill_split_workspace_bytes(C.byref(a), splits))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+            keep.append(ws)
     lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, max_seqlen_q=q.shape[2])
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, key_splits=splits,
+                             max_seqlen_q=q.shape[2])
     return out, lse
 
 
