@@ -107,9 +107,7 @@ int pfa_attn_merge(const pfa_attn_merge_args* a, void* stream) {
 
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};
-    const hipError_t e = hipLaunchKernel(kernel(a), dim3((unsigned)workgroups(a)), dim3(pfa::ATTN_MERGE_THREADS), kargs, 0, (hipStream_t)stream);
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    return pfa::launch(kernel(a), dim3((unsigned)workgroups(a)), pfa::ATTN_MERGE_THREADS, p, 0, stream);
 }
 
 }  // extern "C"

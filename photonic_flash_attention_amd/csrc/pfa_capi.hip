@@ -12,6 +12,7 @@
 #include "fa3_weights_kernel.h"
 #include "fa3_fwd_f32_kernel.h"
 #include "pfa_host.h"
+#include "pfa_mask_host.h"
 #include "pfa_p4.h"
 
 namespace pfa { const void* w4_kernel(int dtype, bool causal, bool out32); }   // pfa_w4.hip
@@ -35,46 +36,30 @@ struct Variant {
 // The 8-wave kernel's names end in _v8269: the schedule-flag word of the round-1 build, kept because tools and logs match on the names.
 constexpr int kFwdNameTag = 8269;
 
-template <typename T, int D, bool C, bool S, bool K, typename OT>
-Variant mk(const char* tn, const char* on) {
+const char* elem_name(const pfa_fa3_args* a) { return a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16"; }
+
+// The 8-wave kernel for every (dtype, D, causal, split, kmask, out).
+Variant w8_variant(const pfa_fa3_args* a, bool causal, bool split, bool kmask, bool out32) {
     Variant v;
-    v.fn = (const void*)&pfa::fa3_fwd_kernel<T, D, C, S, K, OT>;
-    snprintf(v.name, sizeof(v.name), "fa3_fwd_%s_d%d_%s%s%s_%s_v%d", tn, D, C ? "causal" : "full", S ? "_splitp" : "",
-             K ? "_kmask" : "", on, kFwdNameTag);
-    v.lds_bytes = 2 * 2 * pfa::BLOCK_N * D * 2;      // two buffers of a K and a V tile image
+    v.fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return pfa::dispatch_bools([](auto c, auto s, auto k, auto o32) {
+            return (const void*)&pfa::fa3_fwd_kernel<T, decltype(t)::D, c.value, s.value, k.value, pfa::out_t<o32.value, T>>;
+        }, causal, split, kmask, out32);
+    });
+    snprintf(v.name, sizeof(v.name), "fa3_fwd_%s_d%d_%s%s%s_%s_v%d", elem_name(a), a->D, causal ? "causal" : "full", split ? "_splitp" : "",
+             kmask ? "_kmask" : "", out32 ? "o32" : "o16", kFwdNameTag);
+    v.lds_bytes = 2 * 2 * pfa::BLOCK_N * a->D * 2;      // two buffers of a K and a V tile image
     v.nthreads = pfa::FWD_THREADS;
     v.block_m = pfa::FWD_BLOCK_M;
     return v;
 }
 
-// The 8-wave kernel for every (dtype, D, causal, split, kmask, out).
-template <typename T, int D, bool C, bool S, bool K>
-Variant by_out(bool out32, const char* tn) {
-    return out32 ? mk<T, D, C, S, K, float>(tn, "o32") : mk<T, D, C, S, K, T>(tn, "o16");
-}
-template <typename T, int D, bool C, bool S>
-Variant by_kmask(bool kmask, bool out32, const char* tn) {
-    return kmask ? by_out<T, D, C, S, true>(out32, tn) : by_out<T, D, C, S, false>(out32, tn);
-}
-template <typename T, int D, bool C>
-Variant by_split(bool split, bool kmask, bool out32, const char* tn) {
-    return split ? by_kmask<T, D, C, true>(kmask, out32, tn) : by_kmask<T, D, C, false>(kmask, out32, tn);
-}
-template <typename T, int D>
-Variant by_causal(bool causal, bool split, bool kmask, bool out32, const char* tn) {
-    return causal ? by_split<T, D, true>(split, kmask, out32, tn) : by_split<T, D, false>(split, kmask, out32, tn);
-}
-template <typename T>
-Variant by_d(int D, bool causal, bool split, bool kmask, bool out32, const char* tn) {
-    return D == 128 ? by_causal<T, 128>(causal, split, kmask, out32, tn) : by_causal<T, 64>(causal, split, kmask, out32, tn);
-}
-
-
 // persistent 4 waves x 64 rows in assembly (gen_fa3_fwd_p4.py / pfa_p4.hip)
 Variant p4_variant(const pfa_fa3_args* a, bool causal) {
     Variant v;
     v.fn = nullptr;
-    snprintf(v.name, sizeof(v.name), "fa3_fwd_p4_%s_d%d_%s%s_%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D, causal ? "causal" : "full",
+    snprintf(v.name, sizeof(v.name), "fa3_fwd_p4_%s_d%d_%s%s_%s", elem_name(a), a->D, causal ? "causal" : "full",
              pfa::p4_flavour(a) == 1 ? "_km" : (pfa::p4_flavour(a) == 2 ? "_kl" : ""), a->dtype_out == PFA_DTYPE_FP32 ? "splitp_o32" : "o16");
     v.p4 = true;
     v.p4_grid = pfa::p4_workgroups(a);
@@ -88,8 +73,7 @@ Variant p4_variant(const pfa_fa3_args* a, bool causal) {
 Variant w4_variant(const pfa_fa3_args* a, bool causal, bool out32) {
     Variant v;
     v.fn = pfa::w4_kernel(a->dtype_in == PFA_DTYPE_BF16 ? 0 : 1, causal, out32);
-    snprintf(v.name, sizeof(v.name), "fa3_fwd_w4_%s_d128_%s_%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16",
-             causal ? "causal" : "full", out32 ? "o32" : "o16");
+    snprintf(v.name, sizeof(v.name), "fa3_fwd_w4_%s_d128_%s_%s", elem_name(a), causal ? "causal" : "full", out32 ? "o32" : "o16");
     v.grid3 = true;
     v.lds_bytes = 8 * pfa::BLOCK_N * 128 * 2;      // K ring 2 + V ring 2 tiles, then the Q block's 64-KiB landing zone
     v.nthreads = 256;
@@ -124,12 +108,8 @@ Variant pick(const pfa_fa3_args* a) {
         if (v.p4_grid > 0) return v;   // (0: the code object did not load on this device -- fall through to the HIP kernels)
     }
     if (w4_ok && (var == 43 || ((var == 0 || var == 45) && avg_tiles >= 16))) return w4_variant(a, causal, out32);
-    return a->dtype_in == PFA_DTYPE_BF16 ? by_d<__bf16>(a->D, causal, split, kmask, out32, "bf16")
-                                         : by_d<_Float16>(a->D, causal, split, kmask, out32, "fp16");
+    return w8_variant(a, causal, split, kmask, out32);
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool mult8(int64_t s) { return (s % 8) == 0; }
 
 int check(const pfa_fa3_args* a) {
     if (!a) return PFA_ERR_NULL;
@@ -147,61 +127,77 @@ int check(const pfa_fa3_args* a) {
     if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
     if (a->dtype_in != PFA_DTYPE_BF16 && a->dtype_in != PFA_DTYPE_FP16 && a->dtype_in != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
     if (a->dtype_out != a->dtype_in && a->dtype_out != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
+    using pfa::aligned16; using pfa::aligned4; using pfa::slab_fits32;
+    const int32_t Sq = a->Sq, Sk = a->Sk, D = a->D;
     if (a->dtype_in == PFA_DTYPE_FP32) {       // the exact fp32 kernel (fa3_fwd_f32_kernel.h): 16-byte rows, no kernel selector, no split P
         if (a->flags & (PFA_FLAG_SPLIT_P | PFA_FLAG_VARIANT_MASK)) return PFA_ERR_FLAGS;
-        const int64_t st4[] = {a->q_stride_b, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s,
-                               a->v_stride_b, a->v_stride_h, a->v_stride_s};
-        for (int64_t s : st4)
-            if (s % 4 != 0) return PFA_ERR_STRIDE;
-        if (!a->q || !a->k || !a->v || !a->o) return PFA_ERR_NULL;
-        if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || (reinterpret_cast<uintptr_t>(a->o) & 3u)) return PFA_ERR_ALIGN;
-        if (!(a->softmax_scale > 0.f) || !isfinite(a->softmax_scale)) return PFA_ERR_SHAPE;
-        if ((int64_t)((a->Sq + 63) / 64) * a->B * a->H > 0x7fffffffLL) return PFA_ERR_SHAPE;
-        if (a->lse && (reinterpret_cast<uintptr_t>(a->lse) & 3u)) return PFA_ERR_ALIGN;
-        const int64_t rows[] = {a->q_stride_s, a->k_stride_s, a->v_stride_s, a->o_stride_s};       // rows at least D apart, 32-bit slabs
-        for (int64_t s : rows)
-            if (s < a->D) return PFA_ERR_STRIDE;
-        if (((int64_t)(a->Sq - 1) * a->q_stride_s + a->D) * 4 > 0x7fffffffLL || ((int64_t)(a->Sk - 1) * a->k_stride_s + a->D) * 4 > 0x7fffffffLL ||
-            ((int64_t)(a->Sk - 1) * a->v_stride_s + a->D) * 4 > 0x7fffffffLL || ((int64_t)(a->Sq - 1) * a->o_stride_s + a->D) * 4 > 0x7fffffffLL)
+        if (!pfa::qkv_strides_multiples_of(4, a)) return PFA_ERR_STRIDE;
+        if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || !aligned4(a->o)) return PFA_ERR_ALIGN;
+        if (!pfa::scale_ok(a->softmax_scale)) return PFA_ERR_SHAPE;
+        if ((int64_t)((Sq + 63) / 64) * a->B * a->H > 0x7fffffffLL) return PFA_ERR_SHAPE;
+        if (!aligned4(a->lse)) return PFA_ERR_ALIGN;
+        // rows at least D apart, 32-bit slabs
+        if (a->q_stride_s < D || a->k_stride_s < D || a->v_stride_s < D || a->o_stride_s < D) return PFA_ERR_STRIDE;
+        if (!slab_fits32(Sq, a->q_stride_s, D, 4) || !slab_fits32(Sk, a->k_stride_s, D, 4) || !slab_fits32(Sk, a->v_stride_s, D, 4) ||
+            !slab_fits32(Sq, a->o_stride_s, D, 4))
             return PFA_ERR_SHAPE;
         return PFA_OK;
     }
-    if (!(a->softmax_scale > 0.f) || !isfinite(a->softmax_scale)) return PFA_ERR_SHAPE;
-    const int64_t st[] = {a->q_stride_b, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s,
-                          a->v_stride_b, a->v_stride_h, a->v_stride_s};
-    for (int64_t s : st)
-        if (!mult8(s)) return PFA_ERR_STRIDE;
-    const int64_t ost[] = {a->o_stride_b, a->o_stride_h, a->o_stride_s};
-    for (int64_t s : ost)
-        if (s % 4 != 0) return PFA_ERR_STRIDE;
-    if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || !aligned16(a->o)) return PFA_ERR_ALIGN;
-    if (a->lse && (reinterpret_cast<uintptr_t>(a->lse) & 3u)) return PFA_ERR_ALIGN;
-    const int64_t nq = (a->Sq + 127) / 128;
-    if (nq * a->B * a->H > 0x7fffffffLL) return PFA_ERR_SHAPE;
-    // K/V slabs of one (batch, head) are addressed through 32-bit buffer descriptors
-    if (((int64_t)(a->Sk - 1) * a->k_stride_s + a->D) * 2 > 0x7fffffffLL) return PFA_ERR_SHAPE;
-    if (((int64_t)(a->Sk - 1) * a->v_stride_s + a->D) * 2 > 0x7fffffffLL) return PFA_ERR_SHAPE;
-    if (((int64_t)(a->Sq - 1) * a->q_stride_s + a->D) * 2 > 0x7fffffffLL) return PFA_ERR_SHAPE;   // the 4-wave kernel's Q DMA
-    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_s * 64 > 0x3fffffffLL || a->v_stride_s * 64 > 0x3fffffffLL)
-        return PFA_ERR_STRIDE;
+    if (!pfa::scale_ok(a->softmax_scale)) return PFA_ERR_SHAPE;
+    if (!pfa::qkv_strides_multiples_of(8, a) || !pfa::multiples_of(4, {a->o_stride_b, a->o_stride_h, a->o_stride_s})) return PFA_ERR_STRIDE;
+    if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || !aligned16(a->o) || !aligned4(a->lse)) return PFA_ERR_ALIGN;
+    if ((int64_t)((Sq + 127) / 128) * a->B * a->H > 0x7fffffffLL) return PFA_ERR_SHAPE;
+    // K/V slabs of one (batch, head) are addressed through 32-bit buffer descriptors; Q too, by the 4-wave kernel's DMA
+    if (!slab_fits32(Sk, a->k_stride_s, D, 2) || !slab_fits32(Sk, a->v_stride_s, D, 2) || !slab_fits32(Sq, a->q_stride_s, D, 2)) return PFA_ERR_SHAPE;
+    if (!pfa::kv_rows_forward(a) || a->k_stride_s * 64 > 0x3fffffffLL || a->v_stride_s * 64 > 0x3fffffffLL) return PFA_ERR_STRIDE;
     return PFA_OK;
+}
+
+// Masks are condensed into one 64-bit word per mask row and 64-key tile before the forward and the weights pass (pfa_mask_host.h):
+// the [B, Sk] key mask as one row per batch, else the element mask
+pfa::MaskWords mask_words(const pfa_fa3_args* a) {
+    return a->key_mask ? pfa::mask_words(a->key_mask, a->B, 1, 1, a->Sk, a->key_mask_stride_b, 0, 0, 1) : pfa::element_mask_words(a);
+}
+// mask + enough workspace: one word per row and tile instead of a mask byte per score (without workspace the byte path runs)
+template <typename Params>
+bool take_mask_words(Params& p, const pfa::MaskWords& mb, const pfa_fa3_args* a) {
+    const bool use = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
+    p.mbits = use ? (const unsigned long long*)a->workspace : nullptr;
+    p.mb_sb = mb.ob; p.mb_sh = mb.oh; p.mb_sq = mb.oq;
+    return use;
+}
+// (named here, in front of the fp32 launch: the compiler emits template kernels in the order the host code first names them)
+bool enqueue_mask_words(const pfa::MaskWords& mb, const pfa_fa3_args* a, void* stream) { return pfa::launch_row_words(mb, a->workspace, stream); }
+
+// what the three parameter blocks of this file share besides the strides: key counts, mask, shape and the K/V head grouping
+template <typename Params>
+void fill_common(Params& p, const pfa_fa3_args* a) {
+    p.seqlens_k = a->seqlens_k;
+    pfa::fill_mask(p, a);
+    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
+    p.kv_group = pfa::kv_group_of(a);
+}
+
+int launch_f32(const pfa_fa3_args* a, void* stream) {
+    pfa::F32Params p;
+    p.q = (const float*)a->q; p.k = (const float*)a->k; p.v = (const float*)a->v; p.o = (float*)a->o;
+    p.lse = a->lse;
+    fill_common(p, a);
+    pfa::fill_qkvo_strides(p, a);
+    p.causal = a->causal != 0;
+    p.scale = a->softmax_scale;
+    p.drop_mask = a->drop_mask;
+    p.drop_scale = a->drop_scale;
+    const void* fn = pfa::dispatch_dim(a->D, [](auto d) { return (const void*)&pfa::fa3_fwd_f32_kernel<d.value>; });
+    const int lds = pfa::dispatch_dim(a->D, [](auto d) { return pfa::f32_lds_bytes<d.value>(); });
+    const pfa::DeviceScope dev(a->device_id);
+    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
+    return pfa::launch(fn, dim3((unsigned)(((a->Sq + pfa::F32_BM - 1) / pfa::F32_BM) * a->B * a->H)), 256, p, (size_t)lds, stream);
 }
 
 }  // namespace
 
 namespace pfa { void set_last_hip_error(int e) { g_last_hip_error = e; } }   // for the other translation units' entry points
-
-namespace {
-template <typename T, int D, bool C, bool K>
-const void* weights_fn(bool w32) {
-    return w32 ? (const void*)&pfa::fa3_weights_kernel<T, D, C, K, float> : (const void*)&pfa::fa3_weights_kernel<T, D, C, K, T>;
-}
-template <typename T, int D>
-const void* weights_fn_ck(bool causal, bool kmask, bool w32) {
-    if (causal) return kmask ? weights_fn<T, D, true, true>(w32) : weights_fn<T, D, true, false>(w32);
-    return kmask ? weights_fn<T, D, false, true>(w32) : weights_fn<T, D, false, false>(w32);
-}
-}  // namespace
 
 extern "C" {
 
@@ -243,49 +239,7 @@ int pfa_fa3_prepare(int device_id) {
     return st;
 }
 
-// Masks are condensed into one 64-bit word per mask row and 64-key tile before the forward (fa3_maskbits_kernel): geometry of
-// the word array for `a` -- the mask's own (un-broadcast) extents and the word strides the kernels use
-struct MaskBits {
-    int Bm = 0, Hm = 0, Qm = 0, nt = 0;
-    int64_t sb = 0, sh = 0, sq = 0, sk = 0;      // byte strides of the source mask
-    int64_t ob = 0, oh = 0, oq = 0;              // word strides of the result (0 = broadcast)
-    const uint8_t* src = nullptr;
-    int ngran = 0;                               // 256-row granules of the mask (fa3_maskrange_kernel: first / last visible tile of each)
-    size_t word_bytes() const { return src ? (size_t)Bm * Hm * Qm * nt * sizeof(unsigned long long) : 0; }
-    size_t bytes() const { return src ? word_bytes() + (size_t)Bm * Hm * ngran * pfa::RANGE_PARTS * 2 * sizeof(int) : 0; }
-};
-static MaskBits mask_bits(const pfa_fa3_args* a) {
-    MaskBits m;
-    m.nt = (a->Sk + 63) / 64;
-    if (a->key_mask) {
-        m.src = a->key_mask; m.Bm = a->B; m.Hm = 1; m.Qm = 1;
-        m.sb = a->key_mask_stride_b; m.sk = 1;
-    } else if (a->mask) {
-        m.src = a->mask;
-        m.Bm = a->mask_stride_b ? a->B : 1; m.Hm = a->mask_stride_h ? a->H : 1; m.Qm = a->mask_stride_q ? a->Sq : 1;
-        m.sb = a->mask_stride_b; m.sh = a->mask_stride_h; m.sq = a->mask_stride_q; m.sk = a->mask_stride_k;
-    } else {
-        return m;
-    }
-    if (m.Qm > 65535 || (int64_t)m.Bm * m.Hm > 65535) { m.src = nullptr; return m; }      // launch limits: the byte path serves these
-    m.ngran = (m.Qm + 255) / 256;
-    m.oq = m.Qm > 1 ? m.nt : 0;
-    m.oh = m.Hm > 1 ? (int64_t)m.Qm * m.nt : 0;
-    m.ob = m.Bm > 1 ? (int64_t)m.Hm * m.Qm * m.nt : 0;
-    return m;
-}
-
-static bool launch_mask_bits(const MaskBits& mb, const pfa_fa3_args* a, void* stream) {
-    pfa::launch_mask_words(mb.src, mb.sb, mb.sh, mb.sq, mb.sk, mb.Bm, mb.Hm, mb.Qm, a->Sk, mb.nt, (unsigned long long*)a->workspace, mb.ob, mb.oh,
-                           mb.oq, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return false;
-    hipLaunchKernelGGL(pfa::fa3_maskrange_kernel<256>, dim3((unsigned)(mb.ngran * pfa::RANGE_PARTS), (unsigned)(mb.Bm * mb.Hm)), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned long long*)a->workspace, mb.ob, mb.oh, mb.oq, mb.Hm, mb.Qm, mb.nt,
-                       (int*)((char*)a->workspace + mb.word_bytes()), mb.ngran);
-    return hipGetLastError() == hipSuccess;
-}
-
-size_t pfa_fa3_workspace_bytes(const pfa_fa3_args* a) { return (a && a->dtype_in != PFA_DTYPE_FP32) ? mask_bits(a).bytes() : 0; }
+size_t pfa_fa3_workspace_bytes(const pfa_fa3_args* a) { return (a && a->dtype_in != PFA_DTYPE_FP32) ? mask_words(a).bytes() : 0; }
 
 int pfa_fa3_check(const pfa_fa3_args* a) { return check(a); }
 
@@ -306,32 +260,6 @@ int pfa_fa3_describe(const pfa_fa3_args* a, char* buf, size_t n) {
     return nq * a->B * a->H;
 }
 
-static int launch_f32(const pfa_fa3_args* a, void* stream) {
-    pfa::F32Params p;
-    p.q = (const float*)a->q; p.k = (const float*)a->k; p.v = (const float*)a->v; p.o = (float*)a->o;
-    p.lse = a->lse; p.seqlens_k = a->seqlens_k;
-    pfa::fill_mask(p, a);
-    p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
-    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
-    p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
-    p.o_sb = a->o_stride_b; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
-    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
-    p.kv_group = a->kv_group > 1 ? a->kv_group : 1;
-    p.causal = a->causal != 0;
-    p.scale = a->softmax_scale;
-    p.drop_mask = a->drop_mask;
-    p.drop_scale = a->drop_scale;
-    const void* fn = a->D == 128 ? (const void*)&pfa::fa3_fwd_f32_kernel<128> : (const void*)&pfa::fa3_fwd_f32_kernel<64>;
-    const int lds = a->D == 128 ? pfa::f32_lds_bytes<128>() : pfa::f32_lds_bytes<64>();
-    const pfa::DeviceScope dev(a->device_id);
-    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    void* kargs[] = {&p};
-    const hipError_t e =
-        hipLaunchKernel(fn, dim3((unsigned)(((a->Sq + pfa::F32_BM - 1) / pfa::F32_BM) * a->B * a->H)), dim3(256), kargs, (size_t)lds, (hipStream_t)stream);
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
-}
-
 int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
     const int st = check(a);
     if (st != PFA_OK) return st;
@@ -339,24 +267,15 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
 
     pfa::FwdParams p;
     p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o;
-    p.lse = a->lse; p.seqlens_k = a->seqlens_k;
-    pfa::fill_mask(p, a);
-    p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
-    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
-    p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
-    p.o_sb = a->o_stride_b; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
-    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
+    p.lse = a->lse;
+    fill_common(p, a);
+    pfa::fill_qkvo_strides(p, a);
     p.dbg = (unsigned long long*)a->workspace;   // written by diagnostic builds of the 4-wave kernel only (PFA_W4_STAMP)
-    // mask + enough workspace: one word per row and tile instead of a mask byte per score (without workspace the byte path runs)
-    const MaskBits mb = mask_bits(a);
-    const bool use_mbits = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
-    p.mbits = use_mbits ? (const unsigned long long*)a->workspace : nullptr;
-    p.mb_sb = mb.ob; p.mb_sh = mb.oh; p.mb_sq = mb.oq;
+    const pfa::MaskWords mb = mask_words(a);
+    const bool use_mbits = take_mask_words(p, mb, a);
     if (use_mbits) {
         p.mrange = (const int*)((const char*)a->workspace + mb.word_bytes());
-        p.mr_sb = mb.Bm > 1 ? (int64_t)mb.Hm * mb.ngran : 0;
-        p.mr_sh = mb.Hm > 1 ? mb.ngran : 0;
-        p.mr_q = mb.Qm > 1 ? 1 : 0;
+        p.mr_sb = mb.range_sb(); p.mr_sh = mb.range_sh(); p.mr_q = mb.range_q();
     }
     const Variant v = pick(a);
     if (v.p4) {
@@ -366,7 +285,6 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
         return st4;
     }
     p.nqblk = (a->Sq + v.block_m - 1) / v.block_m;
-    p.kv_group = a->kv_group > 1 ? a->kv_group : 1;
     p.xcd_group = v.xcd_group;
     p.scale_log2 = a->softmax_scale * pfa::LOG2E;
     p.magic_h = (uint32_t)((1ull << 32) / (uint64_t)a->H) + 1u;
@@ -382,14 +300,10 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream) {
         grid = p.xcd_group > 0 ? dim3(8u * p.xcd_group, (unsigned)p.nqblk, (unsigned)(BH / (8 * p.xcd_group)))
                                : dim3((unsigned)BH, (unsigned)p.nqblk, 1u);
     }
-    void* kargs[] = {&p};
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    if (use_mbits && !launch_mask_bits(mb, a, stream)) return PFA_ERR_LAUNCH;
-    if (v.lds_bytes > 64 * 1024)   // opt in to > 64 KiB of dynamic LDS (idempotent, per function)
-        (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_bytes);
-    const hipError_t e = hipLaunchKernel(v.fn, grid, dim3(v.nthreads), kargs, (size_t)v.lds_bytes, (hipStream_t)stream);
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    if (use_mbits && !enqueue_mask_words(mb, a, stream)) return PFA_ERR_LAUNCH;
+    return pfa::launch(v.fn, grid, v.nthreads, p, (size_t)v.lds_bytes, stream);
 }
 
 int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_stride_b, int64_t w_stride_h,
@@ -405,31 +319,25 @@ int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_s
     if (w_dtype != a->dtype_in && w_dtype != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
 
     pfa::WeightsParams p;
-    p.q = a->q; p.k = a->k; p.lse = a->lse; p.w = w; p.seqlens_k = a->seqlens_k;
-    pfa::fill_mask(p, a);
-    p.q_sb = a->q_stride_b; p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s;
-    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
+    p.q = a->q; p.k = a->k; p.lse = a->lse; p.w = w;
+    fill_common(p, a);
+    pfa::fill_qk_strides(p, a);
     p.w_sb = w_stride_b; p.w_sh = w_stride_h; p.w_sq = w_stride_q;
-    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
     p.nqblk = (a->Sq + 127) / 128;
-    p.kv_group = a->kv_group > 1 ? a->kv_group : 1;
     p.scale_log2 = a->softmax_scale * pfa::LOG2E;
-    const MaskBits mb = mask_bits(a);          // as in pfa_fa3_fwd: the mask as words when the caller gave workspace
-    const bool use_mbits = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
-    p.mbits = use_mbits ? (const unsigned long long*)a->workspace : nullptr;
-    p.mb_sb = mb.ob; p.mb_sh = mb.oh; p.mb_sq = mb.oq;
+    const pfa::MaskWords mb = mask_words(a);          // as in pfa_fa3_fwd: the mask as words when the caller gave workspace
+    const bool use_mbits = take_mask_words(p, mb, a);
     const bool causal = a->causal != 0, kmask = p.mask != nullptr, w32 = w_dtype == PFA_DTYPE_FP32;
-    const void* fn;
-    if (a->dtype_in == PFA_DTYPE_BF16)
-        fn = a->D == 128 ? weights_fn_ck<__bf16, 128>(causal, kmask, w32) : weights_fn_ck<__bf16, 64>(causal, kmask, w32);
-    else
-        fn = a->D == 128 ? weights_fn_ck<_Float16, 128>(causal, kmask, w32) : weights_fn_ck<_Float16, 64>(causal, kmask, w32);
+    const void* fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return pfa::dispatch_bools([](auto c, auto k, auto o32) {
+            return (const void*)&pfa::fa3_weights_kernel<T, decltype(t)::D, c.value, k.value, pfa::out_t<o32.value, T>>;
+        }, causal, kmask, w32);
+    });
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    if (use_mbits && !launch_mask_bits(mb, a, stream)) return PFA_ERR_LAUNCH;      // (again: the call may come without a forward before it)
-    void* kargs[] = {&p};
-    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(p.nqblk * a->B * a->H)), dim3(256), kargs, 0, (hipStream_t)stream);
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    if (use_mbits && !enqueue_mask_words(mb, a, stream)) return PFA_ERR_LAUNCH;      // (again: the call may come without a forward before it)
+    return pfa::launch(fn, dim3((unsigned)(p.nqblk * a->B * a->H)), 256, p, 0, stream);
 }
 
 }  // extern "C"

@@ -126,13 +126,10 @@ int pfa_fa3_decode_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext
     const void* cfn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) { return combine_fn<typename decltype(t)::type, decltype(t)::D>(out32); });
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: the base, or all of it
-    hipError_t e = hipLaunchKernel(fn, dim3((unsigned)pl.items), dim3(pfa::dec::THREADS), kargs, 0, (hipStream_t)stream);
-    if (e == hipSuccess && pl.nsplit > 1) {
-        const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
-        e = hipLaunchKernel(cfn, dim3((unsigned)((threads + 255) / 256)), dim3(256), kargs, 0, (hipStream_t)stream);
-    }
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    const int st_main = pfa::launch(fn, dim3((unsigned)pl.items), pfa::dec::THREADS, p, 0, stream);
+    if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
+    const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
+    return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
 }
 
 // the calls without the extension block

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #include "pfa_hip.h"
 
@@ -43,6 +44,37 @@ public:
     hipError_t error() const { return err_; }   // of the switch; a launch behind a failed one is PFA_ERR_DEVICE
 };
 
+// The tail of a launch: opt in to more than 64 KiB of dynamic LDS where the kernel asks for it (idempotent, per function), enqueue with
+// the parameter block as the one kernel argument, and map a failure to PFA_ERR_LAUNCH (its code kept for pfa_last_hip_error).
+template <typename Params>
+inline int launch(const void* fn, dim3 grid, unsigned threads, Params& p, size_t lds, void* stream) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: a base of p, or all of it
+    return hip_failed(hipLaunchKernel(fn, grid, dim3(threads), kargs, lds, (hipStream_t)stream)) ? PFA_ERR_LAUNCH : PFA_OK;
+}
+
+// One tensor's strides from an argument block into a kernel parameter block: p.x_sb / x_sh / x_ss = a->x_stride_b / _h / _s.  Every
+// parameter block names them so; the templates below copy the sets the kernels take.
+#define PFA_FILL_STRIDES(p, a, x) ((p).x##_sb = (a)->x##_stride_b, (p).x##_sh = (a)->x##_stride_h, (p).x##_ss = (a)->x##_stride_s)
+template <typename Params, typename Args>
+inline void fill_qk_strides(Params& p, const Args* a) {         // WeightsParams
+    PFA_FILL_STRIDES(p, a, q); PFA_FILL_STRIDES(p, a, k);
+}
+template <typename Params, typename Args>
+inline void fill_qkvo_strides(Params& p, const Args* a) {       // FwdParams, F32Params
+    fill_qk_strides(p, a);
+    PFA_FILL_STRIDES(p, a, v); PFA_FILL_STRIDES(p, a, o);
+}
+template <typename Params>
+inline void fill_bwd_strides(Params& p, const pfa_fa3_bwd_args* a) {      // BwdParams, F32BwdParams: the gradients too, and the element mask
+    fill_qkvo_strides(p, a);
+    PFA_FILL_STRIDES(p, a, do); PFA_FILL_STRIDES(p, a, dq); PFA_FILL_STRIDES(p, a, dk); PFA_FILL_STRIDES(p, a, dv);
+    p.m_sb = a->mask_stride_b; p.m_sh = a->mask_stride_h; p.m_sq = a->mask_stride_q; p.m_sk = a->mask_stride_k;
+}
+// query heads per K/V head as the kernels take it: the argument blocks' 0 means 1
+template <typename Args>
+inline int kv_group_of(const Args* a) { return a->kv_group > 1 ? a->kv_group : 1; }
+
 // The mask fields of a kernel parameter block (FwdParams, F32Params, WeightsParams): the element mask with its four byte
 // strides, or the [B, Sk] key mask as (stride, 0, 0, 1), or null.
 template <typename Params>
@@ -65,6 +97,15 @@ inline bool multiples_of(int m, std::initializer_list<int64_t> strides) {
         if (s % m != 0) return false;
     return true;
 }
+template <typename Args>
+inline bool qkv_strides_multiples_of(int m, const Args* a) {
+    return multiples_of(m, {a->q_stride_b, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s, a->v_stride_b, a->v_stride_h,
+                            a->v_stride_s});
+}
+inline bool scale_ok(float softmax_scale) { return softmax_scale > 0.f && isfinite(softmax_scale); }     // finite and positive
+// The S rows of one (batch, head), `stride` elements apart and D wide, are addressed by 32-bit byte offsets (buffer descriptors, DMA).
+inline int64_t slab_bytes(int32_t S, int64_t stride, int32_t D, int elem_bytes) { return ((int64_t)(S - 1) * stride + D) * elem_bytes; }
+inline bool slab_fits32(int32_t S, int64_t stride, int32_t D, int elem_bytes) { return slab_bytes(S, stride, D, elem_bytes) <= 0x7fffffffLL; }
 // cache rows run forward: k_stride_s / v_stride_s >= 0, for the calls that read the cache and the one that writes it
 template <typename Args>
 inline bool kv_rows_forward(const Args* a) { return a->k_stride_s >= 0 && a->v_stride_s >= 0; }
@@ -80,6 +121,20 @@ inline auto dispatch_elem_dim(int dtype, int D, F&& f) {
     return dtype == PFA_DTYPE_BF16 ? (D == 128 ? f(ElemDim<__bf16, 128>{}) : f(ElemDim<__bf16, 64>{}))
                                    : (D == 128 ? f(ElemDim<_Float16, 128>{}) : f(ElemDim<_Float16, 64>{}));
 }
+// ... with the head dim alone (the fp32 kernels), as a std::integral_constant
+template <typename F>
+inline auto dispatch_dim(int D, F&& f) {
+    return D == 128 ? f(std::integral_constant<int, 128>{}) : f(std::integral_constant<int, 64>{});
+}
+// Calls f with a std::bool_constant tag for every run-time flag, true before false: the flags' half of a kernel ladder.
+template <bool... Bs, typename F>
+inline auto dispatch_bools(F&& f) { return f(std::bool_constant<Bs>{}...); }
+template <bool... Bs, typename F, typename... Rest>
+inline auto dispatch_bools(F&& f, bool b, Rest... rest) {
+    return b ? dispatch_bools<Bs..., true>(f, rest...) : dispatch_bools<Bs..., false>(f, rest...);
+}
+template <bool FP32, typename T>
+using out_t = std::conditional_t<FP32, float, T>;      // what a kernel stores: fp32 where the flag asks for it, else the element type
 
 // The paging fields every call over a KV cache carries (include/pfa_hip.h, pfa_fa3_decode_args): all set, or all zero.
 inline int check_paging(const int32_t* block_table, int64_t block_table_stride_b, int32_t page_size, int32_t num_pages, int32_t Smax) {
@@ -127,7 +182,7 @@ inline int check_cache_args(const Args* a, int max_sq) {
     if (st != PFA_OK) return st;
     if (a->dtype_in != PFA_DTYPE_BF16 && a->dtype_in != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
     if (a->dtype_out != a->dtype_in && a->dtype_out != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
-    if (!(a->softmax_scale > 0.f) || !isfinite(a->softmax_scale)) return PFA_ERR_SHAPE;
+    if (!scale_ok(a->softmax_scale)) return PFA_ERR_SHAPE;
     if (!multiples_of(8, {g.q_sb, a->q_stride_h, a->q_stride_s, a->k_stride_b, a->k_stride_h, a->k_stride_s, a->v_stride_b, a->v_stride_h,
                           a->v_stride_s}))
         return PFA_ERR_STRIDE;
@@ -145,8 +200,7 @@ inline int check_cache_args(const Args* a, int max_sq) {
 template <typename Params, typename Args>
 inline void fill_cache_params(Params& p, const Args* a) {
     p.seqlens = a->cache_seqlens; p.Smax = a->Smax;
-    p.k_sb = a->k_stride_b; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
-    p.v_sb = a->v_stride_b; p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s;
+    PFA_FILL_STRIDES(p, a, k); PFA_FILL_STRIDES(p, a, v);
     p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
 }
 // ... and on top of them what the attention kernels' blocks (DecodeParams, Prefill*Params) share: the tensors, q / o strides, scale.

@@ -79,9 +79,7 @@ int pfa_kv_append(const pfa_kv_append_args* a, void* stream) {
                             : (paged ? (const void*)&pfa::kv_append_kernel<false, true> : (const void*)&pfa::kv_append_kernel<false, false>);
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};
-    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)workgroups(a)), dim3(pfa::KV_APPEND_THREADS), kargs, 0, (hipStream_t)stream);
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    return pfa::launch(fn, dim3((unsigned)workgroups(a)), pfa::KV_APPEND_THREADS, p, 0, stream);
 }
 
 }  // extern "C"

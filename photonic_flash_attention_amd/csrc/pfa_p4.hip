@@ -124,8 +124,10 @@ const DevMod* module_for(int dev, int* hip_err = nullptr) {
 bool fits_u32(int64_t x) { return x >= 0 && x <= 0xffffffffLL; }
 }  // namespace
 
-// 0 = the plain kernels (whole blocks and tiles), 1 = *_km_* ([B, Sk] key mask, whole blocks and tiles), 2 = *_kl_* (ragged: Sq no
-// multiple of 256 or Sk no multiple of 128 -- rows past the end are kept out by buffer descriptors, keys past Sk by a computed mask word)
+// 0 = the plain kernels (whole blocks and tiles, no per-batch key counts), 1 = *_km_* (a [B, Sk] key mask, with Sq / Sk of any length
+// p4_eligible admits, with or without seqlens_k: the generator's len_word / km_len_and cut the mask words at the keys a batch has),
+// 2 = *_kl_* (no key mask, and seqlens_k or a ragged shape -- Sq no multiple of 256 or Sk no multiple of 128: rows past the end are
+// kept out by buffer descriptors, keys past Sk by a computed mask word)
 int p4_flavour(const pfa_fa3_args* a) {
     if (a->key_mask) return 1;
     const bool whole = a->Sq % 256 == 0 && a->Sk % 128 == 0;
@@ -134,7 +136,8 @@ int p4_flavour(const pfa_fa3_args* a) {
 
 // Shapes the persistent kernel takes (everything else stays on the HIP kernels): D = 128 or 64; the fast variant (one P operand, 16-bit
 // store) or the parity variant (split P AND fp32 store); no element mask; Sq >= 128 and Sk >= 193 of any length (ragged: *_kl_*); a
-// [B, Sk] key mask with contiguous rows on whole blocks / tile pairs (*_km_*: the kernel reads the bytes itself); seqlens_k without the
+// [B, Sk] key mask with contiguous rows (key_mask_stride_b == Sk, B * Sk below 2^31) on the same lengths, ragged ones included (*_km_*:
+// the kernel reads the bytes itself); seqlens_k without the
 // causal mask (an item's tile count is cut to its batch's keys), and with it on the ragged kernels (round 3: a block behind its batch's cut
 // runs the tiles of the visible keys without a diagonal); under the causal mask Sq == Sk (units are heavy + light block pairs, with an odd
 // block count the middle block is a unit of its own).
@@ -197,7 +200,7 @@ int p4_launch(const pfa_fa3_args* a, void* stream, int* hip_err) {
     p.NB = (uint32_t)((a->Sq + 255) / 256);
     p.NU = a->causal ? (p.NB + 1) / 2 : p.NB;
     p.magic_NU = magic(p.NU); p.magic_H = magic(p.H);
-    p.kv_group = a->kv_group > 1 ? (uint32_t)a->kv_group : 1u;
+    p.kv_group = (uint32_t)kv_group_of(a);
     p.magic_G = magic(p.kv_group);
     p.scale_log2 = a->softmax_scale * pfa::LOG2E;
     p.thr = 8.0f / p.scale_log2;

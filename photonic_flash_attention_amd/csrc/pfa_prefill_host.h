@@ -69,9 +69,7 @@ int launch(const Args* a, int window, void* stream) {
     const int lds = 2 * 2 * BLOCK_N * a->D * 2;      // two buffers of a K and a V tile image (<= 64 KiB)
     const DeviceScope dev(a->device_id);
     if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: the base, or all of it
-    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)workgroups(a)), dim3(FWD_THREADS), kargs, (size_t)lds, (hipStream_t)stream);
-    return hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    return pfa::launch(fn, dim3((unsigned)workgroups(a)), FWD_THREADS, p, (size_t)lds, stream);
 }
 
 }  // namespace prefill

@@ -140,10 +140,8 @@ int pfa_fa3_prefill_split(const pfa_fa3_decode_args* a, int32_t key_splits, void
     {
         const pfa::DeviceScope dev(a->device_id);
         if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-        void* kargs[] = {&p};
-        const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(pfa::prefill::workgroups(a) * ns)), dim3(pfa::FWD_THREADS), kargs, (size_t)lds,
-                                             (hipStream_t)stream);
-        if (pfa::hip_failed(e)) return PFA_ERR_LAUNCH;
+        const int st_main = pfa::launch(fn, dim3((unsigned)(pfa::prefill::workgroups(a) * ns)), pfa::FWD_THREADS, p, (size_t)lds, stream);
+        if (st_main != PFA_OK) return st_main;
     }
     const pfa_attn_merge_args m = merge_args(a, ns);
     return pfa_attn_merge(&m, stream);

@@ -109,9 +109,7 @@ int pfa_rope_append(const pfa_rope_append_args* a, void* stream) {
     const void* fn = a->dtype == PFA_DTYPE_BF16 ? kernel_of<__bf16>(varlen, paged, il) : kernel_of<_Float16>(varlen, paged, il);
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    void* kargs[] = {&p};
-    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)workgroups(a)), dim3(pfa::ROPE_APPEND_THREADS), kargs, 0, (hipStream_t)stream);
-    return pfa::hip_failed(e) ? PFA_ERR_LAUNCH : PFA_OK;
+    return pfa::launch(fn, dim3((unsigned)workgroups(a)), pfa::ROPE_APPEND_THREADS, p, 0, stream);
 }
 
 }  // extern "C"

@@ -119,6 +119,41 @@ def _as_mask4(mask: torch.Tensor, B: int, H: int, Sq: int, Sk: int, device) -> t
     return m
 
 
+def _set_element_mask(a, mask, B: int, H: int, Sq: int, Sk: int, device, keep: list) -> None:
+    """The element-mask fields of ``pfa_fa3_args`` / ``pfa_fa3_bwd_args``: the ``_as_mask4`` form of ``mask`` (appended to ``keep``)
+    with its byte strides, 0 for a broadcast dim."""
+    m4 = _as_mask4(mask, B, H, Sq, Sk, device)
+    a.mask = m4.data_ptr()
+    st = [0 if m4.shape[i] == 1 else m4.stride(i) for i in range(4)]
+    a.mask_stride_b, a.mask_stride_h, a.mask_stride_q, a.mask_stride_k = st[0], st[1], st[2], (st[3] or 1)
+    keep.append(m4)
+
+
+_STRIDE_FIELDS = {name: tuple(f"{'do' if name == 'dout' else name}_stride_{axis}" for axis in "bhs")
+                  for name in ("q", "k", "v", "o", "dout", "dq", "dk", "dv")}
+
+
+def _set_strides(a, fields) -> None:
+    """``fields``: (pointer field, tensor) pairs of ``[B,H,S,D]``-shaped tensors -> the pointers and the ``*_stride_b/h/s`` triplets
+    (``dout``'s strides are the ``do_stride_*`` fields)."""
+    for name, t in fields:
+        setattr(a, name, t.data_ptr())
+        fb, fh, fs = _STRIDE_FIELDS[name]
+        sb, sh, ss = _bhsd_strides(t)
+        setattr(a, fb, sb); setattr(a, fh, sh); setattr(a, fs, ss)
+
+
+def _lse_ptr(lse: torch.Tensor, B: int, H: int, Sq: int) -> int:
+    if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("lse must be contiguous fp32 [B, H, Sq]")
+    return lse.data_ptr()
+
+
+def _scale(softmax_scale: Optional[float], D: int) -> float:
+    """The softmax scale handed to the library: the caller's, or ``1 / sqrt(D)``."""
+    return float(D ** -0.5 if softmax_scale is None else softmax_scale)
+
+
 _ARANGE1 = {}
 
 
@@ -155,20 +190,15 @@ def build_args(q, k, v, out, *, causal=False, seqlens_k=None, key_mask=None, sof
         raise ValueError("fp32 operands run the exact fp32 kernel: no split P, no kernel selector")
     if not (q.is_cuda and k.is_cuda and v.is_cuda and out.is_cuda):
         raise ValueError("pfa_fa3_fwd needs device tensors (there is no CPU path)")
-    qs, ks, vs, os_ = (_bhsd_strides(t) for t in (q, k, v, out))
     a = _capi.make_args(
         flags=(_capi.PFA_FLAG_SPLIT_P if split_p else 0) | ((int(variant) & 0xFF) << 8),
-        q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), o=out.data_ptr(),
-        q_stride_b=qs[0], q_stride_h=qs[1], q_stride_s=qs[2],
-        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2],
-        v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
-        o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2],
         B=B, H=H, Sq=Sq, Sk=Sk, D=D,
         dtype_in=_DT[q.dtype], dtype_out=_DT[out.dtype], causal=1 if causal else 0,
-        softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
+        softmax_scale=_scale(softmax_scale, D),
         device_id=_device_index(q.device),
         kv_group=H // Hkv,
     )
+    _set_strides(a, (("q", q), ("k", k), ("v", v), ("o", out)))
     keep = []
     if seqlens_k is not None:
         sl = _seqlens_tensor(seqlens_k, q.device)
@@ -199,11 +229,7 @@ def build_args(q, k, v, out, *, causal=False, seqlens_k=None, key_mask=None, sof
     if mask is not None:
         if key_mask is not None:
             raise ValueError("pass either key_mask or mask")
-        m4 = _as_mask4(mask, B, H, Sq, Sk, q.device)
-        a.mask = m4.data_ptr()
-        st = [0 if m4.shape[i] == 1 else m4.stride(i) for i in range(4)]
-        a.mask_stride_b, a.mask_stride_h, a.mask_stride_q, a.mask_stride_k = st[0], st[1], st[2], (st[3] or 1)
-        keep.append(m4)
+        _set_element_mask(a, mask, B, H, Sq, Sk, q.device, keep)
     if key_mask is not None or mask is not None:
         # scratch for the mask condensed to one 64-bit word per row and 64-key tile (pfa_fa3_workspace_bytes; optional for the
         # C ABI, always given here): a padding mask then costs about what seqlens_k costs, an element mask 1/3 of the byte path
@@ -213,9 +239,7 @@ def build_args(q, k, v, out, *, causal=False, seqlens_k=None, key_mask=None, sof
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
             keep.append(ws)
     if lse is not None:
-        if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
-            raise ValueError("lse must be contiguous fp32 [B, H, Sq]")
-        a.lse = lse.data_ptr()
+        a.lse = _lse_ptr(lse, B, H, Sq)
     if drop_mask is not None:
         a.drop_mask, a.drop_scale = _drop_mask_ptr(drop_mask, B, H, Sq, Sk, q), float(drop_scale)
         keep.append(drop_mask)
@@ -247,7 +271,7 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
         # extra output columns are zero and dropped).  The scale stays the TRUE head dim's.
         res = fa3_forward(_pad_d(q, Dp), _pad_d(k, Dp), _pad_d(v, Dp), causal=causal, seqlens_k=seqlens_k,
                           key_mask=key_mask, mask=mask,
-                          softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale), out_dtype=out_dtype,
+                          softmax_scale=_scale(softmax_scale, D), out_dtype=out_dtype,
                           return_lse=return_lse, return_weights=return_weights, weights_dtype=weights_dtype,
                           split_p=split_p, drop_mask=drop_mask, drop_scale=drop_scale, _variant=_variant)
         o = res[0][..., :D]
@@ -332,7 +356,7 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
     if Dp != D:   # as in fa3_forward: zero-padded head dim; the gradients' extra columns are exactly zero and dropped
         grads = fa3_backward(_pad_d(q, Dp), _pad_d(k, Dp), _pad_d(v, Dp), _pad_d(out, Dp), _pad_d(dout, Dp), lse,
                              causal=causal, seqlens_k=seqlens_k, key_mask=key_mask, mask=mask,
-                             softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
+                             softmax_scale=_scale(softmax_scale, D),
                              grad_dtype=grad_dtype, drop_mask=drop_mask, drop_scale=drop_scale)
         return tuple(g[..., :D] for g in grads)
     gdt = q.dtype if grad_dtype is None else grad_dtype
@@ -344,14 +368,8 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
     delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     a = _capi.PfaFa3BwdArgs()
     a.size = C.sizeof(_capi.PfaFa3BwdArgs)
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", out), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
-        setattr(a, name, t.data_ptr())
-        sb, sh, ss = _bhsd_strides(t)
-        pre = "do" if name == "dout" else name
-        setattr(a, f"{pre}_stride_b", sb); setattr(a, f"{pre}_stride_h", sh); setattr(a, f"{pre}_stride_s", ss)
-    if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
-        raise ValueError("lse must be contiguous fp32 [B, H, Sq]")
-    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
+    _set_strides(a, (("q", q), ("k", k), ("v", v), ("o", out), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)))
+    a.lse, a.delta = _lse_ptr(lse, B, H, Sq), delta.data_ptr()
     keep = [delta]
     if seqlens_k is not None:
         sl = _seqlens_tensor(seqlens_k, q.device)
@@ -364,18 +382,14 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
             raise ValueError("key_mask must be [B, Sk]")
         mask = key_mask
     if mask is not None:
-        m4 = _as_mask4(mask, B, H, Sq, Sk, q.device)
-        a.mask = m4.data_ptr()
-        st = [0 if m4.shape[i] == 1 else m4.stride(i) for i in range(4)]
-        a.mask_stride_b, a.mask_stride_h, a.mask_stride_q, a.mask_stride_k = st[0], st[1], st[2], (st[3] or 1)
-        keep.append(m4)
+        _set_element_mask(a, mask, B, H, Sq, Sk, q.device, keep)
     if drop_mask is not None:
         a.drop_mask, a.drop_scale = _drop_mask_ptr(drop_mask, B, H, Sq, Sk, q), float(drop_scale)
         keep.append(drop_mask)
     a.B, a.H, a.Sq, a.Sk, a.D = B, H, Sq, Sk, D
     a.kv_group = H // Hkv
     a.dtype, a.dtype_grad, a.causal = _DT[q.dtype], _DT[gdt], 1 if causal else 0
-    a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
+    a.softmax_scale = _scale(softmax_scale, D)
     a.device_id = _device_index(q.device)
     stream = torch.cuda.current_stream(q.device)
     if a.mask:   # element masks: scratch for the condensed words / tile ranges (0 bytes for key-only masks; optional for the library)
@@ -537,7 +551,7 @@ def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out
         q_stride_b=qs[0], q_stride_h=qs[1], q_stride_s=qs[2], k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2],
         v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2], o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2],
         B=B, H=H, Hkv=Hkv, Sq=Sq, Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt], causal=1 if causal else 0,
-        softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
+        softmax_scale=_scale(softmax_scale, D),
         device_id=_device_index(q.device))
     if block_table is not None:
         a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
@@ -1357,7 +1371,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         q_stride_s=q.stride(0), q_stride_h=q.stride(1), o_stride_s=out.stride(0), o_stride_h=out.stride(1),
         k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
         B=B, H=H, Hkv=Hkv, total_q=total_q, max_seqlen_q=int(max_seqlen_q), Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt],
-        causal=1 if causal else 0, softmax_scale=float(D ** -0.5 if softmax_scale is None else softmax_scale),
+        causal=1 if causal else 0, softmax_scale=_scale(softmax_scale, D),
         device_id=_device_index(q.device))
     if block_table is not None:
         a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)

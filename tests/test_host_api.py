@@ -66,6 +66,11 @@ def test_argument_validation_without_a_gpu(lib):
     ]
     for over, want in cases:
         assert lib.pfa_fa3_check(C.byref(_args(**over))) == want, over
+    f32 = dict(dtype_in=2, dtype_out=2)           # the exact fp32 kernel's branch: no split P, 16-byte rows at least D apart, 32-bit slabs
+    assert lib.pfa_fa3_check(C.byref(_args(**f32))) == 0
+    for over, want in [(dict(flags=1), -10), (dict(q_stride_b=8190), -6), (dict(k_stride_s=32), -6), (dict(o=0x4002), -7),
+                       (dict(Sq=1 << 23), -3)]:
+        assert lib.pfa_fa3_check(C.byref(_args(**f32, **over))) == want, over
     bad = _args()
     bad.size = 8
     assert lib.pfa_fa3_check(C.byref(bad)) == -2
