@@ -15,6 +15,8 @@
  * v9, additive: pfa_rope_append* -- rotary embedding fused into that append: Q and the new K rotated by positions derived on the device.
  * v9, additive: pfa_attn_merge* -- the merge of partial attention results (O, LSE) over disjoint key sets into the result over their
  * union: what a shared prefix computed once per batch, a split over keys or keys spread over several GPUs need behind them.
+ * v9, additive: pfa_page_copy* -- whole or partial pages copied inside the pools of a paged cache from a device pair list: the data
+ * movement of copy-on-write for sequences that share pages.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -545,7 +547,7 @@ int pfa_fa3_prefill_split_describe(const pfa_fa3_decode_args* a, int32_t key_spl
  * and table entries other than those of the destination rows.  Never written: anything but the destination rows, in cache or pool
  * (lengths and table included).
  * If two sequences are given the same destination (a shared prefix page handed to two writers) the row ends up as one of the two.
- * Copy-on-write of shared pages is the caller's business.
+ * Copy-on-write of shared pages is pfa_page_copy (below) in front of this call; PagedKVCache(copy_on_write=True) drives it.
  *
  * One launch; no workspace, no atomics, no LDS.  bf16 / fp16 (any 2-byte type moves the same way), D a multiple of 8 up to 256, strides
  * multiples of 8 elements, base pointers 16-byte aligned: K and V move as 16-byte loads and stores.
@@ -754,6 +756,61 @@ int pfa_attn_merge(const pfa_attn_merge_args* a, void* stream);
 /* Introspection: the kernel name attn_merge_{bf16|fp16|fp32}_{bf16|fp16|fp32}_d{D}_n{N} (part dtype, then output dtype) into buf (NUL
  * terminated, truncated to n); returns the workgroups, or a pfa_status. */
 int pfa_attn_merge_describe(const pfa_attn_merge_args* a, char* buf, size_t n);
+
+/*
+ * Page copy inside a paged KV cache's pools (ABI v9, additive): the data movement of copy-on-write.  Copies whole or partial pages of
+ * the K pool and of the V pool from a device pair list -- what vLLM's copy_blocks does -- so that the first write of a sequence forked
+ * from another (parallel sampling, beam search, a cached prefix) costs one launch and no host round trip, capturable with the step.
+ *
+ * Pair i is (s, d) = (pairs[i * pairs_stride], pairs[i * pairs_stride + 1]).
+ *   - The pair is EMPTY when s or d lies outside [0, num_pages - 1], or when s == d; -1 is the documented "no copy" marker.  An empty
+ *     pair reads nothing and writes nothing.
+ *   - Otherwise tokens [0, r_i) of K page s go to K page d, and the same for V: r_i = page_size when rows is NULL, else
+ *     r_i = clamp(rows[i], 0, page_size).  Tokens >= r_i of page d are not written.
+ * Bad device data can lose a copy; it never yields an address outside the pools (s and d are range-checked, r_i is clamped).
+ * The caller promises: no page is the destination of two non-empty pairs, no destination is the source of another non-empty pair, and
+ * the pages of a pool do not overlap.  Under that promise a replay is idempotent.  Breaking it leaves a destination as one of the
+ * candidate values, with every address still inside the pools.
+ *
+ *   k_pool, v_pool  pools [num_pages, page_size, Hkv, D] by element strides (last dim contiguous), *_stride_b the PAGE strides exactly
+ *                   as pfa_kv_append_args gives them: token t of head hk of page g is at pool + g * stride_b + t * stride_s + hk * stride_h.
+ *                   Head-major and token-major (flash-attn) pools both work.
+ *   pairs           int32 device [n_pairs][2], rows pairs_stride (>= 2) elements apart.
+ *   rows            int32 device [n_pairs], or NULL = whole pages.
+ *
+ * One launch of n_pairs * ceil(page_size * Hkv * (D / 8) / 1024) workgroups, from host shapes only: a captured graph stays valid while
+ * pairs, rows and the pools change between replays, and the workgroups of an empty pair return before any vector memory instruction.
+ * No workspace, no atomics, no LDS.  bf16 / fp16 (any 2-byte type moves the same way): K and V move as 16-byte loads and stores.
+ *
+ * Field rules, in the order their errors are reported: size wrong -> PFA_ERR_STRUCT_SIZE; flags / reserved0 non-zero -> PFA_ERR_FLAGS;
+ * k_pool, v_pool or pairs NULL -> PFA_ERR_NULL; n_pairs, Hkv or num_pages < 1, or page_size not a positive multiple of 64 ->
+ * PFA_ERR_SHAPE; D not a multiple of 8 in [8, 256] -> PFA_ERR_HEAD_DIM; dtype not bf16 / fp16 -> PFA_ERR_DTYPE; a pool stride not a
+ * multiple of 8, a negative token stride, or pairs_stride < 2 -> PFA_ERR_STRIDE; a pool base not 16-byte aligned, pairs / rows not
+ * 4-byte aligned -> PFA_ERR_ALIGN; more workgroups than a grid holds, or page_size * Hkv * (D / 8) + 1024 past 2^31 - 1 -> PFA_ERR_SHAPE.
+ */
+typedef struct pfa_page_copy_args {
+    uint32_t size;              /* = sizeof(pfa_page_copy_args) */
+    uint32_t flags;             /* must be 0 */
+    void* k_pool;
+    void* v_pool;
+    const int32_t* pairs;       /* device [n_pairs][2] = (src, dst), row stride pairs_stride (>= 2) */
+    const int32_t* rows;        /* device [n_pairs], or NULL = whole pages */
+    int64_t pairs_stride;
+    int64_t k_stride_b, k_stride_h, k_stride_s;   /* page, head, token */
+    int64_t v_stride_b, v_stride_h, v_stride_s;
+    int32_t n_pairs, Hkv, D, page_size, num_pages;
+    int32_t dtype;              /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 */
+    int32_t device_id;
+    int32_t reserved0;          /* must be 0 */
+} pfa_page_copy_args;
+
+/* Validate `a` without launching: PFA_OK or the error pfa_page_copy would return. */
+int pfa_page_copy_check(const pfa_page_copy_args* a);
+/* Enqueue the copy (one launch) on `stream`. */
+int pfa_page_copy(const pfa_page_copy_args* a, void* stream);
+/* Introspection: the kernel name page_copy_{bf16|fp16}_d{D} ("_rows" appended with rows) into buf (NUL terminated, truncated to n);
+ * returns the workgroups, or a pfa_status. */
+int pfa_page_copy_describe(const pfa_page_copy_args* a, char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

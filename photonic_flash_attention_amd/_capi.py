@@ -134,12 +134,24 @@ class PfaAttnMergeArgs(C.Structure):
     )
 
 
+class PfaPageCopyArgs(C.Structure):
+    """Mirror of ``struct pfa_page_copy_args`` (include/pfa_hip.h): the page copy inside a paged cache's pools."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("k_pool", "v_pool", "pairs", "rows")]
+        + [("pairs_stride", C.c_int64)]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "kv" for a in "bhs"]
+        + [(n, C.c_int32) for n in ("n_pairs", "Hkv", "D", "page_size", "num_pages", "dtype", "device_id", "reserved0")]
+    )
+
+
 def _prototypes():
     """Export name -> ``(restype, argtypes)``, one row per symbol ``include/pfa_hip.h`` declares (argtypes None: left untyped)."""
     i, sz, vp, buf = C.c_int, C.c_size_t, C.c_void_p, [C.c_char_p, C.c_size_t]
     fa3, bwd, dec, var, app, ext, rope, mrg = (C.POINTER(t) for t in (PfaFa3Args, PfaFa3BwdArgs, PfaFa3DecodeArgs, PfaFa3PrefillVarlenArgs,
                                                                       PfaKvAppendArgs, PfaFa3CacheExt, PfaRopeAppendArgs, PfaAttnMergeArgs))
     ns = [C.POINTER(C.c_int32)]
+    pcp = C.POINTER(PfaPageCopyArgs)
     return {
         "pfa_abi_version": (i, None),
         "pfa_status_string": (C.c_char_p, [i]),
@@ -189,6 +201,9 @@ def _prototypes():
         "pfa_attn_merge_check": (i, [mrg]),
         "pfa_attn_merge": (i, [mrg, vp]),
         "pfa_attn_merge_describe": (i, [mrg] + buf),
+        "pfa_page_copy_check": (i, [pcp]),
+        "pfa_page_copy": (i, [pcp, vp]),
+        "pfa_page_copy_describe": (i, [pcp] + buf),
     }
 
 
@@ -361,3 +376,12 @@ def make_attn_merge_args(**kw) -> PfaAttnMergeArgs:
 def describe_attn_merge(args: PfaAttnMergeArgs):
     """-> (kernel name, workgroups) of ``pfa_attn_merge``: ``ceil(B * Sq * H * (D / 8) / 256)``, from host shapes only."""
     return _describe("pfa_attn_merge_describe", args)
+
+
+def make_page_copy_args(**kw) -> PfaPageCopyArgs:
+    return _make(PfaPageCopyArgs, kw)
+
+
+def describe_page_copy(args: PfaPageCopyArgs):
+    """-> (kernel name, workgroups) of ``pfa_page_copy``: ``n_pairs * ceil(page_size * Hkv * (D / 8) / 1024)``, from host shapes only."""
+    return _describe("pfa_page_copy_describe", args)

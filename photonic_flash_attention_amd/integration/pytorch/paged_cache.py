@@ -16,6 +16,15 @@ Everything except ``decode``, ``prefill`` and ``prefill_varlen`` (the HIP kernel
 capturable form splits the append in two: ``advance`` (host: pages, lengths, table) and ``write_step`` (device: ``ops.kv_append``, the
 HIP copy kernel that places the rows from the device table and lengths).  ``advance`` then ``write_step`` equals ``append_varlen``; a
 graph holds ``write_step`` + ``prefill_varlen``, and ``advance`` runs between replays.
+
+With ``copy_on_write=True`` sequences may share pages.  ``fork`` starts a new sequence from an existing one's first keys by sharing
+the pages that hold them (parallel sampling, beam search, a cached prefix): it moves no K / V and needs no free page.  Every page has a
+reference count; ``free`` and ``release_behind_window`` return a page to the pool only when its last holder lets go.  A slot that
+appends into a partly filled tail page it shares takes a fresh page first and the filled rows are copied over by ``ops.page_copy``
+(the HIP page-copy kernel): at once in ``append`` / ``append_varlen``, and for ``advance`` from the device tensors ``cow_pairs`` /
+``cow_rows`` at the head of ``write_step``, so that a captured step replays through forks.  Full shared pages are never written, so
+they are never copied, and ``common_prefix`` names the keys a group of slots shares page for page: the ``shared_prefix=`` of
+``decode`` / ``prefill`` / ``prefill_varlen``.
 """
 
 from __future__ import annotations
@@ -38,10 +47,19 @@ class PagedKVCache:
 
     A *slot* is a row of ``block_table`` / ``cache_seqlens``: ``allocate`` hands one out, ``free`` takes it back with its pages.
     A slot that is not allocated has length 0, so a ``decode`` over all slots returns zeros for it and reads none of its entries.
+
+    ``copy_on_write=True`` adds page sharing: ``fork``, per-page reference counts (``page_refcount``), the copy of a shared, partly
+    filled tail page in front of the first write into it, and ``common_prefix``.  The copies an ``advance`` calls for wait in the
+    device tensors ``cow_pairs`` / ``cow_rows`` (the pending table) for the ``write_step`` behind it.  Ordering contract: every call
+    that changes page ownership -- ``append``, ``append_varlen``, ``advance``, ``fork``, ``free``, ``release_behind_window``,
+    ``swap_pages`` -- first resets the pending table to empty (``advance`` then fills in its own entries), so the ``write_step`` of an
+    ``advance`` must be enqueued, on the same stream, before the next such call.  With ``copy_on_write=False`` (the default) nothing
+    is shared, no extra tensor exists, no extra launch is made, and ``fork`` raises ``ValueError``.
     """
 
     def __init__(self, num_pages: int, page_size: int, Hkv: int, D: int, dtype: torch.dtype = torch.bfloat16,
-                 device: Union[str, torch.device] = "cuda", max_batch: int = 1, max_pages_per_seq: Optional[int] = None):
+                 device: Union[str, torch.device] = "cuda", max_batch: int = 1, max_pages_per_seq: Optional[int] = None,
+                 copy_on_write: bool = False):
         if page_size < 64 or page_size % 64:
             raise ValueError(f"page size {page_size}: must be a multiple of 64 keys (a key tile of the kernel lies inside one page)")
         if num_pages < 1 or Hkv < 1 or D < 1 or max_batch < 1:
@@ -61,6 +79,14 @@ class PagedKVCache:
         self._pages: List[List[int]] = [[] for _ in range(max_batch)]
         self._live: List[bool] = [False] * max_batch
         self._free_pages: List[int] = list(range(num_pages - 1, -1, -1))      # popped from the end: lowest id first
+        self._ref: List[int] = [0] * num_pages                                # holders per page; never above 1 without copy_on_write
+        self._cow = bool(copy_on_write)
+        self._copies: List[Tuple[int, int, int, int]] = []                    # (slot, old page, new page, rows) of the last _grow
+        self._cow_pairs = self._cow_rows = None
+        self._pending = False                                                 # the device pending table holds an entry
+        if self._cow:
+            self._cow_pairs = torch.full((max_batch, 2), -1, dtype=torch.int32, device=self.device)
+            self._cow_rows = torch.full((max_batch,), -1, dtype=torch.int32, device=self.device)
 
     # --- device tensors (the same storage for the cache's lifetime) ---------------------------------------------------------------
     @property
@@ -72,6 +98,17 @@ class PagedKVCache:
     def cache_seqlens(self) -> torch.Tensor:
         """int32 ``[max_batch]``: tokens held per slot."""
         return self._lens
+
+    @property
+    def cow_pairs(self) -> Optional[torch.Tensor]:
+        """int32 ``[max_batch, 2]`` (None without ``copy_on_write``): the pending table's ``(old page, new page)``, row = slot, of the
+        copies the last ``advance`` calls for; -1 = none.  ``write_step`` hands it to ``ops.page_copy``."""
+        return self._cow_pairs
+
+    @property
+    def cow_rows(self) -> Optional[torch.Tensor]:
+        """int32 ``[max_batch]`` (None without ``copy_on_write``): the filled rows of each pending copy; -1 = none."""
+        return self._cow_rows
 
     @property
     def k_pool(self) -> torch.Tensor:
@@ -95,6 +132,12 @@ class PagedKVCache:
         page ``release_behind_window`` gave back."""
         return tuple(self._pages[self._check_slot(slot)])
 
+    def page_refcount(self, page: int) -> int:
+        """Slots holding the page (0: it is free).  Above 1 only with ``copy_on_write``."""
+        if not 0 <= page < self.num_pages:
+            raise ValueError(f"page {page}: the pool has {self.num_pages}")
+        return self._ref[page]
+
     def _check_slot(self, slot: int) -> int:
         if not 0 <= slot < self.max_batch or not self._live[slot]:
             raise ValueError(f"slot {slot} is not allocated")
@@ -111,16 +154,35 @@ class PagedKVCache:
             return
         first = len(self._pages[slot])
         new = [self._free_pages.pop() for _ in range(count)]
+        for pg in new:
+            self._ref[pg] = 1
         self._pages[slot].extend(new)
         self._table[slot, first:first + count] = torch.tensor(new, dtype=torch.int32)
 
-    def allocate(self, n_tokens: int = 0) -> int:
-        """Take a free slot and assign it pages for ``n_tokens`` tokens (its length stays 0).  -> slot."""
+    def _let_go(self, pages) -> None:
+        """The slot's hold on each page, in the given order; a page goes back to the pool when no slot holds it any more."""
+        for pg in pages:
+            self._ref[pg] -= 1
+            if self._ref[pg] == 0:
+                self._free_pages.append(pg)
+
+    def _reset_pending(self) -> None:
+        """Empty the pending table (skipped when the host mirror knows it is empty)."""
+        self._copies = []
+        if self._pending:
+            self._cow_pairs.fill_(-1)
+            self._cow_rows.fill_(-1)
+            self._pending = False
+
+    def _free_slot(self) -> int:
         for slot in range(self.max_batch):
             if not self._live[slot]:
-                break
-        else:
-            raise PagedCacheFull(f"all {self.max_batch} slots are in use")
+                return slot
+        raise PagedCacheFull(f"all {self.max_batch} slots are in use")
+
+    def allocate(self, n_tokens: int = 0) -> int:
+        """Take a free slot and assign it pages for ``n_tokens`` tokens (its length stays 0).  -> slot."""
+        slot = self._free_slot()
         self._live[slot] = True
         try:
             self.reserve(slot, n_tokens)
@@ -138,10 +200,12 @@ class PagedKVCache:
         self._assign(slot, missing)
 
     def free(self, slot: int) -> None:
-        """Give the slot and its pages back (those not released already).  The pages' contents and the table row stay as they
-        are; neither is read again."""
+        """Give the slot back and let go of its pages (those not released already): a page returns to the pool unless another
+        slot still holds it (``copy_on_write``).  The pages' contents and the table row stay as they are; the slot reads neither
+        again.  Resets the pending copy-on-write table first (see the class's ordering contract)."""
         self._check_slot(slot)
-        self._free_pages.extend(pg for pg in reversed(self._pages[slot]) if pg >= 0)
+        self._reset_pending()
+        self._let_go(pg for pg in reversed(self._pages[slot]) if pg >= 0)
         self._pages[slot] = []
         self._host_lens[slot] = 0
         self._live[slot] = False
@@ -150,14 +214,15 @@ class PagedKVCache:
     def release_behind_window(self, slot: int, window: int) -> int:
         """Return to the pool every page of the slot that lies wholly behind a sliding window of ``window`` keys: logical page p
         with ``(p + 1) * page_size <= max(0, length(slot) - window + 1)``, the lowest key the sequence's newest row sees.  -> the
-        number of pages released by this call.
+        number of entries this slot let go in this call (a page another slot still holds stays alive: ``copy_on_write``).
 
         The slot keeps its length and logical positions: later appends go where they would have gone and take fresh pages.  The
         released table entries are overwritten with -1 and ``pages()`` reports -1 for them.  Afterwards the slot may only be read
         with ``window=`` this value or smaller, by calls whose query rows are the tokens appended since (one decode row, a chunk,
         a ragged step): such a call's lowest visible key is at or above the bound used here, and the kernels read neither a key
         below that key's 64-key boundary nor its table entry.  ``gather`` and ``swap_pages`` refuse a released page.  Host-side
-        bookkeeping plus one small table write; works on CPU tensors."""
+        bookkeeping plus one small table write; works on CPU tensors.  Resets the pending copy-on-write table first (see the class's
+        ordering contract)."""
         self._check_slot(slot)
         if isinstance(window, bool) or not isinstance(window, int) or window < 1:
             raise ValueError(f"window must be an integer >= 1, got {window!r}")
@@ -166,7 +231,8 @@ class PagedKVCache:
         gone = [p for p in range(behind) if pg[p] >= 0]
         if not gone:
             return 0
-        self._free_pages.extend(pg[p] for p in reversed(gone))
+        self._reset_pending()
+        self._let_go(pg[p] for p in reversed(gone))
         for p in gone:
             pg[p] = -1
         self._table[slot, gone[0]:behind] = -1           # every entry in front of it went in an earlier call
@@ -174,16 +240,46 @@ class PagedKVCache:
 
     def _grow(self, slots: List[int], lens: List[int]) -> List[int]:
         """The host half of an append, all or nothing: assign the pages ``lens[i]`` more tokens of ``slots[i]`` need and advance the
-        host lengths.  -> each slot's length before."""
+        host lengths.  -> each slot's length before.
+
+        Copy-on-write: a slot that gains a token while its tail page is partly filled and held by another slot as well takes a fresh
+        page in its place (counted in the all-or-nothing check) and lets go of the old one; ``(slot, old, new, filled rows)`` is
+        recorded in ``_copies`` for the caller to run.  Slots are served in order, so of the holders of one tail page the last keeps it."""
         missing = [self._pages_missing(self._check_slot(s), self._host_lens[s] + x) for s, x in zip(slots, lens)]
-        if sum(missing) > len(self._free_pages):
-            raise PagedCacheFull(f"the append needs {sum(missing)} more pages, the pool has {len(self._free_pages)} free")
+        cow, let_go = set(), {}
+        if self._cow:
+            for s, x in zip(slots, lens):
+                n = self._host_lens[s]
+                if x > 0 and n % self.page_size:
+                    pg = self._pages[s][n // self.page_size]
+                    if self._ref[pg] - let_go.get(pg, 0) > 1:
+                        let_go[pg] = let_go.get(pg, 0) + 1
+                        cow.add(s)
+        if sum(missing) + len(cow) > len(self._free_pages):
+            raise PagedCacheFull(f"the append needs {sum(missing) + len(cow)} more pages, the pool has {len(self._free_pages)} free")
+        self._reset_pending()
         starts = []
         for s, m, x in zip(slots, missing, lens):
+            if s in cow:
+                p, filled = divmod(self._host_lens[s], self.page_size)
+                old, new = self._pages[s][p], self._free_pages.pop()
+                self._ref[new] = 1
+                self._ref[old] -= 1
+                self._pages[s][p] = new
+                self._table[s, p] = new
+                self._copies.append((s, old, new, filled))
             self._assign(s, m)
             starts.append(self._host_lens[s])
             self._host_lens[s] += x
         return starts
+
+    def _copy_now(self) -> None:
+        """Run the copies the last ``_grow`` recorded (``ops.page_copy``, one launch) and forget them."""
+        if self._copies:
+            pairs = torch.tensor([c[1:3] for c in self._copies], dtype=torch.int32).to(self.device, non_blocking=True)
+            rows = torch.tensor([c[3] for c in self._copies], dtype=torch.int32).to(self.device, non_blocking=True)
+            ops.page_copy(self._k.transpose(1, 2), self._v.transpose(1, 2), pairs, rows=rows)
+            self._copies = []
 
     def _dst_rows(self, slots: List[int], starts: List[int], lens: List[int]) -> List[int]:
         """Row of the ``[num_pages * page_size]`` token view each appended token goes to."""
@@ -192,7 +288,9 @@ class PagedKVCache:
 
     def append(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor) -> None:
         """Write ``k_new`` / ``v_new`` ``[n, Hkv, Sq, D]`` at the current end of each of the ``n`` slots and advance their lengths.
-        Pages are assigned as needed; if the pool cannot serve all of them nothing is written and ``PagedCacheFull`` is raised."""
+        Pages are assigned as needed; if the pool cannot serve all of them nothing is written and ``PagedCacheFull`` is raised.
+        With ``copy_on_write`` a shared, partly filled tail page is copied to a fresh page first (``ops.page_copy``), and the pending
+        table is reset (see the class's ordering contract)."""
         slots = [slots] if isinstance(slots, int) else list(slots)
         n = len(slots)
         if len(set(slots)) != n:
@@ -203,6 +301,7 @@ class PagedKVCache:
             raise ValueError("k_new / v_new must have the cache's dtype")
         Sq = k_new.shape[2]
         dst = self._dst_rows(slots, self._grow(slots, [Sq] * n), [Sq] * n)
+        self._copy_now()
         if Sq:
             idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
             rows = self.num_pages * self.page_size
@@ -213,7 +312,8 @@ class PagedKVCache:
     def append_varlen(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor, lens: Sequence[int]) -> None:
         """``append`` for a different number of tokens per slot: ``k_new`` / ``v_new`` are packed ``[total, Hkv, D]``, slot
         ``slots[i]`` takes the next ``lens[i]`` tokens (a host list, 0 allowed; ``sum(lens) == total``) at its current end.  All or
-        nothing: if the pool cannot serve every slot nothing is written and ``PagedCacheFull`` is raised."""
+        nothing: if the pool cannot serve every slot nothing is written and ``PagedCacheFull`` is raised.  Copy-on-write as in
+        ``append``."""
         slots = [slots] if isinstance(slots, int) else list(slots)
         lens = [int(x) for x in lens]
         n, total = len(slots), sum(lens)
@@ -226,6 +326,7 @@ class PagedKVCache:
         if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
             raise ValueError("k_new / v_new must have the cache's dtype")
         dst = self._dst_rows(slots, self._grow(slots, lens), lens)
+        self._copy_now()
         if total:
             idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
             rows = self.num_pages * self.page_size
@@ -238,7 +339,12 @@ class PagedKVCache:
         pages, updates the host mirror and refreshes the device table and lengths in place; moves no K / V.  All or nothing: if the
         pool cannot serve every slot nothing changes and ``PagedCacheFull`` is raised.  ``write_step`` is the device half:
         ``advance(slots, lens)`` followed by ``write_step(k_new, v_new, lens, slots)`` equals ``append_varlen(slots, k_new, v_new,
-        lens)``.  A graph user captures ``write_step`` + ``prefill_varlen`` once and calls ``advance`` between replays."""
+        lens)``.  A graph user captures ``write_step`` + ``prefill_varlen`` once and calls ``advance`` between replays.
+
+        With ``copy_on_write`` the copies of shared tail pages this step calls for are written, whole and in place, into ``cow_pairs``
+        / ``cow_rows`` (row = slot) for ``write_step`` to run; the table is reset first.  Ordering contract: enqueue this step's
+        ``write_step``, on the same stream, before the next call that changes page ownership (``append``, ``append_varlen``,
+        ``advance``, ``fork``, ``free``, ``release_behind_window``, ``swap_pages``): each of them empties the pending table."""
         slots = [slots] if isinstance(slots, int) else list(slots)
         lens = [int(x) for x in lens]
         if len(set(slots)) != len(slots):
@@ -246,18 +352,70 @@ class PagedKVCache:
         if len(lens) != len(slots) or any(x < 0 for x in lens):
             raise ValueError(f"lens must hold one non-negative token count per slot, got {lens} for {len(slots)} slots")
         self._grow(slots, lens)
+        if self._copies:
+            pairs, rows = [[-1, -1] for _ in range(self.max_batch)], [-1] * self.max_batch
+            for s, old, new, filled in self._copies:
+                pairs[s], rows[s] = [old, new], filled
+            self._cow_pairs.copy_(torch.tensor(pairs, dtype=torch.int32), non_blocking=True)
+            self._cow_rows.copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=True)
+            self._pending = True
+            self._copies = []
         self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
+
+    def fork(self, slot: int, n_tokens: Optional[int] = None) -> int:
+        """Take a free slot whose first ``n_tokens`` keys (default: all, ``0 <= n_tokens <= length(slot)``) are those of ``slot``, by
+        sharing the ``ceil(n_tokens / page_size)`` pages that hold them: their counts go up, released ``-1`` entries carry over,
+        pages the parent has only reserved are not shared.  Writes the child's table row and length in place; needs no free page and
+        moves no K / V -- the first append into a shared, partly filled tail page copies it (``_grow``).  -> the new slot.
+        ``PagedCacheFull`` when no slot is free; ``ValueError`` without ``copy_on_write``.  Resets the pending copy-on-write table
+        first (see the class's ordering contract)."""
+        if not self._cow:
+            raise ValueError("fork needs PagedKVCache(copy_on_write=True)")
+        self._check_slot(slot)
+        n = self._host_lens[slot] if n_tokens is None else n_tokens
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= self._host_lens[slot]:
+            raise ValueError(f"n_tokens must be an integer in 0 .. {self._host_lens[slot]}, the parent's length, got {n_tokens!r}")
+        child = self._free_slot()
+        self._reset_pending()
+        shared = self._pages[slot][:-(-n // self.page_size)]
+        for pg in shared:
+            if pg >= 0:
+                self._ref[pg] += 1
+        self._live[child] = True
+        self._pages[child] = list(shared)
+        self._host_lens[child] = n
+        if shared:
+            self._table[child, :len(shared)] = torch.tensor(shared, dtype=torch.int32)
+        self._lens[child] = n
+        return child
+
+    def common_prefix(self, slots: Sequence[int]) -> int:
+        """The largest multiple of ``page_size`` such that every slot in ``slots`` has the same physical pages below it, none of them
+        released, and a length at or above it -- what ``decode(q, slots, shared_prefix=...)`` asks of its batch; forks of one parent
+        have it.  0 when there is none (``shared_prefix=0`` is refused, so check).  Host only."""
+        slots = [self._check_slot(s) for s in slots]
+        if not slots:
+            raise ValueError("no slots")
+        first, p = self._pages[slots[0]], 0
+        while all((p + 1) * self.page_size <= self._host_lens[s] for s in slots) and first[p] >= 0 \
+                and all(self._pages[s][p] == first[p] for s in slots):
+            p += 1
+        return p * self.page_size
 
     def swap_pages(self, slot: int, i: int, j: int) -> None:
         """Exchange the physical pages behind logical pages ``i`` and ``j`` of the slot, moving their contents with them (what a
-        compaction does); the sequence reads the same afterwards."""
+        compaction does); the sequence reads the same afterwards.  A page another slot holds as well (``copy_on_write``) is refused:
+        moving it would have to rewrite the other slots' rows.  Resets the pending copy-on-write table first."""
         pg = self._pages[self._check_slot(slot)]
         if not (0 <= i < len(pg) and 0 <= j < len(pg)):
             raise ValueError(f"slot {slot} has {len(pg)} pages")
         if pg[i] < 0 or pg[j] < 0:
             raise ValueError(f"slot {slot}: page {i if pg[i] < 0 else j} was released behind the window")
+        if self._ref[pg[i]] > 1 or self._ref[pg[j]] > 1:
+            raise ValueError(f"slot {slot}: page {i if self._ref[pg[i]] > 1 else j} is shared with another slot")
         if i == j:
             return
+        self._reset_pending()
         a, b = pg[i], pg[j]
         for pool in (self._k, self._v):
             tmp = pool[a].clone()
@@ -329,7 +487,11 @@ class PagedKVCache:
 
         With ``rotary_cos=, rotary_sin=`` (and ``rotary_interleaved``, ``pos_offsets`` -- int32, one per slot of the call) the launch is
         ``ops.rope_append`` instead: the K rows are rotated at the positions they are written to, and the packed ``q [total, H, D]``, if
-        given, is rotated into a fresh buffer that is returned (else None): the tensor ``prefill_varlen`` then takes."""
+        given, is rotated into a fresh buffer that is returned (else None): the tensor ``prefill_varlen`` then takes.
+
+        With ``copy_on_write`` one ``ops.page_copy`` over the pending table (``cow_pairs`` / ``cow_rows``, whatever slots the call
+        names) is enqueued in front: the copies the last ``advance`` calls for, or nothing when the table is empty.  It reads the
+        device table, so a captured ``write_step`` + attention replays through forks."""
         rotary = rotary_cos is not None or rotary_sin is not None
         if not rotary and (q is not None or rotary_interleaved or pos_offsets is not None):
             raise ValueError("q, rotary_interleaved and pos_offsets need rotary_cos and rotary_sin")
@@ -339,6 +501,8 @@ class PagedKVCache:
         if cu_seqlens_q is None and q_lens is not None and len(q_lens) == table.shape[0] and not any(q_lens):
             return None if q is None else torch.empty_like(q)   # a step without rows, as append_varlen takes one
         cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], k_new.shape[0], "k_new")
+        if self._cow:
+            ops.page_copy(self._k.transpose(1, 2), self._v.transpose(1, 2), self._cow_pairs, rows=self._cow_rows)
         if rotary:
             return ops.rope_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens,
                                    rotary_cos=rotary_cos, rotary_sin=rotary_sin, q=q, rotary_interleaved=rotary_interleaved,

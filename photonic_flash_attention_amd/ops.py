@@ -727,7 +727,8 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
     ``fa3_prefill_varlen`` clamps them), row i goes to logical key ``len_b - Sq_b + i``.  Rows in front of key 0 (len_b < Sq_b) are
     dropped, and so is a row whose page id lies outside the pool: a write is never clamped into someone else's page.  Packed rows no
     sequence covers are never read; nothing but the destination rows is written, lengths and table included, so a replay is
-    idempotent.  Two sequences given the same destination leave one of the two rows there (copy-on-write is the caller's business).
+    idempotent.  Two sequences given the same destination leave one of the two rows there (copy-on-write: ``page_copy`` in front of this
+    call, as ``PagedKVCache(copy_on_write=True)`` does).
 
     On device tensors: one launch of a HIP copy kernel whose grid depends on host shapes only -- no host synchronisation, no tensor
     creation, capturable in ``torch.cuda.graph`` and valid while cu_seqlens_q, lengths, table and cache change between replays.  On CPU
@@ -738,6 +739,79 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
         return
     a = _append_args(_capi.make_kv_append_args, "pfa_kv_append", k_new, v_new, k_cache, v_cache, geo, cu_seqlens_q, block_table)
     _append_launch("pfa_kv_append", a, cache_seqlens, k_new, geo[1])
+
+
+def _page_copy_model(k_pool, v_pool, pairs, rows) -> None:
+    """``pfa_page_copy``'s rule in plain torch, pair by pair in order, every range check and clamp included: the executable
+    specification, and what ``page_copy`` runs on CPU tensors.  ``pairs`` is a host list of ``(src, dst)``, ``rows`` one of counts or
+    None; the pools are ``[num_pages, Hkv, page_size, D]``-shaped views."""
+    num_pages, page_size = k_pool.shape[0], k_pool.shape[2]
+    for i, (s, d) in enumerate(pairs):
+        if not 0 <= s < num_pages or not 0 <= d < num_pages or s == d:       # the empty pair: nothing read, nothing written
+            continue
+        r = page_size if rows is None else min(max(rows[i], 0), page_size)
+        for pool in (k_pool, v_pool):
+            pool[d, :, :r] = pool[s, :, :r].clone()
+
+
+def page_copy(k_pool: torch.Tensor, v_pool: torch.Tensor, pairs: torch.Tensor, *, rows: Optional[torch.Tensor] = None) -> None:
+    """Copy whole or partial pages inside the pools of a paged KV cache (``pfa_page_copy``): the data movement of copy-on-write, what
+    vLLM's ``copy_blocks`` does.
+
+    k_pool / v_pool are passed as everywhere else: ``[num_pages,Hkv,page_size,D]``-shaped views (head-major or token-major memory),
+    bf16 / fp16, page_size a multiple of 64, D a multiple of 8 up to 256.  pairs: int32 ``[n, 2]`` of ``(src, dst)`` page ids on the
+    pools' device (any row stride >= 2, the two ids adjacent); rows: int32 ``[n]`` contiguous, or None for whole pages.  A pair is
+    empty -- nothing read, nothing written -- when an id lies outside ``[0, num_pages - 1]`` (-1 is the "no copy" marker) or
+    ``src == dst``.  Otherwise tokens ``[0, r)`` of page src go to page dst in both pools, ``r = clamp(rows[i], 0, page_size)`` or
+    page_size; tokens from r on are not written.  Bad device data loses a copy, it never reaches outside the pools.  The caller promises
+    that no page is the destination of two non-empty pairs and that no destination is another pair's source: then a replay is
+    idempotent.  ``n == 0`` returns without a launch.
+
+    On device tensors: one launch of a HIP copy kernel on the current stream whose grid depends on host shapes only -- no host
+    synchronisation, no tensor creation, capturable in ``torch.cuda.graph`` and valid while pairs, rows and the pools change between
+    replays.  On CPU tensors the same rule runs in plain torch, pairs in order (the executable specification).  Wrong dtypes, shapes or
+    devices raise ``ValueError`` before anything is enqueued."""
+    if not all(isinstance(t, torch.Tensor) for t in (k_pool, v_pool, pairs)) or k_pool.dim() != 4 or v_pool.shape != k_pool.shape:
+        raise ValueError("k_pool, v_pool must be 4-D tensors of one shape ([num_pages,Hkv,page_size,D])")
+    num_pages, Hkv, page_size, D = k_pool.shape
+    if k_pool.dtype not in (torch.bfloat16, torch.float16) or v_pool.dtype != k_pool.dtype:
+        raise ValueError("k_pool, v_pool must share dtype bf16 or fp16")
+    if num_pages < 1 or Hkv < 1:
+        raise ValueError(f"shape mismatch: k pool {tuple(k_pool.shape)}")
+    if page_size < 64 or page_size % 64:
+        raise ValueError(f"page size {page_size}: must be a multiple of 64 keys")
+    if D < 8 or D % 8 or D > 256:
+        raise ValueError(f"head dim {D}: must be a multiple of 8 up to 256")
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be an int32 [n, 2] tensor of (src, dst) page ids")
+    n = pairs.shape[0]
+    if n > 1 and pairs.stride(0) < 2 or n > 0 and pairs.stride(1) != 1:
+        raise ValueError("pairs: a row's two ids must be adjacent, rows at least 2 apart")
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.shape != (n,):
+            raise ValueError("rows must be an int32 [n] tensor, one count per pair")
+        if n > 1 and rows.stride(0) != 1:
+            raise ValueError("rows must be contiguous")
+    dev = k_pool.device
+    if v_pool.device != dev or pairs.device != dev or (rows is not None and rows.device != dev):
+        raise ValueError("pfa_page_copy needs all its tensors on one device")
+    if n == 0:
+        return
+    if dev.type == "cpu":
+        _page_copy_model(k_pool, v_pool, pairs.tolist(), None if rows is None else rows.tolist())
+        return
+    if not k_pool.is_cuda:
+        raise ValueError("pfa_page_copy needs device tensors (or CPU tensors for the torch model)")
+    if k_pool.stride(-1) != 1 or v_pool.stride(-1) != 1:
+        raise ValueError("last (head_dim) stride must be 1")
+    ks, vs = _bhsd_strides(k_pool), _bhsd_strides(v_pool)
+    a = _capi.make_page_copy_args(
+        k_pool=k_pool.data_ptr(), v_pool=v_pool.data_ptr(), pairs=pairs.data_ptr(), rows=None if rows is None else rows.data_ptr(),
+        pairs_stride=pairs.stride(0) if n > 1 else 2,
+        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
+        n_pairs=n, Hkv=Hkv, D=D, page_size=page_size, num_pages=num_pages, dtype=_DT[k_pool.dtype], device_id=_device_index(dev))
+    st = _capi.load().pfa_page_copy(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    _raise_status("pfa_page_copy", st, null_too=True)
 
 
 def rotary_tables(max_pos: int, rot_dim: int, base: float = 10000.0, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
