@@ -1,0 +1,265 @@
+"""What the KV-cache tests share: the fp64 attention reference, the error bounds, the page scatter and a few small helpers.  Plain
+functions and constants; pytest collects nothing from here, and tests/test_kvcache_testlib.py tests it on the CPU.
+
+The reference is fp64 attention of ``q [B,H,Sq,D]`` over ``k/v [B,Hkv,Smax,D]`` with the bottom-right causal rule per batch: with
+``off_b = len_b - Sq``, row i sees key j iff ``j < len_b``, ``j <= i + off_b`` (causal), ``j > i + off_b - W`` (window) and the key mask
+allows it.  It is computed from CLEAN caches: the NaN a test puts where a kernel must not read goes to the kernel only.
+
+The bounds: ``|err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6`` per element of a 16-bit output (eps 2^-9 bf16, 2^-11 fp16: the
+bound of the fast variant in tests/test_hip_parity.py's docstring), 1e-3 max-abs for an fp32 output, 2e-3 on the LSE with exact
+agreement on which rows are -inf, and O exactly zero on those rows.  Every output must be finite."""
+
+from __future__ import annotations
+
+import functools
+import os
+import subprocess
+
+import torch
+
+EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
+INF, NAN = float("inf"), float("nan")
+
+
+def device():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+def i32(x, dev=None):
+    return torch.tensor(x, dtype=torch.int32, device=device() if dev is None else dev)
+
+
+def built_lib():
+    """The native library through ctypes, built first if it is missing: the body of the host test files' ``lib`` fixtures."""
+    from conftest import REPO
+    from photonic_flash_attention_amd import _capi
+    if not os.path.exists(_capi.LIB_PATH):
+        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
+    return _capi.load()
+
+
+# --- the fp64 reference and the bounds -----------------------------------------------------------------------------------------------
+
+def reference(q, k, v, *, seqlens=None, key_mask=None, causal=True, window=None, scale=None):
+    """fp64 on q's device: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2).  A row that sees no key has o = 0, lse = -inf."""
+    assert window is None or causal, "a window is defined against the causal diagonal"
+    B, H, Sq, D = q.shape
+    Hkv, Smax = k.shape[1], k.shape[2]
+    g = H // Hkv
+    kd = k.double().repeat_interleave(g, dim=1)
+    vd = v.double().repeat_interleave(g, dim=1)
+    s = (q.double() @ kd.transpose(-1, -2)) * (D ** -0.5 if scale is None else scale)        # [B,H,Sq,Smax]
+    j = torch.arange(Smax, device=q.device)
+    i = torch.arange(Sq, device=q.device)
+    L = seqlens.to(q.device).long() if seqlens is not None else torch.full((B,), Smax, device=q.device)
+    vis = (j[None, None, :] < L[:, None, None]).expand(B, Sq, Smax)
+    if causal:
+        diag = L[:, None, None] - Sq + i[None, :, None]                                       # i + off_b: bottom-right, per batch
+        vis = vis & (j[None, None, :] <= diag)
+        if window is not None:
+            vis = vis & (j[None, None, :] > diag - window)
+    if key_mask is not None:
+        vis = vis & key_mask.to(q.device).bool()[:, None, :]
+    s = s.masked_fill(~vis[:, None], -INF)
+    m = s.amax(-1, keepdim=True)
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    safe = torch.where(l > 0, l, torch.ones_like(l))
+    pn = p / safe
+    o = pn @ vd
+    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, -INF))[..., 0]
+    return o, lse, pn.norm(dim=-1, keepdim=True)
+
+
+def check_out(got, ref, pnorm, vmax, dtype, what=""):
+    """``got`` against the reference's ``o``: finite, and within the bound of ``dtype`` (the input dtype) or 1e-3 if ``got`` is fp32."""
+    tag = f"{what}: " if what else ""
+    assert bool(torch.isfinite(got).all()), f"{tag}non-finite output -- a key or a page the call must never read was read"
+    err = (got.double() - ref).abs()
+    if got.dtype == torch.float32:
+        print(f"{tag}max-abs {float(err.max()):.3e} (fp32, bound 1e-3)")
+        assert float(err.max()) <= 1e-3, (what, float(err.max()))
+        return
+    eps = EPS[dtype]
+    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
+    worst = float((err - bound).max())
+    print(f"{tag}max-abs {float(err.max()):.3e}, closest to the bound {worst:.3e}")
+    assert worst <= 0, f"{tag}max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
+
+
+def check_lse(o, lse, rlse, what=""):
+    """``lse`` against the reference's: -inf on exactly the reference's rows (and ``o`` zero there), within 2e-3 on the others."""
+    tag = f"{what}: " if what else ""
+    fin = torch.isfinite(rlse)
+    assert torch.equal(torch.isfinite(lse), fin), f"{tag}the rows with a finite LSE are not the reference's"
+    assert not bool(torch.isnan(lse).any()), f"{tag}NaN in the LSE"
+    assert bool((lse[~fin] == -INF).all()), f"{tag}a row with no visible key has an LSE other than -inf"
+    assert bool((o[~fin[..., None].expand_as(o)] == 0).all()), f"{tag}a row with no visible key is not exactly zero"
+    if bool(fin.any()):
+        d = float((lse.double() - rlse)[fin].abs().max())
+        print(f"{tag}LSE max-abs {d:.3e}")
+        assert d <= 2e-3, (what, d)
+
+
+def merge_ref64(outs, lses):
+    """The merge rule of partial attention results in fp64, for LSEs that are finite or -inf -> (O, LSE)."""
+    L = torch.stack([l.double() for l in lses])
+    m = L.max(dim=0).values
+    w = torch.exp(L - torch.where(m == -INF, torch.zeros_like(m), m))
+    s = w.sum(dim=0)
+    o = sum(torch.where(w[n][..., None] > 0, w[n][..., None] * outs[n].double(), torch.zeros_like(outs[n], dtype=torch.float64))
+            for n in range(len(outs)))
+    o = torch.where(s[..., None] > 0, o / s[..., None].clamp_min(1e-300), torch.zeros_like(o))
+    return o, torch.where(s > 0, m + torch.log(s), torch.full_like(m, -INF))
+
+
+# --- caches and pools ----------------------------------------------------------------------------------------------------------------
+
+def gen(seed):
+    return torch.Generator(device=device()).manual_seed(seed)
+
+
+def problem(B, H, Hkv, Sq, Smax, D, dtype, seed):
+    """q as a [B,H,Sq,D] view of a [B,Sq,H,D] buffer and contiguous k, v [B,Hkv,Smax,D], drawn on the device from one generator."""
+    g = gen(seed)
+    dev = device()
+    q = torch.randn(B, Sq, H, D, generator=g, device=dev).to(dtype).permute(0, 2, 1, 3)
+    k = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
+    v = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
+    return q, k, v
+
+
+def poison(k, v, lens):
+    """Copies of the caches with NaN at and past each batch's length (what an unfilled tail may hold)."""
+    kn, vn = k.clone(), v.clone()
+    for b, n in enumerate(lens):
+        kn[b, :, n:] = NAN
+        vn[b, :, n:] = NAN
+    return kn, vn
+
+
+def scatter(k, v, page, seed, layout="phsd", spare=5):
+    """Scatter contiguous [B, Hkv, Smax, D] caches over pools in a random page order.  -> (k_pool, v_pool, table) with the pools as
+    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN (and so does whatever NaN the caches carry)."""
+    B, Hkv, Smax, D = k.shape
+    assert Smax % page == 0
+    pages = Smax // page
+    NP = B * pages + spare
+    dev = k.device
+    perm = torch.randperm(NP, generator=torch.Generator().manual_seed(seed))[:B * pages]
+    table = perm.to(torch.int32).reshape(B, pages).to(dev)
+    pools = []
+    for src in (k, v):
+        if layout == "phsd":        # flash-attn style [num_pages, page, Hkv, D], passed transposed
+            pool = torch.full((NP, page, Hkv, D), NAN, dtype=k.dtype, device=dev).transpose(1, 2)
+        elif layout == "hpsd":
+            pool = torch.full((NP, Hkv, page, D), NAN, dtype=k.dtype, device=dev)
+        else:                       # every second page of a larger pool, whose pages also have room for 64 more keys
+            pool = torch.full((2 * NP, Hkv, page + 64, D), NAN, dtype=k.dtype, device=dev)[::2, :, :page]
+        pool[perm.to(dev)] = src.reshape(B, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(B * pages, Hkv, page, D)
+        pools.append(pool)
+    return pools[0], pools[1], table
+
+
+def contiguous_of(cache, Smax):
+    """A PagedKVCache's sequences gathered into contiguous [max_batch, Hkv, Smax, D] K and V (zeros past each length)."""
+    B = cache.max_batch
+    k = torch.zeros(B, cache.Hkv, Smax, cache.D, dtype=cache.k_pool.dtype, device=cache.device)
+    v = torch.zeros_like(k)
+    for s in range(B):
+        gk, gv = cache.gather(s)
+        k[s, :, :gk.shape[1]] = gk
+        v[s, :, :gv.shape[1]] = gv
+    return k, v
+
+
+def capture(step):
+    """``step()`` once on a side stream (allocator warm-up), then captured -> (graph, what the captured call returned)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        res = step()
+    return graph, res
+
+
+# --- the shared-prefix step (tests/test_hip_attn_merge.py, tests/test_hip_prefill_split.py) -----------------------------------------
+
+PREFIX_PAGE = 64
+
+
+def _with_nan(kl, lens, P):
+    """The contiguous cache of the logical one: NaN behind every length and over every prefix copy but sequence 0's."""
+    kc = kl.clone()
+    for b, n in enumerate(lens.tolist()):
+        kc[b, :, n:] = NAN
+        if b:
+            kc[b, :, :P] = NAN
+    return kc
+
+
+def _paged(kc, lens, P, perm):
+    """Pool and table of the contiguous cache ``kc`` (NaN tails included): the prefix pages named once, by every sequence; NaN in the
+    pages nobody names; the table entries past a sequence's last page name one of those."""
+    Bc, Hkv, Smax, D = kc.shape
+    n_pre, per = P // PREFIX_PAGE, (Smax - P) // PREFIX_PAGE
+    pool = torch.full((len(perm), Hkv, PREFIX_PAGE, D), NAN, dtype=kc.dtype, device=kc.device)
+    table = torch.empty(Bc, n_pre + per, dtype=torch.int32)
+    for jp in range(n_pre):
+        pool[perm[jp]] = kc[0, :, jp * PREFIX_PAGE:(jp + 1) * PREFIX_PAGE]
+        table[:, jp] = perm[jp]
+    for b, n in enumerate(lens.tolist()):
+        for jp in range(per):
+            pid = perm[n_pre + b * per + jp]
+            if P + jp * PREFIX_PAGE < n:
+                pool[pid] = kc[b, :, P + jp * PREFIX_PAGE:P + (jp + 1) * PREFIX_PAGE]
+                table[b, n_pre + jp] = pid
+            else:
+                table[b, n_pre + jp] = perm[-1]                                # never read: a page of NaN
+    return pool, table.to(kc.device)
+
+
+@functools.lru_cache(maxsize=None)
+def prefix_problem(Bc, Sq, D, private, Smax, dtype, causal=True, P=128, Hq=8, Hkv=2):
+    """One shared-prefix step and its fp64 reference, built once: q, the logical caches (every sequence's first P keys are sequence
+    0's), the lengths P + private, the contiguous caches with NaN, the pools with their table."""
+    g = torch.Generator().manual_seed(Bc * 1000 + Sq * 10 + D + sum(private))
+    dev = device()
+    q = torch.randn(Bc, Sq, Hq, D, generator=g).to(dev, dtype).permute(0, 2, 1, 3)
+    kl, vl = (torch.randn(Bc, Hkv, Smax, D, generator=g).to(dev, dtype) for _ in range(2))
+    kl[:, :, :P], vl[:, :, :P] = kl[:1, :, :P], vl[:1, :, :P]
+    lens = torch.tensor([P + n for n in private], dtype=torch.int32, device=dev)
+    assert all(n >= Sq for n in private) and P + max(private) <= Smax            # the caller's promise: every row lies behind the prefix
+    n_pages = P // PREFIX_PAGE + Bc * ((Smax - P) // PREFIX_PAGE) + 3
+    perm = torch.randperm(n_pages, generator=g).tolist()
+    kc, vc = _with_nan(kl, lens, P), _with_nan(vl, lens, P)
+    kp, table = _paged(kc, lens, P, perm)
+    vp, _ = _paged(vc, lens, P, perm)
+    return dict(q=q, kl=kl, vl=vl, lens=lens, kc=kc, vc=vc, kp=kp, vp=vp, table=table, P=P, causal=causal, dtype=dtype,
+                ref=reference(q, kl, vl, seqlens=lens, causal=causal), vmax=float(vl.abs().max()))
+
+
+def check_step(o, lse, ref, dtype, vmax, what):
+    """A shared-prefix step against ``ref = reference(...)``: every row lies behind the prefix, so every LSE is finite."""
+    check_out(o, ref[0], ref[2], vmax, dtype, what)
+    assert bool(torch.isfinite(lse).all()), f"{what}: a non-finite LSE"
+    check_lse(o, lse, ref[1], what)
+
+
+def both_prefix_caches(fn, pr, what, **kw):
+    """``fn`` with shared_prefix on the contiguous and on the paged cache: each within the bound, the two bit-equal -> (o, lse)."""
+    o_c, lse_c = fn(pr["q"], pr["kc"], pr["vc"], cache_seqlens=pr["lens"], causal=pr["causal"], shared_prefix=pr["P"], return_lse=True, **kw)
+    o_p, lse_p = fn(pr["q"], pr["kp"], pr["vp"], cache_seqlens=pr["lens"], block_table=pr["table"], causal=pr["causal"],
+                    shared_prefix=pr["P"], return_lse=True, **kw)
+    torch.cuda.synchronize()
+    assert o_c.dtype == pr["dtype"] and o_c.shape == pr["q"].shape and lse_c.shape == pr["q"].shape[:3]
+    check_step(o_c, lse_c, pr["ref"], pr["dtype"], pr["vmax"], what + " contiguous")
+    check_step(o_p, lse_p, pr["ref"], pr["dtype"], pr["vmax"], what + " paged")
+    assert torch.equal(o_c, o_p) and torch.equal(lse_c, lse_p)
+    return o_c, lse_c

@@ -1,8 +1,8 @@
 """CPU-side tests (no GPU) of the merge of partial attention results (``pfa_attn_merge*``, ABI v9 additive) and of ``shared_prefix=``:
 exported symbols, the argument block's layout, every validation rule and the order the rules are reported in, the launch
 description, the plain-torch model of the rule (``ops.attn_merge`` on CPU tensors: the executable specification the GPU tests compare
-the kernel with) against an fp64 model written here, its exactness property, and the ``ValueError``s ``shared_prefix`` raises before
-anything is enqueued."""
+the kernel with) against the rule in fp64 (``merge_ref64`` of tests/kvcache_testlib.py), its exactness property, and the
+``ValueError``s ``shared_prefix`` raises before anything is enqueued."""
 
 from __future__ import annotations
 
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib, merge_ref64
 from photonic_flash_attention_amd import _capi, ops
 
 SYMBOLS = ("pfa_attn_merge_check", "pfa_attn_merge", "pfa_attn_merge_describe")
@@ -25,9 +26,7 @@ INF, NAN = float("inf"), float("nan")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _args(**over):
@@ -178,18 +177,6 @@ def test_attn_merge_describe_names(lib):
 
 # ---- the CPU model against fp64 -------------------------------------------------------------------------------------------------
 
-def _ref64(outs, lses):
-    """The rule in fp64 on finite LSEs (and -inf): -> (O, LSE)."""
-    L = torch.stack([l.double() for l in lses])
-    m = L.max(dim=0).values
-    w = torch.exp(L - torch.where(m == -INF, torch.zeros_like(m), m))
-    s = w.sum(dim=0)
-    o = sum(torch.where(w[n][..., None] > 0, w[n][..., None] * outs[n].double(), torch.zeros_like(outs[n], dtype=torch.float64))
-            for n in range(len(outs)))
-    o = torch.where(s[..., None] > 0, o / s[..., None].clamp_min(1e-300), torch.zeros_like(o))
-    return o, torch.where(s > 0, m + torch.log(s), torch.full_like(m, -INF))
-
-
 def _parts(N, B, H, Sq, D, dtype, seed):
     g = torch.Generator().manual_seed(seed)
     offs = [0.0, 5.0, -5.0, 120.0, -120.0, 0.0, 5.0, -5.0]
@@ -205,7 +192,7 @@ def test_cpu_attn_merge_matches_fp64(N, dtype, odt):
     outs, lses = _parts(N, 3, 4, 5, 64, dtype, 100 + N)
     lses[1] = lses[1].permute(1, 0, 2).contiguous().view(1, 4, 15).view(4, 3, 5).transpose(0, 1)   # the prefix pass's [1, H, B * Sq] layout
     o, lse = ops.attn_merge(outs, lses, out_dtype=odt, return_lse=True)
-    ref_o, ref_lse = _ref64(outs, lses)
+    ref_o, ref_lse = merge_ref64(outs, lses)
     assert o.dtype == odt and o.shape == (3, 4, 5, 64) and lse.shape == (3, 4, 5) and lse.dtype == torch.float32
     bound = 1e-5 * torch.stack([t.double().abs() for t in outs]).max(dim=0).values
     if odt != torch.float32:
@@ -232,7 +219,7 @@ def test_cpu_attn_merge_inf_nan_and_exactness():
     assert bool(torch.isfinite(o[clean]).all()) and bool(torch.isfinite(lse[clean]).all())
     assert bool((o[0, 1, 2] == 0).all()) and float(lse[0, 1, 2]) == -INF
     assert bool(torch.isnan(o[1, 0, 3]).all()) and bool(torch.isnan(lse[1, 0, 3]))
-    ref_o, ref_lse = _ref64([t[:, :, :2] for t in outs[1:]], [t[:, :, :2] for t in lses[1:]])
+    ref_o, ref_lse = merge_ref64([t[:, :, :2] for t in outs[1:]], [t[:, :, :2] for t in lses[1:]])
     assert bool(((o[0, 0, 1].double() - ref_o[0, 0, 1]).abs() <= 1e-5 * max(float(t[0, 0, 1].abs().max()) for t in outs[1:])).all())
     # one finite part among -inf parts comes back bit for bit, wherever it stands
     finite = 3 * torch.randn(2, 2, 6, generator=torch.Generator().manual_seed(8)) + 40

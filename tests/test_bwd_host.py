@@ -5,12 +5,10 @@ accepted block would be launched on the made-up pointers wherever a GPU is prese
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi
 
 TENSORS = ("q", "k", "v", "o", "do", "dq", "dk", "dv")          # stride prefixes; the pointer of "do" is dout
@@ -18,9 +16,7 @@ TENSORS = ("q", "k", "v", "o", "do", "dq", "dk", "dv")          # stride prefixe
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _bwd_args(**over):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 EX_SYMBOLS = {
@@ -32,9 +33,7 @@ MIN_SPLIT_KEYS = 256                # kMinSplitKeys of pfa_decode_capi.hip
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _dargs(**over):

@@ -5,54 +5,36 @@ The merge is checked against the rule in fp64 on the same inputs.  Bounds: fp32 
 the N + 3 fp32 roundings plus the hardware exp's argument error, whose weighted effect is at most 0.37 * 88 * 2^-24); 16-bit output that
 plus ``2^-8 |ref|`` (bf16) or ``2^-11 |ref|`` (fp16), twice one round-to-nearest-even; LSE ``|err| <= 4e-6 * max(1, |ref|)``.
 
-A shared-prefix step is checked against fp64 attention over the whole logical cache with the per-element bound of
-tests/test_hip_decode.py, ``eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6`` (EPS copied from there), the LSE within 2e-3.  NaN fills
-every cache tail, every page no table names, every table entry past a sequence's last page and -- in the contiguous cache -- the
-prefix region of every sequence but the first: the prefix is read from sequence 0 alone."""
+A shared-prefix step is checked against fp64 attention over the whole logical cache, within the bounds of that reference
+(tests/kvcache_testlib.py, which also builds the step: ``prefix_problem``).  NaN fills every cache tail, every page no table names,
+every table entry past a sequence's last page and -- in the contiguous cache -- the prefix region of every sequence but the first:
+the prefix is read from sequence 0 alone."""
 
 from __future__ import annotations
 
 import ctypes as C
-import functools
 
 import pytest
 import torch
 
+from kvcache_testlib import INF, NAN, PREFIX_PAGE, both_prefix_caches, check_step, device, merge_ref64, prefix_problem, reference
+
 pytestmark = pytest.mark.gpu
 
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
 RNE2 = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
-INF, NAN = float("inf"), float("nan")
 OUT_DTYPES = {torch.float32: (torch.float32, torch.bfloat16, torch.float16), torch.bfloat16: (torch.bfloat16, torch.float32),
               torch.float16: (torch.float16, torch.float32)}
 B, SQ, H = 3, 5, 4                      # 3 * 5 * 4 * (128 / 8) = 960 items: four workgroups at D = 128, the last partly empty
 OFFSETS = [0.0, 5.0, -5.0, 120.0, -120.0, 0.0, 5.0, -5.0]
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
 # ---- the merge --------------------------------------------------------------------------------------------------------------------
-
-def _ref64(outs, lses):
-    """The rule in fp64, for LSEs that are finite or -inf -> (O, LSE)."""
-    L = torch.stack([l.double() for l in lses])
-    m = L.max(dim=0).values
-    w = torch.exp(L - torch.where(m == -INF, torch.zeros_like(m), m))
-    s = w.sum(dim=0)
-    o = sum(torch.where(w[n][..., None] > 0, w[n][..., None] * outs[n].double(), torch.zeros_like(outs[n], dtype=torch.float64))
-            for n in range(len(outs)))
-    o = torch.where(s[..., None] > 0, o / s[..., None].clamp_min(1e-300), torch.zeros_like(o))
-    return o, torch.where(s > 0, m + torch.log(s), torch.full_like(m, -INF))
-
 
 def _parts(N, D, dtype, seed):
     """N parts as slices of larger [B, Sq + 1, H + 1, D] buffers; LSEs 3 * normal + a per-part offset, so that some weights underflow to
     zero; part 1's LSE in the layout of one call over all B * Sq rows as one sequence, [1, H, B * Sq]."""
     g = torch.Generator().manual_seed(seed)
-    dev = _dev()
+    dev = device()
     outs = [torch.randn(B, SQ + 1, H + 1, D, generator=g).to(dev, dtype)[:, :SQ, :H].permute(0, 2, 1, 3) for _ in range(N)]
     lses = [(3 * torch.randn(B, H, SQ, generator=g) + OFFSETS[n]).to(dev) for n in range(N)]
     lses[1] = lses[1].permute(1, 0, 2).contiguous().view(1, H, B * SQ).view(H, B, SQ).transpose(0, 1)
@@ -61,7 +43,7 @@ def _parts(N, D, dtype, seed):
 
 
 def _check_merge(o, lse, outs, lses):
-    ref_o, ref_lse = _ref64(outs, lses)
+    ref_o, ref_lse = merge_ref64(outs, lses)
     err = (o.double() - ref_o).abs()
     bound = 1e-5 * torch.stack([t.double().abs() for t in outs]).max(dim=0).values
     if o.dtype != torch.float32:
@@ -121,7 +103,7 @@ def test_merge_skips_inf_parts_zeroes_empty_rows_and_keeps_nan_rows_to_themselve
 @pytest.mark.parametrize("N", [2, 8])
 def test_merge_of_one_finite_part_is_exact(N):
     from photonic_flash_attention_amd import ops
-    dev = _dev()
+    dev = device()
     g = torch.Generator().manual_seed(N)
     for dtype, odts in OUT_DTYPES.items():
         part = (torch.randn(B, SQ, H, 128, generator=g) * 3).to(dev, dtype).permute(0, 2, 1, 3)
@@ -141,7 +123,7 @@ def test_merge_writes_nothing_but_its_rows():
     from photonic_flash_attention_amd import ops
     outs, lses = _parts(2, 64, torch.bfloat16, 9)
     for odt in (torch.bfloat16, torch.float32):
-        big = torch.full((B + 2, SQ + 2, H + 2, 64 + 16), 77.0, dtype=odt, device=_dev())
+        big = torch.full((B + 2, SQ + 2, H + 2, 64 + 16), 77.0, dtype=odt, device=device())
         out = big[1:B + 1, 1:SQ + 1, 1:H + 1, 8:72].permute(0, 2, 1, 3)
         o, _ = ops.attn_merge(outs, lses, out=out)
         want, _ = ops.attn_merge(outs, lses, out_dtype=odt)
@@ -154,118 +136,22 @@ def test_merge_writes_nothing_but_its_rows():
 
 # ---- shared_prefix ------------------------------------------------------------------------------------------------------------------
 
-PAGE = 64
-
-
-def _reference(q, k, v, lens, causal):
-    """fp64 attention of q [B,H,Sq,D] over the logical caches k / v [B,Hkv,Smax,D], bottom-right causal -> (o, lse, ||p_row||_2)."""
-    Bq, Hq, Sq, D = q.shape
-    Smax, g = k.shape[2], Hq // k.shape[1]
-    kd, vd = k.double().repeat_interleave(g, dim=1), v.double().repeat_interleave(g, dim=1)
-    s = (q.double() @ kd.transpose(-1, -2)) * D ** -0.5
-    j, i, L = torch.arange(Smax, device=q.device), torch.arange(Sq, device=q.device), lens.long()
-    vis = (j[None, None, :] < L[:, None, None]).expand(Bq, Sq, Smax)
-    if causal:
-        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])
-    s = s.masked_fill(~vis[:, None], -INF)
-    m = s.amax(-1, keepdim=True)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    pn = p / l
-    return pn @ vd, (m + torch.log(l))[..., 0], pn.norm(dim=-1, keepdim=True)
-
-
-def _check_step(o, lse, ref, dtype, vmax, what):
-    ro, rlse, pn = ref
-    assert bool(torch.isfinite(o.float()).all()) and bool(torch.isfinite(lse).all()), what
-    err = (o.double() - ro).abs()
-    bound = EPS[dtype] * ro.abs() + 3 * EPS[dtype] * vmax * pn + 2e-6
-    lerr = float((lse.double() - rlse).abs().max())
-    print(f"{what}: O max err {float(err.max()):.3e} (worst err - bound {float((err - bound).max()):.3e}), LSE max err {lerr:.3e}")
-    assert bool((err <= bound).all()), (what, float((err - bound).max()))
-    assert lerr <= 2e-3, (what, lerr)
-
-
-def _with_nan(kl, lens, P):
-    """The contiguous cache of the logical one: NaN behind every length and over every prefix copy but sequence 0's."""
-    kc = kl.clone()
-    for b, n in enumerate(lens.tolist()):
-        kc[b, :, n:] = NAN
-        if b:
-            kc[b, :, :P] = NAN
-    return kc
-
-
-def _paged(kc, lens, P, perm):
-    """Pool and table of the contiguous cache ``kc`` (NaN tails included): the prefix pages named once, by every sequence; NaN in the
-    pages nobody names; the table entries past a sequence's last page name one of those."""
-    Bc, Hkv, Smax, D = kc.shape
-    n_pre, per = P // PAGE, (Smax - P) // PAGE
-    pool = torch.full((len(perm), Hkv, PAGE, D), NAN, dtype=kc.dtype, device=kc.device)
-    table = torch.empty(Bc, n_pre + per, dtype=torch.int32)
-    for jp in range(n_pre):
-        pool[perm[jp]] = kc[0, :, jp * PAGE:(jp + 1) * PAGE]
-        table[:, jp] = perm[jp]
-    for b, n in enumerate(lens.tolist()):
-        for jp in range(per):
-            pid = perm[n_pre + b * per + jp]
-            if P + jp * PAGE < n:
-                pool[pid] = kc[b, :, P + jp * PAGE:P + (jp + 1) * PAGE]
-                table[b, n_pre + jp] = pid
-            else:
-                table[b, n_pre + jp] = perm[-1]                                # never read: a page of NaN
-    return pool, table.to(kc.device)
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(Bc, Sq, D, private, Smax, dtype, causal=True, P=128, Hq=8, Hkv=2):
-    """One shared-prefix step and its fp64 reference, built once: q, the logical caches (every sequence's first P keys are sequence
-    0's), the lengths P + private, the contiguous caches with NaN, the pools with their table."""
-    g = torch.Generator().manual_seed(Bc * 1000 + Sq * 10 + D + sum(private))
-    dev = _dev()
-    q = torch.randn(Bc, Sq, Hq, D, generator=g).to(dev, dtype).permute(0, 2, 1, 3)
-    kl, vl = (torch.randn(Bc, Hkv, Smax, D, generator=g).to(dev, dtype) for _ in range(2))
-    kl[:, :, :P], vl[:, :, :P] = kl[:1, :, :P], vl[:1, :, :P]
-    lens = torch.tensor([P + n for n in private], dtype=torch.int32, device=dev)
-    assert all(n >= Sq for n in private) and P + max(private) <= Smax            # the caller's promise: every row lies behind the prefix
-    n_pages = P // PAGE + Bc * ((Smax - P) // PAGE) + 3
-    perm = torch.randperm(n_pages, generator=g).tolist()
-    kc, vc = _with_nan(kl, lens, P), _with_nan(vl, lens, P)
-    kp, table = _paged(kc, lens, P, perm)
-    vp, _ = _paged(vc, lens, P, perm)
-    return dict(q=q, kl=kl, vl=vl, lens=lens, kc=kc, vc=vc, kp=kp, vp=vp, table=table, P=P, causal=causal, dtype=dtype,
-                ref=_reference(q, kl, vl, lens, causal), vmax=float(vl.abs().max()))
-
-
-def _both_caches(fn, pr, what, **kw):
-    """``fn`` with shared_prefix on the contiguous and on the paged cache: each within the bound, the two bit-equal -> (o, lse)."""
-    o_c, lse_c = fn(pr["q"], pr["kc"], pr["vc"], cache_seqlens=pr["lens"], causal=pr["causal"], shared_prefix=pr["P"], return_lse=True, **kw)
-    o_p, lse_p = fn(pr["q"], pr["kp"], pr["vp"], cache_seqlens=pr["lens"], block_table=pr["table"], causal=pr["causal"],
-                    shared_prefix=pr["P"], return_lse=True, **kw)
-    torch.cuda.synchronize()
-    assert o_c.dtype == pr["dtype"] and o_c.shape == pr["q"].shape and lse_c.shape == pr["q"].shape[:3]
-    _check_step(o_c, lse_c, pr["ref"], pr["dtype"], pr["vmax"], what + " contiguous")
-    _check_step(o_p, lse_p, pr["ref"], pr["dtype"], pr["vmax"], what + " paged")
-    assert torch.equal(o_c, o_p) and torch.equal(lse_c, lse_p)
-    return o_c, lse_c
-
-
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("Sq", [1, 3])
 @pytest.mark.parametrize("D", [128, 64])
 def test_shared_prefix_decode(D, Sq, dtype):
     from photonic_flash_attention_amd import ops
     private = (1, 64, 65, 130) if Sq == 1 else (3, 64, 65, 130)
-    pr = _problem(4, Sq, D, private, 320, dtype)
-    _both_caches(ops.fa3_decode, pr, f"decode D{D} Sq{Sq}")
+    pr = prefix_problem(4, Sq, D, private, 320, dtype)
+    both_prefix_caches(ops.fa3_decode, pr, f"decode D{D} Sq{Sq}")
 
 
 @pytest.mark.parametrize("Bc,Sq,private,Smax", [(3, 40, (40, 64, 130), 320), (2, 300, (300, 330), 512)])
 def test_shared_prefix_prefill(Bc, Sq, private, Smax):
     from photonic_flash_attention_amd import ops
     for D in (128, 64):
-        pr = _problem(Bc, Sq, D, private, Smax, torch.bfloat16)
-        _both_caches(ops.fa3_prefill_cache, pr, f"prefill B{Bc} Sq{Sq} D{D}")
+        pr = prefix_problem(Bc, Sq, D, private, Smax, torch.bfloat16)
+        both_prefix_caches(ops.fa3_prefill_cache, pr, f"prefill B{Bc} Sq{Sq} D{D}")
     # fp32 output: the merge writes the caller's dtype
     o32, _ = ops.fa3_prefill_cache(pr["q"], pr["kc"], pr["vc"], cache_seqlens=pr["lens"], shared_prefix=pr["P"], out_dtype=torch.float32)
     torch.cuda.synchronize()
@@ -289,10 +175,10 @@ def pass_spy(monkeypatch):
 def test_the_prefix_pass_changes_kernel_past_64_rows(pass_spy, Bc, Sq, prefix_pass):
     """B * Sq = 64 rows: the prefix pass is the split-KV decode kernel over one sequence of 64 rows; 65 rows: the MFMA forward."""
     from photonic_flash_attention_amd import _capi, ops
-    pr = _problem(Bc, Sq, 64, tuple([Sq, 64, 65, 130, 100][:Bc]), 320, torch.bfloat16)
+    pr = prefix_problem(Bc, Sq, 64, tuple([Sq, 64, 65, 130, 100][:Bc]), 320, torch.bfloat16)
     o, lse = ops.fa3_decode(pr["q"], pr["kc"], pr["vc"], cache_seqlens=pr["lens"], shared_prefix=128, return_lse=True)
     torch.cuda.synchronize()
-    _check_step(o, lse, pr["ref"], pr["dtype"], pr["vmax"], f"threshold B{Bc} Sq{Sq}")
+    check_step(o, lse, pr["ref"], pr["dtype"], pr["vmax"], f"threshold B{Bc} Sq{Sq}")
     rows = Bc * Sq
     inner = [c for c in pass_spy if c[3] is None]                                       # the two passes, in the order they are enqueued
     assert inner == [(prefix_pass, (1, 8, rows, 64), False, None), ("fa3_decode", (Bc, 8, Sq, 64), True, None)], pass_spy
@@ -317,8 +203,8 @@ def test_shared_prefix_with_new_rows_and_rotary(paged, rotary):
     """The append runs once, first: the cache ends up as the plain call leaves it, and both passes read the rotated q."""
     from photonic_flash_attention_amd import ops
     Sq, D = 3, 64
-    pr = _problem(4, Sq, D, (3, 64, 65, 130), 320, torch.bfloat16)
-    dev, lens = _dev(), pr["lens"]
+    pr = prefix_problem(4, Sq, D, (3, 64, 65, 130), 320, torch.bfloat16)
+    dev, lens = device(), pr["lens"]
     g = torch.Generator().manual_seed(31)
     kn, vn = (torch.randn(4, 2, Sq, D, generator=g).to(dev, torch.bfloat16) for _ in range(2))
     kw = {}
@@ -333,7 +219,7 @@ def test_shared_prefix_with_new_rows_and_rotary(paged, rotary):
     else:
         ops.kv_append(kn.cpu(), vn.cpu(), kl, vl, cache_seqlens=lens.cpu())
         q_ref = pr["q"].cpu()
-    ref = _reference(q_ref.to(dev), kl.to(dev), vl.to(dev), lens, True)
+    ref = reference(q_ref.to(dev), kl.to(dev), vl.to(dev), seqlens=lens)
     caches = (pr["kp"], pr["vp"]) if paged else (pr["kc"], pr["vc"])
     table = dict(block_table=pr["table"]) if paged else {}
     k1, v1, k2, v2 = caches[0].clone(), caches[1].clone(), caches[0].clone(), caches[1].clone()
@@ -342,21 +228,21 @@ def test_shared_prefix_with_new_rows_and_rotary(paged, rotary):
     torch.cuda.synchronize()
     assert torch.equal(_bits(k1), _bits(k2)) and torch.equal(_bits(v1), _bits(v2))
     assert not torch.equal(_bits(k2), _bits(caches[0]))         # ... and something was appended
-    _check_step(o, lse, ref, torch.bfloat16, float(vl.abs().max()), f"new rows paged={paged} rotary={rotary}")
+    check_step(o, lse, ref, torch.bfloat16, float(vl.abs().max()), f"new rows paged={paged} rotary={rotary}")
 
 
 def test_shared_prefix_step_replays_in_a_graph():
     """Append + prefix pass + own-keys pass + merge captured once; replayed after lengths, table, cache contents, new rows and q
     changed: each replay equals the eager call bit for bit."""
     from photonic_flash_attention_amd import ops
-    dev, dtype, Bc, Hq, Hkv, D, n_pages = _dev(), torch.bfloat16, 4, 8, 2, 64, 24
+    dev, dtype, Bc, Hq, Hkv, D, n_pages = device(), torch.bfloat16, 4, 8, 2, 64, 24
     g = torch.Generator().manual_seed(88)
 
     def rnd(*shape):
         return torch.randn(*shape, generator=g).to(dev, dtype)
 
     q_s, kn_s, vn_s = rnd(Bc, 1, Hq, D).permute(0, 2, 1, 3), rnd(Bc, Hkv, 1, D), rnd(Bc, Hkv, 1, D)
-    kp, vp = rnd(n_pages, Hkv, PAGE, D), rnd(n_pages, Hkv, PAGE, D)
+    kp, vp = rnd(n_pages, Hkv, PREFIX_PAGE, D), rnd(n_pages, Hkv, PREFIX_PAGE, D)
     o_s = torch.empty(Bc, 1, Hq, D, dtype=dtype, device=dev).permute(0, 2, 1, 3)
 
     def table_of(seed):
@@ -387,8 +273,8 @@ def test_shared_prefix_step_replays_in_a_graph():
             q_s.copy_(rnd(Bc, 1, Hq, D).permute(0, 2, 1, 3))
             kn_s.copy_(rnd(Bc, Hkv, 1, D))
             vn_s.copy_(rnd(Bc, Hkv, 1, D))
-            kp.copy_(rnd(n_pages, Hkv, PAGE, D))
-            vp.copy_(rnd(n_pages, Hkv, PAGE, D))
+            kp.copy_(rnd(n_pages, Hkv, PREFIX_PAGE, D))
+            vp.copy_(rnd(n_pages, Hkv, PREFIX_PAGE, D))
             lens_s.copy_(torch.tensor(lens, dtype=torch.int32))
             table_s.copy_(table_of(n))
         ke, ve = kp.clone(), vp.clone()
@@ -402,7 +288,7 @@ def test_shared_prefix_step_replays_in_a_graph():
 
 def test_shared_prefix_none_is_the_plain_call():
     from photonic_flash_attention_amd import ops
-    pr = _problem(4, 3, 64, (3, 64, 65, 130), 320, torch.bfloat16)
+    pr = prefix_problem(4, 3, 64, (3, 64, 65, 130), 320, torch.bfloat16)
     for fn in (ops.fa3_decode, ops.fa3_prefill_cache):
         kw = dict(cache_seqlens=pr["lens"], block_table=pr["table"], return_lse=True)
         plain = fn(pr["q"], pr["kp"], pr["vp"], **kw)
@@ -410,4 +296,4 @@ def test_shared_prefix_none_is_the_plain_call():
         torch.cuda.synchronize()
         assert bool(torch.isfinite(plain[0].float()).all())
         assert torch.equal(plain[0], none[0]) and torch.equal(plain[1], none[1])
-        _check_step(*plain, pr["ref"], pr["dtype"], pr["vmax"], "plain paged call")
+        check_step(*plain, pr["ref"], pr["dtype"], pr["vmax"], "plain paged call")

@@ -2,9 +2,7 @@
 ``ops.fa3_prefill_varlen`` (``pfa_fa3_*_ex`` with a ``pfa_fa3_cache_ext``) and ``PagedKVCache.release_behind_window``.
 
 The rule: with ``off_b = len_b - Sq_b``, row i of sequence b sees key j iff ``j < len_b``, ``j <= i + off_b`` and ``j > i + off_b - W``.
-The reference is fp64 attention with that rule (the ``_reference`` of tests/test_hip_decode.py plus the window term), and the bounds are
-that file's: ``|err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6`` for a 16-bit output (eps 2^-9 bf16, 2^-11 fp16), 1e-3 max-abs for
-fp32, 2e-3 on the LSE with exact agreement on which rows are -inf.
+The reference is fp64 attention with that rule, ``reference(..., window=W)`` of tests/kvcache_testlib.py, within that module's bounds.
 
 The read guarantee: with ``lo_b = max(0, off_b - W + 1)``, keys below ``lo_b`` rounded down to a multiple of 64 and block-table entries
 below ``lo_b // page_size`` are never read.  Every kernel call here gets caches whose keys at and past ``len_b`` AND below that boundary
@@ -23,92 +21,27 @@ import functools
 import pytest
 import torch
 
+from kvcache_testlib import NAN, capture, check_lse, check_out, device, i32, reference
+
 pytestmark = pytest.mark.gpu
 
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
-NAN = float("nan")
 DT_D = [(torch.bfloat16, 128), (torch.float16, 64), (torch.bfloat16, 64), (torch.float16, 128)]
 DT_IDS = ["bf16-d128", "fp16-d64", "bf16-d64", "fp16-d128"]
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _i32(x):
-    return torch.tensor(x, dtype=torch.int32, device=_dev())
-
-
-def _reference(q, k, v, seqlens, key_mask, scale, window):
-    """fp64 on the GPU from CLEAN caches: q [B,H,Sq,D], k/v [B,Hkv,Smax,D], bottom-right causal, window None or W
-    -> (o, lse, ||p_row||_2)."""
-    B, H, Sq, D = q.shape
-    Hkv, Smax = k.shape[1], k.shape[2]
-    g = H // Hkv
-    kd = k.double().repeat_interleave(g, dim=1)
-    vd = v.double().repeat_interleave(g, dim=1)
-    s = (q.double() @ kd.transpose(-1, -2)) * scale
-    j = torch.arange(Smax, device=q.device)
-    i = torch.arange(Sq, device=q.device)
-    L = seqlens.to(q.device).long()
-    diag = L[:, None, None] - Sq + i[None, :, None]                                   # i + off_b
-    vis = (j[None, None, :] < L[:, None, None]) & (j[None, None, :] <= diag)
-    if window is not None:
-        vis = vis & (j[None, None, :] > diag - window)
-    if key_mask is not None:
-        vis = vis & key_mask.to(q.device).bool()[:, None, :]
-    s = s.masked_fill(~vis[:, None], float("-inf"))
-    m = s.amax(-1, keepdim=True)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    safe = torch.where(l > 0, l, torch.ones_like(l))
-    pn = p / safe
-    o = pn @ vd
-    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
-    return o, lse, pn.norm(dim=-1, keepdim=True)
-
-
-def _check(got, ref, pnorm, vmax, dtype, what=""):
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output -- a key past len_b or behind the window's 64-key boundary was read"
-    err = (got.double() - ref).abs()
-    if got.dtype == torch.float32:
-        print(f"{what}: max-abs {float(err.max()):.3e} (fp32, bound 1e-3)")
-        assert float(err.max()) <= 1e-3, (what, float(err.max()))
-        return
-    eps = EPS[dtype]
-    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
-    worst = float((err - bound).max())
-    print(f"{what}: max-abs {float(err.max()):.3e}, closest to the bound {worst:.3e}")
-    assert worst <= 0, f"{what}: max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
-
-
-def _check_lse(o, lse, rlse, what=""):
-    fin = torch.isfinite(rlse)
-    assert torch.equal(torch.isfinite(lse), fin), what
-    assert not bool(torch.isnan(lse).any())
-    assert bool((lse[~fin] == float("-inf")).all())
-    assert bool((o[~fin[..., None].expand_as(o)] == 0).all()), what          # a row with no visible key: exactly zero
-    if bool(fin.any()):
-        d = float((lse.double() - rlse)[fin].abs().max())
-        print(f"{what}: LSE max-abs {d:.3e}")
-        assert d <= 2e-3, (what, d)
 
 
 @functools.lru_cache(maxsize=None)
 def _kv(B, Hkv, Smax, D, dtype, seed=0):
     """Clean caches [B,Hkv,Smax,D]; shared and never modified."""
-    g = torch.Generator(device=_dev()).manual_seed(500 + 7 * D + seed + (0 if dtype is torch.bfloat16 else 1))
-    k = torch.randn(B, Hkv, Smax, D, generator=g, device=_dev()).to(dtype)
-    v = torch.randn(B, Hkv, Smax, D, generator=g, device=_dev()).to(dtype)
+    g = torch.Generator(device=device()).manual_seed(500 + 7 * D + seed + (0 if dtype is torch.bfloat16 else 1))
+    k = torch.randn(B, Hkv, Smax, D, generator=g, device=device()).to(dtype)
+    v = torch.randn(B, Hkv, Smax, D, generator=g, device=device()).to(dtype)
     return k, v
 
 
 @functools.lru_cache(maxsize=None)
 def _q(shape, dtype, seed=0):
-    g = torch.Generator(device=_dev()).manual_seed(900 + seed + shape[-1])
-    return torch.randn(*shape, generator=g, device=_dev()).to(dtype)
+    g = torch.Generator(device=device()).manual_seed(900 + seed + shape[-1])
+    return torch.randn(*shape, generator=g, device=device()).to(dtype)
 
 
 def _q4(B, H, Sq, D, dtype, seed=0):
@@ -143,12 +76,12 @@ def _decode_and_check(dtype, D, H, Hkv, Sq, W, lens, Smax=1024, key_mask=None, o
     k, v = _kv(B, Hkv, Smax, D, dtype)
     q = _q4(B, H, Sq, D, dtype)
     kn, vn = _guard(k, v, lens, [Sq] * B, W)
-    o, lse = ops.fa3_decode(q, kn, vn, cache_seqlens=_i32(lens), key_mask=key_mask, window=W, return_lse=True, out_dtype=out_dtype)
+    o, lse = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(lens), key_mask=key_mask, window=W, return_lse=True, out_dtype=out_dtype)
     torch.cuda.synchronize()
-    ref, rlse, pn = _reference(q, k, v, _i32(lens), key_mask, D ** -0.5, W)
+    ref, rlse, pn = reference(q, k, v, seqlens=i32(lens), key_mask=key_mask, window=W)
     what = f"decode Sq {Sq} W {W}"
-    _check(o, ref, pn, float(v.abs().max()), dtype, what)
-    _check_lse(o, lse, rlse, what)
+    check_out(o, ref, pn, float(v.abs().max()), dtype, what)
+    check_lse(o, lse, rlse, what)
     return o, lse
 
 
@@ -170,13 +103,13 @@ def test_decode_window_many_row_blocks_share_a_split_range():
 def test_decode_window_combined_with_a_left_padding_key_mask():
     Smax = 1024
     for pad, W in (([100, 0], 200), ([900, 500], 200), ([37, 460], 65)):      # the second: the window of batch 0 reaches into the padding
-        km = torch.ones(2, Smax, dtype=torch.bool, device=_dev())
+        km = torch.ones(2, Smax, dtype=torch.bool, device=device())
         for b, n in enumerate(pad):
             km[b, :n] = False
         for Sq in (1, 5):
             _decode_and_check(torch.bfloat16, 128, 8, 2, Sq, W, LENS2, key_mask=km)
     # a window that lies wholly inside the padding: no visible key, O = 0 and LSE = -inf
-    km = torch.ones(2, Smax, dtype=torch.bool, device=_dev())
+    km = torch.ones(2, Smax, dtype=torch.bool, device=device())
     km[0, :990] = False
     o, lse = _decode_and_check(torch.bfloat16, 128, 8, 2, 1, 5, [990, 517], key_mask=km)
     assert bool((o[0] == 0).all()) and bool((lse[0] == float("-inf")).all()) and bool(torch.isfinite(lse[1]).all())
@@ -193,12 +126,12 @@ def _prefill_and_check(dtype, D, W, lens, Sq=300, Smax=768, out_dtype=None):
     k, v = _kv(B, Hkv, Smax, D, dtype, seed=1)
     q = _q4(B, H, Sq, D, dtype, seed=1)
     kn, vn = _guard(k, v, lens, [Sq] * B, W)
-    o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=_i32(lens), window=W, return_lse=True, out_dtype=out_dtype)
+    o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), window=W, return_lse=True, out_dtype=out_dtype)
     torch.cuda.synchronize()
-    ref, rlse, pn = _reference(q, k, v, _i32(lens), None, D ** -0.5, W)
+    ref, rlse, pn = reference(q, k, v, seqlens=i32(lens), window=W)
     what = f"prefill lens {lens} W {W}"
-    _check(o, ref, pn, float(v.abs().max()), dtype, what)
-    _check_lse(o, lse, rlse, what)
+    check_out(o, ref, pn, float(v.abs().max()), dtype, what)
+    check_lse(o, lse, rlse, what)
     return o, lse
 
 
@@ -235,7 +168,7 @@ def _ragged(dtype, D, W, out_dtype=None, guard=True):
     k, v = _kv(RB, RHKV, RSMAX, D, dtype, seed=2)
     q = _q((TOTAL, RH, D), dtype, seed=2)
     kn, vn = _guard(k, v, KV_LENS, Q_LENS, W) if guard else (k, v)
-    o, lse = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS), window=W,
+    o, lse = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS), window=W,
                                     return_lse=True, out_dtype=out_dtype)
     torch.cuda.synchronize()
     return q, k, v, kn, vn, o, lse
@@ -252,10 +185,10 @@ def test_ragged_window_against_fp64_and_per_sequence_calls(dtype, D, W):
             continue
         qb = q[CU[b]:CU[b + 1]].permute(1, 0, 2)[None]
         got, gl = o[CU[b]:CU[b + 1]].permute(1, 0, 2)[None], lse[None, :, CU[b]:CU[b + 1]]
-        ref, rlse, pn = _reference(qb, k[b:b + 1], v[b:b + 1], _i32(KV_LENS[b:b + 1]), None, D ** -0.5, W)
-        _check(got, ref, pn, float(v.abs().max()), dtype, f"ragged sequence {b} W {W}")
-        _check_lse(got, gl, rlse, f"ragged sequence {b} W {W}")
-        ou, lu = ops.fa3_prefill_cache(qb, kn[b:b + 1], vn[b:b + 1], cache_seqlens=_i32(KV_LENS[b:b + 1]), window=W, return_lse=True)
+        ref, rlse, pn = reference(qb, k[b:b + 1], v[b:b + 1], seqlens=i32(KV_LENS[b:b + 1]), window=W)
+        check_out(got, ref, pn, float(v.abs().max()), dtype, f"ragged sequence {b} W {W}")
+        check_lse(got, gl, rlse, f"ragged sequence {b} W {W}")
+        ou, lu = ops.fa3_prefill_cache(qb, kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32(KV_LENS[b:b + 1]), window=W, return_lse=True)
         torch.cuda.synchronize()
         assert torch.equal(got, ou), f"sequence {b}: O differs from the per-sequence call"
         assert torch.equal(gl, lu), f"sequence {b}: LSE differs from the per-sequence call"
@@ -270,8 +203,8 @@ def test_a_window_that_hides_nothing_changes_no_bit():
             k, v = _kv(2, Hkv, 1024, D, dtype)
             q = _q4(2, H, Sq, D, dtype)
             kn, vn = _guard(k, v, LENS2, [Sq] * 2, None)
-            a = ops.fa3_decode(q, kn, vn, cache_seqlens=_i32(LENS2), return_lse=True)
-            b = ops.fa3_decode(q, kn, vn, cache_seqlens=_i32(LENS2), return_lse=True, window=1024 + Sq)
+            a = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(LENS2), return_lse=True)
+            b = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(LENS2), return_lse=True, window=1024 + Sq)
             torch.cuda.synchronize()
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), ("decode", D, Sq, H)
         k, v = _kv(2, 2, 768, D, dtype, seed=1)
@@ -279,8 +212,8 @@ def test_a_window_that_hides_nothing_changes_no_bit():
         for lens in ([700, 300], [120, 700]):
             kn, vn = _guard(k, v, lens, [300] * 2, None)
             for od in (None, torch.float32):
-                a = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=_i32(lens), return_lse=True, out_dtype=od)
-                b = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=_i32(lens), return_lse=True, out_dtype=od, window=768 + 300)
+                a = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), return_lse=True, out_dtype=od)
+                b = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), return_lse=True, out_dtype=od, window=768 + 300)
                 torch.cuda.synchronize()
                 assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), ("prefill", D, lens, od)
         plain = _ragged(dtype, D, None)
@@ -324,8 +257,8 @@ def test_paged_equals_contiguous_with_a_window(page):
                 q = _q4(2, 8, Sq, D, dtype)
                 kn, vn = _guard(k, v, LENS2, [Sq] * 2, W)
                 kp, vp, table = _scatter(kn, vn, page, page + D + Sq, LENS2, [Sq] * 2, W)
-                a = ops.fa3_decode(q, kn, vn, cache_seqlens=_i32(LENS2), return_lse=True, window=W)
-                b = ops.fa3_decode(q, kp, vp, cache_seqlens=_i32(LENS2), return_lse=True, window=W, block_table=table)
+                a = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(LENS2), return_lse=True, window=W)
+                b = ops.fa3_decode(q, kp, vp, cache_seqlens=i32(LENS2), return_lse=True, window=W, block_table=table)
                 torch.cuda.synchronize()
                 assert bool(torch.isfinite(b[0]).all()), "a released table entry or a foreign page was read"
                 assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), ("decode", D, W, Sq)
@@ -335,15 +268,15 @@ def test_paged_equals_contiguous_with_a_window(page):
             lens = [700, 300]
             kn, vn = _guard(k, v, lens, [300] * 2, W)
             kp, vp, table = _scatter(kn, vn, page, page + D, lens, [300] * 2, W)
-            a = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=_i32(lens), return_lse=True, window=W)
-            b = ops.fa3_prefill_cache(q, kp, vp, cache_seqlens=_i32(lens), return_lse=True, window=W, block_table=table)
+            a = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), return_lse=True, window=W)
+            b = ops.fa3_prefill_cache(q, kp, vp, cache_seqlens=i32(lens), return_lse=True, window=W, block_table=table)
             torch.cuda.synchronize()
             assert bool(torch.isfinite(b[0]).all())
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), ("prefill", D, W)
             # ragged
             q, _, _, kn, vn, o, lse = _ragged(dtype, D, W)
             kp, vp, table = _scatter(kn, vn, page, page + D + 1, KV_LENS, Q_LENS, W)
-            op, lp = ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS), window=W,
+            op, lp = ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS), window=W,
                                             return_lse=True, block_table=table)
             torch.cuda.synchronize()
             assert bool(torch.isfinite(op[:CU[-1]]).all())
@@ -354,7 +287,7 @@ def test_paged_equals_contiguous_with_a_window(page):
 
 def test_released_pages_are_never_read():
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev = _dev()
+    dev = device()
     Hq, Hkv, D, page, W, SQ = 8, 2, 128, 64, 128, 40
     cache = PagedKVCache(num_pages=24, page_size=page, Hkv=Hkv, D=D, dtype=torch.bfloat16, device=dev, max_batch=2, max_pages_per_seq=12)
     cache.k_pool.fill_(NAN)
@@ -400,9 +333,9 @@ def test_released_pages_are_never_read():
         gk, gv = cache.gather(s)
         n = cache.length(s)
         for qq, (o, lse) in ((q40, before_p[0]), (q1, before_d)):
-            ref, rlse, pn = _reference(qq[s:s + 1], gk[None], gv[None], _i32([n]), None, D ** -0.5, W)
-            _check(o[s:s + 1], ref, pn, float(gv.abs().max()), torch.bfloat16, f"slot {s} Sq {qq.shape[2]}")
-            _check_lse(o[s:s + 1], lse[s:s + 1], rlse)
+            ref, rlse, pn = reference(qq[s:s + 1], gk[None], gv[None], seqlens=i32([n]), window=W)
+            check_out(o[s:s + 1], ref, pn, float(gv.abs().max()), torch.bfloat16, f"slot {s} Sq {qq.shape[2]}")
+            check_lse(o[s:s + 1], lse[s:s + 1], rlse)
 
     # step 1: the 40-row calls reach W + 39 keys back
     n0 = [cache.release_behind_window(s, W + SQ - 1) for s in slots]
@@ -439,9 +372,9 @@ def test_released_pages_are_never_read():
         vfull[0, :, live_from:n - 1] = vv[:n - 1 - live_from].permute(1, 0, 2)
         kfull[0, :, n - 1] = kt[0, :, 0]
         vfull[0, :, n - 1] = vt[0, :, 0]
-        ref, rlse, pn = _reference(q1[s:s + 1], kfull, vfull, _i32([n]), None, D ** -0.5, W)
-        _check(o[s:s + 1], ref, pn, float(vfull.abs().max()), torch.bfloat16, f"slot {s} after release and append")
-        _check_lse(o[s:s + 1], lse[s:s + 1], rlse)
+        ref, rlse, pn = reference(q1[s:s + 1], kfull, vfull, seqlens=i32([n]), window=W)
+        check_out(o[s:s + 1], ref, pn, float(vfull.abs().max()), torch.bfloat16, f"slot {s} after release and append")
+        check_lse(o[s:s + 1], lse[s:s + 1], rlse)
 
 
 # --- 7. reproducibility and graphs ----------------------------------------------------------------------------------------------------
@@ -451,8 +384,8 @@ def test_windowed_outputs_are_bitwise_reproducible():
     dtype, D, W = torch.bfloat16, 128, 512
     k, v = _kv(2, 2, 1024, D, dtype)
     q = _q4(2, 8, 5, D, dtype)
-    a = ops.fa3_decode(q, k, v, cache_seqlens=_i32(LENS2), return_lse=True, window=W)
-    b = ops.fa3_decode(q, k, v, cache_seqlens=_i32(LENS2), return_lse=True, window=W)
+    a = ops.fa3_decode(q, k, v, cache_seqlens=i32(LENS2), return_lse=True, window=W)
+    b = ops.fa3_decode(q, k, v, cache_seqlens=i32(LENS2), return_lse=True, window=W)
     torch.cuda.synchronize()
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     args = ops._cache_call_args("pfa_fa3_decode", q, k, v, True, None, None, None, None)[0]
@@ -461,37 +394,24 @@ def test_windowed_outputs_are_bitwise_reproducible():
     assert nsplit > 1 and name == "fa3_decode_bf16_d128_o16_win+combine"                 # several splits were merged
     k, v = _kv(2, 2, 768, D, dtype, seed=1)
     q = _q4(2, 4, 300, D, dtype, seed=1)
-    a = ops.fa3_prefill_cache(q, k, v, cache_seqlens=_i32([700, 300]), return_lse=True, window=100)
-    b = ops.fa3_prefill_cache(q, k, v, cache_seqlens=_i32([700, 300]), return_lse=True, window=100)
+    a = ops.fa3_prefill_cache(q, k, v, cache_seqlens=i32([700, 300]), return_lse=True, window=100)
+    b = ops.fa3_prefill_cache(q, k, v, cache_seqlens=i32([700, 300]), return_lse=True, window=100)
     torch.cuda.synchronize()
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-
-
-def _capture(call):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        call()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = call()
-    return graph, out
 
 
 def test_graph_replays_of_windowed_decode_and_ragged_prefill():
     from photonic_flash_attention_amd import ops
     dtype, D, W = torch.bfloat16, 128, 200
-    g = torch.Generator(device=_dev()).manual_seed(71)
+    g = torch.Generator(device=device()).manual_seed(71)
     # decode
     k, v = (t.clone() for t in _kv(2, 2, 1024, D, dtype))
     q = _q4(2, 8, 5, D, dtype)
-    lens = _i32(LENS2)
-    graph, (o, lse) = _capture(lambda: ops.fa3_decode(q, k, v, cache_seqlens=lens, return_lse=True, window=W))
+    lens = i32(LENS2)
+    graph, (o, lse) = capture(lambda: ops.fa3_decode(q, k, v, cache_seqlens=lens, return_lse=True, window=W))
     for new in (None, [300, 1024], [5, 0]):
         if new is not None:
-            lens.copy_(_i32(new))
+            lens.copy_(i32(new))
             k.copy_(torch.randn(k.shape, generator=g, device=k.device).to(dtype))
             v.copy_(torch.randn(v.shape, generator=g, device=v.device).to(dtype))
         graph.replay()
@@ -499,25 +419,25 @@ def test_graph_replays_of_windowed_decode_and_ragged_prefill():
         oe, le = ops.fa3_decode(q, k, v, cache_seqlens=lens, return_lse=True, window=W)
         torch.cuda.synchronize()
         assert torch.equal(o, oe) and torch.equal(lse, le), new
-        ref, rlse, pn = _reference(q, k, v, lens, None, D ** -0.5, W)
-        _check(o, ref, pn, float(v.abs().max()), dtype, f"graph decode {new}")
-        _check_lse(o, lse, rlse)
+        ref, rlse, pn = reference(q, k, v, seqlens=lens, window=W)
+        check_out(o, ref, pn, float(v.abs().max()), dtype, f"graph decode {new}")
+        check_lse(o, lse, rlse)
     # ragged prefill
     k, v = (t.clone() for t in _kv(RB, RHKV, RSMAX, D, dtype, seed=2))
     q = _q((TOTAL, RH, D), dtype, seed=2)
-    cu, lens = _i32(CU), _i32(KV_LENS)
+    cu, lens = i32(CU), i32(KV_LENS)
     out = torch.full((TOTAL, RH, D), 7.0, dtype=dtype, device=q.device)
 
     def call(o_):
         return ops.fa3_prefill_varlen(q, k, v, cu_seqlens_q=cu, max_seqlen_q=MAXQ, cache_seqlens=lens, return_lse=True, window=W, out=o_)
 
-    graph, (o, lse) = _capture(lambda: call(out))
+    graph, (o, lse) = capture(lambda: call(out))
     states = [(None, None), ([0, 64, 64, 364, 380, 384], [1024, 0, 300, 16, 77]), (CU, KV_LENS)]
     results = []
     for new_cu, new_lens in states:
         if new_cu is not None:
-            cu.copy_(_i32(new_cu))
-            lens.copy_(_i32(new_lens))
+            cu.copy_(i32(new_cu))
+            lens.copy_(i32(new_lens))
             k.copy_(torch.randn(k.shape, generator=g, device=k.device).to(dtype))
             v.copy_(torch.randn(v.shape, generator=g, device=v.device).to(dtype))
         rows = int(cu[-1])
@@ -536,8 +456,8 @@ def test_graph_replays_of_windowed_decode_and_ragged_prefill():
                 continue
             s0 = int(cu[b])
             qb = q[s0:s0 + ql[b]].permute(1, 0, 2)[None]
-            ref, rlse, pn = _reference(qb, k[b:b + 1], v[b:b + 1], _i32(cl[b:b + 1]), None, D ** -0.5, W)
+            ref, rlse, pn = reference(qb, k[b:b + 1], v[b:b + 1], seqlens=i32(cl[b:b + 1]), window=W)
             got = o[s0:s0 + ql[b]].permute(1, 0, 2)[None]
-            _check(got, ref, pn, float(v.abs().max()), dtype, f"graph ragged sequence {b}")
-            _check_lse(got, lse[None, :, s0:s0 + ql[b]], rlse)
+            check_out(got, ref, pn, float(v.abs().max()), dtype, f"graph ragged sequence {b}")
+            check_lse(got, lse[None, :, s0:s0 + ql[b]], rlse)
     assert not torch.equal(results[0], results[1])

@@ -1,8 +1,7 @@
-"""GPU tests of the split-KV decode path (``ops.fa3_decode`` / ``pfa_fa3_decode``) against an fp64 reference built here, with the
-bottom-right causal cut, ragged cache lengths and key masks spelled out explicitly; and the Hugging Face generation loop through it.
+"""GPU tests of the split-KV decode path (``ops.fa3_decode`` / ``pfa_fa3_decode``) against fp64 attention with the bottom-right causal
+cut, ragged cache lengths and key masks; and the Hugging Face generation loop through it.
 
-Tolerance: the per-element bound of the fast variant (tests/test_hip_parity.py's docstring) for a 16-bit output,
-|err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6, and 1e-3 max-abs for an fp32 output."""
+The reference and the bounds on O and on the LSE are those of tests/kvcache_testlib.py."""
 
 from __future__ import annotations
 
@@ -11,58 +10,14 @@ import copy
 import pytest
 import torch
 
+from kvcache_testlib import EPS, check_lse, check_out, device, reference
+
 pytestmark = pytest.mark.gpu
-
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _reference(q, k, v, seqlens, key_mask, causal, scale):
-    """fp64 on the GPU: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2)."""
-    B, H, Sq, D = q.shape
-    Hkv, Smax = k.shape[1], k.shape[2]
-    g = H // Hkv
-    kd = k.double().repeat_interleave(g, dim=1)
-    vd = v.double().repeat_interleave(g, dim=1)
-    s = (q.double() @ kd.transpose(-1, -2)) * scale                                   # [B,H,Sq,Smax]
-    j = torch.arange(Smax, device=q.device)
-    i = torch.arange(Sq, device=q.device)
-    L = seqlens.to(q.device).long() if seqlens is not None else torch.full((B,), Smax, device=q.device)
-    vis = (j[None, None, :] < L[:, None, None]).expand(B, Sq, Smax)
-    if causal:
-        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])   # bottom-right, per batch
-    if key_mask is not None:
-        vis = vis & key_mask.to(q.device).bool()[:, None, :]
-    s = s.masked_fill(~vis[:, None], float("-inf"))
-    m = s.amax(-1, keepdim=True)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    safe = torch.where(l > 0, l, torch.ones_like(l))
-    pn = p / safe
-    o = pn @ vd
-    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
-    return o, lse, pn.norm(dim=-1, keepdim=True)
-
-
-def _check(got, ref, pnorm, vmax, dtype):
-    err = (got.double() - ref).abs()
-    if got.dtype == torch.float32:
-        assert float(err.max()) <= 1e-3, float(err.max())
-        return
-    eps = EPS[dtype]
-    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
-    worst = float((err - bound).max())
-    assert worst <= 0, f"max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
 
 
 def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed, layout="bhsd"):
     g = torch.Generator(device="cpu").manual_seed(seed)
-    dev = _dev()
+    dev = device()
     q = torch.randn(B, Sq, H, D, generator=g).to(dev, dtype).permute(0, 2, 1, 3)
     if layout == "bshd":        # flash-attn style [B, Smax, Hkv, D] buffer, passed as a [B, Hkv, Smax, D] view
         k = torch.randn(B, Smax, Hkv, D, generator=g).to(dev, dtype).transpose(1, 2)
@@ -76,20 +31,14 @@ def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed, layout="bhsd"):
     return q, k, v
 
 
-def _run_and_check(q, k, v, *, seqlens=None, key_mask=None, causal=True, out_dtype=None, check_lse=True):
+def _run_and_check(q, k, v, *, seqlens=None, key_mask=None, causal=True, out_dtype=None):
     from photonic_flash_attention_amd import ops
-    D = q.shape[-1]
-    scale = D ** -0.5
     o, lse = ops.fa3_decode(q, k, v, cache_seqlens=seqlens, key_mask=key_mask, causal=causal, out_dtype=out_dtype, return_lse=True)
     torch.cuda.synchronize()
-    ref, rlse, pn = _reference(q, k, v, seqlens, key_mask, causal, scale)
-    _check(o, ref, pn, float(v.abs().max()), q.dtype)
-    if check_lse:
-        fin = torch.isfinite(rlse)
-        assert torch.equal(torch.isfinite(lse), fin)
-        assert bool((o[~fin[..., None].expand_as(o)] == 0).all())
-        if bool(fin.any()):
-            assert float((lse.double() - rlse)[fin].abs().max()) <= 2e-3
+    ref, rlse, pn = reference(q, k, v, seqlens=seqlens, key_mask=key_mask, causal=causal)
+    what = f"decode Sq {q.shape[2]} Smax {k.shape[2]} D {q.shape[-1]}"
+    check_out(o, ref, pn, float(v.abs().max()), q.dtype, what)
+    check_lse(o, lse, rlse, what)
     return o, lse
 
 
@@ -169,7 +118,7 @@ def test_agrees_with_the_forward_on_a_single_token():
     od, _ = ops.fa3_decode(q, k, v, key_mask=km, causal=False)
     of, _ = ops.fa3_forward(q, k, v, key_mask=km)
     torch.cuda.synchronize()
-    ref, _, pn = _reference(q, k, v, None, km, False, 128 ** -0.5)
+    ref, _, pn = reference(q, k, v, key_mask=km, causal=False)
     eps = EPS[torch.bfloat16]
     bound = 2 * (eps * ref.abs() + 3 * eps * float(v.abs().max()) * pn + 2e-6)
     assert float(((od.double() - of.double()).abs() - bound).max()) <= 0
@@ -191,8 +140,9 @@ def test_graph_capture_replays_with_new_lengths_and_cache():
         o, lse = ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
     graph.replay()
     torch.cuda.synchronize()
-    ref, _, pn = _reference(q, k, v, sl, None, True, 128 ** -0.5)
-    _check(o, ref, pn, float(v.abs().max()), q.dtype)
+    ref, rlse, pn = reference(q, k, v, seqlens=sl)
+    check_out(o, ref, pn, float(v.abs().max()), q.dtype, "graph, first replay")
+    check_lse(o, lse, rlse, "graph, first replay")
     # new lengths and new cache contents, written in place
     sl.copy_(torch.tensor([77, 3333], dtype=torch.int32))
     g = torch.Generator(device="cpu").manual_seed(60)
@@ -200,9 +150,9 @@ def test_graph_capture_replays_with_new_lengths_and_cache():
     v.copy_(torch.randn(v.shape, generator=g).to(dev, v.dtype))
     graph.replay()
     torch.cuda.synchronize()
-    ref, rlse, pn = _reference(q, k, v, sl, None, True, 128 ** -0.5)
-    _check(o, ref, pn, float(v.abs().max()), q.dtype)
-    assert float((lse.double() - rlse).abs().max()) <= 2e-3
+    ref, rlse, pn = reference(q, k, v, seqlens=sl)
+    check_out(o, ref, pn, float(v.abs().max()), q.dtype, "graph, new lengths and cache")
+    check_lse(o, lse, rlse, "graph, new lengths and cache")
 
 
 # --- Hugging Face generation ---------------------------------------------------------------------------------------------------------
@@ -211,7 +161,7 @@ def _llama(transformers):
     torch.manual_seed(1)
     cfg = transformers.LlamaConfig(hidden_size=256, num_attention_heads=4, num_key_value_heads=2, num_hidden_layers=2,
                                    intermediate_size=512, vocab_size=500, max_position_embeddings=1024)
-    ref = transformers.LlamaForCausalLM(cfg).to(_dev()).eval()
+    ref = transformers.LlamaForCausalLM(cfg).to(device()).eval()
     ref.config._attn_implementation = "sdpa"
     from photonic_flash_attention_amd.integration.pytorch.hf import convert_hf_model
     return cfg, ref, convert_hf_model(copy.deepcopy(ref))
@@ -248,7 +198,7 @@ def _teacher_forced(transformers, ref, conv, ids, attention_mask, make_cache, pr
 def test_hf_cached_decode_steps_reach_the_decode_kernel(decode_spy):
     transformers = pytest.importorskip("transformers")
     cfg, ref, conv = _llama(transformers)
-    ids = torch.randint(0, 500, (2, 300), device=_dev())
+    ids = torch.randint(0, 500, (2, 300), device=device())
     err = _teacher_forced(transformers, ref, conv, ids, None, lambda: transformers.DynamicCache(config=cfg), 284, 16)
     print(f"DynamicCache, 16 steps: logits max-abs vs sdpa {err:.3e}")
     assert err <= 5e-2
@@ -258,7 +208,7 @@ def test_hf_cached_decode_steps_reach_the_decode_kernel(decode_spy):
 def test_hf_left_padded_batch_decode(decode_spy):
     transformers = pytest.importorskip("transformers")
     cfg, ref, conv = _llama(transformers)
-    ids = torch.randint(0, 500, (2, 200), device=_dev())
+    ids = torch.randint(0, 500, (2, 200), device=device())
     am = torch.ones(2, 200, dtype=torch.long, device=ids.device)
     am[1, :37] = 0
     err = _teacher_forced(transformers, ref, conv, ids, am, lambda: transformers.DynamicCache(config=cfg), 184, 16)
@@ -272,7 +222,7 @@ def test_hf_static_cache_decode(decode_spy):
     if not hasattr(transformers, "StaticCache"):
         pytest.skip("this transformers has no StaticCache")
     cfg, ref, conv = _llama(transformers)
-    ids = torch.randint(0, 500, (2, 150), device=_dev())
+    ids = torch.randint(0, 500, (2, 150), device=device())
     am = torch.ones(2, 150, dtype=torch.long, device=ids.device)
     am[0, :11] = 0
     err = _teacher_forced(transformers, ref, conv, ids, am,
@@ -285,7 +235,7 @@ def test_hf_static_cache_decode(decode_spy):
 def test_hf_greedy_generate(decode_spy):
     transformers = pytest.importorskip("transformers")
     cfg, ref, conv = _llama(transformers)
-    ids = torch.randint(0, 500, (2, 40), device=_dev())
+    ids = torch.randint(0, 500, (2, 40), device=device())
     with torch.no_grad():
         out = conv.generate(input_ids=ids, attention_mask=torch.ones_like(ids), max_new_tokens=8, do_sample=False)
     assert out.shape == (2, 48)

@@ -20,23 +20,16 @@ from __future__ import annotations
 import pytest
 import torch
 
+from kvcache_testlib import NAN, device, i32
+
 pytestmark = pytest.mark.gpu
 
-NAN, SENTINEL = float("nan"), -7.0
+SENTINEL = -7.0
 B, HKV, SMAX, TOTAL, MAXQ = 5, 2, 1024, 640, 300
 Q_LENS = [1, 300, 0, 33, 257]
 KV_LENS = [777, 300, 512, 20, 1000]
 CU = [0, 1, 301, 301, 334, 591]
 SHARED = 256
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _i32(x, dev=None):
-    return torch.tensor(x, dtype=torch.int32, device=_dev() if dev is None else dev)
 
 
 def _rows(shape, seed, dtype, used=None):
@@ -86,9 +79,9 @@ def _shuffled_table(page, seed):
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 def test_ragged_append_equals_the_model(dtype, D, layout):
-    dev = _dev()
+    dev = device()
     kn, vn = (t.to(dev) for t in _rows((TOTAL, HKV, D), 100 + D, dtype, used=CU[-1]))
-    lens, cu, table = _i32(KV_LENS), _i32(CU), None
+    lens, cu, table = i32(KV_LENS), i32(CU), None
     if layout == "contiguous":
         kc = torch.full((B, HKV, SMAX, D), SENTINEL, dtype=dtype, device=dev)
     elif layout == "token-major":                            # a flash-attn [B, Smax, Hkv, D] buffer as a view
@@ -115,17 +108,17 @@ def test_ragged_append_equals_the_model(dtype, D, layout):
 def test_uniform_append_equals_the_model(Sq, lens, D, view):
     """B 3.  Sq 70 to a length of 130 with pages of 64 splits sequence 0's rows 4 / 64 / 2 over three pages; 70 rows into a length of
     40 drop the first 30; D 96 is a head dim the attention kernels do not take and the copy does."""
-    dev, dtype = _dev(), torch.bfloat16
+    dev, dtype = device(), torch.bfloat16
     if view == "bhsd":
         kn, vn = (t.to(dev) for t in _rows((3, HKV, Sq, D), 7 + Sq + D, dtype))
     else:
         kn, vn = (t.to(dev).transpose(1, 2) for t in _rows((3, Sq, HKV, D), 7 + Sq + D, dtype))
     assert kn.shape == (3, HKV, Sq, D)
     kc = torch.full((3, HKV, 256, D), SENTINEL, dtype=dtype, device=dev)
-    _run_and_compare(kn, vn, kc, torch.full_like(kc, SENTINEL), _i32(lens))
-    table = _i32([[5, 2, 7, 0], [1, 3, 4, 6], [8, 9, 10, 11]])
+    _run_and_compare(kn, vn, kc, torch.full_like(kc, SENTINEL), i32(lens))
+    table = i32([[5, 2, 7, 0], [1, 3, 4, 6], [8, 9, 10, 11]])
     kp = torch.full((13, 64, HKV, D), SENTINEL, dtype=dtype, device=dev).transpose(1, 2)
-    mk, _ = _run_and_compare(kn, vn, kp, torch.full_like(kp, SENTINEL), _i32(lens), table)
+    mk, _ = _run_and_compare(kn, vn, kp, torch.full_like(kp, SENTINEL), i32(lens), table)
     if Sq == 70 and lens[0] == 130:
         assert [int((mk[p] != SENTINEL).any(-1)[0].sum()) for p in (5, 2, 7, 0)] == [4, 64, 2, 0]
     assert bool((mk[12] == SENTINEL).all())
@@ -134,12 +127,12 @@ def test_uniform_append_equals_the_model(Sq, lens, D, view):
 @pytest.mark.parametrize("paged", [False, True], ids=["contiguous", "paged"])
 def test_rows_past_max_seqlen_q_are_neither_read_nor_written(paged):
     """300 rows with max_seqlen_q = 256: the first 256 land at len_b - 256 + i, where the attention call of that bound looks for them."""
-    dev, dtype, D = _dev(), torch.bfloat16, 64
+    dev, dtype, D = device(), torch.bfloat16, 64
     kn, vn = (t.to(dev) for t in _rows((320, HKV, D), 55, dtype, used=300))
     kn[256:300], vn[256:300] = NAN, NAN                      # owned by the sequence, but past the bound
-    lens, cu = _i32([400]), _i32([0, 300])
+    lens, cu = i32([400]), i32([0, 300])
     if paged:
-        table = _i32([[6, 1, 4, 3, 0, 2, 7, 5]])
+        table = i32([[6, 1, 4, 3, 0, 2, 7, 5]])
         kc = torch.full((9, 64, HKV, D), SENTINEL, dtype=dtype, device=dev).transpose(1, 2)
     else:
         table = None
@@ -157,7 +150,7 @@ FB, FH, FSMAX, FD = 2, 4, 256, 64
 
 def _fused_fixture(sq_of, lens, seed):
     """Contiguous caches [2, Hkv, 256, D]: valid keys below ``len_b - Sq_b``, NaN from there on (the step's own rows included)."""
-    dev, dtype = _dev(), torch.bfloat16
+    dev, dtype = device(), torch.bfloat16
     kc, vc = (t.to(dev) for t in _rows((FB, HKV, FSMAX, FD), seed, dtype))
     for b in range(FB):
         kc[b, :, lens[b] - sq_of[b]:] = NAN
@@ -168,7 +161,7 @@ def _fused_fixture(sq_of, lens, seed):
 @pytest.mark.parametrize("entry,Sq", [("fa3_decode", 1), ("fa3_decode", 3), ("fa3_prefill_cache", 40)])
 def test_uniform_attention_calls_append_first(entry, Sq):
     from photonic_flash_attention_amd import ops
-    dev, dtype, lens = _dev(), torch.bfloat16, [100, 256]
+    dev, dtype, lens = device(), torch.bfloat16, [100, 256]
     fn = getattr(ops, entry)
     kc, vc = _fused_fixture([Sq, Sq], lens, 300 + Sq)
     kn, vn = (t.to(dev) for t in _rows((FB, HKV, Sq, FD), 301 + Sq, dtype))
@@ -177,8 +170,8 @@ def test_uniform_attention_calls_append_first(entry, Sq):
     for b in range(FB):                                      # the rows written with torch indexing, then the call as it was
         rk[b, :, lens[b] - Sq:lens[b]] = kn[b]
         rv[b, :, lens[b] - Sq:lens[b]] = vn[b]
-    o_ref, lse_ref = fn(q, rk, rv, cache_seqlens=_i32(lens), return_lse=True)
-    o, lse = fn(q, kc, vc, cache_seqlens=_i32(lens), return_lse=True, k_new=kn, v_new=vn)
+    o_ref, lse_ref = fn(q, rk, rv, cache_seqlens=i32(lens), return_lse=True)
+    o, lse = fn(q, kc, vc, cache_seqlens=i32(lens), return_lse=True, k_new=kn, v_new=vn)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(o_ref.float()).all())
     assert torch.equal(o, o_ref) and torch.equal(lse, lse_ref)
@@ -186,13 +179,13 @@ def test_uniform_attention_calls_append_first(entry, Sq):
     with pytest.raises(ValueError, match="k_new / v_new need cache_seqlens"):
         fn(q, kc, vc, k_new=kn, v_new=vn)
     with pytest.raises(ValueError, match="go together"):
-        fn(q, kc, vc, cache_seqlens=_i32(lens), k_new=kn)
+        fn(q, kc, vc, cache_seqlens=i32(lens), k_new=kn)
 
 
 @pytest.mark.parametrize("paged", [False, True], ids=["contiguous", "paged"])
 def test_ragged_attention_call_appends_first(paged):
     from photonic_flash_attention_amd import ops
-    dev, dtype = _dev(), torch.bfloat16
+    dev, dtype = device(), torch.bfloat16
     q_lens, lens, cu = [3, 50], [100, 256], [0, 3, 53]
     kc, vc = _fused_fixture(q_lens, lens, 400)
     kn, vn = (t.to(dev) for t in _rows((64, HKV, FD), 401, dtype, used=53))
@@ -200,7 +193,7 @@ def test_ragged_attention_call_appends_first(paged):
     table = None
     if paged:                                                # the same keys in a pool of 64-key pages, shuffled, one page unnamed
         ids = [[7, 2, 5, 0], [3, 8, 1, 6]]
-        table = _i32(ids)
+        table = i32(ids)
         kp = torch.full((9, HKV, 64, FD), NAN, dtype=dtype, device=dev)
         vp = torch.full_like(kp, NAN)
         for b in range(FB):
@@ -213,7 +206,7 @@ def test_ragged_attention_call_appends_first(paged):
             pos = lens[b] - q_lens[b] + i
             slab, tok = (ids[b][pos // 64], pos % 64) if paged else (b, pos)
             rk[slab, :, tok], rv[slab, :, tok] = kn[cu[b] + i], vn[cu[b] + i]
-    kw = dict(cu_seqlens_q=_i32(cu), max_seqlen_q=50, cache_seqlens=_i32(lens), block_table=table, return_lse=True)
+    kw = dict(cu_seqlens_q=i32(cu), max_seqlen_q=50, cache_seqlens=i32(lens), block_table=table, return_lse=True)
     o_ref, lse_ref = ops.fa3_prefill_varlen(q, rk, rv, **kw)
     o, lse = ops.fa3_prefill_varlen(q, kc, vc, k_new=kn, v_new=vn, **kw)
     torch.cuda.synchronize()
@@ -229,7 +222,7 @@ def test_whole_step_replays_in_a_graph():
     ahead; three replays with different ``q_lens``, ``advance`` and in-place refreshes in between, against an eager twin driven by
     ``append_varlen`` + ``prefill_varlen``."""
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev, dtype, H, D, rows, bound = _dev(), torch.bfloat16, 4, 64, 160, 130
+    dev, dtype, H, D, rows, bound = device(), torch.bfloat16, 4, 64, 160, 130
 
     def make():
         c = PagedKVCache(num_pages=14, page_size=64, Hkv=HKV, D=D, dtype=dtype, device=dev, max_batch=3, max_pages_per_seq=4)

@@ -16,20 +16,12 @@ from __future__ import annotations
 import pytest
 import torch
 
+from kvcache_testlib import EPS, device, i32
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.0
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}      # tests/test_hip_attn_merge.py's, copied from tests/test_hip_decode.py
 HKV = 2
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _i32(x):
-    return torch.tensor(x, dtype=torch.int32, device=_dev())
 
 
 # ---- the kernel against the model -----------------------------------------------------------------------------------------------
@@ -51,7 +43,7 @@ def _pools(num_pages, page_size, D, random_pages, token_major, seed, dtype):
 
 def _to_dev(pool, token_major):
     """The same view of the same memory layout on the GPU."""
-    return pool.transpose(1, 2).contiguous().to(_dev()).transpose(1, 2) if token_major else pool.contiguous().to(_dev())
+    return pool.transpose(1, 2).contiguous().to(device()).transpose(1, 2) if token_major else pool.contiguous().to(device())
 
 
 @pytest.mark.parametrize("token_major", [False, True], ids=["head-major", "token-major"])
@@ -75,8 +67,8 @@ def test_kernel_equals_the_model_on_the_whole_pools(dtype, D, page_size, token_m
         ops.page_copy(mk, mv, pair_t, rows=row_t)                                               # the model
         assert not torch.equal(mk, kp) and bool((mk[10:] == SENTINEL).all())
         dk, dv = _to_dev(kp, token_major), _to_dev(vp, token_major)
-        dpairs = pair_t.to(_dev()) if pair_t.is_contiguous() else wide.to(_dev())[:, :2]
-        drows = None if row_t is None else row_t.to(_dev())
+        dpairs = pair_t.to(device()) if pair_t.is_contiguous() else wide.to(device())[:, :2]
+        drows = None if row_t is None else row_t.to(device())
         ops.page_copy(dk, dv, dpairs, rows=drows)
         torch.cuda.synchronize()
         assert torch.equal(dk.cpu(), mk) and torch.equal(dv.cpu(), mv), (row_l, dpairs.stride())
@@ -88,10 +80,10 @@ def test_kernel_equals_the_model_on_the_whole_pools(dtype, D, page_size, token_m
 def test_an_empty_pair_list_launches_nothing_and_empty_pairs_write_nothing():
     from photonic_flash_attention_amd import ops
     kp, vp = _pools(9, 64, 64, (0, 1), False, 9, torch.bfloat16)
-    dk, dv = kp.to(_dev()), vp.to(_dev())
-    ops.page_copy(dk, dv, _i32([[0, 1]])[:0])
-    ops.page_copy(dk, dv, torch.full((3, 2), -1, dtype=torch.int32, device=_dev()), rows=_i32([-1, -1, -1]))     # a cache's idle table
-    ops.page_copy(dk, dv, _i32([[1, 1], [0, 0]]))
+    dk, dv = kp.to(device()), vp.to(device())
+    ops.page_copy(dk, dv, i32([[0, 1]])[:0])
+    ops.page_copy(dk, dv, torch.full((3, 2), -1, dtype=torch.int32, device=device()), rows=i32([-1, -1, -1]))     # a cache's idle table
+    ops.page_copy(dk, dv, i32([[1, 1], [0, 0]]))
     torch.cuda.synchronize()
     assert torch.equal(dk.cpu(), kp) and torch.equal(dv.cpu(), vp)
 
@@ -103,7 +95,7 @@ H, D, PAGE = 4, 64, 64
 
 def _cache(cow, **kw):
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    base = dict(num_pages=12, page_size=PAGE, Hkv=HKV, D=D, dtype=torch.bfloat16, device=_dev(), max_batch=3, max_pages_per_seq=4)
+    base = dict(num_pages=12, page_size=PAGE, Hkv=HKV, D=D, dtype=torch.bfloat16, device=device(), max_batch=3, max_pages_per_seq=4)
     base.update(kw)
     c = PagedKVCache(**base, copy_on_write=cow)
     c.k_pool.fill_(SENTINEL)
@@ -112,7 +104,7 @@ def _cache(cow, **kw):
 
 
 def _randn(g, *shape):
-    return torch.randn(*shape, generator=g).to(torch.bfloat16).to(_dev())
+    return torch.randn(*shape, generator=g).to(torch.bfloat16).to(device())
 
 
 def _same_keys(cache, twin, slots):
@@ -221,7 +213,7 @@ def test_a_captured_step_replays_through_fork_and_free():
     """``write_step`` + ``decode`` over all slots captured once (a single chain on one stream) on a ``copy_on_write`` cache with pages
     reserved ahead; replays after ``advance``, after ``fork`` + ``advance`` of both, and after ``free(parent)`` + ``advance(child)``,
     against an eager twin that shares nothing."""
-    dev, dtype = _dev(), torch.bfloat16
+    dev, dtype = device(), torch.bfloat16
     g = torch.Generator().manual_seed(99)
     hist_k, hist_v = _randn(g, 1, HKV, 100, D), _randn(g, 1, HKV, 100, D)
     cache, twin = _cache(True), _cache(False)

@@ -3,9 +3,8 @@
 The central check needs no tolerance: a paged call returns the same bits as the contiguous call on the gathered cache -- the
 arithmetic and its order are identical, only addresses differ.  Every case builds a contiguous ``[B, Hkv, Smax, D]`` cache,
 scatters it into a pool in a seeded random page order with unused pages in between (filled with NaN, so a read of a page no
-table entry names shows), runs both calls and asserts ``torch.equal`` on O and on the LSE.  One anchor against an fp64 reference
-(the one of tests/test_hip_decode.py, restated here with its bound: |err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6 for a
-16-bit output, 1e-3 max-abs for fp32) keeps the suite from resting on the contiguous path alone.
+table entry names shows), runs both calls and asserts ``torch.equal`` on O and on the LSE.  One anchor against the fp64 reference
+of tests/kvcache_testlib.py, within its bounds, keeps the suite from resting on the contiguous path alone.
 
 Only in-range page ids are ever put into a table: the kernel's clamp is reviewed in the code, not provoked on the device."""
 
@@ -14,50 +13,9 @@ from __future__ import annotations
 import pytest
 import torch
 
+from kvcache_testlib import NAN, check_lse, check_out, contiguous_of, device, gen, problem, reference, scatter
+
 pytestmark = pytest.mark.gpu
-
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _gen(seed):
-    return torch.Generator(device=_dev()).manual_seed(seed)
-
-
-def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed):
-    g = _gen(seed)
-    dev = _dev()
-    q = torch.randn(B, Sq, H, D, generator=g, device=dev).to(dtype).permute(0, 2, 1, 3)
-    k = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
-    v = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
-    return q, k, v
-
-
-def _scatter(k, v, page, seed, layout="phsd", spare=5):
-    """Scatter contiguous [B, Hkv, Smax, D] caches over pools in a random page order.  -> (k_pool, v_pool, table) with the pools as
-    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN."""
-    B, Hkv, Smax, D = k.shape
-    assert Smax % page == 0
-    pages = Smax // page
-    NP = B * pages + spare
-    dev = k.device
-    perm = torch.randperm(NP, generator=torch.Generator().manual_seed(seed))[:B * pages]
-    table = perm.to(torch.int32).reshape(B, pages).to(dev)
-    pools = []
-    for src in (k, v):
-        if layout == "phsd":        # flash-attn style [num_pages, page, Hkv, D], passed transposed
-            pool = torch.full((NP, page, Hkv, D), float("nan"), dtype=k.dtype, device=dev).transpose(1, 2)
-        elif layout == "hpsd":
-            pool = torch.full((NP, Hkv, page, D), float("nan"), dtype=k.dtype, device=dev)
-        else:                       # every second page of a larger pool, whose pages also have room for 64 more keys
-            pool = torch.full((2 * NP, Hkv, page + 64, D), float("nan"), dtype=k.dtype, device=dev)[::2, :, :page]
-        pool[perm.to(dev)] = src.reshape(B, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(B * pages, Hkv, page, D)
-        pools.append(pool)
-    return pools[0], pools[1], table
 
 
 def _both(q, k, v, kp, vp, table, **kw):
@@ -78,11 +36,11 @@ def test_paged_equals_contiguous(page, D):
     Smax = max(2048, 3 * page)
     for dtype in (torch.bfloat16, torch.float16):
         for H, Hkv in ((32, 8), (8, 8), (64, 1)):
-            _, k, v = _problem(2, H, Hkv, 1, Smax, D, dtype, seed=page + D + H)
-            kp, vp, table = _scatter(k, v, page, seed=page + H)
+            _, k, v = problem(2, H, Hkv, 1, Smax, D, dtype, seed=page + D + H)
+            kp, vp, table = scatter(k, v, page, seed=page + H)
             sl = torch.tensor([Smax, Smax // 2 + 17], dtype=torch.int32, device=k.device)
             for Sq in (1, 4, 8):
-                q = torch.randn(2, Sq, H, D, generator=_gen(Sq), device=k.device).to(dtype).permute(0, 2, 1, 3)
+                q = torch.randn(2, Sq, H, D, generator=gen(Sq), device=k.device).to(dtype).permute(0, 2, 1, 3)
                 for causal in ((True, False) if Sq > 1 else (True,)):
                     for out_dtype in (None, torch.float32):
                         _both(q, k, v, kp, vp, table, cache_seqlens=sl, causal=causal, out_dtype=out_dtype)
@@ -92,14 +50,14 @@ def test_paged_equals_contiguous(page, D):
 @pytest.mark.parametrize("page", [64, 256, 1024])
 def test_ragged_lengths(page):
     Smax = 4 * page
-    q, k, v = _problem(7, 32, 8, 1, Smax, 128, torch.bfloat16, seed=page)
-    kp, vp, table = _scatter(k, v, page, seed=1)
+    q, k, v = problem(7, 32, 8, 1, Smax, 128, torch.bfloat16, seed=page)
+    kp, vp, table = scatter(k, v, page, seed=1)
     sl = torch.tensor([0, 1, page, page + 1, Smax, 2 * page - 1, 63], dtype=torch.int32, device=q.device)
     o, lse = _both(q, k, v, kp, vp, table, cache_seqlens=sl)
     assert bool((o[0] == 0).all()) and bool(torch.isinf(lse[0]).all())
     _both(q, k, v, kp, vp, table, cache_seqlens=sl, out_dtype=torch.float32)
     # bottom-right causal with rows that see nothing: lengths below Sq - 1
-    q4, _, _ = _problem(7, 32, 8, 4, Smax, 128, torch.bfloat16, seed=page + 1)
+    q4, _, _ = problem(7, 32, 8, 4, Smax, 128, torch.bfloat16, seed=page + 1)
     sl4 = torch.tensor([0, 2, 3, page + 1, Smax, 1, page], dtype=torch.int32, device=q.device)
     o, lse = _both(q4, k, v, kp, vp, table, cache_seqlens=sl4, causal=True)
     assert bool(torch.isinf(lse[1, :, 0]).all()) and bool((o[1, :, 0] == 0).all())      # len 2, Sq 4: row 0 sees key j <= -2
@@ -110,8 +68,8 @@ def test_ragged_lengths(page):
 @pytest.mark.parametrize("page", [64, 256])
 def test_key_mask_left_padding_and_a_hole(page):
     B, Smax = 3, 2048
-    q, k, v = _problem(B, 32, 8, 1, Smax, 128, torch.bfloat16, seed=5)
-    kp, vp, table = _scatter(k, v, page, seed=2)
+    q, k, v = problem(B, 32, 8, 1, Smax, 128, torch.bfloat16, seed=5)
+    kp, vp, table = scatter(k, v, page, seed=2)
     dev = q.device
     sl = torch.tensor([2048, 1500, 700], dtype=torch.int32, device=dev)
     km = torch.ones(B, Smax, dtype=torch.bool, device=dev)
@@ -130,8 +88,8 @@ def test_key_mask_left_padding_and_a_hole(page):
 
 @pytest.mark.parametrize("layout", ["phsd", "hpsd", "slice"])
 def test_pool_layouts(layout):
-    q, k, v = _problem(2, 32, 8, 4, 5120, 128, torch.bfloat16, seed=9)
-    kp, vp, table = _scatter(k, v, 256, seed=3, layout=layout)
+    q, k, v = problem(2, 32, 8, 4, 5120, 128, torch.bfloat16, seed=9)
+    kp, vp, table = scatter(k, v, 256, seed=3, layout=layout)
     assert kp.is_contiguous() == (layout == "hpsd")
     sl = torch.tensor([5120, 2222], dtype=torch.int32, device=q.device)
     _both(q, k, v, kp, vp, table, cache_seqlens=sl)
@@ -139,82 +97,40 @@ def test_pool_layouts(layout):
 
 def test_two_sequences_sharing_prefix_pages():
     page = 128
-    q, k, v = _problem(3, 32, 8, 1, 2048, 128, torch.bfloat16, seed=10)
+    q, k, v = problem(3, 32, 8, 1, 2048, 128, torch.bfloat16, seed=10)
     k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
     v[1, :, :5 * page] = v[0, :, :5 * page]
-    kp, vp, table = _scatter(k, v, page, seed=4)
+    kp, vp, table = scatter(k, v, page, seed=4)
     freed = table[1, :5].clone()
     table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
     for pool in (kp, vp):
-        pool[freed.long()] = float("nan")            # the duplicate copies are gone
+        pool[freed.long()] = NAN          # the duplicate copies are gone
     sl = torch.tensor([2048, 5 * page + 70, 900], dtype=torch.int32, device=q.device)
     _both(q, k, v, kp, vp, table, cache_seqlens=sl)
-
-
-def _reference(q, k, v, seqlens, key_mask, causal, scale):
-    """fp64 on the GPU: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2)."""
-    B, H, Sq, D = q.shape
-    Hkv, Smax = k.shape[1], k.shape[2]
-    g = H // Hkv
-    kd = k.double().repeat_interleave(g, dim=1)
-    vd = v.double().repeat_interleave(g, dim=1)
-    s = (q.double() @ kd.transpose(-1, -2)) * scale
-    j = torch.arange(Smax, device=q.device)
-    i = torch.arange(Sq, device=q.device)
-    L = seqlens.to(q.device).long() if seqlens is not None else torch.full((B,), Smax, device=q.device)
-    vis = (j[None, None, :] < L[:, None, None]).expand(B, Sq, Smax)
-    if causal:
-        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])
-    if key_mask is not None:
-        vis = vis & key_mask.to(q.device).bool()[:, None, :]
-    s = s.masked_fill(~vis[:, None], float("-inf"))
-    m = s.amax(-1, keepdim=True)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    safe = torch.where(l > 0, l, torch.ones_like(l))
-    pn = p / safe
-    o = pn @ vd
-    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
-    return o, lse, pn.norm(dim=-1, keepdim=True)
-
-
-def _check(got, ref, pnorm, vmax, dtype):
-    err = (got.double() - ref).abs()
-    print(f"max-abs vs fp64 {float(err.max()):.3e} ({got.dtype})")
-    if got.dtype == torch.float32:
-        assert float(err.max()) <= 1e-3, float(err.max())
-        return
-    eps = EPS[dtype]
-    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
-    worst = float((err - bound).max())
-    assert worst <= 0, f"max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
 
 
 @pytest.mark.parametrize("dtype,D", [(torch.bfloat16, 128), (torch.float16, 64)])
 def test_paged_against_the_fp64_reference(dtype, D):
     from photonic_flash_attention_amd import ops
-    q, k, v = _problem(3, 32, 8, 4, 4096, D, dtype, seed=11)
-    kp, vp, table = _scatter(k, v, 256, seed=5)
+    q, k, v = problem(3, 32, 8, 4, 4096, D, dtype, seed=11)
+    kp, vp, table = scatter(k, v, 256, seed=5)
     sl = torch.tensor([4096, 1234, 3], dtype=torch.int32, device=q.device)
     km = torch.ones(3, 4096, dtype=torch.bool, device=q.device)
     km[0, :200] = False
     km[1, 500:600] = False
-    ref, rlse, pn = _reference(q, k, v, sl, km, True, D ** -0.5)
+    ref, rlse, pn = reference(q, k, v, seqlens=sl, key_mask=km)
     for out_dtype in (None, torch.float32):
         o, lse = ops.fa3_decode(q, kp, vp, block_table=table, cache_seqlens=sl, key_mask=km, causal=True, out_dtype=out_dtype,
                                 return_lse=True)
         torch.cuda.synchronize()
-        _check(o, ref, pn, float(v.abs().max()), dtype)
-        fin = torch.isfinite(rlse)
-        assert torch.equal(torch.isfinite(lse), fin)
-        assert float((lse.double() - rlse)[fin].abs().max()) <= 2e-3
+        check_out(o, ref, pn, float(v.abs().max()), dtype, f"paged decode D {D}")
+        check_lse(o, lse, rlse, f"paged decode D {D}")
 
 
 def test_table_entries_past_a_sequence_are_never_read():
     page = 128
-    q, k, v = _problem(4, 32, 8, 1, 2048, 128, torch.bfloat16, seed=12)
-    kp, vp, table = _scatter(k, v, page, seed=6)
+    q, k, v = problem(4, 32, 8, 1, 2048, 128, torch.bfloat16, seed=12)
+    kp, vp, table = scatter(k, v, page, seed=6)
     lens = [0, 1, 3 * page, 5 * page + 1]
     sl = torch.tensor(lens, dtype=torch.int32, device=q.device)
     _both(q, k, v, kp, vp, table, cache_seqlens=sl)
@@ -232,7 +148,7 @@ def test_table_entries_past_a_sequence_are_never_read():
         assert bool(torch.isfinite(o).all())
         assert torch.equal(o, ref) and torch.equal(lse, rl)
     # with Sq 4, causal: still nothing past ceil(len / page)
-    q4, _, _ = _problem(4, 32, 8, 4, 2048, 128, torch.bfloat16, seed=13)
+    q4, _, _ = problem(4, 32, 8, 4, 2048, 128, torch.bfloat16, seed=13)
     ref, rl = ops.fa3_decode(q4, k, v, cache_seqlens=sl, return_lse=True)
     o, lse = ops.fa3_decode(q4, kp, vp, block_table=t2, cache_seqlens=sl, return_lse=True)
     torch.cuda.synchronize()
@@ -241,8 +157,8 @@ def test_table_entries_past_a_sequence_are_never_read():
 
 def test_paged_outputs_are_bitwise_reproducible():
     from photonic_flash_attention_amd import ops
-    q, k, v = _problem(2, 32, 8, 1, 32768, 128, torch.bfloat16, seed=3)
-    kp, vp, table = _scatter(k, v, 64, seed=7)
+    q, k, v = problem(2, 32, 8, 1, 32768, 128, torch.bfloat16, seed=3)
+    kp, vp, table = scatter(k, v, 64, seed=7)
     sl = torch.tensor([32768, 20000], dtype=torch.int32, device=q.device)
     o1, l1 = ops.fa3_decode(q, kp, vp, block_table=table, cache_seqlens=sl, return_lse=True)
     o2, l2 = ops.fa3_decode(q, kp, vp, block_table=table, cache_seqlens=sl, return_lse=True)
@@ -251,26 +167,14 @@ def test_paged_outputs_are_bitwise_reproducible():
     _both(q, k, v, kp, vp, table, cache_seqlens=sl)
 
 
-def _contiguous_of(cache, Smax):
-    """The cache's sequences gathered into contiguous [max_batch, Hkv, Smax, D] K and V (zeros past each length)."""
-    B = cache.max_batch
-    k = torch.zeros(B, cache.Hkv, Smax, cache.D, dtype=cache.k_pool.dtype, device=cache.device)
-    v = torch.zeros_like(k)
-    for s in range(B):
-        gk, gv = cache.gather(s)
-        k[s, :, :gk.shape[1]] = gk
-        v[s, :, :gv.shape[1]] = gv
-    return k, v
-
-
 def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
     from photonic_flash_attention_amd import ops
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev = _dev()
+    dev = device()
     H, Hkv, D, page, max_pages = 32, 8, 128, 64, 8
     cache = PagedKVCache(num_pages=24, page_size=page, Hkv=Hkv, D=D, dtype=torch.bfloat16, device=dev, max_batch=2,
                          max_pages_per_seq=max_pages)
-    g = _gen(20)
+    g = gen(20)
 
     def tokens(n, rows=1):
         return (torch.randn(rows, Hkv, n, D, generator=g, device=dev).to(torch.bfloat16),
@@ -296,7 +200,7 @@ def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
     def replay_and_compare():
         graph.replay()
         torch.cuda.synchronize()
-        kc, vc = _contiguous_of(cache, max_pages * page)
+        kc, vc = contiguous_of(cache, max_pages * page)
         ro, rl = ops.fa3_decode(q, kc, vc, cache_seqlens=cache.cache_seqlens.clone(), return_lse=True)
         torch.cuda.synchronize()
         assert torch.equal(o, ro) and torch.equal(lse, rl)
@@ -317,12 +221,12 @@ def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
 def test_generation_loop_on_a_paged_cache_matches_a_contiguous_cache():
     from photonic_flash_attention_amd import ops
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev = _dev()
+    dev = device()
     H, Hkv, D, page, max_pages = 32, 8, 128, 64, 4
     Smax = page * max_pages
     cache = PagedKVCache(num_pages=10, page_size=page, Hkv=Hkv, D=D, dtype=torch.bfloat16, device=dev, max_batch=2,
                          max_pages_per_seq=max_pages)
-    g = _gen(30)
+    g = gen(30)
     kc = torch.zeros(2, Hkv, Smax, D, dtype=torch.bfloat16, device=dev)
     vc = torch.zeros_like(kc)
     lens = [100, 37]

@@ -20,20 +20,16 @@ import pytest
 import torch
 
 from conftest import golden_inputs, golden_names, load_golden
+from kvcache_testlib import device
 
 pytestmark = pytest.mark.gpu
 
 PARITY_TOL = 1e-3
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
 def _run(q, k, v, **kw):
     from photonic_flash_attention_amd import ops
-    dev = _dev()
+    dev = device()
     o, lse = ops.fa3_forward_bshd(q.to(dev), k.to(dev), v.to(dev), **kw)
     torch.cuda.synchronize()
     return o.float().cpu(), (None if lse is None else lse.cpu())
@@ -186,7 +182,7 @@ def test_strided_views_of_fused_qkv():
     B, S, H, D = 2, 384, 4, 64
     E = H * D
     qkv = torch.from_numpy(synth.normal_f32((B, S, 3 * E), 5)).to(torch.bfloat16)
-    dev = _dev()
+    dev = device()
     g = qkv.to(dev)
     qv, kv, vv = (t.view(B, S, H, D).transpose(1, 2) for t in g.chunk(3, dim=-1))
     o, _ = ops.fa3_forward(qv, kv, vv, out_dtype=torch.float32)
@@ -244,7 +240,7 @@ def test_scaled_inputs_stay_finite():
 
 def test_bad_arguments_raise_before_launch():
     from photonic_flash_attention_amd import ops
-    dev = _dev()
+    dev = device()
     q = torch.zeros(1, 2, 16, 160, dtype=torch.bfloat16, device=dev)
     with pytest.raises(ValueError):
         ops.fa3_forward(q, q, q)                      # head dim 160 (> 128: no kernel; <= 128 runs zero-padded)
@@ -265,7 +261,7 @@ def test_reentrant_from_threads_on_side_streams():
     re-entrant and honour the caller's stream."""
     import threading
     from photonic_flash_attention_amd import ops, synth
-    dev = _dev()
+    dev = device()
     q, k, v = (t.to(dev) for t in synth.qkv(2, 4, 512, 512, 64, 404, "bf16"))
     want, _ = ops.fa3_forward_bshd(q, k, v, causal=True)
     torch.cuda.synchronize()
@@ -294,7 +290,7 @@ def test_runs_to_run_determinism_and_variant_equivalence():
     formula and are bit-identical with 16-bit stores; the persistent assembly kernel sums its rows in another order and agrees
     to one rounding of the output.  Development variants do not exist in this library (PFA_ERR_FLAGS)."""
     from photonic_flash_attention_amd import ops, synth
-    dev = _dev()
+    dev = device()
     q, k, v = (t.to(dev) for t in synth.qkv(1, 4, 1536, 1536, 128, 505, "bf16"))
     outs = {}
     for var in (0, 43, 44, 45):
@@ -711,7 +707,7 @@ def test_head_dims_without_a_kernel_run_zero_padded(D, causal):
     B, H, Sq, Sk = 2, 3, 150, 333
     q, k, v = synth.qkv(B, H, Sq, Sk, D, 4000 + D, "bf16")
     ref = orc.attention_bshd(q.float(), k.float(), v.float(), causal=causal)
-    DEV = _dev()
+    DEV = device()
     qd, kd, vd = (t.to(DEV).permute(0, 2, 1, 3) for t in (q, k, v))
     out, lse, w = ops.fa3_forward(qd, kd, vd, causal=causal, out_dtype=torch.float32, return_lse=True, return_weights=True,
                                   weights_dtype=torch.float32)
@@ -734,7 +730,7 @@ def test_mask_words_and_mask_bytes_agree(kind, causal):
     workspace, a byte per score: both paths must give the same bits, for every broadcast shape of the reference's masks."""
     import ctypes as C
     from photonic_flash_attention_amd import _capi, ops, synth
-    dev = _dev()
+    dev = device()
     B, H, Sq, Sk, D = 2, 3, 200, 330, 64
     q, k, v = (t.to(dev).permute(0, 2, 1, 3) for t in synth.qkv(B, H, Sq, Sk, D, 9100, "bf16"))
     g = torch.Generator().manual_seed(3)
@@ -793,7 +789,7 @@ def test_every_head_of_the_headline_shapes_on_sampled_rows(shape):
     from photonic_flash_attention_amd import _capi, ops, synth
     name, B, H, S, causal = shape
     rows = _edge_rows(S, S)
-    dev = _dev()
+    dev = device()
     gen = torch.Generator(device=dev).manual_seed(9000 + S)                    # (device RNG: the counter-based generator needs minutes at this size)
     qd, kd, vd = (torch.randn(B, S, H, 128, device=dev, generator=gen).to(torch.bfloat16) for _ in range(3))
     q, k, v = (t.cpu() for t in (qd, kd, vd))
@@ -821,7 +817,7 @@ def test_c4_at_its_full_batch_on_one_gpu():
     ONE GPU (2048 items on the persistent kernel, 8 per CU): determinism, the B = 4 shards bit for bit, sampled rows of every head."""
     from photonic_flash_attention_amd import ops, synth
     B, H, S, D = 32, 16, 4096, 128
-    dev = _dev()
+    dev = device()
     gen = torch.Generator(device=dev).manual_seed(500)
     qd, kd, vd = (torch.randn(B, S, H, D, device=dev, generator=gen).to(torch.bfloat16) for _ in range(3))
     q, k, v = (t.cpu() for t in (qd, kd, vd))
@@ -846,7 +842,7 @@ def test_hip_graph_capture_and_replay_of_the_persistent_kernel():
     """pfa_fa3_prepare / _capi.load() load the code object eagerly, so the FIRST forward of a p4-eligible shape may sit inside a stream
     capture; the replayed graph reproduces the eager result bit for bit, also on a side stream and with new data in the same buffers."""
     from photonic_flash_attention_amd import _capi, ops, synth
-    dev = _dev()
+    dev = device()
     assert _capi.load().pfa_fa3_prepare(0) == 0
     q, k, v = (t.to(dev) for t in synth.qkv(2, 8, 1024, 1024, 128, 321, "bf16"))
     out = torch.empty_like(q)
@@ -876,7 +872,7 @@ def test_reserved_cus_shrink_the_persistent_grid_and_keep_the_result():
     """pfa_fa3_args.reserve_cus (ABI v6): a caller that overlaps a kernel-based collective leaves it CUs; same bits on the smaller grid."""
     import ctypes as C
     from photonic_flash_attention_amd import _capi, ops, synth
-    dev = _dev()
+    dev = device()
     q, k, v = (t.to(dev) for t in synth.qkv(2, 8, 2048, 2048, 128, 99, "bf16"))
     qv, kv, vv = (t.permute(0, 2, 1, 3) for t in (q, k, v))
     full, _ = ops.fa3_forward(qv, kv, vv, causal=True)
@@ -955,7 +951,7 @@ def test_fast_loop_fixup_on_spiked_keys(case):
     k = k.clone()
     for key, row, f in ((70, 100, 0.9), (300, 400, 1.5), (352, 500, 25.0), (453, 600, 3.0), (520, 700, 0.8), (1023, 1023, 30.0), (960, 990, 2.0)):
         k[:, key] = (q[:, row].float() * f).to(torch.bfloat16)      # row `row` (and its friends) jump at key `key`
-    dev = _dev()
+    dev = device()
     qd, kd, vd = (t.to(dev) for t in (q, k, v))
     out, lse = ops.fa3_forward_bshd(qd, kd, vd, causal=causal, return_lse=True)
     torch.cuda.synchronize()
@@ -1025,7 +1021,7 @@ def test_persistent_kernel_extreme_shapes(case):
     heads, a ragged 65535, a key sequence of 100001 -- against the 8-wave HIP kernel (same formulas, other summation order)."""
     from photonic_flash_attention_amd import _capi, ops
     tag, B, H, Sq, Sk, D, causal = case
-    dev = _dev()
+    dev = device()
     g = torch.Generator(device=dev).manual_seed(len(tag))
     q = torch.randn(B, Sq, H, D, device=dev, generator=g).to(torch.bfloat16).permute(0, 2, 1, 3)
     k, v = (torch.randn(B, Sk, H, D, device=dev, generator=g).to(torch.bfloat16).permute(0, 2, 1, 3) for _ in range(2))
@@ -1043,7 +1039,7 @@ def test_persistent_kernel_graph_of_three_flavours_side_stream_and_threads():
     the persistent kernels, captured on a side stream and replayed three times bit for bit; then four host threads on four streams."""
     import threading
     from photonic_flash_attention_amd import ops
-    dev = _dev()
+    dev = device()
 
     def mk(B, H, S, seed):
         g = torch.Generator(device=dev).manual_seed(seed)

@@ -4,8 +4,7 @@ of query rows against a contiguous or paged cache, bottom-right causal per batch
 Every cache handed to the kernel holds NaN at and past each batch's length, and every pool page no table entry names is NaN, so a
 read past ``len_b`` (the descriptor bound) or of a page that is not the sequence's shows as a non-finite output: every test asserts
 that the outputs are finite.  The reference is fp64 attention with the bottom-right rule, computed on the device from the clean
-tensors (the one of tests/test_hip_decode.py, restated here with its bound: |err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6
-for a 16-bit output, 1e-3 max-abs for fp32, 2e-3 on the LSE).  Paged against contiguous needs no tolerance: ``torch.equal``.
+tensors, and the bounds are its own (tests/kvcache_testlib.py).  Paged against contiguous needs no tolerance: ``torch.equal``.
 
 Only in-range page ids and legal arguments ever reach the device; refusals are tested on the host (tests/test_prefill_host.py)."""
 
@@ -14,126 +13,22 @@ from __future__ import annotations
 import pytest
 import torch
 
+from kvcache_testlib import NAN, check_lse, check_out, contiguous_of, device, gen, i32, poison, problem, reference, scatter
+
 pytestmark = pytest.mark.gpu
-
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
-NAN = float("nan")
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _gen(seed):
-    return torch.Generator(device=_dev()).manual_seed(seed)
-
-
-def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed):
-    g = _gen(seed)
-    dev = _dev()
-    q = torch.randn(B, Sq, H, D, generator=g, device=dev).to(dtype).permute(0, 2, 1, 3)
-    k = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
-    v = torch.randn(B, Hkv, Smax, D, generator=g, device=dev).to(dtype)
-    return q, k, v
-
-
-def _lens(lens, dev=None):
-    return torch.tensor(lens, dtype=torch.int32, device=dev or _dev())
-
-
-def _poison(k, v, lens):
-    """Copies of the caches with NaN at and past each batch's length (what an unfilled tail may hold)."""
-    kn, vn = k.clone(), v.clone()
-    for b, n in enumerate(lens):
-        kn[b, :, n:] = NAN
-        vn[b, :, n:] = NAN
-    return kn, vn
-
-
-def _scatter(k, v, page, seed, layout="phsd", spare=5):
-    """Scatter contiguous [B, Hkv, Smax, D] caches over pools in a random page order.  -> (k_pool, v_pool, table) with the pools as
-    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN (and so does whatever NaN the caches carry)."""
-    B, Hkv, Smax, D = k.shape
-    assert Smax % page == 0
-    pages = Smax // page
-    NP = B * pages + spare
-    dev = k.device
-    perm = torch.randperm(NP, generator=torch.Generator().manual_seed(seed))[:B * pages]
-    table = perm.to(torch.int32).reshape(B, pages).to(dev)
-    pools = []
-    for src in (k, v):
-        if layout == "phsd":        # flash-attn style [num_pages, page, Hkv, D], passed transposed
-            pool = torch.full((NP, page, Hkv, D), NAN, dtype=k.dtype, device=dev).transpose(1, 2)
-        elif layout == "hpsd":
-            pool = torch.full((NP, Hkv, page, D), NAN, dtype=k.dtype, device=dev)
-        else:                       # every second page of a larger pool, whose pages also have room for 64 more keys
-            pool = torch.full((2 * NP, Hkv, page + 64, D), NAN, dtype=k.dtype, device=dev)[::2, :, :page]
-        pool[perm.to(dev)] = src.reshape(B, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(B * pages, Hkv, page, D)
-        pools.append(pool)
-    return pools[0], pools[1], table
-
-
-def _reference(q, k, v, seqlens, causal, scale):
-    """fp64 on the GPU from CLEAN caches: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2)."""
-    B, H, Sq, D = q.shape
-    Hkv, Smax = k.shape[1], k.shape[2]
-    g = H // Hkv
-    kd = k.double().repeat_interleave(g, dim=1)
-    vd = v.double().repeat_interleave(g, dim=1)
-    s = (q.double() @ kd.transpose(-1, -2)) * scale
-    j = torch.arange(Smax, device=q.device)
-    i = torch.arange(Sq, device=q.device)
-    L = seqlens.to(q.device).long() if seqlens is not None else torch.full((B,), Smax, device=q.device)
-    vis = (j[None, None, :] < L[:, None, None]).expand(B, Sq, Smax)
-    if causal:
-        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])   # bottom-right, per batch
-    s = s.masked_fill(~vis[:, None], float("-inf"))
-    m = s.amax(-1, keepdim=True)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    safe = torch.where(l > 0, l, torch.ones_like(l))
-    pn = p / safe
-    o = pn @ vd
-    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
-    return o, lse, pn.norm(dim=-1, keepdim=True)
-
-
-def _check(got, ref, pnorm, vmax, dtype):
-    assert bool(torch.isfinite(got).all()), "non-finite output: a key at or past len_b, or a page of another sequence, was read"
-    err = (got.double() - ref).abs()
-    print(f"max-abs vs reference {float(err.max()):.3e} ({got.dtype})")
-    if got.dtype == torch.float32:
-        assert float(err.max()) <= 1e-3, float(err.max())
-        return
-    eps = EPS[dtype]
-    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
-    worst = float((err - bound).max())
-    assert worst <= 0, f"max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
-
-
-def _check_lse(o, lse, rlse):
-    fin = torch.isfinite(rlse)
-    assert torch.equal(torch.isfinite(lse), fin)
-    assert not bool(torch.isnan(lse).any())
-    assert bool((lse[~fin] == float("-inf")).all())
-    assert bool((o[~fin[..., None].expand_as(o)] == 0).all())           # a row with no visible key: exactly zero
-    if bool(fin.any()):
-        assert float((lse.double() - rlse)[fin].abs().max()) <= 2e-3
 
 
 def _run_and_check(q, k, v, lens, *, causal=True, out_dtype=None, ref=None, **kw):
     """The kernel on the NaN-tailed caches against fp64 on the clean ones.  lens: list or None (then nothing is poisoned)."""
     from photonic_flash_attention_amd import ops
-    sl = _lens(lens, q.device) if lens is not None else None
-    kn, vn = _poison(k, v, lens) if lens is not None else (k, v)
+    sl = i32(lens, q.device) if lens is not None else None
+    kn, vn = poison(k, v, lens) if lens is not None else (k, v)
     o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=sl, causal=causal, out_dtype=out_dtype, return_lse=True, **kw)
     torch.cuda.synchronize()
     if ref is None:
-        ref = _reference(q, k, v, sl, causal, q.shape[-1] ** -0.5)
-    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-    _check_lse(o, lse, ref[1])
+        ref = reference(q, k, v, seqlens=sl, causal=causal)
+    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    check_lse(o, lse, ref[1])
     return o, lse
 
 
@@ -144,9 +39,9 @@ def _run_and_check(q, k, v, lens, *, causal=True, out_dtype=None, ref=None, **kw
 def test_against_fp64(Sq, D):
     lens = [Sq + 1000, Sq + 17]
     for dtype in (torch.bfloat16, torch.float16):
-        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=Sq + D)
+        q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=Sq + D)
         for causal in (True, False):
-            ref = _reference(q, k, v, _lens(lens), causal, D ** -0.5)
+            ref = reference(q, k, v, seqlens=i32(lens), causal=causal)
             for out_dtype in (None, torch.float32):
                 _run_and_check(q, k, v, lens, causal=causal, out_dtype=out_dtype, ref=ref)
 
@@ -156,7 +51,7 @@ def test_against_fp64(Sq, D):
 def test_head_groups_against_fp64(H, Hkv, Sq):
     lens = [Sq + 1000, Sq + 17]
     for dtype, D in ((torch.bfloat16, 128), (torch.float16, 64)):
-        q, k, v = _problem(2, H, Hkv, Sq, 2048, D, dtype, seed=H + Sq)
+        q, k, v = problem(2, H, Hkv, Sq, 2048, D, dtype, seed=H + Sq)
         _run_and_check(q, k, v, lens)
         _run_and_check(q, k, v, lens, causal=False, out_dtype=torch.float32)
 
@@ -167,20 +62,20 @@ def test_head_groups_against_fp64(H, Hkv, Sq):
 def test_no_prefix_is_the_top_left_causal_forward(D):
     from photonic_flash_attention_amd import ops
     Sq = 300
-    q, k, v = _problem(2, 8, 2, Sq, 2048, D, torch.bfloat16, seed=40 + D)
+    q, k, v = problem(2, 8, 2, Sq, 2048, D, torch.bfloat16, seed=40 + D)
     o, lse = _run_and_check(q, k, v, [Sq, Sq])
-    ref = _reference(q, k, v, _lens([Sq, Sq]), True, D ** -0.5)
+    ref = reference(q, k, v, seqlens=i32([Sq, Sq]))
     of, lf = ops.fa3_forward(q, k[:, :, :Sq], v[:, :, :Sq], causal=True, return_lse=True)
     torch.cuda.synchronize()
-    _check(of, ref[0], ref[2], float(v.abs().max()), q.dtype)            # the forward meets the bound itself ...
-    _check(o, of.double(), ref[2], float(v.abs().max()), q.dtype)        # ... and the two agree within it
+    check_out(of, ref[0], ref[2], float(v.abs().max()), q.dtype)            # the forward meets the bound itself ...
+    check_out(o, of.double(), ref[2], float(v.abs().max()), q.dtype)        # ... and the two agree within it
     assert float((lse - lf).abs().max()) <= 2e-3
 
 
 def test_length_below_the_row_count_leaves_the_leading_rows_zero():
     Sq = 300
     for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
-        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=50 + D)
+        q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=50 + D)
         for lens in ([Sq + 500, 100], [37, Sq + 1]):
             for out_dtype in (None, torch.float32):
                 o, lse = _run_and_check(q, k, v, lens, out_dtype=out_dtype)
@@ -191,7 +86,7 @@ def test_length_below_the_row_count_leaves_the_leading_rows_zero():
 
 
 def test_zero_length():
-    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=60)
+    q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=60)
     for causal in (True, False):
         for out_dtype in (None, torch.float32):
             o, lse = _run_and_check(q, k, v, [0, 300 + 64], causal=causal, out_dtype=out_dtype)
@@ -203,7 +98,7 @@ def test_zero_length():
 @pytest.mark.parametrize("D", [64, 128])
 def test_full_cache_and_no_lengths(D):
     Smax = 1024
-    q, k, v = _problem(2, 8, 2, 257, Smax, D, torch.bfloat16, seed=70 + D)
+    q, k, v = problem(2, 8, 2, 257, Smax, D, torch.bfloat16, seed=70 + D)
     for causal in (True, False):
         o1, l1 = _run_and_check(q, k, v, [Smax, Smax], causal=causal)            # len_b = Smax
         o2, l2 = _run_and_check(q, k, v, None, causal=causal)                     # cache_seqlens = None
@@ -214,11 +109,11 @@ def test_full_cache_and_no_lengths(D):
 def test_lengths_next_to_tile_and_page_boundaries(page):
     from photonic_flash_attention_amd import ops
     Sq = 40
-    q, k, v = _problem(2, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=80 + page)
+    q, k, v = problem(2, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=80 + page)
     for lens in ([63, 65], [64, 127], [page - 1, page + 1], [4 * page - 1, 4 * page + 1], [4 * page, 2047]):
-        sl = _lens(lens)
-        kn, vn = _poison(k, v, lens)
-        kp, vp, table = _scatter(kn, vn, page, seed=page)
+        sl = i32(lens)
+        kn, vn = poison(k, v, lens)
+        kp, vp, table = scatter(kn, vn, page, seed=page)
         for causal in (True, False):
             o, lse = _run_and_check(q, k, v, lens, causal=causal)
             op, lp = ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=sl, causal=causal, return_lse=True)
@@ -246,57 +141,57 @@ def test_paged_equals_contiguous(page, D):
     Smax = max(2048, 3 * page)
     for dtype in (torch.bfloat16, torch.float16):
         for Sq in (65, 300):
-            q, k, v = _problem(2, 8, 2, Sq, Smax, D, dtype, seed=page + D + Sq)
+            q, k, v = problem(2, 8, 2, Sq, Smax, D, dtype, seed=page + D + Sq)
             lens = [Sq + 1000, Sq + 17]
-            kn, vn = _poison(k, v, lens)
-            kp, vp, table = _scatter(kn, vn, page, seed=page + Sq)
+            kn, vn = poison(k, v, lens)
+            kp, vp, table = scatter(kn, vn, page, seed=page + Sq)
             for causal in (True, False):
                 for out_dtype in (None, torch.float32):
-                    _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens), causal=causal, out_dtype=out_dtype)
-        kp, vp, table = _scatter(k, v, page, seed=page)
+                    _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens), causal=causal, out_dtype=out_dtype)
+        kp, vp, table = scatter(k, v, page, seed=page)
         _both(q, k, v, kp, vp, table)                                  # no lengths: every page is read
     # the paged call against fp64 as well, so that the suite does not rest on the contiguous path alone
-    o, lse = _both(q, kn, vn, *_scatter(kn, vn, page, seed=1), cache_seqlens=_lens(lens))
-    ref = _reference(q, k, v, _lens(lens), True, D ** -0.5)
-    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-    _check_lse(o, lse, ref[1])
+    o, lse = _both(q, kn, vn, *scatter(kn, vn, page, seed=1), cache_seqlens=i32(lens))
+    ref = reference(q, k, v, seqlens=i32(lens))
+    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    check_lse(o, lse, ref[1])
 
 
 @pytest.mark.parametrize("layout", ["phsd", "hpsd", "slice"])
 def test_pool_layouts(layout):
-    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=9)
+    q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=9)
     lens = [2048, 1111]
-    kn, vn = _poison(k, v, lens)
-    kp, vp, table = _scatter(kn, vn, 256, seed=3, layout=layout)
+    kn, vn = poison(k, v, lens)
+    kp, vp, table = scatter(kn, vn, 256, seed=3, layout=layout)
     assert kp.is_contiguous() == (layout == "hpsd")
-    _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens))
+    _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens))
 
 
 def test_two_sequences_sharing_prefix_pages():
     page, Sq = 128, 200
-    q, k, v = _problem(3, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=10)
+    q, k, v = problem(3, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=10)
     k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
     v[1, :, :5 * page] = v[0, :, :5 * page]
     lens = [2048, 5 * page + Sq + 7, 900]            # batch 1: its 207-row suffix attends to the shared pages
-    kn, vn = _poison(k, v, lens)
-    kp, vp, table = _scatter(kn, vn, page, seed=4)
+    kn, vn = poison(k, v, lens)
+    kp, vp, table = scatter(kn, vn, page, seed=4)
     freed = table[1, :5].clone()
     table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
     for pool in (kp, vp):
         pool[freed.long()] = NAN                     # the duplicate copies are gone
-    o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens))
-    ref = _reference(q, k, v, _lens(lens), True, 128 ** -0.5)
-    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-    _check_lse(o, lse, ref[1])
+    o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens))
+    ref = reference(q, k, v, seqlens=i32(lens))
+    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    check_lse(o, lse, ref[1])
 
 
 # --- views, determinism --------------------------------------------------------------------------------------------------------------
 
 def test_strided_views_of_q_cache_and_out():
     from photonic_flash_attention_amd import ops
-    dev = _dev()
+    dev = device()
     B, H, Hkv, Sq, Smax, D = 2, 8, 2, 200, 1024, 128
-    g = _gen(11)
+    g = gen(11)
     qkv = torch.randn(B, Sq, 3, H, D, generator=g, device=dev).to(torch.bfloat16)       # a fused projection
     q = qkv[:, :, 0].permute(0, 2, 1, 3)
     big_k = torch.randn(B, Hkv, Smax + 96, D, generator=g, device=dev).to(torch.bfloat16)
@@ -307,13 +202,13 @@ def test_strided_views_of_q_cache_and_out():
         big_v[b, :, n:] = NAN
     k, v = big_k[:, :, :Smax], big_v[:, :, :Smax]    # the first Smax positions of a larger preallocated cache
     assert not q.is_contiguous() and not k.is_contiguous()
-    sl = _lens(lens)
-    ref = _reference(q, torch.nan_to_num(k), torch.nan_to_num(v), sl, True, D ** -0.5)
+    sl = i32(lens)
+    ref = reference(q, torch.nan_to_num(k), torch.nan_to_num(v), seqlens=sl)
     vmax = float(torch.nan_to_num(v).abs().max())
     o, lse = ops.fa3_prefill_cache(q, k, v, cache_seqlens=sl, return_lse=True)
     torch.cuda.synchronize()
-    _check(o, ref[0], ref[2], vmax, q.dtype)
-    _check_lse(o, lse, ref[1])
+    check_out(o, ref[0], ref[2], vmax, q.dtype)
+    check_lse(o, lse, ref[1])
     # out= given, with strides of its own: a slice of a wider [B, Sq, H, 2 D] buffer, untouched outside the slice
     wide = torch.full((B, Sq, H, 2 * D), 7.0, dtype=torch.bfloat16, device=dev)
     out = wide[..., D:].permute(0, 2, 1, 3)
@@ -329,12 +224,12 @@ def test_strided_views_of_q_cache_and_out():
 
 def test_outputs_are_bitwise_reproducible():
     from photonic_flash_attention_amd import ops
-    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
+    q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
     lens = [2048, 1500]
-    kn, vn = _poison(k, v, lens)
-    kp, vp, table = _scatter(kn, vn, 64, seed=7)
+    kn, vn = poison(k, v, lens)
+    kp, vp, table = scatter(kn, vn, 64, seed=7)
     for out_dtype in (None, torch.float32):
-        runs = [ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=_lens(lens), out_dtype=out_dtype, return_lse=True)
+        runs = [ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=i32(lens), out_dtype=out_dtype, return_lse=True)
                 for _ in range(2)]
         torch.cuda.synchronize()
         assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
@@ -343,27 +238,15 @@ def test_outputs_are_bitwise_reproducible():
 
 # --- graph capture over a PagedKVCache -----------------------------------------------------------------------------------------------
 
-def _contiguous_of(cache, Smax):
-    """The cache's sequences gathered into contiguous [max_batch, Hkv, Smax, D] K and V (zeros past each length)."""
-    B = cache.max_batch
-    k = torch.zeros(B, cache.Hkv, Smax, cache.D, dtype=cache.k_pool.dtype, device=cache.device)
-    v = torch.zeros_like(k)
-    for s in range(B):
-        gk, gv = cache.gather(s)
-        k[s, :, :gk.shape[1]] = gk
-        v[s, :, :gv.shape[1]] = gv
-    return k, v
-
-
 def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev = _dev()
+    dev = device()
     H, Hkv, D, page, max_pages, Sq = 8, 2, 128, 64, 12, 100
     cache = PagedKVCache(num_pages=30, page_size=page, Hkv=Hkv, D=D, dtype=torch.bfloat16, device=dev, max_batch=2,
                          max_pages_per_seq=max_pages)
     cache.k_pool.fill_(NAN)                  # whatever is not appended stays NaN: unfilled page tails, unused pages
     cache.v_pool.fill_(NAN)
-    g = _gen(20)
+    g = gen(20)
 
     def tokens(n, rows=1):
         return (torch.randn(rows, Hkv, n, D, generator=g, device=dev).to(torch.bfloat16),
@@ -389,10 +272,10 @@ def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
     def replay_and_compare():
         graph.replay()
         torch.cuda.synchronize()
-        kc, vc = _contiguous_of(cache, max_pages * page)
-        ref = _reference(q, kc, vc, cache.cache_seqlens, True, D ** -0.5)
-        _check(o, ref[0], ref[2], float(vc.abs().max()), q.dtype)
-        _check_lse(o, lse, ref[1])
+        kc, vc = contiguous_of(cache, max_pages * page)
+        ref = reference(q, kc, vc, seqlens=cache.cache_seqlens)
+        check_out(o, ref[0], ref[2], float(vc.abs().max()), q.dtype)
+        check_lse(o, lse, ref[1])
 
     replay_and_compare()
     assert bool((o[a, :, :Sq - 60] == 0).all())
@@ -415,14 +298,14 @@ def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
 def test_prefill_and_decode_both_meet_the_fp64_bound(Sq):
     from photonic_flash_attention_amd import ops
     for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
-        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=90 + Sq + D)
+        q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=90 + Sq + D)
         lens = [Sq + 1000, Sq + 17]
-        sl = _lens(lens)
-        kn, vn = _poison(k, v, lens)
-        ref = _reference(q, k, v, sl, True, D ** -0.5)
+        sl = i32(lens)
+        kn, vn = poison(k, v, lens)
+        ref = reference(q, k, v, seqlens=sl)
         for out_dtype in (None, torch.float32):
             for fn in (ops.fa3_prefill_cache, ops.fa3_decode):
                 o, lse = fn(q, kn, vn, cache_seqlens=sl, causal=True, out_dtype=out_dtype, return_lse=True)
                 torch.cuda.synchronize()
-                _check(o, ref[0], ref[2], float(v.abs().max()), dtype)
-                _check_lse(o, lse, ref[1])
+                check_out(o, ref[0], ref[2], float(v.abs().max()), dtype)
+                check_lse(o, lse, ref[1])

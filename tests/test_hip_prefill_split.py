@@ -1,12 +1,11 @@
 """GPU tests of the forward over a KV cache with the keys split over workgroups (``ops.fa3_prefill_cache(key_splits=)`` /
 ``pfa_fa3_prefill_split``) and of ``prefix_key_splits=`` on the shared-prefix step.
 
-The fp64 reference, the NaN poisoning (every cache holds NaN at and past each length, every pool page no table entry names is NaN) and
-the bounds are those of tests/test_hip_prefill_cache.py, imported unchanged: |err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6 for
-a 16-bit output, 1e-3 max-abs for fp32, 2e-3 on the LSE, every output finite.  The split path carries P as hi + lo and rounds the
-output once, in the merge, so it sits inside what those bounds already allow.  Paged against contiguous, one split against none, the
-split rule against ``attn_merge`` of plain calls on the key slices, and graph replays against eager calls need no tolerance:
-``torch.equal``.  The shared-prefix helpers are those of tests/test_hip_attn_merge.py.
+The fp64 reference, its bounds, the NaN poisoning (every cache holds NaN at and past each length, every pool page no table entry names
+is NaN) and the shared-prefix step are those of tests/kvcache_testlib.py, as tests/test_hip_prefill_cache.py and
+tests/test_hip_attn_merge.py use them.  The split path carries P as hi + lo and rounds the output once, in the merge, so it sits inside
+what those bounds already allow.  Paged against contiguous, one split against none, the split rule against ``attn_merge`` of plain
+calls on the key slices, and graph replays against eager calls need no tolerance: ``torch.equal``.
 
 Only in-range page ids and legal arguments ever reach the device; refusals are tested on the host (tests/test_prefill_split_host.py)."""
 
@@ -17,8 +16,8 @@ import functools
 import pytest
 import torch
 
-from test_hip_prefill_cache import NAN, _check, _check_lse, _dev, _gen, _lens, _poison, _problem, _reference, _scatter
-import test_hip_attn_merge as sp
+from kvcache_testlib import (NAN, both_prefix_caches, capture, check_lse, check_out, device, gen, i32, poison, prefix_problem, problem,
+                             reference, scatter)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +25,22 @@ pytestmark = pytest.mark.gpu
 @functools.lru_cache(maxsize=None)
 def _case(B, H, Hkv, Sq, Smax, D, dtype, seed, lens, causal):
     """One problem and its fp64 reference, built once and shared by every split count: (q, k, v, reference)."""
-    q, k, v = _problem(B, H, Hkv, Sq, Smax, D, dtype, seed)
-    sl = _lens(list(lens)) if lens is not None else None
-    return q, k, v, _reference(q, k, v, sl, causal, D ** -0.5)
+    q, k, v = problem(B, H, Hkv, Sq, Smax, D, dtype, seed)
+    sl = i32(list(lens)) if lens is not None else None
+    return q, k, v, reference(q, k, v, seqlens=sl, causal=causal)
 
 
 def _run_and_check(case, lens, key_splits, *, causal=True, out_dtype=None, **kw):
     """The split call on the NaN-tailed caches against fp64 on the clean ones.  lens: tuple or None (then nothing is poisoned)."""
     from photonic_flash_attention_amd import ops
     q, k, v, ref = case
-    sl = _lens(list(lens), q.device) if lens is not None else None
-    kn, vn = _poison(k, v, lens) if lens is not None else (k, v)
+    sl = i32(list(lens), q.device) if lens is not None else None
+    kn, vn = poison(k, v, lens) if lens is not None else (k, v)
     o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=sl, causal=causal, out_dtype=out_dtype, return_lse=True, key_splits=key_splits, **kw)
     torch.cuda.synchronize()
     assert o.dtype == (out_dtype or q.dtype)
-    _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-    _check_lse(o, lse, ref[1])
+    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+    check_lse(o, lse, ref[1])
     return o, lse
 
 
@@ -99,12 +98,12 @@ def test_lengths_next_to_tile_and_split_boundaries(page):
     from photonic_flash_attention_amd import ops
     Sq = 40
     for lens in ((63, 65), (64, 127), (128, 129), (511, 513), (512, 1025), (1023, 1024)):
-        sl = _lens(list(lens))
+        sl = i32(list(lens))
         for causal in (True, False):
             case = _case(2, 8, 2, Sq, 2048, 128, torch.bfloat16, 80 + page, lens, causal)
             o, lse = _run_and_check(case, lens, 4, causal=causal)
-            kn, vn = _poison(case[1], case[2], lens)
-            kp, vp, table = _scatter(kn, vn, page, seed=page)
+            kn, vn = poison(case[1], case[2], lens)
+            kp, vp, table = scatter(kn, vn, page, seed=page)
             op, lp = ops.fa3_prefill_cache(case[0], kp, vp, block_table=table, cache_seqlens=sl, causal=causal, return_lse=True, key_splits=4)
             torch.cuda.synchronize()
             assert torch.equal(op, o) and torch.equal(lp, lse), lens
@@ -129,11 +128,11 @@ def test_the_split_rule_is_attn_merge_of_plain_calls_on_the_key_slices(N, lens):
     from photonic_flash_attention_amd import ops
     Sq = 300
     for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
-        q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=N + D)
-        kn, vn = _poison(k, v, lens)
+        q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=N + D)
+        kn, vn = poison(k, v, lens)
         empty = 0
         for out_dtype in (dtype, torch.float32):
-            o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=_lens(list(lens)), causal=False, out_dtype=out_dtype, return_lse=True,
+            o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(list(lens)), causal=False, out_dtype=out_dtype, return_lse=True,
                                            key_splits=N)
             for b, n_keys in enumerate(lens):
                 n = -(-n_keys // 64)
@@ -145,7 +144,7 @@ def test_the_split_rule_is_attn_merge_of_plain_calls_on_the_key_slices(N, lens):
                         start, end, length, empty = 0, 64, 0, empty + 1
                     else:
                         length = min(max(n_keys - start, 0), end - start)
-                    po, pl = ops.fa3_prefill_cache(q[b:b + 1], kn[b:b + 1, :, start:end], vn[b:b + 1, :, start:end], cache_seqlens=_lens([length]),
+                    po, pl = ops.fa3_prefill_cache(q[b:b + 1], kn[b:b + 1, :, start:end], vn[b:b + 1, :, start:end], cache_seqlens=i32([length]),
                                                    causal=False, out_dtype=torch.float32, return_lse=True)
                     outs.append(po)
                     lses.append(pl)
@@ -177,49 +176,49 @@ def test_paged_equals_contiguous(page, D):
     """Pages in random order; with pages of 128 and 256 keys (2 and 4 tiles) the splits of 3, 5 and 8 begin in the middle of a page."""
     for dtype in (torch.bfloat16, torch.float16):
         for Sq in (65, 300):
-            q, k, v = _problem(2, 8, 2, Sq, 2048, D, dtype, seed=page + D + Sq)
+            q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=page + D + Sq)
             lens = [Sq + 1000, Sq + 17]
-            kn, vn = _poison(k, v, lens)
-            kp, vp, table = _scatter(kn, vn, page, seed=page + Sq)
+            kn, vn = poison(k, v, lens)
+            kp, vp, table = scatter(kn, vn, page, seed=page + Sq)
             for causal, N in ((True, 3), (True, 8), (False, 5)):
                 for out_dtype in (None, torch.float32):
-                    _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens), causal=causal, out_dtype=out_dtype, key_splits=N)
-        kp, vp, table = _scatter(k, v, page, seed=page)
+                    _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens), causal=causal, out_dtype=out_dtype, key_splits=N)
+        kp, vp, table = scatter(k, v, page, seed=page)
         _both(q, k, v, kp, vp, table, key_splits=3)                    # no lengths: every page is read
 
 
 def test_two_sequences_sharing_prefix_pages():
     page, Sq = 128, 200
-    q, k, v = _problem(3, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=10)
+    q, k, v = problem(3, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=10)
     k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
     v[1, :, :5 * page] = v[0, :, :5 * page]
     lens = [2048, 5 * page + Sq + 7, 900]
-    kn, vn = _poison(k, v, lens)
-    kp, vp, table = _scatter(kn, vn, page, seed=4)
+    kn, vn = poison(k, v, lens)
+    kp, vp, table = scatter(kn, vn, page, seed=4)
     freed = table[1, :5].clone()
     table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
     for pool in (kp, vp):
         pool[freed.long()] = NAN                     # the duplicate copies are gone
-    ref = _reference(q, k, v, _lens(lens), True, 128 ** -0.5)
+    ref = reference(q, k, v, seqlens=i32(lens))
     for N in (3, 8):
-        o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=_lens(lens), key_splits=N)
-        _check(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-        _check_lse(o, lse, ref[1])
+        o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens), key_splits=N)
+        check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
+        check_lse(o, lse, ref[1])
 
 
 # --- identity, determinism, views ----------------------------------------------------------------------------------------------------
 
 def test_one_split_is_the_plain_call():
     from photonic_flash_attention_amd import ops
-    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=13)
+    q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=13)
     lens = [2048, 700]
-    kn, vn = _poison(k, v, lens)
-    kp, vp, table = _scatter(kn, vn, 128, seed=5)
+    kn, vn = poison(k, v, lens)
+    kp, vp, table = scatter(kn, vn, 128, seed=5)
     for caches in (dict(), dict(block_table=table)):
         kk, vv = (kp, vp) if caches else (kn, vn)
         for out_dtype in (None, torch.float32):
             for causal in (True, False):
-                kw = dict(cache_seqlens=_lens(lens), causal=causal, out_dtype=out_dtype, return_lse=True, **caches)
+                kw = dict(cache_seqlens=i32(lens), causal=causal, out_dtype=out_dtype, return_lse=True, **caches)
                 plain = ops.fa3_prefill_cache(q, kk, vv, **kw)
                 none = ops.fa3_prefill_cache(q, kk, vv, key_splits=None, **kw)
                 one = ops.fa3_prefill_cache(q, kk, vv, key_splits=1, **kw)
@@ -228,7 +227,7 @@ def test_one_split_is_the_plain_call():
                 assert torch.equal(plain[0], one[0]) and torch.equal(plain[1], one[1])
                 assert torch.equal(plain[0], none[0]) and torch.equal(plain[1], none[1])
     # a shape the plan leaves alone (B * H * ceil(Sq / 256) >= 512) takes the same road
-    q, k, v = _problem(64, 8, 2, 40, 128, 64, torch.float16, seed=14)
+    q, k, v = problem(64, 8, 2, 40, 128, 64, torch.float16, seed=14)
     auto = ops.fa3_prefill_cache(q, k, v, return_lse=True, key_splits="auto")
     plain = ops.fa3_prefill_cache(q, k, v, return_lse=True)
     torch.cuda.synchronize()
@@ -237,13 +236,13 @@ def test_one_split_is_the_plain_call():
 
 def test_outputs_are_bitwise_reproducible():
     from photonic_flash_attention_amd import ops
-    q, k, v = _problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
+    q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
     lens = [2048, 1500]
-    kn, vn = _poison(k, v, lens)
-    kp, vp, table = _scatter(kn, vn, 64, seed=7)
+    kn, vn = poison(k, v, lens)
+    kp, vp, table = scatter(kn, vn, 64, seed=7)
     for out_dtype in (None, torch.float32):
         for N in (5, "auto"):
-            runs = [ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=_lens(lens), out_dtype=out_dtype, return_lse=True,
+            runs = [ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=i32(lens), out_dtype=out_dtype, return_lse=True,
                                           key_splits=N) for _ in range(2)]
             torch.cuda.synchronize()
             assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
@@ -252,9 +251,9 @@ def test_outputs_are_bitwise_reproducible():
 
 def test_strided_views_of_q_cache_and_out():
     from photonic_flash_attention_amd import ops
-    dev = _dev()
+    dev = device()
     B, H, Hkv, Sq, Smax, D = 2, 8, 2, 200, 1024, 128
-    g = _gen(11)
+    g = gen(11)
     qkv = torch.randn(B, Sq, 3, H, D, generator=g, device=dev).to(torch.bfloat16)       # a fused projection
     q = qkv[:, :, 0].permute(0, 2, 1, 3)
     big_k = torch.randn(B, Hkv, Smax + 96, D, generator=g, device=dev).to(torch.bfloat16)
@@ -265,13 +264,13 @@ def test_strided_views_of_q_cache_and_out():
         big_v[b, :, n:] = NAN
     k, v = big_k[:, :, :Smax], big_v[:, :, :Smax]    # the first Smax positions of a larger preallocated cache
     assert not q.is_contiguous() and not k.is_contiguous()
-    sl = _lens(lens)
-    ref = _reference(q, torch.nan_to_num(k), torch.nan_to_num(v), sl, True, D ** -0.5)
+    sl = i32(lens)
+    ref = reference(q, torch.nan_to_num(k), torch.nan_to_num(v), seqlens=sl)
     vmax = float(torch.nan_to_num(v).abs().max())
     o, lse = ops.fa3_prefill_cache(q, k, v, cache_seqlens=sl, return_lse=True, key_splits=3)
     torch.cuda.synchronize()
-    _check(o, ref[0], ref[2], vmax, q.dtype)
-    _check_lse(o, lse, ref[1])
+    check_out(o, ref[0], ref[2], vmax, q.dtype)
+    check_lse(o, lse, ref[1])
     # out= given, with strides of its own: a slice of a wider [B, Sq, H, 2 D] buffer, untouched outside the slice
     wide = torch.full((B, Sq, H, 2 * D), 7.0, dtype=torch.bfloat16, device=dev)
     out = wide[..., D:].permute(0, 2, 1, 3)
@@ -287,25 +286,11 @@ def test_strided_views_of_q_cache_and_out():
 
 # --- graph capture -------------------------------------------------------------------------------------------------------------------
 
-def _capture(step):
-    """``step()`` once on a side stream (allocator warm-up), then captured -> (graph, what the captured call returned)."""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        res = step()
-    return graph, res
-
-
 def test_split_step_replays_in_a_graph():
     """Append + split launch + merge captured once on a paged cache; replayed while the lengths grow across a tile (100 -> 130 keys: 2 ->
     3 tiles) and a split boundary (255 -> 257: per 1 -> 2 with 4 splits), pages move and q changes: each replay equals the eager call."""
     from photonic_flash_attention_amd import ops
-    dev, dtype, B, H, Hkv, D, page, n_pages, Sq = _dev(), torch.bfloat16, 2, 8, 2, 128, 64, 24, 70
+    dev, dtype, B, H, Hkv, D, page, n_pages, Sq = device(), torch.bfloat16, 2, 8, 2, 128, 64, 24, 70
     g = torch.Generator().manual_seed(89)
 
     def rnd(*shape):
@@ -325,7 +310,7 @@ def test_split_step_replays_in_a_graph():
     def step(q, kn, vn, k, v, lens, table, out):
         return ops.fa3_prefill_cache(q, k, v, cache_seqlens=lens, block_table=table, k_new=kn, v_new=vn, key_splits=4, out=out, return_lse=True)
 
-    graph, (o_g, lse_g) = _capture(lambda: step(q_s, kn_s, vn_s, kp, vp, lens_s, table_s, o_s))
+    graph, (o_g, lse_g) = capture(lambda: step(q_s, kn_s, vn_s, kp, vp, lens_s, table_s, o_s))
     assert o_g is o_s
     for n, lens in enumerate(all_lens):
         if n:                                                   # everything the graph reads from the device changes
@@ -346,9 +331,9 @@ def test_split_step_replays_in_a_graph():
     # and the eager result is the right one: fp64 on the gathered caches of the last step
     kc = torch.stack([kp[table_s[b].long()].permute(1, 0, 2, 3).reshape(Hkv, 8 * page, D) for b in range(B)])
     vc = torch.stack([vp[table_s[b].long()].permute(1, 0, 2, 3).reshape(Hkv, 8 * page, D) for b in range(B)])
-    ref = _reference(q_s, kc, vc, lens_s, True, D ** -0.5)
-    _check(o_g, ref[0], ref[2], float(vc.abs().max()), dtype)
-    _check_lse(o_g, lse_g, ref[1])
+    ref = reference(q_s, kc, vc, seqlens=lens_s)
+    check_out(o_g, ref[0], ref[2], float(vc.abs().max()), dtype)
+    check_lse(o_g, lse_g, ref[1])
 
 
 # --- shared prefix -------------------------------------------------------------------------------------------------------------------
@@ -359,11 +344,11 @@ PRIVATE = tuple(100 + (37 * b) % 101 for b in range(40))        # 100 .. 200 pri
 def test_prefix_key_splits_on_the_shared_prefix_step():
     """80 and 120 rows against a 1024-key prefix: the prefix pass is fa3_prefill_cache over one sequence, now split over its keys."""
     from photonic_flash_attention_amd import ops
-    pr = sp._problem(40, 2, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
-    sp._both_caches(ops.fa3_decode, pr, "decode B40 Sq2 prefix_key_splits=4", prefix_key_splits=4)
-    pr3 = sp._problem(40, 3, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
-    sp._both_caches(ops.fa3_prefill_cache, pr3, "prefill B40 Sq3 prefix_key_splits=auto", prefix_key_splits="auto")
-    sp._both_caches(ops.fa3_prefill_cache, pr3, "prefill B40 Sq3 prefix_key_splits=8", prefix_key_splits=8)
+    pr = prefix_problem(40, 2, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
+    both_prefix_caches(ops.fa3_decode, pr, "decode B40 Sq2 prefix_key_splits=4", prefix_key_splits=4)
+    pr3 = prefix_problem(40, 3, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
+    both_prefix_caches(ops.fa3_prefill_cache, pr3, "prefill B40 Sq3 prefix_key_splits=auto", prefix_key_splits="auto")
+    both_prefix_caches(ops.fa3_prefill_cache, pr3, "prefill B40 Sq3 prefix_key_splits=8", prefix_key_splits=8)
 
 
 def test_prefix_key_splits_reaches_the_prefix_pass_only_past_64_rows(monkeypatch):
@@ -376,7 +361,7 @@ def test_prefix_key_splits_reaches_the_prefix_pass_only_past_64_rows(monkeypatch
         return real(*a, **kw)
 
     monkeypatch.setattr(ops, "fa3_prefill_cache", spy)
-    pr = sp._problem(40, 2, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
+    pr = prefix_problem(40, 2, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
     kw = dict(cache_seqlens=pr["lens"], block_table=pr["table"], shared_prefix=1024, return_lse=True)
     with_none = ops.fa3_decode(pr["q"], pr["kp"], pr["vp"], prefix_key_splits=None, **kw)
     assert seen == [((1, 8, 80, 128), None, None)]
@@ -390,7 +375,7 @@ def test_prefix_key_splits_reaches_the_prefix_pass_only_past_64_rows(monkeypatch
     assert torch.equal(with_none[0], without[0]) and torch.equal(with_none[1], without[1])
     # 64 rows or fewer: the decode kernel splits by itself, the argument is validated and otherwise unused
     del seen[:]
-    small = sp._problem(4, 3, 64, (3, 64, 65, 130), 320, torch.bfloat16)
+    small = prefix_problem(4, 3, 64, (3, 64, 65, 130), 320, torch.bfloat16)
     skw = dict(cache_seqlens=small["lens"], shared_prefix=128, return_lse=True)
     a = ops.fa3_decode(small["q"], small["kc"], small["vc"], prefix_key_splits=8, **skw)
     b = ops.fa3_decode(small["q"], small["kc"], small["vc"], **skw)
@@ -402,8 +387,8 @@ def test_shared_prefix_step_with_a_split_prefix_pass_replays_in_a_graph():
     """Append + split prefix pass + its merge + own-keys pass + final merge captured once; replayed after q, the new rows and the
     lengths changed: each replay equals the eager call bit for bit."""
     from photonic_flash_attention_amd import ops
-    pr = sp._problem(40, 2, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
-    dev, dtype = _dev(), torch.bfloat16
+    pr = prefix_problem(40, 2, 128, PRIVATE, 1024 + 256, torch.bfloat16, P=1024)
+    dev, dtype = device(), torch.bfloat16
     g = torch.Generator().manual_seed(90)
 
     def rnd(*shape):
@@ -417,7 +402,7 @@ def test_shared_prefix_step_with_a_split_prefix_pass_replays_in_a_graph():
         return ops.fa3_decode(q, k, v, cache_seqlens=lens, block_table=table_s, k_new=kn, v_new=vn, shared_prefix=1024, prefix_key_splits=4,
                               out=out, return_lse=True)
 
-    graph, (o_g, lse_g) = _capture(lambda: step(q_s, kn_s, vn_s, kp, vp, lens_s, o_s))
+    graph, (o_g, lse_g) = capture(lambda: step(q_s, kn_s, vn_s, kp, vp, lens_s, o_s))
     for n in range(3):
         if n:
             q_s.copy_(rnd(40, 2, 8, 128).permute(0, 2, 1, 3))

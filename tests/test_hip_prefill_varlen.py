@@ -10,9 +10,7 @@ and 4 start with the same 256 keys, so that a paged layout can hold that prefix 
 
 Two oracles.  The ragged call must be ``torch.equal`` to ``ops.fa3_prefill_cache`` called per sequence (B = 1) on that sequence's
 rows, cache and length: same Q clamp, same padding rows, same rescale points.  And, independently of the uniform kernel, it must
-meet fp64 attention with the bottom-right rule within the bound of tests/test_hip_prefill_cache.py, restated here:
-|err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6 for a 16-bit output (eps 2^-9 bf16, 2^-11 fp16), 1e-3 max-abs for fp32,
-2e-3 on the LSE.
+meet fp64 attention with the bottom-right rule within its bounds (the reference and the bounds of tests/kvcache_testlib.py).
 
 Every cache tail at and past ``len_b`` and every pool page no table entry names holds NaN, and every packed output buffer holds a
 sentinel before the call, so a read past a length, of a foreign page, or a write outside a sequence's rows shows.  Only legal
@@ -29,10 +27,10 @@ import functools
 import pytest
 import torch
 
+from kvcache_testlib import NAN, check_lse, check_out, device, i32, reference, scatter
+
 pytestmark = pytest.mark.gpu
 
-EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
-NAN = float("nan")
 O_SENTINEL, LSE_SENTINEL = 7.0, 12345.0
 
 B, H, HKV, SMAX, TOTAL, MAXQ = 5, 4, 2, 1024, 640, 300
@@ -46,19 +44,10 @@ CASES = [(dt, D, causal, None) for dt in (torch.bfloat16, torch.float16) for D i
 IDS = [f"{'bf16' if dt is torch.bfloat16 else 'fp16'}-d{D}-{'causal' if c else 'full'}{'-o32' if od else ''}" for dt, D, c, od in CASES]
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _i32(x):
-    return torch.tensor(x, dtype=torch.int32, device=_dev())
-
-
 @functools.lru_cache(maxsize=None)
 def _fixture(dtype, D):
     """-> (q packed [640,H,D], clean k, v [B,Hkv,Smax,D], NaN-tailed kn, vn); shared and never modified."""
-    dev = _dev()
+    dev = device()
     g = torch.Generator(device=dev).manual_seed(1000 + D + (0 if dtype is torch.bfloat16 else 1))
     q = torch.randn(TOTAL, H, D, generator=g, device=dev).to(dtype)
     k = torch.randn(B, HKV, SMAX, D, generator=g, device=dev).to(dtype)
@@ -70,55 +59,6 @@ def _fixture(dtype, D):
         kn[b, :, n:] = NAN
         vn[b, :, n:] = NAN
     return q, k, v, kn, vn
-
-
-def _reference(q, k, v, seqlens, causal, scale):
-    """fp64 on the GPU from CLEAN caches: q [B,H,Sq,D], k/v [B,Hkv,Smax,D] -> (o, lse, ||p_row||_2)."""
-    Bq, Hq, Sq, D = q.shape
-    Hkv, Smax = k.shape[1], k.shape[2]
-    g = Hq // Hkv
-    kd = k.double().repeat_interleave(g, dim=1)
-    vd = v.double().repeat_interleave(g, dim=1)
-    s = (q.double() @ kd.transpose(-1, -2)) * scale
-    j = torch.arange(Smax, device=q.device)
-    i = torch.arange(Sq, device=q.device)
-    L = seqlens.to(q.device).long()
-    vis = (j[None, None, :] < L[:, None, None]).expand(Bq, Sq, Smax)
-    if causal:
-        vis = vis & (j[None, None, :] <= L[:, None, None] - Sq + i[None, :, None])   # bottom-right, per batch
-    s = s.masked_fill(~vis[:, None], float("-inf"))
-    m = s.amax(-1, keepdim=True)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    safe = torch.where(l > 0, l, torch.ones_like(l))
-    pn = p / safe
-    o = pn @ vd
-    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, float("-inf")))[..., 0]
-    return o, lse, pn.norm(dim=-1, keepdim=True)
-
-
-def _check(got, ref, pnorm, vmax, dtype):
-    assert bool(torch.isfinite(got).all()), "non-finite output: a key at or past len_b, or a page of another sequence, was read"
-    err = (got.double() - ref).abs()
-    print(f"max-abs vs reference {float(err.max()):.3e} ({got.dtype})")
-    if got.dtype == torch.float32:
-        assert float(err.max()) <= 1e-3, float(err.max())
-        return
-    eps = EPS[dtype]
-    bound = eps * ref.abs() + 3 * eps * vmax * pnorm + 2e-6
-    worst = float((err - bound).max())
-    assert worst <= 0, f"max-abs {float(err.max()):.3e}, over the bound by {worst:.3e}"
-
-
-def _check_lse(o, lse, rlse):
-    fin = torch.isfinite(rlse)
-    assert torch.equal(torch.isfinite(lse), fin)
-    assert not bool(torch.isnan(lse).any())
-    assert bool((lse[~fin] == float("-inf")).all())
-    assert bool((o[~fin[..., None].expand_as(o)] == 0).all())           # a row with no visible key: exactly zero
-    if bool(fin.any()):
-        assert float((lse.double() - rlse)[fin].abs().max()) <= 2e-3
 
 
 def _seq_q(q, b, cu=CU, n=None):
@@ -133,7 +73,7 @@ def _ragged(dtype, D, causal, out_dtype):
     from photonic_flash_attention_amd import ops
     q, _, _, kn, vn = _fixture(dtype, D)
     out = torch.full((TOTAL, H, D), O_SENTINEL, dtype=out_dtype or dtype, device=q.device)
-    o, lse = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS), causal=causal,
+    o, lse = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS), causal=causal,
                                     out_dtype=out_dtype, return_lse=True, out=out)
     torch.cuda.synchronize()
     assert o.data_ptr() == out.data_ptr() and o.shape == (TOTAL, H, D) and lse.shape == (H, TOTAL) and lse.dtype == torch.float32
@@ -144,7 +84,7 @@ def _ragged(dtype, D, causal, out_dtype):
 def _fp64(dtype, D, causal):
     """Per sequence with rows: the fp64 (o [1,H,Sq,D], lse [1,H,Sq], pnorm) on the clean caches."""
     q, k, v, _, _ = _fixture(dtype, D)
-    return {b: _reference(_seq_q(q, b), k[b:b + 1], v[b:b + 1], _i32(KV_LENS[b:b + 1]), causal, D ** -0.5)
+    return {b: reference(_seq_q(q, b), k[b:b + 1], v[b:b + 1], seqlens=i32(KV_LENS[b:b + 1]), causal=causal)
             for b in range(B) if Q_LENS[b] > 0}
 
 
@@ -158,7 +98,7 @@ def test_ragged_call_equals_per_sequence_uniform_calls(dtype, D, causal, out_dty
     for b in range(B):
         if Q_LENS[b] == 0:
             continue
-        ou, lu = ops.fa3_prefill_cache(_seq_q(q, b), kn[b:b + 1], vn[b:b + 1], cache_seqlens=_i32(KV_LENS[b:b + 1]), causal=causal,
+        ou, lu = ops.fa3_prefill_cache(_seq_q(q, b), kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32(KV_LENS[b:b + 1]), causal=causal,
                                        out_dtype=out_dtype, return_lse=True)
         torch.cuda.synchronize()
         assert bool(torch.isfinite(ou).all())
@@ -175,8 +115,8 @@ def test_ragged_call_against_fp64(dtype, D, causal, out_dtype):
     for b, (ro, rl, pn) in _fp64(dtype, D, causal).items():
         got = o[CU[b]:CU[b + 1]].permute(1, 0, 2)[None]
         gl = lse[None, :, CU[b]:CU[b + 1]]
-        _check(got, ro, pn, vmax, dtype)
-        _check_lse(got, gl, rl)
+        check_out(got, ro, pn, vmax, dtype)
+        check_lse(got, gl, rl)
     # sequence 3 holds 20 keys for 33 rows: under the causal rule its first 13 rows see nothing, without it every row sees the 20
     head_o, head_l = o[CU[3]:CU[3] + 13], lse[:, CU[3]:CU[3] + 13]
     if causal:
@@ -210,7 +150,7 @@ def test_rows_behind_the_last_sequence_are_never_written(out_dtype):
     for causal in (True, False):
         out = torch.full((TOTAL, H, D), O_SENTINEL, dtype=out_dtype or dtype, device=q.device)
         lse = torch.full((H, TOTAL), LSE_SENTINEL, dtype=torch.float32, device=q.device)
-        _raw_call(q, kn, vn, _i32(CU), MAXQ, _i32(KV_LENS), out, lse, causal)
+        _raw_call(q, kn, vn, i32(CU), MAXQ, i32(KV_LENS), out, lse, causal)
         assert bool((out[CU[B]:] == O_SENTINEL).all()), "a spare row of O was written"
         assert bool((lse[:, CU[B]:] == LSE_SENTINEL).all()), "a spare LSE entry was written"
         o_ops, l_ops = _ragged(dtype, D, causal, out_dtype)                      # and the covered rows are the ops call's
@@ -226,7 +166,7 @@ def test_rows_past_max_seqlen_q_are_never_written_and_the_others_equal_the_unifo
     for causal in (True, False):
         out = torch.full((TOTAL, H, D), O_SENTINEL, dtype=dtype, device=q.device)
         lse = torch.full((H, TOTAL), LSE_SENTINEL, dtype=torch.float32, device=q.device)
-        _raw_call(q, kn, vn, _i32(CU), cap, _i32(KV_LENS), out, lse, causal)
+        _raw_call(q, kn, vn, i32(CU), cap, i32(KV_LENS), out, lse, causal)
         assert bool((out[CU[B]:] == O_SENTINEL).all()) and bool((lse[:, CU[B]:] == LSE_SENTINEL).all())
         o_full, l_full = _ragged(dtype, D, causal, None)
         for b in range(B):
@@ -240,7 +180,7 @@ def test_rows_past_max_seqlen_q_are_never_written_and_the_others_equal_the_unifo
             assert bool((lse[:, s + cap:s + n] == LSE_SENTINEL).all())
             sq_b = min(n, cap)
             ln = KV_LENS[b] - (sq_b - cap)
-            ou, lu = ops.fa3_prefill_cache(_seq_q(q, b, n=cap), kn[b:b + 1], vn[b:b + 1], cache_seqlens=_i32([ln]), causal=causal,
+            ou, lu = ops.fa3_prefill_cache(_seq_q(q, b, n=cap), kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32([ln]), causal=causal,
                                            return_lse=True)
             torch.cuda.synchronize()
             assert torch.equal(out[s:s + cap].permute(1, 0, 2), ou[0]) and torch.equal(lse[:, s:s + cap], lu[0]), b
@@ -248,33 +188,13 @@ def test_rows_past_max_seqlen_q_are_never_written_and_the_others_equal_the_unifo
 
 # --- paged == contiguous -------------------------------------------------------------------------------------------------------------
 
-def _scatter(k, v, page, seed, layout="phsd", spare=5):
-    """Scatter contiguous [B, Hkv, Smax, D] caches over pools in a random page order.  -> (k_pool, v_pool, table) with the pools as
-    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN (and so does whatever NaN the caches carry)."""
-    Bk, Hkv, Smax, D = k.shape
-    pages = Smax // page
-    NP = Bk * pages + spare
-    dev = k.device
-    perm = torch.randperm(NP, generator=torch.Generator().manual_seed(seed))[:Bk * pages]
-    table = perm.to(torch.int32).reshape(Bk, pages).to(dev)
-    pools = []
-    for src in (k, v):
-        if layout == "phsd":        # flash-attn style [num_pages, page, Hkv, D], passed transposed
-            pool = torch.full((NP, page, Hkv, D), NAN, dtype=k.dtype, device=dev).transpose(1, 2)
-        else:
-            pool = torch.full((NP, Hkv, page, D), NAN, dtype=k.dtype, device=dev)
-        pool[perm.to(dev)] = src.reshape(Bk, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(Bk * pages, Hkv, page, D)
-        pools.append(pool)
-    return pools[0], pools[1], table
-
-
 @pytest.mark.parametrize("layout", ["phsd", "hpsd"])
 @pytest.mark.parametrize("page", [64, 256])
 def test_paged_equals_contiguous_with_a_shared_prefix_page(page, layout):
     from photonic_flash_attention_amd import ops
     for dtype, D in ((torch.bfloat16, 128), (torch.float16, 64)):
         q, _, _, kn, vn = _fixture(dtype, D)
-        kp, vp, table = _scatter(kn, vn, page, seed=page + D, layout=layout)
+        kp, vp, table = scatter(kn, vn, page, seed=page + D, layout=layout)
         assert kp.is_contiguous() == (layout == "hpsd")
         n = SHARED // page                               # sequences 0 and 4 hold their common prefix once
         freed = table[4, :n].clone()
@@ -286,7 +206,7 @@ def test_paged_equals_contiguous_with_a_shared_prefix_page(page, layout):
                 continue
             oc, lc = _ragged(dtype, D, causal, out_dtype)                 # the contiguous call on the gathered cache
             out = torch.full((TOTAL, H, D), O_SENTINEL, dtype=out_dtype or dtype, device=q.device)
-            op, lp = ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS),
+            op, lp = ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS),
                                             causal=causal, out_dtype=out_dtype, return_lse=True, out=out, block_table=table)
             torch.cuda.synchronize()
             assert bool(torch.isfinite(op).all()), "a page of another sequence, or a key past len_b, was read"
@@ -307,14 +227,14 @@ def test_strided_packed_q_from_a_fused_projection():
         for causal in (True, False):
             oc, lc = _ragged(dtype, D, causal, None)
             out = torch.full((TOTAL, H, D), O_SENTINEL, dtype=dtype, device=q.device)
-            o, lse = ops.fa3_prefill_varlen(qs, kn, vn, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS),
+            o, lse = ops.fa3_prefill_varlen(qs, kn, vn, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS),
                                             causal=causal, return_lse=True, out=out)
             torch.cuda.synchronize()
             assert torch.equal(o, oc) and torch.equal(lse[:, :CU[B]], lc[:, :CU[B]])
     # out= with strides of its own: a slice of a wider buffer, untouched outside the slice
     q, _, _, kn, vn = _fixture(torch.bfloat16, 128)
     wide = torch.full((TOTAL, H, 2 * 128), O_SENTINEL, dtype=torch.bfloat16, device=q.device)
-    o, _ = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS), out=wide[..., 128:])
+    o, _ = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS), out=wide[..., 128:])
     torch.cuda.synchronize()
     assert torch.equal(o, _ragged(torch.bfloat16, 128, True, None)[0]) and bool((wide[..., :128] == O_SENTINEL).all())
 
@@ -325,8 +245,8 @@ def test_graph_replays_while_cu_seqlens_lengths_and_table_change():
     from photonic_flash_attention_amd import ops
     dtype, D, page, cap = torch.bfloat16, 128, 64, 512
     q, k, v, _, _ = _fixture(dtype, D)
-    kp, vp, table = _scatter(k, v, page, seed=77)        # clean caches: every page a table row can name is finite
-    cu, lens = _i32(CU), _i32(KV_LENS)
+    kp, vp, table = scatter(k, v, page, seed=77)        # clean caches: every page a table row can name is finite
+    cu, lens = i32(CU), i32(KV_LENS)
     out = torch.full((TOTAL, H, D), O_SENTINEL, dtype=dtype, device=q.device)
 
     def call(o):
@@ -363,15 +283,15 @@ def test_graph_replays_while_cu_seqlens_lengths_and_table_change():
     assert bool((a[0][CU[B]:] == O_SENTINEL).all())
     # another step of the same server: other row counts (one sequence fills max_seqlen_q, one is empty, none leaves a spare row),
     # other lengths (30 keys for 63 rows: leading rows see nothing) and the sequences' pages dealt out differently
-    cu.copy_(_i32([0, 512, 512, 576, 577, 640]))
-    lens.copy_(_i32([1024, 100, 64, 500, 30]))
+    cu.copy_(i32([0, 512, 512, 576, 577, 640]))
+    lens.copy_(i32([1024, 100, 64, 500, 30]))
     table.copy_(table[[3, 0, 4, 1, 2]].flip(1).contiguous())
     b = replay_and_compare(TOTAL)
     assert not torch.equal(a[0], b[0]) and not bool((b[0] == O_SENTINEL).all(-1).any())              # every row is covered now
     assert bool((b[0][577:577 + 33] == 0).all()) and bool((b[1][:, 577:577 + 33] == float("-inf")).all())
     # and back: the first state's bits again
-    cu.copy_(_i32(CU))
-    lens.copy_(_i32(KV_LENS))
+    cu.copy_(i32(CU))
+    lens.copy_(i32(KV_LENS))
     table.copy_(table.flip(1)[[1, 3, 4, 0, 2]].contiguous())
     c = replay_and_compare(CU[B])
     assert torch.equal(c[0], a[0]) and torch.equal(c[1][:, :CU[B]], a[1][:, :CU[B]])
@@ -380,7 +300,7 @@ def test_graph_replays_while_cu_seqlens_lengths_and_table_change():
 def _scattered_fixture_result(q, kp, vp, table):
     """The fixture's ragged result (max_seqlen_q = 300) on the clean paged cache: what the graph's first state must reproduce."""
     from photonic_flash_attention_amd import ops
-    o, _ = ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=_i32(CU), max_seqlen_q=MAXQ, cache_seqlens=_i32(KV_LENS), block_table=table)
+    o, _ = ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS), block_table=table)
     torch.cuda.synchronize()
     return o
 
@@ -389,7 +309,7 @@ def _scattered_fixture_result(q, kp, vp, table):
 
 def test_paged_cache_append_varlen_then_prefill_varlen():
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev = _dev()
+    dev = device()
     Hq, Hkv, D, page = 8, 2, 128, 64
     cache = PagedKVCache(num_pages=24, page_size=page, Hkv=Hkv, D=D, dtype=torch.bfloat16, device=dev, max_batch=3, max_pages_per_seq=8)
     cache.k_pool.fill_(NAN)                  # whatever is not appended stays NaN: unfilled page tails, unused pages
@@ -413,9 +333,9 @@ def test_paged_cache_append_varlen_then_prefill_varlen():
         for s, n in zip(slots, q_lens):
             if n:
                 gk, gv = cache.gather(s)
-                ref = _reference(q[at:at + n].permute(1, 0, 2)[None], gk[None], gv[None], _i32([cache.length(s)]), True, D ** -0.5)
+                ref = reference(q[at:at + n].permute(1, 0, 2)[None], gk[None], gv[None], seqlens=i32([cache.length(s)]))
                 got = o[at:at + n].permute(1, 0, 2)[None]
-                _check(got, ref[0], ref[2], float(gv.abs().max()), torch.bfloat16)
-                _check_lse(got, lse[None, :, at:at + n], ref[1])
+                check_out(got, ref[0], ref[2], float(gv.abs().max()), torch.bfloat16)
+                check_lse(got, lse[None, :, at:at + n], ref[1])
             at += n
     assert [cache.length(s) for s in slots] == [465, 301, 71]

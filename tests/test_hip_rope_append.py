@@ -21,9 +21,11 @@ import functools
 import pytest
 import torch
 
+from kvcache_testlib import NAN, device, i32
+
 pytestmark = pytest.mark.gpu
 
-NAN, SENTINEL = float("nan"), -7.0
+SENTINEL = -7.0
 B, H, HKV, SMAX, TOTAL, MAXQ, MAX_POS = 5, 4, 2, 1024, 640, 300, 1024
 Q_LENS = [1, 300, 0, 33, 257]
 KV_LENS = [777, 300, 512, 20, 1000]
@@ -31,15 +33,6 @@ CU = [0, 1, 301, 301, 334, 591]
 SHARED = 256
 DTYPES = pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 STYLES = pytest.mark.parametrize("interleaved", [False, True], ids=["half", "interleaved"])
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _i32(x, dev=None):
-    return torch.tensor(x, dtype=torch.int32, device=_dev() if dev is None else dev)
 
 
 @functools.lru_cache(maxsize=None)
@@ -106,7 +99,7 @@ def _shuffled_table(page, seed):
 
 def _ragged_case(dtype, D, layout, seed):
     """The ragged fixture on the device -> (q, kn, vn, kc, vc, lens, cu, table)."""
-    dev = _dev()
+    dev = device()
     q, kn, vn = (t.to(dev) for t in _rows(lambda h: (TOTAL, h, D), seed, dtype, used=CU[-1]))
     table = None
     if layout == "contiguous":
@@ -118,7 +111,7 @@ def _ragged_case(dtype, D, layout, seed):
         table, n_pages = _shuffled_table(page, page + D)
         table = table.to(dev)
         kc = torch.full((n_pages, page, HKV, D), SENTINEL, dtype=dtype, device=dev).transpose(1, 2)
-    return q, kn, vn, kc, torch.full_like(kc, SENTINEL), _i32(KV_LENS), _i32(CU), table
+    return q, kn, vn, kc, torch.full_like(kc, SENTINEL), i32(KV_LENS), i32(CU), table
 
 
 @pytest.mark.parametrize("layout", ["contiguous", "token-major", "page64", "page256"])
@@ -128,7 +121,7 @@ def _ragged_case(dtype, D, layout, seed):
 def test_ragged_rope_append_equals_the_model(dtype, D, interleaved, layout):
     from photonic_flash_attention_amd import ops
     q, kn, vn, kc, vc, lens, cu, table = _ragged_case(dtype, D, layout, 100 + D)
-    cos, sin = (t.to(_dev()) for t in _tables(D))
+    cos, sin = (t.to(device()) for t in _tables(D))
     kw = dict(cu_seqlens_q=cu, max_seqlen_q=MAXQ, rotary_interleaved=interleaved)
     q_out, mq, mk, mv = _run_and_compare(q, kn, vn, kc, vc, lens, cos, sin, table, **kw)
     written = 1 + 300 + 20 + 257                             # sequence 3 drops the K / V of 13 of its 33 rows ...
@@ -147,7 +140,7 @@ def test_ragged_rope_append_equals_the_model(dtype, D, interleaved, layout):
 @DTYPES
 def test_partial_rotation_copies_the_rest_of_the_head(dtype, D, R, interleaved, layout):
     q, kn, vn, kc, vc, lens, cu, table = _ragged_case(dtype, D, layout, 200 + R)
-    cos, sin = (t.to(_dev()) for t in _tables(R))
+    cos, sin = (t.to(device()) for t in _tables(R))
     q_out, mq, mk, _ = _run_and_compare(q, kn, vn, kc, vc, lens, cos, sin, table, cu_seqlens_q=cu, max_seqlen_q=MAXQ, rotary_interleaved=interleaved)
     assert torch.equal(q_out[:CU[-1], :, R:], q[:CU[-1], :, R:]) and not torch.equal(q_out[:CU[-1], :, :R], q[:CU[-1], :, :R])
 
@@ -158,7 +151,7 @@ def test_partial_rotation_copies_the_rest_of_the_head(dtype, D, R, interleaved, 
 def test_uniform_rope_append_on_views_of_a_fused_projection(Sq, lens, interleaved, paged):
     """B 3; q, k and v are strided views cut from one [B, Sq, (H + 2 Hkv) D] projection.  Sq 5 to a length of 130 with pages of 64
     crosses a page (keys 125 .. 129); 5 rows into a length of 3 drop the K / V of the first two."""
-    dev, dtype, D = _dev(), torch.bfloat16, 64
+    dev, dtype, D = device(), torch.bfloat16, 64
     fused = torch.randn(3, Sq, (H + 2 * HKV) * D, generator=torch.Generator().manual_seed(7 + Sq)).to(dtype).to(dev)
     q = fused[..., :H * D].view(3, Sq, H, D).transpose(1, 2)
     kn = fused[..., H * D:(H + HKV) * D].view(3, Sq, HKV, D).transpose(1, 2)
@@ -167,22 +160,22 @@ def test_uniform_rope_append_on_views_of_a_fused_projection(Sq, lens, interleave
     cos, sin = (t.to(dev) for t in _tables(D, 256))
     keep = fused.clone()
     if paged:
-        table = _i32([[5, 2, 7, 0], [1, 3, 4, 6], [8, 9, 10, 11]])
+        table = i32([[5, 2, 7, 0], [1, 3, 4, 6], [8, 9, 10, 11]])
         kc = torch.full((13, 64, HKV, D), SENTINEL, dtype=dtype, device=dev).transpose(1, 2)
     else:
         table = None
         kc = torch.full((3, HKV, 256, D), SENTINEL, dtype=dtype, device=dev)
-    _, _, mk, _ = _run_and_compare(q, kn, vn, kc, torch.full_like(kc, SENTINEL), _i32(lens), cos, sin, table, rotary_interleaved=interleaved)
+    _, _, mk, _ = _run_and_compare(q, kn, vn, kc, torch.full_like(kc, SENTINEL), i32(lens), cos, sin, table, rotary_interleaved=interleaved)
     assert torch.equal(fused, keep)                          # the inputs are only read
     assert int((mk != SENTINEL).any(-1).sum()) == sum(min(Sq, n) for n in lens) * HKV
     # without q_out the fresh buffer has the layout the attention calls prefer and the same bits
     from photonic_flash_attention_amd import ops
     kc2 = torch.full_like(kc, SENTINEL)
-    fresh = ops.rope_append(kn, vn, kc2, torch.full_like(kc, SENTINEL), cache_seqlens=_i32(lens), rotary_cos=cos, rotary_sin=sin, q=q,
+    fresh = ops.rope_append(kn, vn, kc2, torch.full_like(kc, SENTINEL), cache_seqlens=i32(lens), rotary_cos=cos, rotary_sin=sin, q=q,
                             rotary_interleaved=interleaved, block_table=table)
     torch.cuda.synchronize()
     assert fresh.shape == q.shape and fresh.transpose(1, 2).is_contiguous()
-    mq = _model(q, kn, vn, kc2, kc2, _i32(lens), cos, sin, table, rotary_interleaved=interleaved)[0]
+    mq = _model(q, kn, vn, kc2, kc2, i32(lens), cos, sin, table, rotary_interleaved=interleaved)[0]
     assert torch.equal(fresh.cpu(), mq)
 
 
@@ -192,7 +185,7 @@ def test_in_place_equals_out_of_place_and_kv_only(dtype, interleaved):
     from photonic_flash_attention_amd import ops
     D = 128
     q, kn, vn, kc, vc, lens, cu, table = _ragged_case(dtype, D, "page64", 300)
-    cos, sin = (t.to(_dev()) for t in _tables(D))
+    cos, sin = (t.to(device()) for t in _tables(D))
     kw = dict(cu_seqlens_q=cu, max_seqlen_q=MAXQ, rotary_interleaved=interleaved)
     q_out, _, mk, mv = _run_and_compare(q, kn, vn, kc, vc, lens, cos, sin, table, **kw)
     # in place
@@ -215,8 +208,8 @@ def test_pos_offsets_in_range_and_clamped_at_both_ends(interleaved, layout):
     tables (they are the whole allocation)."""
     dtype, D, R = torch.bfloat16, 64, 32
     q, kn, vn, kc, vc, lens, cu, table = _ragged_case(dtype, D, layout, 400)
-    cos, sin = (t.to(_dev()) for t in _tables(R))
-    offs = _i32([100, -400, 7, 5000, -700])
+    cos, sin = (t.to(device()) for t in _tables(R))
+    offs = i32([100, -400, 7, 5000, -700])
     kw = dict(cu_seqlens_q=cu, max_seqlen_q=MAXQ, rotary_interleaved=interleaved)
     q_out = _run_and_compare(q, kn, vn, kc, vc, lens, cos, sin, table, pos_offsets=offs, **kw)[0]
     no_offs = _run_and_compare(q, kn, vn, torch.full_like(kc, SENTINEL), torch.full_like(kc, SENTINEL), lens, cos, sin, table, **kw)[0]
@@ -229,7 +222,7 @@ def test_pos_offsets_in_range_and_clamped_at_both_ends(interleaved, layout):
 @STYLES
 def test_identity_tables_equal_kv_append(interleaved, layout):
     from photonic_flash_attention_amd import ops
-    dev, dtype, D = _dev(), torch.float16, 128
+    dev, dtype, D = device(), torch.float16, 128
     q, kn, vn, kc, vc, lens, cu, table = _ragged_case(dtype, D, layout, 500)
     cos, sin = torch.ones(MAX_POS, D // 2, device=dev), torch.zeros(MAX_POS, D // 2, device=dev)
     q_out = _run_and_compare(q, kn, vn, kc, vc, lens, cos, sin, table, cu_seqlens_q=cu, max_seqlen_q=MAXQ, rotary_interleaved=interleaved)[0]
@@ -257,7 +250,7 @@ def _paged_copy(kc, vc, ids):
 def _end_to_end(fn, q, kn, vn, kc, vc, lens, table, interleaved, offs, **ragged):
     """``fn(k_new=, v_new=, rotary_*=)`` against ``ops.rope_append`` + ``fn`` on the rotated Q -> (o, q_rot), the owned rows to check."""
     from photonic_flash_attention_amd import ops
-    cos, sin = (t.to(_dev()) for t in _tables(FD, 256))
+    cos, sin = (t.to(device()) for t in _tables(FD, 256))
     rot = dict(rotary_cos=cos, rotary_sin=sin, rotary_interleaved=interleaved, pos_offsets=offs)
     rk, rv, q_before = kc.clone(), vc.clone(), q.clone()
     q_rot = ops.rope_append(kn, vn, rk, rv, cache_seqlens=lens, q=q, block_table=table, **rot, **ragged)
@@ -274,7 +267,7 @@ def _end_to_end(fn, q, kn, vn, kc, vc, lens, table, interleaved, offs, **ragged)
 @pytest.mark.parametrize("entry,Sq", [("fa3_decode", 1), ("fa3_decode", 4), ("fa3_prefill_cache", 70)])
 def test_uniform_attention_calls_rotate_and_append_first(entry, Sq, interleaved, paged):
     from photonic_flash_attention_amd import ops
-    dev, dtype, lens = _dev(), torch.bfloat16, [100, 256]
+    dev, dtype, lens = device(), torch.bfloat16, [100, 256]
     g = torch.Generator().manual_seed(600 + Sq)
     kc, vc = (torch.randn(FB, HKV, FSMAX, FD, generator=g).to(dtype).to(dev) for _ in range(2))
     for b in range(FB):                                      # valid keys below len_b - Sq, NaN from there on (the step's own rows included)
@@ -283,9 +276,9 @@ def test_uniform_attention_calls_rotate_and_append_first(entry, Sq, interleaved,
     table = None
     if paged:
         ids = [[7, 2, 5, 0], [3, 8, 1, 6]]
-        table = _i32(ids)
+        table = i32(ids)
         kc, vc = _paged_copy(kc, vc, ids)
-    o, o_ref, lse, lse_ref, q_rot = _end_to_end(getattr(ops, entry), q, kn, vn, kc, vc, _i32(lens), table, interleaved, _i32([3, -20]))
+    o, o_ref, lse, lse_ref, q_rot = _end_to_end(getattr(ops, entry), q, kn, vn, kc, vc, i32(lens), table, interleaved, i32([3, -20]))
     assert bool(torch.isfinite(o_ref.float()).all()) and not torch.equal(q_rot, q)
     assert torch.equal(o, o_ref) and torch.equal(lse, lse_ref)
 
@@ -295,7 +288,7 @@ def test_uniform_attention_calls_rotate_and_append_first(entry, Sq, interleaved,
 def test_ragged_attention_call_rotates_and_appends_first(interleaved, paged):
     """``fa3_prefill_varlen`` on the ragged fixture (D 64): caches of finite keys, the step's rows written by the call itself."""
     from photonic_flash_attention_amd import ops
-    dev, dtype = _dev(), torch.bfloat16
+    dev, dtype = device(), torch.bfloat16
     q, kn, vn, kc, vc, lens, cu, table = _ragged_case(dtype, FD, "page64" if paged else "contiguous", 700)
     g = torch.Generator(device="cpu").manual_seed(701)
     kc.copy_(torch.randn(kc.shape, generator=g).to(dtype))
@@ -324,7 +317,7 @@ def test_whole_rotary_step_replays_in_a_graph():
     inputs and the rotary tables in between, against an eager twin."""
     from photonic_flash_attention_amd import ops
     from photonic_flash_attention_amd.integration.pytorch import PagedKVCache
-    dev, dtype, D, rows, bound = _dev(), torch.bfloat16, 64, 160, 130
+    dev, dtype, D, rows, bound = device(), torch.bfloat16, 64, 160, 130
 
     def make():
         c = PagedKVCache(num_pages=14, page_size=64, Hkv=HKV, D=D, dtype=dtype, device=dev, max_batch=3, max_pages_per_seq=4)

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import REPO, load_golden
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, synth
 
 HEADER = os.path.join(REPO, "include", "pfa_hip.h")
@@ -20,9 +21,7 @@ HEADER = os.path.join(REPO, "include", "pfa_hip.h")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def test_library_exports_every_declared_symbol(lib):

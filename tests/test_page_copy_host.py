@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 SYMBOLS = ("pfa_page_copy_check", "pfa_page_copy", "pfa_page_copy_describe")
@@ -25,9 +26,7 @@ SENTINEL = -7.0
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _args(**over):

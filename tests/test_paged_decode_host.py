@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 # offsets of pfa_fa3_decode_args in ABI v8 (the struct before the paging fields were appended); its size was 232
@@ -25,9 +26,7 @@ NEW_FIELDS = ("block_table", "block_table_stride_b", "page_size", "num_pages")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def test_paging_fields_are_appended_to_the_c_struct(tmp_path):

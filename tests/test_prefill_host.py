@@ -5,12 +5,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 PREFILL_SYMBOLS = ("pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_describe")
@@ -18,9 +18,7 @@ PREFILL_SYMBOLS = ("pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _args(**over):

@@ -6,12 +6,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 SPLIT_SYMBOLS = ("pfa_fa3_prefill_split_plan", "pfa_fa3_prefill_split_workspace_bytes", "pfa_fa3_prefill_split_check",
@@ -21,9 +21,7 @@ NULL, SHAPE, STRIDE, ALIGN, FLAGS = -1, -3, -6, -7, -10
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _args(**over):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 VARLEN_SYMBOLS = ("pfa_fa3_prefill_varlen_check", "pfa_fa3_prefill_varlen", "pfa_fa3_prefill_varlen_describe")
@@ -20,9 +21,7 @@ NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _args(**over):

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from conftest import REPO
+from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
 SYMBOLS = ("pfa_rope_append_check", "pfa_rope_append", "pfa_rope_append_describe")
@@ -30,9 +31,7 @@ IL = _capi.PFA_ROPE_INTERLEAVED
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
+    return built_lib()
 
 
 def _args(**over):
