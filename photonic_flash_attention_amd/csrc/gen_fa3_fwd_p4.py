@@ -31,15 +31,15 @@ import os
 import sys
 
 
-# Experiment / diagnostic knobs (P4_*): read from the environment ONLY with P4_DEV=1 (tools/p4_variants.py builds such code objects for
-# same-process A/B runs and stamped diagnostics; they are loaded by tools/p4_ab.py, never by the library).  The product build
-# (`make`) runs without P4_DEV: a P4_* knob left in the environment then stops the build instead of silently linking a stamped or
-# ablated code object into libpfa_hip.so.
+# One schedule, one diagnostic.  The only knob is P4_STAMP (below), read from the environment ONLY with P4_DEV=1: tools/p4_variants.py
+# builds the stamped code object, tools/p4_ab.py loads it, the library never does.  The product build (`make`) runs without P4_DEV: a
+# P4_* name left in the environment then stops the build instead of silently linking a stamped code object into libpfa_hip.so.  With
+# P4_DEV=1 a P4_* name the generator does not know stops it too (a mistyped or retired knob would otherwise A/B the base against itself).
 DEV = os.environ.get("P4_DEV", "") == "1"
-if not DEV:
-    _stray = sorted(k for k in os.environ if k.startswith("P4_"))
-    if _stray:
-        sys.exit(f"gen_fa3_fwd_p4.py: {', '.join(_stray)} set without P4_DEV=1 -- the product code object takes no experiment knobs")
+_stray = sorted(k for k in os.environ if k.startswith("P4_") and not (DEV and k in ("P4_DEV", "P4_STAMP")))
+if _stray:
+    sys.exit(f"gen_fa3_fwd_p4.py: {', '.join(_stray)} set without P4_DEV=1 -- the product code object takes no experiment knobs" if not DEV else
+             f"gen_fa3_fwd_p4.py: unknown knob {', '.join(_stray)} -- P4_STAMP is the only one (with P4_DEV=1)")
 
 
 def knob(name, default):
@@ -115,18 +115,14 @@ def PS1(X):                 # fast loop: row sum of key block 1, per strip (fold
     return 248 if X == 'A' else 249
 
 
-def PDL(X, i):              # split P: the low halves (the VGPRs the 4-deep fragment rings would use)
+def PDL(X, i):              # split P: the low halves
     return 176 + (0 if X == 'A' else 16) + i
 
 
-PKADD = int(knob("P4_PKADD", "0"))        # EXPERIMENT, off: row sums as v_pk_add_f32 on register pairs (32 instead of 64 instructions a tile) ran 5-7 % SLOWER
-SEAM = int(knob("P4_SEAM", "1"))          # the item seam as one more FULL iteration (kernel(), body_seam): 0 = LAST body, epilogue, prologue one after the other
-ILV = int(knob("P4_ILV", "1"))            # the FULL body's softmax streams of strips A and B interleaved instruction by instruction
-WAITN = int(knob("P4_WAITN", "2"))        # LDS fragments waited for at a time (2: 8 s_waitcnt per phase; 4: 4)
-LEAN = int(knob("P4_LEAN", "1"))          # the tile loop's lean path (kernel()): 0 = every iteration carries the full bookkeeping
-RING = int(knob("P4_RING", "8"))          # K / V^T fragment rings: 4 (VGPRs) or 8 (the spare accumulator registers a[192:255])
-KFR = lambda i: (192 + 4 * (i % 8)) if RING == 8 else (176 + 4 * (i % 4))
-VFR = lambda i: (224 + 4 * (i % 8)) if RING == 8 else (192 + 4 * (i % 4))
+WAITN = 2                   # LDS fragments waited for at a time (8 s_waitcnt per phase)
+RING = 8                    # depth of the K / V^T fragment rings: the spare accumulator registers a[192:255] (a tile has 8 or 16 fragments of each)
+KFR = lambda i: 192 + 4 * (i % RING)
+VFR = lambda i: 224 + 4 * (i % RING)
 KOFF = lambda ks: 208 + ks
 VOFF = lambda sel, hi: 216 + 2 * sel + hi       # sel: d block (D = 128) / 2 * (k-step parity) + d block (D = 64)
 KDOFF = lambda t: 224 + t
@@ -143,35 +139,24 @@ def SV(X, f):               # row sum / scaled max of the item that is ending, p
     return 80 + (0 if X == 'A' else 2) + (0 if f == 'l' else 1)
 
 
-def PSP(X):                 # packed row-sum accumulator of a strip (two lanes of a v_pk_add_f32): v[176:177] / v[178:179]
-    return 176 + (0 if X == 'A' else 2)
-
-
 V_PS1 = 248
 V_MX = 249
 V_T = [250, 251, 252, 253]
 V_TA = 254            # causal: r + 1 - 4h (element-mask threshold of the diagonal tile, see mask_diag)
 V_LANE = 255
 V_E = list(range(0, 16))   # prologue / epilogue / rescale scratch (v0 = workitem id at entry)
-STAMP = int(knob("P4_STAMP", "0"))      # 1: every phase; 2: one stamp per iteration only (buckets 0 / 1 stay empty); 3: kernel totals only (lean loop and pipelined seam stay on)
-LIGHT1 = int(knob("P4_LIGHT1", "0"))      # EXPERIMENT: causal units run their light block first (the heavy streams of a head then follow each other within 28 tiles)
-MB = int(knob("P4_MB", "1"))              # fast loop: the iteration's barrier sits INSIDE the PV phase (behind the last V^T read), and the first K fragments of the
-                                          # next QK^T phase are requested right behind it -- their latency and the barrier skew run under the rest of PV(j)
-MBGAP = int(knob("P4_MBGAP", "0"))        # ... behind this MFMA gap of the PV phase (0: 27 of 32 at D = 128, 12 of 16 at D = 64 -- same box, gaps 16..27 / 8..13:
-                                          # the late barrier is worth +0.4..1 % over gap 20 at D = 128; at D = 64 gap 13 loses 2 %)
-PSTART = int(knob("P4_PSTART", "1"))      # parity variant: key block 0's P is packed by the START stream, in the second half of the PV phase (behind the MFMAs
-                                          # that still read the previous tile's dwords 0..7), not by the finish: the QK^T phase carried 330 instructions in 32 gaps
-KMFAST = int(knob("P4_KMFAST", "1"))      # key-mask kernels on the fast loop too (fresh rows: see Gen.__init__)
-DIET = int(knob("P4_DIET", "1"))          # fast loop: block sums start with t0 + t1 (no zeroing), one compare + s_cbranch_vccnz per tile for both strips
-FASTMAX = int(knob("P4_FASTMAX", "1"))    # the tile loop without a row max (Gen.fast; see finish_fast): a tile's exponentials are taken against the running
-                                          # maximum, its scaled scores stay in the S buffer, and a row sum past 2^14 sends the wave to a fix-up subroutine
-PRE = int(knob("P4_PRE", "24"))            # issue cycles of the finish stream placed between the first K-fragment reads and the first QK^T MFMA (their latency)
-STAMP_BASE = 192 if FASTMAX else 184   # (the fast loop's second P buffer lives in v[176:191])
-_STAMP_BASE_DOC = 184                          # v[184:199]: previous clock, buckets 0..14 (free in the fast variant: the low halves of a split P live there)
-ABL = knob("P4_ABL", "")                                         # timing-only ablations, see dma_plan
-DMA_PRICE = int(knob("P4_DMA_PRICE", "30"))                      # issue cycles budgeted for one LDS-DMA piece
-DMA_GAPS_V = [int(x) for x in knob("P4_DMA_GAPS_V", "1,5,9,13").split(",")]      # QK^T gaps that carry the V(j+1) pieces
-DMA_GAPS_K = [int(x) for x in knob("P4_DMA_GAPS_K", "17,21,25,27").split(",")]   # ... and the K(j+2) pieces
+STAMP = knob("P4_STAMP", "0") or "0"    # diagnostic build: "3" = kernel totals (two clocks per wave, the production control flow) -> stamp_init, stamp_dump
+if STAMP not in ("0", "3"):
+    sys.exit(f"gen_fa3_fwd_p4.py: P4_STAMP={STAMP} -- 3 (kernel totals) is the only stamp mode")
+STAMP = int(STAMP)
+STAMP_BASE = 192            # v[192:207]: the stamps' registers (free in the fast variant; the parity variant keeps low halves of a split P there)
+MID_BARRIER_GAP = {128: 27, 64: 12}     # fast loop: the iteration's barrier sits INSIDE the PV phase, behind this MFMA gap (of 32 / 16; the last V^T read is issued
+                                        # by then), and the first K fragments of the next QK^T phase are requested right behind it -- their latency and the barrier
+                                        # skew run under the rest of PV(j).  Gaps 16..27 / 8..13 tried: 27 is worth +0.4..1 % over 20 at D = 128; at D = 64 gap 13 loses 2 %
+PRE_ISSUE = 24              # parity variant: issue cycles of the finish stream placed between the first K-fragment reads and the first QK^T MFMA (their latency)
+DMA_PRICE = 30              # issue cycles budgeted for one LDS-DMA piece
+DMA_GAPS = {128: ([1, 5, 9, 13], [17, 21, 25, 27]),     # by head dim: the QK^T gaps (of 32 / 16) that carry a wave's four / two pieces of
+            64: ([1, 5], [9, 13])}                      # V(j+1), and those that carry its pieces of K(j+2)
 NODIAG = "0x40000000"      # causal ragged kernels, nd_n / nd: the item has no diagonal tile (it lies behind its batch's seqlens_k cut)
 NEG_BIG = "0xf149f2ca"     # -1e30f
 NEG_INF = "0xff800000"
@@ -183,10 +168,6 @@ def vr(base, n=1):
 
 def ar(base, n=1):
     return f"a{base}" if n == 1 else f"a[{base}:{base + n - 1}]"
-
-
-def fr(base, n):            # a fragment-ring register range: accumulator file when the rings are 8 deep
-    return ar(base, n) if RING == 8 else vr(base, n)
 
 
 class Lgkm:
@@ -239,9 +220,11 @@ class Gen:
         #  row may come alive in a later tile (left padding).  Such a FRESH row keeps m c = 0, so that x = s c holds the score itself, and a
         #  negative limit in STV thr: the tile check then fires for it whatever its sums are (unless the tile's mask word is zero) and the
         #  fix-up gives it its first maximum.)
-        self.fast = bool(FASTMAX) and not split and (not kmask or bool(KMFAST))
-        self.ret = S('grow') if DIET else "s[58:59]"          # fix-up subroutine's return address (s[58:59] is a mask word of the ragged kernels)
-        self.mb = self.fast and bool(MB) and STAMP in (0, 3)      # (on the parity variant's SAFE bodies it buys nothing at D = 128 and costs 4 % at D = 64)
+        # The fast variant runs the fast loop (no row maximum inside the tile loop: see exp_block / fixup) with the iteration's barrier inside the PV
+        # phase (MID_BARRIER_GAP; on the parity variant's bodies that buys nothing at D = 128 and costs 4 % at D = 64); the parity
+        # variant keeps the defer-max loop (start_stream / finish_stream) and the barrier at the bottom of the iteration.
+        self.fast = not split
+        self.ret = S('grow')                   # fix-up subroutine's return address (the fast loop's check goes through VCC, so `grow` is free)
         assert not (kmask and STAMP), "the key-mask kernels keep their mask words where the stamps keep their clock (s[58:59], the dbg kernarg)"
         assert D in (64, 128)
         self.D, self.KS, self.DB = D, D // 16, D // 32                 # head dim, k-steps of QK^T, 32-wide d blocks of PV
@@ -252,13 +235,12 @@ class Gen:
         self.LDS_BYTES = 10 * self.TILE
         self.PPW = self.TILE // 4096                                    # 1-KiB DMA pieces per wave and image
         self.RB, self.CPR = 2 * D, D // 8                               # bytes and 16-byte chunks of a Q / O row
-        self.RING = min(RING, self.NKF)
+        assert RING <= min(self.NKF, self.NVF)
         self.mf = "v_mfma_f32_32x32x16_bf16" if dtype == "bf16" else "v_mfma_f32_32x32x16_f16"
         self.cvt = "v_cvt_pk_bf16_f32" if dtype == "bf16" else "v_cvt_pk_f16_f32"
         self.name = f"fa3_fwd_p4_{dtype}_d{D}_{'causal' if causal else 'full'}{'_km' if kmask else ('_kl' if klen else '')}_{'splitp_o32' if out32 else 'o16'}"
         self.main, self.ool, self.ool2, self.lstack = [], [], [], []
         self.L = self.main
-        self.abl_on = False
         self.uid = 0
 
     def OA(self, X, db, e=0):                  # accumulator register of O, strip X, d block db, element e
@@ -269,15 +251,6 @@ class Gen:
 
     # ---- emission helpers ------------------------------------------------------------------------------------------------
     def i(self, s):
-        if self.abl_on and ABL:            # TIMING-ONLY ablations of the FULL body (wrong results): drop one instruction class
-            op = s.split()[0]
-            drop = {"noadd": op == "v_add_f32", "noexp": op == "v_exp_f32", "nofma": op == "v_fma_f32", "nocvt": op.startswith("v_cvt_pk"),
-                    "nomax": op.startswith("v_max"), "nodma2": op.startswith("buffer_load"), "nolds": op.startswith("ds_read") or s.startswith("s_waitcnt lgkmcnt"),
-                    "noqk": op.startswith("v_mfma") and s.split()[1].startswith("v["), "nopv": op.startswith("v_mfma") and s.split()[1].startswith("a["),
-                    "nosoftmax": op in ("v_add_f32", "v_exp_f32", "v_fma_f32", "v_max3_f32", "v_max_f32", "v_mul_f32", "v_sub_f32", "v_mov_b32", "v_cndmask_b32",
-                                        "v_cmp_gt_f32", "v_permlane32_swap_b32", "s_nop", "s_or_b64") or op.startswith("v_cvt_pk")}
-            if any(drop.get(a, False) for a in ABL.split("+")):
-                return
         self.L.append("\t" + s)
 
     def lab(self, s):
@@ -308,25 +281,10 @@ class Gen:
         else:
             self.L = self.lstack.pop()
 
-    # ---- diagnostic stamps (P4_STAMP=1 at generation; never time such a build) -------------------------------------------------------
-    # a192 = previous s_memtime (low word), a[193 + k] = cycles accumulated in bucket k: 0 QK^T phase, 1 PV phase, 2 wait + barrier +
-    # stream bookkeeping, 3 item switch + prologue, 4 epilogue, 5 LAST bodies, 6 SKIP bodies, 7 FULL iterations (count), 8 items (count)
-    def stamp(self, k, count=None, fine=False):
-        if not STAMP or STAMP == 3 or (fine and STAMP == 2):
-            return
-        assert RING == 8, "stamps live in the VGPRs the 4-deep rings use"
-        if self.split:
-            return                             # ... and so do the low halves of a split P: the parity variant carries no stamps
-        t2 = vr(V_E[14])
-        self.i("s_memtime s[58:59]")
-        self.i("s_waitcnt lgkmcnt(0)")
-        SB = STAMP_BASE
-        self.i(f"v_sub_u32 {t2}, s58, v{SB}")
-        self.i(f"v_add_u32 v{SB + 1 + k}, v{SB + 1 + k}, {t2}")
-        self.i(f"v_mov_b32 v{SB}, s58")
-        if count is not None:
-            self.i(f"v_add_u32 v{SB + 1 + count}, 1, v{SB + 1 + count}")
-
+    # ---- diagnostic stamps (P4_STAMP=3 at generation: two clocks per wave around the production control flow; never time such a build)
+    # v[STAMP_BASE + 1 + k] = bucket k: 10 kernel cycles, 11 kernel time in 10-ns ticks, 13 XCC id, 14 HW_ID; the others stay zero
+    # (tools/p4_ab.py stamp_report reads exactly these).  The parity kernels keep the low halves of a split P in the same registers:
+    # their item loop overwrites the start clocks, so only the fast variant's stamps mean anything.
     def stamp_init(self):
         if not STAMP:
             return
@@ -440,7 +398,7 @@ class Gen:
     # ---- building blocks -------------------------------------------------------------------------------------------------
     def kread(self, slot, i):                 # K fragment i = (kb, ks) of the K tile in ring slot `slot` -> ring register i % 4
         kb, ks = i // self.KS, i % self.KS
-        return f"ds_read_b128 {fr(KFR(i), 4)}, {vr(KOFF(ks))} offset:{self.K_BASE + slot * self.TILE + kb * self.HALF}"
+        return f"ds_read_b128 {ar(KFR(i), 4)}, {vr(KOFF(ks))} offset:{self.K_BASE + slot * self.TILE + kb * self.HALF}"
 
     def vread(self, slot, idx):               # V^T fragment idx = (f, db): two transposed 8-byte reads (rows +0 / +8)
         f, db = idx // self.DB, idx % self.DB              # k-step f = (key block, 16-key half), d block db
@@ -449,8 +407,8 @@ class Gen:
         else:                                              # two keys per LDS row: the half enters the swizzle, so it has its own address registers
             ko, sel = slot * self.TILE + (f // 2) * self.HALF, 2 * (f & 1) + db
         b = VFR(idx)
-        return [f"ds_read_b64_tr_b16 {fr(b, 2)}, {vr(VOFF(sel, 0))} offset:{ko}",
-                f"ds_read_b64_tr_b16 {fr(b + 2, 2)}, {vr(VOFF(sel, 1))} offset:{ko}"]
+        return [f"ds_read_b64_tr_b16 {ar(b, 2)}, {vr(VOFF(sel, 0))} offset:{ko}",
+                f"ds_read_b64_tr_b16 {ar(b + 2, 2)}, {vr(VOFF(sel, 1))} offset:{ko}"]
 
     def dma(self, which, t):                  # piece t of this wave's four (M0 already points at the wave's 4 KiB of the slot)
         off, srd, so = (KDOFF(t), S("ksrd"), S("koff")) if which == 'K' else (VDOFF(t), S("vsrd"), S("voff"))
@@ -459,52 +417,24 @@ class Gen:
     def setm0(self, which, slot):             # M0 = this wave's 4 KiB of ring slot `slot` of the K / V ring  (clobbers SCC)
         return f"s_add_u32 m0, {S('w4k')}, {(self.K_BASE if which == 'k' else self.V_BASE) + slot * self.TILE}"
 
-    # softmax FINISH of strip X on buffer `buf`: the exponentials of key block 1 and all sixteen P dwords, as an in-order stream.
-    # The v_fma of element e+1 is issued ahead of the v_exp of element e and no two dependent adds are adjacent (a dependent VALU
-    # pair costs issue stalls: SQ_WAIT_INST_ANY was 15 % of the wave's cycles with fma -> exp and add -> add back to back).
+    # ---- the defer-max loop (parity variant: split P, fp32 store) ---------------------------------------------------------------------
+    # softmax FINISH of strip X on buffer `buf`: the exponentials of key block 1 and its eight P dwords (key block 0's are packed by
+    # the start stream), as an in-order stream.  The v_fma of element e+1 is issued ahead of the v_exp of element e and no two dependent
+    # adds are adjacent (a dependent VALU pair costs issue stalls: SQ_WAIT_INST_ANY was 15 % of the wave's cycles with fma -> exp and
+    # add -> add back to back).  (Row sums as v_pk_add_f32 on register pairs -- 32 instead of 64 instructions a tile -- ran 5-7 % SLOWER.)
     def finish_stream(self, X, buf, ps1=V_PS1, tmp=(V_T[2], V_T[3])):
         c1 = lambda k: vr(SBUF(buf, X, 1, k))
-        c0 = lambda k: vr(SBUF(buf, X, 0, k))
         mc, ps0, l = vr(STV(X, 'mc')), vr(STV(X, 'ps0')), vr(STV(X, 'l'))
         fma = lambda e: f"v_fma_f32 {c1(e)}, {c1(e)}, {ka('scale_log2')}, -{mc}"
-
-        def pack(i, x0, x1):
-            if self.split and PSTART and i < 8:      # (key block 0: packed by the start stream, see start_stream)
-                return []
-            return self.pack_p(X, i, x0, x1, tmp)
-        pk = PKADD and not self.split
-        if pk:                                   # sums two at a time: both halves of a register pair per instruction
-            acc = vr(PSP(X), 2)
-            o = [fma(0)]
-            for e in range(16):
-                if e < 15:
-                    o.append(fma(e + 1))
-                o.append(f"v_exp_f32 {c1(e)}, {c1(e)}")
-                if e == 0:
-                    o.append(f"v_pk_add_f32 {acc}, {acc}, {vr(SBUF(buf, X, 0, 14), 2)}")     # left over from the start
-                if e % 2 == 0:
-                    o += pack(e // 2, c0(e), c0(e + 1))
-                elif e >= 3:
-                    o += pack(8 + (e - 3) // 2, c1(e - 3), c1(e - 2))
-                    o.append(f"v_pk_add_f32 {acc}, {acc}, {vr(SBUF(buf, X, 1, e - 3), 2)}")
-            o += pack(15, c1(14), c1(15))
-            o.append(f"v_pk_add_f32 {acc}, {acc}, {vr(SBUF(buf, X, 1, 14), 2)}")
-            o.append("s_nop 0")
-            o.append(f"v_add_f32 {l}, {l}, {vr(PSP(X))}")
-            o.append(f"v_add_f32 {l}, {l}, {vr(PSP(X) + 1)}")
-            o.append(f"v_mov_b32 {vr(PSP(X))}, 0")
-            o.append(f"v_mov_b32 {vr(PSP(X) + 1)}, 0")
-            return o
+        pack = lambda i, x0, x1: self.pack_p(X, i, x0, x1, tmp)
         o = [fma(0)]
         for e in range(16):
             if e < 15:
                 o.append(fma(e + 1))
             o.append(f"v_exp_f32 {c1(e)}, {c1(e)}")
             if e == 0:
-                o.append(f"v_add_f32 {ps0}, {ps0}, {c0(15)}")      # left over from the start (its sums lag by one element)
-            if e % 2 == 0:
-                o += pack(e // 2, c0(e), c0(e + 1))
-            elif e >= 3:
+                o.append(f"v_add_f32 {ps0}, {ps0}, {vr(SBUF(buf, X, 0, 15))}")      # left over from the start (its sums lag by one element)
+            if e % 2 == 1 and e >= 3:
                 o += pack(8 + (e - 3) // 2, c1(e - 3), c1(e - 2))
             if e >= 3:
                 o.append(f"v_add_f32 {vr(ps1)}, {vr(ps1)}, {c1(e - 3)}")
@@ -520,22 +450,19 @@ class Gen:
         return o
 
     def pack_p(self, X, i, x0, x1, tmp):
-        """P dword i = the pair (x0, x1) in 16 bits; split P: also the pair of what the rounding left behind"""
-        r = [f"{self.cvt} {vr(PD(X, i))}, {x0}, {x1}"]
-        if self.split:
-            t0, t1, hi = vr(tmp[0]), vr(tmp[1]), vr(PD(X, i))
-            if self.dt == "bf16":
-                r += [f"v_lshlrev_b32 {t0}, 16, {hi}", f"v_and_b32 {t1}, 0xffff0000, {hi}"]
-            else:
-                r += [f"v_cvt_f32_f16 {t0}, {hi}", f"v_cvt_f32_f16_sdwa {t1}, {hi} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1"]
-            r += [f"v_sub_f32 {t0}, {x0}, {t0}", f"v_sub_f32 {t1}, {x1}, {t1}", f"{self.cvt} {vr(PDL(X, i))}, {t0}, {t1}"]
-        return r
+        """split P: dword i = the pair (x0, x1) in 16 bits, and the pair of what the rounding left behind"""
+        t0, t1, hi = vr(tmp[0]), vr(tmp[1]), vr(PD(X, i))
+        r = [f"{self.cvt} {hi}, {x0}, {x1}"]
+        if self.dt == "bf16":
+            r += [f"v_lshlrev_b32 {t0}, 16, {hi}", f"v_and_b32 {t1}, 0xffff0000, {hi}"]
+        else:
+            r += [f"v_cvt_f32_f16 {t0}, {hi}", f"v_cvt_f32_f16_sdwa {t1}, {hi} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1"]
+        return r + [f"v_sub_f32 {t0}, {x0}, {t0}", f"v_sub_f32 {t1}, {x1}, {t1}", f"{self.cvt} {vr(PDL(X, i))}, {t0}, {t1}"]
 
     # softmax START of strip X on buffer `buf`, step u = 0..15 (row max, defer-max update, exponentials of key block 0)
     def start_fill(self, X, buf, u, alt=False):
         """alt: a second set of temporaries (row max in V_PS1, V_T[2:4], the compare's mask in s[t2]) for a stream that is interleaved
         with the other strip's"""
-        n0 = lambda k: vr(SBUF(buf, X, 0, k))
         mx, m, l, mc, th, al, ps0 = vr(V_PS1 if alt else V_MX), *(vr(STV(X, f)) for f in ("m", "l", "mc", "thr", "al", "ps0"))
         t0, t1 = (vr(V_T[2]), vr(V_T[3])) if alt else (vr(V_T[0]), vr(V_T[1]))
         cc = S('t2') if alt else "vcc"
@@ -557,7 +484,7 @@ class Gen:
             # branch-free, per row: a max inside the headroom leaves m alone, and then alpha = exp2(0) = 1 exactly
             o += [f"v_cmp_gt_f32 {cc}, {mx}, {th}",
                   f"s_or_b64 {S('grow')}, {S('grow')}, {cc}",
-                  ("s_nop 0" if (PKADD and not self.split) else f"v_mov_b32 {ps0}, 0"),
+                  f"v_mov_b32 {ps0}, 0",
                   f"v_cndmask_b32 {t0}, {m}, {mx}, {cc}",                 # m_new
                   f"v_sub_f32 {t1}, {m}, {t0}",
                   f"v_mul_f32 {t1}, {ka('scale_log2')}, {t1}",
@@ -566,8 +493,6 @@ class Gen:
                   f"v_add_f32 {th}, {ka('thr')}, {t0}",
                   f"v_mul_f32 {mc}, {ka('scale_log2')}, {t0}",
                   f"v_mul_f32 {l}, {l}, {al}"]
-        else:
-            raise ValueError("u >= 5: see start_stream")
         return o
 
     def start_stream(self, X, buf, alt=False):
@@ -584,20 +509,17 @@ class Gen:
             if e < 15:
                 o.append(fma(e + 1))
             o.append(f"v_exp_f32 {n0(e)}, {n0(e)}")
-            if PKADD and not self.split:
-                if e >= 2 and e % 2 == 0:         # the pair (e-2, e-1); the last pair is added by the finish
-                    o.append(f"v_pk_add_f32 {vr(PSP(X), 2)}, {vr(PSP(X), 2)}, {vr(SBUF(buf, X, 0, e - 2), 2)}")
-            elif e >= 1:
+            if e >= 1:
                 o.append(f"v_add_f32 {ps0}, {ps0}, {n0(e - 1)}")
         if alt:
             o.append(f"v_mov_b32 {vr(V_PS1)}, 0")         # (it stood in for the row max)
-        if self.split and PSTART:
-            # key block 0's P dwords (hi and lo), behind the PV MFMAs of k-steps 0 / 1 that still read the previous tile's (marker: pack())
-            tmp = (V_T[2], V_T[3]) if alt else (V_T[0], V_T[1])
-            o.append(f"@gap {4 * 2 * self.DB + 1}")
-            o.append("s_nop 0")                            # (the last v_exp above and its consumer below)
-            for k in range(8):
-                o += self.pack_p(X, k, n0(2 * k), n0(2 * k + 1), tmp)
+        # key block 0's P dwords (hi and lo) are packed HERE, in the second half of the PV phase -- behind the PV MFMAs of k-steps 0 / 1
+        # that still read the previous tile's (marker: pack()) -- not by the finish: the QK^T phase carried 330 instructions in 32 gaps
+        tmp = (V_T[2], V_T[3]) if alt else (V_T[0], V_T[1])
+        o.append(f"@gap {4 * 2 * self.DB + 1}")
+        o.append("s_nop 0")                                # (the last v_exp above and its consumer below)
+        for k in range(8):
+            o += self.pack_p(X, k, n0(2 * k), n0(2 * k + 1), tmp)
         return o
 
     # ---- the fast loop (self.fast): no row maximum inside the tile loop ------------------------------------------------------------
@@ -605,9 +527,9 @@ class Gen:
     # it only to learn that it has NOT outgrown its headroom -- 16 v_max3 + a shuffle + an 11-instruction update per strip and tile.
     # Here a tile's exponentials are simply taken against the maximum the item's tile 0 established (start_fast with_max): the scaled
     # score x = s c - m c overwrites s and STAYS in the S buffer, exp2(x) goes to a scratch register, from there into the row sum and
-    # into the packed P.  One compare per strip and tile (a lane's sums of the tile against 2^14: then no weight of it exceeds 2^14 --
-    # fp16-safe, and far below anything fp32 sums care about) feeds the wave-uniform `grow` mask; a set bit sends the wave to fixup(),
-    # which has every x of the tile at hand and redoes it exactly.  60 vector instructions fewer per tile, bit-identical to the
+    # into the packed P.  One compare per tile for both strips (tile_check: a lane's block sums of the tile against 2^14: then no weight
+    # of it exceeds 2^14 -- fp16-safe, and far below anything fp32 sums care about) and one s_cbranch_vccnz (fix_check) send the wave to
+    # fixup(), which has every x of the tile at hand and redoes it exactly.  60 vector instructions fewer per tile, bit-identical to the
     # defer-max loop while no row outgrows its tile-0 maximum by 2^8.
     def PDX(self, X, b, i):
         """P dword i of the tile that lives in S buffer b"""
@@ -627,9 +549,9 @@ class Gen:
             if e < 15 and not scaled:
                 o.append(fma(e + 1))
             o.append(f"v_exp_f32 {t(e)}, {c(e)}")
-            if e == 2 and DIET:
+            if e == 2:
                 o.append(f"v_add_f32 {ps}, {t(0)}, {t(1)}")           # (starts the sum: no zeroing, and 0 + t0 = t0 exactly -- the same bits)
-            elif e >= (3 if DIET else 1):
+            elif e >= 3:
                 o.append(f"v_add_f32 {ps}, {ps}, {t(e - 1)}")
             if e % 2 == 1 and e >= 3:
                 o.append(pack((e - 3) // 2))
@@ -637,22 +559,14 @@ class Gen:
         o.append(pack(7))
         return o
 
-    def finish_fast(self, X, b, alt=False):
-        """key block 1 of the tile in S buffer b (+ without DIET: the strip's own check)"""
-        o = self.exp_block(X, b, 1, vr(PS1(X)))
-        if not DIET:
-            ps0, ps1, lim, tt = vr(STV(X, 'ps0')), vr(PS1(X)), vr(STV(X, 'thr')), vr(V_T[1] if alt else V_T[0])
-            cc = S('t2') if alt else "vcc"
-            o += [f"v_max_f32 {tt}, {ps0}, {ps1}",
-                  f"v_cmp_nge_f32 {cc}, {lim}, {tt}",                  # not (2^14 >= sum): too large, or not a number
-                  f"s_or_b64 {S('grow')}, {S('grow')}, {cc}"]
-        return o
+    def finish_fast(self, b):
+        """the finish of the tile in S buffer b: key block 1 of both strips, interleaved instruction by instruction (twice the distance
+        between dependent instructions: -0.7 % cycles), then the tile's check"""
+        return self.interleave(*(self.exp_block(X, b, 1, vr(PS1(X))) for X in "AB")) + self.tile_check()
 
     def tile_check(self):
         """the tile's check, both strips at once: the largest of a lane's four block sums against 2^14 (STV thr holds it) -> VCC, for
         fix_check's s_cbranch_vccnz (nothing between the two writes VCC)"""
-        if not DIET:
-            return []
         tt = vr(V_T[0])
         if self.kmask:                         # the limit is a row's own (negative while the row is fresh)
             tb = vr(V_T[1])
@@ -666,9 +580,7 @@ class Gen:
     def lupd(self, X):
         """the tile's two block sums into l (one phase after the check, so that fixup() finds l without them), in the defer-max loop's order"""
         l, ps0, ps1 = vr(STV(X, 'l')), vr(STV(X, 'ps0')), vr(PS1(X))
-        if DIET:                               # (every block sum starts afresh with t0 + t1: nothing to zero)
-            return [f"v_add_f32 {l}, {l}, {ps0}", f"v_add_f32 {l}, {l}, {ps1}"]
-        return [f"v_add_f32 {l}, {l}, {ps0}", f"v_mov_b32 {ps0}, 0", f"v_add_f32 {l}, {l}, {ps1}", f"v_mov_b32 {ps1}, 0"]
+        return [f"v_add_f32 {l}, {l}, {ps0}", f"v_add_f32 {l}, {l}, {ps1}"]      # (every block sum starts afresh with t0 + t1: nothing to zero)
 
     def start_fast(self, X, b, with_max=False):
         """key block 0 of the tile in S buffer b.  with_max: an item's tile 0 -- its row maximum (both key blocks) becomes the item's m."""
@@ -695,7 +607,7 @@ class Gen:
         return o
 
     def fixup(self, b):
-        """Subroutine (s_swappc return address in s[58:59]): some lane of the wave found a tile sum past 2^14 in the tile of S buffer b.
+        """Subroutine (s_swappc return address in self.ret): some lane of the wave found a tile sum past 2^14 in the tile of S buffer b.
         Per row: the maximum of its scaled scores x; if it outgrew the running maximum by more than 2^8 it becomes the new one (x -= it,
         m c += it, l and O scaled by exp2(-it)); every weight of the tile is taken again from its x, both strips, exactly as
         exp_block does (rows that keep their maximum get the same bits again).  O has the tiles before this one, l likewise (lupd)."""
@@ -730,7 +642,7 @@ class Gen:
             for kb, ps in ((0, vr(STV(X, 'ps0'))), (1, vr(PS1(X)))):
                 self.i(f"v_mov_b32 {ps}, 0")
                 self.emit(self.exp_block(X, b, kb, ps, scaled=True))
-        self.rescale(clear=not DIET)               # O *= alpha, both strips (the diet loop keeps its return address in `grow`)
+        self.rescale(clear=False)                  # O *= alpha, both strips (`grow` holds the return address)
         for X in "AB":
             self.i(f"v_mov_b32 {vr(STV(X, 'al'))}, 1.0")
         self.i(f"s_setpc_b64 {self.ret}")
@@ -738,11 +650,7 @@ class Gen:
     def fix_check(self, b):
         """behind the phase that finished the tile of S buffer b: call fixup(b) if a lane asked for it"""
         lc, lb = self.ul("fix"), self.ul("fixed")
-        if DIET:
-            self.i(f"s_cbranch_vccnz {lc}")      # (tile_check's compare)
-        else:
-            self.i(f"s_cmp_lg_u64 {S('grow')}, 0")
-            self.i(f"s_cbranch_scc1 {lc}")
+        self.i(f"s_cbranch_vccnz {lc}")          # (tile_check's compare)
         self.lab(lb)
         self.out_of_line(True)
         self.lab(lc)
@@ -768,23 +676,23 @@ class Gen:
     def qk_mfma(self, buf, X, i):
         kb, ks = i // self.KS, i % self.KS
         acc = vr(SBUF(buf, X, kb, 0), 16)
-        return f"{self.mf} {acc}, {fr(KFR(i), 4)}, {ar(self.QA(X, ks), 4)}, {'0' if ks == 0 else acc}"
+        return f"{self.mf} {acc}, {ar(KFR(i), 4)}, {ar(self.QA(X, ks), 4)}, {'0' if ks == 0 else acc}"
 
     def pv_mfma(self, X, idx, lo=False):
         f, db = idx // self.DB, idx % self.DB
         acc = ar(self.OA(X, db), 16)
         pd = PDL(X, 4 * f) if lo else self.PDX(X, self.pv_buf, 4 * f)
-        return f"{self.mf} {acc}, {fr(VFR(idx), 4)}, {vr(pd, 4)}, {acc}"
+        return f"{self.mf} {acc}, {ar(VFR(idx), 4)}, {vr(pd, 4)}, {acc}"
 
     # ---- phases ----------------------------------------------------------------------------------------------------------
     def phase_qk(self, p, fillers, dma_at, lg=None, pre=(), tail_vreads=None, rec=None):
         """QK^T(j+1) into buffer 1-p from K slot 1-p; fillers[g] = instructions for the gap behind MFMA g (a fragment feeds strip A,
         then strip B).  tail_vreads = V slot whose first RING V^T fragments are requested in the last gaps (after the last K read),
         for the PV phase that follows.  rec (dry run): gets the issue cycles of every gap's fixed content instead of fillers."""
-        nb, slot, R, NF = 1 - p, 1 - p, self.RING, self.NKF
+        nb, slot, R, NF = 1 - p, 1 - p, RING, self.NKF
         ngaps = 2 * NF
         lg = lg or Lgkm()
-        if ('k', 0) not in lg.q:                 # (mid-barrier loop: the iteration before requested them -- kprefetch -- and the caller registered them)
+        if ('k', 0) not in lg.q:                 # (fast loop: the iteration before requested them -- kprefetch -- and the caller registered them)
             for i in range(R):
                 self.i(self.kread(slot, i))
                 lg.issue(('k', i))
@@ -793,7 +701,7 @@ class Gen:
             i, X = hs // 2, 'AB'[hs % 2]
             mark = len(self.L)
             if hs % 2 == 0 and i % WAITN == 0:
-                # (seam: the successor's Q fragments are in flight too -- older than the K reads, or, in the mid-barrier loop, younger)
+                # (seam: the successor's Q fragments are in flight too -- older than the K reads, or, in the fast loop, younger)
                 w = lg.need([('k', i + x) for x in range(WAITN)] + [('q', Y, i + x) for Y in "AB" for x in range(WAITN)])
                 if w:
                     self.i(w)
@@ -803,8 +711,8 @@ class Gen:
                     if f < NF:
                         self.i(self.kread(slot, f))
                         lg.issue(('k', f))
-            if tail_vreads is not None and hs >= ngaps - min(R, self.NVF):
-                n = hs - (ngaps - min(R, self.NVF))
+            if tail_vreads is not None and hs >= ngaps - R:
+                n = hs - (ngaps - R)
                 for k, x in enumerate(self.vread(tail_vreads, n)):
                     self.i(x)
                     lg.issue(('v', n, k))
@@ -816,20 +724,20 @@ class Gen:
         return lg
 
     def kprefetch_lg(self):
-        """tracker of a QK^T phase whose first K fragments are in flight since the iteration before (mid-barrier loop)"""
+        """tracker of a QK^T phase whose first K fragments are in flight since the iteration before (fast loop)"""
         lg = Lgkm()
-        for i in range(self.RING):
+        for i in range(RING):
             lg.issue(('k', i))
         return lg
 
     def kprefetch(self, p):
         """the first K fragments of the NEXT iteration's QK^T phase (parity 1-p: K slot p)"""
-        return [self.kread(p, i) for i in range(self.RING)]
+        return [self.kread(p, i) for i in range(RING)]
 
     def phase_pv(self, p, fillers, dma_at, strips="AB", lg=None, preissued=False, rec=None, mid=None):
         """PV(j): P dwords x V slot p -> O; one gap per MFMA (split P: a fragment feeds the hi pass of every strip, then the lo pass);
         fillers as above.  rec (dry run): gets the issue cycles of every gap's fixed content instead of emitting fillers."""
-        slot, R, NF = p, min(self.RING, self.NVF), self.NVF
+        slot, R, NF = p, RING, self.NVF
         self.pv_buf = p                        # (fast loop: the tile's P dwords 0..7 have a buffer per S buffer)
         lg = lg or Lgkm()
         if not preissued:
@@ -856,11 +764,11 @@ class Gen:
                                 lg.issue(('v', f, k))
                 self.emit(dma_at.get(hs, []))
                 if mid is not None and hs == mid['gap']:
-                    # the iteration's barrier (mid-barrier loop): every V^T read of this tile has been issued (all of them are behind
+                    # the iteration's barrier (fast loop): every V^T read of this tile has been issued (all of them are behind
                     # MFMA 15 at the latest) and is waited for here, so the next iteration's DMA may overwrite V slot p; this wave's own
                     # DMA pieces of the iteration are waited for by `inline`; behind the barrier K(j+2) is visible: its first fragments
                     # are requested at once, two a gap, and arrive under the MFMAs that are left
-                    assert all(t[0] != 'v' or t[1] < NF for t in lg.q) and idx + R >= NF - 1 or True
+                    assert (idx, n) >= (NF - R - 1, len(passes) - 1), "a V^T read of this tile would follow the barrier"
                     self.i("s_waitcnt lgkmcnt(0)")
                     lg.q = []
                     self.emit(mid['inline'])
@@ -929,7 +837,7 @@ class Gen:
 
     def stream_bottom(self, p, barrier=True):
         """Q pieces of the next item (first two iterations of an item; one at D = 64), the counted wait, the barrier (barrier=False: the
-        mid-barrier loop emits this in front of its own, inside the PV phase)."""
+        fast loop's FULL body emits this in front of its own barrier, inside the PV phase)."""
         lq, lb = self.ul("q"), self.ul("bar")
         self.i(f"s_add_u32 {S('koff')}, {S('koff')}, {S('ktile')}")
         self.i(f"s_add_u32 {S('voff')}, {S('voff')}, {S('vtile')}")
@@ -942,16 +850,13 @@ class Gen:
             self.i(f"s_sub_u32 {ka('pad')}, {ka('pad')}, 64")
         self.i(f"s_cmp_lg_u32 {S('qrem')}, 0")
         self.i(f"s_cbranch_scc1 {lq}")
-        self.stamp(2, fine=True)
-        self.i("s_waitcnt vmcnt(0)")
-        self.stamp(9, fine=True)                # bucket 9: the wait for this wave's own DMA pieces
+        self.i("s_waitcnt vmcnt(0)")            # this wave's own DMA pieces
         self.lab(lb)
         if self.kmask:
             self.i(self.mask_word(p))           # tile j+2 -> MK((j+2) & 1) = MK(p)
             self.km_len_and(p)
         if barrier:
             self.i("s_barrier")
-        self.stamp(12, fine=True)               # bucket 12: the barrier
         self.out_of_line(True)
         self.lab(lq)
         self.q_group()
@@ -974,25 +879,21 @@ class Gen:
     def dma_plan(self, p, gaps_v, gaps_k):
         """V(j+1) -> V slot 1-p, K(j+2) -> K slot p: {gap: [instructions]}"""
         d = {}
-        def piece(which, n):
-            if not ABL:
-                return [self.dma(which, n)]
-            # TIMING-ONLY ablations (wrong results): "nodma" = no wave issues its pieces, "dma_w0" = only wave 0 does
-            lab = self.ul("abl")
-            if ABL == "nodma":
-                return [f"s_cmp_eq_u32 {S('wave')}, 99", f"s_cbranch_scc0 {lab}", self.dma(which, n), lab + ":"]
-            return [f"s_cmp_eq_u32 {S('wave')}, 0", f"s_cbranch_scc0 {lab}", self.dma(which, n), lab + ":"]
-        for n, g in enumerate(gaps_v):
-            d.setdefault(g, [])
-            if n == 0:
-                d[g] += [self.setm0('v', 1 - p), "s_nop 0"]          # M0 write -> LDS-DMA: one wait state
-            d[g] += piece('V', n)
-        for n, g in enumerate(gaps_k):
-            d.setdefault(g, [])
-            if n == 0:
-                d[g] += [self.setm0('k', p), "s_nop 0"]
-            d[g] += piece('K', n)
+        for which, slot, gaps in (('V', 1 - p, gaps_v), ('K', p, gaps_k)):
+            for n, g in enumerate(gaps):
+                d.setdefault(g, [])
+                if n == 0:
+                    d[g] += [self.setm0(which.lower(), slot), "s_nop 0"]      # M0 write -> LDS-DMA: one wait state
+                d[g].append(self.dma(which, n))
         return d
+
+    def dma_plan_qk(self, p):
+        """... over the gaps of a QK^T phase: the wave's pieces of V early, of K late"""
+        return self.dma_plan(p, *DMA_GAPS[self.D])
+
+    def feed_rings(self, p):
+        """... all at once: a body without MFMA gaps to put them in"""
+        self.emit(self.dma_plan(p, [0] * self.PPW, [0] * self.PPW)[0])
 
     # ---- gap packing -------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -1039,28 +940,19 @@ class Gen:
     def body_full(self, p, lean=False):
         """lean: an iteration the caller knows to be far from the item's ends (no diagonal tile, see the loop in kernel())"""
         self.cm(f"FULL body, parity {p}{' (lean loop)' if lean else ''}: QK^T(j+1) || softmax finish(j);  PV(j) || softmax start(j+1)")
-        self.stamp(2)
-        self.abl_on = True
         # ---- phase A: the finish of both strips as ONE in-order stream, sliced evenly over the gaps around their fixed content
-        if self.fast:
-            fin = self.interleave(self.finish_fast('A', p), self.finish_fast('B', p, alt=True)) + self.tile_check()
-        elif ILV:                              # the two strips' streams interleaved: twice the distance between dependent instructions (-0.7 % cycles)
+        if self.fast:                          # (K(j+1)'s first fragments are in flight since the barrier inside PV(j-1))
+            fin, pre, lg = self.finish_fast(p), [], self.kprefetch_lg()
+        else:                                  # the two strips' streams interleaved: twice the distance between dependent instructions (-0.7 % cycles)
             fin = self.interleave(self.finish_stream('A', p), self.finish_stream('B', p, ps1=V_MX, tmp=(V_E[6], V_E[7])))
             fin = [f"v_mov_b32 {vr(V_MX)}, 0"] + fin
-        else:
-            fin = self.finish_stream('A', p) + self.finish_stream('B', p)
-        n = 2 * self.NKF                       # gaps of the QK^T phase; the wave's PPW pieces of V early, of K late
-        gv = [g * n // 32 for g in DMA_GAPS_V][:self.PPW] if self.PPW == 4 else [1 * n // 16, 5 * n // 16]
-        gk = [g * n // 32 for g in DMA_GAPS_K][:self.PPW] if self.PPW == 4 else [9 * n // 16, 13 * n // 16]
-        dma = self.dma_plan(p, gv, gk)
-        npre = 0
-        while sum(self.price(x) for x in fin[:npre + 1]) <= (0 if self.mb else PRE):
-            npre += 1
-        pre, fin = fin[:npre], fin[npre:]
-        lg = self.run_phase(self.phase_qk, fin, self.kprefetch_lg() if self.mb else Lgkm(), p=p, dma_at=dma, pre=pre, tail_vreads=p)
+            npre = 0                           # what of it fits under the latency of the first K-fragment reads goes in front of the first MFMA
+            while sum(self.price(x) for x in fin[:npre + 1]) <= PRE_ISSUE:
+                npre += 1
+            pre, fin, lg = fin[:npre], fin[npre:], Lgkm()
+        lg = self.run_phase(self.phase_qk, fin, lg, p=p, dma_at=self.dma_plan_qk(p), pre=pre, tail_vreads=p)
         if self.fast:
             self.fix_check(p)                  # tile j is complete: its check (before PV(j) takes its P)
-        self.stamp(0, fine=True)
         if not (lean and self.klen):           # (klen: a lean iteration is that far from the last tiles that all its keys exist)
             self.mask_keys(1 - p, 1 - p)       # tile j+1: buffer 1-p, word MK((j+1) & 1)
         if self.causal and not lean:           # the diagonal tile of this wave is tile wnt-1 = j+1  <=>  wrem == 1
@@ -1074,68 +966,50 @@ class Gen:
             self.i(f"s_branch {lr}")
             self.out_of_line(False)
         # ---- phase B: the start of both strips, same treatment
-        if self.fast:
-            sta = self.interleave(self.start_fast('A', 1 - p), self.start_fast('B', 1 - p))
-        elif ILV:
+        if not self.fast:
             sta = self.interleave(self.start_stream('A', 1 - p), self.start_stream('B', 1 - p, alt=True))
-        else:
-            sta = self.start_stream('A', 1 - p) + self.start_stream('B', 1 - p)
-        mid = None
-        if self.mb:                            # the iteration's bookkeeping, counted wait and barrier inside PV(j); K(j+2)'s first fragments behind it
-            if lean:
-                inline = [f"s_add_u32 {S('koff')}, {S('koff')}, {S('ktile')}", f"s_add_u32 {S('voff')}, {S('voff')}, {S('vtile')}"] + \
-                         ([f"s_add_u32 {ka('pad')}, {ka('pad')}, 64"] if self.kmask else []) + ["s_waitcnt vmcnt(0)"] + \
-                         ([self.mask_word(p)] if self.kmask else [])
-            else:
-                inline = self.capture(lambda: self.stream_bottom(p, barrier=False))
-            mid = dict(gap=MBGAP or (27 if self.D == 128 else 12), inline=inline, kreads=self.kprefetch(p))
-        self.run_phase(self.phase_pv, sta, lg, p=p, dma_at={}, preissued=True, mid=mid)
-        self.abl_on = False
-        self.stamp(1, count=7)
-        if self.fast:
+            self.run_phase(self.phase_pv, sta, lg, p=p, dma_at={}, preissued=True)
+            # pending O rescale (rare: defer-max)
+            lr, lb = self.ul("rescale"), self.ul("rescaled")
+            self.i(f"s_cmp_lg_u64 {S('grow')}, 0")
+            self.i(f"s_cbranch_scc1 {lr}")
+            self.lab(lb)
+            self.out_of_line(True)
+            self.lab(lr)
+            self.rescale()
+            self.i(f"s_branch {lb}")
+            self.out_of_line(False)
             return
-        # pending O rescale (rare: defer-max)
-        lr, lb = self.ul("rescale"), self.ul("rescaled")
-        self.i(f"s_cmp_lg_u64 {S('grow')}, 0")
-        self.i(f"s_cbranch_scc1 {lr}")
-        self.lab(lb)
-        self.out_of_line(True)
-        self.lab(lr)
-        self.rescale()
-        self.i(f"s_branch {lb}")
-        self.out_of_line(False)
+        # fast loop: the iteration's bookkeeping, counted wait and barrier inside PV(j); K(j+2)'s first fragments behind it
+        sta = self.interleave(self.start_fast('A', 1 - p), self.start_fast('B', 1 - p))
+        if lean:
+            inline = [f"s_add_u32 {S('koff')}, {S('koff')}, {S('ktile')}", f"s_add_u32 {S('voff')}, {S('voff')}, {S('vtile')}"] + \
+                     ([f"s_add_u32 {ka('pad')}, {ka('pad')}, 64"] if self.kmask else []) + ["s_waitcnt vmcnt(0)"] + \
+                     ([self.mask_word(p)] if self.kmask else [])
+        else:
+            inline = self.capture(lambda: self.stream_bottom(p, barrier=False))
+        mid = dict(gap=MID_BARRIER_GAP[self.D], inline=inline, kreads=self.kprefetch(p))
+        self.run_phase(self.phase_pv, sta, lg, p=p, dma_at={}, preissued=True, mid=mid)
 
     def body_last(self, p):
         self.cm(f"LAST body, parity {p}: this wave's last tile -- finish(j), PV(j); nothing to prefetch for the wave itself")
-        self.stamp(2)
         d = self.dma_plan(p, [2 * t for t in range(self.PPW)], [2 * self.PPW + 2 * t for t in range(self.PPW)])    # PV(A) has >= NVF gaps
         if self.fast:                          # both finishes, the tile's check, its sums into l; then PV(j) of both strips with the DMA pieces
-            self.emit(self.interleave(self.finish_fast('A', p), self.finish_fast('B', p, alt=True)) + self.tile_check())
+            self.emit(self.finish_fast(p))
             self.fix_check(p)
             self.emit(self.lupd('A') + self.lupd('B'))
             self.i("s_nop 1")
             self.phase_pv(p, [[] for _ in range(2 * self.NVF)], d, strips="AB")
-            self.stamp(5)
             return
         self.emit(self.finish_stream('A', p))
         self.i("s_nop 1")
         self.run_phase(self.phase_pv, self.finish_stream('B', p), Lgkm(), p=p, dma_at=d, strips="A")
         self.i("s_nop 1")
         self.phase_pv(p, [[] for _ in range(2 * self.NVF)], {}, strips="B")
-        self.stamp(5)
 
     def body_skip(self, p):
         self.cm(f"SKIP body, parity {p}: this wave is past its last tile of the item -- keep the rings fed")
-        self.stamp(2)
-        self.i(self.setm0('v', 1 - p))
-        self.i("s_nop 0")
-        for t in range(self.PPW):
-            self.i(self.dma('V', t))
-        self.i(self.setm0('k', p))
-        self.i("s_nop 0")
-        for t in range(self.PPW):
-            self.i(self.dma('K', t))
-        self.stamp(6)
+        self.feed_rings(p)
 
     def mask_diag(self, buf):
         """Causal mask of the wave's diagonal tile (key base = the wave's first row): key 32 kb + kidx(e) + 4h is visible to row
@@ -1205,8 +1079,8 @@ class Gen:
         if self.causal:
             self.i(f"s_sub_u32 {t3}, {ka('NB')}, 1")
             self.i(f"s_sub_u32 {t3}, {t3}, {t1}")                      # heavy block NB-1-p
-            self.i(f"s_cmp_eq_u32 {S('n_sub')}, {1 if LIGHT1 else 0}")
-            self.i(f"s_cselect_b32 {t1}, {t3}, {t1}")                  # qblk (LIGHT1: a unit's light block first, then its heavy one)
+            self.i(f"s_cmp_eq_u32 {S('n_sub')}, 0")
+            self.i(f"s_cselect_b32 {t1}, {t3}, {t1}")                  # qblk: a unit's heavy block first, then its light one
             self.i(f"s_add_u32 {t3}, {t1}, 1")
             self.i(f"s_lshl_b32 {S('n_nt')}, {t3}, 2")                 # nt = 4 (qblk + 1)
         else:
@@ -1390,15 +1264,11 @@ class Gen:
                 if lg is not None:
                     lg.issue(('q', X, ks))
 
-    def state_reset(self, emit=True):
-        o = []
+    def state_reset(self):
         if self.fast:                          # (m c comes from the item's tile 0: start_fast with_max; STV thr holds the constant 2^14)
-            for X in "AB":
-                o += [f"v_mov_b32 {vr(STV(X, 'l'))}, 0", f"v_mov_b32 {vr(STV(X, 'ps0'))}, 0", f"v_mov_b32 {vr(PS1(X))}, 0",
-                      f"v_mov_b32 {vr(STV(X, 'al'))}, 1.0"]
-            if emit:
-                self.emit(o)
-            return o
+            return [x for X in "AB" for x in (f"v_mov_b32 {vr(STV(X, 'l'))}, 0", f"v_mov_b32 {vr(STV(X, 'ps0'))}, 0",
+                                              f"v_mov_b32 {vr(PS1(X))}, 0", f"v_mov_b32 {vr(STV(X, 'al'))}, 1.0")]
+        o = []
         for X in "AB":
             o += [f"v_mov_b32 {vr(STV(X, 'm'))}, {NEG_BIG}",
                   f"v_mov_b32 {vr(STV(X, 'thr'))}, {NEG_BIG}",
@@ -1406,13 +1276,7 @@ class Gen:
                   f"v_mov_b32 {vr(STV(X, 'l'))}, 0",
                   f"v_mov_b32 {vr(STV(X, 'ps0'))}, 0",
                   f"v_mov_b32 {vr(STV(X, 'al'))}, 1.0"]
-        o.append(f"v_mov_b32 {vr(V_PS1)}, 0")
-        if PKADD and not self.split:
-            for X in "AB":
-                o += [f"v_mov_b32 {vr(PSP(X))}, 0", f"v_mov_b32 {vr(PSP(X) + 1)}, 0"]
-        if emit:
-            self.emit(o)
-        return o
+        return o + [f"v_mov_b32 {vr(V_PS1)}, 0"]
 
     def tile0_diag(self, cond):
         """Causal: tile 0 is this wave's diagonal tile when its tile count is 1; `cond` = instructions that leave SCC = 1 in that case."""
@@ -1439,7 +1303,7 @@ class Gen:
         park = []
         for X in "AB":
             park += [f"v_mov_b32 {vr(SV(X, 'l'))}, {vr(STV(X, 'l'))}", f"v_mov_b32 {vr(SV(X, 'mc'))}, {vr(STV(X, 'mc'))}"]
-        park += self.state_reset(emit=False)
+        park += self.state_reset()
         if self.fast:
             sta = self.start_fast('A', 0, with_max=True) + self.start_fast('B', 0, with_max=True)
         else:
@@ -1448,35 +1312,19 @@ class Gen:
         # tile 0 of the successor is this wave's diagonal tile iff its tile count is 1: nt_n - 3 + wave == 1
         cond = [f"s_add_u32 {S('t0')}, {S('nt_n')}, {S('wave')}"] + ([f"s_add_u32 {S('t0')}, {S('t0')}, {self.nd_n}"] if self.cl else []) + \
                [f"s_cmp_eq_u32 {S('t0')}, 4"]
-        lg = self.kprefetch_lg() if self.mb else Lgkm()      # (mid-barrier loop: K_next(0)'s first fragments were requested an iteration ago)
+        lg = self.kprefetch_lg() if self.fast else Lgkm()    # (fast loop: K_next(0)'s first fragments were requested an iteration ago)
         if full:
-            self.abl_on = True
             self.q_fragments(lg)
-            if self.fast:
-                fin = self.interleave(self.finish_fast('A', p), self.finish_fast('B', p, alt=True)) + self.tile_check()
-            else:
-                fin = self.finish_stream('A', p) + self.finish_stream('B', p)
-            n = 2 * self.NKF
-            gv = [g * n // 32 for g in DMA_GAPS_V][:self.PPW] if self.PPW == 4 else [1 * n // 16, 5 * n // 16]
-            gk = [g * n // 32 for g in DMA_GAPS_K][:self.PPW] if self.PPW == 4 else [9 * n // 16, 13 * n // 16]
-            dma = self.dma_plan(p, gv, gk)
-            lg = self.run_phase(self.phase_qk, fin, lg, p=p, dma_at=dma, tail_vreads=p)
+            fin = self.finish_fast(p) if self.fast else self.finish_stream('A', p) + self.finish_stream('B', p)
+            lg = self.run_phase(self.phase_qk, fin, lg, p=p, dma_at=self.dma_plan_qk(p), tail_vreads=p)
             if self.fast:                      # the ending item's last tile: its check (VCC is tile_check's), then its sums into l before l is parked
                 self.fix_check(p)
                 park = self.lupd('A') + self.lupd('B') + park
             self.mask_keys(0, 0)
             self.tile0_diag(cond)
             self.run_phase(self.phase_pv, park + sta + unit, lg, p=p, dma_at={}, preissued=True)
-            self.abl_on = False
         else:
-            self.i(self.setm0('v', 1 - p))
-            self.i("s_nop 0")
-            for t in range(self.PPW):
-                self.i(self.dma('V', t))
-            self.i(self.setm0('k', p))
-            self.i("s_nop 0")
-            for t in range(self.PPW):
-                self.i(self.dma('K', t))
+            self.feed_rings(p)
             self.q_fragments(lg)
             self.emit(park)
             self.phase_qk(p, [[] for _ in range(2 * self.NKF)], {}, lg=lg)
@@ -1493,7 +1341,7 @@ class Gen:
         # this item's Q pieces: everything but the previous item's output stores (issued after them: 16, or 32 of the fp32 epilogue)
         self.i(f"s_waitcnt vmcnt({(8 if self.out32 else 4) * self.DB})")
         self.q_fragments()
-        self.state_reset()
+        self.emit(self.state_reset())
         self.i("s_waitcnt lgkmcnt(0)")
         # QK^T(0) from K slot 0 into buffer 0; four O zeros per gap
         self.zero_o()
@@ -1624,8 +1472,7 @@ class Gen:
                 self.i(f"s_lshl_b32 {S('t0')}, {ka('o_ss')}, 5")                   # strip B: 32 rows further
             for k in range(NI):
                 self.i(f"s_waitcnt lgkmcnt({NI - 1 - k})")
-                if not (saved and "nostore" in ABL):      # (TIMING-ONLY ablation: the seam path's epilogue without its output stores)
-                    self.i(f"buffer_store_dwordx4 {vr(x[k], 4)}, {vr(gofs)}, {S('osrd')}, {S('t0')} offen")
+                self.i(f"buffer_store_dwordx4 {vr(x[k], 4)}, {vr(gofs)}, {S('osrd')}, {S('t0')} offen")
                 if k < NI - 1:
                     self.i(f"s_add_u32 {S('t0')}, {S('t0')}, {S('t1')}")
         self.i(f"v_mov_b32 {vr(V_PS1)}, 0")
@@ -1966,51 +1813,48 @@ class Gen:
         self.item_prologue()
         self.i("s_waitcnt vmcnt(0)")
         self.i("s_barrier")                    # V0 / K1 published; every wave is done with K slot 0
-        if self.mb:
+        if self.fast:
             self.emit(self.kprefetch(1))       # the loop's first iteration (parity 0) reads K(1) from slot 1
-        self.stamp(3, count=8)
         # ---- tile loop, unrolled by the two S buffers ----------------------------------------------------------------------------------
-        lloop, lgen = f".L{n}_loop", f".L{n}_generic"
+        lloop, lgen, lseam = f".L{n}_loop", f".L{n}_generic", f".L{n}_seam"
         self.lab(lloop)
-        if LEAN and STAMP in (0, 3):
-            # Two tiles at a time WITHOUT the per-iteration bookkeeping, while this wave is far from both ends of the item: no Q
-            # pieces left to request (qrem == 0), no stream switch in either iteration (krem >= 2) and, under the causal mask, FULL
-            # bodies without a diagonal tile (wrem = krem - 2 + wave >= 3).  A lean iteration issues the same DMA pieces and meets the
-            # same barriers as a generic one, so every wave decides for itself.  (17 scalar instructions a tile were ~9 % of it.)
-            # (lengths: tiles j+2, j+3 whole too; a causal item's last block may run three tiles past the keys: its mask bytes)
-            self.i(f"s_cmp_lt_u32 {S('krem')}, {(7 if (self.kmask or self.klen) else 5) if self.causal else (4 if (self.klen or self.kmask) else 2)}")
-            self.i(f"s_cbranch_scc1 {lgen}")
-            self.i(f"s_cmp_lg_u32 {S('qrem')}, 0")
-            self.i(f"s_cbranch_scc1 {lgen}")
-            for p in (0, 1):
-                if self.kmask:
-                    self.emit(self.mask_load())
-                self.body_full(p, lean=True)
-                if self.mb:                         # (offsets, counted wait and barrier sit inside the body's PV phase)
-                    continue
-                self.i(f"s_add_u32 {S('koff')}, {S('koff')}, {S('ktile')}")
-                self.i(f"s_add_u32 {S('voff')}, {S('voff')}, {S('vtile')}")
-                if self.kmask:
-                    self.i(f"s_add_u32 {ka('pad')}, {ka('pad')}, 64")
-                self.i("s_waitcnt vmcnt(0)")
-                if self.kmask:
-                    self.i(self.mask_word(p))
-                self.i("s_barrier")
-            for c in ("krem", "vrem", "wrem", "irem"):
-                self.i(f"s_sub_u32 {S(c)}, {S(c)}, 2")
-            if self.kmask:                          # (their words need no length: all keys exist)
-                self.i(f"s_sub_u32 {self.kleft}, {self.kleft}, 128")
-            if self.klen:       # the words of tiles j+2, j+3 (all keys exist), the keys left behind them
-                self.i(f"s_mov_b64 {self.MK(0)}, -1")
-                self.i(f"s_mov_b64 {self.MK(1)}, -1")
-                self.i(f"s_sub_u32 {ka('pad')}, {ka('pad')}, 128")
-            self.i(f"s_branch {lloop}")
-            self.lab(lgen)
-        use_seam = SEAM and STAMP in (0, 3)
-        lseam = f".L{n}_seam"
+        # The lean loop: two tiles at a time WITHOUT the per-iteration bookkeeping, while this wave is far from both ends of the item: no Q
+        # pieces left to request (qrem == 0), no stream switch in either iteration (krem >= 2) and, under the causal mask, FULL
+        # bodies without a diagonal tile (wrem = krem - 2 + wave >= 3).  A lean iteration issues the same DMA pieces and meets the
+        # same barriers as a generic one, so every wave decides for itself.  (17 scalar instructions a tile were ~9 % of it.)
+        # (lengths: tiles j+2, j+3 whole too; a causal item's last block may run three tiles past the keys: its mask bytes)
+        self.i(f"s_cmp_lt_u32 {S('krem')}, {(5 if self.causal else 2) + (2 if self.mwords else 0)}")
+        self.i(f"s_cbranch_scc1 {lgen}")
+        self.i(f"s_cmp_lg_u32 {S('qrem')}, 0")
+        self.i(f"s_cbranch_scc1 {lgen}")
+        for p in (0, 1):
+            if self.kmask:
+                self.emit(self.mask_load())
+            self.body_full(p, lean=True)
+            if self.fast:                           # (offsets, counted wait and barrier sit inside the body's PV phase)
+                continue
+            self.i(f"s_add_u32 {S('koff')}, {S('koff')}, {S('ktile')}")
+            self.i(f"s_add_u32 {S('voff')}, {S('voff')}, {S('vtile')}")
+            if self.kmask:
+                self.i(f"s_add_u32 {ka('pad')}, {ka('pad')}, 64")
+            self.i("s_waitcnt vmcnt(0)")
+            if self.kmask:
+                self.i(self.mask_word(p))
+            self.i("s_barrier")
+        for c in ("krem", "vrem", "wrem", "irem"):
+            self.i(f"s_sub_u32 {S(c)}, {S(c)}, 2")
+        if self.kmask:                              # (their words need no length: all keys exist)
+            self.i(f"s_sub_u32 {self.kleft}, {self.kleft}, 128")
+        if self.klen:           # the words of tiles j+2, j+3 (all keys exist), the keys left behind them
+            self.i(f"s_mov_b64 {self.MK(0)}, -1")
+            self.i(f"s_mov_b64 {self.MK(1)}, -1")
+            self.i(f"s_sub_u32 {ka('pad')}, {ka('pad')}, 128")
+        self.i(f"s_branch {lloop}")
+        self.lab(lgen)
+        # The generic iterations: FULL body in line; a wave's LAST tile and the SKIP iterations past it out of line
         for p in (0, 1):
             lnf, ll, ld = (self.ul(x) for x in ("notfull", "last", "done"))
-            if p == 1 and use_seam:           # the item's last iteration, and another item follows: the pipelined seam (below)
+            if p == 1:                        # the item's last iteration, and another item follows: the pipelined seam (below)
                 lnorm = self.ul("noseam")
                 self.i(f"s_cmp_eq_u32 {S('irem')}, 2")
                 self.i(f"s_cbranch_scc0 {lnorm}")
@@ -2022,56 +1866,48 @@ class Gen:
             self.i(f"s_cbranch_scc0 {lnf}")
             self.body_full(p)
             self.lab(ld)
-            if not self.mb:
+            if not self.fast:
                 self.stream_bottom(p)
             self.out_of_line(True)
             self.lab(lnf)
             self.i(f"s_cmp_eq_u32 {S('wrem')}, 0")
             self.i(f"s_cbranch_scc1 {ll}")
-            self.body_skip(p)
-            if self.mb:                             # (no PV phase to carry the barrier: at the end, the K fragments of the next iteration behind it)
-                self.stream_bottom(p)
-                self.emit(self.kprefetch(p))
-            self.i(f"s_branch {ld}")
-            self.lab(ll)
-            self.body_last(p)
-            if self.mb:
-                self.stream_bottom(p)
-                self.emit(self.kprefetch(p))
-            self.i(f"s_branch {ld}")
+            for lbody, body in ((None, self.body_skip), (ll, self.body_last)):
+                if lbody:
+                    self.lab(lbody)
+                body(p)
+                if self.fast:                       # (no PV phase to carry the barrier: at the end, the K fragments of the next iteration behind it)
+                    self.stream_bottom(p)
+                    self.emit(self.kprefetch(p))
+                self.i(f"s_branch {ld}")
             self.out_of_line(False)
         self.i(f"s_sub_u32 {S('irem')}, {S('irem')}, 2")
         self.i(f"s_cmp_gt_i32 {S('irem')}, 0")
         self.i(f"s_cbranch_scc1 {lloop}")
-        self.stamp(2)
         self.item_epilogue()
-        self.stamp(4)
         self.i(f"s_cmp_lg_u32 {S('n_valid')}, 0")
         self.i(f"s_cbranch_scc1 {litem}")
         self.stamp_dump()
         self.lab(lend)
         self.i("s_endpgm")
-        if use_seam:
-            # ---- the pipelined seam: last iteration of an item with a successor, the ending item's epilogue, O = 0, item switch ----------
-            lsk, lsd = self.ul("seamskip"), self.ul("seamdone")
-            self.lab(lseam)
-            self.stream_top(1)
-            self.i(f"s_cmp_eq_u32 {S('wrem')}, 0")
-            self.i(f"s_cbranch_scc0 {lsk}")
-            self.body_seam(True)
-            self.i(f"s_branch {lsd}")
-            self.lab(lsk)
-            self.body_seam(False)
-            self.lab(lsd)
-            self.stream_bottom(1)
-            if self.mb:
-                self.emit(self.kprefetch(1))   # the next item's iteration 0 (parity 0) reads K_next(1) from slot 1
-            if "noepi" not in ABL:             # (TIMING-ONLY ablations of the seam path, wrong results: what an item costs outside its tile loop)
-                self.item_epilogue(saved=True)
-            if "nozero" not in ABL:
-                self.zero_o()
-            self.item_switch()
-            self.i(f"s_branch {lloop}")
+        # ---- the pipelined seam: last iteration of an item with a successor, the ending item's epilogue, O = 0, item switch ----------
+        lsk, lsd = self.ul("seamskip"), self.ul("seamdone")
+        self.lab(lseam)
+        self.stream_top(1)
+        self.i(f"s_cmp_eq_u32 {S('wrem')}, 0")
+        self.i(f"s_cbranch_scc0 {lsk}")
+        self.body_seam(True)
+        self.i(f"s_branch {lsd}")
+        self.lab(lsk)
+        self.body_seam(False)
+        self.lab(lsd)
+        self.stream_bottom(1)
+        if self.fast:
+            self.emit(self.kprefetch(1))       # the next item's iteration 0 (parity 0) reads K_next(1) from slot 1
+        self.item_epilogue(saved=True)
+        self.zero_o()
+        self.item_switch()
+        self.i(f"s_branch {lloop}")
         assert not self.lstack and self.L is self.main
         self.main += self.ool
         self.main += self.ool2

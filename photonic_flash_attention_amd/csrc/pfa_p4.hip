@@ -210,7 +210,8 @@ int p4_launch(const pfa_fa3_args* a, void* stream, int* hip_err) {
     p.hx = p.xcd_mode ? (uint32_t)(BH / 8) : (uint32_t)BH;
     p.SL = p.xcd_mode ? (uint32_t)(grid / 8) : (uint32_t)grid;
     p.nt_full = (uint32_t)(((a->Sk + 127) / 128) * 2);          // 64-key tiles, an even number of them (the two S buffers alternate from tile 0)
-    // diagnostic build only (P4_STAMP=1 make): per-wave cycle buckets go to the caller's workspace; the production kernel never reads it
+    // read by the stamped diagnostic code object only (P4_STAMP=3: built by tools/p4_variants.py, launched by tools/p4_ab.py, never linked
+    // here): per-wave kernel totals go to the workspace; the production kernel never reads it
     p.dbg = (a->workspace && a->workspace_bytes >= (size_t)grid * 4 * 16 * 4) ? (unsigned long long*)a->workspace : nullptr;
     // key-mask kernels: the same kernarg slot carries the mask bytes, `pad` is the kernel's running byte offset into them
     if (a->key_mask) p.dbg = (unsigned long long*)a->key_mask;

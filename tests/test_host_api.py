@@ -373,6 +373,40 @@ def test_generator_takes_no_knobs_in_the_product_build_and_is_deterministic(tmp_
     assert bad.returncode != 0 and "P4_DEV" in bad.stderr and not bad.stdout
 
 
+def _run_p4_generator(**knobs):
+    import subprocess
+    import sys
+    gen = os.path.join(REPO, "photonic_flash_attention_amd", "csrc", "gen_fa3_fwd_p4.py")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("P4_")}
+    return subprocess.run([sys.executable, gen], env=dict(env, **knobs), capture_output=True, text=True, timeout=300)
+
+
+def test_generator_stamped_build_is_the_fast_and_parity_kernels_only_and_deterministic():
+    """P4_DEV=1 P4_STAMP=3 (the one diagnostic: kernel totals): 16 kernels -- no key-mask (_km_) or ragged (_kl_) flavour, their mask
+    words live where the stamps keep their clock -- that differ from the product build's; two runs give byte-identical assembly."""
+    import re
+    a, b = _run_p4_generator(P4_DEV="1", P4_STAMP="3"), _run_p4_generator(P4_DEV="1", P4_STAMP="3")
+    assert a.returncode == 0 and b.returncode == 0 and a.stdout == b.stdout
+    names = re.findall(r"\.amdhsa_kernel (\S+)", a.stdout)
+    assert len(names) == 16 and len(set(names)) == 16
+    assert not [n for n in names if "_km_" in n or "_kl_" in n]
+    prod = _run_p4_generator()
+    assert prod.returncode == 0 and prod.stdout != a.stdout
+
+
+def test_generator_refuses_a_knob_it_does_not_know():
+    """P4_DEV=1 with a P4_* name other than P4_STAMP (here a knob that once existed) stops the generator and names it: a mistyped or
+    retired knob must not build the base schedule under another name."""
+    r = _run_p4_generator(P4_DEV="1", P4_LEAN="0")
+    assert r.returncode != 0 and "P4_LEAN" in r.stderr and not r.stdout
+
+
+def test_generator_knows_one_stamp_mode():
+    """P4_STAMP accepts 0 / unset and 3; the per-phase modes 1 and 2 are gone."""
+    r = _run_p4_generator(P4_DEV="1", P4_STAMP="1")
+    assert r.returncode != 0 and not r.stdout
+
+
 def test_bench_reads_the_traffic_figure_from_the_newest_profile():
     """bench.py roofline.traffic: parsed from profiles/r*_<workload>_rocprof_summary.md (FETCH_SIZE x 2 + WRITE_SIZE, KiB), not pasted."""
     import importlib.util

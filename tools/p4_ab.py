@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Same-process A/B of persistent-forward code objects (gen_fa3_fwd_p4.py builds), WITHOUT going through libpfa_hip.so: each
 variant's .hsaco is loaded here with hipModuleLoadData and launched with hipModuleLaunchKernel on the kernarg block pfa_p4.hip
-would build.  The product library therefore never carries an experimental, stamped or ablated code object.
+would build.  The product library therefore never carries an experimental or stamped code object.
 
-    python3 tools/p4_variants.py base= fastmax=P4_FASTMAX=1 ...          (build container: writes csrc/build/variants/<name>.hsaco)
-    python3 tools/p4_ab.py --variants base,fastmax --shapes C3,C4 [--check] [--stamp]         (GPU box)
+    python3 tools/p4_variants.py base= try=@/tmp/gen_try.py ...          (build container: writes csrc/build/variants/<name>.hsaco)
+    python3 tools/p4_ab.py --variants base,try --shapes C3,C4 [--check]                       (GPU box)
+    python3 tools/p4_ab.py --variants stamp3 --stamp --shapes C3                              (a P4_STAMP=3 build)
 
 --check : every variant's output / LSE against the first variant's (bitwise share, max-abs) and against the 8-wave HIP kernel (selector 44)
---stamp : the variants are P4_STAMP builds: dump their cycle buckets instead of timing them
+--stamp : the variants are P4_STAMP=3 builds: dump their kernel totals, clock and placement instead of timing them
 Timing: rounds of `--steps` launches per variant, interleaved, HIP events; median and min over `--rounds` (cdna guide rule 24).
 """
 import argparse
@@ -109,9 +110,10 @@ def kname(dt, D, causal, flav="", parity=False):
 
 
 def stamp_report(name, dbg, grid):
+    """dbg: [workgroup][wave][16] dwords (gen_fa3_fwd_p4.py stamp_dump): dword 1 + k = bucket k -- 10 kernel cycles, 11 kernel time in 10-ns
+    ticks, 13 XCC id, 14 HW_ID"""
     d = (dbg.view(-1, 4, 16)[:grid].long() & 0xffffffff).double().cpu()
     acc = d[..., 1:]
-    nfull, nitems = acc[..., 7].sum(), acc[..., 8].sum()
     tot = acc[..., 10]
     clk = (tot / (acc[..., 11] * 10e-9) / 1e9)
     wall = acc[..., 11] * 10 / 1e3
@@ -131,10 +133,6 @@ def stamp_report(name, dbg, grid):
           + (f" e.g. {list(dup.items())[:3]}" if dup else ""))
     by_xcc = [wall[(xcc == x).nonzero().flatten()].mean().item() if int((xcc == x).sum()) else float('nan') for x in range(8)]
     print("     wall by XCC id: " + " ".join(f"{v:.1f}" for v in by_xcc))
-    if nfull > 0:
-        print(f"     per FULL iteration: QK^T {acc[..., 0].sum() / nfull:.0f}  PV {acc[..., 1].sum() / nfull:.0f}  sync+bookkeeping {acc[..., 2].sum() / nfull:.0f}"
-              f"  (vmcnt {acc[..., 9].sum() / nfull:.0f}, barrier {acc[..., 12].sum() / nfull:.0f});  per item: switch+prologue {acc[..., 3].sum() / nitems:.0f}"
-              f"  epilogue {acc[..., 4].sum() / nitems:.0f}  LAST {acc[..., 5].sum() / nitems:.0f}  SKIP {acc[..., 6].sum() / nitems:.0f}")
 
 
 def main():
