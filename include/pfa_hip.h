@@ -17,6 +17,8 @@
  * union: what a shared prefix computed once per batch, a split over keys or keys spread over several GPUs need behind them.
  * v9, additive: pfa_page_copy* -- whole or partial pages copied inside the pools of a paged cache from a device pair list: the data
  * movement of copy-on-write for sequences that share pages.
+ * v9, additive: pfa_fa3_tree_mask and pfa_fa3_decode_tree* -- the decode with a 64-bit visibility word per query row over the step's own
+ * keys in place of the causal triangle: the verification of a drafted token TREE (speculative decoding) in one pass over the cache.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -465,6 +467,50 @@ int pfa_fa3_prefill_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cach
 int pfa_fa3_prefill_varlen_check_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext);
 int pfa_fa3_prefill_varlen_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, void* stream);
 int pfa_fa3_prefill_varlen_describe_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, char* buf, size_t n);
+
+/*
+ * Tree attention masks in the decode (ABI v9, additive): the verification step of speculative decoders that draft a TREE of tokens
+ * (Medusa, EAGLE, SpecInfer).  The step's Sq <= 64 rows are the tree's nodes, appended to the cache like any step's rows; a node must
+ * see the cached prefix and its own ancestors, but not its siblings.  pfa_fa3_cache_ext is full, so the mask comes in a block of its
+ * own and through entry points of its own, pfa_fa3_decode_ex with one more argument.  tree == NULL is pfa_fa3_decode_ex in every
+ * respect: status, workspace, kernel function, grid and bits.
+ *
+ * The rule.  With len_b the sequence's valid keys AFTER the step's Sq rows were appended and off_b = len_b - Sq, row i of sequence b
+ * sees key j iff
+ *       j < len_b   and   ( j < off_b   or   bit (j - off_b) of words[b * stride_b + i] is set ),
+ * and, where a key_mask is given, the key mask allows j (logical AND).  Bits at and above Sq are ignored.  Nothing is required of the
+ * pattern: no self bit, no ancestor order, bits above the diagonal are allowed.  The chain (word i = bits 0 .. i) is exactly the causal
+ * rule and returns the bits of the causal call; all-ones is exactly causal = 0.  For len_b < Sq new row r has no key when
+ * off_b + r < 0, and its bit selects nothing.  A row with no visible key (an empty word and no prefix) gets O = 0 and LSE = -inf, as
+ * everywhere.
+ *
+ * What is never read is what the call without a tree never reads: keys at and past len_b, and table entries at and past
+ * ceil(len_b / page_size).  Keys inside [off_b, len_b) that a word hides ARE read and hidden by the score mask: they are live cache
+ * contents and must be finite (the statement the window makes about its boundary keys).  `words` is read once per workgroup lane,
+ * Sq words per sequence.
+ *
+ * The number of key splits and the workspace are those of the call without a tree, a function of (B, H, Hkv, Sq, Smax, D) alone:
+ * a captured graph replays while words, lengths, table and cache change.  Rotary positions: the fused rotary append rotates by row
+ * index; a node's position is off_b + its depth, so the caller of a tree step rotates Q and K itself.
+ *
+ * Field rules, after those of the argument block and of ext, in this order: size wrong -> PFA_ERR_STRUCT_SIZE; flags non-zero ->
+ * PFA_ERR_FLAGS; words NULL -> PFA_ERR_NULL; words not 8-byte aligned -> PFA_ERR_ALIGN; stride_b < Sq -> PFA_ERR_SHAPE; causal == 0 ->
+ * PFA_ERR_FLAGS (the words replace the triangle and have no meaning without one); a window > 0 together with a tree -> PFA_ERR_FLAGS
+ * (a node's window would be by depth, not by row index).  pfa_fa3_decode_tree_workspace_bytes takes no pointers and returns 0 for
+ * what the other rules refuse.  *_describe appends "_tree" to the kernel's name where "_win" would stand.
+ */
+typedef struct pfa_fa3_tree_mask {
+    uint32_t size;              /* = sizeof(pfa_fa3_tree_mask) */
+    uint32_t flags;             /* must be 0 */
+    const uint64_t* words;      /* device [B][stride_b], words[b * stride_b + i] for row i; 8-byte aligned */
+    int64_t  stride_b;          /* words between sequences, >= Sq */
+} pfa_fa3_tree_mask;
+
+size_t pfa_fa3_decode_tree_workspace_bytes(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree);
+int pfa_fa3_decode_tree_check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree);
+int pfa_fa3_decode_tree(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree, void* stream);
+int pfa_fa3_decode_tree_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree, char* buf, size_t n,
+                                 int32_t* nsplit);
 
 /*
  * Forward over a KV cache with the keys split over workgroups (ABI v9, additive).  pfa_fa3_prefill launches B * H * ceil(Sq / 256)

@@ -93,6 +93,11 @@ class PfaFa3CacheExt(C.Structure):
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PfaFa3TreeMask(C.Structure):
+    """Mirror of ``struct pfa_fa3_tree_mask`` (include/pfa_hip.h): a 64-bit visibility word per query row of ``pfa_fa3_decode_tree``."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("words", C.c_void_p), ("stride_b", C.c_int64)]
+
+
 class PfaKvAppendArgs(C.Structure):
     """Mirror of ``struct pfa_kv_append_args`` (include/pfa_hip.h): the device-side KV-cache append."""
     _fields_ = (
@@ -152,6 +157,7 @@ def _prototypes():
                                                                       PfaKvAppendArgs, PfaFa3CacheExt, PfaRopeAppendArgs, PfaAttnMergeArgs))
     ns = [C.POINTER(C.c_int32)]
     pcp = C.POINTER(PfaPageCopyArgs)
+    tree = C.POINTER(PfaFa3TreeMask)
     return {
         "pfa_abi_version": (i, None),
         "pfa_status_string": (C.c_char_p, [i]),
@@ -181,6 +187,10 @@ def _prototypes():
         "pfa_fa3_decode_check_ex": (i, [dec, ext]),
         "pfa_fa3_decode_ex": (i, [dec, ext, vp]),
         "pfa_fa3_decode_describe_ex": (i, [dec, ext] + buf + ns),
+        "pfa_fa3_decode_tree_workspace_bytes": (sz, [dec, ext, tree]),
+        "pfa_fa3_decode_tree_check": (i, [dec, ext, tree]),
+        "pfa_fa3_decode_tree": (i, [dec, ext, tree, vp]),
+        "pfa_fa3_decode_tree_describe": (i, [dec, ext, tree] + buf + ns),
         "pfa_fa3_prefill_check_ex": (i, [dec, ext]),
         "pfa_fa3_prefill_ex": (i, [dec, ext, vp]),
         "pfa_fa3_prefill_describe_ex": (i, [dec, ext] + buf),
@@ -319,6 +329,16 @@ def make_cache_ext(**kw) -> PfaFa3CacheExt:
 def describe_decode_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
     """``describe_decode`` of ``pfa_fa3_decode_ex`` (``ext`` None: the NULL extension); "_win" marks a windowed kernel."""
     return _describe("pfa_fa3_decode_describe_ex", args, ext, nsplit=True)
+
+
+def make_tree_mask(**kw) -> PfaFa3TreeMask:
+    return _make(PfaFa3TreeMask, kw)
+
+
+def describe_decode_tree(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], tree: Optional[PfaFa3TreeMask]):
+    """``describe_decode_ex`` of ``pfa_fa3_decode_tree`` (``tree`` None: the NULL tree, i.e. ``pfa_fa3_decode_ex``); "_tree" marks a
+    kernel that takes the words."""
+    return _describe("pfa_fa3_decode_tree_describe", args, ext, tree, nsplit=True)
 
 
 def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):

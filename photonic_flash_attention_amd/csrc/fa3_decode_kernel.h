@@ -34,6 +34,13 @@
 //     have given those pages away).  Each row's lower bound row_lo = len_b - Sq + i + 1 - W joins the visibility test on the tiles that
 //     reach below the item's largest row_lo; keys in [base_b, row_lo) are read and masked.  The other instantiations are untouched:
 //     WINDOW = false compiles to the code and the kernel arguments it had.
+//   * TREE = true (pfa_fa3_decode_tree, causal only, no window; DecodeTreeParams carries the words): a 64-bit word per query row
+//     replaces the causal triangle over the step's own Sq keys.  Row i sees key j iff j < len_b and (j < off_b or bit (j - off_b) of
+//     tree[b][i] is set), off_b = len_b - Sq.  Each lane loads its row's word once, by a vector load, in front of the tile loop.  Key off_b
+//     itself can be hidden, so the masked path starts one key earlier than under causal (a tile is unmasked only when it ends at or
+//     below off_b) and a row's upper bound is len_b.  Keys in [off_b, len_b) that a word hides are read and masked.  Split rule, paging,
+//     merge, partials and combine are the one code path: the chain words give the bits of the causal call, all-ones those of
+//     causal = 0.  TREE = false compiles to the code and the kernel arguments it had.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,8 +95,14 @@ struct DecodeParams {
 struct DecodeWinParams : DecodeParams {
     int32_t window;
 };
-template <bool WINDOW> struct DecodeParamsOf { typedef DecodeParams type; };
-template <> struct DecodeParamsOf<true> { typedef DecodeWinParams type; };
+// TREE only: one 64-bit visibility word per query row, words[b * tree_sb + i]
+struct DecodeTreeParams : DecodeParams {
+    const uint64_t* tree;
+    int64_t tree_sb;
+};
+template <bool WINDOW, bool TREE = false> struct DecodeParamsOf { typedef DecodeParams type; };
+template <> struct DecodeParamsOf<true, false> { typedef DecodeWinParams type; };
+template <> struct DecodeParamsOf<false, true> { typedef DecodeTreeParams type; };
 
 template <typename T> struct DElem;
 template <> struct DElem<__bf16> {
@@ -149,8 +162,9 @@ __device__ __forceinline__ void split_range(const DecodeParams& p, int s, int ba
     hi = min(lo + c, len);
 }
 
-template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false>
-__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW>::type p) {
+template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false>
+__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE>::type p) {
+    static_assert(!(WINDOW && TREE), "a tree does not combine with a window");
     using E = DElem<T>;
     using v8 = typename E::v8;
     using v4 = typename E::v4;
@@ -184,7 +198,8 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
     const int qi = row_ok ? r / p.G : 0, qg = row_ok ? r % p.G : 0;
     const int head = kvh * p.G + qg;
     const int row_lim = p.causal ? len - p.Sq + qi + 1 : len;     // exclusive key bound of this row (before the split's)
-    const int min_lim = p.causal ? len - p.Sq + 1 : len;          // every row sees at least the keys below this
+    // every row sees at least the keys below this (TREE: a word may hide key off_b = len - Sq itself)
+    const int min_lim = TREE ? len - p.Sq : p.causal ? len - p.Sq + 1 : len;
     // WINDOW (causal): the row's lowest visible key, and the largest of them among the item's rows (its last row's)
     int row_lo = 0, max_lo = 0;
     if constexpr (WINDOW) {
@@ -192,6 +207,10 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
         const int last = min(rb * ROWS + ROWS - 1, p.Sq * p.G - 1);
         max_lo = __builtin_amdgcn_readfirstlane(len - p.Sq + last / p.G + 1 - p.window);
     }
+    // TREE: the row's visibility word over keys off .. off + Sq - 1 (a per-lane vector load; a row past the item's last sees nothing)
+    uint64_t tw = 0;
+    const int off = len - p.Sq;
+    if constexpr (TREE) tw = row_ok ? p.tree[(int64_t)b * p.tree_sb + qi] : 0;
 
     f32x4 oacc[NDB];
 #pragma unroll
@@ -275,7 +294,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
             }
             if (t + NW < ntile) issue(t + NW);
 
-            // scores in log2 units; masks only where the tile reaches past the split, the causal cut, below a row's window, or a key mask exists
+            // scores in log2 units; masks only where the tile reaches past the split, the causal cut (TREE: the step's own keys), below a row's window, or a key mask exists
             const bool edge = km != nullptr || t0 + KT > hi || t0 + KT > min_lim || (WINDOW && t0 < max_lo);
             float mx = -__builtin_inff();
 #pragma unroll
@@ -287,6 +306,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
                         const int key = t0 + kb * 16 + 4 * h + e;
                         bool vis;
                         if constexpr (WINDOW) vis = key < hi && (uint32_t)(key - row_lo) < (uint32_t)p.window;   // row_lo <= key < row_lim
+                        else if constexpr (TREE) vis = key < hi && (key < off || ((tw >> ((key - off) & 63)) & 1));   // hi <= len: the bit is below Sq
                         else vis = key < hi && key < row_lim;
                         if (vis && km) vis = km[key] != 0;
                         sc = vis ? sc : -__builtin_inff();

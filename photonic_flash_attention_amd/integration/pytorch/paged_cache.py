@@ -51,8 +51,8 @@ class PagedKVCache:
     ``copy_on_write=True`` adds page sharing: ``fork``, per-page reference counts (``page_refcount``), the copy of a shared, partly
     filled tail page in front of the first write into it, and ``common_prefix``.  The copies an ``advance`` calls for wait in the
     device tensors ``cow_pairs`` / ``cow_rows`` (the pending table) for the ``write_step`` behind it.  Ordering contract: every call
-    that changes page ownership -- ``append``, ``append_varlen``, ``advance``, ``fork``, ``free``, ``release_behind_window``,
-    ``swap_pages`` -- first resets the pending table to empty (``advance`` then fills in its own entries), so the ``write_step`` of an
+    that changes page ownership -- ``append``, ``append_varlen``, ``advance``, ``fork``, ``free``, ``truncate``,
+    ``release_behind_window``, ``swap_pages`` -- first resets the pending table to empty (``advance`` then fills in its own entries), so the ``write_step`` of an
     ``advance`` must be enqueued, on the same stream, before the next such call.  With ``copy_on_write=False`` (the default) nothing
     is shared, no extra tensor exists, no extra launch is made, and ``fork`` raises ``ValueError``.
     """
@@ -211,6 +211,31 @@ class PagedKVCache:
         self._live[slot] = False
         self._lens[slot] = 0
 
+    def truncate(self, slot: int, n_tokens: int) -> None:
+        """Take the slot back to its first ``n_tokens`` keys (``0 <= n_tokens <= length(slot)``, else ``ValueError``): the other half
+        of a speculative step, which appends a drafted tree's rows, verifies them (``decode(tree_mask=)``) and keeps the accepted
+        path only -- ``truncate(slot, L)`` to the length before the step, then ``append_varlen`` of the accepted rows in path order.
+
+        Lets go of every page past ``ceil(n_tokens / page_size)``, reserved ones included (``reserve`` again before a capture that
+        needs them); a page another slot holds stays alive (``copy_on_write``).  The table row's stale entries stay as they are, as
+        after ``free``: nothing reads them.  A partly filled tail page that is still shared is left shared; the next append copies
+        it.  Refused with ``ValueError`` when ``n_tokens > 0`` and the page holding key ``n_tokens - 1`` was released behind a
+        window: the slot would end in keys that are gone.  Host bookkeeping plus the device length; works on CPU tensors.  Resets the
+        pending copy-on-write table first (see the class's ordering contract)."""
+        self._check_slot(slot)
+        n = n_tokens
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= self._host_lens[slot]:
+            raise ValueError(f"n_tokens must be an integer in 0 .. {self._host_lens[slot]}, the slot's length, got {n_tokens!r}")
+        pg = self._pages[slot]
+        if n > 0 and pg[(n - 1) // self.page_size] < 0:
+            raise ValueError(f"slot {slot}: the page holding key {n - 1} was released behind the window")
+        self._reset_pending()
+        keep = -(-n // self.page_size)
+        self._let_go(p for p in reversed(pg[keep:]) if p >= 0)
+        del pg[keep:]
+        self._host_lens[slot] = n
+        self._lens[slot] = n
+
     def release_behind_window(self, slot: int, window: int) -> int:
         """Return to the pool every page of the slot that lies wholly behind a sliding window of ``window`` keys: logical page p
         with ``(p + 1) * page_size <= max(0, length(slot) - window + 1)``, the lowest key the sequence's newest row sees.  -> the
@@ -344,7 +369,8 @@ class PagedKVCache:
         With ``copy_on_write`` the copies of shared tail pages this step calls for are written, whole and in place, into ``cow_pairs``
         / ``cow_rows`` (row = slot) for ``write_step`` to run; the table is reset first.  Ordering contract: enqueue this step's
         ``write_step``, on the same stream, before the next call that changes page ownership (``append``, ``append_varlen``,
-        ``advance``, ``fork``, ``free``, ``release_behind_window``, ``swap_pages``): each of them empties the pending table."""
+        ``advance``, ``fork``, ``free``, ``truncate``, ``release_behind_window``, ``swap_pages``): each of them empties the pending
+        table."""
         slots = [slots] if isinstance(slots, int) else list(slots)
         lens = [int(x) for x in lens]
         if len(set(slots)) != len(slots):
@@ -515,8 +541,9 @@ class PagedKVCache:
         all ``max_batch`` slots in order).  None and a run of consecutive slots read the cache's own table and lengths, so the
         call can be captured in a graph and replayed while the cache changes; any other list takes a copy of its rows first.
         Keyword arguments (``causal``, ``key_mask`` over ``max_pages_per_seq * page_size`` logical keys, ``out_dtype``,
-        ``window`` -- the sliding window, required once ``release_behind_window`` has given pages back --, ...) pass through.
-        -> ``(o, lse)``."""
+        ``window`` -- the sliding window, required once ``release_behind_window`` has given pages back --, ``tree_mask`` -- int64
+        ``[B, Sq]`` words that verify a drafted token tree, ``ops.tree_mask_from_parents``; ``truncate`` then takes the rejected rows
+        back --, ...) pass through.  -> ``(o, lse)``."""
         table, lens = self._rows(slots)
         return ops.fa3_decode(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
 

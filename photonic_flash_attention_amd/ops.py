@@ -589,6 +589,70 @@ def _window_ext(window, causal):
     return _capi.make_cache_ext(window=min(w, 0x7fffffff))
 
 
+def _tree_mask_arg(tree_mask, q, causal, window, shared_prefix):
+    """``tree_mask`` (None, or an int64 ``[B, Sq]`` tensor on q's device, last dim contiguous) as ``pfa_fa3_decode_tree``'s block
+    (the caller's tensor is pointed into, not copied).  Refused before anything is launched: a wrong dtype, shape or device, ``causal=False``, a
+    ``window`` and ``shared_prefix``."""
+    if tree_mask is None:
+        return None
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
+        raise ValueError("tree_mask must be an int64 tensor (one 64-bit word per query row; the kernel reads it as unsigned)")
+    if q.dim() != 4:
+        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    B, Sq = q.shape[0], q.shape[2]
+    if tree_mask.shape != (B, Sq):
+        raise ValueError(f"tree_mask must be [B, Sq] = [{B}, {Sq}], got {tuple(tree_mask.shape)}")
+    if tree_mask.device != q.device:
+        raise ValueError("tree_mask must live on the operands' device")
+    if not causal:
+        raise ValueError("tree_mask needs causal=True: the words replace the causal triangle over the step's own keys")
+    if window is not None:
+        raise ValueError("tree_mask does not combine with window: a node's window would be by depth, not by row index")
+    if shared_prefix is not None:
+        raise ValueError("tree_mask does not combine with shared_prefix yet")
+    if (Sq > 1 and tree_mask.stride(1) != 1) or (B > 1 and tree_mask.stride(0) < Sq):
+        raise ValueError("tree_mask: the last dim must be contiguous and the sequences' rows must not overlap")
+    return _capi.make_tree_mask(words=tree_mask.data_ptr(), stride_b=max(tree_mask.stride(0), Sq))
+
+
+def tree_mask_from_parents(parents: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ``tree_mask`` words of a drafted token tree given by parent links, and the nodes' depths.
+
+    parents: integer ``[B, Sq]`` tensor on any device, Sq <= 64, nodes in an order that puts every parent in front of its children:
+    ``parents[b, i]`` is in ``-1 .. i - 1``, -1 for a node that hangs off the cached prefix.  Returns ``(words, depths)`` on the same
+    device: ``words[b, i]`` (int64) has bit i set plus the bits of the parent's word, i.e. the node and its ancestors -- what
+    ``fa3_decode(tree_mask=)`` takes; bit 63 is the int64's sign bit, so the last node of a 64-node chain has the word -1.
+    ``depths[b, i]`` (int32) is 0 for a child of the prefix, popcount - 1 in general.  A node's rotary position is
+
+        ``len_b - Sq + depths[b, i]``
+
+    with len_b the length after the step's Sq rows were appended.  Sq vectorised torch steps, no host synchronisation on device
+    tensors: out-of-range parents are the caller's problem there (they are clamped into ``-1 .. i - 1``'s index range, never an
+    out-of-range access); on CPU tensors they raise ``ValueError``, as do Sq > 64, a wrong rank and a non-integer dtype."""
+    if not isinstance(parents, torch.Tensor) or parents.dim() != 2 or parents.dtype.is_floating_point or parents.dtype.is_complex \
+            or parents.dtype == torch.bool:
+        raise ValueError("parents must be an integer [B, Sq] tensor")
+    B, Sq = parents.shape
+    if Sq < 1 or Sq > 64:
+        raise ValueError(f"parents: 1 .. 64 nodes per sequence (one bit of a 64-bit word each), got {Sq}")
+    par = parents.to(torch.int64)
+    if not par.is_cuda and B:
+        idx = torch.arange(Sq, dtype=torch.int64, device=par.device)
+        if bool(((par < -1) | (par >= idx)).any()):
+            raise ValueError("parents[b, i] must be in -1 .. i - 1 (-1: the node hangs off the prefix)")
+    # bit i as an int64: 1 << 63 wraps to the sign bit
+    bits = torch.ones((), dtype=torch.int64, device=par.device) << torch.arange(Sq, dtype=torch.int64, device=par.device)
+    words = torch.zeros((B, Sq), dtype=torch.int64, device=par.device)
+    depths = torch.zeros((B, Sq), dtype=torch.int32, device=par.device)
+    for i in range(Sq):
+        p = par[:, i:i + 1]
+        has = p >= 0
+        at = p.clamp(0, max(i - 1, 0))
+        words[:, i:i + 1] = torch.where(has, words.gather(1, at), torch.zeros_like(p)) | bits[i]
+        depths[:, i:i + 1] = torch.where(has, depths.gather(1, at) + 1, torch.zeros_like(p, dtype=torch.int32))
+    return words, depths
+
+
 def _key_splits_arg(name: str, value):
     """``key_splits`` / ``prefix_key_splits`` (``name``) as the C value: None stays None, ``"auto"`` is 0 (the library's plan), an integer
     1 .. 8 is itself.  Any other value or type is refused before anything is launched."""
@@ -1007,12 +1071,13 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=
     return None
 
 
-def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, **ragged):
+def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, tree=None, **ragged):
     """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
     ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
     the current stream right behind it, the status, and the kept tensors' hold on the stream.  With ``rotary`` the launch reads the
     rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  ``key_splits`` (the C value, ``pfa_fa3_prefill`` only)
-    launches ``pfa_fa3_prefill_split`` instead, which takes no extension.  -> lse or None."""
+    launches ``pfa_fa3_prefill_split`` instead, which takes no extension; ``tree`` (``pfa_fa3_decode`` only) launches
+    ``pfa_fa3_decode_tree``, which takes it behind the extension.  -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
@@ -1028,6 +1093,8 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     stream = torch.cuda.current_stream(q.device)
     if key_splits is not None:
         st = _capi.load().pfa_fa3_prefill_split(C.byref(a), key_splits, C.c_void_p(stream.cuda_stream))
+    elif tree is not None:
+        st = _capi.load().pfa_fa3_decode_tree(C.byref(a), None if ext is None else C.byref(ext), C.byref(tree), C.c_void_p(stream.cuda_stream))
     else:
         st = getattr(_capi.load(), entry + "_ex")(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
@@ -1205,7 +1272,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
-               prefix_key_splits=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               prefix_key_splits=None, tree_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -1261,10 +1328,25 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     ``prefix_key_splits`` (``None``, ``"auto"`` or 1 .. 8; only with ``shared_prefix``, else ``ValueError``): the ``key_splits`` of that
     prefix pass when it is ``fa3_prefill_cache``, i.e. for ``B * Sq`` > 64 -- the P keys are cut over that many workgroups per q block
     and merged (``profiles/prefill_split.md``).  With 64 rows or fewer the decode kernel splits by itself and the value is only
-    validated.  ``None``: exactly the calls made without the argument."""
+    validated.  ``None``: exactly the calls made without the argument.
+
+    ``tree_mask`` (int64 ``[B, Sq]`` DEVICE tensor, last dim contiguous; ``pfa_fa3_decode_tree``): the verification of a drafted token
+    TREE.  The step's Sq rows are the tree's nodes, appended like any step's rows, and word ``tree_mask[b, i]`` replaces the causal
+    triangle over them: with off_b = len_b - Sq, row i sees key j iff j < len_b and (j < off_b or bit (j - off_b) of the word is set).
+    The kernel reads the word as unsigned: bit 63 is the sign bit of the int64.  Bits at and above Sq are ignored and nothing is
+    required of the pattern (no self bit, no order); the chain (bits 0 .. i) returns the bits of the plain causal call, all-ones
+    those of ``causal=False``.  A row whose word is empty and that has no prefix gets O = 0 and LSE = -inf.  Hidden keys of the step
+    are read and masked, so they must be finite.  ``tree_mask_from_parents`` builds the words from parent links.  It needs
+    ``causal=True`` and combines with neither ``window`` nor ``shared_prefix`` (``ValueError`` before any launch, as for a wrong dtype,
+    shape or device); ``key_mask`` (AND), ``block_table``, ``k_new`` / ``v_new``, ``out``, ``out_dtype`` and ``return_lse`` work as above.  The
+    number of key splits and the workspace do not depend on it: a captured step replays while the words change.  The fused rotary
+    arguments rotate by ROW INDEX (row i at ``len_b - Sq + i``), which is a chain's position and not a tree's: for a tree the caller
+    rotates Q and K itself at ``len_b - Sq + depth`` (``tree_mask_from_parents`` returns the depths) and passes no rotary tables.
+    ``None``: exactly the calls made without the argument."""
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
+    tree = _tree_mask_arg(tree_mask, q, causal, window, shared_prefix)
     if prefix_key_splits is not None and shared_prefix is None:
         raise ValueError("prefix_key_splits needs shared_prefix: it splits the keys of the prefix pass")
     if shared_prefix is not None:
@@ -1290,13 +1372,13 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         if cache_seqlens is None:
             cache_seqlens = _mask_bound(km)
     _set_cache_seqlens(a, cache_seqlens, q, keep)
-    ws_bytes = int(_capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)))
+    ws_bytes = int(_capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)))    # a tree changes nothing here
     if ws_bytes:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
         keep.append(ws)
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, max_seqlen_q=Sq)
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, max_seqlen_q=Sq)
     return out, lse
 
 
