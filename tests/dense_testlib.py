@@ -1,0 +1,163 @@
+"""What the tests of the dense calls (``ops.fa3_forward`` / ``ops.fa3_backward`` on the exact-fp32 kernels) share: one fp64 reference,
+the error bounds, the checks, and the guarded buffers of the containment tests.  Plain functions and constants; pytest collects nothing
+from here, and tests/test_dense_testlib.py tests it on the CPU.  The counterpart of tests/kvcache_testlib.py.
+
+The reference is fp64 attention of ``q [B,H,Sq,D]`` over ``k/v [B,Hkv,Sk,D]`` (grouped heads by ``repeat_interleave``, so autograd sums
+each group) with the DENSE causal rule of this project -- row i sees key j iff ``j <= i``, aligned top-left; the caches' rule is
+bottom-right -- ``seqlens`` clamped to ``0 .. Sk``, and a bool ``keep`` broadcastable to ``[B,H,Sq,Sk]``.  The dropout keep-mask ``drop``
+multiplies the NORMALISED weights, scaled by ``drop_scale``: the row sum and the LSE stay un-dropped.  A row that sees no key has
+``o = 0``, ``lse = -inf`` and zero gradients.  Gradients come from autograd through the fp64 expression.
+
+The bounds are the fp32 kernels' own (tests/test_hip_modules.py::test_exact_fp32_kernel_against_the_oracle,
+tests/test_hip_backward.py::test_fp32_backward_matches_autograd_of_oracle and ::test_dense_branch_dropout_statistics_and_gradients):
+
+    o and finite lse            max-abs 2e-5
+    gradients, no dropout       2e-5 * max(1, max|ref|)
+    gradients, with dropout     3e-5 * max(1, max|ref|)
+
+and, as equalities: every output finite; ``lse`` -inf on exactly the reference's rows; ``o`` and ``dq`` exactly 0.0 on those rows; ``dk``
+and ``dv`` exactly 0.0 for keys that no row of the group sees."""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+INF = float("inf")
+BOUND_O = 2e-5                 # o and finite lse, max-abs
+BOUND_GRAD = 2e-5              # x max(1, max|ref|)
+BOUND_GRAD_DROP = 3e-5         # x max(1, max|ref|), with a dropout keep-mask
+DEV = "cuda:0"
+
+
+# --- the fp64 reference --------------------------------------------------------------------------------------------------------------
+
+def visible(B, H, Sq, Sk, *, causal=False, seqlens=None, keep=None):
+    """bool [B,H,Sq,Sk]: row i of (b, h) sees key j.  Dropout is no part of it: a dropped key is seen."""
+    vis = torch.ones(B, H, Sq, Sk, dtype=torch.bool)
+    if causal:
+        vis = vis & torch.tril(torch.ones(Sq, Sk, dtype=torch.bool))
+    if seqlens is not None:
+        L = torch.as_tensor(seqlens).long().cpu().clamp(0, Sk)
+        vis = vis & (torch.arange(Sk)[None, :] < L[:, None])[:, None, None, :]
+    if keep is not None:
+        vis = vis & keep.cpu().bool()
+    return vis
+
+
+def reference(q, k, v, *, causal=False, seqlens=None, keep=None, drop=None, drop_scale=1.0, scale=None, dout=None):
+    """fp64 on the CPU -> (o [B,H,Sq,D], lse [B,H,Sq]), and (dq [B,H,Sq,D], dk, dv [B,Hkv,Sk,D]) behind them when ``dout`` is given."""
+    B, H, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    g = H // Hkv
+    assert H == g * Hkv and k.shape == (B, Hkv, Sk, D) and v.shape == (B, Hkv, Sk, D)
+    qd, kd, vd = (t.detach().cpu().double().clone().requires_grad_(dout is not None) for t in (q, k, v))
+    vis = visible(B, H, Sq, Sk, causal=causal, seqlens=seqlens, keep=keep)
+    s = (qd @ kd.repeat_interleave(g, dim=1).transpose(-1, -2)) * (D ** -0.5 if scale is None else scale)
+    s = s.masked_fill(~vis, -INF)
+    m = s.detach().amax(-1, keepdim=True)
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    safe = torch.where(l > 0, l, torch.ones_like(l))
+    w = p / safe                                                  # the normalised weights: zero rows where no key is seen
+    if drop is not None:
+        w = w * (drop.cpu().to(torch.float64) * float(drop_scale))
+    o = w @ vd.repeat_interleave(g, dim=1)
+    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, -INF))[..., 0].detach()
+    if dout is None:
+        return o, lse
+    dq, dk, dv = torch.autograd.grad(o, (qd, kd, vd), dout.detach().cpu().double())
+    return o.detach(), lse, dq, dk, dv
+
+
+def seen(vis, Hkv):
+    """``visible(...)`` -> (rows that see a key [B,H,Sq], keys that a row of their group sees [B,Hkv,Sk])"""
+    B, H, Sq, Sk = vis.shape
+    return vis.any(dim=3), vis.any(dim=2).reshape(B, Hkv, H // Hkv, Sk).any(dim=2)
+
+
+# --- the checks ----------------------------------------------------------------------------------------------------------------------
+
+def check_forward(o, lse, ref_o, ref_lse, what=""):
+    """``o`` and ``lse`` of a forward call against the reference's -> (max-abs of o, max-abs of the finite lse)."""
+    tag = f"{what}: " if what else ""
+    o, lse = o.detach().cpu(), lse.detach().cpu()
+    assert o.dtype == torch.float32 and lse.dtype == torch.float32, (o.dtype, lse.dtype)
+    assert tuple(o.shape) == tuple(ref_o.shape) and tuple(lse.shape) == tuple(ref_lse.shape), (tuple(o.shape), tuple(lse.shape))
+    assert bool(torch.isfinite(o).all()), f"{tag}non-finite output"
+    assert not bool(torch.isnan(lse).any()), f"{tag}NaN in the LSE"
+    fin = torch.isfinite(ref_lse)
+    assert torch.equal(torch.isfinite(lse), fin), f"{tag}the rows with a finite LSE are not the reference's"
+    assert bool((lse[~fin] == -INF).all()), f"{tag}a row with no visible key has an LSE other than -inf"
+    assert bool((o[~fin] == 0).all()), f"{tag}a row with no visible key is not exactly zero"
+    eo = float((o.double() - ref_o).abs().max())
+    el = float((lse.double() - ref_lse)[fin].abs().max()) if bool(fin.any()) else 0.0
+    print(f"{tag}o max-abs {eo:.3e}, lse max-abs {el:.3e} (bound {BOUND_O:.0e})")
+    assert eo <= BOUND_O, f"{tag}o max-abs {eo:.3e} > {BOUND_O:.0e}"
+    assert el <= BOUND_O, f"{tag}lse max-abs {el:.3e} > {BOUND_O:.0e}"
+    return eo, el
+
+
+def check_grads(grads, ref, row_seen, key_seen, what="", dropout=False):
+    """(dq, dk, dv) against the reference's, with the rows / keys that are seen (``seen``) -> the largest error relative to its bound's
+    scale ``max(1, max|ref|)``."""
+    tag = f"{what}: " if what else ""
+    rel = BOUND_GRAD_DROP if dropout else BOUND_GRAD
+    worst = 0.0
+    for name, got, r, live in zip(("dq", "dk", "dv"), grads, ref, (row_seen, key_seen, key_seen)):
+        got = got.detach().cpu()
+        assert got.dtype == torch.float32 and tuple(got.shape) == tuple(r.shape), (name, got.dtype, tuple(got.shape), tuple(r.shape))
+        assert bool(torch.isfinite(got).all()), f"{tag}{name} not finite"
+        unseen = got[~live]
+        assert unseen.numel() == 0 or bool((unseen == 0).all()), f"{tag}{name} of rows / keys nothing sees is not exactly zero"
+        err, scale = float((got.double() - r).abs().max()), max(1.0, float(r.abs().max()))
+        print(f"{tag}{name} max-abs {err:.3e} (bound {rel * scale:.3e}, max |ref| {float(r.abs().max()):.3e})")
+        assert err <= rel * scale, f"{tag}{name} max-abs {err:.3e} > {rel * scale:.3e}"
+        worst = max(worst, err / scale)
+    return worst
+
+
+# --- containment: gradients written into guarded buffers through the C ABI ----------------------------------------------------------
+
+NAN16, NAN32 = 0x7FC1, 0x7FC00001                  # NaN in bf16 and in fp16; NaN in fp32
+GUARD = 32                                         # rows of one wave: a whole stray wave still lands inside the test's buffer
+
+
+def guarded(B, S, H, D, gdt, pad=8):
+    """[B, 32 + S + 32, H, D + pad] filled with a NaN pattern -> (buffer, its integer view, the pattern)"""
+    idt, pat = (torch.int32, NAN32) if gdt == torch.float32 else (torch.int16, NAN16)
+    ibuf = torch.full((B, GUARD + S + GUARD, H, D + pad), pat, dtype=idt, device=DEV)
+    return ibuf.view(gdt), ibuf, pat
+
+
+def bwd_into(q, k, v, out, dout, lse, causal, gdt, bufs):
+    """pfa_fa3_bwd writing dq, dk, dv at element [0, 32, 0, 0] of the three guarded buffers, with the buffers' strides.  16-bit
+    operands: gradient rows leave in 16-byte pieces (aligned base, strides in multiples of 8); fp32 operands: 4-byte stores, any stride."""
+    from photonic_flash_attention_amd import _capi, ops
+    B, H, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    f32 = q.dtype == torch.float32
+    delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    a = _capi.PfaFa3BwdArgs()
+    a.size = C.sizeof(_capi.PfaFa3BwdArgs)
+    for name, t in (("q", q), ("k", k), ("v", v), ("o", out), ("do", dout)):
+        setattr(a, "dout" if name == "do" else name, t.data_ptr())
+        for ax, s in zip("bhs", t.stride()[:3]):
+            setattr(a, f"{name}_stride_{ax}", s)
+        assert t.stride(3) == 1
+    for name, buf in zip(("dq", "dk", "dv"), bufs):
+        inner = buf[:, GUARD:]                    # [B, S + 32, H, D + pad] view: same strides, base at row 32
+        assert inner.data_ptr() % 4 == 0 if f32 else (inner.data_ptr() % 16 == 0 and buf.stride(1) % 8 == 0)
+        setattr(a, name, inner.data_ptr())
+        setattr(a, f"{name}_stride_b", buf.stride(0))
+        setattr(a, f"{name}_stride_s", buf.stride(1))
+        setattr(a, f"{name}_stride_h", buf.stride(2))
+    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
+    a.B, a.H, a.Sq, a.Sk, a.D, a.kv_group = B, H, Sq, Sk, D, H // Hkv
+    a.dtype, a.dtype_grad, a.causal = ops._DT[q.dtype], ops._DT[gdt], 1 if causal else 0
+    a.softmax_scale = float(D ** -0.5)
+    a.device_id = torch.cuda.current_device()
+    _capi.check_status(_capi.load().pfa_fa3_bwd(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()

@@ -11,12 +11,12 @@ Tolerance of a 16-bit gradient:  |got - ref|_max <= (tol + u) |ref|_max + 1e-6, 
 
 from __future__ import annotations
 
-import ctypes as C
 import functools
 
 import pytest
 import torch
 
+from dense_testlib import GUARD, bwd_into as _bwd_into, guarded as _guarded      # (shared with tests/test_hip_fp32_kernels.py)
 from photonic_flash_attention_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +25,6 @@ DEV = "cuda:0"
 TORCH_DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 TOL = {"bf16": 1.5e-2, "fp16": 4e-3}             # tests/test_hip_backward.py
 HALF_ULP = {"bf16": 2.0 ** -9, "fp16": 2.0 ** -12}
-GUARD = 32                                         # rows of one wave: a whole stray wave still lands inside the test's buffer
 
 
 # ---- reference -------------------------------------------------------------------------------------------------------
@@ -154,48 +153,11 @@ def test_16bit_gradient_store_at_block_edges(idx, dtype):
 
 
 # ---- 2. containment and full writes, through the C ABI ---------------------------------------------------------------
-NAN16, NAN32 = 0x7FC1, 0x7FC00001                  # NaN in bf16 and in fp16; NaN in fp32
 CONTAIN_CASES = [
     # B, H, Hkv, Sq, Sk, D, causal
     (2, 2, 2, 33, 129, 128, True),
     (2, 4, 2, 257, 100, 64, False),
 ]
-
-
-def _guarded(B, S, H, D, gdt):
-    """[B, 32 + S + 32, H, D + 8] filled with a NaN pattern -> (buffer, its integer view, the pattern)"""
-    idt, pat = (torch.int32, NAN32) if gdt == torch.float32 else (torch.int16, NAN16)
-    ibuf = torch.full((B, GUARD + S + GUARD, H, D + 8), pat, dtype=idt, device=DEV)
-    return ibuf.view(gdt), ibuf, pat
-
-
-def _bwd_into(q, k, v, out, dout, lse, causal, gdt, bufs):
-    """pfa_fa3_bwd writing dq, dk, dv at element [0, 32, 0, 0] of the three guarded buffers, with the buffers' strides"""
-    from photonic_flash_attention_amd import _capi, ops
-    B, H, Sq, D = q.shape
-    Hkv, Sk = k.shape[1], k.shape[2]
-    delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-    a = _capi.PfaFa3BwdArgs()
-    a.size = C.sizeof(_capi.PfaFa3BwdArgs)
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", out), ("do", dout)):
-        setattr(a, "dout" if name == "do" else name, t.data_ptr())
-        for ax, s in zip("bhs", t.stride()[:3]):
-            setattr(a, f"{name}_stride_{ax}", s)
-        assert t.stride(3) == 1
-    for name, buf in zip(("dq", "dk", "dv"), bufs):
-        inner = buf[:, GUARD:]                    # [B, S + 32, H, D + 8] view: same strides, base at row 32
-        assert inner.data_ptr() % 16 == 0 and buf.stride(1) % 8 == 0
-        setattr(a, name, inner.data_ptr())
-        setattr(a, f"{name}_stride_b", buf.stride(0))
-        setattr(a, f"{name}_stride_s", buf.stride(1))
-        setattr(a, f"{name}_stride_h", buf.stride(2))
-    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
-    a.B, a.H, a.Sq, a.Sk, a.D, a.kv_group = B, H, Sq, Sk, D, H // Hkv
-    a.dtype, a.dtype_grad, a.causal = ops._DT[q.dtype], ops._DT[gdt], 1 if causal else 0
-    a.softmax_scale = float(D ** -0.5)
-    a.device_id = torch.cuda.current_device()
-    _capi.check_status(_capi.load().pfa_fa3_bwd(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("wide", [False, True], ids=["grad16", "grad32"])

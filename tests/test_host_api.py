@@ -70,6 +70,15 @@ def test_argument_validation_without_a_gpu(lib):
     for over, want in [(dict(flags=1), -10), (dict(q_stride_b=8190), -6), (dict(k_stride_s=32), -6), (dict(o=0x4002), -7),
                        (dict(Sq=1 << 23), -3)]:
         assert lib.pfa_fa3_check(C.byref(_args(**f32, **over))) == want, over
+    # ... a misaligned q, output rows closer than D, a kernel selector; the dropout keep-mask: fp32 operands only, kept weights scaled up
+    for over, want in [(dict(q=0x1004), -7), (dict(v_stride_h=66), -6), (dict(o_stride_s=32), -6), (dict(flags=43 << 8), -10),
+                       (dict(flags=1 | 45 << 8), -10), (dict(drop_mask=0xb000, drop_scale=0.5), -10),
+                       (dict(drop_mask=0xb000, drop_scale=float("nan")), -10), (dict(drop_mask=0xb000, drop_scale=float("inf")), -10)]:
+        assert lib.pfa_fa3_check(C.byref(_args(**f32, **over))) == want, over
+    assert lib.pfa_fa3_check(C.byref(_args(**f32, drop_mask=0xb000, drop_scale=1.25))) == 0
+    assert lib.pfa_fa3_check(C.byref(_args(**f32, o_stride_s=65, o_stride_h=4225))) == 0          # the output alone may have any stride >= D
+    for dt in (0, 1):
+        assert lib.pfa_fa3_check(C.byref(_args(dtype_in=dt, dtype_out=dt, drop_mask=0xb000, drop_scale=1.25))) == -10, dt
     bad = _args()
     bad.size = 8
     assert lib.pfa_fa3_check(C.byref(bad)) == -2
@@ -78,6 +87,29 @@ def test_argument_validation_without_a_gpu(lib):
     for st in range(0, -11, -1):
         assert _capi.status_string(st) != "unknown pfa_status"
     assert _capi.status_string(-99) == "unknown pfa_status"
+
+
+def test_drop_mask_rules_of_the_tensor_layer():
+    """ops.fa3_forward / fa3_backward hand ``drop_mask`` to the library through ``ops._drop_mask_ptr``: a contiguous u8 / bool
+    [B, H, Sq, Sk] tensor on the operands' device, fp32 operands -- anything else is a ValueError before any pointer is taken."""
+    from photonic_flash_attention_amd import ops
+    B, H, Sq, Sk = 1, 2, 5, 7
+    like = torch.zeros(B, H, Sq, 64)
+    good = torch.ones(B, H, Sq, Sk, dtype=torch.bool)
+    assert ops._drop_mask_ptr(good, B, H, Sq, Sk, like) == good.data_ptr()
+    assert ops._drop_mask_ptr(good.view(torch.uint8), B, H, Sq, Sk, like) == good.data_ptr()
+    bad = [torch.ones(B, H, Sq, 2 * Sk, dtype=torch.bool)[..., ::2],          # not contiguous
+           torch.ones(B, H, Sk, Sq, dtype=torch.bool).transpose(2, 3),
+           torch.ones(B, H, Sq, Sk + 1, dtype=torch.bool),                    # the wrong shape
+           torch.ones(B, 1, Sq, Sk, dtype=torch.bool),
+           torch.ones(B * H, Sq, Sk, dtype=torch.bool),
+           torch.ones(B, H, Sq, Sk, dtype=torch.bool, device="meta"),         # the wrong device
+           torch.ones(B, H, Sq, Sk)]                                          # the wrong dtype
+    for m in bad:
+        with pytest.raises(ValueError):
+            ops._drop_mask_ptr(m, B, H, Sq, Sk, like)
+    with pytest.raises(ValueError):
+        ops._drop_mask_ptr(good, B, H, Sq, Sk, like.bfloat16())               # dropout runs on the fp32 kernels only
 
 
 def test_production_library_refuses_development_variants(lib):
