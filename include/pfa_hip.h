@@ -188,6 +188,11 @@ int pfa_fa3_fwd(const pfa_fa3_args* a, void* stream);
  * produced a->lse (required; a->v and a->o are ignored).  W is addressed base + b*w_stride_b + h*w_stride_h +
  * i*w_stride_q + j (ELEMENT strides, last dim contiguous), dtype w_dtype = a->dtype_in or PFA_DTYPE_FP32.
  * Every element of W is written exactly once (masked ones as zeros): W may be uninitialised.
+ *
+ * Field rules: those of pfa_fa3_fwd for `a` (with a->o NULL, q stands in for it: W is never judged by the output's rules), then
+ * fp32 operands -> PFA_ERR_DTYPE; a->lse NULL -> PFA_ERR_NULL; w_dtype neither a->dtype_in nor fp32 -> PFA_ERR_DTYPE; W not aligned
+ * to its own element size (2 or 4 bytes) -> PFA_ERR_ALIGN; w_stride_q < Sk or a negative W stride -> PFA_ERR_STRIDE.  Nothing more is
+ * asked of W: where its base and row stride are multiples of 16 bytes the rows leave in 16-byte pieces, elsewhere element by element.
  */
 int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_stride_b, int64_t w_stride_h,
                     int64_t w_stride_q, void* stream);

@@ -311,12 +311,20 @@ int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_s
     if (!a || !w) return PFA_ERR_NULL;
     pfa_fa3_args probe = *a;             // same validation as the forward; v/o are not read here
     if (!probe.v) probe.v = probe.k;
-    if (!probe.o) probe.o = w;
+    if (!probe.o) {                      // no forward output: q stands in (an operand, so the forward's rules hold for it) -- never W,
+        probe.o = const_cast<void*>(probe.q);                     // whose rules are its own, below
+        probe.o_stride_b = probe.q_stride_b; probe.o_stride_h = probe.q_stride_h; probe.o_stride_s = probe.q_stride_s;
+        probe.dtype_out = probe.dtype_in;
+    }
     const int st = check(&probe);
     if (st != PFA_OK) return st;
     if (a->dtype_in == PFA_DTYPE_FP32) return PFA_ERR_DTYPE;      // the weights pass is MFMA only: hand it the 16-bit operands
     if (!a->lse) return PFA_ERR_NULL;
     if (w_dtype != a->dtype_in && w_dtype != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
+    // W: aligned to its element (the kernel stores 16-byte pieces only where base and row stride allow it, else per element); rows
+    // forward and at least Sk apart
+    if (reinterpret_cast<uintptr_t>(w) % (w_dtype == PFA_DTYPE_FP32 ? 4 : 2) != 0) return PFA_ERR_ALIGN;
+    if (w_stride_q < a->Sk || w_stride_b < 0 || w_stride_h < 0) return PFA_ERR_STRIDE;
 
     pfa::WeightsParams p;
     p.q = a->q; p.k = a->k; p.lse = a->lse; p.w = w;

@@ -1,5 +1,5 @@
-"""What the tests of the dense calls (``ops.fa3_forward`` / ``ops.fa3_backward`` on the exact-fp32 kernels) share: one fp64 reference,
-the error bounds, the checks, and the guarded buffers of the containment tests.  Plain functions and constants; pytest collects nothing
+"""What the tests of the dense calls (``ops.fa3_forward`` / ``ops.fa3_backward`` on the exact-fp32 kernels, and the attention-weights pass
+``pfa_fa3_weights``: the last section) share: one fp64 reference, the error bounds, the checks, and the guarded buffers of the containment tests.  Plain functions and constants; pytest collects nothing
 from here, and tests/test_dense_testlib.py tests it on the CPU.  The counterpart of tests/kvcache_testlib.py.
 
 The reference is fp64 attention of ``q [B,H,Sq,D]`` over ``k/v [B,Hkv,Sk,D]`` (grouped heads by ``repeat_interleave``, so autograd sums
@@ -46,6 +46,22 @@ def visible(B, H, Sq, Sk, *, causal=False, seqlens=None, keep=None):
     return vis
 
 
+def softmax_parts(qd, kd, vis, scale):
+    """What ``reference`` and ``weights_reference`` share.  fp64 ``qd [B,H,Sq,D]``, ``kd [B,Hkv,Sk,D]`` and ``vis [B,H,Sq,Sk]`` -> (the
+    scaled scores before masking; the normalised weights, zero rows where no key is seen; the detached LSE [B,H,Sq], -inf there)."""
+    g = qd.shape[1] // kd.shape[1]
+    raw = (qd @ kd.repeat_interleave(g, dim=1).transpose(-1, -2)) * scale
+    s = raw.masked_fill(~vis, -INF)
+    m = s.detach().amax(-1, keepdim=True)
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    safe = torch.where(l > 0, l, torch.ones_like(l))
+    w = p / safe                                                  # the normalised weights: zero rows where no key is seen
+    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, -INF))[..., 0].detach()
+    return raw, w, lse
+
+
 def reference(q, k, v, *, causal=False, seqlens=None, keep=None, drop=None, drop_scale=1.0, scale=None, dout=None):
     """fp64 on the CPU -> (o [B,H,Sq,D], lse [B,H,Sq]), and (dq [B,H,Sq,D], dk, dv [B,Hkv,Sk,D]) behind them when ``dout`` is given."""
     B, H, Sq, D = q.shape
@@ -54,18 +70,10 @@ def reference(q, k, v, *, causal=False, seqlens=None, keep=None, drop=None, drop
     assert H == g * Hkv and k.shape == (B, Hkv, Sk, D) and v.shape == (B, Hkv, Sk, D)
     qd, kd, vd = (t.detach().cpu().double().clone().requires_grad_(dout is not None) for t in (q, k, v))
     vis = visible(B, H, Sq, Sk, causal=causal, seqlens=seqlens, keep=keep)
-    s = (qd @ kd.repeat_interleave(g, dim=1).transpose(-1, -2)) * (D ** -0.5 if scale is None else scale)
-    s = s.masked_fill(~vis, -INF)
-    m = s.detach().amax(-1, keepdim=True)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    safe = torch.where(l > 0, l, torch.ones_like(l))
-    w = p / safe                                                  # the normalised weights: zero rows where no key is seen
+    _, w, lse = softmax_parts(qd, kd, vis, D ** -0.5 if scale is None else scale)
     if drop is not None:
         w = w * (drop.cpu().to(torch.float64) * float(drop_scale))
     o = w @ vd.repeat_interleave(g, dim=1)
-    lse = torch.where(l > 0, m + torch.log(safe), torch.full_like(l, -INF))[..., 0].detach()
     if dout is None:
         return o, lse
     dq, dk, dv = torch.autograd.grad(o, (qd, kd, vd), dout.detach().cpu().double())
@@ -161,3 +169,109 @@ def bwd_into(q, k, v, out, dout, lse, causal, gdt, bufs):
     a.device_id = torch.cuda.current_device()
     _capi.check_status(_capi.load().pfa_fa3_bwd(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
+
+
+# --- the attention-weights pass (pfa_fa3_weights): reference, a-priori bound, check, guarded call ----------------------------------
+
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+U32 = 2.0 ** -24                                   # unit roundoff of fp32
+ROUND16 = {torch.bfloat16: (2.0 ** -8, 0.0),       # 16-bit W: (unit roundoff of round-to-nearest, half the subnormal spacing where
+           torch.float16: (2.0 ** -11, 2.0 ** -25)}   # subnormals occur: fp16's are 2^-24 apart; bf16 has fp32's exponent range)
+
+
+def weights_reference(q, k, *, causal=False, seqlens=None, keep=None, scale=None, lse32=None):
+    """fp64 on the CPU -> (W [B,H,Sq,Sk], the fp32 LSE [B,H,Sq] it was formed with).  ``W = exp(scale * <q_i, k_j> - lse_i)`` where
+    ``visible(...)`` holds and exactly 0 elsewhere; grouped heads by ``repeat_interleave``.  ``lse32=None``: the fp64 LSE rounded to
+    fp32, returned so that the kernel under test is handed the same values.  ``lse32`` given (a forward kernel's own output): used as
+    it is, which keeps the forward's error out of a check of the weights pass.  Rows whose LSE is -inf are all zero."""
+    B, H, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    assert H % Hkv == 0 and k.shape == (B, Hkv, Sk, D)
+    qd, kd = q.detach().cpu().double(), k.detach().cpu().double()
+    vis = visible(B, H, Sq, Sk, causal=causal, seqlens=seqlens, keep=keep)
+    raw, _, lse = softmax_parts(qd, kd, vis, D ** -0.5 if scale is None else scale)
+    lse32 = lse.float() if lse32 is None else lse32.detach().cpu().float()
+    assert tuple(lse32.shape) == (B, H, Sq)
+    live = vis & torch.isfinite(lse32)[..., None]
+    e = raw - torch.where(torch.isfinite(lse32), lse32.double(), torch.zeros((), dtype=torch.float64))[..., None]
+    return torch.where(live, torch.exp(e), torch.zeros((), dtype=torch.float64)), lse32
+
+
+def weights_bound(q, k, ref, lse32, *, scale=None, wdt=torch.float32):
+    """The per-element a-priori error bound of a W that the kernel's arithmetic computes for ``ref`` -- fp32 MFMA accumulation of the D
+    exact 16-bit products (two roundings a step), ``fma(s, c, -lse * log2e)`` with its three fp32 roundings, ``v_exp_f32``, and for a
+    16-bit W the store's round-to-nearest.  With u = 2^-24, c = scale * log2(e), A_ij = sum_d |q_id k_jd|, L_i = |lse_i * log2(e)|:
+
+        bound32 = W * (ln2 * (2 D u c A + 4 u (|c s| + L)) + 2 u)          bound16 = bound32 * (1 + h) + W * h + t
+
+    Derived from the arithmetic, never from what a kernel returned.  Zero where ``ref`` is zero: those elements must be exact."""
+    B, H, Sq, D = q.shape
+    g = H // k.shape[1]
+    c = (D ** -0.5 if scale is None else scale) * LOG2E
+    qd, kd = q.detach().cpu().double(), k.detach().cpu().double().repeat_interleave(g, dim=1)
+    s = qd @ kd.transpose(-1, -2)
+    A = qd.abs() @ kd.abs().transpose(-1, -2)
+    L = torch.where(torch.isfinite(lse32), lse32.double() * LOG2E, torch.zeros((), dtype=torch.float64)).abs()[..., None]
+    b32 = ref * (LN2 * (2 * D * U32 * c * A + 4 * U32 * ((c * s).abs() + L)) + 2 * U32)
+    if wdt == torch.float32:
+        return b32
+    h, t = ROUND16[wdt]
+    return torch.where(ref > 0, b32 * (1 + h) + ref * h + t, torch.zeros((), dtype=torch.float64))
+
+
+def check_weights(w, ref, bound, vis, what="", wdt=None):
+    """A weights tensor against ``weights_reference`` within ``weights_bound``: dtype and shape, every element finite, exactly 0.0
+    wherever ``vis`` is False, ``|w - ref| <= bound`` at EVERY element -> the largest ``err / bound`` (printed)."""
+    tag = f"{what}: " if what else ""
+    w = w.detach().cpu()
+    assert w.dtype in (torch.float32, torch.bfloat16, torch.float16) and (wdt is None or w.dtype == wdt), (w.dtype, wdt)
+    assert tuple(w.shape) == tuple(ref.shape) == tuple(vis.shape) == tuple(bound.shape), (tuple(w.shape), tuple(ref.shape))
+    wd = w.double()
+    assert bool(torch.isfinite(wd).all()), f"{tag}non-finite weight"
+    hidden = wd[~vis]
+    assert hidden.numel() == 0 or bool((hidden == 0).all()), f"{tag}a weight nothing sees is not exactly zero"
+    err = (wd - ref).abs()
+    ratio = torch.where(err > 0, err / bound, torch.zeros((), dtype=torch.float64))          # (x / 0 = inf: over a zero bound)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    print(f"{tag}weights ({str(w.dtype).replace('torch.', '')}) max err / bound {worst:.3f}, max-abs {float(err.max()):.3e}")
+    over = err > bound
+    if bool(over.any()):
+        i = tuple(int(x) for x in torch.nonzero(over)[0])
+        raise AssertionError(f"{tag}{int(over.sum())} weights over their bound, the first at {i}: {float(wd[i]):.9e} for "
+                             f"{float(ref[i]):.9e}, bound {float(bound[i]):.3e}; worst err / bound {worst:.3f}")
+    return worst
+
+
+def guarded_weights(wdt, B, H, Sq, Sk, *, pad, col_off, device=DEV):
+    """[B, H + 1, 32 + Sq + 32, col_off + Sk + pad] filled with a NaN pattern -> (its [B,H,Sq,Sk] window at [0, 0, 32, col_off] as
+    ``wdt``, the whole buffer's integer view)"""
+    idt, pat = (torch.int32, NAN32) if wdt == torch.float32 else (torch.int16, NAN16)
+    ibuf = torch.full((B, H + 1, GUARD + Sq + GUARD, col_off + Sk + pad), pat, dtype=idt, device=device)
+    return ibuf.view(wdt)[:, :H, GUARD:GUARD + Sq, col_off:col_off + Sk], ibuf
+
+
+def weights_into(args, wdt, B, H, Sq, Sk, *, pad, col_off):
+    """pfa_fa3_weights for the forward arguments ``args`` (``ops.build_args``; ``args.lse`` set) writing W into the window of a
+    ``guarded_weights`` buffer, with the buffer's strides -> (the window, the buffer's integer view).  ``check_guards`` on the latter."""
+    from photonic_flash_attention_amd import _capi, ops
+    inner, ibuf = guarded_weights(wdt, B, H, Sq, Sk, pad=pad, col_off=col_off)
+    st = _capi.load().pfa_fa3_weights(C.byref(args), C.c_void_p(inner.data_ptr()), ops._DT[wdt], inner.stride(0), inner.stride(1),
+                                      inner.stride(2), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _capi.check_status(st)
+    torch.cuda.synchronize()
+    return inner, ibuf
+
+
+def check_guards(ibuf, H, Sq, Sk, col_off, what=""):
+    """The integer view of ``weights_into``'s buffer: every element outside the [B,H,Sq,Sk] window still holds the NaN pattern bit for
+    bit (nothing was written out of bounds), and no element inside does (every one was written)."""
+    tag = f"{what}: " if what else ""
+    i = ibuf.detach().cpu()
+    pat = NAN32 if i.dtype == torch.int32 else NAN16
+    inside = torch.zeros(i.shape, dtype=torch.bool)
+    inside[:, :H, GUARD:GUARD + Sq, col_off:col_off + Sk] = True
+    hit = (i != pat) & ~inside
+    assert not bool(hit.any()), f"{tag}{int(hit.sum())} guard elements overwritten, the first at {tuple(int(x) for x in torch.nonzero(hit)[0])}"
+    left = (i == pat) & inside
+    assert not bool(left.any()), f"{tag}{int(left.sum())} elements of W never written, the first at {tuple(int(x) for x in torch.nonzero(left)[0])}"

@@ -1,14 +1,18 @@
 """CPU tests of tests/dense_testlib.py, the reference and the checks every fp32-kernel GPU test relies on: the fp64 reference against the
 oracle (outputs, LSE and autograd gradients) where the two overlap -- no mask, causal, seqlens_k --, against a direct eager
 ``dropout(softmax) @ v`` with a fixed keep-mask, its conventions for rows that see no key, its grouped-head gradient, and the two checks
-against outputs they must reject."""
+against outputs they must reject.  The same for the attention-weights pass: ``weights_reference`` against a per-row loop, ``weights_bound``
+against an fp32 emulation of the kernel's expression, ``check_weights`` and ``check_guards`` against what they must reject."""
 
 from __future__ import annotations
 
 import pytest
 import torch
 
-from dense_testlib import INF, check_forward, check_grads, reference, seen, visible
+import math
+
+from dense_testlib import (INF, LOG2E, NAN16, NAN32, check_forward, check_grads, check_guards, check_weights, guarded_weights, reference,
+                           seen, visible, weights_bound, weights_reference)
 from oracle import fa3_oracle as orc
 from photonic_flash_attention_amd import synth
 
@@ -140,3 +144,136 @@ def test_the_checks_reject_what_they_must():
     gs = list(good[2:]); gs[2] = bad
     check_grads(gs, (dq, dk, dv), row_seen, key_seen, "dropout bound", dropout=True)      # ... inside the one with
     grads_fail(2, good[4][:, :1])                         # a wrong shape
+
+
+# --- the attention-weights pass ------------------------------------------------------------------------------------------------------
+
+def _weights_case(g):
+    """q [B,6,SQ,D], k [B,6/g,SK,D] in bf16 values, a keep-mask with dead rows, lengths that include 0 and one above SK"""
+    Hq = 6
+    q = torch.from_numpy(synth.normal_f32((B, SQ, Hq, D), 70 + g)).permute(0, 2, 1, 3).bfloat16()
+    k = torch.from_numpy(synth.normal_f32((B, SK, Hq // g, D), 80 + g)).permute(0, 2, 1, 3).bfloat16()
+    gen = torch.Generator().manual_seed(g)
+    keep = torch.rand(B, Hq, SQ, SK, generator=gen) < 0.7
+    keep[:, 1, 2] = False                                 # a row that sees nothing
+    keep[:, :, :, 0] = True
+    keep[:, 1, 2] = False
+    return q, k, keep
+
+
+@pytest.mark.parametrize("g", [1, 2, 3])
+@pytest.mark.parametrize("causal, lens, masked", [(False, None, False), (True, None, False), (False, [0, SK + 4], False),
+                                                  (True, [5, -2], True), (False, None, True), (True, [SK, 3], True)])
+def test_weights_reference_against_a_per_row_loop(g, causal, lens, masked):
+    q, k, keep = _weights_case(g)
+    keep = keep if masked else None
+    Hq, scale = q.shape[1], 0.3
+    w, lse32 = weights_reference(q, k, causal=causal, seqlens=lens, keep=keep, scale=scale)
+    assert w.dtype == torch.float64 and lse32.dtype == torch.float32 and tuple(w.shape) == (B, Hq, SQ, SK) and tuple(lse32.shape) == (B, Hq, SQ)
+    vis = visible(B, Hq, SQ, SK, causal=causal, seqlens=lens, keep=keep)
+    want = torch.zeros(B, Hq, SQ, SK, dtype=torch.float64)
+    for b in range(B):
+        n = SK if lens is None else min(max(lens[b], 0), SK)
+        for h in range(Hq):
+            for i in range(SQ):
+                js = [j for j in range(n) if (not causal or j <= i) and (keep is None or bool(keep[b, h, i, j]))]
+                assert js == [j for j in range(SK) if bool(vis[b, h, i, j])]
+                sc = {j: scale * sum(float(q[b, h, i, d]) * float(k[b, h // g, j, d]) for d in range(D)) for j in js}
+                if not js:
+                    assert float(lse32[b, h, i]) == -INF
+                    continue
+                m = max(sc.values())
+                lse = m + math.log(sum(math.exp(x - m) for x in sc.values()))
+                assert float(lse32[b, h, i]) == float(torch.tensor(lse, dtype=torch.float64).float())
+                for j in js:
+                    want[b, h, i, j] = math.exp(sc[j] - float(lse32[b, h, i]))
+    assert float((w - want).abs().max()) <= 1e-12
+    assert bool((w[~vis] == 0).all())
+    # a row sums to 1 up to the fp32 rounding of its LSE (|lse| 2^-24 <= 1e-6 here), a row that sees no key to exactly 0
+    live = vis.any(-1)
+    assert float((w.sum(-1)[live] - 1).abs().max()) <= 1e-6 and bool((w.sum(-1)[~live] == 0).all())
+    # a given LSE is used as it is, and -inf in it zeroes the row
+    given = lse32.clone() + 0.25
+    given[0, 0, 0] = -INF
+    w2, back = weights_reference(q, k, causal=causal, seqlens=lens, keep=keep, scale=scale, lse32=given)
+    assert back.equal(given) and bool((w2[0, 0, 0] == 0).all())
+    rest = torch.ones(B, Hq, SQ, dtype=torch.bool)
+    rest[0, 0, 0] = False
+    shift = torch.exp(torch.nan_to_num(lse32.double() - given.double(), nan=0.0, neginf=0.0))[..., None]       # (fp32 sum: not exactly 0.25)
+    assert float((w2 - w * shift)[rest].abs().max()) <= 1e-12
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("Dh", [64, 128])
+@pytest.mark.parametrize("qscale", [1.0, 2.5])
+def test_fp32_emulation_of_the_kernel_stays_inside_the_weights_bound(dt, Dh, qscale):
+    """torch's fp32 matmul, the fp32 product ``lse * log2e`` and an fp32 ``exp2`` are the kernel's arithmetic up to the order of the sums
+    and one more rounding (no fma): well inside ``weights_bound`` for an fp32 W, and inside it for the 16-bit stores."""
+    Bq, Hq, Sq, Sk = 1, 2, 96, 160
+    name = "bf16" if dt == torch.bfloat16 else "fp16"
+    q, k, _ = (t.permute(0, 2, 1, 3) for t in synth.qkv(Bq, Hq, Sq, Sk, Dh, 90 + Dh, name))
+    q = (q.float() * qscale).to(dt)
+    lens = [Sk - 9]
+    ref, lse32 = weights_reference(q, k, causal=True, seqlens=lens)
+    vis = visible(Bq, Hq, Sq, Sk, causal=True, seqlens=lens)
+    c = torch.tensor(Dh ** -0.5 * LOG2E, dtype=torch.float32)
+    e = (q.float() @ k.float().transpose(-1, -2)) * c - (lse32 * torch.tensor(LOG2E, dtype=torch.float32))[..., None]
+    w32 = torch.where(vis, torch.exp2(e), torch.zeros((), dtype=torch.float32))
+    assert w32.dtype == torch.float32
+    r32 = check_weights(w32, ref, weights_bound(q, k, ref, lse32, wdt=torch.float32), vis, "emulation, fp32 W", wdt=torch.float32)
+    r16 = check_weights(w32.to(dt), ref, weights_bound(q, k, ref, lse32, wdt=dt), vis, f"emulation, {name} W", wdt=dt)
+    assert r32 <= 0.25 and r16 <= 1.0, (r32, r16)
+    if qscale > 1 and dt == torch.float16:
+        assert bool(((w32.to(dt) > 0) & (w32.to(dt) < 2.0 ** -14)).any())        # fp16 subnormals do occur at this scale
+
+
+def test_check_weights_rejects_what_it_must():
+    Bq, Hq, Sq, Sk, Dh = 2, 3, 40, 72, 64
+    q, k, _ = (t.permute(0, 2, 1, 3) for t in synth.qkv(Bq, Hq, Sq, Sk, Dh, 95, "bf16"))
+    ref, lse32 = weights_reference(q, k, causal=True)
+    vis = visible(Bq, Hq, Sq, Sk, causal=True)
+    bound = weights_bound(q, k, ref, lse32)
+    good = ref.float()
+    assert check_weights(good, ref, bound, vis, "good", wdt=torch.float32) <= 1.0
+
+    def fails(w, **kw):
+        with pytest.raises(AssertionError):
+            check_weights(w, ref, bound, vis, **kw)
+
+    bad = good.clone(); bad[1, 2, 30, 7], bad[1, 2, 30, 8] = good[1, 2, 30, 8], good[1, 2, 30, 7]
+    fails(bad)                                            # two neighbouring keys swapped in one row
+    bad = good.clone(); bad[0, 1, 17] *= 1.001
+    fails(bad)                                            # one row scaled
+    bad = good.clone(); bad[0, 0, 3, 4] = 1e-30
+    fails(bad)                                            # a non-zero above the diagonal
+    bad = good.clone(); bad[1, 0, 5, 2] = float("nan")
+    fails(bad)
+    bad = good.clone(); bad[0, 1], bad[0, 2] = good[0, 2], good[0, 1]
+    fails(bad)                                            # one head's rows exchanged with another's
+    fails(good, wdt=torch.bfloat16)                       # not the dtype asked for
+    fails(good[:, :2])                                    # a wrong shape
+    b16 = weights_bound(q, k, ref, lse32, wdt=torch.bfloat16)
+    assert check_weights(good.bfloat16(), ref, b16, vis, "good bf16", wdt=torch.bfloat16) <= 1.0
+    with pytest.raises(AssertionError):
+        check_weights((good * (1 + 2.0 ** -6)).bfloat16(), ref, b16, vis)         # beyond the bf16 rounding
+
+
+@pytest.mark.parametrize("wdt, pat", [(torch.float32, NAN32), (torch.bfloat16, NAN16), (torch.float16, NAN16)])
+def test_check_guards_rejects_a_stray_store_and_a_missing_one(wdt, pat):
+    Bq, Hq, Sq, Sk, pad, off = 2, 2, 5, 9, 3, 1
+    inner, ibuf = guarded_weights(wdt, Bq, Hq, Sq, Sk, pad=pad, col_off=off, device="cpu")
+    assert tuple(inner.shape) == (Bq, Hq, Sq, Sk) and tuple(ibuf.shape) == (Bq, Hq + 1, 32 + Sq + 32, off + Sk + pad)
+    assert bool(torch.isnan(inner.float()).all()) and bool((ibuf == pat).all())
+    with pytest.raises(AssertionError):
+        check_guards(ibuf, Hq, Sq, Sk, off)               # nothing written yet
+    inner.copy_(torch.rand(Bq, Hq, Sq, Sk).to(wdt))
+    check_guards(ibuf, Hq, Sq, Sk, off)
+    for at in [(0, 0, 31, off), (0, 0, 32, off - 1), (1, 1, 32 + Sq, off + Sk - 1), (0, 1, 33, off + Sk), (1, Hq, 32, off)]:
+        stray = ibuf.clone()
+        stray[at] = 0                                     # the row in front, the column in front, the row behind, the column behind, the next head
+        with pytest.raises(AssertionError):
+            check_guards(stray, Hq, Sq, Sk, off)
+    missing = ibuf.clone()
+    missing[1, 1, 32 + Sq - 1, off + Sk - 1] = pat
+    with pytest.raises(AssertionError):
+        check_guards(missing, Hq, Sq, Sk, off)

@@ -89,6 +89,39 @@ def test_argument_validation_without_a_gpu(lib):
     assert _capi.status_string(-99) == "unknown pfa_status"
 
 
+def test_weights_pass_argument_validation_without_a_gpu(lib):
+    """pfa_fa3_weights' refusals, none of which reaches a device; what it accepts is shown by PFA_ERR_DEVICE (-8) for a device ordinal no
+    machine has -- the one rule behind the argument rules -- so that nothing is launched on a machine with a GPU either."""
+    no_dev = 9999
+
+    def call(w=0x8000, w_dtype=0, strides=(64 * 64 * 2, 64 * 64, 64), a=True, **over):
+        args = _args(**{**dict(lse=0x5000, device_id=no_dev), **over})
+        return lib.pfa_fa3_weights(C.byref(args) if a else None, C.c_void_p(w), w_dtype, *strides, None)
+
+    assert call() == -8                                                   # valid: only the device is missing
+    assert call(a=False) == -1 and call(w=0) == -1                        # a or w NULL
+    assert call(dtype_in=2, dtype_out=2, w_dtype=2) == -5                 # fp32 operands: the pass is MFMA only
+    assert call(lse=0) == -1                                              # the LSE is required
+    assert call(w_dtype=1) == -5 and call(w_dtype=3) == -5                # W in the operands' type or fp32, nothing else
+    assert call(dtype_in=1, dtype_out=1, w_dtype=1) == -8 and call(dtype_in=1, dtype_out=1, w_dtype=2) == -8
+    # the forward's errors pass through: a misaligned q, a bad head dim, a stride, both masks
+    assert call(q=0x1004) == -7 and call(D=80) == -4 and call(k_stride_s=129) == -6 and call(key_mask=0x6000, mask=0x7000) == -10
+    # v and o are not read: NULL is fine, and W is never judged by the output's 16-byte rule -- an fp32 W aligned to 4 bytes, a 16-bit
+    # W aligned to 2, both with odd row strides (the kernel then stores element by element)
+    assert call(v=0, o=0) == -8
+    assert call(o=0, w=0x8004, w_dtype=2, strides=(2 * 64 * 65, 64 * 65, 65)) == -8
+    assert call(o=0, w=0x8002, strides=(2 * 64 * 67, 64 * 67, 67)) == -8
+    assert call(o=0, dtype_in=1, w=0x8002, w_dtype=1) == -8               # (o NULL: dtype_out is not looked at either)
+    assert call(w=0x8004, w_dtype=2) == -8 and call(w=0x8002) == -8       # ... the same with o set
+    # W's own rules, with o set or not: aligned to its element, rows forward and at least Sk apart
+    for o in (0, 0x4000):
+        assert call(o=o, w=0x8002, w_dtype=2) == -7 and call(o=o, w=0x8001) == -7
+        assert call(o=o, strides=(8192, 4096, 63)) == -6 and call(o=o, strides=(8192, 4096, -64)) == -6
+        assert call(o=o, strides=(-8192, 4096, 64)) == -6 and call(o=o, strides=(8192, -4096, 64)) == -6
+        assert call(o=o, strides=(0, 0, 64)) == -8                        # (a broadcast W is the caller's business)
+    assert call(o=0x4008) == -7                                           # an o that is given is still the forward's o
+
+
 def test_drop_mask_rules_of_the_tensor_layer():
     """ops.fa3_forward / fa3_backward hand ``drop_mask`` to the library through ``ops._drop_mask_ptr``: a contiguous u8 / bool
     [B, H, Sq, Sk] tensor on the operands' device, fp32 operands -- anything else is a ValueError before any pointer is taken."""
