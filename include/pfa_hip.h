@@ -19,6 +19,9 @@
  * movement of copy-on-write for sequences that share pages.
  * v9, additive: pfa_fa3_tree_mask and pfa_fa3_decode_tree* -- the decode with a 64-bit visibility word per query row over the step's own
  * keys in place of the causal triangle: the verification of a drafted token TREE (speculative decoding) in one pass over the cache.
+ * v9, additive: pfa_fa3_varlen_args / pfa_fa3_varlen_bwd_args and pfa_fa3_varlen_* -- packed variable-length attention for training,
+ * forward and backward: sequences of different lengths one after the other in [total, H, D] tensors, cu_seqlens_q / cu_seqlens_k on
+ * the device (flash-attn's flash_attn_varlen_func), on the dense 16-bit kernels in a packed mode.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -862,6 +865,123 @@ int pfa_page_copy(const pfa_page_copy_args* a, void* stream);
 /* Introspection: the kernel name page_copy_{bf16|fp16}_d{D} ("_rows" appended with rows) into buf (NUL terminated, truncated to n);
  * returns the workgroups, or a pfa_status. */
 int pfa_page_copy_describe(const pfa_page_copy_args* a, char* buf, size_t n);
+
+/*
+ * Packed variable-length attention for training, forward and backward (ABI v9, additive): pfa_fa3_fwd / pfa_fa3_bwd for a batch of
+ * sequences of DIFFERENT lengths that is not padded -- flash-attn's flash_attn_varlen_func.  The rows of all sequences lie one after the
+ * other in one tensor per operand and two cu_seqlens arrays say where each sequence's query rows and keys start.  The kernels are the
+ * dense 16-bit ones (the 8-wave forward, the dQ and the dK/dV kernel) in their packed mode: same tiles, same arithmetic.
+ *
+ *   q, o, dout, dq  [total_q, H, D] by element strides *_stride_s (between packed rows) and *_stride_h (last dim contiguous); there is
+ *                   no batch stride.  o in dtype_in or fp32; dq / dk / dv in dtype or fp32.
+ *   k, v, dk, dv    [total_k, Hkv, D] likewise.  Grouped-query heads: H % Hkv == 0, query head h reads K/V head h / (H / Hkv); dK / dV
+ *                   are summed over each group inside the kernel.
+ *   cu_seqlens_q    required int32 [B + 1] on the device, non-decreasing, cu[0] >= 0, cu[B] <= total_q: sequence b owns the packed rows
+ *   cu_seqlens_k    cu[b] .. cu[b + 1] - 1 (none if the two are equal); cu_seqlens_k likewise for the keys, against total_k.  Read by
+ *                   the kernels as s_b = clamp(cu[b], 0, total), e_b = clamp(cu[b + 1], s_b, total), S_b = min(e_b - s_b, max_seqlen):
+ *                   bad values give wrong numbers, never an address outside the packed tensors (the rule of
+ *                   pfa_fa3_prefill_varlen_args).  The sequence's offset s_b * stride_s is added to the 64-bit base pointers; buffer
+ *                   descriptors end at the sequence's own last row, so a neighbouring sequence is never loaded and never written.
+ *   max_seqlen_q    host bounds on the rows / keys of one sequence, 1 <= max_seqlen_* <= total_*.  They size the grids from host shapes
+ *   max_seqlen_k    only -- forward and dQ: B * H * ceil(max_seqlen_q / 256) workgroups, dK/dV: B * Hkv * ceil(max_seqlen_k / 128) -- so
+ *                   a captured graph stays valid while the contents of the cu_seqlens arrays change between replays.  Of a longer
+ *                   sequence only the first max_seqlen rows / keys take part; the others are neither read nor written.
+ *   causal          1: the DENSE rule, top-left aligned per sequence -- row i of sequence b sees key j iff j <= i.  This is not the
+ *                   bottom-right rule of the calls over a KV cache; for packed self-attention (cu_seqlens_k is cu_seqlens_q) the two
+ *                   coincide.  0: every row sees its sequence's Sk_b keys.
+ *   lse, delta      fp32 [H, total_q], entry h * total_q + (s_b + i): the layout of pfa_fa3_prefill_varlen and of flash-attn.  lse is
+ *                   optional in the forward and required in the backward; delta is the backward's scratch of
+ *                   pfa_fa3_varlen_bwd_workspace_bytes() bytes.
+ * A row with no visible key (Sk_b = 0) gets O = 0, LSE = -inf and dQ = 0.  Keys no row sees (Sq_b = 0, or under causal the keys
+ * j >= Sq_b) get dK = dV = exactly 0.  Every row of dQ in [s_b, s_b + Sq_b) and every row of dK / dV in [s_b, s_b + Sk_b) is written
+ * exactly once, so the gradient buffers may be uninitialised.  Packed rows no sequence covers -- gaps between sequences, the tail behind
+ * cu[B], rows past max_seqlen -- are never read or written.  A workgroup without rows (keys) of its sequence returns at once.
+ *
+ * The results are bit for bit those of pfa_fa3_fwd (8-wave kernel, selector 44) and pfa_fa3_bwd called per sequence on that sequence's
+ * rows alone; no atomics, bitwise reproducible.  dtype_out = fp32 selects split P (P carried as hi + lo), as ops.fa3_forward does.
+ *
+ * Out of scope (use the dense calls): key and element masks, seqlens_k, dropout, the exact-fp32 kernels, split-P selection other than
+ * through dtype_out, the persistent assembly forward and the 4-wave forward -- the packed forward runs on the 8-wave schedule only.
+ *
+ * Field rules: those of pfa_fa3_fwd / pfa_fa3_bwd where the fields coincide (D in {64, 128}, bf16 / fp16 operands, output and gradients
+ * in the operand dtype or fp32, strides multiples of 8 elements -- 4 for fp32 outputs --, base pointers 16-byte aligned, int32 / fp32
+ * arrays 4-byte aligned, one sequence's slab of max_seqlen rows at the row stride inside the 32-bit descriptor, k / v rows forward), and:
+ * a NULL cu_seqlens pointer -> PFA_ERR_NULL; total_* < 1, max_seqlen_* < 1, max_seqlen_* > total_*, H % Hkv != 0 or more workgroups than
+ * a grid holds -> PFA_ERR_SHAPE; flags or reserved0 not 0 -> PFA_ERR_FLAGS.
+ */
+typedef struct pfa_fa3_varlen_args {
+    uint32_t size;              /* = sizeof(pfa_fa3_varlen_args) */
+    uint32_t flags;             /* must be 0 */
+    const void* q;
+    const void* k;
+    const void* v;
+    void*       o;
+    float*      lse;            /* optional [H, total_q] */
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;
+    int64_t q_stride_s, q_stride_h;
+    int64_t k_stride_s, k_stride_h;
+    int64_t v_stride_s, v_stride_h;
+    int64_t o_stride_s, o_stride_h;
+    int32_t B, H, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D;
+    int32_t dtype_in;           /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16 */
+    int32_t dtype_out;          /* = dtype_in, or PFA_DTYPE_FP32 (split P) */
+    int32_t causal;             /* top-left per sequence, see above */
+    float   softmax_scale;
+    int32_t device_id;
+    int32_t reserved0;          /* must be 0 */
+} pfa_fa3_varlen_args;
+
+/* Validate `a` without launching: PFA_OK or the error pfa_fa3_varlen_fwd would return. */
+int pfa_fa3_varlen_check(const pfa_fa3_varlen_args* a);
+/* Enqueue the packed forward (one launch) on `stream`. */
+int pfa_fa3_varlen_fwd(const pfa_fa3_varlen_args* a, void* stream);
+/* Introspection: the kernel name fa3_fwd_varlen_{bf16|fp16}_d{D}_{causal|full}[_splitp]_{o16|o32} into buf (NUL terminated, truncated
+ * to n); returns the workgroups, or a pfa_status. */
+int pfa_fa3_varlen_describe(const pfa_fa3_varlen_args* a, char* buf, size_t n);
+
+typedef struct pfa_fa3_varlen_bwd_args {
+    uint32_t size;              /* = sizeof(pfa_fa3_varlen_bwd_args) */
+    uint32_t flags;             /* must be 0 */
+    const void* q;
+    const void* k;
+    const void* v;
+    const void* o;              /* forward output, in `dtype` */
+    const void* dout;           /* gradient of the forward output, in `dtype` */
+    const float* lse;           /* [H, total_q] from the forward */
+    void* dq;
+    void* dk;
+    void* dv;
+    float* delta;               /* scratch [H, total_q] */
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k;
+    int64_t q_stride_s, q_stride_h;
+    int64_t k_stride_s, k_stride_h;
+    int64_t v_stride_s, v_stride_h;
+    int64_t o_stride_s, o_stride_h;
+    int64_t do_stride_s, do_stride_h;
+    int64_t dq_stride_s, dq_stride_h;
+    int64_t dk_stride_s, dk_stride_h;
+    int64_t dv_stride_s, dv_stride_h;
+    int32_t B, H, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D;
+    int32_t dtype;              /* PFA_DTYPE_BF16 | PFA_DTYPE_FP16: q, k, v, o, dout */
+    int32_t dtype_grad;         /* = dtype, or PFA_DTYPE_FP32: dq, dk, dv */
+    int32_t causal;
+    float   softmax_scale;
+    int32_t device_id;
+    int32_t reserved0;          /* must be 0 */
+} pfa_fa3_varlen_bwd_args;
+
+/* Bytes of `delta`: H * total_q fp32 (0 for a NULL or shapeless block). */
+size_t pfa_fa3_varlen_bwd_workspace_bytes(const pfa_fa3_varlen_bwd_args* a);
+/* Validate `a` without launching: PFA_OK or the error pfa_fa3_varlen_bwd would return. */
+int pfa_fa3_varlen_bwd_check(const pfa_fa3_varlen_bwd_args* a);
+/* Enqueue the packed backward (two launches: dQ, which also leaves delta, then dK/dV) on `stream`. */
+int pfa_fa3_varlen_bwd(const pfa_fa3_varlen_bwd_args* a, void* stream);
+/* Introspection: "fa3_bwd_dq_varlen_<tag>+fa3_bwd_dkdv_varlen_<tag>", <tag> = {bf16|fp16}_d{D}_{causal|full}_{g16|g32}, into buf (NUL
+ * terminated, truncated to n); returns the dQ launch's workgroups and, in *dkdv_workgroups (may be NULL), the dK/dV launch's; or a
+ * pfa_status. */
+int pfa_fa3_varlen_bwd_describe(const pfa_fa3_varlen_bwd_args* a, char* buf, size_t n, int32_t* dkdv_workgroups);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

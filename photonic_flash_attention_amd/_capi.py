@@ -88,6 +88,30 @@ class PfaFa3PrefillVarlenArgs(C.Structure):
     )
 
 
+class PfaFa3VarlenArgs(C.Structure):
+    """Mirror of ``struct pfa_fa3_varlen_args`` (include/pfa_hip.h): the packed variable-length forward, no batch strides."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("q", "k", "v", "o", "lse", "cu_seqlens_q", "cu_seqlens_k")]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in "qkvo" for a in "sh"]
+        + [(n, C.c_int32) for n in ("B", "H", "Hkv", "total_q", "total_k", "max_seqlen_q", "max_seqlen_k", "D", "dtype_in", "dtype_out",
+                                    "causal")]
+        + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
+    )
+
+
+class PfaFa3VarlenBwdArgs(C.Structure):
+    """Mirror of ``struct pfa_fa3_varlen_bwd_args`` (include/pfa_hip.h): the packed variable-length backward."""
+    _fields_ = (
+        [("size", C.c_uint32), ("flags", C.c_uint32)]
+        + [(n, C.c_void_p) for n in ("q", "k", "v", "o", "dout", "lse", "dq", "dk", "dv", "delta", "cu_seqlens_q", "cu_seqlens_k")]
+        + [(f"{t}_stride_{a}", C.c_int64) for t in ("q", "k", "v", "o", "do", "dq", "dk", "dv") for a in "sh"]
+        + [(n, C.c_int32) for n in ("B", "H", "Hkv", "total_q", "total_k", "max_seqlen_q", "max_seqlen_k", "D", "dtype", "dtype_grad",
+                                    "causal")]
+        + [("softmax_scale", C.c_float), ("device_id", C.c_int32), ("reserved0", C.c_int32)]
+    )
+
+
 class PfaFa3CacheExt(C.Structure):
     """Mirror of ``struct pfa_fa3_cache_ext`` (include/pfa_hip.h): per-call options of the ``*_ex`` calls over a KV cache."""
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_int32), ("reserved", C.c_int32)]
@@ -158,6 +182,7 @@ def _prototypes():
     ns = [C.POINTER(C.c_int32)]
     pcp = C.POINTER(PfaPageCopyArgs)
     tree = C.POINTER(PfaFa3TreeMask)
+    vl, vlb = C.POINTER(PfaFa3VarlenArgs), C.POINTER(PfaFa3VarlenBwdArgs)
     return {
         "pfa_abi_version": (i, None),
         "pfa_status_string": (C.c_char_p, [i]),
@@ -214,6 +239,13 @@ def _prototypes():
         "pfa_page_copy_check": (i, [pcp]),
         "pfa_page_copy": (i, [pcp, vp]),
         "pfa_page_copy_describe": (i, [pcp] + buf),
+        "pfa_fa3_varlen_check": (i, [vl]),
+        "pfa_fa3_varlen_fwd": (i, [vl, vp]),
+        "pfa_fa3_varlen_describe": (i, [vl] + buf),
+        "pfa_fa3_varlen_bwd_workspace_bytes": (sz, [vlb]),
+        "pfa_fa3_varlen_bwd_check": (i, [vlb]),
+        "pfa_fa3_varlen_bwd": (i, [vlb, vp]),
+        "pfa_fa3_varlen_bwd_describe": (i, [vlb] + buf + ns),
     }
 
 
@@ -405,3 +437,22 @@ def make_page_copy_args(**kw) -> PfaPageCopyArgs:
 def describe_page_copy(args: PfaPageCopyArgs):
     """-> (kernel name, workgroups) of ``pfa_page_copy``: ``n_pairs * ceil(page_size * Hkv * (D / 8) / 1024)``, from host shapes only."""
     return _describe("pfa_page_copy_describe", args)
+
+
+def make_varlen_args(**kw) -> PfaFa3VarlenArgs:
+    return _make(PfaFa3VarlenArgs, kw)
+
+
+def describe_varlen(args: PfaFa3VarlenArgs):
+    """-> (kernel name, workgroups) of ``pfa_fa3_varlen_fwd``: ``B * H * ceil(max_seqlen_q / 256)``, from host shapes only."""
+    return _describe("pfa_fa3_varlen_describe", args)
+
+
+def make_varlen_bwd_args(**kw) -> PfaFa3VarlenBwdArgs:
+    return _make(PfaFa3VarlenBwdArgs, kw)
+
+
+def describe_varlen_bwd(args: PfaFa3VarlenBwdArgs):
+    """-> (kernel names "dq+dkdv", workgroups of the dQ launch ``B * H * ceil(max_seqlen_q / 256)``, workgroups of the dK/dV launch
+    ``B * Hkv * ceil(max_seqlen_k / 128)``) of ``pfa_fa3_varlen_bwd``."""
+    return _describe("pfa_fa3_varlen_bwd_describe", args, nsplit=True)

@@ -61,7 +61,26 @@ struct BwdParams {
     int64_t km_sb;              // byte stride between batches (keys contiguous; host: Sk, base and stride multiples of 4)
     float scale;           // softmax scale
     float scale_log2;      // scale * log2(e)
+    // The packed ("varlen") mode of the two kernels (include/pfa_hip.h, pfa_fa3_varlen_bwd_args), as in FwdParams: every tensor is
+    // [total, heads, D] with no batch stride (the *_sb members are unused), Sq / Sk hold max_seqlen_q / max_seqlen_k, lse and delta are
+    // [H, total_q], and a workgroup reads its sequence's rows and keys from the two cu_seqlens arrays.
+    const int32_t* cu_q = nullptr;       // int32 [B + 1] on the device
+    const int32_t* cu_k = nullptr;
+    int32_t total_q = 0, total_k = 0;
 };
+
+// The parameter block rebased to one packed sequence: pointers moved to its first row / key, Sq / Sk its own lengths.
+template <typename T, typename OT>
+__device__ __forceinline__ BwdParams packed_bwd_params(const BwdParams& pin, PackedSeq sq, PackedSeq sk) {
+    BwdParams p = pin;
+    p.Sq = sq.len; p.Sk = sk.len;
+    p.q = rebase_rows<T>(pin.q, sq.start, pin.q_ss); p.o = rebase_rows<T>(pin.o, sq.start, pin.o_ss);
+    p.dout = rebase_rows<T>(pin.dout, sq.start, pin.do_ss); p.dq = (void*)rebase_rows<OT>(pin.dq, sq.start, pin.dq_ss);
+    p.k = rebase_rows<T>(pin.k, sk.start, pin.k_ss); p.v = rebase_rows<T>(pin.v, sk.start, pin.v_ss);
+    p.dk = (void*)rebase_rows<OT>(pin.dk, sk.start, pin.dk_ss); p.dv = (void*)rebase_rows<OT>(pin.dv, sk.start, pin.dv_ss);
+    p.q_sb = p.k_sb = p.v_sb = p.o_sb = p.do_sb = p.dq_sb = p.dk_sb = p.dv_sb = 0;
+    return p;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Shared tile machinery: 64-row x D tile images (two per stage), LDS-DMA by buffer descriptor, swizzled.
@@ -233,8 +252,15 @@ __device__ __forceinline__ void store_tile_rows_via_lds(const f32x16 (&acc)[D / 
 
 // ---------------------------------------------------------------------------------------------------------------
 // dQ: forward geometry.  LDS stage = [K image | V image], double buffered (64 KiB at D = 128).
-template <typename T, int D, bool CAUSAL, bool KMASK, typename OT>
-__global__ __launch_bounds__(512, 2) void fa3_bwd_dq_kernel(const BwdParams p) {
+// OTM: the gradient store type, or Packed<store type> for the packed variable-length mode (pfa_fa3_varlen_bwd; StoreMode in
+// fa3_fwd_kernel.h): grid B * H * ceil(max_seqlen_q / 256) from host shapes, a workgroup past its sequence's rows returns at once, every
+// other works on packed_bwd_params() of its sequence -- every bound below is then the sequence's -- and computes what the dense kernel
+// computes for that sequence alone, bit for bit.
+template <typename T, int D, bool CAUSAL, bool KMASK, typename OTM>
+__global__ __launch_bounds__(512, 2) void fa3_bwd_dq_kernel(const BwdParams pin) {
+    constexpr bool VARLEN = StoreMode<OTM>::packed;
+    using OT = typename StoreMode<OTM>::type;
+    static_assert(!VARLEN || !KMASK, "the packed backward takes no masks");
     using E = Elem<T>;
     using v8 = typename E::v8;
     using v4 = typename E::v4;
@@ -246,10 +272,19 @@ __global__ __launch_bounds__(512, 2) void fa3_bwd_dq_kernel(const BwdParams p) {
 
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int BH = p.B * p.H, n = blockIdx.x, qrank = n / BH, bh = n - qrank * BH;
-    const int qblk = CAUSAL ? (p.nblk - 1 - qrank) : qrank;
-    const int b = bh / p.H, hh = bh - b * p.H;
+    const int BH = pin.B * pin.H, n = blockIdx.x, qrank = n / BH, bh = n - qrank * BH;
+    const int qblk = CAUSAL ? (pin.nblk - 1 - qrank) : qrank;
+    const int b = bh / pin.H, hh = bh - b * pin.H;
     const int q0 = qblk * BLOCK_M, wave_q0 = q0 + wave * WAVE_M, my_q = wave_q0 + r;
+    BwdParams pv;                            // VARLEN: the block of this workgroup's sequence
+    int64_t stat_row0 = 0;                   // VARLEN: LSE / delta entry of the sequence's row 0 in head hh of the [H, total_q] arrays
+    if constexpr (VARLEN) {
+        const PackedSeq sq = packed_seq(pin.cu_q, b, pin.total_q, pin.Sq), sk = packed_seq(pin.cu_k, b, pin.total_k, pin.Sk);
+        if (q0 >= sq.len) return;            // no rows of the sequence in this block (wave-uniform, ahead of every barrier)
+        pv = packed_bwd_params<T, OT>(pin, sq, sk);
+        stat_row0 = (int64_t)hh * pin.total_q + sq.start;
+    }
+    const BwdParams& p = VARLEN ? (const BwdParams&)pv : (const BwdParams&)pin;
 
     int kv_len = p.Sk;
     if (p.seqlens_k) kv_len = min(kv_len, max(p.seqlens_k[b], 0));
@@ -290,7 +325,7 @@ __global__ __launch_bounds__(512, 2) void fa3_bwd_dq_kernel(const BwdParams p) {
     // so the wait hipcc puts in front of its use never holds the K/V prefetch up (the byte / dword loads inside `compute` did)
     const unsigned long long* mwrow = (KMASK && p.mw_row) ? p.mw_row + (int64_t)b * p.mw_sb + (int64_t)hh * p.mw_sh + (int64_t)qrow * p.mw_sq : nullptr;
     unsigned long long cur_bits = ~0ull, next_bits = ~0ull;
-    const int64_t stat = ((int64_t)b * p.H + hh) * p.Sq + qrow;
+    const int64_t stat = VARLEN ? stat_row0 + qrow : ((int64_t)b * p.H + hh) * p.Sq + qrow;
     const float lse = p.lse[stat];
     // delta = rowsum(dO o O) of this lane's row, computed here (this kernel holds the dO row anyway; the lane pair (l, l^32)
     // splits the row) and published for the dK/dV kernel that runs after it: no separate memory-bound delta pass
@@ -466,8 +501,14 @@ __global__ __launch_bounds__(512, 2) void fa3_bwd_dq_kernel(const BwdParams p) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // dK, dV: key-stationary.  Workgroup = 4 waves x 32 keys = 128 keys; LDS stage = [Q image | dO image] (64 rows).
-template <typename T, int D, bool CAUSAL, bool KMASK, typename OT>
-__global__ __launch_bounds__(256, 2) void fa3_bwd_dkdv_kernel(const BwdParams p) {
+// OTM = Packed<store type>: the packed variable-length mode, as in the dQ kernel -- grid B * Hkv * ceil(max_seqlen_k / 128) from host
+// shapes; a workgroup whose key block starts at or past its sequence's keys returns at once.  Keys no row sees (a sequence without rows;
+// under causal the keys j >= Sq_b) get exact zeros, as in the dense mode.
+template <typename T, int D, bool CAUSAL, bool KMASK, typename OTM>
+__global__ __launch_bounds__(256, 2) void fa3_bwd_dkdv_kernel(const BwdParams pin) {
+    constexpr bool VARLEN = StoreMode<OTM>::packed;
+    using OT = typename StoreMode<OTM>::type;
+    static_assert(!VARLEN || !KMASK, "the packed backward takes no masks");
     using E = Elem<T>;
     using v8 = typename E::v8;
     using v4 = typename E::v4;
@@ -481,11 +522,21 @@ __global__ __launch_bounds__(256, 2) void fa3_bwd_dkdv_kernel(const BwdParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // grouped-query heads: a workgroup owns a key block of ONE K/V head and streams the Q / dO tiles of all its G query heads, one head
     // after the other, into the same dK / dV accumulators (the sum over the group happens in registers, nothing is expanded in memory)
-    const int G = p.kv_group, HK = p.H / G;
-    const int BH = p.B * HK, n = blockIdx.x, krank = n / BH, bh = n - krank * BH;
+    const int G = pin.kv_group, HK = pin.H / G;
+    const int BH = pin.B * HK, n = blockIdx.x, krank = n / BH, bh = n - krank * BH;
     const int kblk = krank;                      // causal: low key blocks see the most query rows -> first
     const int b = bh / HK, hh = bh - b * HK;     // hh: the K/V head
     const int k0 = kblk * BLOCK_K, wave_k0 = k0 + wave * 32, my_key = wave_k0 + r;
+    BwdParams pv;                                // VARLEN: the block of this workgroup's sequence
+    int64_t stat_hs = 0, stat_row0 = 0;          // VARLEN: LSE / delta are [H, total_q]: head stride, entry of the sequence's row 0 in head hh * G
+    if constexpr (VARLEN) {
+        const PackedSeq sq = packed_seq(pin.cu_q, b, pin.total_q, pin.Sq), sk = packed_seq(pin.cu_k, b, pin.total_k, pin.Sk);
+        if (k0 >= sk.len) return;                // no keys of the sequence in this block (wave-uniform, ahead of every barrier)
+        pv = packed_bwd_params<T, OT>(pin, sq, sk);
+        stat_hs = pin.total_q;
+        stat_row0 = (int64_t)hh * G * stat_hs + sq.start;
+    }
+    const BwdParams& p = VARLEN ? (const BwdParams&)pv : (const BwdParams&)pin;
 
     int kv_len = p.Sk;
     if (p.seqlens_k) kv_len = min(kv_len, max(p.seqlens_k[b], 0));
@@ -517,8 +568,8 @@ __global__ __launch_bounds__(256, 2) void fa3_bwd_dkdv_kernel(const BwdParams p)
     const T* kp = (const T*)p.k + (int64_t)b * p.k_sb + (int64_t)hh * p.k_sh;
     const T* vp = (const T*)p.v + (int64_t)b * p.v_sb + (int64_t)hh * p.v_sh;
     const int64_t q_slab = ((int64_t)(p.Sq - 1) * p.q_ss + D) * 2, g_slab = ((int64_t)(p.Sq - 1) * p.do_ss + D) * 2;
-    const float* lse_p0 = p.lse + ((int64_t)b * p.H + hh * G) * p.Sq;        // + gq * Sq
-    const float* del_p0 = p.delta + ((int64_t)b * p.H + hh * G) * p.Sq;
+    const float* lse_p0 = p.lse + (VARLEN ? stat_row0 : ((int64_t)b * p.H + hh * G) * p.Sq);        // + gq * Sq (packed: gq * total_q)
+    const float* del_p0 = p.delta + (VARLEN ? stat_row0 : ((int64_t)b * p.H + hh * G) * p.Sq);
     // per-row constants of a 64-row tile, staged through LDS beside the tile: st[buf][0][64] = -lse/scale (or -inf
     // for rows that do not exist / are fully masked), st[buf][1][64] = -delta.  Thread t < 64 moves row t.
     constexpr int STAT_BASE = 2 * BUF_BYTES;
@@ -529,9 +580,9 @@ __global__ __launch_bounds__(256, 2) void fa3_bwd_dkdv_kernel(const BwdParams p)
         if (tid < BLOCK_N) {
             const int qi = j * BLOCK_N + tid;
             const bool live = qi < p.Sq;
-            const float l = live ? lse_p0[(int64_t)gq * p.Sq + qi] : -INFINITY;
+            const float l = live ? lse_p0[(int64_t)gq * (VARLEN ? stat_hs : p.Sq) + qi] : -INFINITY;
             st_l = (l > -INFINITY) ? -l / p.scale : -INFINITY;
-            st_d = live ? -del_p0[(int64_t)gq * p.Sq + qi] : 0.f;
+            st_d = live ? -del_p0[(int64_t)gq * (VARLEN ? stat_hs : p.Sq) + qi] : 0.f;
         }
     };
     auto stat_store = [&](int buf) {

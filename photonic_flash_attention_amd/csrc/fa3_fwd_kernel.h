@@ -71,7 +71,41 @@ struct FwdParams {
     const int* mrange = nullptr;
     int64_t mr_sb = 0, mr_sh = 0;
     int32_t mr_q = 0;
+    // The packed ("varlen") mode of fa3_fwd_kernel (include/pfa_hip.h, pfa_fa3_varlen_args; no other kernel reads these): q / k / v / o
+    // are [total, heads, D] with no batch stride (the *_sb members are unused), Sq / Sk hold max_seqlen_q / max_seqlen_k (they size the
+    // grid), lse is [H, total_q], and a workgroup reads its sequence's rows and keys from the two cu_seqlens arrays.
+    const int32_t* cu_q = nullptr;       // int32 [B + 1] on the device
+    const int32_t* cu_k = nullptr;
+    int32_t total_q = 0, total_k = 0;
 };
+
+// The packed mode of a kernel is selected by handing Packed<store type> where the dense instantiations hand the store type: a mode of
+// the same kernel template that leaves the dense instantiations, their symbols included, as they are.
+template <typename OT> struct Packed {};
+template <typename OT> struct StoreMode {
+    using type = OT;
+    static constexpr bool packed = false;
+};
+template <typename OT> struct StoreMode<Packed<OT>> {
+    using type = OT;
+    static constexpr bool packed = true;
+};
+
+// One sequence of a packed tensor, read by a workgroup from cu[b], cu[b + 1] (b wave-uniform: scalar loads, SALU clamps):
+// s = clamp(cu[b], 0, total), e = clamp(cu[b + 1], s, total), len = min(e - s, max_len) -- bad values give wrong numbers, never a row
+// outside the packed tensor.
+struct PackedSeq {
+    int32_t start, len;
+};
+__device__ __forceinline__ PackedSeq packed_seq(const int32_t* __restrict__ cu, int b, int32_t total, int32_t max_len) {
+    const int32_t s = min(max(cu[b], 0), total), e = min(max(cu[b + 1], s), total);
+    return {s, min(e - s, max_len)};
+}
+// base + rows * stride elements, as 64-bit arithmetic on the pointer (never folded into a 32-bit buffer offset)
+template <typename T>
+__device__ __forceinline__ const void* rebase_rows(const void* base, int32_t rows, int64_t stride) {
+    return (const void*)((const T*)base + (int64_t)rows * stride);
+}
 
 template <typename T> struct Elem;
 template <> struct Elem<__bf16> {
@@ -331,8 +365,18 @@ constexpr int FWD_WAVES = 8;                      // one wave per 32 Q rows
 constexpr int FWD_THREADS = FWD_WAVES * 64;
 constexpr int FWD_BLOCK_M = FWD_WAVES * WAVE_M;   // 256 Q rows per workgroup
 
-template <typename T, int D, bool CAUSAL, bool SPLITP, bool KMASK, typename OT>
-__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_fwd_kernel(const FwdParams p) {
+// OTM: the store type (bf16 / fp16 / float): the dense kernel, `pin` used as it is.  Packed<store type>: the packed variable-length mode
+// (pfa_fa3_varlen_fwd) -- grid B * H * ceil(max_seqlen_q / 256) from host shapes, lengths and offsets from pin.cu_q / cu_k on the device,
+// workgroups past their sequence's rows return at once; the kernel then works on a copy of the block rebased to its sequence (pointers
+// moved to the sequence's first row, Sq / Sk its own lengths), so every bound below, K/V descriptors and row guards alike, is the
+// sequence's, and a workgroup computes what the dense kernel computes for that sequence alone, bit for bit.  Causal is the dense rule
+// in both modes (row i sees key j iff j <= i, top-left aligned), not the caches' bottom-right rule; for packed self-attention (cu_k is
+// cu_q) the two coincide.
+template <typename T, int D, bool CAUSAL, bool SPLITP, bool KMASK, typename OTM>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_fwd_kernel(const FwdParams pin) {
+    constexpr bool VARLEN = StoreMode<OTM>::packed;
+    using OT = typename StoreMode<OTM>::type;
+    static_assert(!VARLEN || !KMASK, "the packed forward takes no masks");
     constexpr int NW = FWD_WAVES, BLOCK_M = FWD_BLOCK_M;
     using E = Elem<T>;
     using v8 = typename E::v8;
@@ -355,15 +399,28 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_fwd_kernel(const FwdParams
     const int h = lane >> 5;
 
     // ---- block -> (q block, batch*head): heaviest (longest causal row) blocks first ----------------
-    const int BH = p.B * p.H;
+    const int BH = pin.B * pin.H;
     const int n = blockIdx.x;
     const int qrank = n / BH;
     const int bh = n - qrank * BH;
-    const int qblk = CAUSAL ? (p.nqblk - 1 - qrank) : qrank;
-    const int b = bh / p.H;
-    const int hh = bh - b * p.H;
+    const int qblk = CAUSAL ? (pin.nqblk - 1 - qrank) : qrank;
+    const int b = bh / pin.H;
+    const int hh = bh - b * pin.H;
 
     const int q0 = qblk * BLOCK_M;
+    FwdParams pv;                            // VARLEN: the block of this workgroup's sequence
+    int64_t lse_row0 = 0;                    // VARLEN: LSE entry of the sequence's row 0 in head hh of the [H, total_q] array
+    if constexpr (VARLEN) {
+        const PackedSeq sq = packed_seq(pin.cu_q, b, pin.total_q, pin.Sq), sk = packed_seq(pin.cu_k, b, pin.total_k, pin.Sk);
+        if (q0 >= sq.len) return;            // no rows of the sequence in this block (wave-uniform, ahead of every barrier)
+        pv = pin;
+        pv.Sq = sq.len; pv.Sk = sk.len;
+        pv.q = rebase_rows<T>(pin.q, sq.start, pin.q_ss); pv.o = (void*)rebase_rows<OT>(pin.o, sq.start, pin.o_ss);
+        pv.k = rebase_rows<T>(pin.k, sk.start, pin.k_ss); pv.v = rebase_rows<T>(pin.v, sk.start, pin.v_ss);
+        pv.q_sb = pv.k_sb = pv.v_sb = pv.o_sb = 0;
+        lse_row0 = (int64_t)hh * pin.total_q + sq.start;
+    }
+    const FwdParams& p = VARLEN ? (const FwdParams&)pv : (const FwdParams&)pin;
     const int wave_q0 = q0 + wave * WAVE_M;
     const int my_q = wave_q0 + r;
 
@@ -700,7 +757,8 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_fwd_kernel(const FwdParams
     if (my_q < p.Sq) {
         if (p.lse && h == 0) {
             const float lse = l_tot > 0.f ? (m_run * c + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : -INFINITY;
-            p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;
+            if constexpr (VARLEN) p.lse[lse_row0 + my_q] = lse;
+            else p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;
         }
     }
 }

@@ -66,16 +66,48 @@ def _is_decode_step(query, key, value, attention_mask) -> bool:
             and attention_mask.shape[2] == 1 and attention_mask.shape[3] == k_len)
 
 
+def _packed_kwargs(query, key, attention_mask, kwargs):
+    """The padding-free collators' packed batch (``DataCollatorWithFlattening``: batch 1, the documents one after the other, and the kwargs
+    ``cu_seq_lens_q`` / ``cu_seq_lens_k`` / ``max_length_q`` / ``max_length_k``) as ``ops.fa3_varlen_attention`` takes it ->
+    ``(cu_q, cu_k, max_q, max_k)``, or None for everything else: a kwarg missing, batch > 1, a mask, a head dim without a packed kernel,
+    or ``max_length_*`` that are not host ints (reading a tensor would synchronise with the device)."""
+    cu_q, cu_k = kwargs.get("cu_seq_lens_q"), kwargs.get("cu_seq_lens_k")
+    max_q, max_k = kwargs.get("max_length_q"), kwargs.get("max_length_k")
+    if not (isinstance(cu_q, torch.Tensor) and isinstance(cu_k, torch.Tensor)) or attention_mask is not None or query.shape[0] != 1:
+        return None
+    if not (isinstance(max_q, int) and isinstance(max_k, int)) or isinstance(max_q, bool) or query.shape[-1] not in (64, 128):
+        return None
+    if cu_q.dim() != 1 or cu_k.shape != cu_q.shape or cu_q.numel() < 2 or cu_q.device != query.device or cu_k.device != query.device:
+        return None
+    if not (1 <= max_q <= query.shape[2] and 1 <= max_k <= key.shape[2]):
+        return None
+    return cu_q.to(torch.int32).contiguous(), cu_k.to(torch.int32).contiguous(), max_q, max_k      # (no-ops for the collators' int32)
+
+
 def pfa_attention_forward(module, query, key, value, attention_mask, dropout: float = 0.0,
                           scaling: Optional[float] = None, is_causal: Optional[bool] = None, **kwargs):
     """``AttentionInterface`` function: ``query/key/value`` are ``[B, H(kv), S, D]``; returns ``([B, Sq, H, D], None)``.
 
     ``attention_mask``: ``None`` (the causal flag decides), the 2-D ``[B, Sk]`` padding mask of ``pfa_attention_mask`` (plus the causal
-    flag), or an sdpa-style 4-D mask (then the flag is off, as in ``transformers.integrations.sdpa_attention.sdpa_attention_forward``)."""
+    flag), or an sdpa-style 4-D mask (then the flag is off, as in ``transformers.integrations.sdpa_attention.sdpa_attention_forward``).
+
+    A padding-free packed batch -- batch 1, no mask, no dropout, and ``cu_seq_lens_q``, ``cu_seq_lens_k``, ``max_length_q``,
+    ``max_length_k`` in ``kwargs`` -- runs ``ops.fa3_varlen_attention`` on the packed ``[total, H, D]`` views: every document attends
+    to itself only, forward and backward.  (Its causal rule is top-left per document, the same as flash-attn's bottom-right one when
+    queries and keys are the same tokens: under the causal flag the packed path is taken only for ``q_len == k_len``.)"""
     if kwargs.get("output_attentions", False):
         raise NotImplementedError(f"'{IMPLEMENTATION_NAME}' attention does not return attention weights; use 'eager'")
     if dropout and getattr(module, "training", False):
         raise NotImplementedError("attention dropout in training mode is not implemented on the HIP path")
+    packed = _packed_kwargs(query, key, attention_mask, kwargs)
+    if packed is not None:
+        packed_causal = bool((is_causal if is_causal is not None else getattr(module, "is_causal", True)) and query.shape[2] > 1)
+        if not packed_causal or query.shape[2] == key.shape[2]:
+            in_dtype = query.dtype
+            cd = in_dtype if in_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+            q, k, v = (t[0].transpose(0, 1).to(cd) for t in (query, key, value))        # [total, H(kv), D] views: nothing is copied
+            out = ops.fa3_varlen_attention(q, k, v, *packed, 0.0, scaling, packed_causal, out_dtype=in_dtype)
+            return out.unsqueeze(0), None
     # (grouped-query attention: forward and backward read the shared K/V heads in place -- pfa_fa3_args.kv_group, and since ABI v7
     #  pfa_fa3_bwd_args.kv_group: the dK/dV kernel sums over each group in registers; nothing is expanded)
     if query.shape[-1] > 128:

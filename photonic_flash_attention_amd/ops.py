@@ -1538,3 +1538,259 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary,
                              cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
     return out, lse
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Packed variable-length attention for training (include/pfa_hip.h, pfa_fa3_varlen_args): flash-attn's flash_attn_varlen_func
+
+def _packed_seqs(cu_q, cu_k, total_q: int, total_k: int, max_seqlen_q: int, max_seqlen_k: int):
+    """The kernels' reading of two host ``cu_seqlens`` lists: per sequence ``(s_q, Sq_b, s_k, Sk_b)`` with ``s = clamp(cu[b], 0,
+    total)``, ``e = clamp(cu[b + 1], s, total)``, ``S_b = min(e - s, max_seqlen)`` -- the rule of ``pfa_fa3_prefill_varlen_args``."""
+    def one(cu, b, total, cap):
+        s = min(max(cu[b], 0), total)
+        e = min(max(cu[b + 1], s), total)
+        return s, min(e - s, cap)
+    return [one(cu_q, b, total_q, max_seqlen_q) + one(cu_k, b, total_k, max_seqlen_k) for b in range(len(cu_q) - 1)]
+
+
+def _packed_probs(qb, kb, lse_b, causal: bool, scale: float):
+    """fp32 scores of one sequence ``[H, Sq_b, Sk_b]`` (top-left causal: row i sees key j iff j <= i) and, given the rows' LSE, the
+    softmax weights ``exp(s - lse)`` (0 where masked or where the row has no key)."""
+    s = torch.matmul(qb, kb.transpose(1, 2)) * scale
+    if causal:
+        i, j = torch.arange(s.shape[1])[:, None], torch.arange(s.shape[2])[None, :]
+        s = s.masked_fill(j > i, float("-inf"))
+    if lse_b is None:
+        return s, None
+    p = torch.exp(s - lse_b[:, :, None])
+    return s, torch.where(torch.isfinite(lse_b)[:, :, None] & torch.isfinite(s), p, torch.zeros_like(p))
+
+
+def _varlen_forward_model(q, k, v, out, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale) -> None:
+    """``pfa_fa3_varlen_fwd``'s rule in plain torch, per sequence in fp32, every clamp included: the executable specification, and
+    what ``fa3_varlen_forward`` runs on CPU tensors.  ``cu_q`` / ``cu_k`` are host lists; writes the covered rows of out / lse only."""
+    g = q.shape[1] // k.shape[1]
+    for sq, nq, sk, nk in _packed_seqs(cu_q, cu_k, q.shape[0], k.shape[0], max_seqlen_q, max_seqlen_k):
+        if nq == 0:
+            continue
+        if nk == 0:                                                     # rows without a key: O = 0, LSE = -inf
+            out[sq:sq + nq] = 0
+            if lse is not None:
+                lse[:, sq:sq + nq] = float("-inf")
+            continue
+        qb = q[sq:sq + nq].float().transpose(0, 1)
+        kb, vb = (t[sk:sk + nk].float().transpose(0, 1).repeat_interleave(g, dim=0) for t in (k, v))
+        s, _ = _packed_probs(qb, kb, None, causal, scale)
+        lse_b = torch.logsumexp(s, dim=-1)                              # (top-left causal: every row sees key 0)
+        out[sq:sq + nq] = torch.matmul(torch.exp(s - lse_b[:, :, None]), vb).transpose(0, 1).to(out.dtype)
+        if lse is not None:
+            lse[:, sq:sq + nq] = lse_b
+
+
+def _varlen_backward_model(q, k, v, out, dout, lse, dq, dk, dv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale) -> None:
+    """``pfa_fa3_varlen_bwd``'s rule in plain torch (see ``_varlen_forward_model``): writes rows ``[s_q, s_q + Sq_b)`` of dq and
+    ``[s_k, s_k + Sk_b)`` of dk / dv of every sequence, and nothing else."""
+    Hkv = k.shape[1]
+    g = q.shape[1] // Hkv
+    for sq, nq, sk, nk in _packed_seqs(cu_q, cu_k, q.shape[0], k.shape[0], max_seqlen_q, max_seqlen_k):
+        if nq == 0 or nk == 0:                                          # no key: dQ = 0; no row: dK = dV = 0
+            dq[sq:sq + nq] = 0
+            dk[sk:sk + nk] = 0
+            dv[sk:sk + nk] = 0
+            continue
+        qb, ob, gb = (t[sq:sq + nq].float().transpose(0, 1) for t in (q, out, dout))
+        kb, vb = (t[sk:sk + nk].float().transpose(0, 1).repeat_interleave(g, dim=0) for t in (k, v))
+        _, p = _packed_probs(qb, kb, lse[:, sq:sq + nq], causal, scale)
+        delta = (gb * ob).sum(-1)
+        ds = p * (torch.matmul(gb, vb.transpose(1, 2)) - delta[:, :, None])
+        dq[sq:sq + nq] = (torch.matmul(ds, kb) * scale).transpose(0, 1).to(dq.dtype)
+        dkb = torch.matmul(ds.transpose(1, 2), qb) * scale              # [H, Sk_b, D] -> summed over each group of query heads
+        dvb = torch.matmul(p.transpose(1, 2), gb)
+        dk[sk:sk + nk] = dkb.reshape(Hkv, g, nk, -1).sum(1).transpose(0, 1).to(dk.dtype)
+        dv[sk:sk + nk] = dvb.reshape(Hkv, g, nk, -1).sum(1).transpose(0, 1).to(dv.dtype)
+
+
+def _varlen_operands(entry: str, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    """What the packed calls check about their operands -> ``(B, H, Hkv, D, total_q, total_k, max_seqlen_q, max_seqlen_k)``."""
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError("q must be [total_q, H, D] and k, v [total_k, Hkv, D]")
+    (total_q, H, D), (total_k, Hkv, _) = q.shape, k.shape
+    if Hkv < 1 or H % Hkv or k.shape != (total_k, Hkv, D) or v.shape != k.shape:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("q, k, v must share dtype bf16 or fp16")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor")
+        if cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [B + 1] tensor, got {tuple(cu.shape)}")
+    if cu_seqlens_k.numel() != cu_seqlens_q.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both be [B + 1]")
+    if any(t.device != q.device for t in (k, v, cu_seqlens_q, cu_seqlens_k)):
+        raise ValueError(f"{entry} needs all its tensors on one device")
+    max_seqlen_q, max_seqlen_k = operator.index(max_seqlen_q), operator.index(max_seqlen_k)      # host ints: they size the grids
+    if total_q < 1 or total_k < 1 or not 1 <= max_seqlen_q <= total_q or not 1 <= max_seqlen_k <= total_k:
+        raise ValueError(f"max_seqlen_q {max_seqlen_q} / max_seqlen_k {max_seqlen_k}: must lie in 1 .. {total_q} / 1 .. {total_k}, the rows held")
+    return cu_seqlens_q.numel() - 1, H, Hkv, D, total_q, total_k, max_seqlen_q, max_seqlen_k
+
+
+def _packed_fields(fields) -> dict:
+    """(field prefix, ``[total, heads, D]`` tensor) pairs -> the pointer and ``*_stride_s`` / ``*_stride_h`` fields (``dout``: ``do_``)."""
+    kw = {}
+    for name, t in fields:
+        if t.stride(2) != 1 and t.shape[2] != 1:
+            raise ValueError("last (head_dim) stride must be 1")
+        pre = "do" if name == "dout" else name
+        kw[name], kw[f"{pre}_stride_s"], kw[f"{pre}_stride_h"] = t.data_ptr(), t.stride(0), t.stride(1)
+    return kw
+
+
+def _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale) -> None:
+    """One ``pfa_fa3_varlen_fwd`` on q's current stream into the caller's ``out`` (``[total_q, H, D]``-shaped, any row / head strides)
+    and ``lse`` (contiguous fp32 ``[H, total_q]`` or None)."""
+    B, H, Hkv, D, total_q, total_k, max_q, max_k = geo
+    if D not in SUPPORTED_HEAD_DIMS:
+        raise ValueError(f"head_dim {D}: the packed kernels exist for {SUPPORTED_HEAD_DIMS}")
+    if out.shape != (total_q, H, D) or out.dtype not in (q.dtype, torch.float32) or out.device != q.device:
+        raise ValueError("out must be a [total_q, H, D] tensor of the input dtype or fp32 on the operands' device")
+    a = _capi.make_varlen_args(
+        cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(), B=B, H=H, Hkv=Hkv, total_q=total_q, total_k=total_k,
+        max_seqlen_q=max_q, max_seqlen_k=max_k, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[out.dtype], causal=1 if causal else 0,
+        softmax_scale=_scale(softmax_scale, D), device_id=_device_index(q.device), **_packed_fields((("q", q), ("k", k), ("v", v), ("o", out))))
+    if lse is not None:
+        if lse.shape != (H, total_q) or lse.dtype != torch.float32 or not lse.is_contiguous():
+            raise ValueError("lse must be contiguous fp32 [H, total_q]")
+        a.lse = lse.data_ptr()
+    st = _capi.load().pfa_fa3_varlen_fwd(C.byref(a), C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
+    _raise_status("pfa_fa3_varlen_fwd", st, null_too=True)
+
+
+def fa3_varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                       max_seqlen_q: int, max_seqlen_k: int, causal: bool = False, softmax_scale: Optional[float] = None,
+                       out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
+                       out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Packed variable-length attention forward (``pfa_fa3_varlen_fwd``): ``fa3_forward`` for a batch of sequences of different
+    lengths that is not padded -- the operand layout of flash-attn's ``flash_attn_varlen_func``.
+
+    q: ``[total_q, H, D]``, k / v: ``[total_k, Hkv, D]`` (bf16 / fp16, D 64 or 128, ``H % Hkv == 0``; any row / head strides that are
+    multiples of 8 elements, head dim contiguous), the sequences' rows one after the other.  cu_seqlens_q / cu_seqlens_k: int32
+    ``[B + 1]`` DEVICE tensors, non-decreasing, ``cu[0] >= 0``; the caller's contract is ``cu[B] == total``.  Sequence b owns the packed
+    rows ``cu[b] .. cu[b + 1] - 1`` (none is fine).  max_seqlen_q / max_seqlen_k: HOST ints, bounds on the rows / keys of one sequence
+    (1 .. total); they alone size the grid, and of a longer sequence only the first max_seqlen rows / keys take part.  Device values out
+    of range are clamped by the kernel as in ``fa3_prefill_varlen``: wrong numbers, never an access outside the packed tensors.
+
+    ``causal`` is the DENSE rule, top-left aligned per sequence: row i of sequence b sees key j iff ``j <= i``.  It is not the
+    bottom-right rule of the calls over a KV cache; for packed self-attention (``cu_seqlens_k is cu_seqlens_q``) the two coincide.
+    A row with no key (``Sk_b == 0``) gets O = 0 and LSE = -inf.  Packed rows no sequence covers are never written.
+
+    Returns ``(out [total_q, H, D], lse [H, total_q] fp32 or None)``.  ``out_dtype=torch.float32`` selects the parity variant (fp32
+    store, split P) as in ``fa3_forward``.  The result is bit for bit that of ``fa3_forward(..., _variant=44)`` per sequence: the
+    8-wave kernel in its packed mode (no masks, no ``seqlens_k``, no dropout, no fp32 operands here).  Nothing synchronises with the
+    device and nothing is cached: capturable in ``torch.cuda.graph`` and valid while the cu_seqlens contents change between replays.
+
+    On CPU tensors the same rule runs in plain torch per sequence in fp32 (the executable specification)."""
+    geo = _varlen_operands("pfa_fa3_varlen_fwd", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    _, H, _, D, total_q = geo[:5]
+    odt = q.dtype if out_dtype is None else out_dtype
+    if out is None:
+        out = torch.empty((total_q, H, D), dtype=odt, device=q.device)
+    elif out.shape != (total_q, H, D) or out.dtype != odt or out.device != q.device:
+        raise ValueError("out must be a [total_q, H, D] tensor of the output dtype on the operands' device")
+    lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    if q.device.type == "cpu":
+        _varlen_forward_model(q, k, v, out, lse, cu_seqlens_q.tolist(), cu_seqlens_k.tolist(), geo[6], geo[7], causal, _scale(softmax_scale, D))
+    else:
+        _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale)
+    return out, lse
+
+
+def _packed_meets_abi(t: torch.Tensor) -> bool:
+    """The packed calls' rules for a 16-bit operand: head dim contiguous, base 16-byte aligned, row / head strides multiples of 8."""
+    return t.stride(2) == 1 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(0) >= 0
+
+
+def _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale) -> None:
+    """One ``pfa_fa3_varlen_bwd`` (two launches) on q's current stream into the caller's ``dq`` / ``dk`` / ``dv``."""
+    B, H, Hkv, D, total_q, total_k, max_q, max_k = geo
+    if D not in SUPPORTED_HEAD_DIMS:
+        raise ValueError(f"head_dim {D}: the packed kernels exist for {SUPPORTED_HEAD_DIMS}")
+    if lse.shape != (H, total_q) or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.device != q.device:
+        raise ValueError("lse must be the forward's contiguous fp32 [H, total_q]")
+    delta = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
+    a = _capi.make_varlen_bwd_args(
+        lse=lse.data_ptr(), delta=delta.data_ptr(), cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(),
+        B=B, H=H, Hkv=Hkv, total_q=total_q, total_k=total_k, max_seqlen_q=max_q, max_seqlen_k=max_k, D=D, dtype=_DT[q.dtype],
+        dtype_grad=_DT[dq.dtype], causal=1 if causal else 0, softmax_scale=_scale(softmax_scale, D), device_id=_device_index(q.device),
+        **_packed_fields((("q", q), ("k", k), ("v", v), ("o", out), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv))))
+    stream = torch.cuda.current_stream(q.device)
+    st = _capi.load().pfa_fa3_varlen_bwd(C.byref(a), C.c_void_p(stream.cuda_stream))
+    _raise_status("pfa_fa3_varlen_bwd", st, null_too=True)
+    delta.record_stream(stream)      # made here: must outlive the enqueued kernels
+
+
+def fa3_varlen_backward(q, k, v, out, dout, lse, *, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int,
+                        max_seqlen_k: int, causal: bool = False, softmax_scale: Optional[float] = None,
+                        grad_dtype: Optional[torch.dtype] = None):
+    """dQ, dK, dV of ``fa3_varlen_forward`` (``pfa_fa3_varlen_bwd``).  q / out / dout ``[total_q, H, D]``, k / v ``[total_k, Hkv, D]``,
+    ``lse`` the forward's fp32 ``[H, total_q]``; ``out`` and ``dout`` in the operand dtype.  Returns ``(dq [total_q, H, D], dk, dv
+    [total_k, Hkv, D])`` in ``grad_dtype`` (the input dtype by default, or fp32); grouped-query heads are summed inside the dK/dV kernel.
+    Every row of dq / dk / dv a sequence covers is written exactly once (rows without a key get dq = 0, keys no row sees -- a sequence
+    without rows, under causal the keys ``j >= Sq_b`` -- get exact zeros); rows no sequence covers are left as ``torch.empty`` made them.
+    ``causal`` is the dense top-left rule, as in ``fa3_varlen_forward``.  The gradients are bit for bit those of ``fa3_backward`` per
+    sequence; no atomics.  A ``dout`` that fails the alignment or stride rules is copied, as ``fa3_backward`` does; nothing
+    synchronises with the device.  On CPU tensors: the plain-torch model, fp32 per sequence."""
+    geo = _varlen_operands("pfa_fa3_varlen_bwd", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    _, H, Hkv, D, total_q, total_k = geo[:6]
+    if out.shape != q.shape or dout.shape != q.shape or out.dtype != q.dtype or dout.dtype != q.dtype:
+        raise ValueError("out and dout must be [total_q, H, D] tensors of the operand dtype")
+    if any(t.device != q.device for t in (out, dout, lse)):
+        raise ValueError("pfa_fa3_varlen_bwd needs all its tensors on one device")
+    gdt = q.dtype if grad_dtype is None else grad_dtype
+    if gdt not in (q.dtype, torch.float32):
+        raise ValueError("grad_dtype must be the input dtype or fp32")
+    dq = torch.empty((total_q, H, D), dtype=gdt, device=q.device)
+    dk = torch.empty((total_k, Hkv, D), dtype=gdt, device=q.device)
+    dv = torch.empty((total_k, Hkv, D), dtype=gdt, device=q.device)
+    if q.device.type == "cpu":
+        _varlen_backward_model(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q.tolist(), cu_seqlens_k.tolist(), geo[6], geo[7], causal,
+                               _scale(softmax_scale, D))
+        return dq, dk, dv
+    if not _packed_meets_abi(dout):
+        dout = dout.contiguous()
+    _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale)
+    return dq, dk, dv
+
+
+class _FA3VarlenFunction(torch.autograd.Function):
+    """Differentiable ``fa3_varlen_forward``: saves q, k, v, a 16-bit O, the LSE and the two cu_seqlens tensors."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, out_dtype):
+        out, lse = fa3_varlen_forward(q, k, v, cu_seqlens_q=cu_seqlens_q, cu_seqlens_k=cu_seqlens_k, max_seqlen_q=max_seqlen_q,
+                                      max_seqlen_k=max_seqlen_k, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
+                                      return_lse=True)
+        o16 = out if out.dtype == q.dtype else out.to(q.dtype)
+        ctx.save_for_backward(q, k, v, o16, lse, cu_seqlens_q, cu_seqlens_k)
+        ctx.meta = (max_seqlen_q, max_seqlen_k, causal, softmax_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        max_q, max_k, causal, softmax_scale = ctx.meta
+        dq, dk, dv = fa3_varlen_backward(q, k, v, out, dout.to(q.dtype), lse, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k, max_seqlen_q=max_q,
+                                         max_seqlen_k=max_k, causal=causal, softmax_scale=softmax_scale)
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+def fa3_varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p: float = 0.0,
+                         softmax_scale: Optional[float] = None, causal: bool = False, *, out_dtype: Optional[torch.dtype] = None):
+    """Autograd-aware packed variable-length attention, arguments in the order of flash-attn's ``flash_attn_varlen_func``: q
+    ``[total_q, H, D]``, k / v ``[total_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]``, host ints ``max_seqlen_*``.  Forward
+    and backward on the packed HIP kernels (``fa3_varlen_forward`` / ``fa3_varlen_backward``: their conventions hold, the dense
+    top-left ``causal`` rule among them); returns ``out [total_q, H, D]``.  ``dropout_p`` must be 0: there is no dropout here.
+    Rows no sequence covers get whatever ``torch.empty`` left, in the output and in the gradients (``cu[B] == total`` leaves none)."""
+    if dropout_p:
+        raise NotImplementedError("attention dropout is not implemented on the packed path (dropout_p must be 0)")
+    return _FA3VarlenFunction.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, operator.index(max_seqlen_q), operator.index(max_seqlen_k),
+                                    bool(causal), softmax_scale, out_dtype)
