@@ -22,6 +22,8 @@
  * v9, additive: pfa_fa3_varlen_args / pfa_fa3_varlen_bwd_args and pfa_fa3_varlen_* -- packed variable-length attention for training,
  * forward and backward: sequences of different lengths one after the other in [total, H, D] tensors, cu_seqlens_q / cu_seqlens_k on
  * the device (flash-attn's flash_attn_varlen_func), on the dense 16-bit kernels in a packed mode.
+ * v9, additive: PFA_DTYPE_FP8_E4M3, pfa_fa3_kv_quant, pfa_fa3_decode_q8* and pfa_kv_append_q8* -- the decode over an FP8 (e4m3fn) KV
+ * cache with one fp32 descale per (sequence, K/V head), and the append that quantises a step's 16-bit rows into it.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -82,7 +84,9 @@ typedef enum pfa_status {
 typedef enum pfa_dtype {
     PFA_DTYPE_BF16 = 0,
     PFA_DTYPE_FP16 = 1,
-    PFA_DTYPE_FP32 = 2          /* output of the 16-bit kernels; as dtype_in: the EXACT fp32 kernel (fp32 modules, slow) */
+    PFA_DTYPE_FP32 = 2,         /* output of the 16-bit kernels; as dtype_in: the EXACT fp32 kernel (fp32 modules, slow) */
+    PFA_DTYPE_FP8_E4M3 = 3      /* OCP e4m3fn (max finite 448, 0x7f / 0xff NaN, no infinities; not MI300's fnuz): only as
+                                   pfa_fa3_kv_quant.kv_dtype, the element type of a KV cache */
 } pfa_dtype;
 
 /* flags */
@@ -982,6 +986,57 @@ int pfa_fa3_varlen_bwd(const pfa_fa3_varlen_bwd_args* a, void* stream);
  * terminated, truncated to n); returns the dQ launch's workgroups and, in *dkdv_workgroups (may be NULL), the dK/dV launch's; or a
  * pfa_status. */
 int pfa_fa3_varlen_bwd_describe(const pfa_fa3_varlen_bwd_args* a, char* buf, size_t n, int32_t* dkdv_workgroups);
+
+/*
+ * FP8 (e4m3fn) KV cache (ABI v9, additive): pfa_fa3_decode over a cache of one-byte elements, and the append that quantises a step's
+ * 16-bit rows into it.  An 8-bit cache halves the bytes a decode step streams and doubles the keys a page pool holds.
+ *
+ * The cache tensors of the argument block (k_cache / v_cache, contiguous or the paged pools) hold OCP e4m3fn bytes; their strides are in
+ * elements, which are bytes.  Everything else in the block keeps its meaning: dtype_in (dtype of pfa_kv_append_args) stays the 16-bit
+ * type of q (of k_new / v_new).  Value of a cache element: e4m3(byte) * descale, with one fp32 descale per (sequence, K/V head),
+ *       k_descale[b * descale_stride_b + hk],   v_descale[b * descale_stride_b + hk]
+ * on the device; descale_stride_b = 0 gives every sequence the same row of Hkv values (what a paged cache with shared pages needs).
+ *
+ * pfa_fa3_decode_q8: pfa_fa3_decode_ex of the dequantised cache.  K and V bytes are converted to q's type in registers (exact: every e4m3
+ * value is a bf16 and an fp16 value) in front of the same 16-bit MFMA; k_descale multiplies softmax_scale, v_descale the output once.
+ * Split rule, key mask, bottom-right causal, paging, partials and the O = 0 / LSE = -inf rule of rows with no visible key are those of
+ * pfa_fa3_decode; with all descales 1 the result has the bits of pfa_fa3_decode on the converted cache.  The number of key splits and
+ * the workspace are those of pfa_fa3_decode for the same shapes, so a captured graph stays valid while lengths, table, cache and the
+ * descales' CONTENTS change.  `ext` may be NULL or carry window = 0: a window does not combine with the FP8 cache here, nor does a tree.
+ * Bytes at and past a sequence's length are never converted into a result (0x7f there is harmless); NaN bytes below it give NaN.
+ *
+ * pfa_kv_append_q8: pfa_kv_append's placement (position len_b - Sq_b + i; rows in front of key 0 and rows whose page id lies outside
+ * the pool are dropped; the grid comes from host shapes; lengths are never written), each 16-bit source element x stored as
+ *       e4m3fn( clamp( float(x) / descale[b, hk], -448, 448 ) )
+ * with an IEEE fp32 division and round-to-nearest-even; NaN stays NaN (0x7f or 0xff).  A work item is 16 elements: 32 bytes loaded, 16
+ * stored.  D a multiple of 16 up to 256.
+ *
+ * Field rules of both calls, in the order their errors are reported: `a` NULL -> PFA_ERR_NULL, a->size wrong -> PFA_ERR_STRUCT_SIZE (the
+ * rules below read the block); quant NULL -> PFA_ERR_NULL; quant->size wrong -> PFA_ERR_STRUCT_SIZE; quant->flags or reserved non-zero ->
+ * PFA_ERR_FLAGS; kv_dtype other than PFA_DTYPE_FP8_E4M3 -> PFA_ERR_DTYPE; k_descale or v_descale NULL -> PFA_ERR_NULL; either not 4-byte
+ * aligned -> PFA_ERR_ALIGN; descale_stride_b neither 0 nor >= Hkv -> PFA_ERR_STRIDE; a cache stride not a multiple of 16 elements, or a
+ * negative cache token stride -> PFA_ERR_STRIDE; k_cache or v_cache not 16-byte aligned -> PFA_ERR_ALIGN; (decode) ext->window > 0 ->
+ * PFA_ERR_FLAGS, (append) D not a multiple of 16 -> PFA_ERR_HEAD_DIM; then the unchanged rules of pfa_fa3_decode_ex / pfa_kv_append.
+ * The workspace query takes no pointers and skips the pointer and stride rules.
+ */
+typedef struct pfa_fa3_kv_quant {
+    uint32_t size;              /* = sizeof(pfa_fa3_kv_quant) */
+    uint32_t flags;             /* must be 0 */
+    int32_t kv_dtype;           /* PFA_DTYPE_FP8_E4M3 */
+    int32_t reserved;           /* must be 0 */
+    const float* k_descale;     /* device fp32 [B or 1][Hkv] */
+    const float* v_descale;
+    int64_t descale_stride_b;   /* elements between sequences; 0: one row for all */
+} pfa_fa3_kv_quant;
+
+size_t pfa_fa3_decode_q8_workspace_bytes(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant);
+int pfa_fa3_decode_q8_check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant);
+int pfa_fa3_decode_q8(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream);
+/* As pfa_fa3_decode_describe_ex; "_kv8" is appended to the kernel's name (in front of "+combine" and "_paged"). */
+int pfa_fa3_decode_q8_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, char* buf, size_t n,
+                               int32_t* nsplit);
+int pfa_kv_append_q8_check(const pfa_kv_append_args* a, const pfa_fa3_kv_quant* quant);
+int pfa_kv_append_q8(const pfa_kv_append_args* a, const pfa_fa3_kv_quant* quant, void* stream);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

@@ -14,7 +14,7 @@ import threading
 from typing import Optional
 
 PFA_ABI_VERSION = 9
-PFA_DTYPE_BF16, PFA_DTYPE_FP16, PFA_DTYPE_FP32 = 0, 1, 2
+PFA_DTYPE_BF16, PFA_DTYPE_FP16, PFA_DTYPE_FP32, PFA_DTYPE_FP8_E4M3 = 0, 1, 2, 3
 PFA_FLAG_SPLIT_P = 0x1
 PFA_FLAG_NO_XCD_MAP = 0x2
 PFA_ROPE_INTERLEAVED = 0x1
@@ -122,6 +122,12 @@ class PfaFa3TreeMask(C.Structure):
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("words", C.c_void_p), ("stride_b", C.c_int64)]
 
 
+class PfaFa3KvQuant(C.Structure):
+    """Mirror of ``struct pfa_fa3_kv_quant`` (include/pfa_hip.h): the element type and the descales of an FP8 KV cache."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("kv_dtype", C.c_int32), ("reserved", C.c_int32),
+                ("k_descale", C.c_void_p), ("v_descale", C.c_void_p), ("descale_stride_b", C.c_int64)]
+
+
 class PfaKvAppendArgs(C.Structure):
     """Mirror of ``struct pfa_kv_append_args`` (include/pfa_hip.h): the device-side KV-cache append."""
     _fields_ = (
@@ -183,6 +189,7 @@ def _prototypes():
     pcp = C.POINTER(PfaPageCopyArgs)
     tree = C.POINTER(PfaFa3TreeMask)
     vl, vlb = C.POINTER(PfaFa3VarlenArgs), C.POINTER(PfaFa3VarlenBwdArgs)
+    quant = C.POINTER(PfaFa3KvQuant)
     return {
         "pfa_abi_version": (i, None),
         "pfa_status_string": (C.c_char_p, [i]),
@@ -246,6 +253,12 @@ def _prototypes():
         "pfa_fa3_varlen_bwd_check": (i, [vlb]),
         "pfa_fa3_varlen_bwd": (i, [vlb, vp]),
         "pfa_fa3_varlen_bwd_describe": (i, [vlb] + buf + ns),
+        "pfa_fa3_decode_q8_workspace_bytes": (sz, [dec, ext, quant]),
+        "pfa_fa3_decode_q8_check": (i, [dec, ext, quant]),
+        "pfa_fa3_decode_q8": (i, [dec, ext, quant, vp]),
+        "pfa_fa3_decode_q8_describe": (i, [dec, ext, quant] + buf + ns),
+        "pfa_kv_append_q8_check": (i, [app, quant]),
+        "pfa_kv_append_q8": (i, [app, quant, vp]),
     }
 
 
@@ -371,6 +384,17 @@ def describe_decode_tree(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], 
     """``describe_decode_ex`` of ``pfa_fa3_decode_tree`` (``tree`` None: the NULL tree, i.e. ``pfa_fa3_decode_ex``); "_tree" marks a
     kernel that takes the words."""
     return _describe("pfa_fa3_decode_tree_describe", args, ext, tree, nsplit=True)
+
+
+def make_kv_quant(**kw) -> PfaFa3KvQuant:
+    """A ``pfa_fa3_kv_quant`` block; ``kv_dtype`` defaults to e4m3."""
+    kw.setdefault("kv_dtype", PFA_DTYPE_FP8_E4M3)
+    return _make(PfaFa3KvQuant, kw)
+
+
+def describe_decode_q8(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], quant: Optional[PfaFa3KvQuant]):
+    """``describe_decode_ex`` of ``pfa_fa3_decode_q8``: "_kv8" marks a kernel over an FP8 cache; workgroups and splits are the 16-bit call's."""
+    return _describe("pfa_fa3_decode_q8_describe", args, ext, quant, nsplit=True)
 
 
 def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):

@@ -41,9 +41,23 @@
 //     below off_b) and a row's upper bound is len_b.  Keys in [off_b, len_b) that a word hides are read and masked.  Split rule, paging,
 //     merge, partials and combine are the one code path: the chain words give the bits of the causal call, all-ones those of
 //     causal = 0.  TREE = false compiles to the code and the kernel arguments it had.
+//   * KV8 = true (pfa_fa3_decode_q8; no window, no tree; DecodeQ8Params carries the descales): the cache holds OCP e4m3fn bytes, one per
+//     element, strides in elements = bytes, and one fp32 descale per (batch, K/V head) each for K and V, read by scalar loads once per
+//     item.  Tiles, splits, masks and descriptors are those of the 16-bit kernel (the record count ends at the split's last key in
+//     bytes, so rows past it read as zero bytes = +0).  K: an 8-byte load per lane per k-step, the 16-bit kernel's element-to-k-step
+//     mapping, converted to T in registers (v_cvt_pk_f32_fp8, then the pack to T: every e4m3 value is a bf16 and an fp16 value, so
+//     both steps are exact) in front of the same MFMA against the same Q operand.  V: a 16-byte load per lane (16 elements of one
+//     key), converted to T and written as two 16-byte pieces into the same row-major LDS image, so the transposed reads and the PV
+//     product stand as they are.  A tile is half the bytes, so two tiles are in flight per wave (two register sets, the tile loop
+//     unrolled by two): 16 KiB, as in the 16-bit kernel.  k_descale is folded into the score multiplier, v_descale into the one
+//     multiplication of the epilogue (the normalisation, or the partial's write), so the combine kernel is reused unchanged.  With both
+//     descales 1 the result has the bits of the 16-bit kernel on the converted cache.  KV8 = false compiles to the code and the kernel
+//     arguments it had.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace pfa {
 namespace dec {
@@ -54,12 +68,18 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __amdgpu_buffer_rsrc_t srd_t;
 typedef __attribute__((address_space(3))) char lds_char;
 typedef const __attribute__((address_space(4))) int32_t* const_i32_ptr;   // read-only for the kernel's lifetime: scalar loads
+typedef const __attribute__((address_space(4))) float* const_f32_ptr;
 
 #ifndef PFA_DECODE_PAGE_LOOKAHEAD
 #define PFA_DECODE_PAGE_LOOKAHEAD 1
+#endif
+#ifndef PFA_DECODE_KV8_SETS
+#define PFA_DECODE_KV8_SETS 2      // KV8: tiles in flight per wave (-DPFA_DECODE_KV8_SETS=1: one, 8 KiB, for measurement)
 #endif
 
 constexpr int NW = 4;            // waves per workgroup
@@ -100,9 +120,16 @@ struct DecodeTreeParams : DecodeParams {
     const uint64_t* tree;
     int64_t tree_sb;
 };
-template <bool WINDOW, bool TREE = false> struct DecodeParamsOf { typedef DecodeParams type; };
+// KV8 only: fp32 descales, k_descale[b * ds_sb + kvh] (ds_sb = 0: one row for every batch)
+struct DecodeQ8Params : DecodeParams {
+    const float* k_descale;
+    const float* v_descale;
+    int64_t ds_sb;
+};
+template <bool WINDOW, bool TREE = false, bool KV8 = false> struct DecodeParamsOf { typedef DecodeParams type; };
 template <> struct DecodeParamsOf<true, false> { typedef DecodeWinParams type; };
 template <> struct DecodeParamsOf<false, true> { typedef DecodeTreeParams type; };
+template <> struct DecodeParamsOf<false, false, true> { typedef DecodeQ8Params type; };
 
 template <typename T> struct DElem;
 template <> struct DElem<__bf16> {
@@ -123,6 +150,13 @@ template <> struct DElem<_Float16> {
     }
 };
 
+// 8 e4m3fn bytes (element j in byte j) -> 8 elements of T, exactly
+template <typename T, typename V8> __device__ __forceinline__ V8 cvt_e4m3x8(uint32_t w0, uint32_t w1) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, true);
+    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, true);
+    return V8{(T)a[0], (T)a[1], (T)b[0], (T)b[1], (T)c[0], (T)c[1], (T)d[0], (T)d[1]};
+}
+
 // Per head dim: keys per wave tile, loads per lane, LDS image geometry.
 template <int D> struct Geo {
     static constexpr int KT = D == 128 ? 32 : 64;        // keys per wave tile: 16 KiB of K + V either way
@@ -132,6 +166,8 @@ template <int D> struct Geo {
     static constexpr int KLD = NKB * KS;                  // 16-byte K loads per lane per tile
     static constexpr int KPI = 512 / D;                   // keys per 1-KiB V load instruction
     static constexpr int VLD = KT / KPI;                  // 16-byte V loads per lane per tile
+    static constexpr int KPI8 = 1024 / D;                 // KV8: keys per 1-KiB V load instruction (16 one-byte elements per lane)
+    static constexpr int VLD8 = KT / KPI8;                // KV8: 16-byte V loads per lane per tile
     static constexpr int VROW = D * 2 + 32;               // LDS bytes per key row of the V image
     static constexpr int VIMG = KT * VROW;                // per wave
     static constexpr int MERGE = NW * ROWS * D * 4 + NW * ROWS * 8;
@@ -162,9 +198,10 @@ __device__ __forceinline__ void split_range(const DecodeParams& p, int s, int ba
     hi = min(lo + c, len);
 }
 
-template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false>
-__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE>::type p) {
+template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false, bool KV8 = false>
+__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE, KV8>::type p) {
     static_assert(!(WINDOW && TREE), "a tree does not combine with a window");
+    static_assert(!(KV8 && (WINDOW || TREE)), "the FP8 cache takes neither a window nor a tree");
     using E = DElem<T>;
     using v8 = typename E::v8;
     using v4 = typename E::v4;
@@ -173,6 +210,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
     // fp32 output: P carried as a 16-bit hi + lo pair (two PV MFMAs) so that the result is within 1e-3 of the exact one; the
     // matrix pipe has time to spare here, the kernel waits on HBM
     constexpr bool SPLIT_P = sizeof(OT) == 4;
+    constexpr uint32_t EB = KV8 ? 1 : 2;       // bytes per cache element
     __shared__ __attribute__((aligned(16))) char smem[Gm::LDS];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -183,6 +221,13 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
     const int rb = x % p.nrb;
     x /= p.nrb;
     const int kvh = x % p.Hkv, b = x / p.Hkv;
+    // KV8: the item's two descales (scalar loads); k_descale rides in the score multiplier, v_descale in the epilogue.  Both are
+    // used under if constexpr (KV8) only, so that the other kernels keep their expressions
+    float score_mul = p.scale_log2, out_mul = 1.f;
+    if constexpr (KV8) {
+        score_mul *= ((const_f32_ptr)(uintptr_t)p.k_descale)[(int64_t)b * p.ds_sb + kvh];
+        out_mul = ((const_f32_ptr)(uintptr_t)p.v_descale)[(int64_t)b * p.ds_sb + kvh];
+    }
     int len = p.seqlens ? min(max(p.seqlens[b], 0), p.Smax) : p.Smax, lo, hi;
     int base = 0;
     if constexpr (WINDOW) base = max(0, len - p.Sq - p.window + 1) & ~(SPLIT_ALIGN - 1);
@@ -228,27 +273,35 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
             qf[ks] = __builtin_bit_cast(v8, w);
         }
         // contiguous: this batch's and head's slab; paged: the head's offset inside every page (the page base is added per tile)
-        const char* kslab = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * 2;
-        const char* vslab = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * 2;
-        const uint32_t kss2 = (uint32_t)p.k_ss * 2u, vss2 = (uint32_t)p.v_ss * 2u;
+        const char* kslab = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * EB;
+        const char* vslab = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * EB;
+        const uint32_t kss2 = (uint32_t)p.k_ss * EB, vss2 = (uint32_t)p.v_ss * EB;     // token strides in bytes
         // per-lane byte offsets inside a tile: K in the A-operand layout (key kb*16 + c, head dims 32 ks + 8 h ..),
-        // V one 1-KiB piece per instruction (key vi*KPI + lane / (D/8), chunk lane % (D/8))
-        const uint32_t koff0 = (uint32_t)c * kss2 + (uint32_t)h * 16u;
-        const uint32_t vkey = (uint32_t)lane / (D / 8), vch = (uint32_t)lane % (D / 8);
+        // V one 1-KiB piece per instruction (key vi*KPI + lane / (D/8), chunk lane % (D/8); KV8: 16 elements per lane, D/16 chunks a key)
+        constexpr int VCH = KV8 ? D / 16 : D / 8, VKPI = KV8 ? Gm::KPI8 : Gm::KPI, NVLD = KV8 ? Gm::VLD8 : VLD;
+        const uint32_t koff0 = (uint32_t)c * kss2 + (uint32_t)h * (8u * EB);
+        const uint32_t vkey = (uint32_t)lane / VCH, vch = (uint32_t)lane % VCH;
         const uint32_t voff0 = vkey * vss2 + vch * 16u;
         lds_char* vimg = (lds_char*)(smem + wave * Gm::VIMG);
-        const uint32_t vwr = vkey * VROW + vch * 16u;
+        const uint32_t vwr = vkey * VROW + vch * (KV8 ? 32u : 16u);
         // transposed read: lane 4q + p of its 16-lane group addresses key row (block base + 4h + q), columns 4p .. 4p + 3
         const uint32_t vtr = (uint32_t)(4 * h + ((lane & 15) >> 2)) * VROW + (uint32_t)(lane & 3) * 8u;
 
-        u32x4 kr[NKB * KS], vr[VLD];
+        // the tile(s) in flight, one register set each: K as loaded (KV8: 8 bytes per k-step), V as loaded.  The one-set kernels name
+        // their set as they always did (kr, vr): arrays of sets, or pointers handed to issue(), change their register allocation
+        constexpr int SETS = KV8 ? PFA_DECODE_KV8_SETS : 1;
+        using kreg_t = typename std::conditional<KV8, u32x2, u32x4>::type;
+        kreg_t kr[NKB * KS], kr2[SETS > 1 ? NKB * KS : 1];
+        u32x4 vr[NVLD], vr2[SETS > 1 ? NVLD : 1];
         // paged: the (unclamped) page id of tile t, a wave-uniform scalar load.  Called only for t < ntile, i.e. for keys below
         // hi <= len_b, so table entries at and past ceil(len_b / page_size) are never read.
         const const_i32_ptr table = PAGED ? (const_i32_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
         auto page_of = [&](int t) { return table[(uint32_t)(lo + t * KT) / (uint32_t)p.page_size]; };
         int pg_next = 0;
         if constexpr (PAGED && PFA_DECODE_PAGE_LOOKAHEAD) pg_next = page_of(wave);
-        auto issue = [&](int t) {
+        // issue(t): tile t's loads into kr / vr; issue(t, true) (KV8): into the second set
+        auto issue = [&](int t, auto... second) {
+            constexpr bool SECOND = sizeof...(second) > 0;
             const int t0 = lo + t * KT;
             const int nk = min(KT, hi - t0);     // rows past the split's end read as zeros
             int64_t koff, voff;                  // element offsets of the tile's first key row from kslab / vslab
@@ -263,36 +316,66 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
                 koff = (int64_t)t0 * p.k_ss;
                 voff = (int64_t)t0 * p.v_ss;
             }
-            const srd_t vs = uniform_srd(vslab + voff * 2, (uint32_t)(nk - 1) * vss2 + D * 2);
-            const srd_t ks = uniform_srd(kslab + koff * 2, (uint32_t)(nk - 1) * kss2 + D * 2);
+            const srd_t vs = uniform_srd(vslab + voff * EB, (uint32_t)(nk - 1) * vss2 + D * EB);
+            const srd_t ks = uniform_srd(kslab + koff * EB, (uint32_t)(nk - 1) * kss2 + D * EB);
 #pragma unroll
-            for (int i = 0; i < VLD; ++i)
-                vr[i] = __builtin_amdgcn_raw_buffer_load_b128(vs, (int)(voff0 + (uint32_t)(i * Gm::KPI) * vss2), 0, 0);
+            for (int i = 0; i < NVLD; ++i)
+                (SECOND ? vr2 : vr)[i] = __builtin_amdgcn_raw_buffer_load_b128(vs, (int)(voff0 + (uint32_t)(i * VKPI) * vss2), 0, 0);
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-                for (int q = 0; q < KS; ++q)
-                    kr[kb * KS + q] = __builtin_amdgcn_raw_buffer_load_b128(ks, (int)(koff0 + (uint32_t)(kb * 16) * kss2 + q * 64), 0, 0);
+                for (int q = 0; q < KS; ++q) {
+                    const int at = (int)(koff0 + (uint32_t)(kb * 16) * kss2 + q * (32 * EB));
+                    if constexpr (KV8) (SECOND ? kr2 : kr)[kb * KS + q] = __builtin_amdgcn_raw_buffer_load_b64(ks, at, 0, 0);
+                    else kr[kb * KS + q] = __builtin_amdgcn_raw_buffer_load_b128(ks, at, 0, 0);
+                }
             if constexpr (PAGED && PFA_DECODE_PAGE_LOOKAHEAD)
                 if (t + NW < ntile) pg_next = page_of(t + NW);   // behind this tile's loads, for the next issue()
         };
         issue(wave);
+        if constexpr (SETS > 1)
+            if (wave + NW < ntile) issue(wave + NW, true);
         const uint8_t* km = p.key_mask ? p.key_mask + (int64_t)b * p.km_sb : nullptr;
 
-        for (int t = wave; t < ntile; t += NW) {
+        // One set: the tile loop as it always was (the do-while and u fold away).  Two sets: set u holds tile tb + u NW, the inner loop
+        // is unrolled over the sets, and a set is refilled with tile t + SETS NW once the math has consumed it.  (Written so, and not as
+        // a lambda or a loop over sets around the body, because those change the one-set kernels' code: tools/isa_same.py.)
+        int tb = wave;
+        do {
+#pragma unroll
+        for (int t = tb, u = 0; t < ntile && (SETS == 1 || u < SETS); t += NW, ++u) {
+            const bool second = SETS > 1 && u > 0;
+            const kreg_t* const krt = second ? kr2 : kr;
+            const u32x4* const vrt = second ? vr2 : vr;
             const int t0 = lo + t * KT;
             // V tile -> this wave's LDS image (row-major, padded rows)
 #pragma unroll
-            for (int i = 0; i < VLD; ++i) *(__attribute__((address_space(3))) u32x4*)(vimg + vwr + i * Gm::KPI * VROW) = vr[i];
+            for (int i = 0; i < NVLD; ++i) {
+                if constexpr (KV8) {
+                    typedef __attribute__((address_space(3))) v8 lds_v8;
+                    *(lds_v8*)(vimg + vwr + i * VKPI * VROW) = cvt_e4m3x8<T, v8>(vrt[i][0], vrt[i][1]);
+                    *(lds_v8*)(vimg + vwr + i * VKPI * VROW + 16) = cvt_e4m3x8<T, v8>(vrt[i][2], vrt[i][3]);
+                } else {
+                    *(__attribute__((address_space(3))) u32x4*)(vimg + vwr + i * VKPI * VROW) = vr[i];
+                }
+            }
             // S^T = K Q^T
             f32x4 sacc[NKB];
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 sacc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int q = 0; q < KS; ++q) sacc[kb] = E::mfma(__builtin_bit_cast(v8, kr[kb * KS + q]), qf[q], sacc[kb]);
+                for (int q = 0; q < KS; ++q) {
+                    v8 kf;
+                    if constexpr (KV8) kf = cvt_e4m3x8<T, v8>(krt[kb * KS + q][0], krt[kb * KS + q][1]);
+                    else kf = __builtin_bit_cast(v8, kr[kb * KS + q]);
+                    sacc[kb] = E::mfma(kf, qf[q], sacc[kb]);
+                }
             }
-            if (t + NW < ntile) issue(t + NW);
+            if (t + SETS * NW < ntile) {
+                if (second) issue(t + SETS * NW, true);
+                else issue(t + SETS * NW);
+            }
 
             // scores in log2 units; masks only where the tile reaches past the split, the causal cut (TREE: the step's own keys), below a row's window, or a key mask exists
             const bool edge = km != nullptr || t0 + KT > hi || t0 + KT > min_lim || (WINDOW && t0 < max_lo);
@@ -301,7 +384,9 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float sc = sacc[kb][e] * p.scale_log2;
+                    float sc;
+                    if constexpr (KV8) sc = sacc[kb][e] * score_mul;
+                    else sc = sacc[kb][e] * p.scale_log2;
                     if (edge) {
                         const int key = t0 + kb * 16 + 4 * h + e;
                         bool vis;
@@ -358,6 +443,8 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
             }
             asm volatile("" ::: "memory");     // ... and the next tile's image writes behind them
         }
+        tb += SETS * NW;
+        } while (SETS > 1 && tb < ntile);
     }
     // row sum over the row's four lane groups
     l += __shfl_xor(l, 16);
@@ -400,7 +487,8 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * D + d0 + d);
-            store4<OT>(orow_p + d0 + d, acc * inv);
+            if constexpr (KV8) store4<OT>(orow_p + d0 + d, acc * (inv * out_mul));
+            else store4<OT>(orow_p + d0 + d, acc * inv);
         }
         if (p.lse && d0 == 0)
             p.lse[((int64_t)b * p.H + oh) * p.Sq + oi] = L > 0.f ? (M + __log2f(L)) * 0.6931471805599453f : -__builtin_inff();
@@ -412,6 +500,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * D + d0 + d);
+            if constexpr (KV8) acc *= out_mul;
             *(f32x4*)(po + d0 + d) = acc;
         }
         if (d0 == 0) {

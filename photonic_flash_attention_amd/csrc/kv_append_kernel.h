@@ -21,6 +21,12 @@
 // uniform per workgroup, so cu[b], cu[b + 1] and cache_seqlens[b] are scalar loads and the workgroups past a sequence's last item
 // (all of them for an empty sequence) return before any vector memory instruction.  The table lookup is per lane: a workgroup's rows
 // may straddle pages.  No LDS, no atomics, no workspace; the element type does not matter (any 2-byte type moves the same way).
+//
+// QUANT (pfa_kv_append_q8; T is the source's 16-bit type, KvAppendQ8Params carries the descales): the cache holds OCP e4m3fn bytes, cache
+// strides are in bytes, and every source element x is stored as e4m3fn(clamp(float(x) / descale[b * ds_sb + hk], -448, 448)): an IEEE
+// fp32 division, the clamp (a NaN passes it and stays NaN), and v_cvt_pk_fp8_f32's round to nearest even.  A work item is 16 elements:
+// two 16-byte loads and one 16-byte store each for K and V; dchunks = D / 16, units = Hkv * D / 16.  Placement, drops and the grid rule
+// are the code above.  The descale is a per-lane load (a workgroup's items span heads).  QUANT = false compiles to the code it had.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,10 +56,40 @@ struct KvAppendParams {
     int32_t page_size, num_pages;
 };
 
-typedef uint32_t kv_append_b128 __attribute__((ext_vector_type(4)));
+// QUANT only: fp32 descales, k_descale[b * ds_sb + hk] (ds_sb = 0: one row for every sequence)
+struct KvAppendQ8Params : KvAppendParams {
+    const float* k_descale;
+    const float* v_descale;
+    int64_t ds_sb;
+};
+template <bool QUANT> struct KvAppendParamsOf { typedef KvAppendParams type; };
+template <> struct KvAppendParamsOf<true> { typedef KvAppendQ8Params type; };
 
-template <bool VARLEN, bool PAGED>
-__global__ __launch_bounds__(KV_APPEND_THREADS) void kv_append_kernel(const KvAppendParams p) {
+typedef uint32_t kv_append_b128 __attribute__((ext_vector_type(4)));
+typedef uint32_t kv_append_b64 __attribute__((ext_vector_type(2)));
+
+// 8 elements of T (16 bytes) -> 8 e4m3fn bytes: x / d in fp32, clamped to the format's finite range (NaN stays NaN), rounded to nearest even
+template <typename T>
+__device__ __forceinline__ kv_append_b64 kv_quant8(kv_append_b128 x, float d) {
+    typedef T t8 __attribute__((ext_vector_type(8)));
+    const t8 e = __builtin_bit_cast(t8, x);
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float y = (float)e[j] / d;
+        f[j] = y != y ? y : fminf(fmaxf(y, -448.f), 448.f);
+    }
+    int a = 0, b = 0;
+    a = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], a, false);
+    a = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], a, true);
+    b = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], b, false);
+    b = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], b, true);
+    return kv_append_b64{(uint32_t)a, (uint32_t)b};
+}
+
+template <bool VARLEN, bool PAGED, bool QUANT = false, typename T = void>
+__global__ __launch_bounds__(KV_APPEND_THREADS) void kv_append_kernel(const typename KvAppendParamsOf<QUANT>::type p) {
+    constexpr int CH = QUANT ? 16 : 8;                   // elements per work item
     const int b = blockIdx.x / p.nchunk;
     const int item0 = (blockIdx.x - b * p.nchunk) * KV_APPEND_THREADS;      // the workgroup's first item of sequence b
 
@@ -83,8 +119,8 @@ __global__ __launch_bounds__(KV_APPEND_THREADS) void kv_append_kernel(const KvAp
         ksrc = (int64_t)b * p.kn_sb + (int64_t)i * p.kn_ss;
         vsrc = (int64_t)b * p.vn_sb + (int64_t)i * p.vn_ss;
     }
-    ksrc += (int64_t)hk * p.kn_sh + c * 8;
-    vsrc += (int64_t)hk * p.vn_sh + c * 8;
+    ksrc += (int64_t)hk * p.kn_sh + c * CH;
+    vsrc += (int64_t)hk * p.vn_sh + c * CH;
 
     int64_t slab = b, tok = pos;                         // contiguous: the sequence's cache; PAGED: the page and the token inside it
     if constexpr (PAGED) {
@@ -94,13 +130,23 @@ __global__ __launch_bounds__(KV_APPEND_THREADS) void kv_append_kernel(const KvAp
         slab = pg;
         tok = pos - lp * p.page_size;
     }
-    const int64_t kdst = slab * p.k_sb + tok * p.k_ss + (int64_t)hk * p.k_sh + c * 8;
-    const int64_t vdst = slab * p.v_sb + tok * p.v_ss + (int64_t)hk * p.v_sh + c * 8;
+    const int64_t kdst = slab * p.k_sb + tok * p.k_ss + (int64_t)hk * p.k_sh + c * CH;
+    const int64_t vdst = slab * p.v_sb + tok * p.v_ss + (int64_t)hk * p.v_sh + c * CH;
 
-    const kv_append_b128 kx = *reinterpret_cast<const kv_append_b128*>((const uint16_t*)p.k_new + ksrc);
-    const kv_append_b128 vx = *reinterpret_cast<const kv_append_b128*>((const uint16_t*)p.v_new + vsrc);
-    *reinterpret_cast<kv_append_b128*>((uint16_t*)p.k_cache + kdst) = kx;
-    *reinterpret_cast<kv_append_b128*>((uint16_t*)p.v_cache + vdst) = vx;
+    if constexpr (QUANT) {
+        const kv_append_b128* ks = reinterpret_cast<const kv_append_b128*>((const uint16_t*)p.k_new + ksrc);
+        const kv_append_b128* vs = reinterpret_cast<const kv_append_b128*>((const uint16_t*)p.v_new + vsrc);
+        const kv_append_b128 k0 = ks[0], k1 = ks[1], v0 = vs[0], v1 = vs[1];
+        const float kd = p.k_descale[(int64_t)b * p.ds_sb + hk], vd = p.v_descale[(int64_t)b * p.ds_sb + hk];
+        const kv_append_b64 ka = kv_quant8<T>(k0, kd), kb = kv_quant8<T>(k1, kd), va = kv_quant8<T>(v0, vd), vb = kv_quant8<T>(v1, vd);
+        *reinterpret_cast<kv_append_b128*>((uint8_t*)p.k_cache + kdst) = kv_append_b128{ka[0], ka[1], kb[0], kb[1]};
+        *reinterpret_cast<kv_append_b128*>((uint8_t*)p.v_cache + vdst) = kv_append_b128{va[0], va[1], vb[0], vb[1]};
+    } else {
+        const kv_append_b128 kx = *reinterpret_cast<const kv_append_b128*>((const uint16_t*)p.k_new + ksrc);
+        const kv_append_b128 vx = *reinterpret_cast<const kv_append_b128*>((const uint16_t*)p.v_new + vsrc);
+        *reinterpret_cast<kv_append_b128*>((uint16_t*)p.k_cache + kdst) = kx;
+        *reinterpret_cast<kv_append_b128*>((uint16_t*)p.v_cache + vdst) = vx;
+    }
 }
 
 }  // namespace pfa

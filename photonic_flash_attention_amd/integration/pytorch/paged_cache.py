@@ -25,6 +25,12 @@ appends into a partly filled tail page it shares takes a fresh page first and th
 ``cow_rows`` at the head of ``write_step``, so that a captured step replays through forks.  Full shared pages are never written, so
 they are never copied, and ``common_prefix`` names the keys a group of slots shares page for page: the ``shared_prefix=`` of
 ``decode`` / ``prefill`` / ``prefill_varlen``.
+
+``dtype=torch.float8_e4m3fn`` with ``k_descale=, v_descale=`` (fp32 ``[Hkv]``: one scale per K/V head for the whole pool, since pages may
+be shared between sequences) keeps the pools in FP8: half the bytes per key, twice the keys per pool.  The append methods take the
+16-bit rows and quantise them (``ops.quantize_kv``'s rule; ``write_step`` runs the quantising HIP append), ``decode`` runs the FP8 decode
+kernel, ``gather`` returns the FP8 pages.  Not built for an FP8 cache, and refused with ``ValueError``: ``prefill``, ``prefill_varlen``,
+the rotary form of ``write_step``, and ``decode``'s ``window`` / ``tree_mask`` / ``shared_prefix``.
 """
 
 from __future__ import annotations
@@ -59,7 +65,7 @@ class PagedKVCache:
 
     def __init__(self, num_pages: int, page_size: int, Hkv: int, D: int, dtype: torch.dtype = torch.bfloat16,
                  device: Union[str, torch.device] = "cuda", max_batch: int = 1, max_pages_per_seq: Optional[int] = None,
-                 copy_on_write: bool = False):
+                 k_descale: Optional[torch.Tensor] = None, v_descale: Optional[torch.Tensor] = None, copy_on_write: bool = False):
         if page_size < 64 or page_size % 64:
             raise ValueError(f"page size {page_size}: must be a multiple of 64 keys (a key tile of the kernel lies inside one page)")
         if num_pages < 1 or Hkv < 1 or D < 1 or max_batch < 1:
@@ -70,6 +76,18 @@ class PagedKVCache:
         if self.max_pages_per_seq < 1:
             raise ValueError("max_pages_per_seq must be positive")
         self.device = torch.device(device)
+        self._fp8 = dtype == ops.FP8
+        self._kd, self._vd = k_descale, v_descale
+        if self._fp8:
+            if D % 16:
+                raise ValueError(f"head dim {D}: an FP8 cache takes a multiple of 16")
+            for name, d in (("k_descale", k_descale), ("v_descale", v_descale)):
+                if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.shape != (Hkv,) or not d.is_contiguous() \
+                        or d.device.type != self.device.type:
+                    raise ValueError(f"an FP8 cache needs {name}: a contiguous fp32 [Hkv] = [{Hkv}] tensor on the cache's device (one scale "
+                                     "per K/V head: pages may be shared between sequences)")
+        elif k_descale is not None or v_descale is not None:
+            raise ValueError("k_descale / v_descale go with dtype=torch.float8_e4m3fn only")
         self._k = torch.zeros(num_pages, page_size, Hkv, D, dtype=dtype, device=self.device)
         self._v = torch.zeros_like(self._k)
         self._table = torch.zeros(max_batch, self.max_pages_per_seq, dtype=torch.int32, device=self.device)
@@ -298,13 +316,38 @@ class PagedKVCache:
             self._host_lens[s] += x
         return starts
 
+    def _copy_pools(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The pools as ``ops.page_copy`` takes them.  The copy kernel moves 16-byte pieces and does not care what they hold: FP8 pools
+        go as a 2-byte view, ``D / 2`` "elements" a row."""
+        if self._fp8:
+            return self._k.view(torch.float16).transpose(1, 2), self._v.view(torch.float16).transpose(1, 2)
+        return self._k.transpose(1, 2), self._v.transpose(1, 2)
+
     def _copy_now(self) -> None:
         """Run the copies the last ``_grow`` recorded (``ops.page_copy``, one launch) and forget them."""
         if self._copies:
             pairs = torch.tensor([c[1:3] for c in self._copies], dtype=torch.int32).to(self.device, non_blocking=True)
             rows = torch.tensor([c[3] for c in self._copies], dtype=torch.int32).to(self.device, non_blocking=True)
-            ops.page_copy(self._k.transpose(1, 2), self._v.transpose(1, 2), pairs, rows=rows)
+            ops.page_copy(*self._copy_pools(), pairs, rows=rows)
             self._copies = []
+
+    def _check_new(self, k_new: torch.Tensor, v_new: torch.Tensor) -> None:
+        if self._fp8:
+            if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype:
+                raise ValueError("k_new / v_new must be bf16 or fp16: an FP8 cache quantises the rows it is given")
+        elif k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
+            raise ValueError("k_new / v_new must have the cache's dtype")
+
+    def _put(self, idx: torch.Tensor, k_rows: torch.Tensor, v_rows: torch.Tensor) -> None:
+        """Rows ``[n, Hkv, D]`` to rows ``idx`` of the ``[num_pages * page_size]`` token view; an FP8 cache quantises them first
+        (``ops.quantize_kv``'s rule) and moves bytes."""
+        rows = self.num_pages * self.page_size
+        for pool, x, d in ((self._k, k_rows, self._kd), (self._v, v_rows, self._vd)):
+            if self._fp8:
+                x8 = (x.to(torch.float32) / d[None, :, None]).clamp(-ops.FP8_MAX, ops.FP8_MAX).to(ops.FP8)
+                pool.view(torch.uint8).view(rows, self.Hkv, self.D).index_copy_(0, idx, x8.view(torch.uint8))
+            else:
+                pool.view(rows, self.Hkv, self.D).index_copy_(0, idx, x)
 
     def _dst_rows(self, slots: List[int], starts: List[int], lens: List[int]) -> List[int]:
         """Row of the ``[num_pages * page_size]`` token view each appended token goes to."""
@@ -322,16 +365,13 @@ class PagedKVCache:
             raise ValueError("a slot may appear once per append")
         if k_new.dim() != 4 or k_new.shape[:2] != (n, self.Hkv) or k_new.shape[3] != self.D or v_new.shape != k_new.shape:
             raise ValueError(f"k_new / v_new must be [{n}, {self.Hkv}, Sq, {self.D}], got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
-        if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
-            raise ValueError("k_new / v_new must have the cache's dtype")
+        self._check_new(k_new, v_new)
         Sq = k_new.shape[2]
         dst = self._dst_rows(slots, self._grow(slots, [Sq] * n), [Sq] * n)
         self._copy_now()
         if Sq:
             idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
-            rows = self.num_pages * self.page_size
-            self._k.view(rows, self.Hkv, self.D).index_copy_(0, idx, k_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D))
-            self._v.view(rows, self.Hkv, self.D).index_copy_(0, idx, v_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D))
+            self._put(idx, k_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D), v_new.permute(0, 2, 1, 3).reshape(n * Sq, self.Hkv, self.D))
         self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
 
     def append_varlen(self, slots: Union[int, Sequence[int]], k_new: torch.Tensor, v_new: torch.Tensor, lens: Sequence[int]) -> None:
@@ -348,15 +388,12 @@ class PagedKVCache:
             raise ValueError(f"lens must hold one non-negative token count per slot, got {lens} for {n} slots")
         if k_new.dim() != 3 or k_new.shape != (total, self.Hkv, self.D) or v_new.shape != k_new.shape:
             raise ValueError(f"k_new / v_new must be [{total}, {self.Hkv}, {self.D}], got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
-        if k_new.dtype != self._k.dtype or v_new.dtype != self._k.dtype:
-            raise ValueError("k_new / v_new must have the cache's dtype")
+        self._check_new(k_new, v_new)
         dst = self._dst_rows(slots, self._grow(slots, lens), lens)
         self._copy_now()
         if total:
             idx = torch.tensor(dst, dtype=torch.int64).to(self.device, non_blocking=True)
-            rows = self.num_pages * self.page_size
-            self._k.view(rows, self.Hkv, self.D).index_copy_(0, idx, k_new)
-            self._v.view(rows, self.Hkv, self.D).index_copy_(0, idx, v_new)
+            self._put(idx, k_new, v_new)
         self._lens.copy_(torch.tensor(self._host_lens, dtype=torch.int32), non_blocking=True)
 
     def advance(self, slots: Union[int, Sequence[int]], lens: Sequence[int]) -> None:
@@ -452,14 +489,15 @@ class PagedKVCache:
         self._table[slot, j] = a
 
     def gather(self, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The slot's K and V as contiguous ``[Hkv, len, D]`` tensors (tests, debugging)."""
+        """The slot's K and V as contiguous ``[Hkv, len, D]`` tensors of the cache's dtype (tests, debugging)."""
         n = self._host_lens[self._check_slot(slot)]
         if any(p < 0 for p in self._pages[slot][:-(-n // self.page_size)]):
             raise ValueError(f"slot {slot}: its first pages were released behind the window, their keys are gone")
         pg = torch.tensor(self._pages[slot][:-(-n // self.page_size)], dtype=torch.int64).to(self.device)
         out = []
         for pool in (self._k, self._v):
-            out.append(pool.index_select(0, pg).reshape(-1, self.Hkv, self.D)[:n].permute(1, 0, 2).contiguous())
+            raw = pool.view(torch.uint8) if self._fp8 else pool            # an FP8 cache: bytes in, the FP8 pages out
+            out.append(raw.index_select(0, pg).reshape(-1, self.Hkv, self.D)[:n].permute(1, 0, 2).contiguous().view(pool.dtype))
         return out[0], out[1]
 
     # --- the kernel ---------------------------------------------------------------------------------------------------------------
@@ -519,6 +557,8 @@ class PagedKVCache:
         names) is enqueued in front: the copies the last ``advance`` calls for, or nothing when the table is empty.  It reads the
         device table, so a captured ``write_step`` + attention replays through forks."""
         rotary = rotary_cos is not None or rotary_sin is not None
+        if self._fp8 and (rotary or q is not None):
+            raise ValueError("write_step: rotary is not fused into the quantising append of an FP8 cache; rotate q and k_new first")
         if not rotary and (q is not None or rotary_interleaved or pos_offsets is not None):
             raise ValueError("q, rotary_interleaved and pos_offsets need rotary_cos and rotary_sin")
         if rotary and (rotary_cos is None or rotary_sin is None):
@@ -528,13 +568,13 @@ class PagedKVCache:
             return None if q is None else torch.empty_like(q)   # a step without rows, as append_varlen takes one
         cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], k_new.shape[0], "k_new")
         if self._cow:
-            ops.page_copy(self._k.transpose(1, 2), self._v.transpose(1, 2), self._cow_pairs, rows=self._cow_rows)
+            ops.page_copy(*self._copy_pools(), self._cow_pairs, rows=self._cow_rows)
         if rotary:
             return ops.rope_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens,
                                    rotary_cos=rotary_cos, rotary_sin=rotary_sin, q=q, rotary_interleaved=rotary_interleaved,
                                    pos_offsets=pos_offsets, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, block_table=table)
         ops.kv_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, cu_seqlens_q=cu_seqlens_q,
-                      max_seqlen_q=max_seqlen_q, block_table=table)
+                      max_seqlen_q=max_seqlen_q, block_table=table, k_descale=self._kd, v_descale=self._vd)
 
     def decode(self, q: torch.Tensor, slots: Slots = None, **kw):
         """``ops.fa3_decode`` of ``q [B, H, Sq, D]`` against the sequences in ``slots`` (batch row i reads slot ``slots[i]``; None:
@@ -545,6 +585,8 @@ class PagedKVCache:
         ``[B, Sq]`` words that verify a drafted token tree, ``ops.tree_mask_from_parents``; ``truncate`` then takes the rejected rows
         back --, ...) pass through.  -> ``(o, lse)``."""
         table, lens = self._rows(slots)
+        if self._fp8:                                                      # the cache's own scales; the refused keywords raise in ops
+            kw = dict(kw, k_descale=self._kd, v_descale=self._vd)
         return ops.fa3_decode(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
 
     def prefill(self, q: torch.Tensor, slots: Slots = None, **kw):
@@ -552,6 +594,8 @@ class PagedKVCache:
         speculative step) against the sequences in ``slots``, which are chosen and captured as in ``decode``.  ``append`` the rows'
         own K / V first: the lengths count them, and ``causal`` (the default) is bottom-right aligned.  Keyword arguments
         (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o, lse)``."""
+        if self._fp8:
+            raise ValueError("prefill over an FP8 cache is not built: run the dense forward on the prompt's 16-bit K / V and append them")
         table, lens = self._rows(slots)
         return ops.fa3_prefill_cache(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, block_table=table, **kw)
 
@@ -563,6 +607,8 @@ class PagedKVCache:
         ``max_seqlen_q = max(q_lens)`` unless given; a caller that captures graphs passes its own device ``cu_seqlens_q`` (int32
         ``[len(slots) + 1]``, updated in place between replays) and the ``max_seqlen_q`` bound instead.  Keyword arguments
         (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
+        if self._fp8:
+            raise ValueError("prefill_varlen over an FP8 cache is not built: run the dense forward on the 16-bit K / V and append them")
         table, lens = self._rows(slots)
         cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], q.shape[0], "q")
         return ops.fa3_prefill_varlen(q, self._k.transpose(1, 2), self._v.transpose(1, 2), cu_seqlens_q=cu_seqlens_q,

@@ -491,6 +491,60 @@ def _raise_status(entry: str, st: int, null_too: bool = False) -> None:
     _capi.check_status(st)
 
 
+FP8 = torch.float8_e4m3fn           # the element type of an FP8 KV cache: OCP e4m3fn (max finite 448, 0x7f / 0xff NaN, no infinities)
+FP8_MAX = 448.0
+
+
+def _descale_like(x: torch.Tensor, descale: torch.Tensor) -> torch.Tensor:
+    """``descale`` ``[Hkv]`` or ``[B, Hkv]`` (fp32) shaped to broadcast over ``x`` ``[B, Hkv, S, D]`` (pools: ``[num_pages, Hkv, page, D]``)."""
+    if not isinstance(descale, torch.Tensor) or descale.dtype != torch.float32 or descale.dim() not in (1, 2):
+        raise ValueError("a descale must be an fp32 tensor [Hkv] or [B, Hkv]")
+    if x.dim() != 4 or descale.shape[-1] != x.shape[1] or (descale.dim() == 2 and descale.shape[0] != x.shape[0]):
+        raise ValueError(f"descale {tuple(descale.shape)} does not match a [B, Hkv, S, D] tensor of shape {tuple(x.shape)}")
+    return descale[..., None, None]
+
+
+def quantize_kv(x: torch.Tensor, descale: torch.Tensor) -> torch.Tensor:
+    """``x`` ``[B, Hkv, S, D]`` (any floating dtype) as the FP8 cache holds it: ``e4m3fn(clamp(float(x) / descale, -448, 448))``, descale
+    fp32 ``[Hkv]`` or ``[B, Hkv]`` -- the rule of ``kv_append`` into an FP8 cache, in plain torch (a first prompt's K / V, the tests).
+    The division is fp32, the cast rounds to nearest even, NaN stays NaN; without the clamp the cast would turn 500.0 into NaN."""
+    d = _descale_like(x, descale)
+    return (x.to(torch.float32) / d).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def dequantize_kv(x8: torch.Tensor, descale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The values an FP8 cache ``x8`` ``[B, Hkv, S, D]`` stands for, ``e4m3(x8) * descale``, as ``dtype``: computed in fp64 for
+    ``torch.float64`` (exact: what a reference takes), else in fp32 and rounded once."""
+    if x8.dtype != FP8:
+        raise ValueError("dequantize_kv takes a torch.float8_e4m3fn tensor")
+    d = _descale_like(x8, descale)
+    w = torch.float64 if dtype == torch.float64 else torch.float32
+    return (x8.to(torch.float32).to(w) * d.to(w)).to(dtype)
+
+
+def _kv_quant_arg(entry: str, k_cache, v_cache, k_descale, v_descale, B: int, Hkv: int, device):
+    """The ``pfa_fa3_kv_quant`` block of a call over the caches, or None for 16-bit caches.  FP8 caches need both descales (fp32,
+    contiguous, ``[Hkv]`` or ``[B, Hkv]``, on ``device``); 16-bit caches refuse them.  The block points into the caller's tensors, so a
+    captured call sees their contents change."""
+    if k_cache.dtype != FP8 and v_cache.dtype != FP8:
+        if k_descale is not None or v_descale is not None:
+            raise ValueError("k_descale / v_descale go with torch.float8_e4m3fn caches only")
+        return None
+    if k_cache.dtype != FP8 or v_cache.dtype != FP8:
+        raise ValueError("k_cache and v_cache must both be torch.float8_e4m3fn")
+    if k_descale is None or v_descale is None:
+        raise ValueError(f"{entry}: torch.float8_e4m3fn caches need k_descale and v_descale (fp32 [Hkv] or [B, Hkv])")
+    for name, d in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.shape not in ((Hkv,), (B, Hkv)) or not d.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 tensor [Hkv] = [{Hkv}] or [B, Hkv] = [{B}, {Hkv}]")
+        if d.device != device:
+            raise ValueError(f"{name} must live on the operands' device")
+    if k_descale.shape != v_descale.shape:
+        raise ValueError("k_descale and v_descale must have one shape")
+    return _capi.make_kv_quant(k_descale=k_descale.data_ptr(), v_descale=v_descale.data_ptr(),
+                               descale_stride_b=Hkv if k_descale.dim() == 2 else 0)
+
+
 def _cache_geometry(name: str, rows, B, Hkv, D, k_cache, v_cache, block_table, H=None):
     """What every call over a KV cache, reading or writing, checks about its 4-D caches (or pools and block table) against B
     sequences of Hkv key heads and head dim D.  ``rows`` (printed as ``name``) is the tensor they are matched with: q, or k_new.
@@ -517,14 +571,17 @@ def _cache_geometry(name: str, rows, B, Hkv, D, k_cache, v_cache, block_table, H
     return Smax, page_size, num_pages
 
 
-def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table):
+def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8=False):
     """What the attention calls over a KV cache check about their caches against a query of B sequences, H heads and head dim D:
     ``_cache_geometry`` and what only the readers ask.  -> ``(Hkv, Smax, page_size, num_pages, output dtype)``."""
     Hkv = k_cache.shape[1]
     Smax, page_size, num_pages = _cache_geometry("q", q, B, Hkv, D, k_cache, v_cache, block_table, H)
     if block_table is not None and (not block_table.is_cuda or block_table.device != q.device):
         raise ValueError("block_table must live on the operands' device (there is no CPU path)")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    if fp8:
+        if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != FP8 or v_cache.dtype != FP8:
+            raise ValueError("q must be bf16 or fp16, k_cache and v_cache torch.float8_e4m3fn")
+    elif q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise ValueError("q, k_cache, v_cache must share dtype bf16 or fp16")
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda) or k_cache.device != q.device or v_cache.device != q.device:
         raise ValueError(f"{entry} needs device tensors on one device (there is no CPU path)")
@@ -534,13 +591,13 @@ def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_t
     return Hkv, Smax, page_size, num_pages, odt
 
 
-def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table):
+def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table, fp8=False):
     """Validation and marshalling ``fa3_decode`` and ``fa3_prefill_cache`` share (both take ``pfa_fa3_decode_args``): the operands,
     the output buffer and the block table.  -> ``(args, out, Smax)``; ``entry`` names the C entry point in the messages."""
     if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
     B, H, Sq, D = q.shape
-    Hkv, Smax, page_size, num_pages, odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table)
+    Hkv, Smax, page_size, num_pages, odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8)
     if out is None:
         out = torch.empty((B, Sq, H, D), dtype=odt, device=q.device).permute(0, 2, 1, 3)
     elif out.shape != (B, H, Sq, D) or out.dtype != odt or out.device != q.device:
@@ -702,7 +759,8 @@ def _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, max_seqlen_q, blo
             pool[pg[ok], :, (pos % page_size)[ok]] = r[ok]
 
 
-def _append_operands(entry: str, k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others=()):
+def _append_operands(entry: str, k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others=(),
+                     fp8=False):
     """What ``kv_append`` and ``rope_append`` check about the step's rows, the caches and the device data they share (``others``: the
     further tensors that must live on k_new's device).  -> ``(ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages)``."""
     ragged = cu_seqlens_q is not None
@@ -727,7 +785,12 @@ def _append_operands(entry: str, k_new, v_new, k_cache, v_cache, cache_seqlens, 
         max_seqlen_q, total = Sq, B * Sq
     max_seqlen_q = int(max_seqlen_q)
     Smax, page_size, num_pages = _cache_geometry("k_new", k_new, B, Hkv, D, k_cache, v_cache, block_table)
-    if k_new.dtype not in (torch.bfloat16, torch.float16) or any(t.dtype != k_new.dtype for t in (v_new, k_cache, v_cache)):
+    if fp8:
+        if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype or k_cache.dtype != FP8 or v_cache.dtype != FP8:
+            raise ValueError("k_new, v_new must share dtype bf16 or fp16, k_cache and v_cache be torch.float8_e4m3fn")
+        if D % 16:
+            raise ValueError(f"head dim {D}: the quantising append takes a multiple of 16 up to 256")
+    elif k_new.dtype not in (torch.bfloat16, torch.float16) or any(t.dtype != k_new.dtype for t in (v_new, k_cache, v_cache)):
         raise ValueError("k_new, v_new, k_cache, v_cache must share dtype bf16 or fp16")
     if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.shape != (B,):
         raise ValueError("cache_seqlens must be a [B] tensor (the lengths after the step)")
@@ -765,20 +828,41 @@ def _append_args(make, entry: str, k_new, v_new, k_cache, v_cache, geometry, cu_
     return a
 
 
-def _append_launch(entry: str, a, cache_seqlens, k_new, B) -> None:
-    """``cache_seqlens`` into the block, then the one launch of ``entry`` on k_new's current stream."""
+def _append_launch(entry: str, a, cache_seqlens, k_new, B, quant=None) -> None:
+    """``cache_seqlens`` into the block, then the one launch of ``entry`` (with ``quant``: of ``{entry}_q8``) on k_new's current stream."""
     keep = []
     _set_cache_seqlens(a, cache_seqlens, k_new, keep, B)
     stream = torch.cuda.current_stream(k_new.device)
-    st = getattr(_capi.load(), entry)(C.byref(a), C.c_void_p(stream.cuda_stream))
+    if quant is not None:
+        st = getattr(_capi.load(), entry + "_q8")(C.byref(a), C.byref(quant), C.c_void_p(stream.cuda_stream))
+    else:
+        st = getattr(_capi.load(), entry)(C.byref(a), C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
     for t in keep:   # tensors made here must outlive the enqueued kernel
         t.record_stream(stream)
 
 
+def _kv_append_q8_model(k_new, v_new, k_cache, v_cache, k_descale, v_descale, lens, cu, max_seqlen_q, block_table) -> None:
+    """``pfa_kv_append_q8``'s rule in plain torch: every source element as ``quantize_kv`` stores it, then ``_kv_append_model``'s
+    placement, on the caches' bytes.  The executable specification, and what ``kv_append`` runs on CPU tensors with FP8 caches."""
+    def rows8(x, d):
+        if cu is None:                                    # [B, Hkv, Sq, D]
+            return quantize_kv(x, d)
+        if d.dim() == 2:                                  # packed rows: each row takes its sequence's scales
+            seq = torch.zeros(x.shape[0], dtype=torch.int64)
+            for b in range(len(lens)):
+                s_b = min(max(cu[b], 0), x.shape[0])
+                seq[s_b:min(max(cu[b + 1], s_b), x.shape[0])] = b
+            d = d[seq]                                    # [total, Hkv]
+        return (x.to(torch.float32) / d[..., None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+    _kv_append_model(rows8(k_new, k_descale).view(torch.uint8), rows8(v_new, v_descale).view(torch.uint8), k_cache.view(torch.uint8),
+                     v_cache.view(torch.uint8), lens, cu, max_seqlen_q, block_table)
+
+
 def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
               cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None,
-              block_table: Optional[torch.Tensor] = None) -> None:
+              block_table: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
+              v_descale: Optional[torch.Tensor] = None) -> None:
     """Device-side KV-cache append (``pfa_kv_append``): place a step's new K / V rows into the cache the calls over a KV cache read --
     the write side of ``fa3_decode`` / ``fa3_prefill_cache`` / ``fa3_prefill_varlen``, from device data alone.
 
@@ -796,13 +880,27 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
 
     On device tensors: one launch of a HIP copy kernel whose grid depends on host shapes only -- no host synchronisation, no tensor
     creation, capturable in ``torch.cuda.graph`` and valid while cu_seqlens_q, lengths, table and cache change between replays.  On CPU
-    tensors the same rule runs in plain torch (the executable specification; ``PagedKVCache``'s bookkeeping is tested through it)."""
-    geo = _append_operands("pfa_kv_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table)
+    tensors the same rule runs in plain torch (the executable specification; ``PagedKVCache``'s bookkeeping is tested through it).
+
+    FP8 cache: k_cache / v_cache of ``torch.float8_e4m3fn`` with ``k_descale=, v_descale=`` (contiguous fp32 ``[Hkv]`` or ``[B, Hkv]`` on the
+    tensors' device; required then, refused otherwise) run the quantising append (``pfa_kv_append_q8``): the same placement, every
+    16-bit source element x stored as ``e4m3fn(clamp(float(x) / descale[b, hk], -448, 448))`` -- an fp32 division, round to nearest
+    even, NaN stays NaN; ``quantize_kv`` is the rule in plain torch, and what runs on CPU tensors.  D a multiple of 16 up to 256."""
+    if not all(isinstance(t, torch.Tensor) for t in (k_new, v_new, k_cache, v_cache)):
+        raise ValueError("k_new, v_new, k_cache, v_cache must be tensors")
+    fp8 = k_cache.dtype == FP8 or v_cache.dtype == FP8
+    geo = _append_operands("pfa_kv_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
+                           fp8=fp8)
+    quant = _kv_quant_arg("pfa_kv_append", k_cache, v_cache, k_descale, v_descale, geo[1], geo[2], k_new.device)
     if k_new.device.type == "cpu":
-        _kv_append_model(k_new, v_new, k_cache, v_cache, cache_seqlens.tolist(), cu_seqlens_q.tolist() if geo[0] else None, geo[5], block_table)
+        lens, cu = cache_seqlens.tolist(), cu_seqlens_q.tolist() if geo[0] else None
+        if fp8:
+            _kv_append_q8_model(k_new, v_new, k_cache, v_cache, k_descale, v_descale, lens, cu, geo[5], block_table)
+        else:
+            _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, geo[5], block_table)
         return
     a = _append_args(_capi.make_kv_append_args, "pfa_kv_append", k_new, v_new, k_cache, v_cache, geo, cu_seqlens_q, block_table)
-    _append_launch("pfa_kv_append", a, cache_seqlens, k_new, geo[1])
+    _append_launch("pfa_kv_append", a, cache_seqlens, k_new, geo[1], quant)
 
 
 def _page_copy_model(k_pool, v_pool, pairs, rows) -> None:
@@ -1055,7 +1153,7 @@ def _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v
     return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets)
 
 
-def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=None, rotary=None, **ragged):
+def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=None, rotary=None, descales=None, **ragged):
     """The ``k_new=, v_new=`` form of the calls over a KV cache: ``kv_append`` enqueued in front of the attention launch, on the
     same stream, with the same lengths, ``cu_seqlens_q`` and table.  With ``rotary`` (``_rotary_kw``) it is ``rope_append`` instead, and
     q rotated into a fresh buffer is returned; otherwise None."""
@@ -1067,22 +1165,25 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     if rotary is not None:
         return rope_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, q=q, **rotary, **ragged)
-    kv_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, **ragged)
+    kd, vd = descales if descales is not None else (None, None)       # an FP8 cache: the quantising append
+    kv_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, k_descale=kd, v_descale=vd, **ragged)
     return None
 
 
-def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, tree=None, **ragged):
+def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, tree=None, quant=None, descales=None,
+                       **ragged):
     """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
     ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
     the current stream right behind it, the status, and the kept tensors' hold on the stream.  With ``rotary`` the launch reads the
     rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  ``key_splits`` (the C value, ``pfa_fa3_prefill`` only)
     launches ``pfa_fa3_prefill_split`` instead, which takes no extension; ``tree`` (``pfa_fa3_decode`` only) launches
-    ``pfa_fa3_decode_tree``, which takes it behind the extension.  -> lse or None."""
+    ``pfa_fa3_decode_tree``, which takes it behind the extension; ``quant`` (``pfa_fa3_decode`` over an FP8 cache, with the caller's
+    ``descales`` for the append) launches ``pfa_fa3_decode_q8``.  -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
         a.lse = lse.data_ptr()
-    q_rot = _append_first(*new_rows, q=q, rotary=rotary, **ragged)
+    q_rot = _append_first(*new_rows, q=q, rotary=rotary, descales=descales, **ragged)
     if q_rot is not None:
         a.q = q_rot.data_ptr()
         if q_rot.dim() == 3:
@@ -1093,6 +1194,8 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     stream = torch.cuda.current_stream(q.device)
     if key_splits is not None:
         st = _capi.load().pfa_fa3_prefill_split(C.byref(a), key_splits, C.c_void_p(stream.cuda_stream))
+    elif quant is not None:
+        st = _capi.load().pfa_fa3_decode_q8(C.byref(a), None if ext is None else C.byref(ext), C.byref(quant), C.c_void_p(stream.cuda_stream))
     elif tree is not None:
         st = _capi.load().pfa_fa3_decode_tree(C.byref(a), None if ext is None else C.byref(ext), C.byref(tree), C.c_void_p(stream.cuda_stream))
     else:
@@ -1272,7 +1375,8 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
-               prefix_key_splits=None, tree_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               prefix_key_splits=None, tree_mask: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
+               v_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -1342,7 +1446,31 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     number of key splits and the workspace do not depend on it: a captured step replays while the words change.  The fused rotary
     arguments rotate by ROW INDEX (row i at ``len_b - Sq + i``), which is a chain's position and not a tree's: for a tree the caller
     rotates Q and K itself at ``len_b - Sq + depth`` (``tree_mask_from_parents`` returns the depths) and passes no rotary tables.
-    ``None``: exactly the calls made without the argument."""
+    ``None``: exactly the calls made without the argument.
+
+    FP8 cache (``pfa_fa3_decode_q8``): k_cache / v_cache of ``torch.float8_e4m3fn`` (contiguous or pools), with ``k_descale=, v_descale=``
+    -- contiguous fp32 DEVICE tensors ``[Hkv]`` or ``[B, Hkv]``, required then and refused with 16-bit caches.  A cache element stands
+    for ``e4m3(byte) * descale[b, hk]``; the bytes are converted to q's dtype in registers (exact) in front of the same MFMA, k_descale
+    multiplies the softmax scale and v_descale the output once, so the call streams half the bytes and returns the attention over
+    ``dequantize_kv`` of the cache.  With all descales 1 it returns the bits of the 16-bit call on ``k_cache.to(q.dtype)``.  ``key_mask``,
+    ``cache_seqlens``, ``block_table``, ``causal``, ``out``, ``out_dtype``, ``return_lse`` work as above; ``k_new=, v_new=`` (16-bit rows) go
+    through the quantising ``kv_append`` first.  Splits and workspace are those of the 16-bit call, and a captured step replays while
+    the descales' contents change.  ``window``, ``tree_mask``, ``shared_prefix`` and the rotary arguments are not built for an FP8 cache
+    and raise ``ValueError``; bytes at and past a length are never read into a result (NaN bytes there are harmless)."""
+    fp8 = isinstance(k_cache, torch.Tensor) and isinstance(v_cache, torch.Tensor) and (k_cache.dtype == FP8 or v_cache.dtype == FP8)
+    if fp8:
+        for name, given in (("window", window is not None), ("tree_mask", tree_mask is not None), ("shared_prefix", shared_prefix is not None),
+                            ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None)):
+            if given:
+                raise ValueError(f"{name} is not supported with an FP8 (torch.float8_e4m3fn) KV cache: the FP8 decode takes key_mask, "
+                                 "cache_seqlens, block_table, causal and k_new / v_new only")
+        if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+            raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+        quant = _kv_quant_arg("pfa_fa3_decode", k_cache, v_cache, k_descale, v_descale, q.shape[0], k_cache.shape[1], q.device)
+    elif k_descale is not None or v_descale is not None:
+        raise ValueError("k_descale / v_descale go with torch.float8_e4m3fn caches only")
+    else:
+        quant = None
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
@@ -1356,7 +1484,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                                    prefix_key_splits=prefix_key_splits)
     if k_new is not None and cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
-    a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
+    a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table, fp8)
     B, H, Sq, _ = q.shape
     keep = []
     if key_mask is not None:
@@ -1372,13 +1500,14 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         if cache_seqlens is None:
             cache_seqlens = _mask_bound(km)
     _set_cache_seqlens(a, cache_seqlens, q, keep)
-    ws_bytes = int(_capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)))    # a tree changes nothing here
+    ws_bytes = int(_capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)))    # neither a tree nor an FP8 cache changes it
     if ws_bytes:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
         keep.append(ws)
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, max_seqlen_q=Sq)
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, quant=quant,
+                             descales=(k_descale, v_descale) if fp8 else None, max_seqlen_q=Sq)
     return out, lse
 
 
