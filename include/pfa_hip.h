@@ -24,6 +24,8 @@
  * the device (flash-attn's flash_attn_varlen_func), on the dense 16-bit kernels in a packed mode.
  * v9, additive: PFA_DTYPE_FP8_E4M3, pfa_fa3_kv_quant, pfa_fa3_decode_q8* and pfa_kv_append_q8* -- the decode over an FP8 (e4m3fn) KV
  * cache with one fp32 descale per (sequence, K/V head), and the append that quantises a step's 16-bit rows into it.
+ * v9, additive: pfa_fa3_prefill_q8* and pfa_fa3_prefill_varlen_q8* -- the forward over an FP8 (e4m3fn) KV cache, uniform and ragged,
+ * contiguous and paged: chunked and prefix-cached prefill, speculative steps past 64 rows and mixed batches on one-byte pages.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -1037,6 +1039,33 @@ int pfa_fa3_decode_q8_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache
                                int32_t* nsplit);
 int pfa_kv_append_q8_check(const pfa_kv_append_args* a, const pfa_fa3_kv_quant* quant);
 int pfa_kv_append_q8(const pfa_kv_append_args* a, const pfa_fa3_kv_quant* quant, void* stream);
+
+/*
+ * The forward over an FP8 (e4m3fn) KV cache (ABI v9, additive): pfa_fa3_prefill_ex and pfa_fa3_prefill_varlen_ex of the dequantised
+ * cache -- any number of query rows per sequence, uniform or ragged, contiguous or paged.  The argument blocks, the cache layout (one
+ * byte per element, strides in elements = bytes) and pfa_fa3_kv_quant are those of pfa_fa3_decode_q8 above.
+ *
+ * K and V tiles are loaded as bytes, converted to q's type in registers (exact) and written into the LDS tile images the 16-bit kernel
+ * builds by LDS-DMA; everything behind the images is the 16-bit kernel's one code path.  k_descale multiplies softmax_scale, v_descale
+ * the output once: with all descales 1 the result has the bits of pfa_fa3_prefill_ex (pfa_fa3_prefill_varlen_ex) on the converted
+ * cache.  Length and causal rules, paging, the O = 0 / LSE = -inf rule and the workgroups (from host shapes only: B * H *
+ * ceil(Sq / 256)) are the 16-bit call's: a captured graph stays valid while lengths, cu_seqlens_q, table, cache and the descales'
+ * CONTENTS change.  No workspace, no atomics.  `ext` may be NULL or carry window = 0: a window does not combine with the FP8 cache
+ * here, nor does the split over keys (pfa_fa3_prefill_split).  Rows at and past a sequence's length read as +0 and table entries at
+ * and past ceil(len_b / page_size) are never read (0x7f bytes there are harmless); NaN bytes below a length give NaN.
+ *
+ * Field rules, in the order their errors are reported: `a` NULL -> PFA_ERR_NULL, a->size wrong -> PFA_ERR_STRUCT_SIZE; the rules of
+ * pfa_fa3_kv_quant as listed above (through the cache alignment); ext->window > 0 -> PFA_ERR_FLAGS; then the unchanged rules of
+ * pfa_fa3_prefill_check_ex / pfa_fa3_prefill_varlen_check_ex, which these calls ask (a key mask -> PFA_ERR_FLAGS, as there).
+ */
+int pfa_fa3_prefill_q8_check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant);
+int pfa_fa3_prefill_q8(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream);
+/* As pfa_fa3_prefill_describe_ex: "fa3_prefill_..._kv8[_varlen][_paged]" into buf -> the 16-bit call's workgroups, or a pfa_status. */
+int pfa_fa3_prefill_q8_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, char* buf, size_t n);
+int pfa_fa3_prefill_varlen_q8_check(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant);
+int pfa_fa3_prefill_varlen_q8(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream);
+int pfa_fa3_prefill_varlen_q8_describe(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant,
+                                       char* buf, size_t n);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

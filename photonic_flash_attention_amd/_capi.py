@@ -259,6 +259,12 @@ def _prototypes():
         "pfa_fa3_decode_q8_describe": (i, [dec, ext, quant] + buf + ns),
         "pfa_kv_append_q8_check": (i, [app, quant]),
         "pfa_kv_append_q8": (i, [app, quant, vp]),
+        "pfa_fa3_prefill_q8_check": (i, [dec, ext, quant]),
+        "pfa_fa3_prefill_q8": (i, [dec, ext, quant, vp]),
+        "pfa_fa3_prefill_q8_describe": (i, [dec, ext, quant] + buf),
+        "pfa_fa3_prefill_varlen_q8_check": (i, [var, ext, quant]),
+        "pfa_fa3_prefill_varlen_q8": (i, [var, ext, quant, vp]),
+        "pfa_fa3_prefill_varlen_q8_describe": (i, [var, ext, quant] + buf),
     }
 
 
@@ -395,6 +401,16 @@ def make_kv_quant(**kw) -> PfaFa3KvQuant:
 def describe_decode_q8(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], quant: Optional[PfaFa3KvQuant]):
     """``describe_decode_ex`` of ``pfa_fa3_decode_q8``: "_kv8" marks a kernel over an FP8 cache; workgroups and splits are the 16-bit call's."""
     return _describe("pfa_fa3_decode_q8_describe", args, ext, quant, nsplit=True)
+
+
+def describe_prefill_q8(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], quant: Optional[PfaFa3KvQuant]):
+    """``describe_prefill_ex`` of ``pfa_fa3_prefill_q8``: "_kv8" marks a kernel over an FP8 cache; the workgroups are the 16-bit call's."""
+    return _describe("pfa_fa3_prefill_q8_describe", args, ext, quant)
+
+
+def describe_prefill_varlen_q8(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaFa3CacheExt], quant: Optional[PfaFa3KvQuant]):
+    """``describe_prefill_varlen_ex`` of ``pfa_fa3_prefill_varlen_q8``."""
+    return _describe("pfa_fa3_prefill_varlen_q8_describe", args, ext, quant)
 
 
 def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):

@@ -59,6 +59,8 @@
 
 #include <type_traits>
 
+#include "fp8_cvt.h"               // cvt_e4m3x8: the KV8 conversion, shared with fa3_prefill_kernel.h
+
 namespace pfa {
 namespace dec {
 
@@ -149,13 +151,6 @@ template <> struct DElem<_Float16> {
         return __builtin_bit_cast(v4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)p));
     }
 };
-
-// 8 e4m3fn bytes (element j in byte j) -> 8 elements of T, exactly
-template <typename T, typename V8> __device__ __forceinline__ V8 cvt_e4m3x8(uint32_t w0, uint32_t w1) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, true);
-    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, true);
-    return V8{(T)a[0], (T)a[1], (T)b[0], (T)b[1], (T)c[0], (T)c[1], (T)d[0], (T)d[1]};
-}
 
 // Per head dim: keys per wave tile, loads per lane, LDS image geometry.
 template <int D> struct Geo {

@@ -73,8 +73,33 @@
 //     no visible key in the split's range (an empty range, rows above the range under the causal cut, len_b < Sq) gets O = 0 and
 //     LSE = -inf from the epilogue below, and the merge skips such a part.
 // SPLIT = false compiles to the code and the kernel arguments the instantiation had.
+//
+// KV8 (pfa_fa3_prefill_q8 / pfa_fa3_prefill_varlen_q8; no WINDOW, no SPLIT; Prefill*Q8Params carry the descales): the cache holds OCP
+// e4m3fn bytes, one per element -- strides in elements = bytes, every stride a multiple of 16, 16-byte bases -- and an element stands for
+// e4m3(byte) * descale[b * ds_sb + kvh].  LDS-DMA cannot widen a byte, so the tiles are staged through registers, one tile ahead of the
+// LDS image and two ahead of the math.  What changes:
+//   - THE CONTRACT: the K and V images in LDS are, byte for byte, the images the 16-bit kernel builds from cache.to(T) (cvt_e4m3x8 is
+//     exact).  Everything behind the images -- fragments, V^T reads, MFMAs, masks, softmax, epilogue -- is the one code path;
+//   - a tile of K (and of V) is 64 * D bytes: at D = 128 every lane loads 16 bytes of K and 16 of V (key tid / 8, bytes 16 (tid % 8) ..),
+//     at D = 64 one load, waves 0-3 of K and waves 4-7 of V (key (tid % 256) / 4).  A load is two 8-element chunks 2c, 2c + 1 of one key,
+//     which tile_off puts 16 bytes apart in one LDS row: two ds_write_b128 after the conversion.  8 (4) staging VGPRs;
+//   - the loads go through descriptors that end at the tile's last valid key, difference (3) above with byte counts: a row at or past
+//     len_b reads as 0x00 = +0.0 and a NaN byte behind a length never reaches LDS;
+//   - step j: convert the held tile j + 1 into buffer BUF ^ 1 (its last readers finished in front of the barrier that ended step j - 1),
+//     issue the loads of tile j + 2 into the freed registers, compute tile j from BUF, lgkmcnt(0), barrier -- so the reads of a tile
+//     come after a barrier that follows its writers' lgkmcnt(0).  There is no vmcnt wait at the barrier: the compiler places the one
+//     the conversion needs, a whole tile's math behind the loads.  A wave that computes no tile (VARLEN idle, above the causal cut)
+//     still stages its share and meets every barrier;
+//   - PAGED: load8 is dma_tile's walk (one scalar entry per tile, fetched when the previous tile's loads were issued, clamped), called
+//     for j = 0, 1, ... < nt in order; that it runs two tiles ahead of the math changes no guard: the entry of tile j + 1 is fetched only
+//     if j + 1 < nt;
+//   - the descales are two scalar loads in the prologue: k_descale multiplies scale_log2 before thr, mc and the LSE are derived from it,
+//     v_descale multiplies inv once in the epilogue.  Both are exact at 1: the call then returns the bits of the 16-bit call on the
+//     converted cache.
+// KV8 = false compiles to the code and the kernel arguments the instantiation had.
 #pragma once
 #include "fa3_fwd_kernel.h"
+#include "fp8_cvt.h"
 
 namespace pfa {
 
@@ -116,16 +141,32 @@ struct PrefillSplitParams : PrefillParams {
     float* part_o;
     float* part_lse;
 };
-template <bool VARLEN, bool WINDOW = false, bool SPLIT = false> struct PrefillParamsOf { typedef PrefillParams type; };
+// KV8: fp32 descales, k_descale[b * ds_sb + kvh] (ds_sb = 0: one row for every batch)
+struct PrefillQ8Params : PrefillParams {
+    const float* k_descale;
+    const float* v_descale;
+    int64_t ds_sb;
+};
+struct PrefillVarlenQ8Params : PrefillVarlenParams {
+    const float* k_descale;
+    const float* v_descale;
+    int64_t ds_sb;
+};
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false> struct PrefillParamsOf { typedef PrefillParams type; };
 template <> struct PrefillParamsOf<true, false> { typedef PrefillVarlenParams type; };
 template <> struct PrefillParamsOf<false, true> { typedef PrefillWinParams type; };
 template <> struct PrefillParamsOf<true, true> { typedef PrefillVarlenWinParams type; };
 template <> struct PrefillParamsOf<false, false, true> { typedef PrefillSplitParams type; };
+template <> struct PrefillParamsOf<false, false, false, true> { typedef PrefillQ8Params type; };
+template <> struct PrefillParamsOf<true, false, false, true> { typedef PrefillVarlenQ8Params type; };
 
 typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
+typedef const __attribute__((address_space(4))) float* prefill_f32_ptr;
 
-template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false, bool SPLIT = false>
-__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW, SPLIT>::type p) {
+template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false, bool SPLIT = false,
+          bool KV8 = false>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8>::type p) {
+    static_assert(!KV8 || (!WINDOW && !SPLIT), "the FP8 cache takes neither a window nor a split over keys");
     static_assert(CAUSAL || !WINDOW, "the window is cut from the causal diagonal");
     static_assert(!SPLIT || (!VARLEN && !WINDOW), "the split over keys is for the uniform, window-less call");
     static_assert(!SPLIT || (SPLITP && sizeof(OT) == 4), "the partial results are fp32, P carried as hi + lo");
@@ -139,6 +180,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     constexpr int TILE_BYTES = BLOCK_N * D * 2;
     constexpr int BUF_BYTES = 2 * TILE_BYTES; // K image + V image
     constexpr int HALF_TILE = TILE_BYTES / 2; // 32 keys
+    constexpr int EB = KV8 ? 1 : 2;           // bytes per cache element
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     lds_char* const smem_l = (lds_char*)smem;   // [buf][K|V][TILE_BYTES]
@@ -209,8 +251,14 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     const int kvh = hh / p.kv_group;
     const T* __restrict__ qp = (const T*)p.q + (VARLEN ? (int64_t)row0 * p.q_ss : (int64_t)b * p.q_sb) + (int64_t)hh * p.q_sh;
     // contiguous: this batch's and head's slab; paged: the head's offset inside every page (the page base is added per tile)
-    const char* kp = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * 2;
-    const char* vp = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * 2;
+    const char* kp = (const char*)p.k + ((PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)kvh * p.k_sh) * EB;
+    const char* vp = (const char*)p.v + ((PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)kvh * p.v_sh) * EB;
+    // KV8: the block's two descales (scalar loads), used under if constexpr (KV8) only so that the other kernels keep their expressions
+    float k_mul = 1.f, v_mul = 1.f;
+    if constexpr (KV8) {
+        k_mul = ((prefill_f32_ptr)(uintptr_t)p.k_descale)[(int64_t)b * p.ds_sb + kvh];
+        v_mul = ((prefill_f32_ptr)(uintptr_t)p.v_descale)[(int64_t)b * p.ds_sb + kvh];
+    }
 
     // ---- Q fragments: B operand of S^T = K Q^T, lane (r,h) holds Q[my_q][16 ks + 8 h .. +7] -----------
     v8 qf[KS];
@@ -292,6 +340,74 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
         }
     };
 
+    // ---- KV8: K/V staging through registers (see the header).  st8 holds the tile that is converted next ----
+    constexpr int NLD8 = D == 128 ? 2 : 1;               // 16-byte loads per lane and tile: K and V, or (D = 64) one of the two
+    u32x4 st8[NLD8];
+    uint32_t src8[NLD8] = {};                            // byte offset of this lane's 16 bytes from the tile's first key row
+    uint32_t dst8 = 0;                                   // byte offset of chunk 2c in buffer 0 (chunk 2c + 1: dst8 ^ 16), V image included
+    const bool stage_v = D == 64 && wave >= NW / 2;      // D = 64: this wave stages V (wave-uniform)
+    if constexpr (KV8) {
+        constexpr int LPK = D / 16;                      // lanes (16-byte loads) per key row
+        const int t8 = D == 128 ? tid : (tid & 255);
+        const int key8 = t8 / LPK, c8 = t8 % LPK;
+        if constexpr (D == 128) {
+            src8[0] = (uint32_t)(key8 * (int)p.k_ss + 16 * c8);
+            src8[NLD8 - 1] = (uint32_t)(key8 * (int)p.v_ss + 16 * c8);
+        } else {
+            src8[0] = (uint32_t)(key8 * (int)(stage_v ? p.v_ss : p.k_ss) + 16 * c8);
+        }
+        dst8 = tile_off<D>(key8, 2 * c8) + (stage_v ? TILE_BYTES : 0);
+    }
+    auto load8 = [&](int j) {
+        const int nk = min(BLOCK_N, kv_len - j * BLOCK_N);
+        int64_t koff, voff;                  // byte offsets of the tile's first key row from kp / vp
+        if constexpr (PAGED) {
+            const int pg = min(max(pg_next, 0), p.num_pages - 1);     // device data: never an address outside the pool
+            koff = (int64_t)pg * p.k_sb + (int64_t)pg_tok * p.k_ss;
+            voff = (int64_t)pg * p.v_sb + (int64_t)pg_tok * p.v_ss;
+        } else {
+            koff = (int64_t)j * BLOCK_N * p.k_ss;
+            voff = (int64_t)j * BLOCK_N * p.v_ss;
+        }
+        // (3) as dma_tile: the descriptors end at the tile's last valid key, rows at and past len_b read as zero bytes
+        if constexpr (D == 128) {
+            const srd_t ksrd = __builtin_amdgcn_make_buffer_rsrc((void*)(kp + koff), 0, (int)((int64_t)(nk - 1) * p.k_ss + D), 0x00020000);
+            const srd_t vsrd = __builtin_amdgcn_make_buffer_rsrc((void*)(vp + voff), 0, (int)((int64_t)(nk - 1) * p.v_ss + D), 0x00020000);
+            st8[0] = __builtin_amdgcn_raw_buffer_load_b128(ksrd, (int)src8[0], 0, 0);
+            st8[NLD8 - 1] = __builtin_amdgcn_raw_buffer_load_b128(vsrd, (int)src8[NLD8 - 1], 0, 0);
+        } else {
+            const char* base = stage_v ? vp + voff : kp + koff;
+            const int64_t ss = stage_v ? p.v_ss : p.k_ss;
+            const srd_t srd = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)((int64_t)(nk - 1) * ss + D), 0x00020000);
+            st8[0] = __builtin_amdgcn_raw_buffer_load_b128(srd, (int)src8[0], 0, 0);
+        }
+        if constexpr (PAGED) {
+            pg_tok += BLOCK_N;
+            if (pg_tok == p.page_size) {
+                pg_tok = 0;
+                ++pg_idx;
+                if (j + 1 < nt) pg_next = table[pg_idx];
+            }
+        }
+    };
+    // the held tile into buffer BUF as the 16-bit images: two chunks per load
+    auto write8 = [&](auto bufc) {
+        constexpr int BUF = decltype(bufc)::value;
+        lds_char* const img = smem_l + BUF * BUF_BYTES;
+#pragma unroll
+        for (int i = 0; i < NLD8; ++i) {
+            *(lds_v8*)(img + i * TILE_BYTES + dst8) = cvt_e4m3x8<T, v8>(st8[i][0], st8[i][1]);
+            *(lds_v8*)(img + i * TILE_BYTES + (dst8 ^ 16u)) = cvt_e4m3x8<T, v8>(st8[i][2], st8[i][3]);
+        }
+    };
+    // this wave's image writes are done, then everybody's; the two empty statements keep LDS accesses on their side of the barrier
+    auto barrier8 = [&]() {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+
     // ---- per-lane LDS read offsets, loop invariant (see fa3_fwd_kernel) ----------
     uint32_t koff[KS];
 #pragma unroll
@@ -321,7 +437,7 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
         for (int e = 0; e < 16; ++e) o[i][e] = 0.f;
     float m_run = -1e30f;   // reference max of the exponentials, raw score units
     float l_run = 0.f;      // this lane's share of the row sum
-    const float c = p.scale_log2;
+    const float c = KV8 ? p.scale_log2 * k_mul : p.scale_log2;   // KV8: raw scores are over the undescaled bytes
     const float thr = 8.0f / c;                 // deferred max: raw-score headroom (2^8 in the exponent) before O is rescaled
     float m_thr = -1e30f, mc = -1e30f * c;      // m_run + thr and m_run * c, updated with m_run
 
@@ -431,19 +547,36 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
 
     auto step = [&](auto bufc, int j) {
         constexpr int BUF = decltype(bufc)::value;
-        if (j + 1 < nt) dma_tile(IC<BUF ^ 1>{}, j + 1);   // lands in the other buffer under this tile's math
-        if (j * BLOCK_N < wave_kv_end && (!WINDOW || j * BLOCK_N + BLOCK_N > wave_lo)) compute_tile(bufc, j * BLOCK_N);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed ...
-        __builtin_amdgcn_s_waitcnt(0xC07F);               // (lgkmcnt(0): this wave's LDS reads are done)
-        __builtin_amdgcn_s_barrier();                     // ... and so have everybody else's
+        if constexpr (KV8) {
+            if (j + 1 < nt) write8(IC<BUF ^ 1>{});        // the held tile j + 1: its buffer's readers finished before the last barrier
+            if (j + 2 < nt) load8(j + 2);                 // into the freed registers, under this tile's math and the next conversion
+            if (j * BLOCK_N < wave_kv_end) compute_tile(bufc, j * BLOCK_N);
+            barrier8();
+        } else {
+            if (j + 1 < nt) dma_tile(IC<BUF ^ 1>{}, j + 1);   // lands in the other buffer under this tile's math
+            if (j * BLOCK_N < wave_kv_end && (!WINDOW || j * BLOCK_N + BLOCK_N > wave_lo)) compute_tile(bufc, j * BLOCK_N);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed ...
+            __builtin_amdgcn_s_waitcnt(0xC07F);               // (lgkmcnt(0): this wave's LDS reads are done)
+            __builtin_amdgcn_s_barrier();                     // ... and so have everybody else's
+        }
     };
 
-    if (j_lo < nt) dma_tile(IC<0>{}, j_lo);
+    if constexpr (KV8) {
+        if (j_lo < nt) load8(j_lo);
+    } else {
+        if (j_lo < nt) dma_tile(IC<0>{}, j_lo);
+    }
     // Q must have LANDED before the loop (see fa3_fwd_kernel: else its vmcnt waits drain the K/V prefetch every iteration)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    if constexpr (KV8) {
+        if (j_lo < nt) write8(IC<0>{});
+        if (j_lo + 1 < nt) load8(j_lo + 1);
+        barrier8();
+    } else {
+        __syncthreads();
+    }
     for (int j = j_lo; j < nt; j += 2) {
         step(IC<0>{}, j);
         if (j + 1 < nt) step(IC<1>{}, j + 1);
@@ -451,7 +584,8 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
 
     // ---- epilogue: normalise once; a row with no visible key -> zeros, LSE = -inf ------------
     const float l_tot = row_pair_sum(l_run);
-    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+    float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+    if constexpr (KV8) inv *= v_mul;
     // VARLEN: the batch's rows start at packed row row0, and the row bound of every store is the batch's own count -- the next
     // packed row is another batch's
     const int64_t o_batch = VARLEN ? (int64_t)row0 * p.o_ss : (int64_t)b * p.o_sb;

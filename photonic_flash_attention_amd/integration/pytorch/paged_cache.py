@@ -31,6 +31,11 @@ be shared between sequences) keeps the pools in FP8: half the bytes per key, twi
 16-bit rows and quantise them (``ops.quantize_kv``'s rule; ``write_step`` runs the quantising HIP append), ``decode`` runs the FP8 decode
 kernel, ``gather`` returns the FP8 pages.  Not built for an FP8 cache, and refused with ``ValueError``: ``prefill``, ``prefill_varlen``,
 the rotary form of ``write_step``, and ``decode``'s ``window`` / ``tree_mask`` / ``shared_prefix``.
+
+The kernels behind ``prefill`` / ``prefill_varlen`` do read FP8 pages (``ops.fa3_prefill_cache`` / ``ops.fa3_prefill_varlen`` with
+``k_descale=, v_descale=``).  The two methods still refuse an FP8 cache because tests pin that refusal and its text; flipping them is
+the follow-up that edits those tests.  Until then ``operands(slots)`` hands out what the calls take:
+``k, v, kw = cache.operands(slots); ops.fa3_prefill_cache(q, k, v, **kw)`` is the FP8 prefill over this cache's pages.
 """
 
 from __future__ import annotations
@@ -515,6 +520,19 @@ class PagedKVCache:
             return self._table[slots[0]:slots[-1] + 1], self._lens[slots[0]:slots[-1] + 1]     # views: capturable
         idx = torch.tensor(slots, dtype=torch.int64).to(self.device)
         return self._table.index_select(0, idx), self._lens.index_select(0, idx)
+
+    def operands(self, slots: Slots = None) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+        """``(k_cache, v_cache, kw)`` as the calls of ``ops`` over a paged cache take them: the pools as ``[num_pages, Hkv, page_size,
+        D]``-shaped views and ``kw = dict(cache_seqlens=, block_table=)``, plus ``k_descale=, v_descale=`` for an FP8 cache.  Slots are
+        chosen and captured as in ``decode``: None and a run of consecutive slots give views of the cache's own table and lengths (a
+        captured call keeps seeing them), any other list a copy of its rows.  ``ops.fa3_prefill_cache(q, k, v, **kw)`` and
+        ``ops.fa3_prefill_varlen(q, k, v, cu_seqlens_q=..., max_seqlen_q=..., **kw)`` are then the prefill over this cache's pages,
+        FP8 included.  Works on CPU tensors (the calls themselves need the device)."""
+        table, lens = self._rows(slots)
+        kw = dict(cache_seqlens=lens, block_table=table)
+        if self._fp8:
+            kw.update(k_descale=self._kd, v_descale=self._vd)
+        return self._k.transpose(1, 2), self._v.transpose(1, 2), kw
 
     def _cu(self, q_lens, cu_seqlens_q, max_seqlen_q, n_slots: int, rows: int, what: str):
         """A ragged step's ``(cu_seqlens_q, max_seqlen_q)``: the caller's device tensor and bound, or the prefix sums of the host

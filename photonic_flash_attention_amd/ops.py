@@ -1178,7 +1178,7 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  ``key_splits`` (the C value, ``pfa_fa3_prefill`` only)
     launches ``pfa_fa3_prefill_split`` instead, which takes no extension; ``tree`` (``pfa_fa3_decode`` only) launches
     ``pfa_fa3_decode_tree``, which takes it behind the extension; ``quant`` (``pfa_fa3_decode`` over an FP8 cache, with the caller's
-    ``descales`` for the append) launches ``pfa_fa3_decode_q8``.  -> lse or None."""
+    ``descales`` for the append) launches ``pfa_fa3_decode_q8``; with the prefill entries it launches ``{entry}_q8``.  -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
@@ -1195,7 +1195,7 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     if key_splits is not None:
         st = _capi.load().pfa_fa3_prefill_split(C.byref(a), key_splits, C.c_void_p(stream.cuda_stream))
     elif quant is not None:
-        st = _capi.load().pfa_fa3_decode_q8(C.byref(a), None if ext is None else C.byref(ext), C.byref(quant), C.c_void_p(stream.cuda_stream))
+        st = getattr(_capi.load(), entry + "_q8")(C.byref(a), None if ext is None else C.byref(ext), C.byref(quant), C.c_void_p(stream.cuda_stream))
     elif tree is not None:
         st = _capi.load().pfa_fa3_decode_tree(C.byref(a), None if ext is None else C.byref(ext), C.byref(tree), C.c_void_p(stream.cuda_stream))
     else:
@@ -1511,6 +1511,24 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     return out, lse
 
 
+def _fp8_prefill_quant(entry: str, q, k_cache, v_cache, k_descale, v_descale, B, refused):
+    """What ``fa3_prefill_cache`` and ``fa3_prefill_varlen`` do first about an FP8 cache: -> ``(fp8, quant)``, the ``pfa_fa3_kv_quant`` block
+    or None for 16-bit caches (which refuse descales).  ``refused``: (name, given) of the arguments the FP8 kernels are not built for;
+    a given one raises ``ValueError`` naming it, before anything is enqueued."""
+    fp8 = isinstance(k_cache, torch.Tensor) and isinstance(v_cache, torch.Tensor) and (k_cache.dtype == FP8 or v_cache.dtype == FP8)
+    if not fp8:
+        if k_descale is not None or v_descale is not None:
+            raise ValueError("k_descale / v_descale go with torch.float8_e4m3fn caches only")
+        return False, None
+    for name, given in refused:
+        if given:
+            raise ValueError(f"{name} is not supported with an FP8 (torch.float8_e4m3fn) KV cache: the FP8 prefill takes cache_seqlens, "
+                             "block_table, causal and k_new / v_new only")
+    if k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("k_cache, v_cache must be 4-D ([B,Hkv,Smax,D])")
+    return True, _kv_quant_arg(entry, k_cache, v_cache, k_descale, v_descale, B, k_cache.shape[1], q.device)
+
+
 def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
                       causal: bool = True, softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
                       return_lse: bool = False, out: Optional[torch.Tensor] = None,
@@ -1518,7 +1536,8 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                       rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                       pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
-                      key_splits=None, prefix_key_splits=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      key_splits=None, prefix_key_splits=None, k_descale: Optional[torch.Tensor] = None,
+                      v_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
@@ -1563,7 +1582,23 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     this call over one sequence of ``B * Sq`` rows, H * ceil(B * Sq / 256) workgroups; ``prefix_key_splits`` (``None``, ``"auto"`` or
     1 .. 8; only with ``shared_prefix``) is that pass's ``key_splits``, as in ``fa3_decode``.  ``key_splits`` itself is refused with
     ``shared_prefix``: the own-keys pass is short.  Measured (``profiles/shared_prefix.md``, ``profiles/prefill_split.md``): the 512-row
-    speculative step through ``fa3_decode``, 1.09 x shared pages, 2.3 x own copies, without a split of the prefix pass."""
+    speculative step through ``fa3_decode``, 1.09 x shared pages, 2.3 x own copies, without a split of the prefix pass.
+
+    FP8 cache (``pfa_fa3_prefill_q8``): k_cache / v_cache of ``torch.float8_e4m3fn`` (contiguous or pools), with ``k_descale=, v_descale=``
+    -- contiguous fp32 DEVICE tensors ``[Hkv]`` or ``[B, Hkv]``, required then and refused with 16-bit caches -- as in ``fa3_decode``.  A
+    cache element stands for ``e4m3(byte) * descale[b, hk]``; the bytes are converted to q's dtype on their way into the same LDS tile
+    images, k_descale multiplies the softmax scale and v_descale the output once, so the call returns the attention over
+    ``dequantize_kv`` of the cache, and with all descales 1 the bits of the 16-bit call on ``k_cache.to(q.dtype)``.  ``cache_seqlens``,
+    ``block_table``, ``causal``, ``out``, ``out_dtype``, ``return_lse`` work as above; ``k_new=, v_new=`` (16-bit rows) go through the
+    quantising ``kv_append`` first.  Still one launch from host shapes: a captured step replays while lengths, table, cache and the
+    descales' contents change.  ``window``, ``shared_prefix``, ``key_splits`` / ``prefix_key_splits`` and the rotary arguments are not
+    built for an FP8 cache and raise ``ValueError`` naming the argument before anything is enqueued; bytes at and past a length are
+    never read into a result (NaN bytes there are harmless).  Over a ``PagedKVCache``:
+    ``k, v, kw = cache.operands(slots); fa3_prefill_cache(q, k, v, **kw)``."""
+    fp8, quant = _fp8_prefill_quant("pfa_fa3_prefill", q, k_cache, v_cache, k_descale, v_descale, q.shape[0] if q.dim() else 0, (
+        ("window", window is not None), ("shared_prefix", shared_prefix is not None), ("key_splits", key_splits is not None),
+        ("prefix_key_splits", prefix_key_splits is not None),
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None)))
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     splits = _key_splits_arg("key_splits", key_splits)
@@ -1579,7 +1614,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                                    key_mask=None, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
                                    return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary,
                                    prefix_key_splits=prefix_key_splits)
-    a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table)
+    a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table, fp8)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
     if splits is not None:
@@ -1589,8 +1624,8 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
             keep.append(ws)
     lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, key_splits=splits,
-                             max_seqlen_q=q.shape[2])
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, key_splits=splits, quant=quant,
+                             descales=(k_descale, v_descale) if fp8 else None, max_seqlen_q=q.shape[2])
     return out, lse
 
 
@@ -1600,7 +1635,8 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                        block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                        k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                        rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-                       pos_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       pos_offsets: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
+                       v_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen_ex``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
     verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
@@ -1628,7 +1664,17 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
 
     ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
     need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
-    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified."""
+    the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified.
+
+    FP8 cache (``pfa_fa3_prefill_varlen_q8``): ``torch.float8_e4m3fn`` caches or pools with ``k_descale=, v_descale=`` (contiguous fp32
+    DEVICE tensors ``[Hkv]`` or ``[B, Hkv]``; refused with 16-bit caches), exactly as in ``fa3_prefill_cache``: the attention over
+    ``dequantize_kv`` of the cache, the bits of the 16-bit call at descales 1, and of per-sequence ``fa3_prefill_cache`` calls over
+    the FP8 cache at any descales.  ``k_new=, v_new=`` go through the quantising ``kv_append``; ``window`` and the rotary arguments raise
+    ``ValueError`` naming the argument before anything is enqueued."""
+    B_cu = cu_seqlens_q.numel() - 1 if isinstance(cu_seqlens_q, torch.Tensor) else 0
+    fp8, quant = _fp8_prefill_quant("pfa_fa3_prefill_varlen", q, k_cache, v_cache, k_descale, v_descale, B_cu, (
+        ("window", window is not None),
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None)))
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
@@ -1639,7 +1685,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         raise ValueError(f"cu_seqlens_q must be [B + 1], got {tuple(cu_seqlens_q.shape)}")
     total_q, H, D = q.shape
     B = cu_seqlens_q.numel() - 1
-    Hkv, Smax, page_size, num_pages, odt = _cache_operands("pfa_fa3_prefill_varlen", q, B, H, D, k_cache, v_cache, out_dtype, block_table)
+    Hkv, Smax, page_size, num_pages, odt = _cache_operands("pfa_fa3_prefill_varlen", q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8)
     if not cu_seqlens_q.is_cuda or cu_seqlens_q.device != q.device:
         raise ValueError("cu_seqlens_q must live on the operands' device (there is no CPU path)")
     if not cu_seqlens_q.is_contiguous():
@@ -1664,8 +1710,8 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep, B)
     lse = _finish_cache_call("pfa_fa3_prefill_varlen", a, ext, q, (H, total_q) if return_lse else None, keep,
-                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary,
-                             cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
+                             (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, quant=quant,
+                             descales=(k_descale, v_descale) if fp8 else None, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
     return out, lse
 
 
