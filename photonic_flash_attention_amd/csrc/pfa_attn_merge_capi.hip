@@ -50,27 +50,29 @@ int check(const pfa_attn_merge_args* a) {
     return PFA_OK;
 }
 
+using MergeFn = pfa::KernelFn<pfa::AttnMergeParams>;
+
 template <typename TP, typename TO>
-const void* kernel_for_parts(int n) {
+MergeFn kernel_for_parts(int n) {
     switch (n) {
-        case 2: return (const void*)&pfa::attn_merge_kernel<TP, TO, 2>;
-        case 3: return (const void*)&pfa::attn_merge_kernel<TP, TO, 3>;
-        case 4: return (const void*)&pfa::attn_merge_kernel<TP, TO, 4>;
-        case 5: return (const void*)&pfa::attn_merge_kernel<TP, TO, 5>;
-        case 6: return (const void*)&pfa::attn_merge_kernel<TP, TO, 6>;
-        case 7: return (const void*)&pfa::attn_merge_kernel<TP, TO, 7>;
-        default: return (const void*)&pfa::attn_merge_kernel<TP, TO, 8>;
+        case 2: return &pfa::attn_merge_kernel<TP, TO, 2>;
+        case 3: return &pfa::attn_merge_kernel<TP, TO, 3>;
+        case 4: return &pfa::attn_merge_kernel<TP, TO, 4>;
+        case 5: return &pfa::attn_merge_kernel<TP, TO, 5>;
+        case 6: return &pfa::attn_merge_kernel<TP, TO, 6>;
+        case 7: return &pfa::attn_merge_kernel<TP, TO, 7>;
+        default: return &pfa::attn_merge_kernel<TP, TO, 8>;
     }
 }
 
 template <typename TP>
-const void* kernel_for_out(int dtype_out, int n) {
+MergeFn kernel_for_out(int dtype_out, int n) {
     return dtype_out == PFA_DTYPE_FP32 ? kernel_for_parts<TP, float>(n)
          : dtype_out == PFA_DTYPE_BF16 ? kernel_for_parts<TP, __bf16>(n) : kernel_for_parts<TP, _Float16>(n);
 }
 
 // the instantiation of a checked call: 16-bit parts keep their type or widen to fp32, fp32 parts go to any of the three
-const void* kernel(const pfa_attn_merge_args* a) {
+MergeFn kernel(const pfa_attn_merge_args* a) {
     if (a->dtype_part == PFA_DTYPE_FP32) return kernel_for_out<float>(a->dtype_out, a->n_parts);
     if (a->dtype_part == PFA_DTYPE_BF16)
         return a->dtype_out == PFA_DTYPE_FP32 ? kernel_for_parts<__bf16, float>(a->n_parts) : kernel_for_parts<__bf16, __bf16>(a->n_parts);

@@ -105,8 +105,8 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream) {
         pfa::fill_bwd_strides(p, a);
         p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk; p.causal = a->causal != 0;
         p.scale = a->softmax_scale; p.drop_scale = a->drop_scale;
-        const void* f0 = pfa::dispatch_dim(a->D, [](auto d) { return (const void*)&pfa::fa3_bwd_f32_kernel<d.value, 0>; });
-        const void* f1 = pfa::dispatch_dim(a->D, [](auto d) { return (const void*)&pfa::fa3_bwd_f32_kernel<d.value, 1>; });
+        const auto f0 = pfa::dispatch_dim(a->D, [](auto d) -> pfa::KernelFn<pfa::F32BwdParams> { return &pfa::fa3_bwd_f32_kernel<d.value, 0>; });
+        const auto f1 = pfa::dispatch_dim(a->D, [](auto d) -> pfa::KernelFn<pfa::F32BwdParams> { return &pfa::fa3_bwd_f32_kernel<d.value, 1>; });
         const size_t lds = pfa::dispatch_dim(a->D, [](auto d) { return pfa::f32_bwd_lds_bytes<d.value>(); });
         const pfa::DeviceScope dev(a->device_id);
         if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
@@ -136,16 +136,16 @@ int pfa_fa3_bwd(const pfa_fa3_bwd_args* a, void* stream) {
     const bool use_words = mw.bytes() > 0 && a->mask_workspace && a->mask_workspace_bytes >= mw.bytes();
 
     const bool causal = a->causal != 0, g32 = a->dtype_grad == PFA_DTYPE_FP32, kmask = p.mask != nullptr;     // (not for key-only masks)
-    const void *kdq = nullptr, *kdkdv = nullptr;
+    pfa::KernelFn<pfa::BwdParams> kdq = nullptr, kdkdv = nullptr;
     pfa::dispatch_elem_dim(a->dtype, a->D, [&](auto t) {
         using T = typename decltype(t)::type;
         constexpr int D = decltype(t)::D;
-        return pfa::dispatch_bools([&](auto c, auto k) {
-            constexpr bool C = decltype(c)::value, K = decltype(k)::value;
-            kdq = pfa::dispatch_bools([](auto o32) { return (const void*)&pfa::fa3_bwd_dq_kernel<T, D, C, K, pfa::out_t<decltype(o32)::value, T>>; }, g32);
-            kdkdv = pfa::dispatch_bools([](auto o32) { return (const void*)&pfa::fa3_bwd_dkdv_kernel<T, D, C, K, pfa::out_t<decltype(o32)::value, T>>; }, g32);
+        return pfa::dispatch_bools([&](auto c, auto k, auto o32) {
+            using OT = pfa::out_t<decltype(o32)::value, T>;
+            kdq = &pfa::fa3_bwd_dq_kernel<T, D, decltype(c)::value, decltype(k)::value, OT>;
+            kdkdv = &pfa::fa3_bwd_dkdv_kernel<T, D, decltype(c)::value, decltype(k)::value, OT>;
             return 0;
-        }, causal, kmask);
+        }, causal, kmask, g32);
     });
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;

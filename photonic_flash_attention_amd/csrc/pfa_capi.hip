@@ -15,14 +15,14 @@
 #include "pfa_mask_host.h"
 #include "pfa_p4.h"
 
-namespace pfa { const void* w4_kernel(int dtype, bool causal, bool out32); }   // pfa_w4.hip
+namespace pfa { KernelFn<FwdParams> w4_kernel(int dtype, bool causal, bool out32); }   // pfa_w4.hip
 
 namespace {
 
 thread_local int g_last_hip_error = 0;
 
 struct Variant {
-    const void* fn;
+    pfa::KernelFn<pfa::FwdParams> fn;
     char name[96];
     int lds_bytes;
     bool grid3 = false;    // 4-wave kernel: (head-in-XCD-group, Q block, group) arrive as blockIdx.x/y/z -- no divisions in its prologue
@@ -43,8 +43,8 @@ Variant w8_variant(const pfa_fa3_args* a, bool causal, bool split, bool kmask, b
     Variant v;
     v.fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
         using T = typename decltype(t)::type;
-        return pfa::dispatch_bools([](auto c, auto s, auto k, auto o32) {
-            return (const void*)&pfa::fa3_fwd_kernel<T, decltype(t)::D, c.value, s.value, k.value, pfa::out_t<o32.value, T>>;
+        return pfa::dispatch_bools([](auto c, auto s, auto k, auto o32) -> pfa::KernelFn<pfa::FwdParams> {
+            return &pfa::fa3_fwd_kernel<T, decltype(t)::D, c.value, s.value, k.value, pfa::out_t<o32.value, T>>;
         }, causal, split, kmask, out32);
     });
     snprintf(v.name, sizeof(v.name), "fa3_fwd_%s_d%d_%s%s%s_%s_v%d", elem_name(a), a->D, causal ? "causal" : "full", split ? "_splitp" : "",
@@ -72,7 +72,7 @@ Variant p4_variant(const pfa_fa3_args* a, bool causal) {
 // 4 waves x 64 rows (fa3_fwd_w4_kernel.h): D = 128, single P, no element mask
 Variant w4_variant(const pfa_fa3_args* a, bool causal, bool out32) {
     Variant v;
-    v.fn = pfa::w4_kernel(a->dtype_in == PFA_DTYPE_BF16 ? 0 : 1, causal, out32);
+    v.fn = pfa::w4_kernel(a->dtype_in, causal, out32);
     snprintf(v.name, sizeof(v.name), "fa3_fwd_w4_%s_d128_%s_%s", elem_name(a), causal ? "causal" : "full", out32 ? "o32" : "o16");
     v.grid3 = true;
     v.lds_bytes = 8 * pfa::BLOCK_N * 128 * 2;      // K ring 2 + V ring 2 tiles, then the Q block's 64-KiB landing zone
@@ -188,7 +188,7 @@ int launch_f32(const pfa_fa3_args* a, void* stream) {
     p.scale = a->softmax_scale;
     p.drop_mask = a->drop_mask;
     p.drop_scale = a->drop_scale;
-    const void* fn = pfa::dispatch_dim(a->D, [](auto d) { return (const void*)&pfa::fa3_fwd_f32_kernel<d.value>; });
+    const auto fn = pfa::dispatch_dim(a->D, [](auto d) -> pfa::KernelFn<pfa::F32Params> { return &pfa::fa3_fwd_f32_kernel<d.value>; });
     const int lds = pfa::dispatch_dim(a->D, [](auto d) { return pfa::f32_lds_bytes<d.value>(); });
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
@@ -336,10 +336,10 @@ int pfa_fa3_weights(const pfa_fa3_args* a, void* w, int32_t w_dtype, int64_t w_s
     const pfa::MaskWords mb = mask_words(a);          // as in pfa_fa3_fwd: the mask as words when the caller gave workspace
     const bool use_mbits = take_mask_words(p, mb, a);
     const bool causal = a->causal != 0, kmask = p.mask != nullptr, w32 = w_dtype == PFA_DTYPE_FP32;
-    const void* fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
+    const auto fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
         using T = typename decltype(t)::type;
-        return pfa::dispatch_bools([](auto c, auto k, auto o32) {
-            return (const void*)&pfa::fa3_weights_kernel<T, decltype(t)::D, c.value, k.value, pfa::out_t<o32.value, T>>;
+        return pfa::dispatch_bools([](auto c, auto k, auto o32) -> pfa::KernelFn<pfa::WeightsParams> {
+            return &pfa::fa3_weights_kernel<T, decltype(t)::D, c.value, k.value, pfa::out_t<o32.value, T>>;
         }, causal, kmask, w32);
     });
     const pfa::DeviceScope dev(a->device_id);

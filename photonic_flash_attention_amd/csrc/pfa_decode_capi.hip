@@ -1,53 +1,15 @@
-// pfa_decode_capi.hip -- C ABI of the split-KV decode path (include/pfa_hip.h, ABI v9): validation, the split rule, launches.
+// pfa_decode_capi.hip -- C ABI of the split-KV decode path (include/pfa_hip.h, ABI v9): validation and the calls; the split rule, the
+// kernel table, the parameter fill and the launches are pfa_decode_host.h's, which the FP8 unit shares.
 // One body per entry point: the *_tree calls; the *_ex calls are those with no tree, the plain calls those with no extension either.
 // No allocation, no synchronisation, no process-wide state.
-#include "pfa_hip.h"
-
-#include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdio.h>
-#include <string.h>
 
-#include "fa3_decode_kernel.h"
-#include "pfa_host.h"
+#include "pfa_decode_host.h"
 
 namespace {
 
-constexpr int kTargetWorkgroups = 512;   // two 4-wave workgroups per CU of the 256-CU part
-constexpr int kMinSplitKeys = 256;       // every split covers at least four 64-key tiles
-constexpr int kMaxSplits = 128;
-
-struct Plan {
-    int G = 1, nrb = 0, nsplit = 1;
-    int64_t items = 0;           // workgroups of the main kernel
-    size_t ws_bytes = 0;
-};
-
-// Everything here depends on shapes and the host window only (never on cache_seqlens / key_mask / the block table or the page size), so a
-// captured graph stays valid while they change, and a paged call splits exactly as the contiguous call of the same (B, H, Hkv, Sq, Smax,
-// D, window).  window (0: none, else 1 .. Smax): the keys a batch's splits divide are at most window + Sq - 1 and the up to 63 below
-// them in the first tile, so that span, rounded to tiles, stands where Smax does -- a 4096-key window over a 128K cache is not cut
-// into 128 splits of a few tiles.
-Plan plan(const pfa_fa3_decode_args* a, int window) {
-    Plan pl;
-    pl.G = a->H / a->Hkv;
-    pl.nrb = (int)(((int64_t)a->Sq * pl.G + pfa::dec::ROWS - 1) / pfa::dec::ROWS);
-    const int64_t base = (int64_t)a->B * a->Hkv * pl.nrb;
-    int64_t ns = (kTargetWorkgroups + base - 1) / base;
-    int64_t keys = a->Smax;
-    if (window > 0) {
-        const int64_t span = ((int64_t)window + a->Sq - 1 + pfa::dec::SPLIT_ALIGN - 1) / pfa::dec::SPLIT_ALIGN * pfa::dec::SPLIT_ALIGN;
-        if (span < keys) keys = span;
-    }
-    const int64_t max_by_len = keys / kMinSplitKeys > 1 ? keys / kMinSplitKeys : 1;
-    if (ns > max_by_len) ns = max_by_len;
-    if (ns > kMaxSplits) ns = kMaxSplits;
-    if (ns < 1) ns = 1;
-    pl.nsplit = (int)ns;
-    pl.items = base * ns;
-    if (ns > 1) pl.ws_bytes = (size_t)ns * a->B * a->H * a->Sq * (size_t)(a->D + 2) * sizeof(float);
-    return pl;
-}
+using pfa::decode::Plan;
+using pfa::decode::plan;
 
 // The tree block's field rules (include/pfa_hip.h, pfa_fa3_tree_mask), in the order their errors are reported; NULL is no tree.
 // pointers = false leaves out the two rules about `words` (the workspace query takes no pointers).
@@ -80,23 +42,6 @@ int check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_
         if (!pfa::aligned16(a->workspace)) return PFA_ERR_ALIGN;
     }
     return PFA_OK;
-}
-
-template <typename T, int D, bool WINDOW, bool TREE>
-const void* main_fn(bool out32, bool paged) {
-    if (paged)
-        return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, true, WINDOW, TREE>
-                     : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, true, WINDOW, TREE>;
-    return out32 ? (const void*)&pfa::dec::fa3_decode_kernel<T, D, float, false, WINDOW, TREE>
-                 : (const void*)&pfa::dec::fa3_decode_kernel<T, D, T, false, WINDOW, TREE>;
-}
-template <bool WINDOW, bool TREE = false>
-const void* main_fn(int dtype, int D, bool out32, bool paged) {
-    return pfa::dispatch_elem_dim(dtype, D, [&](auto t) { return main_fn<typename decltype(t)::type, decltype(t)::D, WINDOW, TREE>(out32, paged); });
-}
-template <typename T, int D>
-const void* combine_fn(bool out32) {
-    return out32 ? (const void*)&pfa::dec::fa3_decode_combine_kernel<D, float> : (const void*)&pfa::dec::fa3_decode_combine_kernel<D, T>;
 }
 
 }  // namespace
@@ -136,34 +81,21 @@ int pfa_fa3_decode_tree(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* e
     const int st = check(a, ext, tree, &window);
     if (st != PFA_OK) return st;
     const Plan pl = plan(a, window);
-    pfa::dec::DecodeWinParams p;    // the window-less kernels take its DecodeParams base, unchanged
-    pfa::fill_attention_params(p, a);
-    p.key_mask = a->key_mask; p.km_sb = a->key_mask_stride_b;
-    p.part_o = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
-    p.part_ml = pl.nsplit > 1 ? (float*)((char*)a->workspace + (size_t)pl.nsplit * a->B * a->H * a->Sq * a->D * sizeof(float)) : nullptr;
-    p.Hkv = a->Hkv; p.G = pl.G; p.nrb = pl.nrb; p.nsplit = pl.nsplit;
-    p.causal = a->causal != 0;
-    p.window = window;
-
-    const bool out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr;
-    const void* fn = tree     ? main_fn<false, true>(a->dtype_in, a->D, out32, paged)
-                     : window ? main_fn<true>(a->dtype_in, a->D, out32, paged)
-                              : main_fn<false>(a->dtype_in, a->D, out32, paged);
-    const void* cfn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) { return combine_fn<typename decltype(t)::type, decltype(t)::D>(out32); });
-    const pfa::DeviceScope dev(a->device_id);
-    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    int st_main;
     if (tree) {
-        pfa::dec::DecodeTreeParams tp;
-        static_cast<pfa::dec::DecodeParams&>(tp) = p;
-        tp.tree = tree->words; tp.tree_sb = tree->stride_b;
-        st_main = pfa::launch(fn, dim3((unsigned)pl.items), pfa::dec::THREADS, tp, 0, stream);
-    } else {
-        st_main = pfa::launch(fn, dim3((unsigned)pl.items), pfa::dec::THREADS, p, 0, stream);
+        pfa::dec::DecodeTreeParams p;
+        pfa::decode::fill_params(p, a, pl);
+        p.tree = tree->words; p.tree_sb = tree->stride_b;
+        return pfa::decode::launch<false, true>(a, pl, p, stream);
     }
-    if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
-    const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
-    return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+    if (window) {
+        pfa::dec::DecodeWinParams p;
+        pfa::decode::fill_params(p, a, pl);
+        p.window = window;
+        return pfa::decode::launch<true>(a, pl, p, stream);
+    }
+    pfa::dec::DecodeParams p;
+    pfa::decode::fill_params(p, a, pl);
+    return pfa::decode::launch<false>(a, pl, p, stream);
 }
 
 // the calls without a tree

@@ -1,5 +1,6 @@
-// pfa_fp8_host.h -- what the two entry-point files of the FP8 KV cache share (pfa_decode_fp8_capi.hip, pfa_kv_append_fp8_capi.hip): the
-// field rules of pfa_fa3_kv_quant and of an argument block's cache tensors when they hold one-byte elements.  Internal.
+// pfa_fp8_host.h -- what the entry-point files of the FP8 KV cache share (pfa_decode_fp8_capi.hip, pfa_kv_append_fp8_capi.hip and, through
+// pfa_prefill_host.h, the two pfa_prefill*_fp8_capi.hip): the field rules of pfa_fa3_kv_quant and of an argument block's cache tensors
+// when they hold one-byte elements, and the refusal of a window.  Internal.
 #pragma once
 #include "pfa_host.h"
 
@@ -23,5 +24,9 @@ inline int check_kv_quant(const pfa_fa3_kv_quant* q, const Args* a, bool pointer
     if (!aligned16(a->k_cache) || !aligned16(a->v_cache)) return PFA_ERR_ALIGN;
     return PFA_OK;
 }
+
+// An FP8 cache takes no window (PFA_ERR_FLAGS; the workspace query answers 0): asked in front of the 16-bit call's own rules, so only
+// of a block whose size says that `window` is where this library reads it.
+inline bool fp8_refuses_window(const pfa_fa3_cache_ext* ext) { return ext && ext->size == sizeof(pfa_fa3_cache_ext) && ext->window > 0; }
 
 }  // namespace pfa

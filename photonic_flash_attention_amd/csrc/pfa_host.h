@@ -44,13 +44,22 @@ public:
     hipError_t error() const { return err_; }   // of the switch; a launch behind a failed one is PFA_ERR_DEVICE
 };
 
+// A kernel of this library: one parameter block, by value.  Every kernel table hands out this type, so a table's rungs agree on the block.
+template <typename Params>
+using KernelFn = void (*)(Params);
+template <typename T>
+struct same_type { using type = T; };       // keeps a function parameter out of template argument deduction
+
 // The tail of a launch: opt in to more than 64 KiB of dynamic LDS where the kernel asks for it (idempotent, per function), enqueue with
 // the parameter block as the one kernel argument, and map a failure to PFA_ERR_LAUNCH (its code kept for pfa_last_hip_error).
+// Params comes from the kernel alone; the block converts to it, so a block of another type does not compile and a derived block
+// (DecodeWinParams for the combine kernel's DecodeParams) is passed as its base, which is what the kernel copies.
 template <typename Params>
-inline int launch(const void* fn, dim3 grid, unsigned threads, Params& p, size_t lds, void* stream) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    void* kargs[] = {&p};           // a kernel copies as many bytes as its parameter type has: a base of p, or all of it
-    return hip_failed(hipLaunchKernel(fn, grid, dim3(threads), kargs, lds, (hipStream_t)stream)) ? PFA_ERR_LAUNCH : PFA_OK;
+inline int launch(KernelFn<Params> fn, dim3 grid, unsigned threads, const typename same_type<Params>::type& p, size_t lds, void* stream) {
+    const void* f = reinterpret_cast<const void*>(fn);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    void* kargs[] = {const_cast<Params*>(&p)};
+    return hip_failed(hipLaunchKernel(f, grid, dim3(threads), kargs, lds, (hipStream_t)stream)) ? PFA_ERR_LAUNCH : PFA_OK;
 }
 
 // One tensor's strides from an argument block into a kernel parameter block: p.x_sb / x_sh / x_ss = a->x_stride_b / _h / _s.  Every

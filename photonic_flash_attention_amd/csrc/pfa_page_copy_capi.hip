@@ -58,7 +58,7 @@ int pfa_page_copy(const pfa_page_copy_args* a, void* stream) {
     p.dchunks = a->D / 8; p.units = a->Hkv * (a->D / 8);
     p.page_size = a->page_size; p.num_pages = a->num_pages;
 
-    const void* fn = a->rows ? (const void*)&pfa::page_copy_kernel<true> : (const void*)&pfa::page_copy_kernel<false>;
+    const pfa::KernelFn<pfa::PageCopyParams> fn = a->rows ? &pfa::page_copy_kernel<true> : &pfa::page_copy_kernel<false>;
     const pfa::DeviceScope dev(a->device_id);
     if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
     return pfa::launch(fn, dim3((unsigned)workgroups(a)), pfa::PAGE_COPY_THREADS, p, 0, stream);

@@ -31,7 +31,7 @@ int pfa_fa3_prefill_describe_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cach
 int pfa_fa3_prefill_ex(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, void* stream) {
     int window;
     const int st = check(a, ext, &window);
-    return st != PFA_OK ? st : pfa::prefill::launch<false>(a, window, stream);
+    return st != PFA_OK ? st : pfa::prefill::launch_windowed<false>(a, window, stream);
 }
 
 // the calls without the extension block

@@ -1,6 +1,6 @@
-// pfa_prefill_host.h -- what pfa_fa3_prefill and pfa_fa3_prefill_varlen share behind their argument blocks (internal): the grid, the
-// kernel table, the parameter fill and the launch of fa3_prefill_kernel.  VARLEN picks the ragged instantiations; each of the two
-// translation units instantiates one side only, so they still compile side by side.
+// pfa_prefill_host.h -- what the five pfa_prefill*_capi.hip units share behind their argument blocks (internal): the grid, the one
+// kernel table, the parameter fill and the one launch of fa3_prefill_kernel.  VARLEN / WINDOW / SPLIT / KV8 are fixed by the unit
+// that calls, so each unit instantiates its own kernels only and they still compile side by side.
 #pragma once
 #include <limits.h>
 #include <stdio.h>
@@ -28,30 +28,21 @@ int check_grid_and_ext(const Args* a, const pfa_fa3_cache_ext* ext, int* window)
     return check_cache_ext(ext, a->causal, a->Smax, window);
 }
 
-// fp32 output: P carried as a 16-bit hi + lo pair (SPLITP), as the forward does for its <= 1e-3 mode
-template <typename T, int D, bool VARLEN, bool CAUSAL, bool PAGED, bool WINDOW = false>
-const void* fn_out(bool out32) {
-    return out32 ? (const void*)&fa3_prefill_kernel<T, D, CAUSAL, true, PAGED, float, VARLEN, WINDOW>
-                 : (const void*)&fa3_prefill_kernel<T, D, CAUSAL, false, PAGED, T, VARLEN, WINDOW>;
-}
-// the windowed instantiations exist under the causal flag only
-template <typename T, int D, bool VARLEN>
-const void* fn_td(bool causal, bool paged, bool out32, bool window) {
-    if (window) return paged ? fn_out<T, D, VARLEN, true, true, true>(out32) : fn_out<T, D, VARLEN, true, false, true>(out32);
-    if (causal) return paged ? fn_out<T, D, VARLEN, true, true>(out32) : fn_out<T, D, VARLEN, true, false>(out32);
-    return paged ? fn_out<T, D, VARLEN, false, true>(out32) : fn_out<T, D, VARLEN, false, false>(out32);
-}
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false>
+using Params = typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8>::type;
 
-// KV8 (pfa_fa3_prefill_q8 / pfa_fa3_prefill_varlen_q8): the instantiations over an FP8 cache, no window
-template <typename T, int D, bool VARLEN, bool CAUSAL, bool PAGED>
-const void* fn_out_q8(bool out32) {
-    return out32 ? (const void*)&fa3_prefill_kernel<T, D, CAUSAL, true, PAGED, float, VARLEN, false, false, true>
-                 : (const void*)&fa3_prefill_kernel<T, D, CAUSAL, false, PAGED, T, VARLEN, false, false, true>;
-}
-template <typename T, int D, bool VARLEN>
-const void* fn_td_q8(bool causal, bool paged, bool out32) {
-    if (causal) return paged ? fn_out_q8<T, D, VARLEN, true, true>(out32) : fn_out_q8<T, D, VARLEN, true, false>(out32);
-    return paged ? fn_out_q8<T, D, VARLEN, false, true>(out32) : fn_out_q8<T, D, VARLEN, false, false>(out32);
+// fa3_prefill_kernel for (dtype, D, causal, paged, out) in the mode the caller fixes.  fp32 output: P carried as a 16-bit hi + lo pair
+// (SPLITP), as the forward does for its <= 1e-3 mode.  The windowed instantiations exist under the causal flag only and the split
+// ones with fp32 output only: validation refuses the rest, and the table has nullptr there, which no launch accepts.
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false>
+KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8>> kernel(int dtype, int D, bool causal, bool paged, bool out32) {
+    return dispatch_elem_dim(dtype, D, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return dispatch_bools([](auto c, auto pg, auto o32) -> KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8>> {
+            if constexpr ((WINDOW && !c.value) || (SPLIT && !o32.value)) return nullptr;
+            else return &fa3_prefill_kernel<T, decltype(t)::D, c.value, o32.value, pg.value, out_t<o32.value, T>, VARLEN, WINDOW, SPLIT, KV8>;
+        }, causal, paged, out32);
+    });
 }
 
 // of checked arguments: the kernel's name into buf -> workgroups.  `mode` (pfa_fa3_prefill_split: "_split{N}+merge") goes in front of "_paged"
@@ -65,8 +56,8 @@ int describe(const Args* a, int window, char* buf, size_t n, const char* mode = 
 }
 
 // what every launch of the kernel fills behind fill_attention_params
-template <bool VARLEN, typename Params, typename Args>
-void fill_prefill_params(Params& p, const Args* a) {
+template <bool VARLEN, typename Block, typename Args>
+void fill_prefill_params(Block& p, const Args* a) {
     fill_attention_params(p, a);
     p.nqblk = (p.Sq + FWD_BLOCK_M - 1) / FWD_BLOCK_M;
     p.kv_group = a->H / a->Hkv;
@@ -78,36 +69,34 @@ void fill_prefill_params(Params& p, const Args* a) {
 template <typename Args>
 size_t lds_bytes(const Args* a) { return (size_t)(2 * 2 * BLOCK_N * a->D * 2); }
 
-// of checked arguments: one launch on `stream`
-template <bool VARLEN, typename Args>
-int launch(const Args* a, int window, void* stream) {
-    typename PrefillParamsOf<VARLEN, true>::type p;   // the window-less kernels take its base, unchanged
+// of checked arguments and a block whose mode's own members (window; descales; split count and parts) the caller has set: the rest of
+// the block and one launch on `stream`, of nsplit times the call's workgroups.  The split parts are fp32 whatever the call's output is.
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, typename Args>
+int launch(const Args* a, Params<VARLEN, WINDOW, SPLIT, KV8>& p, void* stream, int nsplit = 1) {
     fill_prefill_params<VARLEN>(p, a);
-    p.window = window;
-
-    const bool out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr, causal = a->causal != 0, win = window != 0;
-    const void* fn = dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
-        return fn_td<typename decltype(t)::type, decltype(t)::D, VARLEN>(causal, paged, out32, win);
-    });
+    const auto fn = kernel<VARLEN, WINDOW, SPLIT, KV8>(a->dtype_in, a->D, a->causal != 0, a->block_table != nullptr,
+                                                       SPLIT || a->dtype_out == PFA_DTYPE_FP32);
     const DeviceScope dev(a->device_id);
     if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    return pfa::launch(fn, dim3((unsigned)workgroups(a)), FWD_THREADS, p, lds_bytes(a), stream);
+    return pfa::launch(fn, dim3((unsigned)(workgroups(a) * nsplit)), FWD_THREADS, p, lds_bytes(a), stream);
 }
-
+// ... of the 16-bit calls: with the window (0: none) check_grid_and_ext gave
+template <bool VARLEN, typename Args>
+int launch_windowed(const Args* a, int window, void* stream) {
+    if (window) {
+        Params<VARLEN, true> p;
+        p.window = window;
+        return launch<VARLEN, true>(a, p, stream);
+    }
+    Params<VARLEN> p;
+    return launch<VARLEN>(a, p, stream);
+}
 // ... over an FP8 cache (a checked pfa_fa3_kv_quant): the KV8 instantiations, same grid, same LDS
 template <bool VARLEN, typename Args>
 int launch_q8(const Args* a, const pfa_fa3_kv_quant* quant, void* stream) {
-    typename PrefillParamsOf<VARLEN, false, false, true>::type p;
-    fill_prefill_params<VARLEN>(p, a);
+    Params<VARLEN, false, false, true> p;
     p.k_descale = quant->k_descale; p.v_descale = quant->v_descale; p.ds_sb = quant->descale_stride_b;
-
-    const bool out32 = a->dtype_out == PFA_DTYPE_FP32, paged = a->block_table != nullptr, causal = a->causal != 0;
-    const void* fn = dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
-        return fn_td_q8<typename decltype(t)::type, decltype(t)::D, VARLEN>(causal, paged, out32);
-    });
-    const DeviceScope dev(a->device_id);
-    if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    return pfa::launch(fn, dim3((unsigned)workgroups(a)), FWD_THREADS, p, lds_bytes(a), stream);
+    return launch<VARLEN, false, false, true>(a, p, stream);
 }
 
 // The checks both q8 calls make in front of the 16-bit call's: the block, the rules of pfa_fa3_kv_quant, no window
@@ -117,7 +106,7 @@ int check_q8_front(const Args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv
     if (a->size != sizeof(Args)) return PFA_ERR_STRUCT_SIZE;
     const int st = check_kv_quant(quant, a);
     if (st != PFA_OK) return st;
-    if (ext && ext->size == sizeof(pfa_fa3_cache_ext) && ext->window > 0) return PFA_ERR_FLAGS;
+    if (fp8_refuses_window(ext)) return PFA_ERR_FLAGS;
     return PFA_OK;
 }
 // "fa3_prefill_..." of the 16-bit describe with "_kv8" behind the output type's part, in front of "_varlen" / "_paged"

@@ -82,16 +82,6 @@ int check(const pfa_fa3_decode_args* a, int32_t key_splits, int* nsplit) {
     return pfa_attn_merge_check(&m);          // what is left of its rules: the merge's own grid
 }
 
-template <typename T, int D>
-const void* split_fn(bool causal, bool paged) {
-    using namespace pfa;
-    if (causal)
-        return paged ? (const void*)&fa3_prefill_kernel<T, D, true, true, true, float, false, false, true>
-                     : (const void*)&fa3_prefill_kernel<T, D, true, true, false, float, false, false, true>;
-    return paged ? (const void*)&fa3_prefill_kernel<T, D, false, true, true, float, false, false, true>
-                 : (const void*)&fa3_prefill_kernel<T, D, false, true, false, float, false, false, true>;
-}
-
 }  // namespace
 
 extern "C" {
@@ -126,23 +116,11 @@ int pfa_fa3_prefill_split(const pfa_fa3_decode_args* a, int32_t key_splits, void
     if (ns == 1) return pfa_fa3_prefill(a, stream);      // the same kernel function, grid and bits
 
     pfa::PrefillSplitParams p;
-    pfa::fill_attention_params(p, a);
-    p.nqblk = (p.Sq + pfa::FWD_BLOCK_M - 1) / pfa::FWD_BLOCK_M;
-    p.kv_group = a->H / a->Hkv;
     p.nsplit = ns;
     p.part_o = (float*)a->workspace;
     p.part_lse = p.part_o + (int64_t)ns * part_elems(a);
-    const bool paged = a->block_table != nullptr, causal = a->causal != 0;
-    const void* fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
-        return split_fn<typename decltype(t)::type, decltype(t)::D>(causal, paged);
-    });
-    const int lds = 2 * 2 * pfa::BLOCK_N * a->D * 2;     // two buffers of a K and a V tile image, as pfa_fa3_prefill
-    {
-        const pfa::DeviceScope dev(a->device_id);
-        if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-        const int st_main = pfa::launch(fn, dim3((unsigned)(pfa::prefill::workgroups(a) * ns)), pfa::FWD_THREADS, p, (size_t)lds, stream);
-        if (st_main != PFA_OK) return st_main;
-    }
+    const int st_main = pfa::prefill::launch<false, false, true>(a, p, stream, ns);      // the caller's device is back before the merge
+    if (st_main != PFA_OK) return st_main;
     const pfa_attn_merge_args m = merge_args(a, ns);
     return pfa_attn_merge(&m, stream);
 }

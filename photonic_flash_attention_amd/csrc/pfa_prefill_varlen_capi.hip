@@ -33,7 +33,7 @@ int pfa_fa3_prefill_varlen_describe_ex(const pfa_fa3_prefill_varlen_args* a, con
 int pfa_fa3_prefill_varlen_ex(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, void* stream) {
     int window;
     const int st = check(a, ext, &window);
-    return st != PFA_OK ? st : pfa::prefill::launch<true>(a, window, stream);
+    return st != PFA_OK ? st : pfa::prefill::launch_windowed<true>(a, window, stream);
 }
 
 // the calls without the extension block

@@ -81,14 +81,14 @@ int pfa_fa3_varlen_bwd(const pfa_fa3_varlen_bwd_args* a, void* stream) {
     p.cu_q = a->cu_seqlens_q; p.cu_k = a->cu_seqlens_k; p.total_q = a->total_q; p.total_k = a->total_k;
 
     const bool causal = a->causal != 0, g32 = a->dtype_grad == PFA_DTYPE_FP32;
-    const void *kdq = nullptr, *kdkdv = nullptr;
+    pfa::KernelFn<pfa::BwdParams> kdq = nullptr, kdkdv = nullptr;
     pfa::dispatch_elem_dim(a->dtype, a->D, [&](auto t) {
         using T = typename decltype(t)::type;
         constexpr int D = decltype(t)::D;
         return pfa::dispatch_bools([&](auto c, auto o32) {
             using OTM = pfa::Packed<pfa::out_t<decltype(o32)::value, T>>;
-            kdq = (const void*)&pfa::fa3_bwd_dq_kernel<T, D, decltype(c)::value, false, OTM>;
-            kdkdv = (const void*)&pfa::fa3_bwd_dkdv_kernel<T, D, decltype(c)::value, false, OTM>;
+            kdq = &pfa::fa3_bwd_dq_kernel<T, D, decltype(c)::value, false, OTM>;
+            kdkdv = &pfa::fa3_bwd_dkdv_kernel<T, D, decltype(c)::value, false, OTM>;
             return 0;
         }, causal, g32);
     });

@@ -64,10 +64,10 @@ int pfa_fa3_varlen_fwd(const pfa_fa3_varlen_args* a, void* stream) {
     p.cu_q = a->cu_seqlens_q; p.cu_k = a->cu_seqlens_k; p.total_q = a->total_q; p.total_k = a->total_k;
     const bool causal = a->causal != 0, out32 = a->dtype_out == PFA_DTYPE_FP32;
     // (split P goes with the fp32 store: two of the four combinations exist)
-    const void* fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
+    const auto fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {
         using T = typename decltype(t)::type;
-        return pfa::dispatch_bools([](auto c, auto o32) {
-            return (const void*)&pfa::fa3_fwd_kernel<T, decltype(t)::D, c.value, o32.value, false, pfa::Packed<pfa::out_t<o32.value, T>>>;
+        return pfa::dispatch_bools([](auto c, auto o32) -> pfa::KernelFn<pfa::FwdParams> {
+            return &pfa::fa3_fwd_kernel<T, decltype(t)::D, c.value, o32.value, false, pfa::Packed<pfa::out_t<o32.value, T>>>;
         }, causal, out32);
     });
     const pfa::DeviceScope dev(a->device_id);

@@ -3,17 +3,17 @@
 #include <hip/hip_runtime.h>
 
 #include "fa3_fwd_w4_kernel.h"
+#include "pfa_host.h"
 
 namespace pfa {
 
-// dtype: 0 = bf16, 1 = fp16 (PFA_DTYPE_*); out32: fp32 store.  Returns the kernel's address for hipLaunchKernel.
-const void* w4_kernel(int dtype, bool causal, bool out32) {
-    if (dtype == 0) {
-        if (out32) return causal ? (const void*)&fa3_fwd_w4_kernel<__bf16, true, float> : (const void*)&fa3_fwd_w4_kernel<__bf16, false, float>;
-        return causal ? (const void*)&fa3_fwd_w4_kernel<__bf16, true, __bf16> : (const void*)&fa3_fwd_w4_kernel<__bf16, false, __bf16>;
-    }
-    if (out32) return causal ? (const void*)&fa3_fwd_w4_kernel<_Float16, true, float> : (const void*)&fa3_fwd_w4_kernel<_Float16, false, float>;
-    return causal ? (const void*)&fa3_fwd_w4_kernel<_Float16, true, _Float16> : (const void*)&fa3_fwd_w4_kernel<_Float16, false, _Float16>;
+template <typename T>
+static KernelFn<FwdParams> w4_kernel_of(bool causal, bool out32) {
+    return dispatch_bools([](auto c, auto o32) -> KernelFn<FwdParams> { return &fa3_fwd_w4_kernel<T, c.value, out_t<o32.value, T>>; }, causal, out32);
+}
+// dtype: PFA_DTYPE_BF16 or PFA_DTYPE_FP16; out32: fp32 store.
+KernelFn<FwdParams> w4_kernel(int dtype, bool causal, bool out32) {
+    return dtype == PFA_DTYPE_BF16 ? w4_kernel_of<__bf16>(causal, out32) : w4_kernel_of<_Float16>(causal, out32);
 }
 
 }  // namespace pfa

@@ -7,7 +7,8 @@ the commit to compare against under another name).
 
 Prints one line per kernel of OLD: `same` (instruction for instruction, same register counts, LDS, scratch and kernarg size),
 `DIFFERENT` with the first differing line, or `missing`; then the kernels only NEW has.  Exit status 1 if any differs or is missing.
-Comments, debug labels and the order of functions in the file are ignored; nothing else is.  A kernel of OLD is matched with the kernel of
+Comments, debug labels and the order of functions in the file (with it the function index in `.LBB<function>_<block>` labels) are
+ignored; nothing else is.  A kernel of OLD is matched with the kernel of
 NEW that has its name and its template arguments, followed by nothing or by trailing `false` (`Lb0E`) / `void` arguments only: a template
 that gained defaulted parameters keeps its old instantiations under longer mangled names."""
 import re
@@ -19,7 +20,8 @@ def functions(path):
     text = open(path).read()
     out = {}
     for m in re.finditer(r"^(\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:", text, flags=re.S | re.M):
-        body = [re.sub(r"\s*;.*$", "", ln).strip() for ln in m.group(2).splitlines()]
+        # (a local label carries the index of its function in the file, .LBB<function>_<block>: the order of functions is not compared)
+        body = [re.sub(r"\.(LBB|LJTI)\d+_", r".\1_", re.sub(r"\s*;.*$", "", ln)).strip() for ln in m.group(2).splitlines()]
         out[m.group(1)] = [[ln.replace(m.group(1), "SELF") for ln in body if ln and not ln.startswith((".loc", ".file", ".cfi", ";"))], []]
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\w+)\n(.*?)^\s*\.end_amdhsa_kernel", text, flags=re.S | re.M):
         if m.group(1) in out:
