@@ -16,11 +16,13 @@ from __future__ import annotations
 import ctypes as C
 import operator
 import threading
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _capi
+from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _page_copy_model,      # noqa: F401
+                      _rope_append_model, _rope_rotate, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
 
@@ -143,6 +145,58 @@ def _set_strides(a, fields) -> None:
         setattr(a, fb, sb); setattr(a, fh, sh); setattr(a, fs, ss)
 
 
+# pointer field -> the prefix of its ``*_stride_*`` fields, over all blocks; and per (pointer field, axis letters in a block's order) the
+# (stride field, tensor dim) pairs: "bhs" / "bsh" name the dims of a [B,H,S,D]-shaped tensor, "sh" those of packed [total,heads,D] rows
+_STRIDE_PREFIX = {**{n: n for n in ("q", "k", "v", "o", "dq", "dk", "dv")}, "dout": "do", "k_cache": "k", "v_cache": "v", "k_pool": "k",
+                  "v_pool": "v", "k_new": "kn", "v_new": "vn", "q_out": "qo"}
+_VIEW_FIELDS = {(name, axes): tuple((f"{pre}_stride_{x}", ("bhs" if "b" in axes else "sh").index(x)) for x in axes)
+                for axes in ("bhs", "bsh", "sh") for name, pre in _STRIDE_PREFIX.items()}
+
+
+def _set_view(a, name: str, t: torch.Tensor, axes: str = "bhs") -> None:
+    """``_set_strides`` for every other block: ``t``'s pointer into field ``name`` and, for each letter of ``axes`` (the block's own
+    order of them), the stride of the axis it names into that ``*_stride_<letter>`` field.  The head dim must be contiguous."""
+    st = t.stride()
+    if st[-1] != 1 and t.shape[-1] != 1:
+        raise ValueError("last (head_dim) stride must be 1")
+    setattr(a, name, t.data_ptr())
+    for field, dim in _VIEW_FIELDS[name, axes]:
+        setattr(a, field, st[dim])
+
+
+def _set_block_table(a, block_table, page_size: int, num_pages: int) -> None:
+    """The four paging fields of a block over a KV cache; nothing without a table."""
+    if block_table is not None:
+        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
+        a.page_size, a.num_pages = page_size, num_pages
+
+
+def _attach_workspace(a, nbytes, device, keep: list, field: str = "workspace") -> None:
+    """``nbytes`` (what the library asked for) of fresh device scratch into ``field`` / ``{field}_bytes``, kept in ``keep``; nothing for 0."""
+    nbytes = int(nbytes)
+    if nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        setattr(a, field, ws.data_ptr())
+        setattr(a, field + "_bytes", nbytes)
+        keep.append(ws)
+
+
+def _hold(keep, stream) -> None:
+    """Tensors made for a call must outlive the kernels enqueued on ``stream``."""
+    for t in keep:
+        t.record_stream(stream)
+
+
+def _host_int(value):
+    """``value`` as a host integer, or None for a bool and for anything without ``__index__``."""
+    if isinstance(value, bool):
+        return None
+    try:
+        return operator.index(value)
+    except TypeError:
+        return None
+
+
 def _lse_ptr(lse: torch.Tensor, B: int, H: int, Sq: int) -> int:
     if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
         raise ValueError("lse must be contiguous fp32 [B, H, Sq]")
@@ -233,11 +287,7 @@ def build_args(q, k, v, out, *, causal=False, seqlens_k=None, key_mask=None, sof
     if key_mask is not None or mask is not None:
         # scratch for the mask condensed to one 64-bit word per row and 64-key tile (pfa_fa3_workspace_bytes; optional for the
         # C ABI, always given here): a padding mask then costs about what seqlens_k costs, an element mask 1/3 of the byte path
-        ws_bytes = int(_capi.load().pfa_fa3_workspace_bytes(C.byref(a)))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-            keep.append(ws)
+        _attach_workspace(a, _capi.load().pfa_fa3_workspace_bytes(C.byref(a)), q.device, keep)
     if lse is not None:
         a.lse = _lse_ptr(lse, B, H, Sq)
     if drop_mask is not None:
@@ -298,7 +348,8 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
     args, keep = build_args(q, k, v, out, causal=causal, seqlens_k=seqlens_k, key_mask=key_mask, mask=mask,
                             softmax_scale=softmax_scale, lse=lse, split_p=split_p, variant=_variant,
                             drop_mask=drop_mask, drop_scale=drop_scale)
-    stream = torch.cuda.current_stream(q.device).cuda_stream
+    held = torch.cuda.current_stream(q.device)
+    stream = held.cuda_stream
     st = _capi.load().pfa_fa3_fwd(C.byref(args), C.c_void_p(stream))
     _raise_status("pfa_fa3_fwd", st)
     weights = None
@@ -309,8 +360,8 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
         stw = _capi.load().pfa_fa3_weights(C.byref(args), C.c_void_p(weights.data_ptr()), _DT[wdt],
                                            weights.stride(0), weights.stride(1), weights.stride(2), C.c_void_p(stream))
         _raise_status("pfa_fa3_weights", stw)
-    for t in keep:   # tensors made here must outlive the enqueued kernels
-        t.record_stream(torch.cuda.current_stream(q.device))
+    if keep:
+        _hold(keep, held)
     if return_weights:
         return out, (lse if return_lse else None), weights
     return out, lse
@@ -393,15 +444,10 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
     a.device_id = _device_index(q.device)
     stream = torch.cuda.current_stream(q.device)
     if a.mask:   # element masks: scratch for the condensed words / tile ranges (0 bytes for key-only masks; optional for the library)
-        mws = int(_capi.load().pfa_fa3_bwd_mask_workspace_bytes(C.byref(a)))
-        if mws:
-            ws = torch.empty(mws, dtype=torch.uint8, device=q.device)
-            a.mask_workspace, a.mask_workspace_bytes = ws.data_ptr(), mws
-            keep.append(ws)
+        _attach_workspace(a, _capi.load().pfa_fa3_bwd_mask_workspace_bytes(C.byref(a)), q.device, keep, "mask_workspace")
     st = _capi.load().pfa_fa3_bwd(C.byref(a), C.c_void_p(stream.cuda_stream))
     _raise_status("pfa_fa3_bwd", st)
-    for t in keep:
-        t.record_stream(stream)
+    _hold(keep, stream)
     return dq, dk, dv
 
 
@@ -491,35 +537,6 @@ def _raise_status(entry: str, st: int, null_too: bool = False) -> None:
     _capi.check_status(st)
 
 
-FP8 = torch.float8_e4m3fn           # the element type of an FP8 KV cache: OCP e4m3fn (max finite 448, 0x7f / 0xff NaN, no infinities)
-FP8_MAX = 448.0
-
-
-def _descale_like(x: torch.Tensor, descale: torch.Tensor) -> torch.Tensor:
-    """``descale`` ``[Hkv]`` or ``[B, Hkv]`` (fp32) shaped to broadcast over ``x`` ``[B, Hkv, S, D]`` (pools: ``[num_pages, Hkv, page, D]``)."""
-    if not isinstance(descale, torch.Tensor) or descale.dtype != torch.float32 or descale.dim() not in (1, 2):
-        raise ValueError("a descale must be an fp32 tensor [Hkv] or [B, Hkv]")
-    if x.dim() != 4 or descale.shape[-1] != x.shape[1] or (descale.dim() == 2 and descale.shape[0] != x.shape[0]):
-        raise ValueError(f"descale {tuple(descale.shape)} does not match a [B, Hkv, S, D] tensor of shape {tuple(x.shape)}")
-    return descale[..., None, None]
-
-
-def quantize_kv(x: torch.Tensor, descale: torch.Tensor) -> torch.Tensor:
-    """``x`` ``[B, Hkv, S, D]`` (any floating dtype) as the FP8 cache holds it: ``e4m3fn(clamp(float(x) / descale, -448, 448))``, descale
-    fp32 ``[Hkv]`` or ``[B, Hkv]`` -- the rule of ``kv_append`` into an FP8 cache, in plain torch (a first prompt's K / V, the tests).
-    The division is fp32, the cast rounds to nearest even, NaN stays NaN; without the clamp the cast would turn 500.0 into NaN."""
-    d = _descale_like(x, descale)
-    return (x.to(torch.float32) / d).clamp(-FP8_MAX, FP8_MAX).to(FP8)
-
-
-def dequantize_kv(x8: torch.Tensor, descale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    """The values an FP8 cache ``x8`` ``[B, Hkv, S, D]`` stands for, ``e4m3(x8) * descale``, as ``dtype``: computed in fp64 for
-    ``torch.float64`` (exact: what a reference takes), else in fp32 and rounded once."""
-    if x8.dtype != FP8:
-        raise ValueError("dequantize_kv takes a torch.float8_e4m3fn tensor")
-    d = _descale_like(x8, descale)
-    w = torch.float64 if dtype == torch.float64 else torch.float32
-    return (x8.to(torch.float32).to(w) * d.to(w)).to(dtype)
 
 
 def _kv_quant_arg(entry: str, k_cache, v_cache, k_descale, v_descale, B: int, Hkv: int, device):
@@ -571,9 +588,31 @@ def _cache_geometry(name: str, rows, B, Hkv, D, k_cache, v_cache, block_table, H
     return Smax, page_size, num_pages
 
 
-def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8=False):
+class _CacheOperands(NamedTuple):
+    """``_cache_operands``' result."""
+    Hkv: int
+    Smax: int
+    page_size: int
+    num_pages: int
+    odt: torch.dtype
+
+
+def _rank4(*tensors) -> None:
+    """The 4-D rule of the uniform calls over a KV cache, for the operands given."""
+    for t in tensors:
+        if t.dim() != 4:
+            raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+
+
+def _out_arg(out, shape, odt, device) -> None:
+    """A caller's ``out=`` of the uniform calls over a KV cache against the result's shape, dtype and device."""
+    if out.shape != shape or out.dtype != odt or out.device != device:
+        raise ValueError("out must be a [B, H, Sq, D] tensor of the output dtype on the operands' device")
+
+
+def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8=False) -> _CacheOperands:
     """What the attention calls over a KV cache check about their caches against a query of B sequences, H heads and head dim D:
-    ``_cache_geometry`` and what only the readers ask.  -> ``(Hkv, Smax, page_size, num_pages, output dtype)``."""
+    ``_cache_geometry`` and what only the readers ask."""
     Hkv = k_cache.shape[1]
     Smax, page_size, num_pages = _cache_geometry("q", q, B, Hkv, D, k_cache, v_cache, block_table, H)
     if block_table is not None and (not block_table.is_cuda or block_table.device != q.device):
@@ -588,32 +627,29 @@ def _cache_operands(entry: str, q, B, H, D, k_cache, v_cache, out_dtype, block_t
     odt = q.dtype if out_dtype is None else out_dtype
     if odt not in (q.dtype, torch.float32):
         raise ValueError("output dtype must be the input dtype or fp32")
-    return Hkv, Smax, page_size, num_pages, odt
+    return _CacheOperands(Hkv, Smax, page_size, num_pages, odt)
 
 
 def _cache_call_args(entry: str, q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table, fp8=False):
     """Validation and marshalling ``fa3_decode`` and ``fa3_prefill_cache`` share (both take ``pfa_fa3_decode_args``): the operands,
     the output buffer and the block table.  -> ``(args, out, Smax)``; ``entry`` names the C entry point in the messages."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
-        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    _rank4(q, k_cache, v_cache)
     B, H, Sq, D = q.shape
-    Hkv, Smax, page_size, num_pages, odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8)
+    geo = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8)
     if out is None:
-        out = torch.empty((B, Sq, H, D), dtype=odt, device=q.device).permute(0, 2, 1, 3)
-    elif out.shape != (B, H, Sq, D) or out.dtype != odt or out.device != q.device:
-        raise ValueError("out must be a [B, H, Sq, D] tensor of the output dtype on the operands' device")
-    qs, ks, vs, os_ = (_bhsd_strides(t) for t in (q, k_cache, v_cache, out))
+        out = torch.empty((B, Sq, H, D), dtype=geo.odt, device=q.device).permute(0, 2, 1, 3)
+    else:
+        _out_arg(out, (B, H, Sq, D), geo.odt, q.device)
     a = _capi.make_decode_args(
-        q=q.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(), o=out.data_ptr(),
-        q_stride_b=qs[0], q_stride_h=qs[1], q_stride_s=qs[2], k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2],
-        v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2], o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2],
-        B=B, H=H, Hkv=Hkv, Sq=Sq, Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt], causal=1 if causal else 0,
+        B=B, H=H, Hkv=geo.Hkv, Sq=Sq, Smax=geo.Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[geo.odt], causal=1 if causal else 0,
         softmax_scale=_scale(softmax_scale, D),
         device_id=_device_index(q.device))
-    if block_table is not None:
-        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
-        a.page_size, a.num_pages = page_size, num_pages
-    return a, out, Smax
+    _set_view(a, "q", q)
+    _set_view(a, "k_cache", k_cache)
+    _set_view(a, "v_cache", v_cache)
+    _set_view(a, "o", out)
+    _set_block_table(a, block_table, geo.page_size, geo.num_pages)
+    return a, out, geo.Smax
 
 
 def _set_cache_seqlens(a, cache_seqlens, q, keep, B=None) -> None:
@@ -635,10 +671,7 @@ def _window_ext(window, causal):
     Refused before anything is launched: any other value, and a window without ``causal``."""
     if window is None:
         return None
-    try:
-        w = None if isinstance(window, bool) else operator.index(window)
-    except TypeError:
-        w = None
+    w = _host_int(window)
     if w is None or w < 1:
         raise ValueError(f"window must be None or an integer >= 1, got {window!r}")
     if not causal:
@@ -654,8 +687,7 @@ def _tree_mask_arg(tree_mask, q, causal, window, shared_prefix):
         return None
     if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
         raise ValueError("tree_mask must be an int64 tensor (one 64-bit word per query row; the kernel reads it as unsigned)")
-    if q.dim() != 4:
-        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    _rank4(q)
     B, Sq = q.shape[0], q.shape[2]
     if tree_mask.shape != (B, Sq):
         raise ValueError(f"tree_mask must be [B, Sq] = [{B}, {Sq}], got {tuple(tree_mask.shape)}")
@@ -715,69 +747,53 @@ def _key_splits_arg(name: str, value):
     1 .. 8 is itself.  Any other value or type is refused before anything is launched."""
     if value is None:
         return None
-    if isinstance(value, str):
-        if value == "auto":
-            return 0
-    elif not isinstance(value, bool):
-        try:
-            n = operator.index(value)
-        except TypeError:
-            n = 0
-        if 1 <= n <= _capi.PFA_PREFILL_MAX_SPLITS:
-            return n
+    if isinstance(value, str) and value == "auto":
+        return 0
+    n = _host_int(value)
+    if n is not None and 1 <= n <= _capi.PFA_PREFILL_MAX_SPLITS:
+        return n
     raise ValueError(f'{name} must be None, "auto" or an integer 1 .. {_capi.PFA_PREFILL_MAX_SPLITS}, got {value!r}')
 
 
-def _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, max_seqlen_q, block_table) -> None:
-    """``pfa_kv_append``'s rule in plain torch, every clamp and drop included: the executable specification, and what ``kv_append``
-    runs on CPU tensors.  ``lens`` / ``cu`` are host lists; k_new ``[total, Hkv, D]`` with ``cu``, else ``[B, Hkv, Sq, D]``."""
-    paged = block_table is not None
-    Smax = block_table.shape[1] * k_cache.shape[2] if paged else k_cache.shape[2]
-    page_size, num_pages, total = k_cache.shape[2], k_cache.shape[0], k_new.shape[0]
-    for b, n in enumerate(lens):
-        len_b = min(max(n, 0), Smax)
-        if cu is not None:
-            s_b = min(max(cu[b], 0), total)
-            e_b = min(max(cu[b + 1], s_b), total)
-            sq = min(e_b - s_b, max_seqlen_q)
-            rows = [t[s_b:s_b + sq] for t in (k_new, v_new)]                 # [Sq_b, Hkv, D]
-        else:
-            sq = max_seqlen_q
-            rows = [t[b].transpose(0, 1) for t in (k_new, v_new)]
-        first = max(0, sq - len_b)                                            # rows in front of key 0 are dropped
-        if first >= sq:
-            continue
-        pos = torch.arange(len_b - sq + first, len_b)
-        rows = [r[first:sq] for r in rows]
-        if not paged:
-            for cache, r in zip((k_cache, v_cache), rows):
-                cache[b][:, pos] = r.transpose(0, 1)
-            continue
-        pg = block_table[b, pos // page_size].to(torch.int64)
-        ok = (pg >= 0) & (pg < num_pages)                                     # a page id outside the pool drops the write
-        for pool, r in zip((k_cache, v_cache), rows):
-            pool[pg[ok], :, (pos % page_size)[ok]] = r[ok]
+def _cu_seqlens_arg(cu_seqlens_q, *, layout: bool = True, contiguous: bool = True) -> int:
+    """``cu_seqlens_q`` of the ragged calls over a KV cache -> B.  ``layout``: int32 and ``[B + 1]``; ``contiguous``: that too.  The append
+    checks all of it at once; ``fa3_prefill_varlen`` has the caches' checks between the two halves."""
+    if layout:
+        if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
+            raise ValueError("cu_seqlens_q must be an int32 tensor")
+        if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
+            raise ValueError(f"cu_seqlens_q must be [B + 1], got {tuple(cu_seqlens_q.shape)}")
+    if contiguous and not cu_seqlens_q.is_contiguous():
+        raise ValueError("cu_seqlens_q must be contiguous")
+    return cu_seqlens_q.numel() - 1
+
+
+class _AppendOperands(NamedTuple):
+    """``_append_operands``' result."""
+    ragged: bool
+    B: int
+    Hkv: int
+    D: int
+    total: int
+    max_seqlen_q: int
+    Smax: int
+    page_size: int
+    num_pages: int
 
 
 def _append_operands(entry: str, k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others=(),
-                     fp8=False):
+                     fp8=False) -> _AppendOperands:
     """What ``kv_append`` and ``rope_append`` check about the step's rows, the caches and the device data they share (``others``: the
-    further tensors that must live on k_new's device).  -> ``(ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages)``."""
+    further tensors that must live on k_new's device)."""
     ragged = cu_seqlens_q is not None
     if k_new.dim() != (3 if ragged else 4) or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("k_new must be 3-D ([total,Hkv,D]) with cu_seqlens_q, else 4-D ([B,Hkv,Sq,D]); k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
     if v_new.shape != k_new.shape:
         raise ValueError(f"shape mismatch: k_new {tuple(k_new.shape)} v_new {tuple(v_new.shape)}")
     if ragged:
-        if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
-            raise ValueError("cu_seqlens_q must be an int32 tensor")
-        if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
-            raise ValueError(f"cu_seqlens_q must be [B + 1], got {tuple(cu_seqlens_q.shape)}")
-        if not cu_seqlens_q.is_contiguous():
-            raise ValueError("cu_seqlens_q must be contiguous")
+        B, (total, Hkv, D) = _cu_seqlens_arg(cu_seqlens_q), k_new.shape
         if max_seqlen_q is None:
             raise ValueError("cu_seqlens_q needs max_seqlen_q, the host bound on a sequence's rows (it sizes the grid)")
-        B, (total, Hkv, D) = cu_seqlens_q.numel() - 1, k_new.shape
     else:
         B, Hkv, Sq, D = k_new.shape
         if max_seqlen_q is not None and int(max_seqlen_q) != Sq:
@@ -800,31 +816,24 @@ def _append_operands(entry: str, k_new, v_new, k_cache, v_cache, cache_seqlens, 
     if any(t.device != dev for t in (v_new, k_cache, v_cache, cache_seqlens) + ((cu_seqlens_q,) if ragged else ())
            + ((block_table,) if block_table is not None else ()) + tuple(others)):
         raise ValueError(f"{entry} needs all its tensors on one device")
-    return ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages
+    return _AppendOperands(ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages)
 
 
-def _append_args(make, entry: str, k_new, v_new, k_cache, v_cache, geometry, cu_seqlens_q, block_table, **more):
+def _append_args(make, entry: str, k_new, v_new, k_cache, v_cache, geo: _AppendOperands, cu_seqlens_q, block_table, **more):
     """The argument block of ``pfa_kv_append`` / ``pfa_rope_append`` (``make``: its ``_capi`` constructor) with the fields the two
-    share filled in from ``_append_operands``' ``geometry``; ``more`` are further fields."""
-    ragged, B, Hkv, D, total, max_seqlen_q, Smax, page_size, num_pages = geometry
+    share filled in from ``_append_operands``' ``geo``; ``more`` are further fields."""
     if not k_new.is_cuda:
         raise ValueError(f"{entry} needs device tensors (or CPU tensors for the torch model)")
-    if any(t.stride(-1) != 1 and D != 1 for t in (k_new, v_new)):
-        raise ValueError("last (head_dim) stride must be 1")
-    ks, vs = _bhsd_strides(k_cache), _bhsd_strides(v_cache)
-    a = make(
-        k_new=k_new.data_ptr(), v_new=v_new.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(),
-        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
-        B=B, Hkv=Hkv, total_new=total, max_seqlen_q=max_seqlen_q, Smax=Smax, D=D, dtype=_DT[k_new.dtype],
-        device_id=_device_index(k_new.device), **more)
-    if ragged:
-        a.cu_seqlens_q = cu_seqlens_q.data_ptr()
-        a.kn_stride_s, a.kn_stride_h, a.vn_stride_s, a.vn_stride_h = k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1)
-    else:
-        (a.kn_stride_b, a.kn_stride_h, a.kn_stride_s), (a.vn_stride_b, a.vn_stride_h, a.vn_stride_s) = k_new.stride()[:3], v_new.stride()[:3]
-    if block_table is not None:
-        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
-        a.page_size, a.num_pages = page_size, num_pages
+    a = make(B=geo.B, Hkv=geo.Hkv, total_new=geo.total, max_seqlen_q=geo.max_seqlen_q, Smax=geo.Smax, D=geo.D, dtype=_DT[k_new.dtype],
+             device_id=_device_index(k_new.device), **more)
+    rows = "bsh"
+    if geo.ragged:
+        a.cu_seqlens_q, rows = cu_seqlens_q.data_ptr(), "sh"
+    _set_view(a, "k_new", k_new, rows)
+    _set_view(a, "v_new", v_new, rows)
+    _set_view(a, "k_cache", k_cache)
+    _set_view(a, "v_cache", v_cache)
+    _set_block_table(a, block_table, geo.page_size, geo.num_pages)
     return a
 
 
@@ -833,30 +842,11 @@ def _append_launch(entry: str, a, cache_seqlens, k_new, B, quant=None) -> None:
     keep = []
     _set_cache_seqlens(a, cache_seqlens, k_new, keep, B)
     stream = torch.cuda.current_stream(k_new.device)
-    if quant is not None:
-        st = getattr(_capi.load(), entry + "_q8")(C.byref(a), C.byref(quant), C.c_void_p(stream.cuda_stream))
-    else:
-        st = getattr(_capi.load(), entry)(C.byref(a), C.c_void_p(stream.cuda_stream))
+    lib, s = _capi.load(), C.c_void_p(stream.cuda_stream)
+    st = getattr(lib, entry)(C.byref(a), s) if quant is None else getattr(lib, entry + "_q8")(C.byref(a), C.byref(quant), s)
     _raise_status(entry, st, null_too=True)
-    for t in keep:   # tensors made here must outlive the enqueued kernel
-        t.record_stream(stream)
-
-
-def _kv_append_q8_model(k_new, v_new, k_cache, v_cache, k_descale, v_descale, lens, cu, max_seqlen_q, block_table) -> None:
-    """``pfa_kv_append_q8``'s rule in plain torch: every source element as ``quantize_kv`` stores it, then ``_kv_append_model``'s
-    placement, on the caches' bytes.  The executable specification, and what ``kv_append`` runs on CPU tensors with FP8 caches."""
-    def rows8(x, d):
-        if cu is None:                                    # [B, Hkv, Sq, D]
-            return quantize_kv(x, d)
-        if d.dim() == 2:                                  # packed rows: each row takes its sequence's scales
-            seq = torch.zeros(x.shape[0], dtype=torch.int64)
-            for b in range(len(lens)):
-                s_b = min(max(cu[b], 0), x.shape[0])
-                seq[s_b:min(max(cu[b + 1], s_b), x.shape[0])] = b
-            d = d[seq]                                    # [total, Hkv]
-        return (x.to(torch.float32) / d[..., None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
-    _kv_append_model(rows8(k_new, k_descale).view(torch.uint8), rows8(v_new, v_descale).view(torch.uint8), k_cache.view(torch.uint8),
-                     v_cache.view(torch.uint8), lens, cu, max_seqlen_q, block_table)
+    if keep:
+        _hold(keep, stream)
 
 
 def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
@@ -891,29 +881,16 @@ def kv_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v
     fp8 = k_cache.dtype == FP8 or v_cache.dtype == FP8
     geo = _append_operands("pfa_kv_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
                            fp8=fp8)
-    quant = _kv_quant_arg("pfa_kv_append", k_cache, v_cache, k_descale, v_descale, geo[1], geo[2], k_new.device)
+    quant = _kv_quant_arg("pfa_kv_append", k_cache, v_cache, k_descale, v_descale, geo.B, geo.Hkv, k_new.device)
     if k_new.device.type == "cpu":
-        lens, cu = cache_seqlens.tolist(), cu_seqlens_q.tolist() if geo[0] else None
+        lens, cu = cache_seqlens.tolist(), cu_seqlens_q.tolist() if geo.ragged else None
         if fp8:
-            _kv_append_q8_model(k_new, v_new, k_cache, v_cache, k_descale, v_descale, lens, cu, geo[5], block_table)
+            _kv_append_q8_model(k_new, v_new, k_cache, v_cache, k_descale, v_descale, lens, cu, geo.max_seqlen_q, block_table)
         else:
-            _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, geo[5], block_table)
+            _kv_append_model(k_new, v_new, k_cache, v_cache, lens, cu, geo.max_seqlen_q, block_table)
         return
     a = _append_args(_capi.make_kv_append_args, "pfa_kv_append", k_new, v_new, k_cache, v_cache, geo, cu_seqlens_q, block_table)
-    _append_launch("pfa_kv_append", a, cache_seqlens, k_new, geo[1], quant)
-
-
-def _page_copy_model(k_pool, v_pool, pairs, rows) -> None:
-    """``pfa_page_copy``'s rule in plain torch, pair by pair in order, every range check and clamp included: the executable
-    specification, and what ``page_copy`` runs on CPU tensors.  ``pairs`` is a host list of ``(src, dst)``, ``rows`` one of counts or
-    None; the pools are ``[num_pages, Hkv, page_size, D]``-shaped views."""
-    num_pages, page_size = k_pool.shape[0], k_pool.shape[2]
-    for i, (s, d) in enumerate(pairs):
-        if not 0 <= s < num_pages or not 0 <= d < num_pages or s == d:       # the empty pair: nothing read, nothing written
-            continue
-        r = page_size if rows is None else min(max(rows[i], 0), page_size)
-        for pool in (k_pool, v_pool):
-            pool[d, :, :r] = pool[s, :, :r].clone()
+    _append_launch("pfa_kv_append", a, cache_seqlens, k_new, geo.B, quant)
 
 
 def page_copy(k_pool: torch.Tensor, v_pool: torch.Tensor, pairs: torch.Tensor, *, rows: Optional[torch.Tensor] = None) -> None:
@@ -964,14 +941,11 @@ def page_copy(k_pool: torch.Tensor, v_pool: torch.Tensor, pairs: torch.Tensor, *
         return
     if not k_pool.is_cuda:
         raise ValueError("pfa_page_copy needs device tensors (or CPU tensors for the torch model)")
-    if k_pool.stride(-1) != 1 or v_pool.stride(-1) != 1:
-        raise ValueError("last (head_dim) stride must be 1")
-    ks, vs = _bhsd_strides(k_pool), _bhsd_strides(v_pool)
     a = _capi.make_page_copy_args(
-        k_pool=k_pool.data_ptr(), v_pool=v_pool.data_ptr(), pairs=pairs.data_ptr(), rows=None if rows is None else rows.data_ptr(),
-        pairs_stride=pairs.stride(0) if n > 1 else 2,
-        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
+        pairs=pairs.data_ptr(), rows=None if rows is None else rows.data_ptr(), pairs_stride=pairs.stride(0) if n > 1 else 2,
         n_pairs=n, Hkv=Hkv, D=D, page_size=page_size, num_pages=num_pages, dtype=_DT[k_pool.dtype], device_id=_device_index(dev))
+    _set_view(a, "k_pool", k_pool)
+    _set_view(a, "v_pool", v_pool)
     st = _capi.load().pfa_page_copy(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     _raise_status("pfa_page_copy", st, null_too=True)
 
@@ -986,63 +960,6 @@ def rotary_tables(max_pos: int, rot_dim: int, base: float = 10000.0, device=None
     angle = torch.arange(max_pos, dtype=torch.float64)[:, None] * inv_freq[None, :]
     cos, sin = angle.cos().to(torch.float32), angle.sin().to(torch.float32)
     return (cos, sin) if device is None else (cos.to(device), sin.to(device))
-
-
-def _rope_rotate(x: torch.Tensor, c: torch.Tensor, s: torch.Tensor, interleaved: bool) -> torch.Tensor:
-    """Rows ``x [n, heads, D]`` rotated by their table rows ``c`` / ``s`` (fp32 ``[n, half]``), as ``pfa_rope_append`` rounds: operands
-    widened to fp32, the two products and the add / subtract separate fp32 operations, one rounding to the dtype.  Elements at and
-    past ``2 * half`` are copied.  -> a new tensor."""
-    half = c.shape[-1]
-    R = 2 * half
-    c, s = c[:, None, :], s[:, None, :]
-    x1, x2 = (x[..., 0:R:2], x[..., 1:R:2]) if interleaved else (x[..., :half], x[..., half:R])
-    y1 = (x1.float() * c - x2.float() * s).to(x.dtype)
-    y2 = (x2.float() * c + x1.float() * s).to(x.dtype)
-    out = x.clone()
-    if interleaved:
-        out[..., 0:R:2], out[..., 1:R:2] = y1, y2
-    else:
-        out[..., :half], out[..., half:R] = y1, y2
-    return out
-
-
-def _rope_append_model(k_new, v_new, k_cache, v_cache, cos, sin, lens, cu, max_seqlen_q, block_table, offsets, interleaved,
-                       q=None, q_out=None) -> None:
-    """``pfa_rope_append``'s rule in plain torch, every clamp and drop included: the executable specification, and what
-    ``rope_append`` runs on CPU tensors.  The placement is ``_kv_append_model``'s, one sequence at a time, on that sequence's rotated K
-    rows.  ``lens`` / ``cu`` / ``offsets`` are host lists (``offsets`` or None); the tensors as in ``rope_append``."""
-    paged = block_table is not None
-    Smax = block_table.shape[1] * k_cache.shape[2] if paged else k_cache.shape[2]
-    total, max_pos = k_new.shape[0], cos.shape[0]
-    q_src = None if q is None else q.clone()                                   # q_out may be q
-    k_rot = k_new.clone()                                                      # rows no sequence covers stay as they are, unread
-    for b, n in enumerate(lens):
-        len_b = min(max(n, 0), Smax)
-        if cu is not None:
-            s_b = min(max(cu[b], 0), total)
-            e_b = min(max(cu[b + 1], s_b), total)
-            sq = min(e_b - s_b, max_seqlen_q)
-        else:
-            sq = max_seqlen_q
-        if sq < 1:
-            continue
-        pos = torch.arange(len_b - sq, len_b, dtype=torch.int64) + (0 if offsets is None else offsets[b])
-        pos.clamp_(0, max_pos - 1)                                             # rows in front of key 0 too: their Q is still written
-        c, s = cos[pos], sin[pos]
-        if cu is not None:
-            rows = slice(s_b, s_b + sq)
-            k_rot[rows] = _rope_rotate(k_new[rows], c, s, interleaved)
-            if q is not None:
-                q_out[rows] = _rope_rotate(q_src[rows], c, s, interleaved)
-            one = (k_rot, v_new)
-        else:
-            k_rot[b] = _rope_rotate(k_new[b].transpose(0, 1), c, s, interleaved).transpose(0, 1)
-            if q is not None:
-                q_out[b] = _rope_rotate(q_src[b].transpose(0, 1), c, s, interleaved).transpose(0, 1)
-            one = (k_rot[b:b + 1], v_new[b:b + 1])
-        caches = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
-        _kv_append_model(*one, *caches, [n], None if cu is None else [cu[b], cu[b + 1]], max_seqlen_q,
-                         block_table[b:b + 1] if paged else None)
 
 
 def _fp32_tables(rotary_cos, rotary_sin) -> None:
@@ -1093,7 +1010,7 @@ def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
     _fp32_tables(rotary_cos, rotary_sin)
     others = [rotary_cos, rotary_sin] + [t for t in (q, q_out, pos_offsets) if isinstance(t, torch.Tensor)]
     geo = _append_operands("pfa_rope_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others)
-    ragged, B, Hkv, D, total, max_seqlen_q = geo[:6]
+    ragged, B, D, total, max_seqlen_q = geo.ragged, geo.B, geo.D, geo.total, geo.max_seqlen_q
     rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, D)
     if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
                                     or pos_offsets.shape != (B,) or not pos_offsets.is_contiguous()):
@@ -1126,13 +1043,8 @@ def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
     if pos_offsets is not None:
         a.pos_offsets = pos_offsets.data_ptr()
     if q is not None:
-        if any(t.stride(-1) != 1 for t in (q, q_out)):
-            raise ValueError("last (head_dim) stride must be 1")
-        a.q, a.q_out = q.data_ptr(), q_out.data_ptr()
-        if ragged:
-            a.q_stride_s, a.q_stride_h, a.qo_stride_s, a.qo_stride_h = q.stride(0), q.stride(1), q_out.stride(0), q_out.stride(1)
-        else:
-            (a.q_stride_b, a.q_stride_h, a.q_stride_s), (a.qo_stride_b, a.qo_stride_h, a.qo_stride_s) = q.stride()[:3], q_out.stride()[:3]
+        _set_view(a, "q", q, "sh" if ragged else "bsh")
+        _set_view(a, "q_out", q_out, "sh" if ragged else "bsh")
     _append_launch("pfa_rope_append", a, cache_seqlens, k_new, B)
     return q_out
 
@@ -1185,49 +1097,18 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
         a.lse = lse.data_ptr()
     q_rot = _append_first(*new_rows, q=q, rotary=rotary, descales=descales, **ragged)
     if q_rot is not None:
-        a.q = q_rot.data_ptr()
-        if q_rot.dim() == 3:
-            a.q_stride_s, a.q_stride_h = q_rot.stride(0), q_rot.stride(1)
-        else:
-            a.q_stride_b, a.q_stride_h, a.q_stride_s = q_rot.stride()[:3]
+        _set_view(a, "q", q_rot, "sh" if q_rot.dim() == 3 else "bhs")
         keep.append(q_rot)
     stream = torch.cuda.current_stream(q.device)
-    if key_splits is not None:
-        st = _capi.load().pfa_fa3_prefill_split(C.byref(a), key_splits, C.c_void_p(stream.cuda_stream))
-    elif quant is not None:
-        st = getattr(_capi.load(), entry + "_q8")(C.byref(a), None if ext is None else C.byref(ext), C.byref(quant), C.c_void_p(stream.cuda_stream))
-    elif tree is not None:
-        st = _capi.load().pfa_fa3_decode_tree(C.byref(a), None if ext is None else C.byref(ext), C.byref(tree), C.c_void_p(stream.cuda_stream))
-    else:
-        st = getattr(_capi.load(), entry + "_ex")(C.byref(a), None if ext is None else C.byref(ext), C.c_void_p(stream.cuda_stream))
+    e = None if ext is None else C.byref(ext)
+    # the export that serves the call, and what it takes between the argument block and the stream
+    suffix, middle = (("_split", (key_splits,)) if key_splits is not None else ("_q8", (e, C.byref(quant))) if quant is not None
+                      else ("_tree", (e, C.byref(tree))) if tree is not None else ("_ex", (e,)))
+    st = getattr(_capi.load(), entry + suffix)(C.byref(a), *middle, C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
-    for t in keep:   # tensors made here must outlive the enqueued kernels
-        t.record_stream(stream)
+    if keep:
+        _hold(keep, stream)
     return lse
-
-
-def _attn_merge_model(outs, lses, out, lse_out) -> None:
-    """``pfa_attn_merge``'s rule in plain fp32 torch ops, in part order: the executable specification, and what ``attn_merge`` runs on
-    CPU tensors.  A part whose LSE is -inf is selected away, never multiplied in; a NaN LSE makes the row NaN."""
-    neg_inf = float("-inf")
-    L = torch.stack([l.to(torch.float32) for l in lses])                      # [N, B, H, Sq]
-    live = L > neg_inf                                                        # False for -inf and for NaN
-    m = torch.where(live, L, torch.full_like(L, neg_inf)).max(dim=0).values
-    s = torch.zeros_like(m)
-    acc = torch.zeros(outs[0].shape, dtype=torch.float32, device=m.device)
-    for n, o_n in enumerate(outs):
-        w = torch.exp(L[n] - m)
-        s = torch.where(live[n], s + w, s)
-        acc = torch.where(live[n][..., None], acc + w[..., None] * o_n.to(torch.float32), acc)
-    none = ~(m > neg_inf)                                                     # no part with a visible key
-    o = torch.where(none[..., None], torch.zeros_like(acc), acc / s[..., None])
-    lse = torch.where(none, torch.full_like(m, neg_inf), m + torch.log(s))
-    nan = torch.isnan(L).any(dim=0)
-    o = torch.where(nan[..., None], torch.full_like(o, float("nan")), o)
-    lse = torch.where(nan, torch.full_like(lse, float("nan")), lse)
-    out.copy_(o)                                                              # 16-bit: round to nearest even
-    if lse_out is not None:
-        lse_out.copy_(lse)
 
 
 def attn_merge(outs, lses, *, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
@@ -1287,14 +1168,13 @@ def attn_merge(outs, lses, *, out: Optional[torch.Tensor] = None, out_dtype: Opt
         return out, lse_out
     if dev.type != "cuda":
         raise ValueError("attn_merge needs device tensors (or CPU tensors for the torch model)")
-    ostr = [_bhsd_strides(t) for t in outs]
-    os_ = _bhsd_strides(out)
+    ostr = [_bhsd_strides(t) for t in outs]       # the per-part fields are arrays: they stay with make_attn_merge_args
     a = _capi.make_attn_merge_args(
         n_parts=N, B=B, H=H, Sq=Sq, D=D, dtype_part=_DT[o0.dtype], dtype_out=_DT[odt], device_id=_device_index(dev),
-        o_part=[t.data_ptr() for t in outs], lse_part=[t.data_ptr() for t in lses], o=out.data_ptr(),
+        o_part=[t.data_ptr() for t in outs], lse_part=[t.data_ptr() for t in lses],
         op_stride_b=[x[0] for x in ostr], op_stride_h=[x[1] for x in ostr], op_stride_s=[x[2] for x in ostr],
-        lp_stride_b=[t.stride(0) for t in lses], lp_stride_h=[t.stride(1) for t in lses], lp_stride_s=[t.stride(2) for t in lses],
-        o_stride_b=os_[0], o_stride_h=os_[1], o_stride_s=os_[2])
+        lp_stride_b=[t.stride(0) for t in lses], lp_stride_h=[t.stride(1) for t in lses], lp_stride_s=[t.stride(2) for t in lses])
+    _set_view(a, "o", out)
     if lse_out is not None:
         a.lse_out = lse_out.data_ptr()
         a.lo_stride_b, a.lo_stride_h, a.lo_stride_s = lse_out.stride()
@@ -1313,21 +1193,17 @@ def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *,
     enqueued on the current stream with no host synchronisation; every ``ValueError`` is raised before the first launch.
     ``prefix_key_splits`` (as the caller gave it, already validated) is the prefix pass's ``key_splits`` when that pass is
     ``fa3_prefill_cache``; the decode kernel splits by itself."""
-    try:
-        P = None if isinstance(shared_prefix, bool) else operator.index(shared_prefix)
-    except TypeError:
-        P = None
+    P = _host_int(shared_prefix)
     if P is None:
         raise ValueError(f"shared_prefix must be None or a host integer, got {shared_prefix!r}")
     if key_mask is not None or window is not None:
         raise ValueError("shared_prefix does not combine with key_mask or window: their indices are over the unshifted keys")
     if cache_seqlens is None:
         raise ValueError("shared_prefix needs cache_seqlens: each sequence's own keys are those from the prefix up to its length")
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
-        raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
+    _rank4(q, k_cache, v_cache)
     B, H, Sq, D = q.shape
-    Hkv = k_cache.shape[1]
-    Smax, page_size, _ = _cache_geometry("q", q, B, Hkv, D, k_cache, v_cache, block_table, H)
+    # the geometry first and the readers' other checks (_cache_operands, which repeats it) behind P's own: the order the refusals have
+    Smax, page_size, _ = _cache_geometry("q", q, B, k_cache.shape[1], D, k_cache, v_cache, block_table, H)
     if P < 64 or P % 64:
         raise ValueError(f"shared_prefix {P}: must be a positive multiple of 64 keys")
     if block_table is not None and P % page_size:
@@ -1336,11 +1212,12 @@ def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *,
         raise ValueError(f"shared_prefix {P}: must be below the cache capacity {Smax} (the sequences' own keys lie behind it)")
     if entry == "pfa_fa3_decode" and Sq > 64:
         raise ValueError(f"{entry}: at most 64 query rows per sequence, got {Sq} (fa3_prefill_cache takes any number)")
+    # not _set_cache_seqlens' check: here a wrong shape has the device message, and the two passes repeat that check anyway
     if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.device != q.device or cache_seqlens.shape != (B,):
         raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
-    odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table)[4]
-    if out is not None and (out.shape != (B, H, Sq, D) or out.dtype != odt or out.device != q.device):
-        raise ValueError("out must be a [B, H, Sq, D] tensor of the output dtype on the operands' device")
+    odt = _cache_operands(entry, q, B, H, D, k_cache, v_cache, out_dtype, block_table).odt
+    if out is not None:
+        _out_arg(out, (B, H, Sq, D), odt, q.device)
 
     q_rot = _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=q, rotary=rotary, max_seqlen_q=Sq)
     if q_rot is not None:
@@ -1457,26 +1334,15 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     through the quantising ``kv_append`` first.  Splits and workspace are those of the 16-bit call, and a captured step replays while
     the descales' contents change.  ``window``, ``tree_mask``, ``shared_prefix`` and the rotary arguments are not built for an FP8 cache
     and raise ``ValueError``; bytes at and past a length are never read into a result (NaN bytes there are harmless)."""
-    fp8 = isinstance(k_cache, torch.Tensor) and isinstance(v_cache, torch.Tensor) and (k_cache.dtype == FP8 or v_cache.dtype == FP8)
-    if fp8:
-        for name, given in (("window", window is not None), ("tree_mask", tree_mask is not None), ("shared_prefix", shared_prefix is not None),
-                            ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None)):
-            if given:
-                raise ValueError(f"{name} is not supported with an FP8 (torch.float8_e4m3fn) KV cache: the FP8 decode takes key_mask, "
-                                 "cache_seqlens, block_table, causal and k_new / v_new only")
-        if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
-            raise ValueError("q, k_cache, v_cache must be 4-D ([B,H,Sq,D], [B,Hkv,Smax,D])")
-        quant = _kv_quant_arg("pfa_fa3_decode", k_cache, v_cache, k_descale, v_descale, q.shape[0], k_cache.shape[1], q.device)
-    elif k_descale is not None or v_descale is not None:
-        raise ValueError("k_descale / v_descale go with torch.float8_e4m3fn caches only")
-    else:
-        quant = None
+    fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
+    quant = _fp8_quant("pfa_fa3_decode", "decode takes key_mask, cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
+        ("window", window is not None), ("tree_mask", tree_mask is not None), ("shared_prefix", shared_prefix is not None),
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None)), q_too=True) if fp8 else None
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
     tree = _tree_mask_arg(tree_mask, q, causal, window, shared_prefix)
-    if prefix_key_splits is not None and shared_prefix is None:
-        raise ValueError("prefix_key_splits needs shared_prefix: it splits the keys of the prefix pass")
+    _prefix_splits_need_prefix(prefix_key_splits, shared_prefix)
     if shared_prefix is not None:
         return _shared_prefix_step(fa3_decode, "pfa_fa3_decode", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
                                    key_mask=key_mask, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
@@ -1500,33 +1366,43 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         if cache_seqlens is None:
             cache_seqlens = _mask_bound(km)
     _set_cache_seqlens(a, cache_seqlens, q, keep)
-    ws_bytes = int(_capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)))    # neither a tree nor an FP8 cache changes it
-    if ws_bytes:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-        keep.append(ws)
+    # neither a tree nor an FP8 cache changes the workspace
+    _attach_workspace(a, _capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)), q.device, keep)
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, quant=quant,
                              descales=(k_descale, v_descale) if fp8 else None, max_seqlen_q=Sq)
     return out, lse
 
 
-def _fp8_prefill_quant(entry: str, q, k_cache, v_cache, k_descale, v_descale, B, refused):
-    """What ``fa3_prefill_cache`` and ``fa3_prefill_varlen`` do first about an FP8 cache: -> ``(fp8, quant)``, the ``pfa_fa3_kv_quant`` block
-    or None for 16-bit caches (which refuse descales).  ``refused``: (name, given) of the arguments the FP8 kernels are not built for;
-    a given one raises ``ValueError`` naming it, before anything is enqueued."""
-    fp8 = isinstance(k_cache, torch.Tensor) and isinstance(v_cache, torch.Tensor) and (k_cache.dtype == FP8 or v_cache.dtype == FP8)
-    if not fp8:
-        if k_descale is not None or v_descale is not None:
-            raise ValueError("k_descale / v_descale go with torch.float8_e4m3fn caches only")
-        return False, None
+def _fp8_caches(k_cache, v_cache, k_descale, v_descale) -> bool:
+    """What the attention calls over a KV cache ask first: is this an FP8 cache?  16-bit caches refuse descales."""
+    if isinstance(k_cache, torch.Tensor) and isinstance(v_cache, torch.Tensor) and (k_cache.dtype == FP8 or v_cache.dtype == FP8):
+        return True
+    if k_descale is not None or v_descale is not None:
+        raise ValueError("k_descale / v_descale go with torch.float8_e4m3fn caches only")
+    return False
+
+
+def _fp8_quant(entry: str, takes: str, q, k_cache, v_cache, k_descale, v_descale, B, refused, q_too=False):
+    """... and then, over an FP8 cache: -> the ``pfa_fa3_kv_quant`` block.  ``refused``: (name, given) of the arguments the FP8 kernels
+    are not built for; a given one raises ``ValueError`` naming it and what the family ``takes``, before anything is enqueued.  ``B``:
+    the sequences, None for q's first dim.  ``q_too``: the decode asks 4-D of q here."""
     for name, given in refused:
         if given:
-            raise ValueError(f"{name} is not supported with an FP8 (torch.float8_e4m3fn) KV cache: the FP8 prefill takes cache_seqlens, "
+            raise ValueError(f"{name} is not supported with an FP8 (torch.float8_e4m3fn) KV cache: the FP8 {takes}, "
                              "block_table, causal and k_new / v_new only")
-    if k_cache.dim() != 4 or v_cache.dim() != 4:
+    if q_too:
+        _rank4(q, k_cache, v_cache)
+    elif k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("k_cache, v_cache must be 4-D ([B,Hkv,Smax,D])")
-    return True, _kv_quant_arg(entry, k_cache, v_cache, k_descale, v_descale, B, k_cache.shape[1], q.device)
+    if B is None:
+        B = q.shape[0] if q.dim() else 0
+    return _kv_quant_arg(entry, k_cache, v_cache, k_descale, v_descale, B, k_cache.shape[1], q.device)
+
+
+def _prefix_splits_need_prefix(prefix_key_splits, shared_prefix) -> None:
+    if prefix_key_splits is not None and shared_prefix is None:
+        raise ValueError("prefix_key_splits needs shared_prefix: it splits the keys of the prefix pass")
 
 
 def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: Optional[torch.Tensor] = None,
@@ -1595,16 +1471,17 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     built for an FP8 cache and raise ``ValueError`` naming the argument before anything is enqueued; bytes at and past a length are
     never read into a result (NaN bytes there are harmless).  Over a ``PagedKVCache``:
     ``k, v, kw = cache.operands(slots); fa3_prefill_cache(q, k, v, **kw)``."""
-    fp8, quant = _fp8_prefill_quant("pfa_fa3_prefill", q, k_cache, v_cache, k_descale, v_descale, q.shape[0] if q.dim() else 0, (
+    fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
+    quant = _fp8_quant("pfa_fa3_prefill", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
         ("window", window is not None), ("shared_prefix", shared_prefix is not None), ("key_splits", key_splits is not None),
         ("prefix_key_splits", prefix_key_splits is not None),
-        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None)))
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None))
+    ) if fp8 else None
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     splits = _key_splits_arg("key_splits", key_splits)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
-    if prefix_key_splits is not None and shared_prefix is None:
-        raise ValueError("prefix_key_splits needs shared_prefix: it splits the keys of the prefix pass")
+    _prefix_splits_need_prefix(prefix_key_splits, shared_prefix)
     if splits is not None and window is not None:
         raise ValueError("key_splits does not combine with window: the windowed kernel has no split over keys")
     if shared_prefix is not None:
@@ -1618,11 +1495,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep)
     if splits is not None:
-        ws_bytes = int(_capi.load().pfa_fa3_prefill_split_workspace_bytes(C.byref(a), splits))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-            keep.append(ws)
+        _attach_workspace(a, _capi.load().pfa_fa3_prefill_split_workspace_bytes(C.byref(a), splits), q.device, keep)
     lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, key_splits=splits, quant=quant,
                              descales=(k_descale, v_descale) if fp8 else None, max_seqlen_q=q.shape[2])
@@ -1672,41 +1545,36 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     the FP8 cache at any descales.  ``k_new=, v_new=`` go through the quantising ``kv_append``; ``window`` and the rotary arguments raise
     ``ValueError`` naming the argument before anything is enqueued."""
     B_cu = cu_seqlens_q.numel() - 1 if isinstance(cu_seqlens_q, torch.Tensor) else 0
-    fp8, quant = _fp8_prefill_quant("pfa_fa3_prefill_varlen", q, k_cache, v_cache, k_descale, v_descale, B_cu, (
+    fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
+    quant = _fp8_quant("pfa_fa3_prefill_varlen", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, B_cu, (
         ("window", window is not None),
-        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None)))
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None))
+    ) if fp8 else None
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q must be 3-D ([total_q,H,D]) and k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
-    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32:
-        raise ValueError("cu_seqlens_q must be an int32 tensor")
-    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
-        raise ValueError(f"cu_seqlens_q must be [B + 1], got {tuple(cu_seqlens_q.shape)}")
+    B = _cu_seqlens_arg(cu_seqlens_q, contiguous=False)
     total_q, H, D = q.shape
-    B = cu_seqlens_q.numel() - 1
-    Hkv, Smax, page_size, num_pages, odt = _cache_operands("pfa_fa3_prefill_varlen", q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8)
+    geo = _cache_operands("pfa_fa3_prefill_varlen", q, B, H, D, k_cache, v_cache, out_dtype, block_table, fp8)
     if not cu_seqlens_q.is_cuda or cu_seqlens_q.device != q.device:
         raise ValueError("cu_seqlens_q must live on the operands' device (there is no CPU path)")
-    if not cu_seqlens_q.is_contiguous():
-        raise ValueError("cu_seqlens_q must be contiguous")
-    if q.stride(2) != 1 and D != 1:
+    _cu_seqlens_arg(cu_seqlens_q, layout=False)
+    if q.stride(2) != 1 and D != 1:      # (ahead of out's own message; _set_view asks again)
         raise ValueError("last (head_dim) stride must be 1")
     if out is None:
-        out = torch.empty((total_q, H, D), dtype=odt, device=q.device)
-    elif out.shape != (total_q, H, D) or out.dtype != odt or out.device != q.device or (out.stride(2) != 1 and D != 1):
+        out = torch.empty((total_q, H, D), dtype=geo.odt, device=q.device)
+    elif out.shape != (total_q, H, D) or out.dtype != geo.odt or out.device != q.device or (out.stride(2) != 1 and D != 1):
         raise ValueError("out must be a [total_q, H, D] tensor of the output dtype on the operands' device, head dim contiguous")
-    ks, vs = _bhsd_strides(k_cache), _bhsd_strides(v_cache)
     a = _capi.make_prefill_varlen_args(
-        q=q.data_ptr(), k_cache=k_cache.data_ptr(), v_cache=v_cache.data_ptr(), o=out.data_ptr(), cu_seqlens_q=cu_seqlens_q.data_ptr(),
-        q_stride_s=q.stride(0), q_stride_h=q.stride(1), o_stride_s=out.stride(0), o_stride_h=out.stride(1),
-        k_stride_b=ks[0], k_stride_h=ks[1], k_stride_s=ks[2], v_stride_b=vs[0], v_stride_h=vs[1], v_stride_s=vs[2],
-        B=B, H=H, Hkv=Hkv, total_q=total_q, max_seqlen_q=int(max_seqlen_q), Smax=Smax, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[odt],
-        causal=1 if causal else 0, softmax_scale=_scale(softmax_scale, D),
+        cu_seqlens_q=cu_seqlens_q.data_ptr(), B=B, H=H, Hkv=geo.Hkv, total_q=total_q, max_seqlen_q=int(max_seqlen_q), Smax=geo.Smax, D=D,
+        dtype_in=_DT[q.dtype], dtype_out=_DT[geo.odt], causal=1 if causal else 0, softmax_scale=_scale(softmax_scale, D),
         device_id=_device_index(q.device))
-    if block_table is not None:
-        a.block_table, a.block_table_stride_b = block_table.data_ptr(), block_table.stride(0)
-        a.page_size, a.num_pages = page_size, num_pages
+    _set_view(a, "q", q, "sh")
+    _set_view(a, "o", out, "sh")
+    _set_view(a, "k_cache", k_cache)
+    _set_view(a, "v_cache", v_cache)
+    _set_block_table(a, block_table, geo.page_size, geo.num_pages)
     keep = []
     _set_cache_seqlens(a, cache_seqlens, q, keep, B)
     lse = _finish_cache_call("pfa_fa3_prefill_varlen", a, ext, q, (H, total_q) if return_lse else None, keep,
@@ -1717,73 +1585,6 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # Packed variable-length attention for training (include/pfa_hip.h, pfa_fa3_varlen_args): flash-attn's flash_attn_varlen_func
-
-def _packed_seqs(cu_q, cu_k, total_q: int, total_k: int, max_seqlen_q: int, max_seqlen_k: int):
-    """The kernels' reading of two host ``cu_seqlens`` lists: per sequence ``(s_q, Sq_b, s_k, Sk_b)`` with ``s = clamp(cu[b], 0,
-    total)``, ``e = clamp(cu[b + 1], s, total)``, ``S_b = min(e - s, max_seqlen)`` -- the rule of ``pfa_fa3_prefill_varlen_args``."""
-    def one(cu, b, total, cap):
-        s = min(max(cu[b], 0), total)
-        e = min(max(cu[b + 1], s), total)
-        return s, min(e - s, cap)
-    return [one(cu_q, b, total_q, max_seqlen_q) + one(cu_k, b, total_k, max_seqlen_k) for b in range(len(cu_q) - 1)]
-
-
-def _packed_probs(qb, kb, lse_b, causal: bool, scale: float):
-    """fp32 scores of one sequence ``[H, Sq_b, Sk_b]`` (top-left causal: row i sees key j iff j <= i) and, given the rows' LSE, the
-    softmax weights ``exp(s - lse)`` (0 where masked or where the row has no key)."""
-    s = torch.matmul(qb, kb.transpose(1, 2)) * scale
-    if causal:
-        i, j = torch.arange(s.shape[1])[:, None], torch.arange(s.shape[2])[None, :]
-        s = s.masked_fill(j > i, float("-inf"))
-    if lse_b is None:
-        return s, None
-    p = torch.exp(s - lse_b[:, :, None])
-    return s, torch.where(torch.isfinite(lse_b)[:, :, None] & torch.isfinite(s), p, torch.zeros_like(p))
-
-
-def _varlen_forward_model(q, k, v, out, lse, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale) -> None:
-    """``pfa_fa3_varlen_fwd``'s rule in plain torch, per sequence in fp32, every clamp included: the executable specification, and
-    what ``fa3_varlen_forward`` runs on CPU tensors.  ``cu_q`` / ``cu_k`` are host lists; writes the covered rows of out / lse only."""
-    g = q.shape[1] // k.shape[1]
-    for sq, nq, sk, nk in _packed_seqs(cu_q, cu_k, q.shape[0], k.shape[0], max_seqlen_q, max_seqlen_k):
-        if nq == 0:
-            continue
-        if nk == 0:                                                     # rows without a key: O = 0, LSE = -inf
-            out[sq:sq + nq] = 0
-            if lse is not None:
-                lse[:, sq:sq + nq] = float("-inf")
-            continue
-        qb = q[sq:sq + nq].float().transpose(0, 1)
-        kb, vb = (t[sk:sk + nk].float().transpose(0, 1).repeat_interleave(g, dim=0) for t in (k, v))
-        s, _ = _packed_probs(qb, kb, None, causal, scale)
-        lse_b = torch.logsumexp(s, dim=-1)                              # (top-left causal: every row sees key 0)
-        out[sq:sq + nq] = torch.matmul(torch.exp(s - lse_b[:, :, None]), vb).transpose(0, 1).to(out.dtype)
-        if lse is not None:
-            lse[:, sq:sq + nq] = lse_b
-
-
-def _varlen_backward_model(q, k, v, out, dout, lse, dq, dk, dv, cu_q, cu_k, max_seqlen_q, max_seqlen_k, causal, scale) -> None:
-    """``pfa_fa3_varlen_bwd``'s rule in plain torch (see ``_varlen_forward_model``): writes rows ``[s_q, s_q + Sq_b)`` of dq and
-    ``[s_k, s_k + Sk_b)`` of dk / dv of every sequence, and nothing else."""
-    Hkv = k.shape[1]
-    g = q.shape[1] // Hkv
-    for sq, nq, sk, nk in _packed_seqs(cu_q, cu_k, q.shape[0], k.shape[0], max_seqlen_q, max_seqlen_k):
-        if nq == 0 or nk == 0:                                          # no key: dQ = 0; no row: dK = dV = 0
-            dq[sq:sq + nq] = 0
-            dk[sk:sk + nk] = 0
-            dv[sk:sk + nk] = 0
-            continue
-        qb, ob, gb = (t[sq:sq + nq].float().transpose(0, 1) for t in (q, out, dout))
-        kb, vb = (t[sk:sk + nk].float().transpose(0, 1).repeat_interleave(g, dim=0) for t in (k, v))
-        _, p = _packed_probs(qb, kb, lse[:, sq:sq + nq], causal, scale)
-        delta = (gb * ob).sum(-1)
-        ds = p * (torch.matmul(gb, vb.transpose(1, 2)) - delta[:, :, None])
-        dq[sq:sq + nq] = (torch.matmul(ds, kb) * scale).transpose(0, 1).to(dq.dtype)
-        dkb = torch.matmul(ds.transpose(1, 2), qb) * scale              # [H, Sk_b, D] -> summed over each group of query heads
-        dvb = torch.matmul(p.transpose(1, 2), gb)
-        dk[sk:sk + nk] = dkb.reshape(Hkv, g, nk, -1).sum(1).transpose(0, 1).to(dk.dtype)
-        dv[sk:sk + nk] = dvb.reshape(Hkv, g, nk, -1).sum(1).transpose(0, 1).to(dv.dtype)
-
 
 def _varlen_operands(entry: str, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
     """What the packed calls check about their operands -> ``(B, H, Hkv, D, total_q, total_k, max_seqlen_q, max_seqlen_k)``."""
@@ -1809,17 +1610,6 @@ def _varlen_operands(entry: str, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen
     return cu_seqlens_q.numel() - 1, H, Hkv, D, total_q, total_k, max_seqlen_q, max_seqlen_k
 
 
-def _packed_fields(fields) -> dict:
-    """(field prefix, ``[total, heads, D]`` tensor) pairs -> the pointer and ``*_stride_s`` / ``*_stride_h`` fields (``dout``: ``do_``)."""
-    kw = {}
-    for name, t in fields:
-        if t.stride(2) != 1 and t.shape[2] != 1:
-            raise ValueError("last (head_dim) stride must be 1")
-        pre = "do" if name == "dout" else name
-        kw[name], kw[f"{pre}_stride_s"], kw[f"{pre}_stride_h"] = t.data_ptr(), t.stride(0), t.stride(1)
-    return kw
-
-
 def _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale) -> None:
     """One ``pfa_fa3_varlen_fwd`` on q's current stream into the caller's ``out`` (``[total_q, H, D]``-shaped, any row / head strides)
     and ``lse`` (contiguous fp32 ``[H, total_q]`` or None)."""
@@ -1831,7 +1621,9 @@ def _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causa
     a = _capi.make_varlen_args(
         cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(), B=B, H=H, Hkv=Hkv, total_q=total_q, total_k=total_k,
         max_seqlen_q=max_q, max_seqlen_k=max_k, D=D, dtype_in=_DT[q.dtype], dtype_out=_DT[out.dtype], causal=1 if causal else 0,
-        softmax_scale=_scale(softmax_scale, D), device_id=_device_index(q.device), **_packed_fields((("q", q), ("k", k), ("v", v), ("o", out))))
+        softmax_scale=_scale(softmax_scale, D), device_id=_device_index(q.device))
+    for name, t in (("q", q), ("k", k), ("v", v), ("o", out)):
+        _set_view(a, name, t, "sh")
     if lse is not None:
         if lse.shape != (H, total_q) or lse.dtype != torch.float32 or not lse.is_contiguous():
             raise ValueError("lse must be contiguous fp32 [H, total_q]")
@@ -1895,8 +1687,9 @@ def _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seq
     a = _capi.make_varlen_bwd_args(
         lse=lse.data_ptr(), delta=delta.data_ptr(), cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(),
         B=B, H=H, Hkv=Hkv, total_q=total_q, total_k=total_k, max_seqlen_q=max_q, max_seqlen_k=max_k, D=D, dtype=_DT[q.dtype],
-        dtype_grad=_DT[dq.dtype], causal=1 if causal else 0, softmax_scale=_scale(softmax_scale, D), device_id=_device_index(q.device),
-        **_packed_fields((("q", q), ("k", k), ("v", v), ("o", out), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv))))
+        dtype_grad=_DT[dq.dtype], causal=1 if causal else 0, softmax_scale=_scale(softmax_scale, D), device_id=_device_index(q.device))
+    for name, t in (("q", q), ("k", k), ("v", v), ("o", out), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+        _set_view(a, name, t, "sh")
     stream = torch.cuda.current_stream(q.device)
     st = _capi.load().pfa_fa3_varlen_bwd(C.byref(a), C.c_void_p(stream.cuda_stream))
     _raise_status("pfa_fa3_varlen_bwd", st, null_too=True)

@@ -145,6 +145,43 @@ def test_drop_mask_rules_of_the_tensor_layer():
         ops._drop_mask_ptr(good, B, H, Sq, Sk, like.bfloat16())               # dropout runs on the fp32 kernels only
 
 
+def test_stride_filler_puts_every_axis_in_its_field():
+    """``ops._set_view`` (and ``ops._set_strides`` on the dense blocks) write a tensor's pointer and, per letter of the block's axis order,
+    the stride of the axis that letter names -- on views whose strides all differ, so that a slip in the order shows.  Nothing else in
+    the block is touched, and a head dim that is not contiguous is refused with the one message every path has."""
+    from photonic_flash_attention_amd import ops
+    t4 = torch.zeros(2, 5, 3, 8).permute(0, 2, 1, 3)               # [B,H,S,D] = [2,3,5,8] with strides 120, 8, 24, 1
+    t3 = torch.zeros(3, 5, 8).permute(1, 0, 2)                     # packed [S,H,D] = [5,3,8] with strides 8, 40, 1
+    assert len(set(t4.stride())) == 4 and len(set(t3.stride())) == 3
+    dim4, dim3 = dict(b=0, h=1, s=2), dict(s=0, h=1)
+    cases = [(_capi.PfaFa3DecodeArgs, "bhs", t4, dim4, dict(q="q", k_cache="k", v_cache="v", o="o")),
+             (_capi.PfaFa3PrefillVarlenArgs, "sh", t3, dim3, dict(q="q", o="o")),
+             (_capi.PfaFa3PrefillVarlenArgs, "bhs", t4, dim4, dict(k_cache="k", v_cache="v")),
+             (_capi.PfaKvAppendArgs, "bsh", t4, dim4, dict(k_new="kn", v_new="vn")),
+             (_capi.PfaKvAppendArgs, "sh", t3, dim3, dict(k_new="kn", v_new="vn")),      # the packed rows: no batch stride is written
+             (_capi.PfaKvAppendArgs, "bhs", t4, dim4, dict(k_cache="k", v_cache="v"))]
+    for cls, axes, t, dim, fields in cases:
+        for name, pre in fields.items():
+            a = cls()
+            ops._set_view(a, name, t, axes)
+            want = {name: t.data_ptr()}
+            want.update({f"{pre}_stride_{x}": t.stride(dim[x]) for x in axes})
+            got = {f: getattr(a, f) for f, _ in cls._fields_ if getattr(a, f)}
+            assert got == want, (cls.__name__, name, axes)
+    for cls, names in ((_capi.PfaFa3Args, ("q", "k", "v", "o")), (_capi.PfaFa3BwdArgs, ("q", "k", "v", "o", "dout", "dq", "dk", "dv"))):
+        for name in names:
+            a = cls()
+            ops._set_strides(a, ((name, t4),))
+            pre = "do" if name == "dout" else name
+            want = {name: t4.data_ptr(), f"{pre}_stride_b": 120, f"{pre}_stride_h": 8, f"{pre}_stride_s": 24}
+            assert {f: getattr(a, f) for f, _ in cls._fields_ if getattr(a, f)} == want, (cls.__name__, name)
+    for bad, axes in ((t4[..., ::2], "bhs"), (t4[..., ::2], "bsh"), (t3[..., ::2], "sh")):
+        with pytest.raises(ValueError, match=r"last \(head_dim\) stride must be 1"):
+            ops._set_view(_capi.PfaKvAppendArgs(), "k_new", bad, axes)
+    with pytest.raises(ValueError, match=r"last \(head_dim\) stride must be 1"):
+        ops._set_strides(_capi.PfaFa3Args(), (("q", t4[..., ::2]),))
+
+
 def test_production_library_refuses_development_variants(lib):
     """flags bits 8..15: 0 or one of the three production kernel selectors; every other value is refused.  The round-1 schedule
     experiments and timing-only ablations that once lived behind these bits are in git history and in the profile logs, not in the tree."""

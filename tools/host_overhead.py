@@ -33,3 +33,18 @@ for _ in range(N // 10):
     g.replay()
 torch.cuda.synchronize()
 print(f"graph (10 calls per replay): {(time.perf_counter() - t) / N * 1e6:.1f} us/call")
+# one eager serving step over a paged cache: the append and the decode behind it (two launches), Hkv 2, 2 pages of 64 keys per sequence
+kp, vp = (torch.randn(4, 64, 2, D, device=dev).to(torch.bfloat16).transpose(1, 2) for _ in range(2))
+table = torch.tensor([[0, 1], [2, 3]], dtype=torch.int32, device=dev)
+lens = torch.tensor([100, 128], dtype=torch.int32, device=dev)
+q1, k1, v1 = (torch.randn(B, 1, h, D, device=dev).to(torch.bfloat16).permute(0, 2, 1, 3) for h in (H, 2, 2))
+step = lambda: ops.fa3_decode(q1, kp, vp, cache_seqlens=lens, block_table=table, k_new=k1, v_new=v1)
+for _ in range(50):
+    step()
+torch.cuda.synchronize()
+t = time.perf_counter()
+for _ in range(N):
+    step()
+t_enq = (time.perf_counter() - t) / N
+torch.cuda.synchronize()
+print(f"paged decode step (k_new / v_new): enqueue {t_enq * 1e6:.1f} us/step, end-to-end {(time.perf_counter() - t) / N * 1e6:.1f} us/step")
