@@ -2,7 +2,9 @@
 oracle (outputs, LSE and autograd gradients) where the two overlap -- no mask, causal, seqlens_k --, against a direct eager
 ``dropout(softmax) @ v`` with a fixed keep-mask, its conventions for rows that see no key, its grouped-head gradient, and the two checks
 against outputs they must reject.  The same for the attention-weights pass: ``weights_reference`` against a per-row loop, ``weights_bound``
-against an fp32 emulation of the kernel's expression, ``check_weights`` and ``check_guards`` against what they must reject."""
+against an fp32 emulation of the kernel's expression, ``check_weights`` and ``check_guards`` against what they must reject.  And for the
+16-bit backward (the last section): ``backward_given`` against the reference's gradients, ``backward_bound`` against an emulation of the
+kernels' rounding points -- the honest one inside it, five wrong ones outside -- and against the whole-tensor tolerance it replaces."""
 
 from __future__ import annotations
 
@@ -11,8 +13,9 @@ import torch
 
 import math
 
-from dense_testlib import (INF, LOG2E, NAN16, NAN32, check_forward, check_grads, check_guards, check_weights, guarded_weights, reference,
-                           seen, visible, weights_bound, weights_reference)
+from dense_testlib import (BWD16_CASES, INF, LOG2E, MUTANTS, NAN16, NAN32, TOL16, backward_bound, backward_given, backward_model,
+                           bwd16_isolated, check_forward, check_grads, check_grads16, check_guards, check_weights, guarded_weights,
+                           reference, seen, visible, weights_bound, weights_reference)
 from oracle import fa3_oracle as orc
 from photonic_flash_attention_amd import synth
 
@@ -277,3 +280,102 @@ def test_check_guards_rejects_a_stray_store_and_a_missing_one(wdt, pat):
     missing[1, 1, 32 + Sq - 1, off + Sk - 1] = pat
     with pytest.raises(AssertionError):
         check_guards(missing, Hq, Sq, Sk, off)
+
+
+# --- the 16-bit backward -------------------------------------------------------------------------------------------------------------
+
+DT16 = [torch.bfloat16, torch.float16]
+DT16_IDS = ["bf16", "fp16"]
+CASE_IDS = [f"case{min(i + 1, 12)}{'b' if i == 12 else ''}" for i in range(len(BWD16_CASES))]
+
+
+@pytest.mark.parametrize("idx", [0, 2, 3, 4, 6, 9, 10], ids=lambda i: CASE_IDS[i])
+def test_backward_given_with_exact_forward_operands_is_the_gradient(idx):
+    """With the exact fp64 ``o`` and ``lse`` the formula the kernels evaluate is the gradient: ``reference``'s autograd, to 1e-12 relative."""
+    p = bwd16_isolated(idx, torch.bfloat16)
+    kw = p["kw"]
+    keep = kw["mask"] if "mask" in kw else (kw["key_mask"][:, None, None, :] if "key_mask" in kw else None)
+    o, lse, *true = reference(p["q"], p["k"], p["v"], causal=p["causal"], seqlens=kw.get("seqlens_k"), keep=keep, scale=p["scale"], dout=p["dout"])
+    dq, dk, dv, parts = backward_given(p["q"], p["k"], p["v"], o, p["dout"], lse, vis=p["vis"], scale=p["scale"])
+    for name, got, want in zip(("dq", "dk", "dv"), (dq, dk, dv), true):
+        assert got.dtype == torch.float64 and tuple(got.shape) == tuple(want.shape), name
+        assert float((got - want).abs().max()) <= 1e-12 * max(1.0, float(want.abs().max())), name
+    assert bool((parts["P"][~p["vis"]] == 0).all()) and float((parts["P"].sum(-1)[p["row_seen"]] - 1).abs().max()) <= 1e-12
+    assert bool((dq[~p["row_seen"]] == 0).all()) and bool((dk[~p["key_seen"]] == 0).all()) and bool((dv[~p["key_seen"]] == 0).all())
+
+
+@pytest.mark.parametrize("dt", DT16, ids=DT16_IDS)
+@pytest.mark.parametrize("idx", range(len(BWD16_CASES)), ids=CASE_IDS)
+def test_honest_model_of_the_backward_stays_inside_its_bound(idx, dt):
+    """The emulation of the kernels' rounding points is within ``backward_bound`` at every element of every GPU case (the worst ratio is
+    printed: 0.63 bf16 / 0.50 fp16 over the cases), the bound is exactly zero where nothing is seen, and the new check implies the one it
+    stands beside: no element's bound exceeds ``TOL16 * max|ref|`` of its gradient (at most 1.48e-2 bf16, 2.1e-3 fp16 over the cases)."""
+    p = bwd16_isolated(idx, dt)
+    model = backward_model(p["q"], p["k"], p["v"], p["o16"], p["dout"], p["lse32"], vis=p["vis"], scale=p["scale"], dtype=dt)
+    worst = check_grads16(model, p["given"], p["bounds"], p["row_seen"], p["key_seen"], f"{CASE_IDS[idx]} model")
+    assert max(worst) <= 1.0
+    for name, b, live, true in zip(("dq", "dk", "dv"), p["bounds"], (p["row_seen"], p["key_seen"], p["key_seen"]), p["true"]):
+        assert bool((b[~live] == 0).all()) and bool((b[live] > 0).all()) and bool(torch.isfinite(b).all()), name
+        top = float(true.abs().max())
+        if top > 0:                                        # (case 1: one key, dq and dk are exactly zero)
+            print(f"{CASE_IDS[idx]} {name}: max bound / max|ref| {float(b.max()) / top:.3e} (whole-tensor tolerance {TOL16[dt]:.1e})")
+            assert float(b.max()) <= TOL16[dt] * top, name
+    assert idx != 0 or (float(p["true"][0].abs().max()) == 0 and float(p["true"][1].abs().max()) == 0)
+
+
+# where a mutant changes nothing that a check could see
+NOT_APPLICABLE = {(0, "dq_dk_scaled"), (0, "last_key_dropped"),                     # one key: dq = dk = 0, dS = 0
+                  (5, "last_key_dropped"), (7, "last_key_dropped"),                  # causal with Sk > Sq: no row sees the last key
+                  (4, "diagonal_dropped")}                                           # Sq > Sk: the last 32 rows have no diagonal key
+NOT_APPLICABLE |= {(i, "diagonal_dropped") for i, c in enumerate(BWD16_CASES) if not c[6]}
+# cases 3 and 4: the worst err / bound of a CPU prototype of this bound, halved for ROUND16's u
+REQUIRED = {"delta0_last_rows": 28.0, "p_scaled_last_block": 5.8, "dq_dk_scaled": 2.6, "last_key_dropped": 10.0, "diagonal_dropped": 24.0}
+
+
+@pytest.mark.parametrize("dt", DT16, ids=DT16_IDS)
+@pytest.mark.parametrize("idx, mutant", [(i, m) for i in range(len(BWD16_CASES)) for m in MUTANTS if (i, m) not in NOT_APPLICABLE],
+                         ids=lambda x: CASE_IDS[x] if isinstance(x, int) else x)
+def test_wrong_backward_models_are_over_the_bound(idx, mutant, dt):
+    """Each wrong kernel that the whole-tensor tolerance lets through puts at least one element over its bound wherever it changes anything,
+    and by the prototype's margin at case 3 (causal, 300 x 300, D 128) and case 4 (full, grouped heads)."""
+    p = bwd16_isolated(idx, dt)
+    model = backward_model(p["q"], p["k"], p["v"], p["o16"], p["dout"], p["lse32"], vis=p["vis"], scale=p["scale"], dtype=dt, mutant=mutant)
+    worst = 0.0
+    for got, ref, b in zip(model, p["given"], p["bounds"]):
+        err = (got.double() - ref).abs()
+        worst = max(worst, float(torch.where(err > 0, err / b, torch.zeros((), dtype=torch.float64)).max()))
+    print(f"{CASE_IDS[idx]} {mutant}: worst err / bound {worst:.2f}")
+    assert worst > (REQUIRED[mutant] if idx in (2, 3) else 1.0)
+    with pytest.raises(AssertionError):
+        check_grads16(model, p["given"], p["bounds"], p["row_seen"], p["key_seen"])
+
+
+def test_check_grads16_rejects_what_it_must():
+    p = bwd16_isolated(9, torch.float16)                   # rows 5 and 100..132 see nothing
+    good = tuple(g.float() for g in p["given"])
+    args = (p["given"], p["bounds"], p["row_seen"], p["key_seen"])
+    assert max(check_grads16(good, *args, "good")) <= 1.0
+
+    def fails(i, t):
+        gs = list(good)
+        gs[i] = t
+        with pytest.raises(AssertionError):
+            check_grads16(gs, *args)
+
+    bad = good[0].clone(); bad[0, 1, 5, 3] = 1e-30
+    fails(0, bad)                                          # dq of a row that sees nothing
+    bad = good[0].clone(); bad[0, 0, 7, 1] = float("nan")
+    fails(0, bad)
+    b1 = torch.where(p["bounds"][1] > 0, p["bounds"][1], torch.full((), INF, dtype=torch.float64))
+    at = tuple(int(x) for x in torch.nonzero(b1 == b1.min())[0])                    # the seen key element with the tightest bound
+    bad = good[1].clone(); bad[at] += 1.5 * float(p["bounds"][1][at])
+    fails(1, bad)                                          # one element over its own bound, far below the tensor's largest
+    assert 1.5 * float(p["bounds"][1][at]) < 0.1 * TOL16[torch.float16] * float(p["given"][1].abs().max())
+    fails(2, good[2].double())                             # not an fp32 store
+    fails(2, good[2][:, :1])                               # a wrong shape
+    # a key nobody sees: case 6's keys past Sq
+    p = bwd16_isolated(5, torch.bfloat16)
+    good = [g.float() for g in p["given"]]
+    good[2][0, 0, 400, 0] = 1e-30
+    with pytest.raises(AssertionError):
+        check_grads16(good, p["given"], p["bounds"], p["row_seen"], p["key_seen"])
