@@ -26,6 +26,9 @@
  * cache with one fp32 descale per (sequence, K/V head), and the append that quantises a step's 16-bit rows into it.
  * v9, additive: pfa_fa3_prefill_q8* and pfa_fa3_prefill_varlen_q8* -- the forward over an FP8 (e4m3fn) KV cache, uniform and ragged,
  * contiguous and paged: chunked and prefix-cached prefill, speculative steps past 64 rows and mixed batches on one-byte pages.
+ * v9, additive: pfa_fa3_sinks and pfa_fa3_decode_sink*, pfa_fa3_prefill_sink*, pfa_fa3_prefill_varlen_sink*, pfa_fa3_prefill_split_sink* --
+ * attention sinks over a 16-bit KV cache: one learned fp32 value per query head in every row's softmax denominator, in the decode, the
+ * forward (uniform, ragged, windowed) and the split over keys.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):
@@ -1066,6 +1069,64 @@ int pfa_fa3_prefill_varlen_q8_check(const pfa_fa3_prefill_varlen_args* a, const 
 int pfa_fa3_prefill_varlen_q8(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream);
 int pfa_fa3_prefill_varlen_q8_describe(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant,
                                        char* buf, size_t n);
+
+/*
+ * Attention sinks over a 16-bit KV cache (ABI v9, additive): pfa_fa3_decode_ex, pfa_fa3_prefill_ex, pfa_fa3_prefill_varlen_ex and
+ * pfa_fa3_prefill_split with one learned value per QUERY head in every row's softmax denominator (the GPT-OSS-style layer: grouped
+ * heads, D = 64, full and sliding-window layers, a sink per head).  pfa_fa3_cache_ext is full, so the sink has a block of its own.
+ *
+ * sinks[h] is in the units of the scaled scores x_ij = softmax_scale * <q_i, k_j> (natural log); it is NOT multiplied by
+ * softmax_scale.  With V_i the keys row i of head h sees after lengths, causal rule, window and key mask:
+ *     den_i = sum_{j in V_i} exp(x_ij) + exp(sinks[h]),   O_i = sum_{j in V_i} exp(x_ij) v_j / den_i,   LSE_i = log(den_i)
+ * -- one extra key with score sinks[h] and a zero value row; the sink is inside the LSE.  A row with no visible key (length 0, rows in
+ * front of key 0, everything masked) gets O = 0 exactly and LSE = sinks[h], not -inf.  sinks[h] = -inf: head h has the O bits of the
+ * sink-less call and -inf in the LSE where that call has it.  +inf or NaN in `sinks` is the caller's error: device data, not validated;
+ * that head's rows are unspecified, other heads are unaffected, and the call does only arithmetic with it.
+ *
+ * Merging: because the LSE contains the sink, pfa_attn_merge of a sink-carrying part with sink-less parts over disjoint keys is the
+ * sink-carrying result over the union.  Inside these calls exactly ONE part carries it: of the decode's key splits the partial of split 0
+ * of each item, of pfa_fa3_prefill_split_sink the partial of split 0 of each q block.  That part writes O = 0, LSE = sinks[h] when it has
+ * no key of its own; the others write -inf as before.  fa3_decode_combine_kernel and pfa_attn_merge are reused unchanged.  (A caller that
+ * cuts a shared prefix off gives the sinks to ONE of its passes.)
+ *
+ * The sink is read by ordinary loads and written nowhere: no atomics, no workspace beyond the sink-less call's.  Workgroups, split
+ * count and workspace bytes are the sink-less call's, from host shapes alone; the pointer is a launch argument and its contents are
+ * read on the device, so a captured graph replays while the sink values change.  A tree mask (pfa_fa3_decode_tree) and an FP8 cache
+ * (the *_q8 calls) take no sinks.
+ *
+ * `sinks` NULL: the call IS its sink-less sibling (pfa_fa3_decode_ex, pfa_fa3_prefill_ex, pfa_fa3_prefill_varlen_ex,
+ * pfa_fa3_prefill_split) in every respect -- status, workspace, kernel function, grid, bits.  With a block, field rules in the order
+ * their errors are reported: sinks->size wrong -> PFA_ERR_STRUCT_SIZE; sinks->flags != 0 -> PFA_ERR_FLAGS; sinks->sinks NULL ->
+ * PFA_ERR_NULL; not 4-byte aligned -> PFA_ERR_ALIGN; then the unchanged rules of the sibling's _check, which these calls ask.  The
+ * workspace queries leave out the two rules about the pointer and answer 0 where a rule fails.
+ */
+typedef struct pfa_fa3_sinks {
+    uint32_t size;      /* = sizeof(pfa_fa3_sinks) */
+    uint32_t flags;     /* must be 0 */
+    const float* sinks; /* [H] fp32, device, 4-byte aligned; units of the scaled scores */
+} pfa_fa3_sinks;
+
+size_t pfa_fa3_decode_sink_workspace_bytes(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks);
+int pfa_fa3_decode_sink_check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks);
+int pfa_fa3_decode_sink(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, void* stream);
+/* As the sibling's describe, with "_sink" in the name behind "_win" and in front of "+combine", "_varlen", "_split{N}+merge" and "_paged":
+ * "fa3_decode_..._o16[_win]_sink[+combine][_paged]", "fa3_prefill_..._causal[_win]_sink[_varlen][_split{N}+merge][_paged]".  -> the
+ * sibling's workgroups (and split count in *nsplit), or a pfa_status. */
+int pfa_fa3_decode_sink_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, char* buf, size_t n,
+                                 int32_t* nsplit);
+int pfa_fa3_prefill_sink_check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks);
+int pfa_fa3_prefill_sink(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, void* stream);
+int pfa_fa3_prefill_sink_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, char* buf, size_t n);
+int pfa_fa3_prefill_varlen_sink_check(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks);
+int pfa_fa3_prefill_varlen_sink(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, void* stream);
+int pfa_fa3_prefill_varlen_sink_describe(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, char* buf,
+                                         size_t n);
+/* key_splits as in pfa_fa3_prefill_split; a count that resolves to 1 is pfa_fa3_prefill_sink without an extension block */
+size_t pfa_fa3_prefill_split_sink_workspace_bytes(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks);
+int pfa_fa3_prefill_split_sink_check(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks);
+int pfa_fa3_prefill_split_sink(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, void* stream);
+int pfa_fa3_prefill_split_sink_describe(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, char* buf, size_t n,
+                                        int32_t* nsplit);
 
 /*
  * Measurement aid (bench.py, roofline.probe_tflops; not on the hot path): enqueue a bare v_mfma_f32_32x32x16_bf16 stream -- one wave

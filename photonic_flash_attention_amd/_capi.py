@@ -128,6 +128,11 @@ class PfaFa3KvQuant(C.Structure):
                 ("k_descale", C.c_void_p), ("v_descale", C.c_void_p), ("descale_stride_b", C.c_int64)]
 
 
+class PfaFa3Sinks(C.Structure):
+    """Mirror of ``struct pfa_fa3_sinks`` (include/pfa_hip.h): one fp32 attention sink per query head, for the ``*_sink`` calls."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("sinks", C.c_void_p)]
+
+
 class PfaKvAppendArgs(C.Structure):
     """Mirror of ``struct pfa_kv_append_args`` (include/pfa_hip.h): the device-side KV-cache append."""
     _fields_ = (
@@ -190,6 +195,7 @@ def _prototypes():
     tree = C.POINTER(PfaFa3TreeMask)
     vl, vlb = C.POINTER(PfaFa3VarlenArgs), C.POINTER(PfaFa3VarlenBwdArgs)
     quant = C.POINTER(PfaFa3KvQuant)
+    snk = C.POINTER(PfaFa3Sinks)
     return {
         "pfa_abi_version": (i, None),
         "pfa_status_string": (C.c_char_p, [i]),
@@ -265,6 +271,20 @@ def _prototypes():
         "pfa_fa3_prefill_varlen_q8_check": (i, [var, ext, quant]),
         "pfa_fa3_prefill_varlen_q8": (i, [var, ext, quant, vp]),
         "pfa_fa3_prefill_varlen_q8_describe": (i, [var, ext, quant] + buf),
+        "pfa_fa3_decode_sink_workspace_bytes": (sz, [dec, ext, snk]),
+        "pfa_fa3_decode_sink_check": (i, [dec, ext, snk]),
+        "pfa_fa3_decode_sink": (i, [dec, ext, snk, vp]),
+        "pfa_fa3_decode_sink_describe": (i, [dec, ext, snk] + buf + ns),
+        "pfa_fa3_prefill_sink_check": (i, [dec, ext, snk]),
+        "pfa_fa3_prefill_sink": (i, [dec, ext, snk, vp]),
+        "pfa_fa3_prefill_sink_describe": (i, [dec, ext, snk] + buf),
+        "pfa_fa3_prefill_varlen_sink_check": (i, [var, ext, snk]),
+        "pfa_fa3_prefill_varlen_sink": (i, [var, ext, snk, vp]),
+        "pfa_fa3_prefill_varlen_sink_describe": (i, [var, ext, snk] + buf),
+        "pfa_fa3_prefill_split_sink_workspace_bytes": (sz, [dec, C.c_int32, snk]),
+        "pfa_fa3_prefill_split_sink_check": (i, [dec, C.c_int32, snk]),
+        "pfa_fa3_prefill_split_sink": (i, [dec, C.c_int32, snk, vp]),
+        "pfa_fa3_prefill_split_sink_describe": (i, [dec, C.c_int32, snk] + buf + ns),
     }
 
 
@@ -411,6 +431,37 @@ def describe_prefill_q8(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], q
 def describe_prefill_varlen_q8(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaFa3CacheExt], quant: Optional[PfaFa3KvQuant]):
     """``describe_prefill_varlen_ex`` of ``pfa_fa3_prefill_varlen_q8``."""
     return _describe("pfa_fa3_prefill_varlen_q8_describe", args, ext, quant)
+
+
+def make_sinks(**kw) -> PfaFa3Sinks:
+    return _make(PfaFa3Sinks, kw)
+
+
+def describe_decode_sink(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], sinks: Optional[PfaFa3Sinks]):
+    """``describe_decode_ex`` of ``pfa_fa3_decode_sink`` (``sinks`` None: the NULL block, i.e. ``pfa_fa3_decode_ex``): "_sink" marks a kernel
+    that takes the sinks; workgroups and splits are the sink-less call's."""
+    return _describe("pfa_fa3_decode_sink_describe", args, ext, sinks, nsplit=True)
+
+
+def describe_prefill_sink(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt], sinks: Optional[PfaFa3Sinks]):
+    """``describe_prefill_ex`` of ``pfa_fa3_prefill_sink``."""
+    return _describe("pfa_fa3_prefill_sink_describe", args, ext, sinks)
+
+
+def describe_prefill_varlen_sink(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaFa3CacheExt], sinks: Optional[PfaFa3Sinks]):
+    """``describe_prefill_varlen_ex`` of ``pfa_fa3_prefill_varlen_sink``."""
+    return _describe("pfa_fa3_prefill_varlen_sink_describe", args, ext, sinks)
+
+
+def describe_prefill_split_sink(args: PfaFa3DecodeArgs, key_splits: int, sinks: Optional[PfaFa3Sinks]):
+    """``describe_prefill_split`` of ``pfa_fa3_prefill_split_sink``."""
+    buf = C.create_string_buffer(128)
+    ns = C.c_int32(0)
+    n = load().pfa_fa3_prefill_split_sink_describe(C.byref(args), int(key_splits), None if sinks is None else C.byref(sinks), buf, 128,
+                                                   C.byref(ns))
+    if n < 0:
+        check_status(n)
+    return buf.value.decode(), n, ns.value
 
 
 def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):

@@ -53,6 +53,17 @@
 //     multiplication of the epilogue (the normalisation, or the partial's write), so the combine kernel is reused unchanged.  With both
 //     descales 1 the result has the bits of the 16-bit kernel on the converted cache.  KV8 = false compiles to the code and the kernel
 //     arguments it had.
+//   * SINK = true (pfa_fa3_decode_sink; plain and WINDOW, no tree, no FP8 cache; Decode*SinkParams carry the pointer): an attention sink,
+//     one fp32 value per QUERY head in the units of the scaled scores, is one more key with that score and a zero value row.  Nothing
+//     in front of the waves' merge changes.  In the merge, the workgroup of the item's split 0 takes the row's sink (a vector load: the
+//     rows of a packed head group belong to different query heads) times log2(e) as a fifth partial (m, l, O) = (sink, 1, 0): the
+//     maximum runs over it and the row sum gains exp2(sink - M).  nsplit == 1: that normalises the output and enters the LSE.
+//     nsplit > 1: it is part of split 0's (M, L) pair and of the scale of its partial O, and fa3_decode_combine_kernel, unchanged, does
+//     the rest; the other splits' workgroups take -inf for the sink, which adds exp2(-inf) = 0.  An empty split passes the tile loop
+//     (no wave has a tile) and runs the merge like any other, so split 0 writes the sink's partial -- O = 0, (M, L) = (sink, 1) -- also
+//     when its own key range is empty, and a row with no visible key anywhere gets O = 0 and LSE = sink.  A sink of -inf leaves every
+//     value as it was (M unchanged, L + 0): the bits of the sink-less kernel; the Mu guard covers -inf - (-inf).  SINK = false compiles
+//     to the code and the kernel arguments it had.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,10 +139,19 @@ struct DecodeQ8Params : DecodeParams {
     const float* v_descale;
     int64_t ds_sb;
 };
-template <bool WINDOW, bool TREE = false, bool KV8 = false> struct DecodeParamsOf { typedef DecodeParams type; };
+// SINK only: one fp32 sink per query head, sinks[h], in the units of the scaled scores (natural log)
+struct DecodeSinkParams : DecodeParams {
+    const float* sinks;
+};
+struct DecodeWinSinkParams : DecodeWinParams {
+    const float* sinks;
+};
+template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false> struct DecodeParamsOf { typedef DecodeParams type; };
 template <> struct DecodeParamsOf<true, false> { typedef DecodeWinParams type; };
 template <> struct DecodeParamsOf<false, true> { typedef DecodeTreeParams type; };
 template <> struct DecodeParamsOf<false, false, true> { typedef DecodeQ8Params type; };
+template <> struct DecodeParamsOf<false, false, false, true> { typedef DecodeSinkParams type; };
+template <> struct DecodeParamsOf<true, false, false, true> { typedef DecodeWinSinkParams type; };
 
 template <typename T> struct DElem;
 template <> struct DElem<__bf16> {
@@ -193,9 +213,10 @@ __device__ __forceinline__ void split_range(const DecodeParams& p, int s, int ba
     hi = min(lo + c, len);
 }
 
-template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false, bool KV8 = false>
-__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE, KV8>::type p) {
+template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false, bool KV8 = false, bool SINK = false>
+__global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE, KV8, SINK>::type p) {
     static_assert(!(WINDOW && TREE), "a tree does not combine with a window");
+    static_assert(!(SINK && (TREE || KV8)), "the sink is built for the plain and the windowed 16-bit cache");
     static_assert(!(KV8 && (WINDOW || TREE)), "the FP8 cache takes neither a window nor a tree");
     using E = DElem<T>;
     using v8 = typename E::v8;
@@ -466,6 +487,12 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
         mw[w] = mml[(w * ROWS + orow) * 2];
         M = fmaxf(M, mw[w]);
     }
+    // SINK: the row's sink in log2 units as one more partial (m, l, O) = (sink, 1, 0), in the item's split 0 only (-inf elsewhere: + 0)
+    float sink = -__builtin_inff();
+    if constexpr (SINK) {
+        if (s == 0) sink = p.sinks[kvh * p.G + rr % p.G] * 1.4426950408889634f;
+        M = fmaxf(M, sink);
+    }
     const float Mu = M == -__builtin_inff() ? 0.f : M;
     float L = 0.f, sc[NW];
 #pragma unroll
@@ -473,6 +500,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
         sc[w] = __builtin_amdgcn_exp2f(mw[w] - Mu);
         L += sc[w] * mml[(w * ROWS + orow) * 2 + 1];
     }
+    if constexpr (SINK) L += __builtin_amdgcn_exp2f(sink - Mu);     // a sink of -inf with M = -inf: exp2(-inf - 0) = 0
     const int oi = rr / p.G, oh = kvh * p.G + rr % p.G;
     if (p.nsplit == 1) {
         const float inv = L > 0.f ? 1.f / L : 0.f;

@@ -97,6 +97,21 @@
 //     v_descale multiplies inv once in the epilogue.  Both are exact at 1: the call then returns the bits of the 16-bit call on the
 //     converted cache.
 // KV8 = false compiles to the code and the kernel arguments the instantiation had.
+//
+// SINK (pfa_fa3_prefill_sink / _varlen_sink / _split_sink; uniform, VARLEN and SPLIT, with and without WINDOW; no KV8; Prefill*SinkParams
+// carry the pointer): an attention sink, one fp32 value per QUERY head in the units of the scaled scores, is one more key with that
+// score and a zero value row.  The tile loop and everything in front of it are untouched; a workgroup serves one head, so the sink is one
+// scalar load in the prologue.  The epilogue, with mc = m_run * c the deferred-max reference in log2 units and s2 = sinks[hh] * log2(e):
+//     M' = max(mc, s2),  l' = l_tot * exp2(mc - M') + exp2(s2 - M'),  inv = exp2(mc - M') / l',  LSE = (M' + log2 l') ln 2.
+//   - a row with no visible key has l_tot = 0 and mc = -1e30 c: M' = s2, the first factor is 0, l' = 1 -- O = 0 exactly and LSE = sink;
+//   - s2 = -inf: M' = mc, the factors are exactly 1 and 0, l' = l_tot and inv = (1 / l_tot) * 1 -- O keeps the bits of the sink-less
+//     kernel, and a row without keys keeps l' = 0, O = 0, LSE = -inf.  The LSE is written as fma(m_run, c, log2 l') ln 2 where the
+//     keys hold the maximum (M' = mc) and as (s2 + log2 l') ln 2 where the sink does: the first is the sink-less kernel's value on l',
+//     so at s2 = -inf the LSE -- and through a split's partial LSE the merged O -- keeps its bits as well;
+//   - SPLIT: only the workgroup of split 0 takes the sink (the others take s2 = -inf), so exactly one part carries it into the merge,
+//     and split 0's partial LSE is finite even when it runs no tile;
+//   - VARLEN idle waves and rows past sq store nothing, as before.
+// SINK = false compiles to the code and the kernel arguments the instantiation had.
 #pragma once
 #include "fa3_fwd_kernel.h"
 #include "fp8_cvt.h"
@@ -152,20 +167,42 @@ struct PrefillVarlenQ8Params : PrefillVarlenParams {
     const float* v_descale;
     int64_t ds_sb;
 };
-template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false> struct PrefillParamsOf { typedef PrefillParams type; };
+// SINK: one fp32 sink per query head, sinks[h], in the units of the scaled scores (natural log)
+struct PrefillSinkParams : PrefillParams {
+    const float* sinks;
+};
+struct PrefillVarlenSinkParams : PrefillVarlenParams {
+    const float* sinks;
+};
+struct PrefillWinSinkParams : PrefillWinParams {
+    const float* sinks;
+};
+struct PrefillVarlenWinSinkParams : PrefillVarlenWinParams {
+    const float* sinks;
+};
+struct PrefillSplitSinkParams : PrefillSplitParams {
+    const float* sinks;
+};
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, bool SINK = false> struct PrefillParamsOf { typedef PrefillParams type; };
 template <> struct PrefillParamsOf<true, false> { typedef PrefillVarlenParams type; };
 template <> struct PrefillParamsOf<false, true> { typedef PrefillWinParams type; };
 template <> struct PrefillParamsOf<true, true> { typedef PrefillVarlenWinParams type; };
 template <> struct PrefillParamsOf<false, false, true> { typedef PrefillSplitParams type; };
 template <> struct PrefillParamsOf<false, false, false, true> { typedef PrefillQ8Params type; };
 template <> struct PrefillParamsOf<true, false, false, true> { typedef PrefillVarlenQ8Params type; };
+template <> struct PrefillParamsOf<false, false, false, false, true> { typedef PrefillSinkParams type; };
+template <> struct PrefillParamsOf<true, false, false, false, true> { typedef PrefillVarlenSinkParams type; };
+template <> struct PrefillParamsOf<false, true, false, false, true> { typedef PrefillWinSinkParams type; };
+template <> struct PrefillParamsOf<true, true, false, false, true> { typedef PrefillVarlenWinSinkParams type; };
+template <> struct PrefillParamsOf<false, false, true, false, true> { typedef PrefillSplitSinkParams type; };
 
 typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
 typedef const __attribute__((address_space(4))) float* prefill_f32_ptr;
 
 template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false, bool SPLIT = false,
-          bool KV8 = false>
-__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8>::type p) {
+          bool KV8 = false, bool SINK = false>
+__global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8, SINK>::type p) {
+    static_assert(!(SINK && KV8), "the sink is built for the 16-bit cache");
     static_assert(!KV8 || (!WINDOW && !SPLIT), "the FP8 cache takes neither a window nor a split over keys");
     static_assert(CAUSAL || !WINDOW, "the window is cut from the causal diagonal");
     static_assert(!SPLIT || (!VARLEN && !WINDOW), "the split over keys is for the uniform, window-less call");
@@ -258,6 +295,11 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     if constexpr (KV8) {
         k_mul = ((prefill_f32_ptr)(uintptr_t)p.k_descale)[(int64_t)b * p.ds_sb + kvh];
         v_mul = ((prefill_f32_ptr)(uintptr_t)p.v_descale)[(int64_t)b * p.ds_sb + kvh];
+    }
+    // SINK: the head's sink in log2 units (a scalar load); SPLIT: split 0 alone carries it.  Used under if constexpr (SINK) only
+    float s2 = -INFINITY;
+    if constexpr (SINK) {
+        if (!SPLIT || split == 0) s2 = ((prefill_f32_ptr)(uintptr_t)p.sinks)[hh] * 1.4426950408889634f;
     }
 
     // ---- Q fragments: B operand of S^T = K Q^T, lane (r,h) holds Q[my_q][16 ks + 8 h .. +7] -----------
@@ -586,6 +628,16 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
     const float l_tot = row_pair_sum(l_run);
     float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
     if constexpr (KV8) inv *= v_mul;
+    // SINK: one more key of score s2 and a zero value row.  e is exactly 1 and l_sink exactly l_tot when s2 = -inf; mc is finite
+    // (m_run starts at -1e30), the guard is for a scale so large that mc overflows
+    float m_sink = 0.f, l_sink = 0.f;
+    if constexpr (SINK) {
+        m_sink = fmaxf(mc, s2);
+        const float m_use = m_sink == -INFINITY ? 0.f : m_sink;
+        const float e = __builtin_amdgcn_exp2f(mc - m_use);
+        l_sink = l_tot * e + __builtin_amdgcn_exp2f(s2 - m_use);
+        inv = l_sink > 0.f ? (1.0f / l_sink) * e : 0.f;
+    }
     // VARLEN: the batch's rows start at packed row row0, and the row bound of every store is the batch's own count -- the next
     // packed row is another batch's
     const int64_t o_batch = VARLEN ? (int64_t)row0 * p.o_ss : (int64_t)b * p.o_sb;
@@ -629,7 +681,15 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typen
             }
     }
     if (my_q < sq && (SPLIT || p.lse) && h == 0) {
-        const float lse = l_tot > 0.f ? (m_run * c + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : -INFINITY;
+        float lse;
+        if constexpr (SINK) {
+            // where the keys hold the maximum, the sink-less kernel's value on l_sink -- its m_run * c + log2 l is contracted into one
+            // fused multiply-add, spelled out here because the select would keep the compiler from it: at s2 = -inf the partial LSE of a
+            // split then has that kernel's bits, and so has the merged O
+            const float lg = __builtin_amdgcn_logf(l_sink);
+            const float lse_keys = __builtin_fmaf(m_run, c, lg) * 0.6931471805599453f, lse_sink = (s2 + lg) * 0.6931471805599453f;
+            lse = l_sink > 0.f ? (mc >= s2 ? lse_keys : lse_sink) : -INFINITY;
+        } else lse = l_tot > 0.f ? (m_run * c + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : -INFINITY;
         if constexpr (SPLIT) p.part_lse[(((int64_t)split * p.B + b) * p.H + hh) * p.Sq + my_q] = lse;
         else if constexpr (VARLEN) p.lse[(int64_t)hh * p.total_q + row0 + my_q] = lse;
         else p.lse[((int64_t)b * p.H + hh) * p.Sq + my_q] = lse;

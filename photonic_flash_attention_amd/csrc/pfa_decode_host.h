@@ -1,6 +1,6 @@
-// pfa_decode_host.h -- what pfa_decode_capi.hip and pfa_decode_fp8_capi.hip share behind pfa_fa3_decode_args (internal): the split rule,
+// pfa_decode_host.h -- what pfa_decode_capi.hip, pfa_decode_fp8_capi.hip and pfa_decode_sink_capi.hip share behind pfa_fa3_decode_args (internal): the split rule,
 // the kernel tables of fa3_decode_kernel and its combine, the parameter fill with the workspace layout, and the launch with its combine.
-// WINDOW / TREE / KV8 are fixed by the unit that calls, so each unit instantiates its own kernels only.
+// WINDOW / TREE / KV8 / SINK are fixed by the unit that calls, so each unit instantiates its own kernels only.
 #pragma once
 #include "fa3_decode_kernel.h"
 #include "pfa_host.h"
@@ -22,7 +22,7 @@ struct Plan {
 // captured graph stays valid while they change, and a paged call splits exactly as the contiguous call of the same (B, H, Hkv, Sq, Smax,
 // D, window).  window (0: none, else 1 .. Smax): the keys a batch's splits divide are at most window + Sq - 1 and the up to 63 below
 // them in the first tile, so that span, rounded to tiles, stands where Smax does -- a 4096-key window over a 128K cache is not cut
-// into 128 splits of a few tiles.  The cache's element type plays no part: the FP8 call plans as the 16-bit one.
+// into 128 splits of a few tiles.  The cache's element type plays no part: the FP8 call plans as the 16-bit one.  Nor does a sink.
 inline Plan plan(const pfa_fa3_decode_args* a, int window) {
     Plan pl;
     pl.G = a->H / a->Hkv;
@@ -44,16 +44,16 @@ inline Plan plan(const pfa_fa3_decode_args* a, int window) {
     return pl;
 }
 
-template <bool WINDOW, bool TREE = false, bool KV8 = false>
-using Params = typename dec::DecodeParamsOf<WINDOW, TREE, KV8>::type;
+template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false>
+using Params = typename dec::DecodeParamsOf<WINDOW, TREE, KV8, SINK>::type;
 
 // fa3_decode_kernel for (dtype, D, out, paged) in the mode the caller fixes
-template <bool WINDOW, bool TREE = false, bool KV8 = false>
-KernelFn<Params<WINDOW, TREE, KV8>> kernel(int dtype, int D, bool out32, bool paged) {
+template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false>
+KernelFn<Params<WINDOW, TREE, KV8, SINK>> kernel(int dtype, int D, bool out32, bool paged) {
     return dispatch_elem_dim(dtype, D, [&](auto t) {
         using T = typename decltype(t)::type;
-        return dispatch_bools([](auto o32, auto pg) -> KernelFn<Params<WINDOW, TREE, KV8>> {
-            return &dec::fa3_decode_kernel<T, decltype(t)::D, out_t<o32.value, T>, pg.value, WINDOW, TREE, KV8>;
+        return dispatch_bools([](auto o32, auto pg) -> KernelFn<Params<WINDOW, TREE, KV8, SINK>> {
+            return &dec::fa3_decode_kernel<T, decltype(t)::D, out_t<o32.value, T>, pg.value, WINDOW, TREE, KV8, SINK>;
         }, out32, paged);
     });
 }
@@ -66,7 +66,7 @@ inline KernelFn<dec::DecodeParams> combine(int dtype, int D, bool out32) {
     });
 }
 
-// What every mode's block holds of checked arguments and their plan; the mode's own members (window, tree, descales) are the caller's.
+// What every mode's block holds of checked arguments and their plan; the mode's own members (window, tree, descales, sinks) are the caller's.
 // The workspace of a split call is the partial O [nsplit][B][H][Sq][D] and behind it the partial (m, l) pairs, both fp32.
 inline void fill_params(dec::DecodeParams& p, const pfa_fa3_decode_args* a, const Plan& pl) {
     fill_attention_params(p, a);
@@ -78,10 +78,10 @@ inline void fill_params(dec::DecodeParams& p, const pfa_fa3_decode_args* a, cons
 }
 
 // of checked arguments and a filled block: the main kernel on `stream` and, where the plan splits, the combine behind it
-template <bool WINDOW, bool TREE = false, bool KV8 = false>
-int launch(const pfa_fa3_decode_args* a, const Plan& pl, const Params<WINDOW, TREE, KV8>& p, void* stream) {
+template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false>
+int launch(const pfa_fa3_decode_args* a, const Plan& pl, const Params<WINDOW, TREE, KV8, SINK>& p, void* stream) {
     const bool out32 = a->dtype_out == PFA_DTYPE_FP32;
-    const auto fn = kernel<WINDOW, TREE, KV8>(a->dtype_in, a->D, out32, a->block_table != nullptr);
+    const auto fn = kernel<WINDOW, TREE, KV8, SINK>(a->dtype_in, a->D, out32, a->block_table != nullptr);
     const auto cfn = combine(a->dtype_in, a->D, out32);
     const DeviceScope dev(a->device_id);
     if (hip_failed(dev.error())) return PFA_ERR_DEVICE;

@@ -1,5 +1,5 @@
-// pfa_prefill_host.h -- what the five pfa_prefill*_capi.hip units share behind their argument blocks (internal): the grid, the one
-// kernel table, the parameter fill and the one launch of fa3_prefill_kernel.  VARLEN / WINDOW / SPLIT / KV8 are fixed by the unit
+// pfa_prefill_host.h -- what the pfa_prefill*_capi.hip units share behind their argument blocks (internal): the grid, the one
+// kernel table, the parameter fill and the one launch of fa3_prefill_kernel.  VARLEN / WINDOW / SPLIT / KV8 / SINK are fixed by the unit
 // that calls, so each unit instantiates its own kernels only and they still compile side by side.
 #pragma once
 #include <limits.h>
@@ -9,6 +9,7 @@
 #include "fa3_prefill_kernel.h"
 #include "pfa_fp8_host.h"
 #include "pfa_host.h"
+#include "pfa_sink_host.h"
 
 namespace pfa {
 namespace prefill {
@@ -28,19 +29,19 @@ int check_grid_and_ext(const Args* a, const pfa_fa3_cache_ext* ext, int* window)
     return check_cache_ext(ext, a->causal, a->Smax, window);
 }
 
-template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false>
-using Params = typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8>::type;
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, bool SINK = false>
+using Params = typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8, SINK>::type;
 
 // fa3_prefill_kernel for (dtype, D, causal, paged, out) in the mode the caller fixes.  fp32 output: P carried as a 16-bit hi + lo pair
 // (SPLITP), as the forward does for its <= 1e-3 mode.  The windowed instantiations exist under the causal flag only and the split
 // ones with fp32 output only: validation refuses the rest, and the table has nullptr there, which no launch accepts.
-template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false>
-KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8>> kernel(int dtype, int D, bool causal, bool paged, bool out32) {
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, bool SINK = false>
+KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8, SINK>> kernel(int dtype, int D, bool causal, bool paged, bool out32) {
     return dispatch_elem_dim(dtype, D, [&](auto t) {
         using T = typename decltype(t)::type;
-        return dispatch_bools([](auto c, auto pg, auto o32) -> KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8>> {
+        return dispatch_bools([](auto c, auto pg, auto o32) -> KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8, SINK>> {
             if constexpr ((WINDOW && !c.value) || (SPLIT && !o32.value)) return nullptr;
-            else return &fa3_prefill_kernel<T, decltype(t)::D, c.value, o32.value, pg.value, out_t<o32.value, T>, VARLEN, WINDOW, SPLIT, KV8>;
+            else return &fa3_prefill_kernel<T, decltype(t)::D, c.value, o32.value, pg.value, out_t<o32.value, T>, VARLEN, WINDOW, SPLIT, KV8, SINK>;
         }, causal, paged, out32);
     });
 }
@@ -69,12 +70,12 @@ void fill_prefill_params(Block& p, const Args* a) {
 template <typename Args>
 size_t lds_bytes(const Args* a) { return (size_t)(2 * 2 * BLOCK_N * a->D * 2); }
 
-// of checked arguments and a block whose mode's own members (window; descales; split count and parts) the caller has set: the rest of
+// of checked arguments and a block whose mode's own members (window; descales; split count and parts; sinks) the caller has set: the rest of
 // the block and one launch on `stream`, of nsplit times the call's workgroups.  The split parts are fp32 whatever the call's output is.
-template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, typename Args>
-int launch(const Args* a, Params<VARLEN, WINDOW, SPLIT, KV8>& p, void* stream, int nsplit = 1) {
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, bool SINK = false, typename Args>
+int launch(const Args* a, Params<VARLEN, WINDOW, SPLIT, KV8, SINK>& p, void* stream, int nsplit = 1) {
     fill_prefill_params<VARLEN>(p, a);
-    const auto fn = kernel<VARLEN, WINDOW, SPLIT, KV8>(a->dtype_in, a->D, a->causal != 0, a->block_table != nullptr,
+    const auto fn = kernel<VARLEN, WINDOW, SPLIT, KV8, SINK>(a->dtype_in, a->D, a->causal != 0, a->block_table != nullptr,
                                                        SPLIT || a->dtype_out == PFA_DTYPE_FP32);
     const DeviceScope dev(a->device_id);
     if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
@@ -90,6 +91,18 @@ int launch_windowed(const Args* a, int window, void* stream) {
     }
     Params<VARLEN> p;
     return launch<VARLEN>(a, p, stream);
+}
+// ... with sinks (a checked pfa_fa3_sinks): the SINK instantiations, same grid, same LDS
+template <bool VARLEN, typename Args>
+int launch_windowed_sink(const Args* a, int window, const pfa_fa3_sinks* sinks, void* stream) {
+    if (window) {
+        Params<VARLEN, true, false, false, true> p;
+        p.window = window; p.sinks = sinks->sinks;
+        return launch<VARLEN, true, false, false, true>(a, p, stream);
+    }
+    Params<VARLEN, false, false, false, true> p;
+    p.sinks = sinks->sinks;
+    return launch<VARLEN, false, false, false, true>(a, p, stream);
 }
 // ... over an FP8 cache (a checked pfa_fa3_kv_quant): the KV8 instantiations, same grid, same LDS
 template <bool VARLEN, typename Args>

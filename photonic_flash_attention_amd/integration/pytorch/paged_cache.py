@@ -601,7 +601,7 @@ class PagedKVCache:
         Keyword arguments (``causal``, ``key_mask`` over ``max_pages_per_seq * page_size`` logical keys, ``out_dtype``,
         ``window`` -- the sliding window, required once ``release_behind_window`` has given pages back --, ``tree_mask`` -- int64
         ``[B, Sq]`` words that verify a drafted token tree, ``ops.tree_mask_from_parents``; ``truncate`` then takes the rejected rows
-        back --, ...) pass through.  -> ``(o, lse)``."""
+        back --, ``sinks`` -- fp32 ``[H]`` attention sinks, one per query head --, ...) pass through.  -> ``(o, lse)``."""
         table, lens = self._rows(slots)
         if self._fp8:                                                      # the cache's own scales; the refused keywords raise in ops
             kw = dict(kw, k_descale=self._kd, v_descale=self._vd)
@@ -611,7 +611,7 @@ class PagedKVCache:
         """``ops.fa3_prefill_cache`` of ``q [B, H, Sq, D]`` (any Sq: a prompt chunk, the suffix behind shared prefix pages, a
         speculative step) against the sequences in ``slots``, which are chosen and captured as in ``decode``.  ``append`` the rows'
         own K / V first: the lengths count them, and ``causal`` (the default) is bottom-right aligned.  Keyword arguments
-        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o, lse)``."""
+        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ``sinks``, ...) pass through.  -> ``(o, lse)``."""
         if self._fp8:
             raise ValueError("prefill over an FP8 cache is not built: run the dense forward on the prompt's 16-bit K / V and append them")
         table, lens = self._rows(slots)
@@ -624,7 +624,7 @@ class PagedKVCache:
         rows' own K / V first.  A host list ``q_lens`` becomes a device ``cu_seqlens_q`` by a non-blocking copy, with
         ``max_seqlen_q = max(q_lens)`` unless given; a caller that captures graphs passes its own device ``cu_seqlens_q`` (int32
         ``[len(slots) + 1]``, updated in place between replays) and the ``max_seqlen_q`` bound instead.  Keyword arguments
-        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
+        (``causal``, ``out_dtype``, ``return_lse``, ``out``, ``window``, ``sinks``, ...) pass through.  -> ``(o [total_q, H, D], lse [H, total_q])``."""
         if self._fp8:
             raise ValueError("prefill_varlen over an FP8 cache is not built: run the dense forward on the 16-bit K / V and append them")
         table, lens = self._rows(slots)

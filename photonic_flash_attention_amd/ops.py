@@ -704,6 +704,25 @@ def _tree_mask_arg(tree_mask, q, causal, window, shared_prefix):
     return _capi.make_tree_mask(words=tree_mask.data_ptr(), stride_b=max(tree_mask.stride(0), Sq))
 
 
+def _sinks_arg(sinks, q, tree_mask=None):
+    """``sinks`` (None, or a contiguous fp32 ``[H]`` tensor on q's device) as the ``pfa_fa3_sinks`` block of the ``*_sink`` calls, or None.
+    Refused with ``tree_mask``; every refusal is a ``ValueError`` that names the argument, before anything is enqueued."""
+    if sinks is None:
+        return None
+    if tree_mask is not None:
+        raise ValueError("sinks is not supported with tree_mask: the tree kernels carry no sink")
+    if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32:
+        raise ValueError("sinks must be an fp32 tensor (one value per query head, in the units of the scaled scores)")
+    H = q.shape[1] if isinstance(q, torch.Tensor) and q.dim() >= 2 else 0
+    if sinks.shape != (H,):
+        raise ValueError(f"sinks must be [H] = [{H}], got {tuple(sinks.shape)}")
+    if not sinks.is_contiguous():
+        raise ValueError("sinks must be contiguous")
+    if sinks.device != q.device:
+        raise ValueError("sinks must live on the operands' device")
+    return _capi.make_sinks(sinks=sinks.data_ptr())
+
+
 def tree_mask_from_parents(parents: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """The ``tree_mask`` words of a drafted token tree given by parent links, and the nodes' depths.
 
@@ -1083,14 +1102,16 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=
 
 
 def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, tree=None, quant=None, descales=None,
-                       **ragged):
+                       sinks=None, **ragged):
     """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
     ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
     the current stream right behind it, the status, and the kept tensors' hold on the stream.  With ``rotary`` the launch reads the
     rotated copy of q that ``rope_append`` wrote; the caller's q is not modified.  ``key_splits`` (the C value, ``pfa_fa3_prefill`` only)
     launches ``pfa_fa3_prefill_split`` instead, which takes no extension; ``tree`` (``pfa_fa3_decode`` only) launches
     ``pfa_fa3_decode_tree``, which takes it behind the extension; ``quant`` (``pfa_fa3_decode`` over an FP8 cache, with the caller's
-    ``descales`` for the append) launches ``pfa_fa3_decode_q8``; with the prefill entries it launches ``{entry}_q8``.  -> lse or None."""
+    ``descales`` for the append) launches ``pfa_fa3_decode_q8``; with the prefill entries it launches ``{entry}_q8``; ``sinks`` (a
+    ``pfa_fa3_sinks`` block; with neither a tree nor an FP8 cache) launches ``{entry}_sink``, or ``{entry}_split_sink`` with ``key_splits``.
+    -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
@@ -1104,6 +1125,8 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     # the export that serves the call, and what it takes between the argument block and the stream
     suffix, middle = (("_split", (key_splits,)) if key_splits is not None else ("_q8", (e, C.byref(quant))) if quant is not None
                       else ("_tree", (e, C.byref(tree))) if tree is not None else ("_ex", (e,)))
+    if sinks is not None:
+        suffix, middle = ("_split_sink", (key_splits, C.byref(sinks))) if key_splits is not None else ("_sink", (e, C.byref(sinks)))
     st = getattr(_capi.load(), entry + suffix)(C.byref(a), *middle, C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
     if keep:
@@ -1184,7 +1207,7 @@ def attn_merge(outs, lses, *, out: Optional[torch.Tensor] = None, out_dtype: Opt
 
 
 def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *, cache_seqlens, key_mask, window, causal, softmax_scale,
-                        out_dtype, return_lse, out, block_table, k_new, v_new, rotary, prefix_key_splits=None):
+                        out_dtype, return_lse, out, block_table, k_new, v_new, rotary, prefix_key_splits=None, sinks=None):
     """``shared_prefix=P`` of ``fa3_decode`` / ``fa3_prefill_cache`` (``call``; ``entry`` names its C entry point in the messages): the
     attention cut at logical key P.  All ``B * Sq`` rows go as ONE sequence against sequence 0's first P keys (``causal=False``; every
     row lies behind the prefix), each sequence goes against its own keys from P on (``call`` unchanged on the cache view that starts
@@ -1192,7 +1215,8 @@ def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *,
     ``out_dtype``.  The optional append runs once, first, on the whole cache, and both passes read the rotated q.  Everything is
     enqueued on the current stream with no host synchronisation; every ``ValueError`` is raised before the first launch.
     ``prefix_key_splits`` (as the caller gave it, already validated) is the prefix pass's ``key_splits`` when that pass is
-    ``fa3_prefill_cache``; the decode kernel splits by itself."""
+    ``fa3_prefill_cache``; the decode kernel splits by itself.  ``sinks`` (already validated) go to the own-keys pass ONLY: its LSE then
+    contains the sink, and the merge with the sink-less prefix part is the sink-carrying result over all keys."""
     P = _host_int(shared_prefix)
     if P is None:
         raise ValueError(f"shared_prefix must be None or a host integer, got {shared_prefix!r}")
@@ -1239,7 +1263,7 @@ def _shared_prefix_step(call, entry: str, shared_prefix, q, k_cache, v_cache, *,
                                  out_dtype=torch.float32, return_lse=True, **split_kw)
     own_lens = (cache_seqlens.to(torch.int32) - P).clamp_(min=0)
     o_own, lse_own = call(q, own[0], own[1], block_table=own[2], cache_seqlens=own_lens, causal=causal, softmax_scale=softmax_scale,
-                          out_dtype=torch.float32, return_lse=True)
+                          out_dtype=torch.float32, return_lse=True, sinks=sinks)
     return attn_merge([o_pre.transpose(1, 2).reshape(B, Sq, H, D).transpose(1, 2), o_own],
                       [lse_pre.view(H, B, Sq).transpose(0, 1), lse_own], out=out, out_dtype=odt, return_lse=return_lse)
 
@@ -1253,7 +1277,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
                prefix_key_splits=None, tree_mask: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
-               v_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
     q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
@@ -1333,11 +1357,22 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     ``cache_seqlens``, ``block_table``, ``causal``, ``out``, ``out_dtype``, ``return_lse`` work as above; ``k_new=, v_new=`` (16-bit rows) go
     through the quantising ``kv_append`` first.  Splits and workspace are those of the 16-bit call, and a captured step replays while
     the descales' contents change.  ``window``, ``tree_mask``, ``shared_prefix`` and the rotary arguments are not built for an FP8 cache
-    and raise ``ValueError``; bytes at and past a length are never read into a result (NaN bytes there are harmless)."""
+    and raise ``ValueError``; bytes at and past a length are never read into a result (NaN bytes there are harmless).
+
+    Attention sinks: ``sinks`` (contiguous fp32 ``[H]`` DEVICE tensor, one value per QUERY head; ``pfa_fa3_decode_sink``) adds
+    ``exp(sinks[h])`` to every row's softmax denominator -- one extra key with score ``sinks[h]`` and a zero value row.  The values are in
+    the units of the scaled scores (natural log) and are NOT multiplied by ``softmax_scale``.  The sink is inside the returned LSE; a row
+    with no visible key gets O = 0 and LSE = ``sinks[h]`` (not -inf); ``sinks[h] = -inf`` gives head h the O bits of the call without
+    sinks; +inf or NaN is the caller's error (that head's rows are unspecified).  ``window``, ``block_table``, ``cache_seqlens``,
+    ``key_mask``, ``causal``, ``out``, ``out_dtype``, ``return_lse``, ``k_new`` / ``v_new`` and rotary work as above, and with
+    ``shared_prefix`` the sinks go to the own-keys pass only.  Splits and workspace are those of the call without sinks, and a captured step
+    replays while the sink values change.  A wrong dtype, shape, layout or device raises ``ValueError`` naming ``sinks`` before anything is
+    enqueued, and so do ``tree_mask`` and an FP8 cache, which take no sinks.  ``None``: exactly the calls made without the argument."""
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_decode", "decode takes key_mask, cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
         ("window", window is not None), ("tree_mask", tree_mask is not None), ("shared_prefix", shared_prefix is not None),
-        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None)), q_too=True) if fp8 else None
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None), ("sinks", sinks is not None)), q_too=True) if fp8 else None
+    snk = _sinks_arg(sinks, q, tree_mask)
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
@@ -1347,7 +1382,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         return _shared_prefix_step(fa3_decode, "pfa_fa3_decode", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
                                    key_mask=key_mask, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
                                    return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary,
-                                   prefix_key_splits=prefix_key_splits)
+                                   prefix_key_splits=prefix_key_splits, sinks=sinks)
     if k_new is not None and cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     a, out, Smax = _cache_call_args("pfa_fa3_decode", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table, fp8)
@@ -1366,11 +1401,13 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
         if cache_seqlens is None:
             cache_seqlens = _mask_bound(km)
     _set_cache_seqlens(a, cache_seqlens, q, keep)
-    # neither a tree nor an FP8 cache changes the workspace
+    if snk is not None:
+        keep.append(sinks)
+    # neither a tree nor an FP8 cache nor sinks change the workspace
     _attach_workspace(a, _capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)), q.device, keep)
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, quant=quant,
-                             descales=(k_descale, v_descale) if fp8 else None, max_seqlen_q=Sq)
+                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, max_seqlen_q=Sq)
     return out, lse
 
 
@@ -1413,7 +1450,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                       rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                       pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
                       key_splits=None, prefix_key_splits=None, k_descale: Optional[torch.Tensor] = None,
-                      v_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
@@ -1470,13 +1507,24 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     descales' contents change.  ``window``, ``shared_prefix``, ``key_splits`` / ``prefix_key_splits`` and the rotary arguments are not
     built for an FP8 cache and raise ``ValueError`` naming the argument before anything is enqueued; bytes at and past a length are
     never read into a result (NaN bytes there are harmless).  Over a ``PagedKVCache``:
-    ``k, v, kw = cache.operands(slots); fa3_prefill_cache(q, k, v, **kw)``."""
+    ``k, v, kw = cache.operands(slots); fa3_prefill_cache(q, k, v, **kw)``.
+
+    Attention sinks: ``sinks`` (contiguous fp32 ``[H]`` DEVICE tensor; ``pfa_fa3_prefill_sink``, with ``key_splits``
+    ``pfa_fa3_prefill_split_sink``) as in ``fa3_decode``: ``exp(sinks[h])`` joins every row's softmax denominator, in the units of the scaled
+    scores, inside the LSE; a row with no visible key gets O = 0 and LSE = ``sinks[h]``; ``-inf`` gives the O bits of the call without
+    sinks.  It works with ``window``, ``block_table``, ``cache_seqlens``, ``causal=False``, both output types, ``return_lse``, ``out``,
+    ``k_new`` / ``v_new``, rotary, ``key_splits`` (split 0 of every q block carries the sink into the merge; a count of 1 is the unsplit
+    call with sinks bit for bit) and ``shared_prefix`` / ``prefix_key_splits`` (the own-keys pass carries it).  Grid and workspace are
+    those of the call without sinks; a captured step replays while the values change.  An FP8 cache takes no sinks (``ValueError``).
+    ``None``: exactly the calls made without the argument."""
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_prefill", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
         ("window", window is not None), ("shared_prefix", shared_prefix is not None), ("key_splits", key_splits is not None),
         ("prefix_key_splits", prefix_key_splits is not None),
-        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None))
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None),
+        ("sinks", sinks is not None))
     ) if fp8 else None
+    snk = _sinks_arg(sinks, q)
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     splits = _key_splits_arg("key_splits", key_splits)
@@ -1490,15 +1538,15 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         return _shared_prefix_step(fa3_prefill_cache, "pfa_fa3_prefill", shared_prefix, q, k_cache, v_cache, cache_seqlens=cache_seqlens,
                                    key_mask=None, window=window, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
                                    return_lse=return_lse, out=out, block_table=block_table, k_new=k_new, v_new=v_new, rotary=rotary,
-                                   prefix_key_splits=prefix_key_splits)
+                                   prefix_key_splits=prefix_key_splits, sinks=sinks)
     a, out, _ = _cache_call_args("pfa_fa3_prefill", q, k_cache, v_cache, causal, softmax_scale, out_dtype, out, block_table, fp8)
-    keep = []
+    keep = [] if snk is None else [sinks]
     _set_cache_seqlens(a, cache_seqlens, q, keep)
     if splits is not None:
         _attach_workspace(a, _capi.load().pfa_fa3_prefill_split_workspace_bytes(C.byref(a), splits), q.device, keep)
     lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, key_splits=splits, quant=quant,
-                             descales=(k_descale, v_descale) if fp8 else None, max_seqlen_q=q.shape[2])
+                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, max_seqlen_q=q.shape[2])
     return out, lse
 
 
@@ -1509,7 +1557,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                        k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                        rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                        pos_offsets: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
-                       v_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen_ex``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
     verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
@@ -1543,13 +1591,19 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     DEVICE tensors ``[Hkv]`` or ``[B, Hkv]``; refused with 16-bit caches), exactly as in ``fa3_prefill_cache``: the attention over
     ``dequantize_kv`` of the cache, the bits of the 16-bit call at descales 1, and of per-sequence ``fa3_prefill_cache`` calls over
     the FP8 cache at any descales.  ``k_new=, v_new=`` go through the quantising ``kv_append``; ``window`` and the rotary arguments raise
-    ``ValueError`` naming the argument before anything is enqueued."""
+    ``ValueError`` naming the argument before anything is enqueued.
+
+    Attention sinks: ``sinks`` (contiguous fp32 ``[H]`` DEVICE tensor; ``pfa_fa3_prefill_varlen_sink``) exactly as in ``fa3_prefill_cache``,
+    with and without ``window``; the result is still bit for bit that of per-sequence ``fa3_prefill_cache(sinks=)`` calls.  An FP8
+    cache takes no sinks (``ValueError``).  ``None``: exactly the calls made without the argument."""
     B_cu = cu_seqlens_q.numel() - 1 if isinstance(cu_seqlens_q, torch.Tensor) else 0
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_prefill_varlen", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, B_cu, (
         ("window", window is not None),
-        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None))
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None),
+        ("sinks", sinks is not None))
     ) if fp8 else None
+    snk = _sinks_arg(sinks, q)
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
@@ -1575,11 +1629,12 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     _set_view(a, "k_cache", k_cache)
     _set_view(a, "v_cache", v_cache)
     _set_block_table(a, block_table, geo.page_size, geo.num_pages)
-    keep = []
+    keep = [] if snk is None else [sinks]
     _set_cache_seqlens(a, cache_seqlens, q, keep, B)
     lse = _finish_cache_call("pfa_fa3_prefill_varlen", a, ext, q, (H, total_q) if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, quant=quant,
-                             descales=(k_descale, v_descale) if fp8 else None, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q))
+                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, cu_seqlens_q=cu_seqlens_q,
+                             max_seqlen_q=int(max_seqlen_q))
     return out, lse
 
 
