@@ -26,7 +26,7 @@
 //     ceil(len_b / page_size) is never read, because a tile exists only below the split's hi <= len_b.  Everything else (split rule,
 //     masks by logical key, softmax, merge, combine) is the one code path, so a paged call returns the bits of the contiguous call
 //     on the gathered cache.  Pages of 16 or 32 keys would put several pages under one tile and are out of scope.
-//   * WINDOW = true (pfa_fa3_decode_ex with a window W, causal only; DecodeWinParams carries W): row i sees key j iff j < len_b,
+//   * WINDOW = true (pfa_fa3_decode_ex with a window W, causal only; DecodeWindowPart carries W): row i sees key j iff j < len_b,
 //     j <= i + off_b and j > i + off_b - W, off_b = len_b - Sq.  The splits divide [base_b, len_b) instead of [0, len_b), with
 //     base_b = floor64(lo_b) and lo_b = max(0, off_b - W + 1) the lowest key row 0 sees: c_b = roundup(ceil((len_b - base_b) / nsplit), 64),
 //     split s covers [base_b + s c_b, min(base_b + (s+1) c_b, len_b)).  Boundaries stay multiples of 64, so a tile still lies inside
@@ -34,14 +34,14 @@
 //     have given those pages away).  Each row's lower bound row_lo = len_b - Sq + i + 1 - W joins the visibility test on the tiles that
 //     reach below the item's largest row_lo; keys in [base_b, row_lo) are read and masked.  The other instantiations are untouched:
 //     WINDOW = false compiles to the code and the kernel arguments it had.
-//   * TREE = true (pfa_fa3_decode_tree, causal only, no window; DecodeTreeParams carries the words): a 64-bit word per query row
+//   * TREE = true (pfa_fa3_decode_tree, causal only, no window; DecodeTreePart carries the words): a 64-bit word per query row
 //     replaces the causal triangle over the step's own Sq keys.  Row i sees key j iff j < len_b and (j < off_b or bit (j - off_b) of
 //     tree[b][i] is set), off_b = len_b - Sq.  Each lane loads its row's word once, by a vector load, in front of the tile loop.  Key off_b
 //     itself can be hidden, so the masked path starts one key earlier than under causal (a tile is unmasked only when it ends at or
 //     below off_b) and a row's upper bound is len_b.  Keys in [off_b, len_b) that a word hides are read and masked.  Split rule, paging,
 //     merge, partials and combine are the one code path: the chain words give the bits of the causal call, all-ones those of
 //     causal = 0.  TREE = false compiles to the code and the kernel arguments it had.
-//   * KV8 = true (pfa_fa3_decode_q8; no window, no tree; DecodeQ8Params carries the descales): the cache holds OCP e4m3fn bytes, one per
+//   * KV8 = true (pfa_fa3_decode_q8; no window, no tree; DecodeKv8Part carries the descales): the cache holds OCP e4m3fn bytes, one per
 //     element, strides in elements = bytes, and one fp32 descale per (batch, K/V head) each for K and V, read by scalar loads once per
 //     item.  Tiles, splits, masks and descriptors are those of the 16-bit kernel (the record count ends at the split's last key in
 //     bytes, so rows past it read as zero bytes = +0).  K: an 8-byte load per lane per k-step, the 16-bit kernel's element-to-k-step
@@ -53,7 +53,7 @@
 //     multiplication of the epilogue (the normalisation, or the partial's write), so the combine kernel is reused unchanged.  With both
 //     descales 1 the result has the bits of the 16-bit kernel on the converted cache.  KV8 = false compiles to the code and the kernel
 //     arguments it had.
-//   * SINK = true (pfa_fa3_decode_sink; plain and WINDOW, no tree, no FP8 cache; Decode*SinkParams carry the pointer): an attention sink,
+//   * SINK = true (pfa_fa3_decode_sink; plain and WINDOW, no tree, no FP8 cache; DecodeSinkPart carries the pointer): an attention sink,
 //     one fp32 value per QUERY head in the units of the scaled scores, is one more key with that score and a zero value row.  Nothing
 //     in front of the waves' merge changes.  In the merge, the workgroup of the item's split 0 takes the row's sink (a vector load: the
 //     rows of a packed head group belong to different query heads) times log2(e) as a fifth partial (m, l, O) = (sink, 1, 0): the
@@ -71,6 +71,7 @@
 #include <type_traits>
 
 #include "fp8_cvt.h"               // cvt_e4m3x8: the KV8 conversion, shared with fa3_prefill_kernel.h
+#include "param_parts.h"
 
 namespace pfa {
 namespace dec {
@@ -124,34 +125,37 @@ struct DecodeParams {
     int32_t page_size, num_pages;
 };
 
-// WINDOW only: the sliding window, 1 <= window <= Smax (the host clamps it)
-struct DecodeWinParams : DecodeParams {
+// The mode flags' parts, behind the base in this order.  WINDOW: the sliding window, 1 <= window <= Smax (the host clamps it)
+struct DecodeWindowPart {
     int32_t window;
 };
-// TREE only: one 64-bit visibility word per query row, words[b * tree_sb + i]
-struct DecodeTreeParams : DecodeParams {
+// TREE: one 64-bit visibility word per query row, words[b * tree_sb + i]
+struct DecodeTreePart {
     const uint64_t* tree;
     int64_t tree_sb;
 };
-// KV8 only: fp32 descales, k_descale[b * ds_sb + kvh] (ds_sb = 0: one row for every batch)
-struct DecodeQ8Params : DecodeParams {
+// KV8: fp32 descales, k_descale[b * ds_sb + kvh] (ds_sb = 0: one row for every batch)
+struct DecodeKv8Part {
     const float* k_descale;
     const float* v_descale;
     int64_t ds_sb;
 };
-// SINK only: one fp32 sink per query head, sinks[h], in the units of the scaled scores (natural log)
-struct DecodeSinkParams : DecodeParams {
+// SINK: one fp32 sink per query head, sinks[h], in the units of the scaled scores (natural log)
+struct DecodeSinkPart {
     const float* sinks;
 };
-struct DecodeWinSinkParams : DecodeWinParams {
-    const float* sinks;
-};
-template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false> struct DecodeParamsOf { typedef DecodeParams type; };
-template <> struct DecodeParamsOf<true, false> { typedef DecodeWinParams type; };
-template <> struct DecodeParamsOf<false, true> { typedef DecodeTreeParams type; };
-template <> struct DecodeParamsOf<false, false, true> { typedef DecodeQ8Params type; };
-template <> struct DecodeParamsOf<false, false, false, true> { typedef DecodeSinkParams type; };
-template <> struct DecodeParamsOf<true, false, false, true> { typedef DecodeWinSinkParams type; };
+template <bool WINDOW, bool TREE, bool KV8, bool SINK>
+struct DecodeBlock : DecodeParams, PartIf<WINDOW, DecodeWindowPart>, PartIf<TREE, DecodeTreePart>, PartIf<KV8, DecodeKv8Part>,
+                     PartIf<SINK, DecodeSinkPart> {};
+template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false>
+struct DecodeParamsOf { typedef DecodeBlock<WINDOW, TREE, KV8, SINK> type; };
+
+// Which instantiations of fa3_decode_kernel exist: the one statement of it, for the kernel and the host's dispatch.
+constexpr bool decode_kernel_exists(bool WINDOW, bool TREE, bool KV8, bool SINK) {
+    return !(WINDOW && TREE)                // a tree does not combine with a window
+           && !(SINK && (TREE || KV8))      // the sink is built for the plain and the windowed 16-bit cache
+           && !(KV8 && (WINDOW || TREE));   // the FP8 cache takes neither a window nor a tree
+}
 
 template <typename T> struct DElem;
 template <> struct DElem<__bf16> {
@@ -215,9 +219,7 @@ __device__ __forceinline__ void split_range(const DecodeParams& p, int s, int ba
 
 template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false, bool KV8 = false, bool SINK = false>
 __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE, KV8, SINK>::type p) {
-    static_assert(!(WINDOW && TREE), "a tree does not combine with a window");
-    static_assert(!(SINK && (TREE || KV8)), "the sink is built for the plain and the windowed 16-bit cache");
-    static_assert(!(KV8 && (WINDOW || TREE)), "the FP8 cache takes neither a window nor a tree");
+    static_assert(decode_kernel_exists(WINDOW, TREE, KV8, SINK), "no such mode set: see decode_kernel_exists");
     using E = DElem<T>;
     using v8 = typename E::v8;
     using v4 = typename E::v4;

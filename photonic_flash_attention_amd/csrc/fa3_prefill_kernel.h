@@ -38,7 +38,7 @@
 // The Q clamp (row min(my_q, Sq_b - 1)) and therefore the rescale points of the wave-wide deferred max are those of the uniform kernel
 // at Sq = Sq_b, so a ragged call returns the bits of per-batch uniform calls.
 //
-// WINDOW (pfa_fa3_prefill_ex / pfa_fa3_prefill_varlen_ex with a window W; CAUSAL only, Prefill*WinParams carry W, clamped to Smax by the
+// WINDOW (pfa_fa3_prefill_ex / pfa_fa3_prefill_varlen_ex with a window W; CAUSAL only, PrefillWindowPart carries W, clamped to Smax by the
 // host): row i sees key j iff j < len_b, j <= i + off_b and j > i + off_b - W.  What changes:
 //   - a block's first tile is j_lo = max(0, q0 + off_b - W + 1) / 64 and its loop runs j_lo .. nt - 1.  Tiles below it are never
 //     fetched, so keys below floor64(max(0, off_b - W + 1)) -- block 0's first tile -- are never read by anybody;
@@ -53,7 +53,7 @@
 //     advances by addition as before; the first scalar table load is that entry, and entries below it are never read.
 // WINDOW = false compiles to the code and the kernel arguments the instantiation had.
 //
-// SPLIT (pfa_fa3_prefill_split with N = nsplit > 1 key splits; uniform only -- no VARLEN, no WINDOW; PrefillSplitParams carry nsplit and the
+// SPLIT (pfa_fa3_prefill_split with N = nsplit > 1 key splits; uniform only -- no VARLEN, no WINDOW; PrefillSplitPart carries nsplit and the
 // two workspace bases): the keys of a q block are cut over N workgroups, each writes an fp32 partial result, and pfa_attn_merge joins
 // the N parts in split order.  What changes:
 //   - grid B * H * nqblk * N from host shapes; blockIdx = ((qrank * B * H) + bh) * N + s.  The q-block rank stays the slowest index,
@@ -74,7 +74,7 @@
 //     LSE = -inf from the epilogue below, and the merge skips such a part.
 // SPLIT = false compiles to the code and the kernel arguments the instantiation had.
 //
-// KV8 (pfa_fa3_prefill_q8 / pfa_fa3_prefill_varlen_q8; no WINDOW, no SPLIT; Prefill*Q8Params carry the descales): the cache holds OCP
+// KV8 (pfa_fa3_prefill_q8 / pfa_fa3_prefill_varlen_q8; no WINDOW, no SPLIT; PrefillKv8Part carries the descales): the cache holds OCP
 // e4m3fn bytes, one per element -- strides in elements = bytes, every stride a multiple of 16, 16-byte bases -- and an element stands for
 // e4m3(byte) * descale[b * ds_sb + kvh].  LDS-DMA cannot widen a byte, so the tiles are staged through registers, one tile ahead of the
 // LDS image and two ahead of the math.  What changes:
@@ -98,8 +98,8 @@
 //     converted cache.
 // KV8 = false compiles to the code and the kernel arguments the instantiation had.
 //
-// SINK (pfa_fa3_prefill_sink / _varlen_sink / _split_sink; uniform, VARLEN and SPLIT, with and without WINDOW; no KV8; Prefill*SinkParams
-// carry the pointer): an attention sink, one fp32 value per QUERY head in the units of the scaled scores, is one more key with that
+// SINK (pfa_fa3_prefill_sink / _varlen_sink / _split_sink; uniform, VARLEN and SPLIT, with and without WINDOW; no KV8; PrefillSinkPart
+// carries the pointer): an attention sink, one fp32 value per QUERY head in the units of the scaled scores, is one more key with that
 // score and a zero value row.  The tile loop and everything in front of it are untouched; a workgroup serves one head, so the sink is one
 // scalar load in the prologue.  The epilogue, with mc = m_run * c the deferred-max reference in log2 units and s2 = sinks[hh] * log2(e):
 //     M' = max(mc, s2),  l' = l_tot * exp2(mc - M') + exp2(s2 - M'),  inv = exp2(mc - M') / l',  LSE = (M' + log2 l') ln 2.
@@ -115,6 +115,7 @@
 #pragma once
 #include "fa3_fwd_kernel.h"
 #include "fp8_cvt.h"
+#include "param_parts.h"
 
 namespace pfa {
 
@@ -138,63 +139,45 @@ struct PrefillParams {
     int32_t page_size, num_pages;
 };
 
-// VARLEN: q_sb / o_sb are unused, Sq is max_seqlen_q, lse is [H, total_q]
-struct PrefillVarlenParams : PrefillParams {
+// The mode flags' parts, behind the base in this order.  VARLEN: q_sb / o_sb are unused, Sq is max_seqlen_q, lse is [H, total_q]
+struct PrefillVarlenPart : TailPaddingReused {   // (window stands in its padding)
     const int32_t* cu_seqlens_q; // [B + 1] packed row of each batch's first query row
     int32_t total_q;             // rows of the packed q / o
 };
 // WINDOW: the sliding window, 1 <= window <= Smax
-struct PrefillWinParams : PrefillParams {
-    int32_t window;
-};
-struct PrefillVarlenWinParams : PrefillVarlenParams {
+struct PrefillWindowPart {
     int32_t window;
 };
 // SPLIT: the key splits (2 .. 8) and the workspace, partial O [nsplit][B][Sq][H][D] and partial LSE [nsplit][B][H][Sq], both fp32
-struct PrefillSplitParams : PrefillParams {
+struct PrefillSplitPart {
     int32_t nsplit;
     float* part_o;
     float* part_lse;
 };
 // KV8: fp32 descales, k_descale[b * ds_sb + kvh] (ds_sb = 0: one row for every batch)
-struct PrefillQ8Params : PrefillParams {
-    const float* k_descale;
-    const float* v_descale;
-    int64_t ds_sb;
-};
-struct PrefillVarlenQ8Params : PrefillVarlenParams {
+struct PrefillKv8Part {
     const float* k_descale;
     const float* v_descale;
     int64_t ds_sb;
 };
 // SINK: one fp32 sink per query head, sinks[h], in the units of the scaled scores (natural log)
-struct PrefillSinkParams : PrefillParams {
+struct PrefillSinkPart {
     const float* sinks;
 };
-struct PrefillVarlenSinkParams : PrefillVarlenParams {
-    const float* sinks;
-};
-struct PrefillWinSinkParams : PrefillWinParams {
-    const float* sinks;
-};
-struct PrefillVarlenWinSinkParams : PrefillVarlenWinParams {
-    const float* sinks;
-};
-struct PrefillSplitSinkParams : PrefillSplitParams {
-    const float* sinks;
-};
-template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, bool SINK = false> struct PrefillParamsOf { typedef PrefillParams type; };
-template <> struct PrefillParamsOf<true, false> { typedef PrefillVarlenParams type; };
-template <> struct PrefillParamsOf<false, true> { typedef PrefillWinParams type; };
-template <> struct PrefillParamsOf<true, true> { typedef PrefillVarlenWinParams type; };
-template <> struct PrefillParamsOf<false, false, true> { typedef PrefillSplitParams type; };
-template <> struct PrefillParamsOf<false, false, false, true> { typedef PrefillQ8Params type; };
-template <> struct PrefillParamsOf<true, false, false, true> { typedef PrefillVarlenQ8Params type; };
-template <> struct PrefillParamsOf<false, false, false, false, true> { typedef PrefillSinkParams type; };
-template <> struct PrefillParamsOf<true, false, false, false, true> { typedef PrefillVarlenSinkParams type; };
-template <> struct PrefillParamsOf<false, true, false, false, true> { typedef PrefillWinSinkParams type; };
-template <> struct PrefillParamsOf<true, true, false, false, true> { typedef PrefillVarlenWinSinkParams type; };
-template <> struct PrefillParamsOf<false, false, true, false, true> { typedef PrefillSplitSinkParams type; };
+template <bool VARLEN, bool WINDOW, bool SPLIT, bool KV8, bool SINK>
+struct PrefillBlock : PrefillParams, PartIf<VARLEN, PrefillVarlenPart>, PartIf<WINDOW, PrefillWindowPart>, PartIf<SPLIT, PrefillSplitPart>,
+                      PartIf<KV8, PrefillKv8Part>, PartIf<SINK, PrefillSinkPart> {};
+template <bool VARLEN, bool WINDOW = false, bool SPLIT = false, bool KV8 = false, bool SINK = false>
+struct PrefillParamsOf { typedef PrefillBlock<VARLEN, WINDOW, SPLIT, KV8, SINK> type; };
+
+// Which instantiations of fa3_prefill_kernel exist: the one statement of it, for the kernel, its table and the host's dispatch.
+constexpr bool prefill_kernel_exists(bool CAUSAL, bool SPLITP, int out_bytes, bool VARLEN, bool WINDOW, bool SPLIT, bool KV8, bool SINK) {
+    return !(SINK && KV8)                               // the sink is built for the 16-bit cache
+           && !(KV8 && (WINDOW || SPLIT))               // the FP8 cache takes neither a window nor a split over keys
+           && (CAUSAL || !WINDOW)                       // the window is cut from the causal diagonal
+           && !(SPLIT && (VARLEN || WINDOW))            // the split over keys is for the uniform, window-less call
+           && (!SPLIT || (SPLITP && out_bytes == 4));   // the partial results are fp32, P carried as hi + lo
+}
 
 typedef const __attribute__((address_space(4))) int32_t* prefill_table_ptr;   // read-only for the kernel's lifetime: scalar loads
 typedef const __attribute__((address_space(4))) float* prefill_f32_ptr;
@@ -202,11 +185,7 @@ typedef const __attribute__((address_space(4))) float* prefill_f32_ptr;
 template <typename T, int D, bool CAUSAL, bool SPLITP, bool PAGED, typename OT, bool VARLEN = false, bool WINDOW = false, bool SPLIT = false,
           bool KV8 = false, bool SINK = false>
 __global__ __launch_bounds__(FWD_THREADS, 2) void fa3_prefill_kernel(const typename PrefillParamsOf<VARLEN, WINDOW, SPLIT, KV8, SINK>::type p) {
-    static_assert(!(SINK && KV8), "the sink is built for the 16-bit cache");
-    static_assert(!KV8 || (!WINDOW && !SPLIT), "the FP8 cache takes neither a window nor a split over keys");
-    static_assert(CAUSAL || !WINDOW, "the window is cut from the causal diagonal");
-    static_assert(!SPLIT || (!VARLEN && !WINDOW), "the split over keys is for the uniform, window-less call");
-    static_assert(!SPLIT || (SPLITP && sizeof(OT) == 4), "the partial results are fp32, P carried as hi + lo");
+    static_assert(prefill_kernel_exists(CAUSAL, SPLITP, sizeof(OT), VARLEN, WINDOW, SPLIT, KV8, SINK), "no such mode set: see prefill_kernel_exists");
     constexpr int NW = FWD_WAVES, BLOCK_M = FWD_BLOCK_M;
     using E = Elem<T>;
     using v8 = typename E::v8;

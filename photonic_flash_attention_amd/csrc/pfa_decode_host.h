@@ -1,9 +1,12 @@
 // pfa_decode_host.h -- what pfa_decode_capi.hip, pfa_decode_fp8_capi.hip and pfa_decode_sink_capi.hip share behind pfa_fa3_decode_args (internal): the split rule,
-// the kernel tables of fa3_decode_kernel and its combine, the parameter fill with the workspace layout, and the launch with its combine.
-// WINDOW / TREE / KV8 / SINK are fixed by the unit that calls, so each unit instantiates its own kernels only.
+// validation, the describe, the kernel tables of fa3_decode_kernel and its combine, the parameter fill with the workspace layout, and the
+// launch with its combine.  A unit names the mode sets it instantiates (pfa_cache_modes.h: ON, MAY), so each unit instantiates its own
+// kernels only.
 #pragma once
+#include <stdio.h>
+
 #include "fa3_decode_kernel.h"
-#include "pfa_host.h"
+#include "pfa_cache_modes.h"
 
 namespace pfa {
 namespace decode {
@@ -66,7 +69,7 @@ inline KernelFn<dec::DecodeParams> combine(int dtype, int D, bool out32) {
     });
 }
 
-// What every mode's block holds of checked arguments and their plan; the mode's own members (window, tree, descales, sinks) are the caller's.
+// What every mode's block holds of checked arguments and their plan; the mode's own members are fill_modes'.
 // The workspace of a split call is the partial O [nsplit][B][H][Sq][D] and behind it the partial (m, l) pairs, both fp32.
 inline void fill_params(dec::DecodeParams& p, const pfa_fa3_decode_args* a, const Plan& pl) {
     fill_attention_params(p, a);
@@ -77,18 +80,112 @@ inline void fill_params(dec::DecodeParams& p, const pfa_fa3_decode_args* a, cons
     p.causal = a->causal != 0;
 }
 
-// of checked arguments and a filled block: the main kernel on `stream` and, where the plan splits, the combine behind it
-template <bool WINDOW, bool TREE = false, bool KV8 = false, bool SINK = false>
-int launch(const pfa_fa3_decode_args* a, const Plan& pl, const Params<WINDOW, TREE, KV8, SINK>& p, void* stream) {
-    const bool out32 = a->dtype_out == PFA_DTYPE_FP32;
-    const auto fn = kernel<WINDOW, TREE, KV8, SINK>(a->dtype_in, a->D, out32, a->block_table != nullptr);
-    const auto cfn = combine(a->dtype_in, a->D, out32);
-    const DeviceScope dev(a->device_id);
-    if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    const int st_main = pfa::launch(fn, dim3((unsigned)pl.items), dec::THREADS, p, 0, stream);
-    if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
-    const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
-    return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+// The tree block's field rules (include/pfa_hip.h, pfa_fa3_tree_mask), in the order their errors are reported; NULL is no tree.
+// pointers = false leaves out the two rules about `words` (the workspace query takes no pointers).
+inline int check_tree(const pfa_fa3_tree_mask* t, const pfa_fa3_decode_args* a, int window, bool pointers) {
+    if (!t) return PFA_OK;
+    if (t->size != sizeof(pfa_fa3_tree_mask)) return PFA_ERR_STRUCT_SIZE;
+    if (t->flags != 0) return PFA_ERR_FLAGS;
+    if (pointers) {
+        if (!t->words) return PFA_ERR_NULL;
+        if ((reinterpret_cast<uintptr_t>(t->words) & 7u) != 0) return PFA_ERR_ALIGN;
+    }
+    if (t->stride_b < a->Sq) return PFA_ERR_SHAPE;
+    if (a->causal == 0) return PFA_ERR_FLAGS;     // the words replace the causal triangle
+    if (window > 0) return PFA_ERR_FLAGS;         // a node's window would be by depth, not by row index
+    return PFA_OK;
+}
+
+// The optional blocks of the decode calls; a unit passes the ones its exports take
+struct Blocks {
+    const pfa_fa3_cache_ext* ext = nullptr;
+    const pfa_fa3_tree_mask* tree = nullptr;
+    const pfa_fa3_kv_quant* quant = nullptr;
+    const pfa_fa3_sinks* sinks = nullptr;
+};
+
+// Every decode call's check -> PFA_OK, the modes in *m and their plan in *pl.  KV8: the unit over an FP8 cache, whose quant block is
+// not optional.  The split count and the workspace never depend on tree, quant or sinks, so a captured graph replays while they change.
+template <bool KV8 = false>
+int check(const pfa_fa3_decode_args* a, const Blocks& b, CacheModes* m, Plan* pl) {
+    *m = CacheModes{};
+    int st = check_blocks_front<KV8>(a, b.ext, b.quant, b.sinks);
+    if (st != PFA_OK) return st;
+    st = check_cache_args(a, 64);
+    if (st != PFA_OK) return st;
+    st = check_cache_ext(b.ext, a->causal, a->Smax, &m->window);
+    if (st != PFA_OK) return st;
+    st = check_tree(b.tree, a, m->window, true);
+    if (st != PFA_OK) return st;
+    *pl = plan(a, m->window);
+    if (pl->items > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (a->D / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
+    if (pl->ws_bytes) {
+        if (!a->workspace || a->workspace_bytes < pl->ws_bytes) return PFA_ERR_NULL;
+        if (!aligned16(a->workspace)) return PFA_ERR_ALIGN;
+    }
+    m->tree = b.tree; m->quant = b.quant; m->sinks = b.sinks;
+    return PFA_OK;
+}
+
+// ... of the workspace queries, which stop in front of the pointer rules -> the bytes, 0 for arguments no plan can be made from
+template <bool KV8 = false>
+size_t workspace_bytes(const pfa_fa3_decode_args* a, const Blocks& b) {
+    if (check_blocks_front<KV8>(a, b.ext, b.quant, b.sinks, false) != PFA_OK) return 0;
+    if (!a || a->size != sizeof(pfa_fa3_decode_args) || check_cache_shape(a) != PFA_OK) return 0;
+    int window;
+    if (check_cache_ext(b.ext, a->causal, a->Smax, &window) != PFA_OK || check_tree(b.tree, a, window, false) != PFA_OK) return 0;
+    return plan(a, window).ws_bytes;
+}
+
+template <bool KV8 = false>
+int check_only(const pfa_fa3_decode_args* a, const Blocks& b) {
+    CacheModes m;
+    Plan pl;
+    return check<KV8>(a, b, &m, &pl);
+}
+
+// of arguments that pass: the kernel's name into buf, the split count into *nsplit -> workgroups
+template <bool KV8 = false>
+int describe(const pfa_fa3_decode_args* a, const Blocks& b, char* buf, size_t n, int32_t* nsplit) {
+    CacheModes m;
+    Plan pl;
+    const int st = check<KV8>(a, b, &m, &pl);
+    if (st != PFA_OK) return st;
+    if (buf && n)
+        snprintf(buf, n, "fa3_decode_%s_d%d_%s%s%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
+                 a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", m.tree ? "_tree" : m.window ? "_win" : "", m.quant ? "_kv8" : "",
+                 m.sinks ? "_sink" : "", pl.nsplit > 1 ? "+combine" : "", a->block_table ? "_paged" : "");
+    if (nsplit) *nsplit = pl.nsplit;
+    return (int)pl.items;
+}
+
+// of arguments that pass: the block of the call's mode set, the main kernel on `stream` and, where the plan splits, the combine behind it.
+// The run-time modes become the kernel's flags here; a set the unit does not name (ON, MAY) instantiates nothing.
+template <unsigned ON, unsigned MAY = 0>
+int run(const pfa_fa3_decode_args* a, const Blocks& b, void* stream) {
+    CacheModes m;
+    Plan pl;
+    const int st = check<(ON & MODE_KV8) != 0>(a, b, &m, &pl);
+    if (st != PFA_OK) return st;
+    return dispatch_bools([&](auto w, auto t, auto k8, auto sk) -> int {
+        constexpr bool W = w.value, T = t.value, K8 = k8.value, SK = sk.value;
+        if constexpr (!unit_has(ON, MAY, mode_bits(W, T, false, K8, SK)) || !dec::decode_kernel_exists(W, T, K8, SK)) {
+            return PFA_ERR_FLAGS;      // not this unit's: its check lets no such call through
+        } else {
+            Params<W, T, K8, SK> p;
+            fill_params(p, a, pl);
+            fill_modes<W, T, false, K8, SK>(p, m);
+            const bool out32 = a->dtype_out == PFA_DTYPE_FP32;
+            const auto fn = kernel<W, T, K8, SK>(a->dtype_in, a->D, out32, a->block_table != nullptr);
+            const auto cfn = combine(a->dtype_in, a->D, out32);
+            const DeviceScope dev(a->device_id);
+            if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
+            const int st_main = pfa::launch(fn, dim3((unsigned)pl.items), dec::THREADS, p, 0, stream);
+            if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
+            const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
+            return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+        }
+    }, m.window != 0, m.tree != nullptr, m.quant != nullptr, m.sinks != nullptr);
 }
 
 }  // namespace decode

@@ -1,5 +1,5 @@
-// pfa_fp8_host.h -- what the entry-point files of the FP8 KV cache share (pfa_decode_fp8_capi.hip, pfa_kv_append_fp8_capi.hip and, through
-// pfa_prefill_host.h, the two pfa_prefill*_fp8_capi.hip): the field rules of pfa_fa3_kv_quant and of an argument block's cache tensors
+// pfa_fp8_host.h -- what the entry-point files of the FP8 KV cache share (pfa_kv_append_fp8_capi.hip and, through
+// pfa_cache_modes.h, pfa_decode_fp8_capi.hip and the two pfa_prefill*_fp8_capi.hip): the field rules of pfa_fa3_kv_quant and of an argument block's cache tensors
 // when they hold one-byte elements, and the refusal of a window.  Internal.
 #pragma once
 #include "pfa_host.h"

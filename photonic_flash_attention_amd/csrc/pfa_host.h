@@ -53,7 +53,7 @@ struct same_type { using type = T; };       // keeps a function parameter out of
 // The tail of a launch: opt in to more than 64 KiB of dynamic LDS where the kernel asks for it (idempotent, per function), enqueue with
 // the parameter block as the one kernel argument, and map a failure to PFA_ERR_LAUNCH (its code kept for pfa_last_hip_error).
 // Params comes from the kernel alone; the block converts to it, so a block of another type does not compile and a derived block
-// (DecodeWinParams for the combine kernel's DecodeParams) is passed as its base, which is what the kernel copies.
+// (a decode block with mode parts for the combine kernel's DecodeParams) is passed as its base, which is what the kernel copies.
 template <typename Params>
 inline int launch(KernelFn<Params> fn, dim3 grid, unsigned threads, const typename same_type<Params>::type& p, size_t lds, void* stream) {
     const void* f = reinterpret_cast<const void*>(fn);
@@ -204,7 +204,7 @@ inline int check_cache_args(const Args* a, int max_sq) {
     return check_paging(a->block_table, a->block_table_stride_b, a->page_size, a->num_pages, a->Smax);
 }
 
-// What every kernel parameter block over a cache carries (DecodeParams, Prefill*Params, KvAppendParams name these members alike):
+// What every kernel parameter block over a cache carries (DecodeParams, PrefillParams, KvAppendParams name these members alike):
 // the cache strides, the lengths and the paging fields.
 template <typename Params, typename Args>
 inline void fill_cache_params(Params& p, const Args* a) {
@@ -212,7 +212,7 @@ inline void fill_cache_params(Params& p, const Args* a) {
     PFA_FILL_STRIDES(p, a, k); PFA_FILL_STRIDES(p, a, v);
     p.block_table = a->block_table; p.bt_sb = a->block_table_stride_b; p.page_size = a->page_size; p.num_pages = a->num_pages;
 }
-// ... and on top of them what the attention kernels' blocks (DecodeParams, Prefill*Params) share: the tensors, q / o strides, scale.
+// ... and on top of them what the attention kernels' blocks (DecodeParams, PrefillParams) share: the tensors, q / o strides, scale.
 template <typename Params, typename Args>
 inline void fill_attention_params(Params& p, const Args* a) {
     fill_cache_params(p, a);

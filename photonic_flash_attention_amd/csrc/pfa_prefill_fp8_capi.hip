@@ -1,37 +1,24 @@
-// pfa_prefill_fp8_capi.hip -- C ABI of the forward over an FP8 (e4m3fn) KV cache (include/pfa_hip.h, pfa_fa3_prefill_q8*): the rules of
-// pfa_fa3_kv_quant, then everything pfa_fa3_prefill_check_ex says of the same argument block, and the launch of the KV8 instantiations of
-// fa3_prefill_kernel.  Every other field rule and the workgroups are asked of the 16-bit call, so the two cannot drift apart.  A file of
+// pfa_prefill_fp8_capi.hip -- C ABI of the forward over an FP8 (e4m3fn) KV cache (include/pfa_hip.h, pfa_fa3_prefill_q8*): the entry
+// points and the uniform KV8 instantiations of fa3_prefill_kernel.  The rules of pfa_fa3_kv_quant come first, then everything
+// pfa_fa3_prefill_check_ex says of the same argument block: one check in pfa_prefill_host.h, so the two cannot drift apart.  A file of
 // its own: the 16-bit objects are built from what they were built from, and the 32 kernels compile side by side with theirs.
 // No allocation, no synchronisation, no process-wide state, no workspace.
 #include "pfa_prefill_host.h"
 
-namespace {
-
-int check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant) {
-    const int st = pfa::prefill::check_q8_front(a, ext, quant);
-    return st != PFA_OK ? st : pfa_fa3_prefill_check_ex(a, ext);
-}
-
-}  // namespace
+using namespace pfa::prefill;
 
 extern "C" {
 
 int pfa_fa3_prefill_q8_check(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant) {
-    return check(a, ext, quant);
+    return entry_check<true>(a, ext, quant, nullptr);
 }
 
 int pfa_fa3_prefill_q8_describe(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, char* buf, size_t n) {
-    const int st = pfa::prefill::check_q8_front(a, ext, quant);
-    if (st != PFA_OK) return st;
-    char name[160];
-    const int items = pfa_fa3_prefill_describe_ex(a, ext, name, sizeof name);
-    if (items >= 0) pfa::prefill::name_q8(name, buf, n);
-    return items;
+    return entry_describe<true>(a, ext, quant, nullptr, buf, n);
 }
 
 int pfa_fa3_prefill_q8(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream) {
-    const int st = check(a, ext, quant);
-    return st != PFA_OK ? st : pfa::prefill::launch_q8<false>(a, quant, stream);
+    return entry_run<pfa::MODE_KV8>(a, ext, quant, nullptr, stream);
 }
 
 }  // extern "C"

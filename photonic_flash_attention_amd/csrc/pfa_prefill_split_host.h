@@ -1,6 +1,6 @@
 // pfa_prefill_split_host.h -- what pfa_prefill_split_capi.hip and pfa_prefill_split_sink_capi.hip share behind pfa_fa3_prefill_split's
-// arguments (internal): the plan of key_splits = 0, the workspace layout, the merge's argument block, validation, and the launch of
-// fa3_prefill_kernel's SPLIT instantiations with the merge behind it.  SINK is fixed by the unit that calls.
+// arguments (internal): the plan of key_splits = 0, the workspace layout, the merge's argument block, validation, and the bodies of the
+// entry points: the launch of fa3_prefill_kernel's SPLIT instantiations (with MODE_SINK in the sink unit) and the merge behind it.
 #pragma once
 #include "pfa_prefill_host.h"
 
@@ -65,41 +65,69 @@ inline pfa_attn_merge_args merge_args(const pfa_fa3_decode_args* a, int nsplit) 
     return m;
 }
 
-// -> PFA_OK and the resolved count in *nsplit.  A count of 1 is pfa_fa3_prefill's check and nothing else.
-inline int check(const pfa_fa3_decode_args* a, int32_t key_splits, int* nsplit) {
-    *nsplit = 1;
-    int st = check_cache_args(a, INT_MAX);
+// -> PFA_OK and the modes in *m: the resolved count and, above 1, the workspace bases; the sinks (NULL: none), whose own rules come
+// first.  A count of 1 is pfa_fa3_prefill's check and nothing else.
+inline int check(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, CacheModes* m) {
+    *m = CacheModes{};
+    int st = check_blocks_front<false>(a, nullptr, nullptr, sinks);
     if (st != PFA_OK) return st;
-    if (a->key_mask) return PFA_ERR_FLAGS;
+    st = check_cache_args(a, INT_MAX);
+    if (st != PFA_OK) return st;
+    st = prefill::check_own_rules(a);
+    if (st != PFA_OK) return st;
     const int ns = resolve(a, key_splits);
     if (ns < 0) return ns;
-    *nsplit = ns;
     if (prefill::workgroups(a) * ns > 0x7fffffffLL) return PFA_ERR_SHAPE;
+    m->sinks = sinks;
     if (ns == 1) return PFA_OK;
     // the merge writes o: a 16-bit o in rows of 8 elements
     if (a->dtype_out != PFA_DTYPE_FP32 && !multiples_of(8, {a->o_stride_b, a->o_stride_h, a->o_stride_s})) return PFA_ERR_STRIDE;
     if (!a->workspace || a->workspace_bytes < workspace_bytes(a, ns)) return PFA_ERR_NULL;
     if (!aligned16(a->workspace)) return PFA_ERR_ALIGN;
-    const pfa_attn_merge_args m = merge_args(a, ns);
-    return pfa_attn_merge_check(&m);          // what is left of its rules: the merge's own grid
+    const pfa_attn_merge_args mg = merge_args(a, ns);
+    st = pfa_attn_merge_check(&mg);           // what is left of its rules: the merge's own grid
+    if (st != PFA_OK) return st;
+    m->nsplit = ns;
+    m->part_o = (float*)a->workspace;
+    m->part_lse = m->part_o + (int64_t)ns * part_elems(a);
+    return PFA_OK;
 }
 
-template <bool SINK>
-using Params_t = prefill::Params<false, false, true, false, SINK>;
-
-// of checked arguments and their resolved count ns > 1: the SPLIT kernel into the workspace (SINK: with the sinks, which split 0 of
-// every q block carries) and pfa_attn_merge, unchanged, behind it
-template <bool SINK = false>
-int run(const pfa_fa3_decode_args* a, int ns, const pfa_fa3_sinks* sinks, void* stream) {
-    Params_t<SINK> p;
-    p.nsplit = ns;
-    p.part_o = (float*)a->workspace;
-    p.part_lse = p.part_o + (int64_t)ns * part_elems(a);
-    if constexpr (SINK) p.sinks = sinks->sinks;
-    const int st_main = prefill::launch<false, false, true, false, SINK>(a, p, stream, ns);      // the caller's device is back before the merge
+// the bodies of the entry points, with and without sinks
+inline size_t entry_workspace_bytes(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks) {
+    if (sinks && check_sinks(sinks, false) != PFA_OK) return 0;
+    const int ns = resolve_from_shapes(a, key_splits);
+    return ns < 0 ? 0 : workspace_bytes(a, ns);
+}
+inline int entry_check(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks) {
+    CacheModes m;
+    return check(a, key_splits, sinks, &m);
+}
+inline int entry_describe(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, char* buf, size_t n, int32_t* nsplit) {
+    CacheModes m;
+    const int st = check(a, key_splits, sinks, &m);
+    if (st != PFA_OK) return st;
+    if (nsplit) *nsplit = m.nsplit;
+    return prefill::describe(a, m, buf, n);
+}
+// ON: MODE_SPLIT, with MODE_SINK in the sink unit.  A count of 1 is the unsplit call (its export: the kernel function, grid and bits are
+// that unit's); above 1 the SPLIT kernel into the workspace (SINK: with the sinks, which split 0 of every q block carries) and
+// pfa_attn_merge, unchanged, behind it.
+template <unsigned ON>
+int entry_run(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, void* stream) {
+    if constexpr ((ON & MODE_SINK) != 0)
+        if (!sinks) return pfa_fa3_prefill_split(a, key_splits, stream);       // a NULL block is the sink-less call itself
+    CacheModes m;
+    const int st = check(a, key_splits, sinks, &m);
+    if (st != PFA_OK) return st;
+    if (m.nsplit == 1) {
+        if constexpr ((ON & MODE_SINK) != 0) return pfa_fa3_prefill_sink(a, nullptr, sinks, stream);
+        else return pfa_fa3_prefill(a, stream);
+    }
+    const int st_main = prefill::launch<ON>(a, m, stream);      // the caller's device is back before the merge
     if (st_main != PFA_OK) return st_main;
-    const pfa_attn_merge_args m = merge_args(a, ns);
-    return pfa_attn_merge(&m, stream);
+    const pfa_attn_merge_args mg = merge_args(a, m.nsplit);
+    return pfa_attn_merge(&mg, stream);
 }
 
 }  // namespace prefill_split

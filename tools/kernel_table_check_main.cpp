@@ -8,7 +8,7 @@
 //   hipcc -std=c++17 --offload-arch=gfx950 -Iinclude -Iphotonic_flash_attention_amd/csrc \
 //         -x hip tools/kernel_table_check_main.cpp -o kernel_table_check && ./kernel_table_check
 //
-// (About two minutes: the device side of all 274 kernels is compiled into the one program, whose link wants it.)
+// (A few minutes: the device side of all 418 kernels is compiled into the one program, whose link wants it.)
 #include <stdio.h>
 
 #include <set>
@@ -71,15 +71,15 @@ struct Table {
     }
 };
 
-template <bool WINDOW, bool TREE, bool KV8>
+template <bool WINDOW, bool TREE, bool KV8, bool SINK = false>
 Table decode_table(const char* name) {
     Table tb{name};
     each_elem_dim([&](auto e) {
         using T = typename decltype(e)::type;
         constexpr int D = decltype(e)::D;
         each_bools<2>([&](auto o32, auto pg) {
-            tb.add(pfa::decode::kernel<WINDOW, TREE, KV8>(e.dtype, D, o32.value, pg.value),
-                   &pfa::dec::fa3_decode_kernel<T, D, Out<o32.value, T>, pg.value, WINDOW, TREE, KV8>);
+            tb.add(pfa::decode::kernel<WINDOW, TREE, KV8, SINK>(e.dtype, D, o32.value, pg.value),
+                   &pfa::dec::fa3_decode_kernel<T, D, Out<o32.value, T>, pg.value, WINDOW, TREE, KV8, SINK>);
         });
     });
     return tb;
@@ -95,10 +95,11 @@ Table combine_table() {
     return tb;
 }
 
-// nullptr where the kernel's static_asserts allow no instantiation: a window without the causal flag, split parts that are not fp32
-template <bool VARLEN, bool WINDOW, bool SPLIT, bool KV8>
+// nullptr where the kernel allows no instantiation: a window without the causal flag, split parts that are not fp32 (spelled out here, not
+// asked of prefill_kernel_exists, which the table under test asks)
+template <bool VARLEN, bool WINDOW, bool SPLIT, bool KV8, bool SINK = false>
 Table prefill_table(const char* name) {
-    using Fn = pfa::KernelFn<pfa::prefill::Params<VARLEN, WINDOW, SPLIT, KV8>>;
+    using Fn = pfa::KernelFn<pfa::prefill::Params<VARLEN, WINDOW, SPLIT, KV8, SINK>>;
     Table tb{name};
     each_elem_dim([&](auto e) {
         using T = typename decltype(e)::type;
@@ -106,17 +107,17 @@ Table prefill_table(const char* name) {
         each_bools<3>([&](auto c, auto pg, auto o32) {
             Fn want = nullptr;
             if constexpr (!(WINDOW && !c.value) && !(SPLIT && !o32.value))
-                want = &pfa::fa3_prefill_kernel<T, D, c.value, o32.value, pg.value, Out<o32.value, T>, VARLEN, WINDOW, SPLIT, KV8>;
-            tb.add(pfa::prefill::kernel<VARLEN, WINDOW, SPLIT, KV8>(e.dtype, D, c.value, pg.value, o32.value), want);
+                want = &pfa::fa3_prefill_kernel<T, D, c.value, o32.value, pg.value, Out<o32.value, T>, VARLEN, WINDOW, SPLIT, KV8, SINK>;
+            tb.add(pfa::prefill::kernel<VARLEN, WINDOW, SPLIT, KV8, SINK>(e.dtype, D, c.value, pg.value, o32.value), want);
         });
     });
     return tb;
 }
-template <bool VARLEN>
+template <bool VARLEN, bool SINK = false>
 Table prefill16_table(const char* name) {
     Table tb{name};
-    tb.merge(prefill_table<VARLEN, false, false, false>(""));
-    tb.merge(prefill_table<VARLEN, true, false, false>(""));
+    tb.merge(prefill_table<VARLEN, false, false, false, SINK>(""));
+    tb.merge(prefill_table<VARLEN, true, false, false, SINK>(""));
     return tb;
 }
 
@@ -145,12 +146,19 @@ int main() {
     dec16.merge(none); dec16.merge(win); dec16.merge(tree);
     dec16.report(48);
     decode_table<false, false, true>("decode FP8").report(16);
+    Table sink = decode_table<false, false, false, true>("decode sink: none"), wsink = decode_table<true, false, false, true>("decode sink: window");
+    sink.report(16); wsink.report(16);
+    sink.merge(wsink); sink.name = "decode sink";
+    sink.report(32);
     combine_table().report(6);
     prefill16_table<false>("prefill uniform").report(48);
     prefill16_table<true>("prefill ragged").report(48);
     prefill_table<false, false, true, false>("prefill split").report(16);
     prefill_table<false, false, false, true>("prefill FP8 uniform").report(32);
     prefill_table<true, false, false, true>("prefill FP8 ragged").report(32);
+    prefill16_table<false, true>("prefill sink uniform").report(48);
+    prefill16_table<true, true>("prefill sink ragged").report(48);
+    prefill_table<false, false, true, false, true>("prefill sink split").report(16);
     Table kv{"kv_append"}, kv8{"kv_append_q8"}, rope{"rope_append"};
     kv_append_rows<false, void>(kv);
     kv_append_rows<true, __bf16>(kv8); kv_append_rows<true, _Float16>(kv8);
