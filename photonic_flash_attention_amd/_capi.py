@@ -349,12 +349,13 @@ def _make(cls, kw):
     return a
 
 
-def _describe(export: str, args, *ext, nsplit: bool = False):
+def _describe(export: str, args, *mid, nsplit: bool = False):
     """One ``*_describe`` export: -> ``(kernel name, workgroups)``, with ``nsplit`` also the call's int32 out-parameter.
-    ``ext``: nothing, or the ``_ex`` form's extension block (None: the NULL extension)."""
+    ``mid``: what the call takes between its argument block and the buffer -- an option block goes by reference (None: the NULL block),
+    a plain value such as ``key_splits`` as it is."""
     buf = C.create_string_buffer(128)
     ns = C.c_int32(0)
-    refs = [None if e is None else C.byref(e) for e in ext] + [buf, 128] + ([C.byref(ns)] if nsplit else [])
+    refs = [C.byref(m) if isinstance(m, C.Structure) else m for m in mid] + [buf, 128] + ([C.byref(ns)] if nsplit else [])
     n = getattr(load(), export)(C.byref(args), *refs)
     if n < 0:
         check_status(n)
@@ -455,13 +456,7 @@ def describe_prefill_varlen_sink(args: PfaFa3PrefillVarlenArgs, ext: Optional[Pf
 
 def describe_prefill_split_sink(args: PfaFa3DecodeArgs, key_splits: int, sinks: Optional[PfaFa3Sinks]):
     """``describe_prefill_split`` of ``pfa_fa3_prefill_split_sink``."""
-    buf = C.create_string_buffer(128)
-    ns = C.c_int32(0)
-    n = load().pfa_fa3_prefill_split_sink_describe(C.byref(args), int(key_splits), None if sinks is None else C.byref(sinks), buf, 128,
-                                                   C.byref(ns))
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n, ns.value
+    return _describe("pfa_fa3_prefill_split_sink_describe", args, int(key_splits), sinks, nsplit=True)
 
 
 def describe_prefill_ex(args: PfaFa3DecodeArgs, ext: Optional[PfaFa3CacheExt]):
@@ -477,12 +472,7 @@ def describe_prefill_varlen_ex(args: PfaFa3PrefillVarlenArgs, ext: Optional[PfaF
 def describe_prefill_split(args: PfaFa3DecodeArgs, key_splits: int):
     """-> (kernel name, workgroups of the main launch, resolved number of key splits) of ``pfa_fa3_prefill_split`` (``key_splits`` 0:
     the library's plan); "_split{N}+merge" marks a split call."""
-    buf = C.create_string_buffer(128)
-    ns = C.c_int32(0)
-    n = load().pfa_fa3_prefill_split_describe(C.byref(args), int(key_splits), buf, 128, C.byref(ns))
-    if n < 0:
-        check_status(n)
-    return buf.value.decode(), n, ns.value
+    return _describe("pfa_fa3_prefill_split_describe", args, int(key_splits), nsplit=True)
 
 
 def make_kv_append_args(**kw) -> PfaKvAppendArgs:

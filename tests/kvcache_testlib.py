@@ -12,10 +12,10 @@ agreement on which rows are -inf, and O exactly zero on those rows.  Every outpu
 from __future__ import annotations
 
 import functools
-import os
-import subprocess
 
 import torch
+
+from capi_testlib import built_lib  # noqa: F401  (kept here for the users of this module)
 
 EPS = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -11}
 INF, NAN = float("inf"), float("nan")
@@ -28,15 +28,6 @@ def device():
 
 def i32(x, dev=None):
     return torch.tensor(x, dtype=torch.int32, device=device() if dev is None else dev)
-
-
-def built_lib():
-    """The native library through ctypes, built first if it is missing: the body of the host test files' ``lib`` fixtures."""
-    from conftest import REPO
-    from photonic_flash_attention_amd import _capi
-    if not os.path.exists(_capi.LIB_PATH):
-        subprocess.run(["make", "-C", os.path.join(REPO, "photonic_flash_attention_amd", "csrc")], check=True)
-    return _capi.load()
 
 
 # --- the fp64 reference and the bounds -----------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """CPU-side tests (no GPU) of the merge of partial attention results (``pfa_attn_merge*``, ABI v9 additive) and of ``shared_prefix=``:
-exported symbols, the argument block's layout, every validation rule and the order the rules are reported in, the launch
+every validation rule and the order the rules are reported in, the launch
 description, the plain-torch model of the rule (``ops.attn_merge`` on CPU tensors: the executable specification the GPU tests compare
 the kernel with) against the rule in fp64 (``merge_ref64`` of tests/kvcache_testlib.py), its exactness property, and the
 ``ValueError``s ``shared_prefix`` raises before anything is enqueued."""
@@ -9,37 +9,18 @@ from __future__ import annotations
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import pytest
 import torch
 
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, lib  # noqa: F401
+from capi_testlib import attn_merge_args as _args
 from conftest import REPO
-from kvcache_testlib import built_lib, merge_ref64
+from kvcache_testlib import merge_ref64
 from photonic_flash_attention_amd import _capi, ops
 
-SYMBOLS = ("pfa_attn_merge_check", "pfa_attn_merge", "pfa_attn_merge_describe")
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 BF16, FP16, FP32 = 0, 1, 2
 INF, NAN = float("inf"), float("nan")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def _args(**over):
-    """A valid call: three fp32 parts of B 3, Sq 5, H 4, D 128 in [B, Sq, H, D] buffers, [B, H, Sq] LSEs, fp32 output and an output LSE."""
-    n = over.pop("_n", 3)
-    d = over.get("D", 128)
-    base = dict(n_parts=n, B=3, H=4, Sq=5, D=d, dtype_part=FP32, dtype_out=FP32,
-                o_part=[0x100000 * (k + 1) for k in range(n)], lse_part=[0x10000 * (k + 1) for k in range(n)], o=0x9000000, lse_out=0x8000,
-                op_stride_b=[5 * 4 * d] * n, op_stride_h=[d] * n, op_stride_s=[4 * d] * n,
-                lp_stride_b=[20] * n, lp_stride_h=[5] * n, lp_stride_s=[1] * n,
-                o_stride_b=5 * 4 * d, o_stride_h=d, o_stride_s=4 * d, lo_stride_b=20, lo_stride_h=5, lo_stride_s=1)
-    base.update(over)
-    return _capi.make_attn_merge_args(**base)
 
 
 def _set(a, field, n, value):
@@ -51,34 +32,9 @@ def _check(lib, a):
     return lib.pfa_attn_merge_check(C.byref(a))
 
 
-def test_every_attn_merge_symbol_is_declared_and_resolves(lib):
-    assert set(SYMBOLS) <= set(_capi.EXPORTS)
+def test_the_part_limit_is_eight():
     header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in SYMBOLS:
-        assert getattr(lib, sym) is not None
-        assert f"int {sym}(const pfa_attn_merge_args* a" in header
     assert "#define PFA_MERGE_MAX_PARTS 8" in header and _capi.PFA_MERGE_MAX_PARTS == 8
-
-
-def test_abi_version_and_argument_block_layout(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    A = _capi.PfaAttnMergeArgs
-    fields = [f for f, _ in A._fields_]
-    offs = ",".join(f"offsetof(pfa_attn_merge_args,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 3))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_kv_append_args),'
-                   f'sizeof(pfa_attn_merge_args),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[:2] == [C.sizeof(_capi.PfaFa3DecodeArgs), C.sizeof(_capi.PfaKvAppendArgs)]      # the neighbours are what they were
-    assert got[2:] == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    assert C.sizeof(A) == 8 + 2 * 64 + 16 + 6 * 64 + 48 + 40
-    for name in ("o_part", "lse_part", "o", "lse_out", "op_stride_b", "op_stride_h", "op_stride_s", "lp_stride_b", "lp_stride_h",
-                 "lp_stride_s", "o_stride_s", "lo_stride_b", "n_parts", "dtype_part", "dtype_out", "device_id", "reserved0", "reserved1"):
-        assert name in fields
 
 
 def test_attn_merge_argument_validation(lib):

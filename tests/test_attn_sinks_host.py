@@ -1,5 +1,5 @@
 """CPU-side tests (no GPU) of attention sinks over the KV cache (``pfa_fa3_sinks`` and the ``*_sink`` entry points, ABI v9 additive):
-exported symbols, the block's layout, a NULL block agreeing with the sink-less sibling, the block's rules in their documented order with
+a NULL block agreeing with the sink-less sibling, the block's rules in their documented order with
 the sibling's errors behind them, the describe names, plan and workspace equal to the sink-less call's, ``ops``' refusals on CPU
 tensors, the signatures -- and the reference helper of tests/test_hip_attn_sinks.py against an independent formulation, with the
 condition that the sinks those tests choose matter."""
@@ -8,83 +8,28 @@ from __future__ import annotations
 
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import INF, built_lib, reference
+from capi_testlib import ALIGN, FLAGS, NULL, SIZE, decode_args, decode_paged, lib, name_of, prefill_varlen_args, ref, sinks  # noqa: F401
+from kvcache_testlib import INF, reference
 from photonic_flash_attention_amd import _capi, ops
 from test_hip_attn_sinks import CASES, assert_sinks_matter, choose_sinks, with_sink
-
-SINK_SYMBOLS = {
-    "pfa_fa3_decode_sink_workspace_bytes": "size_t {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks",
-    "pfa_fa3_decode_sink_check": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks",
-    "pfa_fa3_decode_sink": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, void* stream",
-    "pfa_fa3_decode_sink_describe": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, char* buf",
-    "pfa_fa3_prefill_sink_check": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks",
-    "pfa_fa3_prefill_sink": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, void* stream",
-    "pfa_fa3_prefill_sink_describe": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, char* buf",
-    "pfa_fa3_prefill_varlen_sink_check": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks",
-    "pfa_fa3_prefill_varlen_sink": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, void* stream",
-    "pfa_fa3_prefill_varlen_sink_describe": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_sinks* sinks, char* buf",
-    "pfa_fa3_prefill_split_sink_workspace_bytes": "size_t {}(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks",
-    "pfa_fa3_prefill_split_sink_check": "int {}(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks",
-    "pfa_fa3_prefill_split_sink": "int {}(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, void* stream",
-    "pfa_fa3_prefill_split_sink_describe": "int {}(const pfa_fa3_decode_args* a, int32_t key_splits, const pfa_fa3_sinks* sinks, char* buf",
-}
-OK, NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = 0, -1, -2, -3, -4, -5, -6, -7, -10
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _dargs(**over):
     """A valid contiguous block of the decode / prefill calls: B 2, H 8, Hkv 2, Sq 4, Smax 4096, D 128, with a workspace."""
-    d, sq = over.get("D", 128), over.get("Sq", 4)
-    h, hkv, smax = over.get("H", 8), over.get("Hkv", 2), over.get("Smax", 4096)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=h, Hkv=hkv, Sq=sq, Smax=smax, D=d,
-                q_stride_b=sq * h * d, q_stride_h=d, q_stride_s=h * d, k_stride_b=smax * hkv * d, k_stride_h=d, k_stride_s=hkv * d,
-                v_stride_b=smax * hkv * d, v_stride_h=d, v_stride_s=hkv * d, o_stride_b=sq * h * d, o_stride_h=d, o_stride_s=h * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5, workspace=0x4000000, workspace_bytes=1 << 40)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    return decode_args(over, Sq=4)
 
 
 def _paged(**over):
-    d, hkv, smax = over.get("D", 128), over.get("Hkv", 2), over.get("Smax", 4096)
-    return _dargs(**{**dict(k_stride_b=128 * hkv * d, v_stride_b=128 * hkv * d, block_table=0x8000, block_table_stride_b=smax // 128,
-                            page_size=128, num_pages=100), **over})
+    return decode_paged(over, Sq=4)
 
 
 def _vargs(**over):
     """A valid block of the ragged call: B 5, H 8, Hkv 2, 640 packed rows, Smax 4096, D 128."""
-    d = over.get("D", 128)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, cu_seqlens_q=0x9000, B=5, H=8, Hkv=2, total_q=640,
-                max_seqlen_q=300, Smax=4096, D=d, q_stride_s=8 * d, q_stride_h=d, o_stride_s=8 * d, o_stride_h=d,
-                k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d, v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_prefill_varlen_args(**base)
-
-
-def _sinks(**kw):
-    return _capi.make_sinks(**{"sinks": 0xA000, **kw})
-
-
-def _ref(x):
-    return None if x is None else C.byref(x)
-
-
-def _name(fn, a, *mid, nsplit=False):
-    """(status or workgroups, name, nsplit) of a describe export."""
-    buf, ns = C.create_string_buffer(128), C.c_int32(-1)
-    n = fn(C.byref(a), *mid, buf, 128, *([C.byref(ns)] if nsplit else []))
-    return n, buf.value.decode(), ns.value
+    return prefill_varlen_args(over)
 
 
 # blocks good and bad, for every family: the sibling's verdict must come through
@@ -103,35 +48,6 @@ def _families(lib):
              lib.pfa_fa3_prefill_varlen_sink_describe, False)]
 
 
-def test_every_sink_symbol_is_declared_and_resolves(lib):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    assert set(SINK_SYMBOLS) <= set(_capi.EXPORTS)
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym, proto in SINK_SYMBOLS.items():
-        assert getattr(lib, sym) is not None
-        assert proto.format(sym) in header, sym
-    assert "typedef struct pfa_fa3_sinks" in header
-
-
-def test_sinks_block_layout_and_the_old_blocks_are_unchanged(lib, tmp_path):
-    S = _capi.PfaFa3Sinks
-    fields = [f for f, _ in S._fields_]
-    assert fields == ["size", "flags", "sinks"]
-    offs = ",".join(f"offsetof(pfa_fa3_sinks,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 4))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_fa3_prefill_varlen_args),sizeof(pfa_fa3_cache_ext),'
-                   f'sizeof(pfa_fa3_sinks),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(_capi.PfaFa3DecodeArgs) == 256
-    assert got[1] == C.sizeof(_capi.PfaFa3PrefillVarlenArgs)
-    assert got[2] == C.sizeof(_capi.PfaFa3CacheExt) == 16
-    assert got[3:] == [C.sizeof(S)] + [getattr(S, f).offset for f in fields] == [16, 0, 4, 8]
-
-
 def test_a_null_block_is_the_sibling_call(lib):
     for name, make, chk, schk, desc, sdesc, ns in _families(lib):
         for over in BAD + [dict(Smax=1024), dict(Smax=65536)]:
@@ -139,19 +55,19 @@ def test_a_null_block_is_the_sibling_call(lib):
                 a = mk(**over)
                 for e in EXTS:
                     ext = None if e is None else _capi.make_cache_ext(**e)
-                    want = chk(C.byref(a), _ref(ext))
-                    assert schk(C.byref(a), _ref(ext), None) == want, (name, over, e)
-                    assert _name(sdesc, a, _ref(ext), None, nsplit=ns) == _name(desc, a, _ref(ext), nsplit=ns), (name, over, e)
+                    want = chk(C.byref(a), ref(ext))
+                    assert schk(C.byref(a), ref(ext), None) == want, (name, over, e)
+                    assert name_of(sdesc, a, ref(ext), None, nsplit=ns) == name_of(desc, a, ref(ext), nsplit=ns), (name, over, e)
                     if name == "decode":
-                        assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), _ref(ext), None) == \
-                            lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), _ref(ext))
+                        assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), ref(ext), None) == \
+                            lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), ref(ext))
         assert schk(None, None, None) == NULL
     for over in BAD + [dict(Sq=256, Smax=8192), dict(Sq=300)]:
         a = _dargs(**{"Sq": 256, **over})
         for ks in (0, 1, 3, 8, 9, -1):
             assert lib.pfa_fa3_prefill_split_sink_check(C.byref(a), ks, None) == lib.pfa_fa3_prefill_split_check(C.byref(a), ks)
-            assert _name(lib.pfa_fa3_prefill_split_sink_describe, a, ks, None, nsplit=True) == \
-                _name(lib.pfa_fa3_prefill_split_describe, a, ks, nsplit=True)
+            assert name_of(lib.pfa_fa3_prefill_split_sink_describe, a, ks, None, nsplit=True) == \
+                name_of(lib.pfa_fa3_prefill_split_describe, a, ks, nsplit=True)
             assert lib.pfa_fa3_prefill_split_sink_workspace_bytes(C.byref(a), ks, None) == lib.pfa_fa3_prefill_split_workspace_bytes(C.byref(a), ks)
 
 
@@ -161,24 +77,24 @@ def test_block_rules_in_their_documented_order_then_the_siblings(lib):
     for name, make, chk, schk, _, sdesc, ns in _families(lib):
         for a in (make(), make(B=0), make(q=0)):
             for kw, want in wrong:
-                s = _sinks(**kw)
+                s = sinks(**kw)
                 assert schk(C.byref(a), None, C.byref(s)) == want, (name, kw)
                 assert schk(C.byref(a), C.byref(_capi.make_cache_ext(flags=1)), C.byref(s)) == want, (name, kw)
-                assert _name(sdesc, a, None, C.byref(s), nsplit=ns)[0] == want
+                assert name_of(sdesc, a, None, C.byref(s), nsplit=ns)[0] == want
         # behind a good block the sibling's errors come through, for the argument block and for the extension
-        good = _sinks()
+        good = sinks()
         for over in BAD:
             a = make(**over)
             for e in EXTS:
                 ext = None if e is None else _capi.make_cache_ext(**e)
-                assert schk(C.byref(a), _ref(ext), C.byref(good)) == chk(C.byref(a), _ref(ext)), (name, over, e)
+                assert schk(C.byref(a), ref(ext), C.byref(good)) == chk(C.byref(a), ref(ext)), (name, over, e)
         assert schk(None, None, C.byref(good)) == NULL
     a = _dargs(Sq=256)
     for kw, want in wrong:
-        s = _sinks(**kw)
+        s = sinks(**kw)
         for ks in (0, 3, 9):
             assert lib.pfa_fa3_prefill_split_sink_check(C.byref(a), ks, C.byref(s)) == want
-    good = _sinks()
+    good = sinks()
     for over in BAD + [dict(workspace=0), dict(workspace=0x4000004), dict(o_stride_s=4 * 8 * 128 + 4, dtype_out=0)]:
         a = _dargs(**{"Sq": 256, **over})
         for ks in (0, 1, 3, 9, -1):
@@ -187,17 +103,17 @@ def test_block_rules_in_their_documented_order_then_the_siblings(lib):
     a = _dargs(Smax=65536)
     full = lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None)
     assert full > 0
-    assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), None, C.byref(_sinks(sinks=0))) == full
-    assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), None, C.byref(_sinks(flags=1))) == 0
-    assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), None, C.byref(_sinks(size=12))) == 0
+    assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), None, C.byref(sinks(sinks=0))) == full
+    assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), None, C.byref(sinks(flags=1))) == 0
+    assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), None, C.byref(sinks(size=12))) == 0
     a = _dargs(Sq=256, Smax=8192)
-    assert lib.pfa_fa3_prefill_split_sink_workspace_bytes(C.byref(a), 3, C.byref(_sinks(sinks=0))) == \
+    assert lib.pfa_fa3_prefill_split_sink_workspace_bytes(C.byref(a), 3, C.byref(sinks(sinks=0))) == \
         lib.pfa_fa3_prefill_split_workspace_bytes(C.byref(a), 3) > 0
-    assert lib.pfa_fa3_prefill_split_sink_workspace_bytes(C.byref(a), 3, C.byref(_sinks(flags=1))) == 0
+    assert lib.pfa_fa3_prefill_split_sink_workspace_bytes(C.byref(a), 3, C.byref(sinks(flags=1))) == 0
 
 
 def test_describe_names_plan_and_workspace_are_the_sink_less_calls(lib):
-    s = _sinks()
+    s = sinks()
     win = _capi.make_cache_ext(window=128)
     wide = _capi.make_cache_ext(window=2048)
     want = [
@@ -215,19 +131,19 @@ def test_describe_names_plan_and_workspace_are_the_sink_less_calls(lib):
     for name, paged, ext, text in want:
         _, make, _, _, desc, sdesc, ns = fam[name]
         a = make() if not paged else (_paged() if name == "decode" else _paged(Sq=300))
-        got, plain = _name(sdesc, a, _ref(ext), C.byref(s), nsplit=ns), _name(desc, a, _ref(ext), nsplit=ns)
+        got, plain = name_of(sdesc, a, ref(ext), C.byref(s), nsplit=ns), name_of(desc, a, ref(ext), nsplit=ns)
         assert got[1] == text and got[1].replace("_sink", "") == plain[1]
         assert got[0] == plain[0] > 0 and got[2] == plain[2]          # workgroups and split count
         if name == "decode":
-            assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), _ref(ext), C.byref(s)) == \
-                lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), _ref(ext))
+            assert lib.pfa_fa3_decode_sink_workspace_bytes(C.byref(a), ref(ext), C.byref(s)) == \
+                lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), ref(ext))
     a = _vargs(block_table=0x8000, block_table_stride_b=32, page_size=128, num_pages=100, k_stride_b=128 * 2 * 128, v_stride_b=128 * 2 * 128)
-    assert _name(lib.pfa_fa3_prefill_varlen_sink_describe, a, None, C.byref(s))[1] == "fa3_prefill_bf16_d128_o16_causal_sink_varlen_paged"
+    assert name_of(lib.pfa_fa3_prefill_varlen_sink_describe, a, None, C.byref(s))[1] == "fa3_prefill_bf16_d128_o16_causal_sink_varlen_paged"
     for mk in (_dargs, _paged):
         a = mk(Sq=256, Smax=8192, dtype_out=2)
         for ks in (0, 1, 3, 8):
-            got = _name(lib.pfa_fa3_prefill_split_sink_describe, a, ks, C.byref(s), nsplit=True)
-            plain = _name(lib.pfa_fa3_prefill_split_describe, a, ks, nsplit=True)
+            got = name_of(lib.pfa_fa3_prefill_split_sink_describe, a, ks, C.byref(s), nsplit=True)
+            plain = name_of(lib.pfa_fa3_prefill_split_describe, a, ks, nsplit=True)
             assert got[0] == plain[0] > 0 and got[2] == plain[2] and got[1].replace("_sink", "") == plain[1]
             tail = "_paged" if mk is _paged else ""
             assert got[1] == ("fa3_prefill_bf16_d128_o32_causal_sink" + (f"_split{got[2]}+merge" if got[2] > 1 else "") + tail)

@@ -6,17 +6,10 @@ from __future__ import annotations
 
 import ctypes as C
 
-import pytest
-
-from kvcache_testlib import built_lib
+from capi_testlib import lib  # noqa: F401
 from photonic_flash_attention_amd import _capi
 
 TENSORS = ("q", "k", "v", "o", "do", "dq", "dk", "dv")          # stride prefixes; the pointer of "do" is dout
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _bwd_args(**over):

@@ -1,80 +1,32 @@
 """CPU-side tests (no GPU) of sliding-window attention over the KV cache (``pfa_fa3_cache_ext`` and the ``*_ex`` entry points, ABI v9
-additive): exported symbols, the extension block's layout, old and new entry points agreeing without a window, the new field rules,
+additive): old and new entry points agreeing without a window, the new field rules,
 the decode's split plan under a window, ``ops``' refusals and ``PagedKVCache.release_behind_window``."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, decode_args, decode_paged, ext, lib, prefill_varlen_args, ref  # noqa: F401
 from photonic_flash_attention_amd import _capi, ops
 
-EX_SYMBOLS = {
-    "pfa_fa3_decode_workspace_bytes_ex": "size_t {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_decode_check_ex": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_decode_ex": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_decode_describe_ex": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_prefill_check_ex": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_prefill_ex": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_prefill_describe_ex": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_prefill_varlen_check_ex": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_prefill_varlen_ex": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext",
-    "pfa_fa3_prefill_varlen_describe_ex": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext",
-}
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 MIN_SPLIT_KEYS = 256                # kMinSplitKeys of pfa_decode_capi.hip
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _dargs(**over):
     """A valid contiguous block of the decode / prefill calls: B 2, H 8, Hkv 2, Sq 4, Smax 4096, D 128, with a workspace."""
-    d, sq = over.get("D", 128), over.get("Sq", 4)
-    h, hkv, smax = over.get("H", 8), over.get("Hkv", 2), over.get("Smax", 4096)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=h, Hkv=hkv, Sq=sq, Smax=smax, D=d,
-                q_stride_b=sq * h * d, q_stride_h=d, q_stride_s=h * d, k_stride_b=smax * hkv * d, k_stride_h=d, k_stride_s=hkv * d,
-                v_stride_b=smax * hkv * d, v_stride_h=d, v_stride_s=hkv * d, o_stride_b=sq * h * d, o_stride_h=d, o_stride_s=h * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5, workspace=0x4000000, workspace_bytes=1 << 40)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    return decode_args(over, Sq=4)
 
 
 def _paged(**over):
-    ps = over.pop("_page", 128)
-    smax = over.get("Smax", 4096)
-    d, hkv = over.get("D", 128), over.get("Hkv", 2)
-    base = dict(k_stride_b=ps * hkv * d, v_stride_b=ps * hkv * d, block_table=0x8000, block_table_stride_b=smax // ps, page_size=ps,
-                num_pages=100)
-    base.update(over)
-    return _dargs(**base)
+    return decode_paged(over, Sq=4)
 
 
 def _vargs(**over):
     """A valid block of the ragged call: B 5, H 8, Hkv 2, 640 packed rows, Smax 4096, D 128."""
-    d = over.get("D", 128)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, cu_seqlens_q=0x9000, B=5, H=8, Hkv=2, total_q=640,
-                max_seqlen_q=300, Smax=4096, D=d, q_stride_s=8 * d, q_stride_h=d, o_stride_s=8 * d, o_stride_h=d,
-                k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d, v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_prefill_varlen_args(**base)
-
-
-def _ext(**kw):
-    return _capi.make_cache_ext(**kw)
-
-
-def _ref(e):
-    return None if e is None else C.byref(e)
+    return prefill_varlen_args(over)
 
 
 def _entries(lib):
@@ -84,36 +36,6 @@ def _entries(lib):
             ("varlen", lib.pfa_fa3_prefill_varlen_check, lib.pfa_fa3_prefill_varlen_check_ex, _vargs)]
 
 
-def test_every_ex_symbol_is_declared_and_resolves(lib):
-    assert set(EX_SYMBOLS) <= set(_capi.EXPORTS)
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym, proto in EX_SYMBOLS.items():
-        assert getattr(lib, sym) is not None
-        assert proto.format(sym) in header, sym
-    assert "typedef struct pfa_fa3_cache_ext" in header
-
-
-def test_extension_block_layout_and_the_old_blocks_are_unchanged(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    E = _capi.PfaFa3CacheExt
-    fields = [f for f, _ in E._fields_]
-    assert fields == ["size", "flags", "window", "reserved"]
-    offs = ",".join(f"offsetof(pfa_fa3_cache_ext,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 3))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_fa3_prefill_varlen_args),'
-                   f'sizeof(pfa_fa3_cache_ext),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(_capi.PfaFa3DecodeArgs) == 256
-    assert got[1] == C.sizeof(_capi.PfaFa3PrefillVarlenArgs)
-    assert got[2:] == [C.sizeof(E)] + [getattr(E, f).offset for f in fields] == [16, 0, 4, 8, 12]
-    assert "reserved0" in [f for f, _ in _capi.PfaFa3DecodeArgs._fields_]
-    assert "reserved0" in [f for f, _ in _capi.PfaFa3PrefillVarlenArgs._fields_]
-
-
 def test_old_and_new_entry_points_agree_without_a_window(lib):
     bad = [dict(), dict(q=0), dict(B=0), dict(D=96), dict(dtype_out=1), dict(k_stride_s=257), dict(o=0x800008), dict(flags=1),
            dict(reserved0=1), dict(page_size=64), dict(causal=0), dict(dtype_out=2), dict(D=64)]
@@ -121,65 +43,65 @@ def test_old_and_new_entry_points_agree_without_a_window(lib):
         for over in bad:
             a = make(**over)
             want = old(C.byref(a))
-            for e in (None, _ext(), _ext(window=0)):
-                assert new(C.byref(a), _ref(e)) == want, (name, over)
-        assert old(None) == NULL and new(None, None) == NULL and new(None, C.byref(_ext(window=4))) == NULL
+            for e in (None, ext(), ext(window=0)):
+                assert new(C.byref(a), ref(e)) == want, (name, over)
+        assert old(None) == NULL and new(None, None) == NULL and new(None, C.byref(ext(window=4))) == NULL
         short = make()
         short.size = 16
-        assert old(C.byref(short)) == SIZE and new(C.byref(short), C.byref(_ext(window=4))) == SIZE
+        assert old(C.byref(short)) == SIZE and new(C.byref(short), C.byref(ext(window=4))) == SIZE
     # decode: key_mask, a missing workspace
     for over in (dict(key_mask=0x6000, key_mask_stride_b=4096), dict(workspace=0), dict(workspace_bytes=16), dict(Sq=65),
                  dict(B=8, H=32, Hkv=8, Sq=1, Smax=32768)):
         a = _dargs(**over)
-        for e in (None, _ext(window=0)):
-            assert lib.pfa_fa3_decode_check_ex(C.byref(a), _ref(e)) == lib.pfa_fa3_decode_check(C.byref(a)), over
+        for e in (None, ext(window=0)):
+            assert lib.pfa_fa3_decode_check_ex(C.byref(a), ref(e)) == lib.pfa_fa3_decode_check(C.byref(a)), over
     # describe / workspace
     for make in (_dargs, _paged):
         for over in (dict(), dict(B=1, H=32, Hkv=8, Sq=1, Smax=32768), dict(Sq=64, dtype_out=2), dict(D=64, dtype_in=1, dtype_out=1, causal=0)):
             a = make(**over)
-            for e in (None, _ext(window=0)):
+            for e in (None, ext(window=0)):
                 assert _capi.describe_decode_ex(a, e) == _capi.describe_decode(a)
-                assert lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), _ref(e)) == lib.pfa_fa3_decode_workspace_bytes(C.byref(a))
+                assert lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), ref(e)) == lib.pfa_fa3_decode_workspace_bytes(C.byref(a))
             p = make(Sq=300, **{k: v for k, v in over.items() if k != "Sq"})
-            for e in (None, _ext(window=0)):
+            for e in (None, ext(window=0)):
                 assert _capi.describe_prefill_ex(p, e) == _capi.describe_prefill(p)
     for over in (dict(), dict(causal=0), dict(dtype_out=2), dict(D=64)):
-        for e in (None, _ext(window=0)):
+        for e in (None, ext(window=0)):
             assert _capi.describe_prefill_varlen_ex(_vargs(**over), e) == _capi.describe_prefill_varlen(_vargs(**over))
 
 
 def test_extension_field_rules(lib):
     for name, _, new, make in _entries(lib):
         ok = make()
-        assert new(C.byref(ok), C.byref(_ext(window=1))) == 0, name
-        assert new(C.byref(ok), C.byref(_ext(window=4096))) == 0
-        assert new(C.byref(ok), C.byref(_ext(window=2 ** 31 - 1))) == 0              # larger than the cache: hides nothing
-        wrong = _ext(window=4)
+        assert new(C.byref(ok), C.byref(ext(window=1))) == 0, name
+        assert new(C.byref(ok), C.byref(ext(window=4096))) == 0
+        assert new(C.byref(ok), C.byref(ext(window=2 ** 31 - 1))) == 0              # larger than the cache: hides nothing
+        wrong = ext(window=4)
         wrong.size = 12
         assert new(C.byref(ok), C.byref(wrong)) == SIZE
         wrong.size = 24
         assert new(C.byref(ok), C.byref(wrong)) == SIZE
-        assert new(C.byref(ok), C.byref(_ext(window=4, flags=1))) == FLAGS
-        assert new(C.byref(ok), C.byref(_ext(flags=0x100))) == FLAGS
-        assert new(C.byref(ok), C.byref(_ext(window=4, reserved=1))) == FLAGS
-        assert new(C.byref(ok), C.byref(_ext(reserved=-1))) == FLAGS
-        assert new(C.byref(ok), C.byref(_ext(window=-1))) == SHAPE
-        assert new(C.byref(ok), C.byref(_ext(window=-(2 ** 31)))) == SHAPE
+        assert new(C.byref(ok), C.byref(ext(window=4, flags=1))) == FLAGS
+        assert new(C.byref(ok), C.byref(ext(flags=0x100))) == FLAGS
+        assert new(C.byref(ok), C.byref(ext(window=4, reserved=1))) == FLAGS
+        assert new(C.byref(ok), C.byref(ext(reserved=-1))) == FLAGS
+        assert new(C.byref(ok), C.byref(ext(window=-1))) == SHAPE
+        assert new(C.byref(ok), C.byref(ext(window=-(2 ** 31)))) == SHAPE
         full = make(causal=0)
-        assert new(C.byref(full), C.byref(_ext(window=4))) == FLAGS                  # a window needs the causal flag
-        assert new(C.byref(full), C.byref(_ext(window=0))) == 0
+        assert new(C.byref(full), C.byref(ext(window=4))) == FLAGS                  # a window needs the causal flag
+        assert new(C.byref(full), C.byref(ext(window=0))) == 0
         # the block's own rules come first
-        assert new(C.byref(make(D=96)), C.byref(_ext(window=-1))) == HEAD_DIM
-        assert new(C.byref(make(reserved0=1)), C.byref(_ext(window=4))) == FLAGS
+        assert new(C.byref(make(D=96)), C.byref(ext(window=-1))) == HEAD_DIM
+        assert new(C.byref(make(reserved0=1)), C.byref(ext(window=4))) == FLAGS
     # prefill still refuses a key mask, decode combines it with the window
     km = dict(key_mask=0x6000, key_mask_stride_b=4096)
-    assert lib.pfa_fa3_prefill_check_ex(C.byref(_dargs(Sq=300, **km)), C.byref(_ext(window=4))) == FLAGS
-    assert lib.pfa_fa3_decode_check_ex(C.byref(_dargs(**km)), C.byref(_ext(window=4))) == 0
-    assert lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(_dargs(causal=0)), C.byref(_ext(window=4))) == 0       # refused: 0
+    assert lib.pfa_fa3_prefill_check_ex(C.byref(_dargs(Sq=300, **km)), C.byref(ext(window=4))) == FLAGS
+    assert lib.pfa_fa3_decode_check_ex(C.byref(_dargs(**km)), C.byref(ext(window=4))) == 0
+    assert lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(_dargs(causal=0)), C.byref(ext(window=4))) == 0       # refused: 0
 
 
 def test_describe_marks_windowed_kernels(lib):
-    w = _ext(window=1024)
+    w = ext(window=1024)
     assert _capi.describe_decode_ex(_dargs(Smax=256), w)[0] == "fa3_decode_bf16_d128_o16_win"
     assert _capi.describe_decode_ex(_dargs(), w)[0] == "fa3_decode_bf16_d128_o16_win+combine"
     assert _capi.describe_decode_ex(_paged(D=64, dtype_in=1, dtype_out=2), w)[0] == "fa3_decode_fp16_d64_o32_win+combine_paged"
@@ -191,8 +113,8 @@ def test_describe_marks_windowed_kernels(lib):
         _capi.describe_prefill_ex(_dargs(Sq=300, causal=0), w)
     # the grid of the prefill calls does not depend on the window
     for win in (1, 64, 5000):
-        assert _capi.describe_prefill_ex(_dargs(Sq=300), _ext(window=win))[1] == 32
-        assert _capi.describe_prefill_varlen_ex(_vargs(), _ext(window=win))[1] == 80
+        assert _capi.describe_prefill_ex(_dargs(Sq=300), ext(window=win))[1] == 32
+        assert _capi.describe_prefill_varlen_ex(_vargs(), ext(window=win))[1] == 80
 
 
 def test_decode_plan_under_a_window(lib):
@@ -202,29 +124,29 @@ def test_decode_plan_under_a_window(lib):
         _, items0, ns0 = _capi.describe_decode(a)
         ws0 = lib.pfa_fa3_decode_workspace_bytes(C.byref(a))
         assert ns0 > 1 and ws0 > 0
-        w = _ext(window=256)
+        w = ext(window=256)
         _, items, ns = _capi.describe_decode_ex(a, w)
         ws = lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), C.byref(w))
         assert ns < ns0 and ws < ws0 and items < items0
         span = -(-(256 + 1 - 1) // 64) * 64
         assert span // ns >= MIN_SPLIT_KEYS                     # no split covers fewer than kMinSplitKeys keys of the span
         for win in (1, 63, 1000, 4096, 20000):
-            _, _, n = _capi.describe_decode_ex(a, _ext(window=win))
+            _, _, n = _capi.describe_decode_ex(a, ext(window=win))
             sp = min(32768, -(-win // 64) * 64)
             assert n == 1 or sp // n >= MIN_SPLIT_KEYS, win
             assert n <= ns0
         for win in (32768, 32769, 2 ** 31 - 1):                 # a window the cache fits in: the plan without a window
-            e = _ext(window=win)
+            e = ext(window=win)
             assert _capi.describe_decode_ex(a, e)[1:] == (items0, ns0)
             assert lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), C.byref(e)) == ws0
     # a 4096-key window over a 128K cache is not cut into 128 splits of a few tiles
     big = _dargs(B=1, H=32, Hkv=8, Sq=1, Smax=131072)
     assert _capi.describe_decode(big)[2] == 64
-    assert _capi.describe_decode_ex(big, _ext(window=4096))[2] == 16
+    assert _capi.describe_decode_ex(big, ext(window=4096))[2] == 16
     # paged and contiguous plans are equal, and device-side inputs do not enter
     for win in (256, 4096):
         c, p = _dargs(**shape), _paged(**shape)
-        e = _ext(window=win)
+        e = ext(window=win)
         assert _capi.describe_decode_ex(c, e)[1:] == _capi.describe_decode_ex(p, e)[1:]
         assert lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(c), C.byref(e)) == lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(p), C.byref(e))
         before = _capi.describe_decode_ex(p, e)
@@ -232,8 +154,8 @@ def test_decode_plan_under_a_window(lib):
         assert _capi.describe_decode_ex(p, e) == before
     # Sq enters the span: 64 rows behind a 193-key window reach 256 keys back
     a = _dargs(B=1, H=8, Hkv=8, Sq=64, Smax=32768)
-    assert _capi.describe_decode_ex(a, _ext(window=193))[2] == 1
-    assert _capi.describe_decode_ex(a, _ext(window=512 - 63))[2] == 2
+    assert _capi.describe_decode_ex(a, ext(window=193))[2] == 1
+    assert _capi.describe_decode_ex(a, ext(window=512 - 63))[2] == 2
 
 
 def test_ops_refuse_a_bad_window_before_any_launch():

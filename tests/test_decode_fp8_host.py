@@ -1,5 +1,5 @@
 """CPU-side tests (no GPU) of the FP8 (e4m3fn) KV cache: ``pfa_fa3_kv_quant`` and the ``pfa_fa3_decode_q8*`` / ``pfa_kv_append_q8*`` entry
-points (ABI v9 additive) -- exported symbols, the block's layout, every field rule in its documented order, names, split counts and
+points (ABI v9 additive) -- every field rule in its documented order, names, split counts and
 workspace sizes equal to the 16-bit call's -- then ``ops``' refusals, ``quantize_kv`` / ``dequantize_kv``, the plain-torch model of the
 quantising append (placement, saturation, NaN) and ``PagedKVCache`` in FP8 on CPU tensors."""
 
@@ -7,53 +7,25 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 import torch
 
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, decode_args, decode_paged, lib, quant, ref  # noqa: F401
 from conftest import REPO
-from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
-SYMBOLS = {
-    "pfa_fa3_decode_q8_workspace_bytes": "size_t {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant)",
-    "pfa_fa3_decode_q8_check": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant)",
-    "pfa_fa3_decode_q8": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream)",
-    "pfa_fa3_decode_q8_describe": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, char* buf",
-    "pfa_kv_append_q8_check": "int {}(const pfa_kv_append_args* a, const pfa_fa3_kv_quant* quant)",
-    "pfa_kv_append_q8": "int {}(const pfa_kv_append_args* a, const pfa_fa3_kv_quant* quant, void* stream)",
-}
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 FP8 = torch.float8_e4m3fn
 KD, VD = 0x7000, 0x7400
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
 def _dargs(**over):
     """A valid contiguous block of the decode over one-byte caches: B 2, H 8, Hkv 2, Sq 5, Smax 1024, D 128, with a workspace."""
-    d, sq = over.get("D", 128), over.get("Sq", 5)
-    h, hkv, smax = over.get("H", 8), over.get("Hkv", 2), over.get("Smax", 1024)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=h, Hkv=hkv, Sq=sq, Smax=smax, D=d,
-                q_stride_b=sq * h * d, q_stride_h=d, q_stride_s=h * d, k_stride_b=smax * hkv * d, k_stride_h=d, k_stride_s=hkv * d,
-                v_stride_b=smax * hkv * d, v_stride_h=d, v_stride_s=hkv * d, o_stride_b=sq * h * d, o_stride_h=d, o_stride_s=h * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5, workspace=0x4000000, workspace_bytes=1 << 40)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    return decode_args(over, Sq=5, Smax=1024)
 
 
 def _paged(**over):
-    ps = over.pop("_page", 128)
-    smax = over.get("Smax", 1024)
-    d, hkv = over.get("D", 128), over.get("Hkv", 2)
-    base = dict(k_stride_b=ps * hkv * d, v_stride_b=ps * hkv * d, block_table=0x8000, block_table_stride_b=smax // ps, page_size=ps,
-                num_pages=100)
-    base.update(over)
-    return _dargs(**base)
+    return decode_paged(over, Sq=5, Smax=1024)
 
 
 def _aargs(**over):
@@ -67,143 +39,113 @@ def _aargs(**over):
     return _capi.make_kv_append_args(**base)
 
 
-def _quant(**kw):
-    return _capi.make_kv_quant(**{"k_descale": KD, "v_descale": VD, **kw})
-
-
-def _ref(e):
-    return None if e is None else C.byref(e)
-
-
-def test_every_symbol_is_declared_and_resolves(lib):
-    assert set(SYMBOLS) <= set(_capi.EXPORTS)
+def test_the_fp8_dtype_value_the_abi_history_entry_and_the_quant_block_defaults():
     header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym, proto in SYMBOLS.items():
-        assert getattr(lib, sym) is not None
-        assert proto.format(sym) in header, sym
-    assert "typedef struct pfa_fa3_kv_quant" in header and "PFA_DTYPE_FP8_E4M3 = 3" in header
+    assert "PFA_DTYPE_FP8_E4M3 = 3" in header
     assert "pfa_fa3_decode_q8*" in header.split("Reference seam")[0]            # the ABI history names it
     assert _capi.PFA_DTYPE_FP8_E4M3 == 3
-
-
-def test_quant_block_layout_matches_the_mirror(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9              # additive: the version stands
-    T = _capi.PfaFa3KvQuant
-    fields = [f for f, _ in T._fields_]
-    assert fields == ["size", "flags", "kv_dtype", "reserved", "k_descale", "v_descale", "descale_stride_b"]
-    offs = ",".join(f"offsetof(pfa_fa3_kv_quant,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 3))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_kv_append_args),'
-                   f'sizeof(pfa_fa3_kv_quant),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(_capi.PfaFa3DecodeArgs) == 256 and got[1] == C.sizeof(_capi.PfaKvAppendArgs)      # the old blocks stand
-    assert got[2:] == [C.sizeof(T)] + [getattr(T, f).offset for f in fields] == [40, 0, 4, 8, 12, 16, 24, 32]
     assert _capi.make_kv_quant().size == 40 and _capi.make_kv_quant().kv_dtype == 3
 
 
 def _quant_rules(chk, make, ok_over=None):
     """The rules of pfa_fa3_kv_quant and of one-byte caches, each alone and in their order, for ``chk(a, quant)`` over blocks ``make``."""
     ok = make()
-    assert chk(ok, _quant()) == 0
-    assert chk(ok, _quant(descale_stride_b=2)) == 0 and chk(ok, _quant(descale_stride_b=64)) == 0
+    assert chk(ok, quant()) == 0
+    assert chk(ok, quant(descale_stride_b=2)) == 0 and chk(ok, quant(descale_stride_b=64)) == 0
     # each rule alone
-    assert chk(None, _quant()) == NULL
+    assert chk(None, quant()) == NULL
     short = make()
     short.size -= 8
-    assert chk(short, _quant()) == SIZE
+    assert chk(short, quant()) == SIZE
     assert chk(ok, None) == NULL
-    wrong = _quant()
+    wrong = quant()
     for size in (32, 48):
         wrong.size = size
         assert chk(ok, wrong) == SIZE
-    assert chk(ok, _quant(flags=1)) == FLAGS
-    assert chk(ok, _quant(reserved=1)) == FLAGS
+    assert chk(ok, quant(flags=1)) == FLAGS
+    assert chk(ok, quant(reserved=1)) == FLAGS
     for dt in (0, 1, 2, 4, -1):
-        assert chk(ok, _quant(kv_dtype=dt)) == DTYPE
-    assert chk(ok, _quant(k_descale=0)) == NULL and chk(ok, _quant(v_descale=0)) == NULL
-    assert chk(ok, _quant(k_descale=KD + 2)) == ALIGN and chk(ok, _quant(v_descale=VD + 1)) == ALIGN
-    assert chk(ok, _quant(descale_stride_b=1)) == STRIDE and chk(ok, _quant(descale_stride_b=-2)) == STRIDE
+        assert chk(ok, quant(kv_dtype=dt)) == DTYPE
+    assert chk(ok, quant(k_descale=0)) == NULL and chk(ok, quant(v_descale=0)) == NULL
+    assert chk(ok, quant(k_descale=KD + 2)) == ALIGN and chk(ok, quant(v_descale=VD + 1)) == ALIGN
+    assert chk(ok, quant(descale_stride_b=1)) == STRIDE and chk(ok, quant(descale_stride_b=-2)) == STRIDE
     for f in ("k_stride_b", "k_stride_h", "k_stride_s", "v_stride_b", "v_stride_h", "v_stride_s"):
         a = make()
         setattr(a, f, getattr(a, f) + 8)                                         # a multiple of 8 passes the 16-bit rule, not this one
-        assert chk(a, _quant()) == STRIDE, f
-    assert chk(make(k_stride_s=-256), _quant()) == STRIDE and chk(make(v_stride_s=-256), _quant()) == STRIDE
-    assert chk(make(k_cache=0x1000008), _quant()) == ALIGN and chk(make(v_cache=0x2000004), _quant()) == ALIGN
+        assert chk(a, quant()) == STRIDE, f
+    assert chk(make(k_stride_s=-256), quant()) == STRIDE and chk(make(v_stride_s=-256), quant()) == STRIDE
+    assert chk(make(k_cache=0x1000008), quant()) == ALIGN and chk(make(v_cache=0x2000004), quant()) == ALIGN
     # the order: each rule wins over all that follow it
     bad = make(k_stride_s=264, k_cache=0x1000008)
     every = dict(flags=1, kv_dtype=0, k_descale=0, v_descale=VD + 2, descale_stride_b=1)
-    q = _quant(**every)
+    q = quant(**every)
     q.size = 8
     assert chk(bad, q) == SIZE
-    assert chk(bad, _quant(**every)) == FLAGS
+    assert chk(bad, quant(**every)) == FLAGS
     del every["flags"]
-    assert chk(bad, _quant(**every)) == DTYPE
+    assert chk(bad, quant(**every)) == DTYPE
     del every["kv_dtype"]
-    assert chk(bad, _quant(**every)) == NULL
+    assert chk(bad, quant(**every)) == NULL
     del every["k_descale"]
-    assert chk(bad, _quant(**every)) == ALIGN
+    assert chk(bad, quant(**every)) == ALIGN
     del every["v_descale"]
-    assert chk(bad, _quant(**every)) == STRIDE                                   # descale_stride_b
-    assert chk(bad, _quant()) == STRIDE                                          # the cache stride in front of the cache base
-    assert chk(make(k_cache=0x1000008), _quant()) == ALIGN
+    assert chk(bad, quant(**every)) == STRIDE                                   # descale_stride_b
+    assert chk(bad, quant()) == STRIDE                                          # the cache stride in front of the cache base
+    assert chk(make(k_cache=0x1000008), quant()) == ALIGN
     # the block's own size comes first of all; its other rules behind the quant block's
     short = make(k_stride_s=264)
     short.size -= 8
-    assert chk(short, _quant(flags=1)) == SIZE
+    assert chk(short, quant(flags=1)) == SIZE
     return ok
 
 
 def test_decode_q8_field_rules_in_their_order(lib):
     for make in (_dargs, _paged):
         def chk(a, q, ext=None):
-            return lib.pfa_fa3_decode_q8_check(_ref(a), _ref(ext), _ref(q))
+            return lib.pfa_fa3_decode_q8_check(ref(a), ref(ext), ref(q))
         ok = _quant_rules(chk, make)
         # a window does not combine; window = 0 and a NULL extension are the plain call
-        assert chk(ok, _quant(), _capi.make_cache_ext(window=4)) == FLAGS
-        assert chk(ok, _quant(), _capi.make_cache_ext(window=0)) == 0
-        assert chk(make(k_cache=0x1000008), _quant(), _capi.make_cache_ext(window=4)) == ALIGN      # the cache base in front of the window
-        assert chk(make(D=96), _quant(), _capi.make_cache_ext(window=4)) == FLAGS                   # ... which is in front of the old rules
+        assert chk(ok, quant(), _capi.make_cache_ext(window=4)) == FLAGS
+        assert chk(ok, quant(), _capi.make_cache_ext(window=0)) == 0
+        assert chk(make(k_cache=0x1000008), quant(), _capi.make_cache_ext(window=4)) == ALIGN      # the cache base in front of the window
+        assert chk(make(D=96), quant(), _capi.make_cache_ext(window=4)) == FLAGS                   # ... which is in front of the old rules
         # then the unchanged rules of pfa_fa3_decode_ex: the same status for every block the quant rules pass
         for over in (dict(q=0), dict(B=0), dict(D=96), dict(dtype_out=1), dict(dtype_in=2), dict(o=0x800008), dict(flags=1), dict(reserved0=1),
                      dict(Sq=65), dict(workspace=0), dict(workspace_bytes=16), dict(softmax_scale=0.0), dict(q_stride_s=4), dict(o_stride_s=6),
                      dict(H=7), dict(key_mask=0x6000, key_mask_stride_b=1024), dict(causal=0), dict(dtype_out=2)):
             a = make(**over)
-            assert chk(a, _quant()) == lib.pfa_fa3_decode_check_ex(C.byref(a), None), over
+            assert chk(a, quant()) == lib.pfa_fa3_decode_check_ex(C.byref(a), None), over
         bad_ext = _capi.make_cache_ext(window=-1)
-        assert chk(ok, _quant(), bad_ext) == lib.pfa_fa3_decode_check_ex(C.byref(ok), C.byref(bad_ext)) == SHAPE
-        assert chk(ok, _quant(), _capi.make_cache_ext(flags=1)) == FLAGS
+        assert chk(ok, quant(), bad_ext) == lib.pfa_fa3_decode_check_ex(C.byref(ok), C.byref(bad_ext)) == SHAPE
+        assert chk(ok, quant(), _capi.make_cache_ext(flags=1)) == FLAGS
         # dtype_in stays q's dtype: FP8 is refused there
-        assert chk(make(dtype_in=3), _quant()) == DTYPE
+        assert chk(make(dtype_in=3), quant()) == DTYPE
         # describe and the launch entry refuse the same way (nothing is launched: the status comes first)
         with pytest.raises(_capi.PfaError) as e:
-            _capi.describe_decode_q8(ok, None, _quant(kv_dtype=1))
+            _capi.describe_decode_q8(ok, None, quant(kv_dtype=1))
         assert e.value.status == DTYPE
-        assert lib.pfa_fa3_decode_q8(C.byref(ok), None, C.byref(_quant(k_descale=0)), None) == NULL
+        assert lib.pfa_fa3_decode_q8(C.byref(ok), None, C.byref(quant(k_descale=0)), None) == NULL
         assert lib.pfa_fa3_decode_q8(C.byref(ok), None, None, None) == NULL
 
 
 def test_append_q8_field_rules_in_their_order(lib):
     def chk(a, q):
-        return lib.pfa_kv_append_q8_check(_ref(a), _ref(q))
+        return lib.pfa_kv_append_q8_check(ref(a), ref(q))
     ok = _quant_rules(chk, _aargs)
     pg = dict(k_stride_b=64 * 2 * 64, v_stride_b=64 * 2 * 64, block_table=0x8000, block_table_stride_b=4, page_size=64, num_pages=9)
-    assert chk(_aargs(**pg), _quant()) == 0
-    assert chk(_aargs(cu_seqlens_q=0x6000, kn_stride_b=0, vn_stride_b=0), _quant()) == 0
+    assert chk(_aargs(**pg), quant()) == 0
+    assert chk(_aargs(cu_seqlens_q=0x6000, kn_stride_b=0, vn_stride_b=0), quant()) == 0
     for d in (16, 48, 256):
-        assert chk(_aargs(D=d), _quant()) == 0
+        assert chk(_aargs(D=d), quant()) == 0
     for d in (8, 24, 72):                                                        # fine for the 16-bit append, not for 16-element items
         a = _aargs(D=d, k_stride_b=256 * 2 * 80, v_stride_b=256 * 2 * 80, k_stride_h=80, v_stride_h=80, k_stride_s=160, v_stride_s=160)
-        assert lib.pfa_kv_append_check(C.byref(a)) == 0 and chk(a, _quant()) == HEAD_DIM, d
-    assert chk(_aargs(D=272), _quant()) == HEAD_DIM                              # past 256: the 16-bit append's own rule
+        assert lib.pfa_kv_append_check(C.byref(a)) == 0 and chk(a, quant()) == HEAD_DIM, d
+    assert chk(_aargs(D=272), quant()) == HEAD_DIM                              # past 256: the 16-bit append's own rule
     for over in (dict(k_new=0), dict(cache_seqlens=0), dict(B=0), dict(dtype=2), dict(dtype=3), dict(kn_stride_s=4), dict(k_new=0x1008),
                  dict(flags=1), dict(reserved1=1), dict(page_size=64), dict(total_new=5), dict(max_seqlen_q=0)):
         a = _aargs(**over)
-        assert chk(a, _quant()) == lib.pfa_kv_append_check(C.byref(a)) != 0, over
-    assert lib.pfa_kv_append_q8(C.byref(ok), C.byref(_quant(v_descale=0)), None) == NULL
+        assert chk(a, quant()) == lib.pfa_kv_append_check(C.byref(a)) != 0, over
+    assert lib.pfa_kv_append_q8(C.byref(ok), C.byref(quant(v_descale=0)), None) == NULL
     assert lib.pfa_kv_append_q8(C.byref(ok), None, None) == NULL
 
 
@@ -217,22 +159,22 @@ def test_names_splits_and_workspace_are_the_16_bit_calls(lib, smax, want_ns):
             ws0 = lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None)
             if "B" not in over:
                 assert ns0 == want_ns and (ws0 > 0) == (want_ns > 1)
-            for q in (_quant(), _quant(descale_stride_b=a.Hkv), _quant(k_descale=0x123450)):
+            for q in (quant(), quant(descale_stride_b=a.Hkv), quant(k_descale=0x123450)):
                 for ext in (None, _capi.make_cache_ext()):
                     name, items, ns = _capi.describe_decode_q8(a, ext, q)
                     assert (items, ns) == (items0, ns0)
                     head, plus, tail = name0.partition("+combine") if "+combine" in name0 else name0.partition("_paged")
                     assert name == head + "_kv8" + plus + tail and "_kv8" not in name0
-                    assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), _ref(ext), C.byref(q)) == ws0
+                    assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), ref(ext), C.byref(q)) == ws0
             # the workspace query takes no pointers and skips the pointer and stride rules; what the other rules refuse is 0
-            assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), None, C.byref(_quant(k_descale=0, v_descale=0))) == ws0
-            assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), None, C.byref(_quant(kv_dtype=0))) == 0
+            assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), None, C.byref(quant(k_descale=0, v_descale=0))) == ws0
+            assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), None, C.byref(quant(kv_dtype=0))) == 0
             assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), None, None) == 0
-            assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), C.byref(_capi.make_cache_ext(window=8)), C.byref(_quant())) == 0
-    assert _capi.describe_decode_q8(_dargs(Smax=128), None, _quant())[0] == "fa3_decode_bf16_d128_o16_kv8"
-    assert _capi.describe_decode_q8(_dargs(), None, _quant())[0] == "fa3_decode_bf16_d128_o16_kv8+combine"
-    assert _capi.describe_decode_q8(_paged(D=64, dtype_in=1, dtype_out=2), None, _quant())[0] == "fa3_decode_fp16_d64_o32_kv8+combine_paged"
-    assert _capi.describe_decode_q8(_paged(Smax=128), None, _quant())[0] == "fa3_decode_bf16_d128_o16_kv8_paged"
+            assert lib.pfa_fa3_decode_q8_workspace_bytes(C.byref(a), C.byref(_capi.make_cache_ext(window=8)), C.byref(quant())) == 0
+    assert _capi.describe_decode_q8(_dargs(Smax=128), None, quant())[0] == "fa3_decode_bf16_d128_o16_kv8"
+    assert _capi.describe_decode_q8(_dargs(), None, quant())[0] == "fa3_decode_bf16_d128_o16_kv8+combine"
+    assert _capi.describe_decode_q8(_paged(D=64, dtype_in=1, dtype_out=2), None, quant())[0] == "fa3_decode_fp16_d64_o32_kv8+combine_paged"
+    assert _capi.describe_decode_q8(_paged(Smax=128), None, quant())[0] == "fa3_decode_bf16_d128_o16_kv8_paged"
 
 
 # --- ops: refusals ------------------------------------------------------------------------------------------------------------------

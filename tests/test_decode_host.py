@@ -1,52 +1,21 @@
-"""CPU-side tests (no GPU) of the split-KV decode path: C layout, argument validation, workspace contract, host-tensor refusal and
+"""CPU-side tests (no GPU) of the split-KV decode path: argument validation, workspace contract, host-tensor refusal and
 the Hugging Face routing decision."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import decode_args, lib  # noqa: F401
 from photonic_flash_attention_amd import _capi, ops
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def test_decode_struct_matches_c_layout(tmp_path):
-    fields = ("q", "cache_seqlens", "key_mask", "q_stride_b", "k_stride_s", "key_mask_stride_b", "B", "Smax", "causal",
-              "softmax_scale", "reserved0", "workspace", "workspace_bytes")
-    src = tmp_path / "sz.c"
-    fmt = " ".join(["%zu"] * (len(fields) + 1))
-    offs = ",".join(f"offsetof(pfa_fa3_decode_args,{f})" for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    A = _capi.PfaFa3DecodeArgs
-    assert got == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-
-
 def _dargs(**over):
-    # B 2, H 8, Hkv 2, Sq 1, Smax 4096, D 128, [B, S, H, D] q and cache
-    base = dict(q=0x1000, k_cache=0x100000, v_cache=0x200000, o=0x3000, B=2, H=8, Hkv=2, Sq=1, Smax=4096, D=128,
-                q_stride_b=8 * 128, q_stride_h=128, q_stride_s=8 * 128, k_stride_b=4096 * 2 * 128, k_stride_h=128, k_stride_s=2 * 128,
-                v_stride_b=4096 * 2 * 128, v_stride_h=128, v_stride_s=2 * 128, o_stride_b=8 * 128, o_stride_h=128, o_stride_s=8 * 128,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=128 ** -0.5)
-    base.update(over)
-    a = _capi.make_decode_args(**base)
-    n = _capi.load().pfa_fa3_decode_workspace_bytes(C.byref(a))
-    if n and "workspace" not in over:
-        a.workspace, a.workspace_bytes = 0x40000000, n
-    return a
+    """B 2, H 8, Hkv 2, Sq 1, Smax 4096, D 128, [B, S, H, D] q and cache, with the workspace the library asks for; the strides are
+    those of this shape whatever is overridden."""
+    return decode_args({**dict(k_cache=0x100000, v_cache=0x200000, o=0x3000), **over}, Sq=1, ws="asked", follow="")
 
 
 def test_decode_argument_validation(lib):

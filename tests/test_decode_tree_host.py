@@ -1,5 +1,5 @@
 """CPU-side tests (no GPU) of tree attention masks in the decode (``pfa_fa3_tree_mask`` and the ``pfa_fa3_decode_tree*`` entry points,
-ABI v9 additive): exported symbols, the block's layout, a NULL tree agreeing with ``pfa_fa3_decode_ex``, the field rules in their
+ABI v9 additive): a NULL tree agreeing with ``pfa_fa3_decode_ex``, the field rules in their
 stated order, the plan not depending on a tree, ``ops.fa3_decode``'s refusals, ``ops.tree_mask_from_parents`` against an ancestor walk,
 ``PagedKVCache.truncate`` and the accept flow of a speculative step."""
 
@@ -7,90 +7,29 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 import torch
 
+from capi_testlib import ALIGN, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, decode_args, decode_paged, ext, lib, ref, tree  # noqa: F401
 from conftest import REPO
-from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
-TREE_SYMBOLS = {
-    "pfa_fa3_decode_tree_workspace_bytes": "size_t {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree",
-    "pfa_fa3_decode_tree_check": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree",
-    "pfa_fa3_decode_tree": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree, void* stream",
-    "pfa_fa3_decode_tree_describe": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_tree_mask* tree, char* buf",
-}
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 WORDS = 0x7000
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _dargs(**over):
     """A valid contiguous block of the decode: B 2, H 8, Hkv 2, Sq 5, Smax 1024, D 128, with a workspace."""
-    d, sq = over.get("D", 128), over.get("Sq", 5)
-    h, hkv, smax = over.get("H", 8), over.get("Hkv", 2), over.get("Smax", 1024)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=h, Hkv=hkv, Sq=sq, Smax=smax, D=d,
-                q_stride_b=sq * h * d, q_stride_h=d, q_stride_s=h * d, k_stride_b=smax * hkv * d, k_stride_h=d, k_stride_s=hkv * d,
-                v_stride_b=smax * hkv * d, v_stride_h=d, v_stride_s=hkv * d, o_stride_b=sq * h * d, o_stride_h=d, o_stride_s=h * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5, workspace=0x4000000, workspace_bytes=1 << 40)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    return decode_args(over, Sq=5, Smax=1024)
 
 
 def _paged(**over):
-    ps = over.pop("_page", 128)
-    smax = over.get("Smax", 1024)
-    d, hkv = over.get("D", 128), over.get("Hkv", 2)
-    base = dict(k_stride_b=ps * hkv * d, v_stride_b=ps * hkv * d, block_table=0x8000, block_table_stride_b=smax // ps, page_size=ps,
-                num_pages=100)
-    base.update(over)
-    return _dargs(**base)
+    return decode_paged(over, Sq=5, Smax=1024)
 
 
-def _ext(**kw):
-    return _capi.make_cache_ext(**kw)
-
-
-def _tree(**kw):
-    return _capi.make_tree_mask(**{"words": WORDS, "stride_b": 5, **kw})
-
-
-def _ref(e):
-    return None if e is None else C.byref(e)
-
-
-def test_every_tree_symbol_is_declared_and_resolves(lib):
-    assert set(TREE_SYMBOLS) <= set(_capi.EXPORTS)
+def test_the_abi_history_entry_and_the_tree_block_default_size():
     header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym, proto in TREE_SYMBOLS.items():
-        assert getattr(lib, sym) is not None
-        assert proto.format(sym) in header, sym
-    assert "typedef struct pfa_fa3_tree_mask" in header
     assert "pfa_fa3_decode_tree*" in header.split("Reference seam")[0]          # the ABI history names it
-
-
-def test_tree_block_layout_matches_the_mirror(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    T = _capi.PfaFa3TreeMask
-    fields = [f for f, _ in T._fields_]
-    assert fields == ["size", "flags", "words", "stride_b"]
-    offs = ",".join(f"offsetof(pfa_fa3_tree_mask,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 3))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_fa3_cache_ext),'
-                   f'sizeof(pfa_fa3_tree_mask),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(_capi.PfaFa3DecodeArgs) == 256 and got[1] == C.sizeof(_capi.PfaFa3CacheExt) == 16
-    assert got[2:] == [C.sizeof(T)] + [getattr(T, f).offset for f in fields] == [24, 0, 4, 8, 16]
     assert _capi.make_tree_mask().size == 24
 
 
@@ -98,24 +37,24 @@ def test_a_null_tree_is_the_ex_call(lib):
     bad = [dict(), dict(q=0), dict(B=0), dict(D=96), dict(dtype_out=1), dict(k_stride_s=257), dict(o=0x800008), dict(flags=1),
            dict(reserved0=1), dict(page_size=64), dict(causal=0), dict(dtype_out=2), dict(D=64), dict(Sq=65), dict(workspace=0),
            dict(workspace_bytes=16), dict(key_mask=0x6000, key_mask_stride_b=1024), dict(B=8, H=32, Hkv=8, Sq=1, Smax=32768)]
-    exts = (None, _ext(), _ext(window=4), _ext(window=300), _ext(window=-1), _ext(flags=1))
+    exts = (None, ext(), ext(window=4), ext(window=300), ext(window=-1), ext(flags=1))
     for make in (_dargs, _paged):
         for over in bad:
             a = make(**over)
             for e in exts:
-                assert lib.pfa_fa3_decode_tree_check(C.byref(a), _ref(e), None) == lib.pfa_fa3_decode_check_ex(C.byref(a), _ref(e)), over
-                assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(a), _ref(e), None) == \
-                    lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), _ref(e)), over
-                if lib.pfa_fa3_decode_check_ex(C.byref(a), _ref(e)) == 0:
+                assert lib.pfa_fa3_decode_tree_check(C.byref(a), ref(e), None) == lib.pfa_fa3_decode_check_ex(C.byref(a), ref(e)), over
+                assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(a), ref(e), None) == \
+                    lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), ref(e)), over
+                if lib.pfa_fa3_decode_check_ex(C.byref(a), ref(e)) == 0:
                     assert _capi.describe_decode_tree(a, e, None) == _capi.describe_decode_ex(a, e), over
                 else:
                     with pytest.raises(_capi.PfaError):
                         _capi.describe_decode_tree(a, e, None)
     assert lib.pfa_fa3_decode_tree_check(None, None, None) == NULL
-    assert lib.pfa_fa3_decode_tree_check(None, None, C.byref(_tree())) == NULL
-    assert lib.pfa_fa3_decode_tree_workspace_bytes(None, None, C.byref(_tree())) == 0
-    assert _capi.describe_decode_tree(_dargs(), _ext(window=300), None)[0] == "fa3_decode_bf16_d128_o16_win"
-    assert _capi.describe_decode_tree(_dargs(), _ext(window=800), None)[0] == "fa3_decode_bf16_d128_o16_win+combine"
+    assert lib.pfa_fa3_decode_tree_check(None, None, C.byref(tree())) == NULL
+    assert lib.pfa_fa3_decode_tree_workspace_bytes(None, None, C.byref(tree())) == 0
+    assert _capi.describe_decode_tree(_dargs(), ext(window=300), None)[0] == "fa3_decode_bf16_d128_o16_win"
+    assert _capi.describe_decode_tree(_dargs(), ext(window=800), None)[0] == "fa3_decode_bf16_d128_o16_win+combine"
     assert _capi.describe_decode_tree(_paged(Smax=128), None, None)[0] == "fa3_decode_bf16_d128_o16_paged"
 
 
@@ -123,62 +62,62 @@ def test_tree_field_rules_in_their_order(lib):
     chk = lib.pfa_fa3_decode_tree_check
     for make in (_dargs, _paged):
         ok = make()
-        assert chk(C.byref(ok), None, C.byref(_tree())) == 0
-        assert chk(C.byref(ok), C.byref(_ext()), C.byref(_tree(stride_b=64))) == 0
-        assert chk(C.byref(make(key_mask=0x6000, key_mask_stride_b=1024)), None, C.byref(_tree())) == 0      # a key mask combines
-        assert chk(C.byref(make(Sq=64)), None, C.byref(_tree(stride_b=64))) == 0
+        assert chk(C.byref(ok), None, C.byref(tree())) == 0
+        assert chk(C.byref(ok), C.byref(ext()), C.byref(tree(stride_b=64))) == 0
+        assert chk(C.byref(make(key_mask=0x6000, key_mask_stride_b=1024)), None, C.byref(tree())) == 0      # a key mask combines
+        assert chk(C.byref(make(Sq=64)), None, C.byref(tree(stride_b=64))) == 0
         # each rule alone
-        wrong = _tree()
+        wrong = tree()
         wrong.size = 16
         assert chk(C.byref(ok), None, C.byref(wrong)) == SIZE
         wrong.size = 32
         assert chk(C.byref(ok), None, C.byref(wrong)) == SIZE
-        assert chk(C.byref(ok), None, C.byref(_tree(flags=1))) == FLAGS
-        assert chk(C.byref(ok), None, C.byref(_tree(words=0))) == NULL
-        assert chk(C.byref(ok), None, C.byref(_tree(words=WORDS + 4))) == ALIGN
-        assert chk(C.byref(ok), None, C.byref(_tree(stride_b=4))) == SHAPE
-        assert chk(C.byref(ok), None, C.byref(_tree(stride_b=-8))) == SHAPE
-        assert chk(C.byref(make(causal=0)), None, C.byref(_tree())) == FLAGS
-        assert chk(C.byref(ok), C.byref(_ext(window=4)), C.byref(_tree())) == FLAGS
-        assert chk(C.byref(ok), C.byref(_ext(window=0)), C.byref(_tree())) == 0
+        assert chk(C.byref(ok), None, C.byref(tree(flags=1))) == FLAGS
+        assert chk(C.byref(ok), None, C.byref(tree(words=0))) == NULL
+        assert chk(C.byref(ok), None, C.byref(tree(words=WORDS + 4))) == ALIGN
+        assert chk(C.byref(ok), None, C.byref(tree(stride_b=4))) == SHAPE
+        assert chk(C.byref(ok), None, C.byref(tree(stride_b=-8))) == SHAPE
+        assert chk(C.byref(make(causal=0)), None, C.byref(tree())) == FLAGS
+        assert chk(C.byref(ok), C.byref(ext(window=4)), C.byref(tree())) == FLAGS
+        assert chk(C.byref(ok), C.byref(ext(window=0)), C.byref(tree())) == 0
         # the order: each rule wins over all that follow it
         every = dict(flags=1, words=0, stride_b=4)                              # + causal = 0 and a window, below
-        full, win = make(causal=0), _ext(window=4)
-        t = _tree(**every)
+        full, win = make(causal=0), ext(window=4)
+        t = tree(**every)
         t.size = 8
         assert chk(C.byref(ok), None, C.byref(t)) == SIZE
-        assert chk(C.byref(ok), None, C.byref(_tree(**every))) == FLAGS
-        assert chk(C.byref(ok), None, C.byref(_tree(words=0, stride_b=4))) == NULL
-        assert chk(C.byref(ok), None, C.byref(_tree(words=WORDS + 1, stride_b=4))) == ALIGN
-        assert chk(C.byref(full), None, C.byref(_tree(words=0))) == NULL           # NULL (3) in front of causal == 0 (6)
-        assert chk(C.byref(full), None, C.byref(_tree(words=WORDS + 2))) == ALIGN
-        assert chk(C.byref(full), None, C.byref(_tree(stride_b=4))) == SHAPE       # stride (5) in front of causal == 0 (6)
-        assert chk(C.byref(ok), C.byref(win), C.byref(_tree(stride_b=4))) == SHAPE  # ... and in front of the window (7)
-        assert chk(C.byref(ok), C.byref(win), C.byref(_tree(words=0))) == NULL
+        assert chk(C.byref(ok), None, C.byref(tree(**every))) == FLAGS
+        assert chk(C.byref(ok), None, C.byref(tree(words=0, stride_b=4))) == NULL
+        assert chk(C.byref(ok), None, C.byref(tree(words=WORDS + 1, stride_b=4))) == ALIGN
+        assert chk(C.byref(full), None, C.byref(tree(words=0))) == NULL           # NULL (3) in front of causal == 0 (6)
+        assert chk(C.byref(full), None, C.byref(tree(words=WORDS + 2))) == ALIGN
+        assert chk(C.byref(full), None, C.byref(tree(stride_b=4))) == SHAPE       # stride (5) in front of causal == 0 (6)
+        assert chk(C.byref(ok), C.byref(win), C.byref(tree(stride_b=4))) == SHAPE  # ... and in front of the window (7)
+        assert chk(C.byref(ok), C.byref(win), C.byref(tree(words=0))) == NULL
         # the argument block's and the extension's rules come first
         assert chk(C.byref(make(D=96)), None, C.byref(wrong)) == HEAD_DIM
-        assert chk(C.byref(make(Sq=65)), None, C.byref(_tree(stride_b=4))) == SHAPE
-        assert chk(C.byref(make(q=0)), None, C.byref(_tree(flags=1))) == NULL
-        assert chk(C.byref(ok), C.byref(_ext(window=-1)), C.byref(_tree(flags=1))) == SHAPE
-        short = _ext()
+        assert chk(C.byref(make(Sq=65)), None, C.byref(tree(stride_b=4))) == SHAPE
+        assert chk(C.byref(make(q=0)), None, C.byref(tree(flags=1))) == NULL
+        assert chk(C.byref(ok), C.byref(ext(window=-1)), C.byref(tree(flags=1))) == SHAPE
+        short = ext()
         short.size = 12
-        assert chk(C.byref(ok), C.byref(short), C.byref(_tree(flags=1))) == SIZE
-        assert chk(C.byref(ok), C.byref(_ext(reserved=1)), C.byref(wrong)) == FLAGS
+        assert chk(C.byref(ok), C.byref(short), C.byref(tree(flags=1))) == SIZE
+        assert chk(C.byref(ok), C.byref(ext(reserved=1)), C.byref(wrong)) == FLAGS
         # ... and the workspace rules behind the tree's
-        assert chk(C.byref(make(workspace=0)), None, C.byref(_tree())) == NULL
-        assert chk(C.byref(make(workspace=0)), None, C.byref(_tree(words=WORDS + 4))) == ALIGN
-        assert chk(C.byref(make(Smax=128, workspace=0)), None, C.byref(_tree())) == 0
+        assert chk(C.byref(make(workspace=0)), None, C.byref(tree())) == NULL
+        assert chk(C.byref(make(workspace=0)), None, C.byref(tree(words=WORDS + 4))) == ALIGN
+        assert chk(C.byref(make(Smax=128, workspace=0)), None, C.byref(tree())) == 0
         # describe and the launch entry refuse the same way (nothing is launched: the status comes first)
         with pytest.raises(_capi.PfaError) as e:
-            _capi.describe_decode_tree(ok, None, _tree(flags=2))
+            _capi.describe_decode_tree(ok, None, tree(flags=2))
         assert e.value.status == FLAGS
-        assert lib.pfa_fa3_decode_tree(C.byref(ok), None, C.byref(_tree(words=0)), None) == NULL
-        assert lib.pfa_fa3_decode_tree(C.byref(full), None, C.byref(_tree()), None) == FLAGS
+        assert lib.pfa_fa3_decode_tree(C.byref(ok), None, C.byref(tree(words=0)), None) == NULL
+        assert lib.pfa_fa3_decode_tree(C.byref(full), None, C.byref(tree()), None) == FLAGS
         # the workspace query takes no pointers; what the other rules refuse is 0
-        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(ok), None, C.byref(_tree(words=0))) > 0
-        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(ok), None, C.byref(_tree(stride_b=4))) == 0
-        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(full), None, C.byref(_tree())) == 0
-        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(ok), C.byref(win), C.byref(_tree())) == 0
+        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(ok), None, C.byref(tree(words=0))) > 0
+        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(ok), None, C.byref(tree(stride_b=4))) == 0
+        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(full), None, C.byref(tree())) == 0
+        assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(ok), C.byref(win), C.byref(tree())) == 0
 
 
 @pytest.mark.parametrize("smax, want_ns", [(128, 1), (1024, 4)])
@@ -189,22 +128,22 @@ def test_the_plan_does_not_depend_on_the_tree(lib, smax, want_ns):
             name0, items0, ns0 = _capi.describe_decode_ex(a, None)
             ws0 = lib.pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None)
             assert ns0 == want_ns and (ws0 > 0) == (want_ns > 1)
-            for t in (_tree(), _tree(stride_b=4096), _tree(words=0x123458)):
+            for t in (tree(), tree(stride_b=4096), tree(words=0x123458)):
                 name, items, ns = _capi.describe_decode_tree(a, None, t)
                 assert (items, ns) == (items0, ns0)
                 assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(a), None, C.byref(t)) == ws0
-                assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(a), C.byref(_ext()), C.byref(t)) == ws0
+                assert lib.pfa_fa3_decode_tree_workspace_bytes(C.byref(a), C.byref(ext()), C.byref(t)) == ws0
             # device-side inputs do not enter
-            before = _capi.describe_decode_tree(a, None, _tree())
+            before = _capi.describe_decode_tree(a, None, tree())
             a.cache_seqlens, a.lse = 0x5000, 0x7000
-            assert _capi.describe_decode_tree(a, None, _tree()) == before
+            assert _capi.describe_decode_tree(a, None, tree()) == before
 
 
 def test_describe_marks_tree_kernels(lib):
-    t = _tree()
+    t = tree()
     assert _capi.describe_decode_tree(_dargs(Smax=128), None, t)[0] == "fa3_decode_bf16_d128_o16_tree"
     assert _capi.describe_decode_tree(_dargs(), None, t)[0] == "fa3_decode_bf16_d128_o16_tree+combine"
-    assert _capi.describe_decode_tree(_dargs(), _ext(window=0), t)[0] == "fa3_decode_bf16_d128_o16_tree+combine"
+    assert _capi.describe_decode_tree(_dargs(), ext(window=0), t)[0] == "fa3_decode_bf16_d128_o16_tree+combine"
     assert _capi.describe_decode_tree(_paged(D=64, dtype_in=1, dtype_out=2), None, t)[0] == "fa3_decode_fp16_d64_o32_tree+combine_paged"
     assert _capi.describe_decode_tree(_paged(Smax=128), None, t)[0] == "fa3_decode_bf16_d128_o16_tree_paged"
 

@@ -1,5 +1,5 @@
-"""CPU-side tests (no GPU) of the device-side KV-cache append (``pfa_kv_append*``, ABI v9 additive): exported symbols, the argument
-block's layout, every validation rule, the launch description, ``ops.kv_append``'s refusals, the plain-torch model of the rule
+"""CPU-side tests (no GPU) of the device-side KV-cache append (``pfa_kv_append*``, ABI v9 additive):
+every validation rule, the launch description, ``ops.kv_append``'s refusals, the plain-torch model of the rule
 (``ops.kv_append`` on CPU tensors: the executable specification the GPU tests compare the kernel with) against token-by-token
 loops written here, and ``PagedKVCache.advance`` + ``write_step`` against ``append_varlen``.
 
@@ -9,85 +9,19 @@ write and a read of a foreign row all show.  Every comparison is ``torch.equal``
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, lib  # noqa: F401
+from capi_testlib import kv_append_args as _args, kv_append_paged as _pargs, kv_append_uniform as _uargs
 from photonic_flash_attention_amd import _capi, ops
 
-SYMBOLS = ("pfa_kv_append_check", "pfa_kv_append", "pfa_kv_append_describe")
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 SENTINEL, NAN = -7.0, float("nan")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def _args(**over):
-    """A valid ragged contiguous call: B 5, Hkv 2, 640 packed rows of which a sequence has at most 300, Smax 4096, D 128."""
-    d = over.get("D", 128)
-    base = dict(k_new=0x1000, v_new=0x3000, k_cache=0x1000000, v_cache=0x2000000, cu_seqlens_q=0x9000, cache_seqlens=0x5000,
-                B=5, Hkv=2, total_new=640, max_seqlen_q=300, Smax=4096, D=d, dtype=0,
-                kn_stride_s=2 * d, kn_stride_h=d, vn_stride_s=2 * d, vn_stride_h=d,
-                k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d, v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d)
-    base.update(over)
-    return _capi.make_kv_append_args(**base)
-
-
-def _uargs(**over):
-    """The uniform call of the same cache: [B, Sq, Hkv, D] rows, Sq 300, no cu_seqlens_q."""
-    d = over.get("D", 128)
-    base = dict(cu_seqlens_q=0, total_new=1500, kn_stride_b=300 * 2 * d, vn_stride_b=300 * 2 * d)
-    base.update(over)
-    return _args(**base)
-
-
-def _pargs(**over):
-    """The ragged call over a pool of 100 pages laid out [num_pages, page_size, Hkv, D], 32 pages per sequence."""
-    ps, d = over.pop("_page", 128), over.get("D", 128)
-    base = dict(Smax=32 * ps, k_stride_b=ps * 2 * d, v_stride_b=ps * 2 * d, block_table=0x8000, block_table_stride_b=32,
-                page_size=ps, num_pages=100)
-    base.update(over)
-    return _args(**base)
 
 
 def _check(lib, a):
     return lib.pfa_kv_append_check(C.byref(a))
-
-
-def test_every_kv_append_symbol_is_declared_and_resolves(lib):
-    assert set(SYMBOLS) <= set(_capi.EXPORTS)
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in SYMBOLS:
-        assert getattr(lib, sym) is not None
-        assert f"int {sym}(const pfa_kv_append_args* a" in header
-
-
-def test_abi_version_layout_and_the_existing_argument_blocks_are_unchanged(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    A = _capi.PfaKvAppendArgs
-    fields = [f for f, _ in A._fields_]
-    offs = ",".join(f"offsetof(pfa_kv_append_args,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 4))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_fa3_prefill_varlen_args),'
-                   f'sizeof(pfa_fa3_cache_ext),sizeof(pfa_kv_append_args),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    # the three cache argument blocks as ABI v9 shipped them
-    assert got[:3] == [C.sizeof(_capi.PfaFa3DecodeArgs), C.sizeof(_capi.PfaFa3PrefillVarlenArgs), C.sizeof(_capi.PfaFa3CacheExt)] == [256, 224, 16]
-    assert got[3:] == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    for name in ("k_new", "v_new", "k_cache", "v_cache", "cu_seqlens_q", "cache_seqlens", "kn_stride_b", "vn_stride_h", "total_new",
-                 "max_seqlen_q", "dtype", "device_id", "block_table", "block_table_stride_b", "page_size", "num_pages", "reserved1"):
-        assert name in fields
 
 
 def test_kv_append_argument_validation(lib):

@@ -1,5 +1,5 @@
-"""CPU-side tests (no GPU) of the page copy inside a paged KV cache's pools (``pfa_page_copy*``, ABI v9 additive): exported symbols,
-the argument block's layout, every validation rule and the order the rules are reported in, the launch description,
+"""CPU-side tests (no GPU) of the page copy inside a paged KV cache's pools (``pfa_page_copy*``, ABI v9 additive):
+every validation rule and the order the rules are reported in, the launch description,
 ``ops.page_copy``'s refusals, and the plain-torch model of the rule (``ops.page_copy`` on CPU tensors: the executable specification the
 GPU tests compare the kernel with) against a token-by-token loop written here.
 
@@ -9,71 +9,19 @@ is ``torch.equal``: a copy is bit-exact."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, lib  # noqa: F401
+from capi_testlib import page_copy_args as _args
 from photonic_flash_attention_amd import _capi, ops
 
-SYMBOLS = ("pfa_page_copy_check", "pfa_page_copy", "pfa_page_copy_describe")
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 SENTINEL = -7.0
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def _args(**over):
-    """A valid call: 8 pairs with row counts over token-major pools of 100 pages of 128 keys, Hkv 2, D 128."""
-    ps, d, hkv = over.get("page_size", 128), over.get("D", 128), over.get("Hkv", 2)
-    base = dict(k_pool=0x1000000, v_pool=0x2000000, pairs=0x9000, rows=0x5000, pairs_stride=2,
-                k_stride_b=ps * hkv * d, k_stride_h=d, k_stride_s=hkv * d, v_stride_b=ps * hkv * d, v_stride_h=d, v_stride_s=hkv * d,
-                n_pairs=8, Hkv=hkv, D=d, page_size=ps, num_pages=100, dtype=0)
-    base.update(over)
-    return _capi.make_page_copy_args(**base)
 
 
 def _check(lib, a):
     return lib.pfa_page_copy_check(C.byref(a))
-
-
-def test_every_page_copy_symbol_is_declared_and_resolves(lib):
-    assert set(SYMBOLS) <= set(_capi.EXPORTS)
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in SYMBOLS:
-        assert getattr(lib, sym) is not None
-        assert f"int {sym}(const pfa_page_copy_args* a" in header
-
-
-def test_abi_version_layout_and_the_existing_argument_blocks_are_unchanged(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    A = _capi.PfaPageCopyArgs
-    fields = [f for f, _ in A._fields_]
-    offs = ",".join(f"offsetof(pfa_page_copy_args,{f})" for f in fields)
-    old = ("pfa_fa3_decode_args", "pfa_fa3_prefill_varlen_args", "pfa_fa3_cache_ext", "pfa_kv_append_args", "pfa_rope_append_args",
-           "pfa_attn_merge_args", "pfa_fa3_args", "pfa_fa3_bwd_args")
-    fmt = " ".join(["%zu"] * (len(fields) + len(old) + 1))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",{",".join(f"sizeof({t})" for t in old)},sizeof(pfa_page_copy_args),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    mirrors = (_capi.PfaFa3DecodeArgs, _capi.PfaFa3PrefillVarlenArgs, _capi.PfaFa3CacheExt, _capi.PfaKvAppendArgs, _capi.PfaRopeAppendArgs,
-               _capi.PfaAttnMergeArgs, _capi.PfaFa3Args, _capi.PfaFa3BwdArgs)
-    assert got[:len(old)] == [C.sizeof(m) for m in mirrors]
-    assert got[:4] == [256, 224, 16, 216]                    # the cache argument blocks as ABI v9 shipped them
-    assert got[len(old):] == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    assert fields == ["size", "flags", "k_pool", "v_pool", "pairs", "rows", "pairs_stride", "k_stride_b", "k_stride_h", "k_stride_s",
-                      "v_stride_b", "v_stride_h", "v_stride_s", "n_pairs", "Hkv", "D", "page_size", "num_pages", "dtype", "device_id",
-                      "reserved0"]
-    assert C.sizeof(A) == 8 + 4 * 8 + 8 + 6 * 8 + 8 * 4 == 128
 
 
 def test_page_copy_argument_validation(lib):

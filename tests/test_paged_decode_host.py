@@ -1,18 +1,15 @@
-"""CPU-side tests (no GPU) of the paged KV cache of the decode path (ABI v9): C layout of the appended fields, argument validation,
+"""CPU-side tests (no GPU) of the paged KV cache of the decode path (ABI v9): where the appended fields lie, argument validation,
 the workspace / split contract against the contiguous call, ``ops.fa3_decode(block_table=...)`` refusals and the ``PagedKVCache``
 bookkeeping on CPU tensors."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import decode_paged, lib  # noqa: F401
 from photonic_flash_attention_amd import _capi, ops
 
 # offsets of pfa_fa3_decode_args in ABI v8 (the struct before the paging fields were appended); its size was 232
@@ -24,44 +21,18 @@ V8_OFFSETS = dict(size=0, flags=4, q=8, k_cache=16, v_cache=24, o=32, lse=40, ca
 NEW_FIELDS = ("block_table", "block_table_stride_b", "page_size", "num_pages")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def test_paging_fields_are_appended_to_the_c_struct(tmp_path):
-    fields = tuple(V8_OFFSETS) + NEW_FIELDS
-    src = tmp_path / "sz.c"
-    fmt = " ".join(["%zu"] * (len(fields) + 1))
-    offs = ",".join(f"offsetof(pfa_fa3_decode_args,{f})" for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+def test_paging_fields_are_appended_behind_the_abi_v8_fields():
+    """Against the mirror, whose offsets tests/test_capi_conformance.py holds to the C struct's."""
     A = _capi.PfaFa3DecodeArgs
-    assert got == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    c_off = dict(zip(fields, got[1:]))
-    assert {f: c_off[f] for f in V8_OFFSETS} == V8_OFFSETS               # every old field where it was
-    assert [c_off[f] for f in NEW_FIELDS] == [232, 240, 248, 252] and got[0] == 256
-    assert _capi.PFA_ABI_VERSION == 9
+    assert [f for f, _ in A._fields_] == list(V8_OFFSETS) + list(NEW_FIELDS)
+    assert {f: getattr(A, f).offset for f in V8_OFFSETS} == V8_OFFSETS   # every old field where it was
+    assert [getattr(A, f).offset for f in NEW_FIELDS] == [232, 240, 248, 252] and C.sizeof(A) == 256
 
 
 def _pargs(**over):
     """A valid paged call: B 2, H 8, Hkv 2, Sq 1, D 128, 32 pages of 128 keys per sequence (Smax 4096) out of a pool of 100
-    pages laid out [num_pages, page_size, Hkv, D]."""
-    ps, hkv, d = over.pop("_page", 128), 2, over.get("D", 128)
-    base = dict(q=0x1000, k_cache=0x100000, v_cache=0x4000000, o=0x3000, B=2, H=8, Hkv=hkv, Sq=1, Smax=32 * ps, D=d,
-                q_stride_b=8 * d, q_stride_h=d, q_stride_s=8 * d, k_stride_b=ps * hkv * d, k_stride_h=d, k_stride_s=hkv * d,
-                v_stride_b=ps * hkv * d, v_stride_h=d, v_stride_s=hkv * d, o_stride_b=8 * d, o_stride_h=d, o_stride_s=8 * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5,
-                block_table=0x8000, block_table_stride_b=32, page_size=ps, num_pages=100)
-    base.update(over)
-    a = _capi.make_decode_args(**base)
-    n = _capi.load().pfa_fa3_decode_workspace_bytes(C.byref(a))
-    if n and "workspace" not in over:
-        a.workspace, a.workspace_bytes = 0x40000000, n
-    return a
+    pages laid out [num_pages, page_size, Hkv, D], with the workspace the library asks for; the strides move with D only."""
+    return decode_paged({**dict(k_cache=0x100000, v_cache=0x4000000, o=0x3000), **over}, Sq=1, pages=32, ws="asked", follow="D")
 
 
 def _contiguous(a):

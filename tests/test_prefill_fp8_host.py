@@ -1,5 +1,5 @@
 """CPU-side tests (no GPU) of the forward over an FP8 (e4m3fn) KV cache: the ``pfa_fa3_prefill_q8*`` / ``pfa_fa3_prefill_varlen_q8*`` entry
-points (ABI v9 additive) -- exported symbols, every field rule of ``pfa_fa3_kv_quant`` in its documented order through both ``_check``
+points (ABI v9 additive) -- every field rule of ``pfa_fa3_kv_quant`` in its documented order through both ``_check``
 calls, the rules of one-byte caches, the window, everything else equal to the 16-bit call's status, names and workgroups equal to the
 16-bit ``describe_ex`` -- then the refusals of ``ops.fa3_prefill_cache`` / ``ops.fa3_prefill_varlen`` and ``PagedKVCache.operands`` on
 CPU tensors."""
@@ -12,73 +12,31 @@ import os
 import pytest
 import torch
 
+from capi_testlib import (ALIGN, DTYPE, FLAGS, NULL, SHAPE, SIZE, STRIDE, decode_args, decode_paged, lib,  # noqa: F401
+                          prefill_varlen_args, prefill_varlen_paged, quant, ref)
 from conftest import REPO
-from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
-SYMBOLS = {
-    "pfa_fa3_prefill_q8_check": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant)",
-    "pfa_fa3_prefill_q8": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream)",
-    "pfa_fa3_prefill_q8_describe": "int {}(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, char* buf",
-    "pfa_fa3_prefill_varlen_q8_check": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant)",
-    "pfa_fa3_prefill_varlen_q8": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, void* stream)",
-    "pfa_fa3_prefill_varlen_q8_describe": "int {}(const pfa_fa3_prefill_varlen_args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant,",
-}
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 FP8 = torch.float8_e4m3fn
 KD, VD = 0x7000, 0x7400
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
 def _uargs(**over):
     """A valid contiguous block of the uniform call over one-byte caches: B 2, H 8, Hkv 2, Sq 300, Smax 1024, D 128."""
-    d, sq = over.get("D", 128), over.get("Sq", 300)
-    h, hkv, smax = over.get("H", 8), over.get("Hkv", 2), over.get("Smax", 1024)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=h, Hkv=hkv, Sq=sq, Smax=smax, D=d,
-                q_stride_b=sq * h * d, q_stride_h=d, q_stride_s=h * d, k_stride_b=smax * hkv * d, k_stride_h=d, k_stride_s=hkv * d,
-                v_stride_b=smax * hkv * d, v_stride_h=d, v_stride_s=hkv * d, o_stride_b=sq * h * d, o_stride_h=d, o_stride_s=h * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    return decode_args(over, Sq=300, Smax=1024, ws=False)
 
 
 def _upaged(**over):
-    ps, smax = 128, over.get("Smax", 1024)
-    d, hkv = over.get("D", 128), over.get("Hkv", 2)
-    base = dict(k_stride_b=ps * hkv * d, v_stride_b=ps * hkv * d, block_table=0x8000, block_table_stride_b=smax // ps, page_size=ps, num_pages=100)
-    base.update(over)
-    return _uargs(**base)
+    return decode_paged(over, Sq=300, Smax=1024, ws=False)
 
 
 def _vargs(**over):
     """A valid contiguous block of the ragged call: B 5, H 8, Hkv 2, 640 packed rows, at most 300 a sequence, Smax 1024, D 128."""
-    d, h, hkv, smax = over.get("D", 128), over.get("H", 8), over.get("Hkv", 2), over.get("Smax", 1024)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, cu_seqlens_q=0x9000, B=5, H=h, Hkv=hkv, total_q=640,
-                max_seqlen_q=300, Smax=smax, D=d, q_stride_s=h * d, q_stride_h=d, o_stride_s=h * d, o_stride_h=d,
-                k_stride_b=smax * hkv * d, k_stride_h=d, k_stride_s=hkv * d, v_stride_b=smax * hkv * d, v_stride_h=d, v_stride_s=hkv * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_prefill_varlen_args(**base)
+    return prefill_varlen_args(over, Smax=1024, follow="D H Hkv Smax")
 
 
 def _vpaged(**over):
-    ps, smax = 128, over.get("Smax", 1024)
-    d, hkv = over.get("D", 128), over.get("Hkv", 2)
-    base = dict(k_stride_b=ps * hkv * d, v_stride_b=ps * hkv * d, block_table=0x8000, block_table_stride_b=smax // ps, page_size=ps, num_pages=100)
-    base.update(over)
-    return _vargs(**base)
-
-
-def _quant(**kw):
-    return _capi.make_kv_quant(**{"k_descale": KD, "v_descale": VD, **kw})
-
-
-def _ref(e):
-    return None if e is None else C.byref(e)
+    return prefill_varlen_paged(over, Smax=1024, follow="D H Hkv Smax")
 
 
 # (check, 16-bit check_ex, launch, q8 describe, 16-bit describe_ex, blocks)
@@ -91,64 +49,59 @@ def _calls(lib):
     )
 
 
-def test_every_symbol_is_declared_and_resolves(lib):
-    assert set(SYMBOLS) <= set(_capi.EXPORTS)
+def test_the_abi_history_names_the_entry_points():
     header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym, proto in SYMBOLS.items():
-        assert getattr(lib, sym) is not None
-        assert proto.format(sym) in header, sym
-    assert "pfa_fa3_prefill_q8*" in header.split("Reference seam")[0]           # the ABI history names it
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9             # additive: the version stands
+    assert "pfa_fa3_prefill_q8*" in header.split("Reference seam")[0]
 
 
 def _quant_rules(chk, make):
     """The rules of pfa_fa3_kv_quant and of one-byte caches, each alone and in their documented order, for ``chk(a, quant)``."""
     ok = make()
-    assert chk(ok, _quant()) == 0
-    assert chk(ok, _quant(descale_stride_b=2)) == 0 and chk(ok, _quant(descale_stride_b=64)) == 0
-    assert chk(None, _quant()) == NULL
+    assert chk(ok, quant()) == 0
+    assert chk(ok, quant(descale_stride_b=2)) == 0 and chk(ok, quant(descale_stride_b=64)) == 0
+    assert chk(None, quant()) == NULL
     short = make()
     short.size -= 8
-    assert chk(short, _quant()) == SIZE
+    assert chk(short, quant()) == SIZE
     assert chk(ok, None) == NULL
-    wrong = _quant()
+    wrong = quant()
     for size in (32, 48):
         wrong.size = size
         assert chk(ok, wrong) == SIZE
-    assert chk(ok, _quant(flags=1)) == FLAGS
-    assert chk(ok, _quant(reserved=1)) == FLAGS
+    assert chk(ok, quant(flags=1)) == FLAGS
+    assert chk(ok, quant(reserved=1)) == FLAGS
     for dt in (0, 1, 2, 4, -1):
-        assert chk(ok, _quant(kv_dtype=dt)) == DTYPE
-    assert chk(ok, _quant(k_descale=0)) == NULL and chk(ok, _quant(v_descale=0)) == NULL
-    assert chk(ok, _quant(k_descale=KD + 2)) == ALIGN and chk(ok, _quant(v_descale=VD + 1)) == ALIGN
-    assert chk(ok, _quant(descale_stride_b=1)) == STRIDE and chk(ok, _quant(descale_stride_b=-2)) == STRIDE
+        assert chk(ok, quant(kv_dtype=dt)) == DTYPE
+    assert chk(ok, quant(k_descale=0)) == NULL and chk(ok, quant(v_descale=0)) == NULL
+    assert chk(ok, quant(k_descale=KD + 2)) == ALIGN and chk(ok, quant(v_descale=VD + 1)) == ALIGN
+    assert chk(ok, quant(descale_stride_b=1)) == STRIDE and chk(ok, quant(descale_stride_b=-2)) == STRIDE
     # a one-byte stride that is no multiple of 16: a multiple of 8 passes the 16-bit rule, not this one
     for f in ("k_stride_b", "k_stride_h", "k_stride_s", "v_stride_b", "v_stride_h", "v_stride_s"):
         a = make()
         setattr(a, f, getattr(a, f) + 8)
-        assert chk(a, _quant()) == STRIDE, f
-    assert chk(make(k_stride_s=-256), _quant()) == STRIDE and chk(make(v_stride_s=-256), _quant()) == STRIDE
+        assert chk(a, quant()) == STRIDE, f
+    assert chk(make(k_stride_s=-256), quant()) == STRIDE and chk(make(v_stride_s=-256), quant()) == STRIDE
     # a misaligned cache
-    assert chk(make(k_cache=0x1000008), _quant()) == ALIGN and chk(make(v_cache=0x2000004), _quant()) == ALIGN
+    assert chk(make(k_cache=0x1000008), quant()) == ALIGN and chk(make(v_cache=0x2000004), quant()) == ALIGN
     # the order: each rule wins over all that follow it
     bad = make(k_stride_s=264, k_cache=0x1000008)
     every = dict(flags=1, kv_dtype=0, k_descale=0, v_descale=VD + 2, descale_stride_b=1)
-    q = _quant(**every)
+    q = quant(**every)
     q.size = 8
     assert chk(bad, q) == SIZE
-    assert chk(bad, _quant(**every)) == FLAGS
+    assert chk(bad, quant(**every)) == FLAGS
     del every["flags"]
-    assert chk(bad, _quant(**every)) == DTYPE
+    assert chk(bad, quant(**every)) == DTYPE
     del every["kv_dtype"]
-    assert chk(bad, _quant(**every)) == NULL
+    assert chk(bad, quant(**every)) == NULL
     del every["k_descale"]
-    assert chk(bad, _quant(**every)) == ALIGN
+    assert chk(bad, quant(**every)) == ALIGN
     del every["v_descale"]
-    assert chk(bad, _quant(**every)) == STRIDE                                   # descale_stride_b
-    assert chk(bad, _quant()) == STRIDE                                          # the cache stride in front of the cache base
+    assert chk(bad, quant(**every)) == STRIDE                                   # descale_stride_b
+    assert chk(bad, quant()) == STRIDE                                          # the cache stride in front of the cache base
     short = make(k_stride_s=264)
     short.size -= 8
-    assert chk(short, _quant(flags=1)) == SIZE                                   # the block's own size comes first of all
+    assert chk(short, quant(flags=1)) == SIZE                                   # the block's own size comes first of all
     return ok
 
 
@@ -156,13 +109,13 @@ def test_field_rules_in_their_order_through_both_checks(lib):
     for check, check16, launch, describe, _, makes in _calls(lib):
         for make in makes:
             def chk(a, q, ext=None):
-                return check(_ref(a), _ref(ext), _ref(q))
+                return check(ref(a), ref(ext), ref(q))
             ok = _quant_rules(chk, make)
             # a window does not combine; window = 0 and a NULL extension are the plain call
-            assert chk(ok, _quant(), _capi.make_cache_ext(window=4)) == FLAGS
-            assert chk(ok, _quant(), _capi.make_cache_ext(window=0)) == 0
-            assert chk(make(k_cache=0x1000008), _quant(), _capi.make_cache_ext(window=4)) == ALIGN   # the cache base in front of the window
-            assert chk(make(D=96), _quant(), _capi.make_cache_ext(window=4)) == FLAGS                # ... which is in front of the old rules
+            assert chk(ok, quant(), _capi.make_cache_ext(window=4)) == FLAGS
+            assert chk(ok, quant(), _capi.make_cache_ext(window=0)) == 0
+            assert chk(make(k_cache=0x1000008), quant(), _capi.make_cache_ext(window=4)) == ALIGN   # the cache base in front of the window
+            assert chk(make(D=96), quant(), _capi.make_cache_ext(window=4)) == FLAGS                # ... which is in front of the old rules
             # then the 16-bit call's rules: the same status for every block the quant rules pass
             overs = [dict(q=0), dict(B=0), dict(D=96), dict(dtype_out=1), dict(dtype_in=2), dict(dtype_in=3), dict(o=0x800008), dict(flags=1),
                      dict(reserved0=1), dict(softmax_scale=0.0), dict(q_stride_s=4), dict(o_stride_s=6), dict(H=7), dict(causal=0),
@@ -171,26 +124,26 @@ def test_field_rules_in_their_order_through_both_checks(lib):
                 [dict(key_mask=0x6000, key_mask_stride_b=1024), dict(Sq=65), dict(Sq=1), dict(Sq=0)]
             for over in overs:
                 a = make(**over)
-                assert chk(a, _quant()) == check16(C.byref(a), None), over
+                assert chk(a, quant()) == check16(C.byref(a), None), over
             bad_ext = _capi.make_cache_ext(window=-1)
-            assert chk(ok, _quant(), bad_ext) == check16(C.byref(ok), C.byref(bad_ext)) == SHAPE
-            assert chk(ok, _quant(), _capi.make_cache_ext(flags=1)) == FLAGS
+            assert chk(ok, quant(), bad_ext) == check16(C.byref(ok), C.byref(bad_ext)) == SHAPE
+            assert chk(ok, quant(), _capi.make_cache_ext(flags=1)) == FLAGS
             # describe and the launch entry refuse the same way (nothing is launched: the status comes first)
             with pytest.raises(_capi.PfaError) as e:
-                describe(ok, None, _quant(kv_dtype=1))
+                describe(ok, None, quant(kv_dtype=1))
             assert e.value.status == DTYPE
-            assert launch(C.byref(ok), None, C.byref(_quant(k_descale=0)), None) == NULL
+            assert launch(C.byref(ok), None, C.byref(quant(k_descale=0)), None) == NULL
             assert launch(C.byref(ok), None, None, None) == NULL
-            assert launch(C.byref(ok), C.byref(_capi.make_cache_ext(window=4)), C.byref(_quant()), None) == FLAGS
+            assert launch(C.byref(ok), C.byref(_capi.make_cache_ext(window=4)), C.byref(quant()), None) == FLAGS
 
 
 def test_a_key_mask_gives_the_16_bit_calls_error_and_any_row_count_is_accepted(lib):
     chk = lib.pfa_fa3_prefill_q8_check
     for make in (_uargs, _upaged):
         a = make(key_mask=0x6000, key_mask_stride_b=1024)
-        assert chk(C.byref(a), None, C.byref(_quant())) == lib.pfa_fa3_prefill_check_ex(C.byref(a), None) == FLAGS
+        assert chk(C.byref(a), None, C.byref(quant())) == lib.pfa_fa3_prefill_check_ex(C.byref(a), None) == FLAGS
         for sq in (1, 64, 65, 257, 5000):                                        # no 64-row limit: that is the decode's
-            assert chk(C.byref(make(Sq=sq)), None, C.byref(_quant())) == 0, sq
+            assert chk(C.byref(make(Sq=sq)), None, C.byref(quant())) == 0, sq
 
 
 def test_describe_is_the_16_bit_describe_with_kv8_in_the_name(lib):
@@ -199,19 +152,19 @@ def test_describe_is_the_16_bit_describe_with_kv8_in_the_name(lib):
             for over in (dict(), dict(D=64, dtype_in=1, dtype_out=1), dict(dtype_out=2), dict(causal=0), dict(B=8, H=32, Hkv=8)):
                 a = make(**over)
                 name0, items0 = describe16(a, None)
-                for q in (_quant(), _quant(descale_stride_b=a.Hkv), _quant(k_descale=0x123450)):
+                for q in (quant(), quant(descale_stride_b=a.Hkv), quant(k_descale=0x123450)):
                     for ext in (None, _capi.make_cache_ext()):
                         name, items = describe(a, ext, q)
                         assert items == items0 > 0
                         assert "_kv8" in name and "_kv8" not in name0 and name.replace("_kv8", "") == name0
-    assert _capi.describe_prefill_q8(_uargs(), None, _quant()) == ("fa3_prefill_bf16_d128_o16_causal_kv8", 2 * 8 * 2)
-    assert _capi.describe_prefill_q8(_upaged(D=64, dtype_in=1, dtype_out=2, causal=0), None, _quant())[0] == "fa3_prefill_fp16_d64_o32_kv8_paged"
-    assert _capi.describe_prefill_varlen_q8(_vargs(), None, _quant()) == ("fa3_prefill_bf16_d128_o16_causal_kv8_varlen", 5 * 8 * 2)
-    assert _capi.describe_prefill_varlen_q8(_vpaged(dtype_out=2), None, _quant())[0] == "fa3_prefill_bf16_d128_o32_causal_kv8_varlen_paged"
+    assert _capi.describe_prefill_q8(_uargs(), None, quant()) == ("fa3_prefill_bf16_d128_o16_causal_kv8", 2 * 8 * 2)
+    assert _capi.describe_prefill_q8(_upaged(D=64, dtype_in=1, dtype_out=2, causal=0), None, quant())[0] == "fa3_prefill_fp16_d64_o32_kv8_paged"
+    assert _capi.describe_prefill_varlen_q8(_vargs(), None, quant()) == ("fa3_prefill_bf16_d128_o16_causal_kv8_varlen", 5 * 8 * 2)
+    assert _capi.describe_prefill_varlen_q8(_vpaged(dtype_out=2), None, quant())[0] == "fa3_prefill_bf16_d128_o32_causal_kv8_varlen_paged"
     # a short buffer is truncated and terminated, a NULL buffer only counts
     buf = C.create_string_buffer(b"x" * 16, 16)
-    assert lib.pfa_fa3_prefill_q8_describe(C.byref(_uargs()), None, C.byref(_quant()), buf, 12) == 32 and buf.value == b"fa3_prefill"
-    assert lib.pfa_fa3_prefill_q8_describe(C.byref(_uargs()), None, C.byref(_quant()), None, 0) == 32
+    assert lib.pfa_fa3_prefill_q8_describe(C.byref(_uargs()), None, C.byref(quant()), buf, 12) == 32 and buf.value == b"fa3_prefill"
+    assert lib.pfa_fa3_prefill_q8_describe(C.byref(_uargs()), None, C.byref(quant()), None, 0) == 32
 
 
 # --- ops: refusals --------------------------------------------------------------------------------------------------------------------

@@ -1,58 +1,30 @@
-"""CPU-side tests (no GPU) of the forward over a KV cache (``pfa_fa3_prefill*``, ABI v9 additive): exported symbols, argument
+"""CPU-side tests (no GPU) of the forward over a KV cache (``pfa_fa3_prefill*``, ABI v9 additive): argument
 validation on the decode's argument block, the launch description, host-tensor refusal and ``PagedKVCache.prefill``'s plumbing."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import decode_args, decode_paged, lib  # noqa: F401
 from photonic_flash_attention_amd import _capi, ops
-
-PREFILL_SYMBOLS = ("pfa_fa3_prefill_check", "pfa_fa3_prefill", "pfa_fa3_prefill_describe")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _args(**over):
-    """A valid contiguous call: B 2, H 8, Hkv 2, Sq 300, Smax 4096, D 128, [B, S, H, D] q and cache."""
-    sq, d = over.get("Sq", 300), over.get("D", 128)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=8, Hkv=2, Sq=sq, Smax=4096, D=d,
-                q_stride_b=max(sq, 1) * 8 * d, q_stride_h=d, q_stride_s=8 * d, k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d,
-                v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d, o_stride_b=max(sq, 1) * 8 * d, o_stride_h=d, o_stride_s=8 * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    """A valid contiguous call: B 2, H 8, Hkv 2, Sq 300, Smax 4096, D 128, [B, S, H, D] q and cache, no workspace.  The derived strides
+    move with Sq and D only: an override of H, Hkv or Smax leaves those of the default shape in place."""
+    return decode_args(over, Sq=300, ws=False, follow="D Sq", min_rows=1)
 
 
 def _pargs(**over):
     """A valid paged call of the same logical shape: 32 pages of ``_page`` keys per sequence out of a pool of 100 pages laid out
     [num_pages, page_size, Hkv, D]."""
-    ps, d = over.pop("_page", 128), over.get("D", 128)
-    base = dict(Smax=32 * ps, k_stride_b=ps * 2 * d, v_stride_b=ps * 2 * d, block_table=0x8000, block_table_stride_b=32,
-                page_size=ps, num_pages=100)
-    base.update(over)
-    return _args(**base)
+    return decode_paged(over, Sq=300, pages=32, ws=False, follow="D Sq", min_rows=1)
 
 
-def test_every_prefill_symbol_is_declared_and_resolves(lib):
-    assert set(PREFILL_SYMBOLS) <= set(_capi.EXPORTS)
-    for sym in PREFILL_SYMBOLS:
-        assert getattr(lib, sym) is not None
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in PREFILL_SYMBOLS:
-        assert f"int {sym}(const pfa_fa3_decode_args* a" in header
-
-
-def test_abi_version_and_the_decode_row_limit_are_unchanged(lib):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
+def test_the_decode_row_limit_is_unchanged(lib):
     a = _args(Sq=65)
     n = lib.pfa_fa3_decode_workspace_bytes(C.byref(a))
     a.workspace, a.workspace_bytes = 0x40000000, n

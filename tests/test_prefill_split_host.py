@@ -1,5 +1,5 @@
 """CPU-side tests (no GPU) of the forward over a KV cache with the keys split over workgroups (``pfa_fa3_prefill_split*``, ABI v9
-additive): exported symbols, the plan and its invariance, the workspace size, validation on the decode's argument block, the launch
+additive): the plan and its invariance, the workspace size, validation on the decode's argument block, the launch
 description, and the refusals of ``ops.fa3_prefill_cache(key_splits=)`` / ``prefix_key_splits=`` before any launch."""
 
 from __future__ import annotations
@@ -10,38 +10,21 @@ import os
 import pytest
 import torch
 
+from capi_testlib import ALIGN, FLAGS, NULL, SHAPE, STRIDE, decode_args, decode_paged, lib  # noqa: F401
 from conftest import REPO
-from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
-
-SPLIT_SYMBOLS = ("pfa_fa3_prefill_split_plan", "pfa_fa3_prefill_split_workspace_bytes", "pfa_fa3_prefill_split_check",
-                 "pfa_fa3_prefill_split", "pfa_fa3_prefill_split_describe")
-NULL, SHAPE, STRIDE, ALIGN, FLAGS = -1, -3, -6, -7, -10
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _args(**over):
-    """A valid contiguous call: B 2, H 8, Hkv 2, Sq 300, Smax 4096, D 128, [B, S, H, D] q and cache (test_prefill_host's)."""
-    sq, d = over.get("Sq", 300), over.get("D", 128)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=8, Hkv=2, Sq=sq, Smax=4096, D=d,
-                q_stride_b=max(sq, 1) * 8 * d, q_stride_h=d, q_stride_s=8 * d, k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d,
-                v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d, o_stride_b=max(sq, 1) * 8 * d, o_stride_h=d, o_stride_s=8 * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_decode_args(**base)
+    """A valid contiguous call: B 2, H 8, Hkv 2, Sq 300, Smax 4096, D 128, [B, S, H, D] q and cache, no workspace.  The derived strides
+    move with Sq and D only: an override of H, Hkv or Smax leaves those of the default shape in place."""
+    return decode_args(over, Sq=300, ws=False, follow="D Sq", min_rows=1)
 
 
 def _pargs(**over):
-    """The paged call of the same logical shape: 32 pages of ``_page`` keys per sequence out of a pool of 100 pages."""
-    ps, d = over.pop("_page", 128), over.get("D", 128)
-    base = dict(Smax=32 * ps, k_stride_b=ps * 2 * d, v_stride_b=ps * 2 * d, block_table=0x8000, block_table_stride_b=32,
-                page_size=ps, num_pages=100)
-    base.update(over)
-    return _args(**base)
+    """A valid paged call of the same logical shape: 32 pages of ``_page`` keys per sequence out of a pool of 100 pages laid out
+    [num_pages, page_size, Hkv, D]."""
+    return decode_paged(over, Sq=300, pages=32, ws=False, follow="D Sq", min_rows=1)
 
 
 def _with_ws(lib, a, n, ptr=0x40000000):
@@ -49,14 +32,9 @@ def _with_ws(lib, a, n, ptr=0x40000000):
     return a
 
 
-def test_every_split_symbol_is_declared_and_resolves(lib):
-    assert set(SPLIT_SYMBOLS) <= set(_capi.EXPORTS)
+def test_the_split_limit_is_the_merge_limit():
     header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in SPLIT_SYMBOLS:
-        assert getattr(lib, sym) is not None
-        assert f" {sym}(const pfa_fa3_decode_args* a, int32_t key_splits" in header
     assert "#define PFA_PREFILL_MAX_SPLITS 8" in header and _capi.PFA_PREFILL_MAX_SPLITS == _capi.PFA_MERGE_MAX_PARTS == 8
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
 
 
 def test_plan_returns_an_explicit_count_and_refuses_the_rest(lib):

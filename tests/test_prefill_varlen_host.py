@@ -1,76 +1,33 @@
-"""CPU-side tests (no GPU) of the ragged forward over a KV cache (``pfa_fa3_prefill_varlen*``, ABI v9 additive): exported symbols,
-the argument block's layout, every validation rule, the launch description, ``ops.fa3_prefill_varlen``'s refusals and the
+"""CPU-side tests (no GPU) of the ragged forward over a KV cache (``pfa_fa3_prefill_varlen*``, ABI v9 additive):
+every validation rule, the launch description, ``ops.fa3_prefill_varlen``'s refusals and the
 ``PagedKVCache`` plumbing (``append_varlen`` against per-slot ``append``, ``prefill_varlen``'s cu_seqlens_q)."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
-from kvcache_testlib import built_lib
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, lib, prefill_varlen_args, prefill_varlen_paged  # noqa: F401
 from photonic_flash_attention_amd import _capi, ops
-
-VARLEN_SYMBOLS = ("pfa_fa3_prefill_varlen_check", "pfa_fa3_prefill_varlen", "pfa_fa3_prefill_varlen_describe")
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
 
 
 def _args(**over):
     """A valid contiguous call: B 5, H 8, Hkv 2, 640 packed rows of which a sequence has at most 300, Smax 4096, D 128."""
-    d = over.get("D", 128)
-    base = dict(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, cu_seqlens_q=0x9000, B=5, H=8, Hkv=2, total_q=640,
-                max_seqlen_q=300, Smax=4096, D=d, q_stride_s=8 * d, q_stride_h=d, o_stride_s=8 * d, o_stride_h=d,
-                k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d, v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d,
-                dtype_in=0, dtype_out=0, causal=1, softmax_scale=d ** -0.5)
-    base.update(over)
-    return _capi.make_prefill_varlen_args(**base)
+    return prefill_varlen_args(over)
 
 
 def _pargs(**over):
     """The same logical shape over a pool of 100 pages laid out [num_pages, page_size, Hkv, D], 32 pages per sequence."""
-    ps, d = over.pop("_page", 128), over.get("D", 128)
-    base = dict(Smax=32 * ps, k_stride_b=ps * 2 * d, v_stride_b=ps * 2 * d, block_table=0x8000, block_table_stride_b=32,
-                page_size=ps, num_pages=100)
-    base.update(over)
-    return _args(**base)
+    return prefill_varlen_paged(over, pages=32)
 
 
 def _check(lib, a):
     return lib.pfa_fa3_prefill_varlen_check(C.byref(a))
 
 
-def test_every_varlen_symbol_is_declared_and_resolves(lib):
-    assert set(VARLEN_SYMBOLS) <= set(_capi.EXPORTS)
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in VARLEN_SYMBOLS:
-        assert getattr(lib, sym) is not None
-        assert f"int {sym}(const pfa_fa3_prefill_varlen_args* a" in header
-
-
-def test_abi_version_and_the_decode_argument_block_are_unchanged(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    A, D = _capi.PfaFa3PrefillVarlenArgs, _capi.PfaFa3DecodeArgs
-    fields = [f for f, _ in A._fields_]
-    offs = ",".join(f"offsetof(pfa_fa3_prefill_varlen_args,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 2))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_fa3_prefill_varlen_args),{offs});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(D) == 256                   # the decode's block as ABI v9 shipped it
-    assert got[1:] == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    # the existing prefill entry point still takes the decode's block
+def test_the_uniform_prefill_still_takes_the_decode_block(lib):
     a = _capi.make_decode_args(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=2, H=8, Hkv=2, Sq=300, Smax=4096, D=128,
                                q_stride_b=300 * 1024, q_stride_h=128, q_stride_s=1024, k_stride_b=4096 * 256, k_stride_h=128, k_stride_s=256,
                                v_stride_b=4096 * 256, v_stride_h=128, v_stride_s=256, o_stride_b=300 * 1024, o_stride_h=128, o_stride_s=1024,

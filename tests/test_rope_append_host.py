@@ -1,5 +1,5 @@
-"""CPU-side tests (no GPU) of the rotary embedding fused into the KV-cache append (``pfa_rope_append*``, ABI v9 additive): exported
-symbols, the argument block's layout, every validation rule in the order the header states, the launch description, the refusals of
+"""CPU-side tests (no GPU) of the rotary embedding fused into the KV-cache append (``pfa_rope_append*``, ABI v9 additive):
+every validation rule in the order the header states, the launch description, the refusals of
 ``ops.rope_append`` and of the attention calls' rotary keywords, and the plain-torch model of the rule (``ops.rope_append`` on CPU
 tensors: the executable specification the GPU tests compare the kernel with).
 
@@ -13,95 +13,28 @@ from __future__ import annotations
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, lib  # noqa: F401
+from capi_testlib import rope_append_args as _args, rope_append_paged as _pargs, rope_append_uniform as _uargs
 from conftest import REPO
-from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
-SYMBOLS = ("pfa_rope_append_check", "pfa_rope_append", "pfa_rope_append_describe")
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 SENTINEL, NAN = -7.0, float("nan")
 IL = _capi.PFA_ROPE_INTERLEAVED
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def _args(**over):
-    """A valid ragged contiguous call with Q: B 5, H 4, Hkv 2, 640 packed rows of which a sequence has at most 300, Smax 4096, D 128,
-    rot_dim 64, tables of 4096 positions."""
-    d = over.get("D", 128)
-    base = dict(q=0x100000, q_out=0x200000, k_new=0x1000, v_new=0x3000, k_cache=0x1000000, v_cache=0x2000000, cos=0x400000, sin=0x500000,
-                cu_seqlens_q=0x9000, cache_seqlens=0x5000, pos_offsets=0x6000,
-                B=5, H=4, Hkv=2, total_new=640, max_seqlen_q=300, Smax=4096, D=d, rot_dim=min(64, d), max_pos=4096, dtype=0, cs_stride=32,
-                q_stride_s=4 * d, q_stride_h=d, qo_stride_s=4 * d, qo_stride_h=d,
-                kn_stride_s=2 * d, kn_stride_h=d, vn_stride_s=2 * d, vn_stride_h=d,
-                k_stride_b=4096 * 2 * d, k_stride_h=d, k_stride_s=2 * d, v_stride_b=4096 * 2 * d, v_stride_h=d, v_stride_s=2 * d)
-    base.update(over)
-    return _capi.make_rope_append_args(**base)
-
-
-def _uargs(**over):
-    """The uniform call of the same cache: [B, Sq, heads, D] rows, Sq 300, no cu_seqlens_q."""
-    d = over.get("D", 128)
-    base = dict(cu_seqlens_q=0, total_new=1500, kn_stride_b=300 * 2 * d, vn_stride_b=300 * 2 * d, q_stride_b=300 * 4 * d, qo_stride_b=300 * 4 * d)
-    base.update(over)
-    return _args(**base)
-
-
-def _pargs(**over):
-    """The ragged call over a pool of 100 pages laid out [num_pages, page_size, Hkv, D], 32 pages per sequence."""
-    ps, d = over.pop("_page", 128), over.get("D", 128)
-    base = dict(Smax=32 * ps, k_stride_b=ps * 2 * d, v_stride_b=ps * 2 * d, block_table=0x8000, block_table_stride_b=32,
-                page_size=ps, num_pages=100)
-    base.update(over)
-    return _args(**base)
 
 
 def _check(lib, a):
     return lib.pfa_rope_append_check(C.byref(a))
 
 
-def test_every_rope_append_symbol_is_declared_and_resolves(lib):
-    assert set(SYMBOLS) <= set(_capi.EXPORTS)
+def test_the_interleaved_flag_and_the_abi_history_entry():
     header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in SYMBOLS:
-        assert getattr(lib, sym) is not None
-        assert f"int {sym}(const pfa_rope_append_args* a" in header
     assert "#define PFA_ROPE_INTERLEAVED 0x1u" in header and "v9, additive: pfa_rope_append*" in header
-
-
-def test_abi_version_layout_and_the_existing_argument_blocks_are_unchanged(lib, tmp_path):
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9
-    A = _capi.PfaRopeAppendArgs
-    fields = [f for f, _ in A._fields_]
-    offs = ",".join(f"offsetof(pfa_rope_append_args,{f})" for f in fields)
-    fmt = " ".join(["%zu"] * (len(fields) + 6))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{fmt}",sizeof(pfa_fa3_decode_args),sizeof(pfa_fa3_prefill_varlen_args),'
-                   f'sizeof(pfa_fa3_cache_ext),sizeof(pfa_kv_append_args),(size_t)PFA_ROPE_INTERLEAVED,sizeof(pfa_rope_append_args),{offs});'
-                   'return 0;}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    # the argument blocks ABI v9 shipped
-    assert got[:4] == [C.sizeof(_capi.PfaFa3DecodeArgs), C.sizeof(_capi.PfaFa3PrefillVarlenArgs), C.sizeof(_capi.PfaFa3CacheExt),
-                       C.sizeof(_capi.PfaKvAppendArgs)] == [256, 224, 16, 216]
-    assert got[4] == IL == 1
-    assert got[5:] == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    for name in ("flags", "q", "q_out", "k_new", "v_new", "k_cache", "v_cache", "cos", "sin", "cu_seqlens_q", "cache_seqlens", "pos_offsets",
-                 "q_stride_b", "q_stride_s", "q_stride_h", "qo_stride_b", "qo_stride_s", "qo_stride_h", "kn_stride_b", "vn_stride_h",
-                 "k_stride_s", "v_stride_b", "cs_stride", "B", "H", "Hkv", "total_new", "max_seqlen_q", "Smax", "D", "rot_dim", "max_pos",
-                 "dtype", "device_id", "block_table", "block_table_stride_b", "page_size", "num_pages", "reserved0", "reserved1"):
-        assert name in fields
+    assert IL == 1
 
 
 # every rule of the header's "Field rules", in the order the errors are reported (the size rule is checked apart)

@@ -1,5 +1,5 @@
-"""CPU-side tests (no GPU) of the packed variable-length training path (``pfa_fa3_varlen_*``, ABI v9 additive): exported symbols, the two
-argument blocks' layout, every field rule through ``pfa_fa3_varlen_check`` / ``pfa_fa3_varlen_bwd_check`` and the order the rules are
+"""CPU-side tests (no GPU) of the packed variable-length training path (``pfa_fa3_varlen_*``, ABI v9 additive):
+every field rule through ``pfa_fa3_varlen_check`` / ``pfa_fa3_varlen_bwd_check`` and the order the rules are
 reported in, the launch descriptions, and the plain-torch model (``ops.fa3_varlen_forward`` / ``fa3_varlen_backward`` /
 ``fa3_varlen_attention`` on CPU tensors: the executable specification) against ``dense_testlib.reference`` per sequence in fp64, its
 exact cases and its clamping rule."""
@@ -7,49 +7,17 @@ exact cases and its clamping rule."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-from conftest import REPO
+from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, SHAPE, SIZE, STRIDE, lib  # noqa: F401
+from capi_testlib import varlen_args as _fwd, varlen_bwd_args as _bwd
 from dense_testlib import BOUND_GRAD, BOUND_O, reference
-from kvcache_testlib import built_lib
 from photonic_flash_attention_amd import _capi, ops
 
-FWD_SYMBOLS = ("pfa_fa3_varlen_check", "pfa_fa3_varlen_fwd", "pfa_fa3_varlen_describe")
-BWD_SYMBOLS = ("pfa_fa3_varlen_bwd_check", "pfa_fa3_varlen_bwd", "pfa_fa3_varlen_bwd_describe", "pfa_fa3_varlen_bwd_workspace_bytes")
-NULL, SIZE, SHAPE, HEAD_DIM, DTYPE, STRIDE, ALIGN, FLAGS = -1, -2, -3, -4, -5, -6, -7, -10
 BF16, FP16, FP32 = 0, 1, 2
 INF = float("inf")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return built_lib()
-
-
-def _fwd(**over):
-    """A valid forward block: B 3, H 4, Hkv 2, D 128, 1000 packed rows and 900 packed keys, bf16 in and out."""
-    base = dict(q=0x100000, k=0x200000, v=0x300000, o=0x400000, lse=0x500000, cu_seqlens_q=0x600000, cu_seqlens_k=0x700000,
-                q_stride_s=512, q_stride_h=128, k_stride_s=256, k_stride_h=128, v_stride_s=256, v_stride_h=128, o_stride_s=512, o_stride_h=128,
-                B=3, H=4, Hkv=2, total_q=1000, total_k=900, max_seqlen_q=300, max_seqlen_k=257, D=128, dtype_in=BF16, dtype_out=BF16,
-                causal=1, softmax_scale=128 ** -0.5)
-    base.update(over)
-    return _capi.make_varlen_args(**base)
-
-
-def _bwd(**over):
-    """The backward block of the same problem, 16-bit gradients."""
-    base = dict(q=0x100000, k=0x200000, v=0x300000, o=0x400000, dout=0x800000, lse=0x500000, dq=0x900000, dk=0xA00000, dv=0xB00000,
-                delta=0xC00000, cu_seqlens_q=0x600000, cu_seqlens_k=0x700000,
-                q_stride_s=512, q_stride_h=128, k_stride_s=256, k_stride_h=128, v_stride_s=256, v_stride_h=128, o_stride_s=512, o_stride_h=128,
-                do_stride_s=512, do_stride_h=128, dq_stride_s=512, dq_stride_h=128, dk_stride_s=256, dk_stride_h=128, dv_stride_s=256,
-                dv_stride_h=128, B=3, H=4, Hkv=2, total_q=1000, total_k=900, max_seqlen_q=300, max_seqlen_k=257, D=128, dtype=BF16,
-                dtype_grad=BF16, causal=1, softmax_scale=128 ** -0.5)
-    base.update(over)
-    return _capi.make_varlen_bwd_args(**base)
 
 
 def _fc(lib, a):
@@ -58,38 +26,6 @@ def _fc(lib, a):
 
 def _bc(lib, a):
     return lib.pfa_fa3_varlen_bwd_check(C.byref(a))
-
-
-def test_every_varlen_symbol_is_declared_and_resolves(lib):
-    assert set(FWD_SYMBOLS + BWD_SYMBOLS) <= set(_capi.EXPORTS)
-    header = open(os.path.join(REPO, "include", "pfa_hip.h")).read()
-    for sym in FWD_SYMBOLS:
-        assert getattr(lib, sym) is not None and f"int {sym}(const pfa_fa3_varlen_args* a" in header
-    for sym in BWD_SYMBOLS:
-        assert getattr(lib, sym) is not None and f" {sym}(const pfa_fa3_varlen_bwd_args* a" in header
-    assert _capi.PFA_ABI_VERSION == 9 and lib.pfa_abi_version() == 9            # additive: the version stays
-
-
-def test_sizeof_and_offsets_of_the_ctypes_structs_match_the_header(tmp_path):
-    blocks = (("pfa_fa3_varlen_args", _capi.PfaFa3VarlenArgs), ("pfa_fa3_varlen_bwd_args", _capi.PfaFa3VarlenBwdArgs))
-    exprs = []
-    for name, A in blocks:
-        exprs += [f"sizeof({name})"] + [f"offsetof({name},{f})" for f, _ in A._fields_]
-    exprs += ["sizeof(pfa_fa3_bwd_args)", "sizeof(pfa_fa3_prefill_varlen_args)"]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pfa_hip.h"\n'
-                   f'int main(){{printf("{" ".join(["%zu"] * len(exprs))}",{",".join(exprs)});return 0;}}')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    want = []
-    for _, A in blocks:
-        want += [C.sizeof(A)] + [getattr(A, f).offset for f, _ in A._fields_]
-    want += [C.sizeof(_capi.PfaFa3BwdArgs), C.sizeof(_capi.PfaFa3PrefillVarlenArgs)]       # the neighbours are what they were
-    assert got == want
-    assert C.sizeof(_capi.PfaFa3VarlenArgs) == 8 + 7 * 8 + 8 * 8 + 14 * 4
-    assert C.sizeof(_capi.PfaFa3VarlenBwdArgs) == 8 + 12 * 8 + 16 * 8 + 14 * 4
-    assert _fwd().size == C.sizeof(_capi.PfaFa3VarlenArgs) and _bwd().size == C.sizeof(_capi.PfaFa3VarlenBwdArgs)
 
 
 def test_forward_field_rules_one_case_per_error_code(lib):
