@@ -1,5 +1,19 @@
-"""What the KV-cache tests share: the fp64 attention reference, the error bounds, the page scatter and a few small helpers.  Plain
-functions and constants; pytest collects nothing from here, and tests/test_kvcache_testlib.py tests it on the CPU.
+"""What the KV-cache tests share.  Plain functions and constants; pytest collects nothing from here, and tests/test_kvcache_testlib.py
+tests it on the CPU, the runner with a stand-in kernel.  A new mode's GPU tests are its cases and its own assertions around these:
+
+  ``reference`` / ``check_out`` / ``check_lse``     the fp64 attention, the bound on O, the rule for the LSE (below); ``merge_ref64``
+  ``problem`` / ``gen`` / ``i32`` / ``device``      device draws of q, k, v; small tensors
+  ``guard(k, v, lens, sqs, window)``                the one NaN rule: copies with NaN wherever a kernel promises not to read (``window_lo``)
+  ``scatter`` / ``share_prefix_pages``              caches over pools in a random page order (page 0 unnamed, pages released below a window),
+                                                    a prefix held once; ``contiguous_of`` gathers a ``PagedKVCache`` back
+  ``run_and_check(call, q, k, v, lens, ...)``       guard, call, synchronise, fp64 reference (``with_ref`` makes it the mode's), dtype, bounds
+  ``both(call, q, kn, vn, kp, vp, table, ...)``     contiguous call == paged call, bit for bit and finite
+  ``seq_rows`` / ``ragged_equals_uniform``          ragged call == per-sequence uniform calls, bit for bit
+  ``capture(step)`` / ``check_against_cache``       warm-up and graph capture; a replay over a ``PagedKVCache`` against fp64
+  ``FP8, NANB, b8, quant, dequant, to16, poisoned, scatter_fp8``     the same small change for e4m3 caches, as bytes
+  ``prefix_problem`` / ``check_step`` / ``both_prefix_caches``       the shared-prefix step
+
+Every helper that runs a kernel takes the attention function as its first argument and its device from the tensors.
 
 The reference is fp64 attention of ``q [B,H,Sq,D]`` over ``k/v [B,Hkv,Smax,D]`` with the bottom-right causal rule per batch: with
 ``off_b = len_b - Sq``, row i sees key j iff ``j < len_b``, ``j <= i + off_b`` (causal), ``j > i + off_b - W`` (window) and the key mask
@@ -122,24 +136,35 @@ def problem(B, H, Hkv, Sq, Smax, D, dtype, seed):
     return q, k, v
 
 
-def poison(k, v, lens):
-    """Copies of the caches with NaN at and past each batch's length (what an unfilled tail may hold)."""
+def window_lo(lens, sqs, window):
+    """Per sequence the first key a window lets any row see, ``max(0, len_b - Sq_b - W + 1)`` (0 without a window).  sqs: an int or a list."""
+    if window is None:
+        return [0] * len(lens)
+    return [max(0, n - (sqs if isinstance(sqs, int) else sqs[b]) - window + 1) for b, n in enumerate(lens)]
+
+
+def guard(k, v, lens, sqs=None, window=None):
+    """Copies of the caches with NaN wherever the kernels promise not to read: at and past ``len_b`` (what an unfilled tail may hold) and,
+    under a window, below ``floor64(max(0, len_b - Sq_b - W + 1))``.  sqs: the row count, or one per sequence; needed with a window only."""
     kn, vn = k.clone(), v.clone()
-    for b, n in enumerate(lens):
-        kn[b, :, n:] = NAN
-        vn[b, :, n:] = NAN
+    for b, (n, lo) in enumerate(zip(lens, window_lo(lens, sqs, window))):
+        for t in (kn, vn):
+            t[b, :, n:] = NAN
+            t[b, :, :lo // 64 * 64] = NAN
     return kn, vn
 
 
-def scatter(k, v, page, seed, layout="phsd", spare=5):
+def scatter(k, v, page, seed, layout="phsd", spare=5, first=0, lo=None):
     """Scatter contiguous [B, Hkv, Smax, D] caches over pools in a random page order.  -> (k_pool, v_pool, table) with the pools as
-    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN (and so does whatever NaN the caches carry)."""
+    [num_pages, Hkv, page, D] views; pages no table entry names hold NaN (and so does whatever NaN the caches carry).  first: the first
+    page a table may name (1 leaves page 0, where a clamped -1 lands, unnamed).  lo: per sequence the first key that is read
+    (``window_lo``); the table entries below ``lo_b // page`` become -1 and their pages NaN."""
     B, Hkv, Smax, D = k.shape
     assert Smax % page == 0
     pages = Smax // page
-    NP = B * pages + spare
+    NP = first + B * pages + spare
     dev = k.device
-    perm = torch.randperm(NP, generator=torch.Generator().manual_seed(seed))[:B * pages]
+    perm = torch.randperm(NP - first, generator=torch.Generator().manual_seed(seed))[:B * pages] + first
     table = perm.to(torch.int32).reshape(B, pages).to(dev)
     pools = []
     for src in (k, v):
@@ -151,7 +176,20 @@ def scatter(k, v, page, seed, layout="phsd", spare=5):
             pool = torch.full((2 * NP, Hkv, page + 64, D), NAN, dtype=k.dtype, device=dev)[::2, :, :page]
         pool[perm.to(dev)] = src.reshape(B, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(B * pages, Hkv, page, D)
         pools.append(pool)
+    for b, n in enumerate(lo or ()):
+        dead = table[b, :n // page].long()
+        table[b, :n // page] = -1
+        for pool in pools:
+            pool[dead] = NAN
     return pools[0], pools[1], table
+
+
+def share_prefix_pages(kp, vp, table, src, dst, n_pages):
+    """Sequence ``dst`` names ``src``'s first ``n_pages`` pages from now on -- a prefix held once -- and its own copies turn to NaN."""
+    freed = table[dst, :n_pages].clone()
+    table[dst, :n_pages] = table[src, :n_pages]
+    for pool in (kp, vp):
+        pool[freed.long()] = NAN
 
 
 def contiguous_of(cache, Smax):
@@ -178,6 +216,130 @@ def capture(step):
     with torch.cuda.graph(graph):
         res = step()
     return graph, res
+
+
+# --- run, synchronise, check: what a mode's GPU tests are made of ---------------------------------------------------------------------
+# Every helper takes the attention function as ``call`` and its device from the tensors, so the CPU tests drive them with a stand-in.
+
+def _sync(t):
+    if t.is_cuda:
+        torch.cuda.synchronize()
+
+
+def run_and_check(call, q, k, v, lens, *, causal=True, window=None, key_mask=None, out_dtype=None, ref=None, sqs=None, guarded=True,
+                  with_ref=None, what="", **kw):
+    """``call`` on the guarded caches against fp64 on the clean ones -> (o, lse).  lens: a list, an int32 tensor or None (the whole cache;
+    then nothing is guarded).  guarded=False hands the clean caches over.  ref: ``reference(...)``'s triple if the caller has it; with_ref
+    turns it into the mode's own (``with_sink``).  sqs: the rows of each sequence where q's shape does not say (a ragged call)."""
+    sl = lens if lens is None or torch.is_tensor(lens) else i32(list(lens), q.device)
+    kn, vn = (k, v) if lens is None or not guarded else guard(k, v, sl.tolist(), q.shape[2] if sqs is None else sqs, window)
+    opt = {n: x for n, x in (("window", window), ("key_mask", key_mask), ("out_dtype", out_dtype)) if x is not None}
+    o, lse = call(q, kn, vn, cache_seqlens=sl, causal=causal, return_lse=True, **opt, **kw)
+    _sync(o)
+    if ref is None:
+        ref = reference(q, k, v, seqlens=sl, key_mask=key_mask, causal=causal, window=window)
+    ref = tuple(t.to(o.device) for t in (ref if with_ref is None else with_ref(ref)))
+    assert o.dtype == (out_dtype or q.dtype), f"{what}: the output is {o.dtype}"
+    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype, what)
+    check_lse(o, lse, ref[1], what)
+    return o, lse
+
+
+def both(call, q, kn, vn, kp, vp, table, **kw):
+    """The contiguous and the paged call: both finite, O and LSE bit-equal -> the paged (o, lse)."""
+    kw.setdefault("return_lse", True)
+    oc, lc = call(q, kn, vn, **kw)
+    op, lp = call(q, kp, vp, block_table=table, **kw)
+    _sync(op)
+    assert bool(torch.isfinite(op).all()) and bool(torch.isfinite(oc).all()), "a key or a page the call must never read was read"
+    assert torch.equal(op, oc), f"O differs: max-abs {float((op.double() - oc.double()).abs().max()):.3e}"
+    assert torch.equal(lp, lc), "LSE differs"
+    return op, lp
+
+
+def seq_rows(t, cu, b):
+    """Sequence b's rows of a packed [total, H, D] tensor as the uniform call's [1, H, Sq_b, D] view."""
+    return t[cu[b]:cu[b + 1]].permute(1, 0, 2)[None]
+
+
+def ragged_equals_uniform(uniform_call, o, lse, q, kn, vn, cu, kv_lens, **kw):
+    """The ragged result ``o [total,H,D]``, ``lse [H,total]`` against ``uniform_call`` per sequence with rows, on that sequence's rows,
+    cache and length: the uniform result is finite and O and LSE are bit-equal."""
+    for b in range(len(cu) - 1):
+        if cu[b + 1] == cu[b]:
+            continue
+        ou, lu = uniform_call(seq_rows(q, cu, b), kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32(list(kv_lens[b:b + 1]), q.device),
+                              return_lse=True, **kw)
+        _sync(ou)
+        assert bool(torch.isfinite(ou).all()), f"sequence {b}: non-finite output of the per-sequence call"
+        got = seq_rows(o, cu, b)
+        assert torch.equal(got, ou), f"sequence {b}: O differs, max-abs {float((got.double() - ou.double()).abs().max()):.3e}"
+        assert torch.equal(lse[None, :, cu[b]:cu[b + 1]], lu), f"sequence {b}: LSE differs from the per-sequence call"
+
+
+def check_against_cache(cache, q, o, lse, Smax, what="", **ref_kw):
+    """A result over a ``PagedKVCache`` (after a replay, say) against fp64 on the cache's sequences gathered as they are now."""
+    kc, vc = contiguous_of(cache, Smax)
+    ref = reference(q, kc, vc, seqlens=cache.cache_seqlens, **ref_kw)
+    check_out(o, ref[0], ref[2], float(vc.abs().max()), q.dtype, what)
+    check_lse(o, lse, ref[1], what)
+
+
+# --- FP8 (e4m3fn) caches: bytes, made on the CPU and moved as bytes ---------------------------------------------------------------------
+
+FP8 = torch.float8_e4m3fn
+NANB = 0x7f                       # a NaN byte
+
+
+def b8(x):
+    return x.view(torch.uint8)
+
+
+def quant(x, d):
+    """``ops.quantize_kv`` on the CPU -> the FP8 tensor on x's device."""
+    from photonic_flash_attention_amd import ops
+    return ops.quantize_kv(x.detach().cpu().float(), d.cpu()).to(x.device)
+
+
+def dequant(x8, d, dtype):
+    from photonic_flash_attention_amd import ops
+    return ops.dequantize_kv(x8.cpu(), d.cpu(), dtype).to(x8.device)
+
+
+def to16(x8, dtype):
+    """``x8.to(dtype)`` through the CPU, strides kept: every e4m3 value is a value of dtype, a NaN byte a NaN."""
+    out = torch.empty_strided(x8.shape, x8.stride(), dtype=dtype, device=x8.device)
+    out.copy_(x8.cpu().float().to(dtype))
+    return out
+
+
+def poisoned(x8, lens):
+    """A copy with NaN bytes at and past each sequence's length: ``guard`` for an FP8 cache."""
+    y = b8(x8).clone()
+    for b, n in enumerate(lens):
+        y[b, :, n:] = NANB
+    return y.view(FP8)
+
+
+def scatter_fp8(k8, v8, page, seed, lens, layout="phsd"):
+    """``scatter`` of FP8 caches (through fp16 carriers of the bytes): pools in a random page order whose unnamed pages are NaN bytes,
+    page 0 among them, and the table entries behind each length name page 0."""
+    kp, vp, table = scatter(b8(k8).to(torch.float16), b8(v8).to(torch.float16), page, seed, layout)
+    spare = next(p for p in range(kp.shape[0]) if p not in set(table.flatten().tolist()))
+    if bool((table == 0).any()):                                                # move page 0's keys to a spare page: page 0 becomes NaN
+        for pool in (kp, vp):
+            pool[spare] = pool[0]
+            pool[0] = NAN
+        table[table == 0] = spare
+    for b, n in enumerate(lens):
+        table[b, -(-n // page):] = 0
+    out = []
+    for pool in (kp, vp):
+        raw = torch.empty_strided(pool.shape, pool.stride(), dtype=torch.uint8, device=pool.device)
+        raw.copy_(torch.nan_to_num(pool, nan=float(NANB)))
+        out.append(raw.view(FP8))
+    assert bool((b8(out[0])[0] == NANB).all())
+    return out[0], out[1], table
 
 
 # --- the shared-prefix step (tests/test_hip_attn_merge.py, tests/test_hip_prefill_split.py) -----------------------------------------

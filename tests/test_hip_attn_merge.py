@@ -17,7 +17,8 @@ import ctypes as C
 import pytest
 import torch
 
-from kvcache_testlib import INF, NAN, PREFIX_PAGE, both_prefix_caches, check_step, device, merge_ref64, prefix_problem, reference
+from capi_testlib import decode_args
+from kvcache_testlib import INF, NAN, PREFIX_PAGE, both_prefix_caches, capture, check_step, device, merge_ref64, prefix_problem, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -183,10 +184,7 @@ def test_the_prefix_pass_changes_kernel_past_64_rows(pass_spy, Bc, Sq, prefix_pa
     inner = [c for c in pass_spy if c[3] is None]                                       # the two passes, in the order they are enqueued
     assert inner == [(prefix_pass, (1, 8, rows, 64), False, None), ("fa3_decode", (Bc, 8, Sq, 64), True, None)], pass_spy
     # and the kernels behind those two calls, on an equivalent argument block
-    a = _capi.make_decode_args(q=0x1000, k_cache=0x100000, v_cache=0x200000, o=0x300000, B=1, H=8, Hkv=2, Sq=rows, Smax=128, D=64,
-                               q_stride_h=64, q_stride_s=512, k_stride_h=128 * 64, k_stride_s=64, v_stride_h=128 * 64, v_stride_s=64,
-                               o_stride_h=64, o_stride_s=512, dtype_in=0, dtype_out=2, causal=0, softmax_scale=0.125,
-                               workspace=0x400000, workspace_bytes=1 << 30)
+    a = decode_args(dict(B=1, D=64, dtype_out=2, causal=0), Sq=rows, Smax=128)
     if prefix_pass == "fa3_decode":
         assert _capi.describe_decode(a)[0].startswith("fa3_decode")
     else:
@@ -257,15 +255,7 @@ def test_shared_prefix_step_replays_in_a_graph():
         return ops.fa3_decode(q, k, v, cache_seqlens=lens, block_table=table, k_new=kn, v_new=vn, shared_prefix=128, out=out,
                               return_lse=True)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        step(q_s, kn_s, vn_s, kp, vp, lens_s, table_s, o_s)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        o_g, lse_g = step(q_s, kn_s, vn_s, kp, vp, lens_s, table_s, o_s)
+    graph, (o_g, lse_g) = capture(lambda: step(q_s, kn_s, vn_s, kp, vp, lens_s, table_s, o_s))
     assert o_g is o_s
 
     for n, lens in enumerate(([129, 200, 257, 320], [192, 130, 300, 193], [320, 129, 129, 256])):

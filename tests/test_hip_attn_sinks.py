@@ -28,7 +28,10 @@ import math
 import pytest
 import torch
 
-from kvcache_testlib import EPS, INF, NAN, capture, check_lse, check_out, device, i32, reference, scatter
+from capi_testlib import decode_args
+from kvcache_testlib import (EPS, INF, capture, check_lse, check_out, device, guard, i32, ragged_equals_uniform, reference, run_and_check,
+                             scatter)
+from photonic_flash_attention_amd import ops
 
 pytestmark = pytest.mark.gpu
 
@@ -184,35 +187,6 @@ CASES = all_cases
 
 # --- on the device -----------------------------------------------------------------------------------------------------------------
 
-def _guarded(c, sqs=None):
-    """The case's caches on the device with NaN wherever the kernels promise not to read: at and past len_b, and under a window
-    below floor64(max(0, len_b - Sq_b - W + 1))."""
-    kn, vn = c["k"].to(device()).clone(), c["v"].to(device()).clone()
-    W = c["window"]
-    Sq = c["q"].shape[2] if c["q"].dim() == 4 else None
-    for b, n in enumerate(c["lens"]):
-        sq = Sq if sqs is None else sqs[b]
-        lo = max(0, n - sq - W + 1) // 64 * 64 if W is not None else 0
-        for t in (kn, vn):
-            t[b, :, n:] = NAN
-            t[b, :, :lo] = NAN
-    return kn, vn
-
-
-def _check(c, o, lse, what, o_plain=None):
-    """O and LSE against the case's reference with sinks; rows without keys exactly zero with LSE = sink; head 0 (sink -inf) with the
-    bits of the sink-less call ``o_plain``."""
-    dev = device()
-    ro, rlse, rpn = (t.to(dev) for t in with_sink(c["ref"], c["sinks"]))
-    check_out(o, ro, rpn, c["vmax"], c["dtype"], what)
-    check_lse(o, lse, rlse, what)
-    dead = torch.isneginf(c["ref"][1]).to(dev)
-    assert bool((o[dead[..., None].expand_as(o)] == 0).all()), f"{what}: a row with no visible key is not exactly zero"
-    assert bool((lse.double() - rlse)[dead & torch.isfinite(rlse)].abs().le(2e-3).all()), f"{what}: LSE of a row without keys is not its sink"
-    if o_plain is not None:
-        assert torch.equal(o[:, 0], o_plain[:, 0]), f"{what}: the head with a sink of -inf does not have the sink-less call's bits"
-
-
 def _matter(c, out32=False):
     return assert_sinks_matter(c["ref"], c["sinks"], c["dtype"], c["vmax"], out32)
 
@@ -220,78 +194,53 @@ def _matter(c, out32=False):
 def _nsplit_decode(q, k, Smax, window=None, sinks=True):
     from photonic_flash_attention_amd import _capi
     B, H, Sq, D = q.shape
-    a = _capi.make_decode_args(q=0x1000, k_cache=0x1000000, v_cache=0x2000000, o=0x800000, B=B, H=H, Hkv=k.shape[1], Sq=Sq, Smax=Smax, D=D,
-                               q_stride_b=Sq * H * D, q_stride_h=D, q_stride_s=H * D, k_stride_b=Smax * k.shape[1] * D, k_stride_h=D,
-                               k_stride_s=k.shape[1] * D, v_stride_b=Smax * k.shape[1] * D, v_stride_h=D, v_stride_s=k.shape[1] * D,
-                               o_stride_b=Sq * H * D, o_stride_h=D, o_stride_s=H * D, dtype_in=0 if q.dtype == torch.bfloat16 else 1,
-                               dtype_out=0 if q.dtype == torch.bfloat16 else 1, causal=1, softmax_scale=D ** -0.5, workspace=0x4000000,
-                               workspace_bytes=1 << 40)
+    dt = 0 if q.dtype == torch.bfloat16 else 1
+    a = decode_args(dict(B=B, H=H, Hkv=k.shape[1], D=D, dtype_in=dt, dtype_out=dt), Sq=Sq, Smax=Smax)
     ext = None if window is None else _capi.make_cache_ext(window=window)
     name, _, ns = _capi.describe_decode_sink(a, ext, _capi.make_sinks(sinks=0x9000) if sinks else None)
     assert ("_sink" in name) == sinks
     return ns
 
 
-def _decode(c, paged=False, out_dtype=None, sinks="case", **kw):
-    from photonic_flash_attention_amd import ops
-    dev = device()
-    q = c["q"].to(dev)
-    kn, vn = _guarded(c)
-    s = c["sinks"].to(dev) if isinstance(sinks, str) else sinks
-    km = None if c["km"] is None else c["km"].to(dev)
-    if paged:
-        kn, vn, table = scatter(kn, vn, 64, seed=3)
-        kw["block_table"] = table
-    o, lse = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(c["lens"]), key_mask=km, window=c["window"], sinks=s, return_lse=True,
-                            out_dtype=out_dtype, **kw)
-    torch.cuda.synchronize()
-    return o, lse
-
-
-def _prefill(c, paged=False, out_dtype=None, sinks="case", **kw):
-    from photonic_flash_attention_amd import ops
-    dev = device()
-    kn, vn = _guarded(c)
-    s = c["sinks"].to(dev) if isinstance(sinks, str) else sinks
-    if paged:
-        kn, vn, table = scatter(kn, vn, 64, seed=4)
-        kw["block_table"] = table
-    o, lse = ops.fa3_prefill_cache(c["q"].to(dev), kn, vn, cache_seqlens=i32(c["lens"]), causal=c["causal"], window=c["window"], sinks=s,
-                                   return_lse=True, out_dtype=out_dtype, **kw)
-    torch.cuda.synchronize()
-    return o, lse
-
-
-def _ragged(c, sinks="case", paged=False):
-    """-> (o [1,H,total,D], lse [1,H,total]) in the layout of the packed reference."""
-    from photonic_flash_attention_amd import ops
-    dev = device()
-    kn, vn = _guarded(c, RAGGED_Q)
-    s = c["sinks"].to(dev) if isinstance(sinks, str) else sinks
-    kw = {}
-    if paged:
-        kn, vn, kw["block_table"] = scatter(kn, vn, 64, seed=5)
+def _varlen(q, kn, vn, **kw):
+    """``ops.fa3_prefill_varlen`` of ``RAGGED_Q`` rows -> (o [1,H,total,D], lse [1,H,total]) in the layout of the packed reference."""
     cu = i32([0] + list(torch.tensor(RAGGED_Q).cumsum(0)))
-    o, lse = ops.fa3_prefill_varlen(c["q"].to(dev), kn, vn, cu_seqlens_q=cu, max_seqlen_q=max(RAGGED_Q), cache_seqlens=i32(c["lens"]),
-                                    window=c["window"], sinks=s, return_lse=True, **kw)
-    torch.cuda.synchronize()
+    o, lse = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=cu, max_seqlen_q=max(RAGGED_Q), **kw)
     return o.permute(1, 0, 2)[None], lse[None]
+
+
+def _run(fn, c, what, sinks="case", paged=None, o_plain=None, **kw):
+    """``fn`` on the case's caches, guarded (``run_and_check``), against the case's reference with ``sinks`` ("case": the case's own; None:
+    the sink-less call) -> (o, lse).  paged: the seed of a scatter over pages of 64 keys.  Then the mode's own assertions: rows without
+    keys exactly zero with LSE = sink; head 0 (sink -inf) with the bits of the sink-less call ``o_plain``."""
+    dev = device()
+    s = c["sinks"].to(dev) if isinstance(sinks, str) else sinks
+
+    def on_pages(q, kn, vn, **kw2):
+        kp, vp, table = scatter(kn, vn, 64, seed=paged)
+        return fn(q, kp, vp, block_table=table, **kw2)
+
+    km = c.get("km")
+    o, lse = run_and_check(fn if paged is None else on_pages, c["q"].to(dev), c["k"].to(dev), c["v"].to(dev), c["lens"],
+                           causal=c.get("causal", True), window=c["window"], key_mask=None if km is None else km.to(dev), ref=c["ref"],
+                           with_ref=None if s is None else (lambda ref: with_sink(ref, s)), what=what, sinks=s, **kw)
+    if s is not None:
+        rlse = with_sink(c["ref"], s)[1].to(dev)
+        dead = torch.isneginf(c["ref"][1]).to(dev)
+        assert bool((o[dead[..., None].expand_as(o)] == 0).all()), f"{what}: a row with no visible key is not exactly zero"
+        assert bool((lse.double() - rlse)[dead & torch.isfinite(rlse)].abs().le(2e-3).all()), f"{what}: LSE of a row without keys is not its sink"
+    if o_plain is not None:
+        assert torch.equal(o[:, 0], o_plain[:, 0]), f"{what}: the head with a sink of -inf does not have the sink-less call's bits"
+    return o, lse
 
 
 def _ragged_equals_uniform(c, o, lse):
     """The ragged result against per-sequence uniform calls with the same sinks: bit for bit."""
-    from photonic_flash_attention_amd import ops
     dev = device()
-    kn, vn = _guarded(c, RAGGED_Q)
-    at = 0
-    for b, n in enumerate(RAGGED_Q):
-        if n:
-            qb = c["q"][at:at + n].to(dev).permute(1, 0, 2)[None]
-            ob, lb = ops.fa3_prefill_cache(qb, kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32(c["lens"][b:b + 1]), window=c["window"],
-                                           sinks=c["sinks"].to(dev), return_lse=True)
-            torch.cuda.synchronize()
-            assert torch.equal(o[:, :, at:at + n], ob) and torch.equal(lse[:, :, at:at + n], lb), f"sequence {b}"
-        at += n
+    kn, vn = guard(c["k"].to(dev), c["v"].to(dev), c["lens"], RAGGED_Q, c["window"])
+    cu = [0] + torch.tensor(RAGGED_Q).cumsum(0).tolist()
+    ragged_equals_uniform(ops.fa3_prefill_cache, o[0].permute(1, 0, 2), lse[0], c["q"].to(dev), kn, vn, cu, c["lens"], window=c["window"],
+                          sinks=c["sinks"].to(dev))
 
 
 # --- 1. decode -----------------------------------------------------------------------------------------------------------------------
@@ -303,11 +252,9 @@ def test_decode_with_sinks_against_fp64(dtype, D):
         _matter(c)
         ns = _nsplit_decode(c["q"], c["k"], Smax)
         assert ns == _nsplit_decode(c["q"], c["k"], Smax, sinks=False) and (ns > 1) == (Smax == 1024)
-        o_plain, _ = _decode(c, sinks=None)
-        o, lse = _decode(c)
-        _check(c, o, lse, f"decode Sq {Sq} Smax {Smax}", o_plain)
-        op, lsep = _decode(c, paged=True)
-        _check(c, op, lsep, f"decode paged Sq {Sq} Smax {Smax}", o_plain)
+        o_plain, _ = _run(ops.fa3_decode, c, "decode, no sinks", sinks=None)
+        o, lse = _run(ops.fa3_decode, c, f"decode Sq {Sq} Smax {Smax}", o_plain=o_plain)
+        op, lsep = _run(ops.fa3_decode, c, f"decode paged Sq {Sq} Smax {Smax}", paged=3, o_plain=o_plain)
         assert torch.equal(o, op) and torch.equal(lse, lsep)
 
 
@@ -315,12 +262,11 @@ def test_decode_with_sinks_against_fp64(dtype, D):
 def test_decode_with_sinks_key_mask_and_fp32_output(dtype, D):
     c = decode_case(dtype, D, 5, 1024, mask_seed=11)
     _matter(c)
-    _check(c, *_decode(c), "decode key mask")
+    _run(ops.fa3_decode, c, "decode key mask")
     c = decode_case(dtype, D, 5, 1024)
     _matter(c, out32=True)
-    o, lse = _decode(c, out_dtype=torch.float32)
+    o, lse = _run(ops.fa3_decode, c, "decode fp32", out_dtype=torch.float32)
     assert o.dtype == torch.float32
-    _check(c, o, lse, "decode fp32")
 
 
 # --- 2. sinks all -inf: the sink-less call -----------------------------------------------------------------------------------------
@@ -328,13 +274,13 @@ def test_decode_with_sinks_key_mask_and_fp32_output(dtype, D):
 @pytest.mark.parametrize("dtype,D", DT_D[:2], ids=DT_IDS[:2])
 def test_sinks_of_minus_infinity_give_the_sink_less_bits(dtype, D):
     off = torch.full((8,), -INF, device=device())
-    for what, run, c, kw in (("decode one split", _decode, decode_case(dtype, D, 5, 448), {}),
-                             ("decode four splits", _decode, decode_case(dtype, D, 5, 1024), {}),
-                             ("prefill", _prefill, prefill_case(dtype, D, 257), {}),
-                             ("prefill key_splits 3", _prefill, prefill_case(dtype, D, 257), dict(key_splits=3)),
-                             ("ragged", _ragged, ragged_case(dtype, D), {})):
-        o0, lse0 = run(c, sinks=None, **kw)
-        o, lse = run(c, sinks=off, **kw)
+    for what, fn, c, kw in (("decode one split", ops.fa3_decode, decode_case(dtype, D, 5, 448), {}),
+                            ("decode four splits", ops.fa3_decode, decode_case(dtype, D, 5, 1024), {}),
+                            ("prefill", ops.fa3_prefill_cache, prefill_case(dtype, D, 257), {}),
+                            ("prefill key_splits 3", ops.fa3_prefill_cache, prefill_case(dtype, D, 257), dict(key_splits=3)),
+                            ("ragged", _varlen, ragged_case(dtype, D), dict(sqs=RAGGED_Q))):
+        o0, lse0 = _run(fn, c, what, sinks=None, **kw)
+        o, lse = _run(fn, c, what, sinks=off, **kw)
         assert torch.equal(o, o0), what
         check_lse(o, lse, lse0.double(), what)
 
@@ -347,16 +293,14 @@ def test_prefill_with_sinks_against_fp64(dtype, D):
         for causal in (True, False):
             c = prefill_case(dtype, D, Sq, causal)
             _matter(c)
-            o_plain, _ = _prefill(c, sinks=None)
-            o, lse = _prefill(c)
-            _check(c, o, lse, f"prefill Sq {Sq} causal {causal}", o_plain)
-            op, lsep = _prefill(c, paged=True)
+            o_plain, _ = _run(ops.fa3_prefill_cache, c, "prefill, no sinks", sinks=None)
+            o, lse = _run(ops.fa3_prefill_cache, c, f"prefill Sq {Sq} causal {causal}", o_plain=o_plain)
+            op, lsep = _run(ops.fa3_prefill_cache, c, "prefill paged", paged=4)
             assert torch.equal(o, op) and torch.equal(lse, lsep)
         c = prefill_case(dtype, D, Sq)
         _matter(c, out32=True)
-        o, lse = _prefill(c, out_dtype=torch.float32, paged=Sq == 70)
+        o, lse = _run(ops.fa3_prefill_cache, c, f"prefill fp32 Sq {Sq}", out_dtype=torch.float32, paged=4 if Sq == 70 else None)
         assert o.dtype == torch.float32
-        _check(c, o, lse, f"prefill fp32 Sq {Sq}")
 
 
 # --- 4. ragged -----------------------------------------------------------------------------------------------------------------------
@@ -365,10 +309,9 @@ def test_prefill_with_sinks_against_fp64(dtype, D):
 def test_ragged_prefill_with_sinks(dtype, D):
     c = ragged_case(dtype, D)
     _matter(c)
-    o, lse = _ragged(c)
-    _check(c, o, lse, "ragged")
+    o, lse = _run(_varlen, c, "ragged", sqs=RAGGED_Q)
     _ragged_equals_uniform(c, o, lse)
-    op, lsep = _ragged(c, paged=True)
+    op, lsep = _run(_varlen, c, "ragged paged", sqs=RAGGED_Q, paged=5)
     assert torch.equal(o, op) and torch.equal(lse, lsep)
 
 
@@ -381,25 +324,22 @@ def test_window_and_sinks_decode():
         ns = _nsplit_decode(c["q"], c["k"], 1024, window=W)
         # the plan is the sink-less call's: the span of a 128-key window is below two splits' worth of keys, that of 640 keys is not
         assert ns == _nsplit_decode(c["q"], c["k"], 1024, window=W, sinks=False) and (ns > 1) == (W == 640)
-        o_plain, _ = _decode(c, sinks=None)
-        o, lse = _decode(c)
-        _check(c, o, lse, f"decode W {W}", o_plain)
-        op, lsep = _decode(c, paged=True)
+        o_plain, _ = _run(ops.fa3_decode, c, "decode, no sinks", sinks=None)
+        o, lse = _run(ops.fa3_decode, c, f"decode W {W}", o_plain=o_plain)
+        op, lsep = _run(ops.fa3_decode, c, f"decode paged W {W}", paged=3)
         assert torch.equal(o, op) and torch.equal(lse, lsep)
 
 
 def test_window_and_sinks_prefill_and_ragged():
     c = window_case("prefill")
     _matter(c)
-    o_plain, _ = _prefill(c, sinks=None)
-    o, lse = _prefill(c)
-    _check(c, o, lse, "prefill W 128", o_plain)
-    op, lsep = _prefill(c, paged=True)
+    o_plain, _ = _run(ops.fa3_prefill_cache, c, "prefill, no sinks", sinks=None)
+    o, lse = _run(ops.fa3_prefill_cache, c, "prefill W 128", o_plain=o_plain)
+    op, lsep = _run(ops.fa3_prefill_cache, c, "prefill paged W 128", paged=4)
     assert torch.equal(o, op) and torch.equal(lse, lsep)
     c = ragged_case(torch.bfloat16, 64, window=128, H=16, Smax=1024, lens=RAGGED_WIN_LENS)
     _matter(c)
-    o, lse = _ragged(c)
-    _check(c, o, lse, "ragged W 128")
+    o, lse = _run(_varlen, c, "ragged W 128", sqs=RAGGED_Q)
     _ragged_equals_uniform(c, o, lse)
 
 
@@ -409,39 +349,29 @@ def test_window_and_sinks_prefill_and_ragged():
 def test_key_splits_with_sinks(dtype, D):
     c = split_case(dtype, D)
     _matter(c)
-    o_plain, _ = _prefill(c, sinks=None)
-    o1, lse1 = _prefill(c)
-    _check(c, o1, lse1, "unsplit", o_plain)
+    o_plain, _ = _run(ops.fa3_prefill_cache, c, "unsplit, no sinks", sinks=None)
+    o1, lse1 = _run(ops.fa3_prefill_cache, c, "unsplit", o_plain=o_plain)
     for ks in (1, 2, 3, 8, "auto"):
-        o, lse = _prefill(c, key_splits=ks)
-        _check(c, o, lse, f"key_splits {ks}")
+        o, lse = _run(ops.fa3_prefill_cache, c, f"key_splits {ks}", key_splits=ks)
         if ks == 1:
             assert torch.equal(o, o1) and torch.equal(lse, lse1)
-    op, lsep = _prefill(c, key_splits=3, paged=True)
-    _check(c, op, lsep, "key_splits 3 paged")
+    _run(ops.fa3_prefill_cache, c, "key_splits 3 paged", key_splits=3, paged=4)
 
 
 # --- 7. shared prefix --------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype,D", DT_D, ids=DT_IDS)
 def test_shared_prefix_with_sinks(dtype, D):
-    from photonic_flash_attention_amd import ops
-    dev = device()
     for Sq, fn, kws in ((1, ops.fa3_decode, ({},)), (70, ops.fa3_prefill_cache, ({}, dict(prefix_key_splits=2)))):
         c = prefix_case(dtype, D, Sq)
         _matter(c)
-        kn, vn = _guarded(c)
         for kw in kws:
-            o, lse = fn(c["q"].to(dev), kn, vn, cache_seqlens=i32(c["lens"]), shared_prefix=c["P"], sinks=c["sinks"].to(dev), return_lse=True,
-                        **kw)
-            torch.cuda.synchronize()
-            _check(c, o, lse, f"shared_prefix Sq {Sq} {kw}")
+            _run(fn, c, f"shared_prefix Sq {Sq} {kw}", shared_prefix=c["P"], **kw)
 
 
 # --- 8. graph replay -----------------------------------------------------------------------------------------------------------------
 
 def test_captured_step_replays_while_sinks_lengths_and_rows_change():
-    from photonic_flash_attention_amd import ops
     dev = device()
     B, H, Hkv, Sq, Smax, D, dtype = 3, 8, 2, 2, 1024, 64, torch.bfloat16
     q0, k, v = (t.to(dev) for t in problem(B, H, Hkv, Sq, Smax, D, dtype, seed=8))
@@ -473,7 +403,6 @@ def test_captured_step_replays_while_sinks_lengths_and_rows_change():
 # --- 9. refusals on device tensors: nothing is enqueued --------------------------------------------------------------------------------
 
 def test_refusals_enqueue_nothing():
-    from photonic_flash_attention_amd import ops
     dev = device()
     q, k, v = (t.to(dev) for t in problem(2, 8, 2, 2, 128, 64, torch.bfloat16, seed=10))
     lens = i32([100, 50])

@@ -21,7 +21,8 @@ import functools
 import pytest
 import torch
 
-from kvcache_testlib import NAN, capture, check_lse, check_out, device, i32, reference
+from kvcache_testlib import (NAN, both, capture, check_lse, check_out, device, guard, i32, ragged_equals_uniform, reference, run_and_check,
+                             scatter, seq_rows, window_lo)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,40 +50,17 @@ def _q4(B, H, Sq, D, dtype, seed=0):
     return _q((B, Sq, H, D), dtype, seed).permute(0, 2, 1, 3)
 
 
-def _floor64_lo(length, sq, window):
-    return (max(0, length - sq - window + 1) // 64 * 64) if window is not None else 0
-
-
-def _guard(k, v, lens, sqs, window):
-    """Copies of the caches with NaN wherever the kernels promise not to read: at and past len_b, and below floor64(lo_b)."""
-    kn, vn = k.clone(), v.clone()
-    for b, (n, sq) in enumerate(zip(lens, sqs)):
-        lo = _floor64_lo(n, sq, window)
-        for t in (kn, vn):
-            t[b, :, n:] = NAN
-            t[b, :, :lo] = NAN
-    return kn, vn
-
-
 LENS2 = [1000, 517]
 WINDOWS_DECODE = [1, 63, 64, 65, 200, 512, 2000]
 
 
 # --- 1. decode ---------------------------------------------------------------------------------------------------------------------
 
-def _decode_and_check(dtype, D, H, Hkv, Sq, W, lens, Smax=1024, key_mask=None, out_dtype=None):
+def _decode_and_check(dtype, D, H, Hkv, Sq, W, lens, Smax=1024, **kw):
     from photonic_flash_attention_amd import ops
     B = len(lens)
     k, v = _kv(B, Hkv, Smax, D, dtype)
-    q = _q4(B, H, Sq, D, dtype)
-    kn, vn = _guard(k, v, lens, [Sq] * B, W)
-    o, lse = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(lens), key_mask=key_mask, window=W, return_lse=True, out_dtype=out_dtype)
-    torch.cuda.synchronize()
-    ref, rlse, pn = reference(q, k, v, seqlens=i32(lens), key_mask=key_mask, window=W)
-    what = f"decode Sq {Sq} W {W}"
-    check_out(o, ref, pn, float(v.abs().max()), dtype, what)
-    check_lse(o, lse, rlse, what)
-    return o, lse
+    return run_and_check(ops.fa3_decode, _q4(B, H, Sq, D, dtype), k, v, lens, window=W, what=f"decode Sq {Sq} W {W}", **kw)
 
 
 @pytest.mark.parametrize("dtype,D", DT_D, ids=DT_IDS)
@@ -120,19 +98,11 @@ def test_decode_window_combined_with_a_left_padding_key_mask():
 WINDOWS_PREFILL = [1, 64, 100, 256, 257, 1000]
 
 
-def _prefill_and_check(dtype, D, W, lens, Sq=300, Smax=768, out_dtype=None):
+def _prefill_and_check(dtype, D, W, lens, Sq=300, Smax=768, **kw):
     from photonic_flash_attention_amd import ops
     B, H, Hkv = len(lens), 4, 2
     k, v = _kv(B, Hkv, Smax, D, dtype, seed=1)
-    q = _q4(B, H, Sq, D, dtype, seed=1)
-    kn, vn = _guard(k, v, lens, [Sq] * B, W)
-    o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), window=W, return_lse=True, out_dtype=out_dtype)
-    torch.cuda.synchronize()
-    ref, rlse, pn = reference(q, k, v, seqlens=i32(lens), window=W)
-    what = f"prefill lens {lens} W {W}"
-    check_out(o, ref, pn, float(v.abs().max()), dtype, what)
-    check_lse(o, lse, rlse, what)
-    return o, lse
+    return run_and_check(ops.fa3_prefill_cache, _q4(B, H, Sq, D, dtype, seed=1), k, v, lens, window=W, what=f"prefill lens {lens} W {W}", **kw)
 
 
 @pytest.mark.parametrize("dtype,D", DT_D, ids=DT_IDS)
@@ -163,11 +133,11 @@ CU = [0, 300, 301, 301, 318, 382]
 TOTAL, MAXQ, RB, RH, RHKV, RSMAX = 384, 300, 5, 4, 2, 1024
 
 
-def _ragged(dtype, D, W, out_dtype=None, guard=True):
+def _ragged(dtype, D, W, out_dtype=None):
     from photonic_flash_attention_amd import ops
     k, v = _kv(RB, RHKV, RSMAX, D, dtype, seed=2)
     q = _q((TOTAL, RH, D), dtype, seed=2)
-    kn, vn = _guard(k, v, KV_LENS, Q_LENS, W) if guard else (k, v)
+    kn, vn = guard(k, v, KV_LENS, Q_LENS, W)
     o, lse = ops.fa3_prefill_varlen(q, kn, vn, cu_seqlens_q=i32(CU), max_seqlen_q=MAXQ, cache_seqlens=i32(KV_LENS), window=W,
                                     return_lse=True, out_dtype=out_dtype)
     torch.cuda.synchronize()
@@ -180,18 +150,13 @@ def test_ragged_window_against_fp64_and_per_sequence_calls(dtype, D, W):
     from photonic_flash_attention_amd import ops
     q, k, v, kn, vn, o, lse = _ragged(dtype, D, W)
     for b in range(RB):
-        n = Q_LENS[b]
-        if n == 0:
+        if Q_LENS[b] == 0:
             continue
-        qb = q[CU[b]:CU[b + 1]].permute(1, 0, 2)[None]
-        got, gl = o[CU[b]:CU[b + 1]].permute(1, 0, 2)[None], lse[None, :, CU[b]:CU[b + 1]]
-        ref, rlse, pn = reference(qb, k[b:b + 1], v[b:b + 1], seqlens=i32(KV_LENS[b:b + 1]), window=W)
+        got, gl = seq_rows(o, CU, b), lse[None, :, CU[b]:CU[b + 1]]
+        ref, rlse, pn = reference(seq_rows(q, CU, b), k[b:b + 1], v[b:b + 1], seqlens=i32(KV_LENS[b:b + 1]), window=W)
         check_out(got, ref, pn, float(v.abs().max()), dtype, f"ragged sequence {b} W {W}")
         check_lse(got, gl, rlse, f"ragged sequence {b} W {W}")
-        ou, lu = ops.fa3_prefill_cache(qb, kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32(KV_LENS[b:b + 1]), window=W, return_lse=True)
-        torch.cuda.synchronize()
-        assert torch.equal(got, ou), f"sequence {b}: O differs from the per-sequence call"
-        assert torch.equal(gl, lu), f"sequence {b}: LSE differs from the per-sequence call"
+    ragged_equals_uniform(ops.fa3_prefill_cache, o, lse, q, kn, vn, CU, KV_LENS, window=W)
 
 
 # --- 4. a window that hides nothing changes no bit --------------------------------------------------------------------------------------
@@ -202,7 +167,7 @@ def test_a_window_that_hides_nothing_changes_no_bit():
         for Sq, H, Hkv in ((1, 8, 2), (5, 8, 2), (5, 64, 1)):
             k, v = _kv(2, Hkv, 1024, D, dtype)
             q = _q4(2, H, Sq, D, dtype)
-            kn, vn = _guard(k, v, LENS2, [Sq] * 2, None)
+            kn, vn = guard(k, v, LENS2)
             a = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(LENS2), return_lse=True)
             b = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(LENS2), return_lse=True, window=1024 + Sq)
             torch.cuda.synchronize()
@@ -210,7 +175,7 @@ def test_a_window_that_hides_nothing_changes_no_bit():
         k, v = _kv(2, 2, 768, D, dtype, seed=1)
         q = _q4(2, 4, 300, D, dtype, seed=1)
         for lens in ([700, 300], [120, 700]):
-            kn, vn = _guard(k, v, lens, [300] * 2, None)
+            kn, vn = guard(k, v, lens)
             for od in (None, torch.float32):
                 a = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), return_lse=True, out_dtype=od)
                 b = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), return_lse=True, out_dtype=od, window=768 + 300)
@@ -224,26 +189,8 @@ def test_a_window_that_hides_nothing_changes_no_bit():
 # --- 5. paged == contiguous -----------------------------------------------------------------------------------------------------------
 
 def _scatter(kn, vn, page, seed, lens, sqs, window):
-    """Scatter [B,Hkv,Smax,D] caches over pools in a random page order that never uses page 0.  -> (k_pool, v_pool, table), pools as
-    [num_pages,Hkv,page,D] views of flash-attn style buffers.  Pages no entry names hold NaN; the entries below lo_b // page are -1."""
-    B, Hkv, Smax, D = kn.shape
-    pages = Smax // page
-    NP = B * pages + 6
-    dev = kn.device
-    perm = torch.randperm(NP - 1, generator=torch.Generator().manual_seed(seed))[:B * pages] + 1
-    table = perm.to(torch.int32).reshape(B, pages).to(dev)
-    pools = []
-    for src in (kn, vn):
-        pool = torch.full((NP, page, Hkv, D), NAN, dtype=kn.dtype, device=dev).transpose(1, 2)
-        pool[perm.to(dev)] = src.reshape(B, Hkv, pages, page, D).permute(0, 2, 1, 3, 4).reshape(B * pages, Hkv, page, D)
-        pools.append(pool)
-    for b, (n, sq) in enumerate(zip(lens, sqs)):
-        first = max(0, n - sq - window + 1) // page
-        dead = table[b, :first].long()
-        table[b, :first] = -1
-        for pool in pools:
-            pool[dead] = NAN
-    return pools[0], pools[1], table
+    """Pools whose page 0 no table names (a clamped -1 lands there), with -1 in the entries below lo_b // page and NaN in their pages."""
+    return scatter(kn, vn, page, seed, first=1, lo=window_lo(lens, sqs, window))
 
 
 @pytest.mark.parametrize("page", [64, 128])
@@ -255,24 +202,14 @@ def test_paged_equals_contiguous_with_a_window(page):
             for Sq in (1, 5):
                 k, v = _kv(2, 2, 1024, D, dtype)
                 q = _q4(2, 8, Sq, D, dtype)
-                kn, vn = _guard(k, v, LENS2, [Sq] * 2, W)
-                kp, vp, table = _scatter(kn, vn, page, page + D + Sq, LENS2, [Sq] * 2, W)
-                a = ops.fa3_decode(q, kn, vn, cache_seqlens=i32(LENS2), return_lse=True, window=W)
-                b = ops.fa3_decode(q, kp, vp, cache_seqlens=i32(LENS2), return_lse=True, window=W, block_table=table)
-                torch.cuda.synchronize()
-                assert bool(torch.isfinite(b[0]).all()), "a released table entry or a foreign page was read"
-                assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), ("decode", D, W, Sq)
+                kn, vn = guard(k, v, LENS2, Sq, W)
+                both(ops.fa3_decode, q, kn, vn, *_scatter(kn, vn, page, page + D + Sq, LENS2, Sq, W), cache_seqlens=i32(LENS2), window=W)
             # prefill
             k, v = _kv(2, 2, 768, D, dtype, seed=1)
             q = _q4(2, 4, 300, D, dtype, seed=1)
             lens = [700, 300]
-            kn, vn = _guard(k, v, lens, [300] * 2, W)
-            kp, vp, table = _scatter(kn, vn, page, page + D, lens, [300] * 2, W)
-            a = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(lens), return_lse=True, window=W)
-            b = ops.fa3_prefill_cache(q, kp, vp, cache_seqlens=i32(lens), return_lse=True, window=W, block_table=table)
-            torch.cuda.synchronize()
-            assert bool(torch.isfinite(b[0]).all())
-            assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), ("prefill", D, W)
+            kn, vn = guard(k, v, lens, 300, W)
+            both(ops.fa3_prefill_cache, q, kn, vn, *_scatter(kn, vn, page, page + D, lens, 300, W), cache_seqlens=i32(lens), window=W)
             # ragged
             q, _, _, kn, vn, o, lse = _ragged(dtype, D, W)
             kp, vp, table = _scatter(kn, vn, page, page + D + 1, KV_LENS, Q_LENS, W)
@@ -450,14 +387,12 @@ def test_graph_replays_of_windowed_decode_and_ragged_prefill():
         assert torch.equal(o, oe) and torch.equal(lse[:, :rows], le[:, :rows]), new_cu
         assert bool((o[rows:] == 7.0).all())
         results.append(o.clone())
-        cl, ql = lens.tolist(), [b - a for a, b in zip(cu.tolist(), cu.tolist()[1:])]
+        cl, cul = lens.tolist(), cu.tolist()
         for b in range(RB):
-            if ql[b] == 0:
+            if cul[b + 1] == cul[b]:
                 continue
-            s0 = int(cu[b])
-            qb = q[s0:s0 + ql[b]].permute(1, 0, 2)[None]
-            ref, rlse, pn = reference(qb, k[b:b + 1], v[b:b + 1], seqlens=i32(cl[b:b + 1]), window=W)
-            got = o[s0:s0 + ql[b]].permute(1, 0, 2)[None]
+            ref, rlse, pn = reference(seq_rows(q, cul, b), k[b:b + 1], v[b:b + 1], seqlens=i32(cl[b:b + 1]), window=W)
+            got = seq_rows(o, cul, b)
             check_out(got, ref, pn, float(v.abs().max()), dtype, f"graph ragged sequence {b}")
-            check_lse(got, lse[None, :, s0:s0 + ql[b]], rlse)
+            check_lse(got, lse[None, :, cul[b]:cul[b + 1]], rlse)
     assert not torch.equal(results[0], results[1])

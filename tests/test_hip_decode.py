@@ -10,7 +10,7 @@ import copy
 import pytest
 import torch
 
-from kvcache_testlib import EPS, check_lse, check_out, device, reference
+from kvcache_testlib import EPS, capture, check_lse, check_out, device, reference, run_and_check
 
 pytestmark = pytest.mark.gpu
 
@@ -31,15 +31,11 @@ def _problem(B, H, Hkv, Sq, Smax, D, dtype, seed, layout="bhsd"):
     return q, k, v
 
 
-def _run_and_check(q, k, v, *, seqlens=None, key_mask=None, causal=True, out_dtype=None):
+def _run_and_check(q, k, v, *, seqlens=None, **kw):
+    """The decode on the clean caches it is given (every key of them is finite) against fp64."""
     from photonic_flash_attention_amd import ops
-    o, lse = ops.fa3_decode(q, k, v, cache_seqlens=seqlens, key_mask=key_mask, causal=causal, out_dtype=out_dtype, return_lse=True)
-    torch.cuda.synchronize()
-    ref, rlse, pn = reference(q, k, v, seqlens=seqlens, key_mask=key_mask, causal=causal)
     what = f"decode Sq {q.shape[2]} Smax {k.shape[2]} D {q.shape[-1]}"
-    check_out(o, ref, pn, float(v.abs().max()), q.dtype, what)
-    check_lse(o, lse, rlse, what)
-    return o, lse
+    return run_and_check(ops.fa3_decode, q, k, v, seqlens, guarded=False, what=what, **kw)
 
 
 @pytest.mark.parametrize("H,Hkv", [(32, 8), (8, 8), (28, 4), (64, 1)])
@@ -129,15 +125,7 @@ def test_graph_capture_replays_with_new_lengths_and_cache():
     q, k, v = _problem(2, 32, 8, 1, 4096, 128, torch.bfloat16, seed=6)
     dev = q.device
     sl = torch.tensor([4096, 1000], dtype=torch.int32, device=dev)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        o, lse = ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True)
+    graph, (o, lse) = capture(lambda: ops.fa3_decode(q, k, v, cache_seqlens=sl, return_lse=True))
     graph.replay()
     torch.cuda.synchronize()
     ref, rlse, pn = reference(q, k, v, seqlens=sl)

@@ -19,7 +19,7 @@ import functools
 import pytest
 import torch
 
-from kvcache_testlib import capture, check_lse, check_out, contiguous_of, device, i32, poison, reference, scatter
+from kvcache_testlib import capture, check_lse, check_out, contiguous_of, device, guard, i32, reference, scatter
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,7 @@ def _problem(H, Hkv, Sq, Smax, lens, D, dtype):
     q = torch.randn(B, Sq, H, D, generator=g, device=device()).to(dtype).permute(0, 2, 1, 3)
     k = torch.randn(B, Hkv, Smax, D, generator=g, device=device()).to(dtype)
     v = torch.randn(B, Hkv, Smax, D, generator=g, device=device()).to(dtype)
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     return dict(q=q, k=k, v=v, kn=kn, vn=vn, lens=i32(list(lens)), vmax=float(v.abs().max()), dtype=dtype, Sq=Sq, Smax=Smax, B=B)
 
 

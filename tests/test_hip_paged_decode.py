@@ -13,21 +13,14 @@ from __future__ import annotations
 import pytest
 import torch
 
-from kvcache_testlib import NAN, check_lse, check_out, contiguous_of, device, gen, problem, reference, scatter
+from kvcache_testlib import both, capture, contiguous_of, device, gen, problem, reference, run_and_check, scatter, share_prefix_pages
 
 pytestmark = pytest.mark.gpu
 
 
-def _both(q, k, v, kp, vp, table, **kw):
-    """The contiguous and the paged call; asserts bitwise equality, returns the paged (o, lse)."""
+def _both(*a, **kw):
     from photonic_flash_attention_amd import ops
-    oc, lc = ops.fa3_decode(q, k, v, return_lse=True, **kw)
-    op, lp = ops.fa3_decode(q, kp, vp, block_table=table, return_lse=True, **kw)
-    torch.cuda.synchronize()
-    assert torch.equal(op, oc), f"O differs: max-abs {float((op.double() - oc.double()).abs().max()):.3e}"
-    assert torch.equal(lp, lc), "LSE differs"
-    assert bool(torch.isfinite(op).all())
-    return op, lp
+    return both(ops.fa3_decode, *a, **kw)
 
 
 @pytest.mark.parametrize("page", [64, 128, 256, 1024])
@@ -101,10 +94,7 @@ def test_two_sequences_sharing_prefix_pages():
     k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
     v[1, :, :5 * page] = v[0, :, :5 * page]
     kp, vp, table = scatter(k, v, page, seed=4)
-    freed = table[1, :5].clone()
-    table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
-    for pool in (kp, vp):
-        pool[freed.long()] = NAN          # the duplicate copies are gone
+    share_prefix_pages(kp, vp, table, 0, 1, 5)       # ... held once: both tables name the same pages, the duplicate copies are gone
     sl = torch.tensor([2048, 5 * page + 70, 900], dtype=torch.int32, device=q.device)
     _both(q, k, v, kp, vp, table, cache_seqlens=sl)
 
@@ -118,13 +108,10 @@ def test_paged_against_the_fp64_reference(dtype, D):
     km = torch.ones(3, 4096, dtype=torch.bool, device=q.device)
     km[0, :200] = False
     km[1, 500:600] = False
-    ref, rlse, pn = reference(q, k, v, seqlens=sl, key_mask=km)
+    ref = reference(q, k, v, seqlens=sl, key_mask=km)
     for out_dtype in (None, torch.float32):
-        o, lse = ops.fa3_decode(q, kp, vp, block_table=table, cache_seqlens=sl, key_mask=km, causal=True, out_dtype=out_dtype,
-                                return_lse=True)
-        torch.cuda.synchronize()
-        check_out(o, ref, pn, float(v.abs().max()), dtype, f"paged decode D {D}")
-        check_lse(o, lse, rlse, f"paged decode D {D}")
+        run_and_check(lambda q, kn, vn, **kw: ops.fa3_decode(q, kp, vp, block_table=table, **kw), q, k, v, sl, key_mask=km,
+                      out_dtype=out_dtype, ref=ref, guarded=False, what=f"paged decode D {D}")
 
 
 def test_table_entries_past_a_sequence_are_never_read():
@@ -187,15 +174,7 @@ def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
     cache.reserve(a, 200)                    # pages a will grow into during the replays
     table_ptr, lens_ptr = cache.block_table.data_ptr(), cache.cache_seqlens.data_ptr()
     q = torch.randn(2, 1, H, D, generator=g, device=dev).to(torch.bfloat16).permute(0, 2, 1, 3)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        cache.decode(q, return_lse=True)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        o, lse = cache.decode(q, return_lse=True)
+    graph, (o, lse) = capture(lambda: cache.decode(q, return_lse=True))
 
     def replay_and_compare():
         graph.replay()

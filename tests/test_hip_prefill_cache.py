@@ -13,23 +13,16 @@ from __future__ import annotations
 import pytest
 import torch
 
-from kvcache_testlib import NAN, check_lse, check_out, contiguous_of, device, gen, i32, poison, problem, reference, scatter
+from kvcache_testlib import (NAN, both, capture, check_against_cache, check_lse, check_out, device, gen, guard, i32, problem, reference,
+                             run_and_check, scatter, share_prefix_pages)
 
 pytestmark = pytest.mark.gpu
 
 
-def _run_and_check(q, k, v, lens, *, causal=True, out_dtype=None, ref=None, **kw):
+def _run_and_check(*a, **kw):
     """The kernel on the NaN-tailed caches against fp64 on the clean ones.  lens: list or None (then nothing is poisoned)."""
     from photonic_flash_attention_amd import ops
-    sl = i32(lens, q.device) if lens is not None else None
-    kn, vn = poison(k, v, lens) if lens is not None else (k, v)
-    o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=sl, causal=causal, out_dtype=out_dtype, return_lse=True, **kw)
-    torch.cuda.synchronize()
-    if ref is None:
-        ref = reference(q, k, v, seqlens=sl, causal=causal)
-    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-    check_lse(o, lse, ref[1])
-    return o, lse
+    return run_and_check(ops.fa3_prefill_cache, *a, **kw)
 
 
 # --- against fp64 --------------------------------------------------------------------------------------------------------------------
@@ -112,7 +105,7 @@ def test_lengths_next_to_tile_and_page_boundaries(page):
     q, k, v = problem(2, 8, 2, Sq, 2048, 128, torch.bfloat16, seed=80 + page)
     for lens in ([63, 65], [64, 127], [page - 1, page + 1], [4 * page - 1, 4 * page + 1], [4 * page, 2047]):
         sl = i32(lens)
-        kn, vn = poison(k, v, lens)
+        kn, vn = guard(k, v, lens)
         kp, vp, table = scatter(kn, vn, page, seed=page)
         for causal in (True, False):
             o, lse = _run_and_check(q, k, v, lens, causal=causal)
@@ -123,16 +116,9 @@ def test_lengths_next_to_tile_and_page_boundaries(page):
 
 # --- paged == contiguous -------------------------------------------------------------------------------------------------------------
 
-def _both(q, kn, vn, kp, vp, table, **kw):
-    """The contiguous and the paged call; asserts bitwise equality and finiteness, returns the paged (o, lse)."""
+def _both(*a, **kw):
     from photonic_flash_attention_amd import ops
-    oc, lc = ops.fa3_prefill_cache(q, kn, vn, return_lse=True, **kw)
-    op, lp = ops.fa3_prefill_cache(q, kp, vp, block_table=table, return_lse=True, **kw)
-    torch.cuda.synchronize()
-    assert bool(torch.isfinite(op).all()) and bool(torch.isfinite(oc).all())
-    assert torch.equal(op, oc), f"O differs: max-abs {float((op.double() - oc.double()).abs().max()):.3e}"
-    assert torch.equal(lp, lc), "LSE differs"
-    return op, lp
+    return both(ops.fa3_prefill_cache, *a, **kw)
 
 
 @pytest.mark.parametrize("page", [64, 128, 256, 1024])
@@ -143,7 +129,7 @@ def test_paged_equals_contiguous(page, D):
         for Sq in (65, 300):
             q, k, v = problem(2, 8, 2, Sq, Smax, D, dtype, seed=page + D + Sq)
             lens = [Sq + 1000, Sq + 17]
-            kn, vn = poison(k, v, lens)
+            kn, vn = guard(k, v, lens)
             kp, vp, table = scatter(kn, vn, page, seed=page + Sq)
             for causal in (True, False):
                 for out_dtype in (None, torch.float32):
@@ -161,7 +147,7 @@ def test_paged_equals_contiguous(page, D):
 def test_pool_layouts(layout):
     q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=9)
     lens = [2048, 1111]
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     kp, vp, table = scatter(kn, vn, 256, seed=3, layout=layout)
     assert kp.is_contiguous() == (layout == "hpsd")
     _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens))
@@ -173,12 +159,9 @@ def test_two_sequences_sharing_prefix_pages():
     k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
     v[1, :, :5 * page] = v[0, :, :5 * page]
     lens = [2048, 5 * page + Sq + 7, 900]            # batch 1: its 207-row suffix attends to the shared pages
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     kp, vp, table = scatter(kn, vn, page, seed=4)
-    freed = table[1, :5].clone()
-    table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
-    for pool in (kp, vp):
-        pool[freed.long()] = NAN                     # the duplicate copies are gone
+    share_prefix_pages(kp, vp, table, 0, 1, 5)       # ... held once: both tables name the same pages, the duplicate copies are gone
     o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens))
     ref = reference(q, k, v, seqlens=i32(lens))
     check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
@@ -226,7 +209,7 @@ def test_outputs_are_bitwise_reproducible():
     from photonic_flash_attention_amd import ops
     q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
     lens = [2048, 1500]
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     kp, vp, table = scatter(kn, vn, 64, seed=7)
     for out_dtype in (None, torch.float32):
         runs = [ops.fa3_prefill_cache(q, kp, vp, block_table=table, cache_seqlens=i32(lens), out_dtype=out_dtype, return_lse=True)
@@ -259,23 +242,12 @@ def test_graph_capture_replays_while_the_cache_grows_and_pages_move():
     cache.reserve(a, 500)                    # pages a will grow into during the replays
     table_ptr, lens_ptr = cache.block_table.data_ptr(), cache.cache_seqlens.data_ptr()
     q = torch.randn(2, Sq, H, D, generator=g, device=dev).to(torch.bfloat16).permute(0, 2, 1, 3)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        cache.prefill(q, return_lse=True)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        o, lse = cache.prefill(q, return_lse=True)
+    graph, (o, lse) = capture(lambda: cache.prefill(q, return_lse=True))
 
     def replay_and_compare():
         graph.replay()
         torch.cuda.synchronize()
-        kc, vc = contiguous_of(cache, max_pages * page)
-        ref = reference(q, kc, vc, seqlens=cache.cache_seqlens)
-        check_out(o, ref[0], ref[2], float(vc.abs().max()), q.dtype)
-        check_lse(o, lse, ref[1])
+        check_against_cache(cache, q, o, lse, max_pages * page)
 
     replay_and_compare()
     assert bool((o[a, :, :Sq - 60] == 0).all())
@@ -300,12 +272,7 @@ def test_prefill_and_decode_both_meet_the_fp64_bound(Sq):
     for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
         q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=90 + Sq + D)
         lens = [Sq + 1000, Sq + 17]
-        sl = i32(lens)
-        kn, vn = poison(k, v, lens)
-        ref = reference(q, k, v, seqlens=sl)
+        ref = reference(q, k, v, seqlens=i32(lens))
         for out_dtype in (None, torch.float32):
             for fn in (ops.fa3_prefill_cache, ops.fa3_decode):
-                o, lse = fn(q, kn, vn, cache_seqlens=sl, causal=True, out_dtype=out_dtype, return_lse=True)
-                torch.cuda.synchronize()
-                check_out(o, ref[0], ref[2], float(v.abs().max()), dtype)
-                check_lse(o, lse, ref[1])
+                run_and_check(fn, q, k, v, lens, out_dtype=out_dtype, ref=ref)

@@ -16,8 +16,8 @@ import functools
 import pytest
 import torch
 
-from kvcache_testlib import (NAN, both_prefix_caches, capture, check_lse, check_out, device, gen, i32, poison, prefix_problem, problem,
-                             reference, scatter)
+from kvcache_testlib import (NAN, both, both_prefix_caches, capture, check_lse, check_out, device, gen, guard, i32, prefix_problem, problem,
+                             reference, run_and_check, scatter, share_prefix_pages)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,18 +30,11 @@ def _case(B, H, Hkv, Sq, Smax, D, dtype, seed, lens, causal):
     return q, k, v, reference(q, k, v, seqlens=sl, causal=causal)
 
 
-def _run_and_check(case, lens, key_splits, *, causal=True, out_dtype=None, **kw):
+def _run_and_check(case, lens, key_splits, **kw):
     """The split call on the NaN-tailed caches against fp64 on the clean ones.  lens: tuple or None (then nothing is poisoned)."""
     from photonic_flash_attention_amd import ops
     q, k, v, ref = case
-    sl = i32(list(lens), q.device) if lens is not None else None
-    kn, vn = poison(k, v, lens) if lens is not None else (k, v)
-    o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=sl, causal=causal, out_dtype=out_dtype, return_lse=True, key_splits=key_splits, **kw)
-    torch.cuda.synchronize()
-    assert o.dtype == (out_dtype or q.dtype)
-    check_out(o, ref[0], ref[2], float(v.abs().max()), q.dtype)
-    check_lse(o, lse, ref[1])
-    return o, lse
+    return run_and_check(ops.fa3_prefill_cache, q, k, v, lens, ref=ref, key_splits=key_splits, **kw)
 
 
 # --- against fp64 --------------------------------------------------------------------------------------------------------------------
@@ -102,7 +95,7 @@ def test_lengths_next_to_tile_and_split_boundaries(page):
         for causal in (True, False):
             case = _case(2, 8, 2, Sq, 2048, 128, torch.bfloat16, 80 + page, lens, causal)
             o, lse = _run_and_check(case, lens, 4, causal=causal)
-            kn, vn = poison(case[1], case[2], lens)
+            kn, vn = guard(case[1], case[2], lens)
             kp, vp, table = scatter(kn, vn, page, seed=page)
             op, lp = ops.fa3_prefill_cache(case[0], kp, vp, block_table=table, cache_seqlens=sl, causal=causal, return_lse=True, key_splits=4)
             torch.cuda.synchronize()
@@ -129,7 +122,7 @@ def test_the_split_rule_is_attn_merge_of_plain_calls_on_the_key_slices(N, lens):
     Sq = 300
     for D, dtype in ((128, torch.bfloat16), (64, torch.float16)):
         q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=N + D)
-        kn, vn = poison(k, v, lens)
+        kn, vn = guard(k, v, lens)
         empty = 0
         for out_dtype in (dtype, torch.float32):
             o, lse = ops.fa3_prefill_cache(q, kn, vn, cache_seqlens=i32(list(lens)), causal=False, out_dtype=out_dtype, return_lse=True,
@@ -158,16 +151,9 @@ def test_the_split_rule_is_attn_merge_of_plain_calls_on_the_key_slices(N, lens):
 
 # --- paged == contiguous -------------------------------------------------------------------------------------------------------------
 
-def _both(q, kn, vn, kp, vp, table, **kw):
-    """The contiguous and the paged split call; asserts bitwise equality and finiteness, returns the paged (o, lse)."""
+def _both(*a, **kw):
     from photonic_flash_attention_amd import ops
-    oc, lc = ops.fa3_prefill_cache(q, kn, vn, return_lse=True, **kw)
-    op, lp = ops.fa3_prefill_cache(q, kp, vp, block_table=table, return_lse=True, **kw)
-    torch.cuda.synchronize()
-    assert bool(torch.isfinite(op).all()) and bool(torch.isfinite(oc).all())
-    assert torch.equal(op, oc), f"O differs: max-abs {float((op.double() - oc.double()).abs().max()):.3e}"
-    assert torch.equal(lp, lc), "LSE differs"
-    return op, lp
+    return both(ops.fa3_prefill_cache, *a, **kw)
 
 
 @pytest.mark.parametrize("page", [64, 128, 256])
@@ -178,7 +164,7 @@ def test_paged_equals_contiguous(page, D):
         for Sq in (65, 300):
             q, k, v = problem(2, 8, 2, Sq, 2048, D, dtype, seed=page + D + Sq)
             lens = [Sq + 1000, Sq + 17]
-            kn, vn = poison(k, v, lens)
+            kn, vn = guard(k, v, lens)
             kp, vp, table = scatter(kn, vn, page, seed=page + Sq)
             for causal, N in ((True, 3), (True, 8), (False, 5)):
                 for out_dtype in (None, torch.float32):
@@ -193,12 +179,9 @@ def test_two_sequences_sharing_prefix_pages():
     k[1, :, :5 * page] = k[0, :, :5 * page]          # batches 0 and 1 have a common 640-key prefix
     v[1, :, :5 * page] = v[0, :, :5 * page]
     lens = [2048, 5 * page + Sq + 7, 900]
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     kp, vp, table = scatter(kn, vn, page, seed=4)
-    freed = table[1, :5].clone()
-    table[1, :5] = table[0, :5]                      # ... held once: both tables name the same pages
-    for pool in (kp, vp):
-        pool[freed.long()] = NAN                     # the duplicate copies are gone
+    share_prefix_pages(kp, vp, table, 0, 1, 5)       # ... held once: both tables name the same pages, the duplicate copies are gone
     ref = reference(q, k, v, seqlens=i32(lens))
     for N in (3, 8):
         o, lse = _both(q, kn, vn, kp, vp, table, cache_seqlens=i32(lens), key_splits=N)
@@ -212,7 +195,7 @@ def test_one_split_is_the_plain_call():
     from photonic_flash_attention_amd import ops
     q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=13)
     lens = [2048, 700]
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     kp, vp, table = scatter(kn, vn, 128, seed=5)
     for caches in (dict(), dict(block_table=table)):
         kk, vv = (kp, vp) if caches else (kn, vn)
@@ -238,7 +221,7 @@ def test_outputs_are_bitwise_reproducible():
     from photonic_flash_attention_amd import ops
     q, k, v = problem(2, 8, 2, 300, 2048, 128, torch.bfloat16, seed=12)
     lens = [2048, 1500]
-    kn, vn = poison(k, v, lens)
+    kn, vn = guard(k, v, lens)
     kp, vp, table = scatter(kn, vn, 64, seed=7)
     for out_dtype in (None, torch.float32):
         for N in (5, "auto"):

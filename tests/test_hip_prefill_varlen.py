@@ -27,7 +27,8 @@ import functools
 import pytest
 import torch
 
-from kvcache_testlib import NAN, check_lse, check_out, device, i32, reference, scatter
+from kvcache_testlib import (NAN, capture, check_lse, check_out, device, guard, i32, ragged_equals_uniform, reference, scatter, seq_rows,
+                             share_prefix_pages)
 
 pytestmark = pytest.mark.gpu
 
@@ -54,17 +55,7 @@ def _fixture(dtype, D):
     v = torch.randn(B, HKV, SMAX, D, generator=g, device=dev).to(dtype)
     k[4, :, :SHARED] = k[0, :, :SHARED]
     v[4, :, :SHARED] = v[0, :, :SHARED]
-    kn, vn = k.clone(), v.clone()
-    for b, n in enumerate(KV_LENS):
-        kn[b, :, n:] = NAN
-        vn[b, :, n:] = NAN
-    return q, k, v, kn, vn
-
-
-def _seq_q(q, b, cu=CU, n=None):
-    """Sequence b's rows of the packed q as the uniform call's [1, H, Sq, D] view."""
-    n = cu[b + 1] - cu[b] if n is None else n
-    return q[cu[b]:cu[b] + n].permute(1, 0, 2)[None]
+    return (q, k, v) + guard(k, v, KV_LENS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,7 +75,7 @@ def _ragged(dtype, D, causal, out_dtype):
 def _fp64(dtype, D, causal):
     """Per sequence with rows: the fp64 (o [1,H,Sq,D], lse [1,H,Sq], pnorm) on the clean caches."""
     q, k, v, _, _ = _fixture(dtype, D)
-    return {b: reference(_seq_q(q, b), k[b:b + 1], v[b:b + 1], seqlens=i32(KV_LENS[b:b + 1]), causal=causal)
+    return {b: reference(seq_rows(q, CU, b), k[b:b + 1], v[b:b + 1], seqlens=i32(KV_LENS[b:b + 1]), causal=causal)
             for b in range(B) if Q_LENS[b] > 0}
 
 
@@ -95,16 +86,7 @@ def test_ragged_call_equals_per_sequence_uniform_calls(dtype, D, causal, out_dty
     from photonic_flash_attention_amd import ops
     q, _, _, kn, vn = _fixture(dtype, D)
     o, lse = _ragged(dtype, D, causal, out_dtype)
-    for b in range(B):
-        if Q_LENS[b] == 0:
-            continue
-        ou, lu = ops.fa3_prefill_cache(_seq_q(q, b), kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32(KV_LENS[b:b + 1]), causal=causal,
-                                       out_dtype=out_dtype, return_lse=True)
-        torch.cuda.synchronize()
-        assert bool(torch.isfinite(ou).all())
-        got = o[CU[b]:CU[b + 1]].permute(1, 0, 2)
-        assert torch.equal(got, ou[0]), f"sequence {b}: O differs, max-abs {float((got.double() - ou[0].double()).abs().max()):.3e}"
-        assert torch.equal(lse[:, CU[b]:CU[b + 1]], lu[0]), f"sequence {b}: LSE differs"
+    ragged_equals_uniform(ops.fa3_prefill_cache, o, lse, q, kn, vn, CU, KV_LENS, causal=causal, out_dtype=out_dtype)
 
 
 @pytest.mark.parametrize("dtype,D,causal,out_dtype", CASES, ids=IDS)
@@ -113,10 +95,9 @@ def test_ragged_call_against_fp64(dtype, D, causal, out_dtype):
     o, lse = _ragged(dtype, D, causal, out_dtype)
     vmax = float(v.abs().max())
     for b, (ro, rl, pn) in _fp64(dtype, D, causal).items():
-        got = o[CU[b]:CU[b + 1]].permute(1, 0, 2)[None]
-        gl = lse[None, :, CU[b]:CU[b + 1]]
+        got = seq_rows(o, CU, b)
         check_out(got, ro, pn, vmax, dtype)
-        check_lse(got, gl, rl)
+        check_lse(got, lse[None, :, CU[b]:CU[b + 1]], rl)
     # sequence 3 holds 20 keys for 33 rows: under the causal rule its first 13 rows see nothing, without it every row sees the 20
     head_o, head_l = o[CU[3]:CU[3] + 13], lse[:, CU[3]:CU[3] + 13]
     if causal:
@@ -180,7 +161,7 @@ def test_rows_past_max_seqlen_q_are_never_written_and_the_others_equal_the_unifo
             assert bool((lse[:, s + cap:s + n] == LSE_SENTINEL).all())
             sq_b = min(n, cap)
             ln = KV_LENS[b] - (sq_b - cap)
-            ou, lu = ops.fa3_prefill_cache(_seq_q(q, b, n=cap), kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32([ln]), causal=causal,
+            ou, lu = ops.fa3_prefill_cache(q[s:s + cap].permute(1, 0, 2)[None], kn[b:b + 1], vn[b:b + 1], cache_seqlens=i32([ln]), causal=causal,
                                            return_lse=True)
             torch.cuda.synchronize()
             assert torch.equal(out[s:s + cap].permute(1, 0, 2), ou[0]) and torch.equal(lse[:, s:s + cap], lu[0]), b
@@ -197,10 +178,7 @@ def test_paged_equals_contiguous_with_a_shared_prefix_page(page, layout):
         kp, vp, table = scatter(kn, vn, page, seed=page + D, layout=layout)
         assert kp.is_contiguous() == (layout == "hpsd")
         n = SHARED // page                               # sequences 0 and 4 hold their common prefix once
-        freed = table[4, :n].clone()
-        table[4, :n] = table[0, :n]
-        for pool in (kp, vp):
-            pool[freed.long()] = NAN                     # the duplicate copies are gone
+        share_prefix_pages(kp, vp, table, 0, 4, n)       # the duplicate copies are gone
         for causal, out_dtype in ((True, None), (False, None), (True, torch.float32)):
             if out_dtype is not None and dtype is not torch.bfloat16:
                 continue
@@ -253,15 +231,7 @@ def test_graph_replays_while_cu_seqlens_lengths_and_table_change():
         return ops.fa3_prefill_varlen(q, kp, vp, cu_seqlens_q=cu, max_seqlen_q=cap, cache_seqlens=lens, return_lse=True, out=o,
                                       block_table=table)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        call(out)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        o_g, l_g = call(out)
+    graph, (o_g, l_g) = capture(lambda: call(out))
 
     def replay_and_compare(rows):
         o_g.fill_(O_SENTINEL)
