@@ -244,7 +244,12 @@ class PagedKVCache:
         after ``free``: nothing reads them.  A partly filled tail page that is still shared is left shared; the next append copies
         it.  Refused with ``ValueError`` when ``n_tokens > 0`` and the page holding key ``n_tokens - 1`` was released behind a
         window: the slot would end in keys that are gone.  Host bookkeeping plus the device length; works on CPU tensors.  Resets the
-        pending copy-on-write table first (see the class's ordering contract)."""
+        pending copy-on-write table first (see the class's ordering contract).
+
+        The window rule, which is the caller's to keep: once ``release_behind_window(slot, W)`` has let go of ``gone`` pages, pass
+        ``n_tokens >= gone * page_size + W - 1``, because the next read of Sq new rows at length L starts at key ``L - Sq - W + 1``, which is
+        ``n_tokens - W + 1`` right after this call.  A smaller ``n_tokens`` that this method still accepts makes that read name a ``-1``
+        table entry, which the kernels clamp into the pool: wrong numbers and no error."""
         self._check_slot(slot)
         n = n_tokens
         if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= self._host_lens[slot]:
@@ -270,7 +275,12 @@ class PagedKVCache:
         a ragged step): such a call's lowest visible key is at or above the bound used here, and the kernels read neither a key
         below that key's 64-key boundary nor its table entry.  ``gather`` and ``swap_pages`` refuse a released page.  Host-side
         bookkeeping plus one small table write; works on CPU tensors.  Resets the pending copy-on-write table first (see the class's
-        ordering contract)."""
+        ordering contract).
+
+        Once this has let go of ``gone`` pages, ``truncate`` and ``fork`` of the slot are the caller's to keep at
+        ``n_tokens >= gone * page_size + W - 1``: a later read of Sq new rows at length L starts at key ``L - Sq - W + 1``.  Below that
+        bound (``truncate`` itself refuses only a tail page that is gone) the next windowed read names a ``-1`` table entry, which the
+        kernels clamp into the pool: wrong numbers and no error."""
         self._check_slot(slot)
         if isinstance(window, bool) or not isinstance(window, int) or window < 1:
             raise ValueError(f"window must be an integer >= 1, got {window!r}")
@@ -436,7 +446,11 @@ class PagedKVCache:
         pages the parent has only reserved are not shared.  Writes the child's table row and length in place; needs no free page and
         moves no K / V -- the first append into a shared, partly filled tail page copies it (``_grow``).  -> the new slot.
         ``PagedCacheFull`` when no slot is free; ``ValueError`` without ``copy_on_write``.  Resets the pending copy-on-write table
-        first (see the class's ordering contract)."""
+        first (see the class's ordering contract).
+
+        The window rule of ``truncate`` holds for the child: when the parent has released ``gone`` pages behind a window W, pass
+        ``n_tokens >= gone * page_size + W - 1`` (so never 0), or the child's first read of new rows starts in a released page.  Nothing
+        here refuses a smaller value: that read names a ``-1`` entry, which the kernels clamp into the pool -- wrong numbers, no error."""
         if not self._cow:
             raise ValueError("fork needs PagedKVCache(copy_on_write=True)")
         self._check_slot(slot)

@@ -2,6 +2,7 @@
 tests it on the CPU, the runner with a stand-in kernel.  A new mode's GPU tests are its cases and its own assertions around these:
 
   ``reference`` / ``check_out`` / ``check_lse``     the fp64 attention, the bound on O, the rule for the LSE (below); ``merge_ref64``
+  ``with_sink`` / ``tree_visible`` / ``folded_reference``   the reference of a call with sinks, and of a tree step (rows folded into the batch)
   ``problem`` / ``gen`` / ``i32`` / ``device``      device draws of q, k, v; small tensors
   ``guard(k, v, lens, sqs, window)``                the one NaN rule: copies with NaN wherever a kernel promises not to read (``window_lo``)
   ``scatter`` / ``share_prefix_pages``              caches over pools in a random page order (page 0 unnamed, pages released below a window),
@@ -118,6 +119,42 @@ def merge_ref64(outs, lses):
             for n in range(len(outs)))
     o = torch.where(s[..., None] > 0, o / s[..., None].clamp_min(1e-300), torch.zeros_like(o))
     return o, torch.where(s > 0, m + torch.log(s), torch.full_like(m, -INF))
+
+
+# --- the references of two modes: attention sinks (tests/test_hip_attn_sinks.py) and the tree step (tests/test_hip_decode_tree.py) ------
+
+def with_sink(ref, sinks):
+    """``reference()``'s ``(o [B,H,Sq,D], lse [B,H,Sq], pnorm [B,H,Sq,1])`` and ``sinks [H]`` -> the same three with the sink, in fp64."""
+    o, lse, pn = ref
+    s = sinks.to(lse.device).double().view(1, -1, 1).expand_as(lse)
+    dead = torch.isneginf(lse)
+    w = torch.where(torch.isneginf(s), torch.ones_like(lse), torch.sigmoid(lse - s))
+    w = torch.where(dead, torch.zeros_like(w), w)
+    lse2 = torch.where(dead, s, torch.logaddexp(lse, s))
+    return o * w[..., None], lse2, pn * w[..., None]
+
+
+def tree_visible(words, lens, Sq, Smax):
+    """The rule of the specification, from the words: bool [B, Sq, Smax]."""
+    j = torch.arange(Smax, device=words.device)
+    L = lens.long()
+    rel = j[None, :] - (L - Sq)[:, None]                                     # j - off_b, [B, Smax]
+    bit = ((words[:, :, None] >> rel.clamp(0, 63)[:, None, :]) & 1).bool()   # an arithmetic shift: the bit asked for is still bit 0
+    return (j[None, None, :] < L[:, None, None]) & ((rel < 0)[:, None, :] | bit)
+
+
+def folded_reference(pr, words, key_mask=None):
+    """fp64 reference of the tree step, the rows folded into the batch -> (o [B,H,Sq,D], lse [B,H,Sq], pnorm [B,H,Sq,1])."""
+    q, B, Sq, Smax = pr["q"], pr["B"], pr["Sq"], pr["Smax"]
+    H, D = q.shape[1], q.shape[3]
+    vis = tree_visible(words, pr["lens"], Sq, Smax)
+    if key_mask is not None:
+        vis = vis & key_mask.bool()[:, None, :]
+    qf = q.permute(0, 2, 1, 3).reshape(B * Sq, H, 1, D)
+    o, lse, pn = reference(qf, pr["k"].repeat_interleave(Sq, dim=0), pr["v"].repeat_interleave(Sq, dim=0),
+                           seqlens=pr["lens"].repeat_interleave(Sq), key_mask=vis.reshape(B * Sq, Smax), causal=False)
+    unfold = lambda t, last: t.reshape(B, Sq, H, last).permute(0, 2, 1, 3)
+    return unfold(o, D), lse.reshape(B, Sq, H).permute(0, 2, 1), unfold(pn, 1)
 
 
 # --- caches and pools ----------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 The rule: ``sinks[h]`` (fp32, one per query head, in the units of the scaled scores) is one extra key with that score and a zero value
 row -- ``den_i = sum_j exp(x_ij) + exp(sinks[h])``, ``LSE_i = log(den_i)``; a row with no visible key has O = 0 and LSE = sinks[h].
 
-The reference: ``with_sink`` turns ``kvcache_testlib.reference``'s fp64 ``(o, lse, pnorm)`` into the sink result with
+The reference: ``kvcache_testlib.with_sink`` turns ``reference``'s fp64 ``(o, lse, pnorm)`` into the sink result with
 ``w = sigmoid(lse - sink_h)``: ``o' = o w``, ``pnorm' = pnorm w``, ``lse' = logaddexp(lse, sink_h)``, and on rows with ``lse = -inf``
 ``o' = 0``, ``lse' = sink_h``.  tests/test_attn_sinks_host.py checks it on the CPU against the formulation that appends a key.  The
 bounds are ``check_out`` and ``check_lse`` of tests/kvcache_testlib.py, unchanged, with ``pnorm'``.
@@ -30,7 +30,7 @@ import torch
 
 from capi_testlib import decode_args
 from kvcache_testlib import (EPS, INF, capture, check_lse, check_out, device, guard, i32, ragged_equals_uniform, reference, run_and_check,
-                             scatter)
+                             scatter, with_sink)
 from photonic_flash_attention_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -41,17 +41,6 @@ DT_IDS = ["bf16-d64", "fp16-d128", "fp16-d64", "bf16-d128"]
 
 
 # --- the reference with sinks, and sinks that matter (CPU or GPU tensors; no kernel) -------------------------------------------------
-
-def with_sink(ref, sinks):
-    """``reference()``'s ``(o [B,H,Sq,D], lse [B,H,Sq], pnorm [B,H,Sq,1])`` and ``sinks [H]`` -> the same three with the sink, in fp64."""
-    o, lse, pn = ref
-    s = sinks.to(lse.device).double().view(1, -1, 1).expand_as(lse)
-    dead = torch.isneginf(lse)
-    w = torch.where(torch.isneginf(s), torch.ones_like(lse), torch.sigmoid(lse - s))
-    w = torch.where(dead, torch.zeros_like(w), w)
-    lse2 = torch.where(dead, s, torch.logaddexp(lse, s))
-    return o * w[..., None], lse2, pn * w[..., None]
-
 
 def choose_sinks(rlse):
     """``rlse [B,H,Sq]`` (the sink-less reference LSE) -> fp32 ``sinks [H]`` on the CPU: per head the median of the finite LSEs plus an

@@ -19,7 +19,8 @@ import functools
 import pytest
 import torch
 
-from kvcache_testlib import capture, check_lse, check_out, contiguous_of, device, guard, i32, reference, scatter
+from kvcache_testlib import (capture, check_lse, check_out, contiguous_of, device, folded_reference, guard, i32, reference, scatter,
+                             tree_visible)  # noqa: F401  (tree_visible: kept importable from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,29 +50,6 @@ def _problem(H, Hkv, Sq, Smax, lens, D, dtype):
 def _pools(H, Hkv, Sq, Smax, lens, D, dtype, page):
     pr = _problem(H, Hkv, Sq, Smax, lens, D, dtype)
     return scatter(pr["kn"], pr["vn"], page, seed=page + D)
-
-
-def tree_visible(words, lens, Sq, Smax):
-    """The rule of the specification, from the words: bool [B, Sq, Smax]."""
-    j = torch.arange(Smax, device=words.device)
-    L = lens.long()
-    rel = j[None, :] - (L - Sq)[:, None]                                     # j - off_b, [B, Smax]
-    bit = ((words[:, :, None] >> rel.clamp(0, 63)[:, None, :]) & 1).bool()   # an arithmetic shift: the bit asked for is still bit 0
-    return (j[None, None, :] < L[:, None, None]) & ((rel < 0)[:, None, :] | bit)
-
-
-def folded_reference(pr, words, key_mask=None):
-    """fp64 reference of the tree step, the rows folded into the batch -> (o [B,H,Sq,D], lse [B,H,Sq], pnorm [B,H,Sq,1])."""
-    q, B, Sq, Smax = pr["q"], pr["B"], pr["Sq"], pr["Smax"]
-    H, D = q.shape[1], q.shape[3]
-    vis = tree_visible(words, pr["lens"], Sq, Smax)
-    if key_mask is not None:
-        vis = vis & key_mask.bool()[:, None, :]
-    qf = q.permute(0, 2, 1, 3).reshape(B * Sq, H, 1, D)
-    o, lse, pn = reference(qf, pr["k"].repeat_interleave(Sq, dim=0), pr["v"].repeat_interleave(Sq, dim=0),
-                           seqlens=pr["lens"].repeat_interleave(Sq), key_mask=vis.reshape(B * Sq, Smax), causal=False)
-    unfold = lambda t, last: t.reshape(B, Sq, H, last).permute(0, 2, 1, 3)
-    return unfold(o, D), lse.reshape(B, Sq, H).permute(0, 2, 1), unfold(pn, 1)
 
 
 def _chain(B, Sq):
