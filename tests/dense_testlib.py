@@ -16,7 +16,12 @@ tests/test_hip_backward.py::test_fp32_backward_matches_autograd_of_oracle and ::
     gradients, with dropout     3e-5 * max(1, max|ref|)
 
 and, as equalities: every output finite; ``lse`` -inf on exactly the reference's rows; ``o`` and ``dq`` exactly 0.0 on those rows; ``dk``
-and ``dv`` exactly 0.0 for keys that no row of the group sees."""
+and ``dv`` exactly 0.0 for keys that no row of the group sees.
+
+Random operands measure the arithmetic; which keys a row of the dense forward sees (the causal diagonal, ``seqlens_k``, key and element
+masks, block and tile edges, on every kernel family) is checked by the exact probes of tests/probe_testlib.py
+(tests/test_hip_dense_probes.py), on inputs whose answer is a count of keys.  There an exactly known fp32 value also pins the 16-bit
+store to half a unit in the last place: the truncating store that ``backward_bound`` cannot tell from a rounding one."""
 
 from __future__ import annotations
 

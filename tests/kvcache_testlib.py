@@ -22,7 +22,12 @@ allows it.  It is computed from CLEAN caches: the NaN a test puts where a kernel
 
 The bounds: ``|err| <= eps |ref| + 3 eps max|v| ||p_row||_2 + 2e-6`` per element of a 16-bit output (eps 2^-9 bf16, 2^-11 fp16: the
 bound of the fast variant in tests/test_hip_parity.py's docstring), 1e-3 max-abs for an fp32 output, 2e-3 on the LSE with exact
-agreement on which rows are -inf, and O exactly zero on those rows.  Every output must be finite."""
+agreement on which rows are -inf, and O exactly zero on those rows.  Every output must be finite.
+
+These bounds measure the arithmetic.  WHICH KEYS a row sees they measure poorly: one wrong key among n random ones moves O by about
+``|v| / n`` and the LSE by about ``1 / n``, below every bound above at a few thousand keys.  Visibility -- lengths, the causal diagonal,
+windows, tree words, masks, split, tile and page edges, sinks, the shared-prefix cut -- is checked by the exact probes of
+tests/probe_testlib.py (tests/test_hip_cache_probes.py), on inputs whose answer is a count of keys."""
 
 from __future__ import annotations
 
