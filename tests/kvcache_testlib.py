@@ -27,7 +27,8 @@ agreement on which rows are -inf, and O exactly zero on those rows.  Every outpu
 These bounds measure the arithmetic.  WHICH KEYS a row sees they measure poorly: one wrong key among n random ones moves O by about
 ``|v| / n`` and the LSE by about ``1 / n``, below every bound above at a few thousand keys.  Visibility -- lengths, the causal diagonal,
 windows, tree words, masks, split, tile and page edges, sinks, the shared-prefix cut -- is checked by the exact probes of
-tests/probe_testlib.py (tests/test_hip_cache_probes.py), on inputs whose answer is a count of keys."""
+tests/probe_testlib.py (tests/test_hip_cache_probes.py), on inputs whose answer is a count of keys.  WHERE a kernel reads and writes once
+index times stride passes 2^31 and 2^32 is tests/far_testlib.py's (tests/test_hip_far_cache.py, tests/test_hip_far_dense.py)."""
 
 from __future__ import annotations
 
