@@ -29,6 +29,9 @@
  * v9, additive: pfa_fa3_sinks and pfa_fa3_decode_sink*, pfa_fa3_prefill_sink*, pfa_fa3_prefill_varlen_sink*, pfa_fa3_prefill_split_sink* --
  * attention sinks over a 16-bit KV cache: one learned fp32 value per query head in every row's softmax denominator, in the decode, the
  * forward (uniform, ragged, windowed) and the split over keys.
+ * v9, additive, declared in pfa_hip_train_sinks.h: pfa_fa3_fwd_sink*, pfa_fa3_varlen_fwd_sink* and pfa_fa3_sink_grad* -- attention sinks
+ * for training: the dense and the packed forward (8-wave kernel) with a pfa_fa3_sinks block, and the gradient of the sinks behind the
+ * unchanged backward.
  *
  * Reference seam (danieleschmidt/Photonic-Flash-Attention, all paths under
  * src/photonic_flash_attention/):

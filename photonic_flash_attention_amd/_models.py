@@ -243,3 +243,20 @@ def _varlen_backward_model(q, k, v, out, dout, lse, dq, dk, dv, cu_q, cu_k, max_
         dvb = torch.matmul(p.transpose(1, 2), gb)
         dk[sk:sk + nk] = dkb.reshape(Hkv, g, nk, -1).sum(1).transpose(0, 1).to(dk.dtype)
         dv[sk:sk + nk] = dvb.reshape(Hkv, g, nk, -1).sum(1).transpose(0, 1).to(dv.dtype)
+
+
+def _sink_grad_model(lse, delta, sinks, d_sinks, rows=None) -> None:
+    """``pfa_fa3_sink_grad``'s rule in plain torch, fp32: ``d_sinks[h] = - sum exp(sinks[h] - lse) * delta`` over the rows of head h --
+    the executable specification, and what ``fa3_sink_grad`` runs on CPU tensors.  Dense ``[B, H, Sq]`` arrays (``rows`` None), or packed
+    ``[H, total_q]`` ones with ``rows`` the host list of ``(start, count)`` per sequence: rows no sequence covers are not read.  A row
+    with ``lse = -inf`` is SKIPPED (``delta`` there may hold anything, NaN included), and a ``-inf`` sink skips every row of its head."""
+    H = sinks.shape[0]
+    if rows is None:
+        l, d = lse.transpose(0, 1).reshape(H, -1), delta.transpose(0, 1).reshape(H, -1)
+    else:
+        idx = torch.cat([torch.arange(s, s + n) for s, n in rows] + [torch.zeros(0, dtype=torch.long)])
+        l, d = lse[:, idx], delta[:, idx]
+    s = sinks.float()[:, None]
+    live = (l > float("-inf")) & (s > float("-inf"))
+    terms = torch.exp(torch.where(live, s - l.float(), torch.zeros_like(l))) * torch.where(live, d.float(), torch.zeros_like(d))
+    d_sinks.copy_(-torch.where(live, terms, torch.zeros_like(terms)).sum(dim=1) + 0.0)

@@ -42,13 +42,21 @@ class FlashAttention3(nn.Module):
         device: Optional[torch.device] = None,
         dtype: Optional[torch.dtype] = None,
         fp32_attention: str = "exact",
+        attention_sinks: bool = False,
     ):
         """``fp32_attention`` (not in the reference; only matters for fp32 modules, the reference's default dtype): "exact" runs the
         attention core of an fp32 module in fp32 on the vector ALUs -- the reference's numbers to ~1e-6, at a few TFLOP/s -- and is
         the default, so that nothing is rounded behind the caller's back; "bf16" rounds q, k, v to bf16 and takes the MFMA kernels
         (about 1e-2 from the fp32 reference at the module output, two orders of magnitude faster).  "exact" covers autograd too: the
-        fp32 forward and the fp32 backward kernels."""
+        fp32 forward and the fp32 backward kernels.
+
+        ``attention_sinks`` (not in the reference): the module holds ``sinks``, one learned fp32 value per head (initially 0: an extra
+        key of weight 1 and a zero value row), in every row's softmax denominator -- the GPT-OSS-style layer (``ops.fa3_attention(...,
+        sinks=)``).  The attention then runs on the 16-bit kernels; no attention dropout, no ``need_weights``.  False
+        (the default): parameters, state dict and launches are the module's without the option."""
         super().__init__()
+        if attention_sinks and dropout > 0:
+            raise ValueError("attention_sinks does not combine with attention dropout")
         if fp32_attention not in ("exact", "bf16"):
             raise ValueError('fp32_attention must be "exact" or "bf16"')
         self.fp32_attention = fp32_attention
@@ -62,6 +70,7 @@ class FlashAttention3(nn.Module):
         self.qkv_proj = nn.Linear(embed_dim, 3 * embed_dim, bias=bias, device=device, dtype=dtype)
         self.out_proj = nn.Linear(embed_dim, embed_dim, bias=bias, device=device, dtype=dtype)
         self.dropout_module = nn.Dropout(dropout) if dropout > 0 else None
+        self.sinks = nn.Parameter(torch.zeros(num_heads, dtype=torch.float32, device=device)) if attention_sinks else None
 
         # fp32 modules with fp32_attention="bf16", and every fp32 module under autograd, compute attention in this dtype
         self.compute_dtype = torch.bfloat16
@@ -144,6 +153,16 @@ class FlashAttention3(nn.Module):
         # 2-D [B,Sk] masks take the cheap key-mask path (:166-167); 3-D / 4-D masks the general one (:168,:235)
         key_mask = attention_mask if (attention_mask is not None and attention_mask.dim() == 2) else None
         mask = attention_mask if (attention_mask is not None and attention_mask.dim() != 2) else None
+        if self.sinks is not None:
+            if need_weights:
+                raise NotImplementedError("need_weights together with attention_sinks is not supported")
+            if q.dtype == torch.float32 and self.fp32_attention == "exact":
+                raise ValueError('attention_sinks runs on the 16-bit kernels: build an fp32 module with fp32_attention="bf16"')
+            cd = self.compute_dtype if q.dtype == torch.float32 else q.dtype
+            # (.float(): module.to(bfloat16) narrows the parameter with the weights; the kernels take the sinks in fp32)
+            out = ops.fa3_attention(q.to(cd), k.to(cd), v.to(cd), causal=is_causal, key_mask=key_mask, mask=mask, softmax_scale=self.scaling,
+                                    out_dtype=q.dtype, sinks=self.sinks.float())
+            return out, None
         if self.training and self.dropout > 0:
             # The reference applies attention dropout only in its dense branch (:174-175), i.e. when both sequence lengths
             # fit one tile of min(Sq, Sk, 512) (floor 32, :264-293); its tiled branch (:182-262) has no dropout at all.

@@ -146,6 +146,7 @@ class HybridFlashAttention(nn.Module):
         dtype: Optional[torch.dtype] = None,
         enable_scaling: bool = True,
         max_concurrent_requests: int = 4,
+        attention_sinks: bool = False,
     ):
         super().__init__()
         self.embed_dim = embed_dim
@@ -158,7 +159,7 @@ class HybridFlashAttention(nn.Module):
 
         self.gpu_attention = FlashAttention3(
             embed_dim=embed_dim, num_heads=num_heads, dropout=dropout, bias=bias,
-            device=device if device != "auto" else None, dtype=dtype)
+            device=device if device != "auto" else None, dtype=dtype, attention_sinks=attention_sinks)
         self.photonic_attention = None   # out of scope (north_star): never constructed
 
         self.router = AdaptiveRouter()

@@ -153,30 +153,13 @@ int check(const pfa_fa3_args* a) {
     return PFA_OK;
 }
 
-// Masks are condensed into one 64-bit word per mask row and 64-key tile before the forward and the weights pass (pfa_mask_host.h):
-// the [B, Sk] key mask as one row per batch, else the element mask
-pfa::MaskWords mask_words(const pfa_fa3_args* a) {
-    return a->key_mask ? pfa::mask_words(a->key_mask, a->B, 1, 1, a->Sk, a->key_mask_stride_b, 0, 0, 1) : pfa::element_mask_words(a);
-}
-// mask + enough workspace: one word per row and tile instead of a mask byte per score (without workspace the byte path runs)
-template <typename Params>
-bool take_mask_words(Params& p, const pfa::MaskWords& mb, const pfa_fa3_args* a) {
-    const bool use = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
-    p.mbits = use ? (const unsigned long long*)a->workspace : nullptr;
-    p.mb_sb = mb.ob; p.mb_sh = mb.oh; p.mb_sq = mb.oq;
-    return use;
-}
+// Masks are condensed into one 64-bit word per mask row and 64-key tile before the forward and the weights pass (pfa_mask_host.h)
+using pfa::take_mask_words;
+pfa::MaskWords mask_words(const pfa_fa3_args* a) { return pfa::fwd_mask_words(a); }
 // (named here, in front of the fp32 launch: the compiler emits template kernels in the order the host code first names them)
 bool enqueue_mask_words(const pfa::MaskWords& mb, const pfa_fa3_args* a, void* stream) { return pfa::launch_row_words(mb, a->workspace, stream); }
 
-// what the three parameter blocks of this file share besides the strides: key counts, mask, shape and the K/V head grouping
-template <typename Params>
-void fill_common(Params& p, const pfa_fa3_args* a) {
-    p.seqlens_k = a->seqlens_k;
-    pfa::fill_mask(p, a);
-    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
-    p.kv_group = pfa::kv_group_of(a);
-}
+using pfa::fill_common;
 
 int launch_f32(const pfa_fa3_args* a, void* stream) {
     pfa::F32Params p;

@@ -41,6 +41,27 @@ inline MaskWords element_mask_words(const Args* a) {
                       a->mask_stride_h, a->mask_stride_q, a->mask_stride_k);
 }
 
+// ... of a forward call (pfa_fa3_args): the [B, Sk] key mask as one row per batch, else the element mask
+inline MaskWords fwd_mask_words(const pfa_fa3_args* a) {
+    return a->key_mask ? mask_words(a->key_mask, a->B, 1, 1, a->Sk, a->key_mask_stride_b, 0, 0, 1) : element_mask_words(a);
+}
+// mask + enough workspace: one word per row and tile instead of a mask byte per score (without workspace the byte path runs)
+template <typename Params>
+inline bool take_mask_words(Params& p, const MaskWords& mb, const pfa_fa3_args* a) {
+    const bool use = mb.src && a->workspace && a->workspace_bytes >= mb.bytes();
+    p.mbits = use ? (const unsigned long long*)a->workspace : nullptr;
+    p.mb_sb = mb.ob; p.mb_sh = mb.oh; p.mb_sq = mb.oq;
+    return use;
+}
+// what the parameter blocks of the dense forward calls share besides the strides: key counts, mask, shape and the K/V head grouping
+template <typename Params>
+inline void fill_common(Params& p, const pfa_fa3_args* a) {
+    p.seqlens_k = a->seqlens_k;
+    fill_mask(p, a);
+    p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk;
+    p.kv_group = kv_group_of(a);
+}
+
 // Enqueue the two kernels that fill the scratch at `ws` (m.bytes() of it).  false: a launch failed (its HIP error is not kept).
 template <int UNUSED = 0>      // (a template so that the kernels are instantiated where a translation unit first calls it, not where it includes this)
 bool launch_row_words(const MaskWords& m, void* ws, void* stream) {

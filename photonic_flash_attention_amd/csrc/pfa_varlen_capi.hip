@@ -50,18 +50,7 @@ int pfa_fa3_varlen_fwd(const pfa_fa3_varlen_args* a, void* stream) {
     const int st = check(a);
     if (st != PFA_OK) return st;
     pfa::FwdParams p;
-    p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse;
-    p.seqlens_k = nullptr; p.mask = nullptr; p.mbits = nullptr; p.dbg = nullptr;
-    p.q_sb = p.k_sb = p.v_sb = p.o_sb = 0;
-    p.m_sb = p.m_sh = p.m_sq = p.m_sk = 0; p.mb_sb = p.mb_sh = p.mb_sq = 0;
-    p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
-    p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
-    p.B = a->B; p.H = a->H; p.Sq = a->max_seqlen_q; p.Sk = a->max_seqlen_k;
-    p.nqblk = (a->max_seqlen_q + pfa::FWD_BLOCK_M - 1) / pfa::FWD_BLOCK_M;
-    p.kv_group = a->H / a->Hkv;
-    p.xcd_group = 0; p.magic_h = p.magic_g = 0;
-    p.scale_log2 = a->softmax_scale * pfa::LOG2E;
-    p.cu_q = a->cu_seqlens_q; p.cu_k = a->cu_seqlens_k; p.total_q = a->total_q; p.total_k = a->total_k;
+    pfa::varlen::fill_fwd_params(p, a);
     const bool causal = a->causal != 0, out32 = a->dtype_out == PFA_DTYPE_FP32;
     // (split P goes with the fp32 store: two of the four combinations exist)
     const auto fn = pfa::dispatch_elem_dim(a->dtype_in, a->D, [&](auto t) {

@@ -37,6 +37,23 @@ inline int check_tail(const Args* a) {
     return PFA_OK;
 }
 
+// fa3_fwd_kernel's parameter block (FwdParams, or a block derived from it) of a checked packed forward call
+template <typename Params>
+inline void fill_fwd_params(Params& p, const pfa_fa3_varlen_args* a) {
+    p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse;
+    p.seqlens_k = nullptr; p.mask = nullptr; p.mbits = nullptr; p.dbg = nullptr;
+    p.q_sb = p.k_sb = p.v_sb = p.o_sb = 0;
+    p.m_sb = p.m_sh = p.m_sq = p.m_sk = 0; p.mb_sb = p.mb_sh = p.mb_sq = 0;
+    p.q_sh = a->q_stride_h; p.q_ss = a->q_stride_s; p.k_sh = a->k_stride_h; p.k_ss = a->k_stride_s;
+    p.v_sh = a->v_stride_h; p.v_ss = a->v_stride_s; p.o_sh = a->o_stride_h; p.o_ss = a->o_stride_s;
+    p.B = a->B; p.H = a->H; p.Sq = a->max_seqlen_q; p.Sk = a->max_seqlen_k;
+    p.nqblk = (a->max_seqlen_q + 255) / 256;      // Q blocks of 256 rows, as q_workgroups counts them
+    p.kv_group = a->H / a->Hkv;
+    p.xcd_group = 0; p.magic_h = p.magic_g = 0;
+    p.scale_log2 = a->softmax_scale * LOG2E;
+    p.cu_q = a->cu_seqlens_q; p.cu_k = a->cu_seqlens_k; p.total_q = a->total_q; p.total_k = a->total_k;
+}
+
 inline const char* elem_name(int dtype) { return dtype == PFA_DTYPE_BF16 ? "bf16" : "fp16"; }
 
 }  // namespace varlen

@@ -58,7 +58,7 @@ class PhotonicFlashAttention(nn.Module):
 
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0, bias: bool = True,
                  photonic_threshold: Optional[int] = None, device: Union[str, torch.device] = "auto",
-                 dtype: Optional[torch.dtype] = None):
+                 dtype: Optional[torch.dtype] = None, attention_sinks: bool = False):
         super().__init__()
         if embed_dim % num_heads:
             raise AssertionError("embed_dim must be divisible by num_heads")
@@ -68,7 +68,8 @@ class PhotonicFlashAttention(nn.Module):
         self.photonic_threshold = photonic_threshold or cfg.photonic_threshold
         self.auto_device_selection = device == "auto" and cfg.auto_device_selection
         self.gpu_attention = FlashAttention3(embed_dim=embed_dim, num_heads=num_heads, dropout=dropout, bias=bias,
-                                             device=None if device == "auto" else device, dtype=dtype)
+                                             device=None if device == "auto" else device, dtype=dtype,
+                                             attention_sinks=attention_sinks)      # gpu_attention.sinks, fp32 [num_heads]
         self.photonic_attention = None                      # out of scope (north_star): never built
         self.photonic_available = is_photonic_available()   # False on an MI355X box
         self.last_device_used, self.last_latency_ms, self.last_energy_mj = "gpu", 0.0, 0.0
@@ -122,13 +123,13 @@ class PhotonicMultiHeadAttention(PhotonicFlashAttention):
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0, bias: bool = True,
                  add_bias_kv: bool = False, add_zero_attn: bool = False, kdim: Optional[int] = None,
                  vdim: Optional[int] = None, batch_first: bool = False, photonic_threshold: Optional[int] = None,
-                 device: Union[str, torch.device] = "auto", dtype: Optional[torch.dtype] = None):
+                 device: Union[str, torch.device] = "auto", dtype: Optional[torch.dtype] = None, attention_sinks: bool = False):
         if add_bias_kv or add_zero_attn:
             raise NotImplementedError(self._UNSUPPORTED.format("add_bias_kv and add_zero_attn"))
         if kdim is not None or vdim is not None:
             raise NotImplementedError(self._UNSUPPORTED.format("Different key/value dimensions"))
         super().__init__(embed_dim, num_heads, dropout=dropout, bias=bias, photonic_threshold=photonic_threshold,
-                         device=device, dtype=dtype)
+                         device=device, dtype=dtype, attention_sinks=attention_sinks)
         self.batch_first = batch_first
 
     def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,

@@ -20,9 +20,9 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi
+from . import _capi, _capi_sinks
 from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _page_copy_model,      # noqa: F401
-                      _rope_append_model, _rope_rotate, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
+                      _rope_append_model, _rope_rotate, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
 
@@ -301,7 +301,8 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
                 softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
                 return_lse: bool = False, return_weights: bool = False, weights_dtype: Optional[torch.dtype] = None,
                 split_p: Optional[bool] = None, drop_mask: Optional[torch.Tensor] = None, drop_scale: float = 1.0,
-                out: Optional[torch.Tensor] = None, _variant: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                out: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None,
+                _variant: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """softmax(scale * q k^T + mask) v on the MI355X kernel.
 
     q: ``[B,H,Sq,D]``, k/v: ``[B,H,Sk,D]`` (any batch/head/seq strides that are multiples of 8
@@ -313,8 +314,21 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
     ``out_dtype=torch.float32`` selects the parity variant: fp32 store and, unless
     ``split_p=False`` is forced, P carried as bf16 hi+lo so the result is within 1e-3 of the
     fp32 reference ("numerics").
+
+    ``sinks``: fp32 ``[H]`` on q's device, one learned attention sink per query head in the units of the scaled scores -- one more key of
+    that score and a zero value row in every row's softmax, inside the returned LSE (``pfa_fa3_fwd_sink``).  A row with no
+    visible key gets O = 0 and LSE = the sink; a ``-inf`` sink gives its head the bits of the sink-less 8-wave call.  Runs the 8-wave
+    kernel only; 16-bit operands; refused with dropout and ``return_weights``.
     """
     B, H, Sq, D = q.shape
+    snk = _sinks_arg(sinks, q)
+    if snk is not None:
+        if q.dtype == torch.float32:
+            raise ValueError("sinks need bf16 / fp16 operands: the exact fp32 kernels carry no sink")
+        if drop_mask is not None:
+            raise ValueError("sinks do not combine with attention dropout (drop_mask)")
+        if return_weights:
+            raise ValueError("sinks do not combine with return_weights: the weights pass carries no sink")
     Dp = _padded_head_dim(D)
     if Dp != D:
         # no kernel instantiation for this head dim: run the next larger one on zero-padded operands (same scores, the
@@ -323,7 +337,7 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
                           key_mask=key_mask, mask=mask,
                           softmax_scale=_scale(softmax_scale, D), out_dtype=out_dtype,
                           return_lse=return_lse, return_weights=return_weights, weights_dtype=weights_dtype,
-                          split_p=split_p, drop_mask=drop_mask, drop_scale=drop_scale, _variant=_variant)
+                          split_p=split_p, drop_mask=drop_mask, drop_scale=drop_scale, sinks=sinks, _variant=_variant)
         o = res[0][..., :D]
         if out is not None:
             out.copy_(o)
@@ -350,8 +364,12 @@ def fa3_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bo
                             drop_mask=drop_mask, drop_scale=drop_scale)
     held = torch.cuda.current_stream(q.device)
     stream = held.cuda_stream
-    st = _capi.load().pfa_fa3_fwd(C.byref(args), C.c_void_p(stream))
-    _raise_status("pfa_fa3_fwd", st)
+    if snk is None:
+        st = _capi.load().pfa_fa3_fwd(C.byref(args), C.c_void_p(stream))
+        _raise_status("pfa_fa3_fwd", st)
+    else:
+        st = _capi_sinks.load().pfa_fa3_fwd_sink(C.byref(args), C.byref(snk), C.c_void_p(stream))
+        _raise_status("pfa_fa3_fwd_sink", st)
     weights = None
     if return_weights:
         Sk = k.shape[2]
@@ -385,15 +403,21 @@ def _dout_meets_abi(dout: torch.Tensor, D: int) -> bool:
 
 def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=None, key_mask=None, mask=None,
                  softmax_scale: Optional[float] = None, grad_dtype: Optional[torch.dtype] = None,
-                 drop_mask: Optional[torch.Tensor] = None, drop_scale: float = 1.0):
+                 drop_mask: Optional[torch.Tensor] = None, drop_scale: float = 1.0, sinks: Optional[torch.Tensor] = None):
     """dQ, dK, dV of ``fa3_forward`` (``pfa_fa3_bwd``).  All operands ``[B,H,S,D]``-shaped (any strides, head dim
     contiguous), ``lse`` the forward's ``[B,H,Sq]`` fp32 LSE.  Returns gradients as ``[B,H,S,D]`` views of
     ``[B,S,H,D]`` buffers, in ``grad_dtype`` (input dtype by default, or fp32).  ``key_mask`` / ``mask``: the masks
     the forward was called with (same conventions as ``fa3_forward``).  Grouped-query heads: ``k`` / ``v`` may hold ``H / g`` heads as in
-    the forward; ``dk`` / ``dv`` then have ``H / g`` heads too (summed over each group inside the dK/dV kernel, ABI v7)."""
+    the forward; ``dk`` / ``dv`` then have ``H / g`` heads too (summed over each group inside the dK/dV kernel, ABI v7).
+
+    ``sinks``: the forward's sinks; ``out`` and ``lse`` are then that forward's.  The backward kernels run unchanged (the LSE holds the
+    sink, its value row is zero), ``fa3_sink_grad`` follows on the same stream and the same ``delta``, and the result is
+    ``(dq, dk, dv, d_sinks)`` with ``d_sinks`` fp32 ``[H]``."""
     B, H, Sq, D = q.shape
     Sk = k.shape[2]
     Hkv = k.shape[1]
+    if _sinks_arg(sinks, q) is not None and (q.dtype == torch.float32 or drop_mask is not None):
+        raise ValueError("sinks need bf16 / fp16 operands and do not combine with attention dropout")
     if v.shape[1] != Hkv or Hkv <= 0 or H % Hkv:
         raise ValueError(f"k / v carry {k.shape[1]} / {v.shape[1]} heads: both must hold H / g heads for an integer g (H = {H})")
     if Hkv != H and q.dtype == torch.float32:
@@ -408,8 +432,8 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
         grads = fa3_backward(_pad_d(q, Dp), _pad_d(k, Dp), _pad_d(v, Dp), _pad_d(out, Dp), _pad_d(dout, Dp), lse,
                              causal=causal, seqlens_k=seqlens_k, key_mask=key_mask, mask=mask,
                              softmax_scale=_scale(softmax_scale, D),
-                             grad_dtype=grad_dtype, drop_mask=drop_mask, drop_scale=drop_scale)
-        return tuple(g[..., :D] for g in grads)
+                             grad_dtype=grad_dtype, drop_mask=drop_mask, drop_scale=drop_scale, sinks=sinks)
+        return tuple(g[..., :D] for g in grads[:3]) + tuple(grads[3:])
     gdt = q.dtype if grad_dtype is None else grad_dtype
     if not _dout_meets_abi(dout, D):
         dout = dout.contiguous()
@@ -448,7 +472,56 @@ def fa3_backward(q, k, v, out, dout, lse, *, causal: bool = False, seqlens_k=Non
     st = _capi.load().pfa_fa3_bwd(C.byref(a), C.c_void_p(stream.cuda_stream))
     _raise_status("pfa_fa3_bwd", st)
     _hold(keep, stream)
+    if sinks is not None:
+        return dq, dk, dv, fa3_sink_grad(lse, delta, sinks)
     return dq, dk, dv
+
+
+def fa3_sink_grad(lse: torch.Tensor, delta: torch.Tensor, sinks: torch.Tensor, *, cu_seqlens_q: Optional[torch.Tensor] = None,
+                  max_seqlen_q: Optional[int] = None) -> torch.Tensor:
+    """The gradient of the attention sinks (``pfa_fa3_sink_grad``): ``d_sinks[h] = - sum_rows exp(sinks[h] - lse) * delta``, fp32 ``[H]``.
+
+    ``lse``: the LSE of a forward with ``sinks``; ``delta``: ``rowsum(dO o O)`` as the backward leaves it.  Dense: both contiguous fp32
+    ``[B, H, Sq]``.  Packed (``cu_seqlens_q`` int32 ``[B + 1]`` on the device, ``max_seqlen_q`` a host int): both contiguous ``[H, total_q]``;
+    rows no sequence covers are not read.  Rows with ``lse = -inf`` are skipped, a ``-inf`` sink gets gradient 0.  Two launches on q's
+    current stream, no atomics, bitwise reproducible; grids from host shapes only (capturable, valid while the sink values change).
+    On CPU tensors the same rule runs in plain torch (the executable specification)."""
+    packed = cu_seqlens_q is not None
+    if lse.dim() != (2 if packed else 3) or delta.shape != lse.shape or lse.dtype != torch.float32 or delta.dtype != torch.float32 \
+            or not lse.is_contiguous() or not delta.is_contiguous() or delta.device != lse.device:
+        raise ValueError("lse and delta must be contiguous fp32 tensors of one shape, [B, H, Sq] or packed [H, total_q], on one device")
+    H = lse.shape[0] if packed else lse.shape[1]
+    if not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32 or sinks.shape != (H,) or not sinks.is_contiguous() \
+            or sinks.device != lse.device:
+        raise ValueError(f"sinks must be a contiguous fp32 [H] = [{H}] tensor on the device of lse")
+    if packed:
+        if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous() \
+                or cu_seqlens_q.device != lse.device:
+            raise ValueError("cu_seqlens_q must be a contiguous int32 [B + 1] tensor on the device of lse")
+        B, total_q, Sq = cu_seqlens_q.numel() - 1, lse.shape[1], operator.index(max_seqlen_q)
+        if not 1 <= Sq <= total_q:
+            raise ValueError(f"max_seqlen_q {Sq}: must lie in 1 .. {total_q}")
+    else:
+        (B, _, Sq), total_q = lse.shape, 0
+    d_sinks = torch.empty((H,), dtype=torch.float32, device=lse.device)
+    if lse.device.type == "cpu":
+        rows = [sq[:2] for sq in _packed_seqs(cu_seqlens_q.tolist(), cu_seqlens_q.tolist(), total_q, total_q, Sq, Sq)] if packed else None
+        _sink_grad_model(lse, delta, sinks.detach(), d_sinks, rows)
+        return d_sinks
+    a = _capi_sinks.make_sink_grad_args(lse=lse.data_ptr(), delta=delta.data_ptr(), sinks=sinks.data_ptr(), d_sinks=d_sinks.data_ptr(),
+                                  B=B, H=H, Sq=Sq, total_q=total_q, device_id=_device_index(lse.device))
+    if packed:
+        a.cu_seqlens_q = cu_seqlens_q.data_ptr()
+    else:
+        a.lse_stride_b = a.delta_stride_b = H * Sq
+        a.lse_stride_h = a.delta_stride_h = Sq
+    keep = []
+    _attach_workspace(a, _capi_sinks.load().pfa_fa3_sink_grad_workspace_bytes(C.byref(a)), lse.device, keep)
+    stream = torch.cuda.current_stream(lse.device)
+    st = _capi_sinks.load().pfa_fa3_sink_grad(C.byref(a), C.c_void_p(stream.cuda_stream))
+    _raise_status("pfa_fa3_sink_grad", st, null_too=True)
+    _hold(keep, stream)
+    return d_sinks
 
 
 class _FA3Function(torch.autograd.Function):
@@ -479,6 +552,28 @@ class _FA3Function(torch.autograd.Function):
         dq, dk, dv = fa3_backward(q, k, v, out, dout.to(q.dtype), lse, causal=ctx.causal, seqlens_k=ctx.seqlens_k,
                                   key_mask=ctx.key_mask, mask=ctx.mask, softmax_scale=ctx.softmax_scale)
         return dq, dk, dv, None, None, None, None, None, None, None, None
+
+
+class _FA3SinkFunction(torch.autograd.Function):
+    """``_FA3Function`` with attention sinks (no weights): saves the sinks beside q, k, v, o and the LSE.  A sibling, so that the
+    sink-less Function keeps its saved tensors and its launches.  ``sinks.requires_grad`` False: the backward skips the sink-grad launches."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, sinks, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype):
+        out, lse = fa3_forward(q, k, v, causal=causal, seqlens_k=seqlens_k, key_mask=key_mask, mask=mask, softmax_scale=softmax_scale,
+                               return_lse=True, out_dtype=out_dtype, sinks=sinks)
+        o16 = out if out.dtype == q.dtype else out.to(q.dtype)
+        ctx.save_for_backward(q, k, v, o16, lse, sinks)
+        ctx.causal, ctx.seqlens_k, ctx.softmax_scale = causal, seqlens_k, softmax_scale
+        ctx.key_mask, ctx.mask = key_mask, mask
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, sinks = ctx.saved_tensors
+        grads = fa3_backward(q, k, v, out, dout.to(q.dtype), lse, causal=ctx.causal, seqlens_k=ctx.seqlens_k, key_mask=ctx.key_mask,
+                             mask=ctx.mask, softmax_scale=ctx.softmax_scale, sinks=sinks if ctx.needs_input_grad[3] else None)
+        return grads[0], grads[1], grads[2], (grads[3] if len(grads) > 3 else None), None, None, None, None, None, None
 
 
 class _FA3DropoutFunction(torch.autograd.Function):
@@ -519,9 +614,14 @@ def fa3_attention_dropout(q, k, v, p_drop: float, *, causal: bool = False, key_m
 
 def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=None, mask=None,
                   softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
-                  return_weights: bool = False, weights_dtype: Optional[torch.dtype] = None):
+                  return_weights: bool = False, weights_dtype: Optional[torch.dtype] = None, sinks: Optional[torch.Tensor] = None):
     """Autograd-aware attention on ``[B,H,S,D]`` bf16/fp16 operands: forward + backward on the HIP kernels.
-    ``return_weights=True`` -> ``(out, weights)``; the weights are detached (no gradient flows through them)."""
+    ``return_weights=True`` -> ``(out, weights)``; the weights are detached (no gradient flows through them).
+    ``sinks``: fp32 ``[H]`` attention sinks (``fa3_forward``), differentiable: ``sinks.grad`` is ``fa3_sink_grad``'s result."""
+    if sinks is not None:
+        if return_weights:
+            raise ValueError("sinks do not combine with return_weights: the weights pass carries no sink")
+        return _FA3SinkFunction.apply(q, k, v, sinks, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype)
     return _FA3Function.apply(q, k, v, causal, seqlens_k, softmax_scale, key_mask, mask, out_dtype, bool(return_weights), weights_dtype)
 
 
@@ -1665,7 +1765,7 @@ def _varlen_operands(entry: str, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen
     return cu_seqlens_q.numel() - 1, H, Hkv, D, total_q, total_k, max_seqlen_q, max_seqlen_k
 
 
-def _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale) -> None:
+def _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale, snk=None) -> None:
     """One ``pfa_fa3_varlen_fwd`` on q's current stream into the caller's ``out`` (``[total_q, H, D]``-shaped, any row / head strides)
     and ``lse`` (contiguous fp32 ``[H, total_q]`` or None)."""
     B, H, Hkv, D, total_q, total_k, max_q, max_k = geo
@@ -1683,14 +1783,18 @@ def _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causa
         if lse.shape != (H, total_q) or lse.dtype != torch.float32 or not lse.is_contiguous():
             raise ValueError("lse must be contiguous fp32 [H, total_q]")
         a.lse = lse.data_ptr()
-    st = _capi.load().pfa_fa3_varlen_fwd(C.byref(a), C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
-    _raise_status("pfa_fa3_varlen_fwd", st, null_too=True)
+    stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+    if snk is None:
+        _raise_status("pfa_fa3_varlen_fwd", _capi.load().pfa_fa3_varlen_fwd(C.byref(a), stream), null_too=True)
+    else:
+        _raise_status("pfa_fa3_varlen_fwd_sink", _capi_sinks.load().pfa_fa3_varlen_fwd_sink(C.byref(a), C.byref(snk), stream), null_too=True)
 
 
 def fa3_varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
                        max_seqlen_q: int, max_seqlen_k: int, causal: bool = False, softmax_scale: Optional[float] = None,
                        out_dtype: Optional[torch.dtype] = None, return_lse: bool = False,
-                       out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       out: Optional[torch.Tensor] = None,
+                       sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Packed variable-length attention forward (``pfa_fa3_varlen_fwd``): ``fa3_forward`` for a batch of sequences of different
     lengths that is not padded -- the operand layout of flash-attn's ``flash_attn_varlen_func``.
 
@@ -1710,8 +1814,14 @@ def fa3_varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, cu_
     8-wave kernel in its packed mode (no masks, no ``seqlens_k``, no dropout, no fp32 operands here).  Nothing synchronises with the
     device and nothing is cached: capturable in ``torch.cuda.graph`` and valid while the cu_seqlens contents change between replays.
 
+    ``sinks``: fp32 ``[H]`` attention sinks as in ``fa3_forward`` (``pfa_fa3_varlen_fwd_sink``): a row of a sequence without keys gets
+    O = 0 and LSE = the sink, and the result is bit for bit ``fa3_forward(..., sinks=)`` per sequence.  Device tensors only.
+
     On CPU tensors the same rule runs in plain torch per sequence in fp32 (the executable specification)."""
     geo = _varlen_operands("pfa_fa3_varlen_fwd", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    snk = _sinks_arg(sinks, q.unsqueeze(0).transpose(1, 2))      # (as [1, H, total_q, D]: the helper reads H from dim 1)
+    if snk is not None and q.device.type == "cpu":
+        raise ValueError("sinks need device tensors: the plain-torch model of the packed forward carries no sink")
     _, H, _, D, total_q = geo[:5]
     odt = q.dtype if out_dtype is None else out_dtype
     if out is None:
@@ -1722,7 +1832,7 @@ def fa3_varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, cu_
     if q.device.type == "cpu":
         _varlen_forward_model(q, k, v, out, lse, cu_seqlens_q.tolist(), cu_seqlens_k.tolist(), geo[6], geo[7], causal, _scale(softmax_scale, D))
     else:
-        _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale)
+        _varlen_fwd_launch(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale, snk)
     return out, lse
 
 
@@ -1731,8 +1841,9 @@ def _packed_meets_abi(t: torch.Tensor) -> bool:
     return t.stride(2) == 1 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(0) >= 0
 
 
-def _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale) -> None:
-    """One ``pfa_fa3_varlen_bwd`` (two launches) on q's current stream into the caller's ``dq`` / ``dk`` / ``dv``."""
+def _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale) -> torch.Tensor:
+    """One ``pfa_fa3_varlen_bwd`` (two launches) on q's current stream into the caller's ``dq`` / ``dk`` / ``dv``; returns the ``delta``
+    scratch ``[H, total_q]`` the launches leave."""
     B, H, Hkv, D, total_q, total_k, max_q, max_k = geo
     if D not in SUPPORTED_HEAD_DIMS:
         raise ValueError(f"head_dim {D}: the packed kernels exist for {SUPPORTED_HEAD_DIMS}")
@@ -1749,11 +1860,12 @@ def _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seq
     st = _capi.load().pfa_fa3_varlen_bwd(C.byref(a), C.c_void_p(stream.cuda_stream))
     _raise_status("pfa_fa3_varlen_bwd", st, null_too=True)
     delta.record_stream(stream)      # made here: must outlive the enqueued kernels
+    return delta
 
 
 def fa3_varlen_backward(q, k, v, out, dout, lse, *, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int,
                         max_seqlen_k: int, causal: bool = False, softmax_scale: Optional[float] = None,
-                        grad_dtype: Optional[torch.dtype] = None):
+                        grad_dtype: Optional[torch.dtype] = None, sinks: Optional[torch.Tensor] = None):
     """dQ, dK, dV of ``fa3_varlen_forward`` (``pfa_fa3_varlen_bwd``).  q / out / dout ``[total_q, H, D]``, k / v ``[total_k, Hkv, D]``,
     ``lse`` the forward's fp32 ``[H, total_q]``; ``out`` and ``dout`` in the operand dtype.  Returns ``(dq [total_q, H, D], dk, dv
     [total_k, Hkv, D])`` in ``grad_dtype`` (the input dtype by default, or fp32); grouped-query heads are summed inside the dK/dV kernel.
@@ -1761,8 +1873,13 @@ def fa3_varlen_backward(q, k, v, out, dout, lse, *, cu_seqlens_q: torch.Tensor, 
     without rows, under causal the keys ``j >= Sq_b`` -- get exact zeros); rows no sequence covers are left as ``torch.empty`` made them.
     ``causal`` is the dense top-left rule, as in ``fa3_varlen_forward``.  The gradients are bit for bit those of ``fa3_backward`` per
     sequence; no atomics.  A ``dout`` that fails the alignment or stride rules is copied, as ``fa3_backward`` does; nothing
-    synchronises with the device.  On CPU tensors: the plain-torch model, fp32 per sequence."""
+    synchronises with the device.  On CPU tensors: the plain-torch model, fp32 per sequence.
+
+    ``sinks``: the forward's sinks (device tensors only); the packed backward runs unchanged, ``fa3_sink_grad`` follows on its ``delta``, and
+    the result is ``(dq, dk, dv, d_sinks)``."""
     geo = _varlen_operands("pfa_fa3_varlen_bwd", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    if _sinks_arg(sinks, q.unsqueeze(0).transpose(1, 2)) is not None and q.device.type == "cpu":
+        raise ValueError("sinks need device tensors: the plain-torch model of the packed backward carries no sink")
     _, H, Hkv, D, total_q, total_k = geo[:6]
     if out.shape != q.shape or dout.shape != q.shape or out.dtype != q.dtype or dout.dtype != q.dtype:
         raise ValueError("out and dout must be [total_q, H, D] tensors of the operand dtype")
@@ -1780,7 +1897,9 @@ def fa3_varlen_backward(q, k, v, out, dout, lse, *, cu_seqlens_q: torch.Tensor, 
         return dq, dk, dv
     if not _packed_meets_abi(dout):
         dout = dout.contiguous()
-    _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale)
+    delta = _varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, cu_seqlens_q, cu_seqlens_k, geo, causal, softmax_scale)
+    if sinks is not None:
+        return dq, dk, dv, fa3_sink_grad(lse, delta, sinks, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=geo[6])
     return dq, dk, dv
 
 
@@ -1806,8 +1925,32 @@ class _FA3VarlenFunction(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None, None
 
 
+class _FA3VarlenSinkFunction(torch.autograd.Function):
+    """``_FA3VarlenFunction`` with attention sinks: a sibling that also saves the sinks (see ``_FA3SinkFunction``)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, out_dtype):
+        out, lse = fa3_varlen_forward(q, k, v, cu_seqlens_q=cu_seqlens_q, cu_seqlens_k=cu_seqlens_k, max_seqlen_q=max_seqlen_q,
+                                      max_seqlen_k=max_seqlen_k, causal=causal, softmax_scale=softmax_scale, out_dtype=out_dtype,
+                                      return_lse=True, sinks=sinks)
+        o16 = out if out.dtype == q.dtype else out.to(q.dtype)
+        ctx.save_for_backward(q, k, v, o16, lse, cu_seqlens_q, cu_seqlens_k, sinks)
+        ctx.meta = (max_seqlen_q, max_seqlen_k, causal, softmax_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k, sinks = ctx.saved_tensors
+        max_q, max_k, causal, softmax_scale = ctx.meta
+        grads = fa3_varlen_backward(q, k, v, out, dout.to(q.dtype), lse, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k, max_seqlen_q=max_q,
+                                    max_seqlen_k=max_k, causal=causal, softmax_scale=softmax_scale,
+                                    sinks=sinks if ctx.needs_input_grad[3] else None)
+        return grads[0], grads[1], grads[2], (grads[3] if len(grads) > 3 else None), None, None, None, None, None, None, None
+
+
 def fa3_varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p: float = 0.0,
-                         softmax_scale: Optional[float] = None, causal: bool = False, *, out_dtype: Optional[torch.dtype] = None):
+                         softmax_scale: Optional[float] = None, causal: bool = False, *, out_dtype: Optional[torch.dtype] = None,
+                         sinks: Optional[torch.Tensor] = None):
     """Autograd-aware packed variable-length attention, arguments in the order of flash-attn's ``flash_attn_varlen_func``: q
     ``[total_q, H, D]``, k / v ``[total_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]``, host ints ``max_seqlen_*``.  Forward
     and backward on the packed HIP kernels (``fa3_varlen_forward`` / ``fa3_varlen_backward``: their conventions hold, the dense
@@ -1815,5 +1958,8 @@ def fa3_varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     Rows no sequence covers get whatever ``torch.empty`` left, in the output and in the gradients (``cu[B] == total`` leaves none)."""
     if dropout_p:
         raise NotImplementedError("attention dropout is not implemented on the packed path (dropout_p must be 0)")
+    if sinks is not None:      # fp32 [H] attention sinks (fa3_varlen_forward), differentiable
+        return _FA3VarlenSinkFunction.apply(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, operator.index(max_seqlen_q),
+                                            operator.index(max_seqlen_k), bool(causal), softmax_scale, out_dtype)
     return _FA3VarlenFunction.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, operator.index(max_seqlen_q), operator.index(max_seqlen_k),
                                     bool(causal), softmax_scale, out_dtype)
