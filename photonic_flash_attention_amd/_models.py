@@ -154,6 +154,38 @@ def _rope_append_model(k_new, v_new, k_cache, v_cache, cos, sin, lens, cu, max_s
                          block_table[b:b + 1] if paged else None)
 
 
+def _rotary_model(xs, outs, cos, sin, interleaved, conjugate, cu, max_seqlen, offsets, position_ids) -> None:
+    """``pfa_rotary``'s rule in plain torch, every clamp included: the executable specification, and what ``apply_rotary`` runs on CPU
+    tensors.  ``xs``: one or two tensors over the same rows, ``[total, H, D]`` with ``cu`` (a host list), else ``[B, H, S, D]``;
+    ``outs``: where each goes, the tensor itself for the in-place call, which touches nothing at and past ``rot_dim``.  ``offsets``: a
+    host list or None; ``position_ids``: int32 ``[total]`` / ``[B, S]`` or None.  The conjugate rotation is the rule at ``-sin``."""
+    max_pos, R = cos.shape[0], 2 * cos.shape[1]
+    if conjugate:
+        sin = -sin
+    src = [x.clone() for x in xs]                                              # an output may be its input
+    packed = cu is not None
+    total = xs[0].shape[0]
+    for b in range(len(cu) - 1 if packed else xs[0].shape[0]):
+        s_b, rows = 0, max_seqlen
+        if packed:
+            s_b = min(max(cu[b], 0), total)
+            rows = min(min(max(cu[b + 1], s_b), total) - s_b, max_seqlen)
+        if rows < 1:
+            continue
+        if position_ids is not None:
+            pos = (position_ids[s_b:s_b + rows] if packed else position_ids[b, :rows]).to(torch.int64)
+        else:
+            pos = torch.arange(rows, dtype=torch.int64) + (0 if offsets is None else offsets[b])
+        pos = pos.clamp(0, max_pos - 1)
+        c, s = cos[pos], sin[pos]
+        for x, o in zip(src, outs):
+            cut = R if any(o is t for t in xs) else x.shape[-1]
+            if packed:
+                o[s_b:s_b + rows, :, :cut] = _rope_rotate(x[s_b:s_b + rows], c, s, interleaved)[..., :cut]
+            else:
+                o[b, :, :rows, :cut] = _rope_rotate(x[b, :, :rows].transpose(0, 1), c, s, interleaved).transpose(0, 1)[..., :cut]
+
+
 def _attn_merge_model(outs, lses, out, lse_out) -> None:
     """``pfa_attn_merge``'s rule in plain fp32 torch ops, in part order: the executable specification, and what ``attn_merge`` runs on
     CPU tensors.  A part whose LSE is -inf is selected away, never multiplied in; a NaN LSE makes the row NaN."""

@@ -43,6 +43,9 @@ class FlashAttention3(nn.Module):
         dtype: Optional[torch.dtype] = None,
         fp32_attention: str = "exact",
         attention_sinks: bool = False,
+        rotary: bool = False,
+        rotary_base: float = 10000.0,
+        rotary_max_position: int = 4096,
     ):
         """``fp32_attention`` (not in the reference; only matters for fp32 modules, the reference's default dtype): "exact" runs the
         attention core of an fp32 module in fp32 on the vector ALUs -- the reference's numbers to ~1e-6, at a few TFLOP/s -- and is
@@ -53,8 +56,17 @@ class FlashAttention3(nn.Module):
         ``attention_sinks`` (not in the reference): the module holds ``sinks``, one learned fp32 value per head (initially 0: an extra
         key of weight 1 and a zero value row), in every row's softmax denominator -- the GPT-OSS-style layer (``ops.fa3_attention(...,
         sinks=)``).  The attention then runs on the 16-bit kernels; no attention dropout, no ``need_weights``.  False
-        (the default): parameters, state dict and launches are the module's without the option."""
+        (the default): parameters, state dict and launches are the module's without the option.
+
+        ``rotary`` (not in the reference): q and k are rotated between the projection and the attention by the position of their row --
+        the Llama / Qwen / GPT-OSS layer (``ops.fa3_attention(..., rotary_cos=, rotary_sin=)``) -- over the whole head dim,
+        in the ``rotate_half`` pairing, with the tables of ``ops.rotary_tables(rotary_max_position, head_dim, rotary_base)`` held as
+        non-persistent buffers: the state dict is the module's without the option.  Rows at and past ``rotary_max_position`` rotate as
+        the last table row.  The attention then runs on the 16-bit kernels; no attention dropout, no ``need_weights``.  False (the
+        default): constructor, state dict and launches are what they were."""
         super().__init__()
+        if rotary and dropout > 0:
+            raise ValueError("rotary does not combine with attention dropout")
         if attention_sinks and dropout > 0:
             raise ValueError("attention_sinks does not combine with attention dropout")
         if fp32_attention not in ("exact", "bf16"):
@@ -71,6 +83,14 @@ class FlashAttention3(nn.Module):
         self.out_proj = nn.Linear(embed_dim, embed_dim, bias=bias, device=device, dtype=dtype)
         self.dropout_module = nn.Dropout(dropout) if dropout > 0 else None
         self.sinks = nn.Parameter(torch.zeros(num_heads, dtype=torch.float32, device=device)) if attention_sinks else None
+
+        self.rotary, self.rotary_base, self.rotary_max_position = bool(rotary), float(rotary_base), int(rotary_max_position)
+        if self.rotary:
+            if self.head_dim % 16 or not 16 <= self.head_dim <= 256:
+                raise ValueError(f"rotary needs a head dim that is a multiple of 16 in 16 .. 256, got {self.head_dim}")
+            cos, sin = ops.rotary_tables(self.rotary_max_position, self.head_dim, self.rotary_base, device=device)
+            self.register_buffer("rotary_cos", cos, persistent=False)
+            self.register_buffer("rotary_sin", sin, persistent=False)
 
         # fp32 modules with fp32_attention="bf16", and every fp32 module under autograd, compute attention in this dtype
         self.compute_dtype = torch.bfloat16
@@ -153,6 +173,19 @@ class FlashAttention3(nn.Module):
         # 2-D [B,Sk] masks take the cheap key-mask path (:166-167); 3-D / 4-D masks the general one (:168,:235)
         key_mask = attention_mask if (attention_mask is not None and attention_mask.dim() == 2) else None
         mask = attention_mask if (attention_mask is not None and attention_mask.dim() != 2) else None
+        if self.rotary:
+            if need_weights:
+                raise NotImplementedError("need_weights together with rotary is not supported")
+            if q.dtype == torch.float32 and self.fp32_attention == "exact":
+                raise ValueError('rotary runs on the 16-bit kernels: build an fp32 module with fp32_attention="bf16"')
+            if self.rotary_cos.dtype != torch.float32:      # module.to(bfloat16) narrowed the buffers with the weights: the tables stay fp32
+                self.rotary_cos, self.rotary_sin = ops.rotary_tables(self.rotary_max_position, self.head_dim, self.rotary_base,
+                                                                     device=self.rotary_cos.device)
+            cd = self.compute_dtype if q.dtype == torch.float32 else q.dtype
+            out = ops.fa3_attention(q.to(cd), k.to(cd), v.to(cd), causal=is_causal, key_mask=key_mask, mask=mask, softmax_scale=self.scaling,
+                                    out_dtype=q.dtype, sinks=None if self.sinks is None else self.sinks.float(),
+                                    rotary_cos=self.rotary_cos, rotary_sin=self.rotary_sin)
+            return out, None
         if self.sinks is not None:
             if need_weights:
                 raise NotImplementedError("need_weights together with attention_sinks is not supported")

@@ -147,6 +147,9 @@ class HybridFlashAttention(nn.Module):
         enable_scaling: bool = True,
         max_concurrent_requests: int = 4,
         attention_sinks: bool = False,
+        rotary: bool = False,
+        rotary_base: float = 10000.0,
+        rotary_max_position: int = 4096,
     ):
         super().__init__()
         self.embed_dim = embed_dim
@@ -159,7 +162,8 @@ class HybridFlashAttention(nn.Module):
 
         self.gpu_attention = FlashAttention3(
             embed_dim=embed_dim, num_heads=num_heads, dropout=dropout, bias=bias,
-            device=device if device != "auto" else None, dtype=dtype, attention_sinks=attention_sinks)
+            device=device if device != "auto" else None, dtype=dtype, attention_sinks=attention_sinks,
+            rotary=rotary, rotary_base=rotary_base, rotary_max_position=rotary_max_position)
         self.photonic_attention = None   # out of scope (north_star): never constructed
 
         self.router = AdaptiveRouter()

@@ -20,9 +20,9 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_sinks
+from . import _capi, _capi_rotary, _capi_sinks
 from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _page_copy_model,      # noqa: F401
-                      _rope_append_model, _rope_rotate, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
+                      _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
 
@@ -614,10 +614,21 @@ def fa3_attention_dropout(q, k, v, p_drop: float, *, causal: bool = False, key_m
 
 def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=None, mask=None,
                   softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
-                  return_weights: bool = False, weights_dtype: Optional[torch.dtype] = None, sinks: Optional[torch.Tensor] = None):
+                  return_weights: bool = False, weights_dtype: Optional[torch.dtype] = None, sinks: Optional[torch.Tensor] = None,
+                  rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+                  pos_offsets: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None):
     """Autograd-aware attention on ``[B,H,S,D]`` bf16/fp16 operands: forward + backward on the HIP kernels.
     ``return_weights=True`` -> ``(out, weights)``; the weights are detached (no gradient flows through them).
-    ``sinks``: fp32 ``[H]`` attention sinks (``fa3_forward``), differentiable: ``sinks.grad`` is ``fa3_sink_grad``'s result."""
+    ``sinks``: fp32 ``[H]`` attention sinks (``fa3_forward``), differentiable: ``sinks.grad`` is ``fa3_sink_grad``'s result.
+    ``rotary_cos`` / ``rotary_sin`` (with ``rotary_interleaved``, ``pos_offsets``, ``position_ids``): q and k are rotated first by
+    ``apply_rotary`` -- one launch, two where ``Sq != Sk`` -- and the call is the one without them on the rotated operands, in both
+    directions: the backward's dq and dk go through the conjugate launch."""
+    rot = _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, position_ids)
+    if rot is not None:
+        if q.dim() == 4 and k.dim() == 4 and q.shape[2] != k.shape[2]:
+            q, k = apply_rotary(q, **rot), apply_rotary(k, **rot)
+        else:
+            q, k = apply_rotary(q, k, **rot)
     if sinks is not None:
         if return_weights:
             raise ValueError("sinks do not combine with return_weights: the weights pass carries no sink")
@@ -1166,6 +1177,198 @@ def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
         _set_view(a, "q_out", q_out, "sh" if ragged else "bsh")
     _append_launch("pfa_rope_append", a, cache_seqlens, k_new, B)
     return q_out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Rotary embedding for the training calls (include/pfa_hip_rotary.h, pfa_rotary): flash-attn's apply_rotary_emb
+
+class _RotaryGeo(NamedTuple):
+    packed: bool
+    B: int
+    S: int            # rows of a sequence; packed: max_seqlen
+    total: int        # packed rows (0 when dense)
+    D: int
+    rot_dim: int
+    max_pos: int
+
+
+def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids) -> _RotaryGeo:
+    """What ``apply_rotary`` checks about its operands, before anything is enqueued."""
+    _fp32_tables(rotary_cos, rotary_sin)
+    if not isinstance(q, torch.Tensor) or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("apply_rotary takes bf16 / fp16 operands (fp32 operands are not rotated here)")
+    packed = cu_seqlens is not None
+    if q.dim() != (3 if packed else 4):
+        raise ValueError("q must be [total, H, D] with cu_seqlens, else [B, H, S, D]")
+    D = q.shape[-1]
+    if packed:
+        if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 \
+                or not cu_seqlens.is_contiguous():
+            raise ValueError("cu_seqlens must be a contiguous int32 [B + 1] tensor")
+        B, total, H = cu_seqlens.numel() - 1, q.shape[0], q.shape[1]
+        S = _host_int(max_seqlen)
+        if S is None or total < 1 or not 1 <= S <= total:
+            raise ValueError(f"max_seqlen {max_seqlen!r}: must be a host int in 1 .. {total}, the rows held")
+    else:
+        if max_seqlen is not None:
+            raise ValueError("max_seqlen goes with cu_seqlens")
+        (B, H, S, _), total = q.shape, 0
+    if B < 1 or H < 1 or S < 1:
+        raise ValueError(f"apply_rotary: empty operand {tuple(q.shape)}")
+    if k is not None:
+        if not isinstance(k, torch.Tensor) or k.dtype != q.dtype or k.device != q.device or k.dim() != q.dim() or k.shape[1] < 1:
+            raise ValueError("k must be a tensor of q's dtype, device and rank")
+        same_rows = k.shape[0] == q.shape[0] and k.shape[-1] == D and (packed or k.shape[2] == S)
+        if not same_rows:
+            raise ValueError(f"k {tuple(k.shape)} does not share q's rows and head dim {tuple(q.shape)}: one launch rotates tensors over the "
+                             "same rows; make two calls, one for q and one for k")
+    rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, D)
+    if pos_offsets is not None and position_ids is not None:
+        raise ValueError("pos_offsets and position_ids exclude each other")
+    if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
+                                    or pos_offsets.shape != (B,) or not pos_offsets.is_contiguous()):
+        raise ValueError("pos_offsets must be a contiguous int32 [B] tensor")
+    if position_ids is not None and (not isinstance(position_ids, torch.Tensor) or position_ids.dtype != torch.int32
+                                     or position_ids.shape != ((total,) if packed else (B, S))
+                                     or (packed and not position_ids.is_contiguous())):
+        raise ValueError("position_ids must be an int32 tensor, [B, S] for dense operands and contiguous [total] for packed ones")
+    if any(t is not None and t.device != q.device for t in (rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)):
+        raise ValueError("pfa_rotary needs all its tensors on one device")
+    return _RotaryGeo(packed, B, S, total, D, rot_dim, max_pos)
+
+
+def _rotary_meets_abi(t: torch.Tensor) -> bool:
+    """``pfa_rotary``'s rules for a 16-bit tensor: head dim contiguous, base 16-byte aligned, every other stride a multiple of 8."""
+    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1])
+
+
+def _rotary_out(x: torch.Tensor, packed: bool) -> torch.Tensor:
+    """A fresh output for ``x``, in the layout the attention calls prefer: packed rows contiguous, dense a [B, S, H, D] buffer seen as
+    [B, H, S, D]."""
+    if packed:
+        return torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    B, H, S, D = x.shape
+    return torch.empty((B, S, H, D), dtype=x.dtype, device=x.device).permute(0, 2, 1, 3)
+
+
+def _rotary_call(xs, geo: _RotaryGeo, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids, conjugate, inplace,
+                 outs=None):
+    """One ``pfa_rotary`` over the one or two tensors ``xs`` (checked by ``_rotary_geometry``) on their current stream, or on CPU tensors
+    the plain-torch model.  -> the outputs: fresh tensors (or the caller's ``outs``, of the shapes and dtype of ``xs``), or ``xs``
+    themselves in place."""
+    if outs is not None:
+        outs = list(outs)
+    elif inplace:
+        if not all(_rotary_meets_abi(x) for x in xs):
+            raise ValueError("apply_rotary(inplace=True): the head dim must be contiguous, the base 16-byte aligned and every other stride "
+                             "a multiple of 8 elements")
+        outs = list(xs)
+    else:
+        outs = [_rotary_out(x, geo.packed) for x in xs]
+    if xs[0].device.type == "cpu":
+        _rotary_model(xs, outs, rotary_cos, rotary_sin, bool(interleaved), bool(conjugate),
+                      cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
+        return outs
+    given, xs = xs, [x if _rotary_meets_abi(x) else x.contiguous() for x in xs]
+    flags = (_capi_rotary.PFA_ROTARY_INTERLEAVED if interleaved else 0) | (_capi_rotary.PFA_ROTARY_CONJUGATE if conjugate else 0)
+    a = _capi_rotary.make_rotary_args(flags=flags, cos=rotary_cos.data_ptr(), sin=rotary_sin.data_ptr(), cs_stride=rotary_cos.stride(0),
+                                      B=geo.B, S=geo.S, total=geo.total, H0=xs[0].shape[1], H1=xs[1].shape[1] if len(xs) > 1 else 0, D=geo.D,
+                                      rot_dim=geo.rot_dim, max_pos=geo.max_pos, dtype=_DT[xs[0].dtype], device_id=_device_index(xs[0].device))
+    for pre, x, o in zip(("x0", "x1"), xs, outs):
+        setattr(a, pre, x.data_ptr())
+        setattr(a, pre + "_out", o.data_ptr())
+        for fields, t in ((pre, x), (pre + "o", o)):
+            for axis, st in zip("sh" if geo.packed else "bhs", t.stride()):
+                setattr(a, f"{fields}_stride_{axis}", st)
+    if geo.packed:
+        a.cu_seqlens = cu_seqlens.data_ptr()
+    if pos_offsets is not None:
+        a.pos_offsets = pos_offsets.data_ptr()
+    if position_ids is not None:
+        a.position_ids = position_ids.data_ptr()
+        if not geo.packed:
+            a.pid_stride_b, a.pid_stride_s = position_ids.stride()
+    stream = torch.cuda.current_stream(xs[0].device)
+    _raise_status("pfa_rotary", _capi_rotary.load().pfa_rotary(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
+    _hold([x for x, g in zip(xs, given) if x is not g], stream)      # a copy made above must outlive the launch
+    return outs
+
+
+class _RotaryFunction(torch.autograd.Function):
+    """Differentiable ``apply_rotary``, out of place: saves no activation, only the tables and the position tensors.  The backward is
+    one conjugate launch over the gradients that are asked for, into fresh tensors."""
+
+    @staticmethod
+    def forward(ctx, q, k, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids, conjugate, geo):
+        ctx.save_for_backward(rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
+        ctx.meta = (interleaved, conjugate, geo)
+        outs = _rotary_call([q] if k is None else [q, k], geo, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids,
+                            conjugate, False)
+        return outs[0] if k is None else tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids = ctx.saved_tensors
+        interleaved, conjugate, geo = ctx.meta
+        want = [i for i in range(len(grads)) if ctx.needs_input_grad[i] and grads[i] is not None]
+        res = [None, None]
+        if want:
+            outs = _rotary_call([grads[i] for i in want], geo, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids,
+                                not conjugate, False)
+            for i, o in zip(want, outs):
+                res[i] = o
+        return res[0], res[1], None, None, None, None, None, None, None, None
+
+
+def apply_rotary(q: torch.Tensor, k: Optional[torch.Tensor] = None, *, rotary_cos: torch.Tensor, rotary_sin: torch.Tensor,
+                 rotary_interleaved: bool = False, cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: Optional[int] = None,
+                 pos_offsets: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None, conjugate: bool = False,
+                 inplace: bool = False):
+    """Rotary embedding of training tensors (``pfa_rotary``) -- flash-attn's ``apply_rotary_emb`` -- in ONE launch for q and, when given,
+    k: ``[B, H, S, D]`` and ``[B, Hkv, S, D]`` (any strides with the head dim contiguous, so the views of a fused projection are read in
+    place), or with ``cu_seqlens`` (int32 ``[B + 1]`` on the device) and ``max_seqlen`` (a host int) packed ``[total, H, D]`` and
+    ``[total, Hkv, D]``.  bf16 / fp16, D a multiple of 16 in 16 .. 256.  Returns ``q_out`` or ``(q_out, k_out)``.
+
+    The arithmetic, the tables and the pairing are ``rope_append``'s, bit for bit: rotary_cos / rotary_sin fp32 ``[max_pos, rot_dim / 2]``
+    (``rotary_tables``), rot_dim a multiple of 16 in 16 .. D, the pair ``(x[j], x[j + rot_dim / 2])`` or with ``rotary_interleaved``
+    ``(x[2j], x[2j + 1])``.  Row i of sequence b is rotated at ``clamp(p, 0, max_pos - 1)`` with ``p = position_ids[b, i]`` (int32
+    ``[B, S]``, packed ``[total]``) when given, else ``i + pos_offsets[b]`` (int32 ``[B]``, optional): an out-of-range position gives
+    wrong numbers, never an access outside the tables.  Packed rows no sequence covers, and a sequence's rows past ``max_seqlen``, are
+    neither read nor written.  ``conjugate`` rotates the other way (by ``-sin``).
+
+    Out of place (the default) the elements at and past rot_dim are copied into fresh tensors.  ``inplace=True`` rotates the given
+    tensors, touching nothing at and past rot_dim, and returns them; refused on a tensor that requires grad.
+
+    Differentiable: no activation is saved, only the tables and the position tensors, and the backward is one conjugate launch over
+    both gradients into fresh tensors.  The grid depends on host shapes only: no host synchronisation, capturable, and valid while
+    cu_seqlens, offsets, position_ids, tables and inputs change between replays.  On CPU tensors the same rule runs in plain torch,
+    bit for bit (``_rotary_model``, the executable specification)."""
+    geo = _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids)
+    xs = [q] if k is None else [q, k]
+    needs_grad = torch.is_grad_enabled() and any(x.requires_grad for x in xs)
+    if inplace:
+        if needs_grad:
+            raise ValueError("apply_rotary(inplace=True) on a tensor that requires grad: the backward needs the call out of place")
+        _rotary_call(xs, geo, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens, pos_offsets, position_ids, conjugate, True)
+        return q if k is None else (q, k)
+    if needs_grad:
+        return _RotaryFunction.apply(q, k, rotary_cos, rotary_sin, bool(rotary_interleaved), cu_seqlens, pos_offsets, position_ids,
+                                     bool(conjugate), geo)
+    outs = _rotary_call(xs, geo, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens, pos_offsets, position_ids, conjugate, False)
+    return outs[0] if k is None else tuple(outs)
+
+
+def _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, position_ids):
+    """The rotary keywords of the training attention calls: None without tables (then the other three must be unset), else what
+    ``apply_rotary`` takes."""
+    if rotary_cos is None and rotary_sin is None:
+        if rotary_interleaved or pos_offsets is not None or position_ids is not None:
+            raise ValueError("rotary_interleaved / pos_offsets / position_ids need rotary_cos and rotary_sin")
+        return None
+    if rotary_cos is None or rotary_sin is None:
+        raise ValueError("rotary_cos and rotary_sin go together")
+    return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets,
+                position_ids=position_ids)
 
 
 def _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens):
@@ -1950,14 +2153,26 @@ class _FA3VarlenSinkFunction(torch.autograd.Function):
 
 def fa3_varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p: float = 0.0,
                          softmax_scale: Optional[float] = None, causal: bool = False, *, out_dtype: Optional[torch.dtype] = None,
-                         sinks: Optional[torch.Tensor] = None):
+                         sinks: Optional[torch.Tensor] = None, rotary_cos: Optional[torch.Tensor] = None,
+                         rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+                         pos_offsets: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None):
     """Autograd-aware packed variable-length attention, arguments in the order of flash-attn's ``flash_attn_varlen_func``: q
     ``[total_q, H, D]``, k / v ``[total_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]``, host ints ``max_seqlen_*``.  Forward
     and backward on the packed HIP kernels (``fa3_varlen_forward`` / ``fa3_varlen_backward``: their conventions hold, the dense
     top-left ``causal`` rule among them); returns ``out [total_q, H, D]``.  ``dropout_p`` must be 0: there is no dropout here.
-    Rows no sequence covers get whatever ``torch.empty`` left, in the output and in the gradients (``cu[B] == total`` leaves none)."""
+    Rows no sequence covers get whatever ``torch.empty`` left, in the output and in the gradients (``cu[B] == total`` leaves none).
+    ``rotary_cos`` / ``rotary_sin`` (with ``rotary_interleaved``, ``pos_offsets``, ``position_ids``): q and k are rotated first by
+    ``apply_rotary`` at their row in the sequence -- one launch for packed self-attention (``cu_seqlens_k is cu_seqlens_q``), else one
+    each over their own ``cu_seqlens`` -- and the call is the one without them on the rotated operands, in both directions."""
     if dropout_p:
         raise NotImplementedError("attention dropout is not implemented on the packed path (dropout_p must be 0)")
+    rot = _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, position_ids)
+    if rot is not None:
+        if cu_seqlens_q is cu_seqlens_k and _host_int(max_seqlen_q) == _host_int(max_seqlen_k):
+            q, k = apply_rotary(q, k, cu_seqlens=cu_seqlens_q, max_seqlen=max_seqlen_q, **rot)
+        else:
+            q = apply_rotary(q, cu_seqlens=cu_seqlens_q, max_seqlen=max_seqlen_q, **rot)
+            k = apply_rotary(k, cu_seqlens=cu_seqlens_k, max_seqlen=max_seqlen_k, **rot)
     if sinks is not None:      # fp32 [H] attention sinks (fa3_varlen_forward), differentiable
         return _FA3VarlenSinkFunction.apply(q, k, v, sinks, cu_seqlens_q, cu_seqlens_k, operator.index(max_seqlen_q),
                                             operator.index(max_seqlen_k), bool(causal), softmax_scale, out_dtype)
