@@ -186,6 +186,176 @@ def _rotary_model(xs, outs, cos, sin, interleaved, conjugate, cu, max_seqlen, of
                 o[b, :, :rows, :cut] = _rope_rotate(x[b, :, :rows].transpose(0, 1), c, s, interleaved).transpose(0, 1)[..., :cut]
 
 
+QKNORM_BWD_ROWS = 32      # rows of one sequence a stage-1 workgroup of pfa_qk_norm_bwd walks (csrc/qk_norm_kernel.h)
+_QKNORM_THREADS = 256
+
+
+def _qkn_order(D: int, R: int, interleaved: bool) -> torch.Tensor:
+    """``[D / 16, 2]``: the two 8-element chunks of every 16-element unit of a head -- ``(u, u + R / 16)`` in the rotated region of the
+    half pairing, ``(2u, 2u + 1)`` everywhere else (csrc/rotary_kernel.h)."""
+    ru = R // 16
+    return torch.tensor([(u, u + ru) if (not interleaved and u < ru) else (2 * u, 2 * u + 1) for u in range(D // 16)], dtype=torch.int64)
+
+
+def _qkn_head_sum(p: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """The kernels' sum tree over the head dim of the fp32 products ``p [..., D]`` -> ``[..., 1]``: every 8-element chunk left to
+    right, a unit's two chunk sums in the order of its pair, the D / 16 unit sums by an xor butterfly (masks 1, 2, .. D / 32)."""
+    ch = p.contiguous().reshape(*p.shape[:-1], p.shape[-1] // 8, 8)
+    s = ch[..., 0]
+    for k in range(1, 8):
+        s = s + ch[..., k]
+    lane = s[..., order[:, 0]] + s[..., order[:, 1]]
+    G, m = order.shape[0], 1
+    idx = torch.arange(G)
+    while m < G:
+        lane = lane + lane[..., idx ^ m]
+        m <<= 1
+    return lane[..., :1]
+
+
+def _qkn_scale(w: torch.Tensor, unit_offset: bool) -> torch.Tensor:
+    s = w.to(torch.float32)
+    return 1.0 + s if unit_offset else s
+
+
+def _qkn_r(xf: torch.Tensor, eps: float, order: torch.Tensor) -> torch.Tensor:
+    """``r = 1 / sqrt(mean(x^2) + eps)`` of every head of the fp32 ``xf [..., D]`` -> ``[..., 1]``, as the kernels round it: the IEEE
+    fp32 square root, then the IEEE fp32 divide.  torch's fp32 ``sqrt`` on the CPU comes from a vector math library and is NOT
+    correctly rounded (it misses by one unit in the last place in about one value in 150), so each of the two operations is taken in
+    fp64 and rounded once to fp32 -- which is the correctly rounded fp32 result, for the square root and for the quotient alike,
+    because fp64 carries 53 >= 2 * 24 + 2 bits."""
+    ms = _qkn_head_sum(xf * xf, order) * (1.0 / xf.shape[-1])
+    root = torch.sqrt((ms + torch.tensor(eps, dtype=torch.float32)).to(torch.float64)).to(torch.float32)
+    return (1.0 / root.to(torch.float64)).to(torch.float32)
+
+
+def _qkn_rotate32(n: torch.Tensor, c, s, interleaved: bool) -> torch.Tensor:
+    """``_rope_rotate`` on fp32 rows ``n [rows, heads, D]`` with no narrowing: the three roundings of a pair, elements at and past
+    ``2 * half`` as they are.  ``c`` None: no rotation."""
+    if c is None:
+        return n
+    half = c.shape[-1]
+    R = 2 * half
+    c, s = c[:, None, :], s[:, None, :]
+    n1, n2 = (n[..., 0:R:2], n[..., 1:R:2]) if interleaved else (n[..., :half], n[..., half:R])
+    y1, y2 = n1 * c - n2 * s, n2 * c + n1 * s
+    out = n.clone()
+    if interleaved:
+        out[..., 0:R:2], out[..., 1:R:2] = y1, y2
+    else:
+        out[..., :half], out[..., half:R] = y1, y2
+    return out
+
+
+def _qkn_forward_rows(x, w, eps, unit_offset, c, s, interleaved) -> torch.Tensor:
+    """Rows ``x [rows, heads, D]`` normalised and rotated: ``pfa_qk_norm``'s rule for one tensor of one sequence.  -> a new tensor."""
+    order = _qkn_order(x.shape[-1], 0 if c is None else 2 * c.shape[-1], interleaved)
+    xf = x.to(torch.float32)
+    n = (xf * _qkn_r(xf, eps, order)) * _qkn_scale(w, unit_offset)
+    return _qkn_rotate32(n, c, s, interleaved).to(x.dtype)
+
+
+def _qkn_backward_rows(x, dy, w, eps, unit_offset, c, s, interleaved):
+    """``pfa_qk_norm_bwd``'s rule for rows ``x`` / ``dy [rows, heads, D]`` -> (``dx`` in the dtype, the fp32 terms ``g * xh`` of the
+    weight gradient)."""
+    order = _qkn_order(x.shape[-1], 0 if c is None else 2 * c.shape[-1], interleaved)
+    xf = x.to(torch.float32)
+    r = _qkn_r(xf, eps, order)
+    g = _qkn_rotate32(dy.to(torch.float32), c, None if s is None else -s, interleaved)      # the conjugate: the rule at -sin, exact
+    xh = xf * r
+    a = g * _qkn_scale(w, unit_offset)
+    cc = _qkn_head_sum(a * xh, order) * (1.0 / x.shape[-1])
+    return (r * (a - xh * cc)).to(x.dtype), g * xh
+
+
+def _qkn_sequences(first, cos, sin, cu, max_seqlen, offsets, position_ids):
+    """(b, first packed row, rows, cos rows, sin rows) of every sequence, with ``pfa_rotary``'s clamps; the table rows are None without
+    tables.  ``first``: the first tensor, ``[total, H, D]`` with ``cu`` else ``[B, H, S, D]``."""
+    packed = cu is not None
+    total = first.shape[0]
+    for b in range(len(cu) - 1 if packed else first.shape[0]):
+        s_b, rows = 0, max_seqlen
+        if packed:
+            s_b = min(max(cu[b], 0), total)
+            rows = min(min(max(cu[b + 1], s_b), total) - s_b, max_seqlen)
+        c = s = None
+        if cos is not None and rows >= 1:
+            if position_ids is not None:
+                pos = (position_ids[s_b:s_b + rows] if packed else position_ids[b, :rows]).to(torch.int64)
+            else:
+                pos = torch.arange(rows, dtype=torch.int64) + (0 if offsets is None else offsets[b])
+            pos = pos.clamp(0, cos.shape[0] - 1)
+            c, s = cos[pos], sin[pos]
+        yield b, s_b, rows, c, s
+
+
+def _qk_norm_model(xs, outs, ws, eps, unit_offset, cos, sin, interleaved, cu, max_seqlen, offsets, position_ids) -> None:
+    """``pfa_qk_norm``'s rule in plain torch, every clamp and every rounding included: the executable specification, and what
+    ``qk_norm`` runs on CPU tensors.  ``xs``: one or two tensors over the same rows, ``[total, H, D]`` with ``cu`` (a host list), else
+    ``[B, H, S, D]``; ``outs``: where each goes (the tensor itself in place); ``ws``: their weights ``[D]``; ``cos`` / ``sin`` None:
+    the norm alone.  All arithmetic is fp32 on widened operands, every product and sum an op of its own; the sum over the head dim is
+    ``_qkn_head_sum``'s tree, spelled out in slices and index tables."""
+    src = [x.clone() for x in xs]                                              # an output may be its input
+    packed = cu is not None
+    for b, s_b, rows, c, s in _qkn_sequences(xs[0], cos, sin, cu, max_seqlen, offsets, position_ids):
+        if rows < 1:
+            continue
+        for x, o, w in zip(src, outs, ws):
+            if packed:
+                o[s_b:s_b + rows] = _qkn_forward_rows(x[s_b:s_b + rows], w, eps, unit_offset, c, s, interleaved)
+            else:
+                o[b, :, :rows] = _qkn_forward_rows(x[b, :, :rows].transpose(0, 1), w, eps, unit_offset, c, s, interleaved).transpose(0, 1)
+
+
+def _qk_norm_bwd_model(xs, dys, dxs, ws, dws, eps, unit_offset, cos, sin, interleaved, cu, max_seqlen, offsets, position_ids) -> None:
+    """``pfa_qk_norm_bwd``'s rule in plain torch: ``dxs`` (the dtype) and ``dws`` (fp32 ``[D]``, overwritten) from ``xs``, ``dys`` and
+    the forward's other operands.  The weight gradient is summed in the kernels' order: per tensor and sequence, chunks of
+    ``QKNORM_BWD_ROWS`` rows; inside a chunk the heads in ``[row][head]`` order are dealt to ``256 / (D / 16)`` slots, every slot adds
+    its heads in order, the slots are added in order into the chunk's partial (zeros for a chunk past its sequence); the partials
+    ``k, k + 16, ...`` are added in order for every ``k`` in 0 .. 15 and those 16 sums in order."""
+    packed = cu is not None
+    D = xs[0].shape[-1]
+    slots, groups = _QKNORM_THREADS // (D // 16), 16
+    nrc = -(-max_seqlen // QKNORM_BWD_ROWS)
+    partials = [[] for _ in xs]
+    for b, s_b, rows, c, s in _qkn_sequences(xs[0], cos, sin, cu, max_seqlen, offsets, position_ids):
+        for t, (x, dy, dx, w) in enumerate(zip(xs, dys, dxs, ws)):
+            terms = None
+            if rows >= 1:
+                if packed:
+                    got, terms = _qkn_backward_rows(x[s_b:s_b + rows], dy[s_b:s_b + rows], w, eps, unit_offset, c, s, interleaved)
+                    dx[s_b:s_b + rows] = got
+                else:
+                    got, terms = _qkn_backward_rows(x[b, :, :rows].transpose(0, 1), dy[b, :, :rows].transpose(0, 1), w, eps, unit_offset, c, s,
+                                                    interleaved)
+                    dx[b, :, :rows] = got.transpose(0, 1)
+            for ch in range(nrc):
+                r0 = ch * QKNORM_BWD_ROWS
+                if r0 >= rows:
+                    partials[t].append(torch.zeros(D))
+                    continue
+                heads = terms[r0:r0 + QKNORM_BWD_ROWS].reshape(-1, D)          # [row][head]
+                acc = torch.zeros(slots, D)
+                for at in range(0, heads.shape[0], slots):
+                    step = heads[at:at + slots]
+                    acc[:step.shape[0]] = acc[:step.shape[0]] + step
+                part = acc[0]
+                for q in range(1, slots):
+                    part = part + acc[q]
+                partials[t].append(part)
+    for t, dw in enumerate(dws):
+        sums = []
+        for k in range(groups):
+            v = torch.zeros(D)
+            for part in partials[t][k::groups]:
+                v = v + part
+            sums.append(v)
+        v = sums[0]
+        for other in sums[1:]:
+            v = v + other
+        dw.copy_(v)
+
+
 def _attn_merge_model(outs, lses, out, lse_out) -> None:
     """``pfa_attn_merge``'s rule in plain fp32 torch ops, in part order: the executable specification, and what ``attn_merge`` runs on
     CPU tensors.  A part whose LSE is -inf is selected away, never multiplied in; a NaN LSE makes the row NaN."""

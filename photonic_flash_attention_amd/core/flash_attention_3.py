@@ -30,6 +30,14 @@ from .. import ops
 from ..config import get_config
 
 
+class _HeadNormWeight(nn.Module):
+    """The learned scale of a per-head RMSNorm: ``weight [head_dim]``, ones.  The norm itself runs inside ``ops.qk_norm``."""
+
+    def __init__(self, head_dim: int, device=None, dtype=None):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(head_dim, device=device, dtype=dtype))
+
+
 class FlashAttention3(nn.Module):
     """Electronic ("gpu") attention branch: QKV projection -> HIP flash forward -> out projection."""
 
@@ -46,6 +54,8 @@ class FlashAttention3(nn.Module):
         rotary: bool = False,
         rotary_base: float = 10000.0,
         rotary_max_position: int = 4096,
+        qk_norm: bool = False,
+        qk_norm_eps: float = 1e-6,
     ):
         """``fp32_attention`` (not in the reference; only matters for fp32 modules, the reference's default dtype): "exact" runs the
         attention core of an fp32 module in fp32 on the vector ALUs -- the reference's numbers to ~1e-6, at a few TFLOP/s -- and is
@@ -63,8 +73,16 @@ class FlashAttention3(nn.Module):
         in the ``rotate_half`` pairing, with the tables of ``ops.rotary_tables(rotary_max_position, head_dim, rotary_base)`` held as
         non-persistent buffers: the state dict is the module's without the option.  Rows at and past ``rotary_max_position`` rotate as
         the last table row.  The attention then runs on the 16-bit kernels; no attention dropout, no ``need_weights``.  False (the
-        default): constructor, state dict and launches are what they were."""
+        default): constructor, state dict and launches are what they were.
+
+        ``qk_norm`` (not in the reference): every head of q and k is RMS-normalised over the head dim between the projection and the
+        rotation -- the Qwen3 / OLMo-2-style layer (``ops.fa3_attention(..., q_norm_weight=, k_norm_weight=)``) -- with the
+        learned ``q_norm.weight`` and ``k_norm.weight`` (``[head_dim]``, initially ones) and ``qk_norm_eps``; with ``rotary`` the norm
+        and the rotation are one launch.  The head dim must be 64 or 128.  It refuses where ``rotary`` refuses: attention dropout,
+        ``need_weights``, an exact-fp32 module.  False (the default): parameters, state dict and launches are what they were."""
         super().__init__()
+        if qk_norm and dropout > 0:
+            raise ValueError("qk_norm does not combine with attention dropout")
         if rotary and dropout > 0:
             raise ValueError("rotary does not combine with attention dropout")
         if attention_sinks and dropout > 0:
@@ -91,6 +109,13 @@ class FlashAttention3(nn.Module):
             cos, sin = ops.rotary_tables(self.rotary_max_position, self.head_dim, self.rotary_base, device=device)
             self.register_buffer("rotary_cos", cos, persistent=False)
             self.register_buffer("rotary_sin", sin, persistent=False)
+
+        self.qk_norm, self.qk_norm_eps = bool(qk_norm), float(qk_norm_eps)
+        if self.qk_norm:
+            if self.head_dim not in (64, 128):
+                raise ValueError(f"qk_norm needs a head dim of 64 or 128, got {self.head_dim}")
+            self.q_norm = _HeadNormWeight(self.head_dim, device, dtype)
+            self.k_norm = _HeadNormWeight(self.head_dim, device, dtype)
 
         # fp32 modules with fp32_attention="bf16", and every fp32 module under autograd, compute attention in this dtype
         self.compute_dtype = torch.bfloat16
@@ -173,18 +198,22 @@ class FlashAttention3(nn.Module):
         # 2-D [B,Sk] masks take the cheap key-mask path (:166-167); 3-D / 4-D masks the general one (:168,:235)
         key_mask = attention_mask if (attention_mask is not None and attention_mask.dim() == 2) else None
         mask = attention_mask if (attention_mask is not None and attention_mask.dim() != 2) else None
-        if self.rotary:
+        if self.rotary or self.qk_norm:
+            what = "rotary" if self.rotary else "qk_norm"
             if need_weights:
-                raise NotImplementedError("need_weights together with rotary is not supported")
+                raise NotImplementedError(f"need_weights together with {what} is not supported")
             if q.dtype == torch.float32 and self.fp32_attention == "exact":
-                raise ValueError('rotary runs on the 16-bit kernels: build an fp32 module with fp32_attention="bf16"')
-            if self.rotary_cos.dtype != torch.float32:      # module.to(bfloat16) narrowed the buffers with the weights: the tables stay fp32
+                raise ValueError(f'{what} runs on the 16-bit kernels: build an fp32 module with fp32_attention="bf16"')
+            if self.rotary and self.rotary_cos.dtype != torch.float32:      # module.to(bfloat16) narrowed the buffers with the weights: the tables stay fp32
                 self.rotary_cos, self.rotary_sin = ops.rotary_tables(self.rotary_max_position, self.head_dim, self.rotary_base,
                                                                      device=self.rotary_cos.device)
             cd = self.compute_dtype if q.dtype == torch.float32 else q.dtype
+            extra = dict(rotary_cos=self.rotary_cos, rotary_sin=self.rotary_sin) if self.rotary else {}
+            if self.qk_norm:      # fp32 weights or the compute dtype's: what the kernel takes
+                wq, wk = (w if w.dtype in (torch.float32, cd) else w.to(cd) for w in (self.q_norm.weight, self.k_norm.weight))
+                extra.update(q_norm_weight=wq, k_norm_weight=wk, qk_norm_eps=self.qk_norm_eps)
             out = ops.fa3_attention(q.to(cd), k.to(cd), v.to(cd), causal=is_causal, key_mask=key_mask, mask=mask, softmax_scale=self.scaling,
-                                    out_dtype=q.dtype, sinks=None if self.sinks is None else self.sinks.float(),
-                                    rotary_cos=self.rotary_cos, rotary_sin=self.rotary_sin)
+                                    out_dtype=q.dtype, sinks=None if self.sinks is None else self.sinks.float(), **extra)
             return out, None
         if self.sinks is not None:
             if need_weights:

@@ -150,6 +150,8 @@ class HybridFlashAttention(nn.Module):
         rotary: bool = False,
         rotary_base: float = 10000.0,
         rotary_max_position: int = 4096,
+        qk_norm: bool = False,
+        qk_norm_eps: float = 1e-6,
     ):
         super().__init__()
         self.embed_dim = embed_dim
@@ -163,7 +165,7 @@ class HybridFlashAttention(nn.Module):
         self.gpu_attention = FlashAttention3(
             embed_dim=embed_dim, num_heads=num_heads, dropout=dropout, bias=bias,
             device=device if device != "auto" else None, dtype=dtype, attention_sinks=attention_sinks,
-            rotary=rotary, rotary_base=rotary_base, rotary_max_position=rotary_max_position)
+            rotary=rotary, rotary_base=rotary_base, rotary_max_position=rotary_max_position, qk_norm=qk_norm, qk_norm_eps=qk_norm_eps)
         self.photonic_attention = None   # out of scope (north_star): never constructed
 
         self.router = AdaptiveRouter()

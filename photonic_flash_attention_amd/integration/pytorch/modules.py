@@ -59,7 +59,7 @@ class PhotonicFlashAttention(nn.Module):
     def __init__(self, embed_dim: int, num_heads: int, dropout: float = 0.0, bias: bool = True,
                  photonic_threshold: Optional[int] = None, device: Union[str, torch.device] = "auto",
                  dtype: Optional[torch.dtype] = None, attention_sinks: bool = False, rotary: bool = False,
-                 rotary_base: float = 10000.0, rotary_max_position: int = 4096):
+                 rotary_base: float = 10000.0, rotary_max_position: int = 4096, qk_norm: bool = False, qk_norm_eps: float = 1e-6):
         super().__init__()
         if embed_dim % num_heads:
             raise AssertionError("embed_dim must be divisible by num_heads")
@@ -71,7 +71,8 @@ class PhotonicFlashAttention(nn.Module):
         self.gpu_attention = FlashAttention3(embed_dim=embed_dim, num_heads=num_heads, dropout=dropout, bias=bias,
                                              device=None if device == "auto" else device, dtype=dtype,
                                              attention_sinks=attention_sinks,      # gpu_attention.sinks, fp32 [num_heads]
-                                             rotary=rotary, rotary_base=rotary_base, rotary_max_position=rotary_max_position)
+                                             rotary=rotary, rotary_base=rotary_base, rotary_max_position=rotary_max_position,
+                                             qk_norm=qk_norm, qk_norm_eps=qk_norm_eps)      # gpu_attention.{q,k}_norm.weight
         self.photonic_attention = None                      # out of scope (north_star): never built
         self.photonic_available = is_photonic_available()   # False on an MI355X box
         self.last_device_used, self.last_latency_ms, self.last_energy_mj = "gpu", 0.0, 0.0
@@ -126,14 +127,15 @@ class PhotonicMultiHeadAttention(PhotonicFlashAttention):
                  add_bias_kv: bool = False, add_zero_attn: bool = False, kdim: Optional[int] = None,
                  vdim: Optional[int] = None, batch_first: bool = False, photonic_threshold: Optional[int] = None,
                  device: Union[str, torch.device] = "auto", dtype: Optional[torch.dtype] = None, attention_sinks: bool = False,
-                 rotary: bool = False, rotary_base: float = 10000.0, rotary_max_position: int = 4096):
+                 rotary: bool = False, rotary_base: float = 10000.0, rotary_max_position: int = 4096, qk_norm: bool = False,
+                 qk_norm_eps: float = 1e-6):
         if add_bias_kv or add_zero_attn:
             raise NotImplementedError(self._UNSUPPORTED.format("add_bias_kv and add_zero_attn"))
         if kdim is not None or vdim is not None:
             raise NotImplementedError(self._UNSUPPORTED.format("Different key/value dimensions"))
         super().__init__(embed_dim, num_heads, dropout=dropout, bias=bias, photonic_threshold=photonic_threshold,
                          device=device, dtype=dtype, attention_sinks=attention_sinks, rotary=rotary, rotary_base=rotary_base,
-                         rotary_max_position=rotary_max_position)
+                         rotary_max_position=rotary_max_position, qk_norm=qk_norm, qk_norm_eps=qk_norm_eps)
         self.batch_first = batch_first
 
     def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,

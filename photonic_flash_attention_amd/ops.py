@@ -14,15 +14,16 @@ No fallback lives here: unsupported arguments raise ``ValueError`` (pre-launch
 from __future__ import annotations
 
 import ctypes as C
+import math
 import operator
 import threading
 from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_rotary, _capi_sinks
+from . import _capi, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
 from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _page_copy_model,      # noqa: F401
-                      _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
+                      _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
 
@@ -615,6 +616,8 @@ def fa3_attention_dropout(q, k, v, p_drop: float, *, causal: bool = False, key_m
 def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=None, mask=None,
                   softmax_scale: Optional[float] = None, out_dtype: Optional[torch.dtype] = None,
                   return_weights: bool = False, weights_dtype: Optional[torch.dtype] = None, sinks: Optional[torch.Tensor] = None,
+                  q_norm_weight: Optional[torch.Tensor] = None, k_norm_weight: Optional[torch.Tensor] = None, qk_norm_eps: float = 1e-6,
+                  qk_norm_unit_offset: bool = False,
                   rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                   pos_offsets: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None):
     """Autograd-aware attention on ``[B,H,S,D]`` bf16/fp16 operands: forward + backward on the HIP kernels.
@@ -622,9 +625,19 @@ def fa3_attention(q, k, v, *, causal: bool = False, seqlens_k=None, key_mask=Non
     ``sinks``: fp32 ``[H]`` attention sinks (``fa3_forward``), differentiable: ``sinks.grad`` is ``fa3_sink_grad``'s result.
     ``rotary_cos`` / ``rotary_sin`` (with ``rotary_interleaved``, ``pos_offsets``, ``position_ids``): q and k are rotated first by
     ``apply_rotary`` -- one launch, two where ``Sq != Sk`` -- and the call is the one without them on the rotated operands, in both
-    directions: the backward's dq and dk go through the conjugate launch."""
+    directions: the backward's dq and dk go through the conjugate launch.
+    ``q_norm_weight`` / ``k_norm_weight`` (with ``qk_norm_eps``, ``qk_norm_unit_offset``): ``qk_norm`` takes the place of the
+    ``apply_rotary`` step -- the norm of every head of q and k, and the rotation when tables are given, in the same launch (two where
+    ``Sq != Sk``) -- and the call is the one without them on its outputs; the weights' gradients come from ``pfa_qk_norm_bwd``."""
     rot = _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, position_ids)
-    if rot is not None:
+    qkn = _train_qk_norm_kw(q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset)
+    if qkn is not None:
+        qkn.update(rot or {})
+        if q.dim() == 4 and k.dim() == 4 and q.shape[2] != k.shape[2]:
+            q, k = qk_norm(q, q_weight=q_norm_weight, **qkn), qk_norm(k, q_weight=k_norm_weight, **qkn)
+        else:
+            q, k = qk_norm(q, k, q_weight=q_norm_weight, k_weight=k_norm_weight, **qkn)
+    elif rot is not None:
         if q.dim() == 4 and k.dim() == 4 and q.shape[2] != k.shape[2]:
             q, k = apply_rotary(q, **rot), apply_rotary(k, **rot)
         else:
@@ -1192,11 +1205,13 @@ class _RotaryGeo(NamedTuple):
     max_pos: int
 
 
-def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids) -> _RotaryGeo:
-    """What ``apply_rotary`` checks about its operands, before anything is enqueued."""
-    _fp32_tables(rotary_cos, rotary_sin)
+def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids, who: str = "apply_rotary") -> _RotaryGeo:
+    """What ``apply_rotary`` checks about its operands, before anything is enqueued.  ``who``: the caller the messages name; ``qk_norm``
+    passes no tables for the norm alone, and ``rot_dim`` and ``max_pos`` are then 0."""
+    if rotary_cos is not None:
+        _fp32_tables(rotary_cos, rotary_sin)
     if not isinstance(q, torch.Tensor) or q.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("apply_rotary takes bf16 / fp16 operands (fp32 operands are not rotated here)")
+        raise ValueError(f"{who} takes bf16 / fp16 operands (fp32 operands are not rotated here)")
     packed = cu_seqlens is not None
     if q.dim() != (3 if packed else 4):
         raise ValueError("q must be [total, H, D] with cu_seqlens, else [B, H, S, D]")
@@ -1214,7 +1229,7 @@ def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_o
             raise ValueError("max_seqlen goes with cu_seqlens")
         (B, H, S, _), total = q.shape, 0
     if B < 1 or H < 1 or S < 1:
-        raise ValueError(f"apply_rotary: empty operand {tuple(q.shape)}")
+        raise ValueError(f"{who}: empty operand {tuple(q.shape)}")
     if k is not None:
         if not isinstance(k, torch.Tensor) or k.dtype != q.dtype or k.device != q.device or k.dim() != q.dim() or k.shape[1] < 1:
             raise ValueError("k must be a tensor of q's dtype, device and rank")
@@ -1222,7 +1237,7 @@ def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_o
         if not same_rows:
             raise ValueError(f"k {tuple(k.shape)} does not share q's rows and head dim {tuple(q.shape)}: one launch rotates tensors over the "
                              "same rows; make two calls, one for q and one for k")
-    rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, D)
+    rot_dim, max_pos = (0, 0) if rotary_cos is None else _rotary_operands(rotary_cos, rotary_sin, D)
     if pos_offsets is not None and position_ids is not None:
         raise ValueError("pos_offsets and position_ids exclude each other")
     if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
@@ -1233,7 +1248,7 @@ def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_o
                                      or (packed and not position_ids.is_contiguous())):
         raise ValueError("position_ids must be an int32 tensor, [B, S] for dense operands and contiguous [total] for packed ones")
     if any(t is not None and t.device != q.device for t in (rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)):
-        raise ValueError("pfa_rotary needs all its tensors on one device")
+        raise ValueError(f"{'pfa_rotary' if who == 'apply_rotary' else who} needs all its tensors on one device")
     return _RotaryGeo(packed, B, S, total, D, rot_dim, max_pos)
 
 
@@ -1369,6 +1384,204 @@ def _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, po
         raise ValueError("rotary_cos and rotary_sin go together")
     return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets,
                 position_ids=position_ids)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# QK-norm fused with the rotary embedding of the training calls (include/pfa_hip_qk_norm.h, pfa_qk_norm / pfa_qk_norm_bwd)
+
+QKNORM_BWD_ROWS = _models.QKNORM_BWD_ROWS      # rows of one sequence a stage-1 workgroup of the backward walks
+
+
+def _qk_norm_geometry(q, k, q_weight, k_weight, eps, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids) -> _RotaryGeo:
+    """What ``qk_norm`` checks about its operands, before anything is enqueued.  Without tables ``rot_dim`` and ``max_pos`` are 0."""
+    if not isinstance(q, torch.Tensor) or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("qk_norm takes bf16 / fp16 operands (fp32 operands are not normalised here)")
+    D = q.shape[-1]
+    if D not in (64, 128):
+        raise ValueError(f"head dim {D}: qk_norm takes 64 or 128, the attention's head dims")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("rotary_cos and rotary_sin go together")
+    if rotary_cos is None:
+        if pos_offsets is not None or position_ids is not None:
+            raise ValueError("pos_offsets / position_ids need rotary_cos and rotary_sin")
+        geo = _rotary_geometry(q, k, None, None, cu_seqlens, max_seqlen, None, None, who="qk_norm")
+    else:
+        geo = _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids, who="qk_norm")
+    if (k is None) != (k_weight is None):
+        raise ValueError("k and k_weight go together")
+    ws = [w for w in (q_weight, k_weight) if w is not None]
+    for w in ws:
+        if not isinstance(w, torch.Tensor) or w.shape != (D,) or w.dtype not in (torch.float32, q.dtype) or w.device != q.device:
+            raise ValueError(f"a norm weight must be a [{D}] tensor on q's device, fp32 or of q's dtype")
+    if len(ws) == 2 and ws[0].dtype != ws[1].dtype:
+        raise ValueError("q_weight and k_weight must share a dtype")
+    eps = float(eps)
+    if not (eps >= 0.0 and math.isfinite(eps)):
+        raise ValueError(f"eps {eps!r}: must be finite and not negative")
+    return geo
+
+
+def _qk_norm_weight(w: torch.Tensor) -> torch.Tensor:
+    return w if w.is_contiguous() and w.data_ptr() % 16 == 0 else w.clone(memory_format=torch.contiguous_format)
+
+
+def _qk_norm_fill(a, geo: _RotaryGeo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids) -> None:
+    """The fields both argument blocks name alike; ``tensors``: (field prefix, stride prefix, tensor) of every 16-bit tensor."""
+    for field, strides, t in tensors:
+        setattr(a, field, t.data_ptr())
+        for axis, st in zip("sh" if geo.packed else "bhs", t.stride()):
+            setattr(a, f"{strides}_stride_{axis}", st)
+    if rotary_cos is not None:
+        a.cos, a.sin, a.cs_stride = rotary_cos.data_ptr(), rotary_sin.data_ptr(), rotary_cos.stride(0)
+    if geo.packed:
+        a.cu_seqlens = cu_seqlens.data_ptr()
+    if pos_offsets is not None:
+        a.pos_offsets = pos_offsets.data_ptr()
+    if position_ids is not None:
+        a.position_ids = position_ids.data_ptr()
+        if not geo.packed:
+            a.pid_stride_b, a.pid_stride_s = position_ids.stride()
+
+
+def _qk_norm_block(make, xs, ws, geo: _RotaryGeo, eps, unit_offset, interleaved):
+    flags = (_capi_qk_norm.PFA_QKNORM_INTERLEAVED if interleaved else 0) | (_capi_qk_norm.PFA_QKNORM_UNIT_OFFSET if unit_offset else 0)
+    return make(flags=flags, eps=eps, B=geo.B, S=geo.S, total=geo.total, H0=xs[0].shape[1], H1=xs[1].shape[1] if len(xs) > 1 else 0, D=geo.D,
+                rot_dim=geo.rot_dim, max_pos=geo.max_pos, dtype=_DT[xs[0].dtype], w_dtype=_DT[ws[0].dtype], device_id=_device_index(xs[0].device))
+
+
+def _qk_norm_call(xs, ws, geo: _RotaryGeo, eps, unit_offset, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids,
+                  inplace, outs=None):
+    """One ``pfa_qk_norm`` over the one or two tensors ``xs`` with the weights ``ws`` (checked by ``_qk_norm_geometry``) on their current
+    stream, or on CPU tensors the plain-torch model.  -> the outputs: fresh tensors (or the caller's ``outs``), or ``xs`` in place."""
+    if outs is not None:
+        outs = list(outs)
+    elif inplace:
+        if not all(_rotary_meets_abi(x) for x in xs):
+            raise ValueError("qk_norm(inplace=True): the head dim must be contiguous, the base 16-byte aligned and every other stride "
+                             "a multiple of 8 elements")
+        outs = list(xs)
+    else:
+        outs = [_rotary_out(x, geo.packed) for x in xs]
+    if xs[0].device.type == "cpu":
+        _qk_norm_model(xs, outs, ws, float(eps), bool(unit_offset), rotary_cos, rotary_sin, bool(interleaved),
+                       cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
+        return outs
+    given, xs = xs, [x if _rotary_meets_abi(x) else x.contiguous() for x in xs]
+    gw, ws = ws, [_qk_norm_weight(w) for w in ws]
+    a = _qk_norm_block(_capi_qk_norm.make_qk_norm_args, xs, ws, geo, eps, unit_offset, interleaved)
+    tensors = [(pre, pre, x) for pre, x in zip(("x0", "x1"), xs)] + [(pre + "_out", pre + "o", o) for pre, o in zip(("x0", "x1"), outs)]
+    _qk_norm_fill(a, geo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
+    for pre, w in zip(("w0", "w1"), ws):
+        setattr(a, pre, w.data_ptr())
+    stream = torch.cuda.current_stream(xs[0].device)
+    _raise_status("pfa_qk_norm", _capi_qk_norm.load().pfa_qk_norm(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
+    _hold([x for x, g in zip(xs + ws, list(given) + list(gw)) if x is not g], stream)      # a copy made above must outlive the launch
+    return outs
+
+
+def _qk_norm_bwd_call(xs, dys, ws, geo: _RotaryGeo, eps, unit_offset, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets,
+                      position_ids, dxs=None):
+    """One ``pfa_qk_norm_bwd`` (two launches) on the current stream, or on CPU tensors the plain-torch model.  -> (``dxs`` in the
+    tensors' dtype -- fresh, or the caller's --, ``dws`` fp32 ``[D]``)."""
+    dxs = [_rotary_out(x, geo.packed) for x in xs] if dxs is None else list(dxs)
+    dws = [torch.empty(geo.D, dtype=torch.float32, device=xs[0].device) for _ in xs]
+    if xs[0].device.type == "cpu":
+        _qk_norm_bwd_model(xs, dys, dxs, ws, dws, float(eps), bool(unit_offset), rotary_cos, rotary_sin, bool(interleaved),
+                           cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
+        return dxs, dws
+    given = list(xs) + list(dys) + list(ws)
+    xs, dys = ([t if _rotary_meets_abi(t) else t.contiguous() for t in ts] for ts in (xs, dys))
+    ws = [_qk_norm_weight(w) for w in ws]
+    a = _qk_norm_block(_capi_qk_norm.make_qk_norm_bwd_args, xs, ws, geo, eps, unit_offset, interleaved)
+    tensors = [(f"{n}{i}", f"{n}{i}", t) for n, ts in (("x", xs), ("dy", dys), ("dx", dxs)) for i, t in enumerate(ts)]
+    _qk_norm_fill(a, geo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
+    for i, (w, dw) in enumerate(zip(ws, dws)):
+        setattr(a, f"w{i}", w.data_ptr())
+        setattr(a, f"dw{i}", dw.data_ptr())
+    nbytes = _capi_qk_norm.bwd_workspace_bytes(a)
+    if nbytes == 0:
+        raise ValueError("pfa_qk_norm_bwd: the shape is refused")
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=xs[0].device)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+    stream = torch.cuda.current_stream(xs[0].device)
+    _raise_status("pfa_qk_norm_bwd", _capi_qk_norm.load().pfa_qk_norm_bwd(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
+    _hold([t for t, g in zip(xs + dys + ws, given) if t is not g] + [workspace], stream)
+    return dxs, dws
+
+
+class _QkNormFunction(torch.autograd.Function):
+    """Differentiable ``qk_norm``, out of place: saves q, k, the weights, the tables and the position tensors -- nothing computed.  The
+    backward is ``pfa_qk_norm_bwd``'s two launches; the weight gradients are cast to the weights' dtype."""
+
+    @staticmethod
+    def forward(ctx, q, k, q_weight, k_weight, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids, meta):
+        ctx.save_for_backward(q, k, q_weight, k_weight, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
+        ctx.meta = meta
+        eps, unit_offset, interleaved, geo = meta
+        xs, ws = ([q], [q_weight]) if k is None else ([q, k], [q_weight, k_weight])
+        outs = _qk_norm_call(xs, ws, geo, eps, unit_offset, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids, False)
+        return outs[0] if k is None else tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        q, k, q_weight, k_weight, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids = ctx.saved_tensors
+        eps, unit_offset, interleaved, geo = ctx.meta
+        xs, ws = ([q], [q_weight]) if k is None else ([q, k], [q_weight, k_weight])
+        dys = [torch.zeros_like(x) if g is None else g.to(x.dtype) for x, g in zip(xs, grads)]      # an output nobody used
+        dxs, dws = _qk_norm_bwd_call(xs, dys, ws, geo, eps, unit_offset, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets,
+                                     position_ids)
+        dws = [dw.to(w.dtype) for dw, w in zip(dws, ws)]
+        if k is None:
+            dxs, dws = dxs + [None], dws + [None]
+        need = ctx.needs_input_grad
+        return (dxs[0] if need[0] else None, dxs[1] if need[1] else None, dws[0] if need[2] else None, dws[1] if need[3] else None,
+                None, None, None, None, None, None)
+
+
+def qk_norm(q: torch.Tensor, k: Optional[torch.Tensor] = None, *, q_weight: torch.Tensor, k_weight: Optional[torch.Tensor] = None,
+            eps: float = 1e-6, unit_offset: bool = False, rotary_cos: Optional[torch.Tensor] = None,
+            rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False, cu_seqlens: Optional[torch.Tensor] = None,
+            max_seqlen: Optional[int] = None, pos_offsets: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+            inplace: bool = False):
+    """QK-norm -- an RMSNorm over the head dim of every head of q and, when given, k (Qwen3's ``q_norm`` / ``k_norm``) -- and, with
+    ``rotary_cos`` / ``rotary_sin``, the rotary embedding behind it, in ONE launch (``pfa_qk_norm``).  Operands, layouts, tables,
+    positions, ``cu_seqlens`` / ``max_seqlen`` and ``inplace`` are ``apply_rotary``'s; the head dim is 64 or 128.  ``q_weight`` /
+    ``k_weight``: ``[D]``, fp32 or of the operands' dtype, shared by the heads of a tensor.  Returns ``q_out`` or ``(q_out, k_out)``.
+
+    Per head, all in fp32 with every product and sum rounded on its own: ``r = 1 / sqrt(sum(x^2) / D + eps)`` (the sum in the fixed
+    tree of ``_models._qkn_head_sum``), ``n = (x * r) * w`` -- with ``unit_offset`` (Gemma) ``(x * r) * (1 + w)`` --, the elements
+    under rot_dim rotated as ``apply_rotary`` rotates them but on the fp32 ``n``, one rounding to the dtype.  Without tables: the norm
+    alone.
+
+    Differentiable: q, k and the weights are saved (nothing computed), the backward is ``pfa_qk_norm_bwd`` -- ``r`` recomputed, dq and
+    dk in one launch together with the partial weight gradients, a second small launch adds those in a fixed order: no atomics,
+    bitwise reproducible -- and the weight gradients come back in the weights' dtype.  ``inplace=True`` is refused on a tensor that
+    requires grad.  The grids depend on host shapes only: no host synchronisation, capturable.  On CPU tensors the same rule runs in
+    plain torch, bit for bit (``_models._qk_norm_model`` / ``_qk_norm_bwd_model``, the executable specification)."""
+    geo = _qk_norm_geometry(q, k, q_weight, k_weight, eps, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids)
+    xs, ws = ([q], [q_weight]) if k is None else ([q, k], [q_weight, k_weight])
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in xs + ws)
+    if inplace:
+        if needs_grad:
+            raise ValueError("qk_norm(inplace=True) on a tensor that requires grad: the backward needs the input")
+        _qk_norm_call(xs, ws, geo, eps, unit_offset, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens, pos_offsets, position_ids, True)
+        return q if k is None else (q, k)
+    if needs_grad:
+        return _QkNormFunction.apply(q, k, q_weight, k_weight, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids,
+                                     (float(eps), bool(unit_offset), bool(rotary_interleaved), geo))
+    outs = _qk_norm_call(xs, ws, geo, eps, unit_offset, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens, pos_offsets, position_ids, False)
+    return outs[0] if k is None else tuple(outs)
+
+
+def _train_qk_norm_kw(q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset):
+    """The QK-norm keywords of the training attention calls: None without weights, else what ``qk_norm`` takes."""
+    if q_norm_weight is None and k_norm_weight is None:
+        if qk_norm_unit_offset:
+            raise ValueError("qk_norm_unit_offset needs q_norm_weight and k_norm_weight")
+        return None
+    if q_norm_weight is None or k_norm_weight is None:
+        raise ValueError("q_norm_weight and k_norm_weight go together")
+    return dict(eps=qk_norm_eps, unit_offset=bool(qk_norm_unit_offset))
 
 
 def _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens):
@@ -2153,7 +2366,9 @@ class _FA3VarlenSinkFunction(torch.autograd.Function):
 
 def fa3_varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p: float = 0.0,
                          softmax_scale: Optional[float] = None, causal: bool = False, *, out_dtype: Optional[torch.dtype] = None,
-                         sinks: Optional[torch.Tensor] = None, rotary_cos: Optional[torch.Tensor] = None,
+                         sinks: Optional[torch.Tensor] = None, q_norm_weight: Optional[torch.Tensor] = None,
+                         k_norm_weight: Optional[torch.Tensor] = None, qk_norm_eps: float = 1e-6, qk_norm_unit_offset: bool = False,
+                         rotary_cos: Optional[torch.Tensor] = None,
                          rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
                          pos_offsets: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None):
     """Autograd-aware packed variable-length attention, arguments in the order of flash-attn's ``flash_attn_varlen_func``: q
@@ -2163,11 +2378,21 @@ def fa3_varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     Rows no sequence covers get whatever ``torch.empty`` left, in the output and in the gradients (``cu[B] == total`` leaves none).
     ``rotary_cos`` / ``rotary_sin`` (with ``rotary_interleaved``, ``pos_offsets``, ``position_ids``): q and k are rotated first by
     ``apply_rotary`` at their row in the sequence -- one launch for packed self-attention (``cu_seqlens_k is cu_seqlens_q``), else one
-    each over their own ``cu_seqlens`` -- and the call is the one without them on the rotated operands, in both directions."""
+    each over their own ``cu_seqlens`` -- and the call is the one without them on the rotated operands, in both directions.
+    ``q_norm_weight`` / ``k_norm_weight`` (with ``qk_norm_eps``, ``qk_norm_unit_offset``): ``qk_norm`` takes the place of that step,
+    the rotation (if any) fused into its launch, under the same one-launch rule."""
     if dropout_p:
         raise NotImplementedError("attention dropout is not implemented on the packed path (dropout_p must be 0)")
     rot = _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, position_ids)
-    if rot is not None:
+    qkn = _train_qk_norm_kw(q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset)
+    if qkn is not None:
+        qkn.update(rot or {})
+        if cu_seqlens_q is cu_seqlens_k and _host_int(max_seqlen_q) == _host_int(max_seqlen_k):
+            q, k = qk_norm(q, k, q_weight=q_norm_weight, k_weight=k_norm_weight, cu_seqlens=cu_seqlens_q, max_seqlen=max_seqlen_q, **qkn)
+        else:
+            q = qk_norm(q, q_weight=q_norm_weight, cu_seqlens=cu_seqlens_q, max_seqlen=max_seqlen_q, **qkn)
+            k = qk_norm(k, q_weight=k_norm_weight, cu_seqlens=cu_seqlens_k, max_seqlen=max_seqlen_k, **qkn)
+    elif rot is not None:
         if cu_seqlens_q is cu_seqlens_k and _host_int(max_seqlen_q) == _host_int(max_seqlen_k):
             q, k = apply_rotary(q, k, cu_seqlens=cu_seqlens_q, max_seqlen=max_seqlen_q, **rot)
         else:
