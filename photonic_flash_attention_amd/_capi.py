@@ -318,14 +318,33 @@ def load(path: Optional[str] = None):
                 f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C photonic_flash_attention_amd/csrc` (there is no CPU fallback)")
         lib = C.CDLL(p)
-        for name, (restype, argtypes) in _PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
+        _type(lib, _PROTOTYPES)
         v = lib.pfa_abi_version()
         if v != PFA_ABI_VERSION:
             raise OSError(f"{p}: ABI version {v}, binding expects {PFA_ABI_VERSION}")
         _lib = lib
     return _lib
+
+
+def _type(lib, prototypes) -> None:
+    for name, (restype, argtypes) in prototypes.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+
+
+def bind(prototypes):
+    """The ``load`` of a side header's binding module (``_capi_sinks``, ``_capi_rotary``, ``_capi_qk_norm``): -> a function that returns
+    ``load()``'s library with the exports of ``prototypes`` typed on it (once).  It raises ``OSError`` if the library has not been built."""
+    typed = []
+
+    def load_typed():
+        lib = load()
+        if not typed:
+            with _lock:
+                _type(lib, prototypes)
+                typed.append(True)
+        return lib
+    return load_typed
 
 
 def status_string(status: int) -> str:

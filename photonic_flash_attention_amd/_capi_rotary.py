@@ -5,7 +5,6 @@ training calls (``pfa_rotary*``).  The counterpart of ``_capi`` for that header,
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 from . import _capi
 
@@ -37,21 +36,7 @@ def _prototypes():
 _PROTOTYPES = _prototypes()
 EXPORTS = tuple(_PROTOTYPES)
 
-_typed = False
-_lock = threading.Lock()
-
-
-def load():
-    """``_capi.load()``'s library with the exports of this header typed (once).  Raises ``OSError`` if it has not been built."""
-    global _typed
-    lib = _capi.load()
-    if not _typed:
-        with _lock:
-            for name, (restype, argtypes) in _PROTOTYPES.items():
-                fn = getattr(lib, name)
-                fn.restype, fn.argtypes = restype, argtypes
-            _typed = True
-    return lib
+load = _capi.bind(_PROTOTYPES)      # ``_capi.load()``'s library with the exports of this header typed (once)
 
 
 def make_rotary_args(**kw) -> PfaRotaryArgs:

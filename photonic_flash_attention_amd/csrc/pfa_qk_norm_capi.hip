@@ -7,85 +7,48 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "pfa_host.h"
+#include "pfa_rows_host.h"
 #include "qk_norm_kernel.h"
 
 namespace {
 
-constexpr int kPiece = 16;     // a work item is 16 elements of a row
-constexpr int64_t kLim = 0x7fffffffLL;
+namespace rows = pfa::rows;
+using rows::in_place;
+using rows::kLim;
+using rows::kPiece;
 constexpr uint32_t kFlags = PFA_QKNORM_INTERLEAVED | PFA_QKNORM_UNIT_OFFSET;
 
-// ---- the rules both blocks share: the fields have one name in both -------------------------------------------------------------------
+// ---- what both blocks add to the rules of pfa_rows_host.h ------------------------------------------------------------------------------
 template <typename A>
-int64_t units(const A* a) { return ((int64_t)a->H0 + a->H1) * (a->D / kPiece); }
+int64_t units(const A* a) { return rows::units(a, a->D); }
 template <typename A>
-int64_t items(const A* a) { return (int64_t)a->S * units(a); }                      // of one sequence, at most
-
+bool head_dims_ok(const A* a) { return (a->D == 64 || a->D == 128) && rows::rot_dim_ok(a, true); }
+// the rules of both blocks between the pointer rules and the stride rules, in their order
 template <typename A>
-int check_shape(const A* a) {
-    if (a->B < 1 || a->S < 1 || a->H0 < 1 || a->H1 < 0) return PFA_ERR_SHAPE;
-    if (a->rot_dim != 0 && a->max_pos < 1) return PFA_ERR_SHAPE;
-    if (!(a->eps >= 0.f) || !isfinite(a->eps)) return PFA_ERR_SHAPE;
-    if (a->cu_seqlens && (a->total < 1 || a->S > a->total)) return PFA_ERR_SHAPE;
-    return PFA_OK;
-}
-template <typename A>
-int check_dims(const A* a) {
-    if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
-    if (a->rot_dim != 0 && (a->rot_dim < 16 || a->rot_dim % 16 != 0 || a->rot_dim > a->D)) return PFA_ERR_HEAD_DIM;
-    return PFA_OK;
-}
-template <typename A>
-int check_dtypes(const A* a) {
+int check_shape_dims_dtypes(const A* a) {
+    if (!rows::shape_ok(a, true) || !(a->eps >= 0.f) || !isfinite(a->eps)) return PFA_ERR_SHAPE;
+    if (!head_dims_ok(a)) return PFA_ERR_HEAD_DIM;
     if (a->dtype != PFA_DTYPE_BF16 && a->dtype != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
     if (a->w_dtype != a->dtype && a->w_dtype != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;
     return PFA_OK;
 }
-template <typename A>
-bool tables_ok(const A* a) { return a->rot_dim == 0 || (a->cs_stride % 4 == 0 && a->cs_stride >= a->rot_dim / 2); }
-template <typename A>
-bool ints_aligned(const A* a) { return pfa::aligned4(a->cu_seqlens) && pfa::aligned4(a->pos_offsets) && pfa::aligned4(a->position_ids); }
 
 // ---- forward -------------------------------------------------------------------------------------------------------------------------
-bool in_place(const pfa_qk_norm_args* a) { return a->x0_out == a->x0; }
-int64_t nchunk(const pfa_qk_norm_args* a) { return (items(a) + pfa::QKNORM_THREADS - 1) / pfa::QKNORM_THREADS; }
-int64_t workgroups(const pfa_qk_norm_args* a) {     // saturated so that the product cannot wrap
-    return nchunk(a) > kLim ? kLim + 1 : (int64_t)a->B * nchunk(a);
-}
+int64_t workgroups(const pfa_qk_norm_args* a) { return rows::workgroups(a, units(a), pfa::QKNORM_THREADS); }
 
 int check(const pfa_qk_norm_args* a) {
-    using pfa::aligned16;
     if (!a) return PFA_ERR_NULL;
     if (a->size != sizeof(pfa_qk_norm_args)) return PFA_ERR_STRUCT_SIZE;
     if (a->flags & ~kFlags) return PFA_ERR_FLAGS;
-    if (a->position_ids && a->pos_offsets) return PFA_ERR_FLAGS;
-    if (a->x1 && a->x1_out && (a->x1_out == a->x1) != in_place(a)) return PFA_ERR_FLAGS;
+    if (!rows::positions_exclusive(a) || !rows::in_place_consistent(a)) return PFA_ERR_FLAGS;
     if (!a->x0 || !a->x0_out || !a->w0) return PFA_ERR_NULL;
-    if ((a->x1 == nullptr) != (a->H1 == 0) || (a->x1_out == nullptr) != (a->H1 == 0) || (a->w1 == nullptr) != (a->H1 == 0)) return PFA_ERR_NULL;
-    if ((a->cos == nullptr) != (a->rot_dim == 0) || (a->sin == nullptr) != (a->rot_dim == 0)) return PFA_ERR_NULL;
-    const bool packed = a->cu_seqlens != nullptr;
-    int st = check_shape(a);
-    if (st == PFA_OK) st = check_dims(a);
-    if (st == PFA_OK) st = check_dtypes(a);
+    if (!rows::null_iff(a->H1 == 0, {a->x1, a->x1_out, a->w1}) || !rows::null_iff(a->rot_dim == 0, {a->cos, a->sin})) return PFA_ERR_NULL;
+    const int st = check_shape_dims_dtypes(a);
     if (st != PFA_OK) return st;
-    if (!pfa::multiples_of(8, {a->x0_stride_s, a->x0_stride_h, a->x0o_stride_s, a->x0o_stride_h, a->x1_stride_s, a->x1_stride_h,
-                               a->x1o_stride_s, a->x1o_stride_h}))
-        return PFA_ERR_STRIDE;
-    if (!packed && !pfa::multiples_of(8, {a->x0_stride_b, a->x0o_stride_b, a->x1_stride_b, a->x1o_stride_b})) return PFA_ERR_STRIDE;
-    if (in_place(a)) {     // the same tensor: an item reads what it writes and nothing else
-        if (a->x0o_stride_s != a->x0_stride_s || a->x0o_stride_h != a->x0_stride_h || a->x1o_stride_s != a->x1_stride_s ||
-            a->x1o_stride_h != a->x1_stride_h)
-            return PFA_ERR_STRIDE;
-        if (!packed && (a->x0o_stride_b != a->x0_stride_b || a->x1o_stride_b != a->x1_stride_b)) return PFA_ERR_STRIDE;
-    }
-    if (!tables_ok(a)) return PFA_ERR_STRIDE;
-    if (!aligned16(a->x0) || !aligned16(a->x0_out) || !aligned16(a->x1) || !aligned16(a->x1_out) || !aligned16(a->w0) || !aligned16(a->w1) ||
-        !aligned16(a->cos) || !aligned16(a->sin))
-        return PFA_ERR_ALIGN;
-    if (!ints_aligned(a)) return PFA_ERR_ALIGN;
+    if (!rows::fwd_strides_ok(a) || (in_place(a) && !rows::in_place_strides_equal(a)) || !rows::tables_ok(a)) return PFA_ERR_STRIDE;
+    if (!rows::all_aligned16({a->x0, a->x0_out, a->x1, a->x1_out, a->w0, a->w1, a->cos, a->sin}) || !rows::ints_aligned(a)) return PFA_ERR_ALIGN;
     // a sequence's item index and the grid inside 32 bits
-    if (items(a) + pfa::QKNORM_THREADS > kLim || workgroups(a) > kLim) return PFA_ERR_SHAPE;
+    if (!rows::items_fit(a, units(a), pfa::QKNORM_THREADS) || workgroups(a) > kLim) return PFA_ERR_SHAPE;
     return PFA_OK;
 }
 
@@ -94,41 +57,31 @@ int64_t nrc(const pfa_qk_norm_bwd_args* a) { return ((int64_t)a->S + pfa::QKNORM
 int64_t partials(const pfa_qk_norm_bwd_args* a) {   // stage-1 workgroups (after the shape rules: all factors >= 1)
     return (a->H1 > 0 ? 2 : 1) * (int64_t)a->B * nrc(a);
 }
-int check_limits(const pfa_qk_norm_bwd_args* a) { return (items(a) + pfa::QKNORM_THREADS > kLim || partials(a) > kLim) ? PFA_ERR_SHAPE : PFA_OK; }
+bool limits_ok(const pfa_qk_norm_bwd_args* a) { return rows::items_fit(a, units(a), pfa::QKNORM_THREADS) && partials(a) <= kLim; }
 size_t workspace_bytes(const pfa_qk_norm_bwd_args* a) { return (size_t)partials(a) * (size_t)a->D * sizeof(float); }
 
 int check(const pfa_qk_norm_bwd_args* a) {
-    using pfa::aligned16;
     using pfa::aligned4;
     if (!a) return PFA_ERR_NULL;
     if (a->size != sizeof(pfa_qk_norm_bwd_args)) return PFA_ERR_STRUCT_SIZE;
     if (a->flags & ~kFlags) return PFA_ERR_FLAGS;
-    if (a->position_ids && a->pos_offsets) return PFA_ERR_FLAGS;
+    if (!rows::positions_exclusive(a)) return PFA_ERR_FLAGS;
     if (a->dx0 && (a->dx0 == a->x0 || a->dx0 == a->dy0)) return PFA_ERR_FLAGS;      // in place is refused in the backward
     if (a->dx1 && (a->dx1 == a->x1 || a->dx1 == a->dy1)) return PFA_ERR_FLAGS;
     if (!a->x0 || !a->dy0 || !a->dx0 || !a->w0 || !a->dw0 || !a->workspace) return PFA_ERR_NULL;
-    const bool none = a->H1 == 0;
-    if ((a->x1 == nullptr) != none || (a->dy1 == nullptr) != none || (a->dx1 == nullptr) != none || (a->w1 == nullptr) != none ||
-        (a->dw1 == nullptr) != none)
+    if (!rows::null_iff(a->H1 == 0, {a->x1, a->dy1, a->dx1, a->w1, a->dw1}) || !rows::null_iff(a->rot_dim == 0, {a->cos, a->sin}))
         return PFA_ERR_NULL;
-    if ((a->cos == nullptr) != (a->rot_dim == 0) || (a->sin == nullptr) != (a->rot_dim == 0)) return PFA_ERR_NULL;
-    const bool packed = a->cu_seqlens != nullptr;
-    int st = check_shape(a);
-    if (st == PFA_OK) st = check_dims(a);
-    if (st == PFA_OK) st = check_dtypes(a);
+    const int st = check_shape_dims_dtypes(a);
     if (st != PFA_OK) return st;
     if (!pfa::multiples_of(8, {a->x0_stride_s, a->x0_stride_h, a->dy0_stride_s, a->dy0_stride_h, a->dx0_stride_s, a->dx0_stride_h,
                                a->x1_stride_s, a->x1_stride_h, a->dy1_stride_s, a->dy1_stride_h, a->dx1_stride_s, a->dx1_stride_h}))
         return PFA_ERR_STRIDE;
-    if (!packed && !pfa::multiples_of(8, {a->x0_stride_b, a->dy0_stride_b, a->dx0_stride_b, a->x1_stride_b, a->dy1_stride_b, a->dx1_stride_b}))
+    if (!a->cu_seqlens && !pfa::multiples_of(8, {a->x0_stride_b, a->dy0_stride_b, a->dx0_stride_b, a->x1_stride_b, a->dy1_stride_b, a->dx1_stride_b}))
         return PFA_ERR_STRIDE;
-    if (!tables_ok(a)) return PFA_ERR_STRIDE;
-    if (!aligned16(a->x0) || !aligned16(a->dy0) || !aligned16(a->dx0) || !aligned16(a->x1) || !aligned16(a->dy1) || !aligned16(a->dx1) ||
-        !aligned16(a->w0) || !aligned16(a->w1) || !aligned16(a->cos) || !aligned16(a->sin))
-        return PFA_ERR_ALIGN;
-    if (!aligned4(a->dw0) || !aligned4(a->dw1) || !aligned4(a->workspace) || !ints_aligned(a)) return PFA_ERR_ALIGN;
-    st = check_limits(a);
-    if (st != PFA_OK) return st;
+    if (!rows::tables_ok(a)) return PFA_ERR_STRIDE;
+    if (!rows::all_aligned16({a->x0, a->dy0, a->dx0, a->x1, a->dy1, a->dx1, a->w0, a->w1, a->cos, a->sin})) return PFA_ERR_ALIGN;
+    if (!aligned4(a->dw0) || !aligned4(a->dw1) || !aligned4(a->workspace) || !rows::ints_aligned(a)) return PFA_ERR_ALIGN;
+    if (!limits_ok(a)) return PFA_ERR_SHAPE;
     if (a->workspace_bytes < workspace_bytes(a)) return PFA_ERR_NULL;
     return PFA_OK;
 }
@@ -171,18 +124,9 @@ int pfa_qk_norm(const pfa_qk_norm_args* a, void* stream) {
     if (st != PFA_OK) return st;
     const bool packed = a->cu_seqlens != nullptr;
     pfa::QkNormParams p;
-    p.x0 = a->x0; p.x0_out = a->x0_out; p.x1 = a->x1; p.x1_out = a->x1_out;
+    rows::fill_fwd(p, a, units(a), pfa::QKNORM_THREADS);
     p.w0 = a->w0; p.w1 = a->w1;
-    p.cos = a->cos; p.sin = a->sin;
-    p.cu_seqlens = a->cu_seqlens; p.pos_offsets = a->pos_offsets; p.position_ids = a->position_ids;
-    PFA_FILL_STRIDES(p, a, x0); PFA_FILL_STRIDES(p, a, x0o); PFA_FILL_STRIDES(p, a, x1); PFA_FILL_STRIDES(p, a, x1o);
-    p.pid_sb = a->pid_stride_b; p.pid_ss = a->pid_stride_s; p.cs_stride = a->cs_stride;
     p.eps = a->eps; p.inv_d = 1.0f / (float)a->D;
-    p.nchunk = (int32_t)nchunk(a);
-    p.S = a->S; p.total = a->total; p.H0 = a->H0;
-    p.runits = a->rot_dim / kPiece;
-    p.units = (int32_t)units(a);
-    p.max_pos = a->max_pos;
     p.w_fp32 = a->w_dtype == PFA_DTYPE_FP32;
     p.unit_offset = (a->flags & PFA_QKNORM_UNIT_OFFSET) ? 1 : 0;
 
@@ -199,7 +143,7 @@ int pfa_qk_norm(const pfa_qk_norm_args* a, void* stream) {
 size_t pfa_qk_norm_bwd_workspace_bytes(const pfa_qk_norm_bwd_args* a) {
     if (!a || a->size != sizeof(pfa_qk_norm_bwd_args)) return 0;
     if (a->B < 1 || a->S < 1 || a->H0 < 1 || a->H1 < 0 || (a->cu_seqlens && (a->total < 1 || a->S > a->total))) return 0;
-    if (check_dims(a) != PFA_OK || check_limits(a) != PFA_OK) return 0;
+    if (!head_dims_ok(a) || !limits_ok(a)) return 0;
     return workspace_bytes(a);
 }
 
@@ -224,16 +168,12 @@ int pfa_qk_norm_bwd(const pfa_qk_norm_bwd_args* a, void* stream) {
     p.x0 = a->x0; p.dy0 = a->dy0; p.dx0 = a->dx0; p.x1 = a->x1; p.dy1 = a->dy1; p.dx1 = a->dx1;
     p.w0 = a->w0; p.w1 = a->w1; p.dw0 = a->dw0; p.dw1 = a->dw1;
     p.partial = (float*)a->workspace;
-    p.cos = a->cos; p.sin = a->sin;
-    p.cu_seqlens = a->cu_seqlens; p.pos_offsets = a->pos_offsets; p.position_ids = a->position_ids;
+    rows::fill_common(p, a);
     PFA_FILL_STRIDES(p, a, x0); PFA_FILL_STRIDES(p, a, dy0); PFA_FILL_STRIDES(p, a, dx0);
     PFA_FILL_STRIDES(p, a, x1); PFA_FILL_STRIDES(p, a, dy1); PFA_FILL_STRIDES(p, a, dx1);
-    p.pid_sb = a->pid_stride_b; p.pid_ss = a->pid_stride_s; p.cs_stride = a->cs_stride;
     p.eps = a->eps; p.inv_d = 1.0f / (float)a->D;
     p.nrc = (int32_t)nrc(a);
-    p.B = a->B; p.S = a->S; p.total = a->total; p.H0 = a->H0; p.H1 = a->H1;
-    p.runits = a->rot_dim / kPiece;
-    p.max_pos = a->max_pos;
+    p.B = a->B; p.H1 = a->H1;
     p.w_fp32 = a->w_dtype == PFA_DTYPE_FP32;
     p.unit_offset = (a->flags & PFA_QKNORM_UNIT_OFFSET) ? 1 : 0;
 

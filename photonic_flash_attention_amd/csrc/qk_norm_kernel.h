@@ -1,6 +1,7 @@
 // qk_norm_kernel.h -- QK-norm (an RMSNorm over the head dim of every head of Q and K) fused with the rotary embedding of the training
 // calls, forward and backward, hand-written HIP for MI355X (gfx950).  One launch handles x0 with H0 heads (Q) and optionally x1 with H1
-// heads (K) over the same rows and positions.  Layouts, clamps, positions, tables and the grid rule are rotary_kernel.h's, to the letter:
+// heads (K) over the same rows and positions.  Layouts, clamps, positions, tables and the grid rule are rotary_kernel.h's, to the letter
+// (the clamp, the position and the table load are rope_parts.h's functions, shared with it):
 // dense [B, H, S, D] by element strides (sb, ss, sh), D contiguous; PACKED [total, H, D] with
 //   s_b = clamp(cu[b], 0, total), e_b = clamp(cu[b + 1], s_b, total), rows_b = min(e_b - s_b, S)   (S: max_seqlen);
 // the position of row i of sequence b is clamp(p, 0, max_pos - 1) in 64 bits, p = position_ids[...] or i + pos_offsets[b]; tables fp32
@@ -44,8 +45,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rope_append_kernel.h"
-#include "rotary_kernel.h"
+#include "rope_parts.h"
 
 namespace pfa {
 
@@ -120,12 +120,6 @@ struct QkNormBwdParams {
     int32_t unit_offset;
 };
 
-// rope_pair on fp32 operands: the same three roundings (this object is built with -ffp-contract=off), no narrowing
-__device__ __forceinline__ void rope_pair_f32(float a, float b, float c, float s, float& y1, float& y2) {
-    y1 = a * c - b * s;
-    y2 = b * c + a * s;
-}
-
 template <typename T>
 __device__ __forceinline__ void qkn_widen8(const rope_b128 v, float* f) {
 #pragma unroll
@@ -173,16 +167,6 @@ __device__ __forceinline__ float qkn_head_sum(const float* a0, const float* b0, 
     return v;
 }
 
-// the unit's eight cos and sin at the row's clamped position
-__device__ __forceinline__ void qkn_tables(const float* cos, const float* sin, int64_t pos, int max_pos, int64_t cs_stride, int u, float* cs, float* sn) {
-    const int64_t rp = min(max(pos, (int64_t)0), (int64_t)max_pos - 1);
-    const int64_t at = rp * cs_stride + u * 8;
-    const rope_f4 ca = *reinterpret_cast<const rope_f4*>(cos + at), cb = *reinterpret_cast<const rope_f4*>(cos + at + 4);
-    const rope_f4 sa = *reinterpret_cast<const rope_f4*>(sin + at), sb = *reinterpret_cast<const rope_f4*>(sin + at + 4);
-    cs[0] = ca.x; cs[1] = ca.y; cs[2] = ca.z; cs[3] = ca.w; cs[4] = cb.x; cs[5] = cb.y; cs[6] = cb.z; cs[7] = cb.w;
-    sn[0] = sa.x; sn[1] = sa.y; sn[2] = sa.z; sn[3] = sa.w; sn[4] = sb.x; sn[5] = sb.y; sn[6] = sb.z; sn[7] = sb.w;
-}
-
 // the unit's eight pairs rotated in fp32, in registers: half style (na[k], nb[k]), INTERLEAVED (n[2w], n[2w + 1]) with pairs 0..3 in na
 template <bool INTERLEAVED>
 __device__ __forceinline__ void qkn_rotate(float* na, float* nb, const float* cs, const float* sn) {
@@ -210,13 +194,8 @@ __global__ __launch_bounds__(QKNORM_THREADS) void qk_norm_kernel(const QkNormPar
     const int b = blockIdx.x / p.nchunk;
     const int item0 = (blockIdx.x - b * p.nchunk) * QKNORM_THREADS;         // the workgroup's first item of sequence b
 
-    int rows = p.S, row0 = 0;
-    if constexpr (PACKED) {
-        const int s_b = min(max(p.cu_seqlens[b], 0), p.total);
-        const int e_b = min(max(p.cu_seqlens[b + 1], s_b), p.total);
-        row0 = s_b;
-        rows = min(e_b - s_b, p.S);
-    }
+    int rows, row0;
+    rope_seq_rows<PACKED>(p.cu_seqlens, b, p.total, p.S, row0, rows);
     if (item0 >= rows * p.units) return;                 // workgroup-uniform: the only return (see the header of this file)
     const int64_t off = p.pos_offsets ? (int64_t)p.pos_offsets[b] : 0;
 
@@ -269,10 +248,8 @@ __global__ __launch_bounds__(QKNORM_THREADS) void qk_norm_kernel(const QkNormPar
         nb[k] = (xb[k] * r) * wb[k];
     }
     if (live && rot) {
-        int64_t pos = (int64_t)i + off;
-        if (p.position_ids) pos = PACKED ? (int64_t)p.position_ids[row] : (int64_t)p.position_ids[bb * p.pid_sb + row * p.pid_ss];
         float cs[8], sn[8];
-        qkn_tables(p.cos, p.sin, pos, p.max_pos, p.cs_stride, u, cs, sn);
+        rope_tables(p.cos, p.sin, rope_row_pos<PACKED>(p.position_ids, bb, row, p.pid_sb, p.pid_ss, i, off), p.max_pos, p.cs_stride, u, cs, sn);
         qkn_rotate<INTERLEAVED>(na, nb, cs, sn);
     }
     if (live) {
@@ -291,13 +268,8 @@ __global__ __launch_bounds__(QKNORM_THREADS) void qk_norm_bwd_kernel(const QkNor
     const int tid = (int)threadIdx.x;
     float* part = p.partial + (int64_t)blockIdx.x * D;
 
-    int rows = p.S, row0 = 0;
-    if constexpr (PACKED) {
-        const int s_b = min(max(p.cu_seqlens[b], 0), p.total);
-        const int e_b = min(max(p.cu_seqlens[b + 1], s_b), p.total);
-        row0 = s_b;
-        rows = min(e_b - s_b, p.S);
-    }
+    int rows, row0;
+    rope_seq_rows<PACKED>(p.cu_seqlens, b, p.total, p.S, row0, rows);
     const int r0 = c * QKNORM_BWD_ROWS;
     if (r0 >= rows) {                                    // workgroup-uniform: a chunk past its sequence leaves zeros and reads nothing
         if (tid < D) part[tid] = 0.f;
@@ -348,10 +320,8 @@ __global__ __launch_bounds__(QKNORM_THREADS) void qk_norm_bwd_kernel(const QkNor
             qkn_widen8<T>(*reinterpret_cast<const rope_b128*>(dys + c1), gb);
         }
         if (live && rot) {
-            int64_t pos = (int64_t)i + off;
-            if (p.position_ids) pos = PACKED ? (int64_t)p.position_ids[row] : (int64_t)p.position_ids[bb * p.pid_sb + row * p.pid_ss];
             float cs[8], sn[8];
-            qkn_tables(p.cos, p.sin, pos, p.max_pos, p.cs_stride, u, cs, sn);
+            rope_tables(p.cos, p.sin, rope_row_pos<PACKED>(p.position_ids, bb, row, p.pid_sb, p.pid_ss, i, off), p.max_pos, p.cs_stride, u, cs, sn);
 #pragma unroll
             for (int k = 0; k < 8; ++k) sn[k] = -sn[k];  // exact: the conjugate is the same three roundings
             qkn_rotate<INTERLEAVED>(ga, gb, cs, sn);

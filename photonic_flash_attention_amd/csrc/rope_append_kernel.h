@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rope_parts.h"
+
 namespace pfa {
 
 constexpr int ROPE_APPEND_THREADS = 256;
@@ -71,37 +73,13 @@ struct RopeAppendParams {
     int32_t page_size, num_pages;
 };
 
-typedef uint32_t rope_b128 __attribute__((ext_vector_type(4)));
-typedef float rope_f4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ float rope_widen(uint32_t h) {
-    return static_cast<float>(__builtin_bit_cast(T, (uint16_t)h));
-}
-template <typename T>
-__device__ __forceinline__ uint32_t rope_narrow(float f) {       // round to nearest even
-    return __builtin_bit_cast(uint16_t, static_cast<T>(f));
-}
-// one pair: the three roundings are separate fp32 operations (this object is built with -ffp-contract=off)
-template <typename T>
-__device__ __forceinline__ void rope_pair(uint32_t x1, uint32_t x2, float c, float s, uint32_t& y1, uint32_t& y2) {
-    const float a = rope_widen<T>(x1), b = rope_widen<T>(x2);
-    y1 = rope_narrow<T>(a * c - b * s);
-    y2 = rope_narrow<T>(b * c + a * s);
-}
-
 template <typename T, bool VARLEN, bool PAGED, bool INTERLEAVED>
 __global__ __launch_bounds__(ROPE_APPEND_THREADS) void rope_append_kernel(const RopeAppendParams p) {
     const int b = blockIdx.x / p.nchunk;
     const int item0 = (blockIdx.x - b * p.nchunk) * ROPE_APPEND_THREADS;    // the workgroup's first item of sequence b
 
-    int sq = p.Sq, row0 = 0;
-    if constexpr (VARLEN) {
-        const int s_b = min(max(p.cu_seqlens_q[b], 0), p.total_new);
-        const int e_b = min(max(p.cu_seqlens_q[b + 1], s_b), p.total_new);
-        row0 = s_b;
-        sq = min(e_b - s_b, p.Sq);
-    }
+    int sq, row0;
+    rope_seq_rows<VARLEN>(p.cu_seqlens_q, b, p.total_new, p.Sq, row0, sq);
     if (item0 >= sq * p.units) return;                   // wave-uniform: nothing of this sequence in the workgroup
     const int len = min(max(p.seqlens[b], 0), p.Smax);
     const int64_t off = p.pos_offsets ? (int64_t)p.pos_offsets[b] : 0;
@@ -153,12 +131,8 @@ __global__ __launch_bounds__(ROPE_APPEND_THREADS) void rope_append_kernel(const 
     rope_b128 x1 = *reinterpret_cast<const rope_b128*>(src + c1);
 
     if (rot) {
-        const int64_t rp = min(max((int64_t)pos + off, (int64_t)0), (int64_t)p.max_pos - 1);
-        const int64_t at = rp * p.cs_stride + u * 8;
-        const rope_f4 ca = *reinterpret_cast<const rope_f4*>(p.cos + at), cb = *reinterpret_cast<const rope_f4*>(p.cos + at + 4);
-        const rope_f4 sa = *reinterpret_cast<const rope_f4*>(p.sin + at), sb = *reinterpret_cast<const rope_f4*>(p.sin + at + 4);
-        const float cs[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
-        const float sn[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+        float cs[8], sn[8];
+        rope_tables(p.cos, p.sin, (int64_t)pos + off, p.max_pos, p.cs_stride, u, cs, sn);
         if constexpr (INTERLEAVED) {
 #pragma unroll
             for (int w = 0; w < 4; ++w) {                // a 32-bit word is one pair: pairs 0..3 in x0, 4..7 in x1

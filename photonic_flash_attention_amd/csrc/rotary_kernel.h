@@ -7,7 +7,7 @@
 // pointer is given (int32; dense by (pid_sb, pid_ss), packed [total]) and else i + pos_offsets[b] (pos_offsets NULL: 0): an
 // out-of-range position gives wrong numbers, never an address outside the tables.
 //
-// The arithmetic is rope_append_kernel.h's, to the letter (rope_pair, rope_widen and rope_narrow are its): with R = rot_dim,
+// The arithmetic is rope_append_kernel.h's, to the letter (rope_pair, rope_widen and rope_narrow are rope_parts.h's): with R = rot_dim,
 // half = R / 2, c = cos[p][j], s = sin[p][j] (fp32 tables [max_pos, half], row stride cs_stride) the pair (x1, x2) = (x[j], x[j + half])
 // -- or, INTERLEAVED, (x[2j], x[2j + 1]) -- becomes y1 = x1 * c - x2 * s, y2 = x2 * c + x1 * s, operands widened to fp32, each product
 // and the one add / subtract rounded to fp32 SEPARATELY (the unit is built with -ffp-contract=off), one round-to-nearest-even to the
@@ -32,7 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rope_append_kernel.h"
+#include "rope_parts.h"
 
 namespace pfa {
 
@@ -69,13 +69,8 @@ __global__ __launch_bounds__(ROTARY_THREADS) void rotary_kernel(const RotaryPara
     const int b = blockIdx.x / p.nchunk;
     const int item0 = (blockIdx.x - b * p.nchunk) * ROTARY_THREADS;         // the workgroup's first item of sequence b
 
-    int rows = p.S, row0 = 0;
-    if constexpr (PACKED) {
-        const int s_b = min(max(p.cu_seqlens[b], 0), p.total);
-        const int e_b = min(max(p.cu_seqlens[b + 1], s_b), p.total);
-        row0 = s_b;
-        rows = min(e_b - s_b, p.S);
-    }
+    int rows, row0;
+    rope_seq_rows<PACKED>(p.cu_seqlens, b, p.total, p.S, row0, rows);
     if (item0 >= rows * p.units) return;                 // wave-uniform: nothing of this sequence in the workgroup
     const int64_t off = p.pos_offsets ? (int64_t)p.pos_offsets[b] : 0;
 
@@ -109,14 +104,8 @@ __global__ __launch_bounds__(ROTARY_THREADS) void rotary_kernel(const RotaryPara
     rope_b128 a1 = *reinterpret_cast<const rope_b128*>(src + c1);
 
     if (rot) {
-        int64_t pos = (int64_t)i + off;
-        if (p.position_ids) pos = PACKED ? (int64_t)p.position_ids[row] : (int64_t)p.position_ids[bb * p.pid_sb + row * p.pid_ss];
-        const int64_t rp = min(max(pos, (int64_t)0), (int64_t)p.max_pos - 1);
-        const int64_t at = rp * p.cs_stride + u * 8;
-        const rope_f4 ca = *reinterpret_cast<const rope_f4*>(p.cos + at), cb = *reinterpret_cast<const rope_f4*>(p.cos + at + 4);
-        const rope_f4 sa = *reinterpret_cast<const rope_f4*>(p.sin + at), sb = *reinterpret_cast<const rope_f4*>(p.sin + at + 4);
-        const float cs[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
-        float sn[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+        float cs[8], sn[8];
+        rope_tables(p.cos, p.sin, rope_row_pos<PACKED>(p.position_ids, bb, row, p.pid_sb, p.pid_ss, i, off), p.max_pos, p.cs_stride, u, cs, sn);
         if (p.conjugate) {
 #pragma unroll
             for (int w = 0; w < 8; ++w) sn[w] = -sn[w];  // exact: the conjugate is the same three roundings

@@ -1125,6 +1125,23 @@ def _rotary_operands(rotary_cos, rotary_sin, D: int):
     return 2 * half, max_pos
 
 
+def _pos_offsets_operand(pos_offsets, B: int) -> None:
+    if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
+                                    or pos_offsets.shape != (B,) or not pos_offsets.is_contiguous()):
+        raise ValueError("pos_offsets must be a contiguous int32 [B] tensor")
+
+
+def _tables_given(rotary_cos, rotary_sin, **dependent) -> bool:
+    """Are there rotary tables?  They are given together; without them every ``dependent`` keyword must be unset (None or False)."""
+    if rotary_cos is None and rotary_sin is None:
+        if any(v is not None and v is not False for v in dependent.values()):
+            raise ValueError(f"{' / '.join(dependent)} need rotary_cos and rotary_sin")
+        return False
+    if rotary_cos is None or rotary_sin is None:
+        raise ValueError("rotary_cos and rotary_sin go together")
+    return True
+
+
 def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
                 rotary_cos: torch.Tensor, rotary_sin: torch.Tensor, q: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None,
                 rotary_interleaved: bool = False, pos_offsets: Optional[torch.Tensor] = None,
@@ -1155,9 +1172,7 @@ def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
     geo = _append_operands("pfa_rope_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, others)
     ragged, B, D, total, max_seqlen_q = geo.ragged, geo.B, geo.D, geo.total, geo.max_seqlen_q
     rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, D)
-    if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
-                                    or pos_offsets.shape != (B,) or not pos_offsets.is_contiguous()):
-        raise ValueError("pos_offsets must be a contiguous int32 [B] tensor")
+    _pos_offsets_operand(pos_offsets, B)
     H = 0
     if q is None:
         if q_out is not None:
@@ -1240,9 +1255,7 @@ def _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_o
     rot_dim, max_pos = (0, 0) if rotary_cos is None else _rotary_operands(rotary_cos, rotary_sin, D)
     if pos_offsets is not None and position_ids is not None:
         raise ValueError("pos_offsets and position_ids exclude each other")
-    if pos_offsets is not None and (not isinstance(pos_offsets, torch.Tensor) or pos_offsets.dtype != torch.int32
-                                    or pos_offsets.shape != (B,) or not pos_offsets.is_contiguous()):
-        raise ValueError("pos_offsets must be a contiguous int32 [B] tensor")
+    _pos_offsets_operand(pos_offsets, B)
     if position_ids is not None and (not isinstance(position_ids, torch.Tensor) or position_ids.dtype != torch.int32
                                      or position_ids.shape != ((total,) if packed else (B, S))
                                      or (packed and not position_ids.is_contiguous())):
@@ -1266,35 +1279,50 @@ def _rotary_out(x: torch.Tensor, packed: bool) -> torch.Tensor:
     return torch.empty((B, S, H, D), dtype=x.dtype, device=x.device).permute(0, 2, 1, 3)
 
 
-def _rotary_call(xs, geo: _RotaryGeo, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids, conjugate, inplace,
-                 outs=None):
-    """One ``pfa_rotary`` over the one or two tensors ``xs`` (checked by ``_rotary_geometry``) on their current stream, or on CPU tensors
-    the plain-torch model.  -> the outputs: fresh tensors (or the caller's ``outs``, of the shapes and dtype of ``xs``), or ``xs``
-    themselves in place."""
+# The glue of the three calls over rows (pfa_rotary, pfa_qk_norm, pfa_qk_norm_bwd): their argument blocks name the shared fields alike.
+
+def _rows_outs(who: str, xs, geo: _RotaryGeo, inplace, outs) -> list:
+    """The outputs of ``who``: the caller's ``outs``, else in place ``xs`` themselves (refused unless they meet the ABI as they are: a
+    copy would not be the caller's tensor), else fresh tensors."""
     if outs is not None:
-        outs = list(outs)
-    elif inplace:
-        if not all(_rotary_meets_abi(x) for x in xs):
-            raise ValueError("apply_rotary(inplace=True): the head dim must be contiguous, the base 16-byte aligned and every other stride "
-                             "a multiple of 8 elements")
-        outs = list(xs)
+        return list(outs)
+    if not inplace:
+        return [_rotary_out(x, geo.packed) for x in xs]
+    if not all(_rotary_meets_abi(x) for x in xs):
+        raise ValueError(f"{who}(inplace=True): the head dim must be contiguous, the base 16-byte aligned and every other stride "
+                         "a multiple of 8 elements")
+    return list(xs)
+
+
+def _meeting_abi(ts, held: list, weights: bool = False) -> list:
+    """``ts`` with a copy in place of every tensor that does not meet the ABI (16-bit row tensors: ``_rotary_meets_abi``; norm
+    ``weights``: contiguous and 16-byte aligned).  The copies are added to ``held``: they must outlive the launch."""
+    if weights:
+        out = [w if w.is_contiguous() and w.data_ptr() % 16 == 0 else w.clone(memory_format=torch.contiguous_format) for w in ts]
     else:
-        outs = [_rotary_out(x, geo.packed) for x in xs]
-    if xs[0].device.type == "cpu":
-        _rotary_model(xs, outs, rotary_cos, rotary_sin, bool(interleaved), bool(conjugate),
-                      cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
-        return outs
-    given, xs = xs, [x if _rotary_meets_abi(x) else x.contiguous() for x in xs]
-    flags = (_capi_rotary.PFA_ROTARY_INTERLEAVED if interleaved else 0) | (_capi_rotary.PFA_ROTARY_CONJUGATE if conjugate else 0)
-    a = _capi_rotary.make_rotary_args(flags=flags, cos=rotary_cos.data_ptr(), sin=rotary_sin.data_ptr(), cs_stride=rotary_cos.stride(0),
-                                      B=geo.B, S=geo.S, total=geo.total, H0=xs[0].shape[1], H1=xs[1].shape[1] if len(xs) > 1 else 0, D=geo.D,
-                                      rot_dim=geo.rot_dim, max_pos=geo.max_pos, dtype=_DT[xs[0].dtype], device_id=_device_index(xs[0].device))
-    for pre, x, o in zip(("x0", "x1"), xs, outs):
-        setattr(a, pre, x.data_ptr())
-        setattr(a, pre + "_out", o.data_ptr())
-        for fields, t in ((pre, x), (pre + "o", o)):
-            for axis, st in zip("sh" if geo.packed else "bhs", t.stride()):
-                setattr(a, f"{fields}_stride_{axis}", st)
+        out = [t if _rotary_meets_abi(t) else t.contiguous() for t in ts]
+    held += [o for o, t in zip(out, ts) if o is not t]
+    return out
+
+
+def _rows_shape(xs, geo: _RotaryGeo) -> dict:
+    return dict(B=geo.B, S=geo.S, total=geo.total, H0=xs[0].shape[1], H1=xs[1].shape[1] if len(xs) > 1 else 0, D=geo.D, rot_dim=geo.rot_dim,
+                max_pos=geo.max_pos, dtype=_DT[xs[0].dtype], device_id=_device_index(xs[0].device))
+
+
+def _fwd_tensors(xs, outs) -> list:
+    """``_qk_norm_fill``'s ``tensors`` of a forward block: x0, x1 and x0_out, x1_out (strides x0o, x1o)."""
+    return [(pre, pre, x) for pre, x in zip(("x0", "x1"), xs)] + [(pre + "_out", pre + "o", o) for pre, o in zip(("x0", "x1"), outs)]
+
+
+def _qk_norm_fill(a, geo: _RotaryGeo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids) -> None:
+    """The fields all three argument blocks name alike; ``tensors``: (field prefix, stride prefix, tensor) of every 16-bit tensor."""
+    for field, strides, t in tensors:
+        setattr(a, field, t.data_ptr())
+        for axis, st in zip("sh" if geo.packed else "bhs", t.stride()):
+            setattr(a, f"{strides}_stride_{axis}", st)
+    if rotary_cos is not None:
+        a.cos, a.sin, a.cs_stride = rotary_cos.data_ptr(), rotary_sin.data_ptr(), rotary_cos.stride(0)
     if geo.packed:
         a.cu_seqlens = cu_seqlens.data_ptr()
     if pos_offsets is not None:
@@ -1303,9 +1331,31 @@ def _rotary_call(xs, geo: _RotaryGeo, rotary_cos, rotary_sin, interleaved, cu_se
         a.position_ids = position_ids.data_ptr()
         if not geo.packed:
             a.pid_stride_b, a.pid_stride_s = position_ids.stride()
-    stream = torch.cuda.current_stream(xs[0].device)
-    _raise_status("pfa_rotary", _capi_rotary.load().pfa_rotary(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
-    _hold([x for x, g in zip(xs, given) if x is not g], stream)      # a copy made above must outlive the launch
+
+
+def _rows_launch(name: str, binding, a, device, held) -> None:
+    """Enqueue export ``name`` of ``binding`` on ``device``'s current stream; ``held`` is kept until the stream has passed the launch."""
+    stream = torch.cuda.current_stream(device)
+    _raise_status(name, getattr(binding.load(), name)(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
+    _hold(held, stream)
+
+
+def _rotary_call(xs, geo: _RotaryGeo, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids, conjugate, inplace,
+                 outs=None):
+    """One ``pfa_rotary`` over the one or two tensors ``xs`` (checked by ``_rotary_geometry``) on their current stream, or on CPU tensors
+    the plain-torch model.  -> the outputs: fresh tensors (or the caller's ``outs``, of the shapes and dtype of ``xs``), or ``xs``
+    themselves in place."""
+    outs = _rows_outs("apply_rotary", xs, geo, inplace, outs)
+    if xs[0].device.type == "cpu":
+        _rotary_model(xs, outs, rotary_cos, rotary_sin, bool(interleaved), bool(conjugate),
+                      cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
+        return outs
+    held = []
+    xs = _meeting_abi(xs, held)
+    flags = (_capi_rotary.PFA_ROTARY_INTERLEAVED if interleaved else 0) | (_capi_rotary.PFA_ROTARY_CONJUGATE if conjugate else 0)
+    a = _capi_rotary.make_rotary_args(flags=flags, **_rows_shape(xs, geo))
+    _qk_norm_fill(a, geo, _fwd_tensors(xs, outs), rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
+    _rows_launch("pfa_rotary", _capi_rotary, a, xs[0].device, held)
     return outs
 
 
@@ -1376,14 +1426,8 @@ def apply_rotary(q: torch.Tensor, k: Optional[torch.Tensor] = None, *, rotary_co
 def _train_rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, position_ids):
     """The rotary keywords of the training attention calls: None without tables (then the other three must be unset), else what
     ``apply_rotary`` takes."""
-    if rotary_cos is None and rotary_sin is None:
-        if rotary_interleaved or pos_offsets is not None or position_ids is not None:
-            raise ValueError("rotary_interleaved / pos_offsets / position_ids need rotary_cos and rotary_sin")
-        return None
-    if rotary_cos is None or rotary_sin is None:
-        raise ValueError("rotary_cos and rotary_sin go together")
-    return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets,
-                position_ids=position_ids)
+    kw = dict(rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets, position_ids=position_ids)
+    return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, **kw) if _tables_given(rotary_cos, rotary_sin, **kw) else None
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1399,14 +1443,8 @@ def _qk_norm_geometry(q, k, q_weight, k_weight, eps, rotary_cos, rotary_sin, cu_
     D = q.shape[-1]
     if D not in (64, 128):
         raise ValueError(f"head dim {D}: qk_norm takes 64 or 128, the attention's head dims")
-    if (rotary_cos is None) != (rotary_sin is None):
-        raise ValueError("rotary_cos and rotary_sin go together")
-    if rotary_cos is None:
-        if pos_offsets is not None or position_ids is not None:
-            raise ValueError("pos_offsets / position_ids need rotary_cos and rotary_sin")
-        geo = _rotary_geometry(q, k, None, None, cu_seqlens, max_seqlen, None, None, who="qk_norm")
-    else:
-        geo = _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids, who="qk_norm")
+    _tables_given(rotary_cos, rotary_sin, pos_offsets=pos_offsets, position_ids=position_ids)
+    geo = _rotary_geometry(q, k, rotary_cos, rotary_sin, cu_seqlens, max_seqlen, pos_offsets, position_ids, who="qk_norm")
     if (k is None) != (k_weight is None):
         raise ValueError("k and k_weight go together")
     ws = [w for w in (q_weight, k_weight) if w is not None]
@@ -1421,61 +1459,27 @@ def _qk_norm_geometry(q, k, q_weight, k_weight, eps, rotary_cos, rotary_sin, cu_
     return geo
 
 
-def _qk_norm_weight(w: torch.Tensor) -> torch.Tensor:
-    return w if w.is_contiguous() and w.data_ptr() % 16 == 0 else w.clone(memory_format=torch.contiguous_format)
-
-
-def _qk_norm_fill(a, geo: _RotaryGeo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids) -> None:
-    """The fields both argument blocks name alike; ``tensors``: (field prefix, stride prefix, tensor) of every 16-bit tensor."""
-    for field, strides, t in tensors:
-        setattr(a, field, t.data_ptr())
-        for axis, st in zip("sh" if geo.packed else "bhs", t.stride()):
-            setattr(a, f"{strides}_stride_{axis}", st)
-    if rotary_cos is not None:
-        a.cos, a.sin, a.cs_stride = rotary_cos.data_ptr(), rotary_sin.data_ptr(), rotary_cos.stride(0)
-    if geo.packed:
-        a.cu_seqlens = cu_seqlens.data_ptr()
-    if pos_offsets is not None:
-        a.pos_offsets = pos_offsets.data_ptr()
-    if position_ids is not None:
-        a.position_ids = position_ids.data_ptr()
-        if not geo.packed:
-            a.pid_stride_b, a.pid_stride_s = position_ids.stride()
-
-
 def _qk_norm_block(make, xs, ws, geo: _RotaryGeo, eps, unit_offset, interleaved):
     flags = (_capi_qk_norm.PFA_QKNORM_INTERLEAVED if interleaved else 0) | (_capi_qk_norm.PFA_QKNORM_UNIT_OFFSET if unit_offset else 0)
-    return make(flags=flags, eps=eps, B=geo.B, S=geo.S, total=geo.total, H0=xs[0].shape[1], H1=xs[1].shape[1] if len(xs) > 1 else 0, D=geo.D,
-                rot_dim=geo.rot_dim, max_pos=geo.max_pos, dtype=_DT[xs[0].dtype], w_dtype=_DT[ws[0].dtype], device_id=_device_index(xs[0].device))
+    return make(flags=flags, eps=eps, w_dtype=_DT[ws[0].dtype], **_rows_shape(xs, geo))
 
 
 def _qk_norm_call(xs, ws, geo: _RotaryGeo, eps, unit_offset, rotary_cos, rotary_sin, interleaved, cu_seqlens, pos_offsets, position_ids,
                   inplace, outs=None):
     """One ``pfa_qk_norm`` over the one or two tensors ``xs`` with the weights ``ws`` (checked by ``_qk_norm_geometry``) on their current
     stream, or on CPU tensors the plain-torch model.  -> the outputs: fresh tensors (or the caller's ``outs``), or ``xs`` in place."""
-    if outs is not None:
-        outs = list(outs)
-    elif inplace:
-        if not all(_rotary_meets_abi(x) for x in xs):
-            raise ValueError("qk_norm(inplace=True): the head dim must be contiguous, the base 16-byte aligned and every other stride "
-                             "a multiple of 8 elements")
-        outs = list(xs)
-    else:
-        outs = [_rotary_out(x, geo.packed) for x in xs]
+    outs = _rows_outs("qk_norm", xs, geo, inplace, outs)
     if xs[0].device.type == "cpu":
         _qk_norm_model(xs, outs, ws, float(eps), bool(unit_offset), rotary_cos, rotary_sin, bool(interleaved),
                        cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
         return outs
-    given, xs = xs, [x if _rotary_meets_abi(x) else x.contiguous() for x in xs]
-    gw, ws = ws, [_qk_norm_weight(w) for w in ws]
+    held = []
+    xs, ws = _meeting_abi(xs, held), _meeting_abi(ws, held, weights=True)
     a = _qk_norm_block(_capi_qk_norm.make_qk_norm_args, xs, ws, geo, eps, unit_offset, interleaved)
-    tensors = [(pre, pre, x) for pre, x in zip(("x0", "x1"), xs)] + [(pre + "_out", pre + "o", o) for pre, o in zip(("x0", "x1"), outs)]
-    _qk_norm_fill(a, geo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
+    _qk_norm_fill(a, geo, _fwd_tensors(xs, outs), rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
     for pre, w in zip(("w0", "w1"), ws):
         setattr(a, pre, w.data_ptr())
-    stream = torch.cuda.current_stream(xs[0].device)
-    _raise_status("pfa_qk_norm", _capi_qk_norm.load().pfa_qk_norm(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
-    _hold([x for x, g in zip(xs + ws, list(given) + list(gw)) if x is not g], stream)      # a copy made above must outlive the launch
+    _rows_launch("pfa_qk_norm", _capi_qk_norm, a, xs[0].device, held)
     return outs
 
 
@@ -1489,9 +1493,8 @@ def _qk_norm_bwd_call(xs, dys, ws, geo: _RotaryGeo, eps, unit_offset, rotary_cos
         _qk_norm_bwd_model(xs, dys, dxs, ws, dws, float(eps), bool(unit_offset), rotary_cos, rotary_sin, bool(interleaved),
                            cu_seqlens.tolist() if geo.packed else None, geo.S, None if pos_offsets is None else pos_offsets.tolist(), position_ids)
         return dxs, dws
-    given = list(xs) + list(dys) + list(ws)
-    xs, dys = ([t if _rotary_meets_abi(t) else t.contiguous() for t in ts] for ts in (xs, dys))
-    ws = [_qk_norm_weight(w) for w in ws]
+    held = []
+    xs, dys, ws = _meeting_abi(xs, held), _meeting_abi(dys, held), _meeting_abi(ws, held, weights=True)
     a = _qk_norm_block(_capi_qk_norm.make_qk_norm_bwd_args, xs, ws, geo, eps, unit_offset, interleaved)
     tensors = [(f"{n}{i}", f"{n}{i}", t) for n, ts in (("x", xs), ("dy", dys), ("dx", dxs)) for i, t in enumerate(ts)]
     _qk_norm_fill(a, geo, tensors, rotary_cos, rotary_sin, cu_seqlens, pos_offsets, position_ids)
@@ -1503,9 +1506,7 @@ def _qk_norm_bwd_call(xs, dys, ws, geo: _RotaryGeo, eps, unit_offset, rotary_cos
         raise ValueError("pfa_qk_norm_bwd: the shape is refused")
     workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=xs[0].device)
     a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
-    stream = torch.cuda.current_stream(xs[0].device)
-    _raise_status("pfa_qk_norm_bwd", _capi_qk_norm.load().pfa_qk_norm_bwd(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
-    _hold([t for t, g in zip(xs + dys + ws, given) if t is not g] + [workspace], stream)
+    _rows_launch("pfa_qk_norm_bwd", _capi_qk_norm, a, xs[0].device, held + [workspace])
     return dxs, dws
 
 
@@ -1588,12 +1589,8 @@ def _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v
     """The rotary keywords of the attention calls over a KV cache: None without them, else what ``rope_append`` takes.  Refused before
     anything else is looked at: one table without the other, ``rotary_interleaved`` / ``pos_offsets`` without tables, tables that are
     not fp32, and rotary without ``k_new`` / ``v_new`` and ``cache_seqlens`` (the positions are those of the appended rows)."""
-    if rotary_cos is None and rotary_sin is None:
-        if rotary_interleaved or pos_offsets is not None:
-            raise ValueError("rotary_interleaved / pos_offsets need rotary_cos and rotary_sin")
+    if not _tables_given(rotary_cos, rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets):
         return None
-    if rotary_cos is None or rotary_sin is None:
-        raise ValueError("rotary_cos and rotary_sin go together")
     _fp32_tables(rotary_cos, rotary_sin)
     if k_new is None or v_new is None or cache_seqlens is None:
         raise ValueError("rotary_cos / rotary_sin need k_new, v_new and cache_seqlens: rows are rotated at the positions they are appended at")

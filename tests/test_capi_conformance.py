@@ -1,10 +1,12 @@
-"""The one ABI conformance test (no GPU): ``include/pfa_hip.h`` against the ctypes binding in ``_capi`` and the built library.
+"""The one ABI conformance test (no GPU): every header under ``include/`` against the ctypes module that binds it (``HEADERS``:
+``pfa_hip.h`` and ``_capi``, and the side headers with ``_capi_sinks``, ``_capi_rotary`` and ``_capi_qk_norm``) and the built library.
 
-Every ``typedef struct pfa_*`` of the header has a mirror class and every mirror a struct, with the same field names in the same order
-and -- by one C program that ``gcc`` compiles -- the same ``sizeof`` and, per field, the same ``offsetof`` and size.  Every function
-the header declares has a row in ``_capi._PROTOTYPES`` with the header's return and parameter types, every row is declared, and every
-symbol resolves.  The sizes are pinned as literals too, so that a change made to both sides at once still shows, and the ABI version
-is pinned here and nowhere else.  The comparisons are plain functions over the tables, and three mutants show that they bite."""
+Every ``typedef struct pfa_*`` of a header has a mirror class in its module and every mirror a struct, with the same field names in the
+same order and -- by one C program per header that ``gcc`` compiles -- the same ``sizeof`` and, per field, the same ``offsetof`` and
+size.  Every function a header declares has a row in its module's ``_PROTOTYPES`` with the header's return and parameter types (a side
+header's may name ``_capi``'s structs), every row is declared, no two headers share an export, and every symbol resolves.  The sizes
+are pinned as literals too, so that a change made to both sides at once still shows, and the ABI version and the side headers' flag
+values are pinned here and nowhere else.  The comparisons are plain functions over the tables, and three mutants show that they bite."""
 
 from __future__ import annotations
 
@@ -17,14 +19,22 @@ import pytest
 
 from capi_testlib import lib  # noqa: F401  (the fixture)
 from conftest import REPO
-from photonic_flash_attention_amd import _capi
+from photonic_flash_attention_amd import _capi, _capi_qk_norm, _capi_rotary, _capi_sinks
 
 INCLUDE = os.path.join(REPO, "include")
+
+# every header with the module that binds it, and what a full reading of it finds: (structs, fields, prototypes)
+HEADERS = {"pfa_hip.h": (_capi, (14, 402, 88)), "pfa_hip_train_sinks.h": (_capi_sinks, (1, 19, 10)),
+           "pfa_hip_rotary.h": (_capi_rotary, (1, 36, 3)), "pfa_hip_qk_norm.h": (_capi_qk_norm, (2, 92, 7))}
 
 # sizeof of every argument and option block, as ABI v9 shipped them
 SIZES = dict(pfa_fa3_args=288, pfa_fa3_bwd_args=400, pfa_fa3_decode_args=256, pfa_fa3_prefill_varlen_args=224, pfa_fa3_cache_ext=16,
              pfa_fa3_tree_mask=24, pfa_kv_append_args=216, pfa_rope_append_args=328, pfa_attn_merge_args=624, pfa_page_copy_args=128,
-             pfa_fa3_varlen_args=184, pfa_fa3_varlen_bwd_args=288, pfa_fa3_kv_quant=40, pfa_fa3_sinks=16)
+             pfa_fa3_varlen_args=184, pfa_fa3_varlen_bwd_args=288, pfa_fa3_kv_quant=40, pfa_fa3_sinks=16,
+             pfa_fa3_sink_grad_args=120, pfa_rotary_args=240, pfa_qk_norm_args=264, pfa_qk_norm_bwd_args=360)
+# the flag bits of the side headers, as their #define lines spell them and as the bindings must have them
+FLAG_DEFINES = {"pfa_hip_rotary.h": (_capi_rotary, {"PFA_ROTARY_INTERLEAVED": 1, "PFA_ROTARY_CONJUGATE": 2}),
+                "pfa_hip_qk_norm.h": (_capi_qk_norm, {"PFA_QKNORM_INTERLEAVED": 1, "PFA_QKNORM_UNIT_OFFSET": 2})}
 
 SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "char*": C.c_char_p,
            "void*": C.c_void_p, "float*": C.c_void_p, "int32_t*": C.POINTER(C.c_int32), "double*": C.POINTER(C.c_double)}
@@ -49,9 +59,9 @@ def parse_header(text):
     return structs, {k: (v[0], list(v[1:])) for k, v in protos.items()}
 
 
-def c_layout(structs, workdir):
+def c_layout(header_file, structs, workdir):
     """-> {struct: (sizeof, [(field, offsetof, sizeof the field)])} from one C program over the header."""
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "pfa_hip.h"', "int main(void) {"]
+    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{header_file}"', "int main(void) {"]
     for s, fields in structs.items():
         lines.append(f'  printf("{s} %zu\\n", sizeof({s}));')
         lines += [f'  printf("{s}.{f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)0)->{f}));' for f in fields]
@@ -78,7 +88,8 @@ def snake(cls_name):
 
 def mirrors_of(module):
     """{C struct name: mirror class} of every ``ctypes.Structure`` a module defines."""
-    return {snake(n): t for n, t in vars(module).items() if isinstance(t, type) and issubclass(t, C.Structure) and t is not C.Structure}
+    return {snake(n): t for n, t in vars(module).items()
+            if isinstance(t, type) and issubclass(t, C.Structure) and t.__module__ == module.__name__}      # not what it imports
 
 
 def struct_mismatches(structs, layout, mirrors, sizes):
@@ -126,39 +137,68 @@ def prototype_mismatches(protos, table, mirrors):
 
 # --- the tests ------------------------------------------------------------------------------------------------------------------------
 
+def read_header(header_file, workdir):
+    """(structs, prototypes, C layout) of one header."""
+    structs, protos = parse_header(open(os.path.join(INCLUDE, header_file)).read())
+    return structs, protos, c_layout(header_file, structs, workdir)
+
+
 @pytest.fixture(scope="module")
-def header(tmp_path_factory):
-    """(structs, prototypes, C layout) of the header: parsed and compiled once."""
-    structs, protos = parse_header(open(os.path.join(INCLUDE, "pfa_hip.h")).read())
-    return structs, protos, c_layout(structs, str(tmp_path_factory.mktemp("layout")))
+def headers(tmp_path_factory):
+    """{header file: (structs, prototypes, C layout)} of every header: each parsed and compiled once."""
+    return {h: read_header(h, str(tmp_path_factory.mktemp("layout"))) for h in HEADERS}
 
 
-def test_the_header_is_read_in_full(header):
-    structs, protos, layout = header
-    assert len(structs) == 14 and sum(len(f) for f in structs.values()) == 402 and len(protos) == 88
-    assert set(layout) == set(structs) and all(len(layout[s][1]) == len(structs[s]) for s in structs)
+@pytest.fixture(scope="module")
+def header(headers):
+    return headers["pfa_hip.h"]
+
+
+def sizes_of(structs):
+    return {s: n for s, n in SIZES.items() if s in structs}
+
+
+def test_the_header_is_read_in_full(headers):
+    for h, (structs, protos, layout) in headers.items():
+        assert (len(structs), sum(len(f) for f in structs.values()), len(protos)) == HEADERS[h][1], h
+        assert set(layout) == set(structs) and all(len(layout[s][1]) == len(structs[s]) for s in structs), h
+    structs, protos, _ = headers["pfa_hip.h"]
     assert structs["pfa_fa3_cache_ext"] == ["size", "flags", "window", "reserved"]
     assert protos["pfa_abi_version"] == ("int", []) and protos["pfa_status_string"] == ("char*", ["int"])
     assert protos["pfa_fa3_prefill_split_sink_describe"] == ("int", ["pfa_fa3_decode_args*", "int32_t", "pfa_fa3_sinks*", "char*", "size_t",
                                                                      "int32_t*"])
+    assert list(headers["pfa_hip_train_sinks.h"][0]) == ["pfa_fa3_sink_grad_args"]
+    assert list(headers["pfa_hip_rotary.h"][0]) == ["pfa_rotary_args"]
+    assert sorted(headers["pfa_hip_rotary.h"][1]) == ["pfa_rotary", "pfa_rotary_check", "pfa_rotary_describe"]
+    assert list(headers["pfa_hip_qk_norm.h"][0]) == ["pfa_qk_norm_args", "pfa_qk_norm_bwd_args"]
+    assert sorted(headers["pfa_hip_qk_norm.h"][1]) == ["pfa_qk_norm", "pfa_qk_norm_bwd", "pfa_qk_norm_bwd_check", "pfa_qk_norm_bwd_describe",
+                                                       "pfa_qk_norm_bwd_workspace_bytes", "pfa_qk_norm_check", "pfa_qk_norm_describe"]
 
 
-def test_every_struct_matches_its_mirror_and_its_pinned_size(header):
-    structs, _, layout = header
-    assert struct_mismatches(structs, layout, mirrors_of(_capi), SIZES) == []
+def test_every_struct_matches_its_mirror_and_its_pinned_size(headers):
+    for h, (structs, _, layout) in headers.items():
+        assert struct_mismatches(structs, layout, mirrors_of(HEADERS[h][0]), sizes_of(structs)) == [], h
+    assert set(SIZES) == {s for structs, _, _ in headers.values() for s in structs}
 
 
-def test_every_prototype_matches_the_header_and_resolves(header, lib):
-    _, protos, _ = header
-    assert prototype_mismatches(protos, _capi._PROTOTYPES, mirrors_of(_capi)) == []
-    assert set(_capi.EXPORTS) == set(protos)
-    for name in protos:
-        assert getattr(lib, name) is not None
+def test_every_prototype_matches_the_header_and_resolves(headers, lib):
+    seen = set()
+    for h, (_, protos, _) in headers.items():
+        module = HEADERS[h][0]
+        assert prototype_mismatches(protos, module._PROTOTYPES, dict(mirrors_of(_capi), **mirrors_of(module))) == [], h
+        assert set(module.EXPORTS) == set(protos) and not seen & set(protos), h         # no two headers share an export
+        seen |= set(protos)
+        for name in protos:
+            assert getattr(lib, name) is not None
 
 
 def test_abi_version(lib):
     assert lib.pfa_abi_version() == _capi.PFA_ABI_VERSION == 9
     assert re.search(r"^#define PFA_ABI_VERSION 9$", open(os.path.join(INCLUDE, "pfa_hip.h")).read(), flags=re.M)
+    for h, (module, flags) in FLAG_DEFINES.items():
+        text = open(os.path.join(INCLUDE, h)).read()
+        for name, value in flags.items():
+            assert re.search(rf"^#define {name}\s+{value}u$", text, flags=re.M) and getattr(module, name) == value, name
 
 
 # --- mutants: each hands a checker a spoilt table and expects the mismatch by name --------------------------------------------------------
@@ -173,7 +213,7 @@ def test_mutant_two_fields_swapped_is_named(header):
     i, j = [n for n, _ in f].index("dq"), [n for n, _ in f].index("dk")            # same type: sizes and offsets stay, only the order tells
     f[i], f[j] = f[j], f[i]
     mirrors = dict(mirrors_of(_capi), pfa_fa3_bwd_args=_mutant(_capi.PfaFa3BwdArgs, f))
-    bad = struct_mismatches(structs, layout, mirrors, SIZES)
+    bad = struct_mismatches(structs, layout, mirrors, sizes_of(structs))
     assert len(bad) == 1 and bad[0].startswith("pfa_fa3_bwd_args: field names") and "('dk', 'dq')" in bad[0]
 
 
@@ -181,7 +221,7 @@ def test_mutant_one_int32_widened_is_named(header):
     structs, _, layout = header
     f = [(n, C.c_int64 if n == "page_size" else t) for n, t in _capi.PfaFa3DecodeArgs._fields_]
     mirrors = dict(mirrors_of(_capi), pfa_fa3_decode_args=_mutant(_capi.PfaFa3DecodeArgs, f))
-    bad = struct_mismatches(structs, layout, mirrors, SIZES)
+    bad = struct_mismatches(structs, layout, mirrors, sizes_of(structs))
     assert any(b.startswith("pfa_fa3_decode_args.page_size: offset 248 size 4 in C, offset 248 size 8") for b in bad), bad
     assert any(b.startswith("pfa_fa3_decode_args: sizeof 256 in C, 264 in the mirror") for b in bad), bad
     assert all(b.startswith("pfa_fa3_decode_args") for b in bad)

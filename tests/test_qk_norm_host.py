@@ -1,6 +1,6 @@
 """CPU-side tests (no GPU) of QK-norm fused with the rotary embedding of the training calls (``pfa_qk_norm*`` / ``pfa_qk_norm_bwd*``, ABI v9
 additive, declared in ``include/pfa_hip_qk_norm.h`` and bound by ``_capi_qk_norm``; ``ops.qk_norm``; the ``q_norm_weight=`` keywords of
-``ops.fa3_attention`` and ``ops.fa3_varlen_attention``; ``qk_norm=`` on the modules): the header against its binding, every validation
+``ops.fa3_attention`` and ``ops.fa3_varlen_attention``; ``qk_norm=`` on the modules): every validation
 rule in the order the header states (pairwise: of two broken rules the earlier wins), the launch descriptions, the workspace, the
 plain-torch models (``ops.qk_norm`` on CPU tensors: the executable specification the GPU tests compare the kernels with) against fp64
 element by element under the bounds derived in tests/qk_norm_testlib.py, mutants of the rule that must each miss those bounds, and the
@@ -13,25 +13,19 @@ from __future__ import annotations
 
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import pytest
 import torch
 
 import qk_norm_testlib as Q
 from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, OK, SHAPE, SIZE, STRIDE, built_lib, name_of
-from conftest import REPO
-from photonic_flash_attention_amd import _capi, _capi_qk_norm, _capi_rotary, _capi_sinks, ops
+from photonic_flash_attention_amd import _capi, _capi_qk_norm, ops
 from photonic_flash_attention_amd.core.flash_attention_3 import FlashAttention3
 from photonic_flash_attention_amd.core.hybrid_router import HybridFlashAttention
 from photonic_flash_attention_amd.integration.pytorch.modules import PhotonicFlashAttention, PhotonicMultiHeadAttention
-from test_capi_conformance import mirrors_of, parse_header, prototype_mismatches
 
 IL, UNIT = _capi_qk_norm.PFA_QKNORM_INTERLEAVED, _capi_qk_norm.PFA_QKNORM_UNIT_OFFSET
 EPS = 1e-6
-EXPORTS = ["pfa_qk_norm", "pfa_qk_norm_bwd", "pfa_qk_norm_bwd_check", "pfa_qk_norm_bwd_describe", "pfa_qk_norm_bwd_workspace_bytes",
-           "pfa_qk_norm_check", "pfa_qk_norm_describe"]
 
 
 def _shape(over):
@@ -70,34 +64,6 @@ INPLACE = dict(x0_out=0x100000, x1_out=0x300000)
 def lib():
     built_lib()
     return _capi_qk_norm.load()
-
-
-def test_the_header_of_its_own_matches_its_binding_and_the_library(lib, tmp_path):
-    text = open(os.path.join(REPO, "include", "pfa_hip_qk_norm.h")).read()
-    structs, protos = parse_header(text)
-    assert list(structs) == ["pfa_qk_norm_args", "pfa_qk_norm_bwd_args"] and sorted(protos) == EXPORTS
-    assert "#define PFA_QKNORM_INTERLEAVED 1u" in text and "#define PFA_QKNORM_UNIT_OFFSET 2u" in text and (IL, UNIT) == (1, 2)
-    mirrors = {"pfa_qk_norm_args": _capi_qk_norm.PfaQkNormArgs, "pfa_qk_norm_bwd_args": _capi_qk_norm.PfaQkNormBwdArgs}
-    assert mirrors == mirrors_of(_capi_qk_norm)
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "pfa_hip_qk_norm.h"', "int main(void) {"]
-    for s, t in mirrors.items():
-        assert [f for f, _ in t._fields_] == structs[s]
-        lines.append(f'  printf("%zu\\n", sizeof({s}));')
-        lines += [f'  printf("%zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)0)->{f}));' for f, _ in t._fields_]
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.split()
-    for (s, t), pinned in zip(mirrors.items(), (264, 360)):
-        n = 1 + 2 * len(t._fields_)
-        mine, out = out[:n], out[n:]
-        assert int(mine[0]) == C.sizeof(t) == pinned, s
-        assert [(int(a), int(b)) for a, b in zip(mine[1::2], mine[2::2])] == [(getattr(t, f).offset, getattr(t, f).size) for f, _ in t._fields_]
-    assert prototype_mismatches(protos, _capi_qk_norm._PROTOTYPES, dict(mirrors_of(_capi), **mirrors)) == []
-    others = set(_capi.EXPORTS) | set(_capi_sinks.EXPORTS) | set(_capi_rotary.EXPORTS)
-    assert set(_capi_qk_norm.EXPORTS) == set(protos) and not set(protos) & others
-    for name in protos:
-        assert getattr(lib, name) is not None
-    assert lib.pfa_abi_version() == 9
 
 
 # every rule of the header's "Field rules", in the order the errors are reported (the size rule is checked apart)

@@ -1,25 +1,21 @@
 """CPU-side tests (no GPU) of the rotary embedding for the training calls (``pfa_rotary*``, ABI v9 additive, declared in
 ``include/pfa_hip_rotary.h`` and bound by ``_capi_rotary``; ``ops.apply_rotary``; the ``rotary_*=`` keywords of ``ops.fa3_attention`` and
-``ops.fa3_varlen_attention``; ``rotary=`` on the modules): the header against its binding, every validation rule in the order the header
-states, the launch description, the plain-torch model (``ops.apply_rotary`` on CPU tensors: the executable specification the GPU
+``ops.fa3_varlen_attention``; ``rotary=`` on the modules): every validation rule in the order the header
+states (the header against its binding is tests/test_capi_conformance.py's), the launch description, the plain-torch model (``ops.apply_rotary`` on CPU tensors: the executable specification the GPU
 tests compare the kernel with) against fp64 pair by pair, forward and conjugate, and the refusals of ``ops`` and of the modules."""
 
 from __future__ import annotations
 
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import pytest
 import torch
 
 from capi_testlib import ALIGN, DTYPE, FLAGS, HEAD_DIM, NULL, OK, SHAPE, SIZE, STRIDE, built_lib, name_of
-from conftest import REPO
-from photonic_flash_attention_amd import _capi, _capi_rotary, _capi_sinks, _models, ops
+from photonic_flash_attention_amd import _capi, _capi_rotary, _models, ops
 from photonic_flash_attention_amd.core.flash_attention_3 import FlashAttention3
 from photonic_flash_attention_amd.integration.pytorch.modules import PhotonicFlashAttention, PhotonicMultiHeadAttention
-from test_capi_conformance import mirrors_of, parse_header, prototype_mismatches
 
 IL, CONJ = _capi_rotary.PFA_ROTARY_INTERLEAVED, _capi_rotary.PFA_ROTARY_CONJUGATE
 NAN = float("nan")
@@ -54,31 +50,6 @@ def lib():
 
 def _check(lib, a):
     return lib.pfa_rotary_check(C.byref(a))
-
-
-def test_the_header_of_its_own_matches_its_binding_and_the_library(lib, tmp_path):
-    # include/pfa_hip_rotary.h against _capi_rotary, as tests/test_train_sinks_host.py holds its header: the struct's fields, offsets and
-    # size (pinned: 240), every prototype, every symbol; and pfa_hip.h's ABI version is what it was
-    text = open(os.path.join(REPO, "include", "pfa_hip_rotary.h")).read()
-    structs, protos = parse_header(text)
-    assert list(structs) == ["pfa_rotary_args"] and sorted(protos) == ["pfa_rotary", "pfa_rotary_check", "pfa_rotary_describe"]
-    assert "#define PFA_ROTARY_INTERLEAVED 1u" in text and "#define PFA_ROTARY_CONJUGATE   2u" in text and (IL, CONJ) == (1, 2)
-    t = _capi_rotary.PfaRotaryArgs
-    assert [f for f, _ in t._fields_] == structs["pfa_rotary_args"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "pfa_hip_rotary.h"', "int main(void) {",
-             '  printf("%zu\\n", sizeof(pfa_rotary_args));']
-    lines += [f'  printf("%zu %zu\\n", offsetof(pfa_rotary_args, {f}), sizeof(((pfa_rotary_args*)0)->{f}));' for f, _ in t._fields_]
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.split()
-    assert int(out[0]) == C.sizeof(t) == 240
-    assert [(int(a), int(b)) for a, b in zip(out[1::2], out[2::2])] == [(getattr(t, f).offset, getattr(t, f).size) for f, _ in t._fields_]
-    mirrors = dict(mirrors_of(_capi), **mirrors_of(_capi_rotary))
-    assert prototype_mismatches(protos, _capi_rotary._PROTOTYPES, mirrors) == []
-    assert set(_capi_rotary.EXPORTS) == set(protos) and not set(protos) & (set(_capi.EXPORTS) | set(_capi_sinks.EXPORTS))
-    for name in protos:
-        assert getattr(lib, name) is not None
-    assert lib.pfa_abi_version() == 9
 
 
 # every rule of the header's "Field rules", in the order the errors are reported (the size rule is checked apart)

@@ -3,23 +3,19 @@ ABI v9 additive, declared in ``include/pfa_hip_train_sinks.h`` and bound by ``_c
 ``_check`` exports in their documented order, a NULL block agreeing with the sibling, the describe names and the sink-grad workspace,
 ``ops``' refusals before anything is enqueued, the modules' state dicts -- and the plain-torch model of ``fa3_sink_grad`` (the
 executable specification of the kernel) against fp64 autograd of an explicit softmax with one more key, with two mutants that must be
-caught.  The new header is held against its binding as tests/test_capi_conformance.py holds ``include/pfa_hip.h`` against ``_capi``."""
+caught.  The header is held against its binding by tests/test_capi_conformance.py."""
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
 from capi_testlib import ALIGN, DTYPE, FLAGS, NULL, OK, SHAPE, SIZE, STRIDE, built_lib, fa3_args, name_of, sinks, varlen_args
-from conftest import REPO
 from photonic_flash_attention_amd import _capi, _capi_sinks, _models, ops
 from photonic_flash_attention_amd.core.flash_attention_3 import FlashAttention3
 from photonic_flash_attention_amd.integration.pytorch.modules import PhotonicFlashAttention, PhotonicMultiHeadAttention
-from test_capi_conformance import mirrors_of, parse_header, prototype_mismatches
 
 INF = float("inf")
 
@@ -45,28 +41,6 @@ def sink_grad_args(**over):
 def lib():
     built_lib()
     return _capi_sinks.load()
-
-
-def test_the_header_of_its_own_matches_its_binding_and_the_library(lib, tmp_path):
-    # include/pfa_hip_train_sinks.h against _capi_sinks, as tests/test_capi_conformance.py holds include/pfa_hip.h against _capi: the
-    # struct's fields, offsets and size (pinned: 120), every prototype, every symbol
-    structs, protos = parse_header(open(os.path.join(REPO, "include", "pfa_hip_train_sinks.h")).read())
-    assert list(structs) == ["pfa_fa3_sink_grad_args"] and len(protos) == 10
-    t = _capi_sinks.PfaFa3SinkGradArgs
-    assert [f for f, _ in t._fields_] == structs["pfa_fa3_sink_grad_args"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "pfa_hip_train_sinks.h"', "int main(void) {",
-             '  printf("%zu\\n", sizeof(pfa_fa3_sink_grad_args));']
-    lines += [f'  printf("%zu %zu\\n", offsetof(pfa_fa3_sink_grad_args, {f}), sizeof(((pfa_fa3_sink_grad_args*)0)->{f}));' for f, _ in t._fields_]
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
-    subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.split()
-    assert int(out[0]) == C.sizeof(t) == 120
-    assert [(int(a), int(b)) for a, b in zip(out[1::2], out[2::2])] == [(getattr(t, f).offset, getattr(t, f).size) for f, _ in t._fields_]
-    mirrors = dict(mirrors_of(_capi), **mirrors_of(_capi_sinks))
-    assert prototype_mismatches(protos, _capi_sinks._PROTOTYPES, mirrors) == []
-    assert set(_capi_sinks.EXPORTS) == set(protos) and not set(protos) & set(_capi.EXPORTS)
-    for name in protos:
-        assert getattr(lib, name) is not None
 
 
 def test_a_null_block_is_the_sibling_call(lib):
