@@ -307,6 +307,60 @@ def _qk_norm_model(xs, outs, ws, eps, unit_offset, cos, sin, interleaved, cu, ma
                 o[b, :, :rows] = _qkn_forward_rows(x[b, :, :rows].transpose(0, 1), w, eps, unit_offset, c, s, interleaved).transpose(0, 1)
 
 
+def _norm_rope_append_model(k_new, v_new, k_cache, v_cache, q_weight, k_weight, eps, unit_offset, cos, sin, lens, cu, max_seqlen_q,
+                            block_table, offsets, interleaved, q=None, q_out=None, k_descale=None, v_descale=None) -> None:
+    """``pfa_norm_rope_append``'s rule in plain torch: the executable specification, and what ``norm_rope_append`` runs on CPU tensors.
+    Composed of the models it fuses and of nothing else: sequences, positions and clamps as ``_rope_append_model`` derives them; a tensor
+    with a weight through ``_qkn_forward_rows`` (``pfa_qk_norm``'s forward rule: norm, rotation on the fp32 ``n``, one narrowing), a
+    tensor without one through ``_rope_rotate`` (or untouched without tables); the placement ``_kv_append_model``'s, or with descales
+    ``_kv_append_q8_model``'s -- ``quantize_kv`` of the 16-bit rows -- one sequence at a time.  ``lens`` / ``cu`` / ``offsets`` are host
+    lists; ``cos`` / ``sin`` None: no rotation; the tensors as in ``norm_rope_append``."""
+    paged = block_table is not None
+    Smax = block_table.shape[1] * k_cache.shape[2] if paged else k_cache.shape[2]
+    total = k_new.shape[0]
+    q_src = None if q is None else q.clone()                                   # q_out may be q
+    k_rot = k_new.clone()                                                      # rows no sequence covers stay as they are, unread
+
+    def rows16(x, w, c, s):
+        if w is not None:
+            return _qkn_forward_rows(x, w, eps, unit_offset, c, s, interleaved)
+        return x.clone() if c is None else _rope_rotate(x, c, s, interleaved)
+
+    for b, n in enumerate(lens):
+        len_b = min(max(n, 0), Smax)
+        if cu is not None:
+            s_b = min(max(cu[b], 0), total)
+            e_b = min(max(cu[b + 1], s_b), total)
+            sq = min(e_b - s_b, max_seqlen_q)
+        else:
+            sq = max_seqlen_q
+        if sq < 1:
+            continue
+        c = s = None
+        if cos is not None:
+            pos = torch.arange(len_b - sq, len_b, dtype=torch.int64) + (0 if offsets is None else offsets[b])
+            pos.clamp_(0, cos.shape[0] - 1)                                    # rows in front of key 0 too: their Q is still written
+            c, s = cos[pos], sin[pos]
+        if cu is not None:
+            rows = slice(s_b, s_b + sq)
+            k_rot[rows] = rows16(k_new[rows], k_weight, c, s)
+            if q is not None:
+                q_out[rows] = rows16(q_src[rows], q_weight, c, s)
+            one = (k_rot, v_new)
+        else:
+            k_rot[b] = rows16(k_new[b].transpose(0, 1), k_weight, c, s).transpose(0, 1)
+            if q is not None:
+                q_out[b] = rows16(q_src[b].transpose(0, 1), q_weight, c, s).transpose(0, 1)
+            one = (k_rot[b:b + 1], v_new[b:b + 1])
+        caches = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
+        where = ([n], None if cu is None else [cu[b], cu[b + 1]], max_seqlen_q, block_table[b:b + 1] if paged else None)
+        if k_descale is None:
+            _kv_append_model(*one, *caches, *where)
+        else:
+            kd, vd = (d[b:b + 1] if d.dim() == 2 else d for d in (k_descale, v_descale))
+            _kv_append_q8_model(*one, *caches, kd, vd, *where)
+
+
 def _qk_norm_bwd_model(xs, dys, dxs, ws, dws, eps, unit_offset, cos, sin, interleaved, cu, max_seqlen, offsets, position_ids) -> None:
     """``pfa_qk_norm_bwd``'s rule in plain torch: ``dxs`` (the dtype) and ``dws`` (fp32 ``[D]``, overwritten) from ``xs``, ``dys`` and
     the forward's other operands.  The weight gradient is summed in the kernels' order: per tensor and sequence, chunks of

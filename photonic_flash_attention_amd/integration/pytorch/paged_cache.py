@@ -572,7 +572,9 @@ class PagedKVCache:
     def write_step(self, k_new: torch.Tensor, v_new: torch.Tensor, q_lens: Optional[Sequence[int]] = None, slots: Slots = None, *,
                    cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None, q: Optional[torch.Tensor] = None,
                    rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-                   pos_offsets: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+                   pos_offsets: Optional[torch.Tensor] = None, q_norm_weight: Optional[torch.Tensor] = None,
+                   k_norm_weight: Optional[torch.Tensor] = None, qk_norm_eps: float = 1e-6,
+                   qk_norm_unit_offset: bool = False) -> Optional[torch.Tensor]:
         """The device half of an append (``ops.kv_append``, one launch of the HIP copy kernel): write the packed ``k_new`` / ``v_new``
         ``[total, Hkv, D]`` of a ragged step to where the cache's own table and lengths say, sequence i bringing ``q_lens[i]`` rows.
         Call ``advance`` first: the lengths count the step's rows, and row j of sequence i goes to key ``length - q_lens[i] + j``.  Does
@@ -585,13 +587,19 @@ class PagedKVCache:
         ``ops.rope_append`` instead: the K rows are rotated at the positions they are written to, and the packed ``q [total, H, D]``, if
         given, is rotated into a fresh buffer that is returned (else None): the tensor ``prefill_varlen`` then takes.
 
+        With ``q_norm_weight=`` / ``k_norm_weight=`` (either or both; ``qk_norm_eps``, ``qk_norm_unit_offset`` as in ``ops.qk_norm``) the
+        launch is ``ops.norm_rope_append``: QK-norm of ``q`` and of the K rows in front of the rotation (if any), still one launch.
+
         With ``copy_on_write`` one ``ops.page_copy`` over the pending table (``cow_pairs`` / ``cow_rows``, whatever slots the call
         names) is enqueued in front: the copies the last ``advance`` calls for, or nothing when the table is empty.  It reads the
         device table, so a captured ``write_step`` + attention replays through forks."""
         rotary = rotary_cos is not None or rotary_sin is not None
-        if self._fp8 and (rotary or q is not None):
+        norm = q_norm_weight is not None or k_norm_weight is not None
+        if self._fp8 and (rotary or norm or q is not None):
             raise ValueError("write_step: rotary is not fused into the quantising append of an FP8 cache; rotate q and k_new first")
-        if not rotary and (q is not None or rotary_interleaved or pos_offsets is not None):
+        if qk_norm_unit_offset and not norm:
+            raise ValueError("qk_norm_unit_offset needs q_norm_weight or k_norm_weight")
+        if not rotary and (rotary_interleaved or pos_offsets is not None or (q is not None and not norm)):
             raise ValueError("q, rotary_interleaved and pos_offsets need rotary_cos and rotary_sin")
         if rotary and (rotary_cos is None or rotary_sin is None):
             raise ValueError("rotary_cos and rotary_sin go together")
@@ -601,6 +609,11 @@ class PagedKVCache:
         cu_seqlens_q, max_seqlen_q = self._cu(q_lens, cu_seqlens_q, max_seqlen_q, table.shape[0], k_new.shape[0], "k_new")
         if self._cow:
             ops.page_copy(*self._copy_pools(), self._cow_pairs, rows=self._cow_rows)
+        if norm:
+            return ops.norm_rope_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens, q=q,
+                                        q_weight=q_norm_weight, k_weight=k_norm_weight, eps=qk_norm_eps, unit_offset=qk_norm_unit_offset,
+                                        rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                                        pos_offsets=pos_offsets, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, block_table=table)
         if rotary:
             return ops.rope_append(k_new, v_new, self._k.transpose(1, 2), self._v.transpose(1, 2), cache_seqlens=lens,
                                    rotary_cos=rotary_cos, rotary_sin=rotary_sin, q=q, rotary_interleaved=rotary_interleaved,

@@ -21,8 +21,8 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
-from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _page_copy_model,      # noqa: F401
+from . import _capi, _capi_norm_rope_append, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
+from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
                       _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
@@ -1142,6 +1142,28 @@ def _tables_given(rotary_cos, rotary_sin, **dependent) -> bool:
     return True
 
 
+def _append_q_operands(q, q_out, k_new, geo: _AppendOperands):
+    """What ``rope_append`` and ``norm_rope_append`` check about the optional ``q`` / ``q_out`` against the step's rows.  -> ``(H, q_out)``:
+    0 and None without q; else q's heads and the given ``q_out`` or a fresh one in the layout the attention calls prefer."""
+    if q is None:
+        if q_out is not None:
+            raise ValueError("q_out without q")
+        return 0, None
+    H = q.shape[1] if q.dim() >= 2 else 0
+    want = (geo.total, H, geo.D) if geo.ragged else (geo.B, H, geo.max_seqlen_q, geo.D)
+    if q.shape != want or H < 1:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_new {tuple(k_new.shape)}: q must be "
+                         + ("[total, H, D]" if geo.ragged else "[B, H, Sq, D]") + " over k_new's rows and head dim")
+    if q.dtype != k_new.dtype:
+        raise ValueError("q must have k_new's dtype")
+    if q_out is None:
+        q_out = torch.empty(want, dtype=q.dtype, device=q.device) if geo.ragged else \
+            torch.empty((geo.B, geo.max_seqlen_q, H, geo.D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+    elif q_out.shape != q.shape or q_out.dtype != q.dtype:
+        raise ValueError("q_out must have q's shape and dtype")
+    return H, q_out
+
+
 def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
                 rotary_cos: torch.Tensor, rotary_sin: torch.Tensor, q: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None,
                 rotary_interleaved: bool = False, pos_offsets: Optional[torch.Tensor] = None,
@@ -1173,23 +1195,7 @@ def rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
     ragged, B, D, total, max_seqlen_q = geo.ragged, geo.B, geo.D, geo.total, geo.max_seqlen_q
     rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, D)
     _pos_offsets_operand(pos_offsets, B)
-    H = 0
-    if q is None:
-        if q_out is not None:
-            raise ValueError("q_out without q")
-    else:
-        H = q.shape[1] if q.dim() >= 2 else 0
-        want = (total, H, D) if ragged else (B, H, max_seqlen_q, D)
-        if q.shape != want or H < 1:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_new {tuple(k_new.shape)}: q must be "
-                             + ("[total, H, D]" if ragged else "[B, H, Sq, D]") + " over k_new's rows and head dim")
-        if q.dtype != k_new.dtype:
-            raise ValueError("q must have k_new's dtype")
-        if q_out is None:
-            q_out = torch.empty(want, dtype=q.dtype, device=q.device) if ragged else \
-                torch.empty((B, max_seqlen_q, H, D), dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        elif q_out.shape != q.shape or q_out.dtype != q.dtype:
-            raise ValueError("q_out must have q's shape and dtype")
+    H, q_out = _append_q_operands(q, q_out, k_new, geo)
     if k_new.device.type == "cpu":
         _rope_append_model(k_new, v_new, k_cache, v_cache, rotary_cos, rotary_sin, cache_seqlens.tolist(),
                            cu_seqlens_q.tolist() if ragged else None, max_seqlen_q, block_table,
@@ -1574,6 +1580,101 @@ def qk_norm(q: torch.Tensor, k: Optional[torch.Tensor] = None, *, q_weight: torc
     return outs[0] if k is None else tuple(outs)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# QK-norm, rotary and the FP8 store fused into the KV-cache append (include/pfa_hip_norm_rope_append.h, pfa_norm_rope_append)
+
+def _norm_weights(q, q_weight, k_weight, eps, unit_offset, D: int, like: torch.Tensor, tables: bool) -> list:
+    """What ``norm_rope_append`` checks about its norm arguments against head dim D and the rows' tensor ``like``.  -> the given weights."""
+    if D not in (64, 128):
+        raise ValueError(f"head dim {D}: norm_rope_append takes 64 or 128, the attention's head dims")
+    if q_weight is not None and q is None:
+        raise ValueError("q_weight without q")
+    ws = [w for w in (q_weight, k_weight) if w is not None]
+    if not ws:
+        if unit_offset:
+            raise ValueError("unit_offset needs q_weight or k_weight")
+        if not tables:
+            raise ValueError("norm_rope_append without a weight and without rotary tables has nothing to do: that call is kv_append")
+    for w in ws:
+        if not isinstance(w, torch.Tensor) or w.shape != (D,) or w.dtype not in (torch.float32, like.dtype) or w.device != like.device:
+            raise ValueError(f"a norm weight must be a [{D}] tensor on k_new's device, fp32 or of k_new's dtype")
+    if len(ws) == 2 and ws[0].dtype != ws[1].dtype:
+        raise ValueError("q_weight and k_weight must share a dtype")
+    if not (float(eps) >= 0.0 and math.isfinite(float(eps))):
+        raise ValueError(f"eps {eps!r}: must be finite and not negative")
+    return ws
+
+
+def norm_rope_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
+                     q: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None, q_weight: Optional[torch.Tensor] = None,
+                     k_weight: Optional[torch.Tensor] = None, eps: float = 1e-6, unit_offset: bool = False,
+                     rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
+                     pos_offsets: Optional[torch.Tensor] = None, cu_seqlens_q: Optional[torch.Tensor] = None,
+                     max_seqlen_q: Optional[int] = None, block_table: Optional[torch.Tensor] = None,
+                     k_descale: Optional[torch.Tensor] = None, v_descale: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """The write side of a serving step in ONE launch (``pfa_norm_rope_append``): QK-norm of the step's Q and new K (``qk_norm``'s
+    forward rule; Qwen3, Gemma-3), the rotary embedding of both at the positions the rows are appended at (``rope_append``), K and V
+    placed into the cache -- 16-bit, or FP8 with ``k_descale=, v_descale=`` (``kv_append``'s quantising store) -- and Q written to
+    ``q_out``, which is returned as ``rope_append`` returns it.
+
+    k_new / v_new, the caches, ``block_table``, ``cache_seqlens`` (the lengths AFTER the step), ``cu_seqlens_q``, ``max_seqlen_q``, ``q`` /
+    ``q_out``, the tables, ``rotary_interleaved`` and ``pos_offsets`` are ``rope_append``'s, with D 64 or 128; the tables are optional (none:
+    no rotation).  ``q_weight`` / ``k_weight``: ``[D]``, fp32 or of the rows' dtype, each optional -- a tensor without a weight is not
+    normalised (``n = x`` exactly), so with neither the call returns ``rope_append``'s bits; ``eps`` and ``unit_offset`` (Gemma: ``1 + w``)
+    as in ``qk_norm``.  V is only placed.  A call with neither a weight nor tables is refused: it is ``kv_append``.
+
+    FP8 caches (``torch.float8_e4m3fn``, with contiguous fp32 descales ``[Hkv]`` or ``[B, Hkv]``; required then, refused otherwise): the
+    16-bit result of K and the raw V are stored as ``e4m3fn(clamp(float(x16) / descale, -448, 448))`` -- quantisation starts from the
+    value already narrowed to 16 bits, so the cache bytes are those of the quantising ``kv_append`` run on what the 16-bit call would have
+    stored.  Q stays 16-bit.  The FP8 attention calls (``fa3_decode`` / ``fa3_prefill_cache`` / ``fa3_prefill_varlen`` with descales, without
+    ``k_new``) read the result.
+
+    On device tensors one launch of a HIP kernel whose grid depends on host shapes only: no host synchronisation, capturable, and valid
+    while cu_seqlens_q, lengths, offsets, table, tables, weights, descales and inputs change between replays.  On CPU tensors the same
+    rule runs in plain torch, bit for bit (``_models._norm_rope_append_model``, the executable specification)."""
+    if not all(isinstance(t, torch.Tensor) for t in (k_new, v_new, k_cache, v_cache)):
+        raise ValueError("k_new, v_new, k_cache, v_cache must be tensors")
+    tables = _tables_given(rotary_cos, rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets)
+    if tables:
+        _fp32_tables(rotary_cos, rotary_sin)
+    fp8 = k_cache.dtype == FP8 or v_cache.dtype == FP8
+    others = [t for t in (rotary_cos, rotary_sin, q, q_out, pos_offsets) if isinstance(t, torch.Tensor)]
+    geo = _append_operands("pfa_norm_rope_append", k_new, v_new, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
+                           others, fp8=fp8)
+    ws = _norm_weights(q, q_weight, k_weight, eps, unit_offset, geo.D, k_new, tables)
+    rot_dim, max_pos = _rotary_operands(rotary_cos, rotary_sin, geo.D) if tables else (0, 0)
+    _pos_offsets_operand(pos_offsets, geo.B)
+    quant = _kv_quant_arg("pfa_norm_rope_append", k_cache, v_cache, k_descale, v_descale, geo.B, geo.Hkv, k_new.device)
+    H, q_out = _append_q_operands(q, q_out, k_new, geo)
+    if k_new.device.type == "cpu":
+        _norm_rope_append_model(k_new, v_new, k_cache, v_cache, q_weight, k_weight, float(eps), bool(unit_offset), rotary_cos, rotary_sin,
+                                cache_seqlens.tolist(), cu_seqlens_q.tolist() if geo.ragged else None, geo.max_seqlen_q, block_table,
+                                None if pos_offsets is None else pos_offsets.tolist(), bool(rotary_interleaved), q, q_out, k_descale, v_descale)
+        return q_out
+    nra = _capi_norm_rope_append
+    nra.load()
+    held = []
+    a = _append_args(nra.make_norm_rope_append_args, "pfa_norm_rope_append", k_new, v_new, k_cache, v_cache, geo, cu_seqlens_q, block_table,
+                     flags=(nra.PFA_NRA_INTERLEAVED if rotary_interleaved else 0) | (nra.PFA_NRA_UNIT_OFFSET if unit_offset else 0),
+                     eps=float(eps), rot_dim=rot_dim, max_pos=max_pos, H=H, weight_dtype=_DT[ws[0].dtype] if ws else _DT[k_new.dtype],
+                     kv_dtype=_capi.PFA_DTYPE_FP8_E4M3 if fp8 else _DT[k_new.dtype])
+    if tables:
+        a.cos, a.sin, a.cs_stride = rotary_cos.data_ptr(), rotary_sin.data_ptr(), rotary_cos.stride(0)
+    for field, w in (("q_weight", q_weight), ("k_weight", k_weight)):
+        if w is not None:
+            setattr(a, field, _meeting_abi([w], held, weights=True)[0].data_ptr())
+    if quant is not None:
+        a.k_descale, a.v_descale, a.ds_sb = quant.k_descale, quant.v_descale, quant.descale_stride_b
+    if pos_offsets is not None:
+        a.pos_offsets = pos_offsets.data_ptr()
+    if q is not None:
+        _set_view(a, "q", q, "sh" if geo.ragged else "bsh")
+        _set_view(a, "q_out", q_out, "sh" if geo.ragged else "bsh")
+    _append_launch("pfa_norm_rope_append", a, cache_seqlens, k_new, geo.B)
+    _hold(held, torch.cuda.current_stream(k_new.device))
+    return q_out
+
+
 def _train_qk_norm_kw(q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset):
     """The QK-norm keywords of the training attention calls: None without weights, else what ``qk_norm`` takes."""
     if q_norm_weight is None and k_norm_weight is None:
@@ -1597,10 +1698,24 @@ def _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v
     return dict(rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=bool(rotary_interleaved), pos_offsets=pos_offsets)
 
 
+def _with_qk_norm(rotary, q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset, k_new, v_new, cache_seqlens):
+    """The QK-norm keywords of the attention calls over a KV cache, joined to ``_rotary_kw``'s result: ``rotary`` as it is without them,
+    else what ``norm_rope_append`` takes (the weights, eps, the unit offset, and the rotary keywords if any).  Refused as the rotary
+    keywords are: ``qk_norm_unit_offset`` without a weight, and a weight without ``k_new`` / ``v_new`` and ``cache_seqlens``."""
+    if q_norm_weight is None and k_norm_weight is None:
+        if qk_norm_unit_offset:
+            raise ValueError("qk_norm_unit_offset needs q_norm_weight or k_norm_weight")
+        return rotary
+    if k_new is None or v_new is None or cache_seqlens is None:
+        raise ValueError("q_norm_weight / k_norm_weight need k_new, v_new and cache_seqlens: the norm is fused into the append of the step's rows")
+    return dict(rotary or {}, q_weight=q_norm_weight, k_weight=k_norm_weight, eps=qk_norm_eps, unit_offset=bool(qk_norm_unit_offset))
+
+
 def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=None, rotary=None, descales=None, **ragged):
     """The ``k_new=, v_new=`` form of the calls over a KV cache: ``kv_append`` enqueued in front of the attention launch, on the
     same stream, with the same lengths, ``cu_seqlens_q`` and table.  With ``rotary`` (``_rotary_kw``) it is ``rope_append`` instead, and
-    q rotated into a fresh buffer is returned; otherwise None."""
+    q rotated into a fresh buffer is returned; otherwise None.  With the norm weights in it (``_with_qk_norm``) it is
+    ``norm_rope_append``, and the returned q is normalised too."""
     if k_new is None and v_new is None:
         return None
     if k_new is None or v_new is None:
@@ -1608,7 +1723,8 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=
     if cache_seqlens is None:
         raise ValueError("k_new / v_new need cache_seqlens: the lengths after the step say where the rows go")
     if rotary is not None:
-        return rope_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, q=q, **rotary, **ragged)
+        write = norm_rope_append if "eps" in rotary else rope_append
+        return write(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, q=q, **rotary, **ragged)
     kd, vd = descales if descales is not None else (None, None)       # an FP8 cache: the quantising append
     kv_append(k_new, v_new, k_cache, v_cache, cache_seqlens=cache_seqlens, block_table=block_table, k_descale=kd, v_descale=vd, **ragged)
     return None
@@ -1788,8 +1904,9 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-               pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
-               prefix_key_splits=None, tree_mask: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
+               pos_offsets: Optional[torch.Tensor] = None, q_norm_weight: Optional[torch.Tensor] = None,
+               k_norm_weight: Optional[torch.Tensor] = None, qk_norm_eps: float = 1e-6, qk_norm_unit_offset: bool = False,
+               shared_prefix: Optional[int] = None, prefix_key_splits=None, tree_mask: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
                v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
@@ -1822,6 +1939,11 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     ``rotary_cos=, rotary_sin=`` (fp32 ``[max_pos, rot_dim / 2]``, with ``rotary_interleaved`` and ``pos_offsets`` as in ``rope_append``; they
     need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
     the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified.
+
+    ``q_norm_weight=, k_norm_weight=`` (``[D]``, fp32 or of q's dtype, either or both; with ``qk_norm_eps`` and ``qk_norm_unit_offset`` as in
+    ``qk_norm``; they need ``k_new`` / ``v_new`` and ``cache_seqlens``): QK-norm of q and of the new K rows, in front of the rotation if there
+    is one -- ``norm_rope_append`` is enqueued as the step's write side, still one launch.  Not built into the keyword route over an FP8
+    cache (``ValueError``): call ``norm_rope_append(..., k_descale=, v_descale=)`` and then this function without ``k_new``.
 
     ``shared_prefix=P`` (a host integer; ``None``: the call above, unchanged): the caller promises that (a) the first P logical keys of
     every sequence have the same contents -- with a block table normally the same page ids -- and (b) every row of the step lies
@@ -1884,10 +2006,12 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_decode", "decode takes key_mask, cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
         ("window", window is not None), ("tree_mask", tree_mask is not None), ("shared_prefix", shared_prefix is not None),
-        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None), ("sinks", sinks is not None)), q_too=True) if fp8 else None
+        ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None), ("sinks", sinks is not None),
+        _qk_norm_refused(q_norm_weight, k_norm_weight, qk_norm_unit_offset)), q_too=True) if fp8 else None
     snk = _sinks_arg(sinks, q, tree_mask)
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
+    rotary = _with_qk_norm(rotary, q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset, k_new, v_new, cache_seqlens)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
     tree = _tree_mask_arg(tree_mask, q, causal, window, shared_prefix)
     _prefix_splits_need_prefix(prefix_key_splits, shared_prefix)
@@ -1933,6 +2057,11 @@ def _fp8_caches(k_cache, v_cache, k_descale, v_descale) -> bool:
     return False
 
 
+def _qk_norm_refused(q_norm_weight, k_norm_weight, qk_norm_unit_offset):
+    """``_fp8_quant``'s ``refused`` row of the QK-norm keywords: over an FP8 cache the fused write side is ``norm_rope_append`` itself."""
+    return "q_norm_weight / k_norm_weight", q_norm_weight is not None or k_norm_weight is not None or bool(qk_norm_unit_offset)
+
+
 def _fp8_quant(entry: str, takes: str, q, k_cache, v_cache, k_descale, v_descale, B, refused, q_too=False):
     """... and then, over an FP8 cache: -> the ``pfa_fa3_kv_quant`` block.  ``refused``: (name, given) of the arguments the FP8 kernels
     are not built for; a given one raises ``ValueError`` naming it and what the family ``takes``, before anything is enqueued.  ``B``:
@@ -1961,8 +2090,9 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
                       block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                       k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                       rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-                      pos_offsets: Optional[torch.Tensor] = None, shared_prefix: Optional[int] = None,
-                      key_splits=None, prefix_key_splits=None, k_descale: Optional[torch.Tensor] = None,
+                      pos_offsets: Optional[torch.Tensor] = None, q_norm_weight: Optional[torch.Tensor] = None,
+                      k_norm_weight: Optional[torch.Tensor] = None, qk_norm_eps: float = 1e-6, qk_norm_unit_offset: bool = False,
+                      shared_prefix: Optional[int] = None, key_splits=None, prefix_key_splits=None, k_descale: Optional[torch.Tensor] = None,
                       v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
@@ -2001,6 +2131,11 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
     the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified.
 
+    ``q_norm_weight=, k_norm_weight=`` (``[D]``, fp32 or of q's dtype, either or both; with ``qk_norm_eps`` and ``qk_norm_unit_offset`` as in
+    ``qk_norm``; they need ``k_new`` / ``v_new`` and ``cache_seqlens``): QK-norm of q and of the new K rows, in front of the rotation if there
+    is one -- ``norm_rope_append`` is enqueued as the step's write side, still one launch.  Not built into the keyword route over an FP8
+    cache (``ValueError``): call ``norm_rope_append(..., k_descale=, v_descale=)`` and then this function without ``k_new``.
+
     ``shared_prefix=P``: as in ``fa3_decode`` -- the first P keys of every sequence are the same and every row lies behind them
     (``len_b - Sq >= P``); all ``B * Sq`` rows go once against sequence 0's first P keys, each sequence against its own keys from P on
     with ``causal`` as given, and ``attn_merge`` joins the two.  Same restrictions (a multiple of 64 and of the page size, below Smax,
@@ -2035,12 +2170,13 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         ("window", window is not None), ("shared_prefix", shared_prefix is not None), ("key_splits", key_splits is not None),
         ("prefix_key_splits", prefix_key_splits is not None),
         ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None),
-        ("sinks", sinks is not None))
+        ("sinks", sinks is not None), _qk_norm_refused(q_norm_weight, k_norm_weight, qk_norm_unit_offset))
     ) if fp8 else None
     snk = _sinks_arg(sinks, q)
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
-    splits = _key_splits_arg("key_splits", key_splits)
+    rotary = _with_qk_norm(rotary, q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset, k_new, v_new, cache_seqlens)
+    splits =_key_splits_arg("key_splits", key_splits)
     _key_splits_arg("prefix_key_splits", prefix_key_splits)
     _prefix_splits_need_prefix(prefix_key_splits, shared_prefix)
     if splits is not None and window is not None:
@@ -2069,7 +2205,9 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                        block_table: Optional[torch.Tensor] = None, window: Optional[int] = None,
                        k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                        rotary_cos: Optional[torch.Tensor] = None, rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False,
-                       pos_offsets: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
+                       pos_offsets: Optional[torch.Tensor] = None, q_norm_weight: Optional[torch.Tensor] = None,
+                       k_norm_weight: Optional[torch.Tensor] = None, qk_norm_eps: float = 1e-6, qk_norm_unit_offset: bool = False,
+                       k_descale: Optional[torch.Tensor] = None,
                        v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Ragged forward over a KV cache (``pfa_fa3_prefill_varlen_ex``): ``fa3_prefill_cache`` for sequences that bring DIFFERENT numbers
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
@@ -2100,6 +2238,11 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     need ``k_new`` / ``v_new`` and ``cache_seqlens``): ``rope_append`` is enqueued instead of ``kv_append`` -- the new K rows are rotated at
     the positions they are appended at, and the attention launch reads q rotated into a fresh buffer; the caller's q is not modified.
 
+    ``q_norm_weight=, k_norm_weight=`` (``[D]``, fp32 or of q's dtype, either or both; with ``qk_norm_eps`` and ``qk_norm_unit_offset`` as in
+    ``qk_norm``; they need ``k_new`` / ``v_new`` and ``cache_seqlens``): QK-norm of q and of the new K rows, in front of the rotation if there
+    is one -- ``norm_rope_append`` is enqueued as the step's write side, still one launch.  Not built into the keyword route over an FP8
+    cache (``ValueError``): call ``norm_rope_append(..., k_descale=, v_descale=)`` and then this function without ``k_new``.
+
     FP8 cache (``pfa_fa3_prefill_varlen_q8``): ``torch.float8_e4m3fn`` caches or pools with ``k_descale=, v_descale=`` (contiguous fp32
     DEVICE tensors ``[Hkv]`` or ``[B, Hkv]``; refused with 16-bit caches), exactly as in ``fa3_prefill_cache``: the attention over
     ``dequantize_kv`` of the cache, the bits of the 16-bit call at descales 1, and of per-sequence ``fa3_prefill_cache`` calls over
@@ -2114,11 +2257,12 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     quant = _fp8_quant("pfa_fa3_prefill_varlen", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, B_cu, (
         ("window", window is not None),
         ("rotary_cos / rotary_sin", rotary_cos is not None or rotary_sin is not None or bool(rotary_interleaved) or pos_offsets is not None),
-        ("sinks", sinks is not None))
+        ("sinks", sinks is not None), _qk_norm_refused(q_norm_weight, k_norm_weight, qk_norm_unit_offset))
     ) if fp8 else None
     snk = _sinks_arg(sinks, q)
     ext = _window_ext(window, causal)
     rotary = _rotary_kw(rotary_cos, rotary_sin, rotary_interleaved, pos_offsets, k_new, v_new, cache_seqlens)
+    rotary = _with_qk_norm(rotary, q_norm_weight, k_norm_weight, qk_norm_eps, qk_norm_unit_offset, k_new, v_new, cache_seqlens)
     if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("q must be 3-D ([total_q,H,D]) and k_cache, v_cache 4-D ([B,Hkv,Smax,D])")
     B = _cu_seqlens_arg(cu_seqlens_q, contiguous=False)
