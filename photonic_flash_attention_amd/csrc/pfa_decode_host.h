@@ -105,13 +105,14 @@ struct Blocks {
 };
 
 // Every decode call's check -> PFA_OK, the modes in *m and their plan in *pl.  KV8: the unit over an FP8 cache, whose quant block is
-// not optional.  The split count and the workspace never depend on tree, quant or sinks, so a captured graph replays while they change.
-template <bool KV8 = false>
+// not optional.  DIMS: the head dims the unit's kernels exist for (pfa_host.h; the head dim 256 unit names its own).  The split count and
+// the workspace never depend on tree, quant or sinks, so a captured graph replays while they change.
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128>
 int check(const pfa_fa3_decode_args* a, const Blocks& b, CacheModes* m, Plan* pl) {
     *m = CacheModes{};
     int st = check_blocks_front<KV8>(a, b.ext, b.quant, b.sinks);
     if (st != PFA_OK) return st;
-    st = check_cache_args(a, 64);
+    st = check_cache_args(a, 64, DIMS);
     if (st != PFA_OK) return st;
     st = check_cache_ext(b.ext, a->causal, a->Smax, &m->window);
     if (st != PFA_OK) return st;
@@ -128,28 +129,28 @@ int check(const pfa_fa3_decode_args* a, const Blocks& b, CacheModes* m, Plan* pl
 }
 
 // ... of the workspace queries, which stop in front of the pointer rules -> the bytes, 0 for arguments no plan can be made from
-template <bool KV8 = false>
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128>
 size_t workspace_bytes(const pfa_fa3_decode_args* a, const Blocks& b) {
     if (check_blocks_front<KV8>(a, b.ext, b.quant, b.sinks, false) != PFA_OK) return 0;
-    if (!a || a->size != sizeof(pfa_fa3_decode_args) || check_cache_shape(a) != PFA_OK) return 0;
+    if (!a || a->size != sizeof(pfa_fa3_decode_args) || check_cache_shape(a, DIMS) != PFA_OK) return 0;
     int window;
     if (check_cache_ext(b.ext, a->causal, a->Smax, &window) != PFA_OK || check_tree(b.tree, a, window, false) != PFA_OK) return 0;
     return plan(a, window).ws_bytes;
 }
 
-template <bool KV8 = false>
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128>
 int check_only(const pfa_fa3_decode_args* a, const Blocks& b) {
     CacheModes m;
     Plan pl;
-    return check<KV8>(a, b, &m, &pl);
+    return check<KV8, DIMS>(a, b, &m, &pl);
 }
 
 // of arguments that pass: the kernel's name into buf, the split count into *nsplit -> workgroups
-template <bool KV8 = false>
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128>
 int describe(const pfa_fa3_decode_args* a, const Blocks& b, char* buf, size_t n, int32_t* nsplit) {
     CacheModes m;
     Plan pl;
-    const int st = check<KV8>(a, b, &m, &pl);
+    const int st = check<KV8, DIMS>(a, b, &m, &pl);
     if (st != PFA_OK) return st;
     if (buf && n)
         snprintf(buf, n, "fa3_decode_%s_d%d_%s%s%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,

@@ -168,26 +168,30 @@ struct QueryRows {
 inline QueryRows query_rows(const pfa_fa3_decode_args* a) { return {a->Sq, a->q_stride_b, a->o_stride_b}; }
 inline QueryRows query_rows(const pfa_fa3_prefill_varlen_args* a) { return {a->max_seqlen_q, 0, 0}; }
 
+// The head dims a family of kernels over a cache exists for: 64 and 128, or (pfa_fa3_decode_d256) 256 alone.
+enum class HeadDims { D64_128, D256 };
+inline bool head_dim_ok(int D, HeadDims dims) { return dims == HeadDims::D256 ? D == 256 : (D == 64 || D == 128); }
+
 // The shape rules a plan can be made from (pfa_fa3_decode_workspace_bytes stops here: it takes no pointers and no strides).
 template <typename Args>
-inline int check_cache_shape(const Args* a) {
+inline int check_cache_shape(const Args* a, HeadDims dims = HeadDims::D64_128) {
     if (a->B <= 0 || a->H <= 0 || a->Hkv <= 0 || a->Smax <= 0 || query_rows(a).Sq < 1 || a->H % a->Hkv != 0) return PFA_ERR_SHAPE;
-    if (a->D != 64 && a->D != 128) return PFA_ERR_HEAD_DIM;
+    if (!head_dim_ok(a->D, dims)) return PFA_ERR_HEAD_DIM;
     return PFA_OK;
 }
 
 // The field rules pfa_fa3_decode, pfa_fa3_prefill and pfa_fa3_prefill_varlen share (include/pfa_hip.h, pfa_fa3_decode_args), in the
 // order their errors are reported: everything but the limits that depend on the kernel (key mask, cu_seqlens_q, grid, workspace).
-// max_sq: the most query rows the caller takes.
+// max_sq: the most query rows the caller takes; dims: the head dims its kernels exist for.
 template <typename Args>
-inline int check_cache_args(const Args* a, int max_sq) {
+inline int check_cache_args(const Args* a, int max_sq, HeadDims dims = HeadDims::D64_128) {
     if (!a) return PFA_ERR_NULL;
     if (a->size != sizeof(Args)) return PFA_ERR_STRUCT_SIZE;
     if (a->flags != 0 || a->reserved0 != 0) return PFA_ERR_FLAGS;
     if (!a->q || !a->k_cache || !a->v_cache || !a->o) return PFA_ERR_NULL;
     const QueryRows g = query_rows(a);
     if (g.Sq > max_sq) return PFA_ERR_SHAPE;
-    const int st = check_cache_shape(a);
+    const int st = check_cache_shape(a, dims);
     if (st != PFA_OK) return st;
     if (a->dtype_in != PFA_DTYPE_BF16 && a->dtype_in != PFA_DTYPE_FP16) return PFA_ERR_DTYPE;
     if (a->dtype_out != a->dtype_in && a->dtype_out != PFA_DTYPE_FP32) return PFA_ERR_DTYPE;

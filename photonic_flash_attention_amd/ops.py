@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_norm_rope_append, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
+from . import _capi, _capi_decode_d256, _capi_norm_rope_append, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
 from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
                       _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
@@ -1731,7 +1731,7 @@ def _append_first(k_new, v_new, k_cache, v_cache, cache_seqlens, block_table, q=
 
 
 def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=None, key_splits=None, tree=None, quant=None, descales=None,
-                       sinks=None, **ragged):
+                       sinks=None, d256=False, **ragged):
     """The tail the attention calls over a KV cache share, behind all their validation: the optional LSE (``lse_shape`` or None),
     ``_append_first`` of ``new_rows`` = (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), the launch of ``{entry}_ex`` on
     the current stream right behind it, the status, and the kept tensors' hold on the stream.  With ``rotary`` the launch reads the
@@ -1739,8 +1739,8 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     launches ``pfa_fa3_prefill_split`` instead, which takes no extension; ``tree`` (``pfa_fa3_decode`` only) launches
     ``pfa_fa3_decode_tree``, which takes it behind the extension; ``quant`` (``pfa_fa3_decode`` over an FP8 cache, with the caller's
     ``descales`` for the append) launches ``pfa_fa3_decode_q8``; with the prefill entries it launches ``{entry}_q8``; ``sinks`` (a
-    ``pfa_fa3_sinks`` block; with neither a tree nor an FP8 cache) launches ``{entry}_sink``, or ``{entry}_split_sink`` with ``key_splits``.
-    -> lse or None."""
+    ``pfa_fa3_sinks`` block; with neither a tree nor an FP8 cache) launches ``{entry}_sink``, or ``{entry}_split_sink`` with ``key_splits``;
+    ``d256`` (``pfa_fa3_decode`` at head dim 256, with none of the others) launches ``pfa_fa3_decode_d256``.  -> lse or None."""
     lse = None
     if lse_shape is not None:
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
@@ -1756,6 +1756,9 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
                       else ("_tree", (e, C.byref(tree))) if tree is not None else ("_ex", (e,)))
     if sinks is not None:
         suffix, middle = ("_split_sink", (key_splits, C.byref(sinks))) if key_splits is not None else ("_sink", (e, C.byref(sinks)))
+    if d256:
+        _capi_decode_d256.load()
+        suffix = "_d256"
     st = getattr(_capi.load(), entry + suffix)(C.byref(a), *middle, C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
     if keep:
@@ -1910,7 +1913,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
                v_descale: Optional[torch.Tensor] = None, sinks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Decode attention over a KV cache (``pfa_fa3_decode_ex``): a few new query rows per batch against the cached keys.  Inference only.
 
-    q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64 or 128, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
+    q: ``[B,H,Sq,D]`` (1 <= Sq <= 64, D 64, 128 or 256, bf16 / fp16; any strides, head dim contiguous) as in ``fa3_forward``.
     k_cache / v_cache: ``[B,Hkv,Smax,D]``-shaped views, H a multiple of Hkv (a flash-attn ``[B,Smax,Hkv,D]`` buffer is passed as
     ``.transpose(1, 2)``; a slice of a larger preallocated cache is just a view).  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of
     valid keys per batch.  key_mask: optional ``[B,Smax]`` (0 / False = masked); given alone, each batch's length is derived from it
@@ -2002,7 +2005,16 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     ``key_mask``, ``causal``, ``out``, ``out_dtype``, ``return_lse``, ``k_new`` / ``v_new`` and rotary work as above, and with
     ``shared_prefix`` the sinks go to the own-keys pass only.  Splits and workspace are those of the call without sinks, and a captured step
     replays while the sink values change.  A wrong dtype, shape, layout or device raises ``ValueError`` naming ``sinks`` before anything is
-    enqueued, and so do ``tree_mask`` and an FP8 cache, which take no sinks.  ``None``: exactly the calls made without the argument."""
+    enqueued, and so do ``tree_mask`` and an FP8 cache, which take no sinks.  ``None``: exactly the calls made without the argument.
+
+    Head dim 256 (``pfa_fa3_decode_d256``; Gemma 2 / 3, Qwen3-Next): q ``[B,H,Sq,256]`` goes to a kernel of its own -- the same work
+    split and key splits, a 16-key wave tile.  ``cache_seqlens``, ``key_mask``, ``causal``, ``window``, ``block_table``, ``out``,
+    ``out_dtype``, ``return_lse``, ``softmax_scale``, ``k_new`` / ``v_new`` and the rotary keywords work as above; ``tree_mask``, ``sinks``,
+    ``shared_prefix`` / ``prefix_key_splits`` and FP8 caches are not built at this head dim and raise ``ValueError`` naming the argument
+    and "head dim 256" before anything is enqueued; ``q_norm_weight`` / ``k_norm_weight`` meet ``norm_rope_append``'s own refusal.  Other
+    head dims above 128 stay refused, and the prefill calls take 64 and 128 only."""
+    d256 = _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, tree_mask=tree_mask, sinks=sinks, shared_prefix=shared_prefix,
+                         prefix_key_splits=prefix_key_splits)
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_decode", "decode takes key_mask, cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
         ("window", window is not None), ("tree_mask", tree_mask is not None), ("shared_prefix", shared_prefix is not None),
@@ -2040,12 +2052,28 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     _set_cache_seqlens(a, cache_seqlens, q, keep)
     if snk is not None:
         keep.append(sinks)
-    # neither a tree nor an FP8 cache nor sinks change the workspace
-    _attach_workspace(a, _capi.load().pfa_fa3_decode_workspace_bytes_ex(C.byref(a), None if ext is None else C.byref(ext)), q.device, keep)
+    # neither a tree nor an FP8 cache nor sinks change the workspace; head dim 256 asks its own unit (the same plan, wider partials)
+    ws_bytes = _capi_decode_d256.load().pfa_fa3_decode_d256_workspace_bytes if d256 else _capi.load().pfa_fa3_decode_workspace_bytes_ex
+    _attach_workspace(a, ws_bytes(C.byref(a), None if ext is None else C.byref(ext)), q.device, keep)
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, quant=quant,
-                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, max_seqlen_q=Sq)
+                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, d256=d256, max_seqlen_q=Sq)
     return out, lse
+
+
+def _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, **refused) -> bool:
+    """Is this ``fa3_decode`` call the head dim 256 one (``pfa_fa3_decode_d256``)?  Then what that kernel is not built for is refused
+    here, before anything else is looked at and before anything is enqueued: ``refused`` (name -> value) and FP8 caches."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 4 or q.shape[3] != 256:
+        return False
+    for name, value in refused.items():
+        if value is not None:
+            raise ValueError(f"{name} is not supported at head dim 256: that decode kernel takes cache_seqlens, key_mask, causal, window, "
+                             "block_table and k_new / v_new only")
+    if k_descale is not None or v_descale is not None or any(isinstance(t, torch.Tensor) and t.dtype == FP8 for t in (k_cache, v_cache)):
+        raise ValueError("an FP8 (torch.float8_e4m3fn) k_cache / v_cache with k_descale / v_descale is not supported at head dim 256: "
+                         "that decode kernel reads 16-bit caches only")
+    return True
 
 
 def _fp8_caches(k_cache, v_cache, k_descale, v_descale) -> bool:

@@ -22,6 +22,13 @@ windowed calls take their lengths from a list that slides the window to a differ
 TB/s of a windowed call is taken over the bytes of its span (the W keys and the up to 63 below them in the first tile).
 
     python tools/decode_bench.py --window 1024,4096 [--shapes "8,32,8,128,32768;8,32,8,128,131072"] [--reps 7]
+
+``--head-dim 256`` measures the head dim 256 kernel (``pfa_fa3_decode_d256``): per (B, Skv) the call at H 16 / Hkv 4 / D 256, contiguous and
+over pages of 256 keys, against (a) the D 128 kernel at H 32 / Hkv 8, which streams the same cache bytes per step, and (b)
+``scaled_dot_product_attention`` at D 256 -- all timed alternately in one process, every path cycling through its own >= 768 MiB of caches.
+The minimum and maximum over the repetitions are kept: the spread of the D 128 kernel is what the D 256 figure is compared with.
+
+    python tools/decode_bench.py --head-dim 256 [--reps 7] [--json out.jsonl]
 """
 
 from __future__ import annotations
@@ -276,6 +283,72 @@ def main_window(args, dev):
                 f.write(json.dumps(r) + "\n")
 
 
+def bench_head_dim(B, S, reps, dev, page=256):
+    """D 256 (H 16 / Hkv 4) contiguous and paged, D 128 (H 32 / Hkv 8: the same bytes) and sdpa at D 256, timed alternately."""
+    H, Hkv, D = 16, 4, 256
+    cache_bytes = 2 * B * Hkv * S * D * 2
+    if cache_bytes > MAX_CACHE:
+        return None
+    n = max(1, math.ceil(MIN_POOL / cache_bytes))
+    pages = S // page
+    q = torch.randn(B, H, 1, D, device=dev, dtype=torch.bfloat16)
+    q128 = torch.randn(B, 2 * H, 1, D // 2, device=dev, dtype=torch.bfloat16)
+    sl = torch.full((B,), S, dtype=torch.int32, device=dev)
+    wide, narrow = _caches(B, Hkv, S, D, n, dev), _caches(B, 2 * Hkv, S, D // 2, n, dev)
+    pools = []
+    for i in range(n):                  # flash-attn style [num_pages, page, Hkv, D] pools passed transposed, pages in a seeded random order
+        perm = torch.randperm(B * pages, generator=torch.Generator().manual_seed(i)).to(dev)
+        kp, vp = (torch.randn(B * pages, page, Hkv, D, device=dev, dtype=torch.bfloat16).transpose(1, 2) for _ in range(2))
+        pools.append((kp, vp, perm.to(torch.int32).reshape(B, pages).contiguous()))
+    paths = {"d256": lambda i: ops.fa3_decode(q, wide[i][0], wide[i][1], cache_seqlens=sl),
+             "d256_paged": lambda i: ops.fa3_decode(q, pools[i][0], pools[i][1], cache_seqlens=sl, block_table=pools[i][2]),
+             "d128": lambda i: ops.fa3_decode(q128, narrow[i][0], narrow[i][1], cache_seqlens=sl),
+             "sdpa_d256": lambda i: torch.nn.functional.scaled_dot_product_attention(q, wide[i][0], wide[i][1], enable_gqa=True)}
+    for f in paths.values():
+        for i in range(min(2, n)):
+            f(i)
+    torch.cuda.synchronize()
+    times = {name: [] for name in paths}
+    for _ in range(reps):
+        for name, f in paths.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(n):
+                f(i)
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / n)
+    res = dict(B=B, H=H, Hkv=Hkv, D=D, Skv=S, page=page, cache_MB=round(cache_bytes / 1e6, 2), n_caches=n, reps=reps)
+    for name, ts in times.items():
+        us = sorted(ts)[len(ts) // 2]
+        res[f"{name}_us"], res[f"{name}_us_min"], res[f"{name}_us_max"] = round(us, 2), round(min(ts), 2), round(max(ts), 2)
+        res[f"{name}_TBs"] = round(cache_bytes / us / 1e6, 3)
+    res["d256_over_d128"] = round(res["d256_us"] / res["d128_us"], 4)
+    res["d128_spread"] = round(res["d128_us_max"] / res["d128_us_min"], 4)
+    del wide, narrow, pools
+    torch.cuda.empty_cache()
+    return res
+
+
+def main_head_dim(args, dev):
+    rows = []
+    for B in (1, 8, 32):
+        for S in (4096, 32768, 131072):
+            r = bench_head_dim(B, S, args.reps, dev)
+            if r is None:
+                print(f"B {B} Skv {S}: skipped (cache above {MAX_CACHE >> 30} GiB)", flush=True)
+                continue
+            rows.append(r)
+            print(f"B {B:>2} Skv {S:>6} {r['cache_MB']:>8.1f} MB | " + " | ".join(
+                f"{name} {r[f'{name}_us']:.2f} us [{r[f'{name}_us_min']:.2f}, {r[f'{name}_us_max']:.2f}] {r[f'{name}_TBs']:.2f} TB/s"
+                for name in ("d256", "d256_paged", "d128", "sdpa_d256")) + f" | d256 / d128 {r['d256_over_d128']:.3f}, d128 max / min "
+                f"{r['d128_spread']:.3f}", flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 def host_cost(dev):
     """Python + ctypes cost of one fa3_decode call (enqueue only: the GPU side is tiny), and one graph replay of it."""
     B, H, Hkv, D, S = 1, 32, 8, 128, 4096
@@ -334,9 +407,14 @@ def main():
                          "(a head's tokens adjacent, like the contiguous [B, Hkv, S, D] caches this tool times)")
     ap.add_argument("--shapes", default=None, help='with --paged / --window: "B,H,Hkv,D,Skv;..." instead of the DESIGN 4.6 shapes')
     ap.add_argument("--window", default=None, metavar="W[,W...]", help="measure sliding windows of these many keys against no window")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(128, 256),
+                    help="256: the head dim 256 kernel at H 16 / Hkv 4 against the D 128 kernel at H 32 / Hkv 8 (the same bytes) and sdpa")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench measures on the GPU"
     dev = torch.device("cuda:0")
+    if args.head_dim == 256:
+        main_head_dim(args, dev)
+        return
     if args.paged:
         main_paged(args, dev)
         return
