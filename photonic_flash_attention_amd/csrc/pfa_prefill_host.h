@@ -20,11 +20,14 @@ namespace prefill {
 template <typename Args>
 constexpr bool kVarlen = std::is_same<Args, pfa_fa3_prefill_varlen_args>::value;
 
+// query rows per workgroup of the kernels a unit has: fa3_prefill_kernel's 256, or 128 at head dim 256 (fa3_prefill_d256_kernel.h)
+constexpr int rows_per_workgroup(HeadDims dims) { return dims == HeadDims::D256 ? 128 : FWD_BLOCK_M; }
+
 // workgroups: from host shapes only (Sq or max_seqlen_q, never device data), so a captured graph stays valid while cache_seqlens,
 // cu_seqlens_q, the block table and the cache change
-template <typename Args>
+template <HeadDims DIMS = HeadDims::D64_128, typename Args>
 int64_t workgroups(const Args* a) {
-    return (int64_t)a->B * a->H * (((int64_t)query_rows(a).Sq + FWD_BLOCK_M - 1) / FWD_BLOCK_M);
+    return (int64_t)a->B * a->H * (((int64_t)query_rows(a).Sq + rows_per_workgroup(DIMS) - 1) / rows_per_workgroup(DIMS));
 }
 
 // the rules each call has of its own, behind check_cache_args
@@ -39,17 +42,18 @@ inline int check_own_rules(const pfa_fa3_prefill_varlen_args* a) {      // (max_
 }
 
 // The check of the uniform and the ragged call, with whichever blocks the export takes -> PFA_OK and the modes in *m.  KV8: the unit over
-// an FP8 cache, whose quant block is not optional.  The grid, then the extension block, come last.
-template <bool KV8 = false, typename Args>
+// an FP8 cache, whose quant block is not optional.  DIMS: the head dims the unit's kernels exist for (pfa_host.h; the head dim 256 unit
+// names its own), and with them the rows of a workgroup.  The grid, then the extension block, come last.
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128, typename Args>
 int check(const Args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, const pfa_fa3_sinks* sinks, CacheModes* m) {
     *m = CacheModes{};
     int st = check_blocks_front<KV8>(a, ext, quant, sinks);
     if (st != PFA_OK) return st;
-    st = check_cache_args(a, INT_MAX);
+    st = check_cache_args(a, INT_MAX, DIMS);
     if (st != PFA_OK) return st;
     st = check_own_rules(a);
     if (st != PFA_OK) return st;
-    if (workgroups(a) > 0x7fffffffLL) return PFA_ERR_SHAPE;
+    if (workgroups<DIMS>(a) > 0x7fffffffLL) return PFA_ERR_SHAPE;
     st = check_cache_ext(ext, a->causal, a->Smax, &m->window);
     if (st != PFA_OK) return st;
     m->quant = quant; m->sinks = sinks;
@@ -74,7 +78,7 @@ KernelFn<Params<VARLEN, WINDOW, SPLIT, KV8, SINK>> kernel(int dtype, int D, bool
 }
 
 // of checked arguments and their modes: the kernel's name into buf -> workgroups
-template <typename Args>
+template <HeadDims DIMS = HeadDims::D64_128, typename Args>
 int describe(const Args* a, const CacheModes& m, char* buf, size_t n) {
     static const char* const kSplit[PFA_PREFILL_MAX_SPLITS + 1] = {"", "", "_split2+merge", "_split3+merge", "_split4+merge", "_split5+merge",
                                                                    "_split6+merge", "_split7+merge", "_split8+merge"};
@@ -82,14 +86,14 @@ int describe(const Args* a, const CacheModes& m, char* buf, size_t n) {
         snprintf(buf, n, "fa3_prefill_%s_d%d_%s%s%s%s%s%s%s%s", a->dtype_in == PFA_DTYPE_BF16 ? "bf16" : "fp16", a->D,
                  a->dtype_out == PFA_DTYPE_FP32 ? "o32" : "o16", a->causal ? "_causal" : "", m.window ? "_win" : "", m.quant ? "_kv8" : "",
                  m.sinks ? "_sink" : "", kVarlen<Args> ? "_varlen" : "", kSplit[m.nsplit], a->block_table ? "_paged" : "");
-    return (int)(workgroups(a) * m.nsplit);
+    return (int)(workgroups<DIMS>(a) * m.nsplit);
 }
 
 // what every launch of the kernel fills behind fill_attention_params
-template <bool VARLEN, typename Block, typename Args>
+template <bool VARLEN, HeadDims DIMS = HeadDims::D64_128, typename Block, typename Args>
 void fill_prefill_params(Block& p, const Args* a) {
     fill_attention_params(p, a);
-    p.nqblk = (p.Sq + FWD_BLOCK_M - 1) / FWD_BLOCK_M;
+    p.nqblk = (p.Sq + rows_per_workgroup(DIMS) - 1) / rows_per_workgroup(DIMS);
     p.kv_group = a->H / a->Hkv;
     if constexpr (VARLEN) {
         p.cu_seqlens_q = a->cu_seqlens_q; p.total_q = a->total_q;
@@ -124,16 +128,16 @@ int launch(const Args* a, const CacheModes& m, void* stream) {
 
 // The bodies of the entry points of the uniform and the ragged call, written once over Args.  The 16-bit units pass no quant and no
 // sinks, the FP8 units (ON has MODE_KV8) no sinks, the sink units no quant.
-template <bool KV8 = false, typename Args>
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128, typename Args>
 int entry_check(const Args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, const pfa_fa3_sinks* sinks) {
     CacheModes m;
-    return check<KV8>(a, ext, quant, sinks, &m);
+    return check<KV8, DIMS>(a, ext, quant, sinks, &m);
 }
-template <bool KV8 = false, typename Args>
+template <bool KV8 = false, HeadDims DIMS = HeadDims::D64_128, typename Args>
 int entry_describe(const Args* a, const pfa_fa3_cache_ext* ext, const pfa_fa3_kv_quant* quant, const pfa_fa3_sinks* sinks, char* buf, size_t n) {
     CacheModes m;
-    const int st = check<KV8>(a, ext, quant, sinks, &m);
-    return st != PFA_OK ? st : describe(a, m, buf, n);
+    const int st = check<KV8, DIMS>(a, ext, quant, sinks, &m);
+    return st != PFA_OK ? st : describe<DIMS>(a, m, buf, n);
 }
 // the sink-less call of the same arguments: the 16-bit unit's export, whose kernels a sink unit does not have
 inline int sinkless(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* ext, void* stream) { return pfa_fa3_prefill_ex(a, ext, stream); }

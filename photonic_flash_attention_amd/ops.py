@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_decode_d256, _capi_norm_rope_append, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
+from . import _capi, _capi_decode_d256, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
 from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
                       _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
@@ -1757,7 +1757,7 @@ def _finish_cache_call(entry: str, a, ext, q, lse_shape, keep, new_rows, rotary=
     if sinks is not None:
         suffix, middle = ("_split_sink", (key_splits, C.byref(sinks))) if key_splits is not None else ("_sink", (e, C.byref(sinks)))
     if d256:
-        _capi_decode_d256.load()
+        (_capi_decode_d256 if entry == "pfa_fa3_decode" else _capi_prefill_d256).load()
         suffix = "_d256"
     st = getattr(_capi.load(), entry + suffix)(C.byref(a), *middle, C.c_void_p(stream.cuda_stream))
     _raise_status(entry, st, null_too=True)
@@ -2012,7 +2012,7 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     ``out_dtype``, ``return_lse``, ``softmax_scale``, ``k_new`` / ``v_new`` and the rotary keywords work as above; ``tree_mask``, ``sinks``,
     ``shared_prefix`` / ``prefix_key_splits`` and FP8 caches are not built at this head dim and raise ``ValueError`` naming the argument
     and "head dim 256" before anything is enqueued; ``q_norm_weight`` / ``k_norm_weight`` meet ``norm_rope_append``'s own refusal.  Other
-    head dims above 128 stay refused, and the prefill calls take 64 and 128 only."""
+    head dims above 128 stay refused; the prefill calls take 256 on a kernel of their own (``fa3_prefill_cache``)."""
     d256 = _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, tree_mask=tree_mask, sinks=sinks, shared_prefix=shared_prefix,
                          prefix_key_splits=prefix_key_splits)
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
@@ -2061,18 +2061,20 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     return out, lse
 
 
-def _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, **refused) -> bool:
+def _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, _kernel="decode", _takes="cache_seqlens, key_mask, causal, window", _rank=4,
+                  **refused) -> bool:
     """Is this ``fa3_decode`` call the head dim 256 one (``pfa_fa3_decode_d256``)?  Then what that kernel is not built for is refused
-    here, before anything else is looked at and before anything is enqueued: ``refused`` (name -> value) and FP8 caches."""
-    if not isinstance(q, torch.Tensor) or q.dim() != 4 or q.shape[3] != 256:
+    here, before anything else is looked at and before anything is enqueued: ``refused`` (name -> value) and FP8 caches.  The prefill
+    calls (``pfa_fa3_prefill_d256``, ``pfa_fa3_prefill_varlen_d256``) ask the same with their kernel's name, what it takes and q's rank."""
+    if not isinstance(q, torch.Tensor) or q.dim() != _rank or q.shape[-1] != 256:
         return False
     for name, value in refused.items():
         if value is not None:
-            raise ValueError(f"{name} is not supported at head dim 256: that decode kernel takes cache_seqlens, key_mask, causal, window, "
+            raise ValueError(f"{name} is not supported at head dim 256: that {_kernel} kernel takes {_takes}, "
                              "block_table and k_new / v_new only")
     if k_descale is not None or v_descale is not None or any(isinstance(t, torch.Tensor) and t.dtype == FP8 for t in (k_cache, v_cache)):
         raise ValueError("an FP8 (torch.float8_e4m3fn) k_cache / v_cache with k_descale / v_descale is not supported at head dim 256: "
-                         "that decode kernel reads 16-bit caches only")
+                         f"that {_kernel} kernel reads 16-bit caches only")
     return True
 
 
@@ -2125,7 +2127,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     """Forward over a KV cache (``pfa_fa3_prefill_ex``): ANY number of new query rows per batch against the cached keys -- the later
     chunks of a chunked prefill, the suffix of a prefix-cached prompt, speculative verification.  Inference only.
 
-    The tensor conventions are those of ``fa3_decode``: q ``[B,H,Sq,D]`` (Sq >= 1, D 64 or 128, bf16 / fp16), k_cache / v_cache
+    The tensor conventions are those of ``fa3_decode``: q ``[B,H,Sq,D]`` (Sq >= 1, D 64, 128 or 256, bf16 / fp16), k_cache / v_cache
     ``[B,Hkv,Smax,D]``-shaped views, or with ``block_table`` (int32 ``[B, max_pages]`` device tensor) pools
     ``[num_pages,Hkv,page_size,D]``-shaped, page_size a multiple of 64.  cache_seqlens: optional int32 ``[B]`` DEVICE tensor of valid
     keys per batch, the query rows' own keys included (append first, then call); keys at and past it are never read.  ``causal`` is
@@ -2192,7 +2194,16 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     ``k_new`` / ``v_new``, rotary, ``key_splits`` (split 0 of every q block carries the sink into the merge; a count of 1 is the unsplit
     call with sinks bit for bit) and ``shared_prefix`` / ``prefix_key_splits`` (the own-keys pass carries it).  Grid and workspace are
     those of the call without sinks; a captured step replays while the values change.  An FP8 cache takes no sinks (``ValueError``).
-    ``None``: exactly the calls made without the argument."""
+    ``None``: exactly the calls made without the argument.
+
+    Head dim 256 (``pfa_fa3_prefill_d256``; Gemma 2 / 3, Qwen3-Next): q ``[B,H,Sq,256]`` goes to a kernel of its own -- 128 query rows
+    per workgroup, four waves of 32 rows with one wave per SIMD, B * H * ceil(Sq / 128) workgroups.  ``cache_seqlens``, ``causal``,
+    ``window``, ``block_table``, ``out``, ``out_dtype``, ``return_lse``, ``softmax_scale``, ``k_new`` / ``v_new`` and the rotary keywords work
+    as above, with the same bit-equalities; ``key_splits``, ``shared_prefix`` / ``prefix_key_splits``, ``sinks`` and FP8 caches are not
+    built at this head dim and raise ``ValueError`` naming the argument and "head dim 256" before anything is enqueued;
+    ``q_norm_weight`` / ``k_norm_weight`` meet ``norm_rope_append``'s own refusal.  Other head dims above 128 stay refused."""
+    d256 = _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, _kernel="prefill", _takes="cache_seqlens, causal, window",
+                         key_splits=key_splits, shared_prefix=shared_prefix, prefix_key_splits=prefix_key_splits, sinks=sinks)
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_prefill", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, None, (
         ("window", window is not None), ("shared_prefix", shared_prefix is not None), ("key_splits", key_splits is not None),
@@ -2223,7 +2234,7 @@ def fa3_prefill_cache(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         _attach_workspace(a, _capi.load().pfa_fa3_prefill_split_workspace_bytes(C.byref(a), splits), q.device, keep)
     lse = _finish_cache_call("pfa_fa3_prefill", a, ext, q, q.shape[:3] if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, key_splits=splits, quant=quant,
-                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, max_seqlen_q=q.shape[2])
+                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, d256=d256, max_seqlen_q=q.shape[2])
     return out, lse
 
 
@@ -2241,7 +2252,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     of query rows -- one step of continuous batching (a prompt chunk, a suffix behind shared prefix pages, a speculative
     verification, one-token decode rows) in one launch.  The packed form flash-attn calls varlen.  Inference only.
 
-    q: ``[total_q, H, D]`` (D 64 or 128, bf16 / fp16; any token / head strides, head dim contiguous), the sequences' rows one after
+    q: ``[total_q, H, D]`` (D 64, 128 or 256, bf16 / fp16; any token / head strides, head dim contiguous), the sequences' rows one after
     the other.  cu_seqlens_q: int32 ``[B + 1]`` DEVICE tensor, non-decreasing, within ``[0, total_q]``: sequence b owns the packed rows
     ``cu[b] .. cu[b+1] - 1`` (none is fine).  max_seqlen_q: host bound on the rows of one sequence (1 .. total_q); it alone sizes the
     grid, ``B * H * ceil(max_seqlen_q / 256)`` workgroups, and of a longer sequence only the first max_seqlen_q rows are computed.
@@ -2279,7 +2290,13 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
 
     Attention sinks: ``sinks`` (contiguous fp32 ``[H]`` DEVICE tensor; ``pfa_fa3_prefill_varlen_sink``) exactly as in ``fa3_prefill_cache``,
     with and without ``window``; the result is still bit for bit that of per-sequence ``fa3_prefill_cache(sinks=)`` calls.  An FP8
-    cache takes no sinks (``ValueError``).  ``None``: exactly the calls made without the argument."""
+    cache takes no sinks (``ValueError``).  ``None``: exactly the calls made without the argument.
+
+    Head dim 256 (``pfa_fa3_prefill_varlen_d256``): q ``[total_q, H, 256]`` goes to the head dim 256 kernel of ``fa3_prefill_cache``,
+    ``B * H * ceil(max_seqlen_q / 128)`` workgroups, still bit for bit the per-sequence calls.  ``sinks`` and FP8 caches are not built at
+    this head dim and raise ``ValueError`` naming the argument and "head dim 256" before anything is enqueued."""
+    d256 = _head_dim_256(q, k_cache, v_cache, k_descale, v_descale, _kernel="prefill", _takes="cache_seqlens, causal, window", _rank=3,
+                         sinks=sinks)
     B_cu = cu_seqlens_q.numel() - 1 if isinstance(cu_seqlens_q, torch.Tensor) else 0
     fp8 = _fp8_caches(k_cache, v_cache, k_descale, v_descale)
     quant = _fp8_quant("pfa_fa3_prefill_varlen", "prefill takes cache_seqlens", q, k_cache, v_cache, k_descale, v_descale, B_cu, (
@@ -2318,7 +2335,7 @@ def fa3_prefill_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     _set_cache_seqlens(a, cache_seqlens, q, keep, B)
     lse = _finish_cache_call("pfa_fa3_prefill_varlen", a, ext, q, (H, total_q) if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, quant=quant,
-                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, cu_seqlens_q=cu_seqlens_q,
+                             descales=(k_descale, v_descale) if fp8 else None, sinks=snk, d256=d256, cu_seqlens_q=cu_seqlens_q,
                              max_seqlen_q=int(max_seqlen_q))
     return out, lse
 

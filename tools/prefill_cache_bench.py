@@ -19,6 +19,11 @@ the minimum and maximum in the JSON.  TFLOP/s = 4 D x visible (row, key) pairs x
 same caches (``prefill_win_us``, ``window_over_none``), TFLOP/s over the pairs the window leaves visible.
 
     python tools/prefill_cache_bench.py --window 4096 --shapes "8,32,8,128,2048,30720" --no-paged --no-today
+
+``--head-dim 256`` measures the head dim 256 kernel (``pfa_fa3_prefill_d256``): per (B, chunk, keys) the call at H 16 / Hkv 4 / D 256,
+contiguous and paged, the D 128 call at H 32 / Hkv 8 (the same flops and K/V bytes) and ``scaled_dot_product_attention`` at D 256.
+
+    python tools/prefill_cache_bench.py --head-dim 256 --md profiles/prefill_d256.md [--shapes "B,chunk,Skv;..."]
 """
 
 from __future__ import annotations
@@ -158,8 +163,81 @@ def bench_shape(B, H, Hkv, D, Sq, prefix, reps, dev, paged=True, today=True, win
     return res
 
 
+SDPA_MAX_SCORES = 8 << 30      # bytes of fp32 scores above which the masked sdpa baseline is not run (a mask takes it off the fused path)
+
+
+def bench_head_dim(B, Sq, S, reps, dev, page=256):
+    """A chunk of Sq rows over a cache of S keys (its own included), bf16 causal, timed alternately: D 256 (H 16 / Hkv 4) contiguous and
+    paged, D 128 (H 32 / Hkv 8: the same flops and the same K/V bytes), and ``scaled_dot_product_attention`` at D 256 on the contiguous
+    cache -- ``is_causal`` where the chunk is the whole cache, else the bottom-right mask, built once outside the timed window."""
+    H, Hkv, D = 16, 4, 256
+    cache_bytes = 2 * B * Hkv * S * D * 2
+    n = max(1, math.ceil(MIN_POOL / cache_bytes))
+    pages, prefix = S // page, S - Sq
+    flops = 4.0 * D * (Sq * prefix + Sq * (Sq + 1) // 2) * B * H
+    q = torch.randn(B, Sq, H, D, device=dev, dtype=BF).permute(0, 2, 1, 3)
+    q128 = torch.randn(B, Sq, 2 * H, D // 2, device=dev, dtype=BF).permute(0, 2, 1, 3)
+    sl = torch.full((B,), S, dtype=torch.int32, device=dev)
+    wide = [tuple(torch.randn(B, Hkv, S, D, device=dev, dtype=BF) for _ in range(2)) for _ in range(n)]
+    narrow = [tuple(torch.randn(B, 2 * Hkv, S, D // 2, device=dev, dtype=BF) for _ in range(2)) for _ in range(n)]
+    pools = _pools(B, Hkv, S, D, page, "phsd", n, dev, seed=page)
+    paths = {"d256": lambda i: ops.fa3_prefill_cache(q, wide[i][0], wide[i][1], cache_seqlens=sl),
+             "d256_paged": lambda i: ops.fa3_prefill_cache(q, pools[i][0], pools[i][1], cache_seqlens=sl, block_table=pools[i][2]),
+             "d128": lambda i: ops.fa3_prefill_cache(q128, narrow[i][0], narrow[i][1], cache_seqlens=sl)}
+    res = dict(B=B, H=H, Hkv=Hkv, D=D, chunk=Sq, Skv=S, page=page, cache_MB=round(cache_bytes / 1e6, 1), n_caches=n, reps=reps,
+               gflop=round(flops / 1e9, 2))
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    if prefix == 0:
+        paths["sdpa_d256"] = lambda i: sdpa(q, wide[i][0], wide[i][1], is_causal=True, enable_gqa=True)
+    elif 4 * B * H * Sq * S <= SDPA_MAX_SCORES:
+        mask = torch.arange(S, device=dev)[None, :] <= torch.arange(Sq, device=dev)[:, None] + prefix
+        paths["sdpa_d256"] = lambda i: sdpa(q, wide[i][0], wide[i][1], attn_mask=mask, enable_gqa=True)
+    else:
+        res["sdpa_d256_skipped"] = "scores above the memory bound of the masked path"
+    _stats(res, _timed(paths, n, reps))
+    for name in paths:
+        res[f"{name}_tflops"] = round(flops / res[f"{name}_us"] / 1e6, 1)
+    res["d256_over_d128"] = round(res["d256_us"] / res["d128_us"], 4)
+    res["d256_paged_over_d128"] = round(res["d256_paged_us"] / res["d128_us"], 4)
+    res["d128_spread"] = round(res["d128_us_max"] / res["d128_us_min"], 4)
+    if "sdpa_d256_us" in res:
+        res["sdpa_over_d256"] = round(res["sdpa_d256_us"] / res["d256_us"], 4)
+        res["sdpa_over_d256_paged"] = round(res["sdpa_d256_us"] / res["d256_paged_us"], 4)
+    del wide, narrow, pools
+    torch.cuda.empty_cache()
+    return res
+
+
+def main_head_dim(args, dev):
+    """``--head-dim 256``: the table of profiles/prefill_d256.md, also written there as markdown with ``--md``."""
+    if args.shapes:
+        shapes = [tuple(int(x) for x in s.split(",")) for s in args.shapes.split(";") if s]      # "B,chunk,Skv;..."
+    else:
+        shapes = [(B, c, S) for B in (1, 8) for S in (8192, 32768) for c in (512, 2048, 8192) if c <= S]
+    rows = []
+    head = "| B | chunk | keys | d256 us [min, max] | TF/s | paged us [min, max] | d128 us [min, max] | TF/s | d256 / d128 | paged / d128 | " \
+           "sdpa us [min, max] | sdpa / d256 |"
+    lines = [head, "|" + "---|" * 12]
+    print(head, flush=True)
+    for B, c, S in shapes:
+        r = bench_head_dim(B, c, S, args.reps, dev)
+        rows.append(r)
+        t = lambda name: f"{r[f'{name}_us']:.1f} [{r[f'{name}_us_min']:.1f}, {r[f'{name}_us_max']:.1f}]"      # noqa: E731
+        sd = (t("sdpa_d256"), f"{r['sdpa_over_d256']:.2f}") if "sdpa_d256_us" in r else ("not run", "-")
+        lines.append(f"| {B} | {c} | {S} | {t('d256')} | {r['d256_tflops']:.0f} | {t('d256_paged')} | {t('d128')} | {r['d128_tflops']:.0f} | "
+                     f"{r['d256_over_d128']:.3f} | {r['d256_paged_over_d128']:.3f} | {sd[0]} | {sd[1]} |")
+        print(lines[-1], flush=True)
+    for path, text in ((args.json, "".join(json.dumps(r) + "\n" for r in rows)), (args.md, "\n".join(lines) + "\n")):
+        if path:
+            with open(path, "w") as f:
+                f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--head-dim", type=int, default=128, choices=(128, 256),
+                    help="256: the head dim 256 kernel against the D 128 call of the same flops and bytes and against sdpa; --shapes is then B,chunk,Skv")
+    ap.add_argument("--md", default=None, help="with --head-dim 256: also write the table as markdown (profiles/prefill_d256.md)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="H 32 / Hkv 8, D 128, B 8, chunk 512 only")
     ap.add_argument("--no-paged", action="store_true")
@@ -170,6 +248,8 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "prefill_cache_bench measures on the GPU"
     dev = torch.device("cuda:0")
+    if args.head_dim == 256:
+        return main_head_dim(args, dev)
     if args.shapes:
         shapes = [tuple(int(x) for x in s.split(",")) for s in args.shapes.split(";") if s]
     elif args.quick:
