@@ -516,3 +516,34 @@ def _sink_grad_model(lse, delta, sinks, d_sinks, rows=None) -> None:
     live = (l > float("-inf")) & (s > float("-inf"))
     terms = torch.exp(torch.where(live, s - l.float(), torch.zeros_like(l))) * torch.where(live, d.float(), torch.zeros_like(d))
     d_sinks.copy_(-torch.where(live, terms, torch.zeros_like(terms)).sum(dim=1) + 0.0)
+
+
+def _mla_decode_model(q, kv_cache, lens, causal: bool, scale: float, block_table, out, lse_out) -> None:
+    """``pfa_mla_decode``'s rule in plain fp32 torch ops: the executable specification, and what ``mla_decode`` runs on CPU tensors.
+    q ``[B,H,Sq,576]``; kv_cache ``[B,Smax,576]``, or with ``block_table [B,max_pages]`` a pool ``[num_pages,page_size,576]`` whose ids are
+    clamped into the pool.  Row i of sequence b sees key j iff ``j < len_b`` and (causal) ``j <= len_b - Sq + i``; the row of key j is the
+    key at width 576 and its first 512 columns are the value.  Keys at and past ``len_b`` are never read: they are replaced by zeros
+    before any arithmetic.  A row with no visible key gets O = 0 and LSE = -inf."""
+    B, H, Sq, _ = q.shape
+    neg_inf = float("-inf")
+    for b in range(B):
+        if block_table is None:
+            rows = kv_cache[b]
+        else:
+            rows = kv_cache[block_table[b].long().clamp(0, kv_cache.shape[0] - 1)].reshape(-1, kv_cache.shape[-1])
+        Smax = rows.shape[0]
+        n = min(max(int(lens[b]), 0), Smax)
+        j = torch.arange(Smax, device=q.device)
+        rows = torch.where((j < n)[:, None], rows.to(torch.float32), torch.zeros((), dtype=torch.float32, device=q.device))
+        s = (q[b].to(torch.float32) @ rows.t()) * scale                                    # [H, Sq, Smax]
+        vis = (j < n)[None, :].expand(Sq, Smax)
+        if causal:
+            vis = vis & (j[None, :] <= n - Sq + torch.arange(Sq, device=q.device)[:, None])
+        s = torch.where(vis[None], s, torch.full_like(s, neg_inf))
+        m = s.amax(-1, keepdim=True)
+        p = torch.exp(s - torch.where(m > neg_inf, m, torch.zeros_like(m)))
+        l = p.sum(-1, keepdim=True)
+        o = (p @ rows[:, :out.shape[-1]]) / torch.where(l > 0, l, torch.ones_like(l))
+        out[b].copy_(o)                                                                    # 16-bit: round to nearest even
+        if lse_out is not None:
+            lse_out[b].copy_(torch.where(l > 0, m + torch.log(l), torch.full_like(l, neg_inf))[..., 0])

@@ -21,8 +21,8 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_decode_d256, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
-from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
+from . import _capi, _capi_decode_d256, _capi_mla, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
+from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _mla_decode_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
                       _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
@@ -2058,6 +2058,102 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     lse = _finish_cache_call("pfa_fa3_decode", a, ext, q, (B, H, Sq) if return_lse else None, keep,
                              (k_new, v_new, k_cache, v_cache, cache_seqlens, block_table), rotary, tree=tree, quant=quant,
                              descales=(k_descale, v_descale) if fp8 else None, sinks=snk, d256=d256, max_seqlen_q=Sq)
+    return out, lse
+
+
+def _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_table, out, out_dtype):
+    """``mla_decode``'s validation and marshalling, every refusal a ``ValueError`` before anything is enqueued -> ``(args, out, scale, keep)``:
+    the ``pfa_mla_decode_args`` block without LSE and workspace, the output view, the scale as a float, the tensors the block points into."""
+    DQK, DV = _capi_mla.D_QK, _capi_mla.D_V
+    if not isinstance(q, torch.Tensor) or not isinstance(kv_cache, torch.Tensor) or q.dim() != 4 or kv_cache.dim() != 3:
+        raise ValueError("mla_decode: q must be 4-D ([B,H,Sq,576]) and kv_cache 3-D ([B,Smax,576] or a pool [num_pages,page_size,576])")
+    B, H, Sq, D = q.shape
+    if D != DQK or kv_cache.shape[2] != DQK:
+        raise ValueError(f"mla_decode: the last dim of q and kv_cache must be {DQK} (512 compressed + 64 rotary columns), got {D} and "
+                         f"{kv_cache.shape[2]}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or kv_cache.dtype != q.dtype:
+        raise ValueError("mla_decode: q and kv_cache must share dtype bf16 or fp16")
+    if min(B, H) < 1 or not 1 <= Sq <= 64:
+        raise ValueError(f"mla_decode: q {tuple(q.shape)}: B and H must be >= 1 and Sq in 1 .. 64")
+    scale = None if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)) else float(softmax_scale)
+    if scale is None or not 0.0 < scale < float("inf"):
+        raise ValueError(f"mla_decode: softmax_scale must be a finite positive number, got {softmax_scale!r}")
+    page_size = num_pages = 0
+    if block_table is None:
+        Smax = kv_cache.shape[1]
+        if kv_cache.shape[0] != B or Smax < 1:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} kv_cache {tuple(kv_cache.shape)}")
+    else:
+        num_pages, page_size = kv_cache.shape[0], kv_cache.shape[1]
+        if num_pages < 1 or page_size < 64 or page_size % 64:
+            raise ValueError(f"kv pool {tuple(kv_cache.shape)}: needs a page and a page size that is a multiple of 64 keys")
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.device != q.device:
+            raise ValueError("block_table must be an int32 tensor on the operands' device")
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be [B, max_pages] with B = {B}, got {tuple(block_table.shape)}")
+        if block_table.stride(1) != 1 and block_table.shape[1] != 1:
+            raise ValueError("block_table: the last dim must be contiguous")
+        Smax = block_table.shape[1] * page_size
+    if kv_cache.device != q.device:
+        raise ValueError("mla_decode needs its tensors on one device")
+    if kv_cache.stride(2) != 1 or kv_cache.stride(1) < DQK:
+        raise ValueError("kv_cache: the last dim must be contiguous and the token stride at least 576")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.shape != (B,) or cache_seqlens.device != q.device:
+        raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
+    odt = q.dtype if out_dtype is None else out_dtype
+    if odt not in (q.dtype, torch.float32):
+        raise ValueError("output dtype must be the input dtype or fp32")
+    if out is None:
+        out = torch.empty((B, Sq, H, DV), dtype=odt, device=q.device).permute(0, 2, 1, 3)
+    else:
+        _out_arg(out, (B, H, Sq, DV), odt, q.device)
+    a = _capi_mla.make_mla_decode_args(B=B, H=H, Sq=Sq, Smax=Smax, dtype_in=_DT[q.dtype], dtype_out=_DT[odt], causal=1 if causal else 0,
+                                       softmax_scale=scale, device_id=_device_index(q.device) if q.is_cuda else 0, kv_cache=kv_cache.data_ptr(),
+                                       kv_stride_b=kv_cache.stride(0), kv_stride_s=kv_cache.stride(1))
+    _set_view(a, "q", q)
+    _set_view(a, "o", out)
+    _set_block_table(a, block_table, page_size, num_pages)
+    sl = cache_seqlens if cache_seqlens.dtype == torch.int32 and cache_seqlens.is_contiguous() else cache_seqlens.to(torch.int32).contiguous()
+    a.cache_seqlens = sl.data_ptr()
+    return a, out, scale, [sl]
+
+
+def mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, *, cache_seqlens: torch.Tensor, softmax_scale: float, causal: bool = True,
+               block_table: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+               return_lse: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Multi-head latent attention decode in its absorbed form over a latent KV cache (``pfa_mla_decode``; DeepSeek-V2 / V3 / R1,
+    Kimi K2): every token has one 576-wide latent row that all heads share, the key at width 576 and, in its first 512 columns, the
+    value.
+
+    q: ``[B,H,Sq,576]`` view (bf16 / fp16, last dim contiguous, 1 <= Sq <= 64): columns 0 .. 511 the query already multiplied by W_UK,
+    512 .. 575 the rotated part.  kv_cache: ``[B,Smax,576]`` (token stride >= 576, a multiple of 8; any batch stride), or with
+    ``block_table`` (int32 ``[B,max_pages]``) a pool ``[num_pages,page_size,576]`` with ``page_size`` a multiple of 64 and the table
+    rules of ``fa3_decode``.  ``cache_seqlens`` (int32 ``[B]``) and ``softmax_scale`` are required: ``576 ** -0.5`` is wrong for every
+    model that uses this.  ``causal`` is bottom-right per batch, as in ``fa3_decode``: row i sees key j iff ``j < len_b`` and
+    ``j <= len_b - Sq + i``.  Returns ``(o [B,H,Sq,512] view of a [B,Sq,H,512] buffer, in q's dtype or fp32; lse [B,H,Sq] fp32 or
+    None)``; a row with no visible key gets O = 0 and LSE = -inf; keys at and past ``len_b`` are never read.
+
+    On device tensors one launch of a HIP kernel of its own (16 rows packed over all heads per work item, the cache read once per item),
+    plus the decode's combine launch where the keys are split; grid and workspace from host shapes only, so the call is capturable and a
+    captured call replays while lengths, table and cache change; no atomics, and a paged call returns the bits of the contiguous one.
+    On CPU tensors the same rule runs in plain fp32 torch ops (``_models._mla_decode_model``, the executable specification).  Wrong
+    shapes, head dims or dtypes raise ``ValueError`` before anything is enqueued."""
+    a, out, scale, keep = _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_table, out, out_dtype)
+    B, H, Sq, _ = q.shape
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device) if return_lse else None
+    if q.device.type == "cpu":
+        _mla_decode_model(q, kv_cache, cache_seqlens, bool(causal), scale, block_table, out, lse)
+        return out, lse
+    if q.device.type != "cuda":
+        raise ValueError("mla_decode needs device tensors (or CPU tensors for the torch model)")
+    if lse is not None:
+        a.lse = lse.data_ptr()
+    lib = _capi_mla.load()
+    _attach_workspace(a, lib.pfa_mla_decode_workspace_bytes(C.byref(a)), q.device, keep)
+    stream = torch.cuda.current_stream(q.device)
+    _raise_status("pfa_mla_decode", lib.pfa_mla_decode(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
+    if keep:
+        _hold(keep, stream)
     return out, lse
 
 
