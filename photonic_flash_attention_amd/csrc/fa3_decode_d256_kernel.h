@@ -1,11 +1,11 @@
 // fa3_decode_d256_kernel.h -- split-KV decode attention over a KV cache at head dim 256 for MI355X (gfx950), hand-written HIP.
 //
-// fa3_decode_kernel.h's work split with a tile of its own.  Kept from there (by inclusion; that file is untouched): the work item
-// (batch, K/V head, 16-row block, key split) with rows packed r = i * G + g, split_range with boundaries at multiples of 64 keys,
-// 4 waves with wave w on tiles w, w + 4, ..., DecodeParams and the window part, uniform_srd descriptors whose record count ends at
-// the split's last key, the paged lookup (one wave-uniform table entry per tile, a scalar load one issue ahead, the id clamped into
-// the pool), the fp32 log2-domain online softmax with masks on edge tiles only, and the fp32 partial layout [nsplit][B][H][Sq][D] +
-// (m, l), so that fa3_decode_combine_kernel<256, OT> and the host's plan serve this kernel as they are.
+// fa3_decode_kernel.h's work split with a tile of its own.  Kept from there: the work item (batch, K/V head, 16-row block, key split) with
+// rows packed r = i * G + g, 4 waves with wave w on tiles w, w + 4, ..., the window part, and the fp32 partial layout
+// [nsplit][B][H][Sq][D] + (m, l), so that fa3_decode_combine_kernel<256, OT> and the host's plan serve this kernel as they are.  Shared with
+// it and with fa3_mla_decode_kernel.h, each written once: decode_parts.h (DecodeParams, split_range, uniform_srd, the paged lookup and
+// the clamped per-tile offset, DElem16, the image's row padding), decode_tile16.inc (the score step and the PV product of a 16-key tile)
+// and decode_merge.inc (the waves' merge).
 //
 // The tile.  Geo<256> in that kernel would be a 32-key tile feeding the 16x16x32 MFMA's 32-key k-step in PV: 64 (O^T) + 32 (Q) + 64 (K) +
 // 64 (V) = 224 VGPRs before an address or a score.  Here a wave tile is 16 keys -- 8 KiB of K + 8 KiB of V, the 16 KiB per wave in
@@ -26,38 +26,25 @@
 // heads are run-time.  No tree, no FP8 cache, no sinks.  No atomics: bitwise reproducible, and a paged call returns the bits of the
 // contiguous call on the gathered cache.
 #pragma once
-#include "fa3_decode_kernel.h"
+#include "fa3_decode_kernel.h"     // ... which includes decode_parts.h
 
 namespace pfa {
 namespace dec {
 
-typedef __attribute__((ext_vector_type(4))) short i16x4;
-
-// the x16 MFMA of the PV product: A = V^T (4 keys of one column per lane), B = P^T (4 keys of one row per lane)
-template <typename T> struct DElem16;
-template <> struct DElem16<__bf16> {
-    static __device__ __forceinline__ f32x4 mfma(bf16x4 a, bf16x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(i16x4, a), __builtin_bit_cast(i16x4, b), c, 0, 0, 0);
-    }
-};
-template <> struct DElem16<_Float16> {
-    static __device__ __forceinline__ f32x4 mfma(f16x4 a, f16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-};
-
 struct Geo256 {
     static constexpr int D = 256;
-    static constexpr int KT = 16;                         // keys per wave tile: 8 KiB of K + 8 KiB of V
+    static constexpr int KT = KT16;                       // keys per wave tile: 8 KiB of K + 8 KiB of V
     static constexpr int KS = D / 32;                     // QK^T k-steps
     static constexpr int NDB = D / 16;                    // 16-column blocks of O^T
     static constexpr int KPI = 2;                         // keys per 1-KiB V load instruction
     static constexpr int VLD = KT / KPI;                  // 16-byte V loads per lane per tile
-    static constexpr int VROW = D * 2 + 32;               // LDS bytes per key row of the V image
+    static constexpr int VROW = image_row(D);             // LDS bytes per key row of the V image
     static constexpr int VIMG = KT * VROW;                // per wave
-    static constexpr int HALF = D / 2;                    // columns per merge pass
-    static constexpr int MERGE = NW * ROWS * HALF * 4 + NW * ROWS * 8;
+    static constexpr int PASSES = 2;                      // merge passes
+    static constexpr int PCOLS = D / PASSES;              // columns per merge pass
+    static constexpr int MERGE = NW * ROWS * PCOLS * 4 + NW * ROWS * 8;
     static constexpr int LDS = VIMG * NW > MERGE ? VIMG * NW : MERGE;
 };
-static_assert(SPLIT_ALIGN % Geo256::KT == 0, "a tile must not straddle a split boundary or a page");
 
 template <typename T, typename OT, bool PAGED = false, bool WINDOW = false>
 __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typename DecodeParamsOf<WINDOW>::type p) {
@@ -66,7 +53,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typen
     using v8 = typename E::v8;
     using v4 = typename E::v4;
     using Gm = Geo256;
-    constexpr int D = Gm::D, KT = Gm::KT, KS = Gm::KS, NDB = Gm::NDB, VLD = Gm::VLD, VROW = Gm::VROW, HALF = Gm::HALF;
+    constexpr int D = Gm::D, KT = Gm::KT, KS = Gm::KS, NDB = Gm::NDB, VLD = Gm::VLD, VROW = Gm::VROW, PASSES = Gm::PASSES, PCOLS = Gm::PCOLS, OCOLS = D;
     // fp32 output: P carried as a 16-bit hi + lo pair (two PV MFMAs), as in fa3_decode_kernel
     constexpr bool SPLIT_P = sizeof(OT) == 4;
     __shared__ __attribute__((aligned(16))) char smem[Gm::LDS];
@@ -79,6 +66,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typen
     const int rb = x % p.nrb;
     x /= p.nrb;
     const int kvh = x % p.Hkv, b = x / p.Hkv;
+    const int grp = p.G;                                          // the item's rows are packed r = i * grp + g
     int len = p.seqlens ? min(max(p.seqlens[b], 0), p.Smax) : p.Smax, lo, hi;
     int base = 0;
     if constexpr (WINDOW) base = max(0, len - p.Sq - p.window + 1) & ~(SPLIT_ALIGN - 1);
@@ -96,8 +84,9 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typen
     const int row_lim = p.causal ? len - p.Sq + qi + 1 : len;     // exclusive key bound of this row (before the split's)
     const int min_lim = p.causal ? len - p.Sq + 1 : len;          // every row sees at least the keys below this
     // WINDOW (causal): the row's lowest visible key, and the largest of them among the item's rows (its last row's)
-    int row_lo = 0, max_lo = 0;
+    int row_lo = 0, max_lo = 0, window = 0;
     if constexpr (WINDOW) {
+        window = p.window;
         row_lo = row_lim - p.window;
         const int last = min(rb * ROWS + ROWS - 1, p.Sq * p.G - 1);
         max_lo = __builtin_amdgcn_readfirstlane(len - p.Sq + last / p.G + 1 - p.window);
@@ -133,26 +122,15 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typen
         const uint32_t vtr = (uint32_t)(4 * h + ((lane & 15) >> 2)) * VROW + (uint32_t)(lane & 3) * 8u;
 
         u32x4 kr[KS], vr[VLD];     // the tile in flight, as loaded
-        // paged: the (unclamped) page id of tile t, a wave-uniform scalar load.  Called only for t < ntile, i.e. for keys below
-        // hi <= len_b, so table entries at and past ceil(len_b / page_size) are never read.
+        // paged: the (unclamped) page id of tile t, called only for t < ntile
         const const_i32_ptr table = PAGED ? (const_i32_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
-        auto page_of = [&](int t) { return table[(uint32_t)(lo + t * KT) / (uint32_t)p.page_size]; };
+        auto page_of = [&](int t) { return page_id(table, lo + t * KT, p.page_size); };
         int pg_next = 0;
         if constexpr (PAGED) pg_next = page_of(wave);
         auto issue = [&](int t) {
             const int t0 = lo + t * KT;
             const int nk = min(KT, hi - t0);     // rows past the split's end read as zeros
-            int64_t koff, voff;                  // element offsets of the tile's first key row from kslab / vslab
-            if constexpr (PAGED) {
-                // the tile lies inside one page (page_size % 64 == 0, lo % 64 == 0, 64 % KT == 0)
-                const int pg = min(max(pg_next, 0), p.num_pages - 1);     // device data: never an address outside the pool
-                const int tok = (int)((uint32_t)t0 % (uint32_t)p.page_size);
-                koff = (int64_t)pg * p.k_sb + (int64_t)tok * p.k_ss;
-                voff = (int64_t)pg * p.v_sb + (int64_t)tok * p.v_ss;
-            } else {
-                koff = (int64_t)t0 * p.k_ss;
-                voff = (int64_t)t0 * p.v_ss;
-            }
+            const int64_t koff = tile_offset<PAGED>(p, t0, pg_next, p.k_sb, p.k_ss), voff = tile_offset<PAGED>(p, t0, pg_next, p.v_sb, p.v_ss);
             const srd_t vs = uniform_srd(vslab + voff * 2, (uint32_t)(nk - 1) * vss2 + D * 2);
             const srd_t ks = uniform_srd(kslab + koff * 2, (uint32_t)(nk - 1) * kss2 + D * 2);
 #pragma unroll
@@ -179,96 +157,10 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typen
 
             // scores in log2 units; masks only where the tile reaches past the split, the causal cut, below a row's window, or a key mask exists
             const bool edge = km != nullptr || t0 + KT > hi || t0 + KT > min_lim || (WINDOW && t0 < max_lo);
-            float mx = -__builtin_inff();
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float sc = sacc[e] * p.scale_log2;
-                if (edge) {
-                    const int key = t0 + 4 * h + e;
-                    bool vis;
-                    if constexpr (WINDOW) vis = key < hi && (uint32_t)(key - row_lo) < (uint32_t)p.window;   // row_lo <= key < row_lim
-                    else vis = key < hi && key < row_lim;
-                    if (vis && km) vis = km[key] != 0;
-                    sc = vis ? sc : -__builtin_inff();
-                }
-                sacc[e] = sc;
-                mx = fmaxf(mx, sc);
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m, mx);
-            const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m - m_use);
-            m = m_new;
-            float ps = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float pe = __builtin_amdgcn_exp2f(sacc[e] - m_use);
-                sacc[e] = pe;
-                ps += pe;
-            }
-            l = l * alpha + ps;
-#pragma unroll
-            for (int d = 0; d < NDB; ++d) oacc[d] *= alpha;
-
-            // P^T operand: keys 4h .. 4h + 3 of row c, as the accumulator holds them
-            v4 pf, plo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf[e] = (T)sacc[e];
-                if constexpr (SPLIT_P) plo[e] = (T)(sacc[e] - (float)pf[e]);
-            }
-            asm volatile("" ::: "memory");     // the image writes above stay ahead of the transposed reads below (in-order LDS)
-            // O^T += V^T P^T: the tile's 16 keys are the x16 MFMA's k dimension
-#pragma unroll
-            for (int d = 0; d < NDB; ++d) {
-                const v4 va = E::tr_read(vimg + vtr + d * 32);
-                oacc[d] = E16::mfma(va, pf, oacc[d]);
-                if constexpr (SPLIT_P) oacc[d] = E16::mfma(va, plo, oacc[d]);
-            }
-            asm volatile("" ::: "memory");     // ... and the next tile's image writes behind them
+#include "decode_tile16.inc"
         }
     }
-    // row sum over the row's four lane groups
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-
-    // merge the waves' partials through LDS (the V images are dead after this barrier), 128 columns a pass
-    __syncthreads();
-    float* mo = (float*)smem;                                   // [NW][ROWS][HALF]
-    float* mml = (float*)(smem + NW * ROWS * HALF * 4);         // [NW][ROWS][2]
-    constexpr int TPR = THREADS / ROWS, DPT = HALF / TPR;       // threads per row, head-dim elements per thread and pass
-    const int orow = tid / TPR, d0 = (tid % TPR) * DPT;
-    const int rr = rb * ROWS + orow;
-    const bool live = rr < p.Sq * p.G;                          // (no early return: every thread meets the barriers below)
-    const int oi = live ? rr / p.G : 0, oh = kvh * p.G + (live ? rr % p.G : 0);
-    float M = -__builtin_inff(), L = 0.f, sc[NW];
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if (half) __syncthreads();                              // pass 0's reads are done before the buffer is written again
-#pragma unroll
-        for (int d = 0; d < NDB / 2; ++d) *(f32x4*)(mo + (wave * ROWS + c) * HALF + 16 * d + 4 * h) = oacc[half * (NDB / 2) + d];
-        if (half == 0 && h == 0) {
-            mml[(wave * ROWS + c) * 2] = m;
-            mml[(wave * ROWS + c) * 2 + 1] = l;
-        }
-        __syncthreads();
-        if (half == 0) {
-            float mw[NW];
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                mw[w] = mml[(w * ROWS + orow) * 2];
-                M = fmaxf(M, mw[w]);
-            }
-            const float Mu = M == -__builtin_inff() ? 0.f : M;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                sc[w] = __builtin_amdgcn_exp2f(mw[w] - Mu);
-                L += sc[w] * mml[(w * ROWS + orow) * 2 + 1];
-            }
-        }
-        if (!live) continue;
-        const int col = half * HALF + d0;
+#include "decode_merge.inc"     // ... which leaves its pass loop open, at a live row's thread with the pass's first column `col`
         if (p.nsplit == 1) {
             const float inv = L > 0.f ? 1.f / L : 0.f;
             OT* orow_p = (OT*)p.o + (int64_t)b * p.o_sb + (int64_t)oi * p.o_ss + (int64_t)oh * p.o_sh;
@@ -276,19 +168,19 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_d256_kernel(const typen
             for (int d = 0; d < DPT; d += 4) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * HALF + d0 + d);
+                for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * PCOLS + d0 + d);
                 store4<OT>(orow_p + col + d, acc * inv);
             }
             if (p.lse && col == 0)
                 p.lse[((int64_t)b * p.H + oh) * p.Sq + oi] = L > 0.f ? (M + __log2f(L)) * 0.6931471805599453f : -__builtin_inff();
         } else {
             const int64_t prow = (((int64_t)s * p.B + b) * p.H + oh) * p.Sq + oi;
-            float* po = p.part_o + prow * D;
+            float* po = p.part_o + prow * OCOLS;
 #pragma unroll
             for (int d = 0; d < DPT; d += 4) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * HALF + d0 + d);
+                for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * PCOLS + d0 + d);
                 *(f32x4*)(po + col + d) = acc;
             }
             if (col == 0) {

@@ -70,24 +70,12 @@
 
 #include <type_traits>
 
+#include "decode_parts.h"         // the vector types, DecodeParams, DElem, uniform_srd, store4, split_range
 #include "fp8_cvt.h"               // cvt_e4m3x8: the KV8 conversion, shared with fa3_prefill_kernel.h
 #include "param_parts.h"
 
 namespace pfa {
 namespace dec {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __amdgpu_buffer_rsrc_t srd_t;
-typedef __attribute__((address_space(3))) char lds_char;
-typedef const __attribute__((address_space(4))) int32_t* const_i32_ptr;   // read-only for the kernel's lifetime: scalar loads
-typedef const __attribute__((address_space(4))) float* const_f32_ptr;
 
 #ifndef PFA_DECODE_PAGE_LOOKAHEAD
 #define PFA_DECODE_PAGE_LOOKAHEAD 1
@@ -95,35 +83,6 @@ typedef const __attribute__((address_space(4))) float* const_f32_ptr;
 #ifndef PFA_DECODE_KV8_SETS
 #define PFA_DECODE_KV8_SETS 2      // KV8: tiles in flight per wave (-DPFA_DECODE_KV8_SETS=1: one, 8 KiB, for measurement)
 #endif
-
-constexpr int NW = 4;            // waves per workgroup
-constexpr int ROWS = 16;         // query rows per row block (the MFMA's 16-wide dimension)
-constexpr int SPLIT_ALIGN = 64;  // split boundaries are multiples of this many keys
-constexpr int THREADS = NW * 64;
-
-struct DecodeParams {
-    const void* q;
-    const void* k;
-    const void* v;
-    void* o;
-    float* lse;                  // optional [B, H, Sq]
-    const int32_t* seqlens;      // optional [B]
-    const uint8_t* key_mask;     // optional [B, Smax] bytes, 0 = masked
-    int64_t q_sb, q_sh, q_ss;    // element strides
-    int64_t k_sb, k_sh, k_ss;
-    int64_t v_sb, v_sh, v_ss;
-    int64_t o_sb, o_sh, o_ss;
-    int64_t km_sb;
-    float* part_o;               // nsplit > 1: [nsplit][B][H][Sq][D] fp32, un-normalised
-    float* part_ml;              // nsplit > 1: [nsplit][B][H][Sq][2] fp32 (running max in log2 units, row sum)
-    int32_t B, H, Hkv, G, Sq, Smax, nrb, nsplit;
-    int32_t causal;              // bottom-right: row i sees key j iff j <= len_b - Sq + i
-    float scale_log2;            // softmax_scale * log2(e)
-    // PAGED only: k / v are the pools, k_sb / v_sb the page strides, Smax = max_pages * page_size the logical capacity
-    const int32_t* block_table;  // [B][max_pages] page ids
-    int64_t bt_sb;               // entries between batches
-    int32_t page_size, num_pages;
-};
 
 // The mode flags' parts, behind the base in this order.  WINDOW: the sliding window, 1 <= window <= Smax (the host clamps it)
 struct DecodeWindowPart {
@@ -157,25 +116,6 @@ constexpr bool decode_kernel_exists(bool WINDOW, bool TREE, bool KV8, bool SINK)
            && !(KV8 && (WINDOW || TREE));   // the FP8 cache takes neither a window nor a tree
 }
 
-template <typename T> struct DElem;
-template <> struct DElem<__bf16> {
-    using v8 = bf16x8;
-    using v4 = bf16x4;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ v4 tr_read(const lds_char* p) {
-        return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) v4*)p);
-    }
-};
-template <> struct DElem<_Float16> {
-    using v8 = f16x8;
-    using v4 = f16x4;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ v4 tr_read(const lds_char* p) {
-        typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 h4;
-        return __builtin_bit_cast(v4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)p));
-    }
-};
-
 // Per head dim: keys per wave tile, loads per lane, LDS image geometry.
 template <int D> struct Geo {
     static constexpr int KT = D == 128 ? 32 : 64;        // keys per wave tile: 16 KiB of K + V either way
@@ -192,30 +132,6 @@ template <int D> struct Geo {
     static constexpr int MERGE = NW * ROWS * D * 4 + NW * ROWS * 8;
     static constexpr int LDS = VIMG * NW > MERGE ? VIMG * NW : MERGE;
 };
-
-// raw-buffer descriptor whose inputs are provably wave-uniform
-__device__ __forceinline__ srd_t uniform_srd(const char* base, uint32_t bytes) {
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), 0, (int)__builtin_amdgcn_readfirstlane(bytes),
-                                             0x00020000);
-}
-
-template <typename OT> __device__ __forceinline__ void store4(OT* p, f32x4 x);
-template <> __device__ __forceinline__ void store4<float>(float* p, f32x4 x) { *(f32x4*)p = x; }
-template <> __device__ __forceinline__ void store4<__bf16>(__bf16* p, f32x4 x) { *(bf16x4*)p = bf16x4{(__bf16)x[0], (__bf16)x[1], (__bf16)x[2], (__bf16)x[3]}; }
-template <> __device__ __forceinline__ void store4<_Float16>(_Float16* p, f32x4 x) {
-    *(f16x4*)p = f16x4{(_Float16)x[0], (_Float16)x[1], (_Float16)x[2], (_Float16)x[3]};
-}
-
-// The split of batch b this item covers: [lo, hi) (empty when lo >= hi).  len is the batch's valid key count.  The splits divide
-// [base, len): base = 0, or under a window the 64-key boundary at or below the lowest key row 0 of the batch sees.
-__device__ __forceinline__ void split_range(const DecodeParams& p, int s, int base, int len, int& lo, int& hi) {
-    const int per = (len - base + p.nsplit - 1) / p.nsplit;
-    const int c = (per + SPLIT_ALIGN - 1) / SPLIT_ALIGN * SPLIT_ALIGN;
-    lo = min(base + s * c, len);
-    hi = min(lo + c, len);
-}
 
 template <typename T, int D, typename OT, bool PAGED = false, bool WINDOW = false, bool TREE = false, bool KV8 = false, bool SINK = false>
 __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename DecodeParamsOf<WINDOW, TREE, KV8, SINK>::type p) {
@@ -314,7 +230,7 @@ __global__ __launch_bounds__(THREADS, 2) void fa3_decode_kernel(const typename D
         // paged: the (unclamped) page id of tile t, a wave-uniform scalar load.  Called only for t < ntile, i.e. for keys below
         // hi <= len_b, so table entries at and past ceil(len_b / page_size) are never read.
         const const_i32_ptr table = PAGED ? (const_i32_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
-        auto page_of = [&](int t) { return table[(uint32_t)(lo + t * KT) / (uint32_t)p.page_size]; };
+        auto page_of = [&](int t) { return page_id(table, lo + t * KT, p.page_size); };
         int pg_next = 0;
         if constexpr (PAGED && PFA_DECODE_PAGE_LOOKAHEAD) pg_next = page_of(wave);
         // issue(t): tile t's loads into kr / vr; issue(t, true) (KV8): into the second set

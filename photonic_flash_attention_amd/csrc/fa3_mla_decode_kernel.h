@@ -2,12 +2,11 @@
 // hand-written HIP.  DeepSeek-V2 / V3 / R1, Kimi K2: every token has ONE 576-wide latent row (512 compressed + 64 rotary columns) that all
 // query heads share; the row is the key at width 576 and its first 512 columns are the value.
 //
-// fa3_decode_d256_kernel.h's design at these widths.  Kept from fa3_decode_kernel.h (by inclusion; that file is untouched): DecodeParams
-// (k is the latent cache, v is unused, Hkv = 1 and G = H), split_range with boundaries at multiples of 64 keys, 4 waves with wave w on the
-// 16-key tiles w, w + 4, ..., uniform_srd descriptors whose record count ends at the split's last key, the paged lookup (one wave-uniform
-// table entry per tile, a scalar load one issue ahead, the id clamped into the pool), the fp32 log2-domain online softmax with masks on edge
-// tiles only, and the fp32 partial layout [nsplit][B][H][Sq][512] + (m, l), so that fa3_decode_combine_kernel<512, OT> and the host's plan
-// serve this kernel as they are.
+// fa3_decode_d256_kernel.h's design at these widths: DecodeParams (k is the latent cache, v is unused, Hkv = 1 and G = H), 4 waves with
+// wave w on the 16-key tiles w, w + 4, ..., and the fp32 partial layout [nsplit][B][H][Sq][512] + (m, l), so that
+// fa3_decode_combine_kernel<512, OT> and the host's plan serve this kernel as they are.  What the two kernels share is written once, in
+// decode_parts.h (split_range, uniform_srd, the paged lookup and the clamped per-tile offset, DElem16, the image's row padding),
+// decode_tile16.inc (the score step and the PV product of a 16-key tile) and decode_merge.inc (the waves' merge).
 //
 //   * Work item (b, 16-row block, key split).  There is one "K/V head", so the rows of a block are packed r = i * H + h over all H heads;
 //     the last block is zero-padded and the key limit is per row (a block can span two values of i).
@@ -29,7 +28,7 @@
 // window, sinks, tree or FP8 cache.  No atomics: bitwise reproducible, and a paged call returns the bits of the contiguous call on the
 // gathered cache.
 #pragma once
-#include "fa3_decode_d256_kernel.h"     // DElem16: the x16 MFMA of the PV product
+#include "fa3_decode_kernel.h"     // decode_parts.h, and fa3_decode_combine_kernel for the unit
 
 #ifndef PFA_MLA_SETS
 #define PFA_MLA_SETS 2      // tiles in flight per wave (-DPFA_MLA_SETS=1: one K register set, for measurement)
@@ -41,11 +40,11 @@ namespace dec {
 struct GeoMla {
     static constexpr int DQK = 576;                       // score width: the whole latent row
     static constexpr int DV = 512;                        // value width: its compressed part
-    static constexpr int KT = 16;                         // keys per wave tile: 18 KiB
+    static constexpr int KT = KT16;                       // keys per wave tile: 18 KiB
     static constexpr int KS = DQK / 32;                   // QK^T k-steps = 16-byte loads per lane per tile
     static constexpr int KSV = DV / 32;                   // ... of which the first go into the image
     static constexpr int NDB = DV / 16;                   // 16-column blocks of O^T
-    static constexpr int VROW = DV * 2 + 32;              // LDS bytes per key row of the image
+    static constexpr int VROW = image_row(DV);            // LDS bytes per key row of the image
     static constexpr int VIMG = KT * VROW;                // per wave
     static constexpr int PASSES = 4;                      // merge passes
     static constexpr int PCOLS = DV / PASSES;             // columns per merge pass
@@ -54,7 +53,6 @@ struct GeoMla {
     static constexpr int XCDS = 8;                        // workgroup n runs on XCD n % 8
 };
 static_assert(GeoMla::MERGE <= GeoMla::LDS, "the merge buffer lies under the images");
-static_assert(SPLIT_ALIGN % GeoMla::KT == 0, "a tile must not straddle a split boundary or a page");
 
 // workgroups of the main launch: (b, split) pairs padded to whole groups of XCDS, times the row blocks
 constexpr int64_t mla_grid(int64_t B, int64_t nsplit, int64_t nrb) {
@@ -96,6 +94,12 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_mla_decode_kernel(const Decode
     const int qi = row_ok ? r / p.H : 0, head = row_ok ? r % p.H : 0;
     const int row_lim = p.causal ? len - p.Sq + qi + 1 : len;     // exclusive key bound of this row (before the split's)
     const int min_lim = p.causal ? len - p.Sq + 1 : len;          // every row sees at least the keys below this
+    // decode_tile16.inc's flags: no window, no key mask; decode_merge.inc's: the rows are packed over all H heads of the one K/V head
+    constexpr bool WINDOW = false;
+    constexpr int row_lo = 0, window = 0;
+    const uint8_t* const km = nullptr;
+    constexpr int PASSES = Gm::PASSES, OCOLS = DV, kvh = 0;
+    const int grp = p.H;
 
     f32x4 oacc[NDB];
 #pragma unroll
@@ -123,25 +127,16 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_mla_decode_kernel(const Decode
         const uint32_t vtr = (uint32_t)(4 * h + ((lane & 15) >> 2)) * VROW + (uint32_t)(lane & 3) * 8u;
 
         u32x4 ka[KS], kb[SETS > 1 ? KS : 1];     // the tiles in flight, as loaded: set u holds tiles wave + (2 j + u) NW
-        // paged: the (unclamped) page id of tile t, a wave-uniform scalar load.  Called only for t < ntile, i.e. for keys below
-        // hi <= len_b, so table entries at and past ceil(len_b / page_size) are never read.
+        // paged: the (unclamped) page id of tile t, called only for t < ntile
         const const_i32_ptr table = PAGED ? (const_i32_ptr)(uintptr_t)(p.block_table + (int64_t)b * p.bt_sb) : nullptr;
-        auto page_of = [&](int t) { return table[(uint32_t)(lo + t * KT) / (uint32_t)p.page_size]; };
+        auto page_of = [&](int t) { return page_id(table, lo + t * KT, p.page_size); };
         int pg_next = 0;
         if constexpr (PAGED) pg_next = page_of(wave);
         // issue(t, kr): tile t's loads into the set kr.  Tiles are issued in the order t, t + NW, ..., so pg_next is tile t's entry
         auto issue = [&](int t, u32x4(&kr)[KS]) __attribute__((always_inline)) {
             const int t0 = lo + t * KT;
             const int nk = min(KT, hi - t0);     // rows past the split's end read as zeros
-            int64_t koff;                        // element offset of the tile's first key row from slab
-            if constexpr (PAGED) {
-                // the tile lies inside one page (page_size % 64 == 0, lo % 64 == 0, 64 % KT == 0)
-                const int pg = min(max(pg_next, 0), p.num_pages - 1);     // device data: never an address outside the pool
-                const int tok = (int)((uint32_t)t0 % (uint32_t)p.page_size);
-                koff = (int64_t)pg * p.k_sb + (int64_t)tok * p.k_ss;
-            } else {
-                koff = (int64_t)t0 * p.k_ss;
-            }
+            const int64_t koff = tile_offset<PAGED>(p, t0, pg_next, p.k_sb, p.k_ss);     // from slab, in elements
             const srd_t ks = uniform_srd(slab + koff * 2, (uint32_t)(nk - 1) * ss2 + Gm::DQK * 2);
 #pragma unroll
             for (int q = 0; q < KS; ++q) kr[q] = __builtin_amdgcn_raw_buffer_load_b128(ks, (int)(koff0 + q * 64), 0, 0);
@@ -163,50 +158,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_mla_decode_kernel(const Decode
 
             // scores in log2 units; masks only where the tile reaches past the split or the causal cut
             const bool edge = t0 + KT > hi || t0 + KT > min_lim;
-            float mx = -__builtin_inff();
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float sc = sacc[e] * p.scale_log2;
-                if (edge) {
-                    const int key = t0 + 4 * h + e;
-                    sc = key < hi && key < row_lim ? sc : -__builtin_inff();
-                }
-                sacc[e] = sc;
-                mx = fmaxf(mx, sc);
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m, mx);
-            const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m - m_use);
-            m = m_new;
-            float ps = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float pe = __builtin_amdgcn_exp2f(sacc[e] - m_use);
-                sacc[e] = pe;
-                ps += pe;
-            }
-            l = l * alpha + ps;
-#pragma unroll
-            for (int d = 0; d < NDB; ++d) oacc[d] *= alpha;
-
-            // P^T operand: keys 4h .. 4h + 3 of row c, as the accumulator holds them
-            v4 pf, plo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf[e] = (T)sacc[e];
-                if constexpr (SPLIT_P) plo[e] = (T)(sacc[e] - (float)pf[e]);
-            }
-            asm volatile("" ::: "memory");     // the image writes above stay ahead of the transposed reads below (in-order LDS)
-            // O^T += V^T P^T: the tile's 16 keys are the x16 MFMA's k dimension
-#pragma unroll
-            for (int d = 0; d < NDB; ++d) {
-                const v4 va = E::tr_read(vimg + vtr + d * 32);
-                oacc[d] = E16::mfma(va, pf, oacc[d]);
-                if constexpr (SPLIT_P) oacc[d] = E16::mfma(va, plo, oacc[d]);
-            }
-            asm volatile("" ::: "memory");     // ... and the next tile's image writes behind them
+#include "decode_tile16.inc"
         };
 
         issue(wave, ka);
@@ -220,47 +172,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_mla_decode_kernel(const Decode
             for (int t = wave; t < ntile; t += NW) tile(t, ka);
         }
     }
-    // row sum over the row's four lane groups
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-
-    // merge the waves' partials through LDS (the images are dead after this barrier), 128 columns a pass
-    __syncthreads();
-    float* mo = (float*)smem;                                   // [NW][ROWS][PCOLS]
-    float* mml = (float*)(smem + NW * ROWS * PCOLS * 4);        // [NW][ROWS][2]
-    constexpr int TPR = THREADS / ROWS, DPT = PCOLS / TPR;      // threads per row, columns per thread and pass
-    const int orow = tid / TPR, d0 = (tid % TPR) * DPT;
-    const int rr = rb * ROWS + orow;
-    const bool live = rr < p.Sq * p.H;                          // (no early return: every thread meets the barriers below)
-    const int oi = live ? rr / p.H : 0, oh = live ? rr % p.H : 0;
-    float M = -__builtin_inff(), L = 0.f, sc[NW];
-#pragma unroll
-    for (int pass = 0; pass < Gm::PASSES; ++pass) {
-        if (pass) __syncthreads();                              // the pass before's reads are done before the buffer is written again
-#pragma unroll
-        for (int d = 0; d < NDB / Gm::PASSES; ++d)
-            *(f32x4*)(mo + (wave * ROWS + c) * PCOLS + 16 * d + 4 * h) = oacc[pass * (NDB / Gm::PASSES) + d];
-        if (pass == 0 && h == 0) {
-            mml[(wave * ROWS + c) * 2] = m;
-            mml[(wave * ROWS + c) * 2 + 1] = l;
-        }
-        __syncthreads();
-        if (pass == 0) {
-            float mw[NW];
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                mw[w] = mml[(w * ROWS + orow) * 2];
-                M = fmaxf(M, mw[w]);
-            }
-            const float Mu = M == -__builtin_inff() ? 0.f : M;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                sc[w] = __builtin_amdgcn_exp2f(mw[w] - Mu);
-                L += sc[w] * mml[(w * ROWS + orow) * 2 + 1];
-            }
-        }
-        if (!live) continue;
-        const int col = pass * PCOLS + d0;
+#include "decode_merge.inc"     // ... which leaves its pass loop open, at a live row's thread with the pass's first column `col`
         const float inv = L > 0.f ? 1.f / L : 0.f;
         const int64_t prow = (((int64_t)s * p.B + b) * p.H + oh) * p.Sq + oi;
 #pragma unroll
@@ -269,7 +181,7 @@ __global__ __launch_bounds__(THREADS, 1) void fa3_mla_decode_kernel(const Decode
 #pragma unroll
             for (int w = 0; w < NW; ++w) acc += sc[w] * *(const f32x4*)(mo + (w * ROWS + orow) * PCOLS + d0 + d);
             if (p.nsplit == 1) store4<OT>((OT*)p.o + (int64_t)b * p.o_sb + (int64_t)oi * p.o_ss + (int64_t)oh * p.o_sh + col + d, acc * inv);
-            else *(f32x4*)(p.part_o + prow * DV + col + d) = acc;
+            else *(f32x4*)(p.part_o + prow * OCOLS + col + d) = acc;
         }
         if (col != 0) continue;
         if (p.nsplit == 1) {

@@ -21,13 +21,6 @@ pfa::KernelFn<Params<WINDOW>> kernel_d256(int dtype, bool out32, bool paged) {
         return &pfa::dec::fa3_decode_d256_kernel<T, pfa::out_t<o32.value, T>, pg.value, WINDOW>;
     }, dtype == PFA_DTYPE_BF16, out32, paged);
 }
-// ... and the shared combine kernel, which is generic in D
-pfa::KernelFn<pfa::dec::DecodeParams> combine_d256(int dtype, bool out32) {
-    return pfa::dispatch_bools([](auto bf, auto o32) -> pfa::KernelFn<pfa::dec::DecodeParams> {
-        using T = std::conditional_t<bf.value, __bf16, _Float16>;
-        return &pfa::dec::fa3_decode_combine_kernel<256, pfa::out_t<o32.value, T>>;
-    }, dtype == PFA_DTYPE_BF16, out32);
-}
 
 }  // namespace
 
@@ -55,13 +48,8 @@ int pfa_fa3_decode_d256(const pfa_fa3_decode_args* a, const pfa_fa3_cache_ext* e
         pfa::fill_modes<W, false, false, false, false>(p, m);
         const bool out32 = a->dtype_out == PFA_DTYPE_FP32;
         const auto fn = kernel_d256<W>(a->dtype_in, out32, a->block_table != nullptr);
-        const auto cfn = combine_d256(a->dtype_in, out32);
-        const pfa::DeviceScope dev(a->device_id);
-        if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-        const int st_main = pfa::launch(fn, dim3((unsigned)pl.items), pfa::dec::THREADS, p, 0, stream);
-        if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
-        const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
-        return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+        const auto cfn = combine_at<256>(a->dtype_in, out32);
+        return launch_with_combine(fn, cfn, p, a, pl, pl.items, 0, stream);
     }, m.window != 0);
 }
 

@@ -60,14 +60,16 @@ KernelFn<Params<WINDOW, TREE, KV8, SINK>> kernel(int dtype, int D, bool out32, b
         }, out32, paged);
     });
 }
-// ... and the kernel that joins the splits: it reads the DecodeParams every mode's block begins with
-inline KernelFn<dec::DecodeParams> combine(int dtype, int D, bool out32) {
-    return dispatch_elem_dim(dtype, D, [&](auto t) {
-        using T = typename decltype(t)::type;
-        return dispatch_bools([](auto o32) -> KernelFn<dec::DecodeParams> { return &dec::fa3_decode_combine_kernel<decltype(t)::D, out_t<o32.value, T>>; },
-                              out32);
-    });
+// ... and the kernel that joins the splits: it reads the DecodeParams every mode's block begins with.  combine_at: at the head dim a unit
+// fixes (256, MLA's 512)
+template <int D>
+KernelFn<dec::DecodeParams> combine_at(int dtype, bool out32) {
+    return dispatch_bools([](auto bf, auto o32) -> KernelFn<dec::DecodeParams> {
+        using T = std::conditional_t<bf.value, __bf16, _Float16>;
+        return &dec::fa3_decode_combine_kernel<D, out_t<o32.value, T>>;
+    }, dtype == PFA_DTYPE_BF16, out32);
 }
+inline KernelFn<dec::DecodeParams> combine(int dtype, int D, bool out32) { return D == 128 ? combine_at<128>(dtype, out32) : combine_at<64>(dtype, out32); }
 
 // What every mode's block holds of checked arguments and their plan; the mode's own members are fill_modes'.
 // The workspace of a split call is the partial O [nsplit][B][H][Sq][D] and behind it the partial (m, l) pairs, both fp32.
@@ -104,6 +106,17 @@ struct Blocks {
     const pfa_fa3_sinks* sinks = nullptr;
 };
 
+// The end of every decode call's check, the MLA decode's included: `grid` workgroups of the main kernel and the combine's grid fit a launch,
+// and a plan that splits has its workspace
+inline int check_launch(const pfa_fa3_decode_args* a, const Plan& pl, int64_t grid) {
+    if (grid > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (a->D / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
+    if (pl.ws_bytes) {
+        if (!a->workspace || a->workspace_bytes < pl.ws_bytes) return PFA_ERR_NULL;
+        if (!aligned16(a->workspace)) return PFA_ERR_ALIGN;
+    }
+    return PFA_OK;
+}
+
 // Every decode call's check -> PFA_OK, the modes in *m and their plan in *pl.  KV8: the unit over an FP8 cache, whose quant block is
 // not optional.  DIMS: the head dims the unit's kernels exist for (pfa_host.h; the head dim 256 unit names its own).  The split count and
 // the workspace never depend on tree, quant or sinks, so a captured graph replays while they change.
@@ -119,11 +132,8 @@ int check(const pfa_fa3_decode_args* a, const Blocks& b, CacheModes* m, Plan* pl
     st = check_tree(b.tree, a, m->window, true);
     if (st != PFA_OK) return st;
     *pl = plan(a, m->window);
-    if (pl->items > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (a->D / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
-    if (pl->ws_bytes) {
-        if (!a->workspace || a->workspace_bytes < pl->ws_bytes) return PFA_ERR_NULL;
-        if (!aligned16(a->workspace)) return PFA_ERR_ALIGN;
-    }
+    st = check_launch(a, *pl, pl->items);
+    if (st != PFA_OK) return st;
     m->tree = b.tree; m->quant = b.quant; m->sinks = b.sinks;
     return PFA_OK;
 }
@@ -160,6 +170,19 @@ int describe(const pfa_fa3_decode_args* a, const Blocks& b, char* buf, size_t n,
     return (int)pl.items;
 }
 
+// Every decode unit's launch: the main kernel over `grid` workgroups with `lds` bytes of dynamic LDS on `stream` and, where the plan splits,
+// the combine at a->D behind it (one thread per 4 columns of a row), on a's device
+template <typename P>
+int launch_with_combine(KernelFn<P> fn, KernelFn<dec::DecodeParams> cfn, const P& p, const pfa_fa3_decode_args* a, const Plan& pl, int64_t grid,
+                        size_t lds, void* stream) {
+    const DeviceScope dev(a->device_id);
+    if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
+    const int st_main = pfa::launch(fn, dim3((unsigned)grid), dec::THREADS, p, lds, stream);
+    if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
+    const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
+    return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+}
+
 // of arguments that pass: the block of the call's mode set, the main kernel on `stream` and, where the plan splits, the combine behind it.
 // The run-time modes become the kernel's flags here; a set the unit does not name (ON, MAY) instantiates nothing.
 template <unsigned ON, unsigned MAY = 0>
@@ -179,12 +202,7 @@ int run(const pfa_fa3_decode_args* a, const Blocks& b, void* stream) {
             const bool out32 = a->dtype_out == PFA_DTYPE_FP32;
             const auto fn = kernel<W, T, K8, SK>(a->dtype_in, a->D, out32, a->block_table != nullptr);
             const auto cfn = combine(a->dtype_in, a->D, out32);
-            const DeviceScope dev(a->device_id);
-            if (hip_failed(dev.error())) return PFA_ERR_DEVICE;
-            const int st_main = pfa::launch(fn, dim3((unsigned)pl.items), dec::THREADS, p, 0, stream);
-            if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
-            const int64_t threads = (int64_t)a->B * a->H * a->Sq * (a->D / 4);
-            return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+            return launch_with_combine(fn, cfn, p, a, pl, pl.items, 0, stream);
         }
     }, m.window != 0, m.tree != nullptr, m.quant != nullptr, m.sinks != nullptr);
 }

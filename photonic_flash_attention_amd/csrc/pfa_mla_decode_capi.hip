@@ -22,14 +22,6 @@ pfa::KernelFn<DecodeParams> kernel_mla(int dtype, bool out32, bool paged) {
         return &pfa::dec::fa3_mla_decode_kernel<T, pfa::out_t<o32.value, T>, pg.value>;
     }, dtype == PFA_DTYPE_BF16, out32, paged);
 }
-// ... and the shared combine kernel, which is generic in D
-pfa::KernelFn<DecodeParams> combine_mla(int dtype, bool out32) {
-    return pfa::dispatch_bools([](auto bf, auto o32) -> pfa::KernelFn<DecodeParams> {
-        using T = std::conditional_t<bf.value, __bf16, _Float16>;
-        return &pfa::dec::fa3_decode_combine_kernel<GeoMla::DV, pfa::out_t<o32.value, T>>;
-    }, dtype == PFA_DTYPE_BF16, out32);
-}
-
 // the shape rules a plan can be made from (the workspace query stops here: it takes no pointers and no strides)
 int check_shape(const pfa_mla_decode_args* a) {
     if (!a) return PFA_ERR_NULL;
@@ -77,12 +69,7 @@ int check(const pfa_mla_decode_args* a, pfa_fa3_decode_args* d, Plan* pl, int64_
     *d = as_decode(a);
     *pl = plan(d, 0);
     *grid = pfa::dec::mla_grid(a->B, pl->nsplit, pl->nrb);
-    if (*grid > 0x7fffffffLL || (int64_t)a->B * a->H * a->Sq * (GeoMla::DV / 4) / 256 + 1 > 0x7fffffffLL) return PFA_ERR_SHAPE;
-    if (pl->ws_bytes) {
-        if (!a->workspace || a->workspace_bytes < pl->ws_bytes) return PFA_ERR_NULL;
-        if (!pfa::aligned16(a->workspace)) return PFA_ERR_ALIGN;
-    }
-    return PFA_OK;
+    return check_launch(d, *pl, *grid);
 }
 
 }  // namespace
@@ -125,13 +112,8 @@ int pfa_mla_decode(const pfa_mla_decode_args* a, void* stream) {
     fill_params(p, &d, pl);
     const bool out32 = a->dtype_out == PFA_DTYPE_FP32;
     const auto fn = kernel_mla(a->dtype_in, out32, a->block_table != nullptr);
-    const auto cfn = combine_mla(a->dtype_in, out32);
-    const pfa::DeviceScope dev(a->device_id);
-    if (pfa::hip_failed(dev.error())) return PFA_ERR_DEVICE;
-    const int st_main = pfa::launch(fn, dim3((unsigned)grid), pfa::dec::THREADS, p, GeoMla::LDS, stream);
-    if (st_main != PFA_OK || pl.nsplit <= 1) return st_main;
-    const int64_t threads = (int64_t)a->B * a->H * a->Sq * (GeoMla::DV / 4);
-    return pfa::launch(cfn, dim3((unsigned)((threads + 255) / 256)), 256, p, 0, stream);
+    const auto cfn = combine_at<GeoMla::DV>(a->dtype_in, out32);
+    return launch_with_combine(fn, cfn, p, &d, pl, grid, GeoMla::LDS, stream);
 }
 
 }  // extern "C"

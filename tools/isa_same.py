@@ -3,10 +3,12 @@
 kernel descriptor directives of two -save-temps device assemblies (`make asm ASM_SRC=...` leaves one in /tmp/pfa_asm; keep the one of
 the commit to compare against under another name).
 
-    python tools/isa_same.py OLD.s NEW.s
+    python tools/isa_same.py [--accept-renamed] OLD.s NEW.s
 
 Prints one line per kernel of OLD: `same` (instruction for instruction, same register counts, LDS, scratch and kernarg size),
-`DIFFERENT` with the first differing line, or `missing`; then the kernels only NEW has.  Exit status 1 if any differs or is missing.
+`renamed` (not the same text, but equal descriptor directives, equal instruction count and an equal multiset of opcodes: the registers
+are assigned or the instructions ordered otherwise), `DIFFERENT`, or `missing`; `renamed` and `DIFFERENT` come with the first differing
+line.  Then the kernels only NEW has.  Exit status 1 unless every kernel is `same`; with --accept-renamed, `renamed` passes too.
 Comments, debug labels and the order of functions in the file (with it the function index in `.LBB<function>_<block>` labels) are
 ignored; nothing else is.  A kernel of OLD is matched with the kernel of
 NEW that has its name and its template arguments, followed by nothing or by trailing `false` (`Lb0E`) / `void` arguments only: a template
@@ -36,8 +38,15 @@ def template_args(mangled):
     return mangled if at < 0 else mangled[:at]
 
 
+def opcodes(ins):
+    """The sorted opcodes of the instruction lines (labels and directives, which carry no opcode, stay as they are)."""
+    return sorted(ln.split()[0] for ln in ins)
+
+
 def main():
-    old, new = functions(sys.argv[1]), functions(sys.argv[2])
+    argv = [a for a in sys.argv[1:] if a != "--accept-renamed"]
+    accept_renamed = len(argv) != len(sys.argv) - 1
+    old, new = functions(argv[0]), functions(argv[1])
     sigs = {n: template_args(n) for n in new}
     bad, used = 0, set()
     for old_name, (ins, desc) in old.items():
@@ -52,14 +61,15 @@ def main():
         if ins == ins2 and desc == desc2:
             print(f"same       {name}  ({len(ins)} lines)")
             continue
-        bad += 1
+        renamed = desc == desc2 and len(ins) == len(ins2) and opcodes(ins) == opcodes(ins2)
+        bad += not (renamed and accept_renamed)
         a, b = (ins, ins2) if ins != ins2 else (desc, desc2)
         at = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
-        print(f"DIFFERENT  {name}: line {at}: {a[at] if at < len(a) else '<end>'!r} / {b[at] if at < len(b) else '<end>'!r}")
+        print(f"{'renamed  ' if renamed else 'DIFFERENT'}  {name}: line {at}: {a[at] if at < len(a) else '<end>'!r} / {b[at] if at < len(b) else '<end>'!r}")
     for name in new:
         if name not in used:
             print(f"new        {name}")
-    print(f"{len(old) - bad} of {len(old)} kernels unchanged")
+    print(f"{len(old) - bad} of {len(old)} kernels {'unchanged or renamed' if accept_renamed else 'unchanged'}")
     return 1 if bad else 0
 
 
