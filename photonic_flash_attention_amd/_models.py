@@ -547,3 +547,29 @@ def _mla_decode_model(q, kv_cache, lens, causal: bool, scale: float, block_table
         out[b].copy_(o)                                                                    # 16-bit: round to nearest even
         if lse_out is not None:
             lse_out[b].copy_(torch.where(l > 0, m + torch.log(l), torch.full_like(l, neg_inf))[..., 0])
+
+
+def _mla_prefill_model(q, k_nope, k_rope, v, out, lse_out, cu_q, cu_k, max_seqlen_q: int, max_seqlen_k: int, causal: bool, scale: float) -> None:
+    """``pfa_mla_prefill``'s rule in plain fp32 torch ops: the executable specification, and what ``mla_prefill`` runs on CPU tensors.
+    q ``[total_q,H,192]``, k_nope / v ``[total_k,H,128]``, k_rope ``[total_k,1 or H,64]``; cu_q / cu_k host lists read as ``_packed_seqs``
+    reads them.  Row i of a sequence with Lq rows and Lk keys sees key j iff ``j < Lk`` and (causal, bottom-right) ``j <= i + Lk - Lq``;
+    its score is ``scale * (<q[:128], k_nope> + <q[128:], k_rope>)``.  A row with no visible key gets O = 0 and LSE = -inf; rows no
+    sequence covers are not written."""
+    H = q.shape[1]
+    neg_inf = float("-inf")
+    for sq, nq, sk, nk in _packed_seqs(cu_q, cu_k, q.shape[0], k_nope.shape[0], max_seqlen_q, max_seqlen_k):
+        if nq == 0:
+            continue
+        qb = q[sq:sq + nq].to(torch.float32).transpose(0, 1)                                # [H, Lq, 192]
+        kb = torch.cat([k_nope[sk:sk + nk], k_rope[sk:sk + nk].expand(nk, H, k_rope.shape[2])], dim=-1).to(torch.float32).transpose(0, 1)
+        s = (qb @ kb.transpose(1, 2)) * scale                                               # [H, Lq, Lk]
+        if causal:
+            vis = torch.arange(nk, device=q.device)[None, :] <= torch.arange(nq, device=q.device)[:, None] + (nk - nq)
+            s = torch.where(vis[None], s, torch.full_like(s, neg_inf))
+        m = s.amax(-1, keepdim=True) if nk else torch.full((H, nq, 1), neg_inf, device=q.device)
+        p = torch.exp(s - torch.where(m > neg_inf, m, torch.zeros_like(m)))
+        l = p.sum(-1, keepdim=True)
+        o = (p @ v[sk:sk + nk].to(torch.float32).transpose(0, 1)) / torch.where(l > 0, l, torch.ones_like(l))
+        out[sq:sq + nq].copy_(o.transpose(0, 1))                                            # 16-bit: round to nearest even
+        if lse_out is not None:
+            lse_out[:, sq:sq + nq].copy_(torch.where(l > 0, m + torch.log(l), torch.full_like(l, neg_inf))[..., 0])

@@ -21,8 +21,8 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_decode_d256, _capi_mla, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
-from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _mla_decode_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
+from . import _capi, _capi_decode_d256, _capi_mla, _capi_mla_prefill, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
+from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _mla_decode_model, _mla_prefill_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
                       _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
@@ -2154,6 +2154,108 @@ def mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, *, cache_seqlens: torch.
     _raise_status("pfa_mla_decode", lib.pfa_mla_decode(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
     if keep:
         _hold(keep, stream)
+    return out, lse
+
+
+def _mla_prefill_call_args(q, k_nope, k_rope, v, k, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale, causal, out, out_dtype):
+    """``mla_prefill``'s validation and marshalling, every refusal a ``ValueError`` before anything is enqueued -> ``(args, out, scale,
+    (k_nope, k_rope), max_seqlen_q, max_seqlen_k)``: the ``pfa_mla_prefill_args`` block without LSE, the output, the scale as a float, the
+    two key parts (the column views of ``k`` where that was given) and the two bounds as host ints."""
+    DN, DR, DV, DQK = _capi_mla_prefill.D_NOPE, _capi_mla_prefill.D_ROPE, _capi_mla_prefill.D_V, _capi_mla_prefill.D_QK
+    if k is not None:
+        if k_nope is not None or k_rope is not None:
+            raise ValueError("mla_prefill: give k (width 192) or k_nope and k_rope, not both")
+        if not isinstance(k, torch.Tensor) or k.dim() != 3 or k.shape[2] != DQK:
+            raise ValueError(f"mla_prefill: k must be [total_k, H, {DQK}] (128 nope + 64 rotary columns)")
+        k_nope, k_rope = k[:, :, :DN], k[:, :, DN:]
+    if not all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in (q, k_nope, k_rope, v)):
+        raise ValueError("mla_prefill: q must be [total_q, H, 192], k_nope and v [total_k, H, 128], k_rope [total_k, 1 or H, 64]")
+    total_q, H, _ = q.shape
+    total_k = k_nope.shape[0]
+    if q.shape[2] != DQK or k_nope.shape[2] != DN or k_rope.shape[2] != DR or v.shape[2] != DV:
+        raise ValueError(f"mla_prefill: the last dims of q, k_nope, k_rope, v must be {DQK}, {DN}, {DR}, {DV}, got {q.shape[2]}, "
+                         f"{k_nope.shape[2]}, {k_rope.shape[2]}, {v.shape[2]}")
+    if H < 1 or k_nope.shape != (total_k, H, DN) or v.shape != (total_k, H, DV) or k_rope.shape[0] != total_k or k_rope.shape[1] not in (1, H):
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} k_nope {tuple(k_nope.shape)} k_rope {tuple(k_rope.shape)} v {tuple(v.shape)} "
+                         "(no grouped heads: k_nope and v have q's heads, k_rope one head or q's)")
+    if q.dtype not in (torch.bfloat16, torch.float16) or any(t.dtype != q.dtype for t in (k_nope, k_rope, v)):
+        raise ValueError("mla_prefill: q, k_nope, k_rope, v must share dtype bf16 or fp16")
+    scale = None if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)) else float(softmax_scale)
+    if scale is None or not 0.0 < scale < float("inf"):
+        raise ValueError(f"mla_prefill: softmax_scale must be a finite positive number, got {softmax_scale!r}")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor")
+        if cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [B + 1] tensor, got {tuple(cu.shape)}")
+    if cu_seqlens_k.numel() != cu_seqlens_q.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must both be [B + 1]")
+    if any(t.device != q.device for t in (k_nope, k_rope, v, cu_seqlens_q, cu_seqlens_k)):
+        raise ValueError("mla_prefill needs all its tensors on one device")
+    max_q, max_k = _host_int(max_seqlen_q), _host_int(max_seqlen_k)      # host ints: max_seqlen_q sizes the grid
+    if total_q < 1 or total_k < 1 or max_q is None or max_k is None or not 1 <= max_q <= total_q or not 1 <= max_k <= total_k:
+        raise ValueError(f"max_seqlen_q {max_seqlen_q!r} / max_seqlen_k {max_seqlen_k!r}: must be host ints in 1 .. {total_q} / 1 .. {total_k}, "
+                         "the rows held")
+    for name, t, width in (("q", q, DQK), ("k_nope", k_nope, DN), ("k_rope", k_rope, DR), ("v", v, DV)):
+        if t.stride(2) != 1 or t.stride(0) < width or t.stride(0) % 8 or (t.shape[1] > 1 and t.stride(1) % 8) or t.data_ptr() % 16:
+            raise ValueError(f"{name}: needs a contiguous last dim, a row stride of at least {width}, row and head strides that are multiples "
+                             "of 8 elements and a 16-byte aligned base")
+    odt = q.dtype if out_dtype is None else out_dtype
+    if odt not in (q.dtype, torch.float32):
+        raise ValueError("output dtype must be the input dtype or fp32")
+    if out is None:
+        out = torch.empty((total_q, H, DV), dtype=odt, device=q.device)
+    elif not isinstance(out, torch.Tensor) or out.shape != (total_q, H, DV) or out.dtype != odt or out.device != q.device or out.stride(2) != 1:
+        raise ValueError(f"out must be a [total_q, H, {DV}] tensor of the output dtype on the operands' device, last dim contiguous")
+    a = _capi_mla_prefill.make_mla_prefill_args(
+        q=q.data_ptr(), k_nope=k_nope.data_ptr(), k_rope=k_rope.data_ptr(), v=v.data_ptr(), o=out.data_ptr(),
+        cu_seqlens_q=cu_seqlens_q.data_ptr(), cu_seqlens_k=cu_seqlens_k.data_ptr(), B=cu_seqlens_q.numel() - 1, H=H, rope_heads=k_rope.shape[1],
+        total_q=total_q, total_k=total_k, max_seqlen_q=max_q, max_seqlen_k=max_k, dtype_in=_DT[q.dtype], dtype_out=_DT[odt],
+        causal=1 if causal else 0, softmax_scale=scale, device_id=_device_index(q.device) if q.is_cuda else 0)
+    for pre, t in (("q", q), ("kn", k_nope), ("kr", k_rope), ("v", v), ("o", out)):
+        setattr(a, f"{pre}_stride_s", t.stride(0))
+        setattr(a, f"{pre}_stride_h", t.stride(1))
+    return a, out, scale, (k_nope, k_rope), max_q, max_k
+
+
+def mla_prefill(q: torch.Tensor, k_nope: Optional[torch.Tensor] = None, k_rope: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                *, k: Optional[torch.Tensor] = None, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int, max_seqlen_k: int,
+                softmax_scale: float, causal: bool = True, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+                return_lse: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Multi-head latent attention prefill in its non-absorbed form over packed sequences (``pfa_mla_prefill``; the prompt of
+    DeepSeek-V2 / V3 / R1 and Kimi K2): every head scores with a 192-wide q.k -- 128 "nope" columns of its own and 64 rotary columns whose
+    key part all heads may share -- and sums 128-wide values.
+
+    q: ``[total_q, H, 192]``, k_nope and v: ``[total_k, H, 128]`` (in practice two column ranges of one ``[total_k, H, 256]`` projection
+    output), k_rope: ``[total_k, 1 or H, 64]``; bf16 / fp16, last dim contiguous, row and head strides multiples of 8 elements.  ``k=`` of
+    width 192 stands for ``k_nope`` and ``k_rope``: it is passed on as its two column views and returns the same bits.  The layout is
+    ``flash_attn_varlen_func``'s: int32 ``[B + 1]`` DEVICE tensors cu_seqlens_q / cu_seqlens_k, sequence b owning the packed rows and keys
+    ``cu[b] .. cu[b + 1] - 1``; max_seqlen_q / max_seqlen_k HOST ints (1 .. total) that bound one sequence -- max_seqlen_q alone sizes the
+    grid -- and device values out of range are clamped by the kernel.  ``softmax_scale`` is required: no default is right for these
+    models.  ``causal`` is bottom-right per sequence, as in every serving call here: row i sees key j iff ``j <= i + (Lk_b - Lq_b)``.
+
+    Returns ``(o [total_q, H, 128] in q's dtype or fp32, lse [H, total_q] fp32 natural log or None)`` -- the LSE in the layout
+    ``fa3_prefill_varlen`` returns, so a causal call over new tokens and a full call over an up-projected context chunk go straight into
+    ``attn_merge``.  A row with no visible key (Lk_b = 0, or the first Lq_b - Lk_b rows of a causal sequence with Lk_b < Lq_b) gets
+    O = 0 and LSE = -inf; rows no sequence covers are never written.
+
+    On device tensors one launch of a HIP kernel of its own (256 rows per workgroup, the key in two LDS images); no workspace, no
+    atomics, the same bits every run and per sequence those of a call that holds it alone; capturable, and a captured call replays while
+    both cu_seqlens and the operands change.  On CPU tensors the same rule runs in plain fp32 torch ops
+    (``_models._mla_prefill_model``, the executable specification).  Wrong shapes or dtypes raise ``ValueError`` before anything is
+    enqueued."""
+    a, out, scale, (k_nope, k_rope), max_q, max_k = _mla_prefill_call_args(q, k_nope, k_rope, v, k, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                                                           max_seqlen_k, softmax_scale, causal, out, out_dtype)
+    lse = torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=q.device) if return_lse else None
+    if q.device.type == "cpu":
+        _mla_prefill_model(q, k_nope, k_rope, v, out, lse, cu_seqlens_q.tolist(), cu_seqlens_k.tolist(), max_q, max_k, bool(causal), scale)
+        return out, lse
+    if q.device.type != "cuda":
+        raise ValueError("mla_prefill needs device tensors (or CPU tensors for the torch model)")
+    if lse is not None:
+        a.lse = lse.data_ptr()
+    stream = torch.cuda.current_stream(q.device)
+    _raise_status("pfa_mla_prefill", _capi_mla_prefill.load().pfa_mla_prefill(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
     return out, lse
 
 
