@@ -549,6 +549,40 @@ def _mla_decode_model(q, kv_cache, lens, causal: bool, scale: float, block_table
             lse_out[b].copy_(torch.where(l > 0, m + torch.log(l), torch.full_like(l, neg_inf))[..., 0])
 
 
+def _mla_decode_q8_model(q, kv_cache, kv_descale, lens, causal: bool, scale: float, block_table, out, lse_out) -> None:
+    """``pfa_mla_decode_q8``'s rule in plain torch: the FP8 latent cache (e4m3fn bytes, fp32 ``kv_descale`` ``[B]`` or ``[1]``) dequantised
+    in fp32, sequence by sequence -- a paged sequence's pages gathered by its clamped ids first -- then ``_mla_decode_model``."""
+    for b in range(q.shape[0]):
+        if block_table is None:
+            rows = kv_cache[b]
+        else:
+            rows = kv_cache[block_table[b].long().clamp(0, kv_cache.shape[0] - 1)].reshape(-1, kv_cache.shape[-1])
+        rows = rows.to(torch.float32) * kv_descale[b if kv_descale.numel() > 1 else 0]
+        _mla_decode_model(q[b:b + 1], rows[None], lens[b:b + 1], causal, scale, None, out[b:b + 1], None if lse_out is None else lse_out[b:b + 1])
+
+
+def _mla_append_model(kv_c, k_pe, kv_cache, kv_descale, lens, cu, max_seqlen_q, block_table) -> None:
+    """``pfa_mla_append``'s rule in plain torch: the executable specification, and what ``mla_append`` runs on CPU tensors.  The new latent
+    row is ``kv_c`` (512 columns) followed by ``k_pe`` (64); into an FP8 cache every element goes as ``quantize_kv`` stores it, with its
+    sequence's ``kv_descale`` (``[B]`` or ``[1]``); the placement, every clamp and drop included, is ``_kv_append_model``'s with the row as
+    the one K/V head.  ``lens`` / ``cu`` are host lists; the sources are ``[total, .]`` with ``cu``, else ``[B, Sq, .]``."""
+    rows, cache = torch.cat([kv_c, k_pe], dim=-1), kv_cache
+    if kv_cache.dtype == FP8:
+        d = kv_descale.expand(len(lens))
+        if cu is None:
+            d = d[:, None, None]
+        else:                                                 # packed rows: each row takes its sequence's scale
+            seq = torch.zeros(rows.shape[0], dtype=torch.int64)
+            for b in range(len(lens)):
+                s_b = min(max(cu[b], 0), rows.shape[0])
+                seq[s_b:min(max(cu[b + 1], s_b), rows.shape[0])] = b
+            d = d[seq][:, None]
+        rows = (rows.to(torch.float32) / d).clamp(-FP8_MAX, FP8_MAX).to(FP8).view(torch.uint8)
+        cache = kv_cache.view(torch.uint8)
+    new = rows[:, None]                                       # [B, 1, Sq, 576], or packed [total, 1, 576]
+    _kv_append_model(new, new, cache[:, None], cache[:, None], lens, cu, max_seqlen_q, block_table)
+
+
 def _mla_prefill_model(q, k_nope, k_rope, v, out, lse_out, cu_q, cu_k, max_seqlen_q: int, max_seqlen_k: int, causal: bool, scale: float) -> None:
     """``pfa_mla_prefill``'s rule in plain fp32 torch ops: the executable specification, and what ``mla_prefill`` runs on CPU tensors.
     q ``[total_q,H,192]``, k_nope / v ``[total_k,H,128]``, k_rope ``[total_k,1 or H,64]``; cu_q / cu_k host lists read as ``_packed_seqs``

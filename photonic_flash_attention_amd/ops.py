@@ -21,8 +21,8 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _capi, _capi_decode_d256, _capi_mla, _capi_mla_prefill, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
-from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _mla_decode_model, _mla_prefill_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
+from . import _capi, _capi_decode_d256, _capi_mla, _capi_mla_cache, _capi_mla_prefill, _capi_norm_rope_append, _capi_prefill_d256, _capi_qk_norm, _capi_rotary, _capi_sinks, _models
+from ._models import (FP8, FP8_MAX, _attn_merge_model, _kv_append_model, _kv_append_q8_model, _mla_append_model, _mla_decode_model, _mla_decode_q8_model, _mla_prefill_model, _packed_seqs, _norm_rope_append_model, _page_copy_model,      # noqa: F401
                       _qk_norm_bwd_model, _qk_norm_model, _rope_append_model, _rope_rotate, _rotary_model, _sink_grad_model, _varlen_backward_model, _varlen_forward_model, dequantize_kv, quantize_kv)
 
 _DT = {torch.bfloat16: _capi.PFA_DTYPE_BF16, torch.float16: _capi.PFA_DTYPE_FP16, torch.float32: _capi.PFA_DTYPE_FP32}
@@ -2061,9 +2061,10 @@ def fa3_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *,
     return out, lse
 
 
-def _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_table, out, out_dtype):
+def _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_table, out, out_dtype, fp8=False):
     """``mla_decode``'s validation and marshalling, every refusal a ``ValueError`` before anything is enqueued -> ``(args, out, scale, keep)``:
-    the ``pfa_mla_decode_args`` block without LSE and workspace, the output view, the scale as a float, the tensors the block points into."""
+    the ``pfa_mla_decode_args`` block without LSE and workspace, the output view, the scale as a float, the tensors the block points into.
+    ``fp8``: kv_cache holds ``torch.float8_e4m3fn`` bytes (``pfa_mla_decode_q8``; the descale is ``_mla_kv_quant_arg``'s)."""
     DQK, DV = _capi_mla.D_QK, _capi_mla.D_V
     if not isinstance(q, torch.Tensor) or not isinstance(kv_cache, torch.Tensor) or q.dim() != 4 or kv_cache.dim() != 3:
         raise ValueError("mla_decode: q must be 4-D ([B,H,Sq,576]) and kv_cache 3-D ([B,Smax,576] or a pool [num_pages,page_size,576])")
@@ -2071,8 +2072,8 @@ def _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_tabl
     if D != DQK or kv_cache.shape[2] != DQK:
         raise ValueError(f"mla_decode: the last dim of q and kv_cache must be {DQK} (512 compressed + 64 rotary columns), got {D} and "
                          f"{kv_cache.shape[2]}")
-    if q.dtype not in (torch.bfloat16, torch.float16) or kv_cache.dtype != q.dtype:
-        raise ValueError("mla_decode: q and kv_cache must share dtype bf16 or fp16")
+    if q.dtype not in (torch.bfloat16, torch.float16) or kv_cache.dtype != (FP8 if fp8 else q.dtype):
+        raise ValueError("mla_decode: q and kv_cache must share dtype bf16 or fp16 (or kv_cache be torch.float8_e4m3fn with kv_descale=)")
     if min(B, H) < 1 or not 1 <= Sq <= 64:
         raise ValueError(f"mla_decode: q {tuple(q.shape)}: B and H must be >= 1 and Sq in 1 .. 64")
     scale = None if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)) else float(softmax_scale)
@@ -2098,6 +2099,8 @@ def _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_tabl
         raise ValueError("mla_decode needs its tensors on one device")
     if kv_cache.stride(2) != 1 or kv_cache.stride(1) < DQK:
         raise ValueError("kv_cache: the last dim must be contiguous and the token stride at least 576")
+    if fp8 and (kv_cache.stride(0) % 16 or kv_cache.stride(1) % 16):
+        raise ValueError("kv_cache: the strides of a torch.float8_e4m3fn cache must be a multiple of 16")
     if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.shape != (B,) or cache_seqlens.device != q.device:
         raise ValueError("cache_seqlens must be a [B] tensor on the operands' device")
     odt = q.dtype if out_dtype is None else out_dtype
@@ -2118,9 +2121,27 @@ def _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_tabl
     return a, out, scale, [sl]
 
 
+def _mla_kv_quant_arg(entry: str, kv_cache, kv_descale, B: int, device):
+    """The ``pfa_mla_kv_quant`` block of a call over a latent cache, or None for a 16-bit cache.  A ``torch.float8_e4m3fn`` cache needs
+    ``kv_descale`` (fp32, contiguous, ``[B]`` or ``[1]``, on ``device``); a 16-bit cache refuses it.  The block points into the caller's
+    tensor, so a captured call sees its contents change."""
+    if kv_cache.dtype != FP8:
+        if kv_descale is not None:
+            raise ValueError(f"{entry}: kv_descale goes with a torch.float8_e4m3fn kv_cache only")
+        return None
+    if kv_descale is None:
+        raise ValueError(f"{entry}: a torch.float8_e4m3fn kv_cache needs kv_descale (fp32 [B] or [1])")
+    if not isinstance(kv_descale, torch.Tensor) or kv_descale.dtype != torch.float32 or kv_descale.shape not in ((B,), (1,)) \
+            or not kv_descale.is_contiguous():
+        raise ValueError(f"{entry}: kv_descale must be a contiguous fp32 tensor [B] = [{B}] or [1]")
+    if kv_descale.device != device:
+        raise ValueError(f"{entry}: kv_descale must live on the operands' device")
+    return _capi_mla_cache.make_mla_kv_quant(kv_descale=kv_descale.data_ptr(), descale_stride_b=1 if kv_descale.numel() > 1 else 0)
+
+
 def mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, *, cache_seqlens: torch.Tensor, softmax_scale: float, causal: bool = True,
                block_table: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
-               return_lse: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+               return_lse: bool = False, kv_descale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Multi-head latent attention decode in its absorbed form over a latent KV cache (``pfa_mla_decode``; DeepSeek-V2 / V3 / R1,
     Kimi K2): every token has one 576-wide latent row that all heads share, the key at width 576 and, in its first 512 columns, the
     value.
@@ -2137,24 +2158,139 @@ def mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, *, cache_seqlens: torch.
     plus the decode's combine launch where the keys are split; grid and workspace from host shapes only, so the call is capturable and a
     captured call replays while lengths, table and cache change; no atomics, and a paged call returns the bits of the contiguous one.
     On CPU tensors the same rule runs in plain fp32 torch ops (``_models._mla_decode_model``, the executable specification).  Wrong
-    shapes, head dims or dtypes raise ``ValueError`` before anything is enqueued."""
-    a, out, scale, keep = _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_table, out, out_dtype)
+    shapes, head dims or dtypes raise ``ValueError`` before anything is enqueued.
+
+    FP8 cache: a kv_cache of ``torch.float8_e4m3fn`` (strides multiples of 16) with ``kv_descale=`` (contiguous fp32 ``[B]`` or ``[1]`` on
+    the tensors' device; required then, refused otherwise) runs ``pfa_mla_decode_q8``: a cache element stands for ``e4m3(byte) *
+    kv_descale[b]``, one scale for the row that is key and value at once (``mla_append`` writes such a cache; ``quantize_kv`` /
+    ``dequantize_kv`` on the ``[B,1,S,576]`` view with a ``[B,1]`` descale are the rule in plain torch).  q stays bf16 / fp16 and the
+    conversion of a byte is exact; splits, grid and workspace are the 16-bit call's, and with descales that are powers of two so are the
+    bits, against the 16-bit call on the dequantised cache.  A captured call sees the descales change."""
+    fp8 = isinstance(kv_cache, torch.Tensor) and kv_cache.dtype == FP8
+    a, out, scale, keep = _mla_call_args(q, kv_cache, cache_seqlens, softmax_scale, causal, block_table, out, out_dtype, fp8)
     B, H, Sq, _ = q.shape
+    quant = _mla_kv_quant_arg("mla_decode", kv_cache, kv_descale, B, q.device)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device) if return_lse else None
     if q.device.type == "cpu":
-        _mla_decode_model(q, kv_cache, cache_seqlens, bool(causal), scale, block_table, out, lse)
+        if fp8:
+            _mla_decode_q8_model(q, kv_cache, kv_descale, cache_seqlens, bool(causal), scale, block_table, out, lse)
+        else:
+            _mla_decode_model(q, kv_cache, cache_seqlens, bool(causal), scale, block_table, out, lse)
         return out, lse
     if q.device.type != "cuda":
         raise ValueError("mla_decode needs device tensors (or CPU tensors for the torch model)")
     if lse is not None:
         a.lse = lse.data_ptr()
-    lib = _capi_mla.load()
-    _attach_workspace(a, lib.pfa_mla_decode_workspace_bytes(C.byref(a)), q.device, keep)
     stream = torch.cuda.current_stream(q.device)
-    _raise_status("pfa_mla_decode", lib.pfa_mla_decode(C.byref(a), C.c_void_p(stream.cuda_stream)), null_too=True)
+    if fp8:
+        lib = _capi_mla_cache.load()
+        _attach_workspace(a, lib.pfa_mla_decode_q8_workspace_bytes(C.byref(a), C.byref(quant)), q.device, keep)
+        st = lib.pfa_mla_decode_q8(C.byref(a), C.byref(quant), C.c_void_p(stream.cuda_stream))
+    else:
+        lib = _capi_mla.load()
+        _attach_workspace(a, lib.pfa_mla_decode_workspace_bytes(C.byref(a)), q.device, keep)
+        st = lib.pfa_mla_decode(C.byref(a), C.c_void_p(stream.cuda_stream))
+    _raise_status("pfa_mla_decode_q8" if fp8 else "pfa_mla_decode", st, null_too=True)
     if keep:
         _hold(keep, stream)
     return out, lse
+
+
+def mla_append(kv_c: torch.Tensor, k_pe: torch.Tensor, kv_cache: torch.Tensor, *, cache_seqlens: torch.Tensor,
+               cu_seqlens_q: Optional[torch.Tensor] = None, max_seqlen_q: Optional[int] = None,
+               block_table: Optional[torch.Tensor] = None, kv_descale: Optional[torch.Tensor] = None) -> None:
+    """Device-side append to the latent KV cache of ``mla_decode`` (``pfa_mla_append``; vLLM's ``concat_and_cache_mla``): a step's new
+    latent rows, given as their two parts, into the 576-wide cache, from device data alone.
+
+    kv_c: the normalised compressed latent, ``[B,Sq,512]``, or with ``cu_seqlens_q`` (int32 ``[B + 1]``) the packed ``[total,512]`` rows and
+    ``max_seqlen_q`` the host bound on one sequence's rows; k_pe: the rotated part, ``[B,Sq,64]`` / ``[total,64]``.  bf16 / fp16, rows by any
+    strides that are multiples of 8 (k_pe is usually a column slice of the ``kv_a`` projection's output), last dim contiguous.  kv_cache
+    (and ``block_table``) exactly as ``mla_decode`` takes them.  The placement rule is ``kv_append``'s, word for word: cache_seqlens
+    (int32 ``[B]``, required) are the lengths AFTER the step; with len_b = clamp(cache_seqlens[b], 0, Smax) and Sq_b the sequence's rows,
+    row i goes to key ``len_b - Sq_b + i``; rows in front of key 0 are dropped, and so is a row whose page id lies outside the pool (a
+    write is never clamped into someone else's page); nothing but the destination rows is written.
+
+    A 16-bit cache (kv_c's dtype) gets a copy.  A ``torch.float8_e4m3fn`` cache with ``kv_descale=`` (contiguous fp32 ``[B]`` or ``[1]``;
+    required then, refused otherwise) gets every element x as ``e4m3fn(clamp(float(x) / kv_descale[b], -448, 448))``: an fp32 division,
+    round to nearest even, NaN stays NaN -- ``quantize_kv``'s rule.
+
+    On device tensors: one launch of a HIP kernel whose grid depends on host shapes only -- capturable in ``torch.cuda.graph`` and valid
+    while cu_seqlens_q, lengths, table, cache and descales change between replays.  On CPU tensors the same rule runs in plain torch
+    (``_models._mla_append_model``, the executable specification).  Every refusal is a ``ValueError`` before anything is enqueued."""
+    DQK, DV = _capi_mla.D_QK, _capi_mla.D_V
+    if not all(isinstance(t, torch.Tensor) for t in (kv_c, k_pe, kv_cache)):
+        raise ValueError("mla_append: kv_c, k_pe, kv_cache must be tensors")
+    ragged = cu_seqlens_q is not None
+    if kv_c.dim() != (2 if ragged else 3) or k_pe.dim() != kv_c.dim() or kv_cache.dim() != 3:
+        raise ValueError("mla_append: kv_c / k_pe must be 2-D ([total,512] / [total,64]) with cu_seqlens_q, else 3-D ([B,Sq,512] / [B,Sq,64]); "
+                         "kv_cache 3-D ([B,Smax,576] or a pool [num_pages,page_size,576])")
+    if kv_c.shape[-1] != DV or k_pe.shape[-1] != DQK - DV or kv_cache.shape[-1] != DQK or k_pe.shape[:-1] != kv_c.shape[:-1]:
+        raise ValueError(f"shape mismatch: kv_c {tuple(kv_c.shape)} k_pe {tuple(k_pe.shape)} kv_cache {tuple(kv_cache.shape)} "
+                         f"(last dims 512, 64 and 576)")
+    if kv_c.dtype not in (torch.bfloat16, torch.float16) or k_pe.dtype != kv_c.dtype or kv_cache.dtype not in (kv_c.dtype, FP8):
+        raise ValueError("mla_append: kv_c and k_pe must share dtype bf16 or fp16, kv_cache have it or be torch.float8_e4m3fn")
+    fp8 = kv_cache.dtype == FP8
+    if ragged:
+        B, total = _cu_seqlens_arg(cu_seqlens_q), kv_c.shape[0]
+        if max_seqlen_q is None:
+            raise ValueError("cu_seqlens_q needs max_seqlen_q, the host bound on a sequence's rows (it sizes the grid)")
+    else:
+        B, Sq = kv_c.shape[:2]
+        if max_seqlen_q is not None and int(max_seqlen_q) != Sq:
+            raise ValueError(f"max_seqlen_q {max_seqlen_q}: without cu_seqlens_q every sequence brings kv_c's {Sq} rows")
+        max_seqlen_q, total = Sq, B * Sq
+    max_seqlen_q = int(max_seqlen_q)
+    if B < 1 or total < 1 or not 1 <= max_seqlen_q <= total:
+        raise ValueError(f"max_seqlen_q {max_seqlen_q}: must lie in 1 .. {total}, the rows kv_c holds")
+    page_size = num_pages = 0
+    if block_table is None:
+        Smax = kv_cache.shape[1]
+        if kv_cache.shape[0] != B or Smax < 1:
+            raise ValueError(f"shape mismatch: kv_c {tuple(kv_c.shape)} kv_cache {tuple(kv_cache.shape)}")
+    else:
+        num_pages, page_size = kv_cache.shape[0], kv_cache.shape[1]
+        if num_pages < 1 or page_size < 64 or page_size % 64:
+            raise ValueError(f"kv pool {tuple(kv_cache.shape)}: needs a page and a page size that is a multiple of 64 keys")
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+            raise ValueError("block_table must be an int32 tensor")
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be [B, max_pages] with B = {B}, got {tuple(block_table.shape)}")
+        if block_table.stride(1) != 1 and block_table.shape[1] != 1:
+            raise ValueError("block_table: the last dim must be contiguous")
+        Smax = block_table.shape[1] * page_size
+    if any(t.stride(-1) != 1 for t in (kv_c, k_pe, kv_cache)) or kv_cache.stride(1) < DQK:
+        raise ValueError("mla_append: last dims must be contiguous and the cache's token stride at least 576")
+    piece = 16 if fp8 else 8
+    if any(st % 8 for t in (kv_c, k_pe) for st in t.stride()[:-1]) or kv_cache.stride(0) % piece or kv_cache.stride(1) % piece:
+        raise ValueError(f"mla_append: the row strides of kv_c and k_pe must be multiples of 8, those of this kv_cache a multiple of {piece}")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.shape != (B,):
+        raise ValueError("cache_seqlens must be a [B] tensor (the lengths after the step)")
+    dev = kv_c.device
+    if any(t.device != dev for t in (k_pe, kv_cache, cache_seqlens) + ((cu_seqlens_q,) if ragged else ())
+           + ((block_table,) if block_table is not None else ())):
+        raise ValueError("mla_append needs all its tensors on one device")
+    quant = _mla_kv_quant_arg("mla_append", kv_cache, kv_descale, B, dev)
+    if dev.type == "cpu":
+        _mla_append_model(kv_c, k_pe, kv_cache, kv_descale, cache_seqlens.tolist(), cu_seqlens_q.tolist() if ragged else None, max_seqlen_q,
+                          block_table)
+        return
+    if dev.type != "cuda":
+        raise ValueError("mla_append needs device tensors (or CPU tensors for the torch model)")
+    a = _capi_mla_cache.make_mla_append_args(
+        B=B, Smax=Smax, total_new=total, max_seqlen_q=max_seqlen_q, dtype=_DT[kv_c.dtype], device_id=_device_index(dev),
+        kv_c=kv_c.data_ptr(), k_pe=k_pe.data_ptr(), kv_cache=kv_cache.data_ptr(), kv_stride_b=kv_cache.stride(0), kv_stride_s=kv_cache.stride(1),
+        kvc_stride_b=0 if ragged else kv_c.stride(0), kvc_stride_s=kv_c.stride(-2), kpe_stride_b=0 if ragged else k_pe.stride(0),
+        kpe_stride_s=k_pe.stride(-2))
+    if ragged:
+        a.cu_seqlens_q = cu_seqlens_q.data_ptr()
+    _set_block_table(a, block_table, page_size, num_pages)
+    keep = []
+    _set_cache_seqlens(a, cache_seqlens, kv_c, keep, B)
+    stream = torch.cuda.current_stream(dev)
+    st = _capi_mla_cache.load().pfa_mla_append(C.byref(a), None if quant is None else C.byref(quant), C.c_void_p(stream.cuda_stream))
+    _raise_status("pfa_mla_append", st, null_too=True)
+    if keep:
+        _hold(keep, stream)
 
 
 def _mla_prefill_call_args(q, k_nope, k_rope, v, k, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale, causal, out, out_dtype):
